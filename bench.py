@@ -11,13 +11,19 @@ RANSAC -> [host: match graph, camera initialisation] -> spherical inverse warp +
 Images are generated on the GPU (seeded, procedural) and are resident in HBM before the timed region.
 With N > 1 the SAME 64-image job is sharded over the ranks (strong scaling, see parallel.py).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps and prints
+ONE JSON line from rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+`--dump-outputs DIR` also writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
+
+With `--full` the line also carries everything else the bench measures, in legs and passes of their own:
   "roofline"     : the dominant kernel (the int8-MFMA screening pass of the descriptor matcher) against its MFMA
                    roofline, timed with HIP events on the stream the kernel runs on (aps_profile_*);
   "value_end_to_end": the same steps with the images starting in pinned host memory (uploads overlapped with SIFT);
   "value_resident": the same steps without the final device-to-host copy of the panorama;
   "cpu_baseline" : the CPU oracle (oracle/, kind "port") timed on a bounded 2x2-view sample of the same
-                   workload on this box's host cores (rank 0, N = 1 only).
+                   workload on this box's host cores (rank 0, N = 1 only);
+and the sequential and gain-compensated series, the per-kernel and per-stage tables, the GPU clock/power sample and the
+matcher / SIFT probes.  The --cpu-baseline / --end-to-end / --global-probe / --with-gain switches select among those legs.
 """
 from __future__ import annotations
 
@@ -98,6 +104,12 @@ def parse():
     ap.add_argument("--gain-compensation", action="store_true",
                     help="also run gainCompensationRKf (device overlap statistics + host solve) before the render; "
                          "off in the headline configuration, which follows BASELINE.json configs[2]")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the extra legs (sequential, gain, end-to-end series, CPU baseline, matcher and SIFT "
+                         "probes), kernel timing, rooflines, stage tables and the GPU clock/power sample (off: the headline only)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, "
+                         "a fixed sample of the panorama; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -385,6 +397,59 @@ def cpu_sample(synth, input_, w, h, f, overlap, finest, bands, mode, seed, n_vie
                                       "how": f"{n_views}/4 x SIFT + {n_pairs}/6 x match + {n_cand}/6 x RANSAC + {ratio:.1f} x render of the sample"}}
 
 
+DUMP_SAMPLE_PX = 1 << 21       # panorama pixels drawn for panorama_sample (x 3 channels x 4 B: 24 MiB at most)
+DUMP_BLOCK_BYTES = 24 << 20    # panorama_block_mean stays below this (the block side doubles from 16 until it does)
+
+
+def save_pano(path, pano):
+    """--save-pano: a downscaled PNG of the panorama (debug)."""
+    from PIL import Image
+
+    small = pano[:: max(1, pano.shape[0] // 1200), :: max(1, pano.shape[0] // 1200)].cpu().numpy()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    Image.fromarray(small).save(path)
+
+
+def dump_outputs(out_dir, pano, info):
+    """--dump-outputs: what the last timed step handed its caller (stitch_distributed's panorama and info), as out_dir/<name>.npy
+    in float32 / float64, under 64 MB in all.  The cropped uint8 panorama (737 MB for the headline job) is written as the mean of
+    every b x b block (every pixel enters one; sums of uint8 are exact, so the means are too) and as the exact values at a fixed,
+    seeded sample of pixels (panorama_sample_index: flat row-major indices); beside them its shape, the feature count of every
+    view, the verified pairs with their homographies, the component's members and every view's camera (NaN: no camera)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"n_features": np.asarray(info["n_features"], np.float64),
+              "pairs": np.asarray(info["pairs"], np.float64).reshape(-1, 2),
+              "models": np.asarray(info["models"], np.float64).reshape(-1, 3, 3),
+              "members": np.asarray(info["members"], np.float64)}
+    cams = info["cameras"]
+    for key in ("K", "R"):
+        arrays["cameras_" + key] = np.stack([np.asarray(c[key], np.float64) if c is not None else np.full((3, 3), np.nan)
+                                             for c in cams]) if cams else np.zeros((0, 3, 3))
+    shape = tuple(int(v) for v in pano.shape) if pano is not None else (0, 0, 3)
+    arrays["panorama_shape"] = np.asarray(shape, np.float64)
+    h_, w_ = shape[0], shape[1]
+    if h_ and w_:
+        b = 16
+        while (h_ // b) * (w_ // b) * 3 * 4 > DUMP_BLOCK_BYTES:
+            b *= 2
+        hb, wb = h_ // b, w_ // b
+        if hb and wb:
+            sums = pano[: hb * b, : wb * b].to(torch.int32).reshape(hb, b, wb, b, 3).sum(dim=(1, 3))
+            arrays["panorama_block_mean"] = (sums.cpu().numpy().astype(np.float64) / (b * b)).astype(np.float32)
+            arrays["panorama_block_side"] = np.asarray([b], np.float64)
+        idx = np.unique(np.random.default_rng(20240601).integers(0, h_ * w_, size=min(DUMP_SAMPLE_PX, h_ * w_)))
+        rows = torch.from_numpy(idx // w_).to(pano.device)
+        cols = torch.from_numpy(idx % w_).to(pano.device)
+        arrays["panorama_sample"] = pano[rows, cols].cpu().numpy().astype(np.float32)
+        arrays["panorama_sample_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64_000_000:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, over the 64 MB limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def run_config(args):
     """`bench.py --config N`: BASELINE.json configs[N] (N != 2) on ONE GPU - the same contract as the headline line (W warm-up
     steps, K timed steps between device synchronisations, inputs resident in HBM, ONE JSON line with roofline / cpu_baseline /
@@ -659,7 +724,12 @@ def main():
         if args.gpus != 1:
             print("bench.py: --config N runs on one GPU (the headline, configs[2], is the line that scales)", file=sys.stderr)
             sys.exit(2)
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs writes the headline run's outputs; it does not apply to --config N", file=sys.stderr)
+            sys.exit(2)
         sys.exit(run_config(args))
+    if not args.full:  # a plain run: the headline figure only, none of the extra legs
+        args.cpu_baseline = args.end_to_end = args.global_probe = args.with_gain = "off"
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a five-line version banner to stdout
     # when a communicator comes up): everything but the result line is sent to stderr by pointing fd 1 at fd 2 for the
     # run; the result is written to the saved descriptor at the end.
@@ -874,7 +944,7 @@ def main():
     warm_prof, warm_steps = {}, 0
     pano_w = None
     for k in range(args.warmup):
-        last = k == args.warmup - 1
+        last = k == args.warmup - 1 and args.full
         if last:
             capi.profile_enable(1)
             capi.profile_reset()
@@ -891,13 +961,17 @@ def main():
         # malloc'ed - and its pages scrubbed - inside the second TIMED step (+12-18 ms there in every run's series).  The second
         # of the two is also the step the GPU's clock and power are sampled in.
         step()
-        sampler = GpuStateSampler(local_rank)
-        sampler.start()
+        sampler = GpuStateSampler(local_rank) if args.full else None
+        if sampler is not None:
+            sampler.start()
         t_s0 = time.perf_counter()
         _, info_s = step()
         barrier()
-        sampler.stop()
-        if sampler.files and rank == 0:
+        if sampler is not None:
+            sampler.stop()
+        if sampler is None or rank != 0:
+            pass
+        elif sampler.files:
             tm = info_s["times"]
             t_f = t_s0 + tm.get("features", 0.0) + tm.get("exchange", 0.0)
             t_m = t_f + tm.get("matching", 0.0)
@@ -905,13 +979,14 @@ def main():
                          "features": sampler.window(t_s0 + 0.1 * (t_f - t_s0), t_f - 0.1 * (t_f - t_s0)),
                          "matching_screen": sampler.window(t_f + 0.05 * (t_m - t_f), t_f + 0.75 * (t_m - t_f)),
                          "render": sampler.window(t_s0 + info_s["t_stitch"] - tm.get("render", 0.0), t_s0 + info_s["t_stitch"])}
-        elif rank == 0:
+        else:
             gpu_state = {"source": None, "note": "no readable amdgpu hwmon files for this rank's GPU"}
     # the un-overlapped cost of one panorama copy (both pinned buffers exist by now): three synchronous copies of a
-    # canvas-sized device buffer, the fastest counts
+    # canvas-sized device buffer, the fastest counts (--full).  A plain run allocates and frees the buffer all the same: the
+    # block it leaves in torch's cache is one the pipelined timed steps would otherwise malloc (+20 ms in a timed step).
     if rank == 0 and args.warmup > 0 and pano_w is not None and pano_w.numel():
         probe = torch.empty(tuple(pano_w.shape), dtype=torch.uint8, device="cuda")
-        for _ in range(3):
+        for _ in range(3 if args.full else 0):
             torch.cuda.synchronize()
             t_c = time.perf_counter()
             to_host(probe, wait=True)
@@ -935,19 +1010,24 @@ def main():
         barrier()
         return time.perf_counter() - t_b, infos_, marks_, t_b, pano_
 
-    capi.profile_enable(2 if warm_steps else 1)
-    capi.profile_reset()
+    if args.full:
+        capi.profile_enable(2 if warm_steps else 1)
+        capi.profile_reset()
     dt, infos, marks, t0, pano = run_series(args.steps, pipe=pipelined)
     # wall time of each timed step (start of step k to start of step k + 1; the last one ends at the closing barrier, which
     # includes the last panorama's copy): their mean is ms_per_step, the median and the minimum make a 2 ms change visible
     step_walls = [b - a for a, b in zip([t0] + marks[:-1], marks[:-1] + [t0 + dt])]
-    prof = capi.profile_all()
-    screen_series = capi.profile_series("match_screen_i8")
-    capi.profile_enable(False)
+    prof, screen_series = {}, []
+    if args.full:
+        prof = capi.profile_all()
+        screen_series = capi.profile_series("match_screen_i8")
+        capi.profile_enable(False)
+    if args.dump_outputs and rank == 0:  # (the panorama is delivered to rank 0 only)
+        dump_outputs(args.dump_outputs, pano, infos[-1])
     # The same steps strictly one after the other (value_sequential; the stage table comes from these steps: in the pipelined
     # series a step's "features" is only what was left to wait for and its "render" shares the chip with the next extraction).
     dt_seq, infos_seq, seq_walls = None, infos, None
-    if pipelined:
+    if pipelined and args.full:
         n_seq = max(2, min(args.steps, 8))
         capi.profile_enable(2 if warm_steps else 1)
         capi.profile_reset()
@@ -999,6 +1079,19 @@ def main():
             if (other["n_pairs_verified"], tuple(other["panorama_shape"])) != \
                     (info["n_pairs_verified"], tuple(info["panorama_shape"])):
                 raise RuntimeError("non-deterministic stitch: steps disagree on verified pairs / panorama size")
+    if rank == 0 and not args.full:
+        mpix_in = n * w * h / 1e6
+        out = {"metric": "MPix/s end-to-end stitch (SIFT->blend), 64x4K images",
+               "value": round(mpix_in * args.steps / dt, 2), "unit": "MPix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True, "scaling": "strong",
+               "ms_per_step_median": round(1e3 * float(np.median(step_walls)), 2), "ms_per_step_min": round(1e3 * min(step_walls), 2),
+               "ms_per_step_series": [round(1e3 * x, 2) for x in step_walls],
+               "vs_baseline": None, "dtype": "f32", "data": "synthetic", "pipelined": pipelined, "full": False}
+        sys.stdout.flush()
+        os.write(result_fd, (json.dumps(out) + "\n").encode())
+        if args.save_pano:
+            save_pano(args.save_pano, pano)
+    if rank == 0 and args.full:
         mpix_in = n * w * h / 1e6
         value = mpix_in * args.steps / dt
         dt_resident = sum(i["t_stitch"] for i in infos)
@@ -1272,11 +1365,7 @@ def main():
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
         if args.save_pano:
-            from PIL import Image
-
-            small = pano[:: max(1, pano.shape[0] // 1200), :: max(1, pano.shape[0] // 1200)].cpu().numpy()
-            os.makedirs(os.path.dirname(os.path.abspath(args.save_pano)), exist_ok=True)
-            Image.fromarray(small).save(args.save_pano)
+            save_pano(args.save_pano, pano)
     if multi:
         dist.destroy_process_group()
 

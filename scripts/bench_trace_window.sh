@@ -1,10 +1,13 @@
 #!/bin/bash
 # kernel trace of two bench steps; prints what runs around a named kernel of the last step.  usage: bench_trace_window.sh <kernel substring> [before_us] [after_us]
+# (output under $OUT, default out/ in the repository)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+OUT=${OUT:-out}
+mkdir -p "$R/$OUT"
 rm -rf /tmp/bt
-(cd $R && rocprofv3 --kernel-trace --output-format csv -d /tmp/bt -o p -- python3 bench.py --steps 2 --warmup 1 --end-to-end off --global-probe off --cpu-baseline off > $R/gpurun_out/bench_trace_line.txt 2>&1) || { tail -5 $R/gpurun_out/bench_trace_line.txt; exit 1; }
-python3 - "$1" "${2:-300}" "${3:-3000}" <<'PY' | tee $R/gpurun_out/bench_trace_window.txt
+(cd "$R" && rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/bt" -o p -- python3 bench.py --full --steps 2 --warmup 1 --end-to-end off --global-probe off --cpu-baseline off > "$R/$OUT/bench_trace_line.txt" 2>&1) || { tail -5 "$R/$OUT/bench_trace_line.txt"; exit 1; }
+python3 - "$1" "${2:-300}" "${3:-3000}" <<'PY' | tee "$R/$OUT/bench_trace_window.txt"
 import csv, sys
 name, before, after = sys.argv[1], float(sys.argv[2]) * 1e3, float(sys.argv[3]) * 1e3
 rows = sorted(csv.DictReader(open("/tmp/bt/p_kernel_trace.csv")), key=lambda r: int(r["Start_Timestamp"]))

@@ -1,5 +1,5 @@
 set -e
-B="python bench.py --steps 10 --warmup 2 --cpu-baseline off --global-probe off --with-gain off"
+B="python bench.py --full --steps 10 --warmup 2 --cpu-baseline off --global-probe off --with-gain off"
 show() { python - "$1" <<'P'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

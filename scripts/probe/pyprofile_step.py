@@ -5,7 +5,7 @@ import pstats
 import sys
 
 STEPS = 8
-sys.argv = ["bench.py", "--steps", str(STEPS - 2), "--warmup", "2", "--cpu-baseline", "off", "--end-to-end", "off", "--global-probe", "off"]
+sys.argv = ["bench.py", "--full", "--steps", str(STEPS - 2), "--warmup", "2", "--cpu-baseline", "off", "--end-to-end", "off", "--global-probe", "off"]
 sys.path.insert(0, ".")
 import bench  # noqa: E402
 

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/bg
-(cd $R && rocprofv3 --kernel-trace --output-format csv -d /tmp/bg -o p -- python3 bench.py --steps 3 --warmup 1 --end-to-end off --global-probe off --cpu-baseline off --with-gain off > /tmp/bg_line.txt 2>&1) || { tail -5 /tmp/bg_line.txt; exit 1; }
+(cd "$R" && rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/bg" -o p -- python3 bench.py --full --steps 3 --warmup 1 --end-to-end off --global-probe off --cpu-baseline off --with-gain off > "$TMPDIR/bg_line.txt" 2>&1) || { tail -5 "$TMPDIR/bg_line.txt"; exit 1; }
 python3 - <<'PY'
 import csv
 rows = sorted(csv.DictReader(open("/tmp/bg/p_kernel_trace.csv")), key=lambda r: int(r["Start_Timestamp"]))
