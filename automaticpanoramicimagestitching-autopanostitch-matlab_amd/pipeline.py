@@ -1,8 +1,8 @@
 """The reference driver's stage order (PP/main.m:83-138) over the device hot path.
 
     loadImages/getFeaturePoints -> featureMatchingPairwise -> imageMatching (+ connected components)
-    -> [host: camera initialisation; bundle adjustment / straightening / gain compensation are the
-       reference's host code and out of scope] -> renderPanorama (warp + multiband blend)
+    -> [host: camera initialisation from known intrinsics, or focal estimation + bundle adjustment (normal equations
+       on the device) when they are unknown; straightening] -> renderPanorama (warp + multiband blend)
 
 Everything heavy stays resident in HBM between stages: descriptors never leave the device, images are
 uploaded once, only keypoint coordinates, match index lists and 3x3 models visit the host (they feed the
@@ -29,6 +29,9 @@ DEFAULT_INPUT = {
     # inputs.m:62-74
     "useMATLABImageMatching": 0, "imageMatchingMethod": "ransac", "mBrownLowe": 6, "maxIter": 500,
     "maxDistance": 5.5, "inliersConfidence": 99.9, "transformationType": "projective",
+    # inputs.m:76-85 (bundle adjustment, used when the intrinsics are not given)
+    "maxIterLM": 40, "lambda": 1e-3, "sigmaHuber": 2.0, "focalEstimateMethod": "shumSzeliskiOneHPaper",
+    "residualOneDirection": False, "MaxMatches": 300,
     # inputs.m:94-113
     "gainCompensation": 0, "blending": "multiband", "bands": 3, "MBBsigma": 1, "resizeImage": 0,
     "resizeImagePanoramaCluster": 0, "heightLimit": 800, "widthLimit": 800,
@@ -262,8 +265,9 @@ def connected_components(numMatches):
 
 def cameras_from_models(n, pairs, models, num_matches, Ks):
     """Minimal stand-in for the reference's HOST camera initialisation (initializeCameraMatrices.m:332-455:
-    maximum spanning tree over the match graph + rotation propagation).  Bundle adjustment, straightening
-    and gain compensation are the reference's own host code and are not rebuilt here.
+    maximum spanning tree over the match graph + rotation propagation) for callers that KNOW the intrinsics Ks.
+    When they are unknown, use recognize_panoramas / stitch without Ks: they estimate the focal and run the bundle
+    adjustment (bundleAdjustment.bundleAdjustmentRKf).
     models[p] maps image-j pixels to image-i pixels for pairs[p] = (i, j): H = K_i R_i R_j' K_j^-1.
     Returns (cameras list or None for unreachable images, seed index)."""
     adj = {k: [] for k in range(n)}
@@ -347,12 +351,53 @@ def straightening(cameras, up_angle_t=(60, 60, 105), theta_t=90):
     return out
 
 
-def recognize_panoramas(n, pairs, models, num_matches, Ks, labels, cameras=None):
+def _component_ba(input, members, pairs, models, num_matches, keypoints, inliers, image_sizes, evaluator=None):
+    """bundleAdjustmentRKf over one connected component (recognizePanoramas.m:135-176): the component's verified pairs,
+    their inlier lists and homographies in local indices.  Returns (cameras in member order, seed index into members,
+    stats of the bundle adjustment)."""
+    from . import bundleAdjustment as ba
+
+    loc = {k: q for q, k in enumerate(members)}
+    m = len(members)
+    nm = np.zeros((m, m))
+    matches = [[None] * m for _ in range(m)]
+    tforms = [[None] * m for _ in range(m)]
+    for p, (i, j) in enumerate(pairs):
+        if i in loc and j in loc:
+            a, b = loc[i], loc[j]
+            nm[a, b] = num_matches[i, j]
+            matches[a][b] = np.asarray(inliers[p], np.int64)
+            tforms[a][b] = np.asarray(models[p], np.float64)
+            tforms[b][a] = np.linalg.inv(tforms[a][b])
+    kps = [np.asarray(keypoints[k].cpu() if _capi.is_torch(keypoints[k]) else keypoints[k], np.float64) for k in members]
+    sizes = np.array([[image_sizes[k][0], image_sizes[k][1], 3] for k in members], np.float64)
+    cams, seed, stats = ba.bundleAdjustmentRKf(input, nm, matches, kps, sizes, tforms,
+                                               **({} if evaluator is None else {"evaluator": evaluator}))
+    out = [{k: c[k] for k in ("K", "R", "f", "noRotation") if k in c} for c in cams]
+    if stats["noRotation"] or input.get("forcePlanarScan", False):
+        for o, c in zip(out, cams):
+            o["noRotation"] = 1
+            o["H2refined"] = c["H2refined"]
+    else:
+        for q, c in enumerate(out):
+            if not cams[q]["initialized"]:
+                out[q] = None  # never reached by the incremental loop
+    return out, seed, stats
+
+
+def recognize_panoramas(n, pairs, models, num_matches, Ks, labels, cameras=None, keypoints=None, inliers=None,
+                        image_sizes=None, input=None, ba_info=None):
     """recognizePanoramas.m:70-113 + straightening per panorama (main.m:110-118) over the match graph: every connected
     component with at least two images becomes one panorama with its own cameras and its own reference image.
     The reference runs bundleAdjustmentRKf per component (host code, out of scope); here the cameras are the
     caller's (`cameras`, e.g. from that bundle adjustment) or the host stand-in cameras_from_models, run per component
     from that component's best-connected image.  Components come in conncomp order (by lowest image index).
+    With neither `cameras` nor `Ks`, the cameras are estimated per component instead - focal estimation, spanning-tree
+    rotations and the incremental bundle adjustment of bundleAdjustmentRKf (bundleAdjustment.py; the normal equations on
+    the device) - from `keypoints` (per image), `inliers` (per verified pair, 1-based index pairs as match_and_verify
+    returns them), `image_sizes` ((rows, cols) per image) and `input` (default_input's BA keys); one dict of statistics
+    per component is appended to `ba_info` when given.  Planar sets (noRotation or forcePlanarScan) keep the chained
+    homographies (H2refined = H2seed) and are not straightened.
     Returns a list of dict(members=[global image indices], ref=index INTO members, cameras=[one per member])."""
     labels = np.asarray(labels)
     deg = (np.asarray(num_matches) + np.asarray(num_matches).T).sum(1)
@@ -364,9 +409,17 @@ def recognize_panoramas(n, pairs, models, num_matches, Ks, labels, cameras=None)
         if cameras is not None:
             cams = [cameras[k] for k in members]
             ref = int(np.argmax(deg[members]))
+        elif Ks is None:
+            if keypoints is None or inliers is None or image_sizes is None:
+                raise ValueError("without cameras or the intrinsics Ks, the bundle adjustment needs keypoints, inliers and "
+                                 "image_sizes")
+            cams, ref, stats = _component_ba(input or DEFAULT_INPUT, members, pairs, models, np.asarray(num_matches),
+                                             keypoints, inliers, image_sizes)
+            if not stats["noRotation"] and not (input or {}).get("forcePlanarScan", False):
+                cams = straightening(cams)
+            if ba_info is not None:
+                ba_info.append(dict(stats, members=members))
         else:
-            if Ks is None:
-                raise ValueError("either cameras or the intrinsics Ks must be given (focal estimation/BA are host code out of scope)")
             inside = set(members)
             sel = [p for p, (i, j) in enumerate(pairs) if i in inside and j in inside]
             cams_all, seed = cameras_from_models(n, [pairs[p] for p in sel], [models[p] for p in sel], num_matches, Ks)
@@ -464,7 +517,10 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
            images_original=None):
     """main.m for one dataset.  images: list of uint8 H x W x 3 (torch CUDA tensors stay resident).
     cameras: optional externally supplied cameras (e.g. from the reference's own bundle adjustment);
-    otherwise they are initialised on the host from the verified homographies and the intrinsics Ks.
+    otherwise they are initialised on the host from the verified homographies and the intrinsics Ks.  With neither,
+    they are estimated (focal estimation + bundle adjustment, recognize_panoramas); info then holds
+    times['bundle_adjustment'] and 'ba': per component the estimated focal, the initial and final RMSE, the LM's
+    normal-equation evaluations and noRotation.
     Every connected component of at least two images is rendered (displayPanorama.m:88-116).
     Returns (panoramas [one per component, in component order], info dict with per-stage wall times in seconds)."""
     times = StageTimes()
@@ -478,8 +534,15 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     if second and Ks is not None:  # the intrinsics follow the per-component resize
         Ks = [rescale_K(K, first_hw[k], sizes[k][:2]) for k, K in enumerate(Ks)]
     t0 = time.perf_counter()
-    comps = recognize_panoramas(n, res["pairs"], res["models"], res["numMatches"], Ks, labels, cameras)
-    times.add("host_cameras", t0)
+    ba_info = None
+    if Ks is None and cameras is None:  # estimate the cameras: focal estimation + bundle adjustment per component
+        ba_info = []
+        comps = recognize_panoramas(n, res["pairs"], res["models"], res["numMatches"], None, labels, None, keypoints=kps,
+                                    inliers=res["inliers"], image_sizes=[s[:2] for s in sizes], input=input, ba_info=ba_info)
+        times.add("bundle_adjustment", t0)
+    else:
+        comps = recognize_panoramas(n, res["pairs"], res["models"], res["numMatches"], Ks, labels, cameras)
+        times.add("host_cameras", t0)
     panos = []
     t0 = time.perf_counter()
     opts = {"anglePower": 2, "blending": input["blending"], "pyrLevels": input["bands"], "pyrSigma": input["MBBsigma"],
@@ -500,4 +563,6 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
             "n_components": int(ncomp), "putative": res["putative"], "result": res, "cameras": cams,
             "components": comps, "labels": labels, "second_pass": bool(second), "n_features_first_pass": first_counts,
             "images_processed": images}
+    if ba_info is not None:
+        info["ba"] = ba_info
     return panos, info

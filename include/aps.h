@@ -436,6 +436,28 @@ int aps_imresize_u8(const uint8_t* img, int h, int w, int c, int layout, int oh,
 int aps_ba_pair_blocks(const double* Ui, const double* Uj, int64_t ldu, const int64_t* pair_ptr, int n_pairs,
                        const double* cams, double sigma_huber, int both_directions, double* out);
 
+/* The same blocks for a resident problem, assembled on the device: the normal-equation evaluation of the LM loop of
+ * bundleAdjustmentRKf (accumulateNormalEqnsBlock, :609-791), a few thousand times per set.
+ * aps_ba_problem_create uploads the matched points of every verified pair once (host memory; Ui, Uj, ldu, pair_ptr laid
+ * out as for aps_ba_pair_blocks).  pair_ij: 2 x n_pairs int32, the 0-based cameras (i, j) of pair p with i < j < n_cams,
+ * pairs sorted by (i, j) without repeats.
+ * aps_ba_normal_eqns evaluates at the cameras base_cams (the linearisation point) and lin_cams (base + increments), both
+ * n_cams x 12 f64 packed as for aps_ba_pair_blocks.  col_start[k]: camera k's first column of H, or -1 when k is not in
+ * camList; n_params[k]: 1 for the seed, 4 otherwise.  The active cameras must tile the columns 0 .. P-1 exactly.  A pair
+ * takes part when both its cameras are active and it has matches.  Outputs (host memory): H dense P x P column-major, g
+ * (P), stats = {E, rmse}.  want_H = 0: energy only (the LM trial step, :553-555): no Jacobians, H and g untouched (may be
+ * NULL), the same E and rmse bits as want_H = 1.
+ * Bit contract: H, g, E and rmse equal the host loop of accumulateNormalEqnsBlock over these blocks for a sorted camList
+ * (bundleAdjustment.py): every cell and sum starts at +0.0 and takes its blocks in ascending (i, j) order.
+ * Errors: APS_E_ARG for a NULL handle, a non-positive sigma, a column map that overlaps or does not cover P. */
+typedef struct aps_ba_problem aps_ba_problem;
+int aps_ba_problem_create(const double* Ui, const double* Uj, int64_t ldu, const int64_t* pair_ptr, const int* pair_ij,
+                          int n_pairs, int n_cams, aps_ba_problem** handle);
+int aps_ba_problem_destroy(aps_ba_problem* handle);
+int aps_ba_normal_eqns(aps_ba_problem* handle, const double* base_cams, const double* lin_cams, const int* col_start,
+                       const int* n_params, int P, double sigma_huber, int both_directions, int want_H, double* H, double* g,
+                       double* stats);
+
 /* SURVEY 8(f) rank 4 -- the crop rectangle of PP/imageProcessing/panoramaCropper.m:73-165: rgb2gray + imbinarize against
  * `range` (input.blackRange, or input.whiteRange with canvas_white = 1 and the mask complemented), imfill(.,'holes'), and
  * the line-by-line largest-rectangle scan (first maximum in (line, column) order, the last column never part of a
