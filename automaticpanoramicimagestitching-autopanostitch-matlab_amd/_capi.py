@@ -140,6 +140,7 @@ _SIGNATURES = {
     "aps_ba_problem_create": [_vp, _vp, _i64, _vp, _vp, _i, _i, C.POINTER(_vp)],
     "aps_ba_problem_destroy": [_vp],
     "aps_ba_normal_eqns": [_vp, _vp, _vp, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp],
+    "aps_ba_h_normal_eqns": [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp],
     "aps_multiband_blend": [_vp, _vp, _i, _i, _i, _i, _f, _vp],
     "aps_linear_blend": [_vp, _vp, _i, _i, _i, _vp],
     "aps_image_warp_h_u8": [_vp, _i, _i, _i, _vp, _i, _i, _d, _d, _d, _d, C.c_uint8, _vp],

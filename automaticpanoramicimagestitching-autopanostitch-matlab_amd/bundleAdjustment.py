@@ -12,7 +12,12 @@ homographies) and bundleAdjustmentRKf.m (incremental Brown-Lowe driver, Levenber
 match subsampling).  The LM loop takes its normal-equation evaluator as an argument: DeviceEvaluator (a resident
 BaProblem: blocks and assembly on the device, bit-identical to the host reduction) in production, HostEvaluator
 (accumulateNormalEqnsBlock with any block function) for the CPU tests.  The prior and the solve stay on the host (they
-are O(P^2..P^3) in the camera count, not in the match count)."""
+are O(P^2..P^3) in the camera count, not in the match count).
+
+Planar sets are refined by bundleAdjustmentH.m (joint LM over the absolute homographies, opt-in through
+input['planarBundleAdjustment']): its data term runs on the same resident problem (aps_ba_h_normal_eqns, DeviceEvaluatorH),
+hNormalEqnsMirror restates it bit for bit in numpy (HostEvaluatorH), and adaptiveLM, the RegProj rows and the solve stay
+here."""
 from __future__ import annotations
 
 import numpy as np
@@ -189,6 +194,19 @@ class BaProblem:
                                      int(bool(both)), int(bool(want_H)), ptr(H), ptr(g), ptr(st)))
         return H, g, float(st[0]), float(st[1])
 
+    def h_normal_eqns(self, G, seed, huber, want_H=True):
+        """The data term of bundleAdjustmentH (aps_ba_h_normal_eqns) at the absolute homographies G (n_cams x 3 x 3 or
+        x 9, H(3,3) = 1): (J'J P x P, J'r, stats = [sum (w res)^2, sum |res|^2, match count]), P = 8 (n_cams - 1); with
+        want_H=False (H, g) are None."""
+        G = np.ascontiguousarray(np.asarray(G, np.float64).reshape(self.n_cams, 9))
+        P = 8 * (self.n_cams - 1)
+        H = np.empty((P, P), np.float64, order="F") if want_H else None
+        g = np.empty(P, np.float64) if want_H else None
+        st = np.zeros(3, np.float64)
+        check(lib.aps_ba_h_normal_eqns(self._h, ptr(G), self.n_cams, int(seed), float(huber), int(bool(want_H)), ptr(H),
+                                       ptr(g), ptr(st)))
+        return H, g, st
+
     def close(self):
         if getattr(self, "_h", None):
             check(lib.aps_ba_problem_destroy(self._h))
@@ -253,6 +271,333 @@ class HostEvaluator:
         self.calls += 1
         return accumulateNormalEqnsBlock(Phi, pmap, baseCams, camList, seed, self.matches, self.keypoints, None, sigmaHuber,
                                          {"OneDirection": not self.both}, blocks=self.blocks)
+
+
+# ---- bundleAdjustmentH.m: joint refinement of the absolute homographies of a planar set ----------------------------------
+
+def normalizeH(H):
+    """H = normalizeH(H) (bundleAdjustmentH.m:965-980): H / H(3,3); when H(3,3) == 0 first H / (sign(det) cbrt(max(eps,
+    |det|)))."""
+    H = np.array(H, np.float64, copy=True).reshape(3, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if H[2, 2] == 0:
+            d = np.linalg.det(H)
+            H = H / (np.sign(d) * np.cbrt(max(np.finfo(float).eps, abs(d))))
+        if H[2, 2] != 0:
+            H = H / H[2, 2]
+    return H
+
+
+def hom2param(H):
+    """p = hom2param(H) (:924-941): [a b c d e f g h] of normalizeH(H), row-major."""
+    return normalizeH(H).ravel()[:8].copy()
+
+
+def param2hom(p):
+    """H = param2hom(p) (:943-963): [a b c; d e f; g h 1]."""
+    return np.append(np.asarray(p, np.float64).reshape(8), 1.0).reshape(3, 3)
+
+
+def randPermutationPairSeed(imgI, imgJ):
+    """The RandStream seed of randPermutationPair (:1118-1138) for the 1-based image indices, in MATLAB's saturating
+    uint32 arithmetic: mod(sat(sat(1664525 imgI) + sat(1013904223 imgJ)), 2^31 - 1), 0 becoming 1."""
+    a = _u32(1664525.0 * _u32(imgI))
+    b = _u32(1013904223.0 * _u32(imgJ))
+    seed = int(_u32(a + b)) % (2 ** 31 - 1)
+    return seed if seed != 0 else 1
+
+
+def randPermutationPair(M, kCap, imgI, imgJ):
+    """kCap distinct 0-based indices of 0 .. M-1 (randperm(rs, M, kCap)), drawn from numpy's Philox stream under
+    randPermutationPairSeed; MATLAB's threefry randperm order is not reproduced."""
+    rng = np.random.Generator(np.random.Philox(randPermutationPairSeed(imgI, imgJ)))
+    return rng.choice(int(M), int(min(kCap, M)), replace=False)
+
+
+def subsampleMatchesH(Ui, Uj, i, j, cap, mode="random"):
+    """[Ui, Uj] = subsampleMatches(...) of bundleAdjustmentH (:1020-1069) for the 0-based images i, j: a pair of at most
+    `cap` matches is returned as it is, a larger one keeps `cap` of them ('random': randPermutationPair of the 1-based
+    indices).  'grid' and 'polar' are not built."""
+    Ui, Uj = np.asarray(Ui, np.float64), np.asarray(Uj, np.float64)
+    if cap is None or not np.isfinite(cap) or len(Ui) <= cap:
+        return Ui, Uj
+    if mode != "random":
+        raise NotImplementedError("SubsampleMode %r is not built (only 'random')" % (mode,))
+    idx = randPermutationPair(len(Ui), int(cap), i + 1, j + 1)
+    return Ui[idx], Uj[idx]
+
+
+def _h_jacobian_rows(Hm, u, v, Y1, Y2, Y3, w):
+    """computeJacobianBatch (:685-737) as written: the (M, 2, 8) rows du/dp, dv/dp times w, elementwise."""
+    M = len(u)
+    one, zero = np.ones(M), np.zeros(M)
+    dY1 = np.stack([u, v, one, zero, zero, zero, zero, zero], 1)
+    dY2 = np.stack([zero, zero, zero, u, v, one, zero, zero], 1)
+    dY3 = np.stack([zero, zero, zero, zero, zero, zero, u, v], 1)
+    y3sq = (Y3 * Y3)[:, None]
+    du = (dY1 * Y3[:, None] - Y1[:, None] * dY3) / y3sq * w[:, None]
+    dv = (dY2 * Y3[:, None] - Y2[:, None] * dY3) / y3sq * w[:, None]
+    return np.stack([du, dv], 1)
+
+
+def hNormalEqnsMirror(Ui, Uj, pair_ptr, pairs, G, seed, huber, want_H=True):
+    """The numpy mirror of aps_ba_h_normal_eqns: the same f64 operations in the same order (include/aps.h), elementwise
+    numpy and explicit loops only - the oracle of that entry's bit contract.  Ui, Uj: the pairs' points back to back
+    (pair_ptr delimits them); pairs: [(i, j)] 0-based, i < j, sorted; G: n x 3 x 3 (or n x 9), H(3,3) = 1.
+    Returns (H P x P, g, stats = [sum (w res)^2, sum |res|^2, match count]); H, g are None when want_H is False."""
+    pairs = [tuple(int(x) for x in q) for q in pairs]
+    n = len(G)
+    Gm = np.asarray(G, np.float64).reshape(n, 9)
+    Ui = np.asarray(Ui, np.float64).reshape(-1, 2)
+    Uj = np.asarray(Uj, np.float64).reshape(-1, 2)
+    ptr_ = np.asarray(pair_ptr, np.int64)
+    n_pairs = len(pairs)
+    cnt = ptr_[1:] - ptr_[:-1]
+    delta = max(0.0, float(huber))
+    P = 8 * (n - 1)
+    Mt = int(ptr_[-1]) if n_pairs else 0
+    # per match: the pair's homographies, the residual, the Huber weight
+    owner = np.repeat(np.arange(n_pairs), cnt)
+    ii = np.array([q[0] for q in pairs], np.int64)[owner] if n_pairs else np.zeros(0, np.int64)
+    jj = np.array([q[1] for q in pairs], np.int64)[owner] if n_pairs else np.zeros(0, np.int64)
+
+    def project(Hr, u, v):
+        return (Hr[:, 0] * u + Hr[:, 1] * v + Hr[:, 2], Hr[:, 3] * u + Hr[:, 4] * v + Hr[:, 5], Hr[:, 6] * u + Hr[:, 7] * v + 1.0)
+
+    ui, vi, uj, vj = Ui[:Mt, 0], Ui[:Mt, 1], Uj[:Mt, 0], Uj[:Mt, 1]
+    Yi1, Yi2, Yi3 = project(Gm[ii], ui, vi)
+    Yj1, Yj2, Yj3 = project(Gm[jj], uj, vj)
+    ru = Yi1 / Yi3 - Yj1 / Yj3
+    rv = Yi2 / Yi3 - Yj2 / Yj3
+    nn = ru * ru + rv * rv
+    w = np.ones(Mt)
+    if delta > 0:
+        nrm = np.sqrt(nn)
+        out = nrm >= delta
+        w[out] = delta / nrm[out]
+    wr = np.stack([ru * w, rv * w], 1)
+    if want_H:
+        Ji = _h_jacobian_rows(Gm[ii], ui, vi, Yi1, Yi2, Yi3, w)
+        Jj = -_h_jacobian_rows(Gm[jj], uj, vj, Yj1, Yj2, Yj3, w)
+    # per pair: 64 lane-strided partials (match k on lane k mod 64, ascending k; row u, then row v), then the butterfly
+    steps = int(-(-cnt.max() // 64)) if n_pairs and cnt.max() > 0 else 0
+    lane = np.arange(64)
+    sums = np.zeros((n_pairs, 64, 3))
+    if want_H:
+        Hii = np.zeros((n_pairs, 64, 8, 8))
+        Hjj = np.zeros((n_pairs, 64, 8, 8))
+        Hij = np.zeros((n_pairs, 64, 8, 8))
+        gi = np.zeros((n_pairs, 64, 8))
+        gj = np.zeros((n_pairs, 64, 8))
+    for s in range(steps):
+        k = s * 64 + lane[None, :]
+        valid = k < cnt[:, None]
+        idx = np.where(valid, ptr_[:-1, None] + k, 0)
+        for q in range(2):
+            e = wr[idx, q] * wr[idx, q]
+            sums[:, :, 0] = np.where(valid, sums[:, :, 0] + e, sums[:, :, 0])
+        sums[:, :, 1] = np.where(valid, sums[:, :, 1] + nn[idx], sums[:, :, 1])
+        sums[:, :, 2] = np.where(valid, sums[:, :, 2] + 1.0, sums[:, :, 2])
+        if want_H:
+            v2, v3 = valid[:, :, None], valid[:, :, None, None]
+            for q in range(2):
+                a, b, r = Ji[idx, q], Jj[idx, q], wr[idx, q][:, :, None]
+                Hii = np.where(v3, Hii + a[:, :, :, None] * a[:, :, None, :], Hii)
+                Hjj = np.where(v3, Hjj + b[:, :, :, None] * b[:, :, None, :], Hjj)
+                Hij = np.where(v3, Hij + a[:, :, :, None] * b[:, :, None, :], Hij)
+                gi = np.where(v2, gi + a * r, gi)
+                gj = np.where(v2, gj + b * r, gj)
+    for s in (32, 16, 8, 4, 2, 1):
+        sums = sums + sums[:, lane ^ s]
+        if want_H:
+            Hii, Hjj, Hij = Hii + Hii[:, lane ^ s], Hjj + Hjj[:, lane ^ s], Hij + Hij[:, lane ^ s]
+            gi, gj = gi + gi[:, lane ^ s], gj + gj[:, lane ^ s]
+    # assembly in pair order; the statistics summed in pair order
+    stats = [0.0, 0.0, 0.0]
+    for p in range(n_pairs):
+        if cnt[p] > 0:
+            for e in range(3):
+                stats[e] = stats[e] + float(sums[p, 0, e])
+    if not want_H:
+        return None, None, np.array(stats)
+    col = {}
+    for k in range(n):
+        if k != seed:
+            col[k] = np.arange(8 * len(col), 8 * len(col) + 8)
+    H = np.zeros((P, P))
+    g = np.zeros(P)
+    for p, (i, j) in enumerate(pairs):
+        if cnt[p] == 0:
+            continue
+        if i != seed:
+            H[np.ix_(col[i], col[i])] += Hii[p, 0]
+            g[col[i]] += gi[p, 0]
+        if j != seed:
+            H[np.ix_(col[j], col[j])] += Hjj[p, 0]
+            g[col[j]] += gj[p, 0]
+        if i != seed and j != seed:
+            H[np.ix_(col[i], col[j])] += Hij[p, 0]
+            H[np.ix_(col[j], col[i])] += Hij[p, 0].T
+    return H, g, np.array(stats)
+
+
+def _h_problem(pairs, n):
+    """(Ui, Uj, pair_ptr, [(i, j)]) of bundleAdjustmentH's pairs (dicts with i < j, Ui, Uj), in (i, j) order."""
+    pairs = sorted(pairs, key=lambda q: (q["i"], q["j"]))
+    for q in pairs:
+        if not 0 <= q["i"] < q["j"] < n:
+            raise ValueError("pairs need 0 <= i < j < N, got (%d, %d)" % (q["i"], q["j"]))
+    z = np.zeros((0, 2))
+    Ui = np.concatenate([np.asarray(q["Ui"], np.float64).reshape(-1, 2) for q in pairs]) if pairs else z
+    Uj = np.concatenate([np.asarray(q["Uj"], np.float64).reshape(-1, 2) for q in pairs]) if pairs else z
+    ptrs = np.concatenate([[0], np.cumsum([len(q["Ui"]) for q in pairs])]).astype(np.int64)
+    return Ui, Uj, ptrs, [(q["i"], q["j"]) for q in pairs]
+
+
+class DeviceEvaluatorH:
+    """The production data-term evaluator of bundleAdjustmentH: a resident BaProblem over the (subsampled) pairs, evaluated
+    by aps_ba_h_normal_eqns.  Call signature shared with HostEvaluatorH: (G n x 3 x 3, seed, huber, want_H) ->
+    (J'J, J'r, [sum (w res)^2, sum |res|^2, count])."""
+
+    def __init__(self, pairs, n):
+        Ui, Uj, ptrs, ij = _h_problem(pairs, n)
+        self.problem = BaProblem(Ui, Uj, ptrs, ij, n)
+        self.calls = 0
+
+    def __call__(self, G, seed, huber, want_H=True):
+        self.calls += 1
+        return self.problem.h_normal_eqns(G, seed, huber, want_H)
+
+
+class HostEvaluatorH:
+    """hNormalEqnsMirror over the same pairs (the CPU tests' evaluator)."""
+
+    def __init__(self, pairs, n):
+        self.Ui, self.Uj, self.ptrs, self.ij = _h_problem(pairs, n)
+        self.calls = 0
+
+    def __call__(self, G, seed, huber, want_H=True):
+        self.calls += 1
+        return hNormalEqnsMirror(self.Ui, self.Uj, self.ptrs, self.ij, G, seed, huber, want_H)
+
+
+def adaptiveLM(p0, evaluate, MaxIters=50, Lambda=1e-3):
+    """p = adaptiveLM(...) (bundleAdjustmentH.m:147-279) as written, on an evaluator evaluate(p, want_H) -> (J'J, J'r,
+    E = 0.5 r'r, aux) (J'J and J'r None when want_H is False).  Per iteration: (J'J + lambda I) dp = -g (solveSpd: dense
+    Cholesky, lstsq as the fallback, for the reference's sparse mldivide); stop when |dp| <= 1e-8 (1 + |p|); one energy-only
+    evaluation at p + dp; rho = dE / (|-g'dp - 0.5 lambda dp'dp| + eps); rho > 0 accepts (one full evaluation at the new p,
+    lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2), otherwise lambda *= nu, nu *= 2 and the cached J'J, g stay; then the
+    gradient stop |g| <= 1e-10 (1 + E) on this iteration's g and the stop at lambda > 1e12.
+    Returns (p, info) with info = dict(reason ('step', 'gradient', 'lambda' or 'max_iters'), iterations, accepted, E, aux
+    of the returned p, E_init, aux_init)."""
+    p = np.array(p0, np.float64, copy=True)
+    lam, nu = float(Lambda), 2.0
+    JtJ, g, E, aux = evaluate(p, True)
+    info = {"reason": "max_iters", "iterations": 0, "accepted": 0, "E_init": E, "aux_init": aux}
+    eps = np.finfo(float).eps
+    for it in range(1, int(MaxIters) + 1):
+        info["iterations"] = it
+        dp = solveSpd(JtJ + lam * np.eye(len(p)), -g)
+        if np.linalg.norm(dp) <= 1e-8 * (1 + np.linalg.norm(p)):
+            info["reason"] = "step"
+            break
+        pNew = p + dp
+        _, _, ENew, auxNew = evaluate(pNew, False)
+        dEPred = -float(g @ dp) - 0.5 * float(dp @ (lam * dp))
+        rho = (E - ENew) / (abs(dEPred) + eps)
+        gIt = g
+        if rho > 0:
+            p, E, aux = pNew, ENew, auxNew
+            JtJ, g, _, _ = evaluate(p, True)
+            lam = lam * max(1 / 3, 1 - (2 * rho - 1) ** 3)
+            nu = 2.0
+            info["accepted"] += 1
+        else:
+            lam = lam * nu
+            nu = 2 * nu
+        if np.linalg.norm(gIt) <= 1e-10 * (1 + E):
+            info["reason"] = "gradient"
+            break
+        if lam > 1e12:
+            info["reason"] = "lambda"
+            break
+    info["E"], info["aux"] = E, aux
+    return p, info
+
+
+def _h_absolute(p, G, mask, seed):
+    """Habs of residualsJacobian (:311-323): normalizeH(param2hom(p block)) for every non-seed image, eye(3) for the seed."""
+    out, b = [], 0
+    for k in range(len(G)):
+        if k == seed:
+            out.append(np.eye(3))
+        else:
+            out.append(normalizeH(param2hom(p[8 * b:8 * b + 8])))
+            b += 1
+    return np.stack(out)
+
+
+def bundleAdjustmentH(input, pairs, N, seed, G0, MaxIters=50, Huber=1.0, Lambda=1e-3, RegProj=1e-4, RegDet=0.0,
+                      UseLSQ=False, OneDirection=True, MaxMatches=np.inf, SubsampleMode="random", ImageSizes=None,
+                      evaluator=None):
+    """[G, stats] = bundleAdjustmentH(input, pairs, N, seed, 'Name', Value, ...) (bundleAdjustmentH.m:1-145) with the
+    adaptiveLM optimiser, indices 0-based.  pairs: dicts with i < j and the matched points Ui, Uj (M x 2 pixels) of each;
+    G0: N initial absolute homographies (normalised, the seed's replaced by eye(3)).  Minimises 0.5 r'r over the
+    one-direction Huber-weighted transfer residuals Hi ui - Hj uj (on the device: aps_ba_h_normal_eqns) plus the RegProj
+    rows sqrt(RegProj) H(3,1), sqrt(RegProj) H(3,2) of every non-seed image (on the host).  A pair with more than
+    MaxMatches matches keeps MaxMatches of them (subsampleMatchesH).  evaluator(pairs, N) builds the data-term evaluator
+    (default: DeviceEvaluatorH).  Not built: UseLSQ (lsqnonlin; bundleAdjustmentRKf passes false), bidirectional residuals
+    (OneDirection = false), RegDet > 0, the 'grid' / 'polar' subsampling.
+    Returns (G: N refined homographies with H(3,3) = 1, the seed's exactly eye(3); stats = dict(evaluations, rmse_init,
+    rmse_final [unweighted transfer RMSE in px over the subsampled matches], reason, iterations, accepted, E_init,
+    E_final))."""
+    if UseLSQ:
+        raise NotImplementedError("UseLSQ (lsqnonlin) is not built; the adaptive LM is")
+    if not OneDirection:
+        raise NotImplementedError("bidirectional residuals (OneDirection = false) are not built")
+    if RegDet and RegDet > 0:
+        raise NotImplementedError("RegDet > 0 is not built")
+    G = [normalizeH(G0[k]) for k in range(N)]
+    G[seed] = np.eye(3)
+    sub = []
+    for q in pairs:
+        Ui, Uj = subsampleMatchesH(q["Ui"], q["Uj"], q["i"], q["j"], MaxMatches, SubsampleMode)
+        sub.append({"i": int(q["i"]), "j": int(q["j"]), "Ui": Ui, "Uj": Uj})
+    evaluate_data = (evaluator or DeviceEvaluatorH)(sub, N)
+    mask = [k != seed for k in range(N)]
+    p0 = np.concatenate([hom2param(G[k]) for k in range(N) if mask[k]]) if N > 1 else np.zeros(0)
+    sreg = np.sqrt(RegProj) if RegProj > 0 else 0.0
+
+    def evaluate(p, want_H):
+        Habs = _h_absolute(p, G, mask, seed)
+        JtJ, g, st = evaluate_data(Habs, seed, Huber, want_H)
+        rr = float(st[0])
+        if want_H:
+            JtJ, g = np.array(JtJ, np.float64, order="C"), np.array(g, np.float64)
+        b = 0
+        for k in range(N):  # the RegProj rows (:438-467)
+            if not mask[k] or sreg == 0.0:
+                continue
+            for e, (rr_k, c) in enumerate(((sreg * Habs[k][2, 0], 8 * b + 6), (sreg * Habs[k][2, 1], 8 * b + 7))):
+                rr = rr + rr_k * rr_k
+                if want_H:
+                    JtJ[c, c] = JtJ[c, c] + sreg * sreg
+                    g[c] = g[c] + sreg * rr_k
+            b += 1
+        return JtJ, g, 0.5 * rr, st
+
+    p, info = adaptiveLM(p0, evaluate, MaxIters, Lambda)
+    Gout = [np.eye(3) if k == seed else None for k in range(N)]
+    b = 0
+    for k in range(N):
+        if mask[k]:
+            Gout[k] = normalizeH(param2hom(p[8 * b:8 * b + 8]))
+            b += 1
+    rmse = lambda st: float(np.sqrt(max(float(st[1]), 0.0) / max(float(st[2]), 1.0)))  # noqa: E731
+    stats = {"evaluations": evaluate_data.calls, "rmse_init": rmse(info["aux_init"]), "rmse_final": rmse(info["aux"]),
+             "reason": info["reason"], "iterations": info["iterations"], "accepted": info["accepted"],
+             "E_init": info["E_init"], "E_final": info["E"]}
+    return Gout, stats
 
 
 # ---- camera initialisation: initializeCameraMatrices.m --------------------------------------------------------------------
@@ -674,19 +1019,22 @@ def _intrinsics(f, size):
     return np.array([[f, 0, size[1] / 2.0], [0, f, size[0] / 2.0], [0, 0, 1.0]])
 
 
-def bundleAdjustmentRKf(input, numMatches, matches, keypoints, imageSizes, Tforms, evaluator=None, history=None):
+def bundleAdjustmentRKf(input, numMatches, matches, keypoints, imageSizes, Tforms, evaluator=None, history=None,
+                        evaluatorH=None):
     """[cameras, seed] = bundleAdjustmentRKf(...) (:1-374) for one connected component, indices 0-based.
     numMatches: N x N (upper triangle used); matches[i][j] (i < j): M x 2 1-based keypoint indices; keypoints[i]: K x 2
     pixels; imageSizes: N x 3 (rows, cols, channels); Tforms[i][j]: 3 x 3 homography j -> i for every matched (i, j), both
     orders.  evaluator(matches, keypoints, both) builds the normal-equation evaluator over the subsampled matches
     (default: DeviceEvaluator).
-    Seed = the image with the most matched points; cameras from initializeCameraMatrices; a planar set (noRotation or
-    input['forcePlanarScan']) returns them with H2refined = H2seed (the reference refines those with bundleAdjustmentH,
-    which is not built here).  Otherwise the incremental Brown-Lowe loop: add the uninitialised image with the most
+    Seed = the image with the most matched points; cameras from initializeCameraMatrices.  A planar set (noRotation or
+    input['forcePlanarScan']) returns them with H2refined: with input['planarBundleAdjustment'] the homographies refined
+    by bundleAdjustmentH from H2seed (as the reference always does; evaluatorH(pairs, N) builds its data-term evaluator,
+    default DeviceEvaluatorH), without it H2seed itself.  Otherwise the incremental Brown-Lowe loop: add the uninitialised image with the most
     matches to an initialised one (rotation from their homography, focal of its partner), run the global LM over every
     initialised camera, then min(2, ceil(N / 10)) final passes at sigmaHuber.
     Returns (cameras, seed, stats) with stats = dict(f_init, rmse_init [all images at the initial cameras], rmse_final,
-    evaluations [normal-equation evaluations of the LM], noRotation, ...)."""
+    evaluations [normal-equation evaluations of the LM], noRotation, ...); a refined planar set reports bundleAdjustmentH's
+    evaluations, transfer RMSE and energy before and after, lm_stop and lm_iterations."""
     N = len(keypoints)
     opts = {"SigmaHuber": float(input.get("sigmaHuber", 2.0)), "MaxLMIters": int(input.get("maxIterLM", 40)),
             "Lambda0": float(input.get("lambda", 1e-3)), "FocalSmoothnessWeight": "auto", "FocalMeanWeight": 50,
@@ -704,11 +1052,22 @@ def bundleAdjustmentRKf(input, numMatches, matches, keypoints, imageSizes, Tform
     stats = {"f_init": cameras[0]["f"], "noRotation": int(cameras[0]["noRotation"]), "evaluations": 0,
              "rmse_init": None, "rmse_final": None}
     if cameras[0]["noRotation"] == 1 or input.get("forcePlanarScan", False):
-        # the reference refines H2seed with bundleAdjustmentH here (not built): the chained homographies are kept
         for c in cameras:
             c["noRotation"] = 1
-            c["H2refined"] = c["H2seed"]
         stats["noRotation"] = 1
+        if not input.get("planarBundleAdjustment", False):
+            # opt-in: without the key the chained homographies are kept (the reference always refines them)
+            for c in cameras:
+                c["H2refined"] = c["H2seed"]
+            return cameras, seed, stats
+        # :117-128: bundleAdjustmentH from G0 = H2seed, one-direction residuals, 'random' subsampling, no lsqnonlin
+        G, hst = bundleAdjustmentH(input, pairs, N, seed, G0=[c["H2seed"] for c in cameras], MaxIters=opts["MaxLMIters"],
+                                   Huber=opts["SigmaHuber"], UseLSQ=False, ImageSizes=imageSizes, OneDirection=True,
+                                   MaxMatches=cap, SubsampleMode="random", evaluator=evaluatorH)
+        for c, Gk in zip(cameras, G):
+            c["H2refined"] = Gk
+        stats.update(evaluations=hst["evaluations"], rmse_init=hst["rmse_init"], rmse_final=hst["rmse_final"],
+                     lm_stop=hst["reason"], lm_iterations=hst["iterations"], E_init=hst["E_init"], E_final=hst["E_final"])
         return cameras, seed, stats
     # MaxMatches: one 'random' subset per pair, drawn once (its seed depends on the principal points only)
     sub = [[None] * N for _ in range(N)]

@@ -406,6 +406,321 @@ __global__ __launch_bounds__(256) void ba_assemble_kernel(const double* __restri
     }
 }
 
+// ---- bundleAdjustmentH: the one-direction data term of residualsJacobian (aps_ba_h_normal_eqns) ---------------------------
+//
+// PP/bundleAdjustment/bundleAdjustmentH.m:282-436 with computeUnidirResiduals (:512-590) and computeJacobianBatch (:685-737).
+// Match k of pair (i, j): Y = H [u v 1]' as Y1 = (a u + b v) + c, Y2 = (d u + e v) + f, Y3 = (g u + h v) + 1 (H(3,3) = 1),
+// res = Yi(1:2) / Yi3 - Yj(1:2) / Yj3, the Huber weight w = delta / |res| when |res| >= delta > 0 (else 1) multiplies res
+// itself, and the two rows of a side are ((dY/dp) Y3 - Y (dY3/dp)) / (Y3 Y3) * w, those of Hj negated.  Written out, a
+// side's rows carry seven distinct values: row u = [A0 A1 A2 0 0 0 Bu0 Bu1], row v = [0 0 0 A0 A1 A2 Bv0 Bv1] with
+// A = ([u v 1] Y3 - Y1 0) / Y3^2 w, Bu = (0 Y3 - Y1 [u v]) / Y3^2 w, Bv = (0 Y3 - Y2 [u v]) / Y3^2 w.  The literal row v
+// value of A differs from row u's at most in the sign of a zero, and a product with a +-0 factor leaves an accumulator
+// unchanged (every accumulator starts at +0.0, so none is ever -0.0): the compact sums below equal the literal
+// sum over both rows of J'J and J'r bit for bit (finite inputs).  Each cell takes, match by match, the row u term then
+// the row v term; per pair 64 lane-strided partials and an xor butterfly, as in the RKf blocks.
+//
+// Three waves per pair (blockIdx.y): part 0 = Hii, gi and the sums, part 1 = Hjj and gj, part 2 = Hij; part 3 (the energy-only
+// launch) = the sums alone, computed by the same code as part 0.  Record per pair (kBaHRec f64): Hii, Hjj, Hij (8 x 8
+// column-major), gi, gj (8), then sum (w res)^2, sum |res|^2, match count.
+
+constexpr int kBaHRec = 3 * 64 + 16 + 3;
+constexpr int kHSide = 29;   // AA 6 (symmetric), A Bu 6, A Bv 6, BB 3 (symmetric), g: A ru 3, A rv 3, B 2
+constexpr int kHCross = 37;  // Ai Aj 9, Ai Buj 6, Ai Bvj 6, Bui Aj 6, Bvi Aj 6, BBij 4
+
+struct HSide {
+    double A[3], Bu[2], Bv[2];
+};
+
+__device__ __forceinline__ constexpr int sym3(int a, int b) {
+    return a <= b ? (a == 0 ? b : a == 1 ? 2 + b : 5) : (b == 0 ? a : b == 1 ? 2 + a : 5);
+}
+
+__device__ __forceinline__ constexpr int sym2(int a, int b) { return a + b; }
+
+__device__ __forceinline__ void h_project(const double* Hm, double u, double v, double& Y1, double& Y2, double& Y3) {
+    Y1 = Hm[0] * u + Hm[1] * v + Hm[2];
+    Y2 = Hm[3] * u + Hm[4] * v + Hm[5];
+    Y3 = Hm[6] * u + Hm[7] * v + 1.0;
+}
+
+__device__ __forceinline__ void h_side(double u, double v, double Y1, double Y2, double Y3, double w, bool negate, HSide& s) {
+    const double y3sq = Y3 * Y3;
+    const double z = 0.0 * Y3;
+    const double d[3] = {u, v, 1.0};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) s.A[a] = (d[a] * Y3 - Y1 * 0.0) / y3sq * w;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        s.Bu[b] = (z - Y1 * d[b]) / y3sq * w;
+        s.Bv[b] = (z - Y2 * d[b]) / y3sq * w;
+    }
+    if (negate) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s.A[a] = -s.A[a];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            s.Bu[b] = -s.Bu[b];
+            s.Bv[b] = -s.Bv[b];
+        }
+    }
+}
+
+__device__ __forceinline__ void h_side_acc(double* acc, const HSide& s, double wru, double wrv) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) acc[sym3(a, b)] = acc[sym3(a, b)] + s.A[a] * s.A[b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            acc[6 + 2 * a + b] = acc[6 + 2 * a + b] + s.A[a] * s.Bu[b];
+            acc[12 + 2 * a + b] = acc[12 + 2 * a + b] + s.A[a] * s.Bv[b];
+        }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = a; b < 2; ++b) {
+            acc[18 + sym2(a, b)] = acc[18 + sym2(a, b)] + s.Bu[a] * s.Bu[b];
+            acc[18 + sym2(a, b)] = acc[18 + sym2(a, b)] + s.Bv[a] * s.Bv[b];
+        }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        acc[21 + a] = acc[21 + a] + s.A[a] * wru;
+        acc[24 + a] = acc[24 + a] + s.A[a] * wrv;
+    }
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        acc[27 + b] = acc[27 + b] + s.Bu[b] * wru;
+        acc[27 + b] = acc[27 + b] + s.Bv[b] * wrv;
+    }
+}
+
+__device__ __forceinline__ void h_cross_acc(double* acc, const HSide& si, const HSide& sj) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) acc[3 * a + b] = acc[3 * a + b] + si.A[a] * sj.A[b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            acc[9 + 2 * a + b] = acc[9 + 2 * a + b] + si.A[a] * sj.Bu[b];
+            acc[15 + 2 * a + b] = acc[15 + 2 * a + b] + si.A[a] * sj.Bv[b];
+        }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            acc[21 + 3 * a + b] = acc[21 + 3 * a + b] + si.Bu[a] * sj.A[b];
+            acc[27 + 3 * a + b] = acc[27 + 3 * a + b] + si.Bv[a] * sj.A[b];
+        }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            acc[33 + 2 * a + b] = acc[33 + 2 * a + b] + si.Bu[a] * sj.Bu[b];
+            acc[33 + 2 * a + b] = acc[33 + 2 * a + b] + si.Bv[a] * sj.Bv[b];
+        }
+}
+
+// the 8 x 8 block (column-major) and the 8 g entries of one side from its compact sums; structural zeros are +0.0
+__device__ __forceinline__ void h_side_write(const double* acc, double* Hb, double* gb) {
+    static_for<0, 64>([&](auto e) {
+        constexpr int a = e % 8, b = e / 8;
+        constexpr int ga = a < 3 ? 0 : a < 6 ? 1 : 2, gb_ = b < 3 ? 0 : b < 6 ? 1 : 2;
+        double v = 0.0;
+        if constexpr (ga == gb_ && ga < 2) v = acc[sym3(a - 3 * ga, b - 3 * gb_)];
+        else if constexpr (ga == 0 && gb_ == 2) v = acc[6 + 2 * a + (b - 6)];
+        else if constexpr (ga == 2 && gb_ == 0) v = acc[6 + 2 * b + (a - 6)];
+        else if constexpr (ga == 1 && gb_ == 2) v = acc[12 + 2 * (a - 3) + (b - 6)];
+        else if constexpr (ga == 2 && gb_ == 1) v = acc[12 + 2 * (b - 3) + (a - 6)];
+        else if constexpr (ga == 2 && gb_ == 2) v = acc[18 + sym2(a - 6, b - 6)];
+        Hb[e] = v;
+    });
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        gb[a] = acc[21 + a];
+        gb[3 + a] = acc[24 + a];
+    }
+    gb[6] = acc[27];
+    gb[7] = acc[28];
+}
+
+__device__ __forceinline__ void h_cross_write(const double* acc, double* Hb) {
+    static_for<0, 64>([&](auto e) {
+        constexpr int a = e % 8, b = e / 8;  // a: parameter of i (row), b: parameter of j (column)
+        constexpr int ga = a < 3 ? 0 : a < 6 ? 1 : 2, gb_ = b < 3 ? 0 : b < 6 ? 1 : 2;
+        double v = 0.0;
+        if constexpr (ga == gb_ && ga < 2) v = acc[3 * (a - 3 * ga) + (b - 3 * gb_)];
+        else if constexpr (ga == 0 && gb_ == 2) v = acc[9 + 2 * a + (b - 6)];
+        else if constexpr (ga == 1 && gb_ == 2) v = acc[15 + 2 * (a - 3) + (b - 6)];
+        else if constexpr (ga == 2 && gb_ == 0) v = acc[21 + 3 * (a - 6) + b];
+        else if constexpr (ga == 2 && gb_ == 1) v = acc[27 + 3 * (a - 6) + (b - 3)];
+        else if constexpr (ga == 2 && gb_ == 2) v = acc[33 + 2 * (a - 6) + (b - 6)];
+        Hb[e] = v;
+    });
+}
+
+template <int kPart>
+__device__ __forceinline__ void h_pair_part(const double* hi, const double* hj, const double* __restrict__ Ui,
+                                            const double* __restrict__ Uj, int64_t ldu, int64_t r0, int64_t m, double delta,
+                                            double* __restrict__ rec) {
+    constexpr bool kSums = kPart == 0 || kPart == 3;
+    constexpr int kBody = kPart == 0 ? kHSide : kPart == 1 ? kHSide : kPart == 2 ? kHCross : 0;
+    constexpr int kN = kBody + (kSums ? 3 : 0);
+    const int lane = threadIdx.x;
+    double acc[kN];
+#pragma unroll
+    for (int e = 0; e < kN; ++e) acc[e] = 0.0;
+    for (int64_t k = lane; k < m; k += 64) {
+        const double ui = Ui[r0 + k], vi = Ui[ldu + r0 + k], uj = Uj[r0 + k], vj = Uj[ldu + r0 + k];
+        double Yi1, Yi2, Yi3, Yj1, Yj2, Yj3;
+        h_project(hi, ui, vi, Yi1, Yi2, Yi3);
+        h_project(hj, uj, vj, Yj1, Yj2, Yj3);
+        const double ru = Yi1 / Yi3 - Yj1 / Yj3, rv = Yi2 / Yi3 - Yj2 / Yj3;
+        const double nn = ru * ru + rv * rv;
+        double w = 1.0;
+        if (delta > 0.0) {
+            const double n = sqrt(nn);
+            if (n >= delta) w = delta / n;
+        }
+        const double wru = ru * w, wrv = rv * w;
+        if constexpr (kSums) {
+            acc[kBody] = acc[kBody] + wru * wru;
+            acc[kBody] = acc[kBody] + wrv * wrv;
+            acc[kBody + 1] = acc[kBody + 1] + nn;
+            acc[kBody + 2] = acc[kBody + 2] + 1.0;
+        }
+        if constexpr (kPart == 0 || kPart == 2) {
+            HSide si;
+            h_side(ui, vi, Yi1, Yi2, Yi3, w, false, si);
+            if constexpr (kPart == 0) {
+                h_side_acc(acc, si, wru, wrv);
+            } else {
+                HSide sj;
+                h_side(uj, vj, Yj1, Yj2, Yj3, w, true, sj);
+                h_cross_acc(acc, si, sj);
+            }
+        } else if constexpr (kPart == 1) {
+            HSide sj;
+            h_side(uj, vj, Yj1, Yj2, Yj3, w, true, sj);
+            h_side_acc(acc, sj, wru, wrv);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+#pragma unroll
+        for (int e = 0; e < kN; ++e) acc[e] = acc[e] + __shfl_xor(acc[e], s);
+    }
+    if (lane != 0) return;
+    if constexpr (kPart == 0) h_side_write(acc, rec, rec + 192);
+    if constexpr (kPart == 1) h_side_write(acc, rec + 64, rec + 200);
+    if constexpr (kPart == 2) h_cross_write(acc, rec + 128);
+    if constexpr (kSums) {
+        rec[208] = acc[kBody];
+        rec[209] = acc[kBody + 1];
+        rec[210] = acc[kBody + 2];
+    }
+}
+
+// kFull: grid (n_pairs, 3), one part per wave; otherwise grid (n_pairs, 1), the sums only.  Pairs without matches are left
+// alone (the assembly skips them).  G: n_cams x 9 row-major, G[9 k + 8] = 1.
+template <bool kFull>
+__global__ __launch_bounds__(64) void ba_h_blocks_kernel(const double* __restrict__ Ui, const double* __restrict__ Uj,
+                                                        int64_t ldu, const int64_t* __restrict__ pair_ptr,
+                                                        const int* __restrict__ ij, const double* __restrict__ G, double delta,
+                                                        double* __restrict__ out) {
+    const int p = blockIdx.x;
+    const int64_t r0 = pair_ptr[p], m = pair_ptr[p + 1] - r0;
+    if (m <= 0) return;  // uniform over the wave
+    double hi[8], hj[8];
+    const double* gi = G + (int64_t)ij[2 * p] * 9;
+    const double* gj = G + (int64_t)ij[2 * p + 1] * 9;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        hi[e] = gi[e];
+        hj[e] = gj[e];
+    }
+    double* rec = out + (int64_t)p * kBaHRec;
+    if constexpr (kFull) {
+        if (blockIdx.y == 0)
+            h_pair_part<0>(hi, hj, Ui, Uj, ldu, r0, m, delta, rec);
+        else if (blockIdx.y == 1)
+            h_pair_part<1>(hi, hj, Ui, Uj, ldu, r0, m, delta, rec);
+        else
+            h_pair_part<2>(hi, hj, Ui, Uj, ldu, r0, m, delta, rec);
+    } else {
+        h_pair_part<3>(hi, hj, Ui, Uj, ldu, r0, m, delta, rec);
+    }
+}
+
+// The dense assembly of the data term, in the host mirror's order (bundleAdjustment.py, hNormalEqnsMirror): every cell of
+// H and g starts at +0.0 and takes its blocks in ascending (i, j) pair order.  Workgroup k < n_cams writes the column strip
+// of image k unless k is the seed (col_start[k] = -1): its diagonal block and g walk k's pair list (a pair with the seed
+// adds there too), an off-diagonal cell is 0.0 + x from the one pair of the two images, every other cell 0.0.  The last
+// workgroup sums the three statistics over the pairs with matches, in pair order, on one lane.
+// out = [sum (w res)^2, sum |res|^2, count | g (P) | H (P x P)].
+__global__ __launch_bounds__(256) void ba_h_assemble_kernel(const double* __restrict__ blocks, const int* __restrict__ ij,
+                                                            const int64_t* __restrict__ pair_ptr, const int* __restrict__ cam_ptr,
+                                                            const int* __restrict__ cam_list, const int* __restrict__ pair_of,
+                                                            const int* __restrict__ col_start, const int* __restrict__ blk_cam,
+                                                            int n_cams, int n_pairs, int P, double* __restrict__ out) {
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x == (int)gridDim.x - 1) {
+        if (tid == 0) {
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+            for (int p = 0; p < n_pairs; ++p) {
+                if (pair_ptr[p + 1] <= pair_ptr[p]) continue;
+                const double* o = blocks + (int64_t)p * kBaHRec;
+                s0 = s0 + o[208];
+                s1 = s1 + o[209];
+                s2 = s2 + o[210];
+            }
+            out[0] = s0;
+            out[1] = s1;
+            out[2] = s2;
+        }
+        return;
+    }
+    const int k = blockIdx.x;
+    const int c0 = col_start[k];
+    if (c0 < 0) return;
+    double* g = out + 3;
+    double* H = out + 3 + P;
+    const int q0 = cam_ptr[k], q1 = cam_ptr[k + 1];
+    if (tid < 8) {
+        double s = 0.0;
+        for (int q = q0; q < q1; ++q) {
+            const int p = cam_list[q] >> 1, role = cam_list[q] & 1;
+            if (pair_ptr[p + 1] <= pair_ptr[p]) continue;
+            s = s + blocks[(int64_t)p * kBaHRec + 192 + 8 * role + tid];
+        }
+        g[c0 + tid] = s;
+    }
+    for (int idx = tid; idx < 8 * P; idx += 256) {
+        const int b = idx / P, r = idx - b * P;
+        const int m = blk_cam[r >> 3], a = r & 7;
+        double v = 0.0;
+        if (m == k) {
+            for (int q = q0; q < q1; ++q) {
+                const int p = cam_list[q] >> 1, role = cam_list[q] & 1;
+                if (pair_ptr[p + 1] <= pair_ptr[p]) continue;
+                v = v + blocks[(int64_t)p * kBaHRec + 64 * role + a + 8 * b];
+            }
+        } else {
+            const int lo = m < k ? m : k, hi = m < k ? k : m;
+            const int p = pair_of[(int64_t)lo * n_cams + hi];
+            if (p >= 0 && pair_ptr[p + 1] > pair_ptr[p]) {
+                // Hij is (params of i) x (params of j): row a of image m = i and column b of k = j, or the transpose
+                const double x = blocks[(int64_t)p * kBaHRec + 128 + (k == hi ? a + 8 * b : b + 8 * a)];
+                v = 0.0 + x;
+            }
+        }
+        H[(int64_t)(c0 + b) * P + r] = v;
+    }
+}
+
 }  // namespace aps
 
 using namespace aps;
@@ -455,6 +770,7 @@ struct aps_ba_problem {
     int* cam_list = nullptr;              // 2 x n_pairs entries (pair << 1 | role), role 1 when k is the pair's j; pair order
     int* pair_of = nullptr;               // n_cams x n_cams: the pair of (i, j), i < j, or -1
     double* blocks = nullptr;             // n_pairs x 59
+    double* hblocks = nullptr;            // n_pairs x kBaHRec, allocated by the first aps_ba_h_normal_eqns
     // per-evaluation buffers, grown on demand: the inputs (cams base | cams lin | col_start | n_params | row_cam) and the
     // outputs (E r2sum rcnt | g | H), each with a pinned host twin so that one copy moves each way
     void* d_in = nullptr;
@@ -470,7 +786,7 @@ namespace {
 
 void ba_problem_free(aps_ba_problem* h) {
     for (void* p : {(void*)h->Ui, (void*)h->Uj, (void*)h->ptr, (void*)h->ij, (void*)h->cam_ptr, (void*)h->cam_list,
-                    (void*)h->pair_of, (void*)h->blocks, h->d_in, (void*)h->d_out})
+                    (void*)h->pair_of, (void*)h->blocks, (void*)h->hblocks, h->d_in, (void*)h->d_out})
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
     if (h->h_out) (void)hipHostFree(h->h_out);
@@ -487,6 +803,19 @@ T* dev_upload(const T* src, size_t count) {
 
 void require_host(const void* p, const char* what) {
     APS_REQUIRE(!is_device_ptr(p), APS_E_ARG, "%s must be host memory", what);
+}
+
+// a device buffer and its pinned host twin of at least `bytes`, regrown (contents dropped) when too small
+template <class T>
+void ensure_pair(T*& d, T*& host, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return;
+    if (d) (void)hipFree(d);
+    if (host) (void)hipHostFree(host);
+    d = host = nullptr;
+    cap = 0;
+    APS_HIP(hipMalloc((void**)&d, bytes));
+    APS_HIP(hipHostMalloc((void**)&host, bytes, hipHostMallocDefault));
+    cap = bytes;
 }
 
 }  // namespace
@@ -584,15 +913,7 @@ extern "C" int aps_ba_normal_eqns(aps_ba_problem* h, const double* base_cams, co
         // tile 0 .. P-1 exactly
         const size_t cam_bytes = (size_t)n * 12 * sizeof(double);
         const size_t in_bytes = 2 * cam_bytes + ((size_t)2 * n + P) * sizeof(int);
-        if (in_bytes > h->in_cap) {
-            if (h->d_in) (void)hipFree(h->d_in);
-            if (h->h_in) (void)hipHostFree(h->h_in);
-            h->d_in = h->h_in = nullptr;
-            h->in_cap = 0;
-            APS_HIP(hipMalloc(&h->d_in, in_bytes));
-            APS_HIP(hipHostMalloc(&h->h_in, in_bytes, hipHostMallocDefault));
-            h->in_cap = in_bytes;
-        }
+        ensure_pair(h->d_in, h->h_in, h->in_cap, in_bytes);
         char* hin = static_cast<char*>(h->h_in);
         int* h_cs = reinterpret_cast<int*>(hin + 2 * cam_bytes);
         int* h_np = h_cs + n;
@@ -619,15 +940,7 @@ extern "C" int aps_ba_normal_eqns(aps_ba_problem* h, const double* base_cams, co
         std::memcpy(hin, base_cams, cam_bytes);
         std::memcpy(hin + cam_bytes, lin_cams, cam_bytes);
         const size_t out_n = 3 + (want_H ? (size_t)P + (size_t)P * P : 0);
-        if (out_n > h->out_cap) {
-            if (h->d_out) (void)hipFree(h->d_out);
-            if (h->h_out) (void)hipHostFree(h->h_out);
-            h->d_out = h->h_out = nullptr;
-            h->out_cap = 0;
-            APS_HIP(hipMalloc(&h->d_out, out_n * sizeof(double)));
-            APS_HIP(hipHostMalloc(&h->h_out, out_n * sizeof(double), hipHostMallocDefault));
-            h->out_cap = out_n;
-        }
+        ensure_pair(h->d_out, h->h_out, h->out_cap, out_n * sizeof(double));
         hipStream_t st = stream();
         APS_HIP(hipMemcpyAsync(h->d_in, h->h_in, in_bytes, hipMemcpyHostToDevice, st));
         const char* din = static_cast<const char*>(h->d_in);
@@ -658,6 +971,75 @@ extern "C" int aps_ba_normal_eqns(aps_ba_problem* h, const double* base_cams, co
         stats[0] = h->h_out[0];
         // rmse = sqrt(max(R2sum, 0) / max(Rcnt, 1)) with the host mirror's max (the first argument unless the second is larger)
         stats[1] = std::sqrt((0.0 > R2 ? 0.0 : R2) / (1.0 > cnt ? 1.0 : cnt));
+        if (want_H) {
+            std::memcpy(g, h->h_out + 3, (size_t)P * sizeof(double));
+            std::memcpy(H, h->h_out + 3 + P, (size_t)P * P * sizeof(double));
+        }
+    });
+}
+
+extern "C" int aps_ba_h_normal_eqns(aps_ba_problem* h, const double* G, int n_cams, int seed, double huber, int want_H,
+                                    double* H, double* g, double* stats) {
+    return guarded([&] {
+        APS_REQUIRE(h, APS_E_ARG, "NULL problem handle");
+        APS_REQUIRE(G && stats, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(!want_H || (H && g), APS_E_ARG, "H and g are required when want_H is set");
+        APS_REQUIRE(n_cams == h->n_cams, APS_E_ARG, "n_cams = %d but the problem has %d images", n_cams, h->n_cams);
+        APS_REQUIRE(n_cams >= 2, APS_E_ARG, "the homography adjustment needs at least two images");
+        APS_REQUIRE(0 <= seed && seed < n_cams, APS_E_ARG, "seed %d outside 0 .. %d", seed, n_cams - 1);
+        APS_REQUIRE(std::isfinite(huber), APS_E_ARG, "Huber must be finite");
+        APS_REQUIRE(ctx().device == h->device, APS_E_ARG, "the problem lives on device %d, the calling thread uses %d",
+                    h->device, ctx().device);
+        require_host(G, "G");
+        for (const void* p : {(const void*)H, (const void*)g, (const void*)stats}) require_host(p, "H, g and stats");
+        const int n = n_cams;
+        for (int k = 0; k < n; ++k) APS_REQUIRE(G[9 * k + 8] == 1.0, APS_E_ARG, "G of image %d has H(3,3) != 1", k);
+        const double delta = huber > 0.0 ? huber : 0.0;  // max(0, opts.Huber)
+        const int P = 8 * (n - 1);
+        // inputs: G (n x 9) | col_start (n) | blk_cam (n - 1)
+        const size_t g_bytes = (size_t)n * 9 * sizeof(double);
+        const size_t in_bytes = g_bytes + ((size_t)2 * n - 1) * sizeof(int);
+        ensure_pair(h->d_in, h->h_in, h->in_cap, in_bytes);
+        char* hin = static_cast<char*>(h->h_in);
+        std::memcpy(hin, G, g_bytes);
+        int* h_cs = reinterpret_cast<int*>(hin + g_bytes);
+        int* h_bc = h_cs + n;
+        for (int k = 0, blk = 0; k < n; ++k) {
+            if (k == seed) {
+                h_cs[k] = -1;
+                continue;
+            }
+            h_cs[k] = 8 * blk;
+            h_bc[blk++] = k;
+        }
+        const size_t out_n = 3 + (want_H ? (size_t)P + (size_t)P * P : 0);
+        ensure_pair(h->d_out, h->h_out, h->out_cap, out_n * sizeof(double));
+        if (!h->hblocks) APS_HIP(hipMalloc(&h->hblocks, ((size_t)h->n_pairs * kBaHRec + 1) * sizeof(double)));
+        hipStream_t st = stream();
+        APS_HIP(hipMemcpyAsync(h->d_in, h->h_in, in_bytes, hipMemcpyHostToDevice, st));
+        const char* din = static_cast<const char*>(h->d_in);
+        const double* d_G = reinterpret_cast<const double*>(din);
+        const int* d_cs = reinterpret_cast<const int*>(din + g_bytes);
+        if (h->n_pairs > 0) {
+            Prof prof("ba_h_blocks");
+            if (want_H)
+                ba_h_blocks_kernel<true><<<dim3((unsigned)h->n_pairs, 3), 64, 0, st>>>(h->Ui, h->Uj, h->ldu, h->ptr, h->ij, d_G,
+                                                                                     delta, h->hblocks);
+            else
+                ba_h_blocks_kernel<false><<<dim3((unsigned)h->n_pairs, 1), 64, 0, st>>>(h->Ui, h->Uj, h->ldu, h->ptr, h->ij,
+                                                                                      d_G, delta, h->hblocks);
+        }
+        check_launch("ba_h_blocks_kernel");
+        {
+            Prof prof("ba_h_assemble");
+            ba_h_assemble_kernel<<<want_H ? (unsigned)n + 1 : 1u, 256, 0, st>>>(h->hblocks, h->ij, h->ptr, h->cam_ptr,
+                                                                                h->cam_list, h->pair_of, d_cs, d_cs + n, n,
+                                                                                h->n_pairs, P, h->d_out);
+        }
+        check_launch("ba_h_assemble_kernel");
+        APS_HIP(hipMemcpyAsync(h->h_out, h->d_out, out_n * sizeof(double), hipMemcpyDeviceToHost, st));
+        APS_HIP(hipStreamSynchronize(st));
+        std::memcpy(stats, h->h_out, 3 * sizeof(double));
         if (want_H) {
             std::memcpy(g, h->h_out + 3, (size_t)P * sizeof(double));
             std::memcpy(H, h->h_out + 3 + P, (size_t)P * P * sizeof(double));

@@ -458,6 +458,27 @@ int aps_ba_normal_eqns(aps_ba_problem* handle, const double* base_cams, const do
                        const int* n_params, int P, double sigma_huber, int both_directions, int want_H, double* H, double* g,
                        double* stats);
 
+/* The data term of bundleAdjustmentH's one-direction residualsJacobian (PP/bundleAdjustment/bundleAdjustmentH.m:282-436,
+ * computeUnidirResiduals :512-590, computeJacobianBatch :685-737) on the same resident problem: the refinement of planar
+ * sets, whose LM loop (adaptiveLM, :147-279), regulariser rows and solve stay on the host (bundleAdjustment.py).
+ * G: n_cams x 9 f64, host memory, row-major absolute homographies with G[9 k + 8] == 1 (n_cams must be the problem's).
+ * For match k of pair (i, j): Y = G_i [u v 1]', res = Y_i(1:2) / Y_i(3) - Y_j(1:2) / Y_j(3); Huber weight w = delta / |res|
+ * when |res| >= delta (else 1), delta = max(0, huber), 0 turns it off, and w multiplies res itself (as the reference
+ * does); the rows of image i are ((dY/dp) Y3 - Y (dY3/dp)) / Y3^2 * w over p = [a b c d e f g h] (row-major, H(3,3) = 1),
+ * those of image j the same formula negated.  The seed owns no columns, every other image k the 8 columns from
+ * 8 * blk(k), blk counting the non-seed images in index order: P = 8 (n_cams - 1).  Every pair with matches takes part; a
+ * pair with the seed adds to the other image's diagonal block and g only.
+ * Outputs (host memory): H = J'J dense P x P column-major, g = J'r (P), stats = {sum (w res)^2, sum |res|^2, match count}.
+ * want_H = 0: energy only (adaptiveLM's trial step, :211): no Jacobians, H and g untouched (may be NULL), the same stats bits.
+ * Bit contract: per pair every sum is 64 lane-strided partials (match k on lane k mod 64, in ascending k; per match the
+ * row u term, then the row v term) combined by an xor butterfly (offsets 32, 16, .., 1), every partial starting at +0.0;
+ * blocks assembled in ascending (i, j) pair order into cells that start at +0.0, a lone off-diagonal block written as
+ * 0.0 + x, the stats summed in pair order.  No fma.  bundleAdjustment.hNormalEqnsMirror restates it in numpy.
+ * Errors: APS_E_ARG for a NULL handle or output, a wrong n_cams (or fewer than two), a seed out of range, a non-finite
+ * huber, a G that is not host memory or has G[9 k + 8] != 1. */
+int aps_ba_h_normal_eqns(aps_ba_problem* handle, const double* G, int n_cams, int seed, double huber, int want_H, double* H,
+                         double* g, double* stats);
+
 /* SURVEY 8(f) rank 4 -- the crop rectangle of PP/imageProcessing/panoramaCropper.m:73-165: rgb2gray + imbinarize against
  * `range` (input.blackRange, or input.whiteRange with canvas_white = 1 and the mask complemented), imfill(.,'holes'), and
  * the line-by-line largest-rectangle scan (first maximum in (line, column) order, the last column never part of a
