@@ -58,13 +58,6 @@ static void bind_device(Ctx& c, int dev) {
         if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
         if (c.ev0) (void)hipEventDestroy(c.ev0);
         if (c.ev1) (void)hipEventDestroy(c.ev1);
-        // the auxiliary streams of aux_fork() and their events belong to the old device as well
-        for (auto st : c.aux) (void)hipStreamDestroy(st);
-        for (auto ev : c.aux_ev) (void)hipEventDestroy(ev);
-        if (c.fork_ev) (void)hipEventDestroy(c.fork_ev);
-        c.aux.clear();
-        c.aux_ev.clear();
-        c.fork_ev = nullptr;
         c.own_stream = nullptr;
         c.ev0 = c.ev1 = nullptr;
         c.device = dev;
@@ -100,30 +93,6 @@ Ctx& ctx() {
         APS_HIP(hipSetDevice(c.device));
     }
     return c;
-}
-
-std::vector<hipStream_t>& aux_fork(int n) {
-    Ctx& c = ctx();
-    while ((int)c.aux.size() < n) {
-        hipStream_t st = nullptr;
-        hipEvent_t ev = nullptr;
-        APS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        APS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        c.aux.push_back(st);
-        c.aux_ev.push_back(ev);
-    }
-    if (!c.fork_ev) APS_HIP(hipEventCreateWithFlags(&c.fork_ev, hipEventDisableTiming));
-    APS_HIP(hipEventRecord(c.fork_ev, c.stream()));
-    for (int i = 0; i < n; ++i) APS_HIP(hipStreamWaitEvent(c.aux[i], c.fork_ev, 0));
-    return c.aux;
-}
-
-void aux_join(int n) {
-    Ctx& c = ctx();
-    for (int i = 0; i < n && i < (int)c.aux.size(); ++i) {
-        APS_HIP(hipEventRecord(c.aux_ev[i], c.aux[i]));
-        APS_HIP(hipStreamWaitEvent(c.stream(), c.aux_ev[i], 0));
-    }
 }
 
 void* ws_alloc(size_t bytes) {

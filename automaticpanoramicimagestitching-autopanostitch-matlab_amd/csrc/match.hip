@@ -2970,19 +2970,14 @@ static void sync_q8_symmetric_switch() {
 #endif
 }
 
-static void prepare(const float* X_dev, int64_t n, int64_t ld, int layout, bool normalize,
-                    Prepared& out, hipStream_t st = nullptr, bool bracket = true, float* stat_ext = nullptr) {
-    if (!st) st = stream();
-    prepare_alloc(n, out, st, stat_ext);
+static void prepare(const float* X_dev, int64_t n, int64_t ld, int layout, bool normalize, Prepared& out) {
+    hipStream_t st = stream();
+    prepare_alloc(n, out, st, nullptr);
     float* const qstat = out.stat + 4;
     const int64_t n_pad = (std::max<int64_t>(n, 1) + kTNB - 1) / kTNB * kTNB;
     sync_q8_symmetric_switch();  // A/B switch APS_Q8_SYMMETRIC: column code without the offset
     if (n == 0) return;
-    struct MaybeProf {  // (event brackets live on the caller's own stream: a forked section is bracketed as a whole)
-        Prof* p = nullptr;
-        explicit MaybeProf(bool on) { if (on) p = new Prof("match_prep"); }
-        ~MaybeProf() { delete p; }
-    } prof(bracket);
+    Prof prof("match_prep");
     prep_desc_kernel<<<out.nb1, kPrepThreads, 0, st>>>(X_dev, n, ld, layout, normalize ? 1 : 0, out.P, out.sq, out.H, out.dn, out.part);
     prep_stats_kernel<<<1, 256, 0, st>>>(out.part, out.nb1, out.nb2, out.stat, (const unsigned short*)out.H != nullptr ? 1 : 0, 1);
     q8_desc_kernel<<<out.nb2, 256, 0, st>>>(out.P, n, out.QA, out.QB, out.dnq, out.invs, out.sumq, qstat, out.sq, out.dn, n_pad, out.stat,
@@ -3558,16 +3553,14 @@ static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, flo
             for (size_t j = 0; j < jobs.size(); ++j) seg[j] = jobs[j].out_off;
             // Round 6: the survivors of jobs that ran on exact integer codes take the exact int8 list pass (match_list_i8_kernel +
             // match_rescore_kernel), the others the f16 candidate kernel as before; each kind is pooled on its own.
-            // APS_MATCH_NO_LIST_I8=1: the f16 kernel for all (A/B).
             std::vector<unsigned int> cnt_x(jobs.size(), 0u), cnt_g(h_surv);
             size_t n_x = 0;
-            if (!std::getenv("APS_MATCH_NO_LIST_I8"))
-                for (size_t j = 0; j < jobs.size(); ++j)
-                    if (h_exact[j] && jobs[j].nB >= 1) {
-                        cnt_x[j] = h_surv[j];
-                        cnt_g[j] = 0u;
-                        n_x += h_surv[j];
-                    }
+            for (size_t j = 0; j < jobs.size(); ++j)
+                if (h_exact[j] && jobs[j].nB >= 1) {
+                    cnt_x[j] = h_surv[j];
+                    cnt_g[j] = 0u;
+                    n_x += h_surv[j];
+                }
             if (n_x > 0) {
                 Ws<unsigned int> d_cnt_x(jobs.size()), d_cnt_g(jobs.size());
                 APS_HIP(hipMemcpyAsync(d_cnt_x, cnt_x.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
@@ -3670,8 +3663,7 @@ static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, flo
     if (fwgs.empty()) return;
     // A handful of tiles, each streaming a whole B set through f32 MFMAs, leaves most of the chip idle (63 tiles of ~32
     // rows on the 64 x 4K scene: 1.5 ms): split the columns of every tile into parts and merge the parts' top-2.
-    int n_parts = 1;
-    if (!std::getenv("APS_MATCH_NO_FB_SPLIT")) n_parts = (int)std::min<size_t>(8, std::max<size_t>(1, 512 / fwgs.size()));
+    const int n_parts = (int)std::min<size_t>(8, std::max<size_t>(1, 512 / fwgs.size()));
     if (n_parts > 1) {
         std::vector<WgJob> split;
         for (const WgJob& f : fwgs) {
@@ -4399,28 +4391,14 @@ static void match_pairs_impl(const float* const* desc, const int64_t* counts, co
         (norm ? need_nrm : need_raw)[pa[p]] = 1;
         (norm ? need_nrm : need_raw)[pb[p]] = 1;
     }
-    {  // every set of the batch in four launches (prepare_batch); APS_MATCH_PREP_STREAMS=1 keeps the older form, one chain of
-       // launches per set on eight forked streams
-        constexpr int kPrepStreams = 8;
+    {  // every set of the batch in four launches (prepare_batch)
         APS_HIP(hipMemsetAsync(prep_stats, 0, (size_t)2 * kStatWords * std::max(n_img, 1) * sizeof(float), stream()));  // all sets' statistics
-        if (!std::getenv("APS_MATCH_PREP_STREAMS")) {  // round 4: every set in two launches (see prep_desc_batch_kernel)
-            std::vector<PrepRequest> req;
-            for (int i = 0; i < n_img; ++i) {
-                if (need_raw[i]) req.push_back({din[i], counts[i], ld[i], false, &raw[i], prep_stats.get() + 2 * kStatWords * i});
-                if (need_nrm[i]) req.push_back({din[i], counts[i], ld[i], true, &nrm[i], prep_stats.get() + 2 * kStatWords * i + kStatWords});
-            }
-            prepare_batch(req, layout, &prep_arena);
-        } else {
-            AuxScope fork(kPrepStreams);
-            std::vector<hipStream_t>& aux = fork.streams;
-            Prof prof("match_prep");
-            int k = 0;
-            for (int i = 0; i < n_img; ++i) {
-                if (need_raw[i]) prepare(din[i], counts[i], ld[i], layout, false, raw[i], aux[k++ % kPrepStreams], false, prep_stats.get() + 2 * kStatWords * i);
-                if (need_nrm[i]) prepare(din[i], counts[i], ld[i], layout, true, nrm[i], aux[k++ % kPrepStreams], false, prep_stats.get() + 2 * kStatWords * i + kStatWords);
-            }
-            fork.join();
+        std::vector<PrepRequest> req;
+        for (int i = 0; i < n_img; ++i) {
+            if (need_raw[i]) req.push_back({din[i], counts[i], ld[i], false, &raw[i], prep_stats.get() + 2 * kStatWords * i});
+            if (need_nrm[i]) req.push_back({din[i], counts[i], ld[i], true, &nrm[i], prep_stats.get() + 2 * kStatWords * i + kStatWords});
         }
+        prepare_batch(req, layout, &prep_arena);
     }
     const auto T1 = t_now();
     std::vector<MatchJob> jobs;

@@ -240,34 +240,6 @@ __global__ void norm_weights_kernel(Tab layers_tab, RectTab rects, int use_rects
     if (cov) cov[p] = any ? 1 : 0;
 }
 
-
-__global__ void blur_v_kernel(const float4* __restrict__ in, int h, int w, Taps tp,
-                              float4* __restrict__ out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= w) return;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = 0; t <= 2 * tp.r; ++t) {
-        const int yy = min(max(y + t - tp.r, 0), h - 1);
-        a = fma4(tp.k[t], in[(size_t)yy * w + x], a);
-    }
-    out[(size_t)y * w + x] = a;
-}
-
-__global__ void blur_h_kernel(const float4* __restrict__ in, int h, int w, Taps tp,
-                              float4* __restrict__ out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= w) return;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = 0; t <= 2 * tp.r; ++t) {
-        const int xx = min(max(x + t - tp.r, 0), w - 1);
-        a = fma4(tp.k[t], in[(size_t)y * w + xx], a);
-    }
-    out[(size_t)y * w + x] = a;
-}
-
-
 // dim 0 (rows): in h x w -> out oh x w
 __global__ void resize_rows_kernel(const float4* __restrict__ in, int h, int w, int oh,
                                    float4* __restrict__ out) {
@@ -300,40 +272,6 @@ __global__ void resize_cols_kernel(const float4* __restrict__ in, int h, int w, 
         a = fma4(wts[t], in[(size_t)y * w + xx], a);
     }
     out[(size_t)y * ow + x] = a;
-}
-
-// Num_l += (G - U) .* G.w   (multiBandBlending.m:139-144)
-__global__ void lap_accum_kernel(const float4* __restrict__ G, const float4* __restrict__ U, size_t n,
-                                 float4* __restrict__ Num) {
-    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const float4 g = G[p], u = U[p];
-    float4 a = Num[p];
-    a.x = a.x + (g.x - u.x) * g.w;
-    a.y = a.y + (g.y - u.y) * g.w;
-    a.z = a.z + (g.z - u.z) * g.w;
-    Num[p] = a;
-}
-
-// Num_L += G .* G.w   (:159)
-__global__ void coarse_accum_kernel(const float4* __restrict__ G, size_t n, float4* __restrict__ Num) {
-    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const float4 g = G[p];
-    float4 a = Num[p];
-    a.x = a.x + g.x * g.w;
-    a.y = a.y + g.y * g.w;
-    a.z = a.z + g.z * g.w;
-    Num[p] = a;
-}
-
-// F = up + Num_l   (:166)
-__global__ void add_kernel(const float4* __restrict__ A, const float4* __restrict__ B, size_t n,
-                           float4* __restrict__ out) {
-    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const float4 a = A[p], b = B[p];
-    out[p] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, 0.f);
 }
 
 __global__ void pack_layer_kernel(const float* __restrict__ C3, const float* __restrict__ W, size_t n,

@@ -379,7 +379,7 @@ __device__ __forceinline__ float4 sample_finish(const DevImage& im, const Sample
     return L.m ? make_float4(o[0], o[1], o[2], L.wa * wf) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// ---- the fast sampler of rw_warp_kernel ---------------------------------------------------------------------------
+// ---- the fast sampler of the batched warp -------------------------------------------------------------------------
 // Same projection, mask, taps and weights as sample_lut (renderPanorama.m:1089-1131), evaluated for speed instead of
 // for bit-identity with the per-tile path: the contract for warped pixels is a stated tolerance against the oracle
 // (tests: <= 2 grey levels, >= 99.95 % within one, coverage flips <= 1e-4), and the exact IEEE divisions, the u8 -> float
@@ -423,7 +423,7 @@ __device__ __forceinline__ T2 ld_pair(__amdgpu_buffer_rsrc_t rs, int voff, int s
 }
 
 // exact_ray(de): fills de with the pixel's ray as ray_from_tables computes it (called on the rare path only).
-template <bool BAND, bool BUF, class ExactRay>
+template <class ExactRay>
 __device__ __forceinline__ float4 sample_fast(const DevImage& im, const FastImage& fi, const float d[3], float angle_pow,
                                               ExactRay exact_ray) {
     const float cam0 = fmaf(d[2], im.R[6], fmaf(d[1], im.R[3], d[0] * im.R[0]));
@@ -437,15 +437,15 @@ __device__ __forceinline__ float4 sample_fast(const DevImage& im, const FastImag
     // coverage of the batched path stays that of the per-tile path bit for bit.  (About one wave in a hundred goes there.)
     const float band = 1.6e-5f * (float)max(w, h) + 4e-3f;
     float u = 0.f, v = 0.f;
-    bool exact = BAND && fabsf(cam2 - 1e-6f) < 1e-6f;
+    bool exact = fabsf(cam2 - 1e-6f) < 1e-6f;
     if (!exact) {
         if (!(cam2 > 1e-6f)) return make_float4(0.f, 0.f, 0.f, 0.f);  // behind the camera (renderPanorama.m:1112-1116)
         const float rz = fast_rcp(cam2);
         u = fmaf(im.fx * cam0, rz, im.cx);
         v = fmaf(im.fy * cam1, rz, im.cy);
-        exact = BAND && fminf(fminf(fabsf(u - 1.0f), fabsf(u - (float)w)), fminf(fabsf(v - 1.0f), fabsf(v - (float)h))) < band;
+        exact = fminf(fminf(fabsf(u - 1.0f), fabsf(u - (float)w)), fminf(fabsf(v - 1.0f), fabsf(v - (float)h))) < band;
     }
-    if (BAND && exact) {
+    if (exact) {
         float de[3], wa_;
         exact_ray(de);
         if (!project(im, de, 2.0f, u, v, wa_)) return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -461,15 +461,8 @@ __device__ __forceinline__ float4 sample_fast(const DevImage& im, const FastImag
     const int xm = min((int)u, w - 1) - 1, ym = min((int)v, h - 1) - 1;  // 0-based x0, y0 (u, v >= 1: truncation is floor)
     const float s = u - (float)(xm + 1), t = v - (float)(ym + 1);
     const int off = (ym * w + xm) * 4;
-    uint2 pa, pb;  // (x0, y0), (x1, y0) and (x0, y1), (x1, y1)
-    if (BUF) {
-        pa = ld_pair<uint2>(fi.rgba, off, 0);
-        pb = ld_pair<uint2>(fi.rgba, off, fi.row_bytes);
-    } else {
-        const uint32_t* __restrict__ r0p = im.rgba + ((size_t)ym * w + xm);
-        pa = make_uint2(r0p[0], r0p[1]);
-        pb = make_uint2(r0p[w], r0p[w + 1]);
-    }
+    const uint2 pa = ld_pair<uint2>(fi.rgba, off, 0);             // (x0, y0), (x1, y0)
+    const uint2 pb = ld_pair<uint2>(fi.rgba, off, fi.row_bytes);  // (x0, y1), (x1, y1)
     // the tent weight in closed form (DevImage::tx, ty) instead of two more table loads: lerp(wx) * lerp(wy)
     const float px = u - 1.0f, py = v - 1.0f;
     const float wf = fminf(fminf(px * im.tx[0], ((float)(w - 1) - px) * im.tx[1]), 1.0f) *
@@ -659,15 +652,13 @@ __global__ void rw_footprint_kernel(const unsigned long long* __restrict__ rowma
 // renderPanorama.m:1009-1017, then multiBandBlending.m:72-85, both in layer order) and go to the compact G_0 store
 // with their final weight: the level-0 layer is written once and the weights are never re-read for normalising.
 constexpr int kWL = 6;  // layers of a block whose samples are parked in LDS; further ones are re-sampled
-// FAST (default): sample_fast / ray_fast and reciprocal-multiplies in the two normalisations.  !FAST (APS_WARP_EXACT=1):
-// the arithmetic of the per-tile path bit for bit (IEEE divisions, u8 table, 4-tap tent products) - kept so that the
-// tests can still pin the REST of the batched pipeline (footprints, compact stores, pyramids, collapse) byte for byte
-// against render.hip's per-tile kernels.
-// V (experiment switches of the FAST form, APS_WARP_VARIANT, default 6): bit 0 = trig tables from global memory (else
-// evaluated per block into LDS), bit 1 = exact re-projection in the border band, bit 2 = buffer loads for the taps.
+// FAST (rw_warp_staged_kernel, the default): sample_fast / ray_fast and reciprocal-multiplies in the two normalisations.
+// !FAST (rw_warp_kernel, APS_WARP_EXACT=1): the arithmetic of the per-tile path bit for bit (IEEE divisions, u8 table, 4-tap
+// tent products) - kept so that the tests can still pin the REST of the batched pipeline (footprints, compact stores,
+// pyramids, collapse) byte for byte against render.hip's per-tile kernels.
 // The walking form of a block: ray once per pixel, then the tile's layers that meet the block one after the other
 // (sample -> first sum, second sum, store).  ct / rt: the pixel's column / row trig entries.
-template <bool FAST, int V>
+template <bool FAST>
 __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T, int x0, int y0, float* s_u8, float4 (*s_g)[256],
                                                 const ColTrig& ct, const RowTrig& rt) {
     const int tid = threadIdx.x;
@@ -688,7 +679,7 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
     };
     auto sample = [&](const DevImage& im) __attribute__((always_inline)) {
         if (FAST && im.w > 3 && im.h > 3)
-            return sample_fast<(V & 2) != 0, (V & 4) != 0>(im, (V & 4) ? fast_image(im) : FastImage{}, d, A.angle_pow, exact_ray);
+            return sample_fast(im, fast_image(im), d, A.angle_pow, exact_ray);
         if (FAST) {  // (an image of fewer than four rows or columns: the exact sampler on the exact ray)
             float de[3];
             exact_ray(de);
@@ -751,12 +742,10 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
     if (in_tile) A.cov[(size_t)T.plane + (size_t)y * w + x] = any ? 1 : 0;
 }
 
-template <bool FAST, int V = 7>
+// The exact form (APS_RENDER_EXACT=1 / APS_WARP_EXACT=1): the walking form on the canvas-wide trig tables (A.ct, A.rt).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_kernel(RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
-    __shared__ float s_u8[FAST ? 1 : 256];
+    __shared__ float s_u8[256];
     __shared__ float4 s_g[kWL][256];
-    __shared__ ColTrig s_ct[(V & 1) ? 1 : kUW];
-    __shared__ RowTrig s_rt[(V & 1) ? 1 : kUH];
     const int bid = xcd_contiguous_id(n_blocks);
     if (bid >= n_blocks) return;
     const int t = find_segment(blk_ptr, A.n_tiles, bid);
@@ -765,19 +754,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     const int h = T.ht, w = T.wt;
     const int local = bid - blk_ptr[t], nbx = (w + kUW - 1) / kUW;
     const int x0 = (local % nbx) * kUW, y0 = (local / nbx) * kUH;
-    if (!(V & 1)) {
-        if (tid < kUW) s_ct[tid] = col_trig(A.cv, (float)(T.c0 + min(x0 + tid, w - 1)));
-        if (tid >= 64 && tid < 64 + kUH) s_rt[tid - 64] = row_trig(A.cv, (float)(T.r0 + min(y0 + tid - 64, h - 1)));
-    }
-    if (!FAST) s_u8[tid] = (float)tid / 255.0f;
-    if (!FAST || !(V & 1)) __syncthreads();
-    const ColTrig ct = (V & 1) ? A.ct[T.c0 + min(x0 + (tid & (kUW - 1)), w - 1)] : s_ct[tid & (kUW - 1)];
-    const RowTrig rt = (V & 1) ? A.rt[T.r0 + min(y0 + tid / kUW, h - 1)] : s_rt[tid / kUW];
-    warp_block_walk<FAST, V>(A, T, x0, y0, s_u8, s_g, ct, rt);
+    s_u8[tid] = (float)tid / 255.0f;
+    __syncthreads();
+    const ColTrig ct = A.ct[T.c0 + min(x0 + (tid & (kUW - 1)), w - 1)];
+    const RowTrig rt = A.rt[T.r0 + min(y0 + tid / kUW, h - 1)];
+    warp_block_walk<false>(A, T, x0, y0, s_u8, s_g, ct, rt);
 }
 
 // ---- the warp in its staged form (default) ----------------------------------------------------------------------------
-// rw_warp_kernel<true> walks a block's layers one after the other and pays, per layer and serially, a scalar load of
+// warp_block_walk<true> walks a block's layers one after the other and pays, per layer and serially, a scalar load of
 // the entry, a dependent scalar load of the image record and a dependent gather: profiles/r03c_pmc_sq_rw_warp_fast_v7.txt
 // shows 61 % of its wave cycles waiting and no fewer vector instructions than the exact form.  Here
 //   * the layers that meet the block (<= kWF, else the walking form takes the block) are staged ONCE per block: lane j of
@@ -787,7 +772,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 //     broadcasts, (u, v, w) kept in registers (the layer loops are unrolled over kWF with uniform guards);
 //   * pass B is arithmetic on those registers; pass C gathers the four taps of the layers that cover the pixel - the
 //     only dependent memory round trip left per layer - interpolates on the raw bytes and stores with the final weight.
-// Same values as rw_warp_kernel<true> (sample_fast's arithmetic, the exact re-projection in the border band).
+// Same values as warp_block_walk<true> (sample_fast's arithmetic, the exact re-projection in the border band).
 // (Measured and dropped: culling a block's layers against the projected image outline - four corners + centre per
 // layer in phase 0, zero fill for the culled ones - instead of the footprint rectangle: the same 2.26e9 vector
 // instructions per launch, one more barrier, 5.9 -> 6.6 ms; the rectangles are tight enough on these scenes.)
@@ -874,7 +859,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (staged)
         for (int j = 0; j < nvis; ++j) small_image |= f2i(s_lc[j].q[4].w) == 0;
     if (!staged || small_image) {
-        warp_block_walk<true, 6>(A, T, x0, y0, nullptr, s_g, ct, rt);
+        warp_block_walk<true>(A, T, x0, y0, nullptr, s_g, ct, rt);
         return;
     }
     const int x = x0 + (tid & (kUW - 1)), y = y0 + tid / kUW;
@@ -2026,22 +2011,10 @@ bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int 
     if (warp_blocks) {
         Prof prof("render_warp");
         const unsigned wgrid = 8u * (unsigned)((warp_blocks + 7) / 8);
-        const char* wv = std::getenv("APS_WARP_VARIANT");  // experiment switch, see rw_warp_kernel
-        const int variant = wv ? std::atoi(wv) : 6;  // (measured: per-block LDS trig tables 6.97 ms, canvas-wide global ones 7.39)
         if (exact)
-            rw_warp_kernel<false><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else if (!wv)
-            rw_warp_staged_kernel<<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else if (variant == 6)
-            rw_warp_kernel<true, 6><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else if (variant == 5)
-            rw_warp_kernel<true, 5><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else if (variant == 3)
-            rw_warp_kernel<true, 3><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else if (variant == 0)
-            rw_warp_kernel<true, 0><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
+            rw_warp_kernel<<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
         else
-            rw_warp_kernel<true, 7><<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
+            rw_warp_staged_kernel<<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
         check_launch("rw_warp_kernel");
     }
     {

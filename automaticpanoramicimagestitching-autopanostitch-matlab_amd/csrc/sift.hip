@@ -11,7 +11,8 @@
 //   blur_kernel<R>                 : separable Gaussian, row pass then column pass fused through an LDS
 //                                    tile (reflect-101 border), both passes on v_pk_fma_f32; the blur of plane
 //                                    nl also writes the next octave's base (every second pixel) from registers.
-//   extrema_kernel                 : 26-neighbour test + Newton refinement + contrast/edge tests.
+//   extrema_wave_kernel            : 26-neighbour test of every octave in one launch, one wave per strip of columns.
+//   refine_kernel                  : Newton refinement + contrast/edge tests, one lane per candidate.
 //   orient_kernel / descr_kernel   : one 64-lane wave per keypoint, histograms in LDS (int64 atomics).
 #include <algorithm>
 #include <cmath>
@@ -519,138 +520,6 @@ __global__ __launch_bounds__(256) void blur_base_kernel(const uint8_t* __restric
     blur_tile_passes<R>(s_in, s_row, gk, x0, y0, h, w, out, nullptr, 0, 0);
 }
 
-// ---- the same blur, marching (experiment, APS_BLUR_MARCH=1; see launch_blur for the measurement) ------------------------
-// The tile kernel above fetches (kTW + 2 RP) x (kTH + 2 R) inputs for kTW x kTH outputs - 1.4x (R = 4) to 2.2x (R = 10)
-// of the plane through L2 - and row-filters the vertical halo of every tile again.  Here a workgroup owns kSW columns and
-// `ch` rows of the plane and walks down them kRS input rows at a time: the next step's rows are requested before the
-// current ones are consumed, the row pass runs on the kRS new rows only, its results live in a ring of NR rows in LDS, and
-// the column pass produces the kRS output rows whose window the ring now holds.  A chunk re-reads the 2 R rows above it;
-// nothing else is read twice.  Same chains (pk_tap, taps ascending), so the same bits as blur_kernel.
-constexpr int kSW = 128, kRS = 16;
-template <int R>
-__global__ __launch_bounds__(256) void blur_march_kernel(const float* __restrict__ in, int h, int w, GaussK gk,
-                                                         float* __restrict__ out, float* __restrict__ dec, int dh, int dw, int ch) {
-    constexpr int RP = (R + 3) & ~3, OFF = RP - R;
-    constexpr int IW = kSW + 2 * RP, NV = IW / 4;
-    constexpr int LAG = (2 * R + kRS - 1) / kRS;       // steps between a row's arrival and the output batch that ends at it
-    constexpr int NR = kRS * (LAG + 1) <= 32 ? 32 : 64;  // ring rows (a power of two >= kRS (LAG + 1))
-    static_assert(kRS * (LAG + 1) <= NR && kRS % 4 == 0, "ring");
-    constexpr int IP2 = 2 * IW + 4;   // floats per row PAIR of the interleaved input rows (see blur_kernel)
-    constexpr int RPITCH = kSW + 2;
-    static_assert((IP2 / 4) % 2 == 1, "pitch");
-    __shared__ __attribute__((aligned(16))) float s_in[(kRS / 2) * IP2];
-    __shared__ __attribute__((aligned(16))) float s_row[NR * RPITCH];
-    const int x0 = blockIdx.x * kSW, y0 = blockIdx.y * ch, y1 = min(y0 + ch, h);
-    const int tid = threadIdx.x;
-    const bool vec_ok = (w & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-    constexpr int NPF = (kRS * NV + 255) / 256;
-    float4 pf[NPF];
-    // input rows of step t: y0 - R + kRS t .. + kRS - 1 (reflected into the plane)
-    auto fetch = [&](int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < NPF; ++q) {
-            const int e = tid + 256 * q;
-            const int ec = e < kRS * NV ? e : kRS * NV - 1;
-            const int ly = ec / NV, v = ec - ly * NV;
-            const int gy = reflect101(y0 - R + kRS * t + ly, h), gx = x0 - RP + 4 * v;
-            const float* row = in + (size_t)gy * w;
-            if (vec_ok && gx >= 0 && gx + 3 < w) {
-                pf[q] = *reinterpret_cast<const float4*>(row + gx);
-            } else {
-                pf[q].x = row[reflect101(gx, w)];
-                pf[q].y = row[reflect101(gx + 1, w)];
-                pf[q].z = row[reflect101(gx + 2, w)];
-                pf[q].w = row[reflect101(gx + 3, w)];
-            }
-        }
-    };
-    const int n_batches = (y1 - y0 + kRS - 1) / kRS;  // output batches of kRS rows
-    const int n_steps = n_batches + LAG;
-    fetch(0);
-    for (int t = 0; t < n_steps; ++t) {
-        // a. park the rows of step t (row-interleaved pairs), request those of step t + 1
-#pragma unroll
-        for (int q = 0; q < NPF; ++q) {
-            const int e = tid + 256 * q;
-            if (e < kRS * NV) {
-                const int ly = e / NV, v = e - ly * NV;
-                float* dst = &s_in[(ly >> 1) * IP2 + 8 * v + (ly & 1)];
-                dst[0] = pf[q].x;
-                dst[2] = pf[q].y;
-                dst[4] = pf[q].z;
-                dst[6] = pf[q].w;
-            }
-        }
-        if (t + 1 < n_steps) fetch(t + 1);
-        __syncthreads();
-        // b. row pass on the kRS new rows: kRS / 2 row pairs x kSW / 8 segments of 8 outputs -> ring rows kRS t ...
-        for (int u = tid; u < (kRS / 2) * (kSW / 8); u += 256) {
-            const int seg = u / (kRS / 2), p = u - seg * (kRS / 2), xb = seg * 8;
-            const f32x2* src = reinterpret_cast<const f32x2*>(&s_in[p * IP2 + 2 * (OFF + xb)]);
-            f32x2 v[8 + 2 * R], acc[8];
-#pragma unroll
-            for (int j = 0; j < 8 + 2 * R; ++j) v[j] = src[j];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] = f32x2{0.f, 0.f};
-            static_for<0, 2 * R + 1>([&](auto T) {
-                constexpr int tt = decltype(T)::value;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pk_tap<tt>(acc[j], gk, v[j + tt]);
-            });
-            const int rel = kRS * t + 2 * p;  // input row index relative to y0 - R
-            float* d0 = &s_row[(rel & (NR - 1)) * RPITCH + xb];
-            float* d1 = &s_row[((rel + 1) & (NR - 1)) * RPITCH + xb];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                d0[j] = acc[j].x;
-                d1[j] = acc[j].y;
-            }
-        }
-        __syncthreads();
-        // c. column pass for output batch k = t - LAG: output row y0 + o reads ring rows o .. o + 2 R
-        const int k = t - LAG;
-        if (k >= 0) {
-            const int u = tid;  // 64 column pairs x kRS / 4 groups of 4 rows = 256 work items
-            const int lx = 2 * (u & (kSW / 2 - 1)), yb = kRS * k + (u / (kSW / 2)) * 4;
-            f32x2 v[4 + 2 * R], acc[4];
-#pragma unroll
-            for (int j = 0; j < 4 + 2 * R; ++j) v[j] = *reinterpret_cast<const f32x2*>(&s_row[((yb + j) & (NR - 1)) * RPITCH + lx]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = f32x2{0.f, 0.f};
-            static_for<0, 2 * R + 1>([&](auto T) {
-                constexpr int tt = decltype(T)::value;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pk_tap<tt>(acc[j], gk, v[j + tt]);
-            });
-            const int gx = x0 + lx;
-            if (gx + 1 < w && (w & 1) == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int gy = y0 + yb + j;
-                    if (gy < y1) *reinterpret_cast<f32x2*>(&out[(size_t)gy * w + gx]) = acc[j];
-                }
-            } else if (gx < w) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int gy = y0 + yb + j;
-                    if (gy < y1) {
-                        out[(size_t)gy * w + gx] = acc[j].x;
-                        if (gx + 1 < w) out[(size_t)gy * w + gx + 1] = acc[j].y;
-                    }
-                }
-            }
-            if (dec && (gx >> 1) < dw) {  // gx, y0 + yb are even (ch and kRS are)
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const int gy = y0 + yb + j, dy = gy >> 1;
-                    if (gy < y1 && dy < dh) dec[(size_t)dy * dw + (gx >> 1)] = acc[j].x;
-                }
-            }
-        }
-        __syncthreads();  // the next step parks into s_in and writes ring rows this one has read
-    }
-}
-
 // generic fallback for unusual radii: two plain passes through global memory (same arithmetic)
 __global__ void blur_row_generic(const float* __restrict__ in, int h, int w, GaussK gk, float* __restrict__ out) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -775,129 +644,6 @@ __device__ bool adjust_extremum(const OctaveDesc& od, int nl, int o, int layer, 
     kp.contr = fabsf(contr);
     return true;
 }
-
-// 128 x 8 pixel tile per 256-thread workgroup; all nl+2 DoG planes of the tile (plus a 1-pixel halo) are staged
-// in LDS once, so every plane is read from HBM ~1.3x instead of 27x per layer through the caches.  Tile shapes
-// measured on one 4K view (us per view, all octaves): 32x24 573, 64x16 437, 64x12 420, 128x4 454, 128x8 405, 256x4 403,
-// 128x12 416, 128x16 523, 256x8 535 - the rows a workgroup reads should be long, the LDS tile small enough for several
-// workgroups per CU.
-#ifndef APS_EH
-#define APS_EH 8
-#endif
-#ifndef APS_EW
-#define APS_EW 128
-#endif
-constexpr int kEW = APS_EW, kEH = APS_EH, kEGroups = 256 / kEW, kERows = kEH / kEGroups;  // rows of a column owned by one thread
-static_assert(kEH % kEGroups == 0 && 256 % kEW == 0, "row groups");
-
-template <int nl>  // NumLayersInOctave: nl + 3 Gaussian planes, nl + 2 DoG planes (sizes the LDS tile and the loops)
-__global__ __launch_bounds__(256) void extrema_kernel(OctaveDesc od, int o, float thr,
-                                                      unsigned long long* __restrict__ cells,
-                                                      unsigned int* __restrict__ count, unsigned int cap) {
-    // LDS rows hold pixels x0-4 .. x0+kEW+3 (the 1-pixel halo rounded out to 16-byte pieces; pitch TW)
-    constexpr int TW = kEW + 8, TH = kEH + 2, NV = TW / 4, HX = 3;  // HX: LDS column of pixel x0-1
-    constexpr int NG = nl + 3, ND = nl + 2;
-    __shared__ __attribute__((aligned(16))) float s_d[ND][TH * TW];
-    const int w = od.w, h = od.h;
-    const int x0 = blockIdx.x * kEW, y0 = blockIdx.y * kEH;
-    const int tid = threadIdx.x;
-    // DoG planes of the tile, formed here from the nl + 3 Gaussian planes (they are not stored anywhere)
-    const bool vec_ok = (w & 3) == 0;
-    for (int e = tid; e < TH * NV; e += 256) {
-        const int ly = e / NV, v = e - ly * NV;
-        const int gy = min(max(y0 + ly - 1, 0), h - 1), gx = x0 - 4 + 4 * v;
-        const size_t rowoff = (size_t)gy * w;
-        // All plane loads are issued back to back (planes beyond nl + 3 re-read plane 0 and are ignored): with an
-        // early exit between the loads the compiler waits for each one before testing the next, and the seven
-        // round trips in series made this kernel latency-bound (83 % of its wave cycles sat in s_waitcnt).
-        if (vec_ok && gx >= 0 && gx + 3 < w) {
-            float4 g[NG];
-#pragma unroll
-            for (int p = 0; p < NG; ++p) g[p] = *reinterpret_cast<const float4*>(od.G[p] + rowoff + gx);
-#pragma unroll
-            for (int p = 0; p < ND; ++p)
-                *reinterpret_cast<float4*>(&s_d[p][ly * TW + 4 * v]) =
-                    make_float4(g[p + 1].x - g[p].x, g[p + 1].y - g[p].y, g[p + 1].z - g[p].z, g[p + 1].w - g[p].w);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const size_t off = rowoff + min(max(gx + q, 0), w - 1);
-                float g[NG];
-#pragma unroll
-                for (int p = 0; p < NG; ++p) g[p] = od.G[p][off];
-#pragma unroll
-                for (int p = 0; p < ND; ++p) s_d[p][ly * TW + 4 * v + q] = g[p + 1] - g[p];
-            }
-        }
-    }
-    __syncthreads();
-    // thread (lx, g) owns column lx and the kERows consecutive rows kERows g .. of the tile.  Per plane: the
-    // horizontal 3-max/3-min of the kERows + 2 rows it touches, then the vertical 3-max/3-min per owned pixel = the
-    // 3x3 window extrema (centre included).  A pixel is a 26-neighbour maximum iff val >= the max of the three
-    // planes' window maxima (val itself is inside its own window, which changes nothing).
-    const int lx = tid % kEW, g = tid / kEW;
-    const int c = x0 + lx;
-    // Candidates are collected per workgroup in LDS and appended with ONE global atomic: at the octaves where the
-    // texture lives, tens of thousands of single-address atomics serialised in L2 (the 2 MPix octave took 110 us against
-    // 24 us without candidates, longer than the 8 MPix octave).  The order of the cells is irrelevant: they are sorted
-    // into the canonical keypoint order later.
-    constexpr int kLocalCap = 192;  // (1024 cost a fourth workgroup per CU: 44.5 KB of LDS against 38)
-    __shared__ unsigned long long s_cells[kLocalCap];
-    __shared__ unsigned int s_n, s_base;
-    if (tid == 0) s_n = 0u;
-    __syncthreads();
-    const bool col_ok = c >= kBorder && c < w - kBorder;
-    // The window extrema of three consecutive planes are live at a time (plane p in slot p % 3): layer p - 1 is tested
-    // as soon as plane p's are known.
-    float wmax[3][kERows], wmin[3][kERows];
-#pragma unroll
-    for (int p = 0; p < ND; ++p) {
-        float hmx[kERows + 2], hmn[kERows + 2];
-#pragma unroll
-        for (int rr = 0; rr < kERows + 2; ++rr) {
-            const float* row = &s_d[p][(kERows * g + rr) * TW + lx + HX];
-            hmx[rr] = fmaxf(fmaxf(row[0], row[1]), row[2]);
-            hmn[rr] = fminf(fminf(row[0], row[1]), row[2]);
-        }
-#pragma unroll
-        for (int k = 0; k < kERows; ++k) {
-            wmax[p % 3][k] = fmaxf(fmaxf(hmx[k], hmx[k + 1]), hmx[k + 2]);
-            wmin[p % 3][k] = fminf(fminf(hmn[k], hmn[k + 1]), hmn[k + 2]);
-        }
-        if (p < 2) continue;
-        const int layer = p - 1;
-#pragma unroll
-        for (int k = 0; k < kERows; ++k) {
-            const int ry = kERows * g + k;
-            const int r = y0 + ry;
-            if (!col_ok || r < kBorder || r >= h - kBorder) continue;
-            const float val = s_d[layer][(ry + 1) * TW + lx + HX + 1];
-            if (!(fabsf(val) > thr)) continue;
-            const float mx = fmaxf(fmaxf(wmax[0][k], wmax[1][k]), wmax[2][k]);
-            const float mn = fminf(fminf(wmin[0][k], wmin[1][k]), wmin[2][k]);
-            const bool is_max = val > 0 && val >= mx, is_min = val < 0 && val <= mn;
-            if (!(is_max || is_min)) continue;
-            const unsigned long long cell = ((unsigned long long)o << 40) | ((unsigned long long)layer << 32) |
-                                            ((unsigned long long)r << 16) | (unsigned long long)c;
-            const unsigned int local = atomicAdd(&s_n, 1u);
-            if (local < (unsigned)kLocalCap) {
-                s_cells[local] = cell;
-            } else {  // more candidates than the local list holds (a degenerate tile): append directly
-                const unsigned int slot = atomicAdd(count, 1u);
-                if (slot < cap) cells[slot] = cell;
-            }
-        }
-    }
-    __syncthreads();
-    const unsigned int n_loc = min(s_n, (unsigned)kLocalCap);
-    if (n_loc == 0u) return;
-    if (tid == 0) s_base = atomicAdd(count, n_loc);
-    __syncthreads();
-    for (unsigned int e = tid; e < n_loc; e += 256) {
-        const unsigned int slot = s_base + e;
-        if (slot < cap) cells[slot] = s_cells[e];
-    }
-}
 #undef AT
 
 // ---- sort / dedupe helpers ---------------------------------------------------------------------------
@@ -929,147 +675,16 @@ struct PyrTable {
     float sigma;
 };
 
-// ---- the same sweep, marching (default) -----------------------------------------------------------------------------
-// scripts/probe/mem_pattern.hip: the seven planes of octave 0 stream at 6.1 TB/s read linearly, at 4.0 TB/s (useful
-// bytes) through 128 x 8 tiles with their halo, at 6.2 TB/s through 512-wide strips marched top to bottom - the tiles
-// were not slow, they re-read a third of their pixels as halo, and the LDS that holds all DoG planes of a tile kept them
-// from growing.  Here a workgroup owns a strip of kMI columns and CH rows of one octave and walks down it four rows at
-// a time: the next step's seven float4 per thread are requested before the current step is consumed, the DoG rows live
-// in a six-row ring in LDS (the two rows carried over + the four new ones), and a pixel is read ~1.05 times.  Every
-// octave of the image is swept by ONE launch (block table in ExtremaPlan).  Same window logic as extrema_kernel, same
-// cells (their order is irrelevant: they are sorted into the canonical keypoint order later).
-constexpr int kMW = 256;      // columns a workgroup loads per row: 64 float4, the outer four on each side are halo
-constexpr int kMI = kMW - 8;  // columns it owns
-struct ExtremaPlan {
-    int blk_ptr[17];  // first workgroup of octave o
-    int nstrip[16];   // strips per row of chunks
-    int ch[16];       // rows per chunk (multiple of 4)
-};
-
-template <int nl>
-__global__ __launch_bounds__(256) void extrema_march_kernel(const PyrTable* __restrict__ pt, ExtremaPlan plan, float thr,
-                                                            unsigned long long* __restrict__ cells,
-                                                            unsigned int* __restrict__ count, unsigned int cap) {
-    constexpr int NG = nl + 3, ND = nl + 2, RING = 6, TW = kMW;
-    __shared__ __attribute__((aligned(16))) float s_d[ND][RING * TW];
-    constexpr int kLocalCap = 256;
-    __shared__ unsigned long long s_cells[kLocalCap];
-    __shared__ unsigned int s_n, s_base;
-    int o = 0;
-    while (o < 15 && (int)blockIdx.x >= plan.blk_ptr[o + 1]) ++o;
-    const OctaveDesc& od = pt->oct[o];
-    const int w = od.w, h = od.h;
-    const int local = (int)blockIdx.x - plan.blk_ptr[o];
-    const int strip = local % plan.nstrip[o], chunk = local / plan.nstrip[o];
-    const int x0 = strip * kMI - 4, y0 = chunk * plan.ch[o], y1 = min(y0 + plan.ch[o], h);
-    const int tid = threadIdx.x;
-    if (tid == 0) s_n = 0u;
-    const __attribute__((address_space(1))) float* G[NG];
-#pragma unroll
-    for (int p = 0; p < NG; ++p) G[p] = (const __attribute__((address_space(1))) float*)od.G[p];
-    const int lx4 = tid & 63, lr = tid >> 6;
-    const int gx = x0 + 4 * lx4;
-    const bool vec = (w & 3) == 0 && gx >= 0 && gx + 3 < w;
-    auto fetch = [&](int row, float4 g[NG]) __attribute__((always_inline)) {
-        const size_t rowoff = (size_t)min(max(row, 0), h - 1) * w;
-        if (vec) {
-#pragma unroll
-            for (int p = 0; p < NG; ++p) {
-                typedef float f32x4g __attribute__((ext_vector_type(4)));
-                const f32x4g v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4g*>(G[p] + rowoff + gx);
-                g[p] = make_float4(v.x, v.y, v.z, v.w);
-            }
-        } else {
-            const size_t o0 = rowoff + min(max(gx, 0), w - 1), o1 = rowoff + min(max(gx + 1, 0), w - 1);
-            const size_t o2 = rowoff + min(max(gx + 2, 0), w - 1), o3 = rowoff + min(max(gx + 3, 0), w - 1);
-#pragma unroll
-            for (int p = 0; p < NG; ++p) g[p] = make_float4(G[p][o0], G[p][o1], G[p][o2], G[p][o3]);
-        }
-    };
-    auto park = [&](int row, const float4 g[NG]) __attribute__((always_inline)) {
-        const int slot = (row - (y0 - 1)) % RING;
-#pragma unroll
-        for (int p = 0; p < ND; ++p)
-            *reinterpret_cast<float4*>(&s_d[p][slot * TW + 4 * lx4]) =
-                make_float4(g[p + 1].x - g[p].x, g[p + 1].y - g[p].y, g[p + 1].z - g[p].z, g[p + 1].w - g[p].w);
-    };
-    float4 g[NG];
-    if (lr < 2) {  // the two rows above the first step
-        fetch(y0 - 1 + lr, g);
-        park(y0 - 1 + lr, g);
-    }
-    fetch(y0 + 1 + lr, g);
-    const int lx = tid, c = x0 + lx;
-    const int lxc = min(max(lx, 1), kMW - 2);  // (the outermost halo lanes own nothing; keep their reads inside the row)
-    const bool col_ok = lx >= 4 && lx < kMW - 4 && c >= kBorder && c < w - kBorder;
-    for (int ys = y0; ys < y1; ys += 4) {
-        park(ys + 1 + lr, g);                    // rows ys+1 .. ys+4
-        if (ys + 4 < y1) fetch(ys + 5 + lr, g);  // the next step's rows: in flight while this step is consumed
-        __syncthreads();
-        const int base = (ys - y0) % RING;  // ring slot of row ys-1
-        float wmax[3][4], wmin[3][4];
-#pragma unroll
-        for (int p = 0; p < ND; ++p) {
-            float hmx[6], hmn[6];
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr) {
-                int slot = base + rr;
-                slot = slot >= RING ? slot - RING : slot;
-                const float* row = &s_d[p][slot * TW + lxc - 1];
-                hmx[rr] = fmaxf(fmaxf(row[0], row[1]), row[2]);
-                hmn[rr] = fminf(fminf(row[0], row[1]), row[2]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                wmax[p % 3][k] = fmaxf(fmaxf(hmx[k], hmx[k + 1]), hmx[k + 2]);
-                wmin[p % 3][k] = fminf(fminf(hmn[k], hmn[k + 1]), hmn[k + 2]);
-            }
-            if (p < 2) continue;
-            const int layer = p - 1;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = ys + k;
-                if (!col_ok || r >= y1 || r < kBorder || r >= h - kBorder) continue;
-                int slot = base + k + 1;
-                slot = slot >= RING ? slot - RING : slot;
-                const float val = s_d[layer][slot * TW + lx];
-                if (!(fabsf(val) > thr)) continue;
-                const float mx = fmaxf(fmaxf(wmax[0][k], wmax[1][k]), wmax[2][k]);
-                const float mn = fminf(fminf(wmin[0][k], wmin[1][k]), wmin[2][k]);
-                const bool is_max = val > 0 && val >= mx, is_min = val < 0 && val <= mn;
-                if (!(is_max || is_min)) continue;
-                const unsigned long long cell = ((unsigned long long)o << 40) | ((unsigned long long)layer << 32) |
-                                                ((unsigned long long)r << 16) | (unsigned long long)c;
-                const unsigned int loc = atomicAdd(&s_n, 1u);
-                if (loc < (unsigned)kLocalCap) {
-                    s_cells[loc] = cell;
-                } else {
-                    const unsigned int slot2 = atomicAdd(count, 1u);
-                    if (slot2 < cap) cells[slot2] = cell;
-                }
-            }
-        }
-        __syncthreads();  // the next step parks into the slots this one has read
-    }
-    const unsigned int n_loc = min(s_n, (unsigned)kLocalCap);
-    if (n_loc == 0u) return;
-    if (tid == 0) s_base = atomicAdd(count, n_loc);
-    __syncthreads();
-    for (unsigned int e = tid; e < n_loc; e += 256) {
-        const unsigned int slot = s_base + e;
-        if (slot < cap) cells[slot] = s_cells[e];
-    }
-}
-
-// ---- the same sweep, one wave per strip, rows in registers (round 5, the default) ---------------------------------------------
-// extrema_march_kernel's counters (profiles/r04d_pmc_extrema.txt): 61 M vector, 54 M scalar and 16 M LDS wave-instructions per
-// 4K view, two barriers per four rows, four workgroups per CU - three pipes a third busy each and chained by the barriers; it
-// streamed at 2.9 TB/s.  Here nothing is shared between waves: a wave owns a strip of 128 columns (lane l: columns x0 + 2 l and
-// x0 + 2 l + 1, the two outer lanes are halo) and walks down its chunk of rows.  Per arriving row a lane subtracts its 2 x (nl + 2)
-// DoG values, takes the horizontal 3-max / 3-min with its neighbours' edge values through DPP (wave_shr / wave_shl, no LDS), keeps
-// those for the last three rows in registers (slots rotate by a 3x unrolled loop), and tests the centre row.  The loads of the
-// row three steps ahead are in flight while a row is consumed.  No LDS traffic but the rare cell records, no barrier.  Same
-// window logic, same cells (their order is irrelevant: they are sorted into the canonical keypoint order later).
+// ---- extrema sweep: every octave in one launch, one wave per strip, rows in registers ----------------------------------------
+// 26-neighbour extrema of the DoG stack.  The sweep is a stream: 2-D tiles re-read a third of their pixels as halo
+// (scripts/probe/mem_pattern.hip), and a workgroup marching down a strip through an LDS ring (rounds 3-4, profiles/r04d_pmc_extrema.txt)
+// kept three pipes a third busy each, chained by two barriers per four rows.  Here nothing is shared between waves: a wave owns a
+// strip of 128 columns (lane l: columns x0 + 2 l and x0 + 2 l + 1, the two outer lanes are halo) and walks down its chunk of rows
+// (job table in ExtremaWavePlan).  Per arriving row a lane subtracts its 2 x (nl + 2) DoG values, takes the horizontal 3-max /
+// 3-min with its neighbours' edge values through DPP (wave_shr / wave_shl, no LDS), keeps those for the last three rows in registers
+// (slots rotate by a 3x unrolled loop), and tests the centre row.  The loads of the row three steps ahead are in flight while a row
+// is consumed.  No LDS traffic but the rare cell records, no barrier.  The order of the cells is irrelevant: they are sorted into
+// the canonical keypoint order later.
 constexpr int kWS = 124;     // columns a wave owns (64 lanes x 2 - 4)
 constexpr int kWCells = 256; // cell records a wave parks in LDS before they go to the global list
 struct ExtremaWavePlan {
@@ -1361,7 +976,7 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
                                                     const OrientedKp* __restrict__ oks, unsigned int n_out,
                                                     float* __restrict__ desc, int desc_layout, int64_t ldd,
                                                     double* __restrict__ loc, int64_t ldl,
-                                                    float* __restrict__ aux, int plain_sweep) {
+                                                    float* __restrict__ aux) {
     __shared__ unsigned long long s_hist[4][kHistLen];
     __shared__ __attribute__((aligned(16))) float s_raw[4][128];
     __shared__ int s_queue[4][kDescQueue];  // per wave: samples that passed the window test, (i << 16) | (j & 0xffff)
@@ -1497,7 +1112,7 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
         // (|sin| or |cos| below 1e-4 of the scaled units: the estimate's error in j, ~5e-6 / |a|, must stay far below the
         // two-integer search range).  Then every row's samples are queued without any test, 64 to an instruction.  Same set
         // of samples, hence the same histogram bits.
-        bool plain = plain_sweep != 0 || radius > 63 || fabsf(sin_t) < 1e-4f || fabsf(cos_t) < 1e-4f;  // (plain_sweep: APS_DESCR_PLAIN=1, A/B)
+        bool plain = radius > 63 || fabsf(sin_t) < 1e-4f || fabsf(cos_t) < 1e-4f;
         int jl_[2] = {0, 0}, len_[2] = {0, 0};
         if (!plain) {
             bool bad = false;
@@ -1670,39 +1285,8 @@ static bool launch_blur(const float* in, int h, int w, double sigma, float* out,
     const int r = gk.n / 2;
     Prof prof("sift_blur");
     const dim3 grid(cdiv(w, kTW), cdiv(h, kTH));
-    // The marching form (APS_BLUR_MARCH=1) is an experiment that did NOT pay: bit-identical, but 66 / 75 / 109 us per
-    // 33 MPix plane at R = 4 / 5 / 10 against the tile kernel's 60 / 60 / 83 (profiles/r03f_sift_trace.txt).  Unlike the
-    // extrema sweep the blur is not a pure stream: at R = 10 its 42 fma per output and ~1.5 GB of LDS traffic per plane
-    // already cost what the memory system does, and the march adds three barriers per 16 rows with only 3-6 workgroups
-    // per CU to cover them.
-    static const bool march = std::getenv("APS_BLUR_MARCH") != nullptr;
-    if (march && r >= 1 && r <= 12 && h >= 64 && w >= kSW) {
-        const int strips = cdiv(w, kSW);
-        int ch = (int)(((long long)h * strips + 1023) / 1024);  // about a thousand workgroups on the large planes
-        ch = std::max(4 * kRS, (ch + kRS - 1) / kRS * kRS);
-        const dim3 mg(strips, cdiv(h, ch));
-        switch (r) {
-#define APS_BLUR_CASE(R) \
-    case R:              \
-        blur_march_kernel<R><<<mg, 256, 0, stream()>>>(in, h, w, gk, out, dec, dh, dw, ch); \
-        break;
-            APS_BLUR_CASE(1)
-            APS_BLUR_CASE(2)
-            APS_BLUR_CASE(3)
-            APS_BLUR_CASE(4)
-            APS_BLUR_CASE(5)
-            APS_BLUR_CASE(6)
-            APS_BLUR_CASE(7)
-            APS_BLUR_CASE(8)
-            APS_BLUR_CASE(9)
-            APS_BLUR_CASE(10)
-            APS_BLUR_CASE(11)
-            APS_BLUR_CASE(12)
-#undef APS_BLUR_CASE
-        }
-        check_launch("blur_march_kernel");
-        return dec != nullptr;
-    }
+    // (Measured and dropped, round 3: a marching form with a ring of row-filtered rows in LDS - bit-identical, 66 / 75 / 109 us
+    // per 33 MPix plane at R = 4 / 5 / 10 against 60 / 60 / 83: profiles/r03f_sift_trace_march_blur.txt.)
     // (Measured and dropped, round 5: one wave per 128-column strip marching down its rows with the row-pass results of the last
     // 2R + 2 rows in registers - no barrier, no halo rows recomputed, 0.55 instead of 0.93 wave-instructions per pixel at
     // R = 10, bit-identical - read 59 / 61 / 66 / 94 / 92 / 101 us per octave-0 plane at R = 4 / 5 / 6 / 7 / 8 / 10 against
@@ -1744,13 +1328,8 @@ static bool launch_blur(const float* in, int h, int w, double sigma, float* out,
 }
 
 // gray + 2x upsample + first blur in one kernel (blur_base_kernel); false when the radius has no tile instantiation (the
-// caller then takes gray_up_kernel + launch_blur).  APS_SIFT_NO_BASE_FUSE=1 forces that two-kernel path (same bits).
+// caller then takes gray_up_kernel + launch_blur, same bits).
 static bool launch_base_blur(const uint8_t* img, int sh, int sw, int c, int layout, double sigma, float* out, Ws<uint8_t>& gray) {
-    static const bool off = [] {
-        const char* e = std::getenv("APS_SIFT_NO_BASE_FUSE");
-        return e && e[0] == '1';
-    }();
-    if (off) return false;
     const GaussK gk = make_gauss(sigma);
     const int r = (gk.n - 1) / 2;
     if (r < 3 || r > 8) return false;
@@ -1932,7 +1511,7 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
                 dbg::g_stat[dbg::kPyrChanged]++;
         }
 #endif
-        // extrema: detection sweep per octave -> packed cells; then one dense refinement launch
+        // extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch
         Ws<PyrTable> d_table(1);
         APS_HIP(hipMemcpyAsync(d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
         const unsigned int cand_cap = (unsigned int)std::min<size_t>(
@@ -1952,107 +1531,58 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
 #endif
         for (int attempt = 0; attempt < 2; ++attempt) {
             APS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), stream()));
-            if (!std::getenv("APS_EXTREMA_TILES") && !std::getenv("APS_EXTREMA_MARCH")) {
-                // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
-                ExtremaWavePlan plan;
-                std::memset(&plan, 0, sizeof plan);
-                static const int ch_env = std::getenv("APS_EXTREMA_CH") ? std::atoi(std::getenv("APS_EXTREMA_CH")) : 0;
-                int run = 0;
-                for (int o = 0; o < 16; ++o) {
-                    plan.job_ptr[o] = run;
-                    plan.nstrip[o] = plan.ch[o] = 1;
-                    if (o >= n_oct) continue;
-                    const OctaveDesc& od = table.oct[o];
-                    if (od.w <= 2 * kBorder || od.h <= 2 * kBorder) continue;
-                    const int ns = cdiv(od.w, kWS);
-                    // rows per chunk (every chunk re-reads two halo rows): ~8000 wave jobs on the largest octave, >= 24 rows
-                    int ch = (int)(((long long)od.h * ns + 8191) / 8192);
-                    ch = std::max(24, ch);
-                    if (ch_env > 0) ch = ch_env;
-                    plan.nstrip[o] = ns;
-                    plan.ch[o] = ch;
-                    run += ns * cdiv(od.h, ch);
-                }
-                plan.job_ptr[16] = run;
-                if (run > 0) {
-                    Prof prof("sift_extrema");
-                    const int wgs = cdiv(run, 4);
-                    auto launch_sweep = [&](unsigned long long* cl, unsigned int* ct) {
-                        switch (nl) {
-                            case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                            case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                            case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                            case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                            default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                        }
-                    };
-                    launch_sweep(cells, d_count);
-                    check_launch("extrema_wave_kernel");
-#ifdef APS_DBG
-                    if (dbg_replay > 0) {
-                        Ws<unsigned long long> cells2(cells_cap);
-                        Ws<unsigned int> cnt2(2);
-                        unsigned int n1 = 0, n2 = 0;
-                        APS_HIP(hipMemcpyAsync(&n1, d_count, 4, hipMemcpyDeviceToHost, stream()));
-                        APS_HIP(hipStreamSynchronize(stream()));
-                        const unsigned long long c1 = dbg::cks(cells.get(), std::min(n1, cells_cap), 2, 0, dbg_slot);
-                        for (int rep = 0; rep < dbg_replay; ++rep) {
-                            APS_HIP(hipMemsetAsync(cnt2, 0, 8, stream()));
-                            launch_sweep(cells2, cnt2);
-                            APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
-                            APS_HIP(hipStreamSynchronize(stream()));
-                            const unsigned long long c2 = dbg::cks(cells2.get(), std::min(n2, cells_cap), 2, 0, dbg_slot);
-                            dbg::g_stat[dbg::kExtReplays]++;
-                            if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kExtDiff]++;
-                        }
-                    }
-#endif
-                }
-            } else if (!std::getenv("APS_EXTREMA_TILES")) {
-                // one marching launch over all octaves (extrema_march_kernel; APS_EXTREMA_MARCH=1, rounds 3-4)
-                ExtremaPlan plan;
-                std::memset(&plan, 0, sizeof plan);
-                int run = 0;
-                for (int o = 0; o < 16; ++o) {
-                    plan.blk_ptr[o] = run;
-                    plan.nstrip[o] = plan.ch[o] = 1;
-                    if (o >= n_oct) continue;
-                    const OctaveDesc& od = table.oct[o];
-                    if (od.w <= 2 * kBorder || od.h <= 2 * kBorder) continue;
-                    const int ns = cdiv(od.w, kMI);
-                    // rows per chunk: about a thousand workgroups for the large octaves, never fewer than 16 rows
-                    int ch = (int)(((long long)od.h * ns + 1023) / 1024);
-                    ch = std::max(16, (ch + 3) & ~3);
-                    plan.nstrip[o] = ns;
-                    plan.ch[o] = ch;
-                    run += ns * cdiv(od.h, ch);
-                }
-                plan.blk_ptr[16] = run;
-                if (run > 0) {
-                    Prof prof("sift_extrema");
-                    switch (nl) {
-                        case 1: extrema_march_kernel<1><<<run, 256, 0, stream()>>>(d_table, plan, thr, cells, d_count, cells_cap); break;
-                        case 2: extrema_march_kernel<2><<<run, 256, 0, stream()>>>(d_table, plan, thr, cells, d_count, cells_cap); break;
-                        case 3: extrema_march_kernel<3><<<run, 256, 0, stream()>>>(d_table, plan, thr, cells, d_count, cells_cap); break;
-                        case 4: extrema_march_kernel<4><<<run, 256, 0, stream()>>>(d_table, plan, thr, cells, d_count, cells_cap); break;
-                        default: extrema_march_kernel<5><<<run, 256, 0, stream()>>>(d_table, plan, thr, cells, d_count, cells_cap); break;
-                    }
-                    check_launch("extrema_march_kernel");
-                }
-            } else
-            for (int o = 0; o < n_oct; ++o) {
+            // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
+            ExtremaWavePlan plan;
+            std::memset(&plan, 0, sizeof plan);
+            int run = 0;
+            for (int o = 0; o < 16; ++o) {
+                plan.job_ptr[o] = run;
+                plan.nstrip[o] = plan.ch[o] = 1;
+                if (o >= n_oct) continue;
                 const OctaveDesc& od = table.oct[o];
                 if (od.w <= 2 * kBorder || od.h <= 2 * kBorder) continue;
+                const int ns = cdiv(od.w, kWS);
+                // rows per chunk (every chunk re-reads two halo rows): ~8000 wave jobs on the largest octave, >= 24 rows
+                int ch = (int)(((long long)od.h * ns + 8191) / 8192);
+                ch = std::max(24, ch);
+                plan.nstrip[o] = ns;
+                plan.ch[o] = ch;
+                run += ns * cdiv(od.h, ch);
+            }
+            plan.job_ptr[16] = run;
+            if (run > 0) {
                 Prof prof("sift_extrema");
-                const dim3 eg(cdiv(od.w, kEW), cdiv(od.h, kEH));
-                switch (nl) {
-                    case 1: extrema_kernel<1><<<eg, 256, 0, stream()>>>(od, o, thr, cells, d_count, cells_cap); break;
-                    case 2: extrema_kernel<2><<<eg, 256, 0, stream()>>>(od, o, thr, cells, d_count, cells_cap); break;
-                    case 3: extrema_kernel<3><<<eg, 256, 0, stream()>>>(od, o, thr, cells, d_count, cells_cap); break;
-                    case 4: extrema_kernel<4><<<eg, 256, 0, stream()>>>(od, o, thr, cells, d_count, cells_cap); break;
-                    default: extrema_kernel<5><<<eg, 256, 0, stream()>>>(od, o, thr, cells, d_count, cells_cap); break;
+                const int wgs = cdiv(run, 4);
+                auto launch_sweep = [&](unsigned long long* cl, unsigned int* ct) {
+                    switch (nl) {
+                        case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                        case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                        case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                        case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                        default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                    }
+                };
+                launch_sweep(cells, d_count);
+                check_launch("extrema_wave_kernel");
+#ifdef APS_DBG
+                if (dbg_replay > 0) {
+                    Ws<unsigned long long> cells2(cells_cap);
+                    Ws<unsigned int> cnt2(2);
+                    unsigned int n1 = 0, n2 = 0;
+                    APS_HIP(hipMemcpyAsync(&n1, d_count, 4, hipMemcpyDeviceToHost, stream()));
+                    APS_HIP(hipStreamSynchronize(stream()));
+                    const unsigned long long c1 = dbg::cks(cells.get(), std::min(n1, cells_cap), 2, 0, dbg_slot);
+                    for (int rep = 0; rep < dbg_replay; ++rep) {
+                        APS_HIP(hipMemsetAsync(cnt2, 0, 8, stream()));
+                        launch_sweep(cells2, cnt2);
+                        APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
+                        APS_HIP(hipStreamSynchronize(stream()));
+                        const unsigned long long c2 = dbg::cks(cells2.get(), std::min(n2, cells_cap), 2, 0, dbg_slot);
+                        dbg::g_stat[dbg::kExtReplays]++;
+                        if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kExtDiff]++;
+                    }
                 }
-                check_launch("extrema_kernel");
+#endif
             }
             APS_HIP(hipMemcpyAsync(h_counts, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
             APS_HIP(hipStreamSynchronize(stream()));
@@ -2180,9 +1710,8 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
         Out<double> oloc(loc, (size_t)ldl + n_out);
         {
             Prof prof("sift_descr");
-            static const int plain_sweep = std::getenv("APS_DESCR_PLAIN") ? 1 : 0;  // (A/B: the whole-square sweep of rounds 1-5; same bits)
             descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
-                                                               oaux.present() ? oaux.get() : nullptr, plain_sweep);
+                                                               oaux.present() ? oaux.get() : nullptr);
         }
         check_launch("descr_kernel");
 #ifdef APS_DBG
@@ -2191,7 +1720,7 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
             Ws<double> loc2((size_t)2 * n_out);
             for (int rep = 0; rep < dbg_replay; ++rep) {
                 descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, desc2, desc_layout, 128, loc2, n_out,
-                                                                   oaux.present() ? aux2.get() : nullptr, 0);
+                                                                   oaux.present() ? aux2.get() : nullptr);
                 unsigned long long d = dbg::diff(odesc.get(), desc2.get(), (size_t)n_out * 128, dbg_slot) +
                                        dbg::diff(oloc.get(), loc2.get(), (size_t)2 * n_out, dbg_slot) +
                                        dbg::diff(oloc.get() + ldl, loc2.get() + n_out, (size_t)2 * n_out, dbg_slot);

@@ -1,7 +1,7 @@
 // Microbenchmark: HBM read rate of the access patterns the SIFT kernels can choose from, on NP planes of W x H floats
 // (octave 0 of a 4K view: 7680 x 4320, 133 MB per plane, 7 planes):
 //   linear      every thread a float4 at the same linear offset of each plane (the copy-kernel pattern)
-//   tile TWxTH  one 256-thread workgroup per TW x TH tile plus a 1-pixel halo rounded to float4 (extrema_kernel's fill)
+//   tile TWxTH  one 256-thread workgroup per TW x TH tile plus a 1-pixel halo rounded to float4 (the fill of the retired 128 x 8 extrema tiles)
 //   march SWxCH one workgroup per SW-wide strip segment of CH rows, marching down RS rows per step with the next step's
 //               loads requested before the current step is consumed (every row read once, + 2 halo rows per segment)
 // build: hipcc --offload-arch=gfx950 -O3 -o /tmp/mem_pattern scripts/probe/mem_pattern.hip ; run: /tmp/mem_pattern
