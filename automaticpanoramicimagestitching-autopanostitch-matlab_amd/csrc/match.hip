@@ -2,18 +2,32 @@
 //
 // Restates PP/featureMatching/matchFeaturesScratch.m (normalizeRowsL2 :217-234, nearest2SSDExhaustive
 // :322-366, ratio/threshold :170-178, greedy uniqueness :186-207) and the pair scheduling of
-// PP/featureMatching/featureMatchingPairwise.m:48-63.
+// PP/featureMatching/featureMatchingPairwise.m:48-63.  Every path returns the bits of the exact f32 evaluation.
 //
-// Kernels
-//   prep_desc_kernel     : optional row L2-normalisation, canonical ||x||^2, and a k-permuted copy
-//                          P[i][h*64+s] = X[i][2s+h] so that one lane's MFMA operands are contiguous.
-//   match2nn_kernel      : the N1 x 128 . 128 x N2 distance GEMM on v_mfma_f32_32x32x2_f32 (exact f32,
-//                          k-ascending fma chain) with the top-2 reduction fused into the epilogue.
-//                          A (32 rows x 128 k per wave) lives in 64 VGPRs for the whole workgroup
-//                          lifetime; B streams through a padded, double-buffered LDS tile.
-//   filter/unique kernels: ratio + threshold test in f64 (as MATLAB evaluates it), one-to-one
-//                          resolution as a per-column atomicMin on an order-preserving 64-bit key,
-//                          segmented radix sort (rocPRIM) to the reference's stable ascending order.
+// Kernels by stage, in file order
+//   probe      absmax_flat / absmax_batch / absmax_kernel: max |x| of a set (the "looks unnormalised" test).
+//   prepare    prep_desc(_batch) + prep_stats(_batch): optional L2 normalisation, canonical ||x||^2, the k-permuted
+//              f32 copy and the f16 operands of a set; q8_desc(_batch): its int8 codes (rounded, and exact where
+//              the set has them); sort_keys / sort_gather: the sorted column side of arena batches.
+//   exact f32  match2nn_kernel: the distance GEMM on v_mfma_f32_32x32x2_f32 with the top-2 reduction in its
+//              epilogue, dense (APS_MATCH_MODE=f32) or over a row list (the fallback);
+//              match2nn_merge_parts_kernel: top-2 of a tile's column parts; knn3_rows_kernel: top-3 of single rows.
+//   candidates match_cand_f16_kernel<LIST>: f16 MFMA candidate search with exact rescoring of the best few in its
+//              tail; what it cannot certify goes to the fallback list.
+//   screen     match_screen_i8_kernel (32x32x32) / match_screen_i8x16_kernel (16x16x64, default): the int8 pass
+//              that dismisses rows which provably fail the caller's filter; <true> writes bounds for the pooled
+//              matcher instead.  match_list_i8_kernel + match_rescore_kernel: the exact int8 pass over survivors.
+//   filter     filter_mark / select / seg_end / emit(_rows): ratio + threshold in f64, one-to-one resolution by
+//              atomicMin on an order-preserving key, rocPRIM segmented sort to the reference's order.
+//   tables     fb_compact / list_pool / expand_tiles / fb_jobs: row lists and tile tables of the passes above.
+//   pooled     global_screen_reduce / global_phase_b / global_t3_init: featureMatchingGlobal's two phases.
+//
+// Entry points
+//   aps_match_2nn_ssd                                        -> prepare, run_match_jobs
+//   aps_match_features / aps_match_pairwise / aps_match_pairs -> match_pairs_impl: prepare_batch, run_match_jobs
+//                                                               (screen -> survivor passes -> fallback), run_filter
+//   aps_match_set_stats                                      -> prepare
+//   screened_block_top3, screened_global_top3 (from knn.hip) -> prepare(_batch), candidates / screen<true>, top-3
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -479,20 +493,10 @@ struct Q8Set {
     float cb;          // column-side offset (an integer)
 };
 
-__device__ int g_q8_symmetric = 0;  // experiment switch (APS_Q8_SYMMETRIC=1): column code without the offset
-__device__ int g_scr_variant = 0;   // experiment switch (APS_SCR_VARIANT, bits: see match_screen_i8x16_kernel)
-__device__ int g_q8_noexact = 0;    // A/B switch (APS_MATCH_NO_EXACT=1): no set gets exact integer codes (rounds 2-5's screen)
-#ifdef APS_MATCH_TIMING
-__device__ int g_q8_center = 0;     // timing builds only (APS_Q8_CENTER=c, -1 for 0): the exact codes as clamp(u - c): WRONG results, for
-                                    // measuring how the screening kernel's clock depends on the operands' magnitudes
-#endif
+__device__ int g_q8_noexact = 0;  // A/B switch (APS_MATCH_NO_EXACT=1): no set gets exact integer codes (rounds 2-5's screen)
 
 __device__ __forceinline__ Q8Set q8_set(const float* __restrict__ qstat) {
-    float mx = unord_f32(__float_as_uint(qstat[0])), mn = unord_f32(~__float_as_uint(qstat[3]));
-    if (g_q8_symmetric) {
-        mx = fmaxf(fabsf(mx), fabsf(mn));
-        mn = -mx;
-    }
+    const float mx = unord_f32(__float_as_uint(qstat[0])), mn = unord_f32(~__float_as_uint(qstat[3]));
     Q8Set q;
     const float range = mx - mn;
     const bool ok = range > 0.f && range < 1e30f;
@@ -685,12 +689,7 @@ __device__ __forceinline__ void q8_desc_rows(int64_t g, const float* __restrict_
                     uint32_t pw = 0;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-#ifdef APS_MATCH_TIMING
-                        const int cx = g_q8_center == 0 ? 128 : max(g_q8_center, 0);
-                        const int pq = min(max((int)uf[4 * q4 + e] - cx, -128), 127);
-#else
                         const int pq = (int)uf[4 * q4 + e] - 128;
-#endif
                         usum += pq;
                         pw |= ((uint32_t)pq & 0xffu) << (8 * e);
                     }
@@ -709,9 +708,6 @@ __device__ __forceinline__ void q8_desc_rows(int64_t g, const float* __restrict_
                     fail_bits = 1u;
                     if (!lost) *xlost = 1u;
                 }
-#ifdef APS_MATCH_TIMING
-                if (!found && !lost && g_q8_center == 999) printf("[q8] row %lld of %lld has no exact code: min positive entry %g, non-negative %d, first entries %g %g %g %g\n", (long long)i, (long long)n, mn, (int)nonneg, xs[0], xs[1], xs[2], xs[3]);
-#endif
                 if (found && !zero_row) {
                     tmax_bits = __float_as_uint(t_row);   // t > 0: the bit patterns order like the values
                     tmin_bits = ~__float_as_uint(t_row);
@@ -1363,7 +1359,7 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
                                                                 uint32_t* __restrict__ out_idx,
                                                                 float* __restrict__ out_d1, float* __restrict__ out_d2,
                                                                 uint32_t* __restrict__ fb_list,
-                                                                unsigned int* __restrict__ fb_count, int ablate,
+                                                                unsigned int* __restrict__ fb_count,
                                                                 float prune_r2, float prune_thr,
                                                                 uint32_t* __restrict__ t3_idx, float* __restrict__ t3_d,
                                                                 float* __restrict__ t3_b,
@@ -1386,9 +1382,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
         const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
         wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
     }
-#ifdef APS_MATCH_TIMING
-    const unsigned long long T_entry = __builtin_readcyclecounter();
-#endif
     const WgJob w = wgs[wg];
     const MatchJob jb = jobs[w.job];
     const int tid = threadIdx.x;
@@ -1491,9 +1484,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
     // (every ~10 events), with no per-value tests at all: inserting a value <= the list's fourth entry, or the
     // -inf of an empty slot, changes nothing.  A parked group only delays the tightening of that lane's threshold.
     float thr[2] = {-INFINITY, -INFINITY};
-#ifdef APS_MATCH_TIMING
-    if (ablate & 4) thr[0] = thr[1] = INFINITY;  // timing experiment: the screen never fires
-#endif
     float pv[2][4];
     int pj[2] = {-1, -1};
 #pragma unroll
@@ -1514,12 +1504,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
     float m_scr = 0.f;
     auto select_slice = [&](auto PAR, int t, auto CB, auto SL) __attribute__((always_inline)) {
         constexpr int par = decltype(PAR)::value, cb = decltype(CB)::value, sl = decltype(SL)::value;
-#ifdef APS_MATCH_TIMING
-        if (__builtin_expect(ablate & 1, 0)) {
-            asm volatile("" ::"v"(acc[par][0]), "v"(acc[par][1]));
-            return;
-        }
-#endif
         constexpr int g = sl >> 1, rb = sl & 1;
         const f32x16& a = acc[par][rb];
         // max of the four, compared against the row's threshold: three VALU instructions and a scalar branch are
@@ -1532,12 +1516,7 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
         asm("v_max3_f32 %1, %2, %3, %4\n\tv_max_f32 %1, %1, %5\n\tv_cmp_gt_f32 %0, %1, %6"
             : "=s"(any_hit), "+v"(m_scr)
             : "v"(a[4 * g]), "v"(a[4 * g + 1]), "v"(a[4 * g + 2]), "v"(a[4 * g + 3]), "v"(thr[rb]));
-#ifdef APS_NO_EVENTS  // timing experiment: what the event code costs by merely being there
-        asm volatile("" ::"s"(any_hit));
-        if (false) {
-#else
         if (__builtin_expect(any_hit != 0, 0)) {  // cold: the common case must be the fall-through (a taken branch
-#endif
                                                   // per slice costs an instruction refetch the MFMAs cannot hide)
             const bool hit = m_scr > thr[rb];
             if (__any(hit && pj[rb] >= 0)) drain(rb);
@@ -1610,31 +1589,15 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
     constexpr int kAhead = 3;  // an LDS round trip under load is longer than one k-step (two MFMAs + a slice)
     f16x8 bh[4], aug_q[2];
     if (ntiles > 0) {
-        if (ntiles > 1 && !(ablate & 2)) issue_piece(1, 1, 0);
+        if (ntiles > 1) issue_piece(1, 1, 0);
         aug_q[0] = *reinterpret_cast<const f16x8*>(&s_aug[0][c]);
 #pragma unroll
         for (int s = 0; s < kAhead; ++s) bh[s] = *reinterpret_cast<const f16x8*>(lds + c * 256 + ((32 * s) ^ hx));
     }
-#ifdef APS_MATCH_TIMING  // phase timing of one workgroup (make EXTRA=-DAPS_MATCH_TIMING, APS_MATCH_ABLATE=8)
-    unsigned long long T_mf = 0, T_bar = 0;
-    const unsigned long long T_c0 = __builtin_readcyclecounter(), T_w0 = wall_clock64();
-    unsigned long long T_prev = T_c0, T_mark = T_c0;
-#define APS_TICK(acc_)                                              \
-    {                                                               \
-        const unsigned long long n_ = __builtin_readcyclecounter(); \
-        acc_ += n_ - T_prev;                                        \
-        T_prev = n_;                                                \
-    }
-#else
-#define APS_TICK(acc_)
-#endif
     int b_cur = 0;  // t % 3
     for (int t = 0; t < ntiles; ++t) {
-        const bool more = t + 1 < ntiles && !(ablate & 2);
-        const bool more2 = t + 2 < ntiles && !(ablate & 2);
-#ifdef APS_MATCH_TIMING
-        if (t == 128) T_mark = __builtin_readcyclecounter();
-#endif
+        const bool more = t + 1 < ntiles;
+        const bool more2 = t + 2 < ntiles;
         const int b_nxt = b_cur == 2 ? 0 : b_cur + 1, b_nxt2 = b_nxt == 2 ? 0 : b_nxt + 1;
         const unsigned char* tile = lds + b_cur * kTileBytes + c * 256;
         const unsigned char* tile_n = lds + b_nxt * kTileBytes + c * 256;
@@ -1644,7 +1607,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
             constexpr int cb = decltype(CB)::value;
             constexpr int kLast = kTNB / 32 - 1;
             constexpr int par = cb & 1;
-            APS_TICK(T_bar)
             // one DMA piece per block: pieces 1..3 of tile t+1 in blocks 0..2, piece 0 of tile t+2 in block 3
             if (cb < kLast ? more : more2) issue_piece(cb < kLast ? t + 1 : t + 2, cb < kLast ? b_nxt : b_nxt2,
                                                        cb < kLast ? cb + 1 : 0);
@@ -1673,31 +1635,14 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
                 select_slice(std::integral_constant<int, par ^ 1>{}, pt, std::integral_constant<int, pcb>{}, S);
                 __builtin_amdgcn_sched_barrier(0);
             });
-            APS_TICK(T_mf)
             if (cb == kLast - 1) {
                 // hand-over: this wave's DMA pieces of tile t+1 (and its b2) have landed; after the barrier that
                 // holds for every wave, and every wave has left tile t-1
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef APS_MATCH_TIMING
-                if (!(ablate & 32))  // (bit 32 in timing builds: no hand-over barrier, no rescoring - racy, timing only)
-#endif
-                    __syncthreads();
-                APS_TICK(T_bar)
+                __syncthreads();
             }
         });
     }
-#ifdef APS_MATCH_TIMING
-    const unsigned long long T_loop_end = __builtin_readcyclecounter();
-    if ((ablate & 8) && blockIdx.x == 300 && lane == 0 && (wave == 0 || wave == 4)) {
-        const unsigned long long c1 = __builtin_readcyclecounter(), w1 = wall_clock64();
-        printf("wave %d: prologue %llu cycles (entry -> first block); steady state (tiles 128..end): %.0f cycles per block\n", wave,
-               T_c0 - T_entry, ntiles > 128 ? (double)(c1 - T_mark) / ((ntiles - 128) * 4) : 0.0);
-        printf("wave %d: %.3f GHz, %d blocks, cycles per block: total %.0f = mfma+selection %.0f + hand-over %.0f\n",
-               wave, (double)(c1 - T_c0) / ((double)(w1 - T_w0) * 10.0), ntiles * (kTNB / 32),
-               (double)(c1 - T_c0) / (ntiles * (kTNB / 32)), (double)T_mf / (ntiles * (kTNB / 32)),
-               (double)T_bar / (ntiles * (kTNB / 32)));
-    }
-#endif
     if (ntiles > 0) {
         static_for<0, 8>([&](auto S) {
             select_slice(std::integral_constant<int, (kTNB / 32 - 1) & 1>{}, ntiles - 1,
@@ -1728,7 +1673,7 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
         const int myjob = h ? rjob[1] : rjob[0];
         // (pooled list: the row's own job - same B set, its own A side and output slots)
         const MatchJob& jr = (LIST && row_job) ? jobs[myjob] : jb;
-        if ((h ? rvalid[1] : rvalid[0]) && !(ablate & 32)) {  // (bit 32: timing experiment without the rescoring tail)
+        if (h ? rvalid[1] : rvalid[0]) {
             // Rows that cannot pass the caller's ratio / threshold filter (matchFeaturesScratch.m:170-178) are dismissed
             // on the screened values alone: d1 >= L1 and d2 <= H2 hold for the exact f32 distances (see prune_bounds), so
             // L1 > r^2 H2 (or L1 > MatchThreshold) decides the filter's verdict without the exact evaluation - no gathers,
@@ -1756,10 +1701,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
             }
         }
     }
-#ifdef APS_MATCH_TIMING
-    if ((ablate & 8) && blockIdx.x == 300 && lane == 0 && (wave == 0 || wave == 4))
-        printf("wave %d: tail %llu cycles (last block -> exit)\n", wave, __builtin_readcyclecounter() - T_loop_end);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2176,13 +2117,6 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     const signed char* const opA = exact ? jb.AX : jb.AQ;
     const signed char* const opB = exact ? jb.BXs : jb.BQ;  // (exact: the columns in ascending order of their divisor)
     const int* const cin_src = jb.cinBs;
-    // experiment switches (APS_SCR_VARIANT): 1 = static priority for waves 4-7, 2 / 4 = waves 4-7 sleep 64 / 128 cycles after
-    // every hand-over barrier (a stagger between the two waves of a SIMD), 8 = the odd waves instead of waves 4-7
-#ifdef APS_MATCH_TIMING  // (timing builds only, like the ablation bits)
-    const int variant = __builtin_amdgcn_readfirstlane(g_scr_variant);
-    const bool late_half = (variant & 8) ? (wave & 1) != 0 : wave >= 4;
-    if ((variant & 1) && late_half) __builtin_amdgcn_s_setprio(1);
-#endif
 
     i32x4 aq[4][2];
 #pragma unroll
@@ -2402,12 +2336,6 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
             if (cb == kLast - 1) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-#ifdef APS_MATCH_TIMING
-                if ((variant & 6) && late_half) {
-                    if (variant & 2) __builtin_amdgcn_s_sleep(1);
-                    if (variant & 4) __builtin_amdgcn_s_sleep(2);
-                }
-#endif
             }
         });
     };
@@ -2962,20 +2890,13 @@ static void sync_device_switch(const char* env, const void* symbol) {
     APS_HIP(hipMemcpyToSymbol(symbol, &want, sizeof want, 0, hipMemcpyHostToDevice));
     h = want;
 }
-static void sync_q8_symmetric_switch() {
-    sync_device_switch("APS_Q8_SYMMETRIC", &g_q8_symmetric);
-    sync_device_switch("APS_MATCH_NO_EXACT", &g_q8_noexact);
-#ifdef APS_MATCH_TIMING
-    sync_device_switch("APS_Q8_CENTER", &g_q8_center);
-#endif
-}
 
 static void prepare(const float* X_dev, int64_t n, int64_t ld, int layout, bool normalize, Prepared& out) {
     hipStream_t st = stream();
     prepare_alloc(n, out, st, nullptr);
     float* const qstat = out.stat + 4;
     const int64_t n_pad = (std::max<int64_t>(n, 1) + kTNB - 1) / kTNB * kTNB;
-    sync_q8_symmetric_switch();  // A/B switch APS_Q8_SYMMETRIC: column code without the offset
+    sync_device_switch("APS_MATCH_NO_EXACT", &g_q8_noexact);
     if (n == 0) return;
     Prof prof("match_prep");
     prep_desc_kernel<<<out.nb1, kPrepThreads, 0, st>>>(X_dev, n, ld, layout, normalize ? 1 : 0, out.P, out.sq, out.H, out.dn, out.part);
@@ -3151,7 +3072,7 @@ static void prepare_batch(const std::vector<PrepRequest>& req, int layout, Arena
         bp.push_back(bp.back() + o.nb1);
         bq.push_back(bq.back() + o.nb2);
     }
-    sync_q8_symmetric_switch();
+    sync_device_switch("APS_MATCH_NO_EXACT", &g_q8_noexact);
     if (jobs.empty()) return;
     SortPlan sp;
     if (arena) sort_plan(req, *arena, sp);
@@ -3340,34 +3261,50 @@ __global__ void list_pool_kernel(const int64_t* __restrict__ seg_off, const uint
     }
 }
 
-// Pools the list segments of jobs that share a B set (same operand pointer and column count) into common tiles of kTMB
-// rows: returns the tiles (WgJob{a job of the group, start in the pooled list, rows}); pool / pool_job are filled on the
-// stream.  from / to: host copies of the per-job entry ranges (from may be empty = zeros); d_from / d_to: device copies.
-static std::vector<WgJob> pool_lists(const std::vector<MatchJob>& jobs, const std::vector<int64_t>& seg_off,
-                                     const uint32_t* d_list, const std::vector<unsigned int>& from, const std::vector<unsigned int>& to,
-                                     const unsigned int* d_from, const unsigned int* d_to, Ws<uint32_t>& pool, Ws<int>& pool_job) {
+// The walk over the jobs that share a B set - same operand pointer (`key`: the operand the pass streams) and same column
+// count - with the groups in pointer order and the jobs of a group in job order: job j's cnt[j] list entries get the place
+// dst[j] ... of one packed list, and every group's stretch of that list is cut into tiles of tile_rows rows, appended to
+// `tiles` as WgJob{the group's first job, start in the packed list, rows}.  Returns the packed list's length.
+// skip_empty_sets: groups whose B set has no columns get places but no tiles.
+template <class Ptr>
+static size_t tile_by_b_set(const std::vector<MatchJob>& jobs, Ptr MatchJob::*key, const std::vector<unsigned int>& cnt,
+                            int tile_rows, bool skip_empty_sets, std::vector<long long>& dst, std::vector<WgJob>& tiles) {
     const size_t nj = jobs.size();
     std::vector<int> order(nj);
     for (size_t j = 0; j < nj; ++j) order[j] = (int)j;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        return std::less<const void*>()(jobs[a].BF, jobs[b].BF) || (jobs[a].BF == jobs[b].BF && jobs[a].nB < jobs[b].nB);
+        return std::less<const void*>()(jobs[a].*key, jobs[b].*key) || (jobs[a].*key == jobs[b].*key && jobs[a].nB < jobs[b].nB);
     });
-    std::vector<long long> h_dst(nj, 0);
-    std::vector<WgJob> tiles;
+    dst.assign(nj, 0);
     size_t total = 0;
     for (size_t a = 0; a < nj;) {
         size_t b = a;
         const size_t g0 = total;
-        while (b < nj && jobs[order[b]].BF == jobs[order[a]].BF && jobs[order[b]].nB == jobs[order[a]].nB) {
-            const int j = order[b];
-            h_dst[j] = (long long)total;
-            total += to[j] - (from.empty() ? 0u : from[j]);
+        while (b < nj && jobs[order[b]].*key == jobs[order[a]].*key && jobs[order[b]].nB == jobs[order[a]].nB) {
+            dst[order[b]] = (long long)total;
+            total += cnt[order[b]];
             ++b;
         }
-        if (jobs[order[a]].nB > 0)
-            for (size_t r = g0; r < total; r += kTMB) tiles.push_back({order[a], (int)r, (int)std::min<size_t>(kTMB, total - r), 0, 0, 0});
+        if (!skip_empty_sets || jobs[order[a]].nB > 0)
+            for (size_t r = g0; r < total; r += tile_rows)
+                tiles.push_back({order[a], (int)r, (int)std::min<size_t>(tile_rows, total - r), 0, 0, 0});
         a = b;
     }
+    return total;
+}
+
+// Pools the list segments of jobs that share a B set into common tiles of kTMB rows: returns the tiles; pool / pool_job
+// are filled on the stream.  from / to: host copies of the per-job entry ranges (from may be empty = zeros); d_from /
+// d_to: device copies.
+static std::vector<WgJob> pool_lists(const std::vector<MatchJob>& jobs, const std::vector<int64_t>& seg_off,
+                                     const uint32_t* d_list, const std::vector<unsigned int>& from, const std::vector<unsigned int>& to,
+                                     const unsigned int* d_from, const unsigned int* d_to, Ws<uint32_t>& pool, Ws<int>& pool_job) {
+    const size_t nj = jobs.size();
+    std::vector<unsigned int> cnt(to);
+    for (size_t j = 0; j < from.size(); ++j) cnt[j] -= from[j];
+    std::vector<long long> h_dst;
+    std::vector<WgJob> tiles;
+    const size_t total = tile_by_b_set(jobs, &MatchJob::BF, cnt, kTMB, true, h_dst, tiles);
     if (total == 0) return tiles;
     APS_REQUIRE(total < ((size_t)1 << 31), APS_E_DIM, "pooled row list too long (%zu)", total);
     pool.alloc(total);
@@ -3379,25 +3316,6 @@ static std::vector<WgJob> pool_lists(const std::vector<MatchJob>& jobs, const st
     list_pool_kernel<<<(unsigned)nj, 128, 0, stream()>>>(d_seg, d_list, d_from, d_to, d_dst, pool, pool_job);
     check_launch("list_pool_kernel");
     APS_HIP(hipStreamSynchronize(stream()));  // h_dst / seg_off and their device copies go out of scope
-    if (std::getenv("APS_POOL_DEBUG")) {  // consistency of the pooled list with the host's view of it
-        std::vector<int> hj(total);
-        std::vector<uint32_t> hr(total);
-        std::vector<unsigned int> dto(nj);
-        APS_HIP(hipMemcpy(hj.data(), pool_job, total * sizeof(int), hipMemcpyDeviceToHost));
-        APS_HIP(hipMemcpy(hr.data(), pool, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        APS_HIP(hipMemcpy(dto.data(), d_to, nj * sizeof(unsigned int), hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < nj; ++j)
-            if (dto[j] != to[j]) std::fprintf(stderr, "[aps pool] job %zu: device count %u, host count %u\n", j, dto[j], to[j]);
-        size_t bad = 0;
-        for (const WgJob& t : tiles)
-            for (int e = 0; e < t.list_cnt; ++e) {
-                const int j = hj[t.row0 + e];
-                if (j < 0 || j >= (int)nj || jobs[j].BF != jobs[t.job].BF || hr[t.row0 + e] >= (uint32_t)jobs[j].nA) {
-                    if (bad++ < 5) std::fprintf(stderr, "[aps pool] tile at %d entry %d: job %d row %u (tile job %d)\n", t.row0, e, j, hr[t.row0 + e], t.job);
-                }
-            }
-        std::fprintf(stderr, "[aps pool] %zu entries in %zu tiles, %zu bad\n", total, tiles.size(), bad);
-    }
     return tiles;
 }
 
@@ -3452,214 +3370,176 @@ __global__ void expand_tiles_kernel(const int* __restrict__ off, int n_jobs, int
     }
     out[k] = WgJob{lo, (k - off[lo]) * rows_per_tile, 0, 0, 0, 0};
 }
-// Runs the 2-NN search for a list of jobs whose operands are already prepared on the device.
-// prune_r2 > 0: the caller will apply the ratio / threshold filter with these constants, so rows that cannot pass it
-// may come back as idx 0 / inf without an exact evaluation (see match_cand_f16_kernel's tail)
-static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, float* d1, float* d2, float prune_r2 = 0.f,
-                           float prune_thr = 0.f) {
-    g_screen_rows = g_screen_surv = g_screen_jobs = g_screen_exact = 0;
-    bool any_rows = false;
-    for (const MatchJob& j : jobs) any_rows = any_rows || j.nA > 0;
-    if (!any_rows) return;
-    Ws<MatchJob> djobs(jobs.size());
-    APS_HIP(hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(MatchJob), hipMemcpyHostToDevice,
+// ---- run_match_jobs and its steps: the 2-NN search for a list of jobs whose operands are already prepared on the device ----
+
+// APS_MATCH_MODE=f32: the all-f32 MFMA kernel on every row.
+static void match_all_f32(const std::vector<MatchJob>& jobs, const MatchJob* djobs, uint32_t* idx, float* d1, float* d2) {
+    // (the 128-row tile table of the all-f32 kernel: 312 k entries for the 64 x 4K scene - built and uploaded here only;
+    // until round 4 every call paid for it, ~1 ms of host time and a 7.5 MB pageable upload the split path never read)
+    std::vector<WgJob> wgs;
+    for (int j = 0; j < (int)jobs.size(); ++j)
+        for (int r = 0; r < jobs[j].nA; r += kTM) wgs.push_back({j, r, 0});
+    Ws<WgJob> dwgs(wgs.size());
+    APS_HIP(hipMemcpyAsync(dwgs, wgs.data(), wgs.size() * sizeof(WgJob), hipMemcpyHostToDevice,
                            stream()));
-    if (!use_split_path()) {
-        // (the 128-row tile table of the all-f32 kernel: 312 k entries for the 64 x 4K scene - built and uploaded here only;
-        // until round 4 every call paid for it, ~1 ms of host time and a 7.5 MB pageable upload the split path never read)
-        std::vector<WgJob> wgs;
-        for (int j = 0; j < (int)jobs.size(); ++j)
-            for (int r = 0; r < jobs[j].nA; r += kTM) wgs.push_back({j, r, 0});
-        Ws<WgJob> dwgs(wgs.size());
-        APS_HIP(hipMemcpyAsync(dwgs, wgs.data(), wgs.size() * sizeof(WgJob), hipMemcpyHostToDevice,
-                               stream()));
-        {
-            Prof prof("match2nn");
-            match2nn_kernel<false><<<(unsigned)wgs.size(), 256, 0, stream()>>>(djobs, dwgs, nullptr, (int)jobs.size(), idx, d1, d2);
-        }
-        check_launch("match2nn_kernel");
-        APS_HIP(hipStreamSynchronize(stream()));  // the pageable host vectors must outlive the copies
-        return;
+    {
+        Prof prof("match2nn");
+        match2nn_kernel<false><<<(unsigned)wgs.size(), 256, 0, stream()>>>(djobs, dwgs, nullptr, (int)jobs.size(), idx, d1, d2);
     }
-    const int64_t total_rows = jobs.back().out_off + jobs.back().nA;
-    // uncertified rows: one list segment per job (at the job's first output slot) and one counter per job, so the
-    // host only reads the counters back - no sort, no second copy of the list
-    Ws<uint32_t> fb_list((size_t)total_rows);
-    Ws<unsigned int> fb_count(jobs.size());
-    APS_HIP(hipMemsetAsync(fb_count, 0, jobs.size() * sizeof(unsigned int), stream()));
-    // the dense tile table {job, first row} of the screening / candidate kernels, expanded on the device from the jobs' tile
-    // offsets (round 6: 78 k entries for the 64 x 4K scene were built on the host and uploaded from pageable memory, ~0.2 ms)
-    std::vector<int> wg_off(jobs.size() + 1, 0);
-    for (size_t j = 0; j < jobs.size(); ++j) wg_off[j + 1] = wg_off[j] + (jobs[j].nA + kTMB - 1) / kTMB;
-    struct { size_t n; size_t size() const { return n; } } bw{(size_t)wg_off.back()};
-    Ws<WgJob> dbw(std::max<size_t>(bw.size(), 1));
-    Ws<int> d_wg_off(wg_off.size());
-    APS_HIP(hipMemcpyAsync(d_wg_off, wg_off.data(), wg_off.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
-    if (bw.size() > 0) {
-        expand_tiles_kernel<<<(unsigned)cdiv(bw.size(), 256), 256, 0, stream()>>>(d_wg_off, (int)jobs.size(), (int)bw.size(), kTMB, dbw);
-        check_launch("expand_tiles_kernel");
+    check_launch("match2nn_kernel");
+    APS_HIP(hipStreamSynchronize(stream()));  // the pageable host vectors must outlive the copies
+}
+
+// Round 6: the survivors of jobs that ran on exact integer codes (cnt_x, n_x in all) take the exact int8 list pass
+// (match_list_i8_kernel + match_rescore_kernel) here; the others (cnt_g) are left to the f16 candidate kernel as before.
+// Each kind is pooled on its own; returns the tiles of the second kind, their rows in pool / pool_job.
+static std::vector<WgJob> exact_list_pass(const std::vector<MatchJob>& jobs, const MatchJob* djobs, const std::vector<int64_t>& seg,
+                                          const uint32_t* surv_list, const std::vector<unsigned int>& cnt_x,
+                                          const std::vector<unsigned int>& cnt_g, size_t n_x, uint32_t* idx, float* d1, float* d2,
+                                          uint32_t* fb_list, unsigned int* fb_count, Ws<uint32_t>& pool, Ws<int>& pool_job) {
+    Ws<unsigned int> d_cnt_x(jobs.size()), d_cnt_g(jobs.size());
+    APS_HIP(hipMemcpyAsync(d_cnt_x, cnt_x.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
+    APS_HIP(hipMemcpyAsync(d_cnt_g, cnt_g.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
+    Ws<uint32_t> pool_x;
+    Ws<int> pool_job_x;
+    const std::vector<WgJob> lx = pool_lists(jobs, seg, surv_list, {}, cnt_x, nullptr, d_cnt_x, pool_x, pool_job_x);
+    Ws<WgJob> dlx(lx.size());
+    Ws<uint32_t> cand(n_x * kCandCap);
+    Ws<unsigned int> cand_cnt(n_x);
+    APS_HIP(hipMemcpyAsync(dlx, lx.data(), lx.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    APS_HIP(hipMemsetAsync(cand_cnt, 0, n_x * sizeof(unsigned int), stream()));
+    {
+        Prof prof("match_list_i8");
+        require_whole_simd_list();
+        match_list_i8_kernel<<<(unsigned)lx.size(), 512, 0, stream()>>>(djobs, dlx, (int)lx.size(), pool_x, pool_job_x, d1, cand, cand_cnt);
     }
-#ifdef APS_MATCH_TIMING  // ablation bits are honoured by timing builds only (they invalidate the results)
-    const char* ab = std::getenv("APS_MATCH_ABLATE");
-    const int ablate = ab ? std::atoi(ab) : 0;
-#else
-    const int ablate = 0;
-#endif
-    // Filtered callers: the int8 screen dismisses the rows that provably fail the filter, the candidate kernel then runs
-    // on the survivors only (row lists per job, 512 to a workgroup).  APS_MATCH_NO_SCREEN=1: every row takes the f16 path.
-    const bool screen = prune_r2 > 0.f && !std::getenv("APS_MATCH_NO_SCREEN");
-    if (screen) {
-        Ws<uint32_t> surv_list((size_t)total_rows);
-        Ws<unsigned int> surv_count(2 * jobs.size());  // per job: survivors, then 1 where the job ran on exact integer codes
-        APS_HIP(hipMemsetAsync(surv_count, 0, 2 * jobs.size() * sizeof(unsigned int), stream()));
-        {
-            Prof prof("match_screen_i8");
-#ifdef APS_MATCH_TIMING
-            sync_device_switch("APS_SCR_VARIANT", &g_scr_variant);
-#endif
-            require_whole_simd(screen_shape_32() ? 1 : 0);
-            if (screen_shape_32())
-                match_screen_i8_kernel<false><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), idx, d1, d2, surv_list,
-                                                                                          surv_count, prune_r2, prune_thr, nullptr);
-            else
-                match_screen_i8x16_kernel<false><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), idx, d1, d2, surv_list,
-                                                                                             surv_count, prune_r2, prune_thr, nullptr,
-                                                                                             surv_count.get() + jobs.size());
-        }
-        check_launch("match_screen_i8_kernel");
-        const auto S0 = std::chrono::steady_clock::now();
-        std::vector<unsigned int> h_surv(2 * jobs.size());
-        APS_HIP(hipMemcpyAsync(h_surv.data(), surv_count, 2 * jobs.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        g_screen_jobs = (int64_t)jobs.size();
-        g_screen_exact = 0;
-        std::vector<char> h_exact(jobs.size());
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            h_exact[j] = h_surv[jobs.size() + j] ? 1 : 0;
-            g_screen_exact += h_exact[j];
-        }
-        h_surv.resize(jobs.size());
-        const auto S1 = std::chrono::steady_clock::now();
-        // the survivors of the jobs that share a B set are pooled into common 512-row tiles (APS_MATCH_NO_POOL=1: one list per
-        // job, as in rounds 2-3 - 6599 tiles instead of ~5600 for the 64 x 4K scene)
-        const bool pooled = !std::getenv("APS_MATCH_NO_POOL");
-        std::vector<WgJob> lw;
-        size_t n_surv = 0;
-        Ws<uint32_t> pool;
-        Ws<int> pool_job;
-        for (int j = 0; j < (int)jobs.size(); ++j) n_surv += h_surv[j];
-        if (pooled) {
-            std::vector<int64_t> seg(jobs.size());
-            for (size_t j = 0; j < jobs.size(); ++j) seg[j] = jobs[j].out_off;
-            // Round 6: the survivors of jobs that ran on exact integer codes take the exact int8 list pass (match_list_i8_kernel +
-            // match_rescore_kernel), the others the f16 candidate kernel as before; each kind is pooled on its own.
-            std::vector<unsigned int> cnt_x(jobs.size(), 0u), cnt_g(h_surv);
-            size_t n_x = 0;
-            for (size_t j = 0; j < jobs.size(); ++j)
-                if (h_exact[j] && jobs[j].nB >= 1) {
-                    cnt_x[j] = h_surv[j];
-                    cnt_g[j] = 0u;
-                    n_x += h_surv[j];
-                }
-            if (n_x > 0) {
-                Ws<unsigned int> d_cnt_x(jobs.size()), d_cnt_g(jobs.size());
-                APS_HIP(hipMemcpyAsync(d_cnt_x, cnt_x.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
-                APS_HIP(hipMemcpyAsync(d_cnt_g, cnt_g.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
-                Ws<uint32_t> pool_x;
-                Ws<int> pool_job_x;
-                const std::vector<WgJob> lx = pool_lists(jobs, seg, surv_list, {}, cnt_x, nullptr, d_cnt_x, pool_x, pool_job_x);
-                Ws<WgJob> dlx(lx.size());
-                Ws<uint32_t> cand(n_x * kCandCap);
-                Ws<unsigned int> cand_cnt(n_x);
-                APS_HIP(hipMemcpyAsync(dlx, lx.data(), lx.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
-                APS_HIP(hipMemsetAsync(cand_cnt, 0, n_x * sizeof(unsigned int), stream()));
-                {
-                    Prof prof("match_list_i8");
-                    require_whole_simd_list();
-                    match_list_i8_kernel<<<(unsigned)lx.size(), 512, 0, stream()>>>(djobs, dlx, (int)lx.size(), pool_x, pool_job_x, d1, cand, cand_cnt);
-                }
-                {
-                    Prof prof("match_rescore");
-                    match_rescore_kernel<<<(unsigned)cdiv(n_x, 32), 256, 0, stream()>>>(djobs, pool_x, pool_job_x, (int64_t)n_x, cand, cand_cnt, idx, d1, d2,
-                                                                                       fb_list, fb_count);
-                }
-                check_launch("match_list_i8_kernel");
-                lw = pool_lists(jobs, seg, surv_list, {}, cnt_g, nullptr, d_cnt_g, pool, pool_job);
-                APS_HIP(hipStreamSynchronize(stream()));  // (lx, the count tables and the candidate lists go out of scope)
-            } else {
-                lw = pool_lists(jobs, seg, surv_list, {}, h_surv, nullptr, surv_count, pool, pool_job);
+    {
+        Prof prof("match_rescore");
+        match_rescore_kernel<<<(unsigned)cdiv(n_x, 32), 256, 0, stream()>>>(djobs, pool_x, pool_job_x, (int64_t)n_x, cand, cand_cnt, idx, d1, d2,
+                                                                           fb_list, fb_count);
+    }
+    check_launch("match_list_i8_kernel");
+    std::vector<WgJob> lw = pool_lists(jobs, seg, surv_list, {}, cnt_g, nullptr, d_cnt_g, pool, pool_job);
+    APS_HIP(hipStreamSynchronize(stream()));  // (lx, the count tables and the candidate lists go out of scope)
+    return lw;
+}
+
+// Filtered callers: the int8 screen over the dense tiles dbw dismisses the rows that provably fail the filter, the
+// survivor passes (exact_list_pass, match_cand_f16_kernel<true>) then run on the survivors only (row lists, 512 to a workgroup).
+static void screen_and_survivor_passes(const std::vector<MatchJob>& jobs, const MatchJob* djobs, const WgJob* dbw, size_t n_bw,
+                                       int64_t total_rows, uint32_t* idx, float* d1, float* d2, float prune_r2, float prune_thr,
+                                       uint32_t* fb_list, unsigned int* fb_count) {
+    Ws<uint32_t> surv_list((size_t)total_rows);
+    Ws<unsigned int> surv_count(2 * jobs.size());  // per job: survivors, then 1 where the job ran on exact integer codes
+    APS_HIP(hipMemsetAsync(surv_count, 0, 2 * jobs.size() * sizeof(unsigned int), stream()));
+    {
+        Prof prof("match_screen_i8");
+        require_whole_simd(screen_shape_32() ? 1 : 0);
+        if (screen_shape_32())
+            match_screen_i8_kernel<false><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list,
+                                                                                 surv_count, prune_r2, prune_thr, nullptr);
+        else
+            match_screen_i8x16_kernel<false><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list,
+                                                                                    surv_count, prune_r2, prune_thr, nullptr,
+                                                                                    surv_count.get() + jobs.size());
+    }
+    check_launch("match_screen_i8_kernel");
+    const auto S0 = std::chrono::steady_clock::now();
+    std::vector<unsigned int> h_surv(2 * jobs.size());
+    APS_HIP(hipMemcpyAsync(h_surv.data(), surv_count, 2 * jobs.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    g_screen_jobs = (int64_t)jobs.size();
+    g_screen_exact = 0;
+    std::vector<char> h_exact(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        h_exact[j] = h_surv[jobs.size() + j] ? 1 : 0;
+        g_screen_exact += h_exact[j];
+    }
+    h_surv.resize(jobs.size());
+    const auto S1 = std::chrono::steady_clock::now();
+    // the survivors of the jobs that share a B set are pooled into common 512-row tiles (APS_MATCH_NO_POOL=1: one list per
+    // job, as in rounds 2-3 - 6599 tiles instead of ~5600 for the 64 x 4K scene)
+    const bool pooled = !std::getenv("APS_MATCH_NO_POOL");
+    std::vector<WgJob> lw;
+    size_t n_surv = 0;
+    Ws<uint32_t> pool;
+    Ws<int> pool_job;
+    for (int j = 0; j < (int)jobs.size(); ++j) n_surv += h_surv[j];
+    if (pooled) {
+        std::vector<int64_t> seg(jobs.size());
+        for (size_t j = 0; j < jobs.size(); ++j) seg[j] = jobs[j].out_off;
+        std::vector<unsigned int> cnt_x(jobs.size(), 0u), cnt_g(h_surv);
+        size_t n_x = 0;
+        for (size_t j = 0; j < jobs.size(); ++j)
+            if (h_exact[j] && jobs[j].nB >= 1) {
+                cnt_x[j] = h_surv[j];
+                cnt_g[j] = 0u;
+                n_x += h_surv[j];
             }
-        } else {
-            for (int j = 0; j < (int)jobs.size(); ++j)
-                for (unsigned int r = 0; r < h_surv[j]; r += kTMB) lw.push_back({j, (int)r, (int)std::min<unsigned int>(kTMB, h_surv[j] - r)});
-        }
-        g_screen_rows = total_rows;
-        g_screen_surv = (int64_t)n_surv;
-        if (std::getenv("APS_TRACE")) {
-            int hist[5] = {0, 0, 0, 0, 0};  // jobs by surviving share: 0, <1 %, <10 %, <50 %, >= 50 %
-            for (int j = 0; j < (int)jobs.size(); ++j) {
-                const double f = jobs[j].nA ? (double)h_surv[j] / jobs[j].nA : 0.0;
-                ++hist[h_surv[j] == 0 ? 0 : f < 0.01 ? 1 : f < 0.1 ? 2 : f < 0.5 ? 3 : 4];
-            }
-            std::fprintf(stderr, "[aps] int8 screen: %zu of %lld rows survive (%.2f %%), %zu list tiles; jobs by surviving share: none %d, <1%% %d, "
-                         "<10%% %d, <50%% %d, >=50%% %d\n", n_surv, (long long)total_rows, 100.0 * (double)n_surv / (double)total_rows,
-                         lw.size(), hist[0], hist[1], hist[2], hist[3], hist[4]);
-        }
-        if (!lw.empty()) {
-            Ws<WgJob> dlw(lw.size());
-            APS_HIP(hipMemcpyAsync(dlw, lw.data(), lw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
-            {
-                Prof prof("match_cand_f16");
-                match_cand_f16_kernel<true><<<(unsigned)lw.size(), 512, 0, stream()>>>(djobs, dlw, (int)lw.size(), idx, d1, d2, fb_list, fb_count,
-                                                                                        ablate, prune_r2, prune_thr, nullptr, nullptr, nullptr,
-                                                                                        pooled ? pool.get() : surv_list.get(),
-                                                                                        pooled ? pool_job.get() : nullptr);
-            }
-            check_launch("match_cand_f16_kernel<list>");
-            const auto S3 = std::chrono::steady_clock::now();
-            APS_HIP(hipStreamSynchronize(stream()));  // lw must outlive its copy
-            if (std::getenv("APS_TRACE")) {
-                auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-                    return std::chrono::duration<double, std::milli>(b - a).count();
-                };
-                std::fprintf(stderr, "[aps] screen: launch -> counts on the host %.2f ms (incl. the wait for the kernel), tiles + pooling on the host %.2f ms, "
-                             "list pass (wait) %.2f ms\n", ms(S0, S1), ms(S1, S3), ms(S3, std::chrono::steady_clock::now()));
-            }
-        }
+        if (n_x > 0)
+            lw = exact_list_pass(jobs, djobs, seg, surv_list, cnt_x, cnt_g, n_x, idx, d1, d2, fb_list, fb_count, pool, pool_job);
+        else
+            lw = pool_lists(jobs, seg, surv_list, {}, h_surv, nullptr, surv_count, pool, pool_job);
     } else {
-        Prof prof("match_cand_f16");
-        match_cand_f16_kernel<false><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), idx, d1, d2, fb_list, fb_count,
-                                                                                 ablate, prune_r2, prune_thr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        for (int j = 0; j < (int)jobs.size(); ++j)
+            for (unsigned int r = 0; r < h_surv[j]; r += kTMB) lw.push_back({j, (int)r, (int)std::min<unsigned int>(kTMB, h_surv[j] - r)});
     }
-    check_launch("match_cand_f16_kernel");
+    g_screen_rows = total_rows;
+    g_screen_surv = (int64_t)n_surv;
+    if (std::getenv("APS_TRACE")) {
+        int hist[5] = {0, 0, 0, 0, 0};  // jobs by surviving share: 0, <1 %, <10 %, <50 %, >= 50 %
+        for (int j = 0; j < (int)jobs.size(); ++j) {
+            const double f = jobs[j].nA ? (double)h_surv[j] / jobs[j].nA : 0.0;
+            ++hist[h_surv[j] == 0 ? 0 : f < 0.01 ? 1 : f < 0.1 ? 2 : f < 0.5 ? 3 : 4];
+        }
+        std::fprintf(stderr, "[aps] int8 screen: %zu of %lld rows survive (%.2f %%), %zu list tiles; jobs by surviving share: none %d, <1%% %d, "
+                     "<10%% %d, <50%% %d, >=50%% %d\n", n_surv, (long long)total_rows, 100.0 * (double)n_surv / (double)total_rows,
+                     lw.size(), hist[0], hist[1], hist[2], hist[3], hist[4]);
+    }
+    if (lw.empty()) return;
+    Ws<WgJob> dlw(lw.size());
+    APS_HIP(hipMemcpyAsync(dlw, lw.data(), lw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("match_cand_f16");
+        match_cand_f16_kernel<true><<<(unsigned)lw.size(), 512, 0, stream()>>>(djobs, dlw, (int)lw.size(), idx, d1, d2, fb_list, fb_count,
+                                                                                prune_r2, prune_thr, nullptr, nullptr, nullptr,
+                                                                                pooled ? pool.get() : surv_list.get(),
+                                                                                pooled ? pool_job.get() : nullptr);
+    }
+    check_launch("match_cand_f16_kernel<list>");
+    const auto S3 = std::chrono::steady_clock::now();
+    APS_HIP(hipStreamSynchronize(stream()));  // lw must outlive its copy
+    if (std::getenv("APS_TRACE")) {
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+            return std::chrono::duration<double, std::milli>(b - a).count();
+        };
+        std::fprintf(stderr, "[aps] screen: launch -> counts on the host %.2f ms (incl. the wait for the kernel), tiles + pooling on the host %.2f ms, "
+                     "list pass (wait) %.2f ms\n", ms(S0, S1), ms(S1, S3), ms(S3, std::chrono::steady_clock::now()));
+    }
+}
+
+// Unfiltered callers and APS_MATCH_NO_SCREEN=1: every row takes the f16 candidate kernel, over the dense tiles dbw.
+static void dense_cand_pass(const MatchJob* djobs, const WgJob* dbw, size_t n_bw, uint32_t* idx, float* d1, float* d2, float prune_r2,
+                            float prune_thr, uint32_t* fb_list, unsigned int* fb_count) {
+    Prof prof("match_cand_f16");
+    match_cand_f16_kernel<false><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, fb_list, fb_count,
+                                                                        prune_r2, prune_thr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// The rows no earlier pass could certify (fb_list / fb_count, per job): the exact f32 kernel in row-list mode.  The
+// uncertified rows of all jobs that share a B set are pooled into common 128-row tiles (a pair leaves ~80 such rows at
+// 20 k features: one mostly empty tile each otherwise): the segments are compacted in group order on the device, the
+// kernel finds every row's job by its output slot.
+static void fallback_pass(const std::vector<MatchJob>& jobs, const MatchJob* djobs, const uint32_t* fb_list, const unsigned int* fb_count,
+                          uint32_t* idx, float* d1, float* d2) {
     std::vector<unsigned int> h_cnt(jobs.size());
     const auto R0 = std::chrono::steady_clock::now();
     APS_HIP(hipMemcpyAsync(h_cnt.data(), fb_count, jobs.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
     APS_HIP(hipStreamSynchronize(stream()));
     const auto R1 = std::chrono::steady_clock::now();
-    // Exact f32 kernel in row-list mode.  The uncertified rows of all jobs that share a B set are pooled into common
-    // 128-row tiles (a pair leaves ~80 such rows at 20 k features: one mostly empty tile each otherwise): the segments
-    // are compacted in group order on the device, the kernel finds every row's job by its output slot.
-    std::vector<int> order((size_t)jobs.size());
-    for (int j = 0; j < (int)jobs.size(); ++j) order[j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        return std::less<const void*>()(jobs[a].PB, jobs[b].PB) ||
-               (jobs[a].PB == jobs[b].PB && jobs[a].nB < jobs[b].nB);
-    });
-    std::vector<long long> h_dst(jobs.size(), 0);
+    std::vector<long long> h_dst;
     std::vector<WgJob> fwgs;
-    size_t n_fb = 0;
-    for (size_t a = 0; a < order.size();) {
-        size_t b = a;
-        const size_t g0 = n_fb;
-        while (b < order.size() && jobs[order[b]].PB == jobs[order[a]].PB && jobs[order[b]].nB == jobs[order[a]].nB) {
-            h_dst[order[b]] = (long long)n_fb;
-            n_fb += h_cnt[order[b]];
-            ++b;
-        }
-        for (size_t r = g0; r < n_fb; r += kTM) fwgs.push_back({order[a], (int)r, (int)std::min<size_t>(kTM, n_fb - r), 0, 0, 0});
-        a = b;
-    }
+    const size_t n_fb = tile_by_b_set(jobs, &MatchJob::PB, h_cnt, kTM, false, h_dst, fwgs);
     if (fwgs.empty()) return;
     // A handful of tiles, each streaming a whole B set through f32 MFMAs, leaves most of the chip idle (63 tiles of ~32
     // rows on the 64 x 4K scene: 1.5 ms): split the columns of every tile into parts and merge the parts' top-2.
@@ -3699,7 +3579,7 @@ static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, flo
     }
     check_launch("match2nn_kernel<list>");
     const auto R2 = std::chrono::steady_clock::now();
-    APS_HIP(hipStreamSynchronize(stream()));
+    APS_HIP(hipStreamSynchronize(stream()));  // the host tables and their device copies go out of scope
     if (std::getenv("APS_TRACE"))
         std::fprintf(stderr, "[aps] 2-NN: candidates (wait) %.2f ms, fallback list %zu rows: host %.2f ms, kernel (wait) %.2f ms\n",
                      std::chrono::duration<double, std::milli>(R1 - R0).count(), n_fb,
@@ -3707,7 +3587,48 @@ static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, flo
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R2).count());
 }
 
-// ratio/threshold/unique for a list of jobs; returns total kept.  Outputs are device pointers.
+// prune_r2 > 0: the caller will apply the ratio / threshold filter with these constants, so rows that cannot pass it
+// may come back as idx 0 / inf without an exact evaluation (see match_cand_f16_kernel's tail)
+static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, float* d1, float* d2, float prune_r2 = 0.f,
+                           float prune_thr = 0.f) {
+    g_screen_rows = g_screen_surv = g_screen_jobs = g_screen_exact = 0;
+    bool any_rows = false;
+    for (const MatchJob& j : jobs) any_rows = any_rows || j.nA > 0;
+    if (!any_rows) return;
+    Ws<MatchJob> djobs(jobs.size());
+    APS_HIP(hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(MatchJob), hipMemcpyHostToDevice,
+                           stream()));
+    if (!use_split_path()) {
+        match_all_f32(jobs, djobs, idx, d1, d2);
+        return;
+    }
+    const int64_t total_rows = jobs.back().out_off + jobs.back().nA;
+    // uncertified rows: one list segment per job (at the job's first output slot) and one counter per job, so the
+    // host only reads the counters back - no sort, no second copy of the list
+    Ws<uint32_t> fb_list((size_t)total_rows);
+    Ws<unsigned int> fb_count(jobs.size());
+    APS_HIP(hipMemsetAsync(fb_count, 0, jobs.size() * sizeof(unsigned int), stream()));
+    // the dense tile table {job, first row} of the screening / candidate kernels, expanded on the device from the jobs' tile
+    // offsets (round 6: 78 k entries for the 64 x 4K scene were built on the host and uploaded from pageable memory, ~0.2 ms)
+    std::vector<int> wg_off(jobs.size() + 1, 0);
+    for (size_t j = 0; j < jobs.size(); ++j) wg_off[j + 1] = wg_off[j] + (jobs[j].nA + kTMB - 1) / kTMB;
+    const size_t n_bw = (size_t)wg_off.back();
+    Ws<WgJob> dbw(std::max<size_t>(n_bw, 1));
+    Ws<int> d_wg_off(wg_off.size());
+    APS_HIP(hipMemcpyAsync(d_wg_off, wg_off.data(), wg_off.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+    if (n_bw > 0) {
+        expand_tiles_kernel<<<(unsigned)cdiv(n_bw, 256), 256, 0, stream()>>>(d_wg_off, (int)jobs.size(), (int)n_bw, kTMB, dbw);
+        check_launch("expand_tiles_kernel");
+    }
+    // APS_MATCH_NO_SCREEN=1: every row takes the f16 path
+    if (prune_r2 > 0.f && !std::getenv("APS_MATCH_NO_SCREEN"))
+        screen_and_survivor_passes(jobs, djobs, dbw, n_bw, total_rows, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
+    else
+        dense_cand_pass(djobs, dbw, n_bw, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
+    check_launch("match_cand_f16_kernel");
+    fallback_pass(jobs, djobs, fb_list, fb_count, idx, d1, d2);
+}
+
 // job_of[e] for the pooled fallback list: entry e belongs to job j for dst[j] <= e < dst[j] + cnt[j]
 __global__ void fb_jobs_kernel(const long long* __restrict__ dst, const unsigned int* __restrict__ fb_count, int n_jobs,
                                int* __restrict__ job_of) {
@@ -3716,10 +3637,6 @@ __global__ void fb_jobs_kernel(const long long* __restrict__ dst, const unsigned
     const unsigned int cnt = fb_count[j];
     for (unsigned int e = threadIdx.x; e < cnt; e += blockDim.x) job_of[dst[j] + e] = j;
 }
-
-}  // namespace aps (reopened below)
-
-namespace aps {
 
 // The screening half of the blocked global k-NN (aps_knn_global on a pool against itself, knn.hip): the pool is cut into
 // blocks; for every ordered pair of DIFFERENT blocks (i, j) the candidate kernel finds, for each row of block i, its three
@@ -3764,7 +3681,7 @@ int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const st
     {
         Prof prof("match_cand_f16");
         match_cand_f16_kernel<false><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), nullptr, nullptr, nullptr, fb_list,
-                                                                                 fb_count, 0, 0.f, 0.f, t3_idx, t3_d, t3_b, nullptr, nullptr);
+                                                                                 fb_count, 0.f, 0.f, t3_idx, t3_d, t3_b, nullptr, nullptr);
     }
     check_launch("match_cand_f16_kernel");
     std::vector<unsigned int> h_cnt(jobs.size());
@@ -4147,7 +4064,7 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
         {
             Prof prof("match_cand_f16");
             match_cand_f16_kernel<true><<<(unsigned)lw.size(), 512, 0, stream()>>>(dcj, dlw, (int)lw.size(), nullptr, nullptr, nullptr, fb_list,
-                                                                                    fb_count, 0, 0.f, 0.f, t3_idx, t3_d, t3_b,
+                                                                                    fb_count, 0.f, 0.f, t3_idx, t3_d, t3_b,
                                                                                     pooled ? pool.get() : row_list.get(),
                                                                                     pooled ? pool_job.get() : nullptr);
         }
@@ -4178,6 +4095,7 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
     return slots;
 }
 
+// ratio/threshold/unique for a list of jobs; returns total kept.  Outputs are device pointers.
 static int64_t run_filter(const std::vector<FilterJob>& fjobs, int64_t total_rows, int64_t total_cols,
                           const uint32_t* idx, const float* d1, const float* d2,
                           const aps_match_opts& o, unsigned long long* d_job_ptr /* njobs+1 */,

@@ -193,7 +193,7 @@ __global__ void rw_taps_kernel(const TapJob* __restrict__ jobs, int* __restrict_
 // into the border sample).  Products and sums in f64, stored as f32.  This is the blur and the resize of
 // multiBandBlending.m:112-135 in exact arithmetic; it differs from the two-step evaluation by the rounding of the
 // intermediate blurred plane only, which is what the render's stated tolerance is for (the per-tile path and
-// APS_RENDER_EXACT=1 keep the two-step form bit for bit).
+// APS_WARP_EXACT=1 keep the two-step form bit for bit).
 constexpr int kNCPMax = 16;  // kTD + 2 * 4 = 14 weights, padded to whole 16-byte groups
 __global__ void rw_ctaps_kernel(const TapJob* __restrict__ jobs, Taps tp, int ncp, int* __restrict__ c_s0,
                                 float* __restrict__ c_w, int* __restrict__ status) {
@@ -742,7 +742,7 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
     if (in_tile) A.cov[(size_t)T.plane + (size_t)y * w + x] = any ? 1 : 0;
 }
 
-// The exact form (APS_RENDER_EXACT=1 / APS_WARP_EXACT=1): the walking form on the canvas-wide trig tables (A.ct, A.rt).
+// The exact form (APS_WARP_EXACT=1): the walking form on the canvas-wide trig tables (A.ct, A.rt).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_kernel(RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
     __shared__ float s_u8[256];
     __shared__ float4 s_g[kWL][256];
@@ -1854,8 +1854,8 @@ bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int 
                                                                                               d_status);
         check_launch("rw_taps_kernel");
     }
-    // APS_RENDER_EXACT=1 (or its older name APS_WARP_EXACT): the warp and the shrink keep the per-tile path's arithmetic
-    const bool exact = std::getenv("APS_RENDER_EXACT") != nullptr || std::getenv("APS_WARP_EXACT") != nullptr;
+    // APS_WARP_EXACT=1: the warp and the shrink keep the per-tile path's arithmetic
+    const bool exact = std::getenv("APS_WARP_EXACT") != nullptr;
     const int ncp = (kTD + 2 * tp.r + 3) & ~3;
     Ws<int> cd_s0((size_t)std::max(n_down, 1));
     Ws<float> cd_w((size_t)std::max(n_down, 1) * ncp);
@@ -1940,13 +1940,6 @@ bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int 
         std::vector<char> used(n_img, 0);
         for (const RwEntry& E : ents) used[E.img] = 1;
         need_images(used);
-    }
-    if (std::getenv("APS_RENDER_DEBUG")) {
-        long long rect0 = 0, canvas = 0;
-        for (const RwEntry& E : ents) rect0 += (long long)(E.g[0].x1 - E.g[0].x0) * (E.g[0].y1 - E.g[0].y0);
-        for (const RwTile& T : ht_) canvas += (long long)T.ht * T.wt;
-        std::fprintf(stderr, "[aps render] tiles %d entries %d (%.2f per tile) footprint rect area %.1f MPix canvas %.1f MPix G store %.2f GB\n",
-                     nt, ne, (double)ne / nt, rect0 / 1e6, canvas / 1e6, g_total * 16.0 / 1e9);
     }
     // block tables: levels 0 .. max_nl-2 of the shrink over entries, levels 0 .. max_nl-1 of the collapse over tiles
     std::vector<int> blk((size_t)(max_nl) * (ne + 1) + (size_t)max_nl * (nt + 1), 0);

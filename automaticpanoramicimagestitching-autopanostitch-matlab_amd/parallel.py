@@ -295,7 +295,7 @@ class FeatureExchange:
             # batch of workers, four at most (2 ranks x 32 views)
             workers = max(1, int(os.environ.get("APS_SIFT_WORKERS", 10)))
             rounds = min(4, (self.per + workers - 1) // workers)
-        rounds = max(1, min(int(os.environ.get("APS_EXCHANGE_ROUNDS", rounds)), self.per))
+        rounds = max(1, min(int(rounds), self.per))
         self.chunk = (self.per + rounds - 1) // rounds
         self.rounds = (self.per + self.chunk - 1) // self.chunk
         self.futures = futures
@@ -798,11 +798,9 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
             root = pano_root if pano_root is not None else None
             pano = _deliver_panorama(pano, int(comp_owner[ci]), root, dev)
         else:
-            # tiles second: every rank a contiguous, area-balanced run of the tile list (APS_TILE_DEAL=mod: t % world, rounds 1-4)
-            tranges = None
-            if _multi(ws) and os.environ.get("APS_TILE_DEAL") != "mod":
-                tranges = tile_ranges(int(geo["H"]), int(geo["W"]), rp.effective_tile(opts, geo), ws)
-            subset = None if not _multi(ws) else (("range",) + tranges[rank]) if tranges is not None else (rank, ws)
+            # tiles second: every rank a contiguous, area-balanced run of the tile list
+            tranges = tile_ranges(int(geo["H"]), int(geo["W"]), rp.effective_tile(opts, geo), ws) if _multi(ws) else None
+            subset = ("range",) + tranges[rank] if tranges is not None else None
             pano, _ = rp.renderPanorama(input, [images[k] for k in members], sizes, c["cameras"], mode, c["ref"], opts,
                                         gains=gains, device_out=True, tile_subset=subset, geo=geo,
                                         # (runs gathered to a root cover the canvas: nothing outside a rank's run is read)

@@ -5,7 +5,7 @@ instead of computing") only needs an exactly known code product and the measured
     L1 = a2 + min|b|^2 - 2 (D0 + E),  H2 = a2 + max|b|^2 - 2 (D1 - E),   row dismissed iff L1 > r^2 H2 or L1 > MatchThreshold
 with D0 >= D1 the two largest code products of the row.  Emulated here in float64 on the bench scene's descriptors for
   int8   : rows scaled per row to +-127, columns per set with an offset to 0..255 (what q8_desc_kernel does),
-  int7   : the same with 127 column levels (the APS_Q8_SYMMETRIC experiment of round 4, for calibration of the emulation),
+  int7   : the same with 127 column levels (one bit less: the column code without its offset, for calibration of the emulation),
   e2m3   : MX fp6, one power-of-two scale per 32 elements (free in v_mfma_scale_f32_16x16x128_f8f6f4), round to nearest,
   e2m3c  : the same on data centred by a constant per set (uses the sign bit; the cross terms are exact row / column sums),
   e2m1   : MX fp4.

@@ -32,7 +32,7 @@ for rep in range(int(sys.argv[1]) if len(sys.argv) > 1 else 6):
     while not all(fu.done() for fu in futs):
         try:
             ms.append(msig(fm.match_pairs_csr(descs, order, 0.6, 1.5, True, device_out=True)))
-        except Exception as e:  # ablated kernels hand garbage to the filter
+        except Exception as e:  # (a call that fails beside the extraction is recorded, not fatal)
             ms.append(("exc", str(e)[:40]))
     out = [fu.result() for fu in futs]
     torch.cuda.synchronize()
