@@ -85,6 +85,8 @@ inline hipStream_t stream() { return ctx().stream(); }
 // Cached device workspace (hipMalloc is synchronising; steady state must not call it).
 void* ws_alloc(size_t bytes);
 void ws_free(void* p);
+// Bytes of this thread's cached blocks that are not in use (device memory a new request can be served from).
+size_t ws_idle_bytes();
 
 template <class T>
 struct Ws {

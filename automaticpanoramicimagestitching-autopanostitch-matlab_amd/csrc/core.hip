@@ -118,6 +118,13 @@ void* ws_alloc(size_t bytes) {
     return p;
 }
 
+size_t ws_idle_bytes() {
+    size_t n = 0;
+    for (const auto& b : ctx().blocks)
+        if (!b.used) n += b.bytes;
+    return n;
+}
+
 void ws_free(void* p) {
     for (auto& b : g_ctx.blocks)
         if (b.p == p) {

@@ -417,10 +417,6 @@ __global__ void paint_kernel(const float4* __restrict__ F, const uint8_t* __rest
 // ------------------------------------------------------------------------------------------------
 // imageWarp 'bilinear' (imageWarp.m:125-168)
 // ------------------------------------------------------------------------------------------------
-struct HWarp {
-    double A[9];  // adjugate of H/H(3,3)
-    double det;
-};
 
 // bicubicKernel of imageWarp.m:275-301 (Keys, a = -0.5), |x|^2 and |x|^3 as products, terms left to right
 __device__ __forceinline__ double warp_cubic(double x) {
@@ -802,8 +798,8 @@ static void normalize_weights(const std::vector<float4*>& layers, const Rect* re
 // result float4 in F (unclamped).  Level-major: per level one launch blurs up to 16 layers, one launch
 // downsamples them, one pass forms their Laplacians and accumulates them in layer order.  No host sync.
 // rects (optional): footprints of the layers; every kernel then works on footprints only (see struct Rect).
-static void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int h, int w, int levels, float sigma,
-                             float4* F) {
+void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int h, int w, int levels, float sigma,
+                      float4* F) {
     const int K = (int)layers.size();
     const size_t hw = (size_t)h * w;
     Prof prof("multiband");
@@ -1475,67 +1471,7 @@ __device__ __forceinline__ bool gain_sample(const DevImage& im, const float d[3]
     return true;
 }
 
-constexpr int kGainSlots = 128;  // per-workgroup pair table
-constexpr int kGainMaxCover = 16;
-
-// The pair sums of one workgroup of both gain-statistics kernels: a small LDS hash table keyed by the image pair (the points
-// of a 16 x 16 patch share a handful of pairs), flushed with one double atomicAdd per touched entry; a full table sends the
-// contribution straight to memory.  Outputs are n x n (x 3) column-major, entry (i, j), i < j.
-struct GainPairTable {
-    unsigned int key[kGainSlots];
-    unsigned int cnt[kGainSlots];
-    double sum[kGainSlots][6];
-    __device__ __forceinline__ void init() {
-        for (int e = threadIdx.x; e < kGainSlots; e += blockDim.x) {
-            key[e] = 0u;
-            cnt[e] = 0u;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) sum[e][c] = 0.0;
-        }
-        __syncthreads();
-    }
-    __device__ __forceinline__ void add(int n_img, int i, int j, const float* ci, const float* cj, double* __restrict__ Nij,
-                                        double* __restrict__ sCi, double* __restrict__ sCj) {
-        const unsigned int k = (unsigned int)(i * n_img + j) + 1u;
-        unsigned int slot = (k * 2654435761u) >> 25;
-        for (int probe = 0; probe < kGainSlots; ++probe) {
-            const unsigned int old = atomicCAS(&key[slot], 0u, k);
-            if (old == 0u || old == k) {
-                atomicAdd(&cnt[slot], 1u);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    atomicAdd(&sum[slot][c], (double)ci[c]);
-                    atomicAdd(&sum[slot][3 + c], (double)cj[c]);
-                }
-                return;
-            }
-            slot = (slot + 1) & (kGainSlots - 1);
-        }
-        const size_t nn = (size_t)n_img * n_img, e = (size_t)i + (size_t)n_img * j;  // table full: straight to memory
-        atomicAdd(&Nij[e], 1.0);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            atomicAdd(&sCi[e + nn * c], (double)ci[c]);
-            atomicAdd(&sCj[e + nn * c], (double)cj[c]);
-        }
-    }
-    __device__ __forceinline__ void flush(int n_img, double* __restrict__ Nij, double* __restrict__ sCi, double* __restrict__ sCj) {
-        __syncthreads();
-        const size_t nn = (size_t)n_img * n_img;
-        for (int e = threadIdx.x; e < kGainSlots; e += blockDim.x) {
-            const unsigned int k = key[e];
-            if (!k) continue;
-            const int i = (int)((k - 1u) / (unsigned int)n_img), j = (int)((k - 1u) % (unsigned int)n_img);
-            const size_t o = (size_t)i + (size_t)n_img * j;
-            atomicAdd(&Nij[o], (double)cnt[e]);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                atomicAdd(&sCi[o + nn * c], sum[e][c]);
-                atomicAdd(&sCj[o + nn * c], sum[e][3 + c]);
-            }
-        }
-    }
-};
+// (kGainSlots, kGainMaxCover and GainPairTable, the per-workgroup pair table of the gain-statistics kernels: render_dev.h)
 
 // One thread per sampled canvas point.  Pair sums go through a small LDS hash table per workgroup (the points of a
 // 16 x 16 patch share a handful of pairs), flushed with one double atomicAdd per entry.
@@ -1826,7 +1762,7 @@ extern "C" int aps_imresize_u8(const uint8_t* img, int h, int w, int c, int layo
     });
 }
 
-static void make_hwarp(const double* H, HWarp& hw) {
+void aps::make_hwarp(const double* H, HWarp& hw) {
     double h[9];
     for (int e = 0; e < 9; ++e) h[e] = H[8] != 0 ? H[e] / H[8] : H[e];
 #define HH(r, c) h[(r) + 3 * (c)]

@@ -266,4 +266,78 @@ bool render_fuse_batched(const DevImage* dimgs, const DevImage* himgs, int n_img
                               const std::vector<TileRect>& tiles, int out_layout, uint8_t* pano, uint8_t* covered,
                               const NeedImages& need_images);
 
+// ------------------------------------------------------------------------------------------------
+// shared between render.hip and planar.hip
+// ------------------------------------------------------------------------------------------------
+struct HWarp {
+    double A[9];  // adjugate of H/H(3,3)
+    double det;
+};
+// (render.hip) adjugate and determinant of H / H(3,3), H f64 3x3 column-major
+void make_hwarp(const double* H, HWarp& hw);
+// (render.hip) multiBandBlending on K float4 layers with normalised weights, optional footprints; result in F (unclamped)
+void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int h, int w, int levels, float sigma, float4* F);
+
+constexpr int kGainSlots = 128;  // per-workgroup pair table
+constexpr int kGainMaxCover = 16;
+
+// The pair sums of one workgroup of both gain-statistics kernels: a small LDS hash table keyed by the image pair (the points
+// of a 16 x 16 patch share a handful of pairs), flushed with one double atomicAdd per touched entry; a full table sends the
+// contribution straight to memory.  Outputs are n x n (x 3) column-major, entry (i, j), i < j.
+struct GainPairTable {
+    unsigned int key[kGainSlots];
+    unsigned int cnt[kGainSlots];
+    double sum[kGainSlots][6];
+    __device__ __forceinline__ void init() {
+        for (int e = threadIdx.x; e < kGainSlots; e += blockDim.x) {
+            key[e] = 0u;
+            cnt[e] = 0u;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) sum[e][c] = 0.0;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void add(int n_img, int i, int j, const float* ci, const float* cj, double* __restrict__ Nij,
+                                        double* __restrict__ sCi, double* __restrict__ sCj) {
+        const unsigned int k = (unsigned int)(i * n_img + j) + 1u;
+        unsigned int slot = (k * 2654435761u) >> 25;
+        for (int probe = 0; probe < kGainSlots; ++probe) {
+            const unsigned int old = atomicCAS(&key[slot], 0u, k);
+            if (old == 0u || old == k) {
+                atomicAdd(&cnt[slot], 1u);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    atomicAdd(&sum[slot][c], (double)ci[c]);
+                    atomicAdd(&sum[slot][3 + c], (double)cj[c]);
+                }
+                return;
+            }
+            slot = (slot + 1) & (kGainSlots - 1);
+        }
+        const size_t nn = (size_t)n_img * n_img, e = (size_t)i + (size_t)n_img * j;  // table full: straight to memory
+        atomicAdd(&Nij[e], 1.0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            atomicAdd(&sCi[e + nn * c], (double)ci[c]);
+            atomicAdd(&sCj[e + nn * c], (double)cj[c]);
+        }
+    }
+    __device__ __forceinline__ void flush(int n_img, double* __restrict__ Nij, double* __restrict__ sCi, double* __restrict__ sCj) {
+        __syncthreads();
+        const size_t nn = (size_t)n_img * n_img;
+        for (int e = threadIdx.x; e < kGainSlots; e += blockDim.x) {
+            const unsigned int k = key[e];
+            if (!k) continue;
+            const int i = (int)((k - 1u) / (unsigned int)n_img), j = (int)((k - 1u) % (unsigned int)n_img);
+            const size_t o = (size_t)i + (size_t)n_img * j;
+            atomicAdd(&Nij[o], (double)cnt[e]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                atomicAdd(&sCi[o + nn * c], sum[e][c]);
+                atomicAdd(&sCj[o + nn * c], sum[e][3 + c]);
+            }
+        }
+    }
+};
+
 }  // namespace aps

@@ -394,21 +394,181 @@ def pureNonRotationalImagesToCanvas(images, tforms, outputView, srcWeights, opts
     return Iw, Ww, xB, yB, centers
 
 
-def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None):
+def _planar_args(images, tforms):
+    """Checks and marshals the image list and the homographies of the planar entry points (before the library is touched)."""
+    n = len(images)
+    if n == 0 or len(tforms) != n:
+        raise ValueError("images and tforms must be non-empty lists of equal length")
+    keep, hs, ws, cs = [], [], [], []
+    Hs = np.zeros((n, 9), np.float64)
+    for k, (im, T) in enumerate(zip(images, tforms)):
+        T = np.asarray(T, np.float64)
+        if T.shape != (3, 3):
+            raise ValueError(f"tforms[{k}] must be a 3x3 matrix, got {T.shape}")
+        Hs[k] = T.T.reshape(9)  # column-major
+        if _capi.is_torch(im):
+            import torch
+
+            if im.dtype != torch.uint8:
+                raise ValueError(f"images[{k}] must be uint8, got {im.dtype}")
+            a = im if im.is_contiguous() else im.contiguous()
+        else:
+            a = np.asarray(im)
+            if a.dtype != np.uint8:
+                raise ValueError(f"images[{k}] must be uint8, got {a.dtype}")
+            a = np.ascontiguousarray(a)
+        if a.ndim not in (2, 3) or (a.ndim == 3 and int(a.shape[2]) not in (1, 3)) or min(int(v) for v in a.shape[:2]) < 1:
+            raise ValueError(f"images[{k}] must be h x w, h x w x 1 or h x w x 3, got {tuple(a.shape)}")
+        keep.append(a)
+        hs.append(int(a.shape[0]))
+        ws.append(int(a.shape[1]))
+        cs.append(1 if a.ndim == 2 else int(a.shape[2]))
+    if any(_capi.is_torch(a) and a.is_cuda for a in keep):
+        import torch
+
+        torch.cuda.current_stream().synchronize()  # torch produced them; the library reads on its own stream
+    pim = (C.c_void_p * n)(*[ptr(a) for a in keep])
+    ih, iw, ic = (np.asarray(v, np.int32) for v in (hs, ws, cs))
+    return n, keep, pim, ih, iw, ic, Hs
+
+
+def _planar_view(view):
+    Hc, Wc = (int(v) for v in view["ImageSize"])
+    if Hc < 1 or Wc < 1:
+        raise ValueError("degenerate planar canvas")
+    return (Hc, Wc, float(view["XWorldLimits"][0]), float(view["YWorldLimits"][0]), float(view["PixelExtentInWorldX"]),
+            float(view["PixelExtentInWorldY"]))
+
+
+def planar_composite_bytes(shapes, canvas, blending="multiband", levels=3):
+    """Device memory (bytes) planar_composite requests for images of `shapes` [(h, w, c), ...] on a canvas (H, W): the
+    formula of aps_planar_composite_bytes (include/aps.h).  Host only; ValueError for arguments the composite refuses."""
+    ih, iw, ic = (np.asarray([int(s[i]) if len(s) > i else 1 for s in shapes], np.int32) for i in range(3))
+    mode = _BLEND.get(str(blending).lower())
+    if mode is None:
+        raise ValueError("Wrong blening mode.")
+    b = int(lib.aps_planar_composite_bytes(len(shapes), ptr(ih), ptr(iw), ptr(ic), int(canvas[0]), int(canvas[1]), mode, int(levels)))
+    if b < 0:
+        raise ValueError((lib.aps_last_error() or b"").decode("utf-8", "replace"))
+    return b
+
+
+def planar_footprints(shapes, tforms, view):
+    """The canvas rectangles planar_composite confines every image to: (rects [N,4] = x0, y0, x1, y1, 0-based half-open,
+    whole [N] = the whole-canvas fallback was taken).  Host only (aps_planar_footprints)."""
+    n = len(shapes)
+    if n == 0 or len(tforms) != n:
+        raise ValueError("shapes and tforms must be non-empty lists of equal length")
+    Hc, Wc, x0, y0, sx, sy = _planar_view(view)
+    ih, iw = (np.asarray([int(s[i]) for s in shapes], np.int32) for i in range(2))
+    Hs = np.stack([np.asarray(T, np.float64).T.reshape(9) for T in tforms])
+    rects, whole = np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+    check(lib.aps_planar_footprints(n, ptr(ih), ptr(iw), ptr(Hs), Hc, Wc, x0, y0, sx, sy, ptr(rects), ptr(whole)))
+    return rects, whole.astype(bool)
+
+
+def planar_gain_stats(images, tforms, view, ds=4):
+    """gain_overlap_stats_warped's result for the images warped to `view`, accumulated from the resident float4 layers of the
+    planar compositor (aps_planar_gain_stats): no canvas visits the host.  Returns (Nij, sumCi, sumCj) float64."""
+    n, keep, pim, ih, iw, ic, Hs = _planar_args(images, tforms)
+    Hc, Wc, x0, y0, sx, sy = _planar_view(view)
+    Nij = np.zeros((n, n), np.float64, order="F")
+    sCi = np.zeros((n, n, 3), np.float64, order="F")
+    sCj = np.zeros((n, n, 3), np.float64, order="F")
+    check(lib.aps_planar_gain_stats(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, int(ds),
+                                    ptr(Nij), ptr(sCi), ptr(sCj)))
+    del keep
+    return np.ascontiguousarray(Nij), np.ascontiguousarray(sCi), np.ascontiguousarray(sCj)
+
+
+def planar_composite(images, tforms, view, opts=None, gains=None, device_out=False):
+    """panorama = planar_composite(images, tforms, view, opts): the compositing of pureNonRotationalPanoramas
+    (renderPanorama.m:519-699) in one device-resident call (aps_planar_composite).  images: uint8 h x w x 3, h x w x 1 or
+    h x w, numpy arrays or resident CUDA tensors, sizes may differ; tforms: 3x3 homographies (H2refined); view: the canvas
+    (imref2dScratch).  opts: blending, pyrLevels, pyrSigma, canvasColor as pureNonRotationalPanoramas; with
+    opts['gainCompensation'] and no `gains` the overlap statistics are taken from the resident layers and solved on the host
+    (gainCompensationH).  Returns the uint8 out_h x out_w x 3 panorama (a CUDA tensor with device_out=True), byte-identical to
+    the host-orchestrated path."""
+    o = {"blending": "multiband", "pyrLevels": 3, "pyrSigma": 1.0, "canvasColor": "black", "sigmaN": 10.0, "sigmag": 0.1}
+    o.update(opts or {})
+    n, keep, pim, ih, iw, ic, Hs = _planar_args(images, tforms)
+    Hc, Wc, x0, y0, sx, sy = _planar_view(view)
+    mode = _BLEND.get(str(o["blending"]).lower())
+    if mode is None:
+        raise ValueError("Wrong blening mode.")
+    levels, sigma = int(o["pyrLevels"]), float(o["pyrSigma"])
+    if mode == _capi.APS_BLEND_MULTIBAND:
+        if int(o["pyrLevels"]) != o["pyrLevels"] or levels < 1:
+            raise ValueError("levels must be a positive integer")
+        if sigma <= 0:
+            raise ValueError("sigma must be positive")
+    if gains is None and o.get("gainCompensation"):
+        from .gainCompensation import solve_gains_H
+
+        if n <= 1:
+            gains = np.ones((n, 3), np.float32)
+        else:
+            gains = solve_gains_H(*planar_gain_stats(keep, tforms, view, max(1, int(o.get("overlapDownsample", 4)))), o)
+    g = None
+    if gains is not None:
+        g = np.stack([np.broadcast_to(np.asarray(x, np.float32).reshape(-1), (3,)) for x in gains]).astype(np.float32)
+        if g.shape != (n, 3):
+            raise ValueError("gains must be N x 3")
+        g = np.ascontiguousarray(g)
+    if device_out:
+        import torch
+
+        pano = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device="cuda")
+    else:
+        pano = np.zeros((Hc, Wc, 3), np.uint8)
+    check(lib.aps_planar_composite(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, mode, levels,
+                                   sigma, 1 if str(o["canvasColor"]).lower() == "white" else 0, ptr(g), ptr(pano), None))
+    del keep
+    return pano
+
+
+def _planar_device_covers(images, opts):
+    """The inputs aps_planar_composite covers: uint8 images of 1 or 3 channels (one channel count per set), at most 64."""
+    import os
+
+    if str((opts or {}).get("planarCompositor", "device")).lower() == "host" or os.environ.get("APS_PLANAR_HOST"):
+        return False
+    if not 1 <= len(images) <= 64:
+        return False
+    ch = set()
+    for im in images:
+        if _capi.is_torch(im):
+            import torch
+
+            if im.dtype != torch.uint8:
+                return False
+        elif np.asarray(im).dtype != np.uint8:
+            return False
+        if im.ndim not in (2, 3) or (im.ndim == 3 and int(im.shape[2]) not in (1, 3)):
+            return False
+        ch.add(1 if im.ndim == 2 else int(im.shape[2]))
+    return len(ch) == 1
+
+
+def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, device_out=False):
     """[panorama, rgbAnnotation] = pureNonRotationalPanoramas(images, cameras, numImages, opts)
     (renderPanorama.m:519-699): planar-scan compositing.  Canvas = bounding box of all H2refined corner
-    maps with MATLAB-rounded size (:547-575); every image warped to the FULL canvas; then whole-canvas
+    maps with MATLAB-rounded size (:547-575), computed here in f64; then every image is warped to it and blended
     'none' (winner-take-all by weight, first maximum) / 'linear' / 'multiband'; void pixels painted; uint8.
-    Gains: pass `gains` (N x 3), or set opts['gainCompensation'] to have gainCompensationH run on the warped canvases
+    The compositing runs in one device-resident call (planar_composite) for uint8 images of 1 or 3 channels, at most 64;
+    other inputs, opts['planarCompositor'] = 'host' and APS_PLANAR_HOST=1 take the host-orchestrated path
+    (_planar_host: every image warped to the FULL canvas by imageWarp, numpy in between), whose bytes the device path
+    reproduces.
+    Gains: pass `gains` (N x 3), or set opts['gainCompensation'] to have gainCompensationH run on the warped images
     (:584-591: overlap statistics on the device, solve on the host); otherwise ones."""
-    from .blending import linearBlending, multiBandBlending
     from .imageProcessing import imref2dScratch, outputLimitsScratch
 
     o = {"blending": "multiband", "pyrLevels": 3, "pyrSigma": 1.0, "canvasColor": "black",
          "sigmaN": 10.0, "sigmag": 0.1}  # (renderPanorama.m:56-58: the defaults opts carries into gainCompensationH)
     o.update(opts or {})
+    images = [im if _capi.is_torch(im) else np.asarray(im) for im in images[:numImages]]
     tforms = [np.asarray(cam["H2refined"], np.float64) for cam in cameras[:numImages]]
-    lims = [outputLimitsScratch(T, (1, np.asarray(im).shape[1]), (1, np.asarray(im).shape[0]))
+    lims = [outputLimitsScratch(T, (1, int(im.shape[1])), (1, int(im.shape[0])))
             for T, im in zip(tforms, images)]
     xMin, xMax = min(l[0][0] for l in lims), max(l[0][1] for l in lims)
     yMin, yMax = min(l[1][0] for l in lims), max(l[1][1] for l in lims)
@@ -416,6 +576,30 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None):
     if width < 1 or height < 1:
         raise ValueError("degenerate planar canvas")
     view = imref2dScratch((height, width), (xMin, xMax), (yMin, yMax))
+    if _planar_device_covers(images, o):
+        if str(o["blending"]).lower() not in _BLEND:
+            raise ValueError("Wrong blening mode.")
+        pano = planar_composite(images, tforms, view, o, gains, device_out)
+        gray = images[0].ndim == 2 or int(images[0].shape[2]) == 1
+        one = gains is None and not o.get("gainCompensation") or gains is not None and all(np.size(g) == 1 for g in gains)
+        if gray and one and str(o["blending"]).lower() == "none":
+            pano = pano[:, :, :1]  # (the host path's 'none' keeps the single channel of its input; the blends return three)
+        return pano, None
+    if any(_capi.is_torch(im) for im in images):
+        images = [im.cpu().numpy() if _capi.is_torch(im) else im for im in images]
+    pano = _planar_host(images, tforms, view, o, gains)
+    if device_out:
+        import torch
+
+        pano = torch.from_numpy(pano).cuda()
+    return pano, None
+
+
+def _planar_host(images, tforms, view, o, gains=None):
+    """The host-orchestrated compositing of pureNonRotationalPanoramas: 2N whole-canvas imageWarp calls, gains, the blend
+    operators and the uint8 tail in numpy.  The yardstick of planar_composite and the path of inputs it does not cover."""
+    from .blending import linearBlending, multiBandBlending
+
     Iw, Ww, _, _, _ = pureNonRotationalImagesToCanvas(images, tforms, view, warpWeights(images), o)
     if gains is None and o.get("gainCompensation"):
         # renderPanorama.m:584-591: gains from the warped canvases (statistics on the device, N x N solve on the host).  As
@@ -441,7 +625,7 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None):
     pano[void] = 1.0 if str(o["canvasColor"]).lower() == "white" else 0.0
     v = 255.0 * pano.astype(np.float64)
     out = np.sign(v) * np.floor(np.abs(v) + 0.5)  # MATLAB round
-    return np.clip(out, 0, 255).astype(np.uint8), None
+    return np.clip(out, 0, 255).astype(np.uint8)
 
 
 def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gains=None,
@@ -456,7 +640,7 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
       * annotations (insertShape/insertText) are not produced: rgbAnnotation is always None."""
     if cameras and (cameras[0].get("noRotation", 0) == 1 or input.get("forcePlanarScan", False)):
         # renderPanorama.m:78-90: planar scans bypass the tiled ray renderer
-        pano, ann = pureNonRotationalPanoramas(images, cameras, len(images), opts or {}, gains)
+        pano, ann = pureNonRotationalPanoramas(images, cameras, len(images), opts or {}, gains, device_out)
         return (pano, ann, None, None) if return_covered else (pano, ann)
     o = default_opts(opts, cameras, refIdx)
     imgSize = [tuple(int(v) for v in s) for s in imgSize]

@@ -551,6 +551,64 @@ int aps_image_warp_u8(const uint8_t* in, int in_h, int in_w, int c, const double
 int aps_image_warp_f32(const float* in, int in_h, int in_w, int c, const double* H, int out_h, int out_w, double x0,
                        double y0, double sx, double sy, float fill, int method, float* out);
 
+/* Planar scans -- pureNonRotationalPanoramas on the device (PP/renderPanorama/renderPanorama.m:519-699; the warp of
+ * PP/imageProcessing/imageWarp.m:125-168; the statistics of PP/gainCompensation/gainCompensationH.m).  One call takes the uint8
+ * images and their H2refined homographies and returns the uint8 panorama; no canvas-sized array visits the host.
+ *   images[k]: uint8 img_h[k] x img_w[k] x img_c[k] (c = 1 or 3), row-major interleaved, host or device memory like every other
+ *   buffer of this library; sizes may differ per image.  H: n_img 3x3 f64 matrices, column-major each, as aps_image_warp_* takes
+ *   them.  out_h, out_w, x0, y0, sx, sy: the canvas (imref2dScratch: ImageSize, XWorldLimits(1), YWorldLimits(1),
+ *   PixelExtentInWorldX/Y); its size is the caller's computation (outputLimitsScratch, :547-575) and is not re-derived here.
+ *   blending: APS_BLEND_*; levels, sigma: multiBandBlending's (used by APS_BLEND_MULTIBAND only).  white_canvas: void pixels
+ *   (no image has weight > 0 there) become 255 instead of 0.  gains: f32 n_img x 3 row-major, or NULL for ones (:584-591: one
+ *   f32 multiply per channel after the warp).  pano: uint8 out_h x out_w x 3 row-major interleaved (a single-channel image is
+ *   replicated); covered (optional, may be NULL): uint8 out_h x out_w, 1 where some image has weight > 0.
+ * Per canvas pixel and image: source value (float)u8 / 255, the inverse map, validity test and four-tap f64 sum of
+ * aps_image_warp_f32 'bilinear' (fill 0), the weight = the same warp of warpWeights' tent map (:1282-1312) clamped to [0, 1];
+ * 'none' = the first image of maximal weight, 'linear' = linearBlending, 'multiband' = multiBandBlending and max(0, min(1, .));
+ * then uint8(round(255 * v)) with the product in f64 and MATLAB's round.  The result equals, byte for byte, what
+ * aps_image_warp_f32 + aps_multiband_blend / aps_linear_blend and the host arithmetic between them give.  Every image is
+ * written and read inside its footprint only (the canvas bounding box of its forward-mapped border, grown conservatively; the
+ * whole canvas when the homography's denominator changes sign over the image); APS_PLANAR_NO_CULL=1 in the environment forces
+ * whole-canvas footprints (same bytes).
+ * Before its first launch the call compares aps_planar_composite_bytes(...) with the free device memory and returns APS_E_OOM
+ * with a message naming both figures when the composite cannot fit (renderPanorama.m:245-266: skip this panorama).
+ * Errors: APS_E_ARG for a NULL argument, n_img < 1, an unknown blending, levels < 1, sigma <= 0 (or one whose filter has more
+ * than 9 taps), non-positive sx / sy, a singular or non-finite homography; APS_E_DIM for a bad image or canvas size and for more
+ * than 64 images (the limit of the weight normalisation's layer mask, as in the tiled renderer).  None of them reaches a launch. */
+int aps_planar_composite(const uint8_t* const* images, const int* img_h, const int* img_w, const int* img_c, int n_img,
+                         const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int blending, int levels,
+                         float sigma, int white_canvas, const float* gains, uint8_t* pano, uint8_t* covered);
+/* Host only (no device needed): the device memory aps_planar_composite requests for these shapes, in bytes, or a negative
+ * APS_E_* code for arguments the composite would refuse.  With P = out_h * out_w and sum over the images:
+ *   sum(h*w*c) + 4 * sum(h + w)      staged images, tent tables
+ *   + 160 * n + 16 * n * P           job table, float4 layers
+ *   + P + 3 * P                      coverage, panorama
+ * and for APS_BLEND_MULTIBAND, with L = max(1, min(levels, floor(log2(min(out_h, out_w))))), P_0 = P, P_l the pixels of level l
+ * (each side max(1, floor(side / 2)) of the level above), D = P_1 + .. + P_(L-1), I = P_1 + .. + P_(L-2):
+ *   + 16 * P                         blended image
+ *   + 16 * n * D                     Gaussian levels 1..L-1 of every layer
+ *   + 16 * min(n, 16) * P if L > 1   blurred level of one batch of layers
+ *   + 16 * (P + D) + 16 * I          numerator pyramid, collapse buffers
+ * (Requests are rounded up to 256 bytes each by the workspace pool; images and outputs already in device memory are not
+ * staged, so the figure is an upper bound for them.) */
+int64_t aps_planar_composite_bytes(int n_img, const int* img_h, const int* img_w, const int* img_c, int out_h, int out_w,
+                                   int blending, int levels);
+/* gainCompensationH's overlap statistics (gainCompensationH.m:45-52,78-149) from the same resident layers, before gains: every
+ * `downsample`-th row and column of the canvas, valid = weight > 0 and finite colour, pairs i < j whose footprints intersect.
+ * Arguments as aps_planar_composite, outputs as aps_gain_overlap_stats_warped (f64 N x N and N x N x 3, column-major, upper
+ * triangle; counts exact, sums in an unspecified order).  The N x N solve stays with the caller, who passes the gains to
+ * aps_planar_composite; that call warps again and applies them with the same single f32 multiply. */
+int aps_planar_gain_stats(const uint8_t* const* images, const int* img_h, const int* img_w, const int* img_c, int n_img,
+                          const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int downsample,
+                          double* n_ij, double* sum_ci, double* sum_cj);
+/* Host only, for tests and callers that plan memory: the footprints aps_planar_composite uses (without APS_PLANAR_NO_CULL).
+ * rects: int n_img x 4 = (x0, y0, x1, y1), 0-based half-open canvas columns and rows, clipped to the canvas; whole (optional):
+ * 1 where the whole-canvas fallback was taken (horizon across or too close to the image). */
+int aps_planar_footprints(int n_img, const int* img_h, const int* img_w, const double* H, int out_h, int out_w, double x0, double y0,
+                          double sx, double sy, int* rects, int* whole);
+/* Host only: warpWeights' 1-D tent factor of length n (renderPanorama.m:1282-1312), f32, as the composite builds it. */
+int aps_planar_tent(int n, float* t);
+
 /* ============================================================================================
  * (4) SIFT — PP/featureMatching/getFeaturePoints.m:36-40,71-74
  * ============================================================================================ */

@@ -156,6 +156,20 @@ function panorama = planarScanPanorama(images, cameras, numImages, opts)
     xMin = min(lims(:, 1)); xMax = max(lims(:, 2)); yMin = min(lims(:, 3)); yMax = max(lims(:, 4));
     width = round(xMax - xMin); height = round(yMax - yMin);
     view = imref2dScratch([height width], [xMin xMax], [yMin yMax]);
+    if all(cellfun(@(im) isa(im, 'uint8') && any(size(im, 3) == [1 3]), images(1:numImages))) && numImages <= 64
+        % one device-resident call (aps_planar_composite): no canvas-sized array visits the host; same bytes as the body below
+        Hs = zeros(3, 3, numImages);
+        for k = 1:numImages
+            Hs(:, :, k) = cameras(k).H2refined;
+        end
+        mode = find(strcmpi(opts.blending, {'none', 'linear', 'multiband'})) - 1;
+        if isempty(mode), mode = 2; end
+        panorama = aps_mex('planar_composite', images(1:numImages), Hs, [height width], view.XWorldLimits(1), view.YWorldLimits(1), ...
+                           view.PixelExtentInWorldX, view.PixelExtentInWorldY, mode, opts.pyrLevels, opts.pyrSigma, ...
+                           strcmpi(opts.canvasColor, 'white'), []);
+        return;
+    end
+    % other image classes: the host-orchestrated chain over the imageWarp shadow
     Iw = cell(1, numImages); Ww = cell(1, numImages);
     for k = 1:numImages
         [h, w, ~] = size(images{k});
