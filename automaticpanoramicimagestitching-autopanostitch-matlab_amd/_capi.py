@@ -150,13 +150,17 @@ _SIGNATURES = {
     "aps_planar_composite": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _d, _d, _i, _i, _f, _i, _vp, _vp, _vp],
     "aps_planar_composite_bytes": [_i, _vp, _vp, _vp, _i, _i, _i, _i],
     "aps_planar_gain_stats": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _vp],
+    "aps_planar_composite_compact": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _d, _d, _i, _i, _f, _i, _vp, _vp, _vp],
+    "aps_planar_composite_compact_bytes": [_i, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _d, _d, _i, _i],
+    "aps_planar_gain_stats_compact": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _vp],
     "aps_planar_footprints": [_i, _vp, _vp, _vp, _i, _i, _d, _d, _d, _d, _vp, _vp],
     "aps_planar_tent": [_i, _vp],
     "aps_synth_view": [_vp, _vp, _i, _i, C.c_uint, _f, _f, _vp],
     "aps_sift_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_sift_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
 }
-_RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64}
+_RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
+             "aps_planar_composite_compact_bytes": C.c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -467,7 +467,7 @@ def planar_footprints(shapes, tforms, view):
     return rects, whole.astype(bool)
 
 
-def planar_gain_stats(images, tforms, view, ds=4):
+def planar_gain_stats(images, tforms, view, ds=4, _entry="aps_planar_gain_stats"):
     """gain_overlap_stats_warped's result for the images warped to `view`, accumulated from the resident float4 layers of the
     planar compositor (aps_planar_gain_stats): no canvas visits the host.  Returns (Nij, sumCi, sumCj) float64."""
     n, keep, pim, ih, iw, ic, Hs = _planar_args(images, tforms)
@@ -475,13 +475,47 @@ def planar_gain_stats(images, tforms, view, ds=4):
     Nij = np.zeros((n, n), np.float64, order="F")
     sCi = np.zeros((n, n, 3), np.float64, order="F")
     sCj = np.zeros((n, n, 3), np.float64, order="F")
-    check(lib.aps_planar_gain_stats(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, int(ds),
-                                    ptr(Nij), ptr(sCi), ptr(sCj)))
+    check(getattr(lib, _entry)(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, int(ds),
+                               ptr(Nij), ptr(sCi), ptr(sCj)))
     del keep
     return np.ascontiguousarray(Nij), np.ascontiguousarray(sCi), np.ascontiguousarray(sCj)
 
 
-def planar_composite(images, tforms, view, opts=None, gains=None, device_out=False):
+def planar_gain_stats_compact(images, tforms, view, ds=4):
+    """planar_gain_stats from the footprint-compact layers (aps_planar_gain_stats_compact): any number of images up to 65535,
+    device memory that follows the footprints.  Same outputs."""
+    return planar_gain_stats(images, tforms, view, ds, _entry="aps_planar_gain_stats_compact")
+
+
+def planar_composite_compact_bytes(shapes, canvas, tforms, view, blending="multiband", levels=3):
+    """Device memory (bytes) planar_composite_compact requests: the formula of aps_planar_composite_compact_bytes
+    (include/aps.h), which follows the footprints and therefore takes the homographies and the canvas `view` (`canvas` must be
+    its ImageSize).  Host only; ValueError for arguments the composite refuses."""
+    ih, iw, ic = (np.asarray([int(s[i]) if len(s) > i else 1 for s in shapes], np.int32) for i in range(3))
+    mode = _BLEND.get(str(blending).lower())
+    if mode is None:
+        raise ValueError("Wrong blening mode.")
+    if len(tforms) != len(shapes):
+        raise ValueError("shapes and tforms must be lists of equal length")
+    Hc, Wc, x0, y0, sx, sy = _planar_view(view)
+    if (int(canvas[0]), int(canvas[1])) != (Hc, Wc):
+        raise ValueError("canvas must be the view's ImageSize")
+    Hs = np.stack([np.asarray(T, np.float64).T.reshape(9) for T in tforms]) if len(shapes) else np.zeros((0, 9))
+    b = int(lib.aps_planar_composite_compact_bytes(len(shapes), ptr(ih), ptr(iw), ptr(ic), ptr(np.ascontiguousarray(Hs)), Hc, Wc,
+                                                   x0, y0, sx, sy, mode, int(levels)))
+    if b < 0:
+        raise ValueError((lib.aps_last_error() or b"").decode("utf-8", "replace"))
+    return b
+
+
+def planar_composite_compact(images, tforms, view, opts=None, gains=None, device_out=False):
+    """planar_composite through the footprint-compact compositor (aps_planar_composite_compact, with
+    aps_planar_gain_stats_compact for opts['gainCompensation']): the same bytes for any number of images, every layer stored
+    inside its footprint only."""
+    return planar_composite(images, tforms, view, opts, gains, device_out, _compact=True)
+
+
+def planar_composite(images, tforms, view, opts=None, gains=None, device_out=False, _compact=False):
     """panorama = planar_composite(images, tforms, view, opts): the compositing of pureNonRotationalPanoramas
     (renderPanorama.m:519-699) in one device-resident call (aps_planar_composite).  images: uint8 h x w x 3, h x w x 1 or
     h x w, numpy arrays or resident CUDA tensors, sizes may differ; tforms: 3x3 homographies (H2refined); view: the canvas
@@ -508,7 +542,8 @@ def planar_composite(images, tforms, view, opts=None, gains=None, device_out=Fal
         if n <= 1:
             gains = np.ones((n, 3), np.float32)
         else:
-            gains = solve_gains_H(*planar_gain_stats(keep, tforms, view, max(1, int(o.get("overlapDownsample", 4)))), o)
+            stats = planar_gain_stats_compact if _compact else planar_gain_stats
+            gains = solve_gains_H(*stats(keep, tforms, view, max(1, int(o.get("overlapDownsample", 4)))), o)
     g = None
     if gains is not None:
         g = np.stack([np.broadcast_to(np.asarray(x, np.float32).reshape(-1), (3,)) for x in gains]).astype(np.float32)
@@ -521,33 +556,57 @@ def planar_composite(images, tforms, view, opts=None, gains=None, device_out=Fal
         pano = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device="cuda")
     else:
         pano = np.zeros((Hc, Wc, 3), np.uint8)
-    check(lib.aps_planar_composite(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, mode, levels,
-                                   sigma, 1 if str(o["canvasColor"]).lower() == "white" else 0, ptr(g), ptr(pano), None))
+    entry = getattr(lib, "aps_planar_composite_compact" if _compact else "aps_planar_composite")
+    check(entry(C.addressof(pim), ptr(ih), ptr(iw), ptr(ic), n, ptr(Hs), Hc, Wc, x0, y0, sx, sy, mode, levels, sigma,
+                1 if str(o["canvasColor"]).lower() == "white" else 0, ptr(g), ptr(pano), None))
     del keep
     return pano
 
 
 def _planar_device_covers(images, opts):
-    """The inputs aps_planar_composite covers: uint8 images of 1 or 3 channels (one channel count per set), at most 64."""
+    """The inputs the device compositors cover: uint8 images of 1 or 3 channels (one channel count per set).  Returns None
+    (the host path), 'device' (aps_planar_composite: at most 64 images) or 'compact' (aps_planar_composite_compact: asked for
+    with opts['planarCompositor'] = 'compact', or more than 64 images)."""
     import os
 
-    if str((opts or {}).get("planarCompositor", "device")).lower() == "host" or os.environ.get("APS_PLANAR_HOST"):
-        return False
-    if not 1 <= len(images) <= 64:
-        return False
+    which = str((opts or {}).get("planarCompositor", "device")).lower()
+    if which == "host" or os.environ.get("APS_PLANAR_HOST"):
+        return None
+    if len(images) < 1:
+        return None
     ch = set()
     for im in images:
         if _capi.is_torch(im):
             import torch
 
             if im.dtype != torch.uint8:
-                return False
+                return None
         elif np.asarray(im).dtype != np.uint8:
-            return False
+            return None
         if im.ndim not in (2, 3) or (im.ndim == 3 and int(im.shape[2]) not in (1, 3)):
-            return False
+            return None
         ch.add(1 if im.ndim == 2 else int(im.shape[2]))
-    return len(ch) == 1
+    if len(ch) != 1:
+        return None
+    return "compact" if which == "compact" or len(images) > 64 else "device"
+
+
+def _planar_device_composite(route, images, tforms, view, o, gains, device_out):
+    """The dense compositor wherever it runs; the compact one when asked for, for more than 64 images, and when the dense
+    request (planar_composite_bytes) exceeds opts['planarDenseLimitBytes'] - by default the free device memory at the time
+    of the call, which is what the dense call itself compares its request with (APS_E_OOM before any launch)."""
+    if route == "device" and o.get("planarDenseLimitBytes") is not None:
+        shapes = [(int(im.shape[0]), int(im.shape[1]), 1 if im.ndim == 2 else int(im.shape[2])) for im in images]
+        levels = o["pyrLevels"] if str(o["blending"]).lower() == "multiband" else 1
+        if planar_composite_bytes(shapes, view["ImageSize"], o["blending"], levels) > int(o["planarDenseLimitBytes"]):
+            route = "compact"
+    if route == "device":
+        try:
+            return planar_composite(images, tforms, view, o, gains, device_out)
+        except _capi.ApsError as e:
+            if e.code != _capi.APS_E_OOM or o.get("planarDenseLimitBytes") is not None:
+                raise
+    return planar_composite_compact(images, tforms, view, o, gains, device_out)
 
 
 def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, device_out=False):
@@ -555,7 +614,10 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
     (renderPanorama.m:519-699): planar-scan compositing.  Canvas = bounding box of all H2refined corner
     maps with MATLAB-rounded size (:547-575), computed here in f64; then every image is warped to it and blended
     'none' (winner-take-all by weight, first maximum) / 'linear' / 'multiband'; void pixels painted; uint8.
-    The compositing runs in one device-resident call (planar_composite) for uint8 images of 1 or 3 channels, at most 64;
+    The compositing runs in one device-resident call for uint8 images of 1 or 3 channels: planar_composite (one
+    canvas-sized layer per image) for up to 64 images that fit, planar_composite_compact (footprint-sized layers) for more
+    images, for sets whose dense request exceeds opts['planarDenseLimitBytes'] (default: the free device memory) and with
+    opts['planarCompositor'] = 'compact';
     other inputs, opts['planarCompositor'] = 'host' and APS_PLANAR_HOST=1 take the host-orchestrated path
     (_planar_host: every image warped to the FULL canvas by imageWarp, numpy in between), whose bytes the device path
     reproduces.
@@ -576,10 +638,11 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
     if width < 1 or height < 1:
         raise ValueError("degenerate planar canvas")
     view = imref2dScratch((height, width), (xMin, xMax), (yMin, yMax))
-    if _planar_device_covers(images, o):
+    route = _planar_device_covers(images, o)
+    if route:
         if str(o["blending"]).lower() not in _BLEND:
             raise ValueError("Wrong blening mode.")
-        pano = planar_composite(images, tforms, view, o, gains, device_out)
+        pano = _planar_device_composite(route, images, tforms, view, o, gains, device_out)
         gray = images[0].ndim == 2 or int(images[0].shape[2]) == 1
         one = gains is None and not o.get("gainCompensation") or gains is not None and all(np.size(g) == 1 for g in gains)
         if gray and one and str(o["blending"]).lower() == "none":

@@ -601,6 +601,50 @@ int64_t aps_planar_composite_bytes(int n_img, const int* img_h, const int* img_w
 int aps_planar_gain_stats(const uint8_t* const* images, const int* img_h, const int* img_w, const int* img_c, int n_img,
                           const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int downsample,
                           double* n_ij, double* sum_ci, double* sum_cj);
+/* The footprint-compact planar compositor (PP/renderPanorama/renderPanorama.m:519-699, PP/imageProcessing/imageWarp.m:125-168,
+ * PP/blending/multiBandBlending.m:72-167, PP/gainCompensation/gainCompensationH.m:45-52,78-149): arguments, semantics, argument
+ * errors and result BYTES of aps_planar_composite, for scan sets that call cannot take -- many views, each covering a small part
+ * of a large canvas.  Every layer is stored inside its footprint only (its own pitch), at level 0 and at every pyramid level
+ * (the footprint grown by the filter radius, mapped through the resize, clipped to the level: the rectangles the dense call
+ * confines its kernels to); a horizon-crossing homography makes that one layer canvas-sized; APS_PLANAR_NO_CULL=1 makes them
+ * all canvas-sized (same bytes).  The host builds, per level and 64 x 64 block of the canvas, the ascending list of images
+ * whose footprint meets the block and uploads the lists once; weight normalisation, 'none', 'linear', the Laplacian
+ * accumulation (one pass per level for all contributors) and the gain statistics walk the list of their block, so the work
+ * per pixel follows the overlap and not n_img.  Per pixel the layer arithmetic is the dense call's (one shared device
+ * function), every sum runs in ascending image order from +0.0, the Gaussian and resize chains are those of the dense
+ * pyramid, the uint8 tail is the same.
+ * Limits: no cap on n_img other than int32 indexing: n_img * (2 * L - 1) and the total length of the contributor lists (below)
+ * must stay under 2^31 (APS_E_DIM otherwise); out_h * out_w < 2^31 as in the dense call.
+ * Before its first launch the call compares aps_planar_composite_compact_bytes(...) with the free device memory and returns
+ * APS_E_OOM naming both figures.  One host synchronisation, at the end of the call. */
+int aps_planar_composite_compact(const uint8_t* const* images, const int* img_h, const int* img_w, const int* img_c, int n_img,
+                                 const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int blending,
+                                 int levels, float sigma, int white_canvas, const float* gains, uint8_t* pano, uint8_t* covered);
+/* Host only (no device needed): the device memory aps_planar_composite_compact requests, in bytes, or a negative APS_E_* code
+ * for arguments the composite would refuse.  The footprints depend on the homographies and the canvas, so they are arguments.
+ * With P = out_h * out_w, L = 1 for 'none' / 'linear' and max(1, min(levels, floor(log2(min(out_h, out_w))))) for multiband,
+ * G(l,k) the footprint of image k at level l (G(0,k) = aps_planar_footprints; B(l,k) = G(l,k) grown by r = 4 on every side and
+ * clipped to the level; G(l+1,k) = the output pixels of the resize that can see B(l,k)), |.| the pixels of a
+ * rectangle, blocks(l) = ceil(h_l / 64) * ceil(w_l / 64), entries(l) = sum over k of the 64 x 64 blocks G(l,k) meets:
+ *   sum(h*w*c) + 4 * sum(h + w)                      staged images, tent tables
+ *   + 160 * n + 32 * n * (2 * L - 1)                 job table, layer tables (levels and blurred levels)
+ *   + 16 * sum_l sum_k |G(l,k)|                      float4 layers, every level, inside their footprints
+ *   + 16 * max_(l < L-1) sum_k |B(l,k)|              blurred layers of one level (0 for L = 1)
+ *   + 4 * sum_l (blocks(l) + 1 + entries(l))         contributor lists
+ *   + P + 3 * P                                      coverage, panorama
+ * and for APS_BLEND_MULTIBAND, with D and I as in aps_planar_composite_bytes:
+ *   + 16 * P + 16 * (P + D) + 16 * I                 blended image, numerator pyramid, collapse buffers
+ * No term multiplies n by P.  r = 4 is the radius of the widest filter built (9 taps): the formula does not take sigma, and a
+ * narrower filter requests less. */
+int64_t aps_planar_composite_compact_bytes(int n_img, const int* img_h, const int* img_w, const int* img_c, const double* H,
+                                           int out_h, int out_w, double x0, double y0, double sx, double sy, int blending,
+                                           int levels);
+/* aps_planar_gain_stats from the compact layers (gainCompensationH.m:45-52,78-149): same arguments, outputs and tolerance
+ * contract (counts exact, sums in an unspecified order); the pairs of a sampled point are taken from its block's list.
+ * n_img <= 65535 (a pair is keyed i * n_img + j + 1 in 32 bits; the three outputs hold 7 * n_img^2 doubles); APS_E_DIM above. */
+int aps_planar_gain_stats_compact(const uint8_t* const* images, const int* img_h, const int* img_w, const int* img_c, int n_img,
+                                  const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int downsample,
+                                  double* n_ij, double* sum_ci, double* sum_cj);
 /* Host only, for tests and callers that plan memory: the footprints aps_planar_composite uses (without APS_PLANAR_NO_CULL).
  * rects: int n_img x 4 = (x0, y0, x1, y1), 0-based half-open canvas columns and rows, clipped to the canvas; whole (optional):
  * 1 where the whole-canvas fallback was taken (horizon across or too close to the image). */

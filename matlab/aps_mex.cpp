@@ -610,11 +610,8 @@ static void cmd_crop_bbox(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
 
 // panorama = aps_mex('planar_composite', images (1 x N cell of uint8 h x w x c, c = 1 or 3), H (3 x 3 x N double), [oh ow], x0, y0,
 //                    sx, sy, blending (0 none | 1 linear | 2 multiband), levels, sigma, canvasWhite, gains (N x 3 or [] for ones))
-// pureNonRotationalPanoramas (renderPanorama.m:519-699) in one device-resident call; uint8 oh x ow x 3.
-static void cmd_planar_composite(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    (void)nlhs;
-    need(nrhs == 13 && mxIsCell(prhs[1]) && mxIsDouble(prhs[2]), "aps:type",
-         "usage: images (cell of uint8), H 3x3xN double, [oh ow], x0, y0, sx, sy, blending, levels, sigma, canvasWhite, gains");
+// pureNonRotationalPanoramas (renderPanorama.m:519-699) in one device-resident call; uint8 oh x ow x 3.  (Body of both planar commands.)
+static void planar_composite_any(bool compact, mxArray* plhs[], const mxArray* prhs[]) {
     const int n = (int)mxGetNumberOfElements(prhs[1]);
     need(n >= 1 && mxGetNumberOfElements(prhs[2]) == (size_t)9 * n, "aps:dim", "H must be 3 x 3 x N for N images");
     std::vector<std::vector<uint8_t>> rows(n);
@@ -643,16 +640,32 @@ static void cmd_planar_composite(int nlhs, mxArray* plhs[], int nrhs, const mxAr
             for (int c = 0; c < 3; ++c) gains[3 * k + c] = (float)mxGetPr(prhs[12])[k + (size_t)n * c];
     }
     std::vector<uint8_t> out((size_t)oh * ow * 3);
-    check(aps_planar_composite(ptrs.data(), ih.data(), iw.data(), ic.data(), n, mxGetPr(prhs[2]), oh, ow, mxGetScalar(prhs[4]),
-                               mxGetScalar(prhs[5]), mxGetScalar(prhs[6]), mxGetScalar(prhs[7]), (int)mxGetScalar(prhs[8]),
-                               (int)mxGetScalar(prhs[9]), (float)mxGetScalar(prhs[10]), mxGetScalar(prhs[11]) != 0,
-                               gains.empty() ? nullptr : gains.data(), out.data(), nullptr));
+    check((compact ? aps_planar_composite_compact : aps_planar_composite)(
+        ptrs.data(), ih.data(), iw.data(), ic.data(), n, mxGetPr(prhs[2]), oh, ow, mxGetScalar(prhs[4]), mxGetScalar(prhs[5]),
+        mxGetScalar(prhs[6]), mxGetScalar(prhs[7]), (int)mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[9]), (float)mxGetScalar(prhs[10]),
+        mxGetScalar(prhs[11]) != 0, gains.empty() ? nullptr : gains.data(), out.data(), nullptr));
     const mwSize dims[3] = {(mwSize)oh, (mwSize)ow, 3};
     plhs[0] = mxCreateNumericArray(3, dims, mxUINT8_CLASS, mxREAL);
     uint8_t* dst = (uint8_t*)mxGetData(plhs[0]);
     for (int q = 0; q < 3; ++q)
         for (int x = 0; x < ow; ++x)
             for (int y = 0; y < oh; ++y) dst[(size_t)q * oh * ow + (size_t)x * oh + y] = out[((size_t)y * ow + x) * 3 + q];
+}
+
+static void cmd_planar_composite(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    need(nrhs == 13 && mxIsCell(prhs[1]) && mxIsDouble(prhs[2]), "aps:type",
+         "usage: images (cell of uint8), H 3x3xN double, [oh ow], x0, y0, sx, sy, blending, levels, sigma, canvasWhite, gains");
+    planar_composite_any(false, plhs, prhs);
+}
+
+// panorama = aps_mex('planar_composite_compact', <the arguments of 'planar_composite'>): the same panorama from the
+// footprint-compact compositor (aps_planar_composite_compact): any number of images, device memory that follows the footprints.
+static void cmd_planar_composite_compact(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    (void)nlhs;
+    need(nrhs == 13 && mxIsCell(prhs[1]) && mxIsDouble(prhs[2]), "aps:type",
+         "usage: images (cell of uint8), H 3x3xN double, [oh ow], x0, y0, sx, sy, blending, levels, sigma, canvasWhite, gains");
+    planar_composite_any(true, plhs, prhs);
 }
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -683,5 +696,6 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (cmd == "image_warp") cmd_image_warp(nlhs, plhs, nrhs, prhs);
     else if (cmd == "crop_nonzero_bbox") cmd_crop_bbox(nlhs, plhs, nrhs, prhs);
     else if (cmd == "planar_composite") cmd_planar_composite(nlhs, plhs, nrhs, prhs);
+    else if (cmd == "planar_composite_compact") cmd_planar_composite_compact(nlhs, plhs, nrhs, prhs);
     else mexErrMsgIdAndTxt("aps:args", "unknown command '%s'", cmd.c_str());
 }

@@ -156,15 +156,29 @@ function panorama = planarScanPanorama(images, cameras, numImages, opts)
     xMin = min(lims(:, 1)); xMax = max(lims(:, 2)); yMin = min(lims(:, 3)); yMax = max(lims(:, 4));
     width = round(xMax - xMin); height = round(yMax - yMin);
     view = imref2dScratch([height width], [xMin xMax], [yMin yMax]);
-    if all(cellfun(@(im) isa(im, 'uint8') && any(size(im, 3) == [1 3]), images(1:numImages))) && numImages <= 64
-        % one device-resident call (aps_planar_composite): no canvas-sized array visits the host; same bytes as the body below
+    if all(cellfun(@(im) isa(im, 'uint8') && any(size(im, 3) == [1 3]), images(1:numImages)))
+        % one device-resident call: no canvas-sized array visits the host; same bytes as the body below.  The dense compositor
+        % (aps_planar_composite: one canvas-sized layer per image, at most 64) where it runs; the footprint-compact one
+        % (aps_planar_composite_compact) for more than 64 images, when the dense one reports that it cannot fit (aps:oom), and
+        % with opts.planarCompositor = 'compact'.
         Hs = zeros(3, 3, numImages);
         for k = 1:numImages
             Hs(:, :, k) = cameras(k).H2refined;
         end
         mode = find(strcmpi(opts.blending, {'none', 'linear', 'multiband'})) - 1;
         if isempty(mode), mode = 2; end
-        panorama = aps_mex('planar_composite', images(1:numImages), Hs, [height width], view.XWorldLimits(1), view.YWorldLimits(1), ...
+        compact = numImages > 64 || (isfield(opts, 'planarCompositor') && strcmpi(opts.planarCompositor, 'compact'));
+        if ~compact
+            try
+                panorama = aps_mex('planar_composite', images(1:numImages), Hs, [height width], view.XWorldLimits(1), view.YWorldLimits(1), ...
+                                   view.PixelExtentInWorldX, view.PixelExtentInWorldY, mode, opts.pyrLevels, opts.pyrSigma, ...
+                                   strcmpi(opts.canvasColor, 'white'), []);
+                return;
+            catch err
+                if ~strcmp(err.identifier, 'aps:oom'), rethrow(err); end
+            end
+        end
+        panorama = aps_mex('planar_composite_compact', images(1:numImages), Hs, [height width], view.XWorldLimits(1), view.YWorldLimits(1), ...
                            view.PixelExtentInWorldX, view.PixelExtentInWorldY, mode, opts.pyrLevels, opts.pyrSigma, ...
                            strcmpi(opts.canvasColor, 'white'), []);
         return;
