@@ -176,6 +176,14 @@ struct Out {
             APS_HIP(hipStreamSynchronize(stream()));
         }
     }
+    // Copies back `rows` runs of `width` elements that lie `ld` elements apart (a matrix with a caller-given leading
+    // dimension): the elements between the runs belong to the caller and are not written, as with a device target.
+    void commit_2d(size_t width, size_t rows, size_t ld) {
+        if (!host || width == 0 || rows == 0) return;
+        if (ld == width || rows == 1) return commit(width * rows);
+        APS_HIP(hipMemcpy2DAsync(host, ld * sizeof(T), d, ld * sizeof(T), width * sizeof(T), rows, hipMemcpyDeviceToHost, stream()));
+        APS_HIP(hipStreamSynchronize(stream()));
+    }
     T* get() const { return d; }
     operator T*() const { return d; }
     bool present() const { return d != nullptr; }

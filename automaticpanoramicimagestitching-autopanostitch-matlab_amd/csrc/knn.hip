@@ -647,10 +647,14 @@ int aps_knn_global(const float* train, int64_t ft, int64_t ldt, const float* que
         }
         check_launch("knn_prep_kernel");
         if (ft == 0) {
-            std::vector<uint32_t> z(oe, 0u);
-            std::vector<float> inf(oe, INFINITY);
-            APS_HIP(hipMemcpyAsync(oi.get(), z.data(), oe * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
-            APS_HIP(hipMemcpyAsync(od.get(), inf.data(), oe * sizeof(float), hipMemcpyHostToDevice, stream()));
+            // (the logical fq x k elements only: what lies between them under a padded ldo is the caller's)
+            const size_t wd = layout == APS_ROWMAJOR ? (size_t)k : (size_t)fq, rows = layout == APS_ROWMAJOR ? (size_t)fq : (size_t)k;
+            std::vector<uint32_t> z(wd * rows, 0u);
+            std::vector<float> inf(wd * rows, INFINITY);
+            APS_HIP(hipMemcpy2DAsync(oi.get(), ldo * sizeof(uint32_t), z.data(), wd * sizeof(uint32_t), wd * sizeof(uint32_t), rows,
+                                     hipMemcpyHostToDevice, stream()));
+            APS_HIP(hipMemcpy2DAsync(od.get(), ldo * sizeof(float), inf.data(), wd * sizeof(float), wd * sizeof(float), rows,
+                                     hipMemcpyHostToDevice, stream()));
             APS_HIP(hipStreamSynchronize(stream()));
         } else if (same && k <= 4 && ft >= 8192 && !(std::getenv("APS_KNN_MODE") && !std::strcmp(std::getenv("APS_KNN_MODE"), "f32"))) {
             // Blocked, screened form (featureMatchingGlobal's call: the pool against itself, k = 4).  Inside its own block a
@@ -711,8 +715,14 @@ int aps_knn_global(const float* train, int64_t ft, int64_t ldt, const float* que
                 knn_f32_kernel<8><<<cdiv(fq, 128), 256, 0, stream()>>>(pq, sq, (int)fq, PT, sT, (int)ft, k, oi, od, ldo, layout, 0);
         }
         check_launch("knn_f32_kernel");
-        oi.commit();
-        od.commit();
+        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
+        if (layout == APS_ROWMAJOR) {
+            oi.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
+            od.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
+        } else {
+            oi.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
+            od.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
+        }
         APS_HIP(hipStreamSynchronize(stream()));
     });
 }
@@ -823,8 +833,14 @@ int aps_knn_global_screened(const float* pool, int64_t f, int64_t ld, int dim, i
                          (long long)n_surv, (long long)f, n_unc);
         g_global_rows = f;
         g_global_surv = n_surv;
-        oi.commit();
-        od.commit();
+        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
+        if (layout == APS_ROWMAJOR) {
+            oi.commit_2d((size_t)k, (size_t)f, (size_t)ldo);
+            od.commit_2d((size_t)k, (size_t)f, (size_t)ldo);
+        } else {
+            oi.commit_2d((size_t)f, (size_t)k, (size_t)ldo);
+            od.commit_2d((size_t)f, (size_t)k, (size_t)ldo);
+        }
         APS_HIP(hipStreamSynchronize(stream()));
     });
 }
@@ -990,8 +1006,14 @@ int aps_knn_hamming(const uint8_t* train, int64_t ft, int64_t ldt, const uint8_t
 #undef APS_HK
         }
         check_launch("hamming_knn_kernel");
-        oi.commit();
-        od.commit();
+        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
+        if (layout == APS_ROWMAJOR) {
+            oi.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
+            od.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
+        } else {
+            oi.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
+            od.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
+        }
         APS_HIP(hipStreamSynchronize(stream()));
     });
 }

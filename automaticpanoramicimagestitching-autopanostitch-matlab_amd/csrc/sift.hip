@@ -1721,8 +1721,12 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
             }
         }
 #endif
-        odesc.commit();
-        oloc.commit();
+        // strided copy-back: the elements between the logical rows / columns (ldd, ldl beyond the count) stay the caller's
+        if (desc_layout == APS_ROWMAJOR)
+            odesc.commit_2d(128, n_out, (size_t)ldd);
+        else
+            odesc.commit_2d(n_out, 128, (size_t)ldd);
+        oloc.commit_2d(n_out, 2, (size_t)ldl);
         oaux.commit();
         APS_HIP(hipStreamSynchronize(stream()));
     });

@@ -20,7 +20,9 @@
  *     is too small the call fails with APS_E_CAP and *count holds the needed size.
  *   - Matrices carry an explicit layout + leading dimension.  APS_COLMAJOR is MATLAB's layout
  *     (element (i,k) at p[i + k*ld], flann_knn.cpp:111-112); APS_ROWMAJOR is C/numpy/torch
- *     (element (i,k) at p[i*ld + k]).
+ *     (element (i,k) at p[i*ld + k]).  Elements outside the logical result - between the rows / columns of an output whose
+ *     leading dimension exceeds its extent, and rows count..cap of a capacity buffer - are not written, for host and device
+ *     pointers alike.
  *   - Indices crossing the boundary are 1-based uint32 like the reference's mex outputs
  *     (flann_knn.cpp:214,248; nearest2HammingExhaustiveMEX.cpp:76); 0 means "none".
  *   - Thread-safe and re-entrant: per-thread HIP stream and workspace; no global mutable state

@@ -68,3 +68,43 @@ def test_shadows_cover_the_operator_table_of_survey_8b():
             "estimateTransformationMLESAC", "renderPanorama", "multiBandBlending", "linearBlending", "imageWarp",
             "featureMatchingGlobal", "imageMatching"}
     assert need <= have, need - have
+
+
+def _calls(src, name_re=r"aps_[a-z0-9_]+"):
+    """(entry point, argument text) of every call `aps_xxx( ... )` in a source text, parentheses balanced."""
+    out = []
+    for m in re.finditer(r"\b(" + name_re + r")\s*\(", src):
+        depth, i = 1, m.end()
+        while depth and i < len(src):
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        out.append((m.group(1), src[m.end():i - 1]))
+    return out
+
+
+LAYOUT_CONSTANTS = ("APS_IMG_U8_MATLAB", "APS_COLMAJOR")
+
+
+def test_every_matlab_layout_call_of_the_gateway_has_a_layout_test():
+    """The gateway is the only caller of the MATLAB-side layout branches and never runs here.  Every entry point it calls with
+    APS_IMG_U8_MATLAB or APS_COLMAJOR must be called with that constant in tests/test_abi_layouts_gpu.py (a plain text check:
+    the entry point's name and the constant inside one test function), so a new gateway command with a MATLAB layout fails
+    the CPU suite until it has a layout test."""
+    gateway = open(os.path.join(MATLAB, "aps_mex.cpp")).read()
+    need = {(name, c) for name, args in _calls(gateway) for c in LAYOUT_CONSTANTS if re.search(r"\b" + c + r"\b", args)}
+    assert {("aps_sift_extract", "APS_IMG_U8_MATLAB"), ("aps_sift_extract", "APS_COLMAJOR"), ("aps_render", "APS_IMG_U8_MATLAB"),
+            ("aps_knn_global", "APS_COLMAJOR"), ("aps_crop_nonzero_bbox", "APS_IMG_U8_MATLAB")} <= need
+    tests = open(os.path.join(ROOT, "tests", "test_abi_layouts_gpu.py")).read()
+    functions = re.split(r"^(?=def |@pytest)", tests, flags=re.M)  # one chunk per top-level function (helpers included)
+    # a test reaches an entry point either directly (`lib.aps_x`) or through a helper of this module that it names
+    helpers = {m.group(1): chunk for chunk in functions for m in [re.match(r"def (_[a-z0-9_]+)\(", chunk)] if m}
+    have = set()
+    for chunk in functions:
+        if not re.search(r"^def test_", chunk, re.M):
+            continue
+        text = chunk + "".join(body for name, body in helpers.items() if re.search(r"\b" + name + r"\(", chunk))
+        for name in set(re.findall(r"lib\.(aps_[a-z0-9_]+)", text)) | set(re.findall(r'"(aps_[a-z0-9_]+)"', text)):
+            for c in LAYOUT_CONSTANTS:
+                if re.search(r"\b" + c + r"\b", text):
+                    have.add((name, c))
+    assert need <= have, sorted(need - have)
