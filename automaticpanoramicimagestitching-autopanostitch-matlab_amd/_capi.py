@@ -74,6 +74,11 @@ class aps_sift_params(C.Structure):
                 ("edge_threshold", C.c_double), ("max_features", C.c_int)]
 
 
+class aps_surf_params(C.Structure):
+    _fields_ = [("metric_threshold", C.c_double), ("n_octaves", C.c_int), ("n_scale_levels", C.c_int),
+                ("upright", C.c_int), ("max_features", C.c_int)]
+
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/aps.h one to one
@@ -157,6 +162,8 @@ _SIGNATURES = {
     "aps_planar_tent": [_i, _vp],
     "aps_synth_view": [_vp, _vp, _i, _i, C.c_uint, _f, _f, _vp],
     "aps_sift_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_sift_params), _vp, _i, _i64, _vp, _i64,
+                         _vp, _i64, C.POINTER(_i64)],
+    "aps_surf_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,

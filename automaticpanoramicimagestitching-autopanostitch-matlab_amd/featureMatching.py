@@ -92,6 +92,25 @@ def _pad_dim(X):
     return out
 
 
+def _pad_rows(X):
+    """A descriptor set as the 128-wide matchers take it: narrower rows (SURF: 64) are zero-padded, on the host or on the
+    device as the set lives; distances, and with them every match list, are those of the padded rows.  128-wide sets pass
+    through untouched."""
+    if not hasattr(X, "ndim"):
+        X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] >= DIM or X.shape[0] == 0:
+        return X
+    if _capi.is_torch(X):
+        import torch
+
+        out = torch.zeros((X.shape[0], DIM), dtype=torch.float32, device=X.device)
+        out[:, : X.shape[1]] = X
+        if X.is_cuda:
+            torch.cuda.current_stream().synchronize()  # torch made the copy; the library reads it on its own stream
+        return out
+    return _pad_dim(X)
+
+
 def nearest2KDTree(A, B, bucketSize=40):
     """[idx1, idx2, d1, d2] = nearest2KDTree(A, B, bucketSize) (matchFeaturesScratch.m:411-440).  knnsearch on a
     kd-tree is EXACT, so this is the exhaustive device search; d are Euclidean distances (the caller squares
@@ -176,7 +195,7 @@ def filter_matches(idx2, dBest, dSecond, n2, MaxRatio, MatchThreshold, Unique):
 
 
 def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRatio=0.6, Unique=True,
-                         ApproxFloatNNMethod="pca2nn", ApproxKDBucketSize=40, candB=None, seed=0,
+                         ApproxFloatNNMethod="pca2nn", ApproxKDBucketSize=40, candB=None, seed=0, ZeroPad=False,
                          **_ignored_approx_args):
     """[matches, matchMetric] = matchFeaturesScratch(F1, F2, 'Method', ..., 'MatchThreshold', ...,
     'MaxRatio', ..., 'Unique', ...) for float descriptors (matchFeaturesScratch.m:1-215).
@@ -185,6 +204,8 @@ def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRat
     'Approximate' float back ends (:142-160), selected by ApproxFloatNNMethod: 'pca2nn' (PCA-48 + cosine),
     'kdtree' (exact), 'subsetpdist2' (random 12000-row subset of F2; pass candB or seed): their 2-NN search is
     the same device kernel on the transformed data, the filter runs on the host.
+    ZeroPad=True ('Exhaustive'): rows shorter than the 128 the kernels are built for (SURF's 64) are zero-padded, which
+    leaves every distance and so the match list unchanged; by default such sets are refused, as they always were.
     Returns (matches K x 2 uint32 1-based, matchMetric K float32)."""
     method = str(Method).lower()
     if method not in ("exhaustive", "approximate"):
@@ -213,6 +234,9 @@ def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRat
         raise ValueError("Expected input to be nonempty.")  # validateattributes(... 'nonempty') :279-280
     if A.shape[1] != B.shape[1]:
         raise ValueError("Descriptor dimensions must match for non-binary.")
+    if ZeroPad and A.shape[1] < DIM:  # SURF's 64-wide rows
+        A, n1, ld1, la = _as_desc(_pad_rows(A))
+        B, n2, ld2, lb = _as_desc(_pad_rows(B))
     if la != lb:
         B = np.ascontiguousarray(B) if la == _capi.APS_ROWMAJOR else np.asfortranarray(B)
         B, n2, ld2, lb = _as_desc(B)
@@ -233,7 +257,7 @@ def match_pairwise_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True, no
     """Batched all-pairs matcher: the CSR form of featureMatchingPairwise used by the resident pipeline.
     Returns (pair_ptr int64[P+1], idx_i, idx_j, metric) with pairs in the reference's triu order."""
     n = len(allDescriptors)
-    prepared = [_as_desc(d) for d in allDescriptors]
+    prepared = [_as_desc(_pad_rows(d)) for d in allDescriptors]
     layouts = {p[3] for p in prepared if p[1] > 0}
     if len(layouts) > 1:
         raise ValueError("all descriptor matrices must share a storage order")
@@ -277,7 +301,7 @@ def match_pairs_csr(allDescriptors, pairs, MaxRatio, MatchThreshold, Unique=True
     sharded across GPUs.  Returns (pair_ptr int64[P+1], idx_a, idx_b, metric) as numpy arrays, or with
     device_out=True the three match arrays as resident torch tensors (int32, int32, float32)."""
     n = len(allDescriptors)
-    prepared = [_as_desc(d) for d in allDescriptors]
+    prepared = [_as_desc(_pad_rows(d)) for d in allDescriptors]
     layouts = {p[3] for p in prepared if p[1] > 0}
     if len(layouts) > 1:
         raise ValueError("all descriptor matrices must share a storage order")
@@ -470,14 +494,101 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
     return d, pts
 
 
+SURF_DIM = 64
+
+
+def _surf_params(input):
+    p = _capi.aps_surf_params()
+    p.metric_threshold = float(input.get("MetricThreshold", 1000.0))
+    p.n_octaves = int(input.get("NumOctaves", 8))  # getFeaturePoints.m:55
+    p.n_scale_levels = int(input.get("NumScaleLevels", 4))
+    p.upright = 0
+    p.max_features = int(input.get("maxFeatures", 0))
+    return p
+
+
+def surf_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False, padded=False):
+    """aps_surf_extract with automatic capacity: returns (features, validPts[, aux]); the arguments are sift_extract's.
+
+    Host results are n x 64.  Resident results (device_out=True) are the [:, :64] view of an n x 128 buffer whose columns
+    64..127 the library zeroed: the 128-wide matchers take the padded rows behind the view without a copy (_as_desc).
+    padded=True (with device_out) returns that n x 128 buffer itself: the form the resident pipeline hands to the matchers and
+    the all-gather.  aux: n x 4 [scale, angle_deg, metric, sign_of_laplacian]."""
+    if _capi.is_torch(image):
+        img = image.contiguous()
+        h, w = int(img.shape[0]), int(img.shape[1])
+        c = 1 if img.dim() == 2 else int(img.shape[2])
+    else:
+        img = np.ascontiguousarray(image, np.uint8)
+        h, w = img.shape[:2]
+        c = 1 if img.ndim == 2 else img.shape[2]
+    if c not in (1, 3):
+        raise ValueError("image must be gray or RGB")
+    prm = _surf_params(input)
+    cap = max(4096, (h * w) // 64)
+    cnt = C.c_int64(0)
+    ld = DIM if device_out else SURF_DIM
+    while True:
+        if device_out:
+            import torch
+
+            desc = torch.empty((cap, DIM), dtype=torch.float32, device="cuda")
+            _fence_fresh_blocks()
+        else:
+            desc = np.zeros((cap, SURF_DIM), np.float32)
+        if device_out and points_device:
+            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda")
+            _fence_fresh_blocks()
+        else:
+            loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
+        aux = np.zeros((cap, 4), np.float32) if want_aux else None
+        rc = lib.aps_surf_extract(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
+                                  _capi.APS_ROWMAJOR, ld, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
+        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < prm.max_features < cnt.value):
+            cap = int(cnt.value)
+            continue
+        check(rc)
+        break
+    n = cnt.value
+    if device_out and points_device:
+        pts = loc[:, :n].t().contiguous()
+        torch.cuda.current_stream().synchronize()  # the (small) transpose ran on torch's stream; consumers run on the library's
+    else:
+        pts = np.ascontiguousarray(loc[:, :n].T)
+    if device_out and compact:
+        d = desc[:n].clone()                        # (the call returned after its last kernel: it reads the count back)
+        torch.cuda.current_stream().synchronize()
+        d = d if padded else d[:, :SURF_DIM]
+    elif device_out:
+        d = desc[:n] if padded else desc[:n, :SURF_DIM]
+    else:
+        d = np.ascontiguousarray(desc[:n])
+    if want_aux:
+        return d, pts, aux[:n].copy()
+    return d, pts
+
+
+def extract_features(input, image, **kw):
+    """sift_extract or surf_extract, as input.detector says (the dispatch of the pipeline's extraction stages)."""
+    det = input.get("detector", "SIFT")
+    if det == "SURF":
+        return surf_extract(input, image, padded=bool(kw.get("device_out")), **kw)
+    if det == "SIFT":
+        return sift_extract(input, image, **kw)
+    return getFeaturePoints(input, image)  # raises for the rest of the switch
+
+
 def getFeaturePoints(input, ImageOriginal):
     """[features, validPts] = getFeaturePoints(input, ImageOriginal) (getFeaturePoints.m:1-76) for
-    input.detector == 'SIFT': features Kf x 128 single (unit norm), validPts Kf x 2 double [x y] 1-based.
+    input.detector == 'SIFT' (features Kf x 128 single, unit norm) and 'SURF' (Kf x 64 single, unit norm; :54-55);
+    validPts Kf x 2 double [x y] 1-based.
     The other detectors of the switch (:33-68) are toolbox calls with no device counterpart here."""
     det = input.get("detector", "SIFT")
+    if det == "SURF":
+        return surf_extract(input, ImageOriginal)
     if det != "SIFT":
-        if det in ("vl_SIFT", "HARRIS", "FAST", "SURF", "BRISK", "ORB", "KAZE"):
-            raise NotImplementedError(f"detector '{det}' is a MATLAB toolbox/VLFeat call; only 'SIFT' runs on the device")
+        if det in ("vl_SIFT", "HARRIS", "FAST", "BRISK", "ORB", "KAZE"):
+            raise NotImplementedError(f"detector '{det}' is a MATLAB toolbox/VLFeat call; only 'SIFT' and 'SURF' run on the device")
         raise ValueError("Need a valid input!")  # getFeaturePoints.m:67
     return sift_extract(input, ImageOriginal)
 
@@ -548,6 +659,7 @@ def match_global_csr(allDescriptors, ratio=0.6, k=4, device_out=False):
     Returns (pair_ptr int64[P+1] in featureMatchingPairwise's pair order, idx_i, idx_j): 1-based local indices in the
     lower- / higher-numbered image of each pair, query order; device_out=True keeps idx_i/idx_j as int32 CUDA tensors."""
     numImg = len(allDescriptors)
+    allDescriptors = [_pad_rows(d) for d in allDescriptors]
     counts = [int(d.shape[0]) for d in allDescriptors]
     F = sum(counts)
     npairs = numImg * (numImg - 1) // 2

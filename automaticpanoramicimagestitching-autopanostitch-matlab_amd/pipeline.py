@@ -66,6 +66,7 @@ SIFT_WORKERS_DEFAULT = 10
 
 def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
     """getFeaturePoints for many images — the reference runs this loop as a parfor (loadImages.m:82-99).
+    input.detector selects SIFT or SURF (fm.extract_features); the name is kept, it is public.
     Here a few host threads each drive their own HIP stream (the C ABI is thread-safe with per-thread streams
     and workspaces), so the small-octave launches and the count read-backs of one image overlap with the
     large-octave kernels of another.  Results are returned in input order and are independent of the
@@ -87,7 +88,7 @@ def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
                 ev.synchronize()
         elif dev:
             torch.cuda.synchronize()
-        out = [fm.sift_extract(input, img, device_out=dev) for img in images]
+        out = [fm.extract_features(input, img, device_out=dev) for img in images]
         _sync()
         return out
     return [f.result() for f in sift_submit(input, images, workers, ready)]
@@ -165,7 +166,7 @@ def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_
         _capi.check(_capi.lib.aps_set_thread_device(images[k].device.index if dev else here))
         if ready is not None:
             ready[k].synchronize()
-        r = fm.sift_extract(input, images[k], device_out=dev, points_device=bool(dev and points_device), compact=len(images) > 96)
+        r = fm.extract_features(input, images[k], device_out=dev, points_device=bool(dev and points_device), compact=len(images) > 96)
         _sync()  # this thread's stream
         return r
 

@@ -680,6 +680,34 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
 /* ============================================================================================
+ * (4b) SURF — PP/featureMatching/getFeaturePoints.m:54-55,71-74
+ * ============================================================================================ */
+
+typedef struct aps_surf_params {
+    double metric_threshold;   /* detectSURFFeatures MetricThreshold (1000) */
+    int n_octaves;             /* getFeaturePoints.m:55: 8 */
+    int n_scale_levels;        /* 4 (>= 3) */
+    int upright;               /* 0 */
+    int max_features;          /* capacity guard; 0 = library default (none beyond cap) */
+} aps_surf_params;
+
+/* [features, validPts] = getFeaturePoints(input, img) for detector 'SURF' (getFeaturePoints.m:54-55,71-74): rgb2gray,
+ * detectSURFFeatures(gray, 'NumOctaves', 8), extractFeatures.  Both toolbox calls are closed code; the algorithm restated is
+ * SURF of Bay et al. (2008) with the parameters that call implies — see DESIGN.md "SURF contract", which fixes every
+ * operation and its order (parity with MATLAB is unpinned).
+ *   desc : f32 count x 64, `desc_layout` with leading dimension ldd >= 64 (row-major) / >= cap (column-major), unit L2 norm;
+ *          row-major with ldd >= 128: columns 64..127 are zeroed as well, so resident rows feed the 128-wide matchers
+ *   loc  : f64 count x 2 [x y], 1-based sub-pixel, column-major with leading dimension ldl >= cap
+ *   aux  : f32 count x 4 row-major [scale, angle_deg, metric, sign_of_laplacian] or NULL
+ * cap = rows available in desc/loc/aux; *count = features found (APS_E_CAP if cap is too small; desc = NULL or cap = 0 counts).
+ * Images with height * width * 255 >= 2^32 are refused with APS_E_ARG (the integral image holds exact 32-bit sums).
+ * Host and device pointers are accepted; the call runs on the calling thread's library stream.
+ * Feature order is canonical: ascending (octave, level, row, col). */
+int aps_surf_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                     const aps_surf_params* params, float* desc, int desc_layout, int64_t ldd,
+                     double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* ============================================================================================
  * Bench / test support — NOT part of the reference boundary
  * ============================================================================================ */
 /* One uint8 H x W x 3 (row-major interleaved) view of the seeded procedural world used by bench.py and the
