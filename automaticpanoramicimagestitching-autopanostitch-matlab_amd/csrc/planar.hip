@@ -14,6 +14,15 @@
 // The arithmetic per pixel is the one of image_warp_h_kernel<float, APS_WARP_BILINEAR> (render.hip) applied to
 // (float)u8 / 255.0f and to the tent map, so the composite equals the host-orchestrated chain of
 // renderPanorama.pureNonRotationalPanoramas bit for bit.
+//
+// Two compositors, one arithmetic.  The dense one (aps_planar_composite) keeps canvas-sized layers and walks images
+// 0..K-1 at every pixel; the compact one (aps_planar_composite_compact) keeps footprint-sized layers and walks the
+// contributor list of the pixel's 64 x 64 block.  They return the same bytes because every per-pixel computation has ONE
+// source: the warp (planar_layer_pixel), normalisation, fusion and gain statistics (kernel templates over a layer set:
+// DenseSet / CompactSet say who contributes to a pixel and where its value lives), and the pyramid (resize_with, blur_tile,
+// lap_accumulate, multiband_collapse, pyramid_levels, pyramid_footprints in render_dev.h / render.hip).  The compositors
+// differ in storage and contributor walk only; so do the two halves of the host side (DenseCompositor / CompactCompositor
+// under planar_composite_impl and planar_gain_stats_impl).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -24,7 +33,9 @@
 
 namespace aps {
 
-constexpr int kPlanarMaxImages = 64;  // the inside-mask of the weight normalisation is one 64-bit word
+// The dense compositor's documented limit (include/aps.h; refusing the 65th image is tested behaviour): every pixel walks all
+// K layers and memory is K canvases, so beyond it the compact compositor is the one to call.  No kernel depends on the number.
+constexpr int kPlanarMaxImages = 64;
 
 struct PlanarJob {
     const uint8_t* src;  // h x w x c, row-major interleaved
@@ -39,6 +50,15 @@ struct PlanarJob {
     int pad[2];
 };
 static_assert(sizeof(PlanarJob) == 160, "aps_planar_composite_bytes counts 160 bytes per image for this table");
+
+struct PlanarArgs {  // the leading arguments of the entry points (the byte formulas know no images, the dense one no H and no view)
+    const uint8_t* const* images;
+    const int *ih, *iw, *ic;
+    int n;
+    const double* H;
+    int out_h, out_w;
+    double x0, y0, sx, sy;
+};
 
 // renderPanorama.warpWeights' 1-D factor: t(1:ceil(n/2)) = linspace(0,1,.), t(floor(n/2)+1:n) = linspace(1,0,.), the
 // second assignment winning where they overlap; linspace in f64 as start + i * (delta / div) with the last element
@@ -107,27 +127,35 @@ static Rect planar_footprint(const double* H, int h, int w, int out_h, int out_w
     return r;
 }
 
-// The device memory one composite requests (the formula of aps_planar_composite_bytes, include/aps.h).
-static int64_t planar_bytes(int n, const int* ih, const int* iw, const int* ic, int out_h, int out_w, int blending, int levels) {
-    const int64_t P = (int64_t)out_h * out_w;
+// Every image's footprint; APS_PLANAR_NO_CULL (a test switch) makes each one the whole canvas.
+static std::vector<Rect> planar_footprints(const PlanarArgs& a) {
+    const bool no_cull = std::getenv("APS_PLANAR_NO_CULL") != nullptr;
+    std::vector<Rect> r(a.n);
+    for (int k = 0; k < a.n; ++k)
+        r[k] = no_cull ? Rect{0, 0, a.out_w, a.out_h}
+                       : planar_footprint(a.H + 9 * k, a.ih[k], a.iw[k], a.out_h, a.out_w, a.x0, a.y0, a.sx, a.sy, nullptr);
+    return r;
+}
+
+// What both byte formulas charge before the layers: sources, tents, the job table, coverage and the uint8 panorama.
+static int64_t planar_io_bytes(const PlanarArgs& a) {
+    const int64_t P = (int64_t)a.out_h * a.out_w;
     int64_t b = 0;
-    for (int k = 0; k < n; ++k) b += (int64_t)ih[k] * iw[k] * ic[k] + 4 * ((int64_t)ih[k] + iw[k]);
-    b += (int64_t)n * (int64_t)sizeof(PlanarJob) + 16 * (int64_t)n * P + P + 3 * P;
+    for (int k = 0; k < a.n; ++k) b += (int64_t)a.ih[k] * a.iw[k] * a.ic[k] + 4 * ((int64_t)a.ih[k] + a.iw[k]);
+    return b + (int64_t)a.n * (int64_t)sizeof(PlanarJob) + P + 3 * P;
+}
+
+// The device memory one composite requests (the formula of aps_planar_composite_bytes, include/aps.h).
+static int64_t planar_bytes(const PlanarArgs& a, int blending, int levels) {
+    const int64_t P = (int64_t)a.out_h * a.out_w, n = a.n;
+    int64_t b = planar_io_bytes(a) + 16 * n * P;
     if (blending == APS_BLEND_MULTIBAND) {
-        const int maxl = (int)std::floor(std::log2((double)std::min(out_h, out_w)));
-        const int L = std::max(1, std::min(levels, maxl));
-        int64_t down = 0, inner = 0;  // pixels of levels 1..L-1, of levels 1..L-2
-        int hl = out_h, wl = out_w;
-        for (int l = 1; l < L; ++l) {
-            hl = std::max(1, hl / 2);
-            wl = std::max(1, wl / 2);
-            down += (int64_t)hl * wl;
-            if (l < L - 1) inner += (int64_t)hl * wl;
-        }
-        b += 16 * P;                                           // F
-        b += 16 * (int64_t)n * down;                           // the layers' Gaussian levels 1..L-1
-        if (L > 1) b += 16 * (int64_t)std::min(n, kMaxK) * P;  // blurred level of one batch of layers
-        b += 16 * (P + down) + 16 * inner;                     // numerator pyramid, collapse buffers
+        std::vector<int> lh, lw;
+        pyramid_levels(a.out_h, a.out_w, levels, lh, lw);
+        const int L = (int)lh.size();
+        b += 16 * n * pyramid_px(lh, lw, 1, L);              // the layers' Gaussian levels 1..L-1
+        if (L > 1) b += 16 * std::min<int64_t>(n, kMaxK) * P;  // blurred level of one batch of layers
+        b += pyramid_result_bytes(lh, lw);
     }
     return b;
 }
@@ -135,7 +163,7 @@ static int64_t planar_bytes(int n, const int* ih, const int* iw, const int* ic, 
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
-// planar_layer_pixel: one canvas pixel of one image, shared by the dense and the compact layer kernel (one image per
+// planar_layer_pixel: one canvas pixel of one image (planar_layer_kernel: one image per
 // blockIdx.z (jobs[k0 + z]), 64 x 4 canvas pixels of its footprint per workgroup).  Inverse map, validity
 // and the four-tap sums as image_warp_h_kernel<float, APS_WARP_BILINEAR>: f64, ((w11*p11 + w12*p12) + w21*p21) + w22*p22
 // (no contraction: this library is compiled with -ffp-contract=off), rounded to f32; the map is evaluated once for
@@ -178,47 +206,110 @@ __device__ __forceinline__ float4 planar_layer_pixel(const PlanarJob& j, int x, 
     return o;
 }
 
+// where a pixel lives in a layer stored inside its footprint r only: row-major, pitch = the footprint's width
+__device__ __forceinline__ size_t c_index(const Rect& r, int x, int y) {
+    return (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
+}
+
+// COMPACT: the layer is stored inside its footprint only (row pitch = the footprint's width; W is not used); else at canvas pitch W.
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void planar_layer_kernel(const PlanarJob* __restrict__ jobs, int k0, int W, double x0, double y0,
                                                            double sx, double sy) {
     const PlanarJob& j = jobs[k0 + blockIdx.z];
     const int x = j.r.x0 + blockIdx.x * 64 + (threadIdx.x & 63), y = j.r.y0 + blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= j.r.x1 || y >= j.r.y1) return;
-    j.layer[(size_t)y * W + x] = planar_layer_pixel(j, x, y, x0, y0, sx, sy);
+    j.layer[COMPACT ? c_index(j.r, x, y) : (size_t)y * W + x] = planar_layer_pixel(j, x, y, x0, y0, sx, sy);
 }
 
-// The same layer stored inside its footprint only: row pitch = the footprint's width (the footprint-compact compositor below).
-__global__ __launch_bounds__(256) void planar_layer_compact_kernel(const PlanarJob* __restrict__ jobs, int k0, double x0, double y0,
-                                                                   double sx, double sy) {
-    const PlanarJob& j = jobs[k0 + blockIdx.z];
-    const int x = j.r.x0 + blockIdx.x * 64 + (threadIdx.x & 63), y = j.r.y0 + blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= j.r.x1 || y >= j.r.y1) return;
-    j.layer[(size_t)(y - j.r.y0) * (j.r.x1 - j.r.x0) + (x - j.r.x0)] = planar_layer_pixel(j, x, y, x0, y0, sx, sy);
+// ---- layer sets: who contributes to a canvas pixel, and where its value lives ----------------------------------------------------
+// A set maps the launch's threads to pixels (thread_pixel) and offers, at a pixel, n candidates in ascending image order:
+// image(i), its footprint rect(i) (a candidate counts only where in_rect holds) and the address pixel(i) of its value.
+constexpr int kListBlock = 64, kListShift = 6;
+
+struct CLayer {
+    float4* p;  // the footprint's pixels, row-major, pitch r.x1 - r.x0
+    Rect r;     // footprint at this level, clipped to the level
+    int pad[2];
+};
+static_assert(sizeof(CLayer) == 32, "aps_planar_composite_compact_bytes counts 32 bytes per image and level table entry");
+
+__device__ __forceinline__ float4 ld_compact(const CLayer& c, int x, int y) {
+    return in_rect(c.r, x, y) ? c.p[c_index(c.r, x, y)] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
+
+// Canvas-sized layers, all K images at every pixel; a 1-D grid over the npix = H * W pixels.
+struct DenseSet {
+    const PlanarJob* __restrict__ jobs;
+    int K, W;
+    size_t npix;
+    struct At {
+        const PlanarJob* __restrict__ jobs;
+        size_t p;
+        int n;
+        __device__ __forceinline__ int image(int i) const { return i; }
+        __device__ __forceinline__ const Rect& rect(int i) const { return jobs[i].r; }
+        __device__ __forceinline__ float4* pixel(int i) const { return jobs[i].layer + p; }
+    };
+    __device__ __forceinline__ bool thread_pixel(int& x, int& y) const {
+        const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+        y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+        return p < npix;
+    }
+    __device__ __forceinline__ At at(int x, int y) const { return At{jobs, (size_t)y * W + x, K}; }
+};
+
+// Footprint-sized layers (one level's table G) and the ascending contributor list of the pixel's 64 x 64 block; 64 x 4 pixels
+// per workgroup, which therefore lies inside one block (blockIdx.x * 64 and blockIdx.y * 4 never straddle a multiple of 64):
+// list bounds and entries are wave-uniform loads.  lists = start[nblocks + 1], then the entries.
+struct CompactSet {
+    const CLayer* __restrict__ G;
+    const int* __restrict__ lists;
+    int bw, nblocks, W, H;
+    struct At {
+        const CLayer* __restrict__ G;
+        const int* __restrict__ idx;
+        int n, x, y;
+        __device__ __forceinline__ int image(int i) const { return idx[i]; }
+        __device__ __forceinline__ const Rect& rect(int i) const { return G[idx[i]].r; }
+        __device__ __forceinline__ float4* pixel(int i) const {
+            const CLayer& c = G[idx[i]];
+            return c.p + c_index(c.r, x, y);
+        }
+    };
+    __device__ __forceinline__ bool thread_pixel(int& x, int& y) const {
+        x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+        return x < W && y < H;
+    }
+    __device__ __forceinline__ At at(int x, int y) const {
+        const int b = (y >> kListShift) * bw + (x >> kListShift);
+        const int s = lists[b];
+        return At{G, lists + nblocks + 1 + s, lists[b + 1] - s, x, y};
+    }
+};
 
 // multiBandBlending.m:72-85 over the footprints (w = max(0,w) / sum where sum > 1e-8: the arithmetic of
 // norm_weights_kernel, mbb_norm); coverage = any raw weight > 0, taken before the division can flush one to zero.
-__global__ __launch_bounds__(256) void planar_norm_kernel(const PlanarJob* __restrict__ jobs, int K, int W, size_t n,
-                                                          uint8_t* __restrict__ cov) {
-    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
-    unsigned long long inside = 0ull;
+template <class Set>
+__global__ __launch_bounds__(256) void planar_norm_kernel(Set set, uint8_t* __restrict__ cov) {
+    int x, y;
+    if (!set.thread_pixel(x, y)) return;
+    const auto at = set.at(x, y);
     float s = 0.f;
     bool any = false;
-    for (int k = 0; k < K; ++k) {
-        if (!in_rect(jobs[k].r, x, y)) continue;
-        inside |= 1ull << k;
-        const float wv = jobs[k].layer[p].w;
+    for (int i = 0; i < at.n; ++i) {
+        if (!in_rect(at.rect(i), x, y)) continue;
+        const float wv = at.pixel(i)->w;
         s = s + (wv > 0.f ? wv : 0.f);
         any |= wv > 0.f;
     }
-    for (int k = 0; k < K; ++k) {
-        if (!((inside >> k) & 1)) continue;
-        const float w0 = jobs[k].layer[p].w;
+    for (int i = 0; i < at.n; ++i) {
+        if (!in_rect(at.rect(i), x, y)) continue;
+        float4* q = at.pixel(i);
+        const float w0 = q->w;
         const float wv = w0 > 0.f ? w0 : 0.f;
-        jobs[k].layer[p].w = s > 1e-8f ? wv / s : 0.f;
+        q->w = s > 1e-8f ? wv / s : 0.f;
     }
-    cov[p] = any ? 1 : 0;
+    cov[(size_t)y * set.W + x] = any ? 1 : 0;
 }
 
 // uint8(round(255 * f)) as the host tail forms it: the product in f64, MATLAB round (half away from zero), clamp.
@@ -244,17 +335,16 @@ __device__ __forceinline__ void planar_store(uint8_t* __restrict__ pano, uint8_t
 // MODE APS_BLEND_LINEAR: linear_blend_kernel's sums in image order (a layer outside its footprint adds exact zeros) and its
 // division.  MODE APS_BLEND_NONE: the colour of the FIRST layer of maximal weight (numpy argmax / MATLAB max).  Void
 // pixels (no weight > 0) take the canvas colour; then uint8.
-template <int MODE>
-__global__ __launch_bounds__(256) void planar_fuse_kernel(const PlanarJob* __restrict__ jobs, int K, int W, size_t n, int white,
-                                                          uint8_t* __restrict__ pano, uint8_t* __restrict__ covered) {
-    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+template <int MODE, class Set>
+__global__ __launch_bounds__(256) void planar_fuse_kernel(Set set, int white, uint8_t* __restrict__ pano, uint8_t* __restrict__ covered) {
+    int x, y;
+    if (!set.thread_pixel(x, y)) return;
+    const auto at = set.at(x, y);
     float acc[3] = {0.f, 0.f, 0.f}, den = 0.f, best = 0.f;
     bool any = false;
-    for (int k = 0; k < K; ++k) {
-        if (!in_rect(jobs[k].r, x, y)) continue;
-        const float4 g = jobs[k].layer[p];
+    for (int i = 0; i < at.n; ++i) {
+        if (!in_rect(at.rect(i), x, y)) continue;
+        const float4 g = *at.pixel(i);
         any |= g.w > 0.f;
         if (MODE == APS_BLEND_LINEAR) {
             acc[0] = acc[0] + g.x * g.w;
@@ -275,7 +365,7 @@ __global__ __launch_bounds__(256) void planar_fuse_kernel(const PlanarJob* __res
         acc[1] = acc[1] / d;
         acc[2] = acc[2] / d;
     }
-    planar_store(pano, covered, p, any, white, acc[0], acc[1], acc[2]);
+    planar_store(pano, covered, (size_t)y * set.W + x, any, white, acc[0], acc[1], acc[2]);
 }
 
 // the multiband result: max(0, min(1, F)) as unpack_clamp_kernel(clamp01 = 1), void painted, uint8
@@ -296,29 +386,31 @@ __global__ __launch_bounds__(256) void planar_finish_kernel(const float4* __rest
 }
 
 // gainCompensationH.m:45-52,78-149 on the resident layers: gain_stats_warped_kernel with float4 layers and footprints (a
-// pair whose footprints do not intersect is never valid together).  One thread per sampled canvas point.
-__global__ __launch_bounds__(256) void planar_gain_stats_kernel(const PlanarJob* __restrict__ jobs, int n_img, int W, int ds, int ws,
-                                                                int hs, double* __restrict__ Nij, double* __restrict__ sCi,
-                                                                double* __restrict__ sCj) {
+// pair whose footprints do not intersect is never valid together; the pairs of a point are pairs of its candidates).  One
+// thread per sampled canvas point.
+template <class Set>
+__global__ __launch_bounds__(256) void planar_gain_stats_kernel(Set set, int n_img, int ds, int ws, int hs, double* __restrict__ Nij,
+                                                                double* __restrict__ sCi, double* __restrict__ sCj) {
     __shared__ GainPairTable s_tab;
     s_tab.init();
     const int ix = blockIdx.x * 16 + (threadIdx.x & 15), iy = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (ix < ws && iy < hs) {
         const int x = ix * ds, y = iy * ds;
-        auto sample = [&](int k, float* c3) {
-            if (!in_rect(jobs[k].r, x, y)) return false;
-            const float4 g = jobs[k].layer[(size_t)y * W + x];
+        const auto at = set.at(x, y);
+        auto sample = [&](int i, float* c3) {
+            if (!in_rect(at.rect(i), x, y)) return false;
+            const float4 g = *at.pixel(i);
             c3[0] = g.x;
             c3[1] = g.y;
             c3[2] = g.z;
             return g.w > 0.f && isfinite(g.x) && isfinite(g.y) && isfinite(g.z);
         };
-        for (int i = 0; i < n_img; ++i) {
+        for (int a = 0; a < at.n; ++a) {
             float ci[3];
-            if (!sample(i, ci)) continue;
-            for (int j = i + 1; j < n_img; ++j) {
+            if (!sample(a, ci)) continue;
+            for (int b = a + 1; b < at.n; ++b) {
                 float cj[3];
-                if (sample(j, cj)) s_tab.add(n_img, i, j, ci, cj, Nij, sCi, sCj);
+                if (sample(b, cj)) s_tab.add(n_img, at.image(a), at.image(b), ci, cj, Nij, sCi, sCj);
             }
         }
     }
@@ -339,38 +431,53 @@ struct PlanarLayers {
     std::vector<PlanarJob> host_jobs;
 };
 
-static void planar_check_args(const uint8_t* const* images, const int* ih, const int* iw, const int* ic, int n, const double* H,
-                              int out_h, int out_w, double sx, double sy, int max_images = kPlanarMaxImages,
-                              bool need_images = true) {
-    APS_REQUIRE((images || !need_images) && ih && iw && ic && H, APS_E_ARG, "NULL argument");
-    APS_REQUIRE(n >= 1, APS_E_ARG, "need at least one image (%d)", n);
-    APS_REQUIRE(n <= max_images, APS_E_DIM, "more than %d images in one planar composite (%d)", max_images, n);
-    APS_REQUIRE(out_h > 0 && out_w > 0 && (int64_t)out_h * out_w < ((int64_t)1 << 31), APS_E_DIM, "bad canvas size %d x %d", out_h,
-                out_w);
-    APS_REQUIRE(sx > 0 && sy > 0 && std::isfinite(sx) && std::isfinite(sy), APS_E_ARG, "pixel extents must be positive");
-    for (int k = 0; k < n; ++k) {
-        APS_REQUIRE(!need_images || images[k], APS_E_ARG, "NULL image %d", k);
-        APS_REQUIRE(ih[k] > 0 && iw[k] > 0 && (ic[k] == 1 || ic[k] == 3), APS_E_DIM, "image %d: bad size %d x %d x %d", k, ih[k],
-                    iw[k], ic[k]);
+// Shapes, canvas and homographies.  need_view = false: the dense byte formula, which knows sizes only.
+static void planar_check_shapes(const PlanarArgs& a, int max_images, bool need_images = true, bool need_view = true) {
+    APS_REQUIRE((a.images || !need_images) && a.ih && a.iw && a.ic && (a.H || !need_view), APS_E_ARG, "NULL argument");
+    APS_REQUIRE(a.n >= 1, APS_E_ARG, "need at least one image (%d)", a.n);
+    APS_REQUIRE(a.n <= max_images, APS_E_DIM, "more than %d images in one planar composite (%d)", max_images, a.n);
+    APS_REQUIRE(a.out_h > 0 && a.out_w > 0 && (int64_t)a.out_h * a.out_w < ((int64_t)1 << 31), APS_E_DIM, "bad canvas size %d x %d",
+                a.out_h, a.out_w);
+    APS_REQUIRE(!need_view || (a.sx > 0 && a.sy > 0 && std::isfinite(a.sx) && std::isfinite(a.sy)), APS_E_ARG,
+                "pixel extents must be positive");
+    for (int k = 0; k < a.n; ++k) {
+        APS_REQUIRE(!need_images || a.images[k], APS_E_ARG, "NULL image %d", k);
+        APS_REQUIRE(a.ih[k] > 0 && a.iw[k] > 0 && (a.ic[k] == 1 || a.ic[k] == 3), APS_E_DIM, "image %d: bad size %d x %d x %d", k,
+                    a.ih[k], a.iw[k], a.ic[k]);
+        if (!need_view) continue;
         HWarp hw;
-        make_hwarp(H + 9 * k, hw);
+        make_hwarp(a.H + 9 * k, hw);
         // |det| against Hadamard's bound on it (rows and columns of H / H(3,3)): zero up to rounding = no inverse map
-        const double* h = H + 9 * k;
+        const double* h = a.H + 9 * k;
         const double s = h[8] != 0 ? h[8] : 1.0;
         double rows = 1.0, cols = 1.0;
         bool fin = true;
-        for (int a = 0; a < 3; ++a) {
+        for (int i = 0; i < 3; ++i) {
             double r2 = 0, c2 = 0;
             for (int b = 0; b < 3; ++b) {
-                fin = fin && std::isfinite(h[a + 3 * b]);
-                r2 += (h[a + 3 * b] / s) * (h[a + 3 * b] / s);
-                c2 += (h[b + 3 * a] / s) * (h[b + 3 * a] / s);
+                fin = fin && std::isfinite(h[i + 3 * b]);
+                r2 += (h[i + 3 * b] / s) * (h[i + 3 * b] / s);
+                c2 += (h[b + 3 * i] / s) * (h[b + 3 * i] / s);
             }
             rows *= std::sqrt(r2);
             cols *= std::sqrt(c2);
         }
         APS_REQUIRE(fin && std::isfinite(hw.det) && std::fabs(hw.det) > 1e-14 * std::min(rows, cols), APS_E_ARG,
                     "homography %d is singular or not finite (det %g)", k, hw.det);
+    }
+}
+
+// need_sigma = false: the byte formulas, which know no sigma
+static void planar_check_blending(int blending, int levels, float sigma, bool need_sigma) {
+    APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND, APS_E_ARG,
+                "unknown blending mode %d", blending);
+    if (blending == APS_BLEND_MULTIBAND) {
+        APS_REQUIRE(levels >= 1, APS_E_ARG, "levels must be a positive integer");
+        if (!need_sigma) return;
+        APS_REQUIRE(sigma > 0, APS_E_ARG, "sigma must be positive");
+        const Taps tp = make_taps(sigma);
+        APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built", (double)sigma,
+                    2 * tp.r + 1);
     }
 }
 
@@ -383,45 +490,34 @@ static void planar_precheck(int64_t need) {
                 "planar composite needs %lld bytes of device memory, %zu are free: this panorama cannot fit", (long long)need, have);
 }
 
-static void planar_build_layers(const uint8_t* const* images, const int* ih, const int* iw, const int* ic, int n, const double* H,
-                                int out_h, int out_w, double x0, double y0, double sx, double sy, const float* gains,
-                                PlanarLayers& L, bool compact = false) {
-    // compact: the caller has filled L.layers and L.rects (footprint-sized layers of one arena)
-    const size_t P = (size_t)out_h * out_w;
-    const bool no_cull = std::getenv("APS_PLANAR_NO_CULL") != nullptr;
+// Stages sources and tents, fills the job table and warps every image into its layer.  The caller has filled L.layers and
+// L.rects: canvas-sized layers (compact = false) or the footprint-sized ones of the arena.
+static void planar_build_layers(const PlanarArgs& a, const float* gains, bool compact, PlanarLayers& L) {
+    const int n = a.n;
     size_t nt = 0;
-    for (int k = 0; k < n; ++k) nt += (size_t)ih[k] + iw[k];
+    for (int k = 0; k < n; ++k) nt += (size_t)a.ih[k] + a.iw[k];
     std::vector<float>& tents = L.host_tents;
     tents.resize(nt);
     L.tents.alloc(nt);
-    if (!compact) {
-        L.store.resize(n);
-        L.layers.resize(n);
-        L.rects.resize(n);
-    }
     L.host_jobs.resize(n);
     size_t off = 0;
     for (int k = 0; k < n; ++k) {
         PlanarJob& j = L.host_jobs[k];
-        L.imgs.emplace_back(new In<uint8_t>(images[k], (size_t)ih[k] * iw[k] * ic[k]));
+        L.imgs.emplace_back(new In<uint8_t>(a.images[k], (size_t)a.ih[k] * a.iw[k] * a.ic[k]));
         j.src = L.imgs.back()->get();
-        planar_tent(iw[k], tents.data() + off);
+        planar_tent(a.iw[k], tents.data() + off);
         j.tx = L.tents.get() + off;
-        off += iw[k];
-        planar_tent(ih[k], tents.data() + off);
+        off += a.iw[k];
+        planar_tent(a.ih[k], tents.data() + off);
         j.ty = L.tents.get() + off;
-        off += ih[k];
-        if (!compact) {
-            L.store[k].alloc(P);
-            L.layers[k] = L.store[k];
-        }
+        off += a.ih[k];
         j.layer = L.layers[k];
         HWarp hw;
-        make_hwarp(H + 9 * k, hw);
+        make_hwarp(a.H + 9 * k, hw);
         for (int e = 0; e < 9; ++e) j.A[e] = hw.A[e];
         j.det = hw.det;
-        j.r = L.rects[k] = compact ? L.rects[k] : no_cull ? Rect{0, 0, out_w, out_h} : planar_footprint(H + 9 * k, ih[k], iw[k], out_h, out_w, x0, y0, sx, sy, nullptr);
-        j.h = ih[k], j.w = iw[k], j.c = ic[k];
+        j.r = L.rects[k];
+        j.h = a.ih[k], j.w = a.iw[k], j.c = a.ic[k];
         for (int c = 0; c < 3; ++c) j.g[c] = gains ? gains[3 * k + c] : 1.0f;
         j.pad[0] = j.pad[1] = 0;
     }
@@ -437,44 +533,54 @@ static void planar_build_layers(const uint8_t* const* images, const int* ih, con
             mh = std::max(mh, L.rects[k].y1 - L.rects[k].y0);
         }
         if (mw <= 0 || mh <= 0) continue;
+        const dim3 grid(cdiv(mw, 64), cdiv(mh, 4), kc);
         if (compact)
-            planar_layer_compact_kernel<<<dim3(cdiv(mw, 64), cdiv(mh, 4), kc), 256, 0, stream()>>>(L.jobs.get(), k0, x0, y0, sx, sy);
+            planar_layer_kernel<true><<<grid, 256, 0, stream()>>>(L.jobs.get(), k0, a.out_w, a.x0, a.y0, a.sx, a.sy);
         else
-            planar_layer_kernel<<<dim3(cdiv(mw, 64), cdiv(mh, 4), kc), 256, 0, stream()>>>(L.jobs.get(), k0, out_w, x0, y0, sx, sy);
+            planar_layer_kernel<false><<<grid, 256, 0, stream()>>>(L.jobs.get(), k0, a.out_w, a.x0, a.y0, a.sx, a.sy);
         check_launch("planar_layer_kernel");
     }
 }
 
+// The dense compositor's half of planar_composite_impl / planar_gain_stats_impl: one canvas-sized layer per image.
+struct DenseCompositor {
+    static constexpr int kMaxImages = kPlanarMaxImages, kGainMaxImages = kPlanarMaxImages;
+    static constexpr const char *kNorm = "planar_norm_kernel", *kFuse = "planar_fuse_kernel", *kGain = "planar_gain_stats_kernel",
+                                *kGainProf = "planar_gain_stats";
+    const PlanarArgs& a;
+    PlanarLayers L;
+    size_t P() const { return (size_t)a.out_h * a.out_w; }
+    // the statistics' outputs were never part of this formula
+    void plan(int blending, int levels, float, int64_t) { planar_precheck(planar_bytes(a, blending, levels)); }
+    void build(const float* gains) {
+        L.rects = planar_footprints(a);
+        L.store.resize(a.n);
+        L.layers.resize(a.n);
+        for (int k = 0; k < a.n; ++k) {
+            L.store[k].alloc(P());
+            L.layers[k] = L.store[k];
+        }
+        planar_build_layers(a, gains, false, L);
+    }
+    DenseSet set() const { return DenseSet{L.jobs.get(), a.n, a.out_w, P()}; }
+    dim3 grid() const { return dim3(cdiv(P(), 256)); }
+    void multiband(int levels, float sigma, float4* F) { multiband_device(L.layers, L.rects.data(), a.out_h, a.out_w, levels, sigma, F); }
+};
+
 // ------------------------------------------------------------------------------------------------
 // the footprint-compact compositor (aps_planar_composite_compact, aps_planar_gain_stats_compact)
 // ------------------------------------------------------------------------------------------------
-// Same pixels, same arithmetic and same order of every sum as the dense compositor above; what changes is where a layer
-// lives and who looks at it.
+// Same pixels, same arithmetic and same order of every sum as the dense compositor: the same bodies.  What changes is where a
+// layer lives and who looks at it.
 //   layers   : every image at every pyramid level is stored inside its footprint only (CLayer: base pointer, footprint,
 //              row pitch = the footprint's width), all of them carved out of one arena.  No buffer multiplies the image
 //              count by the canvas.
 //   lists    : per level, the canvas is cut into 64 x 64 blocks; the host builds, from the footprints alone, the list of
 //              images (ascending) whose footprint meets each block and uploads all lists once.  The per-pixel kernels walk the
-//              list of their block (a workgroup lies inside one block, so list bounds and entries are wave-uniform loads)
-//              instead of all n jobs, and one pass per level accumulates every contributor.
-constexpr int kListBlock = 64, kListShift = 6;
+//              list of their block (CompactSet) instead of all n jobs, and one pass per level accumulates every contributor.
 
-struct CLayer {
-    float4* p;  // the footprint's pixels, row-major, pitch r.x1 - r.x0
-    Rect r;     // footprint at this level, clipped to the level
-    int pad[2];
-};
-static_assert(sizeof(CLayer) == 32, "aps_planar_composite_compact_bytes counts 32 bytes per image and level table entry");
-
-__device__ __forceinline__ size_t c_index(const CLayer& c, int x, int y) {
-    return (size_t)(y - c.r.y0) * (size_t)(c.r.x1 - c.r.x0) + (size_t)(x - c.r.x0);
-}
-__device__ __forceinline__ float4 ld_compact(const CLayer& c, int x, int y) {
-    return in_rect(c.r, x, y) ? c.p[c_index(c, x, y)] : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// Everything the host derives from the shapes and homographies alone: level sizes, the footprints multiband_device derives
-// (G_l; blurred G_l = grown by the filter radius; G_(l+1) = map_rect through the resize), arena offsets, contributor lists.
+// Everything the host derives from the shapes and homographies alone: level sizes and footprints (pyramid_levels,
+// pyramid_footprints: the ones multiband_device derives), arena offsets, contributor lists.
 struct CompactPlan {
     int L = 1;
     std::vector<int> lh, lw;
@@ -487,45 +593,26 @@ struct CompactPlan {
     int64_t list_ints = 0;
 };
 
-static int compact_levels(int out_h, int out_w, int blending, int levels) {
-    if (blending != APS_BLEND_MULTIBAND) return 1;
-    const int maxl = (int)std::floor(std::log2((double)std::min(out_h, out_w)));
-    return std::max(1, std::min(levels, maxl));
-}
-
-// radius: the Gaussian's (make_taps(sigma).r); fill_lists = false only counts them (the byte formula needs no entries)
-static void compact_plan(int n, const int* ih, const int* iw, const double* H, int out_h, int out_w, double x0, double y0, double sx,
-                         double sy, int L, int radius, bool fill_lists, CompactPlan& pl) {
-    const bool no_cull = std::getenv("APS_PLANAR_NO_CULL") != nullptr;
-    pl.L = L;
-    pl.lh.assign(L, out_h);
-    pl.lw.assign(L, out_w);
-    for (int l = 1; l < L; ++l) {
-        pl.lh[l] = std::max(1, pl.lh[l - 1] / 2);
-        pl.lw[l] = std::max(1, pl.lw[l - 1] / 2);
-    }
-    pl.gr.assign(L, std::vector<Rect>(n));
-    pl.br.assign(L, std::vector<Rect>(n));
+// levels: as asked for (1 unless multiband); radius: the Gaussian's (make_taps(sigma).r); fill_lists = false only counts them
+// (the byte formula needs no entries)
+static void compact_plan(const PlanarArgs& a, int levels, int radius, bool fill_lists, CompactPlan& pl) {
+    const int n = a.n;
+    pyramid_levels(a.out_h, a.out_w, levels, pl.lh, pl.lw);
+    const int L = pl.L = (int)pl.lh.size();
+    pyramid_footprints(planar_footprints(a), radius, pl.lh, pl.lw, pl.gr, pl.br);
     pl.goff.assign(L, std::vector<int64_t>(n, 0));
     pl.boff.assign(L, std::vector<int64_t>(n, 0));
-    for (int k = 0; k < n; ++k)
-        pl.gr[0][k] = no_cull ? Rect{0, 0, out_w, out_h}
-                              : clip_rect(planar_footprint(H + 9 * k, ih[k], iw[k], out_h, out_w, x0, y0, sx, sy, nullptr), out_w, out_h);
     auto area = [](const Rect& r) { return (int64_t)(r.x1 - r.x0) * (int64_t)(r.y1 - r.y0); };
     pl.layer_px = pl.blur_px = 0;
     for (int l = 0; l < L; ++l) {
         int64_t blur = 0;
         for (int k = 0; k < n; ++k) {
-            const Rect g = pl.gr[l][k];
-            const bool empty = g.x1 <= g.x0;
-            pl.br[l][k] = empty ? g : clip_rect(Rect{g.x0 - radius, g.y0 - radius, g.x1 + radius, g.y1 + radius}, pl.lw[l], pl.lh[l]);
             if (l + 1 < L) {
-                pl.gr[l + 1][k] = empty ? g : map_rect(pl.br[l][k], pl.lh[l], pl.lw[l], pl.lh[l + 1], pl.lw[l + 1]);
                 pl.boff[l][k] = blur;
                 blur += area(pl.br[l][k]);
             }
             pl.goff[l][k] = pl.layer_px;
-            pl.layer_px += area(g);
+            pl.layer_px += area(pl.gr[l][k]);
         }
         pl.blur_px = std::max(pl.blur_px, blur);
     }
@@ -578,165 +665,24 @@ static void compact_plan(int n, const int* ih, const int* iw, const double* H, i
 }
 
 // The device memory one compact composite requests (the formula of aps_planar_composite_compact_bytes, include/aps.h).
-static int64_t compact_bytes(const CompactPlan& pl, int n, const int* ih, const int* iw, const int* ic, int out_h, int out_w, int blending) {
-    const int64_t P = (int64_t)out_h * out_w;
-    int64_t b = 0;
-    for (int k = 0; k < n; ++k) b += (int64_t)ih[k] * iw[k] * ic[k] + 4 * ((int64_t)ih[k] + iw[k]);
-    b += (int64_t)n * (int64_t)sizeof(PlanarJob) + (int64_t)sizeof(CLayer) * n * (2 * pl.L - 1);
-    b += 16 * pl.layer_px + 16 * pl.blur_px + 4 * pl.list_ints + P + 3 * P;
-    if (blending == APS_BLEND_MULTIBAND) {
-        int64_t down = 0, inner = 0;
-        for (int l = 1; l < pl.L; ++l) {
-            down += (int64_t)pl.lh[l] * pl.lw[l];
-            if (l < pl.L - 1) inner += (int64_t)pl.lh[l] * pl.lw[l];
-        }
-        b += 16 * P + 16 * (P + down) + 16 * inner;  // F, numerator pyramid, collapse buffers
-    }
+static int64_t compact_bytes(const CompactPlan& pl, const PlanarArgs& a, int blending) {
+    int64_t b = planar_io_bytes(a) + (int64_t)sizeof(CLayer) * a.n * (2 * pl.L - 1);
+    b += 16 * pl.layer_px + 16 * pl.blur_px + 4 * pl.list_ints;
+    if (blending == APS_BLEND_MULTIBAND) b += pyramid_result_bytes(pl.lh, pl.lw);
     return b;
 }
 
-// ---- kernels -------------------------------------------------------------------------------------
-// A workgroup of 64 x 4 (or 32 x 4) pixels lies inside one 64 x 64 block: blockIdx.x * width and blockIdx.y * 4 never
-// straddle a multiple of 64.
-struct BlockList {
-    const int* __restrict__ idx;
-    int n;
-};
-__device__ __forceinline__ BlockList block_list(const int* __restrict__ lists, int bw, int nblocks, int x, int y) {
-    const int b = (y >> kListShift) * bw + (x >> kListShift);
-    const int s = lists[b];
-    return BlockList{lists + nblocks + 1 + s, lists[b + 1] - s};
-}
-
-// planar_norm_kernel over the block's contributors
-__global__ __launch_bounds__(256) void compact_norm_kernel(const CLayer* __restrict__ G, const int* __restrict__ lists, int bw,
-                                                           int nblocks, int W, int Hh, uint8_t* __restrict__ cov) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= Hh) return;
-    const BlockList bl = block_list(lists, bw, nblocks, x, y);
-    float s = 0.f;
-    bool any = false;
-    for (int i = 0; i < bl.n; ++i) {
-        const CLayer& c = G[bl.idx[i]];
-        if (!in_rect(c.r, x, y)) continue;
-        const float wv = c.p[c_index(c, x, y)].w;
-        s = s + (wv > 0.f ? wv : 0.f);
-        any |= wv > 0.f;
-    }
-    for (int i = 0; i < bl.n; ++i) {
-        const CLayer& c = G[bl.idx[i]];
-        if (!in_rect(c.r, x, y)) continue;
-        float4* q = c.p + c_index(c, x, y);
-        const float w0 = q->w;
-        const float wv = w0 > 0.f ? w0 : 0.f;
-        q->w = s > 1e-8f ? wv / s : 0.f;
-    }
-    cov[(size_t)y * W + x] = any ? 1 : 0;
-}
-
-// planar_fuse_kernel over the block's contributors
-template <int MODE>
-__global__ __launch_bounds__(256) void compact_fuse_kernel(const CLayer* __restrict__ G, const int* __restrict__ lists, int bw,
-                                                           int nblocks, int W, int Hh, int white, uint8_t* __restrict__ pano,
-                                                           uint8_t* __restrict__ covered) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= Hh) return;
-    const BlockList bl = block_list(lists, bw, nblocks, x, y);
-    float acc[3] = {0.f, 0.f, 0.f}, den = 0.f, best = 0.f;
-    bool any = false;
-    for (int i = 0; i < bl.n; ++i) {
-        const CLayer& c = G[bl.idx[i]];
-        if (!in_rect(c.r, x, y)) continue;
-        const float4 g = c.p[c_index(c, x, y)];
-        any |= g.w > 0.f;
-        if (MODE == APS_BLEND_LINEAR) {
-            acc[0] = acc[0] + g.x * g.w;
-            acc[1] = acc[1] + g.y * g.w;
-            acc[2] = acc[2] + g.z * g.w;
-            den = den + g.w;
-        } else if (g.w > best) {
-            best = g.w;
-            acc[0] = g.x;
-            acc[1] = g.y;
-            acc[2] = g.z;
-        }
-    }
-    if (MODE == APS_BLEND_LINEAR) {
-        const float tiny = 1.1920928955078125e-07f;
-        const float d = den > tiny ? den : tiny;
-        acc[0] = acc[0] / d;
-        acc[1] = acc[1] / d;
-        acc[2] = acc[2] / d;
-    }
-    planar_store(pano, covered, (size_t)y * W + x, any, white, acc[0], acc[1], acc[2]);
-}
-
-// mb_blur_kernel (render.hip) on compact layers: column pass then row pass through one LDS tile, replicate padding at the
-// level's border, the same fmaf chains; one image per blockIdx.z, input inside G's footprint, output inside B's.
-constexpr int kCBW = 32, kCBH = 16;
+// ---- pyramid kernels on compact layers: the bodies of render_dev.h with footprint-pitch loads and stores ---------------------------
+// imgaussfilt: one image per blockIdx.z, input inside G's footprint, output inside B's
 template <int R>
 __global__ __launch_bounds__(256) void compact_blur_kernel(const CLayer* __restrict__ G, const CLayer* __restrict__ B, int k0, int h,
                                                            int w, Taps tp) {
     const CLayer in = G[k0 + blockIdx.z], out = B[k0 + blockIdx.z];
-    constexpr int IW = kCBW + 2 * R, IH = kCBH + 2 * R;
-    const int x0 = out.r.x0 + blockIdx.x * kCBW, y0 = out.r.y0 + blockIdx.y * kCBH, tid = threadIdx.x;
-    if (x0 >= out.r.x1 || y0 >= out.r.y1) return;  // the grid is sized for the largest output rect of the launch
-    __shared__ float4 s_in[IH * IW];
-    __shared__ float4 s_v[kCBH * IW];
-    for (int e = tid; e < IH * IW; e += 256) {
-        const int ly = e / IW, lx = e - ly * IW;
-        const int gy = min(max(y0 + ly - R, 0), h - 1), gx = min(max(x0 + lx - R, 0), w - 1);
-        s_in[e] = ld_compact(in, gx, gy);
-    }
-    __syncthreads();
-    for (int e = tid; e < kCBH * IW; e += 256) {
-        const int ly = e / IW, lx = e - ly * IW;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_in[(ly + t) * IW + lx], a);
-        s_v[e] = a;
-    }
-    __syncthreads();
-    for (int e = tid; e < kCBH * kCBW; e += 256) {
-        const int ly = e / kCBW, lx = e - ly * kCBW;
-        const int gx = x0 + lx, gy = y0 + ly;
-        if (gx >= out.r.x1 || gy >= out.r.y1) continue;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_v[ly * IW + lx + t], a);
-        out.p[c_index(out, gx, gy)] = a;
-    }
+    blur_tile<R>([&](int x, int y) { return ld_compact(in, x, y); }, [&](int x, int y, float4 v) { out.p[c_index(out.r, x, y)] = v; },
+                 out.r, h, w, tp);
 }
 
-// resize_at (render.hip) with the load left to the caller: ld(x, y) returns the input pixel (zero outside a footprint).
-// Both passes of imresize for one output pixel, the smaller scale factor first, the same fmaf chains and zero-tap skips.
-template <bool ROWS_FIRST, class Ld>
-__device__ __forceinline__ float4 resize_with(const Ld& ld, int h, int w, int Pr, int lr, const float* wr, int Pc, int lc,
-                                              const float* wc) {
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ROWS_FIRST) {
-        for (int tc = 0; tc < Pc; ++tc) {
-            if (wc[tc] == 0.f) continue;
-            const int xx = min(max(lc + tc, 1), w) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tr = 0; tr < Pr; ++tr)
-                if (wr[tr] != 0.f) v = fma4(wr[tr], ld(xx, min(max(lr + tr, 1), h) - 1), v);
-            a = fma4(wc[tc], v, a);
-        }
-    } else {
-        for (int tr = 0; tr < Pr; ++tr) {
-            if (wr[tr] == 0.f) continue;
-            const int yy = min(max(lr + tr, 1), h) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tc = 0; tc < Pc; ++tc)
-                if (wc[tc] != 0.f) v = fma4(wc[tc], ld(min(max(lc + tc, 1), w) - 1, yy), v);
-            a = fma4(wr[tr], v, a);
-        }
-    }
-    return a;
-}
-
-// mb_resize_kernel on compact layers: blurred level (B, h x w) -> next Gaussian level (D, oh x ow), one image per blockIdx.z
+// imresize: blurred level (B, h x w) -> next Gaussian level (D, oh x ow), one image per blockIdx.z
 template <bool ROWS_FIRST>
 __global__ __launch_bounds__(128) void compact_resize_kernel(const CLayer* __restrict__ B, const CLayer* __restrict__ D, int k0, int h,
                                                              int w, int oh, int ow) {
@@ -747,95 +693,24 @@ __global__ __launch_bounds__(128) void compact_resize_kernel(const CLayer* __res
     float wr[12], wc[12];
     const int Pr = resize_taps(h, oh, y, lr, wr);
     const int Pc = resize_taps(w, ow, x, lc, wc);
-    out.p[c_index(out, x, y)] =
+    out.p[c_index(out.r, x, y)] =
         resize_with<ROWS_FIRST>([&](int xx, int yy) { return ld_compact(in, xx, yy); }, h, w, Pr, lr, wr, Pc, lc, wc);
 }
 
-// mb_lap_all_kernel over the block's contributors: Num_l = sum_k (G_k - imresize(D_k, size_l)) .* w_k in ascending image order
-// from +0, every contributor in this one pass; has_d == 0: the coarsest level, Num_L = sum_k G_k .* w_k.
+// The Laplacian numerator of one level over the block's contributors, every contributor in this one pass, from +0
+// (lap_accumulate); 32 x 4 pixels per workgroup, inside one list block.
+struct CompactWalk : CompactSet::At {
+    const CLayer* __restrict__ D;  // the next level's table
+    __device__ __forceinline__ float4 d(int i, int xx, int yy) const { return ld_compact(D[idx[i]], xx, yy); }
+};
 template <bool ROWS_FIRST>
-__global__ __launch_bounds__(128) void compact_lap_kernel(const CLayer* __restrict__ G, const CLayer* __restrict__ D,
-                                                          const int* __restrict__ lists, int bw, int nblocks, int has_d, int h, int w,
-                                                          int dh, int dw, float4* __restrict__ num) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 4 + (threadIdx.x >> 5);
+__global__ __launch_bounds__(128) void compact_lap_kernel(CompactSet set, const CLayer* __restrict__ D, int has_d, int dh, int dw,
+                                                          float4* __restrict__ num) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 4 + (threadIdx.x >> 5), h = set.H, w = set.W;
     if (x >= w || y >= h) return;
-    const BlockList bl = block_list(lists, bw, nblocks, x, y);
     float acc[3] = {0.f, 0.f, 0.f};
-    int lr = 0, lc = 0, Pr = 0, Pc = 0;
-    float wr[12], wc[12];
-    bool have_taps = false;
-    for (int i = 0; i < bl.n; ++i) {
-        const int k = bl.idx[i];
-        const CLayer& c = G[k];
-        if (!in_rect(c.r, x, y)) continue;
-        const float4 g = c.p[c_index(c, x, y)];
-        if (!has_d) {
-            acc[0] = acc[0] + g.x * g.w;
-            acc[1] = acc[1] + g.y * g.w;
-            acc[2] = acc[2] + g.z * g.w;
-            continue;
-        }
-        if (!have_taps) {
-            Pr = resize_taps(dh, h, y, lr, wr);
-            Pc = resize_taps(dw, w, x, lc, wc);
-            have_taps = true;
-        }
-        const CLayer& d = D[k];
-        const float4 u = resize_with<ROWS_FIRST>([&](int xx, int yy) { return ld_compact(d, xx, yy); }, dh, dw, Pr, lr, wr, Pc, lc, wc);
-        acc[0] = acc[0] + (g.x - u.x) * g.w;
-        acc[1] = acc[1] + (g.y - u.y) * g.w;
-        acc[2] = acc[2] + (g.z - u.z) * g.w;
-    }
+    lap_accumulate<ROWS_FIRST>(CompactWalk{set.at(x, y), D}, has_d, x, y, h, w, dh, dw, acc);
     num[(size_t)y * w + x] = make_float4(acc[0], acc[1], acc[2], 0.f);
-}
-
-// mb_collapse_kernel: F_l = imresize(F_(l+1), size_l) + Num_l (canvas-sized buffers, no layers involved)
-template <bool ROWS_FIRST>
-__global__ __launch_bounds__(128) void compact_collapse_kernel(const float4* __restrict__ Fc, int ch, int cw,
-                                                               const float4* __restrict__ num, int h, int w, float4* __restrict__ out) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 4 + (threadIdx.x >> 5);
-    if (x >= w || y >= h) return;
-    int lr, lc;
-    float wr[12], wc[12];
-    const int Pr = resize_taps(ch, h, y, lr, wr);
-    const int Pc = resize_taps(cw, w, x, lc, wc);
-    const float4 u = resize_with<ROWS_FIRST>([&](int xx, int yy) { return Fc[(size_t)yy * cw + xx]; }, ch, cw, Pr, lr, wr, Pc, lc, wc);
-    const float4 n = num[(size_t)y * w + x];
-    out[(size_t)y * w + x] = make_float4(u.x + n.x, u.y + n.y, u.z + n.z, 0.f);
-}
-
-// planar_gain_stats_kernel over the block's contributors: the pairs of a sampled point are pairs of its block's list
-__global__ __launch_bounds__(256) void compact_gain_stats_kernel(const CLayer* __restrict__ G, const int* __restrict__ lists, int bw,
-                                                                 int nblocks, int n_img, int ds, int ws, int hs,
-                                                                 double* __restrict__ Nij, double* __restrict__ sCi,
-                                                                 double* __restrict__ sCj) {
-    __shared__ GainPairTable s_tab;
-    s_tab.init();
-    const int ix = blockIdx.x * 16 + (threadIdx.x & 15), iy = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (ix < ws && iy < hs) {
-        const int x = ix * ds, y = iy * ds;
-        const BlockList bl = block_list(lists, bw, nblocks, x, y);
-        auto sample = [&](int k, float* c3) {
-            const CLayer& c = G[k];
-            if (!in_rect(c.r, x, y)) return false;
-            const float4 g = c.p[c_index(c, x, y)];
-            c3[0] = g.x;
-            c3[1] = g.y;
-            c3[2] = g.z;
-            return g.w > 0.f && isfinite(g.x) && isfinite(g.y) && isfinite(g.z);
-        };
-        for (int a = 0; a < bl.n; ++a) {
-            float ci[3];
-            const int i = bl.idx[a];
-            if (!sample(i, ci)) continue;
-            for (int b = a + 1; b < bl.n; ++b) {
-                float cj[3];
-                const int j = bl.idx[b];
-                if (sample(j, cj)) s_tab.add(n_img, i, j, ci, cj, Nij, sCi, sCj);
-            }
-        }
-    }
-    s_tab.flush(n_img, Nij, sCi, sCj);
 }
 
 // ---- host orchestration --------------------------------------------------------------------------
@@ -847,13 +722,14 @@ struct CompactDevice {
     Ws<int> lists;
     const CLayer* G(int l, int n) const { return tab.get() + (size_t)l * n; }
     const CLayer* B(int l, int n, int L_) const { return tab.get() + (size_t)(L_ + l) * n; }
+    CompactSet set(const CompactPlan& pl, int l, int n) const {
+        return CompactSet{G(l, n), lists.get() + pl.list_off[l], pl.bw[l], pl.bw[l] * pl.bh[l], pl.lw[l], pl.lh[l]};
+    }
 };
 
 // Allocates the arena, uploads tables and lists, warps every image into its footprint (level 0).
-static void compact_setup(const CompactPlan& pl, const uint8_t* const* images, const int* ih, const int* iw, const int* ic, int n,
-                          const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, const float* gains,
-                          CompactDevice& D) {
-    const int L = pl.L;
+static void compact_setup(const CompactPlan& pl, const PlanarArgs& a, const float* gains, CompactDevice& D) {
+    const int L = pl.L, n = a.n;
     D.arena.alloc((size_t)pl.layer_px);
     if (pl.blur_px) D.blur.alloc((size_t)pl.blur_px);
     D.host_tab.resize((size_t)n * (2 * L - 1));
@@ -867,12 +743,9 @@ static void compact_setup(const CompactPlan& pl, const uint8_t* const* images, c
     APS_HIP(hipMemcpyAsync(D.tab, D.host_tab.data(), D.host_tab.size() * sizeof(CLayer), hipMemcpyHostToDevice, stream()));
     APS_HIP(hipMemcpyAsync(D.lists, pl.lists.data(), pl.lists.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
     D.L.layers.resize(n);
-    D.L.rects.resize(n);
-    for (int k = 0; k < n; ++k) {
-        D.L.layers[k] = D.arena.get() + pl.goff[0][k];
-        D.L.rects[k] = pl.gr[0][k];
-    }
-    planar_build_layers(images, ih, iw, ic, n, H, out_h, out_w, x0, y0, sx, sy, gains, D.L, true);
+    for (int k = 0; k < n; ++k) D.L.layers[k] = D.arena.get() + pl.goff[0][k];
+    D.L.rects = pl.gr[0];
+    planar_build_layers(a, gains, true, D.L);
 }
 
 // multiband_device on compact layers with normalised weights: per level, blur and downsample every layer inside its
@@ -903,7 +776,7 @@ static void compact_multiband(const CompactPlan& pl, const CompactDevice& D, int
                 int mw, mh;
                 span(pl.br[l].data() + k0, kc, mw, mh);
                 if (mw > 0 && mh > 0) {
-                    const dim3 bg(cdiv(mw, kCBW), cdiv(mh, kCBH), kc);
+                    const dim3 bg(cdiv(mw, kBlurW), cdiv(mh, kBlurH), kc);
                     switch (tp.r) {
                         case 1: compact_blur_kernel<1><<<bg, 256, 0, stream()>>>(G, B, k0, hl, wl, tp); break;
                         case 2: compact_blur_kernel<2><<<bg, 256, 0, stream()>>>(G, B, k0, hl, wl, tp); break;
@@ -923,48 +796,105 @@ static void compact_multiband(const CompactPlan& pl, const CompactDevice& D, int
             check_launch("compact pyramid level");
         }
         float4* dst = (last && L == 1) ? F : num[l].get();
-        const int* lists = D.lists.get() + pl.list_off[l];
-        const int nblocks = pl.bw[l] * pl.bh[l];
         const dim3 lg(cdiv(wl, 32), cdiv(hl, 4));
         if (last || rows_first(nh, nw, hl, wl))
-            compact_lap_kernel<true><<<lg, 128, 0, stream()>>>(G, last ? G : D.G(l + 1, n), lists, pl.bw[l], nblocks, last ? 0 : 1, hl, wl, nh, nw, dst);
+            compact_lap_kernel<true><<<lg, 128, 0, stream()>>>(D.set(pl, l, n), last ? G : D.G(l + 1, n), last ? 0 : 1, nh, nw, dst);
         else
-            compact_lap_kernel<false><<<lg, 128, 0, stream()>>>(G, D.G(l + 1, n), lists, pl.bw[l], nblocks, 1, hl, wl, nh, nw, dst);
+            compact_lap_kernel<false><<<lg, 128, 0, stream()>>>(D.set(pl, l, n), D.G(l + 1, n), 1, nh, nw, dst);
         check_launch("compact_lap_kernel");
     }
-    std::vector<Ws<float4>> fl(std::max(L - 1, 0));
-    const float4* cur = L > 1 ? num[L - 1].get() : nullptr;
-    for (int l = L - 2; l >= 0; --l) {
-        float4* dst = F;
-        if (l > 0) {
-            fl[l].alloc((size_t)pl.lh[l] * pl.lw[l]);
-            dst = fl[l];
-        }
-        const dim3 cg(cdiv(pl.lw[l], 32), cdiv(pl.lh[l], 4));
-        if (rows_first(pl.lh[l + 1], pl.lw[l + 1], pl.lh[l], pl.lw[l]))
-            compact_collapse_kernel<true><<<cg, 128, 0, stream()>>>(cur, pl.lh[l + 1], pl.lw[l + 1], num[l], pl.lh[l], pl.lw[l], dst);
-        else
-            compact_collapse_kernel<false><<<cg, 128, 0, stream()>>>(cur, pl.lh[l + 1], pl.lw[l + 1], num[l], pl.lh[l], pl.lw[l], dst);
-        check_launch("compact_collapse_kernel");
-        cur = dst;
-    }
+    multiband_collapse(num, pl.lh, pl.lw, F);
 }
 
 constexpr int kCompactMaxImages = 0x7fffffff;  // what remains is the int32 range of tables and lists (compact_plan)
 constexpr int kCompactRadius = 4;  // the byte formula charges every footprint as for the widest filter built (9 taps)
 constexpr int kCompactGainMaxImages = 65535;  // GainPairTable keys a pair as i * n + j + 1 in 32 bits
 
-static void compact_check_blending(int blending, int levels, float sigma, bool need_sigma) {
-    APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND, APS_E_ARG,
-                "unknown blending mode %d", blending);
-    if (blending == APS_BLEND_MULTIBAND) {
-        APS_REQUIRE(levels >= 1, APS_E_ARG, "levels must be a positive integer");
-        if (!need_sigma) return;
-        APS_REQUIRE(sigma > 0, APS_E_ARG, "sigma must be positive");
-        const Taps tp = make_taps(sigma);
-        APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built", (double)sigma,
-                    2 * tp.r + 1);
+// The compact compositor's half of planar_composite_impl / planar_gain_stats_impl.
+struct CompactCompositor {
+    static constexpr int kMaxImages = kCompactMaxImages, kGainMaxImages = kCompactGainMaxImages;
+    static constexpr const char *kNorm = "compact_norm_kernel", *kFuse = "compact_fuse_kernel", *kGain = "compact_gain_stats_kernel",
+                                *kGainProf = "planar_gain_stats_compact";
+    const PlanarArgs& a;
+    CompactPlan pl;
+    CompactDevice D;
+    // counts with the formula's radius, refuses what cannot fit, then plans with the call's own radius and fills the lists
+    void plan(int blending, int levels, float sigma, int64_t stats_bytes) {
+        const bool mb = blending == APS_BLEND_MULTIBAND;
+        compact_plan(a, mb ? levels : 1, kCompactRadius, false, pl);
+        planar_precheck(compact_bytes(pl, a, blending) + stats_bytes);
+        compact_plan(a, mb ? levels : 1, mb ? make_taps(sigma).r : 0, true, pl);
     }
+    void build(const float* gains) { compact_setup(pl, a, gains, D); }
+    CompactSet set() const { return D.set(pl, 0, a.n); }
+    dim3 grid() const { return dim3(cdiv(a.out_w, 64), cdiv(a.out_h, 4)); }
+    void multiband(int, float sigma, float4* F) { compact_multiband(pl, D, a.n, sigma, F); }
+};
+
+// ------------------------------------------------------------------------------------------------
+// the entry points' bodies, for either compositor
+// ------------------------------------------------------------------------------------------------
+template <class Compositor>
+static void planar_composite_impl(const PlanarArgs& a, int blending, int levels, float sigma, int white_canvas, const float* gains,
+                                  uint8_t* pano, uint8_t* covered) {
+    planar_check_shapes(a, Compositor::kMaxImages);
+    APS_REQUIRE(pano, APS_E_ARG, "NULL argument");
+    planar_check_blending(blending, levels, sigma, true);
+    ctx();
+    Compositor c{a};
+    c.plan(blending, levels, sigma, 0);
+    const size_t P = (size_t)a.out_h * a.out_w;
+    Out<uint8_t> oP(pano, 3 * P), oC(covered, P);
+    c.build(gains);
+    uint8_t* cov_out = oC.present() ? oC.get() : nullptr;
+    const int white = white_canvas ? 1 : 0;
+    const auto set = c.set();
+    const dim3 grid = c.grid();
+    if (blending == APS_BLEND_MULTIBAND) {
+        Ws<uint8_t> cov(P);
+        Ws<float4> F(P);
+        planar_norm_kernel<<<grid, 256, 0, stream()>>>(set, cov.get());
+        check_launch(Compositor::kNorm);
+        c.multiband(levels, sigma, F);
+        planar_finish_kernel<<<cdiv(P, 256), 256, 0, stream()>>>(F, cov, P, white, oP.get(), cov_out);
+        check_launch("planar_finish_kernel");
+    } else {
+        if (blending == APS_BLEND_LINEAR)
+            planar_fuse_kernel<APS_BLEND_LINEAR><<<grid, 256, 0, stream()>>>(set, white, oP.get(), cov_out);
+        else
+            planar_fuse_kernel<APS_BLEND_NONE><<<grid, 256, 0, stream()>>>(set, white, oP.get(), cov_out);
+        check_launch(Compositor::kFuse);
+    }
+    oP.commit();
+    oC.commit();
+    APS_HIP(hipStreamSynchronize(stream()));  // the staged inputs, tables and the workspace must outlive the launches
+}
+
+template <class Compositor>
+static void planar_gain_stats_impl(const PlanarArgs& a, int downsample, double* n_ij, double* sum_ci, double* sum_cj) {
+    planar_check_shapes(a, Compositor::kGainMaxImages);
+    APS_REQUIRE(n_ij && sum_ci && sum_cj, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(downsample >= 1, APS_E_ARG, "overlapDownsample must be >= 1");
+    ctx();
+    const size_t nn = (size_t)a.n * a.n;
+    Compositor c{a};
+    c.plan(APS_BLEND_NONE, 1, 0.f, (int64_t)(7 * nn * sizeof(double)));
+    c.build(nullptr);
+    Out<double> oN(n_ij, nn), oI(sum_ci, 3 * nn), oJ(sum_cj, 3 * nn);
+    APS_HIP(hipMemsetAsync(oN.get(), 0, nn * sizeof(double), stream()));
+    APS_HIP(hipMemsetAsync(oI.get(), 0, 3 * nn * sizeof(double), stream()));
+    APS_HIP(hipMemsetAsync(oJ.get(), 0, 3 * nn * sizeof(double), stream()));
+    const int ws = (a.out_w - 1) / downsample + 1, hs = (a.out_h - 1) / downsample + 1;  // numel(1:ds:end)
+    {
+        Prof prof(Compositor::kGainProf);
+        planar_gain_stats_kernel<<<dim3(cdiv(ws, 16), cdiv(hs, 16)), 256, 0, stream()>>>(c.set(), a.n, downsample, ws, hs, oN.get(),
+                                                                                      oI.get(), oJ.get());
+    }
+    check_launch(Compositor::kGain);
+    oN.commit();
+    oI.commit();
+    oJ.commit();
+    APS_HIP(hipStreamSynchronize(stream()));
 }
 
 }  // namespace aps
@@ -977,18 +907,10 @@ int64_t aps_planar_composite_bytes(int n_img, const int* img_h, const int* img_w
                                    int blending, int levels) {
     int64_t bytes = 0;
     const int st = guarded([&] {
-        APS_REQUIRE(img_h && img_w && img_c, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(n_img >= 1, APS_E_ARG, "need at least one image (%d)", n_img);
-        APS_REQUIRE(n_img <= kPlanarMaxImages, APS_E_DIM, "more than %d images in one planar composite (%d)", kPlanarMaxImages, n_img);
-        APS_REQUIRE(out_h > 0 && out_w > 0 && (int64_t)out_h * out_w < ((int64_t)1 << 31), APS_E_DIM, "bad canvas size %d x %d", out_h,
-                    out_w);
-        APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND, APS_E_ARG,
-                    "unknown blending mode %d", blending);
-        APS_REQUIRE(blending != APS_BLEND_MULTIBAND || levels >= 1, APS_E_ARG, "levels must be a positive integer");
-        for (int k = 0; k < n_img; ++k)
-            APS_REQUIRE(img_h[k] > 0 && img_w[k] > 0 && (img_c[k] == 1 || img_c[k] == 3), APS_E_DIM, "image %d: bad size %d x %d x %d", k,
-                        img_h[k], img_w[k], img_c[k]);
-        bytes = planar_bytes(n_img, img_h, img_w, img_c, out_h, out_w, blending, levels);
+        const PlanarArgs a{nullptr, img_h, img_w, img_c, n_img, nullptr, out_h, out_w, 0, 0, 1, 1};
+        planar_check_shapes(a, kPlanarMaxImages, false, false);
+        planar_check_blending(blending, levels, 0.f, false);
+        bytes = planar_bytes(a, blending, levels);
     });
     return st == APS_OK ? bytes : (int64_t)st;
 }
@@ -1021,43 +943,8 @@ int aps_planar_composite(const uint8_t* const* images, const int* img_h, const i
                          const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int blending, int levels,
                          float sigma, int white_canvas, const float* gains, uint8_t* pano, uint8_t* covered) {
     return guarded([&] {
-        planar_check_args(images, img_h, img_w, img_c, n_img, H, out_h, out_w, sx, sy);
-        APS_REQUIRE(pano, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND, APS_E_ARG,
-                    "unknown blending mode %d", blending);
-        if (blending == APS_BLEND_MULTIBAND) {
-            APS_REQUIRE(levels >= 1, APS_E_ARG, "levels must be a positive integer");
-            APS_REQUIRE(sigma > 0, APS_E_ARG, "sigma must be positive");
-            const Taps tp = make_taps(sigma);
-            APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built", (double)sigma,
-                        2 * tp.r + 1);
-        }
-        ctx();
-        planar_precheck(planar_bytes(n_img, img_h, img_w, img_c, out_h, out_w, blending, levels));
-        const size_t P = (size_t)out_h * out_w;
-        Out<uint8_t> oP(pano, 3 * P), oC(covered, P);
-        PlanarLayers L;
-        planar_build_layers(images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy, gains, L);
-        uint8_t* cov_out = oC.present() ? oC.get() : nullptr;
-        const int white = white_canvas ? 1 : 0;
-        if (blending == APS_BLEND_MULTIBAND) {
-            Ws<uint8_t> cov(P);
-            Ws<float4> F(P);
-            planar_norm_kernel<<<cdiv(P, 256), 256, 0, stream()>>>(L.jobs.get(), n_img, out_w, P, cov);
-            check_launch("planar_norm_kernel");
-            multiband_device(L.layers, L.rects.data(), out_h, out_w, levels, sigma, F);
-            planar_finish_kernel<<<cdiv(P, 256), 256, 0, stream()>>>(F, cov, P, white, oP.get(), cov_out);
-            check_launch("planar_finish_kernel");
-        } else {
-            if (blending == APS_BLEND_LINEAR)
-                planar_fuse_kernel<APS_BLEND_LINEAR><<<cdiv(P, 256), 256, 0, stream()>>>(L.jobs.get(), n_img, out_w, P, white, oP.get(), cov_out);
-            else
-                planar_fuse_kernel<APS_BLEND_NONE><<<cdiv(P, 256), 256, 0, stream()>>>(L.jobs.get(), n_img, out_w, P, white, oP.get(), cov_out);
-            check_launch("planar_fuse_kernel");
-        }
-        oP.commit();
-        oC.commit();
-        APS_HIP(hipStreamSynchronize(stream()));  // the staged inputs and the workspace must outlive the launches
+        planar_composite_impl<DenseCompositor>(PlanarArgs{images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy}, blending,
+                                               levels, sigma, white_canvas, gains, pano, covered);
     });
 }
 
@@ -1065,29 +952,8 @@ int aps_planar_gain_stats(const uint8_t* const* images, const int* img_h, const 
                           const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int downsample,
                           double* n_ij, double* sum_ci, double* sum_cj) {
     return guarded([&] {
-        planar_check_args(images, img_h, img_w, img_c, n_img, H, out_h, out_w, sx, sy);
-        APS_REQUIRE(n_ij && sum_ci && sum_cj, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(downsample >= 1, APS_E_ARG, "overlapDownsample must be >= 1");
-        ctx();
-        planar_precheck(planar_bytes(n_img, img_h, img_w, img_c, out_h, out_w, APS_BLEND_NONE, 1));
-        PlanarLayers L;
-        planar_build_layers(images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy, nullptr, L);
-        const size_t nn = (size_t)n_img * n_img;
-        Out<double> oN(n_ij, nn), oI(sum_ci, 3 * nn), oJ(sum_cj, 3 * nn);
-        APS_HIP(hipMemsetAsync(oN.get(), 0, nn * sizeof(double), stream()));
-        APS_HIP(hipMemsetAsync(oI.get(), 0, 3 * nn * sizeof(double), stream()));
-        APS_HIP(hipMemsetAsync(oJ.get(), 0, 3 * nn * sizeof(double), stream()));
-        const int ws = (out_w - 1) / downsample + 1, hs = (out_h - 1) / downsample + 1;  // numel(1:ds:end)
-        {
-            Prof prof("planar_gain_stats");
-            planar_gain_stats_kernel<<<dim3(cdiv(ws, 16), cdiv(hs, 16)), 256, 0, stream()>>>(L.jobs.get(), n_img, out_w, downsample, ws, hs,
-                                                                                          oN.get(), oI.get(), oJ.get());
-        }
-        check_launch("planar_gain_stats_kernel");
-        oN.commit();
-        oI.commit();
-        oJ.commit();
-        APS_HIP(hipStreamSynchronize(stream()));
+        planar_gain_stats_impl<DenseCompositor>(PlanarArgs{images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy}, downsample,
+                                                n_ij, sum_ci, sum_cj);
     });
 }
 
@@ -1095,12 +961,12 @@ int64_t aps_planar_composite_compact_bytes(int n_img, const int* img_h, const in
                                            int out_w, double x0, double y0, double sx, double sy, int blending, int levels) {
     int64_t bytes = 0;
     const int st = guarded([&] {
-        planar_check_args(nullptr, img_h, img_w, img_c, n_img, H, out_h, out_w, sx, sy, kCompactMaxImages, false);
-        compact_check_blending(blending, levels, 0.f, false);
+        const PlanarArgs a{nullptr, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy};
+        planar_check_shapes(a, kCompactMaxImages, false);
+        planar_check_blending(blending, levels, 0.f, false);
         CompactPlan pl;
-        compact_plan(n_img, img_h, img_w, H, out_h, out_w, x0, y0, sx, sy, compact_levels(out_h, out_w, blending, levels), kCompactRadius,
-                     false, pl);
-        bytes = compact_bytes(pl, n_img, img_h, img_w, img_c, out_h, out_w, blending);
+        compact_plan(a, blending == APS_BLEND_MULTIBAND ? levels : 1, kCompactRadius, false, pl);
+        bytes = compact_bytes(pl, a, blending);
     });
     return st == APS_OK ? bytes : (int64_t)st;
 }
@@ -1109,42 +975,8 @@ int aps_planar_composite_compact(const uint8_t* const* images, const int* img_h,
                                  const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int blending,
                                  int levels, float sigma, int white_canvas, const float* gains, uint8_t* pano, uint8_t* covered) {
     return guarded([&] {
-        planar_check_args(images, img_h, img_w, img_c, n_img, H, out_h, out_w, sx, sy, kCompactMaxImages);
-        APS_REQUIRE(pano, APS_E_ARG, "NULL argument");
-        compact_check_blending(blending, levels, sigma, true);
-        ctx();
-        const int L = compact_levels(out_h, out_w, blending, levels);
-        CompactPlan pl;
-        compact_plan(n_img, img_h, img_w, H, out_h, out_w, x0, y0, sx, sy, L, kCompactRadius, false, pl);
-        planar_precheck(compact_bytes(pl, n_img, img_h, img_w, img_c, out_h, out_w, blending));
-        compact_plan(n_img, img_h, img_w, H, out_h, out_w, x0, y0, sx, sy, L, blending == APS_BLEND_MULTIBAND ? make_taps(sigma).r : 0, true,
-                     pl);
-        const size_t P = (size_t)out_h * out_w;
-        Out<uint8_t> oP(pano, 3 * P), oC(covered, P);
-        CompactDevice D;
-        compact_setup(pl, images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy, gains, D);
-        uint8_t* cov_out = oC.present() ? oC.get() : nullptr;
-        const int white = white_canvas ? 1 : 0, nblocks = pl.bw[0] * pl.bh[0];
-        const int* lists0 = D.lists.get() + pl.list_off[0];
-        const dim3 pg(cdiv(out_w, 64), cdiv(out_h, 4));
-        if (blending == APS_BLEND_MULTIBAND) {
-            Ws<uint8_t> cov(P);
-            Ws<float4> F(P);
-            compact_norm_kernel<<<pg, 256, 0, stream()>>>(D.G(0, n_img), lists0, pl.bw[0], nblocks, out_w, out_h, cov);
-            check_launch("compact_norm_kernel");
-            compact_multiband(pl, D, n_img, sigma, F);
-            planar_finish_kernel<<<cdiv(P, 256), 256, 0, stream()>>>(F, cov, P, white, oP.get(), cov_out);
-            check_launch("planar_finish_kernel");
-        } else {
-            if (blending == APS_BLEND_LINEAR)
-                compact_fuse_kernel<APS_BLEND_LINEAR><<<pg, 256, 0, stream()>>>(D.G(0, n_img), lists0, pl.bw[0], nblocks, out_w, out_h, white, oP.get(), cov_out);
-            else
-                compact_fuse_kernel<APS_BLEND_NONE><<<pg, 256, 0, stream()>>>(D.G(0, n_img), lists0, pl.bw[0], nblocks, out_w, out_h, white, oP.get(), cov_out);
-            check_launch("compact_fuse_kernel");
-        }
-        oP.commit();
-        oC.commit();
-        APS_HIP(hipStreamSynchronize(stream()));  // the staged inputs, tables and the workspace must outlive the launches
+        planar_composite_impl<CompactCompositor>(PlanarArgs{images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy}, blending,
+                                                 levels, sigma, white_canvas, gains, pano, covered);
     });
 }
 
@@ -1152,32 +984,8 @@ int aps_planar_gain_stats_compact(const uint8_t* const* images, const int* img_h
                                   const double* H, int out_h, int out_w, double x0, double y0, double sx, double sy, int downsample,
                                   double* n_ij, double* sum_ci, double* sum_cj) {
     return guarded([&] {
-        planar_check_args(images, img_h, img_w, img_c, n_img, H, out_h, out_w, sx, sy, kCompactGainMaxImages);
-        APS_REQUIRE(n_ij && sum_ci && sum_cj, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(downsample >= 1, APS_E_ARG, "overlapDownsample must be >= 1");
-        ctx();
-        CompactPlan pl;
-        compact_plan(n_img, img_h, img_w, H, out_h, out_w, x0, y0, sx, sy, 1, 0, true, pl);
-        const size_t nn = (size_t)n_img * n_img;
-        planar_precheck(compact_bytes(pl, n_img, img_h, img_w, img_c, out_h, out_w, APS_BLEND_NONE) + (int64_t)(7 * nn * sizeof(double)));
-        CompactDevice D;
-        compact_setup(pl, images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy, nullptr, D);
-        Out<double> oN(n_ij, nn), oI(sum_ci, 3 * nn), oJ(sum_cj, 3 * nn);
-        APS_HIP(hipMemsetAsync(oN.get(), 0, nn * sizeof(double), stream()));
-        APS_HIP(hipMemsetAsync(oI.get(), 0, 3 * nn * sizeof(double), stream()));
-        APS_HIP(hipMemsetAsync(oJ.get(), 0, 3 * nn * sizeof(double), stream()));
-        const int ws = (out_w - 1) / downsample + 1, hs = (out_h - 1) / downsample + 1;  // numel(1:ds:end)
-        {
-            Prof prof("planar_gain_stats_compact");
-            compact_gain_stats_kernel<<<dim3(cdiv(ws, 16), cdiv(hs, 16)), 256, 0, stream()>>>(
-                D.G(0, n_img), D.lists.get() + pl.list_off[0], pl.bw[0], pl.bw[0] * pl.bh[0], n_img, downsample, ws, hs, oN.get(), oI.get(),
-                oJ.get());
-        }
-        check_launch("compact_gain_stats_kernel");
-        oN.commit();
-        oI.commit();
-        oJ.commit();
-        APS_HIP(hipStreamSynchronize(stream()));
+        planar_gain_stats_impl<CompactCompositor>(PlanarArgs{images, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy},
+                                                  downsample, n_ij, sum_ci, sum_cj);
     });
 }
 

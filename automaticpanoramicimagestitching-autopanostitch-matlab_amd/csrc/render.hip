@@ -532,72 +532,22 @@ static void imresize4(const float4* in, int h, int w, int oh, int ow, float4* ou
 // ------------------------------------------------------------------------------------------------
 // fused pyramid kernels (same per-stage f32 roundings as the unfused building blocks above)
 // ------------------------------------------------------------------------------------------------
-// imgaussfilt: column (vertical) pass then row pass through one LDS tile; replicate padding.
-constexpr int kBW = 32, kBH = 16;  // output tile of mb_blur_kernel
+// imgaussfilt (blur_tile, render_dev.h) on canvas-pitch layers: input inside irs' footprints, output inside ors'.
 template <int R>
 __global__ __launch_bounds__(256) void mb_blur_kernel(PtrTab ins, RectTab irs, int h, int w, Taps tp, PtrTab outs,
                                                       RectTab ors) {
     const float4* __restrict__ in = ins.p[blockIdx.z];
     float4* __restrict__ out = outs.p[blockIdx.z];
     const Rect ir = irs.r[blockIdx.z], orc = ors.r[blockIdx.z];
-    constexpr int IW = kBW + 2 * R, IH = kBH + 2 * R;
-    const int x0 = orc.x0 + blockIdx.x * kBW, y0 = orc.y0 + blockIdx.y * kBH, tid = threadIdx.x;
-    if (x0 >= orc.x1 || y0 >= orc.y1) return;  // the grid is sized for the largest output rect of the launch
-    __shared__ float4 s_in[IH * IW];
-    __shared__ float4 s_v[kBH * IW];
-    for (int e = tid; e < IH * IW; e += 256) {
-        const int ly = e / IW, lx = e - ly * IW;
-        const int gy = min(max(y0 + ly - R, 0), h - 1), gx = min(max(x0 + lx - R, 0), w - 1);
-        s_in[e] = ld_rect(in, w, ir, gx, gy);
-    }
-    __syncthreads();
-    for (int e = tid; e < kBH * IW; e += 256) {  // vertical pass for every column of the haloed tile
-        const int ly = e / IW, lx = e - ly * IW;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_in[(ly + t) * IW + lx], a);
-        s_v[e] = a;
-    }
-    __syncthreads();
-    for (int e = tid; e < kBH * kBW; e += 256) {  // horizontal pass
-        const int ly = e / kBW, lx = e - ly * kBW;
-        const int gx = x0 + lx, gy = y0 + ly;
-        if (gx >= orc.x1 || gy >= orc.y1) continue;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_v[ly * IW + lx + t], a);
-        out[(size_t)gy * w + gx] = a;
-    }
+    blur_tile<R>([&](int x, int y) { return ld_rect(in, w, ir, x, y); }, [&](int x, int y, float4 v) { out[(size_t)y * w + x] = v; }, orc,
+                 h, w, tp);
 }
 
-// imresize: both passes in one kernel.  Each thread produces one output pixel by evaluating, for each of its
-// second-pass taps, the first-pass result at that intermediate position (an fma chain over the first-pass taps).
-// The intermediate value depends only on its own position, so this equals materialising the intermediate image.
-// ROWS_FIRST = the reference's rule (smaller scale factor first, ties -> rows).
+// imresize (resize_with, render_dev.h) of a canvas-pitch layer that is zero outside its footprint
 template <bool ROWS_FIRST>
 __device__ __forceinline__ float4 resize_at(const float4* __restrict__ in, int h, int w, const Rect& ir, int Pr, int lr,
                                             const float* wr, int Pc, int lc, const float* wc) {
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ROWS_FIRST) {  // pass 1 resizes rows (at full width), pass 2 resizes columns
-        for (int tc = 0; tc < Pc; ++tc) {
-            if (wc[tc] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int xx = min(max(lc + tc, 1), w) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tr = 0; tr < Pr; ++tr)
-                if (wr[tr] != 0.f) v = fma4(wr[tr], ld_rect(in, w, ir, xx, min(max(lr + tr, 1), h) - 1), v);
-            a = fma4(wc[tc], v, a);
-        }
-    } else {
-        for (int tr = 0; tr < Pr; ++tr) {
-            if (wr[tr] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int yy = min(max(lr + tr, 1), h) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tc = 0; tc < Pc; ++tc)
-                if (wc[tc] != 0.f) v = fma4(wc[tc], ld_rect(in, w, ir, min(max(lc + tc, 1), w) - 1, yy), v);
-            a = fma4(wr[tr], v, a);
-        }
-    }
-    return a;
+    return resize_with<ROWS_FIRST>([&](int xx, int yy) { return ld_rect(in, w, ir, xx, yy); }, h, w, Pr, lr, wr, Pc, lc, wc);
 }
 
 template <bool ROWS_FIRST>
@@ -661,72 +611,38 @@ __global__ __launch_bounds__(256) void mb_blur_resize_kernel(PtrTab ins, RectTab
     float wr[12], wc[12];
     const int Pr = resize_taps(h, oh, y, lr, wr);
     const int Pc = resize_taps(w, ow, x, lc, wc);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ROWS_FIRST) {
-        for (int tc = 0; tc < Pc; ++tc) {
-            if (wc[tc] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int xx = min(max(lc + tc, 1), w) - 1 - bx0;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tr = 0; tr < Pr; ++tr)
-                if (wr[tr] != 0.f) v = fma4(wr[tr], s_a[(min(max(lr + tr, 1), h) - 1 - by0) * BC + xx], v);
-            a = fma4(wc[tc], v, a);
-        }
-    } else {
-        for (int tr = 0; tr < Pr; ++tr) {
-            if (wr[tr] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int yy = min(max(lr + tr, 1), h) - 1 - by0;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tc = 0; tc < Pc; ++tc)
-                if (wc[tc] != 0.f) v = fma4(wc[tc], s_a[yy * BC + min(max(lc + tc, 1), w) - 1 - bx0], v);
-            a = fma4(wr[tr], v, a);
-        }
-    }
-    out[(size_t)y * ow + x] = a;
+    out[(size_t)y * ow + x] =
+        resize_with<ROWS_FIRST>([&](int xx, int yy) { return s_a[(yy - by0) * BC + (xx - bx0)]; }, h, w, Pr, lr, wr, Pc, lc, wc);
 }
 
 // Level l of multiBandBlending.m:136-144 for ALL K layers in one pass:
 //   Num_l = sum_k (G_k - imresize(D_k, size_l)) .* w_k      (accumulated in layer order, from zero)
 // or, with D == nullptr, the coarsest level (:159): Num_L = sum_k G_k .* w_k.
-// A layer whose footprint does not contain the pixel contributes (0 - u) * 0: skipped.
+// in layer order (lap_accumulate, render_dev.h), continuing the sum of a previous chunk of layers when cont is set.
+struct TabWalk {  // the K layers of the tables, canvas pitch
+    const PtrTab &Gt, &Dt;
+    const RectTab &Gr, &Dr;
+    int n, w, dw;
+    size_t p;
+    __device__ __forceinline__ const Rect& rect(int i) const { return Gr.r[i]; }
+    __device__ __forceinline__ const float4* pixel(int i) const { return Gt.p[i] + p; }
+    __device__ __forceinline__ float4 d(int i, int xx, int yy) const { return ld_rect(Dt.p[i], dw, Dr.r[i], xx, yy); }
+};
 template <bool ROWS_FIRST>
 __global__ void mb_lap_all_kernel(PtrTab Gt, RectTab Gr, PtrTab Dt, RectTab Dr, int has_d, int cont, int K, int h, int w,
                                   int dh, int dw, float4* __restrict__ num) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 4 + (threadIdx.x >> 5);  // 32 x 4 per block
     if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * w + x;
     float acc[3] = {0.f, 0.f, 0.f};
-    if (cont) {  // continue the layer-ordered sum of a previous chunk of layers
-        const float4 p = num[(size_t)y * w + x];
-        acc[0] = p.x;
-        acc[1] = p.y;
-        acc[2] = p.z;
+    if (cont) {
+        const float4 c = num[p];
+        acc[0] = c.x;
+        acc[1] = c.y;
+        acc[2] = c.z;
     }
-    if (!has_d) {
-        for (int k = 0; k < K; ++k) {
-            if (!in_rect(Gr.r[k], x, y)) continue;
-            const float4 g = Gt.p[k][(size_t)y * w + x];
-            acc[0] = acc[0] + g.x * g.w;
-            acc[1] = acc[1] + g.y * g.w;
-            acc[2] = acc[2] + g.z * g.w;
-        }
-    } else {
-        int lr = 0, lc = 0, Pr = 0, Pc = 0;
-        float wr[12], wc[12];
-        bool have_taps = false;
-        for (int k = 0; k < K; ++k) {
-            if (!in_rect(Gr.r[k], x, y)) continue;
-            if (!have_taps) {
-                Pr = resize_taps(dh, h, y, lr, wr);
-                Pc = resize_taps(dw, w, x, lc, wc);
-                have_taps = true;
-            }
-            const float4 u = resize_at<ROWS_FIRST>(Dt.p[k], dh, dw, Dr.r[k], Pr, lr, wr, Pc, lc, wc);
-            const float4 g = Gt.p[k][(size_t)y * w + x];
-            acc[0] = acc[0] + (g.x - u.x) * g.w;
-            acc[1] = acc[1] + (g.y - u.y) * g.w;
-            acc[2] = acc[2] + (g.z - u.z) * g.w;
-        }
-    }
-    num[(size_t)y * w + x] = make_float4(acc[0], acc[1], acc[2], 0.f);
+    lap_accumulate<ROWS_FIRST>(TabWalk{Gt, Dt, Gr, Dr, K, w, dw, p}, has_d, x, y, h, w, dh, dw, acc);
+    num[p] = make_float4(acc[0], acc[1], acc[2], 0.f);
 }
 
 // collapse step (:166): F_l = imresize(F_{l+1}, size_l) + Num_l
@@ -739,28 +655,30 @@ __global__ void mb_collapse_kernel(const float4* __restrict__ Fc, int ch, int cw
     float wr[12], wc[12];
     const int Pr = resize_taps(ch, h, y, lr, wr);
     const int Pc = resize_taps(cw, w, x, lc, wc);
-    float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ROWS_FIRST) {
-        for (int tc = 0; tc < Pc; ++tc) {
-            if (wc[tc] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int xx = min(max(lc + tc, 1), cw) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tr = 0; tr < Pr; ++tr)
-                if (wr[tr] != 0.f) v = fma4(wr[tr], Fc[(size_t)(min(max(lr + tr, 1), ch) - 1) * cw + xx], v);
-            u = fma4(wc[tc], v, u);
-        }
-    } else {
-        for (int tr = 0; tr < Pr; ++tr) {
-            if (wr[tr] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
-            const int yy = min(max(lr + tr, 1), ch) - 1;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int tc = 0; tc < Pc; ++tc)
-                if (wc[tc] != 0.f) v = fma4(wc[tc], Fc[(size_t)yy * cw + min(max(lc + tc, 1), cw) - 1], v);
-            u = fma4(wr[tr], v, u);
-        }
-    }
+    const float4 u = resize_with<ROWS_FIRST>([&](int xx, int yy) { return Fc[(size_t)yy * cw + xx]; }, ch, cw, Pr, lr, wr, Pc, lc, wc);
     const float4 n = num[(size_t)y * w + x];
     out[(size_t)y * w + x] = make_float4(u.x + n.x, u.y + n.y, u.z + n.z, 0.f);
+}
+
+void multiband_collapse(const std::vector<Ws<float4>>& num, const std::vector<int>& lh, const std::vector<int>& lw, float4* F) {
+    const int levels = (int)lh.size();
+    std::vector<Ws<float4>> fl(std::max(levels - 1, 0));
+    const float4* cur = levels > 1 ? num[levels - 1].get() : nullptr;
+    for (int l = levels - 2; l >= 0; --l) {
+        float4* dst = F;
+        if (l > 0) {
+            fl[l].alloc((size_t)lh[l] * lw[l]);
+            dst = fl[l];
+        }
+        const dim3 cg(cdiv(lw[l], 32), cdiv(lh[l], 4));
+        if (rows_first(lh[l + 1], lw[l + 1], lh[l], lw[l]))
+            mb_collapse_kernel<true><<<cg, 128, 0, stream()>>>(cur, lh[l + 1], lw[l + 1], num[l], lh[l], lw[l], dst);
+        else
+            mb_collapse_kernel<false><<<cg, 128, 0, stream()>>>(cur, lh[l + 1], lw[l + 1], num[l], lh[l], lw[l], dst);
+        check_launch("mb_collapse_kernel");
+        cur = dst;
+    }
+    // no synchronisation: all buffers are stream-ordered workspace of this thread's stream
 }
 
 static PtrTab make_tab(float4* const* p, int count) {
@@ -803,15 +721,9 @@ void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int
     const int K = (int)layers.size();
     const size_t hw = (size_t)h * w;
     Prof prof("multiband");
-    int maxl = (int)std::floor(std::log2((double)std::min(h, w)));  // :98-109
-    levels = std::max(1, std::min(levels, maxl));
-    std::vector<int> lh(levels), lw(levels);
-    lh[0] = h;
-    lw[0] = w;
-    for (int l = 1; l < levels; ++l) {
-        lh[l] = std::max(1, lh[l - 1] / 2);
-        lw[l] = std::max(1, lw[l - 1] / 2);
-    }
+    std::vector<int> lh, lw;
+    pyramid_levels(h, w, levels, lh, lw);
+    levels = (int)lh.size();
     std::vector<Ws<float4>> store((size_t)std::max(levels - 1, 0) * K), blurred(std::min(K, kMaxK)), num(levels);
     std::vector<std::vector<float4*>> lev(levels, std::vector<float4*>(K));
     lev[0] = layers;
@@ -829,16 +741,10 @@ void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int
     for (int l = 0; l < levels; ++l) num[l].alloc((size_t)lh[l] * lw[l]);
     const Taps tp = make_taps(sigma);
     APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built", (double)sigma, 2 * tp.r + 1);
-    // footprints per level: G_l, blurred G_l (grown by the filter radius), G_{l+1} (mapped through the resize)
-    std::vector<std::vector<Rect>> gr(levels, std::vector<Rect>(K)), br(levels, std::vector<Rect>(K));
-    for (int k = 0; k < K; ++k) gr[0][k] = rects ? clip_rect(rects[k], w, h) : Rect{0, 0, w, h};
-    for (int l = 0; l < levels; ++l)
-        for (int k = 0; k < K; ++k) {
-            const Rect g = gr[l][k];
-            const bool empty = g.x1 <= g.x0;
-            br[l][k] = empty ? g : clip_rect(Rect{g.x0 - tp.r, g.y0 - tp.r, g.x1 + tp.r, g.y1 + tp.r}, lw[l], lh[l]);
-            if (l + 1 < levels) gr[l + 1][k] = empty ? g : map_rect(br[l][k], lh[l], lw[l], lh[l + 1], lw[l + 1]);
-        }
+    std::vector<Rect> g0(K);
+    for (int k = 0; k < K; ++k) g0[k] = rects ? clip_rect(rects[k], w, h) : Rect{0, 0, w, h};
+    std::vector<std::vector<Rect>> gr, br;
+    pyramid_footprints(g0, tp.r, lh, lw, gr, br);
     auto span = [](const Rect* r, int count, int& mw, int& mh) {
         mw = mh = 0;
         for (int k = 0; k < count; ++k) {
@@ -888,7 +794,7 @@ void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int
                 }
                 span(br[l].data() + k0, kc, mw, mh);
                 if (!fused && mw > 0 && mh > 0) {
-                    const dim3 bg(cdiv(mw, kBW), cdiv(mh, kBH), kc);
+                    const dim3 bg(cdiv(mw, kBlurW), cdiv(mh, kBlurH), kc);
                     switch (tp.r) {
                         case 1: mb_blur_kernel<1><<<bg, 256, 0, stream()>>>(gt, grt, hl, wl, tp, bt, brt); break;
                         case 2: mb_blur_kernel<2><<<bg, 256, 0, stream()>>>(gt, grt, hl, wl, tp, bt, brt); break;
@@ -913,23 +819,7 @@ void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int
             check_launch("multiband level");
         }
     }
-    // collapse (:163-167)
-    std::vector<Ws<float4>> fl(std::max(levels - 1, 0));
-    const float4* cur = levels > 1 ? num[levels - 1].get() : nullptr;
-    for (int l = levels - 2; l >= 0; --l) {
-        float4* dst = F;
-        if (l > 0) {
-            fl[l].alloc((size_t)lh[l] * lw[l]);
-            dst = fl[l];
-        }
-        if (rows_first(lh[l + 1], lw[l + 1], lh[l], lw[l]))
-            mb_collapse_kernel<true><<<dim3(cdiv(lw[l], 32), cdiv(lh[l], 4)), 128, 0, stream()>>>(cur, lh[l + 1], lw[l + 1], num[l], lh[l], lw[l], dst);
-        else
-            mb_collapse_kernel<false><<<dim3(cdiv(lw[l], 32), cdiv(lh[l], 4)), 128, 0, stream()>>>(cur, lh[l + 1], lw[l + 1], num[l], lh[l], lw[l], dst);
-        check_launch("mb_collapse_kernel");
-        cur = dst;
-    }
-    // no synchronisation: all buffers are stream-ordered workspace of this thread's stream
+    multiband_collapse(num, lh, lw, F);
 }
 
 struct ImgJob {

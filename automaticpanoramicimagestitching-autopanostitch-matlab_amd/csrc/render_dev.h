@@ -1,6 +1,7 @@
 // render_dev.h — device-side structures and sampling functions shared by render.hip (per-tile reference path,
-// linear/none blending, diagnostics) and render_batch.hip (the batched multiband path).  See render.hip's header
-// comment for the reference lines restated here.
+// linear/none blending, diagnostics), render_batch.hip (the batched multiband path) and planar.hip (the planar compositors),
+// and the one statement of the multiband pyramid's arithmetic (resize_with, blur_tile, lap_accumulate) and shape
+// (pyramid_levels, pyramid_footprints).  See render.hip's header comment for the reference lines restated here.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -198,6 +199,109 @@ __device__ __forceinline__ int resize_taps(int in_len, int out_len, int x, int& 
     return P;
 }
 
+// imresize for one output pixel, both passes, with the load left to the caller: ld(x, y) returns the input pixel (zero outside a
+// footprint, a patch in LDS, a plain image).  Per second-pass tap the first-pass result at that intermediate position is an fmaf
+// chain over the first-pass taps; the intermediate value depends only on its own position, so this equals materialising the
+// intermediate image.  ROWS_FIRST = the reference's rule (smaller scale factor first, ties -> rows).  Every resize of the
+// multiband pyramids, dense or compact, down or up, is this one function.
+template <bool ROWS_FIRST, class Ld>
+__device__ __forceinline__ float4 resize_with(const Ld& ld, int h, int w, int Pr, int lr, const float* wr, int Pc, int lc,
+                                              const float* wc) {
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ROWS_FIRST) {  // pass 1 resizes rows (at full width), pass 2 resizes columns
+        for (int tc = 0; tc < Pc; ++tc) {
+            if (wc[tc] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
+            const int xx = min(max(lc + tc, 1), w) - 1;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int tr = 0; tr < Pr; ++tr)
+                if (wr[tr] != 0.f) v = fma4(wr[tr], ld(xx, min(max(lr + tr, 1), h) - 1), v);
+            a = fma4(wc[tc], v, a);
+        }
+    } else {
+        for (int tr = 0; tr < Pr; ++tr) {
+            if (wr[tr] == 0.f) continue;  // a zero tap adds 0 * v: nothing (finite data)
+            const int yy = min(max(lr + tr, 1), h) - 1;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int tc = 0; tc < Pc; ++tc)
+                if (wc[tc] != 0.f) v = fma4(wc[tc], ld(min(max(lc + tc, 1), w) - 1, yy), v);
+            a = fma4(wr[tr], v, a);
+        }
+    }
+    return a;
+}
+
+// imgaussfilt of one kBlurW x kBlurH output tile of the rectangle `orc` (tile blockIdx.x, blockIdx.y; 256 threads): haloed tile into
+// LDS with replicate padding at the h x w level's border, column (vertical) pass, then row pass.  ld(x, y) returns an input
+// pixel, st(x, y, v) stores an output pixel: where a layer lives is the caller's business.
+constexpr int kBlurW = 32, kBlurH = 16;
+template <int R, class Ld, class St>
+__device__ __forceinline__ void blur_tile(const Ld& ld, const St& st, const Rect& orc, int h, int w, const Taps& tp) {
+    constexpr int IW = kBlurW + 2 * R, IH = kBlurH + 2 * R;
+    const int x0 = orc.x0 + blockIdx.x * kBlurW, y0 = orc.y0 + blockIdx.y * kBlurH, tid = threadIdx.x;
+    if (x0 >= orc.x1 || y0 >= orc.y1) return;  // the grid is sized for the largest output rect of the launch
+    __shared__ float4 s_in[IH * IW];
+    __shared__ float4 s_v[kBlurH * IW];
+    for (int e = tid; e < IH * IW; e += 256) {
+        const int ly = e / IW, lx = e - ly * IW;
+        const int gy = min(max(y0 + ly - R, 0), h - 1), gx = min(max(x0 + lx - R, 0), w - 1);
+        s_in[e] = ld(gx, gy);
+    }
+    __syncthreads();
+    for (int e = tid; e < kBlurH * IW; e += 256) {  // vertical pass for every column of the haloed tile
+        const int ly = e / IW, lx = e - ly * IW;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_in[(ly + t) * IW + lx], a);
+        s_v[e] = a;
+    }
+    __syncthreads();
+    for (int e = tid; e < kBlurH * kBlurW; e += 256) {  // horizontal pass
+        const int ly = e / kBlurW, lx = e - ly * kBlurW;
+        const int gx = x0 + lx, gy = y0 + ly;
+        if (gx >= orc.x1 || gy >= orc.y1) continue;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t <= 2 * R; ++t) a = fma4(tp.k[t], s_v[ly * IW + lx + t], a);
+        st(gx, gy, a);
+    }
+}
+
+// Level l of multiBandBlending.m:136-144 at pixel (x, y) of the h x w level, for the contributors of `walk` in ascending order:
+//   acc += (G_k - imresize(D_k, size_l)) .* w_k,   D_k = the dh x dw next level,
+// or, with has_d == 0, the coarsest level (:159): acc += G_k .* w_k.  acc carries in whatever the caller accumulated before.
+// The walk offers n candidates; candidate i has the footprint rect(i), its value at (x, y) behind pixel(i) and the next level's
+// loader d(i, xx, yy).  A layer whose footprint does not contain the pixel contributes (0 - u) * 0: skipped; the resize taps
+// are computed when the first contributor needs them.
+template <bool ROWS_FIRST, class Walk>
+__device__ __forceinline__ void lap_accumulate(const Walk& walk, int has_d, int x, int y, int h, int w, int dh, int dw, float acc[3]) {
+    if (!has_d) {
+        for (int i = 0; i < walk.n; ++i) {
+            if (!in_rect(walk.rect(i), x, y)) continue;
+            const float4 g = *walk.pixel(i);
+            acc[0] = acc[0] + g.x * g.w;
+            acc[1] = acc[1] + g.y * g.w;
+            acc[2] = acc[2] + g.z * g.w;
+        }
+        return;
+    }
+    int lr = 0, lc = 0, Pr = 0, Pc = 0;
+    float wr[12], wc[12];
+    bool have_taps = false;
+    for (int i = 0; i < walk.n; ++i) {
+        if (!in_rect(walk.rect(i), x, y)) continue;
+        if (!have_taps) {
+            Pr = resize_taps(dh, h, y, lr, wr);
+            Pc = resize_taps(dw, w, x, lc, wc);
+            have_taps = true;
+        }
+        const float4 u = resize_with<ROWS_FIRST>([&](int xx, int yy) { return walk.d(i, xx, yy); }, dh, dw, Pr, lr, wr, Pc, lc, wc);
+        const float4 g = *walk.pixel(i);
+        acc[0] = acc[0] + (g.x - u.x) * g.w;
+        acc[1] = acc[1] + (g.y - u.y) * g.w;
+        acc[2] = acc[2] + (g.z - u.z) * g.w;
+    }
+}
+
 // ---- host-side helpers shared by both render translation units ------------------------------------
 inline Taps make_taps(float sigma) {
     Taps tp;
@@ -248,6 +352,46 @@ inline Rect map_rect(const Rect& r, int h, int w, int oh, int ow) {
     return o;
 }
 
+// ---- the shape of a multiband pyramid, derived from sizes and footprints alone ---------------------------------------------------
+// Level count (multiBandBlending.m:98-109: at most floor(log2(min(h, w)))) and level sizes (floor halving, at least 1).
+inline void pyramid_levels(int h, int w, int levels, std::vector<int>& lh, std::vector<int>& lw) {
+    const int maxl = (int)std::floor(std::log2((double)std::min(h, w)));
+    const int L = std::max(1, std::min(levels, maxl));
+    lh.assign(L, h);
+    lw.assign(L, w);
+    for (int l = 1; l < L; ++l) {
+        lh[l] = std::max(1, lh[l - 1] / 2);
+        lw[l] = std::max(1, lw[l - 1] / 2);
+    }
+}
+// Footprints per level from the level-0 footprints g0 (clipped to the level): G_l, B_l = blurred G_l (grown by the filter
+// radius), G_(l+1) = B_l mapped through the resize.  An empty footprint stays empty at every level.
+inline void pyramid_footprints(const std::vector<Rect>& g0, int radius, const std::vector<int>& lh, const std::vector<int>& lw,
+                               std::vector<std::vector<Rect>>& gr, std::vector<std::vector<Rect>>& br) {
+    const int L = (int)lh.size();
+    gr.assign(L, g0);
+    br.assign(L, g0);
+    for (int l = 0; l < L; ++l)
+        for (size_t k = 0; k < g0.size(); ++k) {
+            const Rect g = gr[l][k];
+            const bool empty = g.x1 <= g.x0;
+            br[l][k] = empty ? g : clip_rect(Rect{g.x0 - radius, g.y0 - radius, g.x1 + radius, g.y1 + radius}, lw[l], lh[l]);
+            if (l + 1 < L) gr[l + 1][k] = empty ? g : map_rect(br[l][k], lh[l], lw[l], lh[l + 1], lw[l + 1]);
+        }
+}
+// Pixels of levels from..to-1.
+inline int64_t pyramid_px(const std::vector<int>& lh, const std::vector<int>& lw, int from, int to) {
+    int64_t px = 0;
+    for (int l = from; l < to; ++l) px += (int64_t)lh[l] * lw[l];
+    return px;
+}
+// Bytes of what every multiband composite holds beside its layers: F, the numerator pyramid (levels 0..L-1) and the collapse
+// buffers (levels 1..L-2).
+inline int64_t pyramid_result_bytes(const std::vector<int>& lh, const std::vector<int>& lw) {
+    const int L = (int)lh.size();
+    return 16 * (pyramid_px(lh, lw, 0, 1) + pyramid_px(lh, lw, 0, L) + pyramid_px(lh, lw, 1, L - 1));
+}
+
 
 // ---- the batched multiband path (render_batch.hip) ----------------------------------------------------
 struct TileRect {
@@ -277,6 +421,9 @@ struct HWarp {
 void make_hwarp(const double* H, HWarp& hw);
 // (render.hip) multiBandBlending on K float4 layers with normalised weights, optional footprints; result in F (unclamped)
 void multiband_device(const std::vector<float4*>& layers, const Rect* rects, int h, int w, int levels, float sigma, float4* F);
+// (render.hip) the collapse (multiBandBlending.m:163-167): F_l = imresize(F_(l+1), size_l) + Num_l from the coarsest level down;
+// num[l]: the numerator of level l (lh[l] x lw[l]); F_0 is written to F.  One level: the caller's numerator IS F.
+void multiband_collapse(const std::vector<Ws<float4>>& num, const std::vector<int>& lh, const std::vector<int>& lw, float4* F);
 
 constexpr int kGainSlots = 128;  // per-workgroup pair table
 constexpr int kGainMaxCover = 16;

@@ -203,6 +203,46 @@ def test_resident_tensors_in_and_out(rp, blending):
     assert np.array_equal(out.cpu().numpy(), ref)
 
 
+def _pano_and_cover(rp, entry, imgs, Hs, view, o):
+    """One compositor entry point called as planar_composite calls it, with the coverage map asked for as well."""
+    n, keep, pim, ih, iw, ic, Hm = rp._planar_args(imgs, Hs)
+    Hc, Wc, x0, y0, sx, sy = rp._planar_view(view)
+    pano, cov = np.zeros((Hc, Wc, 3), np.uint8), np.zeros((Hc, Wc), np.uint8)
+    rp.check(getattr(rp.lib, entry)(C.addressof(pim), rp.ptr(ih), rp.ptr(iw), rp.ptr(ic), n, rp.ptr(Hm), Hc, Wc, x0, y0, sx, sy,
+                                    rp._BLEND[o["blending"]], int(o["pyrLevels"]), float(o["pyrSigma"]), 0, None, rp.ptr(pano), rp.ptr(cov)))
+    del keep
+    return pano, cov
+
+
+@pytest.mark.parametrize("blending", ["none", "linear", "multiband"])
+@pytest.mark.parametrize("absent,xlim", [(0, (95.5, 205.5)), (2, (-4.5, 100.5))])
+def test_a_view_wholly_outside_the_canvas(rp, ip, blending, absent, xlim):
+    """The canvas cropped so that the first (then the last) of three views has an empty footprint, (0, 0, 0, 0), at every
+    pyramid level, while the other two overlap inside it: dense, compact and host still agree on every byte, and the gain
+    statistics carry zeros for the absent view."""
+    imgs, Hs = _three(np.random.default_rng(41))
+    view = ip.imref2dScratch((80, int(xlim[1] - xlim[0])), xlim, (-10.5, 69.5))
+    rects, whole = rp.planar_footprints([(60, 90)] * 3, Hs, view)
+    assert not whole.any() and [tuple(r) == (0, 0, 0, 0) for r in rects] == [k == absent for k in range(3)]
+    o = {"blending": blending, "pyrLevels": 3, "pyrSigma": 1.0, "canvasColor": "black"}
+    compact, dense = rp.planar_composite_compact(imgs, Hs, view, o), rp.planar_composite(imgs, Hs, view, o)
+    _same(compact, dense, "compact vs dense")
+    _same(compact, rp._planar_host(imgs, Hs, view, o), "compact vs host")
+    cp, cc = _pano_and_cover(rp, "aps_planar_composite_compact", imgs, Hs, view, o)
+    dp, dc = _pano_and_cover(rp, "aps_planar_composite", imgs, Hs, view, o)
+    _same(cp, compact, "compact with coverage vs without")
+    _same(dp, dense, "dense with coverage vs without")
+    _same(cc, dc, "coverage, compact vs dense")
+    assert 0 < cc.mean() < 1 and compact[cc > 0].any()  # the canvas is 20 rows taller than the views: some void, some cover
+    N, sI, sJ = rp.planar_gain_stats_compact(imgs, Hs, view, 2)
+    dN, dI, dJ = rp.planar_gain_stats(imgs, Hs, view, 2)
+    assert np.array_equal(N, dN) and np.allclose(sI, dI, rtol=1e-12, atol=0) and np.allclose(sJ, dJ, rtol=1e-12, atol=0)
+    a, b = [k for k in range(3) if k != absent]
+    assert N[a, b] > 0 and N.sum() == N[a, b]
+    for M in (N, sI, sJ, dN, dI, dJ):
+        assert not M[absent].any() and not M[:, absent].any()
+
+
 # ---- more than 64 views: the oracle chain ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("blending", ["multiband", "linear", "none"])
 @pytest.mark.parametrize("rows,cols", [(10, 10), (20, 13)])
