@@ -79,6 +79,10 @@ class aps_surf_params(C.Structure):
                 ("upright", C.c_int), ("max_features", C.c_int)]
 
 
+class aps_fast_params(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("quality_num", C.c_int), ("quality_den", C.c_int), ("max_features", C.c_int)]
+
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/aps.h one to one
@@ -165,6 +169,9 @@ _SIGNATURES = {
                          _vp, _i64, C.POINTER(_i64)],
     "aps_surf_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
+    "aps_fast_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_params), _vp, _i, _i64, _vp, _i64,
+                         _vp, _i64, C.POINTER(_i64)],
+    "aps_freak_pattern": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
              "aps_planar_composite_compact_bytes": C.c_int64}

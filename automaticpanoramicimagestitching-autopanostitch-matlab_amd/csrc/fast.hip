@@ -1,0 +1,470 @@
+// fast.hip — FAST-9 corners + FREAK 512-bit descriptors on the gfx950.
+// Stands behind PP/featureMatching/getFeaturePoints.m:51-52,71-74 (rgb2gray -> detectFASTFeatures(gray) -> extractFeatures, which
+// describes corner points with FREAK).  The toolbox functions are closed code; the algorithms are FAST-9 of Rosten & Drummond and
+// FREAK of Alahi, Ortiz & Vandergheynst, restated in DESIGN.md "FAST/FREAK contract".  Every stored value and every discrete
+// decision below is integer arithmetic (gray plane, ring differences, box sums, cross-multiplied comparisons, 64-bit moments), so
+// a NumPy restatement (tests/fast_mirror.py) reproduces the outputs bit for bit: no device transcendental, no float summation.
+// The pattern's f64 layout is rounded to integer tables on the host, once (aps_freak_pattern hands them to the tests).
+//
+// Chain of one call (no host read-back until the final count; every grid is a capacity grid):
+//   integral_image        the u8 gray plane, stored once, and the exact 32-bit integral image (integral_dev.h, shared with surf.hip)
+//   fast_detect_kernel    64 x 8 tile of that plane (+4 halo: 3 for the ring, 1 for suppression) into LDS, the FAST-9 score of the tile
+//                         (+1 halo) into LDS, strict 3 x 3 maximum; writes the plane of kept scores (0 = no corner)
+//   maximum of that plane (rocprim, integers) = s_max of the quality gate
+//   fast_gate_kernel      quality gate per pixel; one ballot = one 64-bit word of the candidate bitmap, whose bit order IS the
+//                         canonical feature order (row, col)
+//   exclusive scan of the words' popcounts (rocprim), fast_emit_kernel (ordered compaction, no atomics, no sort)
+//   freak_keypoint_kernel one wave per keypoint: 43 box sums, 45-pair orientation moment, bin, 43 box sums on the bin's table,
+//                         64 lanes x 8 tests = 512 bits; lane = output byte
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "aps_internal.h"
+#include "integral_dev.h"
+
+#include <rocprim/rocprim.hpp>
+
+namespace aps {
+namespace {
+
+constexpr int kTW = 64, kTH = 8;  // detection tile: a wave's row of it is one row of 64 pixels
+constexpr int kHalo = 4;          // ring radius 3 + 1 for the suppression's neighbours
+constexpr int kFields = 43, kBins = 256, kPairs = 512, kOriPairs = 45;
+constexpr double kPatternScale = 22.0;
+
+// ---- the pattern: f64 layout -> integer tables (host, once) ---------------------------------------------------------
+struct FreakHost {
+    int32_t fields[kBins][kFields][3];  // dx, dy, r
+    int32_t pairs[kPairs][2];
+    int32_t ori_pairs[kOriPairs][2];
+    int32_t ori_dir[kOriPairs][2];
+    int32_t cos_sin[kBins][2];
+    int margin;
+};
+// what the keypoint kernel reads
+struct FreakDev {
+    char4 field[kBins][kFields];  // dx, dy, r, 0
+    int area[kFields];            // (2r + 1)^2
+    uchar2 pair[kPairs];
+    uchar2 ori_pair[kOriPairs];
+    short2 ori_dir[kOriPairs];
+    short2 cos_sin[kBins];
+};
+
+inline int32_t round_half_up_f64(double v) { return (int32_t)std::floor(v + 0.5); }
+inline int ring_of(int f) { return f < 42 ? f / 6 : 7; }
+
+const FreakHost& host_pattern() {
+    static const FreakHost t = [] {
+        FreakHost p;
+        std::memset(&p, 0, sizeof p);
+        const double bigR = 2.0 / 3.0, smallR = 2.0 / 24.0, u = (bigR - smallR) / 21.0;
+        const double steps[6] = {0, 6, 11, 15, 18, 20};
+        double radius[8], px0[kFields], py0[kFields];
+        for (int r = 0; r < 6; ++r) radius[r] = bigR - steps[r] * u;
+        radius[6] = smallR;
+        radius[7] = 0.0;
+        // bins 0..63 from the f64 layout; 64..255 are exact quarter turns (dx, dy) -> (-dy, dx) of them
+        for (int k = 0; k < 64; ++k)
+            for (int f = 0; f < kFields; ++f) {
+                const int r = ring_of(f), j = f % 6;
+                const double th = (f < 42 ? (double)j * M_PI / 3.0 + (r & 1) * M_PI / 6.0 : 0.0) + 2.0 * M_PI * (double)k / 256.0;
+                const double x = radius[r] * kPatternScale * std::cos(th), y = radius[r] * kPatternScale * std::sin(th);
+                if (k == 0) {
+                    px0[f] = x;
+                    py0[f] = y;
+                }
+                const double sigma = (f < 42 ? radius[r] : smallR) / 2.0;  // the centre has the innermost ring's size
+                int32_t dx = f < 42 ? round_half_up_f64(x) : 0, dy = f < 42 ? round_half_up_f64(y) : 0;
+                const int32_t hs = round_half_up_f64(sigma * kPatternScale);
+                for (int q = 0; q < 4; ++q) {
+                    p.fields[k + 64 * q][f][0] = dx;
+                    p.fields[k + 64 * q][f][1] = dy;
+                    p.fields[k + 64 * q][f][2] = hs;
+                    const int32_t t2 = dx;
+                    dx = -dy;
+                    dy = t2;
+                }
+            }
+        p.margin = 0;
+        for (int k = 0; k < kBins; ++k)
+            for (int f = 0; f < kFields; ++f)
+                p.margin = std::max(p.margin, std::max(std::abs(p.fields[k][f][0]), std::abs(p.fields[k][f][1])) + p.fields[k][f][2] + 1);
+        // descriptor pairs: all (a, b), a < b, by ascending (ring(a) + ring(b), a, b) - ring 0 is the outermost; the first 512
+        int n = 0;
+        for (int s = 0; s <= 14 && n < kPairs; ++s)
+            for (int a = 0; a < kFields && n < kPairs; ++a)
+                for (int b = a + 1; b < kFields && n < kPairs; ++b)
+                    if (ring_of(a) + ring_of(b) == s) {
+                        p.pairs[n][0] = a;
+                        p.pairs[n][1] = b;
+                        ++n;
+                    }
+        // orientation pairs: all 15 pairs of the six fields of each of the three outer rings
+        n = 0;
+        for (int r = 0; r < 3; ++r)
+            for (int a = 6 * r; a < 6 * r + 6; ++a)
+                for (int b = a + 1; b < 6 * r + 6; ++b) {
+                    p.ori_pairs[n][0] = a;
+                    p.ori_pairs[n][1] = b;
+                    const double ex = px0[a] - px0[b], ey = py0[a] - py0[b], len = std::sqrt(ex * ex + ey * ey);
+                    p.ori_dir[n][0] = round_half_up_f64(1024.0 * ex / len);
+                    p.ori_dir[n][1] = round_half_up_f64(1024.0 * ey / len);
+                    ++n;
+                }
+        for (int k = 0; k < 64; ++k) {
+            int32_t c = round_half_up_f64(16384.0 * std::cos(2.0 * M_PI * (double)k / 256.0));
+            int32_t s = round_half_up_f64(16384.0 * std::sin(2.0 * M_PI * (double)k / 256.0));
+            for (int q = 0; q < 4; ++q) {
+                p.cos_sin[k + 64 * q][0] = c;
+                p.cos_sin[k + 64 * q][1] = s;
+                const int32_t t2 = c;
+                c = -s;
+                s = t2;
+            }
+        }
+        return p;
+    }();
+    return t;
+}
+
+const FreakDev& dev_pattern() {
+    static const FreakDev t = [] {
+        const FreakHost& h = host_pattern();
+        FreakDev d;
+        std::memset(&d, 0, sizeof d);
+        for (int k = 0; k < kBins; ++k) {
+            for (int f = 0; f < kFields; ++f) d.field[k][f] = make_char4((signed char)h.fields[k][f][0], (signed char)h.fields[k][f][1], (signed char)h.fields[k][f][2], 0);
+            d.cos_sin[k] = make_short2((short)h.cos_sin[k][0], (short)h.cos_sin[k][1]);
+        }
+        for (int f = 0; f < kFields; ++f) d.area[f] = (2 * h.fields[0][f][2] + 1) * (2 * h.fields[0][f][2] + 1);
+        for (int i = 0; i < kPairs; ++i) d.pair[i] = make_uchar2((unsigned char)h.pairs[i][0], (unsigned char)h.pairs[i][1]);
+        for (int i = 0; i < kOriPairs; ++i) {
+            d.ori_pair[i] = make_uchar2((unsigned char)h.ori_pairs[i][0], (unsigned char)h.ori_pairs[i][1]);
+            d.ori_dir[i] = make_short2((short)h.ori_dir[i][0], (short)h.ori_dir[i][1]);
+        }
+        return d;
+    }();
+    return t;
+}
+
+// ---- detection --------------------------------------------------------------------------------------------------------
+// the 16-pixel Bresenham circle of radius 3, clockwise from the top (image coordinates: x right, y down)
+// (constexpr: every use has a constant index after unrolling, so the offsets fold into the LDS addresses)
+constexpr int kRingDx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+constexpr int kRingDy[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
+
+__global__ __launch_bounds__(256) void fast_detect_kernel(const uint8_t* __restrict__ gray, int h, int w, int thr, int margin,
+                                                          uint8_t* __restrict__ kept) {
+    __shared__ uint8_t G[kTH + 2 * kHalo][kTW + 2 * kHalo];
+    __shared__ uint8_t S[kTH + 2][kTW + 2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    constexpr int kGW = kTW + 2 * kHalo, kGN = (kTH + 2 * kHalo) * kGW;
+    for (int e = tid; e < kGN; e += 256) {
+        const int r = e / kGW, cc = e % kGW, y = y0 - kHalo + r, x = x0 - kHalo + cc;
+        G[r][cc] = y >= 0 && y < h && x >= 0 && x < w ? gray[(size_t)y * w + x] : (uint8_t)0;
+    }
+    __syncthreads();
+    constexpr int kSW = kTW + 2, kSN = (kTH + 2) * kSW;
+    for (int e = tid; e < kSN; e += 256) {
+        const int r = e / kSW, cc = e % kSW, y = y0 - 1 + r, x = x0 - 1 + cc;
+        int s = 0;
+        // pixels closer than the descriptor's margin to the edge are never corners (margin >= 4: the ring stays inside the image)
+        if (y >= margin && y <= h - 1 - margin && x >= margin && x <= w - 1 - margin) {
+            const int ctr = G[r + 3][cc + 3];
+            int d[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) d[i] = (int)G[r + 3 + kRingDy[i]][cc + 3 + kRingDx[i]] - ctr;
+#pragma unroll
+            for (int a = 0; a < 16; ++a) {
+                int mb = 255, md = 255;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    mb = min(mb, d[(a + j) & 15]);
+                    md = min(md, -d[(a + j) & 15]);
+                }
+                s = max(s, max(mb, md));
+            }
+            if (s <= thr) s = 0;
+        }
+        S[r][cc] = (uint8_t)s;
+    }
+    __syncthreads();
+    for (int rr = wave; rr < kTH; rr += 4) {
+        const int y = y0 + rr, x = x0 + lane;
+        if (y >= h) break;  // (uniform in the wave)
+        const int v = S[rr + 1][lane + 1];
+        bool keep = v > 0;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+                if (!(dy == 1 && dx == 1)) keep = keep && v > (int)S[rr + dy][lane + dx];
+        if (x < w) kept[(size_t)y * w + x] = keep ? (uint8_t)v : (uint8_t)0;
+    }
+}
+
+struct U8ToU32 {
+    __host__ __device__ unsigned int operator()(uint8_t v) const { return v; }
+};
+
+// keep iff s * q_den >= s_max * q_num; one wave per row segment of 64 pixels, its ballot is the bitmap word
+__global__ __launch_bounds__(256) void fast_gate_kernel(const uint8_t* __restrict__ kept, int h, int w, int wpr,
+                                                        const unsigned int* __restrict__ d_smax, unsigned int q_num, unsigned int q_den,
+                                                        unsigned long long* __restrict__ bitmap) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int y = blockIdx.y * 4 + wave, x = blockIdx.x * 64 + lane;
+    if (y >= h) return;  // (uniform in the wave)
+    const unsigned long long smax = *d_smax;
+    const unsigned long long s = x < w ? kept[(size_t)y * w + x] : 0;
+    const unsigned long long mask = __ballot(s > 0 && s * q_den >= smax * q_num);
+    if (lane == 0) bitmap[(size_t)y * wpr + blockIdx.x] = mask;
+}
+
+struct PopcOp {
+    __host__ __device__ unsigned int operator()(unsigned long long v) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (unsigned int)__popcll(v);
+#else
+        return (unsigned int)__builtin_popcountll(v);
+#endif
+    }
+};
+
+// Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (row, col).
+__global__ __launch_bounds__(256) void fast_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
+                                                        long long n_words, int wpr, int2* __restrict__ kps, unsigned int kcap) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_words) return;
+    unsigned long long bits = bitmap[q];
+    if (!bits) return;
+    unsigned int pos = prefix[q];
+    const int y = (int)(q / wpr), xw = (int)(q % wpr) * 64;
+    while (bits) {
+        const int k = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        if (pos < kcap) kps[pos] = make_int2(y, xw + k);
+        ++pos;
+    }
+}
+
+// ---- description ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ long long wave_max(long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const long long o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// One wave per keypoint.  Every wave of the capacity grid passes every barrier; the ones beyond the count do no work.
+__global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __restrict__ I, int w, const FreakDev* __restrict__ tb,
+                                                             const uint8_t* __restrict__ kept, const int2* __restrict__ kps,
+                                                             const unsigned int* __restrict__ d_total, unsigned int kcap,
+                                                             uint8_t* __restrict__ desc, int desc_layout, long long ldd,
+                                                             double* __restrict__ loc, long long ldl, float* __restrict__ aux) {
+    __shared__ int s_S[4][kFields + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned int kidx = blockIdx.x * 4 + wave;
+    const unsigned int total = min(*d_total, kcap);
+    const bool active = kidx < total;
+    const size_t ws = (size_t)w + 1;
+    int2 kp = make_int2(0, 0);
+    if (active) kp = kps[kidx];
+    // the 43 box sums on the table of `bin`, one field per lane (the margin keeps every box inside the image)
+    auto sums = [&](int bin) {
+        if (active && lane < kFields) {
+            const char4 f = tb->field[bin][lane];
+            const int cy = kp.x + f.y, cx = kp.y + f.x, r = f.z;
+            s_S[wave][lane] = (int)box(I, ws, cy - r, cy + r, cx - r, cx + r);
+        }
+    };
+    sums(0);
+    __syncthreads();
+    // ---- orientation: 45 pairs on the bin-0 table, 64-bit moment, the bin that maximises its projection ---------------
+    long long mx = 0, my = 0;
+    if (active && lane < kOriPairs) {
+        const uchar2 p = tb->ori_pair[lane];
+        const short2 dir = tb->ori_dir[lane];
+        const long long D = (long long)s_S[wave][p.x] * tb->area[p.y] - (long long)s_S[wave][p.y] * tb->area[p.x];
+        mx = D * dir.x;
+        my = D * dir.y;
+    }
+    mx = wave_sum(mx);
+    my = wave_sum(my);
+    // lane holds bins 4 * lane .. 4 * lane + 3: the lowest lane among equals holds the lowest bin among equals
+    long long best = 0;
+    int best_k = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const short2 cs = tb->cos_sin[4 * lane + j];
+        const long long v = mx * cs.x + my * cs.y;
+        if (j == 0 || v > best) {
+            best = v;
+            best_k = 4 * lane + j;
+        }
+    }
+    const long long top = wave_max(best);
+    const unsigned long long tie = __ballot(best == top);
+    const int bin = __shfl(best_k, __ffsll((long long)tie) - 1);
+    __syncthreads();  // (the bin-0 sums are read; the slice is written again)
+    sums(bin);
+    __syncthreads();
+    if (!active) return;
+    // ---- descriptor: lane = output byte, bits 8 * lane .. 8 * lane + 7, LSB first ---------------------------------------
+    unsigned int byte = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const uchar2 p = tb->pair[8 * lane + t];
+        const long long a = (long long)s_S[wave][p.x] * tb->area[p.y], b = (long long)s_S[wave][p.y] * tb->area[p.x];
+        byte |= (a > b ? 1u : 0u) << t;
+    }
+    if (desc_layout == APS_ROWMAJOR)
+        desc[(size_t)kidx * ldd + lane] = (uint8_t)byte;
+    else
+        desc[(size_t)lane * ldd + kidx] = (uint8_t)byte;
+    if (lane == 0) {
+        loc[kidx] = (double)(kp.y + 1);
+        loc[(size_t)ldl + kidx] = (double)(kp.x + 1);
+        if (aux) {
+            aux[(size_t)kidx * 4 + 0] = (float)kept[(size_t)kp.x * w + kp.y];
+            aux[(size_t)kidx * 4 + 1] = (float)bin;
+            aux[(size_t)kidx * 4 + 2] = 0.0f;
+            aux[(size_t)kidx * 4 + 3] = 0.0f;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace aps
+
+using namespace aps;
+
+extern "C" {
+
+int aps_freak_pattern(int32_t* fields, int32_t* pairs, int32_t* ori_pairs, int32_t* ori_dir, int32_t* cos_sin, int* margin) {
+    return guarded([&] {
+        const FreakHost& p = host_pattern();
+        if (fields) std::memcpy(fields, p.fields, sizeof p.fields);
+        if (pairs) std::memcpy(pairs, p.pairs, sizeof p.pairs);
+        if (ori_pairs) std::memcpy(ori_pairs, p.ori_pairs, sizeof p.ori_pairs);
+        if (ori_dir) std::memcpy(ori_dir, p.ori_dir, sizeof p.ori_dir);
+        if (cos_sin) std::memcpy(cos_sin, p.cos_sin, sizeof p.cos_sin);
+        if (margin) *margin = p.margin;
+    });
+}
+
+int aps_fast_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                     const aps_fast_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                     double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
+        APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
+        APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
+        APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
+        APS_REQUIRE(params->threshold >= 0 && params->threshold <= 255, APS_E_ARG, "threshold (floor(MinContrast * 255)) must be in 0..255");
+        APS_REQUIRE(params->quality_den > 0 && params->quality_den <= (1 << 24) && params->quality_num >= 0 && params->quality_num <= params->quality_den,
+                    APS_E_ARG, "MinQuality must be a rational in [0, 1] with a denominator of at most 2^24");
+        APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
+        // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
+        APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
+                    "FAST: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
+        ctx();
+        *count = 0;
+        const int H = height, W = width, margin = host_pattern().margin;
+        if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
+        In<uint8_t> dimg(img, (size_t)H * W * channels);
+        Ws<uint32_t> T((size_t)H * W), I((size_t)(H + 1) * (W + 1));
+        Ws<uint8_t> gray((size_t)H * W);
+        {
+            Prof prof("fast_integral");
+            integral_image(dimg, H, W, channels, img_layout, T, I, gray);
+        }
+        const int wpr = (int)cdiv(W, 64);
+        const long long n_words = (long long)H * wpr;
+        Ws<uint8_t> kept((size_t)H * W);
+        Ws<unsigned int> smax(1);
+        Ws<unsigned long long> bitmap((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
+        Ws<unsigned int> prefix((size_t)n_words + 1);
+        APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
+        {
+            Prof prof("fast_detect");
+            fast_detect_kernel<<<dim3(wpr, cdiv(H, kTH)), 256, 0, stream()>>>(gray, H, W, params->threshold, margin, kept);
+            check_launch("fast_detect_kernel");
+            auto scores = rocprim::make_transform_iterator(kept.get(), U8ToU32());
+            size_t rbytes = 0;
+            APS_HIP(rocprim::reduce(nullptr, rbytes, scores, smax.get(), 0u, (size_t)H * W, rocprim::maximum<unsigned int>(), stream()));
+            Ws<char> rtmp(rbytes);
+            APS_HIP(rocprim::reduce(rtmp.get(), rbytes, scores, smax.get(), 0u, (size_t)H * W, rocprim::maximum<unsigned int>(), stream()));
+            fast_gate_kernel<<<dim3(wpr, cdiv(H, 4)), 256, 0, stream()>>>(kept, H, W, wpr, smax, (unsigned int)params->quality_num,
+                                                                        (unsigned int)params->quality_den, bitmap);
+            check_launch("fast_gate_kernel");
+        }
+        {
+            Prof prof("fast_scan");
+            auto counts = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
+            size_t tbytes = 0;
+            APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+            Ws<char> tmp(tbytes);
+            APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+        }
+        const unsigned int* d_total = prefix.get() + n_words;
+        const bool write = cap > 0 && desc && loc;
+        const unsigned int kcap = write ? (unsigned int)cap : 0u;
+        Out<uint8_t> odesc;
+        Out<double> oloc;
+        Out<float> oaux;
+        if (write) {
+            if (desc_layout == APS_ROWMAJOR)
+                APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
+            else
+                APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
+            APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
+            odesc.bind(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
+            oloc.bind(loc, (size_t)ldl + cap);
+            oaux.bind(aux, (size_t)cap * 4);
+            Ws<int2> kps((size_t)kcap);
+            Ws<FreakDev> d_tb(1);
+            {
+                Prof prof("fast_emit");  // (with the upload of the pattern tables)
+                APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
+                fast_emit_kernel<<<cdiv((size_t)n_words, 256), 256, 0, stream()>>>(bitmap, prefix, n_words, wpr, kps, kcap);
+                check_launch("fast_emit_kernel");
+            }
+            {
+                Prof prof("freak_keypoint");
+                freak_keypoint_kernel<<<cdiv(kcap, 4), 256, 0, stream()>>>(I, W, d_tb, kept, kps, d_total, kcap, odesc, desc_layout, (long long)ldd,
+                                                                          oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
+            }
+            check_launch("freak_keypoint_kernel");
+        }
+        unsigned int n = 0;  // the one read-back of the chain
+        APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
+        APS_HIP(hipStreamSynchronize(stream()));
+        *count = n;
+        if (params->max_features > 0 && n > (unsigned int)params->max_features)
+            fail(APS_E_CAP, "FAST found %u features, more than params.max_features = %d", n, params->max_features);
+        if ((int64_t)n > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n);
+        if (n == 0) return;
+        APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
+        if (desc_layout == APS_ROWMAJOR)
+            odesc.commit_2d(64, n, (size_t)ldd);
+        else
+            odesc.commit_2d(n, 64, (size_t)ldd);
+        oloc.commit_2d(n, 2, (size_t)ldl);
+        oaux.commit((size_t)n * 4);
+    });
+}
+
+}  // extern "C"

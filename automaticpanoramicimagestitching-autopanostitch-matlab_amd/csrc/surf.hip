@@ -8,10 +8,8 @@
 // stored value or discrete decision (atan2f only feeds aux's angle_deg).
 //
 // Chain of one call (no host read-back until the final count; every grid is a capacity grid):
-//   surf_rowscan_kernel   gray value per pixel + prefix sums along each row (workgroup per row, carried across 1024-px chunks)
-//   surf_colscan_kernel   column prefix sums inside chunks of 64 rows, in place
-//   surf_colcarry_kernel  adds the totals of the chunks above and writes the (h+1) x (w+1) integral image
-//   surf_detect_kernel    per octave: all levels of a 64 x 8 tile (+1 halo) into LDS, threshold, strict 3x3x3 maximum and the
+//   integral_image        gray plane and the exact 32-bit integral image (integral_dev.h: row scan, column scan, column carry)
+//   surf_detect_kernel   per octave: all levels of a 64 x 8 tile (+1 halo) into LDS, threshold, strict 3x3x3 maximum and the
 //                         refinement's verdict; one ballot = one 64-bit word of the candidate bitmap, whose bit order IS the
 //                         canonical feature order (octave, level, row, col)
 //   exclusive scan of the words' popcounts (rocprim), surf_emit_kernel (ordered compaction, no atomics)
@@ -23,6 +21,7 @@
 #include <cstring>
 
 #include "aps_internal.h"
+#include "integral_dev.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -32,7 +31,6 @@ namespace {
 constexpr int kMaxOct = 12;   // octaves of one call (the reference asks for 8)
 constexpr int kMaxLev = 8;    // scale levels per octave (the reference's default is 4)
 constexpr int kTW = 64, kTH = 8;  // detection tile (samples): a wave's ballot covers one row of it
-constexpr int kColChunk = 64;     // rows per chunk of the column scan
 constexpr int kOriN = 109;        // disc samples of the orientation: integer (di, dj), di^2 + dj^2 < 36
 constexpr int kWin = 64;          // positions of the pi/3 sliding window, 360/64 degrees apart
 
@@ -87,84 +85,6 @@ const SurfTables& host_tables() {
         return s;
     }();
     return t;
-}
-
-__device__ __forceinline__ uint32_t gray_at(const uint8_t* __restrict__ img, int h, int w, int c, int layout, int y, int x) {
-    if (c == 1) return layout == APS_IMG_U8_HWC ? img[(size_t)y * w + x] : img[(size_t)x * h + y];
-    uint8_t ch[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) ch[q] = layout == APS_IMG_U8_HWC ? img[((size_t)y * w + x) * 3 + q] : img[(size_t)q * h * w + (size_t)x * h + y];
-    // rgb2gray's integer plane, exactly as sift.hip's gray_u8_kernel builds it
-    const double d = 0.298936021293775 * ch[0] + 0.587043074451121 * ch[1] + 0.114020904255103 * ch[2];
-    return (uint32_t)(uint8_t)(float)floor(d + 0.5);
-}
-
-// T[y][x] = sum of gray[y][0..x]: one workgroup per row, 4 pixels per thread and pass, the running total carried from pass to pass.
-__global__ __launch_bounds__(256) void surf_rowscan_kernel(const uint8_t* __restrict__ img, int h, int w, int c, int layout,
-                                                           uint32_t* __restrict__ T) {
-    __shared__ uint32_t s_tot[2][4];
-    const int y = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t carry = 0;
-    int it = 0;
-    for (int x0 = 0; x0 < w; x0 += 1024, ++it) {
-        const int xb = x0 + tid * 4;
-        uint32_t g[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] = xb + k < w ? gray_at(img, h, w, c, layout, y, xb + k) : 0u;
-        g[1] += g[0];
-        g[2] += g[1];
-        g[3] += g[2];
-        uint32_t incl = g[3];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_tot[it & 1][wave] = incl;
-        __syncthreads();  // (the slot of pass it is written again in pass it + 2, behind the barrier of pass it + 1)
-        uint32_t base = carry + (incl - g[3]), tot = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t t = s_tot[it & 1][q];
-            if (q < wave) base += t;
-            tot += t;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (xb + k < w) T[(size_t)y * w + xb + k] = base + g[k];
-        carry += tot;
-    }
-}
-
-// Column prefix sums inside each chunk of kColChunk rows, in place.
-__global__ __launch_bounds__(256) void surf_colscan_kernel(uint32_t* __restrict__ T, int h, int w) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= w) return;
-    const int y0 = blockIdx.y * kColChunk, y1 = min(h, y0 + kColChunk);
-    uint32_t acc = 0;
-    for (int y = y0; y < y1; ++y) {
-        acc += T[(size_t)y * w + x];
-        T[(size_t)y * w + x] = acc;
-    }
-}
-
-// I[y+1][x+1] = T[y][x] + the last rows of the chunks above; column 0 of I is written here, row 0 by the caller's memset.
-__global__ __launch_bounds__(256) void surf_colcarry_kernel(const uint32_t* __restrict__ T, int h, int w, uint32_t* __restrict__ I) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= w) return;
-    const int y0 = blockIdx.y * kColChunk, y1 = min(h, y0 + kColChunk);
-    uint32_t carry = 0;
-    for (int k = 0; k < (int)blockIdx.y; ++k) carry += T[(size_t)(k * kColChunk + kColChunk - 1) * w + x];
-    const size_t ws = (size_t)w + 1;
-    for (int y = y0; y < y1; ++y) {
-        I[(size_t)(y + 1) * ws + x + 1] = T[(size_t)y * w + x] + carry;
-        if (x == 0) I[(size_t)(y + 1) * ws] = 0u;
-    }
-}
-
-// Sum of gray over rows r0..r1, columns c0..c1 (inclusive).  Wrapping u32 arithmetic: exact whenever the true value fits.
-__device__ __forceinline__ uint32_t box(const uint32_t* __restrict__ I, size_t ws, int r0, int r1, int c0, int c1) {
-    return I[(size_t)(r1 + 1) * ws + c1 + 1] - I[(size_t)r0 * ws + c1 + 1] - I[(size_t)(r1 + 1) * ws + c0] + I[(size_t)r0 * ws + c0];
 }
 
 // det of the box-filter Hessian at pixel (y, x) for filter side S (0 where the filter leaves the image); *trace = Dxx + Dyy.
@@ -438,7 +358,7 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
         APS_REQUIRE(params->metric_threshold >= 0, APS_E_ARG, "MetricThreshold must be >= 0");
         APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
         // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
-        APS_REQUIRE((uint64_t)height * (uint64_t)width * 255u < ((uint64_t)1 << 32), APS_E_ARG,
+        APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
                     "SURF: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
         ctx();
         *count = 0;
@@ -472,14 +392,7 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
         Ws<uint32_t> T((size_t)H * W), I((size_t)(H + 1) * (W + 1));
         {
             Prof prof("surf_integral");
-            surf_rowscan_kernel<<<H, 256, 0, stream()>>>(dimg, H, W, channels, img_layout, T);
-            check_launch("surf_rowscan_kernel");
-            const dim3 cg(cdiv(W, 256), cdiv(H, kColChunk));
-            surf_colscan_kernel<<<cg, 256, 0, stream()>>>(T, H, W);
-            check_launch("surf_colscan_kernel");
-            APS_HIP(hipMemsetAsync(I, 0, ((size_t)W + 1) * sizeof(uint32_t), stream()));
-            surf_colcarry_kernel<<<cg, 256, 0, stream()>>>(T, H, W, I);
-            check_launch("surf_colcarry_kernel");
+            integral_image(dimg, H, W, channels, img_layout, T, I, nullptr);
         }
         Ws<unsigned long long> bitmap((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
         Ws<unsigned int> prefix((size_t)n_words + 1);

@@ -169,15 +169,20 @@ def nearest2ApproxFloatFast(A, B, opts=None, return_basis=False):
     return out + ((mu, coeff),) if return_basis else out
 
 
-def filter_matches(idx2, dBest, dSecond, n2, MaxRatio, MatchThreshold, Unique):
-    """matchFeaturesScratch.m:170-211 on the host (used by the approximate back ends, whose 2-NN lists live on
-    the host): ratio on SSD (r^2), threshold, finiteness, greedy one-to-one by ascending distance (stable)."""
+def filter_matches(idx2, dBest, dSecond, n2, MaxRatio, MatchThreshold, Unique, binary=False):
+    """matchFeaturesScratch.m:170-211 on the host (used by the approximate back ends and the binary branch, whose 2-NN
+    lists live on the host): ratio on SSD (r^2), threshold, finiteness, greedy one-to-one by ascending distance (stable).
+    binary=True: the distances are percent mismatched bits and the ratio is linear (:171), evaluated in single as MATLAB
+    evaluates double scalar * single array."""
     dBest = np.asarray(dBest, np.float32)
     dSecond = np.asarray(dSecond, np.float32)
-    # the reference holds dBest/dSecond in double arrays (inf(N1,1), :344) and evaluates MaxRatio^2 in double
-    r2 = float(MaxRatio) * float(MaxRatio)
-    b64, s64 = dBest.astype(np.float64), dSecond.astype(np.float64)
-    keep = (b64 <= r2 * s64) & (b64 <= float(MatchThreshold)) & np.isfinite(b64) & np.isfinite(s64)
+    if binary:
+        keep = (dBest <= np.float32(MaxRatio) * dSecond) & (dBest <= np.float32(MatchThreshold)) & np.isfinite(dBest) & np.isfinite(dSecond)
+    else:
+        # the reference holds dBest/dSecond in double arrays (inf(N1,1), :344) and evaluates MaxRatio^2 in double
+        r2 = float(MaxRatio) * float(MaxRatio)
+        b64, s64 = dBest.astype(np.float64), dSecond.astype(np.float64)
+        keep = (b64 <= r2 * s64) & (b64 <= float(MatchThreshold)) & np.isfinite(b64) & np.isfinite(s64)
     i1 = np.flatnonzero(keep).astype(np.uint32) + 1
     i2 = np.asarray(idx2, np.uint32)[keep]
     d = dBest[keep]
@@ -194,11 +199,95 @@ def filter_matches(idx2, dBest, dSecond, n2, MaxRatio, MatchThreshold, Unique):
     return np.stack([i1, i2], axis=1), d.astype(np.float32)
 
 
+class binaryFeatures:
+    """Stand-in for MATLAB's binaryFeatures object: .Features is uint8 n x nbytes (packed bits; numpy, or a resident torch
+    tensor), .NumFeatures = n, .NumBits = 8 * nbytes."""
+
+    def __init__(self, Features):
+        if _capi.is_torch(Features):
+            import torch
+
+            if Features.dtype != torch.uint8 or Features.dim() != 2:
+                raise TypeError("binaryFeatures takes a 2-D uint8 matrix")
+            self.Features = Features.contiguous()
+        else:
+            F = np.asarray(Features)
+            if F.dtype != np.uint8 or F.ndim != 2:
+                raise TypeError("binaryFeatures takes a 2-D uint8 matrix")
+            self.Features = np.ascontiguousarray(F)
+
+    @property
+    def NumFeatures(self):
+        return int(self.Features.shape[0])
+
+    @property
+    def NumBits(self):
+        return 8 * int(self.Features.shape[1])
+
+    def __len__(self):
+        return self.NumFeatures
+
+
+def packBits(unpacked01):
+    """[packed, nBits] = packBits(unpacked01) (matchFeaturesScratch.m:618-645): n x D bits -> n x ceil(D / 8) uint8,
+    bit b of a row (1-based) into byte ceil(b / 8), MSB first."""
+    U = np.asarray(unpacked01)
+    if U.ndim != 2 or U.dtype not in (np.bool_, np.uint8):
+        raise TypeError("packBits takes a 2-D logical or uint8 matrix")
+    return np.packbits(U.astype(bool), axis=1, bitorder="big"), int(U.shape[1])
+
+
+def _binary_inputs(F1, F2):
+    """normalizeInputs' binary cases (matchFeaturesScratch.m:259-275): (A bytes, B bytes, nBits), or None for the float
+    path.  Deviation from :266-268: a plain uint8 matrix is NOT inspected for holding only 0 / 1 - it keeps the float path it
+    always had here; unpacked bits are given as bool arrays."""
+    if isinstance(F1, binaryFeatures) and isinstance(F2, binaryFeatures):
+        return F1.Features, F2.Features, F1.NumBits
+    if isinstance(F1, binaryFeatures) or isinstance(F2, binaryFeatures):
+        raise TypeError("both sets must be binaryFeatures")
+    if isinstance(F1, np.ndarray) and isinstance(F2, np.ndarray) and F1.dtype == np.bool_ and F2.dtype == np.bool_:
+        A, nBits = packBits(F1)
+        B, _ = packBits(F2)
+        return A, B, nBits
+    return None
+
+
+def _hamming_2nn(A, B):
+    """aps_hamming_2nn on packed rows that live on the host (numpy) or on the device (torch): (idx2, d1, d2) on the host."""
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("Byte width mismatch.")  # hamm2nn:cols
+    n1 = int(A.shape[0])
+    idx2 = np.zeros(n1, np.uint32)
+    d1 = np.zeros(n1, np.float32)
+    d2 = np.zeros(n1, np.float32)
+    check(lib.aps_hamming_2nn(ptr(A), n1, A.shape[1], ptr(B), int(B.shape[0]), B.shape[1], A.shape[1],
+                              _capi.APS_ROWMAJOR, ptr(idx2), ptr(d1), ptr(d2)))
+    return idx2, d1, d2
+
+
+def _match_binary(A, B, nBits, MaxRatio, MatchThreshold, Unique):
+    """The binary branch of matchFeaturesScratch.m:84-88,118-121,170-211 on packed bytes."""
+    n1, n2 = int(A.shape[0]), int(B.shape[0])
+    if n1 == 0 or n2 == 0:  # :84-88
+        return np.zeros((0, 2), np.uint32), np.zeros(0, np.float32)
+    idx2, d1, d2 = _hamming_2nn(A, B)
+    d2[~np.isfinite(d2) | (d2 == 0)] = np.float32(nBits)  # :318
+    nb = np.float32(nBits)
+    return filter_matches(idx2, (d1 / nb) * np.float32(100), (d2 / nb) * np.float32(100), n2, MaxRatio, MatchThreshold, Unique, binary=True)
+
+
 def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRatio=0.6, Unique=True,
                          ApproxFloatNNMethod="pca2nn", ApproxKDBucketSize=40, candB=None, seed=0, ZeroPad=False,
                          **_ignored_approx_args):
     """[matches, matchMetric] = matchFeaturesScratch(F1, F2, 'Method', ..., 'MatchThreshold', ...,
-    'MaxRatio', ..., 'Unique', ...) for float descriptors (matchFeaturesScratch.m:1-215).
+    'MaxRatio', ..., 'Unique', ...) (matchFeaturesScratch.m:1-215).
+
+    Binary branch (:81-135,170-171): a pair of binaryFeatures, or a pair of bool arrays (unpacked bits, packed by packBits),
+    is searched by the device Hamming 2-NN (aps_hamming_2nn; an empty side gives empty results, :84-88); distances are
+    percent mismatched bits, the ratio is linear, MatchThreshold is in percent (:32 suggests 10 or more).  'Approximate' runs
+    the same exact search: the reference's LSH function itself calls the exhaustive mex (:611).  Deviation from :266-268:
+    plain uint8 arrays are not inspected for 0 / 1 content and keep the float path.
+    Float descriptors:
 
     'Exhaustive' (the north-star path): 2-NN + ratio/threshold/uniqueness fused on the device.
     'Approximate' float back ends (:142-160), selected by ApproxFloatNNMethod: 'pca2nn' (PCA-48 + cosine),
@@ -212,6 +301,9 @@ def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRat
         raise ValueError(f"Unknown Method: {Method}")
     if not (0 < MaxRatio <= 1) or MatchThreshold < 0:
         raise ValueError("invalid MaxRatio/MatchThreshold")
+    packed = _binary_inputs(F1, F2)
+    if packed is not None:
+        return _match_binary(*packed, MaxRatio, MatchThreshold, Unique)
     if method == "approximate":
         An, Bn = _normalize_like_reference(F1, F2)
         if An.shape[0] == 0 or Bn.shape[0] == 0:
@@ -372,6 +464,21 @@ def pair_order_array(numImg):
     return _PAIR_ORDER_ARR[numImg]
 
 
+def match_pairwise_binary_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True):
+    """match_pairwise_csr for lists of binaryFeatures: every pair of pair_order through matchFeaturesScratch's binary branch.
+    Returns (pair_ptr int64[P+1], idx_i, idx_j uint32 1-based, metric float32 percent) on the host."""
+    n = len(allDescriptors)
+    pair_ptr, ii, jj, met = [0], [], [], []
+    for (i, j) in pair_order(n):
+        m, d = matchFeaturesScratch(allDescriptors[i], allDescriptors[j], MatchThreshold=MatchThreshold, MaxRatio=MaxRatio, Unique=Unique)
+        ii.append(m[:, 0])
+        jj.append(m[:, 1])
+        met.append(d)
+        pair_ptr.append(pair_ptr[-1] + len(m))
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
+    return np.asarray(pair_ptr, np.int64), cat(ii, np.uint32), cat(jj, np.uint32), cat(met, np.float32)
+
+
 def featureMatchingPairwise(input, allDescriptors, numImg):
     """matches = featureMatchingPairwise(input, allDescriptors, numImg) (featureMatchingPairwise.m:1-63).
 
@@ -387,6 +494,13 @@ def featureMatchingPairwise(input, allDescriptors, numImg):
         raise NotImplementedError("input.useMATLABFeatureMatch = 1 selects the Computer Vision Toolbox's matchFeatures; "
                                   "set it to 0 for the device matcher (the MATLAB overlay forwards this switch to the reference)")
     matches = [[None] * numImg for _ in range(numImg)]
+    if any(isinstance(d, binaryFeatures) for d in allDescriptors):
+        # binary sets: pair by pair through matchFeaturesScratch's binary branch, the reference's own loop (:48-63)
+        pair_ptr, ii, jj, _ = match_pairwise_binary_csr(allDescriptors, ratio, thr, True)
+        for p, (i, j) in enumerate(pair_order(numImg)):
+            s, e = pair_ptr[p], pair_ptr[p + 1]
+            matches[i][j] = np.stack([ii[s:e], jj[s:e]], axis=1).astype(np.float64)
+        return matches
     if str(input.get("Matchingmethod", "Exhaustive")).lower() == "approximate":
         # getMatches :108-117 with Method = 'Approximate': pair by pair through matchFeaturesScratch, as the reference's parfor
         # (:48-63) does; 'pca2nn' = nearest2ApproxFloatFast on the device, 'kdtree' / 'subsetpdist2' the exact device search
@@ -568,9 +682,80 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
     return d, pts
 
 
+FREAK_BYTES = 64
+
+
+def _fast_params(input):
+    p = _capi.aps_fast_params()
+    p.threshold = int(np.floor(float(input.get("MinContrast", 0.2)) * 255))  # detectFASTFeatures: MinContrast 0.2
+    p.quality_num, p.quality_den = int(round(float(input.get("MinQuality", 0.1)) * 1000000)), 1000000
+    p.max_features = int(input.get("maxFeatures", 0))
+    return p
+
+
+def fast_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
+    """aps_fast_extract with automatic capacity: returns (binaryFeatures, validPts[, aux]); the arguments are sift_extract's.
+    Features are n x 64 uint8 (FREAK, 512 bits), on the host or, with device_out, resident; validPts n x 2 [x y] 1-based,
+    integer-valued; aux n x 4 [FAST score, orientation bin, 0, 0].  input.MinContrast (0.2) and input.MinQuality (0.1) are
+    detectFASTFeatures' parameters."""
+    if _capi.is_torch(image):
+        img = image.contiguous()
+        h, w = int(img.shape[0]), int(img.shape[1])
+        c = 1 if img.dim() == 2 else int(img.shape[2])
+    else:
+        img = np.ascontiguousarray(image, np.uint8)
+        h, w = img.shape[:2]
+        c = 1 if img.ndim == 2 else img.shape[2]
+    if c not in (1, 3):
+        raise ValueError("image must be gray or RGB")
+    prm = _fast_params(input)
+    cap = max(4096, (h * w) // 64)
+    cnt = C.c_int64(0)
+    while True:
+        if device_out:
+            import torch
+
+            desc = torch.empty((cap, FREAK_BYTES), dtype=torch.uint8, device="cuda")
+            _fence_fresh_blocks()
+        else:
+            desc = np.zeros((cap, FREAK_BYTES), np.uint8)
+        if device_out and points_device:
+            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda")
+            _fence_fresh_blocks()
+        else:
+            loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
+        aux = np.zeros((cap, 4), np.float32) if want_aux else None
+        rc = lib.aps_fast_extract(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
+                                  _capi.APS_ROWMAJOR, FREAK_BYTES, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
+        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < prm.max_features < cnt.value):
+            cap = int(cnt.value)
+            continue
+        check(rc)
+        break
+    n = cnt.value
+    if device_out and points_device:
+        pts = loc[:, :n].t().contiguous()
+        torch.cuda.current_stream().synchronize()  # the (small) transpose ran on torch's stream; consumers run on the library's
+    else:
+        pts = np.ascontiguousarray(loc[:, :n].T)
+    if device_out and compact:
+        d = desc[:n].clone()                        # (the call returned after its last kernel: it reads the count back)
+        torch.cuda.current_stream().synchronize()
+    elif device_out:
+        d = desc[:n]
+    else:
+        d = np.ascontiguousarray(desc[:n])
+    f = binaryFeatures(d)
+    if want_aux:
+        return f, pts, aux[:n].copy()
+    return f, pts
+
+
 def extract_features(input, image, **kw):
-    """sift_extract or surf_extract, as input.detector says (the dispatch of the pipeline's extraction stages)."""
+    """sift_extract, surf_extract or fast_extract, as input.detector says (the dispatch of the pipeline's extraction stages)."""
     det = input.get("detector", "SIFT")
+    if det == "FAST":
+        return fast_extract(input, image, **kw)
     if det == "SURF":
         return surf_extract(input, image, padded=bool(kw.get("device_out")), **kw)
     if det == "SIFT":
@@ -580,15 +765,17 @@ def extract_features(input, image, **kw):
 
 def getFeaturePoints(input, ImageOriginal):
     """[features, validPts] = getFeaturePoints(input, ImageOriginal) (getFeaturePoints.m:1-76) for
-    input.detector == 'SIFT' (features Kf x 128 single, unit norm) and 'SURF' (Kf x 64 single, unit norm; :54-55);
-    validPts Kf x 2 double [x y] 1-based.
+    input.detector == 'SIFT' (features Kf x 128 single, unit norm), 'SURF' (Kf x 64 single, unit norm; :54-55) and 'FAST'
+    (binaryFeatures, Kf x 64 uint8 FREAK; :51-52); validPts Kf x 2 double [x y] 1-based.
     The other detectors of the switch (:33-68) are toolbox calls with no device counterpart here."""
     det = input.get("detector", "SIFT")
     if det == "SURF":
         return surf_extract(input, ImageOriginal)
+    if det == "FAST":
+        return fast_extract(input, ImageOriginal)
     if det != "SIFT":
-        if det in ("vl_SIFT", "HARRIS", "FAST", "BRISK", "ORB", "KAZE"):
-            raise NotImplementedError(f"detector '{det}' is a MATLAB toolbox/VLFeat call; only 'SIFT' and 'SURF' run on the device")
+        if det in ("vl_SIFT", "HARRIS", "BRISK", "ORB", "KAZE"):
+            raise NotImplementedError(f"detector '{det}' is a MATLAB toolbox/VLFeat call; only 'SIFT', 'SURF' and 'FAST' run on the device")
         raise ValueError("Need a valid input!")  # getFeaturePoints.m:67
     return sift_extract(input, ImageOriginal)
 
@@ -707,6 +894,35 @@ def match_global_csr(allDescriptors, ratio=0.6, k=4, device_out=False):
     return pair_ptr, oi[:n], oj[:n]
 
 
+def match_global_binary_csr(allDescriptors, ratio=0.6, k=4, method="flann"):
+    """The isBinary branch of featureMatchingGlobal.m:54-161 in CSR form: the sets' bytes pooled (:70-74, 85), exact Hamming
+    k-NN of the pool against itself through flann_knn_win ('bf' or 'flann' as input.BFMatch says: one exact device search
+    serves both, :110-118), then the per-query filter of :123-161 (aps_global_filter) on the Hamming distances.
+    Returns (pair_ptr, idx_i, idx_j) as match_global_csr does, on the host.  Every set has to be binaryFeatures: a list that
+    mixes them with float matrices raises TypeError, as the pairwise branch does."""
+    numImg = len(allDescriptors)
+    if not all(isinstance(d, binaryFeatures) for d in allDescriptors):
+        raise TypeError("all sets must be binaryFeatures")
+    sets = [np.asarray(d.Features.cpu() if _capi.is_torch(d.Features) else d.Features, np.uint8) for d in allDescriptors]
+    counts = [int(f.shape[0]) for f in sets]
+    F = sum(counts)
+    pair_ptr = np.zeros(numImg * (numImg - 1) // 2 + 1, np.int64)
+    if F == 0:
+        z = np.zeros(0, np.uint32)
+        return pair_ptr, z, z.copy()
+    pool = np.ascontiguousarray(np.concatenate([f for f in sets if f.shape[0]]))
+    nn_idx, nn_dist = flann_knn_win(pool, pool, k, method)
+    img_idx = np.repeat(np.arange(1, numImg + 1, dtype=np.uint32), counts)
+    local_idx = np.concatenate([np.arange(1, c + 1, dtype=np.uint32) for c in counts])
+    oi = np.zeros(F, np.uint32)
+    oj = np.zeros(F, np.uint32)
+    cnt = C.c_int64(0)
+    check(lib.aps_global_filter(ptr(nn_idx), ptr(nn_dist), F, k, k, _capi.APS_ROWMAJOR, ptr(img_idx), ptr(local_idx),
+                                numImg, float(ratio), ptr(pair_ptr), ptr(oi), ptr(oj), F, C.byref(cnt)))
+    n = cnt.value
+    return pair_ptr, oi[:n], oj[:n]
+
+
 def featureMatchingGlobal(input, allDescriptors, numImg):
     """matches = featureMatchingGlobal(input, allDescriptors, numImg) (featureMatchingGlobal.m:1-161): pool all
     descriptors, L2-normalise (:80-86), exact kNN (k = input.k) of the pool against itself, per-query filter
@@ -717,7 +933,11 @@ def featureMatchingGlobal(input, allDescriptors, numImg):
     F = sum(counts)
     if F == 0:
         return matches
-    pair_ptr, oi, oj = match_global_csr(allDescriptors, float(input.get("Ratiothreshold", 0.6)), int(input.get("k", 4)))
+    if any(isinstance(d, binaryFeatures) for d in allDescriptors):  # :54-56
+        pair_ptr, oi, oj = match_global_binary_csr(allDescriptors, float(input.get("Ratiothreshold", 0.6)), int(input.get("k", 4)),
+                                                   "bf" if input.get("BFMatch") else "flann")
+    else:
+        pair_ptr, oi, oj = match_global_csr(allDescriptors, float(input.get("Ratiothreshold", 0.6)), int(input.get("k", 4)))
     for p, (i, j) in enumerate(pair_order(numImg)):
         s, e = pair_ptr[p], pair_ptr[p + 1]
         if e > s:

@@ -699,6 +699,9 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
     from . import pipeline as pl
     from . import renderPanorama as rp
 
+    if input.get("detector", "SIFT") == "FAST":
+        # the descriptor all-gather and the sharded matchers are built for 128-wide float rows
+        raise NotImplementedError("stitch_distributed does not take binary descriptors (detector = 'FAST'); use pipeline.stitch")
     ws, rank = world()
     dev = next(iter(local_images.values())).device if local_images else torch.device("cuda", torch.cuda.current_device())
     times = pl.StageTimes()

@@ -66,7 +66,7 @@ SIFT_WORKERS_DEFAULT = 10
 
 def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
     """getFeaturePoints for many images — the reference runs this loop as a parfor (loadImages.m:82-99).
-    input.detector selects SIFT or SURF (fm.extract_features); the name is kept, it is public.
+    input.detector selects SIFT, SURF or FAST (fm.extract_features); the name is kept, it is public.
     Here a few host threads each drive their own HIP stream (the C ABI is thread-safe with per-thread streams
     and workspaces), so the small-octave launches and the count read-backs of one image overlap with the
     large-octave kernels of another.  Results are returned in input order and are independent of the
@@ -191,7 +191,10 @@ def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None):
     Returns dict(pairs=[(i,j)], models=[3x3 j->i], inliers=[K x 2 index arrays], numMatches n x n)."""
     n = len(descs)
     t0 = time.perf_counter()
-    pair_ptr, ii, jj, _ = fm.match_pairwise_csr(descs, input["Ratiothreshold"], input["Matchingthreshold"], True)
+    if any(isinstance(d, fm.binaryFeatures) for d in descs):  # detector = 'FAST': the per-pair Hamming branch, same CSR
+        pair_ptr, ii, jj, _ = fm.match_pairwise_binary_csr(descs, input["Ratiothreshold"], input["Matchingthreshold"], True)
+    else:
+        pair_ptr, ii, jj, _ = fm.match_pairwise_csr(descs, input["Ratiothreshold"], input["Matchingthreshold"], True)
     order = fm.pair_order(n)
     if times is not None:
         times.add("matching", t0)

@@ -708,6 +708,46 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
 /* ============================================================================================
+ * (4c) FAST + FREAK — PP/featureMatching/getFeaturePoints.m:51-52,71-74
+ * ============================================================================================ */
+
+typedef struct aps_fast_params {
+    int threshold;             /* t = floor(MinContrast * 255), evaluated by the caller (detectFASTFeatures: MinContrast 0.2 -> 51) */
+    int quality_num;           /* MinQuality as the rational quality_num / quality_den (0.1 -> 100000 / 1000000) */
+    int quality_den;
+    int max_features;          /* capacity guard; 0 = none beyond cap */
+} aps_fast_params;
+
+/* [features, validPts] = getFeaturePoints(input, img) for detector 'FAST' (getFeaturePoints.m:51-52,71-74): rgb2gray,
+ * detectFASTFeatures(gray), extractFeatures - which describes corner points with FREAK: 512 bits in 64 bytes, the binary
+ * family of inputs.m:31-33 that matchFeaturesScratch.m:81-135,170-171 and featureMatchingGlobal.m:54-120 take as
+ * binaryFeatures.  Both toolbox calls are closed code; the algorithms restated are FAST-9 (Rosten & Drummond) and FREAK
+ * (Alahi, Ortiz & Vandergheynst) - see DESIGN.md "FAST/FREAK contract", which fixes every operation in integer arithmetic
+ * (parity with MATLAB is unpinned).
+ *   desc : u8 count x 64, `desc_layout` with leading dimension ldd >= 64 (row-major) / >= cap (column-major); bit i of a
+ *          descriptor is bit (i % 8), LSB first, of byte i / 8
+ *   loc  : f64 count x 2 [x y], 1-based, integer-valued, column-major with leading dimension ldl >= cap
+ *   aux  : f32 count x 4 row-major [metric = FAST score, orientation bin 0..255, 0, 0] or NULL
+ * cap = rows available in desc/loc/aux; *count = features found (APS_E_CAP if cap is too small; desc = NULL or cap = 0 counts).
+ * Elements outside the logical result (padding of ldd / ldl, rows count..cap) are not written.
+ * Images with height * width * 255 >= 2^32 are refused with APS_E_ARG (the integral image holds exact 32-bit sums).
+ * Host and device pointers are accepted; the call runs on the calling thread's library stream.
+ * Feature order is canonical: ascending (row, col). */
+int aps_fast_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                     const aps_fast_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                     double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* The integer FREAK tables the extractor uses (tests restate the contract on them; needs no device).  Every pointer may be
+ * NULL.  All arrays are host int32, row-major:
+ *   fields    [256][43][3]  per orientation bin and receptive field: centre offset dx, dy (pixels) and box half-side r
+ *   pairs     [512][2]      the descriptor's field pairs (a, b): bit i = mean(a) > mean(b)
+ *   ori_pairs [45][2]       the orientation's field pairs
+ *   ori_dir   [45][2]       their unit directions (ux, uy) scaled by 2^10
+ *   cos_sin   [256][2]      (c_k, s_k) = round(2^14 * cos / sin(2 pi k / 256))
+ *   margin                  largest max(|dx|, |dy|) + r + 1 of `fields`: pixels closer than this to the edge are never corners */
+int aps_freak_pattern(int32_t* fields, int32_t* pairs, int32_t* ori_pairs, int32_t* ori_dir, int32_t* cos_sin, int* margin);
+
+/* ============================================================================================
  * Bench / test support — NOT part of the reference boundary
  * ============================================================================================ */
 /* One uint8 H x W x 3 (row-major interleaved) view of the seeded procedural world used by bench.py and the
