@@ -47,6 +47,10 @@ class aps_match_opts(C.Structure):
                 ("normalize", C.c_int)]
 
 
+class aps_hamming_match_opts(C.Structure):
+    _fields_ = [("max_ratio", C.c_double), ("match_threshold", C.c_double), ("unique", C.c_int), ("nbits", C.c_int)]
+
+
 class aps_ransac_opts(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("confidence", C.c_double), ("max_iter", C.c_int),
                 ("tform_type", C.c_int), ("method", C.c_int)]
@@ -118,6 +122,10 @@ _SIGNATURES = {
     "aps_global_filter": [_vp, _vp, _i64, _i, _i64, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _i64,
                           C.POINTER(_i64)],
     "aps_hamming_2nn": [_vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp],
+    "aps_hamming_match_pairs": [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _i, _vp, _vp, _i64,
+                                C.POINTER(aps_hamming_match_opts), _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)],
+    "aps_hamming_match_pairwise": [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _i,
+                                   C.POINTER(aps_hamming_match_opts), _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)],
     "aps_ransac_score": [_vp, _i, _vp, _vp, _i64, _i64, _d, _i, _vp, _vp, _vp],
     "aps_ransac_homography": [_vp, _vp, _i64, _i64, _vp, _i, C.POINTER(aps_ransac_opts), _vp, _vp,
                               C.POINTER(_i), C.POINTER(_i)],

@@ -216,6 +216,17 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
 struct GlobalPrep* global_prep_new();
 void global_prep_free(struct GlobalPrep* p);
 
+// set bits of a 64-bit ballot word, as a rocprim transform (surf.hip, fast.hip, hamming_pairs.hip: the scans behind their ordered compactions)
+struct PopcOp {
+    __host__ __device__ unsigned int operator()(unsigned long long v) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (unsigned int)__popcll(v);
+#else
+        return (unsigned int)__builtin_popcountll(v);
+#endif
+    }
+};
+
 inline unsigned cdiv(size_t a, size_t b) { return static_cast<unsigned>((a + b - 1) / b); }
 
 // compile-time loop: the body receives std::integral_constant<int, I>, so register arrays are indexed by constants

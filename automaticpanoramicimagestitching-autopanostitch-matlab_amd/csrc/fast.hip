@@ -225,16 +225,6 @@ __global__ __launch_bounds__(256) void fast_gate_kernel(const uint8_t* __restric
     if (lane == 0) bitmap[(size_t)y * wpr + blockIdx.x] = mask;
 }
 
-struct PopcOp {
-    __host__ __device__ unsigned int operator()(unsigned long long v) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return (unsigned int)__popcll(v);
-#else
-        return (unsigned int)__builtin_popcountll(v);
-#endif
-    }
-};
-
 // Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (row, col).
 __global__ __launch_bounds__(256) void fast_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
                                                         long long n_words, int wpr, int2* __restrict__ kps, unsigned int kcap) {

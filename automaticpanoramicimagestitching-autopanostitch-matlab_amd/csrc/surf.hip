@@ -168,16 +168,6 @@ __global__ __launch_bounds__(256) void surf_detect_kernel(const uint32_t* __rest
     }
 }
 
-struct PopcOp {
-    __host__ __device__ unsigned int operator()(unsigned long long v) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return (unsigned int)__popcll(v);
-#else
-        return (unsigned int)__builtin_popcountll(v);
-#endif
-    }
-};
-
 // Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (octave, level, row, col).
 __global__ __launch_bounds__(256) void surf_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
                                                         long long n_words, SurfPlan plan, int4* __restrict__ kps, unsigned int kcap) {

@@ -464,19 +464,106 @@ def pair_order_array(numImg):
     return _PAIR_ORDER_ARR[numImg]
 
 
-def match_pairwise_binary_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True):
-    """match_pairwise_csr for lists of binaryFeatures: every pair of pair_order through matchFeaturesScratch's binary branch.
-    Returns (pair_ptr int64[P+1], idx_i, idx_j uint32 1-based, metric float32 percent) on the host."""
+def _hamming_opts(MaxRatio, MatchThreshold, Unique, nbits=0):
+    o = _capi.aps_hamming_match_opts()
+    o.max_ratio = float(MaxRatio)
+    o.match_threshold = float(MatchThreshold)
+    o.unique = 1 if Unique else 0
+    o.nbits = int(nbits)
+    return o
+
+
+def _binary_sets(allDescriptors):
+    """The sets of a binary list as (byte matrices, bit widths): all binaryFeatures, or all bool arrays (unpacked bits, packed
+    by packBits); anything else mixed in raises, as the per-pair branch does."""
+    if all(isinstance(d, binaryFeatures) for d in allDescriptors):
+        return [d.Features for d in allDescriptors], [d.NumBits for d in allDescriptors]
+    if any(isinstance(d, binaryFeatures) for d in allDescriptors):
+        raise TypeError("both sets must be binaryFeatures")
+    if not all(isinstance(d, np.ndarray) and d.dtype == np.bool_ and d.ndim == 2 for d in allDescriptors):
+        raise TypeError("binary sets are binaryFeatures, or bool arrays of unpacked bits")
+    return [packBits(d)[0] for d in allDescriptors], [int(d.shape[1]) for d in allDescriptors]
+
+
+def match_pairs_binary_csr(allDescriptors, pairs, MaxRatio, MatchThreshold, Unique=True, device_out=False, max_columns=None):
+    """aps_hamming_match_pairs: matchFeaturesScratch's binary branch on an explicit list of (a, b) image pairs (0-based; rows of
+    a searched in b) in one batched device call - the lists of matchFeaturesScratch(allDescriptors[a], allDescriptors[b], ...)
+    pair after pair, element for element.  pairs = None: every pair of pair_order (aps_hamming_match_pairwise).
+    allDescriptors: binaryFeatures (host or resident), or bool arrays of unpacked bits.  Returns (pair_ptr int64[P+1], idx_a,
+    idx_b uint32 1-based, metric float32 percent) as numpy arrays; with device_out=True the three lists are resident torch
+    tensors (int32, int32, float32; empty ones when nothing matches or no pair has two non-empty sides), and resident sets never
+    leave the device.  pair_ptr is a numpy array either way, as match_pairs_csr's: P + 1 offsets the host indexes the lists with.
+    The sets that meet in a pair with two non-empty sides share one byte and bit width (ValueError otherwise; one call has
+    one width); sets that meet only empty partners may be of any width.
+    max_columns: bound on the per-column workspace of the uniqueness step (columns of the pairs in flight; the pair list is
+    walked in chunks under it, same results) - for tests of the chunked walk and hosts short of device memory."""
+    if not (0 < MaxRatio <= 1) or MatchThreshold < 0:
+        raise ValueError("invalid MaxRatio/MatchThreshold")
     n = len(allDescriptors)
-    pair_ptr, ii, jj, met = [0], [], [], []
-    for (i, j) in pair_order(n):
-        m, d = matchFeaturesScratch(allDescriptors[i], allDescriptors[j], MatchThreshold=MatchThreshold, MaxRatio=MaxRatio, Unique=Unique)
-        ii.append(m[:, 0])
-        jj.append(m[:, 1])
-        met.append(d)
-        pair_ptr.append(pair_ptr[-1] + len(m))
-    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
-    return np.asarray(pair_ptr, np.int64), cat(ii, np.uint32), cat(jj, np.uint32), cat(met, np.float32)
+    sets, bits = _binary_sets(allDescriptors)
+    cnt = np.asarray([int(s.shape[0]) for s in sets], np.int64)
+    if pairs is None:
+        pp = pair_order_array(n)
+    elif isinstance(pairs, np.ndarray):
+        pp = pairs.reshape(-1, 2)
+    else:
+        pp = np.asarray([(p[0], p[1]) for p in pairs], np.int32).reshape(-1, 2)
+    pa, pb = np.ascontiguousarray(pp[:, 0], np.int32), np.ascontiguousarray(pp[:, 1], np.int32)
+    P = len(pa)
+    if P and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= n):
+        raise ValueError("image index out of range in the pair list")
+    width = np.asarray([int(s.shape[1]) for s in sets], np.int64)
+    bits = np.asarray(bits, np.int64)
+    live = (cnt[pa] > 0) & (cnt[pb] > 0) if P else np.zeros(0, bool)
+    # one width for the sets that meet: bytes (hamm2nn:cols), and bits too (a pair of unpacked sets of 250 and 252 bits shares
+    # the byte width, not the divisor)
+    if np.any(width[pa[live]] != width[pb[live]]) or np.unique(width[pa[live]]).size > 1 or np.unique(bits[pa[live]]).size > 1 \
+            or np.any(bits[pa[live]] != bits[pb[live]]):
+        raise ValueError("Byte width mismatch.")  # hamm2nn:cols
+    # a set that meets only empty partners takes no part (its width does not matter, as pair by pair): handed over as empty
+    used = np.zeros(n, bool)
+    used[pa[live]] = used[pb[live]] = True
+    cnt = np.where(used, cnt, 0)
+    nbytes, nbits = (int(width[pa[live]][0]), int(bits[pa[live]][0])) if live.any() else (1, 0)
+    if nbits == 8 * nbytes:
+        nbits = 0
+    ptrs = (C.c_void_p * n)(*[ptr(s) if c else None for s, c in zip(sets, cnt)])
+    counts = (C.c_int64 * n)(*cnt.tolist())
+    lds = (C.c_int64 * n)(*[max(int(w), 1) for w in width])  # row-major, contiguous (binaryFeatures, packBits)
+    pair_ptr = np.zeros(P + 1, np.int64)
+    o = _hamming_opts(MaxRatio, MatchThreshold, Unique, nbits)
+    total = C.c_int64(0)
+    cap = int(cnt[pa][live].sum()) if P else 0  # every row of every pair: always enough, and only the matches are written
+    if device_out:
+        import torch
+
+        i_a = torch.empty(cap, dtype=torch.int32, device="cuda")
+        i_b = torch.empty(cap, dtype=torch.int32, device="cuda")
+        met = torch.empty(cap, dtype=torch.float32, device="cuda")
+        _fence_fresh_blocks()
+    else:
+        i_a, i_b, met = np.empty(cap, np.uint32), np.empty(cap, np.uint32), np.empty(cap, np.float32)
+    out = (ptr(pair_ptr), ptr(i_a) if cap else None, ptr(i_b) if cap else None, ptr(met) if cap else None, cap, C.byref(total))
+    lay = _capi.APS_ROWMAJOR
+    if max_columns is not None:  # the library's internal entry with the bound as an argument (not part of aps.h)
+        bounded = lib.aps_hamming_match_pairs_bounded
+        bounded.restype = C.c_int
+        bounded.argtypes = list(lib.aps_hamming_match_pairs.argtypes) + [C.c_int64]
+        lists = (None, None) if pairs is None else (ptr(pa), ptr(pb))
+        check(bounded(ptrs, counts, lds, n, nbytes, lay, *lists, P, C.byref(o), *out, int(max_columns)))
+    elif pairs is None:
+        check(lib.aps_hamming_match_pairwise(ptrs, counts, lds, n, nbytes, lay, C.byref(o), *out))
+    else:
+        check(lib.aps_hamming_match_pairs(ptrs, counts, lds, n, nbytes, lay, ptr(pa), ptr(pb), P, C.byref(o), *out))
+    k = total.value
+    return pair_ptr, i_a[:k], i_b[:k], met[:k]
+
+
+def match_pairwise_binary_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True):
+    """match_pairwise_csr for lists of binaryFeatures: every pair of pair_order through matchFeaturesScratch's binary branch, all
+    of them in one batched device call (match_pairs_binary_csr).
+    Returns (pair_ptr int64[P+1], idx_i, idx_j uint32 1-based, metric float32 percent) on the host."""
+    return match_pairs_binary_csr(allDescriptors, None, MaxRatio, MatchThreshold, Unique)
 
 
 def featureMatchingPairwise(input, allDescriptors, numImg):
@@ -495,7 +582,7 @@ def featureMatchingPairwise(input, allDescriptors, numImg):
                                   "set it to 0 for the device matcher (the MATLAB overlay forwards this switch to the reference)")
     matches = [[None] * numImg for _ in range(numImg)]
     if any(isinstance(d, binaryFeatures) for d in allDescriptors):
-        # binary sets: pair by pair through matchFeaturesScratch's binary branch, the reference's own loop (:48-63)
+        # binary sets: the reference's pair loop (:48-63) around matchFeaturesScratch's binary branch, as one batched device call
         pair_ptr, ii, jj, _ = match_pairwise_binary_csr(allDescriptors, ratio, thr, True)
         for p, (i, j) in enumerate(pair_order(numImg)):
             s, e = pair_ptr[p], pair_ptr[p + 1]

@@ -191,7 +191,7 @@ def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None):
     Returns dict(pairs=[(i,j)], models=[3x3 j->i], inliers=[K x 2 index arrays], numMatches n x n)."""
     n = len(descs)
     t0 = time.perf_counter()
-    if any(isinstance(d, fm.binaryFeatures) for d in descs):  # detector = 'FAST': the per-pair Hamming branch, same CSR
+    if any(isinstance(d, fm.binaryFeatures) for d in descs):  # detector = 'FAST': the batched Hamming matcher, same CSR
         pair_ptr, ii, jj, _ = fm.match_pairwise_binary_csr(descs, input["Ratiothreshold"], input["Matchingthreshold"], True)
     else:
         pair_ptr, ii, jj, _ = fm.match_pairwise_csr(descs, input["Ratiothreshold"], input["Matchingthreshold"], True)

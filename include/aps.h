@@ -258,6 +258,47 @@ int aps_global_filter(const uint32_t* nn_idx, const float* nn_dist, int64_t f, i
 int aps_hamming_2nn(const uint8_t* A, int64_t n1, int64_t lda, const uint8_t* B, int64_t n2,
                     int64_t ldb, int nbytes, int layout, uint32_t* idx2, float* d1, float* d2);
 
+/* Options of the binary branch of matchFeaturesScratch (matchFeaturesScratch.m:59-78 name/value pairs). */
+typedef struct aps_hamming_match_opts {
+    double max_ratio;       /* 'MaxRatio', linear for binary sets (matchFeaturesScratch.m:171); rounded to single for the test,
+                               as MATLAB evaluates double scalar * single array */
+    double match_threshold; /* 'MatchThreshold', percent of mismatched bits (:32 suggests 10 or more), rounded to single */
+    int unique;             /* 'Unique' (featureMatchingPairwise.m:113: true) */
+    int nbits;              /* 0 = 8 * nbytes; otherwise 1..8*nbytes: the width of unpacked-bit inputs before packBits padded
+                               them to whole bytes (matchFeaturesScratch.m:618-645).  Distances are counted on the packed bytes
+                               either way (the padding is zero on both sides); nbits is the divisor of the percent values and
+                               the patch of :318. */
+} aps_hamming_match_opts;
+
+/* a3 + a4 + a9 for binary sets: the pair loop of featureMatchingPairwise.m:48-63 with matchFeaturesScratch's binary branch
+ * inside (matchFeaturesScratch.m:81-135,170-211), every pair of the list in ONE batched launch chain.  Per pair, the rows of image
+ * pair_a[p] (0-based ids, pair_a[p] != pair_b[p]) are searched in image pair_b[p]:
+ *   2-NN on packed bytes with the mex's tie rule (nearest2HammingExhaustiveMEX.cpp:63-74: strict < for the best, so ties go to
+ *   the lower index; a single candidate gives second = nbytes * 8); a second distance of 0 becomes nbits (:318);
+ *   dBest = (d1 / nbits) * 100, dSecond = (d2 / nbits) * 100 in single, in that order (:120-121);
+ *   keep iff dBest <= single(MaxRatio) * dSecond (single product, :171) and dBest <= single(MatchThreshold) (:177);
+ *   unique != 0: greedy one-to-one in ascending (dBest, row) order (the stable sort of :186-207) - every row proposes one column,
+ *   so a column goes to its smallest (dBest, row) - and the list is in that order; unique == 0: in row order.
+ *   A pair with an empty side yields an empty list (:84-88).
+ * desc[i]: counts[i] x nbytes uint8 in `layout` with leading dimension ld[i], nbytes in 1..64, one width for all sets.
+ * Every array - the three tables, the pair list, the sets, the outputs - may be host or device memory.
+ * Outputs: pair_ptr int64[n_pairs + 1] CSR offsets; idx_a / idx_b 1-based row indices in image pair_a[p] / pair_b[p]; metric =
+ * dBest (percent).  cap >= sum over pairs of counts[pair_a[p]] always suffices.  With cap too small - cap = 0, or any of the
+ * three lists NULL, asks for the count only - the call fails with APS_E_CAP, *count and pair_ptr hold the true sizes and the
+ * lists are not written; elements count..cap of the lists are never written.
+ * The uniqueness step keeps one 8-byte slot per column of every pair in flight: the pair list is walked in chunks whose
+ * counts[pair_b[p]] sum to at most a bound (2^25 slots, 256 MiB; a single pair above it is a chunk of its own), with the same
+ * result for any chunking.  Arguments are checked before any device work, apart from reading tables and pair lists that live on
+ * the device; a list whose pairs all have an empty side needs no device. */
+int aps_hamming_match_pairs(const uint8_t* const* desc, const int64_t* counts, const int64_t* ld, int n_img, int nbytes, int layout,
+                            const int32_t* pair_a, const int32_t* pair_b, int64_t n_pairs, const aps_hamming_match_opts* opts,
+                            int64_t* pair_ptr, uint32_t* idx_a, uint32_t* idx_b, float* metric, int64_t cap, int64_t* count);
+/* The same for all upper-triangular pairs in aps_match_pairwise's order (featureMatchingPairwise.m:48), n_pairs =
+ * n_img * (n_img - 1) / 2: rows of image i searched in image j, i < j. */
+int aps_hamming_match_pairwise(const uint8_t* const* desc, const int64_t* counts, const int64_t* ld, int n_img, int nbytes, int layout,
+                               const aps_hamming_match_opts* opts, int64_t* pair_ptr, uint32_t* idx_i, uint32_t* idx_j, float* metric,
+                               int64_t cap, int64_t* count);
+
 /* ============================================================================================
  * (2) Geometric verification — PP/imageMatching/estimateTransformationRANSAC.m
  * ============================================================================================ */
