@@ -42,22 +42,22 @@ def blur(img, sigma):
     return ndimage.gaussian_filter(img, sigma, mode="mirror", radius=radius_of(sigma))
 
 
-def scale_space(gray):
+def scale_space(gray, sigma=SIGMA, nl=NL):
     """Gaussian and DoG stacks per octave, float64."""
     h, w = gray.shape
     yy, xx = np.mgrid[0:2 * h, 0:2 * w].astype(np.float64)
     up = ndimage.map_coordinates(gray, [(yy + 0.5) / 2 - 0.5, (xx + 0.5) / 2 - 0.5], order=1, mode="nearest")
-    base = blur(up, math.sqrt(max(SIGMA ** 2 - 1.0, 0.01)))  # the input is assumed to carry sigma 0.5 (1.0 after 2x)
+    base = blur(up, math.sqrt(max(sigma ** 2 - 1.0, 0.01)))  # the input is assumed to carry sigma 0.5 (1.0 after 2x)
     n_oct = int(round(math.log2(min(2 * h, 2 * w)) - 2)) + 1
-    k = 2.0 ** (1.0 / NL)
+    k = 2.0 ** (1.0 / nl)
     G, D = [], []
     for o in range(n_oct):
-        g = [base if o == 0 else G[o - 1][NL][::2, ::2]]
-        for i in range(1, NL + 3):
-            prev = SIGMA * k ** (i - 1)
+        g = [base if o == 0 else G[o - 1][nl][::2, ::2]]
+        for i in range(1, nl + 3):
+            prev = sigma * k ** (i - 1)
             g.append(blur(g[-1], math.sqrt((prev * k) ** 2 - prev ** 2)))
         G.append(g)
-        D.append([g[i + 1] - g[i] for i in range(NL + 2)])
+        D.append([g[i + 1] - g[i] for i in range(nl + 2)])
     return G, D
 
 
@@ -158,6 +158,53 @@ def test_scale_and_location_conventions(world):
     assert np.all(size_oct >= lo * 0.999) and np.all(size_oct <= hi * 1.001)
     assert layer.min() >= 1 and layer.max() <= NL
     assert loc[:, 0].min() >= 1 and loc[:, 0].max() <= img.shape[1] and loc[:, 1].max() <= img.shape[0]
+
+
+# The conventions hold for every parameter set, and nothing else pins the oracle away from the reference's call: the same two
+# checks at Sigma = 1.6 with one layer per octave and at Sigma = 3.2 with three (the sets test_sift_params_gpu.py holds the
+# device to).  The tests with measured thresholds above stay on the default set, which they were measured for.
+OTHER_SETS = [(1.6, 1), (3.2, 3)]
+
+
+@pytest.fixture(scope="module", params=OTHER_SETS, ids=lambda p: f"sigma{p[0]}-layers{p[1]}")
+def other_world(request):
+    sigma, nl = request.param
+    img = textured_image()
+    desc, loc, aux = oracle.sift(img, sigma, nl, CONTRAST, EDGE)
+    assert len(loc) > 100
+    G, _ = scale_space(img[:, :, 0].astype(np.float64), sigma, nl)
+    return sigma, nl, img, loc, aux, G
+
+
+def test_scale_and_location_conventions_at_other_parameter_sets(other_world):
+    sigma, nl, img, loc, aux, _ = other_world
+    o, layer, x, y = unpack(loc, aux)
+    size_oct = aux[:, 0] / 2.0 ** o
+    lo, hi = sigma * 2 ** ((layer - 0.5) / nl), sigma * 2 ** ((layer + 0.5) / nl)
+    assert np.all(size_oct >= lo * 0.999) and np.all(size_oct <= hi * 1.001)
+    assert layer.min() >= 1 and layer.max() <= nl and set(layer) == set(range(1, nl + 1))
+    assert loc[:, 0].min() >= 1 and loc[:, 0].max() <= img.shape[1] and loc[:, 1].min() >= 1 and loc[:, 1].max() <= img.shape[0]
+
+
+def test_octave_shapes_and_oracle_blur_at_other_parameter_sets(other_world):
+    sigma, nl, img, _, _, G = other_world
+    assert len(G) == oracle.sift_num_octaves(*img.shape[:2]) and all(len(g) == nl + 3 for g in G)
+    assert G[0][0].shape == (2 * img.shape[0], 2 * img.shape[1]) and G[1][0].shape == img.shape[:2]
+    # the oracle's f32 blur against scipy's at every sigma of this set's schedule, on a pyramid level.  The oracle caps a
+    # kernel at 63 taps (cv::GaussianBlur as cv::SIFT calls it does not), so the comparison stops where the cap starts.
+    # Bound, not measured: two passes of an fma chain of `taps` terms on values <= 255, half an ulp (2^-24) per step, and
+    # the taps themselves rounded to f32 once.
+    k = 2.0 ** (1.0 / nl)
+    sigmas = [math.sqrt(max(sigma ** 2 - 1.0, 0.01))] + [sigma * k ** (i - 1) * math.sqrt(k * k - 1) for i in range(1, nl + 3)]
+    plane = G[1][0].astype(np.float32)
+    checked = 0
+    for s in sigmas:
+        taps = 2 * radius_of(s) + 1
+        if taps > 63:
+            continue
+        np.testing.assert_allclose(oracle.sift_blur(plane, s), blur(plane.astype(np.float64), s), rtol=0, atol=2 * (taps + 1) * 2.0 ** -24 * 255)
+        checked += 1
+    assert checked >= 3
 
 
 def gradient_field(g):
