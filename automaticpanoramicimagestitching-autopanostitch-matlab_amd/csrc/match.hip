@@ -14,9 +14,13 @@
 //              match2nn_merge_parts_kernel: top-2 of a tile's column parts; knn3_rows_kernel: top-3 of single rows.
 //   candidates match_cand_f16_kernel<LIST>: f16 MFMA candidate search with exact rescoring of the best few in its
 //              tail; what it cannot certify goes to the fallback list.
-//   screen     match_screen_i8_kernel (32x32x32) / match_screen_i8x16_kernel (16x16x64, default): the int8 pass
-//              that dismisses rows which provably fail the caller's filter; <true> writes bounds for the pooled
-//              matcher instead.  match_list_i8_kernel + match_rescore_kernel: the exact int8 pass over survivors.
+//   streaming  xcd_order / lds_dma_16B / claim_whole_register_file: shared by the candidate kernel and the int8 kernels;
+//              Q8TileDma + Q8Stream: the int8 B-tile stream (LDS image, DMA cadence, hand-over, read-ahead, MFMAs),
+//              stated once - a kernel hands it a consumer for the finished blocks.
+//   screen     match_screen_i8x16_kernel (16x16x64, default; on Q8Stream) / match_screen_i8_kernel (32x32x32, superseded:
+//              its own loop on the shared pieces): the int8 pass that dismisses rows which provably fail the caller's
+//              filter; <true> writes bounds for the pooled matcher instead.  match_list_i8_kernel (on Q8Stream) +
+//              match_rescore_kernel: the exact int8 pass over survivors.
 //   filter     filter_mark / select / seg_end / emit(_rows): ratio + threshold in f64, one-to-one resolution by
 //              atomicMin on an order-preserving key, rocPRIM segmented sort to the reference's order.
 //   tables     fb_compact / list_pool / expand_tiles / fb_jobs: row lists and tile tables of the passes above.
@@ -1079,8 +1083,11 @@ __device__ __forceinline__ float max4_raw(float a, float b, float c, float d) {
 
 constexpr int kTileBytes = kTNB * 256;  // one f16 B tile in LDS
 
-// exact canonical distance of A row `pa` and B row `pb` (both in the permuted f32 layout of prep_desc_kernel):
-// G = k-ascending fma chain, d = (a2 + b2) - 2G — the same arithmetic as match2nn_kernel / the oracle.
+// The canonical distance: d = (a2 + b2) - 2G for the k-ascending fma chain G — the same arithmetic as match2nn_kernel /
+// the oracle.
+__device__ __forceinline__ float canonical_dist(float a2, float b2, float g) { return __fsub_rn(__fadd_rn(a2, b2), __fmul_rn(2.0f, g)); }
+
+// ... of A row `pa` and B row `pb` (both in the permuted f32 layout of prep_desc_kernel)
 __device__ __forceinline__ float exact_dist(const float* __restrict__ pa, const float* __restrict__ pb, float a2,
                                             float b2) {
     float g = 0.f;
@@ -1099,11 +1106,9 @@ __device__ __forceinline__ float exact_dist(const float* __restrict__ pa, const 
         g = fmaf(ae.w, be.w, g);
         g = fmaf(ao.w, bo.w, g);
     }
-    return __fsub_rn(__fadd_rn(a2, b2), __fmul_rn(2.0f, g));
+    return canonical_dist(a2, b2, g);
 }
 
-// Exact rescoring of one row's three candidates and the certification test (see the header comment): writes the
-// final (idx, d1, d2) of a certified row, or appends the row to the fallback list.
 // k-ascending fma chains of N candidate rows against the A row, side by side (each chain in the canonical order; the
 // A row is read once and N gathers are in flight: this tail is pure memory latency - unrolled by 8 it keeps 48 16-byte
 // loads per lane in flight, which measured 3 % of the kernel faster than 24; touching the lines first did not help)
@@ -1133,6 +1138,52 @@ __device__ __forceinline__ void exact_chains(const float* __restrict__ pa, const
     }
 }
 
+// The pieces rescore_row and rescore_row3 share.  The order of the floating-point operations in rescore_bound (as in
+// canonical_dist) is a bit-exact contract: the oracle restates them.
+// a row's three candidate columns: which exist, and the row each gather reads (an absent one re-reads the A row)
+__device__ __forceinline__ void rescore_cands(const MatchJob& jb, const float* pa, const int (&id)[3], const float* (&pb)[3], bool (&ok)[3]) {
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        ok[e] = id[e] >= 0 && id[e] < jb.nB;
+        pb[e] = ok[e] ? jb.PB + (size_t)id[e] * kDim : pa;
+    }
+}
+
+// candidate e's exact distance from its chain g (an absent one: +inf, behind every index)
+__device__ __forceinline__ float rescore_dist(const MatchJob& jb, float a2, bool ok, int& id, float g) {
+    const float d = ok ? canonical_dist(a2, jb.sqB[ok ? id : 0], g) : INFINITY;
+    if (!ok) id = 0x7fffffff;
+    return d;
+}
+
+// compare-swap of candidates a, b of the arrays d / id in scope: ascending by (distance, index).  (A macro: as a function
+// over references the conditional stores stay branches in the candidate kernel's tail.)
+#define APS_CSWAP(a, b)                                                    \
+    if (d[b] < d[a] || (d[b] == d[a] && id[b] < id[a])) {                  \
+        const float td = d[a]; d[a] = d[b]; d[b] = td;                     \
+        const int ti = id[a]; id[a] = id[b]; id[b] = ti;                   \
+    }
+
+// eps: how far the exact distance of a column may lie below a2 - 2 U_j for its screened value U_j.
+// The screened value of column j is U_j = a^.b^_j - y~_j + na^ dn^_j, an UPPER bound (up to the row-wise terms
+// below) of s_j = a.b_j - b2_j/2:
+//   |a.b - a^.b^| <= ||a - a^|| ||b^|| + ||a|| ||b - b^||   (Cauchy-Schwarz on the two rounding losses);
+//   the second term, ||a|| dn_j, is column specific and is added by the matrix pipe itself (k-slot 3 of the
+//   extra step: na^ >= ||a|| on the A side, dn^_j >= ||b_j - b^_j|| on the B side, both rounded UP to f16);
+//   row-wise remainder: ||a - a^|| max||b^|| + the largest residual of the three-piece b2/2 the workgroup has
+//   staged + any saturation loss of dn^ + f32 accumulation in the matrix pipe, bounded by 2^-15 (sum|a_k b_k|
+//   + y) (measured <= 7 x 2^-24, scripts/probe/mfma_f16_err.hip).
+// Every column outside the best K has U_j <= u_(K+1), hence s_j <= u_(K+1) + eg; in distance units twice that,
+// plus the roundings of the canonical f32 evaluation itself.
+__device__ __forceinline__ float rescore_bound(const MatchJob& jb, int row, float a2, float aug_res, float dn_res) {
+    const float msb = *jb.maxsqB, mdb = *jb.maxdnB;
+    const float nb = sqrtf(msb) * 1.000001f + mdb;
+    const float na = sqrtf(a2) * 1.000001f;
+    float eg = jb.dnA[row] * nb + aug_res + na * dn_res + 3.0517578125e-05f * (na * (nb + mdb) + 0.5f * msb);
+    if (!(na < 65000.f)) eg = INFINITY;  // ||a|| does not fit the f16 slot: nothing is certified
+    return 2.002f * eg + 1.52587890625e-05f * (a2 + msb + 2.0f * na * nb) + 1e-37f;
+}
+
 // Exact rescoring of one row's candidates and the certification test (see the header comment): writes the final
 // (idx, d1, d2) of a certified row, or appends the row to the fallback list.  bnd3 / bnd4 = a2 - 2 u for the third- /
 // fourth-largest screened value of the row.
@@ -1147,55 +1198,25 @@ __device__ __forceinline__ void rescore_row(const MatchJob& jb, int job, int row
     int id[3] = {c0, c1, c2};
     const float* pb[3];
     bool ok[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        ok[e] = id[e] >= 0 && id[e] < jb.nB;
-        pb[e] = ok[e] ? jb.PB + (size_t)id[e] * kDim : pa;
-    }
-    // The screened value of column j is U_j = a^.b^_j - y~_j + na^ dn^_j, an UPPER bound (up to the row-wise terms
-    // below) of s_j = a.b_j - b2_j/2:
-    //   |a.b - a^.b^| <= ||a - a^|| ||b^|| + ||a|| ||b - b^||   (Cauchy-Schwarz on the two rounding losses);
-    //   the second term, ||a|| dn_j, is column specific and is added by the matrix pipe itself (k-slot 3 of the
-    //   extra step: na^ >= ||a|| on the A side, dn^_j >= ||b_j - b^_j|| on the B side, both rounded UP to f16);
-    //   row-wise remainder: ||a - a^|| max||b^|| + the largest residual of the three-piece b2/2 the workgroup has
-    //   staged + any saturation loss of dn^ + f32 accumulation in the matrix pipe, bounded by 2^-15 (sum|a_k b_k|
-    //   + y) (measured <= 7 x 2^-24, scripts/probe/mfma_f16_err.hip).
-    // Every column outside the best K has U_j <= u_(K+1), hence s_j <= u_(K+1) + eg; in distance units twice that,
-    // plus the roundings of the canonical f32 evaluation itself.
-    const float msb = *jb.maxsqB, mdb = *jb.maxdnB;
-    const float nb = sqrtf(msb) * 1.000001f + mdb;
-    const float na = sqrtf(a2) * 1.000001f;
-    float eg = jb.dnA[row] * nb + aug_res + na * dn_res + 3.0517578125e-05f * (na * (nb + mdb) + 0.5f * msb);
-    if (!(na < 65000.f)) eg = INFINITY;  // ||a|| does not fit the f16 slot: nothing is certified
-    const float eps = 2.002f * eg + 1.52587890625e-05f * (a2 + msb + 2.0f * na * nb) + 1e-37f;
-
-#define APS_CSWAP(a, b)                                                    \
-    if (d[b] < d[a] || (d[b] == d[a] && id[b] < id[a])) {                  \
-        const float td = d[a]; d[a] = d[b]; d[b] = td;                     \
-        const int ti = id[a]; id[a] = id[b]; id[b] = ti;                   \
-    }
+    rescore_cands(jb, pa, id, pb, ok);
+    const float eps = rescore_bound(jb, row, a2, aug_res, dn_res);
     // Stage 1: the best two alone.  If their exact second-best beats the bound of everything else - the third
     // candidate included, through ITS screened value - the row is done after two 512-byte gathers instead of three
     // (the gathers of this tail are 60 % of the kernel's HBM traffic).
     float g[3];
     exact_chains<2>(pa, pb, g);
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        d[e] = ok[e] ? __fsub_rn(__fadd_rn(a2, jb.sqB[ok[e] ? id[e] : 0]), __fmul_rn(2.0f, g[e])) : INFINITY;
-        if (!ok[e]) id[e] = 0x7fffffff;
-    }
+    for (int e = 0; e < 2; ++e) d[e] = rescore_dist(jb, a2, ok[e], id[e], g[e]);
     APS_CSWAP(0, 1)
     bool certified = jb.nB > 3 && d[1] < bnd3 - eps;
     if (!certified) {
         // Stage 2: the third candidate joins; the bound is the fourth screened value
         exact_chains<1>(pa, pb + 2, g + 2);
-        d[2] = ok[2] ? __fsub_rn(__fadd_rn(a2, jb.sqB[ok[2] ? id[2] : 0]), __fmul_rn(2.0f, g[2])) : INFINITY;
-        if (!ok[2]) id[2] = 0x7fffffff;
+        d[2] = rescore_dist(jb, a2, ok[2], id[2], g[2]);
         APS_CSWAP(1, 2)
         APS_CSWAP(0, 1)
         certified = jb.nB <= 3 || (d[1] < bnd4 - eps);
     }
-#undef APS_CSWAP
     if (certified) {
         out_idx[slot] = jb.nB > 0 ? (uint32_t)id[0] + 1u : 0u;
         out_d1[slot] = d[0];
@@ -1211,10 +1232,9 @@ __device__ __forceinline__ void rescore_row(const MatchJob& jb, int job, int row
 // distances of the three candidates, ascending by (distance, index), cut to the prefix that is strictly below the bound of
 // every non-candidate of this B set (a2 - 2 u4 - eps).  t3_b receives that bound: every row of the set that is not
 // listed is at least that far away.
-__device__ __forceinline__ void rescore_row3(const MatchJob& jb, int job, int row, int c0, int c1, int c2, float bnd4,
+__device__ __forceinline__ void rescore_row3(const MatchJob& jb, int row, int c0, int c1, int c2, float bnd4,
                                              float aug_res, float dn_res, uint32_t* __restrict__ t3_idx,
-                                             float* __restrict__ t3_d, float* __restrict__ t3_b,
-                                             uint32_t* __restrict__ fb_list, unsigned int* __restrict__ fb_count) {
+                                             float* __restrict__ t3_d, float* __restrict__ t3_b) {
     const int64_t slot = jb.out_off + row;
     const float a2 = jb.sqA[row];
     const float* pa = jb.PA + (size_t)row * kDim;
@@ -1222,39 +1242,20 @@ __device__ __forceinline__ void rescore_row3(const MatchJob& jb, int job, int ro
     int id[3] = {c0, c1, c2};
     const float* pb[3];
     bool ok[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        ok[e] = id[e] >= 0 && id[e] < jb.nB;
-        pb[e] = ok[e] ? jb.PB + (size_t)id[e] * kDim : pa;
-    }
-    const float msb = *jb.maxsqB, mdb = *jb.maxdnB;
-    const float nb = sqrtf(msb) * 1.000001f + mdb;
-    const float na = sqrtf(a2) * 1.000001f;
-    float eg = jb.dnA[row] * nb + aug_res + na * dn_res + 3.0517578125e-05f * (na * (nb + mdb) + 0.5f * msb);
-    if (!(na < 65000.f)) eg = INFINITY;
-    const float eps = 2.002f * eg + 1.52587890625e-05f * (a2 + msb + 2.0f * na * nb) + 1e-37f;
+    rescore_cands(jb, pa, id, pb, ok);
+    const float eps = rescore_bound(jb, row, a2, aug_res, dn_res);
     float g[3];
     exact_chains<3>(pa, pb, g);
 #pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        d[e] = ok[e] ? __fsub_rn(__fadd_rn(a2, jb.sqB[ok[e] ? id[e] : 0]), __fmul_rn(2.0f, g[e])) : INFINITY;
-        if (!ok[e]) id[e] = 0x7fffffff;
-    }
-#define APS_CSWAP(a, b)                                                    \
-    if (d[b] < d[a] || (d[b] == d[a] && id[b] < id[a])) {                  \
-        const float td = d[a]; d[a] = d[b]; d[b] = td;                     \
-        const int ti = id[a]; id[a] = id[b]; id[b] = ti;                   \
-    }
+    for (int e = 0; e < 3; ++e) d[e] = rescore_dist(jb, a2, ok[e], id[e], g[e]);
     APS_CSWAP(0, 1)
     APS_CSWAP(1, 2)
     APS_CSWAP(0, 1)
-#undef APS_CSWAP
     // Every column that is not one of the three candidates is at least `bound` away.  A candidate whose exact distance is
     // strictly below the bound is therefore in its final place among the set's nearest; the others (if any) are no
     // nearer than the bound either, so they are simply left unlisted: the list is a CERTIFIED PREFIX of the set's
     // nearest rows, and "everything unlisted is >= bound" holds in every case.  The merge decides whether it needs more.
     const float bound = jb.nB <= 3 ? INFINITY : bnd4 - eps;
-    (void)job; (void)fb_list; (void)fb_count;
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
         const bool keep = id[e] < jb.nB && (jb.nB <= 3 || d[e] < bound);
@@ -1263,6 +1264,7 @@ __device__ __forceinline__ void rescore_row3(const MatchJob& jb, int job, int ro
     }
     t3_b[slot] = bound;
 }
+#undef APS_CSWAP
 
 // Exact top-3 of one A row against its job's whole B set (the fallback of rescore_row3): one wave per listed slot, lane j
 // takes columns j, j+64, ...; every distance is the canonical f32 chain (exact_dist); lists merged through LDS.
@@ -1353,6 +1355,35 @@ __device__ __forceinline__ void prune_bounds(const MatchJob& jb, int row, float 
     }
 }
 
+// ---- what the streaming kernels below share (match_cand_f16_kernel and the three int8 kernels) ----
+// XCD-aware workgroup order: consecutive workgroup ids go to different XCDs (one L2 each); give each XCD a contiguous run
+// of the job-major tile list so that the workgroups sharing a B set share an L2
+__device__ __forceinline__ int xcd_order(int wg, int n_wg) {
+    const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
+}
+
+// One LDS-DMA instruction: every lane's 16 bytes at `src` go to the wave-uniform LDS address `lds_dst` + 16 lane (M0 holds
+// the address for the instruction and is put back).  Inline asm on purpose: for the builtin the compiler cannot tell the
+// LDS buffers apart and drains vmcnt before the first ds_read that follows, which exposes the whole DMA latency once per
+// tile.  The DMA of tile t+1 is retired by the explicit vmcnt(0) before the barrier that ends tile t; nothing reads that
+// buffer earlier.
+__device__ __forceinline__ void lds_dma_16B(const void* src, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(lds_dst)
+                 : "memory");
+}
+
+// An int8-MFMA kernel claims the whole vector register file of its SIMDs (2 waves x 256 registers at 512 threads per
+// workgroup) whatever it needs itself: waves of OTHER kernels that shared a SIMD with v_mfma_i32_*_i8 waves came back with
+// different results (SIFT's refine / orientation / descriptor kernels, from another stream, when feature extraction and
+// matching overlap; f16 MFMA, VALU, LDS or LDS-DMA neighbours leave them alone) - measured with
+// scripts/probe/probe_overlap_race3.py, DESIGN.md section 5.  With nothing co-resident the extraction is bit-identical
+// again; the int8 kernels' own results were never affected.  require_whole_simd checks the allocation before a launch.
+__device__ __forceinline__ void claim_whole_register_file() { asm volatile("v_mov_b32 v255, 0" ::: "v255"); }
+
 template <bool LIST>
 __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __restrict__ jobs,
                                                                 const WgJob* __restrict__ wgs, int n_wg,
@@ -1375,14 +1406,7 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
     // accumulator (padded column: -65504 c0)
     __shared__ __attribute__((aligned(1024))) uint4 s_aug[3][kTNB];  // filled by DMA with the B tile (aug_desc_kernel's rows)
 
-    // XCD-aware order: consecutive workgroup ids go to different XCDs (one L2 each); give each XCD a
-    // contiguous run of the job-major list so that the workgroups sharing a B set share an L2
-    int wg = blockIdx.x;
-    {
-        const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
-        wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-    }
-    const WgJob w = wgs[wg];
+    const WgJob w = wgs[xcd_order(blockIdx.x, n_wg)];
     const MatchJob jb = jobs[w.job];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1438,10 +1462,6 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
     // DMA pieces: 32 per tile, 1 KiB = 4 LDS rows each; wave w issues pieces 4w .. 4w+3, one per column block.
     // lane -> LDS row 4*piece + lane/16, chunk position lane&15, which must hold source chunk pos ^ (row&15)
     const int dma_sub = lane >> 4, dma_pos = lane & 15;
-    // The DMA is issued from inline asm on purpose: for the builtin the compiler cannot tell the two LDS
-    // buffers apart and drains vmcnt before the first ds_read that follows, which exposes the whole DMA
-    // latency once per tile.  The DMA of tile t+1 is retired by the explicit vmcnt(0) before the barrier that
-    // ends tile t; nothing reads that buffer earlier.
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const uint32_t aug_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&s_aug[0][0];
     // piece u of this wave's four; with its piece 0, wave 0 / wave 1 also fetch one half of the tile's 2 KiB of extra
@@ -1452,20 +1472,10 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
         const int brow = min(t * kTNB + lrow, nB - 1);
         const unsigned short* src = jb.BF + (size_t)brow * kDim + ((dma_pos ^ (lrow & 15)) << 3);
         const uint32_t dst = lds_base + buf * kTileBytes + piece * 1024;
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(src), "s"(dst)
-            : "memory");
+        lds_dma_16B(src, dst);
         if (u == 0 && wave < 2) {
             const uint4* asrc = jb.augB + (size_t)t * kTNB + wave * 64 + lane;  // the array is padded to whole tiles
-            const uint32_t adst = aug_base + buf * (kTNB * 16) + wave * 1024;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(asrc), "s"(adst)
-                : "memory");
+            lds_dma_16B(asrc, aug_base + buf * (kTNB * 16) + wave * 1024);
         }
     };
     f32x16 acc[2][2];  // [block parity][owned row]: one set is being accumulated while the other is being searched
@@ -1687,7 +1697,7 @@ __global__ __launch_bounds__(512) void match_cand_f16_kernel(const MatchJob* __r
             }
             if (t3_idx) {  // top-3 mode (blocked global k-NN): three exact distances + the set's bound per row
                 const float bnd = jr.sqA[row] - 2.0f * ub;
-                rescore_row3(jr, myjob, row, c0, c1, c2, bnd, jb.augresB[0], jb.augresB[1], t3_idx, t3_d, t3_b, fb_list, fb_count);
+                rescore_row3(jr, row, c0, c1, c2, bnd, jb.augresB[0], jb.augresB[1], t3_idx, t3_d, t3_b);
             } else if (pruned) {
                 const int64_t slot = jr.out_off + row;
                 out_idx[slot] = 0u;  // "no match": the filter drops idx 0 (a row the reference's filter would drop too)
@@ -1869,6 +1879,191 @@ __device__ __forceinline__ void screen_tail(const MatchJob& jb, int job, int row
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the int8 B-tile stream: what the int8-MFMA kernels share
+// ------------------------------------------------------------------------------------------------
+// The DMA of a B tile into the LDS image all three kernels share: [buf][256][128 B], tile t in buf t % 3, in 32 pieces of
+// 1 KiB = 8 LDS rows; wave w issues pieces 4w .. 4w+3 (u = 0..3).  lane -> LDS row 8*piece + lane/8, chunk position lane&7,
+// which must hold source chunk pos ^ ((row >> 1) & 7); rows past the set's end re-read its last row.
+struct Q8TileDma {
+    const signed char* const B;  // the column codes
+    const int nB;
+    const uint32_t lds_base;
+    const int wave, sub, pos;
+    __device__ __forceinline__ Q8TileDma(const signed char* B_, int nB_, const unsigned char* lds)
+        : B(B_), nB(nB_), lds_base((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)lds),
+          wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)), sub((threadIdx.x & 63) >> 3), pos(threadIdx.x & 7) {}
+    __device__ __forceinline__ void issue_piece(int t, int buf, int u) const {
+        const int piece = wave * 4 + u;
+        const int lrow = 8 * piece + sub;
+        const int brow = min(t * kQTN + lrow, nB - 1);
+        lds_dma_16B(B + (size_t)brow * kDim + ((pos ^ ((lrow >> 1) & 7)) << 4), lds_base + buf * kQTileBytes + piece * 1024);
+    }
+};
+
+// What a consumer is told, at compile time, about the slice it is handed: the finished block's accumulator parity, the row
+// group g, the block's index within its tile, whether columns >= nB can lie in it (ragged last tile only), and whether it
+// is the last block of the tile BEFORE the one being streamed (it is searched during block 0 of the next).
+template <int PAR, int G, int BLK, bool MASKED, bool PREV>
+struct Q8Slice {
+    static constexpr int par = PAR, g = G, blk = BLK;
+    static constexpr bool masked = MASKED, prev = PREV, first = BLK == 0, last = BLK == kQBlk - 1;
+};
+
+// The stream of match_screen_i8x16_kernel and match_list_i8_kernel: a 512-thread workgroup, every wave holding 64 A rows
+// (aq: four groups of 16, two 64-byte k-steps), sweeps a B set in tiles of 256 columns on v_mfma_i32_16x16x64_i8.
+// LDS: [buf][256][128 B], tile t in buf t % 3; then [buf][256] accumulator start values (cinB, 1 KiB per tile).
+// Software pipeline (the scheme of match_cand_f16_kernel): the consumer's search of block g-1 is cut into four slices that
+// sit between the MFMA groups of block g (two accumulator sets); operand reads run three slots ahead, across block and tile
+// boundaries, so the hand-over sits one block early - tile t+1 must have landed at the barrier after block kLast - 1 of tile
+// t - and tile t is still being read during its last block, hence three buffers.
+// A kernel declares `lds`, gathers its rows into aq and calls start(), tile() per tile, finish().
+struct Q8Stream {
+    static constexpr int kLdsBytes = 3 * kQTileBytes + 3 * 1024;
+    static constexpr int kAhead = 3;  // an LDS round trip under load is longer than one slot (four MFMAs + a slice)
+    unsigned char* const lds;
+    const Q8TileDma dma;
+    const int* const cinB;  // the accumulators' start values, one per column (with_cin; otherwise the kernel zero-fills the area)
+    const bool with_cin;
+    const int ncin, ntiles;
+    const int lane, wave, c, kq;
+    // per-lane read offsets: slot s of a block = sub-block s >> 1, k-step s & 1: row 16 (s >> 1) + c, chunk (4 (s & 1) + kq)
+    // ^ ((c >> 1) & 7)  (the sub-block's 16 rows leave (row >> 1) & 7 alone)
+    const int hx;
+    const unsigned char* const cin_lds;
+    i32x4 acc[2][2][4];  // [block parity][sub-block][row group]: D[column 4 kq + r of the sub-block][row c of the group]
+    i32x4 bq[4];
+    i32x4 cin[2];  // cin[u]: the start values of the lane's four columns 16 u + 4 kq + r of the NEXT block to start (read one block ahead)
+    int b_cur = 0;  // t % 3
+
+    __device__ __forceinline__ Q8Stream(unsigned char* lds_, const signed char* B_, const int* cinB_, int ncin_, bool with_cin_, int nB_)
+        : lds(lds_), dma(B_, nB_, lds_), cinB(cinB_), with_cin(with_cin_), ncin(ncin_), ntiles((nB_ + kQTN - 1) / kQTN),
+          lane(threadIdx.x & 63), wave(dma.wave), c(lane & 15), kq(lane >> 4),
+          hx((16 * kq) ^ (16 * ((c >> 1) & 7))), cin_lds(lds_ + 3 * kQTileBytes + 16 * kq) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[p][u][g][e] = kScreenNone;
+        cin[0] = cin[1] = i32x4{0, 0, 0, 0};
+    }
+    __device__ __forceinline__ void issue_piece(int t, int buf, int u) const { dma.issue_piece(t, buf, u); }
+    // The start values of tile t travel with piece 0 of the tile, issued by wave 0; entries past the set's padded length are
+    // clamped to its last four (columns >= nB: masked by the consumer).
+    __device__ __forceinline__ void issue_cin(int t, int buf) const {
+        if (with_cin && wave == 0) lds_dma_16B(cinB + min(t * kQTN + 4 * lane, ncin - 4), dma.lds_base + 3 * kQTileBytes + buf * 1024);
+    }
+    __device__ __forceinline__ int slot_off(int s) const { return (s >> 1) * 16 * kDim + ((64 * (s & 1)) ^ hx); }
+
+    // tile 0 in full, piece 0 of tile 1, the first reads
+    __device__ __forceinline__ void start(const i32x4 (&aq)[4][2]) {
+        if (ntiles > 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) issue_piece(0, 0, u);
+            issue_cin(0, 0);
+        }
+        // touch the resident operand here: otherwise the compiler's pending-load state for these registers reaches the loop
+        // header and it drains vmcnt (DMA included) at their first use in EVERY iteration
+#pragma unroll
+        for (int g = 0; g < 4; ++g) asm volatile("" ::"v"(aq[g][0]), "v"(aq[g][1]));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (ntiles > 0) {
+            if (ntiles > 1) {
+                issue_piece(1, 1, 0);
+                issue_cin(1, 1);
+            }
+#pragma unroll
+            for (int s = 0; s < kAhead; ++s) bq[s] = *reinterpret_cast<const i32x4*>(lds + c * kDim + slot_off(s));
+            cin[0] = *reinterpret_cast<const i32x4*>(cin_lds);
+            cin[1] = *reinterpret_cast<const i32x4*>(cin_lds + 64);
+        }
+    }
+
+    // Tile t.  MASK: its columns may reach past nB (the consumer is told per slice).  tile_start(t) runs before block 0,
+    // consume(Q8Slice, col0) once per slot and row group on the block finished before (col0 = that block's first column; at
+    // t == 0, block 0, there is none: the accumulators still hold kScreenNone and col0 < 0), after_block0(t) when block 0
+    // is through, i.e. when the last block of tile t - 1 has been consumed.
+    template <bool MASK, class TileStart, class Consume, class AfterBlock0>
+    __device__ __forceinline__ void tile(int t, const i32x4 (&aq)[4][2], TileStart&& tile_start, Consume&& consume,
+                                         AfterBlock0&& after_block0) {
+        const bool more = t + 1 < ntiles;
+        const bool more2 = t + 2 < ntiles;
+        const int b_nxt = b_cur == 2 ? 0 : b_cur + 1, b_nxt2 = b_nxt == 2 ? 0 : b_nxt + 1;
+        const unsigned char* tile = lds + b_cur * kQTileBytes + c * kDim;
+        const unsigned char* tile_n = lds + b_nxt * kQTileBytes + c * kDim;
+        const unsigned char* cin_t = cin_lds + b_cur * 1024;
+        const unsigned char* cin_n = cin_lds + b_nxt * 1024;
+        b_cur = b_nxt;
+        tile_start(t);
+        static_for<0, kQBlk>([&](auto CB) {
+            constexpr int cb = decltype(CB)::value;
+            constexpr int kLast = kQBlk - 1;
+            constexpr int par = cb & 1;
+            // DMA: pieces 1..3 of tile t+1 in blocks 0, 2, 4; piece 0 of tile t+2 (and its start values) in the last block
+            // (after the hand-over, into the buffer tile t-1 has just left for good)
+            if (cb == 0 || cb == 2 || cb == 4) {
+                if (more) issue_piece(t + 1, b_nxt, cb / 2 + 1);
+            } else if (cb == kLast) {
+                if (more2) {
+                    issue_piece(t + 2, b_nxt2, 0);
+                    issue_cin(t + 2, b_nxt2);
+                }
+            }
+            const unsigned char* blk = tile + cb * 32 * kDim;
+            // first operands of the next block: same tile, or block 0 of the tile handed over one block ago
+            const unsigned char* nblk = cb < kLast ? blk + 32 * kDim : tile_n;
+            const bool fetch = cb < kLast || more;
+            // the block being searched is the previous one: (t, cb - 1), or the last block of tile t - 1 (never ragged)
+            const int col0 = t * kQTN + (cb - 1) * 32;
+            static_for<0, 4>([&](auto S) {
+                constexpr int s = decltype(S)::value;
+                constexpr int u = s >> 1, ks = s & 1;
+                const i32x4 xq = bq[s & 3];
+                if (s + kAhead < 4) {
+                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(blk + slot_off(s + kAhead));
+                } else if (fetch) {
+                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(nblk + slot_off(s + kAhead - 4));
+                }
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    acc[par][u][g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xq, aq[g][ks], ks == 0 ? cin[u] : acc[par][u][g], 0, 0, 0);
+                // sub-block u's start values are consumed: fetch the next block's (the same tile's, or the next tile's first)
+                if (ks == 1) {
+                    if (cb < kLast)
+                        cin[u] = *reinterpret_cast<const i32x4*>(cin_t + (32 * (cb + 1) + 16 * u) * 4);
+                    else if (more)
+                        cin[u] = *reinterpret_cast<const i32x4*>(cin_n + (16 * u) * 4);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                consume(Q8Slice<par ^ 1, s, (cb + kLast) % kQBlk, MASK && cb != 0, cb == 0>{}, col0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            if (cb == 0) after_block0(t);
+            if (cb == kLast - 1) {
+                // hand-over: this wave's DMA pieces of tile t+1 have landed; after the barrier that holds for every
+                // wave, and every wave has left tile t-1
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+        });
+    }
+
+    // the last block of the last tile (call it only where ntiles > 0)
+    template <bool MASK, class Consume>
+    __device__ __forceinline__ void finish(Consume&& consume) {
+        const int col0 = (ntiles - 1) * kQTN + (kQBlk - 1) * 32;
+        static_for<0, 4>([&](auto S) { consume(Q8Slice<(kQBlk - 1) & 1, decltype(S)::value, kQBlk - 1, MASK, false>{}, col0); });
+    }
+};
+
+// The screening pass on v_mfma_i32_32x32x32_i8 (rounds 2-3; APS_SCREEN_SHAPE=32 - superseded by the 16x16x64 kernel below).
+// Shared with the other int8 kernels: xcd_order, the register-file claim, the LDS tile image and its DMA (Q8TileDma), the DMA
+// cadence and the hand-over.  Its own: the MFMA shape and accumulator layout, hence its own copy of the tile loop (no C
+// operand, reads by half-wave), and fold_quarter.
 // BOUNDS: the pooled matcher's form (screened_global_top3) - a separate instantiation, so that profiles keep the two
 // apart.
 template <bool BOUNDS>
@@ -1882,18 +2077,8 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
     // three bounds L1 <= d1, H1 >= d1, H2 >= d2 on the row's two smallest distances in this job's column set are written
     // (rounded outwards; -inf / +inf where nothing can be said) and a later pass combines them over a row's jobs.
     __shared__ __attribute__((aligned(1024))) unsigned char lds[3 * kQTileBytes];  // [buf][256][128 B], tile t in buf t % 3
-    int wg = blockIdx.x;
-    {  // XCD-aware order, as in match_cand_f16_kernel
-        const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
-        wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-    }
-    // The kernel claims the whole vector register file of its SIMDs (2 waves x 256 registers) although it needs 169:
-    // waves of OTHER kernels that shared a SIMD with v_mfma_i32_32x32x32_i8 waves came back with different results
-    // (SIFT's refine / orientation / descriptor kernels, from another stream, when feature extraction and matching
-    // overlap; f16 MFMA, VALU, LDS or LDS-DMA neighbours leave them alone) - measured with scripts/probe/probe_overlap_race3.py,
-    // DESIGN.md section 5.  With nothing co-resident the extraction is bit-identical again; this kernel's own results were
-    // never affected.
-    asm volatile("v_mov_b32 v255, 0" ::: "v255");
+    const int wg = xcd_order(blockIdx.x, n_wg);
+    claim_whole_register_file();
     const WgJob w = wgs[wg];
     const MatchJob jb = jobs[w.job];
     const int tid = threadIdx.x;
@@ -1912,27 +2097,12 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
         for (int s = 0; s < 4; ++s)
             aq[rb][s] = *reinterpret_cast<const i32x4*>(jb.AQ + (size_t)arow * kDim + 32 * s + 16 * h);
     }
-    constexpr int kNone = -2147483647 - 1;
+    constexpr int kNone = kScreenNone;
     int d0[2] = {kNone, kNone}, d1[2] = {kNone, kNone};
 
     const int ntiles = (nB + kQTN - 1) / kQTN;
-    // DMA pieces: 32 per tile, 1 KiB = 8 LDS rows each; wave w issues pieces 4w .. 4w+3.
-    // lane -> LDS row 8*piece + lane/8, chunk position lane&7, which must hold source chunk pos ^ ((row >> 1) & 7)
-    const int dma_sub = lane >> 3, dma_pos = lane & 7;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    auto issue_piece = [&](int t, int buf, int u) {
-        const int piece = wave * 4 + u;
-        const int lrow = 8 * piece + dma_sub;
-        const int brow = min(t * kQTN + lrow, nB - 1);
-        const signed char* src = jb.BQ + (size_t)brow * kDim + ((dma_pos ^ ((lrow >> 1) & 7)) << 4);
-        const uint32_t dst = lds_base + buf * kQTileBytes + piece * 1024;
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(src), "s"(dst)
-            : "memory");
-    };
+    const Q8TileDma dma(jb.BQ, nB, lds);
+    auto issue_piece = [&](int t, int buf, int u) { dma.issue_piece(t, buf, u); };
     i32x16 acc[2][2];  // [block parity][owned row]
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[0][0][e] = acc[0][1][e] = acc[1][0][e] = acc[1][1][e] = kNone;
@@ -2006,8 +2176,7 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
             constexpr int cb = decltype(CB)::value;
             constexpr int kLast = kQBlk - 1;
             constexpr int par = cb & 1;
-            // DMA: pieces 1..3 of tile t+1 in blocks 0, 2, 4; piece 0 of tile t+2 in the last block (after the hand-over,
-            // into the buffer tile t-1 has just left for good)
+            // (the DMA cadence of Q8Stream::tile)
             if (cb == 0 || cb == 2 || cb == 4) {
                 if (more) issue_piece(t + 1, b_nxt, cb / 2 + 1);
             } else if (cb == kLast) {
@@ -2040,9 +2209,7 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
                     fold_quarter(std::integral_constant<int, par ^ 1>{}, S, std::false_type{}, 0);
                 __builtin_amdgcn_sched_barrier(0);
             });
-            if (cb == kLast - 1) {
-                // hand-over: this wave's DMA pieces of tile t+1 have landed; after the barrier that holds for every
-                // wave, and every wave has left tile t-1
+            if (cb == kLast - 1) {  // hand-over
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
             }
@@ -2080,10 +2247,10 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
 // Mapping: a wave owns 64 rows as four groups of 16; operand 2 of the MFMA is a row group (lane l: row l & 15 of the group,
 // k bytes 16 (l >> 4) .. + 15 of the 64-byte k-step), operand 1 a 16-column sub-block of the B tile (lane l: column l & 15,
 // the same k bytes), the result D[column 4 (l >> 4) + r][row l & 15] in four registers.  A 32-column block = two
-// sub-blocks x two k-steps = four ds_read_b128 per lane (the LDS image and its XOR swizzle are unchanged and stay
-// conflict-free for this read pattern: row c, chunk (4 ks + kq) ^ ((c >> 1) & 7)), each feeding four MFMAs of 16 cycles
-// - the cadence of the 32x32x32 loop, so DMA, hand-over and read-ahead carry over.  Selection: see fold_group; the four
-// lane quarters of a row are merged at the end.
+// sub-blocks x two k-steps = four ds_read_b128 per lane (the LDS image and its XOR swizzle are those of the 32x32x32 kernel
+// and stay conflict-free for this read pattern: row c, chunk (4 ks + kq) ^ ((c >> 1) & 7)), each feeding four MFMAs of 16
+// cycles - the cadence of the 32x32x32 loop.  The stream itself is Q8Stream; this kernel's own: the choice of operands, the
+// selection (fold_group, seg_fold) and the merge of the four lane quarters of a row at the end.
 template <bool BOUNDS>
 __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob* __restrict__ jobs,
                                                                     const WgJob* __restrict__ wgs, int n_wg,
@@ -2091,32 +2258,23 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
                                                                     float* __restrict__ out_d2, uint32_t* __restrict__ surv_list,
                                                                     unsigned int* __restrict__ surv_count, float prune_r2,
                                                                     float prune_thr, float* __restrict__ bounds_out, unsigned int* __restrict__ exact_flag) {
-    // [buf][256][128 B], tile t in buf t % 3; then [buf][256] accumulator start values (round 6: cinB, 1 KiB per tile)
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[3 * kQTileBytes + 3 * 1024];
-    int wg = blockIdx.x;
-    {  // XCD-aware order, as in match_cand_f16_kernel
-        const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
-        wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-    }
-    // (the whole register file of the SIMD is claimed: see match_screen_i8_kernel and DESIGN.md section 5)
-    asm volatile("v_mov_b32 v255, 0" ::: "v255");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[Q8Stream::kLdsBytes];
+    const int wg = xcd_order(blockIdx.x, n_wg);
+    claim_whole_register_file();
     const WgJob w = wgs[wg];
     const MatchJob jb = jobs[w.job];
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15;
-    const int kq = lane >> 4;
     const int nA = jb.nA, nB = jb.nB;
-    const int rowb = w.row0 + wave * 64;  // this wave's rows: rowb + 16 g + c, every lane quarter kq sees them
     // Round 6: where every row of both sets has an exact integer code (q8_desc_rows) the pass runs on those - same loop, other
     // operands: the code bytes AX / BX and, as the C operand of each column block's first MFMA, the columns' 128 sum p_j
     // (cinB; zeros for the general codes).  The pooled matcher's bounds pass keeps the general codes.
     const bool exact = !BOUNDS && screen_exact(jb);
     if (!BOUNDS && exact && tid == 0) exact_flag[w.job] = 1u;  // (diagnostics: aps_match_screen_exact_jobs)
     const signed char* const opA = exact ? jb.AX : jb.AQ;
-    const signed char* const opB = exact ? jb.BXs : jb.BQ;  // (exact: the columns in ascending order of their divisor)
-    const int* const cin_src = jb.cinBs;
+    // (exact: the columns in ascending order of their divisor)
+    Q8Stream st(lds, exact ? jb.BXs : jb.BQ, jb.cinBs, jb.ncinB, exact, nB);
+    const int lane = st.lane, c = st.c, kq = st.kq, ntiles = st.ntiles;
+    const int rowb = w.row0 + st.wave * 64;  // this wave's rows: rowb + 16 g + c, every lane quarter kq sees them
 
     i32x4 aq[4][2];
 #pragma unroll
@@ -2128,59 +2286,16 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     }
     constexpr int kNone = kScreenNone;
     int d0[4] = {kNone, kNone, kNone, kNone}, d1[4] = {kNone, kNone, kNone, kNone};
-
-    const int ntiles = (nB + kQTN - 1) / kQTN;
-    // DMA pieces: as in match_screen_i8_kernel
-    const int dma_sub = lane >> 3, dma_pos = lane & 7;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    auto issue_piece = [&](int t, int buf, int u) {
-        const int piece = wave * 4 + u;
-        const int lrow = 8 * piece + dma_sub;
-        const int brow = min(t * kQTN + lrow, nB - 1);
-        const signed char* src = opB + (size_t)brow * kDim + ((dma_pos ^ ((lrow >> 1) & 7)) << 4);
-        const uint32_t dst = lds_base + buf * kQTileBytes + piece * 1024;
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(src), "s"(dst)
-            : "memory");
-    };
-    // The accumulators' start values of tile t (cinB, one int per column: 1 KiB per tile) travel with piece 0 of the tile,
-    // issued by wave 0; entries past the set's padded length are clamped to its last four (columns >= nB: masked in the fold).
-    // General codes: the three 1-KiB areas are zero-filled once, below.
-    const int ncin = jb.ncinB;
-    auto issue_cin = [&](int t, int buf) {
-        if (exact && wave == 0) {
-            const int col = min(t * kQTN + 4 * lane, ncin - 4);
-            const int* src = cin_src + col;
-            const uint32_t dst = lds_base + 3 * kQTileBytes + buf * 1024;
-            uint32_t keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(src), "s"(dst)
-                : "memory");
-        }
-    };
+    // general codes: the three 1-KiB areas of start values are zero-filled once
     if (!exact && tid < 192) *reinterpret_cast<i32x4*>(lds + 3 * kQTileBytes + 16 * tid) = i32x4{0, 0, 0, 0};
-    i32x4 acc[2][2][4];  // [block parity][sub-block][row group]
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[p][u][g][e] = kNone;
 
     // The search of a finished block for row group g: the lane's 8 columns, 16 u + 4 kq + r of the block, are folded into the
-    // running maximum of the lane's columns of the TILE (4 v_max3); the tile's last block (LAST) then updates the two best:
+    // running maximum of the lane's columns of the TILE (4 v_max3); the tile's last block then updates the two best:
     // D1 = med3(D0, D1, m), D0 = max(D0, m).  A group is thus the 64 columns a lane holds of a 256-column tile: D1 is the
     // second largest GROUP maximum, which can only be lower than the second largest dot (when a row's two best columns fall
     // into one group of one lane: 64 of ~20 000 columns) - still a bound, and 17 instead of 24 VALU per block, which matters
     // here: a 16x16x64 MFMA holds the SIMD's vector issue for half of its 16 cycles, twice the share of the 32x32x32 form.
-    // `limit` (ragged last tile only) = number of valid columns counted from the block's first.
+    // limit (ragged last tile only) = number of valid columns counted from the block's first.
     int m_run[4] = {kNone, kNone, kNone, kNone};
     // Exact codes: the columns come sorted by their divisor, and every kSeg tiles the integer best two (d0, d1) of the SEGMENT
     // are turned into bounds on I / t_j with the segment's divisor range [tlo of its first tile, thi of its last] and join the
@@ -2211,18 +2326,19 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
             d0[g] = d1[g] = kNone;
         }
     };
-    auto fold_group = [&](auto PAR, auto G, auto MASK, int limit, auto FIRST, auto LAST) __attribute__((always_inline)) {
-        constexpr int par = decltype(PAR)::value, g = decltype(G)::value;
-        constexpr bool mask = decltype(MASK)::value, first = decltype(FIRST)::value, last = decltype(LAST)::value;
+    auto fold_group = [&](auto SL, int col0) __attribute__((always_inline)) {
+        using sl = decltype(SL);
+        constexpr int g = sl::g;
         int v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            v[e] = acc[par][e >> 2][g][e & 3];
-            if (mask) v[e] = (16 * (e >> 2) + 4 * kq + (e & 3)) < limit ? v[e] : kNone;
+            v[e] = st.acc[sl::par][e >> 2][g][e & 3];
+            if (sl::masked) v[e] = (16 * (e >> 2) + 4 * kq + (e & 3)) < nB - col0 ? v[e] : kNone;
         }
-        // (volatile asm: see match_screen_i8_kernel)
+        // (volatile asm: left to itself the compiler sinks the whole search of a tile's eight blocks behind the tile's last
+        // MFMA - nothing needs the result earlier - and then has eight blocks' accumulators alive at once)
         int m = m_run[g];
-        if (first)
+        if (sl::first)
             asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
                          : "=&v"(m)
                          : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
@@ -2231,126 +2347,34 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
                          : "+v"(m)
                          : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
         m_run[g] = m;
-        if (last) {
+        if (sl::last) {
+            // the runner-up of {d0, d1, m} given d0 >= d1, then the new best
             int t0 = d0[g], t1 = d1[g];
             asm volatile("v_med3_i32 %0, %1, %0, %2\n\tv_max_i32 %1, %1, %2" : "+v"(t1), "+v"(t0) : "v"(m));
             d0[g] = t0;
             d1[g] = t1;
         }
     };
-
-    if (ntiles > 0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) issue_piece(0, 0, u);
-        issue_cin(0, 0);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) asm volatile("" ::"v"(aq[g][0]), "v"(aq[g][1]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // per-lane read offsets: slot s of a block = sub-block s >> 1, k-step s & 1: row 16 (s >> 1) + c, chunk (4 (s & 1) + kq)
-    // ^ ((c >> 1) & 7)  (the sub-block's 16 rows leave (row >> 1) & 7 alone)
-    const int hx = (16 * kq) ^ (16 * ((c >> 1) & 7));
-    constexpr int kAhead = 3;
-    auto slot_off = [&](int s) __attribute__((always_inline)) { return (s >> 1) * 16 * kDim + ((64 * (s & 1)) ^ hx); };
-    i32x4 bq[4];
-    // cin[u]: the start values of the lane's four columns 16 u + 4 kq + r of the NEXT block to start (read one block ahead)
-    i32x4 cin[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    const unsigned char* const cin_lds = lds + 3 * kQTileBytes + 16 * kq;
-    if (ntiles > 0) {
-        if (ntiles > 1) {
-            issue_piece(1, 1, 0);
-            issue_cin(1, 1);
+    // (block 0 of tile t has folded the LAST block of tile t - 1: where that completes a segment, the segment joins)
+    // Segments: the FIRST and the LAST tile alone (where columns with an odd divisor end up: they then loosen the bounds of
+    // 256 columns, not of a segment's 2048), kSeg tiles each in between.
+    auto seg_close = [&](int t) __attribute__((always_inline)) {
+        if (exact && t > 0 && (t == 1 || t - seg_first == kSeg || t == ntiles - 1)) {
+            seg_fold(seg_first, t - 1);
+            seg_first = t;
         }
-#pragma unroll
-        for (int s = 0; s < kAhead; ++s) bq[s] = *reinterpret_cast<const i32x4*>(lds + c * kDim + slot_off(s));
-        cin[0] = *reinterpret_cast<const i32x4*>(cin_lds);
-        cin[1] = *reinterpret_cast<const i32x4*>(cin_lds + 64);
-    }
-    int b_cur = 0;  // t % 3
-    auto run_tile = [&](int t, auto MASK) __attribute__((always_inline)) {
-        constexpr bool mask = decltype(MASK)::value;
-        const bool more = t + 1 < ntiles;
-        const bool more2 = t + 2 < ntiles;
-        const int b_nxt = b_cur == 2 ? 0 : b_cur + 1, b_nxt2 = b_nxt == 2 ? 0 : b_nxt + 1;
-        const unsigned char* tile = lds + b_cur * kQTileBytes + c * kDim;
-        const unsigned char* tile_n = lds + b_nxt * kQTileBytes + c * kDim;
-        const unsigned char* cin_t = cin_lds + b_cur * 1024;
-        const unsigned char* cin_n = cin_lds + b_nxt * 1024;
-        b_cur = b_nxt;
-
-        static_for<0, kQBlk>([&](auto CB) {
-            constexpr int cb = decltype(CB)::value;
-            constexpr int kLast = kQBlk - 1;
-            constexpr int par = cb & 1;
-            if (cb == 0 || cb == 2 || cb == 4) {
-                if (more) issue_piece(t + 1, b_nxt, cb / 2 + 1);
-            } else if (cb == kLast) {
-                if (more2) {
-                    issue_piece(t + 2, b_nxt2, 0);
-                    issue_cin(t + 2, b_nxt2);
-                }
-            }
-            const unsigned char* blk = tile + cb * 32 * kDim;
-            const unsigned char* nblk = cb < kLast ? blk + 32 * kDim : tile_n;
-            const bool fetch = cb < kLast || more;
-            const int limit = mask ? nB - (t * kQTN + (cb - 1) * 32) : 0;
-            static_for<0, 4>([&](auto S) {
-                constexpr int s = decltype(S)::value;
-                constexpr int u = s >> 1, ks = s & 1;
-                const i32x4 xq = bq[s & 3];
-                if (s + kAhead < 4) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(blk + slot_off(s + kAhead));
-                } else if (fetch) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(nblk + slot_off(s + kAhead - 4));
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    acc[par][u][g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xq, aq[g][ks], ks == 0 ? cin[u] : acc[par][u][g], 0, 0, 0);
-                // sub-block u's start values are consumed: fetch the next block's (the same tile's, or the next tile's first)
-                if (ks == 1) {
-                    if (cb < kLast)
-                        cin[u] = *reinterpret_cast<const i32x4*>(cin_t + (32 * (cb + 1) + 16 * u) * 4);
-                    else if (more)
-                        cin[u] = *reinterpret_cast<const i32x4*>(cin_n + (16 * u) * 4);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                // the block being searched is the previous one: (t, cb - 1), or the last block of tile t - 1 (never ragged)
-                constexpr bool first = cb == 1, last = cb == 0;
-                if (mask && cb > 0)
-                    fold_group(std::integral_constant<int, par ^ 1>{}, S, std::true_type{}, limit, std::integral_constant<bool, first>{},
-                               std::integral_constant<bool, last>{});
-                else
-                    fold_group(std::integral_constant<int, par ^ 1>{}, S, std::false_type{}, 0, std::integral_constant<bool, first>{},
-                               std::integral_constant<bool, last>{});
-                __builtin_amdgcn_sched_barrier(0);
-            });
-            // (block 0 of this tile has folded the LAST block of tile t - 1: where that completes a segment, the segment joins)
-            // Segments: the FIRST and the LAST tile alone (where columns with an odd divisor end up: they then loosen the bounds of
-            // 256 columns, not of a segment's 2048), kSeg tiles each in between.
-            if (cb == 0 && exact && t > 0 && (t == 1 || t - seg_first == kSeg || t == ntiles - 1)) {
-                seg_fold(seg_first, t - 1);
-                seg_first = t;
-            }
-            if (cb == kLast - 1) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-            }
-        });
     };
+    auto no_hook = [](int) {};
+
+    st.start(aq);
+    // full tiles run unmasked; a ragged last tile (columns >= nB: the DMA re-reads the last row for them) runs the masked copy
     const int nfull = nB / kQTN;
-    for (int t = 0; t < nfull; ++t) run_tile(t, std::false_type{});
+    for (int t = 0; t < nfull; ++t) st.tile<false>(t, aq, no_hook, fold_group, seg_close);
     if (nfull < ntiles) {
-        run_tile(nfull, std::true_type{});
-        const int limit = nB - (nfull * kQTN + (kQBlk - 1) * 32);
-        static_for<0, 4>([&](auto S) {
-            fold_group(std::integral_constant<int, (kQBlk - 1) & 1>{}, S, std::true_type{}, limit, std::false_type{}, std::true_type{});
-        });
+        st.tile<true>(nfull, aq, no_hook, fold_group, seg_close);
+        st.finish<true>(fold_group);
     } else if (ntiles > 0) {
-        static_for<0, 4>([&](auto S) {
-            fold_group(std::integral_constant<int, (kQBlk - 1) & 1>{}, S, std::false_type{}, 0, std::false_type{}, std::true_type{});
-        });
+        st.finish<false>(fold_group);
     }
     if (exact && ntiles > 0) seg_fold(seg_first, ntiles - 1);  // the last segment
     // the four lane quarters of a wave saw disjoint columns of the same rows; quarter kq then decides row group kq
@@ -2391,36 +2415,29 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
 // column) with a certified error bound (match_cand_f16_kernel<LIST>).  With exact integer codes the same sweep runs on the
 // int8 pipe at twice the rate and needs no error analysis: the products are exact, and the screen has left every survivor a
 // threshold (screen_tail) that only the columns which can be its best or second best by the canonical f32 distance reach - a
-// handful per row.  This kernel streams a pooled 512-row survivor tile against its B set exactly like the screening kernel
-// (same LDS image, DMA, hand-over, read-ahead, C operand), compares instead of folding - per (32-column block, row group)
-// the maximum of the lane's eight products against the row's threshold, and only on a hit (rare) the eight values one by
-// one - and appends (column; its position in the B set's divisor-sorted order) to the row's candidate list: cand[p * kCandCap ..], count in cand_cnt[p], p = the row's position
-// in the pooled survivor list (counts beyond the capacity are kept: such a row goes to the exact-f32 fallback).  match_rescore_kernel then evaluates the canonical f32
-// distance of every candidate and writes the row's (idx, d1, d2).  Whole register file claimed like the screening kernels.
+// handful per row.  This kernel streams a pooled 512-row survivor tile against its B set through the screening kernel's
+// Q8Stream and compares instead of folding - per (32-column block, row group) the maximum of the lane's eight products
+// against the row's threshold, and only on a hit (rare) the eight values one by one - and appends (column; its position in
+// the B set's divisor-sorted order) to the row's candidate list: cand[p * kCandCap ..], count in cand_cnt[p], p = the row's
+// position in the pooled survivor list (counts beyond the capacity are kept: such a row goes to the exact-f32 fallback).
+// match_rescore_kernel then evaluates the canonical f32 distance of every candidate and writes the row's (idx, d1, d2).
 constexpr int kCandCap = 32;
 
 __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __restrict__ jobs, const WgJob* __restrict__ wgs, int n_wg,
                                                             const uint32_t* __restrict__ row_list, const int* __restrict__ list_job,
                                                             const float* __restrict__ thr_slot, uint32_t* __restrict__ cand,
                                                             unsigned int* __restrict__ cand_cnt) {
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[3 * kQTileBytes + 3 * 1024];
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[Q8Stream::kLdsBytes];
     __shared__ unsigned int s_cnt[512];  // candidates found so far per row of the tile (the four lane quarters of a wave share a row)
     s_cnt[threadIdx.x] = 0u;
-    int wg = blockIdx.x;
-    {
-        const int q = n_wg / 8, r = n_wg % 8, x = wg % 8;
-        wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + wg / 8;
-    }
-    asm volatile("v_mov_b32 v255, 0" ::: "v255");  // (nothing shares a SIMD with int8-MFMA waves)
+    const int wg = xcd_order(blockIdx.x, n_wg);
+    claim_whole_register_file();
     const WgJob w = wgs[wg];
     const MatchJob jb = jobs[w.job];  // (any job of the tile's group: the B set is common)
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15;
-    const int kq = lane >> 4;
     const int nB = jb.nB;
-    constexpr int kNone = kScreenNone;
+    Q8Stream st(lds, jb.BXs, jb.cinBs, jb.ncinB, true, nB);
+    const int wave = st.wave, c = st.c, kq = st.kq;
     // this lane's four rows: list entries w.row0 + wave * 64 + 16 g + c (entries past the tile's end: no row, nothing can hit)
     i32x4 aq[4][2];
     // thr[g]: the row's threshold in accumulator units for the tile being streamed, thr_prev[g]: for the tile before (the last
@@ -2452,61 +2469,34 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
         for (int ks = 0; ks < 2; ++ks)
             aq[g][ks] = *reinterpret_cast<const i32x4*>(jr.AX + (size_t)arow * kDim + 64 * ks + 16 * kq);
     }
-    const int ntiles = (nB + kQTN - 1) / kQTN;
-    const int dma_sub = lane >> 3, dma_pos = lane & 7;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    auto issue_piece = [&](int t, int buf, int u) {
-        const int piece = wave * 4 + u;
-        const int lrow = 8 * piece + dma_sub;
-        const int brow = min(t * kQTN + lrow, nB - 1);
-        const signed char* src = jb.BXs + (size_t)brow * kDim + ((dma_pos ^ ((lrow >> 1) & 7)) << 4);
-        const uint32_t dst = lds_base + buf * kQTileBytes + piece * 1024;
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(src), "s"(dst)
-            : "memory");
-    };
-    const int ncin = jb.ncinB;
-    auto issue_cin = [&](int t, int buf) {
-        if (wave == 0) {
-            const int col = min(t * kQTN + 4 * lane, ncin - 4);
-            const int* src = jb.cinBs + col;
-            const uint32_t dst = lds_base + 3 * kQTileBytes + buf * 1024;
-            uint32_t keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(src), "s"(dst)
-                : "memory");
+    // this tile's thresholds (its smallest divisor: wave-uniform); the previous tile's stay for the first block's test
+    auto next_thr = [&](int t) __attribute__((always_inline)) {
+        const float tlo = jb.tscB[t].z;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            thr_prev[g] = thr[g];
+            thr[g] = tile_thr(g, tlo);
         }
     };
-    i32x4 acc[2][2][4];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[p][u][g][e] = kNone;
     // the test of a finished block for row group g: col0 = first column of the block; columns >= nB never count
-    auto test_group = [&](auto PAR, auto G, int col0, const int (&thr)[4]) __attribute__((always_inline)) {
-        constexpr int par = decltype(PAR)::value, g = decltype(G)::value;
+    auto test_group = [&](auto SL, int col0) __attribute__((always_inline)) {
+        using sl = decltype(SL);
+        constexpr int g = sl::g;
+        if (sl::prev && col0 < 0) return;  // (block 0 of tile 0: nothing is finished yet)
+        const int (&th)[4] = sl::prev ? thr_prev : thr;
         int v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = acc[par][e >> 2][g][e & 3];
+        for (int e = 0; e < 8; ++e) v[e] = st.acc[sl::par][e >> 2][g][e & 3];
         int m;
         asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
                      : "=&v"(m)
                      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
-        if (__builtin_expect(__any(m >= thr[g]), 0)) {
+        if (__builtin_expect(__any(m >= th[g]), 0)) {
             // (one emission site behind a bit mask of the lane's hits: with the eight tests unrolled around eight atomics the
             // kernel's loop body outgrew the instruction cache - 32 call sites per tile - and ran at half the screen's rate)
             unsigned hits = 0u;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) hits |= (v[e] >= thr[g] ? 1u : 0u) << e;
+            for (int e = 0; e < 8; ++e) hits |= (v[e] >= th[g] ? 1u : 0u) << e;
 #pragma unroll 1
             while (hits) {
                 const int e = __builtin_ctz(hits);
@@ -2521,101 +2511,9 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
             }
         }
     };
-    if (ntiles > 0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) issue_piece(0, 0, u);
-        issue_cin(0, 0);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) asm volatile("" ::"v"(aq[g][0]), "v"(aq[g][1]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int hx = (16 * kq) ^ (16 * ((c >> 1) & 7));
-    constexpr int kAhead = 3;
-    auto slot_off = [&](int s) __attribute__((always_inline)) { return (s >> 1) * 16 * kDim + ((64 * (s & 1)) ^ hx); };
-    i32x4 bq[4];
-    i32x4 cin[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    const unsigned char* const cin_lds = lds + 3 * kQTileBytes + 16 * kq;
-    if (ntiles > 0) {
-        if (ntiles > 1) {
-            issue_piece(1, 1, 0);
-            issue_cin(1, 1);
-        }
-#pragma unroll
-        for (int s = 0; s < kAhead; ++s) bq[s] = *reinterpret_cast<const i32x4*>(lds + c * kDim + slot_off(s));
-        cin[0] = *reinterpret_cast<const i32x4*>(cin_lds);
-        cin[1] = *reinterpret_cast<const i32x4*>(cin_lds + 64);
-    }
-    int b_cur = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const bool more = t + 1 < ntiles;
-        const bool more2 = t + 2 < ntiles;
-        const int b_nxt = b_cur == 2 ? 0 : b_cur + 1, b_nxt2 = b_nxt == 2 ? 0 : b_nxt + 1;
-        const unsigned char* tile = lds + b_cur * kQTileBytes + c * kDim;
-        const unsigned char* tile_n = lds + b_nxt * kQTileBytes + c * kDim;
-        const unsigned char* cin_t = cin_lds + b_cur * 1024;
-        const unsigned char* cin_n = cin_lds + b_nxt * 1024;
-        b_cur = b_nxt;
-        {  // this tile's thresholds (its smallest divisor: wave-uniform); the previous tile's stay for the first block's test
-            const float tlo = jb.tscB[t].z;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                thr_prev[g] = thr[g];
-                thr[g] = tile_thr(g, tlo);
-            }
-        }
-        static_for<0, kQBlk>([&](auto CB) {
-            constexpr int cb = decltype(CB)::value;
-            constexpr int kLast = kQBlk - 1;
-            constexpr int par = cb & 1;
-            if (cb == 0 || cb == 2 || cb == 4) {
-                if (more) issue_piece(t + 1, b_nxt, cb / 2 + 1);
-            } else if (cb == kLast) {
-                if (more2) {
-                    issue_piece(t + 2, b_nxt2, 0);
-                    issue_cin(t + 2, b_nxt2);
-                }
-            }
-            const unsigned char* blk = tile + cb * 32 * kDim;
-            const unsigned char* nblk = cb < kLast ? blk + 32 * kDim : tile_n;
-            const bool fetch = cb < kLast || more;
-            // the block being tested is the previous one: (t, cb - 1), or the last block of tile t - 1
-            const int col_prev = cb > 0 ? t * kQTN + (cb - 1) * 32 : (t - 1) * kQTN + kLast * 32;
-            static_for<0, 4>([&](auto S) {
-                constexpr int s = decltype(S)::value;
-                constexpr int u = s >> 1, ks = s & 1;
-                const i32x4 xq = bq[s & 3];
-                if (s + kAhead < 4) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(blk + slot_off(s + kAhead));
-                } else if (fetch) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(nblk + slot_off(s + kAhead - 4));
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    acc[par][u][g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xq, aq[g][ks], ks == 0 ? cin[u] : acc[par][u][g], 0, 0, 0);
-                if (ks == 1) {
-                    if (cb < kLast)
-                        cin[u] = *reinterpret_cast<const i32x4*>(cin_t + (32 * (cb + 1) + 16 * u) * 4);
-                    else if (more)
-                        cin[u] = *reinterpret_cast<const i32x4*>(cin_n + (16 * u) * 4);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (cb > 0)
-                    test_group(std::integral_constant<int, par ^ 1>{}, S, col_prev, thr);
-                else if (t > 0)
-                    test_group(std::integral_constant<int, par ^ 1>{}, S, col_prev, thr_prev);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-            if (cb == kLast - 1) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-            }
-        });
-    }
-    if (ntiles > 0) {
-        const int col_last = (ntiles - 1) * kQTN + (kQBlk - 1) * 32;
-        static_for<0, 4>([&](auto S) { test_group(std::integral_constant<int, (kQBlk - 1) & 1>{}, S, col_last, thr); });
-    }
+    st.start(aq);
+    for (int t = 0; t < st.ntiles; ++t) st.tile<false>(t, aq, next_thr, test_group, [](int) {});
+    if (st.ntiles > 0) st.finish<false>(test_group);
     __syncthreads();
     if (tid < w.list_cnt) cand_cnt[w.row0 + tid] = s_cnt[tid];  // (row e of the tile = wave e / 64, group (e % 64) / 16, c = e % 16: s_cnt's order)
 }
@@ -2669,15 +2567,6 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(const MatchJob* __re
 // ------------------------------------------------------------------------------------------------
 // ratio / threshold / uniqueness  (matchFeaturesScratch.m:170-211)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t order_f32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unorder_f32(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
-
 struct FilterJob {
     int64_t row_off;  // first row slot (same as MatchJob::out_off)
     int64_t col_off;  // first slot of this job's B columns in the winner table
@@ -2712,7 +2601,7 @@ __global__ void filter_mark_kernel(const FilterJob* __restrict__ fj, int njobs, 
     if (keep) {  // (the row -> job search, eleven dependent loads, only for the few rows that pass)
         const FilterJob f = fj[find_job(fj, njobs, slot)];
         const uint32_t row = (uint32_t)(slot - f.row_off);
-        key = ((unsigned long long)order_f32(d1[slot]) << 32) | row;
+        key = ((unsigned long long)ord_f32(d1[slot]) << 32) | row;
         if (unique) atomicMin(&winner[f.col_off + (idx[slot] - 1)], key);
     }
     keys[slot] = key;
@@ -2780,7 +2669,7 @@ __global__ void filter_emit_kernel(const FilterJob* __restrict__ fj, int njobs,
         const uint32_t row = (uint32_t)(key & 0xffffffffu);
         o1[base + e] = row + 1;
         o2[base + e] = idx[f.row_off + row];
-        metric[base + e] = unorder_f32((uint32_t)(key >> 32));
+        metric[base + e] = unord_f32((uint32_t)(key >> 32));
     }
 }
 
@@ -3329,35 +3218,37 @@ static bool screen_shape_32() {
 }
 
 // The co-residency rule: waves of other kernels that shared a SIMD with int8-MFMA waves came back with
-// different bits, so the screening kernels claim the SIMD's whole register file - 512 threads per workgroup = two waves
-// per SIMD, 256 registers each (the `v_mov_b32 v255` in their first lines).  That holds only while the compiler really
-// allocates 256: checked against the loaded code object before the first launch of a process, and by tests/test_abi.py
-// against the code object's metadata on the CPU.
-static void screen_regs(int shape32, int bounds, int* num_regs, int* max_threads) {
-    hipFuncAttributes fa;
-    const void* f = shape32 ? (bounds ? reinterpret_cast<const void*>(&match_screen_i8_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8_kernel<false>))
-                            : (bounds ? reinterpret_cast<const void*>(&match_screen_i8x16_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8x16_kernel<false>));
-    APS_HIP(hipFuncGetAttributes(&fa, f));
-    *num_regs = fa.numRegs;
-    *max_threads = fa.maxThreadsPerBlock;
+// different bits, so the int8 kernels claim the SIMD's whole register file - 512 threads per workgroup = two waves per
+// SIMD, 256 registers each (claim_whole_register_file).  That holds only while the compiler really allocates 256: checked
+// against the loaded code object before a kernel's first launch in a process, and by tests/test_abi.py against the code
+// object's metadata on the CPU.
+static const void* screen_kernel(bool shape32, bool bounds) {
+    return shape32 ? (bounds ? reinterpret_cast<const void*>(&match_screen_i8_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8_kernel<false>))
+                   : (bounds ? reinterpret_cast<const void*>(&match_screen_i8x16_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8x16_kernel<false>));
 }
-static void require_whole_simd(int shape32, int bounds = 0) {
-    static std::atomic<int> ok[4];  // (one code object for every device of the process: the answer is the same on all of them)
-    if (ok[2 * shape32 + bounds].load(std::memory_order_relaxed)) return;
-    int regs = 0, thr = 0;
-    screen_regs(shape32, bounds, &regs, &thr);
-    APS_REQUIRE((regs + 7) / 8 * 8 >= 256, APS_E_INTERNAL,
-                "the int8 screening kernel holds %d registers per lane, not 256: other kernels' waves could share its SIMDs (DESIGN.md section 5)", regs);
-    ok[2 * shape32 + bounds].store(1, std::memory_order_relaxed);
-}
-static void require_whole_simd_list() {  // (the same rule for the exact list pass)
-    static std::atomic<int> ok{0};
-    if (ok.load(std::memory_order_relaxed)) return;
+static void require_whole_simd(const void* kernel, const char* what) {
+    static std::mutex mu;  // (one code object for every device of the process: the answer is the same on all of them)
+    static std::map<const void*, bool> ok;
+    std::lock_guard<std::mutex> lock(mu);
+    if (ok[kernel]) return;
     hipFuncAttributes fa;
-    APS_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&match_list_i8_kernel)));
+    APS_HIP(hipFuncGetAttributes(&fa, kernel));
     APS_REQUIRE((fa.numRegs + 7) / 8 * 8 >= 256, APS_E_INTERNAL,
-                "the int8 list kernel holds %d registers per lane, not 256: other kernels' waves could share its SIMDs (DESIGN.md section 5)", fa.numRegs);
-    ok.store(1, std::memory_order_relaxed);
+                "the int8 %s kernel holds %d registers per lane, not 256: other kernels' waves could share its SIMDs (DESIGN.md section 5)", what, fa.numRegs);
+    ok[kernel] = true;
+}
+// The screening pass over the dense tiles dbw in the selected MFMA shape (APS_SCREEN_SHAPE); BOUNDS: the pooled matcher's form.
+template <bool BOUNDS>
+static void launch_screen(const MatchJob* djobs, const WgJob* dbw, size_t n_bw, uint32_t* idx, float* d1, float* d2, uint32_t* surv_list,
+                          unsigned int* surv_count, float prune_r2, float prune_thr, float* bounds, unsigned int* exact_flag) {
+    const bool shape32 = screen_shape_32();
+    require_whole_simd(screen_kernel(shape32, BOUNDS), "screening");
+    if (shape32)
+        match_screen_i8_kernel<BOUNDS><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list, surv_count, prune_r2,
+                                                                              prune_thr, bounds);
+    else
+        match_screen_i8x16_kernel<BOUNDS><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list, surv_count, prune_r2,
+                                                                                 prune_thr, bounds, exact_flag);
 }
 // tile k of a dense pass = rows [r, r + rows_per_tile) of job j, where off[j] <= k < off[j + 1] and r = (k - off[j]) * rows_per_tile
 __global__ void expand_tiles_kernel(const int* __restrict__ off, int n_jobs, int n_tiles, int rows_per_tile, WgJob* __restrict__ out) {
@@ -3410,7 +3301,7 @@ static std::vector<WgJob> exact_list_pass(const std::vector<MatchJob>& jobs, con
     APS_HIP(hipMemsetAsync(cand_cnt, 0, n_x * sizeof(unsigned int), stream()));
     {
         Prof prof("match_list_i8");
-        require_whole_simd_list();
+        require_whole_simd(reinterpret_cast<const void*>(&match_list_i8_kernel), "list");
         match_list_i8_kernel<<<(unsigned)lx.size(), 512, 0, stream()>>>(djobs, dlx, (int)lx.size(), pool_x, pool_job_x, d1, cand, cand_cnt);
     }
     {
@@ -3434,14 +3325,7 @@ static void screen_and_survivor_passes(const std::vector<MatchJob>& jobs, const 
     APS_HIP(hipMemsetAsync(surv_count, 0, 2 * jobs.size() * sizeof(unsigned int), stream()));
     {
         Prof prof("match_screen_i8");
-        require_whole_simd(screen_shape_32() ? 1 : 0);
-        if (screen_shape_32())
-            match_screen_i8_kernel<false><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list,
-                                                                                 surv_count, prune_r2, prune_thr, nullptr);
-        else
-            match_screen_i8x16_kernel<false><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list,
-                                                                                    surv_count, prune_r2, prune_thr, nullptr,
-                                                                                    surv_count.get() + jobs.size());
+        launch_screen<false>(djobs, dbw, n_bw, idx, d1, d2, surv_list, surv_count, prune_r2, prune_thr, nullptr, surv_count.get() + jobs.size());
     }
     check_launch("match_screen_i8_kernel");
     const auto S0 = std::chrono::steady_clock::now();
@@ -4001,13 +3885,7 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
         APS_HIP(hipMemcpyAsync(dbw, bw.data(), bw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
         {
             Prof prof("match_screen_i8_bounds");
-            require_whole_simd(screen_shape_32() ? 1 : 0, 1);
-            if (screen_shape_32())
-                match_screen_i8_kernel<true><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), nullptr, nullptr, nullptr,
-                                                                                         nullptr, nullptr, 0.f, 0.f, bounds);
-            else
-                match_screen_i8x16_kernel<true><<<(unsigned)bw.size(), 512, 0, stream()>>>(djobs, dbw, (int)bw.size(), nullptr, nullptr, nullptr,
-                                                                                            nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
+            launch_screen<true>(djobs, dbw, bw.size(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
         }
         check_launch("match_screen_i8_kernel (bounds)");
         APS_HIP(hipStreamSynchronize(stream()));  // djobs / dbw go out of scope
@@ -4451,6 +4329,9 @@ extern "C" int aps_match_screen_kernel_regs(int shape, int bounds_pass, int* num
     return guarded([&] {
         APS_REQUIRE(num_regs && max_threads_per_block && (shape == 16 || shape == 32), APS_E_ARG, "shape is 16 or 32; the outputs must not be null");
         ctx();
-        screen_regs(shape == 32, bounds_pass != 0, num_regs, max_threads_per_block);
+        hipFuncAttributes fa;
+        APS_HIP(hipFuncGetAttributes(&fa, screen_kernel(shape == 32, bounds_pass != 0)));
+        *num_regs = fa.numRegs;
+        *max_threads_per_block = fa.maxThreadsPerBlock;
     });
 }

@@ -700,6 +700,50 @@ def test_int8_screen_exact_integer_codes(fm, gpu, monkeypatch):
             p += 1
 
 
+@pytest.mark.parametrize("n2", [3, 257, 513, 1025])
+def test_int8_screen_32x32x32_shape_ragged_column_counts(fm, monkeypatch, n2):
+    """APS_SCREEN_SHAPE=32 (the superseded v_mfma_i32_32x32x32_i8 kernel, which shares its DMA and workgroup order with the
+    default one) at small sizes: 700 rows = one full and one ragged row tile, column counts below one block, and one past
+    one, two and four tiles.  Its lists equal the oracle's and the default shape's, indices and metric bits alike."""
+    rng = np.random.default_rng(300 + n2)
+    a, b, _, _ = planted_pair(rng, 700, n2, min(n2, 200), noise=0.03)
+    try:
+        for ratio, thr, unique in ((0.6, 3.5, True), (0.9, 0.5, False)):
+            monkeypatch.delenv("APS_SCREEN_SHAPE", raising=False)
+            _screen_ab(fm, monkeypatch, a, b, ratio, thr, unique)
+            m, met = fm.matchFeaturesScratch(a, b, MatchThreshold=thr, MaxRatio=ratio, Unique=unique)
+            monkeypatch.setenv("APS_SCREEN_SHAPE", "32")
+            _screen_ab(fm, monkeypatch, a, b, ratio, thr, unique)
+            m32, met32 = fm.matchFeaturesScratch(a, b, MatchThreshold=thr, MaxRatio=ratio, Unique=unique)
+            assert np.array_equal(m32, m) and np.array_equal(bits(met32), bits(met)), (ratio, thr, unique)
+    finally:
+        monkeypatch.delenv("APS_SCREEN_SHAPE", raising=False)
+
+
+@pytest.mark.parametrize("n2", [512, 768, 2304, 2305, 2561, 2817])
+def test_int8_exact_codes_tile_and_segment_boundaries(fm, gpu, monkeypatch, n2):
+    """The exact-code screen folds its integer best two into f32 bounds per SEGMENT of tiles: the first tile alone (closed
+    at t == 1), eight tiles each after that (t - seg_first == kSeg), the last tile alone (t == ntiles - 1); the stream
+    itself wraps its three LDS buffers every third tile.  2, 3, 9, 10, 11 and 12 tiles of 256 columns (one and 257 columns
+    into the last where ragged) cover each closing rule on its own and together, for the screen and for the exact list
+    pass that follows it.  Seed 400 + n2: both sets are integer-valued with divisors within 2 % of each other, so the job
+    takes the exact codes (a property of the generator: asserted below, and it holds before this test existed)."""
+    rng = np.random.default_rng(400 + n2)
+    a, b, _, _ = planted_pair(rng, 700, n2, 200, noise=0.03, unit=False)
+    try:
+        for ratio, thr, unique in ((0.6, 3.5, True), (0.9, 0.5, False)):
+            monkeypatch.delenv("APS_MATCH_NO_EXACT", raising=False)
+            _screen_ab(fm, monkeypatch, a, b, ratio, thr, unique)
+            fm.matchFeaturesScratch(a, b, MatchThreshold=thr, MaxRatio=ratio, Unique=unique)
+            assert _exact_jobs(gpu) == (1, 1)
+            monkeypatch.setenv("APS_MATCH_NO_EXACT", "1")
+            _screen_ab(fm, monkeypatch, a, b, ratio, thr, unique)
+            fm.matchFeaturesScratch(a, b, MatchThreshold=thr, MaxRatio=ratio, Unique=unique)
+            assert _exact_jobs(gpu) == (1, 0)
+    finally:
+        monkeypatch.delenv("APS_MATCH_NO_EXACT", raising=False)
+
+
 def test_int8_screen_is_off_for_non_finite_sets(fm, monkeypatch):
     """A NaN or an infinity in a set makes every bound of the screen meaningless: such jobs must take the f16 / f32 path
     for every row (the set's max ||x||^2 is not finite, which switches the screen off)."""
