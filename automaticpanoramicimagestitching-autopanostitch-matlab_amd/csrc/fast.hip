@@ -6,16 +6,23 @@
 // a NumPy restatement (tests/fast_mirror.py) reproduces the outputs bit for bit: no device transcendental, no float summation.
 // The pattern's f64 layout is rounded to integer tables on the host, once (aps_freak_pattern hands them to the tests).
 //
-// Chain of one call (no host read-back until the final count; every grid is a capacity grid):
-//   integral_image        the u8 gray plane, stored once, and the exact 32-bit integral image (integral_dev.h, shared with surf.hip)
-//   fast_detect_kernel    64 x 8 tile of that plane (+4 halo: 3 for the ring, 1 for suppression) into LDS, the FAST-9 score of the tile
-//                         (+1 halo) into LDS, strict 3 x 3 maximum; writes the plane of kept scores (0 = no corner)
-//   maximum of that plane (rocprim, integers) = s_max of the quality gate
+// Chain of one call (no host read-back until the final count; every grid is a capacity grid).  The call works on a plan of 1..16
+// levels (FastPlan; aps_fast_extract's plan is level 0 alone, aps_fast_extract_pyramid's is DESIGN.md "FAST/FREAK scale pyramid");
+// the planes, score planes, integral images and bitmap words of the levels lie packed one after the other:
+//   integral_image        level 0: the u8 gray plane, stored once, and the exact 32-bit integral image (integral_dev.h, shared with
+//                         surf.hip); level l >= 1: the integral image of the resampled plane
+//   fast_resample_kernel  level l >= 1 from level l - 1: bilinear, half-pixel centres, 8-bit weights, integers only (one launch per
+//                         level, each reads the one before)
+//   fast_detect_kernel    64 x 8 tile of a level's plane (+4 halo: 3 for the ring, 1 for suppression) into LDS, the FAST-9 score of the
+//                         tile (+1 halo) into LDS, strict 3 x 3 maximum; writes the plane of kept scores (0 = no corner); one launch
+//                         over the tiles of all levels
+//   maximum of each level's score plane (rocprim, integers) = that level's s_max of the quality gate
 //   fast_gate_kernel      quality gate per pixel; one ballot = one 64-bit word of the candidate bitmap, whose bit order IS the
-//                         canonical feature order (row, col)
-//   exclusive scan of the words' popcounts (rocprim), fast_emit_kernel (ordered compaction, no atomics, no sort)
-//   freak_keypoint_kernel one wave per keypoint: 43 box sums, 45-pair orientation moment, bin, 43 box sums on the bin's table,
-//                         64 lanes x 8 tests = 512 bits; lane = output byte
+//                         canonical feature order (level, row, col)
+//   exclusive scan of the words' popcounts (rocprim), fast_emit_kernel (ordered compaction, no atomics, no sort; the level is
+//                         decoded from the word's offset)
+//   freak_keypoint_kernel one wave per keypoint: 43 box sums on its level's integral image, 45-pair orientation moment, bin, 43 box
+//                         sums on the bin's table, 64 lanes x 8 tests = 512 bits; lane = output byte
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +41,27 @@ constexpr int kTW = 64, kTH = 8;  // detection tile: a wave's row of it is one r
 constexpr int kHalo = 4;          // ring radius 3 + 1 for the suppression's neighbours
 constexpr int kFields = 43, kBins = 256, kPairs = 512, kOriPairs = 45;
 constexpr double kPatternScale = 22.0;
+constexpr int kMaxLevels = 16;
+constexpr int kRW = 64, kRH = 32;  // resampling tile: a wave's row of it is one row of 64 pixels
+
+// ---- the plan: what every kernel knows about the levels (a kernel argument, by value) -------------------------------------
+struct FastLevel {
+    int h, w, wpr;           // plane size; bitmap words per row = detection tiles per row (both span 64 pixels)
+    unsigned int tile0;      // first detection tile of this level
+    unsigned int word0;      // first bitmap word: h rows of wpr words
+    long long plane0;        // first byte of the u8 plane (and of the plane of kept scores)
+    long long integ0;        // first element of the (h + 1) x (w + 1) integral image
+};
+struct FastPlan {
+    int n;
+    FastLevel lv[kMaxLevels];
+};
+// the level that holds item q of a packed sequence (tiles or words): `first` is the member of FastLevel that starts it
+__device__ __forceinline__ int level_of(const FastPlan& P, unsigned int FastLevel::*first, unsigned int q) {
+    int l = 0;
+    while (l + 1 < P.n && q >= P.lv[l + 1].*first) ++l;
+    return l;
+}
 
 // ---- the pattern: f64 layout -> integer tables (host, once) ---------------------------------------------------------
 struct FreakHost {
@@ -157,12 +185,55 @@ const FreakDev& dev_pattern() {
 constexpr int kRingDx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
 constexpr int kRingDy[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
 
-__global__ __launch_bounds__(256) void fast_detect_kernel(const uint8_t* __restrict__ gray, int h, int w, int thr, int margin,
-                                                          uint8_t* __restrict__ kept) {
+// dst (hd x wd) from src (hs x ws), hd <= hs, wd <= ws: the contract's bilinear resampling.  The first 96 threads of a 64 x 32 tile
+// work out its 64 column and 32 row entries (first tap, 8-bit weight), one 64-bit division each; then a wave takes a row at a time.
+__global__ __launch_bounds__(256) void fast_resample_kernel(const uint8_t* __restrict__ src, int hs, int ws, uint8_t* __restrict__ dst,
+                                                            int hd, int wd) {
+    __shared__ int2 s_x[kRW], s_y[kRH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = blockIdx.x * kRW, y0 = blockIdx.y * kRH;
+    if (tid < kRW + kRH) {
+        const bool col = tid < kRW;
+        const long long i = col ? x0 + tid : y0 + tid - kRW, ns = col ? ws : hs, nd = col ? wd : hd;
+        int2 e = make_int2(0, 0);
+        if (i < nd) {
+            const long long X = (2 * i + 1) * ns - nd;  // >= 0, as ns >= nd
+            const long long t0 = X / (2 * nd), f = X - 2 * nd * t0;
+            e = make_int2((int)t0, (int)(256 * f / (2 * nd)));
+        }
+        if (col)
+            s_x[tid] = e;
+        else
+            s_y[tid - kRW] = e;
+    }
+    __syncthreads();
+    const int x = x0 + lane;
+    if (x >= wd) return;
+    const int2 ex = s_x[lane];
+    const int xa = min(ex.x, ws - 1), xb = min(ex.x + 1, ws - 1);
+    const unsigned int wx = (unsigned int)ex.y;
+    for (int r = wave; r < kRH; r += 4) {
+        const int y = y0 + r;
+        if (y >= hd) break;  // (uniform in the wave)
+        const int2 ey = s_y[r];
+        const size_t ra = (size_t)min(ey.x, hs - 1) * ws, rb = (size_t)min(ey.x + 1, hs - 1) * ws;
+        const unsigned int wy = (unsigned int)ey.y;
+        const unsigned int top = (256u - wx) * src[ra + xa] + wx * src[ra + xb], bot = (256u - wx) * src[rb + xa] + wx * src[rb + xb];
+        dst[(size_t)y * wd + x] = (uint8_t)(((256u - wy) * top + wy * bot + 32768u) >> 16);
+    }
+}
+
+__global__ __launch_bounds__(256) void fast_detect_kernel(const uint8_t* __restrict__ planes, const FastPlan P, int thr, int margin,
+                                                          uint8_t* __restrict__ kept_all) {
     __shared__ uint8_t G[kTH + 2 * kHalo][kTW + 2 * kHalo];
     __shared__ uint8_t S[kTH + 2][kTW + 2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const FastLevel& L = P.lv[level_of(P, &FastLevel::tile0, blockIdx.x)];
+    const unsigned int tile = blockIdx.x - L.tile0;
+    const int h = L.h, w = L.w;
+    const int x0 = (int)(tile % L.wpr) * kTW, y0 = (int)(tile / L.wpr) * kTH;
+    const uint8_t* __restrict__ gray = planes + L.plane0;
+    uint8_t* __restrict__ kept = kept_all + L.plane0;
     constexpr int kGW = kTW + 2 * kHalo, kGN = (kTH + 2 * kHalo) * kGW;
     for (int e = tid; e < kGN; e += 256) {
         const int r = e / kGW, cc = e % kGW, y = y0 - kHalo + r, x = x0 - kHalo + cc;
@@ -212,32 +283,42 @@ struct U8ToU32 {
     __host__ __device__ unsigned int operator()(uint8_t v) const { return v; }
 };
 
-// keep iff s * q_den >= s_max * q_num; one wave per row segment of 64 pixels, its ballot is the bitmap word
-__global__ __launch_bounds__(256) void fast_gate_kernel(const uint8_t* __restrict__ kept, int h, int w, int wpr,
+// keep iff s * q_den >= s_max * q_num, s_max being the level's; one wave per bitmap word = row segment of 64 pixels, its ballot is the word
+__global__ __launch_bounds__(256) void fast_gate_kernel(const uint8_t* __restrict__ kept, const FastPlan P, unsigned int n_words,
                                                         const unsigned int* __restrict__ d_smax, unsigned int q_num, unsigned int q_den,
                                                         unsigned long long* __restrict__ bitmap) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int y = blockIdx.y * 4 + wave, x = blockIdx.x * 64 + lane;
-    if (y >= h) return;  // (uniform in the wave)
-    const unsigned long long smax = *d_smax;
-    const unsigned long long s = x < w ? kept[(size_t)y * w + x] : 0;
+    const int lane = threadIdx.x & 63;
+    const unsigned int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (q >= n_words) return;  // (uniform in the wave)
+    const int l = level_of(P, &FastLevel::word0, q);
+    const FastLevel& L = P.lv[l];
+    const unsigned int ql = q - L.word0;
+    const int y = (int)(ql / L.wpr), x = (int)(ql % L.wpr) * 64 + lane;
+    const unsigned long long smax = d_smax[l];
+    const unsigned long long s = x < L.w ? kept[L.plane0 + (size_t)y * L.w + x] : 0;
     const unsigned long long mask = __ballot(s > 0 && s * q_den >= smax * q_num);
-    if (lane == 0) bitmap[(size_t)y * wpr + blockIdx.x] = mask;
+    if (lane == 0) bitmap[q] = mask;
 }
 
-// Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (row, col).
+struct Keypoint {
+    int y, x, level;
+};
+
+// Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (level, row, col).
 __global__ __launch_bounds__(256) void fast_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
-                                                        long long n_words, int wpr, int2* __restrict__ kps, unsigned int kcap) {
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+                                                        const FastPlan P, unsigned int n_words, Keypoint* __restrict__ kps, unsigned int kcap) {
+    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_words) return;
     unsigned long long bits = bitmap[q];
     if (!bits) return;
     unsigned int pos = prefix[q];
-    const int y = (int)(q / wpr), xw = (int)(q % wpr) * 64;
+    const int l = level_of(P, &FastLevel::word0, q);
+    const unsigned int ql = q - P.lv[l].word0;
+    const int y = (int)(ql / P.lv[l].wpr), xw = (int)(ql % P.lv[l].wpr) * 64;
     while (bits) {
         const int k = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
-        if (pos < kcap) kps[pos] = make_int2(y, xw + k);
+        if (pos < kcap) kps[pos] = Keypoint{y, xw + k, l};
         ++pos;
     }
 }
@@ -258,8 +339,8 @@ __device__ __forceinline__ long long wave_max(long long v) {
 }
 
 // One wave per keypoint.  Every wave of the capacity grid passes every barrier; the ones beyond the count do no work.
-__global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __restrict__ I, int w, const FreakDev* __restrict__ tb,
-                                                             const uint8_t* __restrict__ kept, const int2* __restrict__ kps,
+__global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __restrict__ integ, const FastPlan P, const FreakDev* __restrict__ tb,
+                                                             const uint8_t* __restrict__ kept, const Keypoint* __restrict__ kps,
                                                              const unsigned int* __restrict__ d_total, unsigned int kcap,
                                                              uint8_t* __restrict__ desc, int desc_layout, long long ldd,
                                                              double* __restrict__ loc, long long ldl, float* __restrict__ aux) {
@@ -268,14 +349,16 @@ __global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __r
     const unsigned int kidx = blockIdx.x * 4 + wave;
     const unsigned int total = min(*d_total, kcap);
     const bool active = kidx < total;
-    const size_t ws = (size_t)w + 1;
-    int2 kp = make_int2(0, 0);
+    Keypoint kp{0, 0, 0};
     if (active) kp = kps[kidx];
+    const FastLevel& L = P.lv[__builtin_amdgcn_readfirstlane(kp.level)];  // (one keypoint per wave)
+    const uint32_t* __restrict__ I = integ + L.integ0;
+    const size_t ws = (size_t)L.w + 1;
     // the 43 box sums on the table of `bin`, one field per lane (the margin keeps every box inside the image)
     auto sums = [&](int bin) {
         if (active && lane < kFields) {
             const char4 f = tb->field[bin][lane];
-            const int cy = kp.x + f.y, cx = kp.y + f.x, r = f.z;
+            const int cy = kp.y + f.y, cx = kp.x + f.x, r = f.z;
             s_S[wave][lane] = (int)box(I, ws, cy - r, cy + r, cx - r, cx + r);
         }
     };
@@ -324,15 +407,186 @@ __global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __r
     else
         desc[(size_t)lane * ldd + kidx] = (uint8_t)byte;
     if (lane == 0) {
-        loc[kidx] = (double)(kp.y + 1);
-        loc[(size_t)ldl + kidx] = (double)(kp.x + 1);
+        // the pixel's centre in level-0 coordinates, 1-based: one division, one addition (level 0: x + 1 exactly)
+        loc[kidx] = (double)((2LL * kp.x + 1) * P.lv[0].w) / (double)(2LL * L.w) + 0.5;
+        loc[(size_t)ldl + kidx] = (double)((2LL * kp.y + 1) * P.lv[0].h) / (double)(2LL * L.h) + 0.5;
         if (aux) {
-            aux[(size_t)kidx * 4 + 0] = (float)kept[(size_t)kp.x * w + kp.y];
+            aux[(size_t)kidx * 4 + 0] = (float)kept[L.plane0 + (size_t)kp.y * L.w + kp.x];
             aux[(size_t)kidx * 4 + 1] = (float)bin;
-            aux[(size_t)kidx * 4 + 2] = 0.0f;
+            aux[(size_t)kidx * 4 + 2] = (float)kp.level;
             aux[(size_t)kidx * 4 + 3] = 0.0f;
         }
     }
+}
+
+// ---- host: the plan and the chain ----------------------------------------------------------------------------------------
+struct HostPlan {
+    FastPlan dev;
+    size_t plane_bytes, integ_elems;  // of all levels
+    unsigned int n_tiles, n_words;
+};
+
+// Level 0 is the image; level l is level l - 1 divided by num / den, each side rounded half up.  The plan ends before the first level
+// that has no pixel at least `margin` from every edge, or at n_levels.
+HostPlan make_plan(int h, int w, int n_levels, long long num, long long den) {
+    HostPlan hp;
+    std::memset(&hp, 0, sizeof hp);
+    const int least = 2 * host_pattern().margin + 1;
+    for (int l = 0; l < n_levels; ++l) {
+        if (l) {
+            h = (int)((2 * h * den + num) / (2 * num));
+            w = (int)((2 * w * den + num) / (2 * num));
+            if (std::min(h, w) < least) break;
+        }
+        FastLevel& L = hp.dev.lv[l];
+        L.h = h;
+        L.w = w;
+        L.wpr = (int)cdiv(w, 64);
+        L.tile0 = hp.n_tiles;
+        L.word0 = hp.n_words;
+        L.plane0 = (long long)hp.plane_bytes;
+        L.integ0 = (long long)hp.integ_elems;
+        hp.n_tiles += (unsigned int)L.wpr * cdiv(h, kTH);
+        hp.n_words += (unsigned int)L.wpr * (unsigned int)h;
+        hp.plane_bytes += (size_t)h * w;
+        hp.integ_elems += (size_t)(h + 1) * (w + 1);
+        hp.dev.n = l + 1;
+    }
+    return hp;
+}
+
+// the checks of aps_fast_extract, which come before any device work
+void check_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_params& prm, int desc_layout, int64_t cap) {
+    APS_REQUIRE(img, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
+    APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
+    APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
+    APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
+    APS_REQUIRE(prm.threshold >= 0 && prm.threshold <= 255, APS_E_ARG, "threshold (floor(MinContrast * 255)) must be in 0..255");
+    APS_REQUIRE(prm.quality_den > 0 && prm.quality_den <= (1 << 24) && prm.quality_num >= 0 && prm.quality_num <= prm.quality_den, APS_E_ARG,
+                "MinQuality must be a rational in [0, 1] with a denominator of at most 2^24");
+    APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
+    // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
+    APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
+                "FAST: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
+}
+
+void check_pyramid(int n_levels, int scale_num, int scale_den) {
+    APS_REQUIRE(n_levels >= 1 && n_levels <= kMaxLevels, APS_E_ARG, "n_levels (NumLevels) must be in 1..%d", kMaxLevels);
+    APS_REQUIRE(scale_den > 0 && scale_num > scale_den && (long long)scale_num <= 2LL * scale_den, APS_E_ARG,
+                "ScaleFactor = scale_num / scale_den must lie in (1, 2]");
+}
+
+// The planes and integral images of all levels, in the order of their dependences, on the calling thread's stream.
+// T: scratch of level 0's size; I: hp.integ_elems; planes: hp.plane_bytes.
+void build_levels(const uint8_t* dimg, int channels, int img_layout, const HostPlan& hp, uint8_t* planes, uint32_t* T, uint32_t* I) {
+    for (int l = 0; l < hp.dev.n; ++l) {
+        const FastLevel& L = hp.dev.lv[l];
+        if (l) {
+            const FastLevel& S = hp.dev.lv[l - 1];
+            Prof prof("fast_resample");
+            fast_resample_kernel<<<dim3(cdiv(L.w, kRW), cdiv(L.h, kRH)), 256, 0, stream()>>>(planes + S.plane0, S.h, S.w, planes + L.plane0, L.h, L.w);
+            check_launch("fast_resample_kernel");
+        }
+        Prof prof("fast_integral");
+        if (l == 0)
+            integral_image(dimg, L.h, L.w, channels, img_layout, T, I, planes);
+        else
+            integral_image(planes + L.plane0, L.h, L.w, 1, APS_IMG_U8_HWC, T, I + L.integ0, nullptr);
+    }
+}
+
+// aps_fast_extract and aps_fast_extract_pyramid behind their argument checks (check_args, check_pyramid).
+void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, uint8_t* desc,
+                int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    ctx();
+    *count = 0;
+    const FastPlan& P = hp.dev;
+    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
+    if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
+    In<uint8_t> dimg(img, (size_t)H * W * channels);
+    Ws<uint32_t> T((size_t)H * W), I(hp.integ_elems);
+    Ws<uint8_t> planes(hp.plane_bytes);
+    build_levels(dimg, channels, img_layout, hp, planes, T, I);
+    const size_t n_words = hp.n_words;
+    Ws<uint8_t> kept(hp.plane_bytes);
+    Ws<unsigned int> smax((size_t)P.n);
+    Ws<unsigned long long> bitmap(n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    Ws<unsigned int> prefix(n_words + 1);
+    APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
+    {
+        Prof prof("fast_detect");
+        fast_detect_kernel<<<hp.n_tiles, 256, 0, stream()>>>(planes, P, params->threshold, margin, kept);
+        check_launch("fast_detect_kernel");
+        auto scores = rocprim::make_transform_iterator(kept.get(), U8ToU32());
+        // s_max of each level; the reductions run one after the other and share the temporary storage of the one that needs most
+        size_t lbytes[kMaxLevels], rbytes = 0;
+        for (int l = 0; l < P.n; ++l) {
+            APS_HIP(rocprim::reduce(nullptr, lbytes[l], scores + P.lv[l].plane0, smax.get() + l, 0u, (size_t)P.lv[l].h * P.lv[l].w,
+                                    rocprim::maximum<unsigned int>(), stream()));
+            rbytes = std::max(rbytes, lbytes[l]);
+        }
+        Ws<char> rtmp(rbytes);
+        for (int l = 0; l < P.n; ++l)
+            APS_HIP(rocprim::reduce(rtmp.get(), lbytes[l], scores + P.lv[l].plane0, smax.get() + l, 0u, (size_t)P.lv[l].h * P.lv[l].w,
+                                    rocprim::maximum<unsigned int>(), stream()));
+        fast_gate_kernel<<<cdiv(n_words, 4), 256, 0, stream()>>>(kept, P, hp.n_words, smax, (unsigned int)params->quality_num,
+                                                                 (unsigned int)params->quality_den, bitmap);
+        check_launch("fast_gate_kernel");
+    }
+    {
+        Prof prof("fast_scan");
+        auto counts = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
+        size_t tbytes = 0;
+        APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, n_words + 1, rocprim::plus<unsigned int>(), stream()));
+        Ws<char> tmp(tbytes);
+        APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, n_words + 1, rocprim::plus<unsigned int>(), stream()));
+    }
+    const unsigned int* d_total = prefix.get() + n_words;
+    const bool write = cap > 0 && desc && loc;
+    const unsigned int kcap = write ? (unsigned int)cap : 0u;
+    Out<uint8_t> odesc;
+    Out<double> oloc;
+    Out<float> oaux;
+    if (write) {
+        if (desc_layout == APS_ROWMAJOR)
+            APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
+        else
+            APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
+        APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
+        odesc.bind(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
+        oloc.bind(loc, (size_t)ldl + cap);
+        oaux.bind(aux, (size_t)cap * 4);
+        Ws<Keypoint> kps((size_t)kcap);
+        Ws<FreakDev> d_tb(1);
+        {
+            Prof prof("fast_emit");  // (with the upload of the pattern tables)
+            APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
+            fast_emit_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(bitmap, prefix, P, hp.n_words, kps, kcap);
+            check_launch("fast_emit_kernel");
+        }
+        {
+            Prof prof("freak_keypoint");
+            freak_keypoint_kernel<<<cdiv(kcap, 4), 256, 0, stream()>>>(I, P, d_tb, kept, kps, d_total, kcap, odesc, desc_layout, (long long)ldd,
+                                                                      oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
+        }
+        check_launch("freak_keypoint_kernel");
+    }
+    unsigned int n = 0;  // the one read-back of the chain
+    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    *count = n;
+    if (params->max_features > 0 && n > (unsigned int)params->max_features)
+        fail(APS_E_CAP, "FAST found %u features, more than params.max_features = %d", n, params->max_features);
+    if ((int64_t)n > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n);
+    if (n == 0) return;
+    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
+    if (desc_layout == APS_ROWMAJOR)
+        odesc.commit_2d(64, n, (size_t)ldd);
+    else
+        odesc.commit_2d(n, 64, (size_t)ldd);
+    oloc.commit_2d(n, 2, (size_t)ldl);
+    oaux.commit((size_t)n * 4);
 }
 
 }  // namespace
@@ -358,102 +612,55 @@ int aps_fast_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_fast_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        check_args(img, height, width, channels, img_layout, *params, desc_layout, cap);
+        fast_chain(img, channels, img_layout, params, make_plan(height, width, 1, 1, 1), desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_fast_extract_pyramid(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_fast_pyramid_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        check_args(img, height, width, channels, img_layout, params->fast, desc_layout, cap);
+        check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+        fast_chain(img, channels, img_layout, &params->fast, make_plan(height, width, params->n_levels, params->scale_num, params->scale_den),
+                   desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_fast_pyramid_plan(int height, int width, int n_levels, int scale_num, int scale_den, int* heights, int* widths, int* n_used) {
+    return guarded([&] {
+        APS_REQUIRE(n_used, APS_E_ARG, "NULL argument");
         APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
-        APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
-        APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
-        APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
-        APS_REQUIRE(params->threshold >= 0 && params->threshold <= 255, APS_E_ARG, "threshold (floor(MinContrast * 255)) must be in 0..255");
-        APS_REQUIRE(params->quality_den > 0 && params->quality_den <= (1 << 24) && params->quality_num >= 0 && params->quality_num <= params->quality_den,
-                    APS_E_ARG, "MinQuality must be a rational in [0, 1] with a denominator of at most 2^24");
-        APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
-        // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
-        APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
-                    "FAST: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
+        check_pyramid(n_levels, scale_num, scale_den);
+        const HostPlan hp = make_plan(height, width, n_levels, scale_num, scale_den);
+        *n_used = hp.dev.n;
+        for (int l = 0; l < hp.dev.n; ++l) {
+            if (heights) heights[l] = hp.dev.lv[l].h;
+            if (widths) widths[l] = hp.dev.lv[l].w;
+        }
+    });
+}
+
+int aps_fast_pyramid_planes(const uint8_t* img, int height, int width, int channels, int img_layout,
+                            const aps_fast_pyramid_params* params, uint8_t* out, int64_t cap_bytes, int64_t* bytes) {
+    return guarded([&] {
+        APS_REQUIRE(params && bytes, APS_E_ARG, "NULL argument");
+        check_args(img, height, width, channels, img_layout, params->fast, APS_ROWMAJOR, 0);
+        check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+        const HostPlan hp = make_plan(height, width, params->n_levels, params->scale_num, params->scale_den);
+        *bytes = (int64_t)hp.plane_bytes;
+        if (!out) return;  // (the size alone: no device work)
+        APS_REQUIRE(cap_bytes >= *bytes, APS_E_CAP, "plane capacity %lld < %lld bytes", (long long)cap_bytes, (long long)*bytes);
         ctx();
-        *count = 0;
-        const int H = height, W = width, margin = host_pattern().margin;
-        if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
-        In<uint8_t> dimg(img, (size_t)H * W * channels);
-        Ws<uint32_t> T((size_t)H * W), I((size_t)(H + 1) * (W + 1));
-        Ws<uint8_t> gray((size_t)H * W);
-        {
-            Prof prof("fast_integral");
-            integral_image(dimg, H, W, channels, img_layout, T, I, gray);
-        }
-        const int wpr = (int)cdiv(W, 64);
-        const long long n_words = (long long)H * wpr;
-        Ws<uint8_t> kept((size_t)H * W);
-        Ws<unsigned int> smax(1);
-        Ws<unsigned long long> bitmap((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
-        Ws<unsigned int> prefix((size_t)n_words + 1);
-        APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
-        {
-            Prof prof("fast_detect");
-            fast_detect_kernel<<<dim3(wpr, cdiv(H, kTH)), 256, 0, stream()>>>(gray, H, W, params->threshold, margin, kept);
-            check_launch("fast_detect_kernel");
-            auto scores = rocprim::make_transform_iterator(kept.get(), U8ToU32());
-            size_t rbytes = 0;
-            APS_HIP(rocprim::reduce(nullptr, rbytes, scores, smax.get(), 0u, (size_t)H * W, rocprim::maximum<unsigned int>(), stream()));
-            Ws<char> rtmp(rbytes);
-            APS_HIP(rocprim::reduce(rtmp.get(), rbytes, scores, smax.get(), 0u, (size_t)H * W, rocprim::maximum<unsigned int>(), stream()));
-            fast_gate_kernel<<<dim3(wpr, cdiv(H, 4)), 256, 0, stream()>>>(kept, H, W, wpr, smax, (unsigned int)params->quality_num,
-                                                                        (unsigned int)params->quality_den, bitmap);
-            check_launch("fast_gate_kernel");
-        }
-        {
-            Prof prof("fast_scan");
-            auto counts = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
-            size_t tbytes = 0;
-            APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-            Ws<char> tmp(tbytes);
-            APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-        }
-        const unsigned int* d_total = prefix.get() + n_words;
-        const bool write = cap > 0 && desc && loc;
-        const unsigned int kcap = write ? (unsigned int)cap : 0u;
-        Out<uint8_t> odesc;
-        Out<double> oloc;
-        Out<float> oaux;
-        if (write) {
-            if (desc_layout == APS_ROWMAJOR)
-                APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
-            else
-                APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
-            APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
-            odesc.bind(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
-            oloc.bind(loc, (size_t)ldl + cap);
-            oaux.bind(aux, (size_t)cap * 4);
-            Ws<int2> kps((size_t)kcap);
-            Ws<FreakDev> d_tb(1);
-            {
-                Prof prof("fast_emit");  // (with the upload of the pattern tables)
-                APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
-                fast_emit_kernel<<<cdiv((size_t)n_words, 256), 256, 0, stream()>>>(bitmap, prefix, n_words, wpr, kps, kcap);
-                check_launch("fast_emit_kernel");
-            }
-            {
-                Prof prof("freak_keypoint");
-                freak_keypoint_kernel<<<cdiv(kcap, 4), 256, 0, stream()>>>(I, W, d_tb, kept, kps, d_total, kcap, odesc, desc_layout, (long long)ldd,
-                                                                          oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
-            }
-            check_launch("freak_keypoint_kernel");
-        }
-        unsigned int n = 0;  // the one read-back of the chain
-        APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
+        In<uint8_t> dimg(img, (size_t)height * width * channels);
+        Ws<uint32_t> T((size_t)height * width), I(hp.integ_elems);
+        Out<uint8_t> planes(out, hp.plane_bytes);
+        build_levels(dimg, channels, img_layout, hp, planes, T, I);
+        planes.commit();
         APS_HIP(hipStreamSynchronize(stream()));
-        *count = n;
-        if (params->max_features > 0 && n > (unsigned int)params->max_features)
-            fail(APS_E_CAP, "FAST found %u features, more than params.max_features = %d", n, params->max_features);
-        if ((int64_t)n > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n);
-        if (n == 0) return;
-        APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-        if (desc_layout == APS_ROWMAJOR)
-            odesc.commit_2d(64, n, (size_t)ldd);
-        else
-            odesc.commit_2d(n, 64, (size_t)ldd);
-        oloc.commit_2d(n, 2, (size_t)ldl);
-        oaux.commit((size_t)n * 4);
     });
 }
 

@@ -780,11 +780,24 @@ def _fast_params(input):
     return p
 
 
+def _fast_pyramid_params(input, n_levels):
+    p = _capi.aps_fast_pyramid_params()
+    p.fast = _fast_params(input)
+    p.n_levels = n_levels
+    p.scale_num, p.scale_den = int(round(float(input.get("ScaleFactor", 1.2)) * 1000000)), 1000000
+    return p
+
+
 def fast_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
     """aps_fast_extract with automatic capacity: returns (binaryFeatures, validPts[, aux]); the arguments are sift_extract's.
     Features are n x 64 uint8 (FREAK, 512 bits), on the host or, with device_out, resident; validPts n x 2 [x y] 1-based,
     integer-valued; aux n x 4 [FAST score, orientation bin, 0, 0].  input.MinContrast (0.2) and input.MinQuality (0.1) are
-    detectFASTFeatures' parameters."""
+    detectFASTFeatures' parameters.
+
+    input.NumLevels (1) and input.ScaleFactor (1.2), detectORBFeatures' names, ask for a scale pyramid: NumLevels > 1 goes
+    through aps_fast_extract_pyramid, which runs FAST/FREAK on every level of the plan.  validPts are then the level pixels'
+    centres in image coordinates (not integers beyond level 0), aux is [score, bin, level, 0], and the rows are in ascending
+    (level, row, col) order; a corner may be reported at several levels."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -795,8 +808,16 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
         c = 1 if img.ndim == 2 else img.shape[2]
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
-    prm = _fast_params(input)
-    cap = max(4096, (h * w) // 64)
+    n_levels = int(input.get("NumLevels", 1))
+    if n_levels == 1:
+        prm, entry, pixels = _fast_params(input), lib.aps_fast_extract, h * w
+    else:
+        prm, entry = _fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid
+        hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
+        check(lib.aps_fast_pyramid_plan(h, w, prm.n_levels, prm.scale_num, prm.scale_den, hs, ws, C.byref(used)))
+        pixels = sum(hs[l] * ws[l] for l in range(used.value))
+    max_features = int(input.get("maxFeatures", 0))
+    cap = max(4096, pixels // 64)
     cnt = C.c_int64(0)
     while True:
         if device_out:
@@ -812,9 +833,9 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
         else:
             loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
         aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = lib.aps_fast_extract(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                                  _capi.APS_ROWMAJOR, FREAK_BYTES, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < prm.max_features < cnt.value):
+        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
+                   _capi.APS_ROWMAJOR, FREAK_BYTES, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
+        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < max_features < cnt.value):
             cap = int(cnt.value)
             continue
         check(rc)

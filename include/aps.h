@@ -778,6 +778,39 @@ int aps_fast_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_fast_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
+/* FAST/FREAK over a scale pyramid (DESIGN.md "FAST/FREAK scale pyramid"; the parameter names are detectORBFeatures' NumLevels and
+ * ScaleFactor).  ScaleFactor is the rational scale_num / scale_den = round(ScaleFactor * 10^6) / 10^6, evaluated by the caller;
+ * scale_den < scale_num <= 2 * scale_den and n_levels in 1..16, everything else is APS_E_ARG. */
+typedef struct aps_fast_pyramid_params {
+    aps_fast_params fast;
+    int n_levels;              /* NumLevels: levels asked for; the plan ends earlier where a level has no admissible pixel */
+    int scale_num;             /* ScaleFactor (1.2 -> 1200000 / 1000000) */
+    int scale_den;
+} aps_fast_pyramid_params;
+
+/* aps_fast_extract on every level of the plan: level 0 is the rgb2gray plane, level l is level l - 1 resampled (bilinear, half-pixel
+ * centres, 8-bit weights, integer arithmetic), and each level goes through the FAST/FREAK contract unchanged, with its own s_max.
+ * Arguments, capacity, count-only mode, padding and pointers behave as aps_fast_extract's.  Differences in the outputs:
+ *   loc  : the pixel's centre in level-0 coordinates, 1-based: f64((2 x_l + 1) * width) / f64(2 * w_l) + 0.5, and y alike
+ *          (level 0: x_l + 1 exactly)
+ *   aux  : [FAST score, orientation bin, level, 0]
+ * Feature order is canonical: ascending (level, row, col).  A corner may be reported at several levels.
+ * n_levels = 1 gives aps_fast_extract's result. */
+int aps_fast_extract_pyramid(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_fast_pyramid_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* The plan of that call (host only, needs no device): h_0 = height, h_l = floor((2 h_{l-1} scale_den + scale_num) / (2 scale_num)),
+ * widths alike; the plan ends before the first level with min(h_l, w_l) < 2 * margin + 1 (aps_freak_pattern's margin) or at
+ * n_levels; level 0 always exists.  heights / widths: host int[n_levels] or NULL; *n_used = levels in the plan. */
+int aps_fast_pyramid_plan(int height, int width, int n_levels, int scale_num, int scale_den, int* heights, int* widths, int* n_used);
+
+/* Test hook: the u8 level planes of aps_fast_extract_pyramid, packed one after the other, each row-major, to a host or device
+ * pointer `out` of cap_bytes bytes (APS_E_CAP if too small).  *bytes = the sum of h_l * w_l; out = NULL reports it without device
+ * work.  It tells a resampling error from a detection error. */
+int aps_fast_pyramid_planes(const uint8_t* img, int height, int width, int channels, int img_layout,
+                            const aps_fast_pyramid_params* params, uint8_t* out, int64_t cap_bytes, int64_t* bytes);
+
 /* The integer FREAK tables the extractor uses (tests restate the contract on them; needs no device).  Every pointer may be
  * NULL.  All arrays are host int32, row-major:
  *   fields    [256][43][3]  per orientation bin and receptive field: centre offset dx, dy (pixels) and box half-side r
