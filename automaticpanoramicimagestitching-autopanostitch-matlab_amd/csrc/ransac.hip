@@ -1,24 +1,30 @@
-// ransac.hip — batched RANSAC / MLESAC on gfx950 (f64).
+// ransac.hip — batched RANSAC / MLESAC on gfx950 (f64), all five transformTypes.
 //
-// Restates PP/imageMatching/estimateTransformationRANSAC.m:54-183 (loop), :188-225 (normalised DLT),
-// :444-516 (findInliers), :518-535 (checkModel), :537-574 (isDegenerate), :579-610 (normalizePoints)
-// for transformType 'projective', and :227-452, :483-497 for 'affine' / 'similarity' / 'rigid' / 'translation' (the section
-// "The other transformTypes" below), batched over the candidate image pairs of PP/imageMatching/imageMatching.m:121-156.
+// Restates PP/imageMatching/estimateTransformationRANSAC.m:54-183 (loop), :188-225 (normalised DLT), :227-452 (the fits of
+// 'affine' / 'similarity' / 'rigid' / 'translation'), :444-516 (findInliers), :518-535 (checkModel), :537-574
+// (isDegenerate), :579-610 (normalizePoints) and estimateTransformationMLESAC.m (:157-241 loop, :345-510 estimators,
+// :534-598 evaluators), batched over the candidate image pairs of PP/imageMatching/imageMatching.m:121-156.
 //
 // Shape of the computation (why it is batched this way):
-//   fit kernel    : one lane per (pair, draw): 4-point normalised DLT.  The right null vector of the
-//                   8x9 system is the smallest eigenvector of the 9x9 Gram matrix (cyclic Jacobi); the
-//                   two 9x9 work matrices of every lane live in LDS as [element][lane].
-//   score kernel  : one 64-lane wave per (pair, draw): lanes stride over the pair's matches, symmetric
-//                   transfer error in f64, inlier count / error sum / centroid by wavefront butterfly
-//                   reductions, then the collinearity (degeneracy) test on the inliers.
-//   replay (host) : the data-dependent part of the loop — best-so-far update and the adaptive shrink of
-//                   maxTrials (:115-130) — is replayed sequentially over the pre-scored draws, which is
-//                   exactly the sequential algorithm on the same draws.
-//   finalize      : one wave per pair: inlier mask of the winning draw, refit on all inliers (:146-150),
-//                   re-score, fallback rules (:153-176).
-// All reductions use one fixed order (lane-strided partial sums + xor butterfly) that the oracle
-// restates, so inlier masks compare bit-exactly.  f64 only; no contraction (-ffp-contract=off).
+//   fit kernels     : one lane per (pair, draw), a minimal-sample fit.  ransac_fit_kernel: the 4-point normalised DLT of
+//                     'projective' (both estimators) - the right null vector of the 8x9 system is the smallest
+//                     eigenvector of the 9x9 Gram matrix (cyclic Jacobi); the two 9x9 work matrices of every lane live
+//                     in LDS as [element][lane].  tform_fit_kernel: RANSAC's closed forms of the other types (no LDS).
+//                     mlesac_tform_fit_kernel: MLESAC's 7x7 / 5x5 null-vector systems and closed forms.
+//   score kernel    : ransac_score_kernel<MLESAC>, one 64-lane wave per (pair, draw): lanes stride over the pair's
+//                     matches, the type's error in f64, inlier count / error sum / centroid by wavefront butterfly
+//                     reductions, then the collinearity (degeneracy) test on the inliers.
+//   replay (host)   : the data-dependent part of the loop — best-so-far update and the adaptive shrink of
+//                     maxTrials (:115-130) — is replayed sequentially over the pre-scored draws, which is
+//                     exactly the sequential algorithm on the same draws.
+//   finalize kernels: one wave per pair: inlier mask of the winning draw, refit on all inliers (:146-150), re-score,
+//                     fallback rules (:153-176).  ransac_finalize_kernel ('projective', both estimators),
+//                     tform_finalize_kernel (RANSAC, the other types), mlesac_tform_finalize_kernel (MLESAC, the others).
+// All reductions use one fixed order (lane-strided partial sums + xor butterfly, or the draw / index order where the
+// oracle sums sequentially) that the oracle restates, so inlier masks compare bit-exactly.  f64 only; no contraction
+// (-ffp-contract=off).  Every step of an estimator is stated once and shared by the kernels that need it.
+//
+// Order of the file: small linear algebra, normalisation, estimators, evaluators, kernels, draws, host.
 #include <cmath>
 #include <vector>
 
@@ -26,11 +32,27 @@
 
 namespace aps {
 
+// ------------------------------------------------------------------------------------------------
+// small linear algebra
+// ------------------------------------------------------------------------------------------------
 constexpr double kDblEps = 2.220446049250313e-16;
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(v, off);
+        if (o > v) v = o;
+    }
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
 
@@ -70,11 +92,23 @@ __device__ __forceinline__ double norm1_3(const Mat3& H) {
     return m;
 }
 
-// checkModel (estimateTransformationRANSAC.m:518-535)
-__device__ __forceinline__ bool check_model(const Mat3& H) {
+__device__ __forceinline__ bool all_finite(const Mat3& H) {
 #pragma unroll
     for (int e = 0; e < 9; ++e)
         if (!isfinite(H.m[e])) return false;
+    return true;
+}
+
+__device__ __forceinline__ Mat3 identity3() {
+    Mat3 H;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) H.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
+    return H;
+}
+
+// checkModel (estimateTransformationRANSAC.m:518-535)
+__device__ __forceinline__ bool check_model(const Mat3& H) {
+    if (!all_finite(H)) return false;
     const double d = det3(H);
     if (!(fabs(d) > kDblEps)) return false;
     const Mat3 A = adjugate3(H);
@@ -85,155 +119,125 @@ __device__ __forceinline__ bool check_model(const Mat3& H) {
     return rc > kDblEps;
 }
 
-// LDS work matrices: element e of lane l at [e*S + l] (S = 64 in the fit kernel, one problem per lane; S = 2 in the
-// refit, one problem per workgroup)
-#define GE(p, q) sG[((p) * 9 + (q)) * S + lane]
-#define VE(p, q) sV[((p) * 9 + (q)) * S + lane]
+// MATLAB's median of two values
+__device__ __forceinline__ double median2(double a, double b) {
+    if (isnan(a) || isnan(b)) return NAN;
+    if (b < a) {
+        const double t = a;
+        a = b;
+        b = t;
+    }
+    const int sa = (a > 0) - (a < 0), sb = (b > 0) - (b < 0);
+    if (sa != sb || isinf(a) || isinf(b)) return (a + b) / 2;
+    return a + (b - a) / 2;
+}
 
-// Cyclic Jacobi on the symmetric 9x9 in GE; eigenvectors in the columns of VE.
-// (N x N problem in the 9-stride layout; N = 9 is the homography, 7 / 5 MLESAC's affine / similarity systems)
-template <int S, int N = 9>
-__device__ void jacobi9(double* sG, double* sV, int lane) {
+// A symmetric work matrix in LDS, 9-stride: element (p, q) of column `col` at [(p * 9 + q) * S + col].  S = 64, col = lane in
+// the fit kernels (one problem per lane); S = 2, col = 0 in the finalize kernels (one problem per workgroup).
+template <int S>
+struct LdsMat {
+    double* a;
+    int col;
+    __device__ __forceinline__ double& operator()(int p, int q) const { return a[(p * 9 + q) * S + col]; }
+};
+
+// The Jacobi rotation that annihilates entry (p, q).  Returns true where the pair is skipped (the entry is negligible; the
+// rotation is then the identity).
+__device__ __forceinline__ bool jacobi_rotation(double gpp, double gqq, double gpq, double& t, double& c, double& s) {
+    t = 0.0;
+    c = 1.0;
+    s = 0.0;
+    if (fabs(gpq) <= 1e-300 || fabs(gpq) <= 1e-18 * sqrt(fabs(gpp * gqq))) return true;
+    const double theta = (gqq - gpp) / (2.0 * gpq);
+    t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(t * t + 1.0);
+    s = t * c;
+    return false;
+}
+
+// Cyclic Jacobi on the symmetric N x N in G; eigenvectors in the columns of V.
+// (N = 9 is the homography, 7 / 5 MLESAC's affine / similarity systems)
+template <int S, int N>
+__device__ void jacobi9(LdsMat<S> G, LdsMat<S> V) {
     for (int p = 0; p < N; ++p)
-        for (int q = 0; q < N; ++q) VE(p, q) = (p == q) ? 1.0 : 0.0;
+        for (int q = 0; q < N; ++q) V(p, q) = (p == q) ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 30; ++sweep) {
         bool rotated = false;
         for (int p = 0; p < N - 1; ++p)
             for (int q = p + 1; q < N; ++q) {
-                const double gpq = GE(p, q);
-                const double gpp = GE(p, p), gqq = GE(q, q);
-                if (fabs(gpq) <= 1e-300 || fabs(gpq) <= 1e-18 * sqrt(fabs(gpp * gqq))) continue;
+                const double gpq = G(p, q);
+                const double gpp = G(p, p), gqq = G(q, q);
+                double t, c, s;
+                if (jacobi_rotation(gpp, gqq, gpq, t, c, s)) continue;
                 rotated = true;
-                const double theta = (gqq - gpp) / (2.0 * gpq);
-                const double t =
-                    (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0);
-                const double s = t * c;
                 for (int k = 0; k < N; ++k) {
                     if (k == p || k == q) continue;
-                    const double gkp = GE(k, p), gkq = GE(k, q);
+                    const double gkp = G(k, p), gkq = G(k, q);
                     const double np_ = c * gkp - s * gkq;
                     const double nq_ = s * gkp + c * gkq;
-                    GE(k, p) = np_;
-                    GE(p, k) = np_;
-                    GE(k, q) = nq_;
-                    GE(q, k) = nq_;
+                    G(k, p) = np_;
+                    G(p, k) = np_;
+                    G(k, q) = nq_;
+                    G(q, k) = nq_;
                 }
-                GE(p, p) = gpp - t * gpq;
-                GE(q, q) = gqq + t * gpq;
-                GE(p, q) = 0.0;
-                GE(q, p) = 0.0;
+                G(p, p) = gpp - t * gpq;
+                G(q, q) = gqq + t * gpq;
+                G(p, q) = 0.0;
+                G(q, p) = 0.0;
                 for (int k = 0; k < N; ++k) {
-                    const double vkp = VE(k, p), vkq = VE(k, q);
-                    VE(k, p) = c * vkp - s * vkq;
-                    VE(k, q) = s * vkp + c * vkq;
+                    const double vkp = V(k, p), vkq = V(k, q);
+                    V(k, p) = c * vkp - s * vkq;
+                    V(k, q) = s * vkp + c * vkq;
                 }
             }
         if (!rotated) break;
     }
 }
 
-struct Norm {
-    double s, tx, ty;
-    double cx, cy;  // the centroid: MLESAC's normalised points are (p - centroid) * s (normalizePointsHartleyZisserman
-                    // :667-671), RANSAC's are T * [p; 1] = s * p + t (normalizePoints :604-606)
-};
-__device__ __forceinline__ double norm_coord(const Norm& n, double p, double c, double t, int mlesac) {
-    return mlesac ? (p - c) * n.s : n.s * p + t;
-}
-
-// Row `half` (0: x-row, 1: y-row) of the DLT matrix for one normalised correspondence (:209-212)
-__device__ __forceinline__ double dlt_entry(int k, int half, double x, double y, double u, double v) {
-    const double w = half ? v : u;
-    if (k >= 6) return k == 6 ? x * w : (k == 7 ? y * w : w);
-    const int kk = half ? k - 3 : k;
-    if (kk < 0 || kk > 2) return 0.0;
-    return kk == 0 ? -x : (kk == 1 ? -y : -1.0);
-}
-
-// From the filled Gram matrix to the denormalised H (:214-224).  Returns false if not finite.
-template <int S>
-__device__ bool gram_to_h(double* sG, double* sV, int lane, const Norm& n1, const Norm& n2, Mat3& H, int mlesac = 0) {
-    for (int p = 0; p < 9; ++p)
-        for (int q = 0; q < p; ++q) GE(p, q) = GE(q, p);
-    jacobi9<S>(sG, sV, lane);
-    int kmin = 0;
-    for (int k = 1; k < 9; ++k)
-        if (GE(k, k) < GE(kmin, kmin)) kmin = k;
-    double h[9];
-    for (int k = 0; k < 9; ++k) h[k] = VE(k, kmin);
-    Mat3 Hn, M;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) M3(Hn, r, c) = h[3 * r + c] / h[8];
-    for (int c = 0; c < 3; ++c) {
-        const double m2 = M3(Hn, 2, c);
-        M3(M, 2, c) = m2;
-        M3(M, 1, c) = (M3(Hn, 1, c) - n2.ty * m2) / n2.s;
-        M3(M, 0, c) = (M3(Hn, 0, c) - n2.tx * m2) / n2.s;
-    }
-    for (int r = 0; r < 3; ++r) {
-        M3(H, r, 0) = M3(M, r, 0) * n1.s;
-        M3(H, r, 1) = M3(M, r, 1) * n1.s;
-        M3(H, r, 2) = (M3(M, r, 0) * n1.tx + M3(M, r, 1) * n1.ty) + M3(M, r, 2);
-    }
-    if (mlesac) {  // denormalizeTform: tform ./ tform(end) (estimateTransformationMLESAC.m:713-714)
-        const double d = H.m[8];
-        for (int e = 0; e < 9; ++e) H.m[e] = H.m[e] / d;
-    }
-    for (int e = 0; e < 9; ++e)
-        if (!isfinite(H.m[e])) return false;
-    return true;
-}
-
-// The finalize kernel's form of jacobi9 / gram_to_h: ONE 9x9 problem per 64-lane workgroup (column 0 of the S = 2
-// layout).  A rotation (p, q) touches rows/columns k = 0..8 independently, so lane k < 9 updates "its" k while every lane
-// evaluates the (uniform) rotation parameters: the same operations on the same operands as the serial routine - bit
-// for bit - in a ninth of the dependent LDS round trips (the serial form by lane 0 was most of the kernel's 3.5 ms).
-template <int N = 9>
-__device__ void jacobi9_wave(double* sG, double* sV, int lane) {
-#define G2(p, q) sG[((p) * 9 + (q)) * 2]
-#define V2(p, q) sV[((p) * 9 + (q)) * 2]
+// The finalize kernels' form of jacobi9: ONE problem per 64-lane workgroup.  A rotation (p, q) touches rows/columns
+// k = 0..N-1 independently, so lane k < N updates "its" k while every lane evaluates the (uniform) rotation parameters: the
+// same operations on the same operands as the serial routine - bit for bit - in a ninth of the dependent LDS round trips
+// (the serial form by lane 0 was most of the kernel's 3.5 ms).
+template <int N>
+__device__ void jacobi9_wave(LdsMat<2> G, LdsMat<2> V, int lane) {
     const int k = lane;
     if (k < N)
-        for (int q = 0; q < N; ++q) V2(k, q) = (k == q) ? 1.0 : 0.0;
+        for (int q = 0; q < N; ++q) V(k, q) = (k == q) ? 1.0 : 0.0;
     __syncthreads();
     for (int sweep = 0; sweep < 30; ++sweep) {
         bool rotated = false;
         for (int p = 0; p < N - 1; ++p)
             for (int q = p + 1; q < N; ++q) {
-                const double gpq = G2(p, q);
-                const double gpp = G2(p, p), gqq = G2(q, q);
-                if (fabs(gpq) <= 1e-300 || fabs(gpq) <= 1e-18 * sqrt(fabs(gpp * gqq))) continue;  // uniform
+                const double gpq = G(p, q);
+                const double gpp = G(p, p), gqq = G(q, q);
+                double t, c, s;
+                if (jacobi_rotation(gpp, gqq, gpq, t, c, s)) continue;  // uniform
                 rotated = true;
-                const double theta = (gqq - gpp) / (2.0 * gpq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0);
-                const double s = t * c;
                 double gkp = 0, gkq = 0, vkp = 0, vkq = 0;
                 if (k < N) {
-                    gkp = G2(k, p);
-                    gkq = G2(k, q);
-                    vkp = V2(k, p);
-                    vkq = V2(k, q);
+                    gkp = G(k, p);
+                    gkq = G(k, q);
+                    vkp = V(k, p);
+                    vkq = V(k, q);
                 }
                 __syncthreads();  // every read of this rotation before any of its writes
                 if (k < N) {
                     if (k != p && k != q) {
                         const double np_ = c * gkp - s * gkq;
                         const double nq_ = s * gkp + c * gkq;
-                        G2(k, p) = np_;
-                        G2(p, k) = np_;
-                        G2(k, q) = nq_;
-                        G2(q, k) = nq_;
+                        G(k, p) = np_;
+                        G(p, k) = np_;
+                        G(k, q) = nq_;
+                        G(q, k) = nq_;
                     }
-                    V2(k, p) = c * vkp - s * vkq;
-                    V2(k, q) = s * vkp + c * vkq;
+                    V(k, p) = c * vkp - s * vkq;
+                    V(k, q) = s * vkp + c * vkq;
                 }
                 if (lane == 0) {
-                    G2(p, p) = gpp - t * gpq;
-                    G2(q, q) = gqq + t * gpq;
-                    G2(p, q) = 0.0;
-                    G2(q, p) = 0.0;
+                    G(p, p) = gpp - t * gpq;
+                    G(q, q) = gqq + t * gpq;
+                    G(p, q) = 0.0;
+                    G(q, p) = 0.0;
                 }
                 __syncthreads();
             }
@@ -241,544 +245,7 @@ __device__ void jacobi9_wave(double* sG, double* sV, int lane) {
     }
 }
 
-// gram_to_h for that layout; every lane returns the same H and verdict.
-__device__ bool gram_to_h_wave(double* sG, double* sV, int lane, const Norm& n1, const Norm& n2, Mat3& H, int mlesac) {
-    if (lane == 0)
-        for (int p = 0; p < 9; ++p)
-            for (int q = 0; q < p; ++q) G2(p, q) = G2(q, p);
-    __syncthreads();
-    jacobi9_wave(sG, sV, lane);
-    int kmin = 0;
-    for (int k = 1; k < 9; ++k)
-        if (G2(k, k) < G2(kmin, kmin)) kmin = k;
-    double h[9];
-    for (int k = 0; k < 9; ++k) h[k] = V2(k, kmin);
-#undef G2
-#undef V2
-    Mat3 Hn, M;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) M3(Hn, r, c) = h[3 * r + c] / h[8];
-    for (int c = 0; c < 3; ++c) {
-        const double m2 = M3(Hn, 2, c);
-        M3(M, 2, c) = m2;
-        M3(M, 1, c) = (M3(Hn, 1, c) - n2.ty * m2) / n2.s;
-        M3(M, 0, c) = (M3(Hn, 0, c) - n2.tx * m2) / n2.s;
-    }
-    for (int r = 0; r < 3; ++r) {
-        M3(H, r, 0) = M3(M, r, 0) * n1.s;
-        M3(H, r, 1) = M3(M, r, 1) * n1.s;
-        M3(H, r, 2) = (M3(M, r, 0) * n1.tx + M3(M, r, 1) * n1.ty) + M3(M, r, 2);
-    }
-    if (mlesac) {  // denormalizeTform: tform ./ tform(end) (estimateTransformationMLESAC.m:713-714)
-        const double d = H.m[8];
-        for (int e = 0; e < 9; ++e) H.m[e] = H.m[e] / d;
-    }
-    for (int e = 0; e < 9; ++e)
-        if (!isfinite(H.m[e])) return false;
-    return true;
-}
-
-// normalisation scale from the mean distance to the centroid: RANSAC 1/md (:592), MLESAC sqrt(2)/md guarded
-// against md == 0 (normalizePointsHartleyZisserman, estimateTransformationMLESAC.m:653-657)
-__device__ __forceinline__ double norm_scale(double md, int mlesac) {
-    if (!mlesac) return 1.0 / md;
-    return md > 0 ? sqrt(2.0) / md : 1.0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// fit kernel: one lane per (pair, draw)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ransac_fit_kernel(const double* __restrict__ pts1,
-                                                         const double* __restrict__ pts2,
-                                                         int64_t ldp,
-                                                         const int64_t* __restrict__ pair_ptr,
-                                                         const int* __restrict__ act, int n_act,
-                                                         int c0, int nc,
-                                                         const uint32_t* __restrict__ sample_idx,
-                                                         int n_samples, double* __restrict__ Hs,
-                                                         uint8_t* __restrict__ valid, int mlesac) {
-    // work item = (active pair a, draw c0 + k): the host hands the draws over in growing chunks and stops a pair as
-    // soon as its sequential loop has ended, so most of the n_samples draws of a pair are never fitted or scored.
-    // Hs and valid keep the [pair][draw] layout (the finalize kernel picks the winner there; draws may be fitted ahead of
-    // the chunk that scores them).
-    extern __shared__ __attribute__((aligned(16))) double lds_fit[];
-    constexpr int S = 64;  // one 9x9 problem per lane
-    double* sG = lds_fit;
-    double* sV = lds_fit + 81 * 64;
-    const int lane = threadIdx.x;
-    const int64_t wid = blockIdx.x * (int64_t)64 + lane;
-    if (wid >= (int64_t)n_act * nc) return;  // no barriers below: every lane works on its own LDS column
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    double x1[4], y1[4], x2[4], y2[4];
-    bool ok = m >= 4;
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t id = sample_idx[gid * 4 + k];
-        if (id < 1 || (int64_t)id > m) ok = false;
-        const int64_t row = r0 + (ok ? (int64_t)id - 1 : 0);
-        x1[k] = ok ? pts1[row] : 0.0;
-        y1[k] = ok ? pts1[ldp + row] : 0.0;
-        x2[k] = ok ? pts2[row] : 0.0;
-        y2[k] = ok ? pts2[ldp + row] : 0.0;
-    }
-    Mat3 H;
-    for (int e = 0; e < 9; ++e) H.m[e] = 0.0;
-    if (ok) {
-        // normalizePoints (:579-610), sums in index order
-        Norm n1, n2;
-        {
-            double sx = 0, sy = 0;
-            for (int k = 0; k < 4; ++k) {
-                sx = sx + x1[k];
-                sy = sy + y1[k];
-            }
-            const double cx = sx / 4.0, cy = sy / 4.0;
-            double sd = 0;
-            for (int k = 0; k < 4; ++k) {
-                const double dx = x1[k] - cx, dy = y1[k] - cy;
-                sd = sd + sqrt(dx * dx + dy * dy);
-            }
-            n1.s = norm_scale(sd / 4.0, mlesac);
-            n1.tx = -n1.s * cx;
-            n1.ty = -n1.s * cy;
-            n1.cx = cx;
-            n1.cy = cy;
-        }
-        {
-            double sx = 0, sy = 0;
-            for (int k = 0; k < 4; ++k) {
-                sx = sx + x2[k];
-                sy = sy + y2[k];
-            }
-            const double cx = sx / 4.0, cy = sy / 4.0;
-            double sd = 0;
-            for (int k = 0; k < 4; ++k) {
-                const double dx = x2[k] - cx, dy = y2[k] - cy;
-                sd = sd + sqrt(dx * dx + dy * dy);
-            }
-            n2.s = norm_scale(sd / 4.0, mlesac);
-            n2.tx = -n2.s * cx;
-            n2.ty = -n2.s * cy;
-            n2.cx = cx;
-            n2.cy = cy;
-        }
-        for (int a = 0; a < 9; ++a)
-            for (int b = a; b < 9; ++b) GE(a, b) = 0.0;
-        // Gram sums in the reference's row order: RANSAC all "x" rows then all "y" rows (:209-212); MLESAC per
-        // point its "v" row then its "u" row (estimateTransformationMLESAC.m:368-373; a a' is sign-blind)
-        for (int step = 0; step < 8; ++step) {
-            const int half = mlesac ? 1 - (step & 1) : step >> 2;
-            const int k = mlesac ? step >> 1 : step & 3;
-            const double x = norm_coord(n1, x1[k], n1.cx, n1.tx, mlesac), y = norm_coord(n1, y1[k], n1.cy, n1.ty, mlesac);
-            const double u = norm_coord(n2, x2[k], n2.cx, n2.tx, mlesac), v = norm_coord(n2, y2[k], n2.cy, n2.ty, mlesac);
-            double a[9];
-            for (int e = 0; e < 9; ++e) a[e] = dlt_entry(e, half, x, y, u, v);
-            for (int pp = 0; pp < 9; ++pp)
-                for (int qq = pp; qq < 9; ++qq) GE(pp, qq) = GE(pp, qq) + a[pp] * a[qq];
-        }
-        ok = gram_to_h<64>(sG, sV, lane, n1, n2, H, mlesac) && (mlesac || check_model(H));
-    }
-    for (int e = 0; e < 9; ++e) Hs[gid * 9 + e] = H.m[e];
-    valid[gid] = ok ? 1 : 0;  // [pair][draw], like Hs (the score kernels read the chunk-local copy valid_chunk_kernel makes)
-}
-
-// ------------------------------------------------------------------------------------------------
-// wave-collective findInliers (:444-516)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double transfer_error(const Mat3& H, const Mat3& A, double x1, double y1,
-                                                 double x2, double y2) {
-    const double X = (M3(H, 0, 0) * x1 + M3(H, 0, 1) * y1) + M3(H, 0, 2);
-    const double Y = (M3(H, 1, 0) * x1 + M3(H, 1, 1) * y1) + M3(H, 1, 2);
-    const double W = (M3(H, 2, 0) * x1 + M3(H, 2, 1) * y1) + M3(H, 2, 2);
-    const double tx = X / W, ty = Y / W;
-    const double IX = (A.m[0] * x2 + A.m[3] * y2) + A.m[6];
-    const double IY = (A.m[1] * x2 + A.m[4] * y2) + A.m[7];
-    const double IW = (A.m[2] * x2 + A.m[5] * y2) + A.m[8];
-    const double ix = IX / IW, iy = IY / IW;
-    const double ex = x2 - tx, ey = y2 - ty, fx = x1 - ix, fy = y1 - iy;
-    const double d1 = ex * ex + ey * ey;
-    const double d2 = fx * fx + fy * fy;
-    double e = sqrt(d1 + d2);
-    if (!isfinite(e)) e = INFINITY;
-    if (fabs(W) < kDblEps) e = INFINITY;
-    return e;
-}
-
-// All 64 lanes of a wave call this with the same arguments.  mask (may be NULL) receives 0/1 per match.
-__device__ int wave_find_inliers(const Mat3& H, const double* __restrict__ x1,
-                                 const double* __restrict__ y1, const double* __restrict__ x2,
-                                 const double* __restrict__ y2, int64_t m, double thr,
-                                 uint8_t* __restrict__ mask, double* mean_err) {
-    const int lane = threadIdx.x & 63;
-    const Mat3 A = adjugate3(H);
-    double pc = 0, pe = 0, px = 0, py = 0;
-    for (int64_t i = lane; i < m; i += 64) {
-        const double e = transfer_error(H, A, x1[i], y1[i], x2[i], y2[i]);
-        const bool in = e < thr;
-        if (mask) mask[i] = in ? 1 : 0;
-        if (in) {
-            pc += 1.0;
-            pe = pe + e;
-            px = px + x1[i];
-            py = py + y1[i];
-        }
-    }
-    const double cnt = wave_sum(pc);
-    const double se = wave_sum(pe), sx = wave_sum(px), sy = wave_sum(py);
-    const int n = (int)cnt;
-    if (n >= 4) {  // isDegenerate on pts1(inliers) (:506-513, :537-574)
-        const double mx = sx / cnt, my = sy / cnt;
-        double pxx = 0, pxy = 0, pyy = 0;
-        for (int64_t i = lane; i < m; i += 64) {
-            const double e = transfer_error(H, A, x1[i], y1[i], x2[i], y2[i]);
-            if (e < thr) {
-                const double dx = x1[i] - mx, dy = y1[i] - my;
-                pxx = pxx + dx * dx;
-                pxy = pxy + dx * dy;
-                pyy = pyy + dy * dy;
-            }
-        }
-        const double sxx = wave_sum(pxx), sxy = wave_sum(pxy), syy = wave_sum(pyy);
-        const double hs = 0.5 * (sxx + syy), hd = 0.5 * (sxx - syy);
-        const double r = sqrt(hd * hd + sxy * sxy);
-        const double l1 = hs + r;
-        double l2 = hs - r;
-        if (l2 < 0) l2 = 0;
-        const double s1 = sqrt(l1), s2 = sqrt(l2);
-        if (s2 / s1 < 1e-3) {
-            if (mask)
-                for (int64_t i = lane; i < m; i += 64) mask[i] = 0;
-            *mean_err = NAN;
-            return 0;
-        }
-    }
-    *mean_err = n > 0 ? se / cnt : NAN;
-    return n;
-}
-
-// MLESAC evaluateModel (estimateTransformationMLESAC.m:258-295, :534-562): one-way distance of H*x1 to x2,
-// truncated at thr; returns the sum of the truncated distances (wave order), *n_inl = #(d < thr).
-__device__ __forceinline__ double oneway_dist(const Mat3& H, double x1, double y1, double x2, double y2) {
-    const double X = (M3(H, 0, 0) * x1 + M3(H, 0, 1) * y1) + M3(H, 0, 2);
-    const double Y = (M3(H, 1, 0) * x1 + M3(H, 1, 1) * y1) + M3(H, 1, 2);
-    const double W = (M3(H, 2, 0) * x1 + M3(H, 2, 1) * y1) + M3(H, 2, 2);
-    const double dx = X / W - x2, dy = Y / W - y2;
-    double d = sqrt(dx * dx + dy * dy);
-    if (fabs(W) < kDblEps) d = INFINITY;
-    return d;
-}
-__device__ double wave_mlesac_eval(const Mat3& H, const double* __restrict__ x1, const double* __restrict__ y1,
-                                   const double* __restrict__ x2, const double* __restrict__ y2, int64_t m, double thr,
-                                   uint8_t* __restrict__ mask, int* n_inl) {
-    const int lane = threadIdx.x & 63;
-    double ps = 0, pc = 0;
-    for (int64_t i = lane; i < m; i += 64) {
-        double d = oneway_dist(H, x1[i], y1[i], x2[i], y2[i]);
-        if (d > thr) d = thr;  // NaN stays NaN
-        const bool in = d < thr;
-        if (mask) mask[i] = in ? 1 : 0;
-        ps = ps + d;
-        if (in) pc += 1.0;
-    }
-    *n_inl = (int)wave_sum(pc);
-    return wave_sum(ps);
-}
-
-// valid [pair][draw] -> the chunk-local [active pair][draw of the chunk] order the score kernels and the host replay walk
-__global__ void valid_chunk_kernel(const int* __restrict__ act, int n_act, int c0, int nc, int n_samples,
-                                   const uint8_t* __restrict__ valid_abs, uint8_t* __restrict__ valid_loc) {
-    const int64_t wid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (wid >= (int64_t)n_act * nc) return;
-    valid_loc[wid] = valid_abs[(int64_t)act[wid / nc] * n_samples + c0 + (int)(wid % nc)];
-}
-
-__global__ __launch_bounds__(256) void mlesac_score_kernel(
-    const double* __restrict__ pts1, const double* __restrict__ pts2, int64_t ldp,
-    const int64_t* __restrict__ pair_ptr, const int* __restrict__ act, int n_act, int c0, int nc,
-    int n_samples, const double* __restrict__ Hs,
-    const uint8_t* __restrict__ valid, double thr, int32_t* __restrict__ n_inl, double* __restrict__ acc_dis) {
-    const int64_t wid = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);  // (active pair, draw of the chunk)
-    if (wid >= (int64_t)n_act * nc) return;
-    const int lane = threadIdx.x & 63;
-    if (!valid[wid]) {
-        if (lane == 0) {
-            n_inl[wid] = 0;
-            acc_dis[wid] = NAN;
-        }
-        return;
-    }
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    Mat3 H;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = Hs[gid * 9 + e];
-    int n;
-    const double acc = wave_mlesac_eval(H, pts1 + r0, pts1 + ldp + r0, pts2 + r0, pts2 + ldp + r0, m, thr, nullptr, &n);
-    if (lane == 0) {
-        n_inl[wid] = n;
-        acc_dis[wid] = acc;
-    }
-}
-
-__device__ __forceinline__ int wave_find_inliers_any(int type, const Mat3& H, const double* x1, const double* y1,
-                                                     const double* x2, const double* y2, int64_t m, double thr,
-                                                     uint8_t* mask, double* mean_err);  // (defined with the other transformTypes)
-
-// one wave per (pair, draw); 4 waves per block
-__global__ __launch_bounds__(256) void ransac_score_kernel(int type,
-    const double* __restrict__ pts1, const double* __restrict__ pts2, int64_t ldp,
-    const int64_t* __restrict__ pair_ptr, const int* __restrict__ act, int n_act, int c0, int nc,
-    int n_samples, const double* __restrict__ Hs,
-    const uint8_t* __restrict__ valid, double thr, int32_t* __restrict__ n_inl,
-    double* __restrict__ mean_err) {
-    const int64_t wid = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);  // (active pair, draw of the chunk)
-    if (wid >= (int64_t)n_act * nc) return;
-    const int lane = threadIdx.x & 63;
-    if (!valid[wid]) {
-        if (lane == 0) {
-            n_inl[wid] = 0;
-            mean_err[wid] = NAN;
-        }
-        return;
-    }
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    Mat3 H;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = Hs[gid * 9 + e];
-    double me;
-    const int n = wave_find_inliers_any(type, H, pts1 + r0, pts1 + ldp + r0, pts2 + r0, pts2 + ldp + r0, m, thr,
-                                        nullptr, &me);
-    if (lane == 0) {
-        n_inl[wid] = n;
-        mean_err[wid] = me;
-    }
-}
-
-// explicit-hypothesis scoring for aps_ransac_score: one wave per hypothesis, optional masks
-__global__ __launch_bounds__(256) void ransac_score_explicit_kernel(int type,
-    const double* __restrict__ p1, const double* __restrict__ p2, int64_t ldp, int64_t m,
-    const double* __restrict__ Hs, int n_hyp, double thr, int32_t* __restrict__ n_inl,
-    double* __restrict__ mean_err, uint8_t* __restrict__ mask) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= n_hyp) return;
-    Mat3 H;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = Hs[(int64_t)t * 9 + e];
-    double me;
-    const int n = wave_find_inliers_any(type, H, p1, p1 + ldp, p2, p2 + ldp, m, thr,
-                                        mask ? mask + (int64_t)t * m : nullptr, &me);
-    if ((threadIdx.x & 63) == 0) {
-        n_inl[t] = n;
-        mean_err[t] = me;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// finalize: one wave per pair (:146-181)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ransac_finalize_kernel(
-    const double* __restrict__ pts1, const double* __restrict__ pts2, int64_t ldp,
-    const int64_t* __restrict__ pair_ptr, int n_samples, const double* __restrict__ Hs,
-    const int32_t* __restrict__ best_it, double thr, double* __restrict__ models,
-    uint8_t* __restrict__ mask, uint8_t* __restrict__ scratch_mask, int32_t* __restrict__ found,
-    int32_t* __restrict__ n_final, int mlesac) {
-    // one 9x9 problem per workgroup: two columns (work matrix / broadcast scratch), 2.6 KB - with the fit kernel's
-    // 64-column layout (83 KB) only one workgroup fitted a CU and the pairs ran in two rounds
-    __shared__ __attribute__((aligned(16))) double lds_fin[2 * 81 * 2];
-    double* sG = lds_fin;
-    double* sV = lds_fin + 81 * 2;
-    const int p = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    const double *x1 = pts1 + r0, *y1 = pts1 + ldp + r0, *x2 = pts2 + r0, *y2 = pts2 + ldp + r0;
-    uint8_t* out_mask = mask + r0;
-    uint8_t* tmp_mask = scratch_mask + r0;
-    const int bi = best_it[p];
-    if (bi < 0) {
-        for (int64_t i = lane; i < m; i += 64) out_mask[i] = 0;
-        if (lane < 9) models[(int64_t)p * 9 + lane] = NAN;
-        if (lane == 0) {
-            found[p] = 0;
-            n_final[p] = 0;
-        }
-        return;
-    }
-    Mat3 Hb;
-    for (int e = 0; e < 9; ++e) Hb.m[e] = Hs[((int64_t)p * n_samples + bi) * 9 + e];
-    double me;
-    int nb;
-    if (mlesac) {
-        (void)wave_mlesac_eval(Hb, x1, y1, x2, y2, m, thr, out_mask, &nb);
-        if (nb < 4) {  // isFound needs sum(bestInliers) >= sampleSize (estimateTransformationMLESAC.m:213-214)
-            for (int64_t i = lane; i < m; i += 64) out_mask[i] = 0;
-            if (lane < 9) models[(int64_t)p * 9 + lane] = NAN;
-            if (lane == 0) {
-                found[p] = 0;
-                n_final[p] = 0;
-            }
-            return;
-        }
-    } else {
-        nb = wave_find_inliers(Hb, x1, y1, x2, y2, m, thr, out_mask, &me);
-    }
-    __threadfence_block();
-    // Refit on the inliers (:146-181 -> estimateHomography).  Its sums - centroids, mean distances, the Gram sums of the DLT
-    // rows - run in the WAVE ORDER over the point index (round 4; oracle/ransac_oracle.c header): lane l accumulates the
-    // inliers i = l, l + 64, ... in ascending order and the 64 partials meet in the xor butterfly, like the other inlier
-    // sums.  Rounds 1-3 summed sequentially in index order, which made every lane of the pair's wave walk all of its
-    // ~3 700 matches four times behind uniform mask tests: ~134 k serial vector instructions and 1.3 of the 3.4 ms of
-    // the whole RANSAC stage for ~200 pairs, no faster for the 28 pairs of one rank of eight.
-    Norm n1, n2;
-    {
-        double sx = 0, sy = 0, ux = 0, uy = 0;
-        for (int64_t i = lane; i < m; i += 64)
-            if (out_mask[i]) {
-                sx = sx + x1[i];
-                sy = sy + y1[i];
-                ux = ux + x2[i];
-                uy = uy + y2[i];
-            }
-        sx = wave_sum(sx);
-        sy = wave_sum(sy);
-        ux = wave_sum(ux);
-        uy = wave_sum(uy);
-        const double dn = (double)nb;
-        const double cx = sx / dn, cy = sy / dn, dx2 = ux / dn, dy2 = uy / dn;
-        double sd = 0, ud = 0;
-        for (int64_t i = lane; i < m; i += 64)
-            if (out_mask[i]) {
-                const double ax = x1[i] - cx, ay = y1[i] - cy;
-                sd = sd + sqrt(ax * ax + ay * ay);
-                const double bx = x2[i] - dx2, by = y2[i] - dy2;
-                ud = ud + sqrt(bx * bx + by * by);
-            }
-        sd = wave_sum(sd);
-        ud = wave_sum(ud);
-        n1.s = norm_scale(sd / dn, mlesac);
-        n1.tx = -n1.s * cx;
-        n1.ty = -n1.s * cy;
-        n1.cx = cx;
-        n1.cy = cy;
-        n2.s = norm_scale(ud / dn, mlesac);
-        n2.tx = -n2.s * dx2;
-        n2.ty = -n2.s * dy2;
-        n2.cx = dx2;
-        n2.cy = dy2;
-    }
-    // Gram matrix: every lane keeps the 45 upper-triangular partial sums of ITS inliers (rows in the reference's order:
-    // RANSAC all "x" rows, then all "y" rows; MLESAC per inlier its "v" row, then its "u" row), then the butterfly
-    double g[45];
-#pragma unroll
-    for (int e = 0; e < 45; ++e) g[e] = 0;
-    auto add_row = [&](int half, double x, double y, double u, double v) __attribute__((always_inline)) {
-        double a[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) a[k] = dlt_entry(k, half, x, y, u, v);
-        int e = 0;
-#pragma unroll
-        for (int pp = 0; pp < 9; ++pp)
-#pragma unroll
-            for (int qq = pp; qq < 9; ++qq, ++e) g[e] = g[e] + a[pp] * a[qq];
-    };
-    if (mlesac) {
-        for (int64_t i = lane; i < m; i += 64)
-            if (out_mask[i]) {
-                const double x = (x1[i] - n1.cx) * n1.s, y = (y1[i] - n1.cy) * n1.s;
-                const double u = (x2[i] - n2.cx) * n2.s, v = (y2[i] - n2.cy) * n2.s;
-                add_row(1, x, y, u, v);
-                add_row(0, x, y, u, v);
-            }
-    } else {
-        for (int half = 0; half < 2; ++half)
-            for (int64_t i = lane; i < m; i += 64)
-                if (out_mask[i]) {
-                    const double x = n1.s * x1[i] + n1.tx, y = n1.s * y1[i] + n1.ty;
-                    const double u = n2.s * x2[i] + n2.tx, v = n2.s * y2[i] + n2.ty;
-                    add_row(half, x, y, u, v);
-                }
-    }
-    {
-        int e = 0;
-#pragma unroll
-        for (int pp = 0; pp < 9; ++pp)
-#pragma unroll
-            for (int qq = pp; qq < 9; ++qq, ++e) {
-                const double t = wave_sum(g[e]);
-                if (lane == 0) sG[(pp * 9 + qq) * 2 + 0] = t;  // column 0 of the work matrix
-            }
-    }
-    __syncthreads();
-    Mat3 Hr;
-    const bool ok = gram_to_h_wave(sG, sV, lane, n1, n2, Hr, mlesac) && (mlesac || check_model(Hr));
-    bool use_refit = false;
-    int nr = 0;
-    if (mlesac) {  // :216-236: the refit is the answer; invalid or no inlier left -> not found
-        if (ok) (void)wave_mlesac_eval(Hr, x1, y1, x2, y2, m, thr, tmp_mask, &nr);
-        if (!ok || nr < 1) {
-            __threadfence_block();
-            for (int64_t i = lane; i < m; i += 64) out_mask[i] = 0;
-            if (lane < 9) models[(int64_t)p * 9 + lane] = NAN;
-            if (lane == 0) {
-                found[p] = 0;
-                n_final[p] = 0;
-            }
-            return;
-        }
-        use_refit = true;
-    } else if (ok) {
-        nr = wave_find_inliers(Hr, x1, y1, x2, y2, m, thr, tmp_mask, &me);
-        use_refit = nr >= 4;
-    }
-    if (use_refit) {
-        __threadfence_block();
-        for (int64_t i = lane; i < m; i += 64) out_mask[i] = tmp_mask[i];
-    }
-    if (lane < 9) models[(int64_t)p * 9 + lane] = use_refit ? Hr.m[lane] : Hb.m[lane];
-    if (lane == 0) {
-        found[p] = 1;
-        n_final[p] = use_refit ? nr : nb;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The other transformTypes: 'affine' (:227-288), 'similarity' (:290-356), 'rigid' (:358-421), 'translation'
-// (:423-452), findInliers' one-way error for them (:483-497).  svd / pinv / median are the closed forms of the
-// oracle's second header (oracle/ransac_oracle.c), evaluated here in the same order.
-// ------------------------------------------------------------------------------------------------
-__host__ __device__ inline int tf_min_points(int type) {
-    return type == APS_TFORM_AFFINE ? 3 : (type == APS_TFORM_SIMILARITY || type == APS_TFORM_RIGID) ? 2 : type == APS_TFORM_TRANSLATION ? 1 : 4;
-}
-
-// H = T2 \ Hn * T1 (left to right; Hn row-major), then the exact affine last row
-__device__ __forceinline__ void denormalize_affine(const double* Hn, const Norm& n1, const Norm& n2, Mat3& H) {
-    Mat3 M;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double m2 = Hn[6 + c];
-        M3(M, 2, c) = m2;
-        M3(M, 1, c) = (Hn[3 + c] - n2.ty * m2) / n2.s;
-        M3(M, 0, c) = (Hn[c] - n2.tx * m2) / n2.s;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        M3(H, r, 0) = M3(M, r, 0) * n1.s;
-        M3(H, r, 1) = M3(M, r, 1) * n1.s;
-        M3(H, r, 2) = (M3(M, r, 0) * n1.tx + M3(M, r, 1) * n1.ty) + M3(M, r, 2);
-    }
-    M3(H, 2, 0) = 0.0;
-    M3(H, 2, 1) = 0.0;
-    M3(H, 2, 2) = 1.0;
-}
-
-// cyclic Jacobi on a symmetric 3x3 (row-major), the rotation rule of jacobi9
+// cyclic Jacobi on a symmetric 3x3 in registers (row-major)
 __device__ __forceinline__ void jacobi3(double* G, double* V) {
 #pragma unroll
     for (int e = 0; e < 9; ++e) V[e] = (e % 4 == 0) ? 1.0 : 0.0;
@@ -790,12 +257,9 @@ __device__ __forceinline__ void jacobi3(double* G, double* V) {
             for (int q = p + 1; q < 3; ++q) {
                 const double gpq = G[3 * p + q];
                 const double gpp = G[3 * p + p], gqq = G[3 * q + q];
-                if (!(fabs(gpq) <= 1e-300 || fabs(gpq) <= 1e-18 * sqrt(fabs(gpp * gqq)))) {
+                double t, c, s;
+                if (!jacobi_rotation(gpp, gqq, gpq, t, c, s)) {
                     rotated = true;
-                    const double theta = (gqq - gpp) / (2.0 * gpq);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0);
-                    const double s = t * c;
                     const int k = 3 - p - q;
                     const double gkp = G[3 * k + p], gkq = G[3 * k + q];
                     const double np_ = c * gkp - s * gkq;
@@ -820,19 +284,170 @@ __device__ __forceinline__ void jacobi3(double* G, double* V) {
     }
 }
 
-// MATLAB's median of two values
-__device__ __forceinline__ double median2(double a, double b) {
-    if (isnan(a) || isnan(b)) return NAN;
-    if (b < a) {
-        const double t = a;
-        a = b;
-        b = t;
-    }
-    const int sa = (a > 0) - (a < 0), sb = (b > 0) - (b < 0);
-    if (sa != sb || isinf(a) || isinf(b)) return (a + b) / 2;
-    return a + (b - a) / 2;
+// h = the eigenvector of the smallest eigenvalue, after a Jacobi run (eigenvalues on G's diagonal, vectors in V's columns)
+template <int N, int S>
+__device__ __forceinline__ void smallest_eigvec(LdsMat<S> G, LdsMat<S> V, double* h) {
+    int kmin = 0;
+    for (int k = 1; k < N; ++k)
+        if (G(k, k) < G(kmin, kmin)) kmin = k;
+    for (int k = 0; k < N; ++k) h[k] = V(k, kmin);
 }
 
+// The null vector of the system whose Gram matrix fills the upper triangle of G: one problem per lane ...
+template <int N>
+__device__ __forceinline__ void null_vector(LdsMat<64> G, LdsMat<64> V, double* h) {
+    for (int p = 0; p < N; ++p)
+        for (int q = 0; q < p; ++q) G(p, q) = G(q, p);
+    jacobi9<64, N>(G, V);
+    smallest_eigvec<N>(G, V, h);
+}
+// ... and one per workgroup; every lane receives the same h.
+template <int N>
+__device__ __forceinline__ void null_vector_wave(LdsMat<2> G, LdsMat<2> V, int lane, double* h) {
+    if (lane == 0)
+        for (int p = 0; p < N; ++p)
+            for (int q = 0; q < p; ++q) G(p, q) = G(q, p);
+    __syncthreads();
+    jacobi9_wave<N>(G, V, lane);
+    smallest_eigvec<N>(G, V, h);
+}
+
+// k-th smallest (0-based) of the m sortable keys in `keys` (slots that do not take part hold ~0ull and k < #valid): an
+// MSB-first radix select, one counting pass per bit, all 64 lanes.  Exact and independent of the order of the slots.
+__device__ unsigned long long wave_kth_key(const unsigned long long* __restrict__ keys, int64_t m, int64_t k) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long prefix = 0;
+    for (int bit = 63; bit >= 0; --bit) {
+        int c = 0;
+        for (int64_t i = lane; i < m; i += 64) c += ((keys[i] >> bit) == (prefix >> bit)) ? 1 : 0;
+        const int64_t zeros = wave_sum_i(c);  // keys that agree with the prefix above `bit` and have a 0 there
+        if (k >= zeros) {
+            k -= zeros;
+            prefix |= 1ull << bit;
+        }
+    }
+    return prefix;
+}
+__device__ __forceinline__ unsigned long long sort_key(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_value(unsigned long long k) {
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// normalisation (normalizePoints :579-610; normalizePointsHartleyZisserman, estimateTransformationMLESAC.m:640-671)
+// ------------------------------------------------------------------------------------------------
+struct Norm {
+    double s, tx, ty;
+    double cx, cy;  // the centroid: MLESAC's normalised points are (p - centroid) * s (:667-671), RANSAC's are
+                    // T * [p; 1] = s * p + t (:604-606)
+};
+__device__ __forceinline__ double norm_x(const Norm& n, double x, int mlesac) { return mlesac ? (x - n.cx) * n.s : n.s * x + n.tx; }
+__device__ __forceinline__ double norm_y(const Norm& n, double y, int mlesac) { return mlesac ? (y - n.cy) * n.s : n.s * y + n.ty; }
+
+// From a centroid and the mean distance to it.  Scale: RANSAC 1/md (:592), MLESAC sqrt(2)/md guarded against md == 0 (:653-657)
+__device__ __forceinline__ Norm make_norm(double cx, double cy, double mean_dist, int mlesac) {
+    Norm n;
+    n.s = !mlesac ? 1.0 / mean_dist : mean_dist > 0 ? sqrt(2.0) / mean_dist : 1.0;
+    n.tx = -n.s * cx;
+    n.ty = -n.s * cy;
+    n.cx = cx;
+    n.cy = cy;
+    return n;
+}
+
+// Both point sets of an ordered selection, sums in that order.  each(body) calls body(x1, y1, x2, y2) for every selected
+// point in ascending order.
+template <class Each>
+__device__ __forceinline__ void normalize_points(int n, Each&& each, int mlesac, Norm& n1, Norm& n2) {
+    const double dn = (double)n;
+    double sx = 0, sy = 0, ux = 0, uy = 0;
+    each([&](double a, double b, double c, double d) {
+        sx = sx + a;
+        sy = sy + b;
+        ux = ux + c;
+        uy = uy + d;
+    });
+    const double ax = sx / dn, ay = sy / dn, bx = ux / dn, by = uy / dn;
+    double sd = 0, ud = 0;
+    each([&](double a, double b, double c, double d) {
+        const double dx = a - ax, dy = b - ay;
+        sd = sd + sqrt(dx * dx + dy * dy);
+        const double ex = c - bx, ey = d - by;
+        ud = ud + sqrt(ex * ex + ey * ey);
+    });
+    n1 = make_norm(ax, ay, sd / dn, mlesac);
+    n2 = make_norm(bx, by, ud / dn, mlesac);
+}
+
+// H = T2 \ Tn * T1 (left to right; Tn row-major)
+__device__ __forceinline__ void denormalize(const double* Tn, const Norm& n1, const Norm& n2, Mat3& H) {
+    Mat3 M;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double m2 = Tn[6 + c];
+        M3(M, 2, c) = m2;
+        M3(M, 1, c) = (Tn[3 + c] - n2.ty * m2) / n2.s;
+        M3(M, 0, c) = (Tn[c] - n2.tx * m2) / n2.s;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        M3(H, r, 0) = M3(M, r, 0) * n1.s;
+        M3(H, r, 1) = M3(M, r, 1) * n1.s;
+        M3(H, r, 2) = (M3(M, r, 0) * n1.tx + M3(M, r, 1) * n1.ty) + M3(M, r, 2);
+    }
+}
+
+// denormalizeTform's tform ./ tform(end) (estimateTransformationMLESAC.m:713-714)
+__device__ __forceinline__ void divide_by_last(Mat3& H) {
+    const double d = H.m[8];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) H.m[e] = H.m[e] / d;
+}
+
+// ------------------------------------------------------------------------------------------------
+// estimators
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline int tf_min_points(int type) {
+    return type == APS_TFORM_AFFINE ? 3 : (type == APS_TFORM_SIMILARITY || type == APS_TFORM_RIGID) ? 2 : type == APS_TFORM_TRANSLATION ? 1 : 4;
+}
+
+// ---- 'projective': the normalised DLT (:188-225; estimateTransformationMLESAC.m:345-387) ----
+// Row `half` (0: x-row, 1: y-row) of the DLT matrix for one normalised correspondence (:209-212)
+__device__ __forceinline__ double dlt_entry(int k, int half, double x, double y, double u, double v) {
+    const double w = half ? v : u;
+    if (k >= 6) return k == 6 ? x * w : (k == 7 ? y * w : w);
+    const int kk = half ? k - 3 : k;
+    if (kk < 0 || kk > 2) return 0.0;
+    return kk == 0 ? -x : (kk == 1 ? -y : -1.0);
+}
+
+// From the null vector of the DLT system to the denormalised H (:214-224).  Returns false if not finite.
+__device__ __forceinline__ bool null_vector_to_h(const double* h, const Norm& n1, const Norm& n2, Mat3& H, int mlesac) {
+    double Tn[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Tn[k] = h[k] / h[8];
+    denormalize(Tn, n1, n2, H);
+    if (mlesac) divide_by_last(H);
+    return all_finite(H);
+}
+__device__ bool gram_to_h(LdsMat<64> G, LdsMat<64> V, const Norm& n1, const Norm& n2, Mat3& H, int mlesac) {
+    double h[9];
+    null_vector<9>(G, V, h);
+    return null_vector_to_h(h, n1, n2, H, mlesac);
+}
+// every lane returns the same H and verdict
+__device__ bool gram_to_h_wave(LdsMat<2> G, LdsMat<2> V, int lane, const Norm& n1, const Norm& n2, Mat3& H, int mlesac) {
+    double h[9];
+    null_vector_wave<9>(G, V, lane, h);
+    return null_vector_to_h(h, n1, n2, H, mlesac);
+}
+
+// ---- RANSAC's 'affine' (:227-288), 'similarity' (:290-356), 'rigid' (:358-421), 'translation' (:423-452).  svd / pinv /
+// median are the closed forms of the oracle's second header (oracle/ransac_oracle.c), evaluated here in the same order. ----
 // what a median callback may need to form its per-point values
 struct FitCtx {
     Norm n1, n2;
@@ -840,10 +455,10 @@ struct FitCtx {
 };
 enum { MED_DX = 0, MED_DY = 1, MED_RATIO = 2 };
 
-// The estimators over an ordered point selection.  each(body) calls body(x1, y1, x2, y2) for every selected point in
-// ascending order; med(which, ctx, &n_valid) returns the MATLAB median of the per-point quantity `which` over the selection
-// (MED_RATIO: |pts2c| / |pts1c| over the points with |pts1c| > 1e-10; n_valid = how many there were).  Every caller of
-// one fit evaluates the same expressions in the same order, so a wave may run it redundantly in all lanes.
+// The estimators over an ordered point selection.  each as in normalize_points; med(which, ctx, &n_valid) returns the
+// MATLAB median of the per-point quantity `which` over the selection (MED_RATIO: |pts2c| / |pts1c| over the points with
+// |pts1c| > 1e-10; n_valid = how many there were).  Every caller of one fit evaluates the same expressions in the same
+// order, so a wave may run it redundantly in all lanes.
 template <class Each, class Med>
 __device__ __forceinline__ bool fit_tform(int type, int n, Each&& each, Med&& med, Mat3& H) {
     FitCtx cx{};
@@ -851,40 +466,13 @@ __device__ __forceinline__ bool fit_tform(int type, int n, Each&& each, Med&& me
         int nv;
         const double tx = med(MED_DX, cx, &nv);
         const double ty = med(MED_DY, cx, &nv);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) H.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
+        H = identity3();
         M3(H, 0, 2) = tx;
         M3(H, 1, 2) = ty;
         return isfinite(tx) && isfinite(ty);
     }
     const double dn = (double)n;
-    {  // normalizePoints (:579-610) of both sets
-        double sx = 0, sy = 0, ux = 0, uy = 0;
-        each([&](double a, double b, double c, double d) {
-            sx = sx + a;
-            sy = sy + b;
-            ux = ux + c;
-            uy = uy + d;
-        });
-        const double ax = sx / dn, ay = sy / dn, bx = ux / dn, by = uy / dn;
-        double sd = 0, ud = 0;
-        each([&](double a, double b, double c, double d) {
-            const double dx = a - ax, dy = b - ay;
-            sd = sd + sqrt(dx * dx + dy * dy);
-            const double ex = c - bx, ey = d - by;
-            ud = ud + sqrt(ex * ex + ey * ey);
-        });
-        cx.n1.s = 1.0 / (sd / dn);
-        cx.n1.tx = -cx.n1.s * ax;
-        cx.n1.ty = -cx.n1.s * ay;
-        cx.n1.cx = ax;
-        cx.n1.cy = ay;
-        cx.n2.s = 1.0 / (ud / dn);
-        cx.n2.tx = -cx.n2.s * bx;
-        cx.n2.ty = -cx.n2.s * by;
-        cx.n2.cx = bx;
-        cx.n2.cy = by;
-    }
+    normalize_points(n, each, 0, cx.n1, cx.n2);
     const Norm n1 = cx.n1, n2 = cx.n2;
     double Hn[9];
     if (type == APS_TFORM_AFFINE) {
@@ -984,11 +572,11 @@ __device__ __forceinline__ bool fit_tform(int type, int n, Each&& each, Med&& me
     Hn[6] = 0;
     Hn[7] = 0;
     Hn[8] = 1;
-    denormalize_affine(Hn, n1, n2, H);
-#pragma unroll
-    for (int e = 0; e < 9; ++e)
-        if (!isfinite(H.m[e])) return false;
-    return true;
+    denormalize(Hn, n1, n2, H);
+    M3(H, 2, 0) = 0.0;  // the exact affine last row
+    M3(H, 2, 1) = 0.0;
+    M3(H, 2, 2) = 1.0;
+    return all_finite(H);
 }
 
 // the per-point quantity a median runs over (valid = it takes part)
@@ -1032,265 +620,8 @@ __device__ __forceinline__ bool fit_sample(int type, const double* x1, const dou
     return fit_tform(type, K, each, med, H);
 }
 
-__global__ __launch_bounds__(64) void tform_fit_kernel(int type, const double* __restrict__ pts1, const double* __restrict__ pts2,
-                                                        int64_t ldp, const int64_t* __restrict__ pair_ptr,
-                                                        const int* __restrict__ act, int n_act, int c0, int nc,
-                                                        const uint32_t* __restrict__ sample_idx, int n_samples,
-                                                        double* __restrict__ Hs, uint8_t* __restrict__ valid) {
-    const int64_t wid = blockIdx.x * (int64_t)64 + threadIdx.x;
-    if (wid >= (int64_t)n_act * nc) return;
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    const int K = tf_min_points(type);
-    double x1[3], y1[3], x2[3], y2[3];
-    bool ok = m >= K;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint32_t id = k < K ? sample_idx[gid * 4 + k] : 1u;
-        if (k < K && (id < 1 || (int64_t)id > m)) ok = false;
-        const int64_t row = r0 + (ok ? (int64_t)id - 1 : 0);
-        const bool ld = ok && k < K;
-        x1[k] = ld ? pts1[row] : 0.0;
-        y1[k] = ld ? pts1[ldp + row] : 0.0;
-        x2[k] = ld ? pts2[row] : 0.0;
-        y2[k] = ld ? pts2[ldp + row] : 0.0;
-    }
-    Mat3 H;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = 0.0;
-    if (ok) {
-        bool fin;
-        if (K == 3)
-            fin = fit_sample<3>(type, x1, y1, x2, y2, H);
-        else if (K == 2)
-            fin = fit_sample<2>(type, x1, y1, x2, y2, H);
-        else
-            fin = fit_sample<1>(type, x1, y1, x2, y2, H);
-        ok = fin && check_model(H);
-    }
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hs[gid * 9 + e] = H.m[e];
-    valid[gid] = ok ? 1 : 0;  // [pair][draw], like Hs (the score kernels read the chunk-local copy valid_chunk_kernel makes)
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off);
-        if (o > v) v = o;
-    }
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// findInliers (:444-516) for the affine family and translation: all 64 lanes of a wave, same arguments
-__device__ int wave_find_inliers_t(int type, const Mat3& H, const double* __restrict__ x1, const double* __restrict__ y1,
-                                   const double* __restrict__ x2, const double* __restrict__ y2, int64_t m, double thr,
-                                   uint8_t* __restrict__ mask, double* mean_err) {
-    const int lane = threadIdx.x & 63;
-    double scale = 1.0;  // max(abs([pts1_homog(:); pts2_homog(:)])): the homogeneous ones take part (:487)
-    if (type == APS_TFORM_TRANSLATION) {
-        for (int64_t i = lane; i < m; i += 64) {
-            if (fabs(x1[i]) > scale) scale = fabs(x1[i]);
-            if (fabs(y1[i]) > scale) scale = fabs(y1[i]);
-            if (fabs(x2[i]) > scale) scale = fabs(x2[i]);
-            if (fabs(y2[i]) > scale) scale = fabs(y2[i]);
-        }
-        scale = wave_max(scale);
-        thr = thr / scale;
-    }
-    auto error_of = [&](int64_t i) -> double {
-        const double X = (M3(H, 0, 0) * x1[i] + M3(H, 0, 1) * y1[i]) + M3(H, 0, 2);
-        const double Y = (M3(H, 1, 0) * x1[i] + M3(H, 1, 1) * y1[i]) + M3(H, 1, 2);
-        const double W = (M3(H, 2, 0) * x1[i] + M3(H, 2, 1) * y1[i]) + M3(H, 2, 2);
-        const double ex = x2[i] - X / W, ey = y2[i] - Y / W;
-        double e = sqrt(ex * ex + ey * ey);
-        if (type == APS_TFORM_TRANSLATION) e = e / scale;
-        if (!isfinite(e)) e = INFINITY;
-        if (fabs(W) < kDblEps) e = INFINITY;
-        return e;
-    };
-    double pc = 0, pe = 0, px = 0, py = 0;
-    for (int64_t i = lane; i < m; i += 64) {
-        const double e = error_of(i);
-        const bool in = e < thr;
-        if (mask) mask[i] = in ? 1 : 0;
-        if (in) {
-            pc += 1.0;
-            pe = pe + e;
-            px = px + x1[i];
-            py = py + y1[i];
-        }
-    }
-    const double cnt = wave_sum(pc);
-    const double se = wave_sum(pe), sx = wave_sum(px), sy = wave_sum(py);
-    const int n = (int)cnt;
-    if (type == APS_TFORM_AFFINE && n >= 3) {  // isDegenerate (:506-513, :537-574)
-        const double mx = sx / cnt, my = sy / cnt;
-        double pxx = 0, pxy = 0, pyy = 0;
-        for (int64_t i = lane; i < m; i += 64)
-            if (error_of(i) < thr) {
-                const double dx = x1[i] - mx, dy = y1[i] - my;
-                pxx = pxx + dx * dx;
-                pxy = pxy + dx * dy;
-                pyy = pyy + dy * dy;
-            }
-        const double sxx = wave_sum(pxx), sxy = wave_sum(pxy), syy = wave_sum(pyy);
-        const double hs = 0.5 * (sxx + syy), hd = 0.5 * (sxx - syy);
-        const double r = sqrt(hd * hd + sxy * sxy);
-        const double l1 = hs + r;
-        double l2 = hs - r;
-        if (l2 < 0) l2 = 0;
-        if (sqrt(l2) / sqrt(l1) < 1e-3) {
-            if (mask)
-                for (int64_t i = lane; i < m; i += 64) mask[i] = 0;
-            *mean_err = NAN;
-            return 0;
-        }
-    }
-    *mean_err = n > 0 ? se / cnt : NAN;
-    return n;
-}
-
-__device__ __forceinline__ int wave_find_inliers_any(int type, const Mat3& H, const double* x1, const double* y1,
-                                                     const double* x2, const double* y2, int64_t m, double thr,
-                                                     uint8_t* mask, double* mean_err) {
-    return type == APS_TFORM_PROJECTIVE ? wave_find_inliers(H, x1, y1, x2, y2, m, thr, mask, mean_err)
-                                        : wave_find_inliers_t(type, H, x1, y1, x2, y2, m, thr, mask, mean_err);
-}
-
-// k-th smallest (0-based) of the m sortable keys in `keys` (slots that do not take part hold ~0ull and k < #valid): an
-// MSB-first radix select, one counting pass per bit, all 64 lanes.  Exact and independent of the order of the slots.
-__device__ unsigned long long wave_kth_key(const unsigned long long* __restrict__ keys, int64_t m, int64_t k) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long prefix = 0;
-    for (int bit = 63; bit >= 0; --bit) {
-        int c = 0;
-        for (int64_t i = lane; i < m; i += 64) c += ((keys[i] >> bit) == (prefix >> bit)) ? 1 : 0;
-        const int64_t zeros = wave_sum_i(c);  // keys that agree with the prefix above `bit` and have a 0 there
-        if (k >= zeros) {
-            k -= zeros;
-            prefix |= 1ull << bit;
-        }
-    }
-    return prefix;
-}
-__device__ __forceinline__ unsigned long long sort_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(unsigned long long k) {
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
-// finalize for these types: one wave per pair (:146-181)
-__global__ __launch_bounds__(64) void tform_finalize_kernel(int type, const double* __restrict__ pts1,
-                                                             const double* __restrict__ pts2, int64_t ldp,
-                                                             const int64_t* __restrict__ pair_ptr, int n_samples,
-                                                             const double* __restrict__ Hs, const int32_t* __restrict__ best_it,
-                                                             double thr, double* __restrict__ models, uint8_t* __restrict__ mask,
-                                                             uint8_t* __restrict__ scratch_mask,
-                                                             unsigned long long* __restrict__ scratch_keys,
-                                                             int32_t* __restrict__ found, int32_t* __restrict__ n_final) {
-    const int p = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    const int min_pts = tf_min_points(type);
-    const double *x1 = pts1 + r0, *y1 = pts1 + ldp + r0, *x2 = pts2 + r0, *y2 = pts2 + ldp + r0;
-    uint8_t* out_mask = mask + r0;
-    uint8_t* tmp_mask = scratch_mask + r0;
-    unsigned long long* keys = scratch_keys + r0;
-    const int bi = best_it[p];
-    if (bi < 0) {
-        for (int64_t i = lane; i < m; i += 64) out_mask[i] = 0;
-        if (lane < 9) models[(int64_t)p * 9 + lane] = NAN;
-        if (lane == 0) {
-            found[p] = 0;
-            n_final[p] = 0;
-        }
-        return;
-    }
-    Mat3 Hb;
-    for (int e = 0; e < 9; ++e) Hb.m[e] = Hs[((int64_t)p * n_samples + bi) * 9 + e];
-    double me;
-    const int nb = wave_find_inliers_t(type, Hb, x1, y1, x2, y2, m, thr, out_mask, &me);
-    __threadfence_block();
-    __syncthreads();
-    // the refit walks the inliers in ascending order, staged through LDS 64 at a time; every lane evaluates the same sums
-    __shared__ double s_pt[4][64];
-    __shared__ uint8_t s_in[64];
-    auto each = [&](auto&& body) {
-        for (int64_t base = 0; base < m; base += 64) {
-            const int64_t i = base + lane;
-            const bool have = i < m;
-            s_pt[0][lane] = have ? x1[i] : 0.0;
-            s_pt[1][lane] = have ? y1[i] : 0.0;
-            s_pt[2][lane] = have ? x2[i] : 0.0;
-            s_pt[3][lane] = have ? y2[i] : 0.0;
-            s_in[lane] = have ? out_mask[i] : (uint8_t)0;
-            __syncthreads();
-            for (int e = 0; e < 64; ++e)
-                if (s_in[e]) body(s_pt[0][e], s_pt[1][e], s_pt[2][e], s_pt[3][e]);
-            __syncthreads();
-        }
-    };
-    auto med = [&](int which, const FitCtx& cx, int* nv) -> double {
-        int c_valid = 0, c_nan = 0;
-        for (int64_t i = lane; i < m; i += 64) {
-            unsigned long long key = ~0ull;
-            if (out_mask[i]) {
-                bool valid;
-                const double q = med_value(which, cx, x1[i], y1[i], x2[i], y2[i], &valid);
-                if (valid) {
-                    ++c_valid;
-                    if (isnan(q)) ++c_nan;
-                    key = sort_key(q);
-                }
-            }
-            keys[i] = key;
-        }
-        const int n = wave_sum_i(c_valid), n_nan = wave_sum_i(c_nan);
-        __threadfence_block();
-        __syncthreads();
-        *nv = n;
-        if (n == 0 || n_nan > 0) return NAN;
-        if (n & 1) return key_value(wave_kth_key(keys, m, (n - 1) / 2));
-        const double a = key_value(wave_kth_key(keys, m, n / 2 - 1)), b = key_value(wave_kth_key(keys, m, n / 2));
-        return median2(a, b);
-    };
-    Mat3 Hr;
-    const bool ok = fit_tform(type, nb, each, med, Hr) && check_model(Hr);
-    bool use_refit = false;
-    int nr = 0;
-    if (ok) {
-        nr = wave_find_inliers_t(type, Hr, x1, y1, x2, y2, m, thr, tmp_mask, &me);
-        use_refit = nr >= min_pts;
-    }
-    if (use_refit) {
-        __threadfence_block();
-        __syncthreads();
-        for (int64_t i = lane; i < m; i += 64) out_mask[i] = tmp_mask[i];
-    }
-    if (lane < 9) models[(int64_t)p * 9 + lane] = use_refit ? Hr.m[lane] : Hb.m[lane];
-    if (lane == 0) {
-        found[p] = 1;
-        n_final[p] = use_refit ? nr : nb;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// MLESAC for the other transformationTypes (estimateTransformationMLESAC.m): estimateAffine (:389-424, null vector of
-// the 2n x 7 system), estimateSimilarity (:426-458, 2n x 5), estimateRigid (:460-490, Kabsch on the raw points, closed
-// form), estimateTranslation (:492-510, the mean displacement), evaluateTranslation2d (:578-598).
-// ------------------------------------------------------------------------------------------------
+// ---- MLESAC's estimateAffine (:389-424, null vector of the 2n x 7 system), estimateSimilarity (:426-458, 2n x 5),
+// estimateRigid (:460-490, Kabsch on the raw points, closed form), estimateTranslation (:492-510, the mean displacement) ----
 // entry k of a constraint row: half 1 = the point's "v" row (odd rows of :404-407 / :441-444), half 0 its "u" row
 __device__ __forceinline__ double mlesac_entry(int type, int k, int half, double x, double y, double u, double v) {
     if (type == APS_TFORM_AFFINE) {
@@ -1315,35 +646,16 @@ __device__ __forceinline__ bool mlesac_h_to_model(int type, const double* h, con
         Tn[4] = h[0] / h[4];
         Tn[5] = h[3] / h[4];
     }
-    Mat3 M;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double m2 = Tn[6 + c];
-        M3(M, 2, c) = m2;
-        M3(M, 1, c) = (Tn[3 + c] - n2.ty * m2) / n2.s;
-        M3(M, 0, c) = (Tn[c] - n2.tx * m2) / n2.s;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        M3(H, r, 0) = M3(M, r, 0) * n1.s;
-        M3(H, r, 1) = M3(M, r, 1) * n1.s;
-        M3(H, r, 2) = (M3(M, r, 0) * n1.tx + M3(M, r, 1) * n1.ty) + M3(M, r, 2);
-    }
-    const double d = H.m[8];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = H.m[e] / d;
-#pragma unroll
-    for (int e = 0; e < 9; ++e)
-        if (!isfinite(H.m[e])) return false;
-    return true;
+    denormalize(Tn, n1, n2, H);
+    divide_by_last(H);
+    return all_finite(H);
 }
 
-// rigid / translation over an ordered selection (`each` as in fit_tform); every caller evaluates the same expressions
+// rigid / translation over an ordered selection; every caller evaluates the same expressions
 template <class Each>
 __device__ __forceinline__ bool mlesac_fit_closed(int type, int n, Each&& each, Mat3& H) {
     const double dn = (double)n;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
+    H = identity3();
     if (type == APS_TFORM_TRANSLATION) {
         double sx = 0, sy = 0;
         each([&](double a, double b, double c, double d) {
@@ -1379,136 +691,147 @@ __device__ __forceinline__ bool mlesac_fit_closed(int type, int n, Each&& each, 
     M3(H, 1, 1) = c;
     M3(H, 0, 2) = c2x - (c * c1x + (-sn) * c1y);
     M3(H, 1, 2) = c2y - (sn * c1x + c * c1y);
-#pragma unroll
-    for (int e = 0; e < 9; ++e)
-        if (!isfinite(H.m[e])) return false;
-    return true;
+    return all_finite(H);
 }
 
-// Hartley-Zisserman normalisation of an ordered selection (sums in order)
-template <class Each>
-__device__ __forceinline__ void mlesac_normalize(int n, Each&& each, Norm& n1, Norm& n2) {
-    const double dn = (double)n;
-    double sx = 0, sy = 0, ux = 0, uy = 0;
-    each([&](double a, double b, double c, double d) {
-        sx = sx + a;
-        sy = sy + b;
-        ux = ux + c;
-        uy = uy + d;
-    });
-    n1.cx = sx / dn;
-    n1.cy = sy / dn;
-    n2.cx = ux / dn;
-    n2.cy = uy / dn;
-    double sd = 0, ud = 0;
-    each([&](double a, double b, double c, double d) {
-        const double dx = a - n1.cx, dy = b - n1.cy;
-        sd = sd + sqrt(dx * dx + dy * dy);
-        const double ex = c - n2.cx, ey = d - n2.cy;
-        ud = ud + sqrt(ex * ex + ey * ey);
-    });
-    n1.s = norm_scale(sd / dn, 1);
-    n1.tx = -n1.s * n1.cx;
-    n1.ty = -n1.s * n1.cy;
-    n2.s = norm_scale(ud / dn, 1);
-    n2.tx = -n2.s * n2.cx;
-    n2.ty = -n2.s * n2.cy;
-}
-
-// one lane per (pair, draw): K = 3 / 2 / 2 / 1 sample points; the N x N Gram problem of a lane in its LDS column
-template <int N>
-__device__ __forceinline__ bool mlesac_fit_sample_null(int type, int K, const double* x1, const double* y1, const double* x2,
-                                                       const double* y2, double* sG, double* sV, int lane, Mat3& H) {
-    constexpr int S = 64;
-    auto each = [&](auto&& body) {
-        for (int k = 0; k < K; ++k) body(x1[k], y1[k], x2[k], y2[k]);
-    };
+// affine (N = 7) / similarity (N = 5) of one lane's sample: the N x N Gram problem in the lane's LDS column; rows per
+// point: its "v" row, then its "u" row
+template <int N, class Each>
+__device__ __forceinline__ bool mlesac_fit_sample_null(int type, int K, Each&& each, LdsMat<64> G, LdsMat<64> V, Mat3& H) {
     Norm n1, n2;
-    mlesac_normalize(K, each, n1, n2);
+    normalize_points(K, each, 1, n1, n2);
     for (int a = 0; a < N; ++a)
-        for (int b = a; b < N; ++b) GE(a, b) = 0.0;
-    for (int k = 0; k < K; ++k)
+        for (int b = a; b < N; ++b) G(a, b) = 0.0;
+    each([&](double px, double py, double qx, double qy) {
         for (int half = 1; half >= 0; --half) {
-            const double x = (x1[k] - n1.cx) * n1.s, y = (y1[k] - n1.cy) * n1.s;
-            const double u = (x2[k] - n2.cx) * n2.s, v = (y2[k] - n2.cy) * n2.s;
+            const double x = norm_x(n1, px, 1), y = norm_y(n1, py, 1);
+            const double u = norm_x(n2, qx, 1), v = norm_y(n2, qy, 1);
             double a[N];
 #pragma unroll
             for (int e = 0; e < N; ++e) a[e] = mlesac_entry(type, e, half, x, y, u, v);
 #pragma unroll
             for (int pp = 0; pp < N; ++pp)
 #pragma unroll
-                for (int qq = pp; qq < N; ++qq) GE(pp, qq) = GE(pp, qq) + a[pp] * a[qq];
+                for (int qq = pp; qq < N; ++qq) G(pp, qq) = G(pp, qq) + a[pp] * a[qq];
         }
-    for (int p = 0; p < N; ++p)
-        for (int q = 0; q < p; ++q) GE(p, q) = GE(q, p);
-    jacobi9<S, N>(sG, sV, lane);
-    int kmin = 0;
-    for (int k = 1; k < N; ++k)
-        if (GE(k, k) < GE(kmin, kmin)) kmin = k;
+    });
     double h[N];
-    for (int k = 0; k < N; ++k) h[k] = VE(k, kmin);
+    null_vector<N>(G, V, h);
     return mlesac_h_to_model(type, h, n1, n2, H);
 }
 
-__global__ __launch_bounds__(64) void mlesac_tform_fit_kernel(int type, const double* __restrict__ pts1,
-                                                               const double* __restrict__ pts2, int64_t ldp,
-                                                               const int64_t* __restrict__ pair_ptr,
-                                                               const int* __restrict__ act, int n_act, int c0, int nc,
-                                                               const uint32_t* __restrict__ sample_idx, int n_samples,
-                                                               double* __restrict__ Hs, uint8_t* __restrict__ valid) {
-    extern __shared__ __attribute__((aligned(16))) double lds_fit[];
-    double* sG = lds_fit;
-    double* sV = lds_fit + 81 * 64;
-    const int lane = threadIdx.x;
-    const int64_t wid = blockIdx.x * (int64_t)64 + lane;
-    if (wid >= (int64_t)n_act * nc) return;  // no barriers below
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    const int K = tf_min_points(type);
-    double x1[3], y1[3], x2[3], y2[3];
-    bool ok = m >= K;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint32_t id = k < K ? sample_idx[gid * 4 + k] : 1u;
-        if (k < K && (id < 1 || (int64_t)id > m)) ok = false;
-        const int64_t row = r0 + (ok ? (int64_t)id - 1 : 0);
-        const bool ld = ok && k < K;
-        x1[k] = ld ? pts1[row] : 0.0;
-        y1[k] = ld ? pts1[ldp + row] : 0.0;
-        x2[k] = ld ? pts2[row] : 0.0;
-        y2[k] = ld ? pts2[ldp + row] : 0.0;
+// ------------------------------------------------------------------------------------------------
+// evaluators: all 64 lanes of a wave call these with the same arguments; mask (may be NULL) receives 0/1 per match
+// ------------------------------------------------------------------------------------------------
+// findInliers' error of one match (:444-497): the symmetric transfer error for 'projective' (A = adj(H) stands for
+// inv(H)), the one-way error for the other types, 'translation' in units of `scale` (:487)
+__device__ __forceinline__ double inlier_error(int type, const Mat3& H, const Mat3& A, double scale, double x1, double y1,
+                                               double x2, double y2) {
+    const double X = (M3(H, 0, 0) * x1 + M3(H, 0, 1) * y1) + M3(H, 0, 2);
+    const double Y = (M3(H, 1, 0) * x1 + M3(H, 1, 1) * y1) + M3(H, 1, 2);
+    const double W = (M3(H, 2, 0) * x1 + M3(H, 2, 1) * y1) + M3(H, 2, 2);
+    const double ex = x2 - X / W, ey = y2 - Y / W;
+    double d = ex * ex + ey * ey;
+    if (type == APS_TFORM_PROJECTIVE) {
+        const double IX = (A.m[0] * x2 + A.m[3] * y2) + A.m[6];
+        const double IY = (A.m[1] * x2 + A.m[4] * y2) + A.m[7];
+        const double IW = (A.m[2] * x2 + A.m[5] * y2) + A.m[8];
+        const double fx = x1 - IX / IW, fy = y1 - IY / IW;
+        d = d + (fx * fx + fy * fy);
     }
-    Mat3 H;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = 0.0;
-    if (ok) {
-        if (type == APS_TFORM_AFFINE)
-            ok = mlesac_fit_sample_null<7>(type, K, x1, y1, x2, y2, sG, sV, lane, H);
-        else if (type == APS_TFORM_SIMILARITY)
-            ok = mlesac_fit_sample_null<5>(type, K, x1, y1, x2, y2, sG, sV, lane, H);
-        else
-            ok = mlesac_fit_closed(type, K, [&](auto&& body) {
-                for (int k = 0; k < K; ++k) body(x1[k], y1[k], x2[k], y2[k]);
-            }, H);
-    }
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hs[gid * 9 + e] = H.m[e];
-    valid[gid] = ok ? 1 : 0;  // [pair][draw], like Hs (the score kernels read the chunk-local copy valid_chunk_kernel makes)
+    double e = sqrt(d);
+    if (type == APS_TFORM_TRANSLATION) e = e / scale;
+    if (!isfinite(e)) e = INFINITY;
+    if (fabs(W) < kDblEps) e = INFINITY;
+    return e;
 }
 
-// evaluateModel over evaluateTransform2d, or evaluateTranslation2d for 'translation' (no division, no |w| test)
-__device__ double wave_mlesac_eval_any(int type, const Mat3& H, const double* __restrict__ x1, const double* __restrict__ y1,
-                                       const double* __restrict__ x2, const double* __restrict__ y2, int64_t m, double thr,
-                                       uint8_t* __restrict__ mask, int* n_inl) {
-    if (type != APS_TFORM_TRANSLATION) return wave_mlesac_eval(H, x1, y1, x2, y2, m, thr, mask, n_inl);
+// findInliers (:444-516): returns the inlier count, *mean_err their mean error
+__device__ int wave_find_inliers(int type, const Mat3& H, const double* __restrict__ x1, const double* __restrict__ y1,
+                                 const double* __restrict__ x2, const double* __restrict__ y2, int64_t m, double thr,
+                                 uint8_t* __restrict__ mask, double* mean_err) {
+    const int lane = threadIdx.x & 63;
+    Mat3 A{};
+    if (type == APS_TFORM_PROJECTIVE) A = adjugate3(H);
+    double scale = 1.0;  // max(abs([pts1_homog(:); pts2_homog(:)])): the homogeneous ones take part (:487)
+    if (type == APS_TFORM_TRANSLATION) {
+        for (int64_t i = lane; i < m; i += 64) {
+            if (fabs(x1[i]) > scale) scale = fabs(x1[i]);
+            if (fabs(y1[i]) > scale) scale = fabs(y1[i]);
+            if (fabs(x2[i]) > scale) scale = fabs(x2[i]);
+            if (fabs(y2[i]) > scale) scale = fabs(y2[i]);
+        }
+        scale = wave_max(scale);
+        thr = thr / scale;
+    }
+    double pc = 0, pe = 0, px = 0, py = 0;
+    for (int64_t i = lane; i < m; i += 64) {
+        const double e = inlier_error(type, H, A, scale, x1[i], y1[i], x2[i], y2[i]);
+        const bool in = e < thr;
+        if (mask) mask[i] = in ? 1 : 0;
+        if (in) {
+            pc += 1.0;
+            pe = pe + e;
+            px = px + x1[i];
+            py = py + y1[i];
+        }
+    }
+    const double cnt = wave_sum(pc);
+    const double se = wave_sum(pe), sx = wave_sum(px), sy = wave_sum(py);
+    const int n = (int)cnt;
+    // isDegenerate on pts1(inliers) (:506-513, :537-574): collinear inliers
+    if ((type == APS_TFORM_PROJECTIVE && n >= 4) || (type == APS_TFORM_AFFINE && n >= 3)) {
+        const double mx = sx / cnt, my = sy / cnt;
+        double pxx = 0, pxy = 0, pyy = 0;
+        for (int64_t i = lane; i < m; i += 64)
+            if (inlier_error(type, H, A, scale, x1[i], y1[i], x2[i], y2[i]) < thr) {
+                const double dx = x1[i] - mx, dy = y1[i] - my;
+                pxx = pxx + dx * dx;
+                pxy = pxy + dx * dy;
+                pyy = pyy + dy * dy;
+            }
+        const double sxx = wave_sum(pxx), sxy = wave_sum(pxy), syy = wave_sum(pyy);
+        const double hs = 0.5 * (sxx + syy), hd = 0.5 * (sxx - syy);
+        const double r = sqrt(hd * hd + sxy * sxy);
+        const double l1 = hs + r;
+        double l2 = hs - r;
+        if (l2 < 0) l2 = 0;
+        if (sqrt(l2) / sqrt(l1) < 1e-3) {
+            if (mask)
+                for (int64_t i = lane; i < m; i += 64) mask[i] = 0;
+            *mean_err = NAN;
+            return 0;
+        }
+    }
+    *mean_err = n > 0 ? se / cnt : NAN;
+    return n;
+}
+
+// MLESAC's distance of one match: evaluateTransform2d (estimateTransformationMLESAC.m:534-562), the one-way distance of
+// H * x1 to x2, or evaluateTranslation2d for 'translation' (:578-598; no division, no |w| test)
+__device__ __forceinline__ double mlesac_dist(int type, const Mat3& H, double x1, double y1, double x2, double y2) {
+    if (type == APS_TFORM_TRANSLATION) {
+        const double dx = (x1 + M3(H, 0, 2)) - x2, dy = (y1 + M3(H, 1, 2)) - y2;
+        return sqrt(dx * dx + dy * dy);
+    }
+    const double X = (M3(H, 0, 0) * x1 + M3(H, 0, 1) * y1) + M3(H, 0, 2);
+    const double Y = (M3(H, 1, 0) * x1 + M3(H, 1, 1) * y1) + M3(H, 1, 2);
+    const double W = (M3(H, 2, 0) * x1 + M3(H, 2, 1) * y1) + M3(H, 2, 2);
+    const double dx = X / W - x2, dy = Y / W - y2;
+    double d = sqrt(dx * dx + dy * dy);
+    if (fabs(W) < kDblEps) d = INFINITY;
+    return d;
+}
+
+// MLESAC evaluateModel (:258-295): the distances truncated at thr; returns their sum (wave order), *n_inl = #(d < thr)
+__device__ double wave_mlesac_eval(int type, const Mat3& H, const double* __restrict__ x1, const double* __restrict__ y1,
+                                   const double* __restrict__ x2, const double* __restrict__ y2, int64_t m, double thr,
+                                   uint8_t* __restrict__ mask, int* n_inl) {
     const int lane = threadIdx.x & 63;
     double ps = 0, pc = 0;
     for (int64_t i = lane; i < m; i += 64) {
-        const double dx = (x1[i] + M3(H, 0, 2)) - x2[i], dy = (y1[i] + M3(H, 1, 2)) - y2[i];
-        double d = sqrt(dx * dx + dy * dy);
-        if (d > thr) d = thr;
+        double d = mlesac_dist(type, H, x1[i], y1[i], x2[i], y2[i]);
+        if (d > thr) d = thr;  // NaN stays NaN
         const bool in = d < thr;
         if (mask) mask[i] = in ? 1 : 0;
         ps = ps + d;
@@ -1518,98 +841,470 @@ __device__ double wave_mlesac_eval_any(int type, const Mat3& H, const double* __
     return wave_sum(ps);
 }
 
-__global__ __launch_bounds__(256) void mlesac_tform_score_kernel(
-    int type, const double* __restrict__ pts1, const double* __restrict__ pts2, int64_t ldp,
-    const int64_t* __restrict__ pair_ptr, const int* __restrict__ act, int n_act, int c0, int nc, int n_samples,
-    const double* __restrict__ Hs, const uint8_t* __restrict__ valid, double thr, int32_t* __restrict__ n_inl,
-    double* __restrict__ acc_dis) {
-    const int64_t wid = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
-    if (wid >= (int64_t)n_act * nc) return;
-    const int lane = threadIdx.x & 63;
-    if (!valid[wid]) {
-        if (lane == 0) {
-            n_inl[wid] = 0;
-            acc_dis[wid] = NAN;
-        }
-        return;
-    }
-    const int p = act[wid / nc];
-    const int64_t gid = (int64_t)p * n_samples + c0 + (int)(wid % nc);
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
+// ------------------------------------------------------------------------------------------------
+// kernels
+// ------------------------------------------------------------------------------------------------
+// One ransac_batch call as its kernels see it.  Hs and valid are [pair][draw]: the fit kernels write them, every other kernel
+// only reads them.
+struct Batch {
+    const double *pts1, *pts2;  // planar: x at [row], y at [ldp + row]
+    int64_t ldp;
+    const int64_t* pair_ptr;
+    int n_samples;
+    double* Hs;
+    uint8_t* valid;
+    double thr;
+    int type, mlesac;
+};
+// Work item = (active pair a, draw c0 + k), k < nc: the host hands the draws over in growing chunks and stops a pair as
+// soon as its sequential loop has ended, so most of the n_samples draws of a pair are never fitted or scored.
+struct Chunk {
+    const int* act;
+    int n_act, c0, nc;
+};
+struct WorkItem {
+    int p;
+    int64_t gid, r0, m;  // gid: [pair][draw] index; the pair's matches are rows r0 .. r0 + m
+};
+__device__ __forceinline__ int64_t chunk_items(const Chunk& c) { return (int64_t)c.n_act * c.nc; }
+__device__ __forceinline__ WorkItem work_item(const Batch& b, const Chunk& c, int64_t wid) {
+    const int p = c.act[wid / c.nc];
+    const int64_t r0 = b.pair_ptr[p];
+    return {p, (int64_t)p * b.n_samples + c.c0 + (int)(wid % c.nc), r0, b.pair_ptr[p + 1] - r0};
+}
+
+__device__ __forceinline__ Mat3 load_model(const double* __restrict__ Hs, int64_t idx) {
     Mat3 H;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) H.m[e] = Hs[gid * 9 + e];
-    int n;
-    const double acc = wave_mlesac_eval_any(type, H, pts1 + r0, pts1 + ldp + r0, pts2 + r0, pts2 + ldp + r0, m, thr, nullptr, &n);
-    if (lane == 0) {
+    for (int e = 0; e < 9; ++e) H.m[e] = Hs[idx * 9 + e];
+    return H;
+}
+
+// ---- fit: one lane per work item ----
+// The K <= KMAX sampled points of a work item.  Returns false (and zero-fills) if the pair is too small or an index is out
+// of range; nothing is read out of bounds.
+template <int KMAX>
+__device__ __forceinline__ bool load_sample(const Batch& b, const uint32_t* __restrict__ sample_idx, const WorkItem& w, int K,
+                                            double* x1, double* y1, double* x2, double* y2) {
+    bool ok = w.m >= K;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        const uint32_t id = k < K ? sample_idx[w.gid * 4 + k] : 1u;
+        if (k < K && (id < 1 || (int64_t)id > w.m)) ok = false;
+        const int64_t row = w.r0 + (ok ? (int64_t)id - 1 : 0);
+        const bool ld = ok && k < K;
+        x1[k] = ld ? b.pts1[row] : 0.0;
+        y1[k] = ld ? b.pts1[b.ldp + row] : 0.0;
+        x2[k] = ld ? b.pts2[row] : 0.0;
+        y2[k] = ld ? b.pts2[b.ldp + row] : 0.0;
+    }
+    return ok;
+}
+
+// (the score kernel reads the chunk-local copy of valid that valid_chunk_kernel makes; the finalize kernels pick the winner
+// in Hs, and draws may be fitted ahead of the chunk that scores them)
+__device__ __forceinline__ void store_model(const Batch& b, int64_t gid, const Mat3& H, bool ok) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) b.Hs[gid * 9 + e] = H.m[e];
+    b.valid[gid] = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void ransac_fit_kernel(Batch b, Chunk c, const uint32_t* __restrict__ sample_idx) {
+    extern __shared__ __attribute__((aligned(16))) double lds_fit[];
+    const int lane = threadIdx.x;
+    const LdsMat<64> G{lds_fit, lane}, V{lds_fit + 81 * 64, lane};  // one 9x9 problem per lane
+    const int64_t wid = blockIdx.x * (int64_t)64 + lane;
+    if (wid >= chunk_items(c)) return;  // no barriers below: every lane works on its own LDS column
+    const WorkItem w = work_item(b, c, wid);
+    const int mlesac = b.mlesac;
+    double x1[4], y1[4], x2[4], y2[4];
+    bool ok = load_sample<4>(b, sample_idx, w, 4, x1, y1, x2, y2);
+    Mat3 H{};
+    if (ok) {
+        Norm n1, n2;
+        normalize_points(4, [&](auto&& body) {
+            for (int k = 0; k < 4; ++k) body(x1[k], y1[k], x2[k], y2[k]);
+        }, mlesac, n1, n2);
+        for (int a = 0; a < 9; ++a)
+            for (int bb = a; bb < 9; ++bb) G(a, bb) = 0.0;
+        // Gram sums in the reference's row order: RANSAC all "x" rows then all "y" rows (:209-212); MLESAC per
+        // point its "v" row then its "u" row (estimateTransformationMLESAC.m:368-373; a a' is sign-blind)
+#pragma nounroll
+        for (int step = 0; step < 8; ++step) {
+            const int half = mlesac ? 1 - (step & 1) : step >> 2;
+            const int k = mlesac ? step >> 1 : step & 3;
+            const double x = norm_x(n1, x1[k], mlesac), y = norm_y(n1, y1[k], mlesac);
+            const double u = norm_x(n2, x2[k], mlesac), v = norm_y(n2, y2[k], mlesac);
+            double a[9];
+            for (int e = 0; e < 9; ++e) a[e] = dlt_entry(e, half, x, y, u, v);
+            for (int pp = 0; pp < 9; ++pp)
+                for (int qq = pp; qq < 9; ++qq) G(pp, qq) = G(pp, qq) + a[pp] * a[qq];
+        }
+        ok = gram_to_h(G, V, n1, n2, H, mlesac) && (mlesac || check_model(H));
+    }
+    store_model(b, w.gid, H, ok);
+}
+
+__global__ __launch_bounds__(64) void tform_fit_kernel(Batch b, Chunk c, const uint32_t* __restrict__ sample_idx) {
+    const int64_t wid = blockIdx.x * (int64_t)64 + threadIdx.x;
+    if (wid >= chunk_items(c)) return;
+    const WorkItem w = work_item(b, c, wid);
+    const int K = tf_min_points(b.type);
+    double x1[3], y1[3], x2[3], y2[3];
+    bool ok = load_sample<3>(b, sample_idx, w, K, x1, y1, x2, y2);
+    Mat3 H{};
+    if (ok) {
+        bool fin;
+        if (K == 3)
+            fin = fit_sample<3>(b.type, x1, y1, x2, y2, H);
+        else if (K == 2)
+            fin = fit_sample<2>(b.type, x1, y1, x2, y2, H);
+        else
+            fin = fit_sample<1>(b.type, x1, y1, x2, y2, H);
+        ok = fin && check_model(H);
+    }
+    store_model(b, w.gid, H, ok);
+}
+
+__global__ __launch_bounds__(64) void mlesac_tform_fit_kernel(Batch b, Chunk c, const uint32_t* __restrict__ sample_idx) {
+    extern __shared__ __attribute__((aligned(16))) double lds_fit[];
+    const int lane = threadIdx.x;
+    const LdsMat<64> G{lds_fit, lane}, V{lds_fit + 81 * 64, lane};
+    const int64_t wid = blockIdx.x * (int64_t)64 + lane;
+    if (wid >= chunk_items(c)) return;  // no barriers below
+    const WorkItem w = work_item(b, c, wid);
+    const int type = b.type, K = tf_min_points(type);
+    double x1[3], y1[3], x2[3], y2[3];
+    bool ok = load_sample<3>(b, sample_idx, w, K, x1, y1, x2, y2);
+    Mat3 H{};
+    if (ok) {
+        auto each = [&](auto&& body) {
+            for (int k = 0; k < K; ++k) body(x1[k], y1[k], x2[k], y2[k]);
+        };
+        if (type == APS_TFORM_AFFINE)
+            ok = mlesac_fit_sample_null<7>(type, K, each, G, V, H);
+        else if (type == APS_TFORM_SIMILARITY)
+            ok = mlesac_fit_sample_null<5>(type, K, each, G, V, H);
+        else
+            ok = mlesac_fit_closed(type, K, each, H);
+    }
+    store_model(b, w.gid, H, ok);
+}
+
+// ---- score: one wave per work item, 4 waves per block ----
+// valid [pair][draw] -> the chunk-local [active pair][draw of the chunk] order the score kernel and the host replay walk
+__global__ void valid_chunk_kernel(Batch b, Chunk c, uint8_t* __restrict__ valid_loc) {
+    const int64_t wid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (wid >= chunk_items(c)) return;
+    valid_loc[wid] = b.valid[work_item(b, c, wid).gid];
+}
+
+// score: RANSAC the mean inlier error, MLESAC the sum of the truncated distances.  (A template parameter, not b.mlesac: the
+// MLESAC evaluator needs half the registers of findInliers and runs at twice its occupancy.)
+template <int MLESAC>
+__global__ __launch_bounds__(256) void ransac_score_kernel(Batch b, Chunk c, const uint8_t* __restrict__ valid_loc,
+                                                            int32_t* __restrict__ n_inl, double* __restrict__ score) {
+    const int64_t wid = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
+    if (wid >= chunk_items(c)) return;
+    int n = 0;
+    double sc = NAN;
+    if (valid_loc[wid]) {
+        const WorkItem w = work_item(b, c, wid);
+        const Mat3 H = load_model(b.Hs, w.gid);
+        const double *x1 = b.pts1 + w.r0, *y1 = b.pts1 + b.ldp + w.r0, *x2 = b.pts2 + w.r0, *y2 = b.pts2 + b.ldp + w.r0;
+        if (MLESAC)
+            sc = wave_mlesac_eval(b.type, H, x1, y1, x2, y2, w.m, b.thr, nullptr, &n);
+        else if (b.type == APS_TFORM_PROJECTIVE)  // (a constant type: the match loop of the common case carries no type tests)
+            n = wave_find_inliers(APS_TFORM_PROJECTIVE, H, x1, y1, x2, y2, w.m, b.thr, nullptr, &sc);
+        else
+            n = wave_find_inliers(b.type, H, x1, y1, x2, y2, w.m, b.thr, nullptr, &sc);
+    }
+    if ((threadIdx.x & 63) == 0) {
         n_inl[wid] = n;
-        acc_dis[wid] = acc;
+        score[wid] = sc;
     }
 }
 
-// finalize: one wave per pair (:213-241): the best draw's inliers, refit on them, re-evaluate; the refit is the answer
-__global__ __launch_bounds__(64) void mlesac_tform_finalize_kernel(int type, const double* __restrict__ pts1,
-                                                                    const double* __restrict__ pts2, int64_t ldp,
-                                                                    const int64_t* __restrict__ pair_ptr, int n_samples,
-                                                                    const double* __restrict__ Hs,
-                                                                    const int32_t* __restrict__ best_it, double thr,
-                                                                    double* __restrict__ models, uint8_t* __restrict__ mask,
-                                                                    uint8_t* __restrict__ scratch_mask,
-                                                                    int32_t* __restrict__ found, int32_t* __restrict__ n_final) {
-    __shared__ __attribute__((aligned(16))) double lds_fin[2 * 81 * 2];
-    double* sG = lds_fin;
-    double* sV = lds_fin + 81 * 2;
+// explicit-hypothesis scoring for aps_ransac_score: one wave per hypothesis, optional masks
+__global__ __launch_bounds__(256) void ransac_score_explicit_kernel(int type,
+    const double* __restrict__ p1, const double* __restrict__ p2, int64_t ldp, int64_t m,
+    const double* __restrict__ Hs, int n_hyp, double thr, int32_t* __restrict__ n_inl,
+    double* __restrict__ mean_err, uint8_t* __restrict__ mask) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= n_hyp) return;
+    const Mat3 H = load_model(Hs, t);
+    double me;
+    const int n = wave_find_inliers(type, H, p1, p1 + ldp, p2, p2 + ldp, m, thr, mask ? mask + (int64_t)t * m : nullptr, &me);
+    if ((threadIdx.x & 63) == 0) {
+        n_inl[t] = n;
+        mean_err[t] = me;
+    }
+}
+
+// ---- finalize: one wave per pair (:146-181; estimateTransformationMLESAC.m:213-241) ----
+struct PairOut {  // the batch's results: models [pair][9], mask [row], found / n_final [pair]; scratch_mask [row] is workspace
+    double* models;
+    uint8_t *mask, *scratch_mask;
+    int32_t *found, *n_final;
+};
+// the pair of this workgroup
+struct PairView {
+    int p, lane;
+    int64_t m;
+    const double *x1, *y1, *x2, *y2;
+    uint8_t *out_mask, *tmp_mask;
+};
+__device__ __forceinline__ PairView pair_view(const Batch& b, const PairOut& o) {
     const int p = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int64_t r0 = pair_ptr[p];
-    const int64_t m = pair_ptr[p + 1] - r0;
-    const int min_pts = tf_min_points(type);
-    const double *x1 = pts1 + r0, *y1 = pts1 + ldp + r0, *x2 = pts2 + r0, *y2 = pts2 + ldp + r0;
-    uint8_t* out_mask = mask + r0;
-    uint8_t* tmp_mask = scratch_mask + r0;
-    auto not_found = [&]() {
-        __threadfence_block();
-        __syncthreads();
-        for (int64_t i = lane; i < m; i += 64) out_mask[i] = 0;
-        if (lane < 9) models[(int64_t)p * 9 + lane] = NAN;
-        if (lane == 0) {
-            found[p] = 0;
-            n_final[p] = 0;
-        }
-    };
-    const int bi = best_it[p];
-    if (bi < 0) {
-        not_found();
-        return;
-    }
-    Mat3 Hb;
-    for (int e = 0; e < 9; ++e) Hb.m[e] = Hs[((int64_t)p * n_samples + bi) * 9 + e];
-    int nb;
-    (void)wave_mlesac_eval_any(type, Hb, x1, y1, x2, y2, m, thr, out_mask, &nb);
-    if (nb < min_pts) {
-        not_found();
-        return;
-    }
+    const int64_t r0 = b.pair_ptr[p];
+    return {p, (int)threadIdx.x, b.pair_ptr[p + 1] - r0, b.pts1 + r0, b.pts1 + b.ldp + r0, b.pts2 + r0, b.pts2 + b.ldp + r0,
+            o.mask + r0, o.scratch_mask + r0};
+}
+
+// The verdicts.  Every lane of the workgroup takes the same one (they hang on wave-uniform values only).
+__device__ __forceinline__ void not_found(const PairView& v, const PairOut& o) {
     __threadfence_block();
     __syncthreads();
-    __shared__ double s_pt[4][64];
-    __shared__ uint8_t s_in[64];
-    auto each = [&](auto&& body) {
-        for (int64_t base = 0; base < m; base += 64) {
-            const int64_t i = base + lane;
-            const bool have = i < m;
-            s_pt[0][lane] = have ? x1[i] : 0.0;
-            s_pt[1][lane] = have ? y1[i] : 0.0;
-            s_pt[2][lane] = have ? x2[i] : 0.0;
-            s_pt[3][lane] = have ? y2[i] : 0.0;
-            s_in[lane] = have ? out_mask[i] : (uint8_t)0;
-            __syncthreads();
-            for (int e = 0; e < 64; ++e)
-                if (s_in[e]) body(s_pt[0][e], s_pt[1][e], s_pt[2][e], s_pt[3][e]);
-            __syncthreads();
-        }
+    for (int64_t i = v.lane; i < v.m; i += 64) v.out_mask[i] = 0;
+    if (v.lane < 9) o.models[(int64_t)v.p * 9 + v.lane] = NAN;
+    if (v.lane == 0) {
+        o.found[v.p] = 0;
+        o.n_final[v.p] = 0;
+    }
+}
+// (static indices into H: a lane-indexed read of a register array sends the whole Mat3 to scratch memory)
+__device__ __forceinline__ void publish(const PairView& v, const PairOut& o, const Mat3& H, int n) {
+    if (v.lane == 0) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) o.models[(int64_t)v.p * 9 + e] = H.m[e];
+        o.found[v.p] = 1;
+        o.n_final[v.p] = n;
+    }
+}
+// the refit's inliers (tmp_mask) become the pair's
+__device__ __forceinline__ void adopt_refit_mask(const PairView& v) {
+    __threadfence_block();
+    __syncthreads();
+    for (int64_t i = v.lane; i < v.m; i += 64) v.out_mask[i] = v.tmp_mask[i];
+}
+
+// The inliers (out_mask) in ascending order, staged through LDS 64 at a time: body(x1, y1, x2, y2) runs in EVERY lane for
+// every inlier, so every lane evaluates the same sequential sums.
+struct InlierStage {
+    double pt[4][64];
+    uint8_t in[64];
+};
+template <class Body>
+__device__ __forceinline__ void each_inlier(const PairView& v, InlierStage& s, Body&& body) {
+    for (int64_t base = 0; base < v.m; base += 64) {
+        const int64_t i = base + v.lane;
+        const bool have = i < v.m;
+        s.pt[0][v.lane] = have ? v.x1[i] : 0.0;
+        s.pt[1][v.lane] = have ? v.y1[i] : 0.0;
+        s.pt[2][v.lane] = have ? v.x2[i] : 0.0;
+        s.pt[3][v.lane] = have ? v.y2[i] : 0.0;
+        s.in[v.lane] = have ? v.out_mask[i] : (uint8_t)0;
+        __syncthreads();
+        for (int e = 0; e < 64; ++e)
+            if (s.in[e]) body(s.pt[0][e], s.pt[1][e], s.pt[2][e], s.pt[3][e]);
+        __syncthreads();
+    }
+}
+
+// 'projective', both estimators
+__global__ __launch_bounds__(64) void ransac_finalize_kernel(Batch b, const int32_t* __restrict__ best_it, PairOut o) {
+    // one 9x9 problem per workgroup: two columns (work matrix / broadcast scratch), 2.6 KB - with the fit kernel's
+    // 64-column layout (83 KB) only one workgroup fitted a CU and the pairs ran in two rounds
+    __shared__ __attribute__((aligned(16))) double lds_fin[2 * 81 * 2];
+    const LdsMat<2> G{lds_fin, 0}, V{lds_fin + 81 * 2, 0};
+    constexpr int type = APS_TFORM_PROJECTIVE;
+    const PairView v = pair_view(b, o);
+    const int lane = v.lane, mlesac = b.mlesac;
+    const int64_t m = v.m;
+    const double *x1 = v.x1, *y1 = v.y1, *x2 = v.x2, *y2 = v.y2;
+    const int bi = best_it[v.p];
+    if (bi < 0) return not_found(v, o);
+    const Mat3 Hb = load_model(b.Hs, (int64_t)v.p * b.n_samples + bi);
+    double me;
+    int nb;
+    if (mlesac) {
+        (void)wave_mlesac_eval(type, Hb, x1, y1, x2, y2, m, b.thr, v.out_mask, &nb);
+        // isFound needs sum(bestInliers) >= sampleSize (estimateTransformationMLESAC.m:213-214)
+        if (nb < 4) return not_found(v, o);
+    } else {
+        nb = wave_find_inliers(type, Hb, x1, y1, x2, y2, m, b.thr, v.out_mask, &me);
+    }
+    __threadfence_block();
+    // Refit on the inliers (:146-181 -> estimateHomography).  Its sums - centroids, mean distances, the Gram sums of the DLT
+    // rows - run in the WAVE ORDER over the point index (oracle/ransac_oracle.c header): lane l accumulates the inliers
+    // i = l, l + 64, ... in ascending order and the 64 partials meet in the xor butterfly, like the other inlier sums.
+    // Summed sequentially in index order, every lane of the pair's wave walked all of its ~3 700 matches four times behind
+    // uniform mask tests: ~134 k serial vector instructions and 1.3 of the 3.4 ms of the whole RANSAC stage for ~200
+    // pairs, no faster for the 28 pairs of one rank of eight.
+    Norm n1, n2;
+    {
+        double sx = 0, sy = 0, ux = 0, uy = 0;
+        for (int64_t i = lane; i < m; i += 64)
+            if (v.out_mask[i]) {
+                sx = sx + x1[i];
+                sy = sy + y1[i];
+                ux = ux + x2[i];
+                uy = uy + y2[i];
+            }
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
+        ux = wave_sum(ux);
+        uy = wave_sum(uy);
+        const double dn = (double)nb;
+        const double cx = sx / dn, cy = sy / dn, dx2 = ux / dn, dy2 = uy / dn;
+        double sd = 0, ud = 0;
+        for (int64_t i = lane; i < m; i += 64)
+            if (v.out_mask[i]) {
+                const double ax = x1[i] - cx, ay = y1[i] - cy;
+                sd = sd + sqrt(ax * ax + ay * ay);
+                const double bx = x2[i] - dx2, by = y2[i] - dy2;
+                ud = ud + sqrt(bx * bx + by * by);
+            }
+        sd = wave_sum(sd);
+        ud = wave_sum(ud);
+        n1 = make_norm(cx, cy, sd / dn, mlesac);
+        n2 = make_norm(dx2, dy2, ud / dn, mlesac);
+    }
+    // Gram matrix: every lane keeps the 45 upper-triangular partial sums of ITS inliers (rows in the reference's order:
+    // RANSAC all "x" rows, then all "y" rows; MLESAC per inlier its "v" row, then its "u" row), then the butterfly
+    double g[45];
+#pragma unroll
+    for (int e = 0; e < 45; ++e) g[e] = 0;
+    auto add_row = [&](int half, double x, double y, double u, double w) __attribute__((always_inline)) {
+        double a[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a[k] = dlt_entry(k, half, x, y, u, w);
+        int e = 0;
+#pragma unroll
+        for (int pp = 0; pp < 9; ++pp)
+#pragma unroll
+            for (int qq = pp; qq < 9; ++qq, ++e) g[e] = g[e] + a[pp] * a[qq];
     };
+    if (mlesac) {
+        for (int64_t i = lane; i < m; i += 64)
+            if (v.out_mask[i]) {
+                const double x = norm_x(n1, x1[i], 1), y = norm_y(n1, y1[i], 1);
+                const double u = norm_x(n2, x2[i], 1), w = norm_y(n2, y2[i], 1);
+                add_row(1, x, y, u, w);
+                add_row(0, x, y, u, w);
+            }
+    } else {
+        for (int half = 0; half < 2; ++half)
+            for (int64_t i = lane; i < m; i += 64)
+                if (v.out_mask[i]) {
+                    const double x = norm_x(n1, x1[i], 0), y = norm_y(n1, y1[i], 0);
+                    const double u = norm_x(n2, x2[i], 0), w = norm_y(n2, y2[i], 0);
+                    add_row(half, x, y, u, w);
+                }
+    }
+    {
+        int e = 0;
+#pragma unroll
+        for (int pp = 0; pp < 9; ++pp)
+#pragma unroll
+            for (int qq = pp; qq < 9; ++qq, ++e) {
+                const double t = wave_sum(g[e]);
+                if (lane == 0) G(pp, qq) = t;
+            }
+    }
+    __syncthreads();
+    Mat3 Hr;
+    const bool ok = gram_to_h_wave(G, V, lane, n1, n2, Hr, mlesac) && (mlesac || check_model(Hr));
+    bool use_refit = false;
+    int nr = 0;
+    if (mlesac) {  // :216-236: the refit is the answer; invalid or no inlier left -> not found
+        if (ok) (void)wave_mlesac_eval(type, Hr, x1, y1, x2, y2, m, b.thr, v.tmp_mask, &nr);
+        if (!ok || nr < 1) return not_found(v, o);
+        use_refit = true;
+    } else if (ok) {
+        nr = wave_find_inliers(type, Hr, x1, y1, x2, y2, m, b.thr, v.tmp_mask, &me);
+        use_refit = nr >= 4;
+    }
+    if (use_refit) {
+        adopt_refit_mask(v);
+        publish(v, o, Hr, nr);
+    } else {
+        publish(v, o, Hb, nb);
+    }
+}
+
+// RANSAC, the other types
+__global__ __launch_bounds__(64) void tform_finalize_kernel(Batch b, const int32_t* __restrict__ best_it, PairOut o,
+                                                             unsigned long long* __restrict__ scratch_keys) {
+    const PairView v = pair_view(b, o);
+    const int lane = v.lane, type = b.type;
+    const int64_t m = v.m;
+    unsigned long long* keys = scratch_keys + b.pair_ptr[v.p];
+    const int bi = best_it[v.p];
+    if (bi < 0) return not_found(v, o);
+    const Mat3 Hb = load_model(b.Hs, (int64_t)v.p * b.n_samples + bi);
+    double me;
+    const int nb = wave_find_inliers(type, Hb, v.x1, v.y1, v.x2, v.y2, m, b.thr, v.out_mask, &me);
+    __threadfence_block();
+    __syncthreads();
+    __shared__ InlierStage stage;
+    auto each = [&](auto&& body) { each_inlier(v, stage, body); };
+    auto med = [&](int which, const FitCtx& cx, int* nv) -> double {
+        int c_valid = 0, c_nan = 0;
+        for (int64_t i = lane; i < m; i += 64) {
+            unsigned long long key = ~0ull;
+            if (v.out_mask[i]) {
+                bool valid;
+                const double q = med_value(which, cx, v.x1[i], v.y1[i], v.x2[i], v.y2[i], &valid);
+                if (valid) {
+                    ++c_valid;
+                    if (isnan(q)) ++c_nan;
+                    key = sort_key(q);
+                }
+            }
+            keys[i] = key;
+        }
+        const int n = wave_sum_i(c_valid), n_nan = wave_sum_i(c_nan);
+        __threadfence_block();
+        __syncthreads();
+        *nv = n;
+        if (n == 0 || n_nan > 0) return NAN;
+        if (n & 1) return key_value(wave_kth_key(keys, m, (n - 1) / 2));
+        const double a = key_value(wave_kth_key(keys, m, n / 2 - 1)), bb = key_value(wave_kth_key(keys, m, n / 2));
+        return median2(a, bb);
+    };
+    Mat3 Hr;
+    const bool ok = fit_tform(type, nb, each, med, Hr) && check_model(Hr);
+    bool use_refit = false;
+    int nr = 0;
+    if (ok) {
+        nr = wave_find_inliers(type, Hr, v.x1, v.y1, v.x2, v.y2, m, b.thr, v.tmp_mask, &me);
+        use_refit = nr >= tf_min_points(type);
+    }
+    if (use_refit) {
+        adopt_refit_mask(v);
+        publish(v, o, Hr, nr);
+    } else {
+        publish(v, o, Hb, nb);
+    }
+}
+
+// MLESAC, the other types: the best draw's inliers, refit on them, re-evaluate; the refit is the answer
+__global__ __launch_bounds__(64) void mlesac_tform_finalize_kernel(Batch b, const int32_t* __restrict__ best_it, PairOut o) {
+    __shared__ __attribute__((aligned(16))) double lds_fin[2 * 81 * 2];
+    const LdsMat<2> G{lds_fin, 0}, V{lds_fin + 81 * 2, 0};
+    const PairView v = pair_view(b, o);
+    const int lane = v.lane, type = b.type;
+    const int bi = best_it[v.p];
+    if (bi < 0) return not_found(v, o);
+    const Mat3 Hb = load_model(b.Hs, (int64_t)v.p * b.n_samples + bi);
+    int nb;
+    (void)wave_mlesac_eval(type, Hb, v.x1, v.y1, v.x2, v.y2, v.m, b.thr, v.out_mask, &nb);
+    if (nb < tf_min_points(type)) return not_found(v, o);
+    __threadfence_block();
+    __syncthreads();
+    __shared__ InlierStage stage;
+    auto each = [&](auto&& body) { each_inlier(v, stage, body); };
     Mat3 Hr;
     bool ok;
     if (type == APS_TFORM_RIGID || type == APS_TFORM_TRANSLATION) {
@@ -1617,7 +1312,7 @@ __global__ __launch_bounds__(64) void mlesac_tform_finalize_kernel(int type, con
     } else {
         const int N = type == APS_TFORM_AFFINE ? 7 : 5;
         Norm n1, n2;
-        mlesac_normalize(nb, each, n1, n2);
+        normalize_points(nb, each, 1, n1, n2);
         // lane e owns the upper-triangular Gram entry (pp, qq) of the N x N system; rows per inlier: "v" then "u"
         int pp = 0, qq = 0;
         {
@@ -1630,51 +1325,30 @@ __global__ __launch_bounds__(64) void mlesac_tform_finalize_kernel(int type, con
             qq = row + e;
         }
         double g = 0;
-        each([&](double a, double b, double c, double d) {
-            const double x = (a - n1.cx) * n1.s, y = (b - n1.cy) * n1.s;
-            const double u = (c - n2.cx) * n2.s, v = (d - n2.cy) * n2.s;
-            g = g + mlesac_entry(type, pp, 1, x, y, u, v) * mlesac_entry(type, qq, 1, x, y, u, v);
-            g = g + mlesac_entry(type, pp, 0, x, y, u, v) * mlesac_entry(type, qq, 0, x, y, u, v);
+        each([&](double px, double py, double qx, double qy) {
+            const double x = norm_x(n1, px, 1), y = norm_y(n1, py, 1);
+            const double u = norm_x(n2, qx, 1), w = norm_y(n2, qy, 1);
+            g = g + mlesac_entry(type, pp, 1, x, y, u, w) * mlesac_entry(type, qq, 1, x, y, u, w);
+            g = g + mlesac_entry(type, pp, 0, x, y, u, w) * mlesac_entry(type, qq, 0, x, y, u, w);
         });
-#define G2(p, q) sG[((p) * 9 + (q)) * 2]
-#define V2(p, q) sV[((p) * 9 + (q)) * 2]
-        if (lane < N * (N + 1) / 2) G2(pp, qq) = g;
+        if (lane < N * (N + 1) / 2) G(pp, qq) = g;
         __syncthreads();
-        if (lane == 0)
-            for (int a = 0; a < N; ++a)
-                for (int b = 0; b < a; ++b) G2(a, b) = G2(b, a);
-        __syncthreads();
+        double h[7] = {};
         if (N == 7)
-            jacobi9_wave<7>(sG, sV, lane);
+            null_vector_wave<7>(G, V, lane, h);
         else
-            jacobi9_wave<5>(sG, sV, lane);
-        int kmin = 0;
-        for (int k = 1; k < N; ++k)
-            if (G2(k, k) < G2(kmin, kmin)) kmin = k;
-        double h[7];
-        for (int k = 0; k < 7; ++k) h[k] = k < N ? V2(k, kmin) : 0.0;
-#undef G2
-#undef V2
+            null_vector_wave<5>(G, V, lane, h);
         ok = mlesac_h_to_model(type, h, n1, n2, Hr);
     }
     int nr = 0;
-    if (ok) (void)wave_mlesac_eval_any(type, Hr, x1, y1, x2, y2, m, thr, tmp_mask, &nr);
-    if (!ok || nr < 1) {
-        not_found();
-        return;
-    }
-    __threadfence_block();
-    __syncthreads();
-    for (int64_t i = lane; i < m; i += 64) out_mask[i] = tmp_mask[i];
-    if (lane < 9) models[(int64_t)p * 9 + lane] = Hr.m[lane];
-    if (lane == 0) {
-        found[p] = 1;
-        n_final[p] = nr;
-    }
+    if (ok) (void)wave_mlesac_eval(type, Hr, v.x1, v.y1, v.x2, v.y2, v.m, b.thr, v.tmp_mask, &nr);
+    if (!ok || nr < 1) return not_found(v, o);
+    adopt_refit_mask(v);
+    publish(v, o, Hr, nr);
 }
 
 // ------------------------------------------------------------------------------------------------
-// seeded 4-subsets (stand-in for randperm(numPoints, 4), :96)
+// draws: seeded 4-subsets (stand-in for randperm(numPoints, 4), :96), and the matched points they index
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double mix_uniform(unsigned long long seed, unsigned long long key, unsigned long long ctr) {
     unsigned long long x = seed * 0x9E3779B97F4A7C15ull + key * 0xD1B54A32D192ED03ull + ctr * 0x8CB92BA72F3D8DD7ull +
@@ -1717,9 +1391,6 @@ __global__ void draw_samples_kernel(const int64_t* __restrict__ counts, const un
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
 // imageMatching.m:121-135 on the device: one thread per match of the work list
 __global__ void gather_match_points_kernel(const unsigned long long* __restrict__ tab, int n_img, int n_work,
                                            const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b,
@@ -1751,6 +1422,9 @@ __global__ void gather_match_points_kernel(const unsigned long long* __restrict_
     pb[ldp + m] = okb ? kb[2 * rb + 1] : NAN;
 }
 
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
 static void check_opts(const aps_ransac_opts& o) {
     APS_REQUIRE(o.tform_type >= APS_TFORM_PROJECTIVE && o.tform_type <= APS_TFORM_TRANSLATION, APS_E_TYPE,
                 "unknown transformationType %d", o.tform_type);
@@ -1854,12 +1528,11 @@ static void ransac_batch(const double* d_p1, const double* d_p2, int64_t ldp,
     if (!attr_set) {
         APS_HIP(hipFuncSetAttribute((const void*)ransac_fit_kernel,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        APS_HIP(hipFuncSetAttribute((const void*)ransac_finalize_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         APS_HIP(hipFuncSetAttribute((const void*)mlesac_tform_fit_kernel,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         attr_set = true;
     }
+    const Batch b{d_p1, d_p2, ldp, d_ptr, n_samples, Hs, valid, o.max_distance, type, mlesac};
     // The reference's loop ends adaptively (a pair with 80 % inliers needs 13 trials, not 564), and only its
     // sequential part knows when.  So the draws are fitted and scored in growing chunks: after each chunk the host
     // advances every live pair's loop and only the pairs that have not ended yet get the next chunk.  The first
@@ -1895,30 +1568,21 @@ static void ransac_batch(const double* d_p1, const double* d_p2, int64_t ldp,
             const int nf = (int64_t)n_act * (n_samples - fitted) <= 16384 ? n_samples - fitted : c0 + nc - fitted;
             const int64_t nwf = (int64_t)n_act * nf;
             Prof prof("ransac_fit");
+            const Chunk cf{d_act, n_act, fitted, nf};
             if (type == APS_TFORM_PROJECTIVE)
-                ransac_fit_kernel<<<cdiv(nwf, 64), 64, lds_bytes, stream()>>>(d_p1, d_p2, ldp, d_ptr, d_act, n_act, fitted, nf,
-                                                                               d_samples, n_samples, Hs, valid, mlesac);
+                ransac_fit_kernel<<<cdiv(nwf, 64), 64, lds_bytes, stream()>>>(b, cf, d_samples);
             else if (mlesac)
-                mlesac_tform_fit_kernel<<<cdiv(nwf, 64), 64, lds_bytes, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, d_act, n_act,
-                                                                                     fitted, nf, d_samples, n_samples, Hs, valid);
+                mlesac_tform_fit_kernel<<<cdiv(nwf, 64), 64, lds_bytes, stream()>>>(b, cf, d_samples);
             else
-                tform_fit_kernel<<<cdiv(nwf, 64), 64, 0, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, d_act, n_act, fitted, nf,
-                                                                      d_samples, n_samples, Hs, valid);
+                tform_fit_kernel<<<cdiv(nwf, 64), 64, 0, stream()>>>(b, cf, d_samples);
             fitted += nf;
         }
         check_launch("ransac_fit_kernel");
         {
             Prof prof("ransac_score");
-            valid_chunk_kernel<<<cdiv(nw, 256), 256, 0, stream()>>>(d_act, n_act, c0, nc, n_samples, valid, valid_loc);
-            if (mlesac && type != APS_TFORM_PROJECTIVE)
-                mlesac_tform_score_kernel<<<cdiv(nw, 4), 256, 0, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, d_act, n_act, c0, nc,
-                                                                              n_samples, Hs, valid_loc, o.max_distance, ninl, merr);
-            else if (mlesac)
-                mlesac_score_kernel<<<cdiv(nw, 4), 256, 0, stream()>>>(d_p1, d_p2, ldp, d_ptr, d_act, n_act, c0, nc,
-                                                                        n_samples, Hs, valid_loc, o.max_distance, ninl, merr);
-            else
-                ransac_score_kernel<<<cdiv(nw, 4), 256, 0, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, d_act, n_act, c0, nc,
-                                                                        n_samples, Hs, valid_loc, o.max_distance, ninl, merr);
+            const Chunk cs{d_act, n_act, c0, nc};
+            valid_chunk_kernel<<<cdiv(nw, 256), 256, 0, stream()>>>(b, cs, valid_loc);
+            (mlesac ? ransac_score_kernel<1> : ransac_score_kernel<0>)<<<cdiv(nw, 4), 256, 0, stream()>>>(b, cs, valid_loc, ninl, merr);
         }
         check_launch("ransac_score_kernel");
         h_valid.resize(nw);
@@ -1951,17 +1615,13 @@ static void ransac_batch(const double* d_p1, const double* d_p2, int64_t ldp,
                            stream()));
     {
         Prof prof("ransac_finalize");
+        const PairOut out{d_models, d_mask, scratch, d_found, d_ninl};
         if (type == APS_TFORM_PROJECTIVE)
-            ransac_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(d_p1, d_p2, ldp, d_ptr, n_samples, Hs, best, o.max_distance,
-                                                                  d_models, d_mask, scratch, d_found, d_ninl, mlesac);
+            ransac_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(b, best, out);
         else if (mlesac)
-            mlesac_tform_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, n_samples, Hs, best,
-                                                                        o.max_distance, d_models, d_mask, scratch, d_found,
-                                                                        d_ninl);
+            mlesac_tform_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(b, best, out);
         else
-            tform_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(type, d_p1, d_p2, ldp, d_ptr, n_samples, Hs, best,
-                                                                 o.max_distance, d_models, d_mask, scratch, med_keys, d_found,
-                                                                 d_ninl);
+            tform_finalize_kernel<<<n_pairs, 64, 0, stream()>>>(b, best, out, med_keys);
     }
     check_launch("ransac_finalize_kernel");
     APS_HIP(hipStreamSynchronize(stream()));

@@ -249,3 +249,38 @@ def test_adversarial_inputs_agree_with_the_oracle(im, tform, name):
     assert found == ofound and np.array_equal(mask, omask), ("mlesac", tform, name)
     if found:
         assert np.array_equal(bits(H), bits(oH)), ("mlesac", tform, name)
+
+
+# ---- the chunked fit: a batch too large to be fitted whole in the first iteration --------------------------------------------
+@pytest.mark.parametrize("tform", ML_TYPES)
+@pytest.mark.parametrize("method", ["ransac", "mlesac"])
+def test_chunked_fit_equals_per_pair_oracle(im, method, tform):
+    """40 pairs of 12 to 80 matches, alternately 80 % and 15 % inliers.  40 x 564 (RANSAC) and 40 x 1064 (MLESAC) work items
+    exceed the 16384 up to which ransac_batch fits every draw in its first iteration, so the fit is issued chunk by chunk
+    and the pairs leave the active list at different chunks."""
+    rng = np.random.default_rng(0)  # chosen on the CPU: the oracle alone meets the trial-count condition in all ten cases
+    sizes = [int(m) for m in rng.integers(12, 81, 40)]
+    make = ml_scene if method == "mlesac" or tform == "projective" else world
+    worlds = [make(tform, rng, n=m, outliers=0.2 if p % 2 == 0 else 0.85) for p, m in enumerate(sizes)]
+    src = np.concatenate([w[0] for w in worlds])
+    dst = np.concatenate([w[1] for w in worlds])
+    ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if method == "mlesac":
+        samples, inp = im.draw_samples(sizes, 1064, seed=7), dict(ML_INP, transformationType=tform)
+        ref = [oracle.mlesac_tform(tform, p1, p2, samples[p], 2.0, 99.9, 1000) for p, (p1, p2) in enumerate(worlds)]
+    else:
+        samples, inp = im.draw_samples(sizes, 564, seed=7), dict(INP, transformationType=tform)
+        if tform == "projective":
+            ref = [oracle.ransac_homography(p1, p2, samples[p], 3.0, 99.9, 500) for p, (p1, p2) in enumerate(worlds)]
+        else:
+            ref = [oracle.ransac_tform(tform, p1, p2, samples[p], 3.0, 99.9, 500) for p, (p1, p2) in enumerate(worlds)]
+    assert len(sizes) * samples.shape[1] > 16384
+    trials = [r[3] for r in ref]
+    assert min(trials) <= 96 < max(trials), trials  # pairs end inside the first scored chunk (96 draws) and after it
+    models, mask, found, ninl = im.ransac_batch(src, dst, ptr, samples, inp)
+    for p, (oH, omask, ofound, _) in enumerate(ref):
+        assert bool(found[p]) == ofound, (method, tform, p)
+        assert np.array_equal(mask[ptr[p]:ptr[p + 1]].astype(bool), omask), (method, tform, p)
+        if ofound:
+            assert np.array_equal(bits(models[p]), bits(oH)), (method, tform, p)
+            assert ninl[p] == omask.sum(), (method, tform, p)
