@@ -91,6 +91,10 @@ class aps_fast_pyramid_params(C.Structure):
     _fields_ = [("fast", aps_fast_params), ("n_levels", C.c_int), ("scale_num", C.c_int), ("scale_den", C.c_int)]
 
 
+class aps_fast_strongest_params(C.Structure):
+    _fields_ = [("pyramid", aps_fast_pyramid_params), ("n_strongest", C.c_int)]
+
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/aps.h one to one
@@ -188,6 +192,10 @@ _SIGNATURES = {
                                  _vp, _i64, C.POINTER(_i64)],
     "aps_fast_pyramid_plan": [_i, _i, _i, _i, _i, _vp, _vp, C.POINTER(_i)],
     "aps_fast_pyramid_planes": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i64, C.POINTER(_i64)],
+    "aps_fast_extract_strongest": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_strongest_params), _vp, _i, _i64, _vp, _i64,
+                                   _vp, _i64, C.POINTER(_i64)],
+    "aps_fast_strongest_quota": [_i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i)],
+    "aps_fast_harris": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i64, C.POINTER(_i64)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
              "aps_planar_composite_compact_bytes": C.c_int64}

@@ -23,6 +23,13 @@
 //                         decoded from the word's offset)
 //   freak_keypoint_kernel one wave per keypoint: 43 box sums on its level's integral image, 45-pair orientation moment, bin, 43 box
 //                         sums on the bin's table, 64 lanes x 8 tests = 512 bits; lane = output byte
+// aps_fast_extract_strongest (DESIGN.md "FAST/FREAK strongest-N") shares the chain up to the scan, reads the counts per level back,
+// and goes on with grids of the candidates' size:
+//   fast_emit_kernel      the candidate list
+//   fast_harris_kernel    one wave per candidate: integer Harris response of its level's plane, and the sort key (level, -R)
+//   stable radix sort (rocprim) of (key, index), strongest_flag_kernel (rank within the level < k_l, written back by index),
+//                         strongest_word_kernel (ballot), scan of the popcounts, strongest_compact_kernel (canonical order again)
+//   freak_keypoint_kernel on the kept keypoints only; strongest_aux_kernel writes f32(R) into aux[3]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -419,6 +426,128 @@ __global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __r
     }
 }
 
+// ---- strongest-N: Harris response and selection (DESIGN.md "FAST/FREAK strongest-N") ------------------------------------------
+constexpr int kHarrisWin = 7, kHarrisPatch = kHarrisWin + 2;  // window of the sums; with the Sobel taps a 9 x 9 patch, reach 4
+constexpr long long kHarrisBias = 1LL << 54;                  // R + 2^54 > 0
+constexpr unsigned long long kKeyMask = (1ULL << 60) - 1;     // key = group << 60 | (2^60 - 1 - (R + 2^54)): ascending key = descending R
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One wave per candidate: its level's 9 x 9 patch into LDS, lanes 0..48 one window pixel each (Sobel Ix, Iy), three wave sums
+// (49 * 1020^2 < 2^26: int32), R in 64 bits on lane 0.  Writes the response, the sort key and the candidate's index as the sort's value.
+// Every wave of the grid passes the barrier; the ones beyond n do no work.  margin >= 4 keeps the patch inside the plane.
+__global__ __launch_bounds__(256) void fast_harris_kernel(const uint8_t* __restrict__ planes, const FastPlan P, const Keypoint* __restrict__ kps,
+                                                          unsigned int n, long long* __restrict__ resp, unsigned long long* __restrict__ keys,
+                                                          unsigned int* __restrict__ vals) {
+    __shared__ int s_g[4][kHarrisPatch * kHarrisPatch + 3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned int kidx = blockIdx.x * 4 + wave;
+    const bool active = kidx < n;
+    Keypoint kp{0, 0, 0};
+    if (active) kp = kps[kidx];
+    const FastLevel& L = P.lv[__builtin_amdgcn_readfirstlane(kp.level)];  // (one candidate per wave)
+    const uint8_t* __restrict__ g = planes + L.plane0;
+    if (active) {
+        for (int e = lane; e < kHarrisPatch * kHarrisPatch; e += 64) {
+            const int r = e / kHarrisPatch, c = e % kHarrisPatch;
+            s_g[wave][e] = g[(size_t)(kp.y - 4 + r) * L.w + (kp.x - 4 + c)];
+        }
+    }
+    __syncthreads();
+    int a = 0, b = 0, c = 0;
+    if (active && lane < kHarrisWin * kHarrisWin) {
+        const int* p = &s_g[wave][(lane / kHarrisWin) * kHarrisPatch + lane % kHarrisWin];  // top-left of the pixel's 3 x 3
+        const int g00 = p[0], g01 = p[1], g02 = p[2];
+        const int g10 = p[kHarrisPatch], g12 = p[kHarrisPatch + 2];
+        const int g20 = p[2 * kHarrisPatch], g21 = p[2 * kHarrisPatch + 1], g22 = p[2 * kHarrisPatch + 2];
+        const int ix = (g02 + 2 * g12 + g22) - (g00 + 2 * g10 + g20);
+        const int iy = (g20 + 2 * g21 + g22) - (g00 + 2 * g01 + g02);
+        a = ix * ix;
+        b = iy * iy;
+        c = ix * iy;
+    }
+    const long long A = wave_sum_i32(a), B = wave_sum_i32(b), Cxy = wave_sum_i32(c);
+    if (active && lane == 0) {
+        const long long R = 25 * (A * B - Cxy * Cxy) - (A + B) * (A + B);
+        resp[kidx] = R;
+        keys[kidx] = (unsigned long long)kp.level << 60 | (kKeyMask - (unsigned long long)(R + kHarrisBias));
+        vals[kidx] = kidx;
+    }
+}
+
+// the first candidate of every level and the total, gathered for the one read-back of the counts: out[l], l = 0 .. P.n
+__global__ void strongest_counts_kernel(const unsigned int* __restrict__ prefix, const FastPlan P, unsigned int n_words,
+                                        unsigned int* __restrict__ out) {
+    const int l = threadIdx.x;
+    if (l < P.n)
+        out[l] = prefix[P.lv[l].word0];
+    else if (l == P.n)
+        out[l] = prefix[n_words];
+}
+
+// The cut of a sorted key sequence: group g (the key's top 4 bits) starts at start[g] and keeps its first keep[g] items.
+struct StrongestCut {
+    unsigned int start[kMaxLevels], keep[kMaxLevels];
+};
+
+// position p of the sorted sequence -> flag of the item it came from
+__global__ __launch_bounds__(256) void strongest_flag_kernel(const unsigned long long* __restrict__ sorted_keys,
+                                                             const unsigned int* __restrict__ sorted_vals, const StrongestCut cut,
+                                                             unsigned int n, uint8_t* __restrict__ flags) {
+    const unsigned int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int grp = (int)(sorted_keys[p] >> 60);
+    unsigned int start = 0, keep = 0;
+#pragma unroll
+    for (int l = 0; l < kMaxLevels; ++l)  // (constant indices: the table stays in scalar registers)
+        if (grp == l) {
+            start = cut.start[l];
+            keep = cut.keep[l];
+        }
+    flags[sorted_vals[p]] = p - start < keep ? 1 : 0;
+}
+
+// one wave per word: its ballot over 64 flags (a word beyond the n flags is zero)
+__global__ __launch_bounds__(256) void strongest_word_kernel(const uint8_t* __restrict__ flags, unsigned int n, unsigned int n_words,
+                                                             unsigned long long* __restrict__ words) {
+    const int lane = threadIdx.x & 63;
+    const unsigned int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (q >= n_words) return;  // (uniform in the wave)
+    const unsigned int i = q * 64 + lane;
+    const unsigned long long mask = __ballot(i < n && flags[i] != 0);
+    if (lane == 0) words[q] = mask;
+}
+
+// Ordered compaction of the flagged candidates, as fast_emit_kernel's: canonical order is kept.
+__global__ __launch_bounds__(256) void strongest_compact_kernel(const unsigned long long* __restrict__ words, const unsigned int* __restrict__ prefix,
+                                                                unsigned int n_words, const Keypoint* __restrict__ cand,
+                                                                const long long* __restrict__ resp, Keypoint* __restrict__ kps,
+                                                                long long* __restrict__ kresp, unsigned int kcap) {
+    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_words) return;
+    unsigned long long bits = words[q];
+    unsigned int pos = prefix[q];
+    while (bits) {
+        const int k = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        if (pos < kcap) {
+            kps[pos] = cand[q * 64 + k];
+            kresp[pos] = resp[q * 64 + k];
+        }
+        ++pos;
+    }
+}
+
+// aux[3] of the described rows: f32(R), round to nearest
+__global__ __launch_bounds__(256) void strongest_aux_kernel(const long long* __restrict__ kresp, unsigned int n, float* __restrict__ aux) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) aux[(size_t)i * 4 + 3] = (float)kresp[i];
+}
+
 // ---- host: the plan and the chain ----------------------------------------------------------------------------------------
 struct HostPlan {
     FastPlan dev;
@@ -496,23 +625,34 @@ void build_levels(const uint8_t* dimg, int channels, int img_layout, const HostP
     }
 }
 
-// aps_fast_extract and aps_fast_extract_pyramid behind their argument checks (check_args, check_pyramid).
-void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, uint8_t* desc,
-                int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
-    ctx();
-    *count = 0;
+// What the chain holds once the candidates are known: the levels, the plane of kept scores, the candidate bitmap (bit order =
+// canonical order) and the exclusive scan of its popcounts; prefix[n_words] is the number of candidates.
+struct FastFront {
+    In<uint8_t> dimg;
+    Ws<uint32_t> T, I;
+    Ws<uint8_t> planes, kept;
+    Ws<unsigned int> smax, prefix;
+    Ws<unsigned long long> bitmap;
+    const unsigned int* d_total() const { return prefix.get() + prefix.n - 1; }
+};
+
+// levels, detection, gate and scan on the calling thread's stream; no read-back
+void fast_front(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, FastFront& F) {
     const FastPlan& P = hp.dev;
     const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
-    if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
-    In<uint8_t> dimg(img, (size_t)H * W * channels);
-    Ws<uint32_t> T((size_t)H * W), I(hp.integ_elems);
-    Ws<uint8_t> planes(hp.plane_bytes);
-    build_levels(dimg, channels, img_layout, hp, planes, T, I);
     const size_t n_words = hp.n_words;
-    Ws<uint8_t> kept(hp.plane_bytes);
-    Ws<unsigned int> smax((size_t)P.n);
-    Ws<unsigned long long> bitmap(n_words + 1);  // (+1: a zero word, whose prefix is the total)
-    Ws<unsigned int> prefix(n_words + 1);
+    F.dimg.bind(img, (size_t)H * W * channels);
+    F.T.alloc((size_t)H * W);
+    F.I.alloc(hp.integ_elems);
+    F.planes.alloc(hp.plane_bytes);
+    build_levels(F.dimg, channels, img_layout, hp, F.planes, F.T, F.I);
+    F.kept.alloc(hp.plane_bytes);
+    F.smax.alloc((size_t)P.n);
+    F.bitmap.alloc(n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    F.prefix.alloc(n_words + 1);
+    const Ws<uint8_t>&planes = F.planes, &kept = F.kept;
+    const Ws<unsigned int>&smax = F.smax, &prefix = F.prefix;
+    const Ws<unsigned long long>& bitmap = F.bitmap;
     APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
     {
         Prof prof("fast_detect");
@@ -542,7 +682,24 @@ void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast
         Ws<char> tmp(tbytes);
         APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, n_words + 1, rocprim::plus<unsigned int>(), stream()));
     }
-    const unsigned int* d_total = prefix.get() + n_words;
+}
+
+// aps_fast_extract and aps_fast_extract_pyramid behind their argument checks (check_args, check_pyramid).
+void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, uint8_t* desc,
+                int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    ctx();
+    *count = 0;
+    const FastPlan& P = hp.dev;
+    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
+    if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
+    FastFront F;
+    fast_front(img, channels, img_layout, params, hp, F);
+    const size_t n_words = hp.n_words;
+    const Ws<uint32_t>& I = F.I;
+    const Ws<uint8_t>& kept = F.kept;
+    const Ws<unsigned int>& prefix = F.prefix;
+    const Ws<unsigned long long>& bitmap = F.bitmap;
+    const unsigned int* d_total = F.d_total();
     const bool write = cap > 0 && desc && loc;
     const unsigned int kcap = write ? (unsigned int)cap : 0u;
     Out<uint8_t> odesc;
@@ -587,6 +744,160 @@ void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast
         odesc.commit_2d(n, 64, (size_t)ldd);
     oloc.commit_2d(n, 2, (size_t)ldl);
     oaux.commit((size_t)n * 4);
+}
+
+// ---- strongest-N on the host -----------------------------------------------------------------------------------------------
+// q_l = floor(N weight_l / W), weight_l = h_l + w_l; the remainder r < L goes one each to levels 0 .. r - 1
+void strongest_quota(const FastPlan& P, long long N, long long* q) {
+    long long W = 0, given = 0;
+    for (int l = 0; l < P.n; ++l) W += P.lv[l].h + P.lv[l].w;
+    for (int l = 0; l < P.n; ++l) given += q[l] = N * (P.lv[l].h + P.lv[l].w) / W;
+    for (int l = 0; l < N - given; ++l) ++q[l];
+}
+
+// The candidate list of a call (fast_front's bitmap, emitted in canonical order), the response of every candidate and its sort key.
+struct Candidates {
+    unsigned int M = 0, first[kMaxLevels + 1] = {};  // level l holds candidates first[l] .. first[l + 1] - 1
+    Ws<Keypoint> kps;
+    Ws<long long> resp;
+    Ws<unsigned long long> keys;
+    Ws<unsigned int> vals;
+};
+
+// Reads the counts per level back (the first read-back of the strongest-N chain): the grids and the sort below are sized by M.
+void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
+    const FastPlan& P = hp.dev;
+    Ws<unsigned int> d_first((size_t)kMaxLevels + 1);
+    strongest_counts_kernel<<<1, 64, 0, stream()>>>(F.prefix, P, hp.n_words, d_first);
+    check_launch("strongest_counts_kernel");
+    APS_HIP(hipMemcpyAsync(Cd.first, d_first.get(), (size_t)(P.n + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int M = Cd.M = Cd.first[P.n];
+    if (!M) return;
+    Cd.kps.alloc(M);
+    Cd.resp.alloc(M);
+    Cd.keys.alloc(M);
+    Cd.vals.alloc(M);
+    {
+        Prof prof("fast_emit");
+        fast_emit_kernel<<<cdiv(hp.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, P, hp.n_words, Cd.kps, M);
+        check_launch("fast_emit_kernel");
+    }
+    Prof prof("fast_harris");
+    fast_harris_kernel<<<cdiv(M, 4), 256, 0, stream()>>>(F.planes, P, Cd.kps, M, Cd.resp, Cd.keys, Cd.vals);
+    check_launch("fast_harris_kernel");
+}
+
+// The selection proper, for any 64-bit key whose top 4 bits are the group: sorts (key, index) by ascending key (stable: equal keys keep
+// ascending index), flags the first cut.keep[g] items of every group, and returns the flags as a bitmap over the indices with the exclusive
+// scan of its popcounts - words[n / 64 + 1] and prefix alike; prefix[n_words] is the number kept.  No atomics; the result is deterministic.
+void select_by_key(const unsigned long long* keys, const unsigned int* vals, unsigned int n, const StrongestCut& cut,
+                   Ws<unsigned long long>& words, Ws<unsigned int>& prefix, unsigned int& n_words) {
+    Ws<unsigned long long> skeys(n);
+    Ws<unsigned int> svals(n);
+    Ws<uint8_t> flags(n);
+    size_t sbytes = 0;
+    APS_HIP(rocprim::radix_sort_pairs(nullptr, sbytes, keys, skeys.get(), vals, svals.get(), (size_t)n, 0u, 64u, stream()));
+    Ws<char> stmp(sbytes);
+    APS_HIP(rocprim::radix_sort_pairs(stmp.get(), sbytes, keys, skeys.get(), vals, svals.get(), (size_t)n, 0u, 64u, stream()));
+    strongest_flag_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(skeys, svals, cut, n, flags);
+    check_launch("strongest_flag_kernel");
+    n_words = cdiv(n, 64);
+    words.alloc((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    prefix.alloc((size_t)n_words + 1);
+    strongest_word_kernel<<<cdiv((size_t)n_words + 1, 4), 256, 0, stream()>>>(flags, n, n_words + 1, words);
+    check_launch("strongest_word_kernel");
+    auto counts = rocprim::make_transform_iterator(words.get(), PopcOp());
+    size_t tbytes = 0;
+    APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+    Ws<char> tmp(tbytes);
+    APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+}
+
+// aps_fast_extract_strongest behind its argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.
+void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, long long N,
+                     uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    ctx();
+    *count = 0;
+    const FastPlan& P = hp.dev;
+    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
+    if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
+    FastFront F;
+    fast_front(img, channels, img_layout, params, hp, F);
+    Candidates Cd;
+    harris_candidates(hp, F, Cd);
+    const unsigned int M = Cd.M;
+    // k_l: everything, or the quotas with the carry from the coarsest level down (host arithmetic on the counts read back)
+    StrongestCut cut;
+    unsigned int K = 0;
+    {
+        long long q[kMaxLevels] = {}, c = 0;
+        strongest_quota(P, N, q);
+        for (int l = kMaxLevels - 1; l >= 0; --l) {
+            const long long Ml = l < P.n ? Cd.first[l + 1] - Cd.first[l] : 0;
+            const long long kl = l >= P.n ? 0 : (long long)M <= N ? Ml : std::min(Ml, q[l] + c);
+            if (l < P.n) c = q[l] + c - kl;
+            cut.start[l] = l < P.n ? Cd.first[l] : M;
+            cut.keep[l] = (unsigned int)kl;
+            K += (unsigned int)kl;
+        }
+    }
+    *count = K;
+    if (params->max_features > 0 && K > (unsigned int)params->max_features)
+        fail(APS_E_CAP, "FAST kept %u features, more than params.max_features = %d", K, params->max_features);
+    if ((int64_t)K > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, K);
+    if (K == 0) return;
+    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
+    if (desc_layout == APS_ROWMAJOR)
+        APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
+    else
+        APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
+    APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
+    // the kept keypoints, in canonical order, and their responses
+    Ws<Keypoint> sel_kps;
+    Ws<long long> sel_resp;
+    Ws<unsigned long long> words;
+    Ws<unsigned int> prefix;
+    const Keypoint* kps = Cd.kps;
+    const long long* kresp = Cd.resp;
+    const unsigned int* d_total = F.d_total();
+    if (K < M) {
+        Prof prof("fast_select");
+        unsigned int n_words = 0;
+        select_by_key(Cd.keys, Cd.vals, M, cut, words, prefix, n_words);
+        sel_kps.alloc(K);
+        sel_resp.alloc(K);
+        strongest_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, Cd.kps, Cd.resp, sel_kps, sel_resp, K);
+        check_launch("strongest_compact_kernel");
+        kps = sel_kps;
+        kresp = sel_resp;
+        d_total = prefix.get() + n_words;
+    }
+    Out<uint8_t> odesc(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
+    Out<double> oloc(loc, (size_t)ldl + cap);
+    Out<float> oaux(aux, (size_t)cap * 4);
+    Ws<FreakDev> d_tb(1);
+    {
+        Prof prof("freak_keypoint");  // (with the upload of the pattern tables)
+        APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
+        freak_keypoint_kernel<<<cdiv(K, 4), 256, 0, stream()>>>(F.I, P, d_tb, F.kept, kps, d_total, K, odesc, desc_layout, (long long)ldd, oloc,
+                                                                (long long)ldl, oaux.present() ? oaux.get() : nullptr);
+        check_launch("freak_keypoint_kernel");
+        if (oaux.present()) {
+            strongest_aux_kernel<<<cdiv(K, 256), 256, 0, stream()>>>(kresp, K, oaux);
+            check_launch("strongest_aux_kernel");
+        }
+    }
+    unsigned int n = 0;  // the second read-back: the count the device kept is the count the host worked out
+    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
+    if (desc_layout == APS_ROWMAJOR)
+        odesc.commit_2d(64, K, (size_t)ldd);
+    else
+        odesc.commit_2d(K, 64, (size_t)ldd);
+    oloc.commit_2d(K, 2, (size_t)ldl);
+    oaux.commit((size_t)K * 4);
 }
 
 }  // namespace
@@ -641,6 +952,61 @@ int aps_fast_pyramid_plan(int height, int width, int n_levels, int scale_num, in
             if (heights) heights[l] = hp.dev.lv[l].h;
             if (widths) widths[l] = hp.dev.lv[l].w;
         }
+    });
+}
+
+int aps_fast_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_fast_strongest_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        const aps_fast_pyramid_params& pyr = params->pyramid;
+        APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+        check_args(img, height, width, channels, img_layout, pyr.fast, desc_layout, cap);
+        check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+        strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
+                        params->n_strongest, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_fast_strongest_quota(int height, int width, int n_levels, int scale_num, int scale_den, int n_strongest, int* quota, int* n_used) {
+    return guarded([&] {
+        APS_REQUIRE(n_used, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
+        APS_REQUIRE(n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+        check_pyramid(n_levels, scale_num, scale_den);
+        const HostPlan hp = make_plan(height, width, n_levels, scale_num, scale_den);
+        long long q[kMaxLevels] = {};
+        strongest_quota(hp.dev, n_strongest, q);
+        *n_used = hp.dev.n;
+        for (int l = 0; quota && l < hp.dev.n; ++l) quota[l] = (int)q[l];
+    });
+}
+
+int aps_fast_harris(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_pyramid_params* params,
+                    int64_t* response, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        check_args(img, height, width, channels, img_layout, params->fast, APS_ROWMAJOR, cap);
+        check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+        const HostPlan hp = make_plan(height, width, params->n_levels, params->scale_num, params->scale_den);
+        ctx();
+        *count = 0;
+        if (std::min(height, width) < 2 * host_pattern().margin + 1) return;
+        FastFront F;
+        fast_front(img, channels, img_layout, &params->fast, hp, F);
+        Candidates Cd;
+        harris_candidates(hp, F, Cd);
+        *count = Cd.M;
+        if (!response || !Cd.M) {  // (the count alone)
+            APS_HIP(hipStreamSynchronize(stream()));
+            return;
+        }
+        APS_REQUIRE(cap >= (int64_t)Cd.M, APS_E_CAP, "response capacity %lld < %u candidates", (long long)cap, Cd.M);
+        static_assert(sizeof(long long) == sizeof(int64_t), "responses are stored as 64-bit integers");
+        APS_HIP(hipMemcpyAsync(response, Cd.resp.get(), (size_t)Cd.M * sizeof(int64_t),
+                               is_device_ptr(response) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream()));
+        APS_HIP(hipStreamSynchronize(stream()));
     });
 }
 

@@ -788,6 +788,13 @@ def _fast_pyramid_params(input, n_levels):
     return p
 
 
+def _fast_strongest_params(input, n_levels):
+    p = _capi.aps_fast_strongest_params()
+    p.pyramid = _fast_pyramid_params(input, n_levels)
+    p.n_strongest = int(input["NumStrongest"])
+    return p
+
+
 def fast_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
     """aps_fast_extract with automatic capacity: returns (binaryFeatures, validPts[, aux]); the arguments are sift_extract's.
     Features are n x 64 uint8 (FREAK, 512 bits), on the host or, with device_out, resident; validPts n x 2 [x y] 1-based,
@@ -797,7 +804,12 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumLevels (1) and input.ScaleFactor (1.2), detectORBFeatures' names, ask for a scale pyramid: NumLevels > 1 goes
     through aps_fast_extract_pyramid, which runs FAST/FREAK on every level of the plan.  validPts are then the level pixels'
     centres in image coordinates (not integers beyond level 0), aux is [score, bin, level, 0], and the rows are in ascending
-    (level, row, col) order; a corner may be reported at several levels."""
+    (level, row, col) order; a corner may be reported at several levels.
+
+    input.NumStrongest (absent by default; detectORBFeatures' nfeatures, selectStrongest) keeps at most that many rows, for any
+    NumLevels, through aps_fast_extract_strongest: a quota per level in proportion to h_l + w_l, and within a level the rows
+    with the largest integer Harris response.  The kept rows are rows of the result without the key, in the same order;
+    aux is [score, bin, level, f32(R)].  A value below 1 is an ApsError (APS_E_ARG)."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -809,7 +821,8 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
     n_levels = int(input.get("NumLevels", 1))
-    if n_levels == 1:
+    strongest = "NumStrongest" in input
+    if n_levels == 1 and not strongest:
         prm, entry, pixels = _fast_params(input), lib.aps_fast_extract, h * w
     else:
         prm, entry = _fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid
@@ -818,6 +831,9 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
         pixels = sum(hs[l] * ws[l] for l in range(used.value))
     max_features = int(input.get("maxFeatures", 0))
     cap = max(4096, pixels // 64)
+    if strongest:
+        prm, entry = _fast_strongest_params(input, n_levels), lib.aps_fast_extract_strongest
+        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
     cnt = C.c_int64(0)
     while True:
         if device_out:

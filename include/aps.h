@@ -811,6 +811,36 @@ int aps_fast_pyramid_plan(int height, int width, int n_levels, int scale_num, in
 int aps_fast_pyramid_planes(const uint8_t* img, int height, int width, int channels, int img_layout,
                             const aps_fast_pyramid_params* params, uint8_t* out, int64_t cap_bytes, int64_t* bytes);
 
+/* FAST/FREAK strongest-N (DESIGN.md "FAST/FREAK strongest-N"; detectORBFeatures' nfeatures, selectStrongest): of the rows
+ * aps_fast_extract_pyramid returns for the same image and parameters (the candidates), keep at most n_strongest - per level a quota
+ * q_l = floor(N (h_l + w_l) / sum (h + w)) (+ 1 on the first N - sum q_l levels), a short coarse level handing its unused quota to the
+ * finer ones, and within a level the candidates that come first by (Harris response descending, canonical index ascending).  The
+ * response is the integer R = 25 (A B - C^2) - (A + B)^2 of the 3 x 3 Sobel gradients summed over the 7 x 7 window of the level's plane. */
+typedef struct aps_fast_strongest_params {
+    aps_fast_pyramid_params pyramid;   /* n_levels = 1: aps_fast_extract's plan */
+    int n_strongest;                   /* N >= 1; anything else is APS_E_ARG before any device work */
+} aps_fast_strongest_params;
+
+/* Arguments, capacity, count-only mode, padding, layouts and pointers behave as aps_fast_extract_pyramid's.  *count = rows kept;
+ * cap >= min(candidates, n_strongest) always suffices; pyramid.fast.max_features is checked against the rows kept.  With cap below
+ * the rows kept nothing is written (APS_E_CAP, *count = rows kept).  The kept rows come in canonical (level, row, col) order; descriptor,
+ * location, score, bin and level of a kept row are those of the same row of aps_fast_extract_pyramid, and
+ *   aux  : [FAST score, orientation bin, level, f32(R)] (the int64 R rounded to nearest)
+ * With at most n_strongest candidates every one is kept.  The count can stay below n_strongest while candidates are dropped: what a
+ * short level 0 leaves of its quota goes to no other level.  The call reads back the candidate counts, then the final count. */
+int aps_fast_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_fast_strongest_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* The quotas q_l of that call's plan (host only, needs no device).  quota: host int[n_levels] or NULL; *n_used = levels in the plan. */
+int aps_fast_strongest_quota(int height, int width, int n_levels, int scale_num, int scale_den, int n_strongest,
+                             int* quota, int* n_used);
+
+/* Test hook: R of every candidate, in candidate order, as int64 to a host or device pointer `response` of cap elements (APS_E_CAP if
+ * too small).  *count = candidates; response = NULL reports the count alone.  It tells a Harris error from a selection error. */
+int aps_fast_harris(const uint8_t* img, int height, int width, int channels, int img_layout,
+                    const aps_fast_pyramid_params* params, int64_t* response, int64_t cap, int64_t* count);
+
 /* The integer FREAK tables the extractor uses (tests restate the contract on them; needs no device).  Every pointer may be
  * NULL.  All arrays are host int32, row-major:
  *   fields    [256][43][3]  per orientation bin and receptive field: centre offset dx, dy (pixels) and box half-side r
