@@ -83,6 +83,14 @@ class aps_surf_params(C.Structure):
                 ("upright", C.c_int), ("max_features", C.c_int)]
 
 
+class aps_sift_strongest_params(C.Structure):
+    _fields_ = [("sift", aps_sift_params), ("n_strongest", C.c_int)]
+
+
+class aps_surf_strongest_params(C.Structure):
+    _fields_ = [("surf", aps_surf_params), ("n_strongest", C.c_int)]
+
+
 class aps_fast_params(C.Structure):
     _fields_ = [("threshold", C.c_int), ("quality_num", C.c_int), ("quality_den", C.c_int), ("max_features", C.c_int)]
 
@@ -196,6 +204,10 @@ _SIGNATURES = {
                                    _vp, _i64, C.POINTER(_i64)],
     "aps_fast_strongest_quota": [_i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i)],
     "aps_fast_harris": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i64, C.POINTER(_i64)],
+    "aps_sift_extract_strongest": [_vp, _i, _i, _i, _i, C.POINTER(aps_sift_strongest_params), _vp, _i, _i64, _vp, _i64,
+                                   _vp, _i64, C.POINTER(_i64)],
+    "aps_surf_extract_strongest": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_strongest_params), _vp, _i, _i64, _vp, _i64,
+                                   _vp, _i64, C.POINTER(_i64)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
              "aps_planar_composite_compact_bytes": C.c_int64}

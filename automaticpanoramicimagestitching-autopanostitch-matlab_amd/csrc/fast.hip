@@ -27,8 +27,9 @@
 // and goes on with grids of the candidates' size:
 //   fast_emit_kernel      the candidate list
 //   fast_harris_kernel    one wave per candidate: integer Harris response of its level's plane, and the sort key (level, -R)
-//   stable radix sort (rocprim) of (key, index), strongest_flag_kernel (rank within the level < k_l, written back by index),
-//                         strongest_word_kernel (ballot), scan of the popcounts, strongest_compact_kernel (canonical order again)
+//   select_by_key         (select_dev.h, shared with sift.hip and surf.hip) stable radix sort (rocprim) of (key, index),
+//                         strongest_flag_kernel (rank within the level < k_l, written back by index), strongest_word_kernel (ballot),
+//                         scan of the popcounts; then strongest_compact_kernel (canonical order again)
 //   freak_keypoint_kernel on the kept keypoints only; strongest_aux_kernel writes f32(R) into aux[3]
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,7 @@
 
 #include "aps_internal.h"
 #include "integral_dev.h"
+#include "select_dev.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -489,38 +491,7 @@ __global__ void strongest_counts_kernel(const unsigned int* __restrict__ prefix,
         out[l] = prefix[n_words];
 }
 
-// The cut of a sorted key sequence: group g (the key's top 4 bits) starts at start[g] and keeps its first keep[g] items.
-struct StrongestCut {
-    unsigned int start[kMaxLevels], keep[kMaxLevels];
-};
-
-// position p of the sorted sequence -> flag of the item it came from
-__global__ __launch_bounds__(256) void strongest_flag_kernel(const unsigned long long* __restrict__ sorted_keys,
-                                                             const unsigned int* __restrict__ sorted_vals, const StrongestCut cut,
-                                                             unsigned int n, uint8_t* __restrict__ flags) {
-    const unsigned int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const int grp = (int)(sorted_keys[p] >> 60);
-    unsigned int start = 0, keep = 0;
-#pragma unroll
-    for (int l = 0; l < kMaxLevels; ++l)  // (constant indices: the table stays in scalar registers)
-        if (grp == l) {
-            start = cut.start[l];
-            keep = cut.keep[l];
-        }
-    flags[sorted_vals[p]] = p - start < keep ? 1 : 0;
-}
-
-// one wave per word: its ballot over 64 flags (a word beyond the n flags is zero)
-__global__ __launch_bounds__(256) void strongest_word_kernel(const uint8_t* __restrict__ flags, unsigned int n, unsigned int n_words,
-                                                             unsigned long long* __restrict__ words) {
-    const int lane = threadIdx.x & 63;
-    const unsigned int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (q >= n_words) return;  // (uniform in the wave)
-    const unsigned int i = q * 64 + lane;
-    const unsigned long long mask = __ballot(i < n && flags[i] != 0);
-    if (lane == 0) words[q] = mask;
-}
+static_assert(kMaxLevels == kSelectGroups, "a level is a group of the selection (select_dev.h: StrongestCut, strongest_flag_kernel)");
 
 // Ordered compaction of the flagged candidates, as fast_emit_kernel's: canonical order is kept.
 __global__ __launch_bounds__(256) void strongest_compact_kernel(const unsigned long long* __restrict__ words, const unsigned int* __restrict__ prefix,
@@ -786,32 +757,6 @@ void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
     Prof prof("fast_harris");
     fast_harris_kernel<<<cdiv(M, 4), 256, 0, stream()>>>(F.planes, P, Cd.kps, M, Cd.resp, Cd.keys, Cd.vals);
     check_launch("fast_harris_kernel");
-}
-
-// The selection proper, for any 64-bit key whose top 4 bits are the group: sorts (key, index) by ascending key (stable: equal keys keep
-// ascending index), flags the first cut.keep[g] items of every group, and returns the flags as a bitmap over the indices with the exclusive
-// scan of its popcounts - words[n / 64 + 1] and prefix alike; prefix[n_words] is the number kept.  No atomics; the result is deterministic.
-void select_by_key(const unsigned long long* keys, const unsigned int* vals, unsigned int n, const StrongestCut& cut,
-                   Ws<unsigned long long>& words, Ws<unsigned int>& prefix, unsigned int& n_words) {
-    Ws<unsigned long long> skeys(n);
-    Ws<unsigned int> svals(n);
-    Ws<uint8_t> flags(n);
-    size_t sbytes = 0;
-    APS_HIP(rocprim::radix_sort_pairs(nullptr, sbytes, keys, skeys.get(), vals, svals.get(), (size_t)n, 0u, 64u, stream()));
-    Ws<char> stmp(sbytes);
-    APS_HIP(rocprim::radix_sort_pairs(stmp.get(), sbytes, keys, skeys.get(), vals, svals.get(), (size_t)n, 0u, 64u, stream()));
-    strongest_flag_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(skeys, svals, cut, n, flags);
-    check_launch("strongest_flag_kernel");
-    n_words = cdiv(n, 64);
-    words.alloc((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
-    prefix.alloc((size_t)n_words + 1);
-    strongest_word_kernel<<<cdiv((size_t)n_words + 1, 4), 256, 0, stream()>>>(flags, n, n_words + 1, words);
-    check_launch("strongest_word_kernel");
-    auto counts = rocprim::make_transform_iterator(words.get(), PopcOp());
-    size_t tbytes = 0;
-    APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-    Ws<char> tmp(tbytes);
-    APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
 }
 
 // aps_fast_extract_strongest behind its argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.

@@ -14,6 +14,9 @@
 //   extrema_wave_kernel            : 26-neighbour test of every octave in one launch, one wave per strip of columns.
 //   refine_kernel                  : Newton refinement + contrast/edge tests, one lane per candidate.
 //   orient_kernel / descr_kernel   : one 64-lane wave per keypoint, histograms in LDS (int64 atomics).
+//   sift_contr_key_kernel, select_by_key (select_dev.h), sift_select_compact_kernel
+//                                  : aps_sift_extract_strongest only - the N rows of largest contrast, picked from the list of
+//                                    oriented keypoints before descr_kernel runs (DESIGN.md "Strongest-N for SIFT and SURF").
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,6 +28,7 @@
 #endif
 
 #include "aps_internal.h"
+#include "select_dev.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -967,6 +971,35 @@ __global__ void expand_oriented_kernel(const unsigned int* __restrict__ ori_coun
     }
 }
 
+// ---- strongest-N (DESIGN.md "Strongest-N for SIFT and SURF") ---------------------------------------------
+// The contrast of every output row's keypoint (aux[:, 2] of the row) as the selection's key (select_dev.h: one group), and the
+// row's index as the sort's value.  The orientations of one keypoint tie; the stable sort keeps the lower bin first.
+__global__ __launch_bounds__(256) void sift_contr_key_kernel(const KpRec* __restrict__ kps, const OrientedKp* __restrict__ oks,
+                                                             unsigned int n, unsigned long long* __restrict__ keys,
+                                                             unsigned int* __restrict__ vals) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = strength_key_f32(kps[oks[i].kp].contr);
+    vals[i] = i;
+}
+
+// Ordered compaction of the flagged rows: bit k of word q is row 64 q + k, which becomes row prefix[q] + (set bits below k).
+__global__ __launch_bounds__(256) void sift_select_compact_kernel(const unsigned long long* __restrict__ words,
+                                                                  const unsigned int* __restrict__ prefix, unsigned int n_words,
+                                                                  const OrientedKp* __restrict__ oks, unsigned int n,
+                                                                  OrientedKp* __restrict__ out, unsigned int kcap) {
+    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_words) return;
+    unsigned long long bits = words[q];
+    unsigned int pos = prefix[q];
+    while (bits) {
+        const int k = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        if (pos < kcap && q * 64 + k < n) out[pos] = oks[q * 64 + k];
+        ++pos;
+    }
+}
+
 // ---- descriptor: one wave per oriented keypoint -------------------------------------------------------
 constexpr int kD = 4, kN = 8, kHistLen = (kD + 2) * (kD + 2) * (kN + 2);  // 360
 constexpr int kDescQueue = 512;  // queued samples per wave between two strided passes over the queue
@@ -1414,321 +1447,354 @@ static unsigned long long diff(const void* a, const void* b, size_t n_words, uns
 
 using namespace aps;
 
+// aps_sift_extract (n_strongest = 0: every row) and aps_sift_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF": the
+// n_strongest rows of largest contrast) behind one body.  The argument checks come before any device work.
+static void sift_chain(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
+                       long long n_strongest, float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap,
+                       int64_t* count) {
+    APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
+    APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
+    APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
+    APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
+    APS_REQUIRE(params->n_layers >= 1 && params->n_layers <= 5, APS_E_ARG, "NumLayersInOctave must be in 1..5");
+    APS_REQUIRE(params->sigma > 0.5, APS_E_ARG, "Sigma must exceed the assumed camera blur 0.5");
+    APS_REQUIRE(params->contrast_threshold >= 0 && params->edge_threshold >= 1, APS_E_ARG, "bad thresholds");
+    APS_REQUIRE(cap >= 0, APS_E_ARG, "negative capacity");
+    APS_REQUIRE(2 * (int64_t)height < 65536 && 2 * (int64_t)width < 65536, APS_E_DIM, "image side must be < 32768");
+    ctx();
+    *count = 0;
+    const int nl = params->n_layers;
+    const int H = height, W = width;
+    In<uint8_t> dimg(img, (size_t)H * W * channels);
+    Ws<float> up, scratch;  // (up: the doubled gray plane, only when the fused base kernel does not apply)
+    Ws<uint8_t> gray8;      // the source gray plane as bytes (gray_u8_kernel), read by blur_base_kernel
+    const int n_oct = std::min(num_octaves(H, W), 16);
+    if (n_oct <= 0) return;
+    // pyramid storage
+    std::vector<Ws<float>> G((size_t)n_oct * (nl + 3));
+    PyrTable table;
+    std::memset(&table, 0, sizeof table);
+    table.n_oct = n_oct;
+    table.nl = nl;
+    table.sigma = (float)params->sigma;
+    double sig[16];
+    sig[0] = params->sigma;
+    const double kf = std::pow(2.0, 1.0 / nl);
+    for (int i = 1; i < nl + 3; ++i) {
+        const double sp = std::pow(kf, (double)(i - 1)) * params->sigma, st = sp * kf;
+        sig[i] = std::sqrt(st * st - sp * sp);
+    }
+    int ow = 2 * W, oh = 2 * H;
+    bool base_written = false;  // the previous octave's blur of plane nl wrote this octave's base
+    for (int o = 0; o < n_oct; ++o) {
+        if (o > 0) {
+            ow = std::max(1, ow / 2);
+            oh = std::max(1, oh / 2);
+        }
+        OctaveDesc& od = table.oct[o];
+        od.w = ow;
+        od.h = oh;
+        const size_t px = (size_t)ow * oh;
+        for (int i = 0; i < nl + 3; ++i)
+            if (!(i == 0 && base_written)) G[o * (nl + 3) + i].alloc(px);
+        if (o == 0) {
+            double sd = params->sigma * params->sigma - 4.0 * 0.5 * 0.5;
+            if (sd < 0.01) sd = 0.01;
+            if (!launch_base_blur(dimg, H, W, channels, img_layout, std::sqrt(sd), G[0], gray8)) {
+                up.alloc((size_t)4 * H * W);
+                gray_up_kernel<<<dim3(cdiv(2 * W, kGUW), cdiv(2 * H, kGUH)), 256, 0, stream()>>>(dimg, H, W, channels, img_layout, up);
+                check_launch("gray_up_kernel");
+                launch_blur(up, oh, ow, std::sqrt(sd), G[0], scratch);
+            }
+        } else if (!base_written) {
+            const OctaveDesc& pd = table.oct[o - 1];
+            decimate_kernel<<<dim3(cdiv(ow, 256), oh), 256, 0, stream()>>>(G[(o - 1) * (nl + 3) + nl], pd.h, pd.w,
+                                                                        oh, ow, G[o * (nl + 3)]);
+            check_launch("decimate_kernel");
+        }
+        base_written = false;
+        for (int i = 1; i < nl + 3; ++i) {
+            if (i == nl && o + 1 < n_oct) {
+                const int nw = std::max(1, ow / 2), nh = std::max(1, oh / 2);
+                G[(o + 1) * (nl + 3)].alloc((size_t)nw * nh);
+                base_written = launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch,
+                                           G[(o + 1) * (nl + 3)], nh, nw);
+            } else {
+                launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch);
+            }
+        }
+        for (int i = 0; i < nl + 3; ++i) od.G[i] = G[o * (nl + 3) + i];
+    }
+#ifdef APS_DBG
+    static const int dbg_replay = std::getenv("APS_DBG_REPLAY") ? std::atoi(std::getenv("APS_DBG_REPLAY")) : 0;
+    Ws<unsigned long long> dbg_slot(1);
+    if (dbg_replay > 0) {
+        dbg::g_stat[dbg::kCalls]++;
+        unsigned long long h = 0;
+        for (int o = 0; o < std::min(n_oct, 3); ++o)
+            for (int i = 0; i < nl + 3; ++i)
+                h = h * 1000003ull + dbg::cks(G[o * (nl + 3) + i].get(), (size_t)table.oct[o].w * table.oct[o].h, 1, 1, dbg_slot);
+        std::lock_guard<std::mutex> lk(dbg::g_mu);
+        auto it = dbg::g_pyr.find((const void*)img);
+        if (it == dbg::g_pyr.end())
+            dbg::g_pyr[(const void*)img] = h;
+        else if (it->second != h)
+            dbg::g_stat[dbg::kPyrChanged]++;
+    }
+#endif
+    // extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch
+    Ws<PyrTable> d_table(1);
+    APS_HIP(hipMemcpyAsync(d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
+    const unsigned int cand_cap = (unsigned int)std::min<size_t>(
+        params->max_features > 0 ? (size_t)params->max_features : std::max<size_t>((size_t)H * W / 2, 65536), 1u << 26);
+    unsigned int cells_cap = (unsigned int)std::min<size_t>(std::max<size_t>((size_t)H * W / 2, 1u << 18), 1u << 27);
+    Ws<unsigned long long> cells(cells_cap);
+    Ws<KpRec> recs(cand_cap);
+    Ws<unsigned int> d_count(2);  // [0] cells, [1] refined records
+    const float thr = (float)(int)std::floor(0.5 * params->contrast_threshold / nl * 255.0);
+    unsigned int h_counts[2] = {0, 0};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        APS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), stream()));
+        // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
+        ExtremaWavePlan plan;
+        std::memset(&plan, 0, sizeof plan);
+        int run = 0;
+        for (int o = 0; o < 16; ++o) {
+            plan.job_ptr[o] = run;
+            plan.nstrip[o] = plan.ch[o] = 1;
+            if (o >= n_oct) continue;
+            const OctaveDesc& od = table.oct[o];
+            if (od.w <= 2 * kBorder || od.h <= 2 * kBorder) continue;
+            const int ns = cdiv(od.w, kWS);
+            // rows per chunk (every chunk re-reads two halo rows): ~8000 wave jobs on the largest octave, >= 24 rows
+            int ch = (int)(((long long)od.h * ns + 8191) / 8192);
+            ch = std::max(24, ch);
+            plan.nstrip[o] = ns;
+            plan.ch[o] = ch;
+            run += ns * cdiv(od.h, ch);
+        }
+        plan.job_ptr[16] = run;
+        if (run > 0) {
+            Prof prof("sift_extrema");
+            const int wgs = cdiv(run, 4);
+            auto launch_sweep = [&](unsigned long long* cl, unsigned int* ct) {
+                switch (nl) {
+                    case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                    case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                    case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                    case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                    default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
+                }
+            };
+            launch_sweep(cells, d_count);
+            check_launch("extrema_wave_kernel");
+#ifdef APS_DBG
+            if (dbg_replay > 0) {
+                Ws<unsigned long long> cells2(cells_cap);
+                Ws<unsigned int> cnt2(2);
+                unsigned int n1 = 0, n2 = 0;
+                APS_HIP(hipMemcpyAsync(&n1, d_count, 4, hipMemcpyDeviceToHost, stream()));
+                APS_HIP(hipStreamSynchronize(stream()));
+                const unsigned long long c1 = dbg::cks(cells.get(), std::min(n1, cells_cap), 2, 0, dbg_slot);
+                for (int rep = 0; rep < dbg_replay; ++rep) {
+                    APS_HIP(hipMemsetAsync(cnt2, 0, 8, stream()));
+                    launch_sweep(cells2, cnt2);
+                    APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
+                    APS_HIP(hipStreamSynchronize(stream()));
+                    const unsigned long long c2 = dbg::cks(cells2.get(), std::min(n2, cells_cap), 2, 0, dbg_slot);
+                    dbg::g_stat[dbg::kExtReplays]++;
+                    if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kExtDiff]++;
+                }
+            }
+#endif
+        }
+        APS_HIP(hipMemcpyAsync(h_counts, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+        APS_HIP(hipStreamSynchronize(stream()));
+        if (h_counts[0] <= cells_cap) break;
+        // flat or band-limited images can have far more (weak) scale-space extrema than the default room:
+        // grow to the exact need and sweep once more
+        APS_REQUIRE(attempt == 0, APS_E_INTERNAL, "extrema count changed between identical sweeps");
+        cells_cap = h_counts[0];
+        cells.alloc(cells_cap);
+    }
+    if (h_counts[0] > 0) {
+        Prof prof("sift_refine");
+        refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap,
+                                                                 (float)params->contrast_threshold,
+                                                                 (float)params->edge_threshold, recs, d_count.get() + 1,
+                                                                 cand_cap);
+        check_launch("refine_kernel");
+#ifdef APS_DBG
+        if (dbg_replay > 0) {
+            Ws<KpRec> recs2(cand_cap);
+            Ws<unsigned int> cnt2(1);
+            unsigned int n1 = 0, n2 = 0;
+            APS_HIP(hipMemcpyAsync(&n1, d_count.get() + 1, 4, hipMemcpyDeviceToHost, stream()));
+            APS_HIP(hipStreamSynchronize(stream()));
+            const unsigned long long c1 = dbg::cks(recs.get(), std::min(n1, cand_cap), 6, 0, dbg_slot);
+            for (int rep = 0; rep < dbg_replay; ++rep) {
+                APS_HIP(hipMemsetAsync(cnt2, 0, 4, stream()));
+                refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap, (float)params->contrast_threshold,
+                                                                         (float)params->edge_threshold, recs2, cnt2, cand_cap);
+                APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
+                APS_HIP(hipStreamSynchronize(stream()));
+                const unsigned long long c2 = dbg::cks(recs2.get(), std::min(n2, cand_cap), 6, 0, dbg_slot);
+                dbg::g_stat[dbg::kRefReplays]++;
+                if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kRefDiff]++;
+            }
+        }
+#endif
+    }
+    unsigned int n_cand = 0;
+    APS_HIP(hipMemcpyAsync(&n_cand, d_count.get() + 1, sizeof n_cand, hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    if (n_cand > cand_cap)
+        fail(APS_E_CAP, "SIFT found %u extrema, more than the candidate capacity %u (raise params.max_features)", n_cand, cand_cap);
+    if (n_cand == 0) return;
+    // canonical order + dedupe
+    Ws<unsigned long long> keys(n_cand), keys_s(n_cand);
+    Ws<unsigned int> idx(n_cand), idx_s(n_cand), flag(n_cand), pos(n_cand);
+    rec_keys_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, n_cand, keys, idx);
+    size_t tb = 0;
+    APS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
+    Ws<char> tmp(tb);
+    APS_HIP(rocprim::radix_sort_pairs(tmp.get(), tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
+    unique_flag_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(keys_s, n_cand, flag);
+    size_t tb2 = 0;
+    APS_HIP(rocprim::exclusive_scan(nullptr, tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
+    Ws<char> tmp2(tb2);
+    APS_HIP(rocprim::exclusive_scan(tmp2.get(), tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
+    unsigned int last_pos = 0, last_flag = 0;
+    APS_HIP(hipMemcpyAsync(&last_pos, pos.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipMemcpyAsync(&last_flag, flag.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n_kp = last_pos + last_flag;
+    Ws<KpRec> kps(n_kp);
+    compact_recs_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, idx_s, flag, pos, n_cand, kps);
+    check_launch("compact_recs_kernel");
+    // orientations
+    Ws<unsigned int> ocount(n_kp), opos(n_kp);
+    Ws<float> oangle((size_t)n_kp * kOriBins);
+    Ws<unsigned char> obin((size_t)n_kp * kOriBins);
+#ifdef APS_DBG
+    if (dbg_replay > 0) {
+        APS_HIP(hipMemsetAsync(oangle, 0, (size_t)n_kp * kOriBins * 4, stream()));
+        APS_HIP(hipMemsetAsync(obin, 0, (size_t)n_kp * kOriBins, stream()));
+    }
+#endif
+    {
+        Prof prof("sift_orient");
+        orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount, oangle, obin);
+    }
+    check_launch("orient_kernel");
+#ifdef APS_DBG
+    if (dbg_replay > 0) {
+        Ws<unsigned int> ocount2(n_kp);
+        Ws<float> oangle2((size_t)n_kp * kOriBins);
+        Ws<unsigned char> obin2(((size_t)n_kp * kOriBins + 3) & ~(size_t)3);
+        for (int rep = 0; rep < dbg_replay; ++rep) {
+            APS_HIP(hipMemsetAsync(oangle2, 0, (size_t)n_kp * kOriBins * 4, stream()));
+            APS_HIP(hipMemsetAsync(obin2, 0, (size_t)n_kp * kOriBins, stream()));
+            orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount2, oangle2, obin2);
+            const unsigned long long d = dbg::diff(ocount.get(), ocount2.get(), n_kp, dbg_slot) +
+                                         dbg::diff(oangle.get(), oangle2.get(), (size_t)n_kp * kOriBins, dbg_slot) +
+                                         dbg::diff(obin.get(), obin2.get(), (size_t)n_kp * kOriBins / 4, dbg_slot);
+            dbg::g_stat[dbg::kOriReplays]++;
+            if (d) dbg::g_stat[dbg::kOriDiff]++;
+            dbg::g_stat[dbg::kOriWords] += (long long)d;
+        }
+    }
+#endif
+    size_t tb3 = 0;
+    APS_HIP(rocprim::exclusive_scan(nullptr, tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
+    Ws<char> tmp3(tb3);
+    APS_HIP(rocprim::exclusive_scan(tmp3.get(), tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
+    unsigned int lp = 0, lc = 0;
+    APS_HIP(hipMemcpyAsync(&lp, opos.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipMemcpyAsync(&lc, ocount.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n_all = lp + lc;  // the oriented keypoints: the rows of the call without n_strongest
+    const unsigned int n_out = n_strongest > 0 ? (unsigned int)std::min<long long>(n_all, n_strongest) : n_all;
+    *count = n_out;
+    if ((int64_t)n_out > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n_out);
+    if (n_out == 0) return;
+    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
+    if (desc_layout == APS_ROWMAJOR)
+        APS_REQUIRE(ldd >= 128, APS_E_DIM, "ldd < 128");
+    else
+        APS_REQUIRE(ldd >= n_out, APS_E_DIM, "ldd < count");
+    APS_REQUIRE(ldl >= n_out, APS_E_DIM, "ldl < count");
+    Ws<OrientedKp> oks_all(n_all), oks_sel;
+    expand_oriented_kernel<<<cdiv(n_kp, 256), 256, 0, stream()>>>(ocount, opos, oangle, n_kp, oks_all);
+    check_launch("expand_oriented_kernel");
+    const OrientedKp* oks = oks_all;
+    if (n_out < n_all) {
+        // strongest-N: the n_out rows that come first by (contrast descending, canonical index ascending), in canonical order
+        Prof prof("sift_select");
+        Ws<unsigned long long> skeys(n_all), words;
+        Ws<unsigned int> svals(n_all), sprefix;
+        sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
+        check_launch("sift_contr_key_kernel");
+        unsigned int n_words = 0;
+        select_by_key(skeys, svals, n_all, single_group_cut(n_all, n_out), words, sprefix, n_words, 32u);
+        oks_sel.alloc(n_out);
+        sift_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, sprefix, n_words, oks_all, n_all, oks_sel, n_out);
+        check_launch("sift_select_compact_kernel");
+        oks = oks_sel;
+    }
+    const size_t desc_elems = desc_layout == APS_ROWMAJOR ? (size_t)(n_out - 1) * ldd + 128 : (size_t)127 * ldd + n_out;
+    Out<float> odesc(desc, desc_elems), oaux(aux, (size_t)n_out * 4);
+    Out<double> oloc(loc, (size_t)ldl + n_out);
+    {
+        Prof prof("sift_descr");
+        descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
+                                                           oaux.present() ? oaux.get() : nullptr);
+    }
+    check_launch("descr_kernel");
+#ifdef APS_DBG
+    if (dbg_replay > 0 && desc_layout == APS_ROWMAJOR && ldd == 128) {
+        Ws<float> desc2((size_t)n_out * 128), aux2((size_t)n_out * 4);
+        Ws<double> loc2((size_t)2 * n_out);
+        for (int rep = 0; rep < dbg_replay; ++rep) {
+            descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, desc2, desc_layout, 128, loc2, n_out,
+                                                               oaux.present() ? aux2.get() : nullptr);
+            unsigned long long d = dbg::diff(odesc.get(), desc2.get(), (size_t)n_out * 128, dbg_slot) +
+                                   dbg::diff(oloc.get(), loc2.get(), (size_t)2 * n_out, dbg_slot) +
+                                   dbg::diff(oloc.get() + ldl, loc2.get() + n_out, (size_t)2 * n_out, dbg_slot);
+            if (oaux.present()) d += dbg::diff(oaux.get(), aux2.get(), (size_t)n_out * 4, dbg_slot);
+            dbg::g_stat[dbg::kDesReplays]++;
+            if (d) dbg::g_stat[dbg::kDesDiff]++;
+            dbg::g_stat[dbg::kDesWords] += (long long)d;
+        }
+    }
+#endif
+    // strided copy-back: the elements between the logical rows / columns (ldd, ldl beyond the count) stay the caller's
+    if (desc_layout == APS_ROWMAJOR)
+        odesc.commit_2d(128, n_out, (size_t)ldd);
+    else
+        odesc.commit_2d(n_out, 128, (size_t)ldd);
+    oloc.commit_2d(n_out, 2, (size_t)ldl);
+    oaux.commit();
+    APS_HIP(hipStreamSynchronize(stream()));
+}
+
 extern "C" {
 
 int aps_sift_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
                      const aps_sift_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] { sift_chain(img, height, width, channels, img_layout, params, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count); });
+}
+
+int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_sift_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
-        APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
-        APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
-        APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
-        APS_REQUIRE(params->n_layers >= 1 && params->n_layers <= 5, APS_E_ARG, "NumLayersInOctave must be in 1..5");
-        APS_REQUIRE(params->sigma > 0.5, APS_E_ARG, "Sigma must exceed the assumed camera blur 0.5");
-        APS_REQUIRE(params->contrast_threshold >= 0 && params->edge_threshold >= 1, APS_E_ARG, "bad thresholds");
-        APS_REQUIRE(cap >= 0, APS_E_ARG, "negative capacity");
-        APS_REQUIRE(2 * (int64_t)height < 65536 && 2 * (int64_t)width < 65536, APS_E_DIM, "image side must be < 32768");
-        ctx();
-        *count = 0;
-        const int nl = params->n_layers;
-        const int H = height, W = width;
-        In<uint8_t> dimg(img, (size_t)H * W * channels);
-        Ws<float> up, scratch;  // (up: the doubled gray plane, only when the fused base kernel does not apply)
-        Ws<uint8_t> gray8;      // the source gray plane as bytes (gray_u8_kernel), read by blur_base_kernel
-        const int n_oct = std::min(num_octaves(H, W), 16);
-        if (n_oct <= 0) return;
-        // pyramid storage
-        std::vector<Ws<float>> G((size_t)n_oct * (nl + 3));
-        PyrTable table;
-        std::memset(&table, 0, sizeof table);
-        table.n_oct = n_oct;
-        table.nl = nl;
-        table.sigma = (float)params->sigma;
-        double sig[16];
-        sig[0] = params->sigma;
-        const double kf = std::pow(2.0, 1.0 / nl);
-        for (int i = 1; i < nl + 3; ++i) {
-            const double sp = std::pow(kf, (double)(i - 1)) * params->sigma, st = sp * kf;
-            sig[i] = std::sqrt(st * st - sp * sp);
-        }
-        int ow = 2 * W, oh = 2 * H;
-        bool base_written = false;  // the previous octave's blur of plane nl wrote this octave's base
-        for (int o = 0; o < n_oct; ++o) {
-            if (o > 0) {
-                ow = std::max(1, ow / 2);
-                oh = std::max(1, oh / 2);
-            }
-            OctaveDesc& od = table.oct[o];
-            od.w = ow;
-            od.h = oh;
-            const size_t px = (size_t)ow * oh;
-            for (int i = 0; i < nl + 3; ++i)
-                if (!(i == 0 && base_written)) G[o * (nl + 3) + i].alloc(px);
-            if (o == 0) {
-                double sd = params->sigma * params->sigma - 4.0 * 0.5 * 0.5;
-                if (sd < 0.01) sd = 0.01;
-                if (!launch_base_blur(dimg, H, W, channels, img_layout, std::sqrt(sd), G[0], gray8)) {
-                    up.alloc((size_t)4 * H * W);
-                    gray_up_kernel<<<dim3(cdiv(2 * W, kGUW), cdiv(2 * H, kGUH)), 256, 0, stream()>>>(dimg, H, W, channels, img_layout, up);
-                    check_launch("gray_up_kernel");
-                    launch_blur(up, oh, ow, std::sqrt(sd), G[0], scratch);
-                }
-            } else if (!base_written) {
-                const OctaveDesc& pd = table.oct[o - 1];
-                decimate_kernel<<<dim3(cdiv(ow, 256), oh), 256, 0, stream()>>>(G[(o - 1) * (nl + 3) + nl], pd.h, pd.w,
-                                                                            oh, ow, G[o * (nl + 3)]);
-                check_launch("decimate_kernel");
-            }
-            base_written = false;
-            for (int i = 1; i < nl + 3; ++i) {
-                if (i == nl && o + 1 < n_oct) {
-                    const int nw = std::max(1, ow / 2), nh = std::max(1, oh / 2);
-                    G[(o + 1) * (nl + 3)].alloc((size_t)nw * nh);
-                    base_written = launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch,
-                                               G[(o + 1) * (nl + 3)], nh, nw);
-                } else {
-                    launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch);
-                }
-            }
-            for (int i = 0; i < nl + 3; ++i) od.G[i] = G[o * (nl + 3) + i];
-        }
-#ifdef APS_DBG
-        static const int dbg_replay = std::getenv("APS_DBG_REPLAY") ? std::atoi(std::getenv("APS_DBG_REPLAY")) : 0;
-        Ws<unsigned long long> dbg_slot(1);
-        if (dbg_replay > 0) {
-            dbg::g_stat[dbg::kCalls]++;
-            unsigned long long h = 0;
-            for (int o = 0; o < std::min(n_oct, 3); ++o)
-                for (int i = 0; i < nl + 3; ++i)
-                    h = h * 1000003ull + dbg::cks(G[o * (nl + 3) + i].get(), (size_t)table.oct[o].w * table.oct[o].h, 1, 1, dbg_slot);
-            std::lock_guard<std::mutex> lk(dbg::g_mu);
-            auto it = dbg::g_pyr.find((const void*)img);
-            if (it == dbg::g_pyr.end())
-                dbg::g_pyr[(const void*)img] = h;
-            else if (it->second != h)
-                dbg::g_stat[dbg::kPyrChanged]++;
-        }
-#endif
-        // extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch
-        Ws<PyrTable> d_table(1);
-        APS_HIP(hipMemcpyAsync(d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
-        const unsigned int cand_cap = (unsigned int)std::min<size_t>(
-            params->max_features > 0 ? (size_t)params->max_features : std::max<size_t>((size_t)H * W / 2, 65536), 1u << 26);
-        unsigned int cells_cap = (unsigned int)std::min<size_t>(std::max<size_t>((size_t)H * W / 2, 1u << 18), 1u << 27);
-        Ws<unsigned long long> cells(cells_cap);
-        Ws<KpRec> recs(cand_cap);
-        Ws<unsigned int> d_count(2);  // [0] cells, [1] refined records
-        const float thr = (float)(int)std::floor(0.5 * params->contrast_threshold / nl * 255.0);
-        unsigned int h_counts[2] = {0, 0};
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            APS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), stream()));
-            // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
-            ExtremaWavePlan plan;
-            std::memset(&plan, 0, sizeof plan);
-            int run = 0;
-            for (int o = 0; o < 16; ++o) {
-                plan.job_ptr[o] = run;
-                plan.nstrip[o] = plan.ch[o] = 1;
-                if (o >= n_oct) continue;
-                const OctaveDesc& od = table.oct[o];
-                if (od.w <= 2 * kBorder || od.h <= 2 * kBorder) continue;
-                const int ns = cdiv(od.w, kWS);
-                // rows per chunk (every chunk re-reads two halo rows): ~8000 wave jobs on the largest octave, >= 24 rows
-                int ch = (int)(((long long)od.h * ns + 8191) / 8192);
-                ch = std::max(24, ch);
-                plan.nstrip[o] = ns;
-                plan.ch[o] = ch;
-                run += ns * cdiv(od.h, ch);
-            }
-            plan.job_ptr[16] = run;
-            if (run > 0) {
-                Prof prof("sift_extrema");
-                const int wgs = cdiv(run, 4);
-                auto launch_sweep = [&](unsigned long long* cl, unsigned int* ct) {
-                    switch (nl) {
-                        case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                        case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                        case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                        case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                        default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                    }
-                };
-                launch_sweep(cells, d_count);
-                check_launch("extrema_wave_kernel");
-#ifdef APS_DBG
-                if (dbg_replay > 0) {
-                    Ws<unsigned long long> cells2(cells_cap);
-                    Ws<unsigned int> cnt2(2);
-                    unsigned int n1 = 0, n2 = 0;
-                    APS_HIP(hipMemcpyAsync(&n1, d_count, 4, hipMemcpyDeviceToHost, stream()));
-                    APS_HIP(hipStreamSynchronize(stream()));
-                    const unsigned long long c1 = dbg::cks(cells.get(), std::min(n1, cells_cap), 2, 0, dbg_slot);
-                    for (int rep = 0; rep < dbg_replay; ++rep) {
-                        APS_HIP(hipMemsetAsync(cnt2, 0, 8, stream()));
-                        launch_sweep(cells2, cnt2);
-                        APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
-                        APS_HIP(hipStreamSynchronize(stream()));
-                        const unsigned long long c2 = dbg::cks(cells2.get(), std::min(n2, cells_cap), 2, 0, dbg_slot);
-                        dbg::g_stat[dbg::kExtReplays]++;
-                        if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kExtDiff]++;
-                    }
-                }
-#endif
-            }
-            APS_HIP(hipMemcpyAsync(h_counts, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-            APS_HIP(hipStreamSynchronize(stream()));
-            if (h_counts[0] <= cells_cap) break;
-            // flat or band-limited images can have far more (weak) scale-space extrema than the default room:
-            // grow to the exact need and sweep once more
-            APS_REQUIRE(attempt == 0, APS_E_INTERNAL, "extrema count changed between identical sweeps");
-            cells_cap = h_counts[0];
-            cells.alloc(cells_cap);
-        }
-        if (h_counts[0] > 0) {
-            Prof prof("sift_refine");
-            refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap,
-                                                                     (float)params->contrast_threshold,
-                                                                     (float)params->edge_threshold, recs, d_count.get() + 1,
-                                                                     cand_cap);
-            check_launch("refine_kernel");
-#ifdef APS_DBG
-            if (dbg_replay > 0) {
-                Ws<KpRec> recs2(cand_cap);
-                Ws<unsigned int> cnt2(1);
-                unsigned int n1 = 0, n2 = 0;
-                APS_HIP(hipMemcpyAsync(&n1, d_count.get() + 1, 4, hipMemcpyDeviceToHost, stream()));
-                APS_HIP(hipStreamSynchronize(stream()));
-                const unsigned long long c1 = dbg::cks(recs.get(), std::min(n1, cand_cap), 6, 0, dbg_slot);
-                for (int rep = 0; rep < dbg_replay; ++rep) {
-                    APS_HIP(hipMemsetAsync(cnt2, 0, 4, stream()));
-                    refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap, (float)params->contrast_threshold,
-                                                                             (float)params->edge_threshold, recs2, cnt2, cand_cap);
-                    APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
-                    APS_HIP(hipStreamSynchronize(stream()));
-                    const unsigned long long c2 = dbg::cks(recs2.get(), std::min(n2, cand_cap), 6, 0, dbg_slot);
-                    dbg::g_stat[dbg::kRefReplays]++;
-                    if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kRefDiff]++;
-                }
-            }
-#endif
-        }
-        unsigned int n_cand = 0;
-        APS_HIP(hipMemcpyAsync(&n_cand, d_count.get() + 1, sizeof n_cand, hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        if (n_cand > cand_cap)
-            fail(APS_E_CAP, "SIFT found %u extrema, more than the candidate capacity %u (raise params.max_features)", n_cand, cand_cap);
-        if (n_cand == 0) return;
-        // canonical order + dedupe
-        Ws<unsigned long long> keys(n_cand), keys_s(n_cand);
-        Ws<unsigned int> idx(n_cand), idx_s(n_cand), flag(n_cand), pos(n_cand);
-        rec_keys_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, n_cand, keys, idx);
-        size_t tb = 0;
-        APS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
-        Ws<char> tmp(tb);
-        APS_HIP(rocprim::radix_sort_pairs(tmp.get(), tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
-        unique_flag_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(keys_s, n_cand, flag);
-        size_t tb2 = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
-        Ws<char> tmp2(tb2);
-        APS_HIP(rocprim::exclusive_scan(tmp2.get(), tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
-        unsigned int last_pos = 0, last_flag = 0;
-        APS_HIP(hipMemcpyAsync(&last_pos, pos.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipMemcpyAsync(&last_flag, flag.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        const unsigned int n_kp = last_pos + last_flag;
-        Ws<KpRec> kps(n_kp);
-        compact_recs_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, idx_s, flag, pos, n_cand, kps);
-        check_launch("compact_recs_kernel");
-        // orientations
-        Ws<unsigned int> ocount(n_kp), opos(n_kp);
-        Ws<float> oangle((size_t)n_kp * kOriBins);
-        Ws<unsigned char> obin((size_t)n_kp * kOriBins);
-#ifdef APS_DBG
-        if (dbg_replay > 0) {
-            APS_HIP(hipMemsetAsync(oangle, 0, (size_t)n_kp * kOriBins * 4, stream()));
-            APS_HIP(hipMemsetAsync(obin, 0, (size_t)n_kp * kOriBins, stream()));
-        }
-#endif
-        {
-            Prof prof("sift_orient");
-            orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount, oangle, obin);
-        }
-        check_launch("orient_kernel");
-#ifdef APS_DBG
-        if (dbg_replay > 0) {
-            Ws<unsigned int> ocount2(n_kp);
-            Ws<float> oangle2((size_t)n_kp * kOriBins);
-            Ws<unsigned char> obin2(((size_t)n_kp * kOriBins + 3) & ~(size_t)3);
-            for (int rep = 0; rep < dbg_replay; ++rep) {
-                APS_HIP(hipMemsetAsync(oangle2, 0, (size_t)n_kp * kOriBins * 4, stream()));
-                APS_HIP(hipMemsetAsync(obin2, 0, (size_t)n_kp * kOriBins, stream()));
-                orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount2, oangle2, obin2);
-                const unsigned long long d = dbg::diff(ocount.get(), ocount2.get(), n_kp, dbg_slot) +
-                                             dbg::diff(oangle.get(), oangle2.get(), (size_t)n_kp * kOriBins, dbg_slot) +
-                                             dbg::diff(obin.get(), obin2.get(), (size_t)n_kp * kOriBins / 4, dbg_slot);
-                dbg::g_stat[dbg::kOriReplays]++;
-                if (d) dbg::g_stat[dbg::kOriDiff]++;
-                dbg::g_stat[dbg::kOriWords] += (long long)d;
-            }
-        }
-#endif
-        size_t tb3 = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
-        Ws<char> tmp3(tb3);
-        APS_HIP(rocprim::exclusive_scan(tmp3.get(), tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
-        unsigned int lp = 0, lc = 0;
-        APS_HIP(hipMemcpyAsync(&lp, opos.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipMemcpyAsync(&lc, ocount.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        const unsigned int n_out = lp + lc;
-        *count = n_out;
-        if ((int64_t)n_out > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n_out);
-        if (n_out == 0) return;
-        APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-        if (desc_layout == APS_ROWMAJOR)
-            APS_REQUIRE(ldd >= 128, APS_E_DIM, "ldd < 128");
-        else
-            APS_REQUIRE(ldd >= n_out, APS_E_DIM, "ldd < count");
-        APS_REQUIRE(ldl >= n_out, APS_E_DIM, "ldl < count");
-        Ws<OrientedKp> oks(n_out);
-        expand_oriented_kernel<<<cdiv(n_kp, 256), 256, 0, stream()>>>(ocount, opos, oangle, n_kp, oks);
-        check_launch("expand_oriented_kernel");
-        const size_t desc_elems = desc_layout == APS_ROWMAJOR ? (size_t)(n_out - 1) * ldd + 128 : (size_t)127 * ldd + n_out;
-        Out<float> odesc(desc, desc_elems), oaux(aux, (size_t)n_out * 4);
-        Out<double> oloc(loc, (size_t)ldl + n_out);
-        {
-            Prof prof("sift_descr");
-            descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
-                                                               oaux.present() ? oaux.get() : nullptr);
-        }
-        check_launch("descr_kernel");
-#ifdef APS_DBG
-        if (dbg_replay > 0 && desc_layout == APS_ROWMAJOR && ldd == 128) {
-            Ws<float> desc2((size_t)n_out * 128), aux2((size_t)n_out * 4);
-            Ws<double> loc2((size_t)2 * n_out);
-            for (int rep = 0; rep < dbg_replay; ++rep) {
-                descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, desc2, desc_layout, 128, loc2, n_out,
-                                                                   oaux.present() ? aux2.get() : nullptr);
-                unsigned long long d = dbg::diff(odesc.get(), desc2.get(), (size_t)n_out * 128, dbg_slot) +
-                                       dbg::diff(oloc.get(), loc2.get(), (size_t)2 * n_out, dbg_slot) +
-                                       dbg::diff(oloc.get() + ldl, loc2.get() + n_out, (size_t)2 * n_out, dbg_slot);
-                if (oaux.present()) d += dbg::diff(oaux.get(), aux2.get(), (size_t)n_out * 4, dbg_slot);
-                dbg::g_stat[dbg::kDesReplays]++;
-                if (d) dbg::g_stat[dbg::kDesDiff]++;
-                dbg::g_stat[dbg::kDesWords] += (long long)d;
-            }
-        }
-#endif
-        // strided copy-back: the elements between the logical rows / columns (ldd, ldl beyond the count) stay the caller's
-        if (desc_layout == APS_ROWMAJOR)
-            odesc.commit_2d(128, n_out, (size_t)ldd);
-        else
-            odesc.commit_2d(n_out, 128, (size_t)ldd);
-        oloc.commit_2d(n_out, 2, (size_t)ldl);
-        oaux.commit();
-        APS_HIP(hipStreamSynchronize(stream()));
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+        sift_chain(img, height, width, channels, img_layout, &params->sift, params->n_strongest, desc, desc_layout, ldd, loc, ldl, aux, cap,
+                   count);
     });
 }
 

@@ -14,6 +14,12 @@
 //                         canonical feature order (octave, level, row, col)
 //   exclusive scan of the words' popcounts (rocprim), surf_emit_kernel (ordered compaction, no atomics)
 //   surf_keypoint_kernel  one wave per keypoint: the 27 responses again, refinement, orientation, descriptor, outputs
+// aps_surf_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF") shares the chain up to the scan, reads the candidate count
+// back, and goes on with grids of the candidates' size:
+//   surf_emit_kernel      the candidate list
+//   surf_metric_kernel    the centre response of every candidate = its metric, as the sort key
+//   select_by_key         (select_dev.h) stable radix sort, flags, ballot words, scan; surf_select_compact_kernel (canonical order again)
+//   surf_keypoint_kernel  on the kept keypoints only
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +28,7 @@
 
 #include "aps_internal.h"
 #include "integral_dev.h"
+#include "select_dev.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -327,6 +334,195 @@ __global__ __launch_bounds__(256) void surf_keypoint_kernel(const uint32_t* __re
     }
 }
 
+// ---- strongest-N (DESIGN.md "Strongest-N for SIFT and SURF") ----------------------------------------------------------------
+// The metric of every candidate: the centre response, s_a[wave][13] of surf_keypoint_kernel - the same device function on the same
+// operands, so the same bits - as the selection's key (select_dev.h: one group), and the candidate's index as the sort's value.
+__global__ __launch_bounds__(256) void surf_metric_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const int4* __restrict__ cand,
+                                                          unsigned int n, unsigned long long* __restrict__ keys,
+                                                          unsigned int* __restrict__ vals) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int4 kp = cand[i];
+    const SurfOct& oc = plan.oct[kp.x];
+    const int m = kp.y;
+    float tr;
+    const float metric = surf_response(I, plan.h, plan.w, kp.z * oc.step, kp.w * oc.step, oc.size[m], oc.inv[m], oc.inv_xy[m], &tr);
+    keys[i] = strength_key_f32(metric);
+    vals[i] = i;
+}
+
+// Ordered compaction of the flagged candidates, as surf_emit_kernel's: canonical order is kept.
+__global__ __launch_bounds__(256) void surf_select_compact_kernel(const unsigned long long* __restrict__ words,
+                                                                  const unsigned int* __restrict__ prefix, unsigned int n_words,
+                                                                  const int4* __restrict__ cand, unsigned int n, int4* __restrict__ kps,
+                                                                  unsigned int kcap) {
+    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_words) return;
+    unsigned long long bits = words[q];
+    unsigned int pos = prefix[q];
+    while (bits) {
+        const int k = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        if (pos < kcap && q * 64 + k < n) kps[pos] = cand[q * 64 + k];
+        ++pos;
+    }
+}
+
+// the checks of aps_surf_extract, which come before any device work
+void check_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_surf_params* params, int desc_layout,
+                int64_t cap, const int64_t* count) {
+    APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
+    APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
+    APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
+    APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
+    APS_REQUIRE(params->n_octaves >= 1 && params->n_octaves <= kMaxOct, APS_E_ARG, "NumOctaves must be in 1..%d", kMaxOct);
+    APS_REQUIRE(params->n_scale_levels >= 3 && params->n_scale_levels <= kMaxLev, APS_E_ARG, "NumScaleLevels must be in 3..%d", kMaxLev);
+    APS_REQUIRE(params->metric_threshold >= 0, APS_E_ARG, "MetricThreshold must be >= 0");
+    APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
+    // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
+    APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
+                "SURF: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
+}
+
+// What both entries hold once the candidates are known: the integral image, the candidate bitmap (bit order = canonical order) and
+// the exclusive scan of its popcounts; prefix[n_words] is the number of candidates.
+struct SurfFront {
+    SurfPlan plan;
+    long long n_words = 0;
+    In<uint8_t> dimg;
+    Ws<uint32_t> T, I;
+    Ws<unsigned long long> bitmap;
+    Ws<unsigned int> prefix;
+    const unsigned int* d_total() const { return prefix.get() + n_words; }
+};
+
+// plan, integral image, detection and scan on the calling thread's stream; no read-back.  false: smaller than the first octave's support.
+bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, const aps_surf_params* params, SurfFront& F) {
+    const int nlv = params->n_scale_levels;
+    // plan: octaves whose largest filter fits
+    SurfPlan& plan = F.plan;
+    std::memset(&plan, 0, sizeof plan);
+    plan.nlv = nlv;
+    plan.h = H;
+    plan.w = W;
+    long long n_words = 0;
+    for (int o = 1; o <= params->n_octaves; ++o) {
+        const long long top = 3ll * ((1ll << o) * nlv + 1);
+        if (top > std::min(H, W)) break;
+        SurfOct& oc = plan.oct[plan.n_oct++];
+        oc.step = 1 << (o - 1);
+        oc.gh = (H - 1) / oc.step + 1;
+        oc.gw = (W - 1) / oc.step + 1;
+        oc.wpr = (int)cdiv(oc.gw, 64);
+        for (int l = 0; l < nlv; ++l) {
+            oc.size[l] = 3 * ((1 << o) * (l + 1) + 1);
+            const double lobe = (double)(oc.size[l] / 3);
+            oc.inv[l] = (float)(1.0 / ((2.0 * lobe - 1.0) * lobe));
+            oc.inv_xy[l] = (float)(1.0 / (lobe * lobe));
+        }
+        oc.word0 = n_words;
+        n_words += (long long)(nlv - 2) * oc.gh * oc.wpr;
+    }
+    F.n_words = n_words;
+    if (plan.n_oct == 0) return false;
+    F.dimg.bind(img, (size_t)H * W * channels);
+    F.T.alloc((size_t)H * W);
+    F.I.alloc((size_t)(H + 1) * (W + 1));
+    {
+        Prof prof("surf_integral");
+        integral_image(F.dimg, H, W, channels, img_layout, F.T, F.I, nullptr);
+    }
+    F.bitmap.alloc((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    F.prefix.alloc((size_t)n_words + 1);
+    APS_HIP(hipMemsetAsync(F.bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
+    {
+        Prof prof("surf_detect");
+        for (int o = 0; o < plan.n_oct; ++o) {
+            const SurfOct& oc = plan.oct[o];
+            surf_detect_kernel<<<dim3(oc.wpr, cdiv(oc.gh, kTH)), 256, 0, stream()>>>(F.I, H, W, oc, nlv, (float)params->metric_threshold, F.bitmap);
+        }
+        check_launch("surf_detect_kernel");
+    }
+    auto counts = rocprim::make_transform_iterator(F.bitmap.get(), PopcOp());
+    size_t tbytes = 0;
+    APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, F.prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+    Ws<char> tmp(tbytes);
+    APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, F.prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+    return true;
+}
+
+// aps_surf_extract_strongest behind its argument checks.  Two read-backs: the candidate count, which sizes the grids and the sort
+// below, then the final count.
+void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int img_layout, const aps_surf_params* params, long long N,
+                          float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    ctx();
+    *count = 0;
+    SurfFront F;
+    if (!surf_front(img, H, W, channels, img_layout, params, F)) return;
+    unsigned int M = 0;  // the first read-back: the candidates
+    APS_HIP(hipMemcpyAsync(&M, F.d_total(), sizeof M, hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int K = (unsigned int)std::min<long long>(M, N);
+    *count = K;
+    if (params->max_features > 0 && M > (unsigned int)params->max_features) {
+        *count = M;
+        fail(APS_E_CAP, "SURF found %u features, more than params.max_features = %d", M, params->max_features);
+    }
+    if ((int64_t)K > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, K);
+    if (K == 0) return;
+    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
+    if (desc_layout == APS_ROWMAJOR)
+        APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
+    else
+        APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
+    APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
+    Ws<int4> cand(M), sel;
+    surf_emit_kernel<<<cdiv((size_t)F.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, F.n_words, F.plan, cand, M);
+    check_launch("surf_emit_kernel");
+    // the kept keypoints, in canonical order
+    Ws<unsigned long long> keys, words;
+    Ws<unsigned int> vals, prefix;
+    const int4* kps = cand;
+    const unsigned int* d_total = F.d_total();
+    if (K < M) {
+        Prof prof("surf_select");
+        keys.alloc(M);
+        vals.alloc(M);
+        surf_metric_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, keys, vals);
+        check_launch("surf_metric_kernel");
+        unsigned int n_words = 0;
+        select_by_key(keys, vals, M, single_group_cut(M, K), words, prefix, n_words, 32u);
+        sel.alloc(K);
+        surf_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, M, sel, K);
+        check_launch("surf_select_compact_kernel");
+        kps = sel;
+        d_total = prefix.get() + n_words;
+    }
+    const size_t dwidth = desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64;
+    Out<float> odesc(desc, desc_layout == APS_ROWMAJOR ? (size_t)(K - 1) * ldd + dwidth : (size_t)63 * ldd + K);
+    Out<double> oloc(loc, (size_t)ldl + K);
+    Out<float> oaux(aux, (size_t)K * 4);
+    Ws<SurfTables> d_tb(1);
+    APS_HIP(hipMemcpyAsync(d_tb, &host_tables(), sizeof(SurfTables), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("surf_keypoint");
+        surf_keypoint_kernel<<<cdiv(K, 4), 256, 0, stream()>>>(F.I, F.plan, d_tb, kps, d_total, K, params->upright ? 1 : 0, odesc, desc_layout,
+                                                              (long long)ldd, oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
+    }
+    check_launch("surf_keypoint_kernel");
+    unsigned int n = 0;  // the second read-back: the count the device kept is the count the host worked out
+    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
+    if (desc_layout == APS_ROWMAJOR)
+        odesc.commit_2d(dwidth, K, (size_t)ldd);
+    else
+        odesc.commit_2d(K, 64, (size_t)ldd);
+    oloc.commit_2d(K, 2, (size_t)ldl);
+    oaux.commit((size_t)K * 4);
+}
+
 }  // namespace
 }  // namespace aps
 
@@ -338,68 +534,17 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_surf_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
-        APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
-        APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
-        APS_REQUIRE(desc_layout == APS_ROWMAJOR || desc_layout == APS_COLMAJOR, APS_E_TYPE, "unknown descriptor layout");
-        APS_REQUIRE(params->n_octaves >= 1 && params->n_octaves <= kMaxOct, APS_E_ARG, "NumOctaves must be in 1..%d", kMaxOct);
-        APS_REQUIRE(params->n_scale_levels >= 3 && params->n_scale_levels <= kMaxLev, APS_E_ARG, "NumScaleLevels must be in 3..%d", kMaxLev);
-        APS_REQUIRE(params->metric_threshold >= 0, APS_E_ARG, "MetricThreshold must be >= 0");
-        APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
-        // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
-        APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
-                    "SURF: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
+        check_args(img, height, width, channels, img_layout, params, desc_layout, cap, count);
         ctx();
         *count = 0;
-        const int H = height, W = width, nlv = params->n_scale_levels;
-        // plan: octaves whose largest filter fits
-        SurfPlan plan;
-        std::memset(&plan, 0, sizeof plan);
-        plan.nlv = nlv;
-        plan.h = H;
-        plan.w = W;
-        long long n_words = 0;
-        for (int o = 1; o <= params->n_octaves; ++o) {
-            const long long top = 3ll * ((1ll << o) * nlv + 1);
-            if (top > std::min(H, W)) break;
-            SurfOct& oc = plan.oct[plan.n_oct++];
-            oc.step = 1 << (o - 1);
-            oc.gh = (H - 1) / oc.step + 1;
-            oc.gw = (W - 1) / oc.step + 1;
-            oc.wpr = (int)cdiv(oc.gw, 64);
-            for (int l = 0; l < nlv; ++l) {
-                oc.size[l] = 3 * ((1 << o) * (l + 1) + 1);
-                const double lobe = (double)(oc.size[l] / 3);
-                oc.inv[l] = (float)(1.0 / ((2.0 * lobe - 1.0) * lobe));
-                oc.inv_xy[l] = (float)(1.0 / (lobe * lobe));
-            }
-            oc.word0 = n_words;
-            n_words += (long long)(nlv - 2) * oc.gh * oc.wpr;
-        }
-        if (plan.n_oct == 0) return;  // smaller than the first octave's support: no features, no error
-        In<uint8_t> dimg(img, (size_t)H * W * channels);
-        Ws<uint32_t> T((size_t)H * W), I((size_t)(H + 1) * (W + 1));
-        {
-            Prof prof("surf_integral");
-            integral_image(dimg, H, W, channels, img_layout, T, I, nullptr);
-        }
-        Ws<unsigned long long> bitmap((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
-        Ws<unsigned int> prefix((size_t)n_words + 1);
-        APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
-        {
-            Prof prof("surf_detect");
-            for (int o = 0; o < plan.n_oct; ++o) {
-                const SurfOct& oc = plan.oct[o];
-                surf_detect_kernel<<<dim3(oc.wpr, cdiv(oc.gh, kTH)), 256, 0, stream()>>>(I, H, W, oc, nlv, (float)params->metric_threshold, bitmap);
-            }
-            check_launch("surf_detect_kernel");
-        }
-        auto counts = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
-        size_t tbytes = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-        Ws<char> tmp(tbytes);
-        APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+        const int H = height, W = width;
+        SurfFront F;
+        if (!surf_front(img, H, W, channels, img_layout, params, F)) return;  // smaller than the first octave's support: no features, no error
+        const SurfPlan& plan = F.plan;
+        const long long n_words = F.n_words;
+        const Ws<uint32_t>& I = F.I;
+        const Ws<unsigned long long>& bitmap = F.bitmap;
+        const Ws<unsigned int>& prefix = F.prefix;
         const unsigned int* d_total = prefix.get() + n_words;
         const bool write = cap > 0 && desc && loc;
         const unsigned int kcap = write ? (unsigned int)cap : 0u;
@@ -443,6 +588,18 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
             odesc.commit_2d(n, 64, (size_t)ldd);
         oloc.commit_2d(n, 2, (size_t)ldl);
         oaux.commit((size_t)n * 4);
+    });
+}
+
+int aps_surf_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_surf_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+        check_args(img, height, width, channels, img_layout, &params->surf, desc_layout, cap, count);
+        surf_strongest_chain(img, height, width, channels, img_layout, &params->surf, params->n_strongest, desc, desc_layout, ldd, loc, ldl,
+                             aux, cap, count);
     });
 }
 

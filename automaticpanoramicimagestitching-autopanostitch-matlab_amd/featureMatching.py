@@ -614,6 +614,13 @@ def _sift_params(input):
     return p
 
 
+def _sift_strongest_params(input):
+    p = _capi.aps_sift_strongest_params()
+    p.sift = _sift_params(input)
+    p.n_strongest = int(input["NumStrongest"])
+    return p
+
+
 def _fence_fresh_blocks():
     """torch's caching allocator recycles a freed block for the next torch.empty at once, which is safe for consumers on
     torch's own stream only: kernels that were queued there before the block was freed (by ANY thread) may still be
@@ -635,7 +642,12 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
     image: H x W x 3 or H x W uint8, numpy (host) or torch (host/device), row-major.
     device_out=True keeps the descriptors on the GPU (torch float32 [n,128]) for the resident pipeline;
     points_device=True (with device_out) leaves the keypoints there as well (torch float64 [n,2]) instead of bringing
-    them to the host - the resident pipeline only ever hands them back to the device (aps_gather_match_points)."""
+    them to the host - the resident pipeline only ever hands them back to the device (aps_gather_match_points).
+
+    input.NumStrongest (absent by default; cv::SIFT's nfeatures, selectStrongest) keeps at most that many rows through
+    aps_sift_extract_strongest: those that come first by (aux[:, 2], the keypoint's contrast, descending; row index ascending), with
+    no quota per octave.  The kept rows are rows of the result without the key, bit for bit and in the same order, and the capacity
+    buffer of a resident result holds NumStrongest rows, not H*W/64.  A value below 1 is an ApsError (APS_E_ARG)."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -646,8 +658,11 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
         c = 1 if img.ndim == 2 else img.shape[2]
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
-    prm = _sift_params(input)
+    prm, entry = _sift_params(input), lib.aps_sift_extract
     cap = max(4096, (h * w) // 64)
+    if "NumStrongest" in input:
+        prm, entry = _sift_strongest_params(input), lib.aps_sift_extract_strongest
+        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
     cnt = C.c_int64(0)
     while True:
         if device_out:
@@ -663,8 +678,8 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
         else:
             loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
         aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = lib.aps_sift_extract(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                                  _capi.APS_ROWMAJOR, DIM, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
+        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
+                   _capi.APS_ROWMAJOR, DIM, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
         if rc == _capi.APS_E_CAP and cnt.value > cap:
             cap = int(cnt.value)
             continue
@@ -708,13 +723,25 @@ def _surf_params(input):
     return p
 
 
+def _surf_strongest_params(input):
+    p = _capi.aps_surf_strongest_params()
+    p.surf = _surf_params(input)
+    p.n_strongest = int(input["NumStrongest"])
+    return p
+
+
 def surf_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False, padded=False):
     """aps_surf_extract with automatic capacity: returns (features, validPts[, aux]); the arguments are sift_extract's.
 
     Host results are n x 64.  Resident results (device_out=True) are the [:, :64] view of an n x 128 buffer whose columns
     64..127 the library zeroed: the 128-wide matchers take the padded rows behind the view without a copy (_as_desc).
     padded=True (with device_out) returns that n x 128 buffer itself: the form the resident pipeline hands to the matchers and
-    the all-gather.  aux: n x 4 [scale, angle_deg, metric, sign_of_laplacian]."""
+    the all-gather.  aux: n x 4 [scale, angle_deg, metric, sign_of_laplacian].
+
+    input.NumStrongest (absent by default; selectStrongest) keeps at most that many rows through aps_surf_extract_strongest: those
+    that come first by (metric descending, row index ascending), with no quota per octave.  The kept rows are rows of the result
+    without the key, in the same order; the capacity buffer of a resident result holds NumStrongest rows.  A value below 1 is an
+    ApsError (APS_E_ARG)."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -725,8 +752,11 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
         c = 1 if img.ndim == 2 else img.shape[2]
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
-    prm = _surf_params(input)
+    prm, entry, max_features = _surf_params(input), lib.aps_surf_extract, int(input.get("maxFeatures", 0))
     cap = max(4096, (h * w) // 64)
+    if "NumStrongest" in input:
+        prm, entry = _surf_strongest_params(input), lib.aps_surf_extract_strongest
+        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
     cnt = C.c_int64(0)
     ld = DIM if device_out else SURF_DIM
     while True:
@@ -743,9 +773,9 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
         else:
             loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
         aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = lib.aps_surf_extract(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                                  _capi.APS_ROWMAJOR, ld, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < prm.max_features < cnt.value):
+        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
+                   _capi.APS_ROWMAJOR, ld, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
+        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < max_features < cnt.value):
             cap = int(cnt.value)
             continue
         check(rc)

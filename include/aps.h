@@ -720,6 +720,23 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_sift_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
+/* SIFT strongest-N (DESIGN.md "Strongest-N for SIFT and SURF"; cv::SIFT's nfeatures, selectStrongest): of the rows aps_sift_extract
+ * returns for the same image and parameters (the candidates, in canonical order), keep the first min(n_strongest, candidates) by
+ * (aux's response = the keypoint's contrast descending, compared as f32; canonical index ascending).  No quota per octave.  The unit
+ * is the output row: the orientations of one keypoint tie and the lower orientation bin stays. */
+typedef struct aps_sift_strongest_params {
+    aps_sift_params sift;      /* sift.max_features keeps its meaning: the candidate capacity of the detection */
+    int n_strongest;           /* N >= 1; anything else is APS_E_ARG before any device work */
+} aps_sift_strongest_params;
+
+/* Arguments, count-only mode, padding, layouts and pointers behave as aps_sift_extract's.  *count = rows kept;
+ * cap >= min(candidates, n_strongest) always suffices.  With cap below the rows kept nothing is written (APS_E_CAP, *count = rows
+ * kept).  The kept rows come in canonical order, and descriptor, location and aux of a kept row are bit for bit those of the same row
+ * of aps_sift_extract; only kept rows are described.  n_strongest >= candidates gives aps_sift_extract's result. */
+int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_sift_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
 /* ============================================================================================
  * (4b) SURF — PP/featureMatching/getFeaturePoints.m:54-55,71-74
  * ============================================================================================ */
@@ -747,6 +764,23 @@ typedef struct aps_surf_params {
 int aps_surf_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
                      const aps_surf_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* SURF strongest-N (DESIGN.md "Strongest-N for SIFT and SURF"; selectStrongest): of the rows aps_surf_extract returns for the same
+ * image and parameters (the candidates, in canonical order), keep the first min(n_strongest, candidates) by (aux's metric descending,
+ * compared as f32; canonical index ascending).  No quota per octave. */
+typedef struct aps_surf_strongest_params {
+    aps_surf_params surf;      /* surf.max_features keeps its meaning: the call fails when the detection finds more candidates */
+    int n_strongest;           /* N >= 1; anything else is APS_E_ARG before any device work */
+} aps_surf_strongest_params;
+
+/* Arguments, count-only mode, padding, layouts, pointers and the zeroing of columns 64..127 behave as aps_surf_extract's.
+ * *count = rows kept; cap >= min(candidates, n_strongest) always suffices.  With cap below the rows kept nothing is written
+ * (APS_E_CAP, *count = rows kept).  The kept rows come in canonical order, and descriptor, location and aux of a kept row are those of
+ * the same row of aps_surf_extract; only kept rows are described.  n_strongest >= candidates gives aps_surf_extract's result.
+ * The call reads back the candidate count, then the final count. */
+int aps_surf_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
+                               const aps_surf_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
+                               double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
 /* ============================================================================================
  * (4c) FAST + FREAK — PP/featureMatching/getFeaturePoints.m:51-52,71-74

@@ -36,6 +36,17 @@ static void need(bool ok, const char* id, const char* msg) {
     if (!ok) mexErrMsgIdAndTxt(id, "%s", msg);
 }
 
+// aps_sift_extract_strongest with the layouts of cmd_sift's aps_sift_extract call: planar column-major image, column-major descriptors
+// with leading dimension cap (tests/test_strongest_gpu.py, test_matlab_layouts_give_the_same_rows, runs this call shape on the device).
+static int sift_strongest(const aps_sift_params& p, int n_strongest, const uint8_t* img, int h, int w, int c, float* desc, double* loc,
+                          int64_t cap, int64_t* count) {
+    const int img_layout = APS_IMG_U8_MATLAB, desc_layout = APS_COLMAJOR;
+    aps_sift_strongest_params sp;
+    sp.sift = p;
+    sp.n_strongest = n_strongest;
+    return aps_sift_extract_strongest(img, h, w, c, img_layout, &sp, desc, desc_layout, cap, loc, cap, nullptr, cap, count);
+}
+
 // [features, validPts] = aps_mex('sift_extract', img_uint8, input)
 static void cmd_sift(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     need(nrhs == 3 && mxIsUint8(prhs[1]), "aps:type", "usage: aps_mex('sift_extract', uint8 image, input struct)");
@@ -48,11 +59,17 @@ static void cmd_sift(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     p.edge_threshold = field(prhs[2], "EdgeThreshold", 6);
     p.max_features = 0;
     int64_t cap = (int64_t)h * w / 64 + 4096, count = 0;
+    // input.NumStrongest (optional field): the N rows of largest contrast; a value below 1 is the library's to refuse
+    const mxArray* ns = mxIsStruct(prhs[2]) ? mxGetField(prhs[2], 0, "NumStrongest") : nullptr;
+    const int n_strongest = ns ? (int)mxGetScalar(ns) : 0;
+    if (ns && n_strongest >= 1 && n_strongest < cap) cap = n_strongest;  // min(candidates, NumStrongest) rows always suffice
     for (;;) {
         mxArray* desc = mxCreateNumericMatrix(cap, 128, mxSINGLE_CLASS, mxREAL);
         mxArray* loc = mxCreateNumericMatrix(cap, 2, mxDOUBLE_CLASS, mxREAL);
-        const int rc = aps_sift_extract((const uint8_t*)mxGetData(prhs[1]), h, w, c, APS_IMG_U8_MATLAB, &p,
-                                        (float*)mxGetData(desc), APS_COLMAJOR, cap, mxGetPr(loc), cap, nullptr, cap, &count);
+        const int rc = ns ? sift_strongest(p, n_strongest, (const uint8_t*)mxGetData(prhs[1]), h, w, c, (float*)mxGetData(desc), mxGetPr(loc),
+                                           cap, &count)
+                          : aps_sift_extract((const uint8_t*)mxGetData(prhs[1]), h, w, c, APS_IMG_U8_MATLAB, &p,
+                                             (float*)mxGetData(desc), APS_COLMAJOR, cap, mxGetPr(loc), cap, nullptr, cap, &count);
         if (rc == APS_E_CAP && count > cap) {
             mxDestroyArray(desc);
             mxDestroyArray(loc);
