@@ -103,6 +103,18 @@ class aps_fast_strongest_params(C.Structure):
     _fields_ = [("pyramid", aps_fast_pyramid_params), ("n_strongest", C.c_int)]
 
 
+class aps_sift_uniform_params(C.Structure):
+    _fields_ = [("strongest", aps_sift_strongest_params), ("grid_rows", C.c_int), ("grid_cols", C.c_int)]
+
+
+class aps_surf_uniform_params(C.Structure):
+    _fields_ = [("strongest", aps_surf_strongest_params), ("grid_rows", C.c_int), ("grid_cols", C.c_int)]
+
+
+class aps_fast_uniform_params(C.Structure):
+    _fields_ = [("strongest", aps_fast_strongest_params), ("grid_rows", C.c_int), ("grid_cols", C.c_int)]
+
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/aps.h one to one
@@ -208,6 +220,14 @@ _SIGNATURES = {
                                    _vp, _i64, C.POINTER(_i64)],
     "aps_surf_extract_strongest": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_strongest_params), _vp, _i, _i64, _vp, _i64,
                                    _vp, _i64, C.POINTER(_i64)],
+    "aps_sift_extract_uniform": [_vp, _i, _i, _i, _i, C.POINTER(aps_sift_uniform_params), _vp, _i, _i64, _vp, _i64,
+                                 _vp, _i64, C.POINTER(_i64)],
+    "aps_surf_extract_uniform": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_uniform_params), _vp, _i, _i64, _vp, _i64,
+                                 _vp, _i64, C.POINTER(_i64)],
+    "aps_fast_extract_uniform": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_uniform_params), _vp, _i, _i64, _vp, _i64,
+                                 _vp, _i64, C.POINTER(_i64)],
+    "aps_uniform_quota": [_vp, _i, _i64, _vp],
+    "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
              "aps_planar_composite_compact_bytes": C.c_int64}

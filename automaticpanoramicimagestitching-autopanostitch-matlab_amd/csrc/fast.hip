@@ -31,6 +31,8 @@
 //                         strongest_flag_kernel (rank within the level < k_l, written back by index), strongest_word_kernel (ballot),
 //                         scan of the popcounts; then strongest_compact_kernel (canonical order again)
 //   freak_keypoint_kernel on the kept keypoints only; strongest_aux_kernel writes f32(R) into aux[3]
+// aps_fast_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with fast_segment_kernel and select_uniform in the place of
+// select_by_key: the k_l rows of a level are spread over the cells of a grid on the level's plane.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -491,6 +493,23 @@ __global__ void strongest_counts_kernel(const unsigned int* __restrict__ prefix,
         out[l] = prefix[n_words];
 }
 
+// Uniform-N (DESIGN.md "Uniform-N selection"): the segment of every candidate = level * cells + the cell of its level pixel in the
+// rows x cols grid over the level's plane.
+__global__ __launch_bounds__(256) void fast_segment_kernel(const Keypoint* __restrict__ kps, const FastPlan P, unsigned int n, int rows, int cols,
+                                                           unsigned int* __restrict__ segs) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Keypoint kp = kps[i];
+    int h = 1, w = 1;
+#pragma unroll
+    for (int l = 0; l < kMaxLevels; ++l)  // (constant indices: the plan stays in scalar registers)
+        if (kp.level == l) {
+            h = P.lv[l].h;
+            w = P.lv[l].w;
+        }
+    segs[i] = (unsigned int)(kp.level * rows * cols + uniform_cell(kp.y, kp.x, h, w, rows, cols));
+}
+
 static_assert(kMaxLevels == kSelectGroups, "a level is a group of the selection (select_dev.h: StrongestCut, strongest_flag_kernel)");
 
 // Ordered compaction of the flagged candidates, as fast_emit_kernel's: canonical order is kept.
@@ -759,9 +778,10 @@ void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
     check_launch("fast_harris_kernel");
 }
 
-// aps_fast_extract_strongest behind its argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.
+// aps_fast_extract_strongest and, with grid_rows > 0, aps_fast_extract_uniform (each level's k_l spread over the cells of its plane)
+// behind their argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.
 void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, long long N,
-                     uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+                     int grid_rows, int grid_cols, uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     ctx();
     *count = 0;
     const FastPlan& P = hp.dev;
@@ -809,7 +829,16 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     if (K < M) {
         Prof prof("fast_select");
         unsigned int n_words = 0;
-        select_by_key(Cd.keys, Cd.vals, M, cut, words, prefix, n_words);
+        if (grid_rows > 0) {  // uniform-N: a stable sort by (level, -R), then one by segment; the budgets are the k_l
+            Ws<unsigned int> segs(M);
+            fast_segment_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(Cd.kps, P, M, grid_rows, grid_cols, segs);
+            check_launch("fast_segment_kernel");
+            UniformBudget budget;
+            for (int l = 0; l < kMaxLevels; ++l) budget.q[l] = cut.keep[l];
+            select_uniform(Cd.keys, segs, Cd.vals, M, (unsigned int)P.n, (unsigned int)(grid_rows * grid_cols), budget, words, prefix, n_words);
+        } else {
+            select_by_key(Cd.keys, Cd.vals, M, cut, words, prefix, n_words);
+        }
         sel_kps.alloc(K);
         sel_resp.alloc(K);
         strongest_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, Cd.kps, Cd.resp, sel_kps, sel_resp, K);
@@ -910,7 +939,21 @@ int aps_fast_extract_strongest(const uint8_t* img, int height, int width, int ch
         check_args(img, height, width, channels, img_layout, pyr.fast, desc_layout, cap);
         check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
         strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
-                        params->n_strongest, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+                        params->n_strongest, 0, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_fast_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_fast_uniform_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        const aps_fast_pyramid_params& pyr = params->strongest.pyramid;
+        check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
+        check_args(img, height, width, channels, img_layout, pyr.fast, desc_layout, cap);
+        check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+        strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
+                        params->strongest.n_strongest, params->grid_rows, params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
     });
 }
 

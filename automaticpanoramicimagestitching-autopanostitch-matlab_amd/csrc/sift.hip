@@ -17,6 +17,9 @@
 //   sift_contr_key_kernel, select_by_key (select_dev.h), sift_select_compact_kernel
 //                                  : aps_sift_extract_strongest only - the N rows of largest contrast, picked from the list of
 //                                    oriented keypoints before descr_kernel runs (DESIGN.md "Strongest-N for SIFT and SURF").
+//   sift_uniform_key_kernel, select_uniform (select_dev.h), sift_select_compact_kernel
+//                                  : aps_sift_extract_uniform only - N rows spread over the cells of a grid, the largest
+//                                    contrast first within a cell (DESIGN.md "Uniform-N selection").
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -971,6 +974,11 @@ __global__ void expand_oriented_kernel(const unsigned int* __restrict__ ori_coun
     }
 }
 
+// ---- the 1-based f64 location of an output row, stated once for descr_kernel and the uniform selection's cells ------------
+__device__ __forceinline__ float octave_step(int o) { return ldexpf(1.0f, o) * 0.5f; }  // (octave 0 is the doubled image)
+__device__ __forceinline__ float sift_pt(int base, float offset) { return (float)base + offset; }
+__device__ __forceinline__ double sift_loc(float pt, float step) { return (double)(pt * step) + 1.0; }
+
 // ---- strongest-N (DESIGN.md "Strongest-N for SIFT and SURF") ---------------------------------------------
 // The contrast of every output row's keypoint (aux[:, 2] of the row) as the selection's key (select_dev.h: one group), and the
 // row's index as the sort's value.  The orientations of one keypoint tie; the stable sort keeps the lower bin first.
@@ -980,6 +988,21 @@ __global__ __launch_bounds__(256) void sift_contr_key_kernel(const KpRec* __rest
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     keys[i] = strength_key_f32(kps[oks[i].kp].contr);
+    vals[i] = i;
+}
+
+// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the row's segment = its cell in the rows x cols grid over the H x W
+// image, from the pixel clamp(floor(loc) - 1, 0, size - 1) of the row's 1-based f64 location.
+__global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __restrict__ kps, const OrientedKp* __restrict__ oks,
+                                                               unsigned int n, int H, int W, int rows, int cols,
+                                                               unsigned long long* __restrict__ keys, unsigned int* __restrict__ vals) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const KpRec kp = kps[oks[i].kp];
+    const float step = octave_step((int)(kp.key >> 40));
+    const double x = sift_loc(sift_pt((int)(kp.key & 0xffff), kp.xc), step), y = sift_loc(sift_pt((int)((kp.key >> 16) & 0xffff), kp.xr), step);
+    const int px = min(max((int)floor(x) - 1, 0), W - 1), py = min(max((int)floor(y) - 1, 0), H - 1);
+    keys[i] = (unsigned long long)uniform_cell(py, px, H, W, rows, cols) << kSegmentShift | strength_key_f32(kp.contr);
     vals[i] = i;
 }
 
@@ -1040,7 +1063,7 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
     const float scl = kp_scale(pt->sigma, layer, xi, pt->nl);
     float ori = 360.0f - kangle;
     if (fabsf(ori - 360.0f) < kFltEps) ori = 0.0f;
-    const float ptx = (float)c0 + xc, pty = (float)r0 + xr;
+    const float ptx = sift_pt(c0, xc), pty = sift_pt(r0, xr);
     const int px = (int)rintf(ptx), py = (int)rintf(pty);
     float sin_t, cos_t;
     sincos_deg(ori, sin_t, cos_t);
@@ -1280,9 +1303,9 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
             desc[(size_t)e * ldd + oi] = outv;
     }
     if (lane == 0) {
-        const float s = ldexpf(1.0f, o) * 0.5f;
-        loc[oi] = (double)(ptx * s) + 1.0;
-        loc[ldl + oi] = (double)(pty * s) + 1.0;
+        const float s = octave_step(o);
+        loc[oi] = sift_loc(ptx, s);
+        loc[ldl + oi] = sift_loc(pty, s);
         if (aux) {
             aux[(size_t)oi * 4 + 0] = scl * s * 2.0f;
             aux[(size_t)oi * 4 + 1] = kangle;
@@ -1448,10 +1471,12 @@ static unsigned long long diff(const void* a, const void* b, size_t n_words, uns
 using namespace aps;
 
 // aps_sift_extract (n_strongest = 0: every row) and aps_sift_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF": the
-// n_strongest rows of largest contrast) behind one body.  The argument checks come before any device work.
+// n_strongest rows of largest contrast) behind one body; with grid_rows > 0 the n_strongest rows are spread over the cells of a
+// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").  The argument checks come before any
+// device work.
 static void sift_chain(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
-                       long long n_strongest, float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap,
-                       int64_t* count) {
+                       long long n_strongest, int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc,
+                       int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
     APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
     APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
@@ -1734,10 +1759,18 @@ static void sift_chain(const uint8_t* img, int height, int width, int channels, 
         Prof prof("sift_select");
         Ws<unsigned long long> skeys(n_all), words;
         Ws<unsigned int> svals(n_all), sprefix;
-        sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
-        check_launch("sift_contr_key_kernel");
         unsigned int n_words = 0;
-        select_by_key(skeys, svals, n_all, single_group_cut(n_all, n_out), words, sprefix, n_words, 32u);
+        if (grid_rows > 0) {  // uniform-N: the rows that come first in their cell, the cells' shares by water-filling n_out
+            sift_uniform_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, H, W, grid_rows, grid_cols, skeys, svals);
+            check_launch("sift_uniform_key_kernel");
+            UniformBudget budget = {};
+            budget.q[0] = n_out;
+            select_uniform(skeys, nullptr, svals, n_all, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, sprefix, n_words);
+        } else {
+            sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
+            check_launch("sift_contr_key_kernel");
+            select_by_key(skeys, svals, n_all, single_group_cut(n_all, n_out), words, sprefix, n_words, 32u);
+        }
         oks_sel.alloc(n_out);
         sift_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, sprefix, n_words, oks_all, n_all, oks_sel, n_out);
         check_launch("sift_select_compact_kernel");
@@ -1784,7 +1817,7 @@ extern "C" {
 int aps_sift_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
                      const aps_sift_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
-    return guarded([&] { sift_chain(img, height, width, channels, img_layout, params, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count); });
+    return guarded([&] { sift_chain(img, height, width, channels, img_layout, params, 0, 0, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count); });
 }
 
 int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
@@ -1793,8 +1826,19 @@ int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int ch
     return guarded([&] {
         APS_REQUIRE(params, APS_E_ARG, "NULL argument");
         APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
-        sift_chain(img, height, width, channels, img_layout, &params->sift, params->n_strongest, desc, desc_layout, ldd, loc, ldl, aux, cap,
-                   count);
+        sift_chain(img, height, width, channels, img_layout, &params->sift, params->n_strongest, 0, 0, desc, desc_layout, ldd, loc, ldl, aux,
+                   cap, count);
+    });
+}
+
+int aps_sift_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_sift_uniform_params* params, float* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
+        sift_chain(img, height, width, channels, img_layout, &params->strongest.sift, params->strongest.n_strongest, params->grid_rows,
+                   params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
     });
 }
 

@@ -20,6 +20,8 @@
 //   surf_metric_kernel    the centre response of every candidate = its metric, as the sort key
 //   select_by_key         (select_dev.h) stable radix sort, flags, ballot words, scan; surf_select_compact_kernel (canonical order again)
 //   surf_keypoint_kernel  on the kept keypoints only
+// aps_surf_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with surf_uniform_key_kernel and select_uniform in the place
+// of surf_metric_kernel and select_by_key.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -337,17 +339,32 @@ __global__ __launch_bounds__(256) void surf_keypoint_kernel(const uint32_t* __re
 // ---- strongest-N (DESIGN.md "Strongest-N for SIFT and SURF") ----------------------------------------------------------------
 // The metric of every candidate: the centre response, s_a[wave][13] of surf_keypoint_kernel - the same device function on the same
 // operands, so the same bits - as the selection's key (select_dev.h: one group), and the candidate's index as the sort's value.
+__device__ __forceinline__ float surf_metric(const uint32_t* __restrict__ I, const SurfPlan& plan, const int4 kp) {
+    const SurfOct& oc = plan.oct[kp.x];
+    const int m = kp.y;
+    float tr;
+    return surf_response(I, plan.h, plan.w, kp.z * oc.step, kp.w * oc.step, oc.size[m], oc.inv[m], oc.inv_xy[m], &tr);
+}
 __global__ __launch_bounds__(256) void surf_metric_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const int4* __restrict__ cand,
                                                           unsigned int n, unsigned long long* __restrict__ keys,
                                                           unsigned int* __restrict__ vals) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    keys[i] = strength_key_f32(surf_metric(I, plan, cand[i]));
+    vals[i] = i;
+}
+
+// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the candidate's segment = the cell of its detection sample
+// (i * step, j * step), the unrefined one that surf_emit_kernel lists, in the rows x cols grid over the image.
+__global__ __launch_bounds__(256) void surf_uniform_key_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const int4* __restrict__ cand,
+                                                               unsigned int n, int rows, int cols, unsigned long long* __restrict__ keys,
+                                                               unsigned int* __restrict__ vals) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
     const int4 kp = cand[i];
-    const SurfOct& oc = plan.oct[kp.x];
-    const int m = kp.y;
-    float tr;
-    const float metric = surf_response(I, plan.h, plan.w, kp.z * oc.step, kp.w * oc.step, oc.size[m], oc.inv[m], oc.inv_xy[m], &tr);
-    keys[i] = strength_key_f32(metric);
+    const int step = plan.oct[kp.x].step;
+    keys[i] = (unsigned long long)uniform_cell(kp.z * step, kp.w * step, plan.h, plan.w, rows, cols) << kSegmentShift |
+              strength_key_f32(surf_metric(I, plan, kp));
     vals[i] = i;
 }
 
@@ -452,10 +469,10 @@ bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, 
     return true;
 }
 
-// aps_surf_extract_strongest behind its argument checks.  Two read-backs: the candidate count, which sizes the grids and the sort
-// below, then the final count.
+// aps_surf_extract_strongest and, with grid_rows > 0, aps_surf_extract_uniform behind their argument checks.  Two read-backs: the
+// candidate count, which sizes the grids and the sort below, then the final count.
 void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int img_layout, const aps_surf_params* params, long long N,
-                          float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+                          int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     ctx();
     *count = 0;
     SurfFront F;
@@ -489,10 +506,18 @@ void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int im
         Prof prof("surf_select");
         keys.alloc(M);
         vals.alloc(M);
-        surf_metric_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, keys, vals);
-        check_launch("surf_metric_kernel");
         unsigned int n_words = 0;
-        select_by_key(keys, vals, M, single_group_cut(M, K), words, prefix, n_words, 32u);
+        if (grid_rows > 0) {  // uniform-N: the candidates that come first in their cell, the cells' shares by water-filling K
+            surf_uniform_key_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, grid_rows, grid_cols, keys, vals);
+            check_launch("surf_uniform_key_kernel");
+            UniformBudget budget = {};
+            budget.q[0] = K;
+            select_uniform(keys, nullptr, vals, M, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, prefix, n_words);
+        } else {
+            surf_metric_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, keys, vals);
+            check_launch("surf_metric_kernel");
+            select_by_key(keys, vals, M, single_group_cut(M, K), words, prefix, n_words, 32u);
+        }
         sel.alloc(K);
         surf_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, M, sel, K);
         check_launch("surf_select_compact_kernel");
@@ -598,8 +623,20 @@ int aps_surf_extract_strongest(const uint8_t* img, int height, int width, int ch
         APS_REQUIRE(params, APS_E_ARG, "NULL argument");
         APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
         check_args(img, height, width, channels, img_layout, &params->surf, desc_layout, cap, count);
-        surf_strongest_chain(img, height, width, channels, img_layout, &params->surf, params->n_strongest, desc, desc_layout, ldd, loc, ldl,
-                             aux, cap, count);
+        surf_strongest_chain(img, height, width, channels, img_layout, &params->surf, params->n_strongest, 0, 0, desc, desc_layout, ldd, loc,
+                             ldl, aux, cap, count);
+    });
+}
+
+int aps_surf_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_surf_uniform_params* params, float* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
+        check_args(img, height, width, channels, img_layout, &params->strongest.surf, desc_layout, cap, count);
+        surf_strongest_chain(img, height, width, channels, img_layout, &params->strongest.surf, params->strongest.n_strongest,
+                             params->grid_rows, params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
     });
 }
 

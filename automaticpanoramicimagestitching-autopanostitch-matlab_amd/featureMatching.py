@@ -614,10 +614,30 @@ def _sift_params(input):
     return p
 
 
-def _sift_strongest_params(input):
+def _sift_strongest_params(input, n=None):
     p = _capi.aps_sift_strongest_params()
     p.sift = _sift_params(input)
-    p.n_strongest = int(input["NumStrongest"])
+    p.n_strongest = int(input["NumStrongest"] if n is None else n)
+    return p
+
+
+def _uniform_keys(input):
+    """(N, rows, cols) of input.NumUniform and input.UniformGrid (default 8 x 8), or None without NumUniform (UniformGrid alone is
+    ignored).  NumUniform next to NumStrongest is a ValueError, raised before any library call; the values themselves are the
+    library's to refuse (APS_E_ARG)."""
+    if "NumUniform" not in input:
+        return None
+    if "NumStrongest" in input:
+        raise ValueError("input.NumUniform and input.NumStrongest exclude each other: one selection rule per call")
+    rows, cols = input.get("UniformGrid", (8, 8))
+    return int(input["NumUniform"]), int(rows), int(cols)
+
+
+def _uniform_params(struct, strongest, uniform):
+    """aps_*_uniform_params around the detector's strongest params, whose n_strongest is N."""
+    p = struct()
+    p.strongest = strongest
+    p.grid_rows, p.grid_cols = uniform[1:]
     return p
 
 
@@ -647,7 +667,12 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumStrongest (absent by default; cv::SIFT's nfeatures, selectStrongest) keeps at most that many rows through
     aps_sift_extract_strongest: those that come first by (aux[:, 2], the keypoint's contrast, descending; row index ascending), with
     no quota per octave.  The kept rows are rows of the result without the key, bit for bit and in the same order, and the capacity
-    buffer of a resident result holds NumStrongest rows, not H*W/64.  A value below 1 is an ApsError (APS_E_ARG)."""
+    buffer of a resident result holds NumStrongest rows, not H*W/64.  A value below 1 is an ApsError (APS_E_ARG).
+
+    input.NumUniform (absent by default; selectUniform) keeps min(N, rows) rows through aps_sift_extract_uniform, spread over the
+    cells of the input.UniformGrid = (rows, cols) grid (default (8, 8), each 1..32) on the image by water-filling, the largest
+    contrast first within a cell (DESIGN.md "Uniform-N selection").  The kept rows are rows of the result without the key, bit for
+    bit and in the same order; a resident result holds NumUniform rows.  Together with NumStrongest it is a ValueError."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -658,11 +683,15 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
         c = 1 if img.ndim == 2 else img.shape[2]
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
+    uniform = _uniform_keys(input)
     prm, entry = _sift_params(input), lib.aps_sift_extract
     cap = max(4096, (h * w) // 64)
     if "NumStrongest" in input:
         prm, entry = _sift_strongest_params(input), lib.aps_sift_extract_strongest
         cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
+    if uniform:
+        prm = _uniform_params(_capi.aps_sift_uniform_params, _sift_strongest_params(input, uniform[0]), uniform)
+        entry, cap = lib.aps_sift_extract_uniform, min(cap, max(uniform[0], 1))
     cnt = C.c_int64(0)
     while True:
         if device_out:
@@ -723,10 +752,10 @@ def _surf_params(input):
     return p
 
 
-def _surf_strongest_params(input):
+def _surf_strongest_params(input, n=None):
     p = _capi.aps_surf_strongest_params()
     p.surf = _surf_params(input)
-    p.n_strongest = int(input["NumStrongest"])
+    p.n_strongest = int(input["NumStrongest"] if n is None else n)
     return p
 
 
@@ -741,7 +770,11 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumStrongest (absent by default; selectStrongest) keeps at most that many rows through aps_surf_extract_strongest: those
     that come first by (metric descending, row index ascending), with no quota per octave.  The kept rows are rows of the result
     without the key, in the same order; the capacity buffer of a resident result holds NumStrongest rows.  A value below 1 is an
-    ApsError (APS_E_ARG)."""
+    ApsError (APS_E_ARG).
+
+    input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps min(N, rows) rows through
+    aps_surf_extract_uniform, spread over the grid's cells by water-filling, the largest metric first within a cell; a row's cell is
+    that of its detection sample, before refinement (DESIGN.md "Uniform-N selection")."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -752,11 +785,15 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
         c = 1 if img.ndim == 2 else img.shape[2]
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
+    uniform = _uniform_keys(input)
     prm, entry, max_features = _surf_params(input), lib.aps_surf_extract, int(input.get("maxFeatures", 0))
     cap = max(4096, (h * w) // 64)
     if "NumStrongest" in input:
         prm, entry = _surf_strongest_params(input), lib.aps_surf_extract_strongest
         cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
+    if uniform:
+        prm = _uniform_params(_capi.aps_surf_uniform_params, _surf_strongest_params(input, uniform[0]), uniform)
+        entry, cap = lib.aps_surf_extract_uniform, min(cap, max(uniform[0], 1))
     cnt = C.c_int64(0)
     ld = DIM if device_out else SURF_DIM
     while True:
@@ -818,10 +855,10 @@ def _fast_pyramid_params(input, n_levels):
     return p
 
 
-def _fast_strongest_params(input, n_levels):
+def _fast_strongest_params(input, n_levels, n=None):
     p = _capi.aps_fast_strongest_params()
     p.pyramid = _fast_pyramid_params(input, n_levels)
-    p.n_strongest = int(input["NumStrongest"])
+    p.n_strongest = int(input["NumStrongest"] if n is None else n)
     return p
 
 
@@ -839,7 +876,11 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumStrongest (absent by default; detectORBFeatures' nfeatures, selectStrongest) keeps at most that many rows, for any
     NumLevels, through aps_fast_extract_strongest: a quota per level in proportion to h_l + w_l, and within a level the rows
     with the largest integer Harris response.  The kept rows are rows of the result without the key, in the same order;
-    aux is [score, bin, level, f32(R)].  A value below 1 is an ApsError (APS_E_ARG)."""
+    aux is [score, bin, level, f32(R)].  A value below 1 is an ApsError (APS_E_ARG).
+
+    input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps the same number of rows per level as
+    NumStrongest = N does, through aps_fast_extract_uniform, but spreads each level's rows over the cells of the grid on the level's
+    plane by water-filling, the largest Harris response first within a cell (DESIGN.md "Uniform-N selection"); aux as above."""
     if _capi.is_torch(image):
         img = image.contiguous()
         h, w = int(img.shape[0]), int(img.shape[1])
@@ -851,8 +892,9 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
     n_levels = int(input.get("NumLevels", 1))
+    uniform = _uniform_keys(input)
     strongest = "NumStrongest" in input
-    if n_levels == 1 and not strongest:
+    if n_levels == 1 and not strongest and not uniform:
         prm, entry, pixels = _fast_params(input), lib.aps_fast_extract, h * w
     else:
         prm, entry = _fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid
@@ -864,6 +906,9 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     if strongest:
         prm, entry = _fast_strongest_params(input, n_levels), lib.aps_fast_extract_strongest
         cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
+    if uniform:
+        prm = _uniform_params(_capi.aps_fast_uniform_params, _fast_strongest_params(input, n_levels, uniform[0]), uniform)
+        entry, cap = lib.aps_fast_extract_uniform, min(cap, max(uniform[0], 1))
     cnt = C.c_int64(0)
     while True:
         if device_out:

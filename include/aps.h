@@ -886,6 +886,55 @@ int aps_fast_harris(const uint8_t* img, int height, int width, int channels, int
 int aps_freak_pattern(int32_t* fields, int32_t* pairs, int32_t* ori_pairs, int32_t* ori_dir, int32_t* cos_sin, int* margin);
 
 /* ============================================================================================
+ * (4d) Uniform-N selection for SIFT, SURF and FAST — selectUniform next to selectStrongest
+ * ============================================================================================ */
+/* DESIGN.md "Uniform-N selection".  Candidates, strength, groups (one; for FAST one per level) and canonical order are those of the
+ * detector's _strongest entry, and so is the budget of a group: min(N, candidates), for FAST the rows the _strongest call keeps on
+ * the level.  The budget is spread over the cells of a grid_rows x grid_cols grid on the group's plane (the image; for FAST the
+ * level's plane) by water-filling: with counts c_k and budget Q, t is the largest integer with sum_k min(c_k, t) <= Q, cell k keeps
+ * min(c_k, t) rows, and the first Q - sum_k min(c_k, t) cells in ascending k with c_k > t keep one more.  Within a cell the rows that
+ * come first by (strength descending, canonical index ascending) stay.  The cell of a candidate is that of a 0-based pixel (py, px):
+ *   SIFT  px = clamp((int)floor(x) - 1, 0, width - 1) of the row's 1-based f64 location, py alike
+ *   SURF  the candidate's detection sample (i * step, j * step), before refinement
+ *   FAST  the candidate's pixel on its level
+ * A 1 x 1 grid gives the _strongest result. */
+typedef struct aps_sift_uniform_params {
+    aps_sift_strongest_params strongest;   /* strongest.n_strongest is N >= 1 */
+    int grid_rows, grid_cols;              /* each in 1..32; anything else is APS_E_ARG before any device work */
+} aps_sift_uniform_params;
+typedef struct aps_surf_uniform_params {
+    aps_surf_strongest_params strongest;   /* strongest.n_strongest is N >= 1 */
+    int grid_rows, grid_cols;              /* each in 1..32; anything else is APS_E_ARG before any device work */
+} aps_surf_uniform_params;
+typedef struct aps_fast_uniform_params {
+    aps_fast_strongest_params strongest;   /* strongest.n_strongest is N >= 1 */
+    int grid_rows, grid_cols;              /* each in 1..32; anything else is APS_E_ARG before any device work */
+} aps_fast_uniform_params;
+
+/* Arguments, capacity, count-only mode, APS_E_CAP with nothing written, padding, layouts, host and device pointers, the meaning of
+ * max_features and the read-backs are those of the matching _strongest entry, and so is *count.  The kept rows come in canonical order;
+ * every byte of descriptor, location and aux of a kept row is that of the same row of the call without selection (FAST: aux[3] = f32(R)
+ * as in aps_fast_extract_strongest); only kept rows are described. */
+int aps_sift_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_sift_uniform_params* params, float* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+int aps_surf_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_surf_uniform_params* params, float* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+int aps_fast_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
+                             const aps_fast_uniform_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                             double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* The water-filling of that rule (host only, needs no device; the function the device kernel calls): keep[k] of n_cells cells (1..1024)
+ * with counts[k] in 0..2^32-1 under min(budget, sum counts).  counts and keep: host int64[n_cells]. */
+int aps_uniform_quota(const int64_t* counts, int n_cells, int64_t budget, int64_t* keep);
+
+/* The cell of the 0-based pixel (py, px) of a plane_h x plane_w plane (host only, needs no device; the function the device kernels call):
+ * *cell = (py * grid_rows / plane_h) * grid_cols + px * grid_cols / plane_w, integer divisions.  A pixel outside the plane or a grid
+ * value outside 1..32 is APS_E_ARG. */
+int aps_uniform_cell(int py, int px, int plane_h, int plane_w, int grid_rows, int grid_cols, int* cell);
+
+/* ============================================================================================
  * Bench / test support — NOT part of the reference boundary
  * ============================================================================================ */
 /* One uint8 H x W x 3 (row-major interleaved) view of the seeded procedural world used by bench.py and the
