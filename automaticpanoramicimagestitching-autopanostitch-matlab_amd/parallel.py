@@ -12,10 +12,14 @@ What shards how:
                        (model, found, inlier count) are combined with one all-reduce.
   5. host segment    : every rank repeats the tiny deterministic graph/camera step (no broadcast needed):
                        connected components, one camera set + reference per component (recognizePanoramas.m).
+                       Without intrinsics the cameras are ESTIMATED instead (bundleAdjustmentRKf / bundleAdjustmentH,
+                       normal equations on the device): the RANSAC inlier lists are all-gathered once, every component
+                       is estimated by one rank (balanced by members^2) and its packed result is broadcast.
   6. render          : source images are all-gathered once (uint8, started before SIFT); EVERY connected component
                        is rendered (displayPanorama.m:88-116): components first (whole panoramas to ranks, balanced
                        by canvas area, when there are at least as many as ranks), tiles second (tiles t % world of
-                       one canvas, renderPanorama.m:342-406, when there are fewer).
+                       one canvas, renderPanorama.m:342-406, when there are fewer).  A planar set is composited whole
+                       by the rank that estimated it (no tiles).
 There is no other collective on the data path.
 """
 from __future__ import annotations
@@ -254,6 +258,12 @@ class ImageGather:
         self.per = per
         self.work = _all_gather_into(self.recv, self.send, async_op=True)
 
+    def sizes(self):
+        """(rows, cols) of all n images, known on every rank from the start (the shapes travel before the pixels)."""
+        if not _multi(self.ws):
+            return [(int(self.local[i].shape[0]), int(self.local[i].shape[1])) for i in range(self.n)]
+        return [(h, w) for (h, w, _) in self.shapes]
+
     def finish(self):
         """Blocks until the collective has completed (idempotent).  Called before the matching stage: the int8 screening
         kernel claims whole CUs (match_screen_i8_kernel), so a collective left running beside it would only time-slice
@@ -452,12 +462,15 @@ def submit_features_rest(handle):
 
 
 def _match_pass(input, local_images, n, seed, times, dev, image_events=None, before_match=None, after_features=None,
-                features=None, after_matching=None, after_ransac=None):
+                features=None, after_matching=None, after_ransac=None, want_inliers=False):
     """Steps 1-4 on the current images: SIFT on the local shard, the descriptor exchange, the sharded pair matching
     and the sharded RANSAC verification (main.m:88-107 up to imageMatching).  Everything that is exchanged stays on
     the device; the host sees counts, candidate lists and the 3 x 3 models.
     features: the handle of submit_features() for exactly these images (extraction already under way), or None.
     after_matching: optional callable run when the match lists are complete, before candidate selection and RANSAC.
+    want_inliers (set when the cameras have to be estimated, and only then): every rank keeps the inlier index pairs of the
+    pairs it verified itself, ONE ragged all-gather brings them to every rank, and the result gains "inliers" (per entry of
+    "pairs" the K x 2 1-based keypoint indices pipeline.match_and_verify returns) and "keypoints" (host copies of kps_t).
     Returns dict(counts, kps_t, pairs, models, num_matches, n_match, order)."""
     from . import featureMatching as fm
     from . import imageMatching as im
@@ -614,6 +627,7 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
     # model (9), found, inliers per candidate pair: a device tensor only when it has to be all-reduced
     rec = (torch.zeros((max(len(work), 1), 11), dtype=torch.float64, device=dev) if _multi(ws)
            else np.zeros((max(len(work), 1), 11), np.float64))
+    my_inl = torch.zeros((0, 2), dtype=torch.int32, device=dev) if want_inliers else None
     if mine:
         cnts = [int(n_match[p]) for p in mine]
         wptr = np.concatenate([[0], np.cumsum(cnts)]).astype(np.int64)
@@ -623,13 +637,20 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
                                           [order[p][1] for p in mine])
         times.add("im_gather", t0)
         t0 = time.perf_counter()
-        models, mask, found, ninl = im.ransac_batch_drawn(src, dst, wptr, cnts, input, seed, keys=mine)
+        # Draws are keyed so that they do not depend on the sharding: by the global pair index - or, when the cameras are to be
+        # estimated, by candidate_keys: the estimate starts from these models, and a set of images has to get the same
+        # cameras alone and beside other sets, and in a set of its own those of pipeline.stitch.
+        wk = {p: k for k, p in enumerate(work)}
+        keys = mine
+        if want_inliers:
+            ck = candidate_keys([order[p] for p in work], n)
+            keys = [ck[wk[p]] for p in mine]
+        models, mask, found, ninl = im.ransac_batch_drawn(src, dst, wptr, cnts, input, seed, keys=keys)
         times.add("im_ransac", t0)
         if after_ransac is not None:
             after_ransac()
             after_ransac = None
         t0 = time.perf_counter()
-        wk = {p: k for k, p in enumerate(work)}
         vals = np.concatenate([models.reshape(len(mine), 9), found.reshape(-1, 1).astype(np.float64),
                                ninl.reshape(-1, 1).astype(np.float64)], axis=1)
         if _multi(ws):
@@ -637,12 +658,26 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
             rec[rows] = torch.from_numpy(vals).to(dev)
         else:
             rec[[wk[p] for p in mine]] = vals
+        if want_inliers:
+            # rows of this rank's verified pairs in `mine` order: mask -> positions in the resident match lists, one device
+            # gather; the threshold is the one applied to the all-reduced verdicts below, so every rank agrees on who sends
+            pos = []
+            for q, p in enumerate(mine):
+                if found[q] and int(ninl[q]) > 8 + 0.3 * cnts[q]:
+                    sel = np.nonzero(mask[wptr[q]:wptr[q + 1]])[0]
+                    if sel.size != int(ninl[q]):
+                        raise RuntimeError("pair %d: %d mask entries for %d inliers" % (p, sel.size, int(ninl[q])))
+                    pos.append(int(gpos[p]) + sel)
+            if pos:
+                at = torch.from_numpy(np.concatenate(pos).astype(np.int64)).to(dev)
+                my_inl = torch.stack([ia_d[at], ib_d[at]], 1).to(torch.int32).contiguous()
     if after_ransac is not None:
         after_ransac()  # (a rank without candidate pairs of its own)
     if _multi(ws):
         _all_reduce(rec)  # every row is written by exactly one rank, zero elsewhere
         rec = rec.cpu().numpy()
     pairs, models_l, num_matches = [], [], np.zeros((n, n))
+    verified, vninl = [], []
     if work:
         wk_ = np.asarray(work, np.int64)
         nf = n_match[wk_]
@@ -652,9 +687,18 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
             pairs.append((i, j))
             models_l.append(rec[k, :9].reshape(3, 3).copy())
             num_matches[i, j] = ni[k]
+            verified.append(k)
+            vninl.append(int(ni[k]))
+    out = {"counts": counts, "kps_t": kps_t, "pairs": pairs, "models": models_l, "num_matches": num_matches,
+           "n_match": n_match, "order": order}
+    if want_inliers:
+        # the owner (k % ws) and the length (ninl) of every verified pair are known from `rec`: the offsets into the per-rank
+        # blocks follow without a second exchange (inlier_slices)
+        parts = [p_.cpu().numpy() for p_ in allgather_ragged(my_inl)]
+        out["inliers"] = split_inliers(parts, verified, vninl, ws)
+        out["keypoints"] = [k.cpu().numpy() for k in kps_t]
     times.add("im_merge", t0)
-    return {"counts": counts, "kps_t": kps_t, "pairs": pairs, "models": models_l, "num_matches": num_matches,
-            "n_match": n_match, "order": order}
+    return out
 
 
 _PAIR_INDEX = {}
@@ -675,7 +719,242 @@ def _sync_lib():
     pl._sync()
 
 
-def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, cameras=None, pano_root=None,
+# ---- camera estimation without intrinsics: the inlier exchange and the per-component result -------------------------------
+def candidate_keys(work_pairs, n):
+    """Key of the RANSAC draws of every candidate pair when the cameras are estimated: the pair's position among the
+    candidate pairs of ITS OWN connected set of the candidate graph (the work list as edges), in work order.
+    The candidate graph is known before RANSAC, on every rank alike.  Image sets that share no candidate pair - the
+    panoramas-to-be of a mixed collection - are then verified exactly as each would be alone, whatever else is in the
+    collection and wherever its images stand in it; a collection that hangs together gets the positions in the whole work
+    list, which are the keys of pipeline.match_and_verify's single batch."""
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for i, j in work_pairs:
+        ri, rj = find(int(i)), find(int(j))
+        if ri != rj:
+            parent[max(ri, rj)] = min(ri, rj)
+    seen = {}
+    keys = []
+    for i, _ in work_pairs:
+        r = find(int(i))
+        keys.append(seen.get(r, 0))
+        seen[r] = keys[-1] + 1
+    return keys
+
+
+def inlier_slices(verified, ninl, world_size):
+    """Where the inlier rows of every verified pair lie in the per-rank blocks of the inlier all-gather.
+    verified: positions (into the RANSAC work list) of the pairs that passed imageMatching.m:150, ascending; ninl: their
+    inlier counts; work item k was verified by rank k % world_size, and a rank sends the rows of its verified pairs
+    concatenated in work order.  Returns [(rank, begin, end)] in the order of `verified`: nothing but the all-reduced
+    verdicts is needed, so no second exchange."""
+    offs = [0] * world_size
+    out = []
+    for k, c in zip(verified, ninl):
+        r = int(k) % world_size
+        out.append((r, offs[r], offs[r] + int(c)))
+        offs[r] += int(c)
+    return out
+
+
+def split_inliers(parts, verified, ninl, world_size):
+    """The gathered per-rank inlier blocks (K_r x 2 each) cut into one K x 2 int64 array per verified pair."""
+    out = []
+    for r, b, e in inlier_slices(verified, ninl, world_size):
+        if e > int(parts[r].shape[0]):
+            raise ValueError("rank %d sent %d inlier rows, the verdicts announce at least %d" % (r, int(parts[r].shape[0]), e))
+        out.append(np.asarray(parts[r][b:e], np.int64))
+    return out
+
+
+# One float64 tensor per connected component carries what its owner estimated (see DESIGN.md §6):
+#   [0] m, number of members   [1] ref (index into the members)   [2] layout version   [3] total length in words
+#   m camera records of 30 words: [0] field mask (1 K, 2 R, 4 f, 8 noRotation, 16 H2refined; 0 = the camera is None),
+#       [1] f, [2] noRotation, [3:12] K, [12:21] R, [21:30] H2refined, matrices row-major, absent fields zero
+#   the statistics: for every name of _STAT_SCALARS two words (tag: 0 absent, 1 None, 2 float, 3 integer; value),
+#       lm_stop as 1 + _STAT_STR words (length, -1 = absent; code points), camList and focals as 1 + m words each
+#       (length, -1 = absent; values)
+# The length depends on m alone, so every rank can size the receive buffer; floats travel as their own bits.
+_COMP_VERSION = 1
+_CAM_WORDS = 30
+_CAM_FIELDS = (("K", 1, 3), ("R", 2, 12), ("H2refined", 16, 21))
+_STAT_SCALARS = ("f_init", "noRotation", "evaluations", "rmse_init", "rmse_final", "lm_iterations", "E_init", "E_final",
+                 "seconds")
+_STAT_STR = 16
+_STAT_LISTS = ("camList", "focals")
+
+
+def component_words(m):
+    """Length of the packed result of a component of m images."""
+    return 4 + _CAM_WORDS * m + 2 * len(_STAT_SCALARS) + 1 + _STAT_STR + len(_STAT_LISTS) * (1 + m)
+
+
+def pack_component(cams, ref, stats):
+    """(cameras in member order, ref, statistics dict of pipeline._component_ba) -> float64[component_words(m)]."""
+    import numbers
+
+    m = len(cams)
+    buf = np.zeros(component_words(m), np.float64)
+    buf[:4] = (m, int(ref), _COMP_VERSION, buf.size)
+    for q, cam in enumerate(cams):
+        if cam is None:
+            continue
+        rec = buf[4 + _CAM_WORDS * q: 4 + _CAM_WORDS * (q + 1)]
+        unknown = set(cam) - {"K", "R", "f", "noRotation", "H2refined"}
+        if unknown:
+            raise KeyError("camera field(s) without a place in the packed layout: %s" % sorted(unknown))
+        mask = 0
+        if "f" in cam:
+            mask |= 4
+            rec[1] = cam["f"]
+        if "noRotation" in cam:
+            mask |= 8
+            rec[2] = int(cam["noRotation"])
+        for name, bit, at in _CAM_FIELDS:
+            if name in cam:
+                mask |= bit
+                rec[at: at + 9] = np.asarray(cam[name], np.float64).reshape(9)
+        rec[0] = mask
+    unknown = set(stats) - set(_STAT_SCALARS) - set(_STAT_LISTS) - {"lm_stop"}
+    if unknown:
+        raise KeyError("statistic(s) without a place in the packed layout: %s" % sorted(unknown))
+    at = 4 + _CAM_WORDS * m
+    for name in _STAT_SCALARS:
+        if name in stats:
+            v = stats[name]
+            if v is None:
+                buf[at] = 1
+            elif isinstance(v, numbers.Integral):
+                if abs(int(v)) > 2 ** 53:
+                    raise ValueError("%s = %d does not fit a float64 word" % (name, int(v)))
+                buf[at], buf[at + 1] = 3, int(v)
+            else:
+                buf[at], buf[at + 1] = 2, v
+        at += 2
+    buf[at] = -1
+    if "lm_stop" in stats:
+        s = str(stats["lm_stop"])
+        if len(s) > _STAT_STR:
+            raise ValueError("lm_stop %r is longer than %d characters" % (s, _STAT_STR))
+        buf[at] = len(s)
+        buf[at + 1: at + 1 + len(s)] = [ord(ch) for ch in s]
+    at += 1 + _STAT_STR
+    for name in _STAT_LISTS:
+        buf[at] = -1
+        if name in stats:
+            v = list(stats[name])
+            if len(v) > m:
+                raise ValueError("%s has %d entries for %d images" % (name, len(v), m))
+            buf[at] = len(v)
+            buf[at + 1: at + 1 + len(v)] = v
+        at += 1 + m
+    return buf
+
+
+def unpack_component(buf):
+    """float64[component_words(m)] -> (cameras, ref, statistics): the inverse of pack_component, bit for bit."""
+    buf = np.asarray(buf, np.float64)
+    m, ref = int(buf[0]), int(buf[1])
+    if int(buf[2]) != _COMP_VERSION or int(buf[3]) != buf.size or buf.size != component_words(m):
+        raise ValueError("not a packed component result of this layout")
+    cams = []
+    for q in range(m):
+        rec = buf[4 + _CAM_WORDS * q: 4 + _CAM_WORDS * (q + 1)]
+        mask = int(rec[0])
+        if mask == 0:
+            cams.append(None)
+            continue
+        cam = {}
+        if mask & 1:
+            cam["K"] = rec[3:12].reshape(3, 3).copy()
+        if mask & 2:
+            cam["R"] = rec[12:21].reshape(3, 3).copy()
+        if mask & 4:
+            cam["f"] = float(rec[1])
+        if mask & 8:
+            cam["noRotation"] = int(rec[2])
+        if mask & 16:
+            cam["H2refined"] = rec[21:30].reshape(3, 3).copy()
+        cams.append(cam)
+    stats = {}
+    at = 4 + _CAM_WORDS * m
+    for name in _STAT_SCALARS:
+        tag = int(buf[at])
+        if tag:
+            stats[name] = None if tag == 1 else int(buf[at + 1]) if tag == 3 else float(buf[at + 1])
+        at += 2
+    if buf[at] >= 0:
+        stats["lm_stop"] = "".join(chr(int(c)) for c in buf[at + 1: at + 1 + int(buf[at])])
+    at += 1 + _STAT_STR
+    for name in _STAT_LISTS:
+        if buf[at] >= 0:
+            v = buf[at + 1: at + 1 + int(buf[at])]
+            stats[name] = [int(x) for x in v] if name == "camList" else [float(x) for x in v]
+        at += 1 + m
+    return cams, ref, stats
+
+
+def component_owners(sizes, world_size):
+    """Rank that estimates (and, for a planar set, renders) each component.  The weight (number of members)^2 is a stand-in
+    for the cost of the incremental LM - it adds one image per round and every round solves for all cameras so far - not a
+    measured cost model."""
+    return partition_weighted([float(s) * float(s) for s in sizes], world_size)
+
+
+def _estimate_components(input, n, res, labels, image_sizes, dev):
+    """Step 5 without intrinsics: what pipeline.recognize_panoramas does for Ks = None, sharded by component.  The owner of a
+    component runs pipeline._component_ba (focal, spanning-tree rotations, incremental LM with the normal equations on its
+    GPU) and the straightening, packs the result and broadcasts it; EVERY rank, the owner included, goes on with the
+    unpacked bytes.  A rank first estimates all of its components and only then enters the broadcasts, so the LM loops of
+    different ranks run side by side.  One rank, no process group: the same path without the collective.
+    Returns (comps as recognize_panoramas returns them, each with "owner"; ba_info: one statistics dict per component)."""
+    from . import pipeline as pl
+
+    ws, rank = world()
+    multi = _multi(ws)
+    labels = np.asarray(labels)
+    todo = []
+    for c in range(int(labels.max()) + 1 if labels.size else 0):
+        members = [int(k) for k in np.nonzero(labels == c)[0]]
+        if len(members) >= 2:  # recognizePanoramas.m:86-89
+            todo.append(members)
+    owners = component_owners([len(m_) for m_ in todo], ws) if multi else np.zeros(len(todo), np.int64)
+    packed = {}
+    for ci, members in enumerate(todo):
+        if int(owners[ci]) != rank:
+            continue
+        t0 = time.perf_counter()
+        cams, ref, stats = pl._component_ba(input, members, res["pairs"], res["models"], np.asarray(res["num_matches"]),
+                                            res["keypoints"], res["inliers"], image_sizes)
+        if not stats["noRotation"] and not input.get("forcePlanarScan", False):
+            cams = pl.straightening(cams)
+        packed[ci] = pack_component(cams, ref, dict(stats, seconds=time.perf_counter() - t0))
+    comps, ba_info = [], []
+    for ci, members in enumerate(todo):
+        buf = packed.get(ci)
+        if multi:
+            t = (torch.from_numpy(buf) if buf is not None else torch.empty(component_words(len(members)), dtype=torch.float64)).to(dev)
+            buf = _broadcast(t, int(owners[ci])).cpu().numpy()
+        cams, ref, stats = unpack_component(buf)
+        ba_info.append(dict(stats, members=members, owner=int(owners[ci])))
+        comp = pl.keep_reached(members, ref, cams)
+        if comp is not None:
+            comps.append(dict(comp, owner=int(owners[ci])))
+    return comps, ba_info
+
+
+def _is_planar(input, cams):
+    """renderPanorama.m:78-90: the sets that bypass the ray renderer (the test rp.renderPanorama itself makes)."""
+    return bool(cams) and (cams[0].get("noRotation", 0) == 1 or bool(input.get("forcePlanarScan", False)))
+
+
+def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=0, cameras=None, pano_root=None,
                        local_originals=None, image_events=None, after_features=None, features=None, after_matching=None,
                        after_ransac=None):
     """The whole stitch with the work sharded over the ranks of the default process group (see module doc).
@@ -694,6 +973,12 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
     the previous call's after_matching hook); after_matching: optional callable run when the (first-pass) match lists are
     complete - the point from which no int8 kernel runs any more in this call; after_ransac: the same after this rank's
     RANSAC batch (its three launches are latency-bound: beside a busy chip they take 6 instead of 2.3 ms).
+    Ks = None and cameras = None: the cameras are estimated as pipeline.stitch estimates them (focal estimation, bundle
+    adjustment, straightening; bundleAdjustmentH for planar sets with input.planarBundleAdjustment), every component on ONE
+    rank (_estimate_components) whose result is broadcast; info["ba"] then holds one statistics dict per component (those of
+    pipeline.stitch plus "owner" and the owner's wall "seconds") and times["bundle_adjustment"] replaces
+    times["host_cameras"].  Planar sets (cameras with noRotation = 1, or input.forcePlanarScan) are rendered whole by one
+    rank through the planar compositor, also when `cameras` are given.
     Returns (panorama of the component that holds the best-connected image, uint8 H x W x 3 CUDA tensor; info dict
     with info["panoramas"]: one entry per connected component of at least two images, in component order)."""
     from . import pipeline as pl
@@ -714,14 +999,17 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
         image_events = None
     img_gather = ImageGather(local_images, n, dev)
     times.add("exchange", t0)
+    estimate = Ks is None and cameras is None  # no intrinsics: step 5 estimates the cameras and needs the RANSAC inliers
+    cam_key = "bundle_adjustment" if estimate else "host_cameras"
 
     res = _match_pass(input, local_images, n, seed, times, dev, image_events, before_match=img_gather.finish,
-                      after_features=after_features, features=features, after_matching=after_matching, after_ransac=after_ransac)
+                      after_features=after_features, features=features, after_matching=after_matching, after_ransac=after_ransac,
+                      want_inliers=estimate)
 
     # 5) host segment (redundant on every rank): components, second pass if asked for, cameras per component
     t0 = time.perf_counter()
     ncomp, labels = pl.connected_components(res["num_matches"])
-    times.add("host_cameras", t0)
+    times.add(cam_key, t0)
     if (int(input.get("resizeImage", 0)) == 1 and int(input.get("resizeImagePanoramaCluster", 0)) == 1 and ncomp > 1
             and local_originals is not None):
         # imageMatchingPanoramaConComps.m:48-91: images resized per component (the common size is that of the
@@ -751,11 +1039,15 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
         img_gather = ImageGather(local_images, n, dev)
         times.add("exchange", t0)
         first_counts = res["counts"]
-        res = _match_pass(input, local_images, n, seed, times, dev, before_match=img_gather.finish)
+        res = _match_pass(input, local_images, n, seed, times, dev, before_match=img_gather.finish, want_inliers=estimate)
         res["second_pass"], res["counts_first_pass"] = True, first_counts
     t0 = time.perf_counter()
-    comps = pl.recognize_panoramas(n, res["pairs"], res["models"], res["num_matches"], Ks, labels, cameras)
-    times.add("host_cameras", t0)
+    ba_info = None
+    if estimate:
+        comps, ba_info = _estimate_components(input, n, res, labels, img_gather.sizes(), dev)
+    else:
+        comps = pl.recognize_panoramas(n, res["pairs"], res["models"], res["num_matches"], Ks, labels, cameras)
+    times.add(cam_key, t0)
 
     # 6) render every component
     t0 = time.perf_counter()
@@ -768,17 +1060,42 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
             "canvasColor": input["canvasColor"], "tile": tile, "cropBorder": bool(input.get("cropBorder", True))}  # displayPanorama.m:101
     mode = input["panorama2DisplaynSave"]
     # geometry of every canvas (host, f64) decides the sharding: components to ranks when there are enough of them
-    geos = []
-    for c in comps:
+    # (a planar set has no ray-render geometry: it goes whole to one rank below and takes no part in this decision)
+    geos, ray = [], []
+    for ci, c in enumerate(comps):
         sizes = [(int(images[k].shape[0]), int(images[k].shape[1]), 3) for k in c["members"]]
+        if _is_planar(input, c["cameras"]):
+            geos.append((sizes, None))
+            continue
         o_ = rp.default_opts(opts, c["cameras"], c["ref"])
         geos.append((sizes, rp.canvas_geometry(c["cameras"], sizes, mode, c["ref"], o_)))
-    by_component = _multi(ws) and len(comps) >= ws
-    comp_owner = partition_weighted([float(g["H"]) * float(g["W"]) for (_, g) in geos], ws) if by_component else None
+        ray.append(ci)
+    by_component = _multi(ws) and len(ray) >= ws
+    comp_owner = {}
+    if by_component:
+        comp_owner = dict(zip(ray, partition_weighted([float(geos[ci][1]["H"]) * float(geos[ci][1]["W"]) for ci in ray], ws)))
+    flat = [ci for ci in range(len(comps)) if geos[ci][1] is None]
+    if flat and _multi(ws):
+        # the rank that estimated the set renders it; sets that came with `cameras` are dealt by the same rule
+        dealt = component_owners([len(comps[ci]["members"]) for ci in flat], ws)
+        comp_owner.update({ci: comps[ci].get("owner", int(dealt[q])) for q, ci in enumerate(flat)})
     panos = []
     for ci, c in enumerate(comps):
         sizes, geo = geos[ci]
         members = c["members"]
+        if geo is None:
+            # planar scan (renderPanorama.m:78-90): no canvas_geometry, no gainCompensationRKf; rp.renderPanorama routes to
+            # pureNonRotationalPanoramas, which runs gainCompensationH itself when the opts ask for it (:584-591)
+            popts = dict(opts, **{k: input[k] for k in ("gainCompensation", "sigmaN", "sigmag") if k in input})
+            pano = None
+            if not _multi(ws) or int(comp_owner[ci]) == rank:
+                pano, _ = rp.renderPanorama(input, [images[k] for k in members], sizes, c["cameras"], mode, c["ref"], popts,
+                                            device_out=True)
+                pl._sync()
+            if _multi(ws):
+                pano = _deliver_panorama(pano, int(comp_owner[ci]), pano_root, dev)
+            panos.append(pano)
+            continue
         gains = None
         if input.get("gainCompensation"):
             # gainCompensationRKf between cameras and render (renderPanorama.m:303-330).  The device sums in an
@@ -831,6 +1148,8 @@ def stitch_distributed(input, local_images, n, Ks, tile=(2048, 2048), seed=0, ca
             "members": comps[main]["members"] if comps else [], "cameras": _scatter_cameras(comps, n),
             "pairs": res["pairs"], "models": res["models"], "components": comps, "panoramas": panos, "labels": labels,
             "second_pass": bool(res.get("second_pass", False)), "n_features_first_pass": res.get("counts_first_pass")}
+    if ba_info is not None:
+        info["ba"] = ba_info
     return pano, info
 
 

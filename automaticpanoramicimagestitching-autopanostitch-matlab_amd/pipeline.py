@@ -429,15 +429,24 @@ def recognize_panoramas(n, pairs, models, num_matches, Ks, labels, cameras=None,
             cams_all, seed = cameras_from_models(n, [pairs[p] for p in sel], [models[p] for p in sel], num_matches, Ks)
             cams = straightening([cams_all[k] for k in members])
             ref = members.index(seed)
-        keep = [q for q, cam in enumerate(cams) if cam is not None]
-        if len(keep) < 2:
-            continue
-        if len(keep) != len(members):
-            ref = keep.index(ref) if ref in keep else 0
-            members = [members[q] for q in keep]
-            cams = [cams[q] for q in keep]
-        comps.append({"members": members, "ref": ref, "cameras": cams})
+        comp = keep_reached(members, ref, cams)
+        if comp is not None:
+            comps.append(comp)
     return comps
+
+
+def keep_reached(members, ref, cams):
+    """One entry of recognize_panoramas' result from a component's cameras: members whose camera is None (never reached by
+    the spanning tree or the incremental loop) are dropped and `ref` is renumbered; fewer than two cameras left give None.
+    (parallel.stitch_distributed applies the same rule to cameras it received from the rank that estimated them.)"""
+    keep = [q for q, cam in enumerate(cams) if cam is not None]
+    if len(keep) < 2:
+        return None
+    if len(keep) != len(members):
+        ref = keep.index(ref) if ref in keep else 0
+        members = [members[q] for q in keep]
+        cams = [cams[q] for q in keep]
+    return {"members": members, "ref": ref, "cameras": cams}
 
 
 def fit_size(h, w, heightLimit, widthLimit):
