@@ -666,11 +666,7 @@ void fast_front(const uint8_t* img, int channels, int img_layout, const aps_fast
     }
     {
         Prof prof("fast_scan");
-        auto counts = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
-        size_t tbytes = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, n_words + 1, rocprim::plus<unsigned int>(), stream()));
-        Ws<char> tmp(tbytes);
-        APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, n_words + 1, rocprim::plus<unsigned int>(), stream()));
+        exclusive_scan(popcounts(bitmap.get()), prefix.get(), 0u, n_words + 1);
     }
 }
 
@@ -719,9 +715,7 @@ void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast
         }
         check_launch("freak_keypoint_kernel");
     }
-    unsigned int n = 0;  // the one read-back of the chain
-    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n = read_back(d_total);  // the one read-back of the chain
     *count = n;
     if (params->max_features > 0 && n > (unsigned int)params->max_features)
         fail(APS_E_CAP, "FAST found %u features, more than params.max_features = %d", n, params->max_features);
@@ -760,8 +754,7 @@ void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
     Ws<unsigned int> d_first((size_t)kMaxLevels + 1);
     strongest_counts_kernel<<<1, 64, 0, stream()>>>(F.prefix, P, hp.n_words, d_first);
     check_launch("strongest_counts_kernel");
-    APS_HIP(hipMemcpyAsync(Cd.first, d_first.get(), (size_t)(P.n + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    read_back(d_first.get(), Cd.first, P.n + 1);
     const unsigned int M = Cd.M = Cd.first[P.n];
     if (!M) return;
     Cd.kps.alloc(M);
@@ -862,9 +855,7 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
             check_launch("strongest_aux_kernel");
         }
     }
-    unsigned int n = 0;  // the second read-back: the count the device kept is the count the host worked out
-    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n = read_back(d_total);  // the second read-back: the count the device kept is the count the host worked out
     APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
     if (desc_layout == APS_ROWMAJOR)
         odesc.commit_2d(64, K, (size_t)ldd);

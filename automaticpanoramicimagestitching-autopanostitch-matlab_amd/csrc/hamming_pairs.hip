@@ -23,8 +23,7 @@
 #include <vector>
 
 #include "aps_internal.h"
-
-#include <rocprim/rocprim.hpp>
+#include "prims_dev.h"
 
 namespace aps {
 namespace {
@@ -335,18 +334,12 @@ void hamming_pairs_impl(const uint8_t* const* desc, const int64_t* counts, const
     Out<int64_t> optr(pair_ptr, (size_t)n_pairs + 1);
     {
         Prof prof("hamming_pairs_scan");
-        auto pops = rocprim::make_transform_iterator(bitmap.get(), PopcOp());
-        size_t tbytes = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, pops, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-        Ws<char> tmp(tbytes);
-        APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, pops, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+        exclusive_scan(popcounts(bitmap.get()), prefix.get(), 0u, (size_t)n_words + 1);
         hamming_pairs_ptr_kernel<<<cdiv((size_t)n_pairs + 1, 256), 256, 0, stream()>>>(prefix, d_word_start, n_pairs + 1, optr);
         check_launch("hamming_pairs_ptr_kernel");
     }
-    unsigned int total = 0;  // the one read-back of the chain
-    APS_HIP(hipMemcpyAsync(&total, prefix.get() + n_words, sizeof total, hipMemcpyDeviceToHost, stream()));
+    const unsigned int total = read_back(prefix.get() + n_words);  // the one read-back of the chain
     optr.commit();
-    APS_HIP(hipStreamSynchronize(stream()));
     *count = total;
     const bool write = idx_a && idx_b && metric;  // count-only otherwise
     if (total > 0 && ((int64_t)total > cap || !write))
@@ -365,10 +358,7 @@ void hamming_pairs_impl(const uint8_t* const* desc, const int64_t* counts, const
         Prof prof("hamming_pairs_sort");
         int end_bit = kPairShift + 1;
         while (end_bit < 64 && ((int64_t)1 << (end_bit - kPairShift)) < n_pairs) ++end_bit;
-        size_t sbytes = 0;
-        APS_HIP(rocprim::radix_sort_pairs(nullptr, sbytes, keys.get(), sorted_keys.get(), cols.get(), sorted_cols.get(), total, 0, end_bit, stream()));
-        Ws<char> tmp(sbytes);
-        APS_HIP(rocprim::radix_sort_pairs(tmp.get(), sbytes, keys.get(), sorted_keys.get(), cols.get(), sorted_cols.get(), total, 0, end_bit, stream()));
+        sort_pairs<unsigned int>(keys.get(), sorted_keys.get(), cols.get(), sorted_cols.get(), total, (unsigned int)end_bit);
         k_out = sorted_keys;
         c_out = sorted_cols;
     }

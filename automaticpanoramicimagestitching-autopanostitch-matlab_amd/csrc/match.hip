@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "aps_internal.h"
+#include "prims_dev.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -3998,14 +3999,8 @@ static int64_t run_filter(const std::vector<FilterJob>& fjobs, int64_t total_row
     filter_select_kernel<<<grid, 256, 0, stream()>>>(dfj, njobs, total_rows, idx, o.unique, keys,
                                                       winner, packed, cnt);
     check_launch("filter_select_kernel");
-    {  // job_ptr = exclusive scan of the per-job counts, with the total in slot njobs (cnt[njobs] is a zero pad)
-        size_t sb = 0;
-        APS_HIP(rocprim::exclusive_scan(nullptr, sb, cnt.get(), d_job_ptr, 0ull, (size_t)njobs + 1,
-                                        rocprim::plus<unsigned long long>(), stream()));
-        Ws<char> stmp(sb);
-        APS_HIP(rocprim::exclusive_scan(stmp.get(), sb, cnt.get(), d_job_ptr, 0ull, (size_t)njobs + 1,
-                                        rocprim::plus<unsigned long long>(), stream()));
-    }
+    // job_ptr = exclusive scan of the per-job counts, with the total in slot njobs (cnt[njobs] is a zero pad)
+    exclusive_scan(cnt.get(), d_job_ptr, 0ull, (size_t)njobs + 1);
 
     // segmented ascending sort of each job's kept keys (the head of its row segment)
     Ws<int64_t> dseg(2 * (int64_t)njobs);

@@ -5,8 +5,9 @@
 //   strongest_flag_kernel   rank within the group < keep[g], written back by candidate index
 //   strongest_word_kernel   one ballot = one 64-bit word of the bitmap over the candidates, whose bit order is their order
 //   exclusive scan of the words' popcounts (rocprim)
-// The caller's ordered compaction reads (words, prefix) as fast_emit_kernel / surf_emit_kernel read theirs: the kept candidates
-// keep the order they had.  No atomics; every result is the same from run to run.
+// The caller's ordered compaction (select_compact_kernel; fast.hip has its own, which moves two arrays) reads (words, prefix) as
+// fast_emit_kernel / surf_emit_kernel read theirs: the kept candidates keep the order they had.  No atomics; every result is the
+// same from run to run.
 //
 // Uniform-N (DESIGN.md "Uniform-N selection") cuts per (group, cell) instead of per group.  Every candidate also has a segment id,
 // segment = group * cells + cell, below 2^14; select_uniform asks for the first keep[s] candidates of every segment, where keep comes
@@ -21,9 +22,8 @@
 #include <hip/hip_runtime.h>
 
 #include "aps_internal.h"
+#include "prims_dev.h"
 #include "uniform_rule.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace aps {
 namespace {
@@ -86,20 +86,7 @@ inline void flags_to_words(const uint8_t* flags, unsigned int n, Ws<unsigned lon
     prefix.alloc((size_t)n_words + 1);
     strongest_word_kernel<<<cdiv((size_t)n_words + 1, 4), 256, 0, stream()>>>(flags, n, n_words + 1, words);
     check_launch("strongest_word_kernel");
-    auto counts = rocprim::make_transform_iterator(words.get(), PopcOp());
-    size_t tbytes = 0;
-    APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-    Ws<char> tmp(tbytes);
-    APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-}
-
-// stable radix sort of (key, value) by the keys' low key_bits bits
-template <class K>
-inline void sort_pairs(const K* keys, K* skeys, const unsigned int* vals, unsigned int* svals, unsigned int n, unsigned int key_bits) {
-    size_t sbytes = 0;
-    APS_HIP(rocprim::radix_sort_pairs(nullptr, sbytes, keys, skeys, vals, svals, (size_t)n, 0u, key_bits, stream()));
-    Ws<char> stmp(sbytes);
-    APS_HIP(rocprim::radix_sort_pairs(stmp.get(), sbytes, keys, skeys, vals, svals, (size_t)n, 0u, key_bits, stream()));
+    exclusive_scan(popcounts(words.get()), prefix.get(), 0u, (size_t)n_words + 1);
 }
 
 // The selection proper, for any 64-bit key whose top 4 bits are the group: sorts (key, index) by ascending key (stable: equal keys keep
@@ -115,6 +102,25 @@ inline void select_by_key(const unsigned long long* keys, const unsigned int* va
     strongest_flag_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(skeys, svals, cut, n, flags);
     check_launch("strongest_flag_kernel");
     flags_to_words(flags, n, words, prefix, n_words);
+}
+
+// Ordered compaction of the flagged records (sift.hip: oriented keypoints, surf.hip: candidates): bit k of word q is record 64 q + k,
+// which becomes record prefix[q] + (set bits below k), so the kept ones keep the order they had.
+template <class T>
+__global__ __launch_bounds__(256) void select_compact_kernel(const unsigned long long* __restrict__ words,
+                                                             const unsigned int* __restrict__ prefix, unsigned int n_words,
+                                                             const T* __restrict__ in, unsigned int n, T* __restrict__ out,
+                                                             unsigned int kcap) {
+    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_words) return;
+    unsigned long long bits = words[q];
+    unsigned int pos = prefix[q];
+    while (bits) {
+        const int k = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        if (pos < kcap && q * 64 + k < n) out[pos] = in[q * 64 + k];
+        ++pos;
+    }
 }
 
 // ---- uniform-N (DESIGN.md "Uniform-N selection") ------------------------------------------------------------------------------
@@ -247,7 +253,8 @@ inline void select_uniform(const unsigned long long* keys, const unsigned int* s
         sort_pairs(keys, skeys.get(), vals, svals.get(), n, 64u);
         uniform_gather_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(segs, svals, n, kseg);
         check_launch("uniform_gather_kernel");
-        sort_pairs(kseg.get(), sseg.get(), svals.get(), svals2.get(), n, kSegmentBits);
+        const unsigned int *kseg_in = kseg, *svals_in = svals;  // (read-only as the first sort's inputs are: the same kernels)
+        sort_pairs(kseg_in, sseg.get(), svals_in, svals2.get(), n, kSegmentBits);
         uniform_flags(sseg.get(), 0u, svals2.get(), n, n_groups, cells, B, flags.get());
     }
     flags_to_words(flags, n, words, prefix, n_words);

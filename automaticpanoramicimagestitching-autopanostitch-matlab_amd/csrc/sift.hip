@@ -14,26 +14,19 @@
 //   extrema_wave_kernel            : 26-neighbour test of every octave in one launch, one wave per strip of columns.
 //   refine_kernel                  : Newton refinement + contrast/edge tests, one lane per candidate.
 //   orient_kernel / descr_kernel   : one 64-lane wave per keypoint, histograms in LDS (int64 atomics).
-//   sift_contr_key_kernel, select_by_key (select_dev.h), sift_select_compact_kernel
+//   sift_contr_key_kernel, select_by_key, select_compact_kernel (select_dev.h)
 //                                  : aps_sift_extract_strongest only - the N rows of largest contrast, picked from the list of
 //                                    oriented keypoints before descr_kernel runs (DESIGN.md "Strongest-N for SIFT and SURF").
-//   sift_uniform_key_kernel, select_uniform (select_dev.h), sift_select_compact_kernel
+//   sift_uniform_key_kernel, select_uniform, select_compact_kernel (select_dev.h)
 //                                  : aps_sift_extract_uniform only - N rows spread over the cells of a grid, the largest
 //                                    contrast first within a cell (DESIGN.md "Uniform-N selection").
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
-#ifdef APS_DBG
-#include <atomic>
-#include <map>
-#include <mutex>
-#endif
 
 #include "aps_internal.h"
 #include "select_dev.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace aps {
 
@@ -1006,23 +999,6 @@ __global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __re
     vals[i] = i;
 }
 
-// Ordered compaction of the flagged rows: bit k of word q is row 64 q + k, which becomes row prefix[q] + (set bits below k).
-__global__ __launch_bounds__(256) void sift_select_compact_kernel(const unsigned long long* __restrict__ words,
-                                                                  const unsigned int* __restrict__ prefix, unsigned int n_words,
-                                                                  const OrientedKp* __restrict__ oks, unsigned int n,
-                                                                  OrientedKp* __restrict__ out, unsigned int kcap) {
-    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n_words) return;
-    unsigned long long bits = words[q];
-    unsigned int pos = prefix[q];
-    while (bits) {
-        const int k = __ffsll((long long)bits) - 1;
-        bits &= bits - 1;
-        if (pos < kcap && q * 64 + k < n) out[pos] = oks[q * 64 + k];
-        ++pos;
-    }
-}
-
 // ---- descriptor: one wave per oriented keypoint -------------------------------------------------------
 constexpr int kD = 4, kN = 8, kHistLen = (kD + 2) * (kD + 2) * (kN + 2);  // 360
 constexpr int kDescQueue = 512;  // queued samples per wave between two strided passes over the queue
@@ -1416,67 +1392,13 @@ static int num_octaves(int H, int W) {
     return (int)std::lrint(std::log((double)mn) / std::log(2.0) - 2.0) + 1;
 }
 
+// ---- the stages of sift_chain, in the order they run on the calling thread's stream ---------------------------------------
+// What a stage's later launches read, it returns and the caller keeps; what only the stage needs goes back to the workspace when it
+// returns (the workspace hands a thread's blocks out again in the order of that thread's one stream).
 
-#ifdef APS_DBG
-// Debug builds only (`make debug`): the co-residency experiment of DESIGN.md section 5, victim side.  APS_DBG_REPLAY=R makes
-// aps_sift_extract launch the extrema sweep, refine_kernel, orient_kernel and descr_kernel R more times each on the inputs the
-// first launch saw and compare the results on the device (order-free checksums for the atomically appended lists, word by
-// word for the indexed outputs); the pyramid's checksum is kept per image pointer and compared between calls.
-namespace dbg {
-enum { kPyrChanged, kExtReplays, kExtDiff, kRefReplays, kRefDiff, kOriReplays, kOriDiff, kOriWords, kDesReplays, kDesDiff, kDesWords, kCalls, kNStat };
-static std::atomic<long long> g_stat[kNStat];
-static std::mutex g_mu;
-static std::map<const void*, unsigned long long> g_pyr;
-__global__ void cks_kernel(const unsigned int* __restrict__ p, size_t n_rec, int wpr, int positional, unsigned long long* __restrict__ out) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    unsigned long long h = 0;
-    if (i < n_rec) {
-        h = 0x9E3779B97F4A7C15ull;
-        for (int k = 0; k < wpr; ++k) {
-            h ^= p[i * wpr + k];
-            h *= 0x100000001B3ull;
-            h ^= h >> 29;
-        }
-        if (positional) h *= (2ull * i + 1ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off);
-    if ((threadIdx.x & 63) == 0 && h) atomicAdd(out, h);
-}
-__global__ void diff_kernel(const unsigned int* __restrict__ a, const unsigned int* __restrict__ b, size_t n, unsigned long long* __restrict__ out) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    const unsigned long long m = __ballot(i < n && a[i] != b[i]);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__popcll(m));
-}
-static unsigned long long cks(const void* p, size_t n_rec, int wpr, int positional, unsigned long long* d_slot) {
-    APS_HIP(hipMemsetAsync(d_slot, 0, 8, stream()));
-    if (n_rec) cks_kernel<<<cdiv(n_rec, 256), 256, 0, stream()>>>((const unsigned int*)p, n_rec, wpr, positional, d_slot);
-    unsigned long long h = 0;
-    APS_HIP(hipMemcpyAsync(&h, d_slot, 8, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    return h;
-}
-static unsigned long long diff(const void* a, const void* b, size_t n_words, unsigned long long* d_slot) {
-    APS_HIP(hipMemsetAsync(d_slot, 0, 8, stream()));
-    if (n_words) diff_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>((const unsigned int*)a, (const unsigned int*)b, n_words, d_slot);
-    unsigned long long h = 0;
-    APS_HIP(hipMemcpyAsync(&h, d_slot, 8, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    return h;
-}
-}  // namespace dbg
-#endif
-}  // namespace aps
-
-using namespace aps;
-
-// aps_sift_extract (n_strongest = 0: every row) and aps_sift_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF": the
-// n_strongest rows of largest contrast) behind one body; with grid_rows > 0 the n_strongest rows are spread over the cells of a
-// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").  The argument checks come before any
-// device work.
-static void sift_chain(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
-                       long long n_strongest, int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc,
-                       int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+// the checks of the three entries, which come before any device work
+static void check_sift_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
+                            int desc_layout, int64_t cap, const int64_t* count) {
     APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
     APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
     APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
@@ -1487,18 +1409,25 @@ static void sift_chain(const uint8_t* img, int height, int width, int channels, 
     APS_REQUIRE(params->contrast_threshold >= 0 && params->edge_threshold >= 1, APS_E_ARG, "bad thresholds");
     APS_REQUIRE(cap >= 0, APS_E_ARG, "negative capacity");
     APS_REQUIRE(2 * (int64_t)height < 65536 && 2 * (int64_t)width < 65536, APS_E_DIM, "image side must be < 32768");
-    ctx();
-    *count = 0;
+}
+
+// The Gaussian pyramid of a call: the planes, the host table of their sizes and pointers, and the table's device copy.  Every kernel
+// after the blurs reads it, so it lives until descr_kernel is launched and committed.
+struct Pyramid {
+    std::vector<Ws<float>> G;
+    PyrTable table;
+    Ws<PyrTable> d_table;
+};
+
+// dimg (H x W x channels, on the device) -> n_oct octaves of nl + 3 planes each and the uploaded table; no read-back
+static void build_pyramid(const uint8_t* dimg, int H, int W, int channels, int img_layout, const aps_sift_params* params, int n_oct,
+                          Pyramid& P) {
     const int nl = params->n_layers;
-    const int H = height, W = width;
-    In<uint8_t> dimg(img, (size_t)H * W * channels);
     Ws<float> up, scratch;  // (up: the doubled gray plane, only when the fused base kernel does not apply)
     Ws<uint8_t> gray8;      // the source gray plane as bytes (gray_u8_kernel), read by blur_base_kernel
-    const int n_oct = std::min(num_octaves(H, W), 16);
-    if (n_oct <= 0) return;
-    // pyramid storage
-    std::vector<Ws<float>> G((size_t)n_oct * (nl + 3));
-    PyrTable table;
+    std::vector<Ws<float>>& G = P.G;
+    G = std::vector<Ws<float>>((size_t)n_oct * (nl + 3));
+    PyrTable& table = P.table;
     std::memset(&table, 0, sizeof table);
     table.n_oct = n_oct;
     table.nl = nl;
@@ -1551,34 +1480,24 @@ static void sift_chain(const uint8_t* img, int height, int width, int channels, 
         }
         for (int i = 0; i < nl + 3; ++i) od.G[i] = G[o * (nl + 3) + i];
     }
-#ifdef APS_DBG
-    static const int dbg_replay = std::getenv("APS_DBG_REPLAY") ? std::atoi(std::getenv("APS_DBG_REPLAY")) : 0;
-    Ws<unsigned long long> dbg_slot(1);
-    if (dbg_replay > 0) {
-        dbg::g_stat[dbg::kCalls]++;
-        unsigned long long h = 0;
-        for (int o = 0; o < std::min(n_oct, 3); ++o)
-            for (int i = 0; i < nl + 3; ++i)
-                h = h * 1000003ull + dbg::cks(G[o * (nl + 3) + i].get(), (size_t)table.oct[o].w * table.oct[o].h, 1, 1, dbg_slot);
-        std::lock_guard<std::mutex> lk(dbg::g_mu);
-        auto it = dbg::g_pyr.find((const void*)img);
-        if (it == dbg::g_pyr.end())
-            dbg::g_pyr[(const void*)img] = h;
-        else if (it->second != h)
-            dbg::g_stat[dbg::kPyrChanged]++;
-    }
-#endif
-    // extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch
-    Ws<PyrTable> d_table(1);
-    APS_HIP(hipMemcpyAsync(d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
+    P.d_table.alloc(1);
+    APS_HIP(hipMemcpyAsync(P.d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
+}
+
+// extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch -> recs, in no particular order.
+// Returns their number after two read-backs (the cells, then the records; one more when the cells outgrow their room), or fails
+// with APS_E_CAP when the records outgrow cand_cap.
+static unsigned int detect_candidates(const Pyramid& P, const aps_sift_params* params, int H, int W, Ws<KpRec>& recs) {
+    const PyrTable& table = P.table;
+    const int nl = table.nl, n_oct = table.n_oct;
     const unsigned int cand_cap = (unsigned int)std::min<size_t>(
         params->max_features > 0 ? (size_t)params->max_features : std::max<size_t>((size_t)H * W / 2, 65536), 1u << 26);
     unsigned int cells_cap = (unsigned int)std::min<size_t>(std::max<size_t>((size_t)H * W / 2, 1u << 18), 1u << 27);
     Ws<unsigned long long> cells(cells_cap);
-    Ws<KpRec> recs(cand_cap);
+    recs.alloc(cand_cap);
     Ws<unsigned int> d_count(2);  // [0] cells, [1] refined records
     const float thr = (float)(int)std::floor(0.5 * params->contrast_threshold / nl * 255.0);
-    unsigned int h_counts[2] = {0, 0};
+    unsigned int n_cells = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         APS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), stream()));
         // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
@@ -1603,206 +1522,124 @@ static void sift_chain(const uint8_t* img, int height, int width, int channels, 
         if (run > 0) {
             Prof prof("sift_extrema");
             const int wgs = cdiv(run, 4);
-            auto launch_sweep = [&](unsigned long long* cl, unsigned int* ct) {
-                switch (nl) {
-                    case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                    case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                    case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                    case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                    default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(d_table, plan, thr, cl, ct, cells_cap); break;
-                }
-            };
-            launch_sweep(cells, d_count);
-            check_launch("extrema_wave_kernel");
-#ifdef APS_DBG
-            if (dbg_replay > 0) {
-                Ws<unsigned long long> cells2(cells_cap);
-                Ws<unsigned int> cnt2(2);
-                unsigned int n1 = 0, n2 = 0;
-                APS_HIP(hipMemcpyAsync(&n1, d_count, 4, hipMemcpyDeviceToHost, stream()));
-                APS_HIP(hipStreamSynchronize(stream()));
-                const unsigned long long c1 = dbg::cks(cells.get(), std::min(n1, cells_cap), 2, 0, dbg_slot);
-                for (int rep = 0; rep < dbg_replay; ++rep) {
-                    APS_HIP(hipMemsetAsync(cnt2, 0, 8, stream()));
-                    launch_sweep(cells2, cnt2);
-                    APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
-                    APS_HIP(hipStreamSynchronize(stream()));
-                    const unsigned long long c2 = dbg::cks(cells2.get(), std::min(n2, cells_cap), 2, 0, dbg_slot);
-                    dbg::g_stat[dbg::kExtReplays]++;
-                    if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kExtDiff]++;
-                }
+            switch (nl) {
+                case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
+                case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
+                case 3: extrema_wave_kernel<3><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
+                case 4: extrema_wave_kernel<4><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
+                default: extrema_wave_kernel<5><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
             }
-#endif
+            check_launch("extrema_wave_kernel");
         }
-        APS_HIP(hipMemcpyAsync(h_counts, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        if (h_counts[0] <= cells_cap) break;
+        n_cells = read_back(d_count.get());
+        if (n_cells <= cells_cap) break;
         // flat or band-limited images can have far more (weak) scale-space extrema than the default room:
         // grow to the exact need and sweep once more
         APS_REQUIRE(attempt == 0, APS_E_INTERNAL, "extrema count changed between identical sweeps");
-        cells_cap = h_counts[0];
+        cells_cap = n_cells;
         cells.alloc(cells_cap);
     }
-    if (h_counts[0] > 0) {
+    if (n_cells > 0) {
         Prof prof("sift_refine");
-        refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap,
+        refine_kernel<<<cdiv(n_cells, 256), 256, 0, stream()>>>(P.d_table, cells, d_count, cells_cap,
                                                                  (float)params->contrast_threshold,
                                                                  (float)params->edge_threshold, recs, d_count.get() + 1,
                                                                  cand_cap);
         check_launch("refine_kernel");
-#ifdef APS_DBG
-        if (dbg_replay > 0) {
-            Ws<KpRec> recs2(cand_cap);
-            Ws<unsigned int> cnt2(1);
-            unsigned int n1 = 0, n2 = 0;
-            APS_HIP(hipMemcpyAsync(&n1, d_count.get() + 1, 4, hipMemcpyDeviceToHost, stream()));
-            APS_HIP(hipStreamSynchronize(stream()));
-            const unsigned long long c1 = dbg::cks(recs.get(), std::min(n1, cand_cap), 6, 0, dbg_slot);
-            for (int rep = 0; rep < dbg_replay; ++rep) {
-                APS_HIP(hipMemsetAsync(cnt2, 0, 4, stream()));
-                refine_kernel<<<cdiv(h_counts[0], 256), 256, 0, stream()>>>(d_table, cells, d_count, cells_cap, (float)params->contrast_threshold,
-                                                                         (float)params->edge_threshold, recs2, cnt2, cand_cap);
-                APS_HIP(hipMemcpyAsync(&n2, cnt2, 4, hipMemcpyDeviceToHost, stream()));
-                APS_HIP(hipStreamSynchronize(stream()));
-                const unsigned long long c2 = dbg::cks(recs2.get(), std::min(n2, cand_cap), 6, 0, dbg_slot);
-                dbg::g_stat[dbg::kRefReplays]++;
-                if (n1 != n2 || c1 != c2) dbg::g_stat[dbg::kRefDiff]++;
-            }
-        }
-#endif
     }
-    unsigned int n_cand = 0;
-    APS_HIP(hipMemcpyAsync(&n_cand, d_count.get() + 1, sizeof n_cand, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n_cand = read_back(d_count.get() + 1);
     if (n_cand > cand_cap)
         fail(APS_E_CAP, "SIFT found %u extrema, more than the candidate capacity %u (raise params.max_features)", n_cand, cand_cap);
-    if (n_cand == 0) return;
-    // canonical order + dedupe
+    return n_cand;
+}
+
+// canonical order + dedupe: recs[0 .. n_cand - 1], n_cand > 0 -> kps, sorted by the 44-bit key with one record per key.  Returns
+// their number after one read-back.
+static unsigned int canonical_keypoints(const Ws<KpRec>& recs, unsigned int n_cand, Ws<KpRec>& kps) {
     Ws<unsigned long long> keys(n_cand), keys_s(n_cand);
     Ws<unsigned int> idx(n_cand), idx_s(n_cand), flag(n_cand), pos(n_cand);
     rec_keys_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, n_cand, keys, idx);
-    size_t tb = 0;
-    APS_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
-    Ws<char> tmp(tb);
-    APS_HIP(rocprim::radix_sort_pairs(tmp.get(), tb, keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 0, 44, stream()));
+    sort_pairs<unsigned int>(keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 44u);
     unique_flag_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(keys_s, n_cand, flag);
-    size_t tb2 = 0;
-    APS_HIP(rocprim::exclusive_scan(nullptr, tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
-    Ws<char> tmp2(tb2);
-    APS_HIP(rocprim::exclusive_scan(tmp2.get(), tb2, flag.get(), pos.get(), 0u, n_cand, rocprim::plus<unsigned int>(), stream()));
-    unsigned int last_pos = 0, last_flag = 0;
-    APS_HIP(hipMemcpyAsync(&last_pos, pos.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipMemcpyAsync(&last_flag, flag.get() + n_cand - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    const unsigned int n_kp = last_pos + last_flag;
-    Ws<KpRec> kps(n_kp);
+    exclusive_scan(flag.get(), pos.get(), 0u, n_cand);
+    const unsigned int n_kp = scan_total(pos.get(), flag.get(), n_cand);
+    kps.alloc(n_kp);
     compact_recs_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, idx_s, flag, pos, n_cand, kps);
     check_launch("compact_recs_kernel");
-    // orientations
-    Ws<unsigned int> ocount(n_kp), opos(n_kp);
-    Ws<float> oangle((size_t)n_kp * kOriBins);
+    return n_kp;
+}
+
+// The orientations of the keypoints: ocount[i] of them for keypoint i, their angles in oangle[i * kOriBins ..], and opos, the
+// exclusive scan of ocount = the first output row of keypoint i.
+struct Orientations {
+    Ws<unsigned int> ocount, opos;
+    Ws<float> oangle;
+};
+
+// kps[0 .. n_kp - 1], n_kp > 0 -> their orientations.  Returns the number of oriented keypoints after one read-back.
+static unsigned int orient_keypoints(const Pyramid& P, const Ws<KpRec>& kps, unsigned int n_kp, Orientations& O) {
+    O.ocount.alloc(n_kp);
+    O.opos.alloc(n_kp);
+    O.oangle.alloc((size_t)n_kp * kOriBins);
     Ws<unsigned char> obin((size_t)n_kp * kOriBins);
-#ifdef APS_DBG
-    if (dbg_replay > 0) {
-        APS_HIP(hipMemsetAsync(oangle, 0, (size_t)n_kp * kOriBins * 4, stream()));
-        APS_HIP(hipMemsetAsync(obin, 0, (size_t)n_kp * kOriBins, stream()));
-    }
-#endif
     {
         Prof prof("sift_orient");
-        orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount, oangle, obin);
+        orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(P.d_table, kps, n_kp, O.ocount, O.oangle, obin);
     }
     check_launch("orient_kernel");
-#ifdef APS_DBG
-    if (dbg_replay > 0) {
-        Ws<unsigned int> ocount2(n_kp);
-        Ws<float> oangle2((size_t)n_kp * kOriBins);
-        Ws<unsigned char> obin2(((size_t)n_kp * kOriBins + 3) & ~(size_t)3);
-        for (int rep = 0; rep < dbg_replay; ++rep) {
-            APS_HIP(hipMemsetAsync(oangle2, 0, (size_t)n_kp * kOriBins * 4, stream()));
-            APS_HIP(hipMemsetAsync(obin2, 0, (size_t)n_kp * kOriBins, stream()));
-            orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(d_table, kps, n_kp, ocount2, oangle2, obin2);
-            const unsigned long long d = dbg::diff(ocount.get(), ocount2.get(), n_kp, dbg_slot) +
-                                         dbg::diff(oangle.get(), oangle2.get(), (size_t)n_kp * kOriBins, dbg_slot) +
-                                         dbg::diff(obin.get(), obin2.get(), (size_t)n_kp * kOriBins / 4, dbg_slot);
-            dbg::g_stat[dbg::kOriReplays]++;
-            if (d) dbg::g_stat[dbg::kOriDiff]++;
-            dbg::g_stat[dbg::kOriWords] += (long long)d;
-        }
+    exclusive_scan(O.ocount.get(), O.opos.get(), 0u, n_kp);
+    return scan_total(O.opos.get(), O.ocount.get(), n_kp);
+}
+
+// The n_out <= n_all rows to describe, in canonical order: all n_all oriented keypoints, or with n_out < n_all the ones that come
+// first by (contrast descending, canonical index ascending) - over the whole image, or with grid_rows > 0 within their cell of the
+// grid_rows x grid_cols grid over the H x W image, the cells' shares by water-filling n_out.  No read-back.
+static Ws<OrientedKp> select_rows(const Ws<KpRec>& kps, unsigned int n_kp, const Orientations& O, unsigned int n_all, unsigned int n_out,
+                                  int H, int W, int grid_rows, int grid_cols) {
+    Ws<OrientedKp> oks_all(n_all);
+    expand_oriented_kernel<<<cdiv(n_kp, 256), 256, 0, stream()>>>(O.ocount, O.opos, O.oangle, n_kp, oks_all);
+    check_launch("expand_oriented_kernel");
+    if (n_out == n_all) return oks_all;
+    Prof prof("sift_select");
+    Ws<unsigned long long> skeys(n_all), words;
+    Ws<unsigned int> svals(n_all), sprefix;
+    unsigned int n_words = 0;
+    if (grid_rows > 0) {
+        sift_uniform_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, H, W, grid_rows, grid_cols, skeys, svals);
+        check_launch("sift_uniform_key_kernel");
+        UniformBudget budget = {};
+        budget.q[0] = n_out;
+        select_uniform(skeys, nullptr, svals, n_all, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, sprefix, n_words);
+    } else {
+        sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
+        check_launch("sift_contr_key_kernel");
+        select_by_key(skeys, svals, n_all, single_group_cut(n_all, n_out), words, sprefix, n_words, 32u);
     }
-#endif
-    size_t tb3 = 0;
-    APS_HIP(rocprim::exclusive_scan(nullptr, tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
-    Ws<char> tmp3(tb3);
-    APS_HIP(rocprim::exclusive_scan(tmp3.get(), tb3, ocount.get(), opos.get(), 0u, n_kp, rocprim::plus<unsigned int>(), stream()));
-    unsigned int lp = 0, lc = 0;
-    APS_HIP(hipMemcpyAsync(&lp, opos.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipMemcpyAsync(&lc, ocount.get() + n_kp - 1, sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    const unsigned int n_all = lp + lc;  // the oriented keypoints: the rows of the call without n_strongest
-    const unsigned int n_out = n_strongest > 0 ? (unsigned int)std::min<long long>(n_all, n_strongest) : n_all;
-    *count = n_out;
-    if ((int64_t)n_out > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n_out);
-    if (n_out == 0) return;
+    Ws<OrientedKp> oks_sel(n_out);
+    select_compact_kernel<OrientedKp><<<cdiv(n_words, 256), 256, 0, stream()>>>(words, sprefix, n_words, oks_all, n_all, oks_sel, n_out);
+    check_launch("select_compact_kernel");
+    return oks_sel;
+}
+
+// oks[0 .. n_out - 1], n_out > 0 -> the caller's desc, loc and aux.  The checks of the output arguments come before any write; the
+// strided copy-back leaves the elements between the logical rows / columns (ldd, ldl beyond the count) the caller's.
+static void describe(const Pyramid& P, const Ws<KpRec>& kps, const Ws<OrientedKp>& oks, unsigned int n_out, float* desc, int desc_layout,
+                     int64_t ldd, double* loc, int64_t ldl, float* aux) {
     APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
     if (desc_layout == APS_ROWMAJOR)
         APS_REQUIRE(ldd >= 128, APS_E_DIM, "ldd < 128");
     else
         APS_REQUIRE(ldd >= n_out, APS_E_DIM, "ldd < count");
     APS_REQUIRE(ldl >= n_out, APS_E_DIM, "ldl < count");
-    Ws<OrientedKp> oks_all(n_all), oks_sel;
-    expand_oriented_kernel<<<cdiv(n_kp, 256), 256, 0, stream()>>>(ocount, opos, oangle, n_kp, oks_all);
-    check_launch("expand_oriented_kernel");
-    const OrientedKp* oks = oks_all;
-    if (n_out < n_all) {
-        // strongest-N: the n_out rows that come first by (contrast descending, canonical index ascending), in canonical order
-        Prof prof("sift_select");
-        Ws<unsigned long long> skeys(n_all), words;
-        Ws<unsigned int> svals(n_all), sprefix;
-        unsigned int n_words = 0;
-        if (grid_rows > 0) {  // uniform-N: the rows that come first in their cell, the cells' shares by water-filling n_out
-            sift_uniform_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, H, W, grid_rows, grid_cols, skeys, svals);
-            check_launch("sift_uniform_key_kernel");
-            UniformBudget budget = {};
-            budget.q[0] = n_out;
-            select_uniform(skeys, nullptr, svals, n_all, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, sprefix, n_words);
-        } else {
-            sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
-            check_launch("sift_contr_key_kernel");
-            select_by_key(skeys, svals, n_all, single_group_cut(n_all, n_out), words, sprefix, n_words, 32u);
-        }
-        oks_sel.alloc(n_out);
-        sift_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, sprefix, n_words, oks_all, n_all, oks_sel, n_out);
-        check_launch("sift_select_compact_kernel");
-        oks = oks_sel;
-    }
     const size_t desc_elems = desc_layout == APS_ROWMAJOR ? (size_t)(n_out - 1) * ldd + 128 : (size_t)127 * ldd + n_out;
     Out<float> odesc(desc, desc_elems), oaux(aux, (size_t)n_out * 4);
     Out<double> oloc(loc, (size_t)ldl + n_out);
     {
         Prof prof("sift_descr");
-        descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
+        descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(P.d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
                                                            oaux.present() ? oaux.get() : nullptr);
     }
     check_launch("descr_kernel");
-#ifdef APS_DBG
-    if (dbg_replay > 0 && desc_layout == APS_ROWMAJOR && ldd == 128) {
-        Ws<float> desc2((size_t)n_out * 128), aux2((size_t)n_out * 4);
-        Ws<double> loc2((size_t)2 * n_out);
-        for (int rep = 0; rep < dbg_replay; ++rep) {
-            descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(d_table, kps, oks, n_out, desc2, desc_layout, 128, loc2, n_out,
-                                                               oaux.present() ? aux2.get() : nullptr);
-            unsigned long long d = dbg::diff(odesc.get(), desc2.get(), (size_t)n_out * 128, dbg_slot) +
-                                   dbg::diff(oloc.get(), loc2.get(), (size_t)2 * n_out, dbg_slot) +
-                                   dbg::diff(oloc.get() + ldl, loc2.get() + n_out, (size_t)2 * n_out, dbg_slot);
-            if (oaux.present()) d += dbg::diff(oaux.get(), aux2.get(), (size_t)n_out * 4, dbg_slot);
-            dbg::g_stat[dbg::kDesReplays]++;
-            if (d) dbg::g_stat[dbg::kDesDiff]++;
-            dbg::g_stat[dbg::kDesWords] += (long long)d;
-        }
-    }
-#endif
-    // strided copy-back: the elements between the logical rows / columns (ldd, ldl beyond the count) stay the caller's
     if (desc_layout == APS_ROWMAJOR)
         odesc.commit_2d(128, n_out, (size_t)ldd);
     else
@@ -1810,6 +1647,39 @@ static void sift_chain(const uint8_t* img, int height, int width, int channels, 
     oloc.commit_2d(n_out, 2, (size_t)ldl);
     oaux.commit();
     APS_HIP(hipStreamSynchronize(stream()));
+}
+
+}  // namespace aps
+
+using namespace aps;
+
+// aps_sift_extract (n_strongest = 0: every row) and aps_sift_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF": the
+// n_strongest rows of largest contrast) behind one body; with grid_rows > 0 the n_strongest rows are spread over the cells of a
+// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").
+static void sift_chain(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
+                       long long n_strongest, int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc,
+                       int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    check_sift_args(img, height, width, channels, img_layout, params, desc_layout, cap, count);
+    ctx();
+    *count = 0;
+    const int H = height, W = width;
+    In<uint8_t> dimg(img, (size_t)H * W * channels);
+    const int n_oct = std::min(num_octaves(H, W), 16);
+    if (n_oct <= 0) return;
+    Pyramid pyr;
+    build_pyramid(dimg, H, W, channels, img_layout, params, n_oct, pyr);
+    Ws<KpRec> recs, kps;
+    const unsigned int n_cand = detect_candidates(pyr, params, H, W, recs);
+    if (n_cand == 0) return;
+    const unsigned int n_kp = canonical_keypoints(recs, n_cand, kps);
+    Orientations ori;
+    const unsigned int n_all = orient_keypoints(pyr, kps, n_kp, ori);  // the rows of the call without n_strongest
+    const unsigned int n_out = n_strongest > 0 ? (unsigned int)std::min<long long>(n_all, n_strongest) : n_all;
+    *count = n_out;
+    if ((int64_t)n_out > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n_out);
+    if (n_out == 0) return;
+    const Ws<OrientedKp> oks = select_rows(kps, n_kp, ori, n_all, n_out, H, W, grid_rows, grid_cols);
+    describe(pyr, kps, oks, n_out, desc, desc_layout, ldd, loc, ldl, aux);
 }
 
 extern "C" {
@@ -1844,21 +1714,3 @@ int aps_sift_extract_uniform(const uint8_t* img, int height, int width, int chan
 
 }  // extern "C"
 
-#ifdef APS_DBG
-// (debug library only) the counters of the replay experiment as text; reset = 1 clears them and the pyramid checksums
-extern "C" int aps_dbg_replay_report(char* buf, int cap, int reset) {
-    using namespace aps::dbg;
-    static const char* names[kNStat] = {"pyramid_changed", "extrema_replays", "extrema_diff", "refine_replays", "refine_diff", "orient_replays",
-                                        "orient_diff", "orient_words", "descr_replays", "descr_diff", "descr_words", "calls"};
-    int n = 0;
-    for (int i = 0; i < kNStat && n < cap; ++i) n += std::snprintf(buf + n, (size_t)(cap - n), "%s=%lld ", names[i], (long long)g_stat[i].load());
-    if (reset) {
-        for (int i = 0; i < kNStat; ++i) g_stat[i] = 0;
-        if (reset > 1) {
-            std::lock_guard<std::mutex> lk(g_mu);
-            g_pyr.clear();
-        }
-    }
-    return 0;
-}
-#endif

@@ -18,7 +18,7 @@
 // back, and goes on with grids of the candidates' size:
 //   surf_emit_kernel      the candidate list
 //   surf_metric_kernel    the centre response of every candidate = its metric, as the sort key
-//   select_by_key         (select_dev.h) stable radix sort, flags, ballot words, scan; surf_select_compact_kernel (canonical order again)
+//   select_by_key         (select_dev.h) stable radix sort, flags, ballot words, scan; select_compact_kernel (canonical order again)
 //   surf_keypoint_kernel  on the kept keypoints only
 // aps_surf_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with surf_uniform_key_kernel and select_uniform in the place
 // of surf_metric_kernel and select_by_key.
@@ -31,8 +31,6 @@
 #include "aps_internal.h"
 #include "integral_dev.h"
 #include "select_dev.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace aps {
 namespace {
@@ -368,23 +366,6 @@ __global__ __launch_bounds__(256) void surf_uniform_key_kernel(const uint32_t* _
     vals[i] = i;
 }
 
-// Ordered compaction of the flagged candidates, as surf_emit_kernel's: canonical order is kept.
-__global__ __launch_bounds__(256) void surf_select_compact_kernel(const unsigned long long* __restrict__ words,
-                                                                  const unsigned int* __restrict__ prefix, unsigned int n_words,
-                                                                  const int4* __restrict__ cand, unsigned int n, int4* __restrict__ kps,
-                                                                  unsigned int kcap) {
-    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n_words) return;
-    unsigned long long bits = words[q];
-    unsigned int pos = prefix[q];
-    while (bits) {
-        const int k = __ffsll((long long)bits) - 1;
-        bits &= bits - 1;
-        if (pos < kcap && q * 64 + k < n) kps[pos] = cand[q * 64 + k];
-        ++pos;
-    }
-}
-
 // the checks of aps_surf_extract, which come before any device work
 void check_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_surf_params* params, int desc_layout,
                 int64_t cap, const int64_t* count) {
@@ -461,11 +442,7 @@ bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, 
         }
         check_launch("surf_detect_kernel");
     }
-    auto counts = rocprim::make_transform_iterator(F.bitmap.get(), PopcOp());
-    size_t tbytes = 0;
-    APS_HIP(rocprim::exclusive_scan(nullptr, tbytes, counts, F.prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
-    Ws<char> tmp(tbytes);
-    APS_HIP(rocprim::exclusive_scan(tmp.get(), tbytes, counts, F.prefix.get(), 0u, (size_t)n_words + 1, rocprim::plus<unsigned int>(), stream()));
+    exclusive_scan(popcounts(F.bitmap.get()), F.prefix.get(), 0u, (size_t)n_words + 1);
     return true;
 }
 
@@ -477,9 +454,7 @@ void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int im
     *count = 0;
     SurfFront F;
     if (!surf_front(img, H, W, channels, img_layout, params, F)) return;
-    unsigned int M = 0;  // the first read-back: the candidates
-    APS_HIP(hipMemcpyAsync(&M, F.d_total(), sizeof M, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int M = read_back(F.d_total());  // the first read-back: the candidates
     const unsigned int K = (unsigned int)std::min<long long>(M, N);
     *count = K;
     if (params->max_features > 0 && M > (unsigned int)params->max_features) {
@@ -519,8 +494,8 @@ void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int im
             select_by_key(keys, vals, M, single_group_cut(M, K), words, prefix, n_words, 32u);
         }
         sel.alloc(K);
-        surf_select_compact_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, M, sel, K);
-        check_launch("surf_select_compact_kernel");
+        select_compact_kernel<int4><<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, M, sel, K);
+        check_launch("select_compact_kernel");
         kps = sel;
         d_total = prefix.get() + n_words;
     }
@@ -536,9 +511,7 @@ void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int im
                                                               (long long)ldd, oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
     }
     check_launch("surf_keypoint_kernel");
-    unsigned int n = 0;  // the second read-back: the count the device kept is the count the host worked out
-    APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    const unsigned int n = read_back(d_total);  // the second read-back: the count the device kept is the count the host worked out
     APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
     if (desc_layout == APS_ROWMAJOR)
         odesc.commit_2d(dwidth, K, (size_t)ldd);
@@ -598,9 +571,7 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
             }
             check_launch("surf_keypoint_kernel");
         }
-        unsigned int n = 0;  // the one read-back of the chain
-        APS_HIP(hipMemcpyAsync(&n, d_total, sizeof n, hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
+        const unsigned int n = read_back(d_total);  // the one read-back of the chain
         *count = n;
         if (params->max_features > 0 && n > (unsigned int)params->max_features)
             fail(APS_E_CAP, "SURF found %u features, more than params.max_features = %d", n, params->max_features);
