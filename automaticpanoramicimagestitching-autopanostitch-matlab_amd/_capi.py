@@ -78,6 +78,14 @@ class aps_sift_params(C.Structure):
                 ("edge_threshold", C.c_double), ("max_features", C.c_int)]
 
 
+APS_SIFT_MAX_VIEWS = 16
+
+
+class aps_sift_view(C.Structure):
+    _fields_ = [("img", C.c_void_p), ("desc", C.c_void_p), ("loc", C.c_void_p), ("aux", C.c_void_p),
+                ("cap", C.c_int64), ("count", C.c_int64)]
+
+
 class aps_surf_params(C.Structure):
     _fields_ = [("metric_threshold", C.c_double), ("n_octaves", C.c_int), ("n_scale_levels", C.c_int),
                 ("upright", C.c_int), ("max_features", C.c_int)]
@@ -203,6 +211,7 @@ _SIGNATURES = {
     "aps_synth_view": [_vp, _vp, _i, _i, C.c_uint, _f, _f, _vp],
     "aps_sift_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_sift_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
+    "aps_sift_extract_batch": [C.POINTER(aps_sift_view), _i, _i, _i, _i, _i, C.POINTER(aps_sift_params), _i, _i64, _i64],
     "aps_surf_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
     "aps_fast_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_params), _vp, _i, _i64, _vp, _i64,

@@ -6,8 +6,12 @@
 // Gaussians, 2^-20 fixed-point histograms, polynomial exp/atan2/sincos) so that this path and the oracle
 // agree bit for bit.
 //
+// A call works on a group of 1 .. 16 views of one shape (aps_sift_extract_batch; the single-view entries are groups of one): every
+// stage below runs once for the group, the pyramid kernels with the view as blockIdx.z over slabs of the views' planes, the sweep and
+// the refinement with the view as blockIdx.y, the per-keypoint kernels over the group's keypoints, whose records carry their view.
+//
 // Kernels
-//   gray_up_kernel                 : uint8 (HWC or MATLAB planar) -> f32 gray (LDS only) -> 2x bilinear base.
+//   gray_up_kernel                : uint8 (HWC or MATLAB planar) -> f32 gray (LDS only) -> 2x bilinear base.
 //   blur_kernel<R>                 : separable Gaussian, row pass then column pass fused through an LDS
 //                                    tile (reflect-101 border), both passes on v_pk_fma_f32; the blur of plane
 //                                    nl also writes the next octave's base (every second pixel) from registers.
@@ -41,6 +45,16 @@ constexpr float kFix = 1048576.0f;
 // the same integer as the generic f32 -> i64 sequence (a dozen VALU instructions, eight times per sample).
 __device__ __forceinline__ long long to_fix(float v) { return (long long)(int)rintf(v * kFix); }
 constexpr float kFltEps = 1.1920928955078125e-07f;
+
+// A call extracts a group of 1 .. kMaxViews views of one shape (aps_sift_extract_batch; aps_sift_extract is a group of one).  Every
+// plane of the pyramid is a slab of the group's planes at a fixed pitch, the kernels of the pyramid take the view as blockIdx.z,
+// the sweep and the refinement as blockIdx.y, and a keypoint record carries its view above the 44 bits of its canonical key.
+constexpr int kMaxViews = APS_SIFT_MAX_VIEWS;
+constexpr int kViewShift = 44;
+static_assert(kMaxViews <= 16, "the view takes 4 bits of the key");
+struct ViewImgs {
+    const uint8_t* p[kMaxViews];  // the views' source images, on the device
+};
 
 // ---- elementary functions (identical formulas to oracle/sift_oracle.c) --------------------------
 __device__ __forceinline__ float poly_exp2(float f) {
@@ -125,8 +139,10 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 // Gray conversion and 2x bilinear base in one pass: the gray values of a tile's footprint are computed into LDS and the
 // doubled tile is interpolated from there (same expressions, so the same bits); the gray plane is never stored.
 constexpr int kGUW = 128, kGUH = 16;  // output tile per 256-thread workgroup
-__global__ __launch_bounds__(256) void gray_up_kernel(const uint8_t* __restrict__ img, int h, int w, int c, int layout,
-                                                      float* __restrict__ out) {
+__global__ __launch_bounds__(256) void gray_up_kernel(ViewImgs imgs, int h, int w, int c, int layout,
+                                                      float* __restrict__ out_, size_t pitch) {
+    const uint8_t* __restrict__ img = imgs.p[blockIdx.z];
+    float* __restrict__ out = out_ + blockIdx.z * pitch;
     constexpr int GW = kGUW / 2 + 2, GH = kGUH / 2 + 2;
     __shared__ float s_g[GH][GW + 1];
     const int x0 = blockIdx.x * kGUW, y0 = blockIdx.y * kGUH;
@@ -198,8 +214,10 @@ __global__ __launch_bounds__(256) void gray_up_kernel(const uint8_t* __restrict_
     }
 }
 
-__global__ void decimate_kernel(const float* __restrict__ in, int h, int w, int oh, int ow,
-                                float* __restrict__ out) {
+__global__ void decimate_kernel(const float* __restrict__ in_, int h, int w, size_t pitch, int oh, int ow,
+                                float* __restrict__ out_, size_t opitch) {
+    const float* __restrict__ in = in_ + blockIdx.z * pitch;
+    float* __restrict__ out = out_ + blockIdx.z * opitch;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= ow) return;
     out[(size_t)y * ow + x] = in[(size_t)min(2 * y, h - 1) * w + min(2 * x, w - 1)];
@@ -315,8 +333,13 @@ __device__ __forceinline__ void blur_tile_passes(const float* s_in, float* s_row
 }
 
 template <int R, int TW = kTW, int NT = 256>
-__global__ __launch_bounds__(NT) void blur_kernel(const float* __restrict__ in, int h, int w, GaussK gk,
-                                                   float* __restrict__ out, float* __restrict__ dec, int dh, int dw) {
+__global__ __launch_bounds__(NT) void blur_kernel(const float* __restrict__ in_, int h, int w, GaussK gk,
+                                                   float* __restrict__ out_, float* __restrict__ dec_, int dh, int dw,
+                                                   size_t pitch, size_t dpitch) {
+    // the view's planes of the three slabs (pitch, dpitch: multiples of four floats, so a view's plane is aligned as the slab is)
+    const float* __restrict__ in = in_ + blockIdx.z * pitch;
+    float* __restrict__ out = out_ + blockIdx.z * pitch;
+    float* __restrict__ dec = dec_ ? dec_ + blockIdx.z * dpitch : nullptr;
     // dec (optional): the next octave's base plane, out(2y, 2x) for y < dh, x < dw - written from the registers that
     // hold the result instead of by a decimation pass that re-reads the plane.
     // The haloed input tile is fetched in 16-byte pieces: the horizontal halo is rounded up to a multiple of four
@@ -401,8 +424,10 @@ __global__ __launch_bounds__(NT) void blur_kernel(const float* __restrict__ in, 
 // itself - 936 footprint pixels for 512 source pixels, three byte loads and the f64 arithmetic each, a quarter of the
 // kernel's vector instructions; now the conversion runs once per source pixel (25 MB read, 8 MB written per 4K view) and
 // the tiles read bytes.
-__global__ __launch_bounds__(256) void gray_u8_kernel(const uint8_t* __restrict__ img, int h, int w, int c, int layout,
-                                                      uint8_t* __restrict__ gray) {
+__global__ __launch_bounds__(256) void gray_u8_kernel(ViewImgs imgs, int h, int w, int c, int layout,
+                                                      uint8_t* __restrict__ gray_, size_t gpitch) {
+    const uint8_t* __restrict__ img = imgs.p[blockIdx.z];
+    uint8_t* __restrict__ gray = gray_ + blockIdx.z * gpitch;
     const int x4 = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y;
     if (x4 >= w) return;
     uint8_t g[4];
@@ -442,8 +467,10 @@ __global__ __launch_bounds__(256) void gray_u8_kernel(const uint8_t* __restrict_
 // the tile's footprint (computed into LDS first); neither the gray plane nor the doubled plane is ever stored - a 4K view
 // saves the 133 MB write of gray_up_kernel and the 133 MB read of the blur.  img is sh x sw; the output plane 2sh x 2sw.
 template <int R>
-__global__ __launch_bounds__(256) void blur_base_kernel(const uint8_t* __restrict__ gray, int sh, int sw,
-                                                        GaussK gk, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void blur_base_kernel(const uint8_t* __restrict__ gray_, size_t gpitch, int sh, int sw,
+                                                        GaussK gk, float* __restrict__ out_, size_t pitch) {
+    const uint8_t* __restrict__ gray = gray_ + blockIdx.z * gpitch;
+    float* __restrict__ out = out_ + blockIdx.z * pitch;
     constexpr int RP = (R + 3) & ~3;
     constexpr int IW = kTW + 2 * RP, IH = kTH + 2 * R, NV = IW / 4;
     constexpr int IP2 = 2 * IW + 4;
@@ -521,7 +548,9 @@ __global__ __launch_bounds__(256) void blur_base_kernel(const uint8_t* __restric
 }
 
 // generic fallback for unusual radii: two plain passes through global memory (same arithmetic)
-__global__ void blur_row_generic(const float* __restrict__ in, int h, int w, GaussK gk, float* __restrict__ out) {
+__global__ void blur_row_generic(const float* __restrict__ in_, int h, int w, GaussK gk, float* __restrict__ out_, size_t pitch) {
+    const float* __restrict__ in = in_ + blockIdx.z * pitch;
+    float* __restrict__ out = out_ + blockIdx.z * pitch;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
     const int r = gk.n / 2;
@@ -529,7 +558,9 @@ __global__ void blur_row_generic(const float* __restrict__ in, int h, int w, Gau
     for (int t = 0; t < gk.n; ++t) acc = fmaf(gk.k[t], in[(size_t)y * w + reflect101(x + t - r, w)], acc);
     out[(size_t)y * w + x] = acc;
 }
-__global__ void blur_col_generic(const float* __restrict__ tmp, int h, int w, GaussK gk, float* __restrict__ out) {
+__global__ void blur_col_generic(const float* __restrict__ tmp_, int h, int w, GaussK gk, float* __restrict__ out_, size_t pitch) {
+    const float* __restrict__ tmp = tmp_ + blockIdx.z * pitch;
+    float* __restrict__ out = out_ + blockIdx.z * pitch;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
     const int r = gk.n / 2;
@@ -545,7 +576,7 @@ struct OctaveDesc {
 };
 
 struct KpRec {
-    unsigned long long key;  // (o << 40) | (layer << 32) | (r << 16) | c
+    unsigned long long key;  // (view << 44) | (o << 40) | (layer << 32) | (r << 16) | c
     float xc, xr, xi, contr;
 };
 
@@ -646,13 +677,29 @@ __device__ bool adjust_extremum(const OctaveDesc& od, int nl, int o, int layer, 
 }
 #undef AT
 
+__device__ __forceinline__ int key_view(unsigned long long key) { return (int)(key >> kViewShift); }
+__device__ __forceinline__ int key_octave(unsigned long long key) { return (int)((key >> 40) & 0xf); }
+
 // ---- sort / dedupe helpers ---------------------------------------------------------------------------
-__global__ void rec_keys_kernel(const KpRec* __restrict__ recs, unsigned int n, unsigned long long* __restrict__ keys,
+// The views' runs of a concatenated list: view v owns [off[v], off[v + 1]).
+struct Segments {
+    unsigned int off[kMaxViews + 1];
+};
+// recs: the views' records in segments of `pitch`; keys / idx: their concatenation (blockIdx.y = view)
+__global__ void rec_keys_kernel(const KpRec* __restrict__ recs, unsigned int pitch, Segments seg, unsigned long long* __restrict__ keys,
                                 unsigned int* __restrict__ idx) {
-    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = recs[i].key;
-    idx[i] = i;
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
+    if (i >= seg.off[v + 1] - seg.off[v]) return;
+    keys[seg.off[v] + i] = recs[(size_t)v * pitch + i].key;
+    idx[seg.off[v] + i] = v * pitch + i;
+}
+// ends[v] = the inclusive scan (pos + val) at the end of view v's run = the items of views 0 .. v
+__global__ void segment_ends_kernel(const unsigned int* __restrict__ pos, const unsigned int* __restrict__ val, Segments seg, int n_views,
+                                    unsigned int* __restrict__ ends) {
+    const int v = threadIdx.x;
+    if (v >= n_views) return;
+    const unsigned int e = seg.off[v + 1];
+    ends[v] = e == 0 ? 0u : pos[e - 1] + val[e - 1];
 }
 __global__ void unique_flag_kernel(const unsigned long long* __restrict__ keys, unsigned int n,
                                    unsigned int* __restrict__ flag) {
@@ -704,6 +751,7 @@ template <int nl>
 __global__ __launch_bounds__(256) void extrema_wave_kernel(const PyrTable* __restrict__ pt, ExtremaWavePlan plan, float thr,
                                                            unsigned long long* __restrict__ cells,
                                                            unsigned int* __restrict__ count, unsigned int cap) {
+    // cells: segments of cap per view; count: [view][0] the view's cells, [view][1] its refined records (refine_kernel)
     constexpr int NG = nl + 3, ND = nl + 2;
     __shared__ unsigned long long s_cells[4][kWCells];
     const int lane = threadIdx.x & 63;
@@ -712,7 +760,10 @@ __global__ __launch_bounds__(256) void extrema_wave_kernel(const PyrTable* __res
     if (job >= plan.job_ptr[16]) return;  // (whole waves leave: nothing below synchronises across waves)
     int o = 0;
     while (o < 15 && job >= plan.job_ptr[o + 1]) ++o;
-    const OctaveDesc& od = pt->oct[o];
+    // blockIdx.y: the view - its table, its segment of the cells and its pair of counters
+    const OctaveDesc& od = pt[blockIdx.y].oct[o];
+    cells += (size_t)blockIdx.y * cap;
+    count += 2 * blockIdx.y;
     const int w = od.w, h = od.h;
     const int local = job - plan.job_ptr[o];
     const int strip = local % plan.nstrip[o], chunk = local / plan.nstrip[o];
@@ -838,16 +889,18 @@ __global__ void refine_kernel(const PyrTable* __restrict__ pt, const unsigned lo
                               const unsigned int* __restrict__ n_cells, unsigned int cells_cap, float contr_thr,
                               float edge_thr, KpRec* __restrict__ recs, unsigned int* __restrict__ count,
                               unsigned int cap) {
-    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned int n = min(*n_cells, cells_cap);
+    // blockIdx.y: the view; n_cells / count are the view's pair of counters, cells / recs its segments of cells_cap / cap
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x, view = blockIdx.y;
+    const unsigned int n = min(n_cells[2 * view], cells_cap);
     if (i >= n) return;
-    const unsigned long long key = cells[i];
-    const int o = (int)(key >> 40), layer = (int)((key >> 32) & 0xff), r = (int)((key >> 16) & 0xffff),
+    const unsigned long long key = cells[(size_t)view * cells_cap + i];
+    const int o = key_octave(key), layer = (int)((key >> 32) & 0xff), r = (int)((key >> 16) & 0xffff),
               c = (int)(key & 0xffff);
     KpRec kp;
-    if (!adjust_extremum(pt->oct[o], pt->nl, o, layer, r, c, contr_thr, edge_thr, kp)) return;
-    const unsigned int slot = atomicAdd(count, 1u);
-    if (slot < cap) recs[slot] = kp;
+    if (!adjust_extremum(pt[view].oct[o], pt[view].nl, o, layer, r, c, contr_thr, edge_thr, kp)) return;
+    kp.key |= (unsigned long long)view << kViewShift;
+    const unsigned int slot = atomicAdd(count + 2 * view, 1u);
+    if (slot < cap) recs[(size_t)view * cap + slot] = kp;
 }
 
 __device__ __forceinline__ float kp_scale(float sigma, int layer, float xi, int nl) {
@@ -866,16 +919,18 @@ __global__ __launch_bounds__(256) void orient_kernel(const PyrTable* __restrict_
     const bool active = ki < n;
     if (lane < kOriBins) s_hist[wv][lane] = 0ull;
     __syncthreads();
-    int o = 0, layer = 1, r0 = 0, c0 = 0;
+    int o = 0, layer = 1, r0 = 0, c0 = 0, view = 0;
     float xi = 0;
     if (active) {
         const KpRec kp = kps[ki];
-        o = (int)(kp.key >> 40);
+        view = key_view(kp.key);
+        o = key_octave(kp.key);
         layer = (int)((kp.key >> 32) & 0xff);
         r0 = (int)((kp.key >> 16) & 0xffff);
         c0 = (int)(kp.key & 0xffff);
         xi = kp.xi;
     }
+    pt += view;
     const OctaveDesc& od = pt->oct[o];
     // (global address space stated explicitly: a pointer read from the pyramid table otherwise compiles to flat loads)
     const __attribute__((address_space(1))) float* g = (const __attribute__((address_space(1))) float*)od.G[layer];
@@ -992,7 +1047,7 @@ __global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __re
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const KpRec kp = kps[oks[i].kp];
-    const float step = octave_step((int)(kp.key >> 40));
+    const float step = octave_step(key_octave(kp.key));
     const double x = sift_loc(sift_pt((int)(kp.key & 0xffff), kp.xc), step), y = sift_loc(sift_pt((int)((kp.key >> 16) & 0xffff), kp.xr), step);
     const int px = min(max((int)floor(x) - 1, 0), W - 1), py = min(max((int)floor(y) - 1, 0), H - 1);
     keys[i] = (unsigned long long)uniform_cell(py, px, H, W, rows, cols) << kSegmentShift | strength_key_f32(kp.contr);
@@ -1000,15 +1055,20 @@ __global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __re
 }
 
 // ---- descriptor: one wave per oriented keypoint -------------------------------------------------------
+// Where the rows of a view go: the view's outputs and the first of its rows in the group's list of oriented keypoints.
+struct ViewDst {
+    float* desc;
+    double* loc;
+    float* aux;  // (may be NULL)
+    unsigned int row0;
+};
 constexpr int kD = 4, kN = 8, kHistLen = (kD + 2) * (kD + 2) * (kN + 2);  // 360
 constexpr int kDescQueue = 512;  // queued samples per wave between two strided passes over the queue
 
 __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__ pt,
                                                     const KpRec* __restrict__ kps,
                                                     const OrientedKp* __restrict__ oks, unsigned int n_out,
-                                                    float* __restrict__ desc, int desc_layout, int64_t ldd,
-                                                    double* __restrict__ loc, int64_t ldl,
-                                                    float* __restrict__ aux) {
+                                                    const ViewDst* __restrict__ dst, int desc_layout, int64_t ldd, int64_t ldl) {
     __shared__ unsigned long long s_hist[4][kHistLen];
     __shared__ __attribute__((aligned(16))) float s_raw[4][128];
     __shared__ int s_queue[4][kDescQueue];  // per wave: samples that passed the window test, (i << 16) | (j & 0xffff)
@@ -1017,12 +1077,13 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
     const bool active = oi < n_out;
     for (int e = lane; e < kHistLen; e += 64) s_hist[wv][e] = 0ull;
     __syncthreads();
-    int o = 0, layer = 1, r0 = 0, c0 = 0;
+    int o = 0, layer = 1, r0 = 0, c0 = 0, view = 0;
     float xc = 0, xr = 0, xi = 0, contr = 0, kangle = 0;
     if (active) {
         const OrientedKp ok = oks[oi];
         const KpRec kp = kps[ok.kp];
-        o = (int)(kp.key >> 40);
+        view = key_view(kp.key);
+        o = key_octave(kp.key);
         layer = (int)((kp.key >> 32) & 0xff);
         r0 = (int)((kp.key >> 16) & 0xffff);
         c0 = (int)(kp.key & 0xffff);
@@ -1032,6 +1093,7 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
         contr = kp.contr;
         kangle = ok.angle;
     }
+    pt += view;
     const OctaveDesc& od = pt->oct[o];
     // (global address space stated explicitly: a pointer read from the pyramid table otherwise compiles to flat loads)
     const __attribute__((address_space(1))) float* g = (const __attribute__((address_space(1))) float*)od.G[layer];
@@ -1269,24 +1331,28 @@ __global__ __launch_bounds__(256) void descr_kernel(const PyrTable* __restrict__
     __builtin_amdgcn_wave_barrier();
     const float qq = sumsq();
     const float inv = sqrtf(qq);
+    // the row within the view's outputs (global address space stated explicitly, as for the planes)
+    const ViewDst vd = dst[view];
+    const size_t row = oi - vd.row0;
+    __attribute__((address_space(1))) float* desc = (__attribute__((address_space(1))) float*)vd.desc;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const int e = lane + 64 * half;
         const float outv = inv > 0 ? qv[half] / inv : 0.0f;
         if (desc_layout == APS_ROWMAJOR)
-            desc[(size_t)oi * ldd + e] = outv;
+            desc[row * ldd + e] = outv;
         else
-            desc[(size_t)e * ldd + oi] = outv;
+            desc[(size_t)e * ldd + row] = outv;
     }
     if (lane == 0) {
         const float s = octave_step(o);
-        loc[oi] = sift_loc(ptx, s);
-        loc[ldl + oi] = sift_loc(pty, s);
-        if (aux) {
-            aux[(size_t)oi * 4 + 0] = scl * s * 2.0f;
-            aux[(size_t)oi * 4 + 1] = kangle;
-            aux[(size_t)oi * 4 + 2] = contr;
-            aux[(size_t)oi * 4 + 3] = (float)(o + 256 * layer);
+        vd.loc[row] = sift_loc(ptx, s);
+        vd.loc[ldl + row] = sift_loc(pty, s);
+        if (vd.aux) {
+            vd.aux[row * 4 + 0] = scl * s * 2.0f;
+            vd.aux[row * 4 + 1] = kangle;
+            vd.aux[row * 4 + 2] = contr;
+            vd.aux[row * 4 + 3] = (float)(o + 256 * layer);
         }
     }
 }
@@ -1309,14 +1375,20 @@ static GaussK make_gauss(double sigma) {
     return g;
 }
 
-// dec/dh/dw: optional half-resolution copy of the result (the next octave's base); returns false when the radius took the
-// generic path, which does not write it.
-static bool launch_blur(const float* in, int h, int w, double sigma, float* out, Ws<float>& scratch, float* dec = nullptr,
+// The floats between two views' planes of w x h pixels in a slab: a multiple of four, so that every view's plane starts on a
+// 16-byte boundary (blur_kernel's interior fast path).
+static size_t view_pitch(int w, int h) { return ((size_t)w * h + 3) & ~(size_t)3; }
+
+// One launch blurs the slab's nv planes (in, out: nv planes of h x w at view_pitch(w, h)).
+// dec/dh/dw: optional half-resolution copy of the result (the next octave's base, a slab at view_pitch(dw, dh)); returns false when
+// the radius took the generic path, which does not write it.
+static bool launch_blur(int nv, const float* in, int h, int w, double sigma, float* out, Ws<float>& scratch, float* dec = nullptr,
                         int dh = 0, int dw = 0) {
     const GaussK gk = make_gauss(sigma);
     const int r = gk.n / 2;
     Prof prof("sift_blur");
-    const dim3 grid(cdiv(w, kTW), cdiv(h, kTH));
+    const dim3 grid(cdiv(w, kTW), cdiv(h, kTH), nv);
+    const size_t pitch = view_pitch(w, h), dpitch = view_pitch(dw, dh);
     // (Measured and dropped, round 3: a marching form with a ring of row-filtered rows in LDS - bit-identical, 66 / 75 / 109 us
     // per 33 MPix plane at R = 4 / 5 / 10 against 60 / 60 / 83: profiles/r03f_sift_trace_march_blur.txt.)
     // (Measured and dropped, round 5: one wave per 128-column strip marching down its rows with the row-pass results of the last
@@ -1333,7 +1405,7 @@ static bool launch_blur(const float* in, int h, int w, double sigma, float* out,
     switch (r) {
 #define APS_BLUR_CASE(R) \
     case R:              \
-        blur_kernel<R><<<grid, 256, 0, stream()>>>(in, h, w, gk, out, dec, dh, dw); \
+        blur_kernel<R><<<grid, 256, 0, stream()>>>(in, h, w, gk, out, dec, dh, dw, pitch, dpitch); \
         break;
         APS_BLUR_CASE(1)
         APS_BLUR_CASE(2)
@@ -1349,9 +1421,9 @@ static bool launch_blur(const float* in, int h, int w, double sigma, float* out,
         APS_BLUR_CASE(12)
 #undef APS_BLUR_CASE
         default: {
-            if (scratch.n < (size_t)h * w) scratch.alloc((size_t)h * w);
-            blur_row_generic<<<dim3(cdiv(w, 256), h), 256, 0, stream()>>>(in, h, w, gk, scratch);
-            blur_col_generic<<<dim3(cdiv(w, 256), h), 256, 0, stream()>>>(scratch, h, w, gk, out);
+            if (scratch.n < nv * pitch) scratch.alloc(nv * pitch);
+            blur_row_generic<<<dim3(cdiv(w, 256), h, nv), 256, 0, stream()>>>(in, h, w, gk, scratch, pitch);
+            blur_col_generic<<<dim3(cdiv(w, 256), h, nv), 256, 0, stream()>>>(scratch, h, w, gk, out, pitch);
             dec = nullptr;
         }
     }
@@ -1361,18 +1433,19 @@ static bool launch_blur(const float* in, int h, int w, double sigma, float* out,
 
 // gray + 2x upsample + first blur in one kernel (blur_base_kernel); false when the radius has no tile instantiation (the
 // caller then takes gray_up_kernel + launch_blur, same bits).
-static bool launch_base_blur(const uint8_t* img, int sh, int sw, int c, int layout, double sigma, float* out, Ws<uint8_t>& gray) {
+static bool launch_base_blur(int nv, const ViewImgs& imgs, int sh, int sw, int c, int layout, double sigma, float* out, Ws<uint8_t>& gray) {
     const GaussK gk = make_gauss(sigma);
     const int r = (gk.n - 1) / 2;
     if (r < 3 || r > 8) return false;
-    const dim3 grid(cdiv(2 * sw, kTW), cdiv(2 * sh, kTH));
+    const dim3 grid(cdiv(2 * sw, kTW), cdiv(2 * sh, kTH), nv);
     Prof prof("sift_blur");
-    gray.alloc((size_t)sh * sw);
-    gray_u8_kernel<<<dim3(cdiv(cdiv(sw, 4), 256), sh), 256, 0, stream()>>>(img, sh, sw, c, layout, gray);
+    const size_t gpitch = ((size_t)sh * sw + 15) & ~(size_t)15;  // (the gray planes keep the dword alignment of gray_u8_kernel's stores)
+    gray.alloc(nv * gpitch);
+    gray_u8_kernel<<<dim3(cdiv(cdiv(sw, 4), 256), sh, nv), 256, 0, stream()>>>(imgs, sh, sw, c, layout, gray, gpitch);
     switch (r) {
 #define APS_BLUR_CASE(R) \
     case R:              \
-        blur_base_kernel<R><<<grid, 256, 0, stream()>>>(gray, sh, sw, gk, out); \
+        blur_base_kernel<R><<<grid, 256, 0, stream()>>>(gray, gpitch, sh, sw, gk, out, view_pitch(2 * sw, 2 * sh)); \
         break;
         APS_BLUR_CASE(3)
         APS_BLUR_CASE(4)
@@ -1393,13 +1466,17 @@ static int num_octaves(int H, int W) {
 }
 
 // ---- the stages of sift_chain, in the order they run on the calling thread's stream ---------------------------------------
-// What a stage's later launches read, it returns and the caller keeps; what only the stage needs goes back to the workspace when it
-// returns (the workspace hands a thread's blocks out again in the order of that thread's one stream).
+// Every stage works on the call's group of nv views at once: one launch per stage (per plane for the blurs) and one read-back of
+// nv counts where a count is needed on the host.  What a stage's later launches read, it returns and the caller keeps; what only
+// the stage needs goes back to the workspace when it returns (the workspace hands a thread's blocks out again in the order of that
+// thread's one stream).
 
-// the checks of the three entries, which come before any device work
-static void check_sift_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
-                            int desc_layout, int64_t cap, const int64_t* count) {
-    APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+// the checks of the entries, which come before any device work
+static void check_sift_args(const aps_sift_view* views, int nv, int height, int width, int channels, int img_layout,
+                            const aps_sift_params* params, int desc_layout) {
+    APS_REQUIRE(views && params, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(nv >= 1 && nv <= kMaxViews, APS_E_ARG, "n_views must be in 1..%d", kMaxViews);
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].img, APS_E_ARG, "NULL argument");
     APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
     APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
     APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
@@ -1407,31 +1484,36 @@ static void check_sift_args(const uint8_t* img, int height, int width, int chann
     APS_REQUIRE(params->n_layers >= 1 && params->n_layers <= 5, APS_E_ARG, "NumLayersInOctave must be in 1..5");
     APS_REQUIRE(params->sigma > 0.5, APS_E_ARG, "Sigma must exceed the assumed camera blur 0.5");
     APS_REQUIRE(params->contrast_threshold >= 0 && params->edge_threshold >= 1, APS_E_ARG, "bad thresholds");
-    APS_REQUIRE(cap >= 0, APS_E_ARG, "negative capacity");
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].cap >= 0, APS_E_ARG, "negative capacity");
     APS_REQUIRE(2 * (int64_t)height < 65536 && 2 * (int64_t)width < 65536, APS_E_DIM, "image side must be < 32768");
 }
 
-// The Gaussian pyramid of a call: the planes, the host table of their sizes and pointers, and the table's device copy.  Every kernel
-// after the blurs reads it, so it lives until descr_kernel is launched and committed.
+// The Gaussian pyramid of a call: the slabs (one per octave and level, the group's planes at view_pitch), the host tables of their
+// sizes and pointers, one per view, and the tables' device copy.  Every kernel after the blurs reads it, so it lives until
+// descr_kernel is launched and committed.
 struct Pyramid {
+    int nv = 0;
     std::vector<Ws<float>> G;
-    PyrTable table;
+    std::vector<PyrTable> table;  // [view]; the sizes are those of table[0]
     Ws<PyrTable> d_table;
 };
 
-// dimg (H x W x channels, on the device) -> n_oct octaves of nl + 3 planes each and the uploaded table; no read-back
-static void build_pyramid(const uint8_t* dimg, int H, int W, int channels, int img_layout, const aps_sift_params* params, int n_oct,
-                          Pyramid& P) {
+// imgs (nv images of H x W x channels, on the device) -> n_oct octaves of nl + 3 slabs each and the uploaded tables; no read-back
+static void build_pyramid(const ViewImgs& imgs, int nv, int H, int W, int channels, int img_layout, const aps_sift_params* params,
+                          int n_oct, Pyramid& P) {
     const int nl = params->n_layers;
-    Ws<float> up, scratch;  // (up: the doubled gray plane, only when the fused base kernel does not apply)
-    Ws<uint8_t> gray8;      // the source gray plane as bytes (gray_u8_kernel), read by blur_base_kernel
+    Ws<float> up, scratch;  // (up: the doubled gray planes, only when the fused base kernel does not apply)
+    Ws<uint8_t> gray8;      // the source gray planes as bytes (gray_u8_kernel), read by blur_base_kernel
     std::vector<Ws<float>>& G = P.G;
     G = std::vector<Ws<float>>((size_t)n_oct * (nl + 3));
-    PyrTable& table = P.table;
-    std::memset(&table, 0, sizeof table);
-    table.n_oct = n_oct;
-    table.nl = nl;
-    table.sigma = (float)params->sigma;
+    P.nv = nv;
+    P.table.assign(nv, PyrTable());
+    std::memset(P.table.data(), 0, nv * sizeof(PyrTable));
+    for (PyrTable& t : P.table) {
+        t.n_oct = n_oct;
+        t.nl = nl;
+        t.sigma = (float)params->sigma;
+    }
     double sig[16];
     sig[0] = params->sigma;
     const double kf = std::pow(2.0, 1.0 / nl);
@@ -1439,68 +1521,72 @@ static void build_pyramid(const uint8_t* dimg, int H, int W, int channels, int i
         const double sp = std::pow(kf, (double)(i - 1)) * params->sigma, st = sp * kf;
         sig[i] = std::sqrt(st * st - sp * sp);
     }
-    int ow = 2 * W, oh = 2 * H;
+    int ow = 2 * W, oh = 2 * H, pw = 0, ph = 0;  // (pw, ph: the previous octave's)
     bool base_written = false;  // the previous octave's blur of plane nl wrote this octave's base
     for (int o = 0; o < n_oct; ++o) {
         if (o > 0) {
+            pw = ow;
+            ph = oh;
             ow = std::max(1, ow / 2);
             oh = std::max(1, oh / 2);
         }
-        OctaveDesc& od = table.oct[o];
-        od.w = ow;
-        od.h = oh;
-        const size_t px = (size_t)ow * oh;
+        const size_t pitch = view_pitch(ow, oh);
         for (int i = 0; i < nl + 3; ++i)
-            if (!(i == 0 && base_written)) G[o * (nl + 3) + i].alloc(px);
+            if (!(i == 0 && base_written)) G[o * (nl + 3) + i].alloc(nv * pitch);
         if (o == 0) {
             double sd = params->sigma * params->sigma - 4.0 * 0.5 * 0.5;
             if (sd < 0.01) sd = 0.01;
-            if (!launch_base_blur(dimg, H, W, channels, img_layout, std::sqrt(sd), G[0], gray8)) {
-                up.alloc((size_t)4 * H * W);
-                gray_up_kernel<<<dim3(cdiv(2 * W, kGUW), cdiv(2 * H, kGUH)), 256, 0, stream()>>>(dimg, H, W, channels, img_layout, up);
+            if (!launch_base_blur(nv, imgs, H, W, channels, img_layout, std::sqrt(sd), G[0], gray8)) {
+                up.alloc(nv * pitch);
+                gray_up_kernel<<<dim3(cdiv(2 * W, kGUW), cdiv(2 * H, kGUH), nv), 256, 0, stream()>>>(imgs, H, W, channels, img_layout, up, pitch);
                 check_launch("gray_up_kernel");
-                launch_blur(up, oh, ow, std::sqrt(sd), G[0], scratch);
+                launch_blur(nv, up, oh, ow, std::sqrt(sd), G[0], scratch);
             }
         } else if (!base_written) {
-            const OctaveDesc& pd = table.oct[o - 1];
-            decimate_kernel<<<dim3(cdiv(ow, 256), oh), 256, 0, stream()>>>(G[(o - 1) * (nl + 3) + nl], pd.h, pd.w,
-                                                                        oh, ow, G[o * (nl + 3)]);
+            decimate_kernel<<<dim3(cdiv(ow, 256), oh, nv), 256, 0, stream()>>>(G[(o - 1) * (nl + 3) + nl], ph, pw, view_pitch(pw, ph), oh, ow,
+                                                                            G[o * (nl + 3)], pitch);
             check_launch("decimate_kernel");
         }
         base_written = false;
         for (int i = 1; i < nl + 3; ++i) {
             if (i == nl && o + 1 < n_oct) {
                 const int nw = std::max(1, ow / 2), nh = std::max(1, oh / 2);
-                G[(o + 1) * (nl + 3)].alloc((size_t)nw * nh);
-                base_written = launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch,
+                G[(o + 1) * (nl + 3)].alloc(nv * view_pitch(nw, nh));
+                base_written = launch_blur(nv, G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch,
                                            G[(o + 1) * (nl + 3)], nh, nw);
             } else {
-                launch_blur(G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch);
+                launch_blur(nv, G[o * (nl + 3) + i - 1], oh, ow, sig[i], G[o * (nl + 3) + i], scratch);
             }
         }
-        for (int i = 0; i < nl + 3; ++i) od.G[i] = G[o * (nl + 3) + i];
+        for (int v = 0; v < nv; ++v) {
+            OctaveDesc& od = P.table[v].oct[o];
+            od.w = ow;
+            od.h = oh;
+            for (int i = 0; i < nl + 3; ++i) od.G[i] = G[o * (nl + 3) + i].get() + v * pitch;
+        }
     }
-    P.d_table.alloc(1);
-    APS_HIP(hipMemcpyAsync(P.d_table, &table, sizeof table, hipMemcpyHostToDevice, stream()));
+    P.d_table.alloc(nv);
+    APS_HIP(hipMemcpyAsync(P.d_table, P.table.data(), nv * sizeof(PyrTable), hipMemcpyHostToDevice, stream()));
 }
 
-// extrema: one detection sweep over all octaves -> packed cells; then one dense refinement launch -> recs, in no particular order.
-// Returns their number after two read-backs (the cells, then the records; one more when the cells outgrow their room), or fails
-// with APS_E_CAP when the records outgrow cand_cap.
-static unsigned int detect_candidates(const Pyramid& P, const aps_sift_params* params, int H, int W, Ws<KpRec>& recs) {
-    const PyrTable& table = P.table;
-    const int nl = table.nl, n_oct = table.n_oct;
+// extrema: one detection sweep over all views and octaves -> packed cells; then one dense refinement launch -> recs, in no particular
+// order, view v's in recs[v * cand_cap ..].  Returns cand_cap and fills n_cand[v] after two read-backs (the views' cells, then their
+// records; one more when the cells of a view outgrow their room), or fails with APS_E_CAP when a view's records outgrow cand_cap.
+static unsigned int detect_candidates(const Pyramid& P, const aps_sift_params* params, int H, int W, Ws<KpRec>& recs, unsigned int* n_cand) {
+    const PyrTable& table = P.table[0];
+    const int nl = table.nl, n_oct = table.n_oct, nv = P.nv;
     const unsigned int cand_cap = (unsigned int)std::min<size_t>(
         params->max_features > 0 ? (size_t)params->max_features : std::max<size_t>((size_t)H * W / 2, 65536), 1u << 26);
     unsigned int cells_cap = (unsigned int)std::min<size_t>(std::max<size_t>((size_t)H * W / 2, 1u << 18), 1u << 27);
-    Ws<unsigned long long> cells(cells_cap);
-    recs.alloc(cand_cap);
-    Ws<unsigned int> d_count(2);  // [0] cells, [1] refined records
+    Ws<unsigned long long> cells((size_t)nv * cells_cap);
+    recs.alloc((size_t)nv * cand_cap);
+    Ws<unsigned int> d_count(2 * nv);  // [view][0] cells, [view][1] refined records
+    unsigned int h_count[2 * kMaxViews];
     const float thr = (float)(int)std::floor(0.5 * params->contrast_threshold / nl * 255.0);
-    unsigned int n_cells = 0;
+    unsigned int max_cells = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        APS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), stream()));
-        // one launch over all octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
+        APS_HIP(hipMemsetAsync(d_count, 0, 2 * nv * sizeof(unsigned int), stream()));
+        // one launch over all views and octaves, one wave per strip and chunk of rows (extrema_wave_kernel)
         ExtremaWavePlan plan;
         std::memset(&plan, 0, sizeof plan);
         int run = 0;
@@ -1521,7 +1607,7 @@ static unsigned int detect_candidates(const Pyramid& P, const aps_sift_params* p
         plan.job_ptr[16] = run;
         if (run > 0) {
             Prof prof("sift_extrema");
-            const int wgs = cdiv(run, 4);
+            const dim3 wgs(cdiv(run, 4), nv);
             switch (nl) {
                 case 1: extrema_wave_kernel<1><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
                 case 2: extrema_wave_kernel<2><<<wgs, 256, 0, stream()>>>(P.d_table, plan, thr, cells, d_count, cells_cap); break;
@@ -1531,42 +1617,69 @@ static unsigned int detect_candidates(const Pyramid& P, const aps_sift_params* p
             }
             check_launch("extrema_wave_kernel");
         }
-        n_cells = read_back(d_count.get());
-        if (n_cells <= cells_cap) break;
+        read_back(d_count.get(), h_count, 2 * nv);
+        max_cells = 0;
+        for (int v = 0; v < nv; ++v) max_cells = std::max(max_cells, h_count[2 * v]);
+        if (max_cells <= cells_cap) break;
         // flat or band-limited images can have far more (weak) scale-space extrema than the default room:
-        // grow to the exact need and sweep once more
+        // grow every view's room to the largest need and sweep the group once more
         APS_REQUIRE(attempt == 0, APS_E_INTERNAL, "extrema count changed between identical sweeps");
-        cells_cap = n_cells;
-        cells.alloc(cells_cap);
+        cells_cap = max_cells;
+        cells.alloc((size_t)nv * cells_cap);
     }
-    if (n_cells > 0) {
+    if (max_cells > 0) {
         Prof prof("sift_refine");
-        refine_kernel<<<cdiv(n_cells, 256), 256, 0, stream()>>>(P.d_table, cells, d_count, cells_cap,
-                                                                 (float)params->contrast_threshold,
-                                                                 (float)params->edge_threshold, recs, d_count.get() + 1,
-                                                                 cand_cap);
+        refine_kernel<<<dim3(cdiv(max_cells, 256), nv), 256, 0, stream()>>>(P.d_table, cells, d_count, cells_cap,
+                                                                            (float)params->contrast_threshold,
+                                                                            (float)params->edge_threshold, recs, d_count.get() + 1,
+                                                                            cand_cap);
         check_launch("refine_kernel");
     }
-    const unsigned int n_cand = read_back(d_count.get() + 1);
-    if (n_cand > cand_cap)
-        fail(APS_E_CAP, "SIFT found %u extrema, more than the candidate capacity %u (raise params.max_features)", n_cand, cand_cap);
-    return n_cand;
+    read_back(d_count.get(), h_count, 2 * nv);
+    for (int v = 0; v < nv; ++v) {
+        n_cand[v] = h_count[2 * v + 1];
+        if (n_cand[v] > cand_cap)
+            fail(APS_E_CAP, "SIFT found %u extrema, more than the candidate capacity %u (raise params.max_features)", n_cand[v], cand_cap);
+    }
+    return cand_cap;
 }
 
-// canonical order + dedupe: recs[0 .. n_cand - 1], n_cand > 0 -> kps, sorted by the 44-bit key with one record per key.  Returns
-// their number after one read-back.
-static unsigned int canonical_keypoints(const Ws<KpRec>& recs, unsigned int n_cand, Ws<KpRec>& kps) {
-    Ws<unsigned long long> keys(n_cand), keys_s(n_cand);
-    Ws<unsigned int> idx(n_cand), idx_s(n_cand), flag(n_cand), pos(n_cand);
-    rec_keys_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, n_cand, keys, idx);
-    sort_pairs<unsigned int>(keys.get(), keys_s.get(), idx.get(), idx_s.get(), n_cand, 44u);
-    unique_flag_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(keys_s, n_cand, flag);
-    exclusive_scan(flag.get(), pos.get(), 0u, n_cand);
-    const unsigned int n_kp = scan_total(pos.get(), flag.get(), n_cand);
-    kps.alloc(n_kp);
-    compact_recs_kernel<<<cdiv(n_cand, 256), 256, 0, stream()>>>(recs, idx_s, flag, pos, n_cand, kps);
+// The per-view counts behind an exclusive scan `pos` of `val` over the views' concatenated runs `seg`: count[v] for view v, and the
+// total as the return value; one small launch and one read-back.
+static unsigned int segment_counts(const unsigned int* pos, const unsigned int* val, const Segments& seg, int nv, unsigned int* count) {
+    Ws<unsigned int> d_ends(nv);
+    unsigned int ends[kMaxViews];
+    segment_ends_kernel<<<1, 64, 0, stream()>>>(pos, val, seg, nv, d_ends);
+    check_launch("segment_ends_kernel");
+    read_back(d_ends.get(), ends, nv);
+    for (int v = 0; v < nv; ++v) count[v] = ends[v] - (v ? ends[v - 1] : 0u);
+    return ends[nv - 1];
+}
+
+static Segments segments_of(const unsigned int* count, int nv) {
+    Segments seg;
+    std::memset(&seg, 0, sizeof seg);
+    for (int v = 0; v < kMaxViews; ++v) seg.off[v + 1] = seg.off[v] + (v < nv ? count[v] : 0u);
+    return seg;
+}
+
+// canonical order + dedupe: the views' n_cand[v] records (segments of cand_cap, at least one record in all) -> kps, the views one
+// after the other, each sorted by the 44-bit key with one record per key.  Fills n_kp[v] and returns their sum after one read-back.
+static unsigned int canonical_keypoints(const Ws<KpRec>& recs, unsigned int cand_cap, const unsigned int* n_cand, int nv, Ws<KpRec>& kps,
+                                        unsigned int* n_kp) {
+    const Segments seg = segments_of(n_cand, nv);
+    const unsigned int n = seg.off[nv], most = *std::max_element(n_cand, n_cand + nv);
+    Ws<unsigned long long> keys(n), keys_s(n);
+    Ws<unsigned int> idx(n), idx_s(n), flag(n), pos(n);
+    rec_keys_kernel<<<dim3(cdiv(most, 256), nv), 256, 0, stream()>>>(recs, cand_cap, seg, keys, idx);
+    sort_pairs<unsigned int>(keys.get(), keys_s.get(), idx.get(), idx_s.get(), n, nv > 1 ? kViewShift + 4u : (unsigned int)kViewShift);
+    unique_flag_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(keys_s, n, flag);
+    exclusive_scan(flag.get(), pos.get(), 0u, n);
+    const unsigned int total = segment_counts(pos, flag, seg, nv, n_kp);
+    kps.alloc(total);
+    compact_recs_kernel<<<cdiv(n, 256), 256, 0, stream()>>>(recs, idx_s, flag, pos, n, kps);
     check_launch("compact_recs_kernel");
-    return n_kp;
+    return total;
 }
 
 // The orientations of the keypoints: ocount[i] of them for keypoint i, their angles in oangle[i * kOriBins ..], and opos, the
@@ -1576,24 +1689,26 @@ struct Orientations {
     Ws<float> oangle;
 };
 
-// kps[0 .. n_kp - 1], n_kp > 0 -> their orientations.  Returns the number of oriented keypoints after one read-back.
-static unsigned int orient_keypoints(const Pyramid& P, const Ws<KpRec>& kps, unsigned int n_kp, Orientations& O) {
-    O.ocount.alloc(n_kp);
-    O.opos.alloc(n_kp);
-    O.oangle.alloc((size_t)n_kp * kOriBins);
-    Ws<unsigned char> obin((size_t)n_kp * kOriBins);
+// kps (the views' n_kp[v] keypoints one after the other, n > 0 in all) -> their orientations.  Fills n_rows[v], the oriented keypoints
+// of view v, and returns their sum after one read-back.
+static unsigned int orient_keypoints(const Pyramid& P, const Ws<KpRec>& kps, const unsigned int* n_kp, unsigned int n, Orientations& O,
+                                     unsigned int* n_rows) {
+    O.ocount.alloc(n);
+    O.opos.alloc(n);
+    O.oangle.alloc((size_t)n * kOriBins);
+    Ws<unsigned char> obin((size_t)n * kOriBins);
     {
         Prof prof("sift_orient");
-        orient_kernel<<<cdiv(n_kp, 4), 256, 0, stream()>>>(P.d_table, kps, n_kp, O.ocount, O.oangle, obin);
+        orient_kernel<<<cdiv(n, 4), 256, 0, stream()>>>(P.d_table, kps, n, O.ocount, O.oangle, obin);
     }
     check_launch("orient_kernel");
-    exclusive_scan(O.ocount.get(), O.opos.get(), 0u, n_kp);
-    return scan_total(O.opos.get(), O.ocount.get(), n_kp);
+    exclusive_scan(O.ocount.get(), O.opos.get(), 0u, n);
+    return segment_counts(O.opos, O.ocount, segments_of(n_kp, P.nv), P.nv, n_rows);
 }
 
-// The n_out <= n_all rows to describe, in canonical order: all n_all oriented keypoints, or with n_out < n_all the ones that come
-// first by (contrast descending, canonical index ascending) - over the whole image, or with grid_rows > 0 within their cell of the
-// grid_rows x grid_cols grid over the H x W image, the cells' shares by water-filling n_out.  No read-back.
+// The n_out <= n_all rows to describe, in canonical order: all n_all oriented keypoints, or with n_out < n_all (one view) the ones
+// that come first by (contrast descending, canonical index ascending) - over the whole image, or with grid_rows > 0 within their cell
+// of the grid_rows x grid_cols grid over the H x W image, the cells' shares by water-filling n_out.  No read-back.
 static Ws<OrientedKp> select_rows(const Ws<KpRec>& kps, unsigned int n_kp, const Orientations& O, unsigned int n_all, unsigned int n_out,
                                   int H, int W, int grid_rows, int grid_cols) {
     Ws<OrientedKp> oks_all(n_all);
@@ -1621,31 +1736,54 @@ static Ws<OrientedKp> select_rows(const Ws<KpRec>& kps, unsigned int n_kp, const
     return oks_sel;
 }
 
-// oks[0 .. n_out - 1], n_out > 0 -> the caller's desc, loc and aux.  The checks of the output arguments come before any write; the
-// strided copy-back leaves the elements between the logical rows / columns (ldd, ldl beyond the count) the caller's.
-static void describe(const Pyramid& P, const Ws<KpRec>& kps, const Ws<OrientedKp>& oks, unsigned int n_out, float* desc, int desc_layout,
-                     int64_t ldd, double* loc, int64_t ldl, float* aux) {
-    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-    if (desc_layout == APS_ROWMAJOR)
-        APS_REQUIRE(ldd >= 128, APS_E_DIM, "ldd < 128");
-    else
-        APS_REQUIRE(ldd >= n_out, APS_E_DIM, "ldd < count");
-    APS_REQUIRE(ldl >= n_out, APS_E_DIM, "ldl < count");
-    const size_t desc_elems = desc_layout == APS_ROWMAJOR ? (size_t)(n_out - 1) * ldd + 128 : (size_t)127 * ldd + n_out;
-    Out<float> odesc(desc, desc_elems), oaux(aux, (size_t)n_out * 4);
-    Out<double> oloc(loc, (size_t)ldl + n_out);
+// oks[0 .. n - 1], the views' n_out[v] rows one after the other (n > 0 in all) -> every view's desc, loc and aux, one launch.  The
+// checks of the output arguments come before any write; the strided copy-back leaves the elements between the logical rows / columns
+// (ldd, ldl beyond the count) the caller's.
+static void describe(const Pyramid& P, const Ws<KpRec>& kps, const Ws<OrientedKp>& oks, const unsigned int* n_out, unsigned int n,
+                     aps_sift_view* views, int desc_layout, int64_t ldd, int64_t ldl) {
+    const int nv = P.nv;
+    for (int v = 0; v < nv; ++v) {
+        if (n_out[v] == 0) continue;
+        APS_REQUIRE(views[v].desc && views[v].loc, APS_E_ARG, "NULL output with features present");
+        if (desc_layout == APS_ROWMAJOR)
+            APS_REQUIRE(ldd >= 128, APS_E_DIM, "ldd < 128");
+        else
+            APS_REQUIRE(ldd >= n_out[v], APS_E_DIM, "ldd < count");
+        APS_REQUIRE(ldl >= n_out[v], APS_E_DIM, "ldl < count");
+    }
+    std::vector<Out<float>> odesc(nv), oaux(nv);
+    std::vector<Out<double>> oloc(nv);
+    ViewDst dst[kMaxViews];
+    std::memset(dst, 0, sizeof dst);
+    unsigned int row0 = 0;
+    for (int v = 0; v < nv; ++v) {
+        dst[v].row0 = row0;
+        row0 += n_out[v];
+        if (n_out[v] == 0) continue;
+        const size_t desc_elems = desc_layout == APS_ROWMAJOR ? (size_t)(n_out[v] - 1) * ldd + 128 : (size_t)127 * ldd + n_out[v];
+        odesc[v].bind(views[v].desc, desc_elems);
+        oaux[v].bind(views[v].aux, (size_t)n_out[v] * 4);
+        oloc[v].bind(views[v].loc, (size_t)ldl + n_out[v]);
+        dst[v].desc = odesc[v];
+        dst[v].loc = oloc[v];
+        dst[v].aux = oaux[v].present() ? oaux[v].get() : nullptr;
+    }
+    Ws<ViewDst> d_dst(nv);
+    APS_HIP(hipMemcpyAsync(d_dst, dst, nv * sizeof(ViewDst), hipMemcpyHostToDevice, stream()));
     {
         Prof prof("sift_descr");
-        descr_kernel<<<cdiv(n_out, 4), 256, 0, stream()>>>(P.d_table, kps, oks, n_out, odesc, desc_layout, ldd, oloc, ldl,
-                                                           oaux.present() ? oaux.get() : nullptr);
+        descr_kernel<<<cdiv(n, 4), 256, 0, stream()>>>(P.d_table, kps, oks, n, d_dst, desc_layout, ldd, ldl);
     }
     check_launch("descr_kernel");
-    if (desc_layout == APS_ROWMAJOR)
-        odesc.commit_2d(128, n_out, (size_t)ldd);
-    else
-        odesc.commit_2d(n_out, 128, (size_t)ldd);
-    oloc.commit_2d(n_out, 2, (size_t)ldl);
-    oaux.commit();
+    for (int v = 0; v < nv; ++v) {
+        if (n_out[v] == 0) continue;
+        if (desc_layout == APS_ROWMAJOR)
+            odesc[v].commit_2d(128, n_out[v], (size_t)ldd);
+        else
+            odesc[v].commit_2d(n_out[v], 128, (size_t)ldd);
+        oloc[v].commit_2d(n_out[v], 2, (size_t)ldl);
+        oaux[v].commit();
+    }
     APS_HIP(hipStreamSynchronize(stream()));
 }
 
@@ -1653,33 +1791,63 @@ static void describe(const Pyramid& P, const Ws<KpRec>& kps, const Ws<OrientedKp
 
 using namespace aps;
 
-// aps_sift_extract (n_strongest = 0: every row) and aps_sift_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF": the
-// n_strongest rows of largest contrast) behind one body; with grid_rows > 0 the n_strongest rows are spread over the cells of a
-// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").
-static void sift_chain(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
-                       long long n_strongest, int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc,
-                       int64_t ldl, float* aux, int64_t cap, int64_t* count) {
-    check_sift_args(img, height, width, channels, img_layout, params, desc_layout, cap, count);
+// The body of every SIFT entry, on a group of nv views of one shape: aps_sift_extract_batch's group, or the single entries' group of
+// one.  n_strongest = 0: every row (aps_sift_extract); n_strongest > 0 (one view): the n_strongest rows of largest contrast
+// (aps_sift_extract_strongest, DESIGN.md "Strongest-N for SIFT and SURF"), or with grid_rows > 0 spread over the cells of a
+// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").  views[v].count is the view's rows
+// whenever the counts are known, so on APS_E_CAP every view holds what it needs.
+static void sift_chain(aps_sift_view* views, int nv, int height, int width, int channels, int img_layout, const aps_sift_params* params,
+                       long long n_strongest, int grid_rows, int grid_cols, int desc_layout, int64_t ldd, int64_t ldl) {
+    check_sift_args(views, nv, height, width, channels, img_layout, params, desc_layout);
     ctx();
-    *count = 0;
+    for (int v = 0; v < nv; ++v) views[v].count = 0;
     const int H = height, W = width;
-    In<uint8_t> dimg(img, (size_t)H * W * channels);
+    std::vector<In<uint8_t>> dimg(nv);
+    ViewImgs imgs;
+    std::memset(&imgs, 0, sizeof imgs);
+    for (int v = 0; v < nv; ++v) {
+        dimg[v].bind(views[v].img, (size_t)H * W * channels);
+        imgs.p[v] = dimg[v];
+    }
     const int n_oct = std::min(num_octaves(H, W), 16);
     if (n_oct <= 0) return;
     Pyramid pyr;
-    build_pyramid(dimg, H, W, channels, img_layout, params, n_oct, pyr);
+    build_pyramid(imgs, nv, H, W, channels, img_layout, params, n_oct, pyr);
     Ws<KpRec> recs, kps;
-    const unsigned int n_cand = detect_candidates(pyr, params, H, W, recs);
-    if (n_cand == 0) return;
-    const unsigned int n_kp = canonical_keypoints(recs, n_cand, kps);
+    unsigned int n_cand[kMaxViews], n_kp[kMaxViews], n_all[kMaxViews], n_out[kMaxViews];
+    const unsigned int cand_cap = detect_candidates(pyr, params, H, W, recs, n_cand);
+    if (*std::max_element(n_cand, n_cand + nv) == 0) return;
+    const unsigned int n_kp_sum = canonical_keypoints(recs, cand_cap, n_cand, nv, kps, n_kp);
     Orientations ori;
-    const unsigned int n_all = orient_keypoints(pyr, kps, n_kp, ori);  // the rows of the call without n_strongest
-    const unsigned int n_out = n_strongest > 0 ? (unsigned int)std::min<long long>(n_all, n_strongest) : n_all;
-    *count = n_out;
-    if ((int64_t)n_out > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n_out);
-    if (n_out == 0) return;
-    const Ws<OrientedKp> oks = select_rows(kps, n_kp, ori, n_all, n_out, H, W, grid_rows, grid_cols);
-    describe(pyr, kps, oks, n_out, desc, desc_layout, ldd, loc, ldl, aux);
+    const unsigned int n_all_sum = orient_keypoints(pyr, kps, n_kp, n_kp_sum, ori, n_all);  // the rows of the call without n_strongest
+    unsigned int n_out_sum = 0;
+    bool fits = true;
+    for (int v = 0; v < nv; ++v) {
+        n_out[v] = n_strongest > 0 ? (unsigned int)std::min<long long>(n_all[v], n_strongest) : n_all[v];
+        n_out_sum += n_out[v];
+        views[v].count = n_out[v];
+        fits = fits && (int64_t)n_out[v] <= views[v].cap;
+    }
+    for (int v = 0; v < nv && !fits; ++v)
+        if ((int64_t)n_out[v] > views[v].cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)views[v].cap, n_out[v]);
+    if (n_out_sum == 0) return;
+    const Ws<OrientedKp> oks = select_rows(kps, n_kp_sum, ori, n_all_sum, n_out_sum, H, W, grid_rows, grid_cols);
+    describe(pyr, kps, oks, n_out, n_out_sum, views, desc_layout, ldd, ldl);
+}
+
+// the single-view entries: a group of one, *count from the view whether the chain returns or fails
+static void sift_single(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_sift_params* params,
+                        long long n_strongest, int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc,
+                        int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+    aps_sift_view view = {img, desc, loc, aux, cap, *count};
+    try {
+        sift_chain(&view, 1, height, width, channels, img_layout, params, n_strongest, grid_rows, grid_cols, desc_layout, ldd, ldl);
+    } catch (...) {
+        *count = view.count;
+        throw;
+    }
+    *count = view.count;
 }
 
 extern "C" {
@@ -1687,7 +1855,12 @@ extern "C" {
 int aps_sift_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
                      const aps_sift_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
-    return guarded([&] { sift_chain(img, height, width, channels, img_layout, params, 0, 0, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count); });
+    return guarded([&] { sift_single(img, height, width, channels, img_layout, params, 0, 0, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count); });
+}
+
+int aps_sift_extract_batch(aps_sift_view* views, int n_views, int height, int width, int channels, int img_layout,
+                           const aps_sift_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] { sift_chain(views, n_views, height, width, channels, img_layout, params, 0, 0, 0, desc_layout, ldd, ldl); });
 }
 
 int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,
@@ -1696,8 +1869,8 @@ int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int ch
     return guarded([&] {
         APS_REQUIRE(params, APS_E_ARG, "NULL argument");
         APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
-        sift_chain(img, height, width, channels, img_layout, &params->sift, params->n_strongest, 0, 0, desc, desc_layout, ldd, loc, ldl, aux,
-                   cap, count);
+        sift_single(img, height, width, channels, img_layout, &params->sift, params->n_strongest, 0, 0, desc, desc_layout, ldd, loc, ldl, aux,
+                    cap, count);
     });
 }
 
@@ -1707,10 +1880,9 @@ int aps_sift_extract_uniform(const uint8_t* img, int height, int width, int chan
     return guarded([&] {
         APS_REQUIRE(params, APS_E_ARG, "NULL argument");
         check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
-        sift_chain(img, height, width, channels, img_layout, &params->strongest.sift, params->strongest.n_strongest, params->grid_rows,
-                   params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+        sift_single(img, height, width, channels, img_layout, &params->strongest.sift, params->strongest.n_strongest, params->grid_rows,
+                    params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
     });
 }
 
 }  // extern "C"
-

@@ -739,6 +739,67 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
     return d, pts
 
 
+def sift_extract_batch(input, images, device_out=False, want_aux=False, points_device=False, compact=False):
+    """aps_sift_extract_batch with automatic capacity: sift_extract for 1.._capi.APS_SIFT_MAX_VIEWS images of one shape in one call,
+    every stage once for the group.  Returns a list of sift_extract's results, one (features, validPts[, aux]) per image, bit for
+    bit those of sift_extract(input, image, ...) on each.  The arguments are sift_extract's; input.NumStrongest and input.NumUniform
+    are per-view selections and not taken here (ValueError)."""
+    if "NumStrongest" in input or "NumUniform" in input:
+        raise ValueError("sift_extract_batch extracts every row: NumStrongest / NumUniform go through sift_extract, view by view")
+    g = len(images)
+    imgs = [im.contiguous() if _capi.is_torch(im) else np.ascontiguousarray(im, np.uint8) for im in images]
+    shape = tuple(imgs[0].shape) if g else ()
+    if any(tuple(im.shape) != shape for im in imgs):
+        raise ValueError("the images of a batch must have one shape")
+    h, w = (int(shape[0]), int(shape[1])) if g else (1, 1)
+    c = 1 if len(shape) == 2 else (int(shape[2]) if g else 3)
+    if c not in (1, 3):
+        raise ValueError("image must be gray or RGB")
+    prm = _sift_params(input)
+    caps = [max(4096, (h * w) // 64)] * g
+    dev_pts = device_out and points_device
+    if device_out:
+        import torch
+    views = (_capi.aps_sift_view * max(g, 1))()
+    while True:
+        descs, locs, auxs = [], [], []
+        for k in range(g):
+            cap = caps[k]
+            descs.append(torch.empty((cap, DIM), dtype=torch.float32, device="cuda") if device_out else np.zeros((cap, DIM), np.float32))
+            locs.append(torch.empty((2, cap), dtype=torch.float64, device="cuda") if dev_pts else np.zeros((2, cap), np.float64))
+            auxs.append(np.zeros((cap, 4), np.float32) if want_aux else None)
+            views[k].img, views[k].desc, views[k].loc, views[k].aux = ptr(imgs[k]), ptr(descs[k]), ptr(locs[k]), ptr(auxs[k])
+            views[k].cap, views[k].count = cap, 0
+        if device_out:
+            _fence_fresh_blocks()
+        # (the views share one capacity, which is the leading dimension of their column-major locations)
+        rc = lib.aps_sift_extract_batch(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, caps[0] if g else 0)
+        if rc == _capi.APS_E_CAP and any(views[k].count > caps[k] for k in range(g)):
+            caps = [max(int(views[k].count) for k in range(g))] * g
+            continue
+        check(rc)
+        break
+    if device_out:
+        check(lib.aps_synchronize())  # (with every output resident the call returns without waiting for its last kernel)
+    out = []
+    for k in range(g):
+        n = int(views[k].count)
+        if dev_pts:
+            pts = locs[k][:, :n].t().contiguous()
+        else:
+            pts = np.ascontiguousarray(locs[k][:, :n].T)
+        if device_out and compact:
+            d = descs[k][:n].clone()
+        elif device_out:
+            d = descs[k][:n]
+        else:
+            d = np.ascontiguousarray(descs[k][:n])
+        out.append((d, pts, auxs[k][:n].copy()) if want_aux else (d, pts))
+    if device_out and (dev_pts or compact):
+        torch.cuda.current_stream().synchronize()  # the transposes / clones ran on torch's stream; consumers run on the library's
+    return out
+
+
 SURF_DIM = 64
 
 

@@ -57,11 +57,23 @@ def _sync():
 _SIFT_POOL = None
 
 
-# Host threads / HIP streams of the per-image feature extraction.  Measured on the 64 x 4K scene on several boxes:
+# Host threads / HIP streams of the per-image feature extraction (host images, SURF, FAST, NumStrongest / NumUniform; resident SIFT
+# views go in groups, below).  Measured on the 64 x 4K scene on several boxes:
 # 4, 5, 10, 11, 12, 14 threads give 88-93 ms, 10 the best or tied everywhere; 7-9 threads read 100 ms on some boxes and
 # 92 on others (reproducibly per box; the HIP runtime maps streams onto 8 hardware queues), 12 costs the end-to-end
 # step's uploads 14 ms.
 SIFT_WORKERS_DEFAULT = 10
+
+# Resident SIFT images go to the library in groups of consecutive same-shape views (fm.sift_extract_batch: one launch per pyramid
+# plane and per stage for the whole group), a few groups in flight on worker streams of their own, so that the per-keypoint
+# kernels of one group run beside the pyramid of another.  A group of G 4K views holds G x 1.24 GB of pyramid (plus 0.13 GB per
+# view of candidate lists) in its worker's workspace: 8 views x 3 workers = 33 GB.
+# Measured on the 64 x 4K step (median ms per step, three runs each, the per-view parent 162.6-163.6 in the same series):
+# 8 views x 3 workers 156.8-158.0, 8 x 2 156.2-159.5, 8 x 4 158.9-159.6, 4 x 4 162.6-163.3, 4 x 6 156.8-157.6, 16 x 2 156.4-159.9,
+# 16 x 3 157.0-160.2, 2 x 8 166.0-166.7.
+SIFT_GROUP_VIEWS = 8
+SIFT_GROUP_WORKERS = 3
+_SIFT_GROUP_POOL = None
 
 
 def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
@@ -120,7 +132,7 @@ def release_device_memory():
     _capi.check(_capi.lib.aps_release_workspace())
     from . import renderPanorama as _rp
 
-    for pool in (_SIFT_POOL, getattr(_rp, "_RENDER_POOL", None)):
+    for pool in (_SIFT_POOL, _SIFT_GROUP_POOL, getattr(_rp, "_RENDER_POOL", None)):
         n = len(getattr(pool, "_threads", ())) if pool is not None else 0
         if not n:
             continue
@@ -143,17 +155,54 @@ def release_device_memory():
 def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_device=False):
     """The asynchronous form of sift_many: one future per image, submitted in input order to the worker pool, so that
     a caller can start matching the first images while the later ones are still being extracted (parallel._match_pass).
+    Resident SIFT images without a per-view selection are submitted as groups of up to SIFT_GROUP_VIEWS consecutive images of one
+    shape (fm.sift_extract_batch) to SIFT_GROUP_WORKERS threads; the futures of a group resolve together.
     Each future resolves to (descriptors, keypoints) once that worker's stream has finished the image.
     points_device: resident images only - the keypoints stay on the device (fm.sift_extract)."""
-    global _SIFT_POOL
+    global _SIFT_POOL, _SIFT_GROUP_POOL
     import os
     import torch
-    from concurrent.futures import ThreadPoolExecutor
+    from concurrent.futures import Future, ThreadPoolExecutor
 
     workers = max(1, int(os.environ.get("APS_SIFT_WORKERS", workers)))
     dev = _capi.is_torch(images[0]) and images[0].is_cuda
     if dev and ready is None:
         torch.cuda.synchronize()  # the images were produced on torch's stream; worker streams must see them
+    if dev and input.get("detector", "SIFT") == "SIFT" and "NumStrongest" not in input and "NumUniform" not in input:
+        # resident SIFT views: groups of consecutive images of one shape, one pool task per group, one future per image
+        if _SIFT_GROUP_POOL is None:
+            _SIFT_GROUP_POOL = ThreadPoolExecutor(max_workers=SIFT_GROUP_WORKERS, initializer=_init_worker,
+                                                  initargs=(_capi.lib.aps_get_device(),))
+        groups = []
+        for k, img in enumerate(images):
+            if groups and len(groups[-1]) < SIFT_GROUP_VIEWS and tuple(images[groups[-1][0]].shape) == tuple(img.shape) \
+                    and images[groups[-1][0]].device == img.device:
+                groups[-1].append(k)
+            else:
+                groups.append([k])
+        futs = [Future() for _ in images]
+
+        def work_group(ks):
+            for k in ks:
+                futs[k].set_running_or_notify_cancel()
+            try:
+                _capi.check(_capi.lib.aps_set_thread_device(images[ks[0]].device.index))
+                if ready is not None:
+                    for k in ks:
+                        ready[k].synchronize()
+                res = fm.sift_extract_batch(input, [images[k] for k in ks], device_out=True, points_device=bool(points_device),
+                                            compact=len(images) > 96)
+                _sync()  # this thread's stream
+            except BaseException as e:
+                for k in ks:
+                    futs[k].set_exception(e)
+                return
+            for k, r in zip(ks, res):
+                futs[k].set_result(r)
+
+        for ks in groups:
+            _SIFT_GROUP_POOL.submit(work_group, ks)
+        return futs
     if _SIFT_POOL is None:
         _SIFT_POOL = ThreadPoolExecutor(max_workers=workers, initializer=_init_worker, initargs=(_capi.lib.aps_get_device(),))
     pool = _SIFT_POOL

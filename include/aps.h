@@ -720,6 +720,26 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_sift_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
+/* aps_sift_extract for a group of views of one shape (height x width x channels, img_layout): every stage runs once for the group -
+ * one launch per pyramid plane, one extrema sweep, one launch of each per-keypoint kernel - where n_views single calls run it
+ * n_views times.  The rows of view k are bit for bit those of aps_sift_extract on views[k].img, in the same order. */
+#define APS_SIFT_MAX_VIEWS 16
+typedef struct aps_sift_view {
+    const uint8_t* img;   /* H x W x channels, host or device, as aps_sift_extract */
+    float* desc; double* loc; float* aux;   /* per-view outputs, host or device; aux may be NULL */
+    int64_t cap;          /* rows of room in this view's outputs */
+    int64_t count;        /* out: rows found (on APS_E_CAP: rows needed) */
+} aps_sift_view;
+/* n_views in 1..APS_SIFT_MAX_VIEWS (else APS_E_ARG, as for a NULL views or a NULL views[k].img).  desc_layout, ldd and ldl hold for
+ * every view; count-only mode, padding, layouts and host / device pointers behave as aps_sift_extract's, view by view.  When any
+ * view's rows exceed its cap nothing is written and the call returns APS_E_CAP with EVERY view's count set to the rows it needs, so
+ * one retry is enough.  A view without features gets count = 0 and does not touch the others.  params->max_features is the candidate
+ * capacity of each view.  The pyramids of the group live side by side: n_views x 1.24 GB of workspace for 4K views.  The call runs on
+ * the calling thread's stream with that thread's workspace. */
+int aps_sift_extract_batch(aps_sift_view* views, int n_views, int height, int width, int channels,
+                           int img_layout, const aps_sift_params* params,
+                           int desc_layout, int64_t ldd, int64_t ldl);
+
 /* SIFT strongest-N (DESIGN.md "Strongest-N for SIFT and SURF"; cv::SIFT's nfeatures, selectStrongest): of the rows aps_sift_extract
  * returns for the same image and parameters (the candidates, in canonical order), keep the first min(n_strongest, candidates) by
  * (aux's response = the keypoint's contrast descending, compared as f32; canonical index ascending).  No quota per octave.  The unit
