@@ -16,10 +16,9 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdlib>
 #include <memory>
 #include <vector>
-
-#include <functional>
 
 #include "render_dev.h"
 
@@ -1008,6 +1007,122 @@ static DevCanvas make_canvas(const aps_canvas& c) {
     return d;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the tile loop, tile by tile: the arithmetic render_batch.hip's kernels are checked against (APS_RENDER_LEGACY=1) and the
+// fallback for what they are not built for (more than 8 pyramid levels, tiles of 2^31 bytes or more)
+// ------------------------------------------------------------------------------------------------
+// Phase 1: footprint of every image in every tile (the reference skips images with ~any(Mi), :989; here the bounding box of
+// Mi also bounds all later work on that layer); one read-back.  -> [tile][image][x0 y0 x1 y1]
+static std::vector<int> per_tile_footprints(const DevCanvas& cv, const DevImage* dimgs, int n_img, const aps_render_opts& o,
+                                            const std::vector<TileRect>& tiles) {
+    const int nt = (int)tiles.size();
+    std::vector<int> hbox((size_t)nt * n_img * 4, 0);
+    if (o.blending == APS_BLEND_NONE || nt == 0) return hbox;
+    const int nby_max = cdiv(std::min(o.tile_h, cv.H), 8);
+    std::vector<int> dims((size_t)nt * 4);
+    for (int t = 0; t < nt; ++t) {
+        dims[4 * t + 0] = tiles[t].ht;
+        dims[4 * t + 1] = tiles[t].wt;
+        dims[4 * t + 2] = cdiv(tiles[t].ht, 8);
+        dims[4 * t + 3] = cover_xshift(tiles[t].wt);
+    }
+    Ws<unsigned long long> rowmask((size_t)nt * n_img * nby_max);
+    Ws<int> bbox(hbox.size()), ddims(dims.size());
+    APS_HIP(hipMemsetAsync(rowmask, 0, (size_t)nt * n_img * nby_max * sizeof(unsigned long long), stream()));
+    APS_HIP(hipMemcpyAsync(ddims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("cover");
+        for (int t = 0; t < nt; ++t) {
+            const TileRect& tl = tiles[t];
+            cover_kernel<<<dim3(cdiv(tl.wt, 32), cdiv(tl.ht, 8)), 256, 0, stream()>>>(
+                cv, dimgs, n_img, tl.r0, tl.c0, tl.ht, tl.wt, o.angle_power, nby_max, dims[4 * t + 3],
+                std::getenv("APS_RENDER_NO_CULL") ? 0 : 1, rowmask.get() + (size_t)t * n_img * nby_max);
+        }
+        footprint_kernel<<<cdiv((size_t)nt * n_img, 256), 256, 0, stream()>>>(rowmask, ddims, n_img, nby_max, nt * n_img, bbox);
+    }
+    check_launch("cover_kernel");
+    APS_HIP(hipMemcpyAsync(hbox.data(), bbox, hbox.size() * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));  // also keeps `dims` alive until its upload has run
+    return hbox;
+}
+
+// Phase 2: tiles back to back on the stream, no host round trip in between.  pano / covered: device pointers.
+static void render_tiles_per_tile(const DevCanvas& cv, const DevImage* dimgs, int n_img, const aps_render_opts& o,
+                                  const std::vector<TileRect>& tiles, int out_layout, uint8_t* pano, uint8_t* covered) {
+    const int nt = (int)tiles.size(), H = cv.H, W = cv.W;
+    const size_t tmax = (size_t)std::min(o.tile_h, H) * std::min(o.tile_w, W);
+    Ws<float4> F(tmax);
+    Ws<uint8_t> cov(tmax);
+    std::vector<Ws<float4>> store;
+    const std::vector<int> hbox = per_tile_footprints(cv, dimgs, n_img, o, tiles);
+    for (int t = 0; t < nt; ++t) {
+        const TileRect& tl = tiles[t];
+        const int r0 = tl.r0, c0 = tl.c0, ht = tl.ht, wt = tl.wt;
+        const size_t T = (size_t)ht * wt;
+        const dim3 g2(cdiv(wt, 32), cdiv(ht, 8));
+        if (o.blending == APS_BLEND_NONE) {
+            APS_HIP(hipMemsetAsync(F, 0, T * sizeof(float4), stream()));
+            APS_HIP(hipMemsetAsync(cov, 0, T, stream()));
+            for (int i = 0; i < n_img; ++i)
+                none_fuse_kernel<<<g2, 256, 0, stream()>>>(cv, dimgs, i, r0, c0, ht, wt, o.angle_power, o.none_policy, F, cov);
+            check_launch("none_fuse_kernel");
+        } else {
+            std::vector<int> contrib;
+            std::vector<Rect> rects;
+            for (int i = 0; i < n_img; ++i) {
+                const int* b = &hbox[((size_t)t * n_img + i) * 4];
+                if (b[2] > b[0] && b[3] > b[1]) {
+                    contrib.push_back(i);
+                    rects.push_back(Rect{b[0], b[1], b[2], b[3]});
+                }
+            }
+            const int K = (int)contrib.size();
+            // above kMaxK layers the per-pixel kernels take an uploaded pointer table and no footprints
+            const bool culled = K <= kMaxK && !std::getenv("APS_RENDER_NO_CULL");
+            if (!culled)
+                for (auto& r : rects) r = Rect{0, 0, wt, ht};
+            if (K == 0) {
+                APS_HIP(hipMemsetAsync(F, 0, T * sizeof(float4), stream()));
+                APS_HIP(hipMemsetAsync(cov, 0, T, stream()));
+            } else {
+                if ((int)store.size() < K) store.resize(K);
+                std::vector<float4*> layers(K);
+                const float wf_floor = o.blending == APS_BLEND_LINEAR ? 1e-4f : 0.f;
+                {
+                    Prof prof("warp_layer");
+                    for (int k = 0; k < K; ++k) {
+                        if (store[k].n < T) store[k].alloc(tmax);
+                        layers[k] = store[k];
+                        const Rect& rc = rects[k];
+                        warp_layer_kernel<<<dim3(cdiv(rc.x1 - rc.x0, 32), cdiv(rc.y1 - rc.y0, 8)), 256, 0, stream()>>>(
+                            cv, dimgs, contrib[k], r0, c0, wt, rc, o.angle_power, wf_floor, layers[k]);
+                    }
+                }
+                check_launch("warp_layer_kernel");
+                if (o.blending == APS_BLEND_LINEAR) {
+                    if (K <= kMaxK) {
+                        linear_fuse_kernel<PtrTab><<<cdiv(T, 256), 256, 0, stream()>>>(
+                            make_tab(layers.data(), K), make_rtab(rects.data(), K), culled ? 1 : 0, K, wt, T, F, cov);
+                        check_launch("linear_fuse_kernel");
+                    } else {
+                        Ws<float4*> dl(K);
+                        APS_HIP(hipMemcpyAsync(dl, layers.data(), K * sizeof(float4*), hipMemcpyHostToDevice, stream()));
+                        linear_fuse_kernel<float4* const*><<<cdiv(T, 256), 256, 0, stream()>>>(dl.get(), RectTab{}, 0, K, wt, T, F, cov);
+                        check_launch("linear_fuse_kernel");
+                        APS_HIP(hipStreamSynchronize(stream()));
+                    }
+                } else {
+                    // fuseTile's normalisation (:991-1006) and multiBandBlending's own (:72-85), one pass
+                    normalize_weights(layers, culled ? rects.data() : nullptr, ht, wt, 1, 1, cov);
+                    multiband_device(layers, culled ? rects.data() : nullptr, ht, wt, o.pyr_levels, o.pyr_sigma, F);
+                }
+            }
+        }
+        paint_kernel<<<dim3(cdiv(wt, 256), ht), 256, 0, stream()>>>(F, cov, r0, c0, ht, wt, H, W, o.canvas_white, out_layout, pano, covered);
+        check_launch("paint_kernel");
+    }
+}
+
 }  // namespace aps
 
 using namespace aps;
@@ -1101,24 +1216,6 @@ int aps_render(const aps_image* images, int n_img, const aps_canvas* canvas,
 
 // the tile loop for the tiles t (row-major index) with first <= t < last and (t - first) % step == 0; every = all tiles of the canvas
 static int render_tiles_impl(const aps_image* images, int n_img, const aps_canvas* canvas, const aps_render_opts* opts, int out_layout,
-                             int tile_first, int tile_step, int tile_last, bool every, uint8_t* pano, uint8_t* covered);
-
-int aps_render_tiles(const aps_image* images, int n_img, const aps_canvas* canvas,
-                     const aps_render_opts* opts, int out_layout, int tile_first, int tile_step,
-                     uint8_t* pano, uint8_t* covered) {
-    if (!(tile_step >= 1 && tile_first >= 0 && tile_first < tile_step))
-        return guarded([&] { fail(APS_E_ARG, "bad tile subset"); });
-    return render_tiles_impl(images, n_img, canvas, opts, out_layout, tile_first, tile_step, 0x7fffffff, tile_step == 1, pano, covered);
-}
-
-int aps_render_tile_range(const aps_image* images, int n_img, const aps_canvas* canvas, const aps_render_opts* opts, int out_layout,
-                          int tile_begin, int tile_end, uint8_t* pano, uint8_t* covered) {
-    if (!(tile_begin >= 0 && tile_end >= tile_begin))
-        return guarded([&] { fail(APS_E_ARG, "bad tile range"); });
-    return render_tiles_impl(images, n_img, canvas, opts, out_layout, tile_begin, 1, tile_end, false, pano, covered);
-}
-
-static int render_tiles_impl(const aps_image* images, int n_img, const aps_canvas* canvas, const aps_render_opts* opts, int out_layout,
                              int tile_first, int tile_step, int tile_last, bool every, uint8_t* pano, uint8_t* covered) {
     return guarded([&] {
         APS_REQUIRE(images && canvas && opts && pano, APS_E_ARG, "NULL argument");
@@ -1136,24 +1233,18 @@ static int render_tiles_impl(const aps_image* images, int n_img, const aps_canva
         // all tiles: every image's pixels at once, converted while the host works out the footprints; a share of the tiles (a
         // rank of a sharded render): tables now, pixels once the footprints say which images the share meets
         prepare_images(images, n_img, P, every);
-        const std::function<void(const std::vector<char>&)> convert = [&P](const std::vector<char>& used) { convert_images(P, &used); };
+        const NeedImages convert = [&P](const std::vector<char>& used) { convert_images(P, &used); };
         const DevCanvas cv = make_canvas(*canvas);
-        const int H = cv.H, W = cv.W;
+        const int H = cv.H, W = cv.W, TH = opts->tile_h, TW = opts->tile_w;
         const size_t HW = (size_t)H * W;
         Out<uint8_t> oP(pano, HW * 3), oC(covered, HW);
-        const int TH = opts->tile_h, TW = opts->tile_w;
-        const size_t tmax = (size_t)std::min(TH, H) * std::min(TW, W);
-        Ws<float4> F(tmax);
-        Ws<uint8_t> cov(tmax);
-        std::vector<Ws<float4>> store;
         // a host buffer receives the whole canvas back: start from its current content so that tiles of
         // other ranks are left untouched
         if (!every) {
             if (oP.host) APS_HIP(hipMemcpyAsync(oP.d, oP.host, HW * 3, hipMemcpyHostToDevice, stream()));
             if (oC.host) APS_HIP(hipMemcpyAsync(oC.d, oC.host, HW, hipMemcpyHostToDevice, stream()));
         }
-        using Tile = TileRect;
-        std::vector<Tile> tiles;
+        std::vector<TileRect> tiles;
         int tile_index = -1;
         for (int r0 = 0; r0 < H; r0 += TH)
             for (int c0 = 0; c0 < W; c0 += TW) {
@@ -1161,133 +1252,34 @@ static int render_tiles_impl(const aps_image* images, int n_img, const aps_canva
                 if (tile_index < tile_first || tile_index >= tile_last || (tile_index - tile_first) % tile_step != 0) continue;
                 tiles.push_back({r0, c0, std::min(TH, H - r0), std::min(TW, W - c0)});
             }
-        const int nt = (int)tiles.size();
-        // multiband: all tiles level-major in one launch sequence (render_batch.hip); APS_RENDER_LEGACY=1 keeps the
-        // per-tile path below, whose arithmetic the batched kernels reproduce bit for bit
-        if (opts->blending == APS_BLEND_MULTIBAND && !std::getenv("APS_RENDER_LEGACY") &&
-            render_multiband_batched(P.dev, P.host.data(), n_img, cv, *opts, tiles, out_layout, oP, oC.present() ? oC.get() : nullptr, convert)) {
-            oP.commit();
-            oC.commit();
-            APS_HIP(hipStreamSynchronize(stream()));
-            return;
-        }
-        // 'linear' / 'none': one fused launch over all tiles (render_batch.hip, rw_fuse_kernel); APS_RENDER_LEGACY=1 keeps the
-        // per-tile kernels below, whose bytes it reproduces
-        if (opts->blending != APS_BLEND_MULTIBAND && !std::getenv("APS_RENDER_LEGACY") &&
-            render_fuse_batched(P.dev, P.host.data(), n_img, cv, *opts, tiles, out_layout, oP, oC.present() ? oC.get() : nullptr, convert)) {
-            oP.commit();
-            oC.commit();
-            APS_HIP(hipStreamSynchronize(stream()));
-            return;
-        }
-        convert_images(P, nullptr);  // the per-tile path below samples whatever its cover pass finds
-        // phase 1: footprint of every image in every tile (the reference skips images with ~any(Mi), :989;
-        // here the bounding box of Mi also bounds all later work on that layer); one read-back
-        std::vector<int> hbox((size_t)nt * n_img * 4, 0);
-        if (opts->blending != APS_BLEND_NONE && nt > 0) {
-            const int nby_max = cdiv(std::min(TH, H), 8);
-            std::vector<int> dims((size_t)nt * 4);
-            for (int t = 0; t < nt; ++t) {
-                int xs = 0;
-                while ((cdiv(tiles[t].wt, 32) >> xs) > 64 || (((cdiv(tiles[t].wt, 32) - 1) >> xs) > 63)) ++xs;
-                dims[4 * t + 0] = tiles[t].ht;
-                dims[4 * t + 1] = tiles[t].wt;
-                dims[4 * t + 2] = cdiv(tiles[t].ht, 8);
-                dims[4 * t + 3] = xs;
-            }
-            Ws<unsigned long long> rowmask((size_t)nt * n_img * nby_max);
-            Ws<int> bbox(hbox.size()), ddims(dims.size());
-            APS_HIP(hipMemsetAsync(rowmask, 0, (size_t)nt * n_img * nby_max * sizeof(unsigned long long), stream()));
-            APS_HIP(hipMemcpyAsync(ddims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
-            {
-                Prof prof("cover");
-                for (int t = 0; t < nt; ++t) {
-                    const Tile& tl = tiles[t];
-                    cover_kernel<<<dim3(cdiv(tl.wt, 32), cdiv(tl.ht, 8)), 256, 0, stream()>>>(
-                        cv, P.dev, n_img, tl.r0, tl.c0, tl.ht, tl.wt, opts->angle_power, nby_max, dims[4 * t + 3],
-                        std::getenv("APS_RENDER_NO_CULL") ? 0 : 1, rowmask.get() + (size_t)t * n_img * nby_max);
-                }
-                footprint_kernel<<<cdiv((size_t)nt * n_img, 256), 256, 0, stream()>>>(rowmask, ddims, n_img, nby_max,
-                                                                                     nt * n_img, bbox);
-            }
-            check_launch("cover_kernel");
-            APS_HIP(hipMemcpyAsync(hbox.data(), bbox, hbox.size() * sizeof(int), hipMemcpyDeviceToHost, stream()));
-            APS_HIP(hipStreamSynchronize(stream()));  // also keeps `dims` alive until its upload has run
-        }
-        // phase 2: tiles back to back on the stream, no host round trip in between
-        for (int t = 0; t < nt; ++t) {
-            const Tile& tl = tiles[t];
-            const int r0 = tl.r0, c0 = tl.c0, ht = tl.ht, wt = tl.wt;
-            const size_t T = (size_t)ht * wt;
-            const dim3 g2(cdiv(wt, 32), cdiv(ht, 8));
-            if (opts->blending == APS_BLEND_NONE) {
-                APS_HIP(hipMemsetAsync(F, 0, T * sizeof(float4), stream()));
-                APS_HIP(hipMemsetAsync(cov, 0, T, stream()));
-                for (int i = 0; i < n_img; ++i)
-                    none_fuse_kernel<<<g2, 256, 0, stream()>>>(cv, P.dev, i, r0, c0, ht, wt, opts->angle_power,
-                                                               opts->none_policy, F, cov);
-                check_launch("none_fuse_kernel");
-            } else {
-                std::vector<int> contrib;
-                std::vector<Rect> rects;
-                for (int i = 0; i < n_img; ++i) {
-                    const int* b = &hbox[((size_t)t * n_img + i) * 4];
-                    if (b[2] > b[0] && b[3] > b[1]) {
-                        contrib.push_back(i);
-                        rects.push_back(Rect{b[0], b[1], b[2], b[3]});
-                    }
-                }
-                const int K = (int)contrib.size();
-                // above kMaxK layers the per-pixel kernels take an uploaded pointer table and no footprints
-                const bool culled = K <= kMaxK && !std::getenv("APS_RENDER_NO_CULL");
-                if (!culled)
-                    for (auto& r : rects) r = Rect{0, 0, wt, ht};
-                if (K == 0) {
-                    APS_HIP(hipMemsetAsync(F, 0, T * sizeof(float4), stream()));
-                    APS_HIP(hipMemsetAsync(cov, 0, T, stream()));
-                } else {
-                    if ((int)store.size() < K) store.resize(K);
-                    std::vector<float4*> layers(K);
-                    const float wf_floor = opts->blending == APS_BLEND_LINEAR ? 1e-4f : 0.f;
-                    {
-                        Prof prof("warp_layer");
-                        for (int k = 0; k < K; ++k) {
-                            if (store[k].n < T) store[k].alloc(tmax);
-                            layers[k] = store[k];
-                            const Rect& rc = rects[k];
-                            warp_layer_kernel<<<dim3(cdiv(rc.x1 - rc.x0, 32), cdiv(rc.y1 - rc.y0, 8)), 256, 0, stream()>>>(
-                                cv, P.dev, contrib[k], r0, c0, wt, rc, opts->angle_power, wf_floor, layers[k]);
-                        }
-                    }
-                    check_launch("warp_layer_kernel");
-                    if (opts->blending == APS_BLEND_LINEAR) {
-                        if (K <= kMaxK) {
-                            linear_fuse_kernel<PtrTab><<<cdiv(T, 256), 256, 0, stream()>>>(
-                                make_tab(layers.data(), K), make_rtab(rects.data(), K), culled ? 1 : 0, K, wt, T, F, cov);
-                            check_launch("linear_fuse_kernel");
-                        } else {
-                            Ws<float4*> dl(K);
-                            APS_HIP(hipMemcpyAsync(dl, layers.data(), K * sizeof(float4*), hipMemcpyHostToDevice, stream()));
-                            linear_fuse_kernel<float4* const*><<<cdiv(T, 256), 256, 0, stream()>>>(dl.get(), RectTab{}, 0, K, wt, T, F, cov);
-                            check_launch("linear_fuse_kernel");
-                            APS_HIP(hipStreamSynchronize(stream()));
-                        }
-                    } else {
-                        // fuseTile's normalisation (:991-1006) and multiBandBlending's own (:72-85), one pass
-                        normalize_weights(layers, culled ? rects.data() : nullptr, ht, wt, 1, 1, cov);
-                        multiband_device(layers, culled ? rects.data() : nullptr, ht, wt, opts->pyr_levels, opts->pyr_sigma, F);
-                    }
-                }
-            }
-            paint_kernel<<<dim3(cdiv(wt, 256), ht), 256, 0, stream()>>>(
-                F, cov, r0, c0, ht, wt, H, W, opts->canvas_white, out_layout, oP,
-                oC.present() ? oC.get() : nullptr);
-            check_launch("paint_kernel");
+        // All tiles in one call (render_batch.hip): multiband level-major in one launch sequence, 'linear' / 'none' as one fused
+        // launch.  APS_RENDER_LEGACY=1, or a configuration the batched kernels are not built for, takes the per-tile path, whose
+        // bytes they reproduce.
+        uint8_t* const d_cov = oC.present() ? oC.get() : nullptr;
+        const auto batched = opts->blending == APS_BLEND_MULTIBAND ? render_multiband_batched : render_fuse_batched;
+        if (std::getenv("APS_RENDER_LEGACY") || !batched(P.dev, P.host.data(), n_img, cv, *opts, tiles, out_layout, oP, d_cov, convert)) {
+            convert_images(P, nullptr);  // the per-tile path samples whatever its cover pass finds
+            render_tiles_per_tile(cv, P.dev, n_img, *opts, tiles, out_layout, oP, d_cov);
         }
         oP.commit();
         oC.commit();
         APS_HIP(hipStreamSynchronize(stream()));
     });
+}
+
+int aps_render_tiles(const aps_image* images, int n_img, const aps_canvas* canvas,
+                     const aps_render_opts* opts, int out_layout, int tile_first, int tile_step,
+                     uint8_t* pano, uint8_t* covered) {
+    if (!(tile_step >= 1 && tile_first >= 0 && tile_first < tile_step))
+        return guarded([&] { fail(APS_E_ARG, "bad tile subset"); });
+    return render_tiles_impl(images, n_img, canvas, opts, out_layout, tile_first, tile_step, 0x7fffffff, tile_step == 1, pano, covered);
+}
+
+int aps_render_tile_range(const aps_image* images, int n_img, const aps_canvas* canvas, const aps_render_opts* opts, int out_layout,
+                          int tile_begin, int tile_end, uint8_t* pano, uint8_t* covered) {
+    if (!(tile_begin >= 0 && tile_end >= tile_begin))
+        return guarded([&] { fail(APS_E_ARG, "bad tile range"); });
+    return render_tiles_impl(images, n_img, canvas, opts, out_layout, tile_begin, 1, tile_end, false, pano, covered);
 }
 
 }  // extern "C"

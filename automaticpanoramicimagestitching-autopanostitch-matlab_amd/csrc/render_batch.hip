@@ -20,15 +20,15 @@
 // are the restatement checked against oracle/render_oracle.c: tests/test_render_gpu.py compares both paths
 // bit for bit (APS_RENDER_LEGACY=1 selects the per-tile path).
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <future>
 #include <map>
 #include <thread>
 #include <vector>
-
-#include <chrono>
 
 #include "render_dev.h"
 
@@ -1572,23 +1572,302 @@ void launch_down(int r, const RwArgs& A, int l, const int* blk_ptr, int n_blocks
     }
 }
 
-}  // namespace
+// ================================================================================================
+// host side: both batched renderers as a chain of stages with one job each
+// ================================================================================================
+template <class T>
+void upload(Ws<T>& d, const std::vector<T>& h) {
+    if (!h.empty()) APS_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, stream()));
+}
 
-namespace {
+// Exclusive prefix of blocks_of(i), i in [0, count), into p[0 .. count]; p[count] = the total, which is returned.  A launch's
+// block index and the segment search of its kernel (find_segment) are ints: the total stays below 2^30.
+template <class BlocksOf>
+int block_prefix(int* p, int count, const char* what, BlocksOf blocks_of) {
+    long long run = 0;
+    for (int i = 0; i < count; ++i) {
+        p[i] = (int)run;
+        run += blocks_of(i);
+    }
+    APS_REQUIRE(run < (1ll << 30), APS_E_DIM, "too many %s blocks in one render call (%lld)", what, run);
+    p[count] = (int)run;
+    return (int)run;
+}
 
+// ---- stage: the tiles --------------------------------------------------------------------------------------------------------
+// What is known about the tiles before any footprint: the RwTile records with their pyramid shape (pyramid_levels; 'linear' and
+// 'none' ask for one level), the cover pass's column shifts, and the sizes of the canvas-sized planes and of the collapse planes.
+struct TilePlan {
+    std::vector<RwTile> tiles;
+    std::vector<int> xshift;  // cover_xshift of every tile
+    int max_ht = 0, max_wt = 0, max_nl = 1;
+    long long plane_px = 0;  // pixels of all tiles
+    long long f_total = 0;   // float4s of all F_l, l >= 1
+    long long g_total = 0;   // float4s of the compact G store (known once build_entries has run)
+};
+TilePlan plan_tiles(const std::vector<TileRect>& tiles, int levels) {
+    APS_REQUIRE(levels <= kML, APS_E_INTERNAL, "plan_tiles: %d levels", levels);
+    TilePlan P;
+    std::vector<int> lh, lw;
+    for (const TileRect& tr : tiles) {
+        RwTile T;
+        std::memset(&T, 0, sizeof T);
+        T.r0 = tr.r0;
+        T.c0 = tr.c0;
+        T.ht = tr.ht;
+        T.wt = tr.wt;
+        pyramid_levels(T.ht, T.wt, levels, lh, lw);
+        T.nl = (int)lh.size();
+        std::copy(lh.begin(), lh.end(), T.lh);
+        std::copy(lw.begin(), lw.end(), T.lw);
+        for (int l = 0; l + 1 < T.nl; ++l) {
+            if (rows_first(T.lh[l], T.lw[l], T.lh[l + 1], T.lw[l + 1])) T.rf_down |= 1 << l;
+            if (rows_first(T.lh[l + 1], T.lw[l + 1], T.lh[l], T.lw[l])) T.rf_up |= 1 << l;
+        }
+        T.plane = P.plane_px;
+        P.plane_px += (long long)T.ht * T.wt;
+        for (int l = 1; l < T.nl; ++l) {
+            T.f[l] = P.f_total;
+            P.f_total += (long long)T.lh[l] * T.lw[l];
+        }
+        P.max_ht = std::max(P.max_ht, T.ht);
+        P.max_wt = std::max(P.max_wt, T.wt);
+        P.max_nl = std::max(P.max_nl, T.nl);
+        P.xshift.push_back(cover_xshift(T.wt));
+        P.tiles.push_back(T);
+    }
+    return P;
+}
+
+// ---- stage: the tap tables ---------------------------------------------------------------------------------------------------
+// One table per distinct (in_len, out_len) of a shrink or an enlargement, shared by every tile, row and column that resizes so;
+// a tile refers to its tables by their offset in output samples.
+struct TapTables {
+    std::vector<TapJob> jobs;
+    std::map<std::pair<int, int>, int> down_off, up_off;  // (in_len, out_len) -> offset
+    int n_down = 0, n_up = 0;  // output samples of all shrinks / enlargements
+    int ncp = 0;               // weights per output sample of the fused shrink
+    Ws<TapJob> d_jobs;
+    Ws<int> td_idx, tu_idx, cd_s0;
+    Ws<float> td_w, tu_w, cd_w;
+
+    int tap_table(int in_len, int out_len, bool down) {
+        auto& m = down ? down_off : up_off;
+        int& total = down ? n_down : n_up;
+        auto it = m.find({in_len, out_len});
+        if (it != m.end()) return it->second;
+        const int off = total;
+        m[{in_len, out_len}] = off;
+        jobs.push_back(TapJob{in_len, out_len, down ? kTD : kTU, off});
+        total += out_len;
+        return off;
+    }
+    void add_tile(RwTile& T) {
+        for (int l = 0; l + 1 < T.nl; ++l) {
+            T.tdr[l] = tap_table(T.lh[l], T.lh[l + 1], true);
+            T.tdc[l] = tap_table(T.lw[l], T.lw[l + 1], true);
+            T.tur[l] = tap_table(T.lh[l + 1], T.lh[l], false);
+            T.tuc[l] = tap_table(T.lw[l + 1], T.lw[l], false);
+        }
+    }
+    // rw_taps_kernel for every job and, unless the shrink keeps the two-step form (exact), rw_ctaps_kernel for the shrinks
+    void build(const Taps& tp, bool exact, int* d_status) {
+        ncp = (kTD + 2 * tp.r + 3) & ~3;
+        const size_t nd = (size_t)std::max(n_down, 1), nu = (size_t)std::max(n_up, 1);
+        td_idx.alloc(nd * kTD);
+        td_w.alloc(nd * kTD);
+        tu_idx.alloc(nu * kTU);
+        tu_w.alloc(nu * kTU);
+        cd_s0.alloc(nd);
+        cd_w.alloc(nd * ncp);
+        d_jobs.alloc(std::max<size_t>(jobs.size(), 1));
+        if (jobs.empty()) return;
+        upload(d_jobs, jobs);
+        int longest = 1;
+        for (const TapJob& j : jobs) longest = std::max(longest, j.out_len);
+        const dim3 grid(cdiv(longest, 256), (unsigned)jobs.size());
+        rw_taps_kernel<<<grid, 256, 0, stream()>>>(d_jobs, td_idx, td_w, tu_idx, tu_w, d_status);
+        check_launch("rw_taps_kernel");
+        if (exact) return;
+        rw_ctaps_kernel<<<grid, 256, 0, stream()>>>(d_jobs, tp, ncp, cd_s0, cd_w, d_status);
+        check_launch("rw_ctaps_kernel");
+    }
+    void set_args(RwArgs& A) const {
+        A.td_idx = td_idx;
+        A.td_w = td_w;
+        A.tu_idx = tu_idx;
+        A.tu_w = tu_w;
+        A.cd_s0 = cd_s0;
+        A.cd_w = cd_w;
+    }
+};
+
+// ---- stage: the kernel arguments both renderers set --------------------------------------------------------------------------
+RwArgs base_args(const RwTile* d_tiles, int nt, const DevImage* dimgs, const DevCanvas& cv, const aps_render_opts& o, int out_layout,
+                 uint8_t* pano, uint8_t* covered) {
+    RwArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.tiles = d_tiles;
+    A.n_tiles = nt;
+    A.imgs = dimgs;
+    A.cv = cv;
+    A.angle_pow = o.angle_power;
+    A.pano = pano;
+    A.covered = covered;
+    A.H = cv.H;
+    A.W = cv.W;
+    A.out_layout = out_layout;
+    A.white = o.canvas_white;
+    return A;
+}
+
+// ---- stage: footprints -------------------------------------------------------------------------------------------------------
 // Footprints on the host (cylindrical / spherical canvases): the image rectangle [1,w] x [1,h] maps to a region of the
 // canvas whose outline is the forward image of the rectangle's border (pixel -> K^-1 -> R' -> angles -> canvas pixels,
 // f64 on the f32 camera / canvas values the kernels use).  The outline, sampled in short chords and grown by half a pixel,
 // is clipped against each tile (Sutherland-Hodgman) and the clipped polygon's bounding box, padded by 3 pixels (chord sag
 // < 0.1, f32 vs f64 rounding < 0.01), is a SUPERSET of the tile pixels that sample the image - which is all a footprint must
 // be (kernels evaluate the exact predicate per pixel inside it).  This replaces the coverage kernel and its read-back.
-// Not applicable (returns false, the caller runs rw_cover_kernel): planar / stereographic canvases, an outline that
-// crosses the theta = +-pi seam, an image that contains a pole.
+// Not applicable (host_footprints returns false, the caller runs rw_cover_kernel): planar / stereographic canvases, an outline
+// that crosses the theta = +-pi seam, an image that contains a pole.
+struct Polygon {
+    std::vector<double> x, y;
+    void clear() {
+        x.clear();
+        y.clear();
+    }
+    void add(double px, double py) {
+        x.push_back(px);
+        y.push_back(py);
+    }
+};
+struct Bounds {
+    double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
+    explicit Bounds(const Polygon& p) {
+        for (size_t q = 0; q < p.x.size(); ++q) {
+            x0 = std::min(x0, p.x[q]);
+            x1 = std::max(x1, p.x[q]);
+            y0 = std::min(y0, p.y[q]);
+            y1 = std::max(y1, p.y[q]);
+        }
+    }
+};
+
+// image pixel (u, v) -> canvas pixel (x, y) and the azimuth th it lies at
+struct ToCanvas {
+    double R[9], fx, fy, cx, cy, f, o0, o1;
+    bool spherical;
+    ToCanvas(const DevImage& im, const DevCanvas& cv)
+        : fx(im.fx), fy(im.fy), cx(im.cx), cy(im.cy), f(cv.f), o0(cv.o0), o1(cv.o1), spherical(cv.mode == APS_PROJ_SPHERICAL) {
+        for (int k = 0; k < 9; ++k) R[k] = im.R[k];
+    }
+    void operator()(double u, double v, double& x, double& y, double& th) const {
+        const double c[3] = {(u - cx) / fx, (v - cy) / fy, 1.0};
+        // cam = R d  (device: cam[c] = d0 R[c] + d1 R[c+3] + d2 R[c+6])  =>  d = R' cam: d[j] = sum_c R[c + 3j] cam[c]
+        const double d0 = R[0] * c[0] + R[1] * c[1] + R[2] * c[2];
+        const double d1 = R[3] * c[0] + R[4] * c[1] + R[5] * c[2];
+        const double d2 = R[6] * c[0] + R[7] * c[1] + R[8] * c[2];
+        th = std::atan2(d0, d2);
+        const double hz = std::hypot(d0, d2);
+        const double b = spherical ? std::atan2(d1, hz) : d1 / hz;
+        x = (th - o0) * f;
+        y = (b - o1) * f;
+    }
+};
+
+// a pole inside the w x h image: the elevation has an interior extremum, the outline does not bound the region
+bool contains_pole(const ToCanvas& tc, int w, int h) {
+    for (int sgn = -1; sgn <= 1; sgn += 2) {
+        const double cz = tc.R[5] * sgn;  // cam = R (0, sgn, 0)'
+        if (cz > 1e-9) {
+            const double u = tc.fx * (tc.R[3] * sgn / cz) + tc.cx, v = tc.fy * (tc.R[4] * sgn / cz) + tc.cy;
+            if (u >= -1 && u <= w + 2 && v >= -1 && v <= h + 2) return true;
+        }
+    }
+    return false;
+}
+
+// The border of the w x h image, grown by half a pixel, on the canvas; false when it crosses the seam or is not finite.
+bool image_outline(const ToCanvas& tc, int w, int h, Polygon& out) {
+    out.clear();
+    // chord length ~ 1/64 of the shorter side (at least 4 px): the sag stays far below the 3-pixel pad
+    const double u0 = 0.5, u1 = w + 0.5, v0 = 0.5, v1 = h + 0.5, step = std::max(4.0, std::min(w, h) / 64.0);
+    const double kPi = 3.14159265358979323846;
+    double prev_th = 0;
+    bool first = true, ok = true;
+    auto add = [&](double u, double v) {
+        double x, y, th;
+        tc(u, v, x, y, th);
+        if (!std::isfinite(x) || !std::isfinite(y)) ok = false;
+        if (!first && std::fabs(th - prev_th) > 0.5 * kPi) ok = false;  // seam crossing (or a degenerate camera)
+        prev_th = th;
+        first = false;
+        out.add(x, y);
+    };
+    for (double u = u0; u < u1; u += step) add(u, v0);
+    for (double v = v0; v < v1; v += step) add(u1, v);
+    for (double u = u1; u > u0; u -= step) add(u, v1);
+    for (double v = v1; v > v0; v -= step) add(u0, v);
+    add(u0, v0);
+    return ok;
+}
+
+// The outline clipped against the four sides of the tile (Sutherland-Hodgman; q and r are scratch): the clipped polygon's
+// bounding box, padded by 3 pixels, in tile coordinates; all zero when nothing is left.
+Rect clip_to_tile(const Polygon& outline, const RwTile& T, Polygon& q, Polygon& r) {
+    const double tx0 = T.c0 - 0.5, tx1 = T.c0 + T.wt - 0.5, ty0 = T.r0 - 0.5, ty1 = T.r0 + T.ht - 0.5;
+    q = outline;
+    for (int side = 0; side < 4 && !q.x.empty(); ++side) {
+        r.clear();
+        const size_t n = q.x.size();
+        auto inside = [&](double x, double y) { return side == 0 ? x >= tx0 : side == 1 ? x <= tx1 : side == 2 ? y >= ty0 : y <= ty1; };
+        for (size_t k = 0; k < n; ++k) {
+            const double ax = q.x[k], ay = q.y[k], bx = q.x[(k + 1) % n], by = q.y[(k + 1) % n];
+            const bool ia = inside(ax, ay), ib = inside(bx, by);
+            if (ia != ib) {
+                if (side < 2) {
+                    const double lim = side == 0 ? tx0 : tx1;
+                    r.add(lim, ay + (lim - ax) / (bx - ax) * (by - ay));
+                } else {
+                    const double lim = side == 2 ? ty0 : ty1;
+                    r.add(ax + (lim - ay) / (by - ay) * (bx - ax), lim);
+                }
+            }
+            if (ib) r.add(bx, by);
+        }
+        std::swap(q, r);
+    }
+    if (q.x.empty()) return Rect{0, 0, 0, 0};
+    const Bounds c(q);
+    const double m = 3.0;
+    const Rect b{std::max(0, (int)std::floor(c.x0 - m) - T.c0), std::max(0, (int)std::floor(c.y0 - m) - T.r0),
+                 std::min(T.wt, (int)std::ceil(c.x1 + m) + 1 - T.c0), std::min(T.ht, (int)std::ceil(c.y1 + m) + 1 - T.r0)};
+    return b.x1 <= b.x0 || b.y1 <= b.y0 ? Rect{0, 0, 0, 0} : b;
+}
+
+// images [i_begin, i_end) against every tile; hbox (all zero on entry): [tile][image][x0 y0 x1 y1]
+bool host_footprints_range(const DevImage* himgs, int n_img, int i_begin, int i_end, const DevCanvas& cv, const std::vector<RwTile>& tiles,
+                           std::vector<int>& hbox) {
+    Polygon outline, q, r;
+    for (int i = i_begin; i < i_end; ++i) {
+        const DevImage& im = himgs[i];
+        if (!(im.fx > 0.f) || !(im.fy > 0.f)) return false;
+        const ToCanvas tc(im, cv);
+        if (contains_pole(tc, im.w, im.h) || !image_outline(tc, im.w, im.h, outline)) return false;
+        const Bounds ob(outline);
+        for (size_t t = 0; t < tiles.size(); ++t) {
+            const RwTile& T = tiles[t];
+            if (ob.x1 < T.c0 - 0.5 || ob.x0 > T.c0 + T.wt - 0.5 || ob.y1 < T.r0 - 0.5 || ob.y0 > T.r0 + T.ht - 0.5) continue;
+            const Rect b = clip_to_tile(outline, T, q, r);
+            std::memcpy(&hbox[(t * n_img + i) * 4], &b, sizeof b);
+        }
+    }
+    return true;
+}
+
 // The images are independent (image i writes hbox[(t * n_img + i) * 4 ..] only), so the loop runs on a few host threads
 // (round 6: 0.65 ms of every render call on one thread, in front of the call's first kernel launch - most of a rank's fixed
 // render cost at 8 ranks).  APS_RENDER_HOST_THREADS=1: one thread.
-static bool host_footprints_range(const DevImage* himgs, int n_img, int i_begin, int i_end, const DevCanvas& cv, const std::vector<RwTile>& tiles,
-                                  std::vector<int>& hbox);
 bool host_footprints(const DevImage* himgs, int n_img, const DevCanvas& cv, const std::vector<RwTile>& tiles, std::vector<int>& hbox) {
     if (cv.mode != APS_PROJ_SPHERICAL && cv.mode != APS_PROJ_CYLINDRICAL) return false;
     std::fill(hbox.begin(), hbox.end(), 0);
@@ -1605,293 +1884,203 @@ bool host_footprints(const DevImage* himgs, int n_img, const DevCanvas& cv, cons
     for (auto& p : parts) ok = p.get() && ok;
     return ok;
 }
-static bool host_footprints_range(const DevImage* himgs, int n_img, int i_begin, int i_end, const DevCanvas& cv, const std::vector<RwTile>& tiles,
-                                  std::vector<int>& hbox) {
-    const double f = (double)cv.f, o0 = (double)cv.o0, o1 = (double)cv.o1;
-    const int nt = (int)tiles.size();
-    std::vector<double> px, py, qx, qy, rx, ry;
-    const double kPi = 3.14159265358979323846;
-    for (int i = i_begin; i < i_end; ++i) {
-        const DevImage& im = himgs[i];
-        if (!(im.fx > 0.f) || !(im.fy > 0.f)) return false;
-        const double R[9] = {im.R[0], im.R[1], im.R[2], im.R[3], im.R[4], im.R[5], im.R[6], im.R[7], im.R[8]};
-        auto to_canvas = [&](double u, double v, double& x, double& y, double& th) {
-            const double c[3] = {(u - im.cx) / im.fx, (v - im.cy) / im.fy, 1.0};
-            // cam = R d  (device: cam[c] = d0 R[c] + d1 R[c+3] + d2 R[c+6])  =>  d = R' cam: d[j] = sum_c R[c + 3j] cam[c]
-            const double d0 = R[0] * c[0] + R[1] * c[1] + R[2] * c[2];
-            const double d1 = R[3] * c[0] + R[4] * c[1] + R[5] * c[2];
-            const double d2 = R[6] * c[0] + R[7] * c[1] + R[8] * c[2];
-            th = std::atan2(d0, d2);
-            const double hz = std::hypot(d0, d2);
-            const double b = cv.mode == APS_PROJ_SPHERICAL ? std::atan2(d1, hz) : d1 / hz;
-            x = (th - o0) * f;
-            y = (b - o1) * f;
-        };
-        // a pole inside the image: the elevation has an interior extremum, the outline does not bound the region
-        for (int sgn = -1; sgn <= 1; sgn += 2) {
-            const double cz = R[5] * sgn;  // cam = R (0, sgn, 0)'
-            if (cz > 1e-9) {
-                const double u = im.fx * (R[3] * sgn / cz) + im.cx, v = im.fy * (R[4] * sgn / cz) + im.cy;
-                if (u >= -1 && u <= im.w + 2 && v >= -1 && v <= im.h + 2) return false;
-            }
-        }
-        px.clear();
-        py.clear();
-        // chord length ~ 1/64 of the shorter side (at least 4 px): the sag stays far below the 3-pixel pad
-        const double u0 = 0.5, u1 = im.w + 0.5, v0 = 0.5, v1 = im.h + 0.5, step = std::max(4.0, std::min(im.w, im.h) / 64.0);
-        double prev_th = 0;
-        bool first = true, ok = true;
-        auto add = [&](double u, double v) {
-            double x, y, th;
-            to_canvas(u, v, x, y, th);
-            if (!std::isfinite(x) || !std::isfinite(y)) ok = false;
-            if (!first && std::fabs(th - prev_th) > 0.5 * kPi) ok = false;  // seam crossing (or a degenerate camera)
-            prev_th = th;
-            first = false;
-            px.push_back(x);
-            py.push_back(y);
-        };
-        for (double u = u0; u < u1; u += step) add(u, v0);
-        for (double v = v0; v < v1; v += step) add(u1, v);
-        for (double u = u1; u > u0; u -= step) add(u, v1);
-        for (double v = v1; v > v0; v -= step) add(u0, v);
-        add(u0, v0);
-        if (!ok) return false;
-        double bx0 = 1e300, bx1 = -1e300, by0 = 1e300, by1 = -1e300;
-        for (size_t q = 0; q < px.size(); ++q) {
-            bx0 = std::min(bx0, px[q]);
-            bx1 = std::max(bx1, px[q]);
-            by0 = std::min(by0, py[q]);
-            by1 = std::max(by1, py[q]);
-        }
-        for (int t = 0; t < nt; ++t) {
-            const RwTile& T = tiles[t];
-            const double tx0 = T.c0 - 0.5, tx1 = T.c0 + T.wt - 0.5, ty0 = T.r0 - 0.5, ty1 = T.r0 + T.ht - 0.5;
-            if (bx1 < tx0 || bx0 > tx1 || by1 < ty0 || by0 > ty1) continue;
-            // Sutherland-Hodgman against the four sides of the tile
-            qx = px;
-            qy = py;
-            for (int side = 0; side < 4 && !qx.empty(); ++side) {
-                rx.clear();
-                ry.clear();
-                const size_t n = qx.size();
-                auto inside = [&](double x, double y) {
-                    return side == 0 ? x >= tx0 : side == 1 ? x <= tx1 : side == 2 ? y >= ty0 : y <= ty1;
-                };
-                for (size_t q = 0; q < n; ++q) {
-                    const double ax = qx[q], ay = qy[q], bx = qx[(q + 1) % n], by = qy[(q + 1) % n];
-                    const bool ia = inside(ax, ay), ib = inside(bx, by);
-                    if (ia != ib) {
-                        double tt;
-                        if (side < 2) {
-                            const double lim = side == 0 ? tx0 : tx1;
-                            tt = (lim - ax) / (bx - ax);
-                            rx.push_back(lim);
-                            ry.push_back(ay + tt * (by - ay));
-                        } else {
-                            const double lim = side == 2 ? ty0 : ty1;
-                            tt = (lim - ay) / (by - ay);
-                            rx.push_back(ax + tt * (bx - ax));
-                            ry.push_back(lim);
-                        }
-                    }
-                    if (ib) {
-                        rx.push_back(bx);
-                        ry.push_back(by);
-                    }
-                }
-                qx.swap(rx);
-                qy.swap(ry);
-            }
-            if (qx.empty()) continue;
-            double cx0 = 1e300, cx1 = -1e300, cy0 = 1e300, cy1 = -1e300;
-            for (size_t q = 0; q < qx.size(); ++q) {
-                cx0 = std::min(cx0, qx[q]);
-                cx1 = std::max(cx1, qx[q]);
-                cy0 = std::min(cy0, qy[q]);
-                cy1 = std::max(cy1, qy[q]);
-            }
-            const double m = 3.0;
-            int* b = &hbox[((size_t)t * n_img + i) * 4];
-            b[0] = std::max(0, (int)std::floor(cx0 - m) - T.c0);
-            b[1] = std::max(0, (int)std::floor(cy0 - m) - T.r0);
-            b[2] = std::min(T.wt, (int)std::ceil(cx1 + m) + 1 - T.c0);
-            b[3] = std::min(T.ht, (int)std::ceil(cy1 + m) + 1 - T.r0);
-            if (b[2] <= b[0] || b[3] <= b[1]) b[0] = b[1] = b[2] = b[3] = 0;
-        }
+
+// The exact footprints: the coverage kernel over all tiles and one read-back.
+std::vector<int> device_footprints(const RwArgs& A, int n_img, const TilePlan& P, const int* d_xshift) {
+    const int nt = (int)P.tiles.size(), nby_max = cdiv(P.max_ht, 8);
+    Ws<unsigned long long> rowmask((size_t)nt * n_img * nby_max);
+    Ws<int> d_bbox((size_t)nt * n_img * 4);
+    std::vector<int> dbox((size_t)nt * n_img * 4);
+    APS_HIP(hipMemsetAsync(rowmask, 0, (size_t)nt * n_img * nby_max * sizeof(unsigned long long), stream()));
+    {
+        Prof prof("render_cover");
+        rw_cover_kernel<<<dim3(cdiv(P.max_wt, 32), cdiv(P.max_ht, 8), nt), 256, 0, stream()>>>(A, n_img, nby_max, d_xshift, rowmask);
+        rw_footprint_kernel<<<cdiv((size_t)nt * n_img, 256), 256, 0, stream()>>>(rowmask, A.tiles, d_xshift, n_img, nby_max, nt * n_img,
+                                                                                d_bbox);
     }
-    return true;
+    check_launch("rw_cover_kernel");
+    APS_HIP(hipMemcpyAsync(dbox.data(), d_bbox, dbox.size() * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+    return dbox;
+}
+
+// test hook (APS_RENDER_CHECK_RECTS): every exact footprint must lie inside its analytic rectangle
+void require_rects_contain(const std::vector<int>& hbox, const std::vector<int>& dbox, int n_img, const TilePlan& P) {
+    for (size_t e = 0; e < dbox.size() / 4; ++e) {
+        const int* d = &dbox[4 * e];
+        const int* hb = &hbox[4 * e];
+        if (!(d[2] > d[0] && d[3] > d[1])) continue;
+        // the coverage kernel reports whole 32 x 8 blocks (32 << xshift wide): compare on that grid
+        const RwTile& T = P.tiles[e / n_img];
+        const int gx = 32 << P.xshift[e / n_img];
+        const bool inside = hb[2] > hb[0] && hb[0] / gx * gx <= d[0] && hb[1] / 8 * 8 <= d[1] &&
+                            std::min((hb[2] + gx - 1) / gx * gx, T.wt) >= d[2] && std::min((hb[3] + 7) / 8 * 8, T.ht) >= d[3];
+        APS_REQUIRE(inside, APS_E_INTERNAL,
+                    "analytic footprint [%d %d %d %d] does not contain the exact one [%d %d %d %d] (tile %zu, image %zu)", hb[0], hb[1],
+                    hb[2], hb[3], d[0], d[1], d[2], d[3], e / n_img, e % n_img);
+    }
 }
 
 // pass 1 of both batched renderers: the footprint rectangle of every image in every tile, on the host where the
-// projection allows it (no kernel, no read-back), else by the exact coverage kernel.  hbox: [tile][image][x0 y0 x1 y1].
-static void tile_footprints(const RwArgs& A, const DevImage* himgs, int n_img, const std::vector<RwTile>& ht_, const std::vector<int>& xshift,
-                            const int* d_xshift, const RwTile* d_tiles, int max_ht, int max_wt, std::vector<int>& hbox) {
-    const int nt = (int)ht_.size();
-    const DevCanvas& cv = A.cv;
-    hbox.assign((size_t)nt * n_img * 4, 0);
+// projection allows it (no kernel, no read-back), else by the exact coverage kernel.  -> [tile][image][x0 y0 x1 y1]
+std::vector<int> tile_footprints(const RwArgs& A, const DevImage* himgs, int n_img, const TilePlan& P, const int* d_xshift) {
+    std::vector<int> hbox(P.tiles.size() * n_img * 4, 0);
     const bool check_rects = std::getenv("APS_RENDER_CHECK_RECTS") != nullptr;
-    const bool analytic = !std::getenv("APS_RENDER_DEVICE_COVER") && host_footprints(himgs, n_img, cv, ht_, hbox);
-    if (!analytic || check_rects) {
-        const int nby_max = cdiv(max_ht, 8);
-        Ws<unsigned long long> rowmask((size_t)nt * n_img * nby_max);
-        Ws<int> d_bbox((size_t)nt * n_img * 4);
-        std::vector<int> dbox((size_t)nt * n_img * 4);
-        APS_HIP(hipMemsetAsync(rowmask, 0, (size_t)nt * n_img * nby_max * sizeof(unsigned long long), stream()));
-        {
-            Prof prof("render_cover");
-            rw_cover_kernel<<<dim3(cdiv(max_wt, 32), cdiv(max_ht, 8), nt), 256, 0, stream()>>>(A, n_img, nby_max, d_xshift, rowmask);
-            rw_footprint_kernel<<<cdiv((size_t)nt * n_img, 256), 256, 0, stream()>>>(rowmask, d_tiles, d_xshift, n_img, nby_max,
-                                                                                    nt * n_img, d_bbox);
-        }
-        check_launch("rw_cover_kernel");
-        APS_HIP(hipMemcpyAsync(dbox.data(), d_bbox, dbox.size() * sizeof(int), hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        if (analytic) {  // test hook: every exact footprint must lie inside its analytic rectangle
-            for (size_t e = 0; e < dbox.size() / 4; ++e) {
-                const int* d = &dbox[4 * e];
-                const int* hb = &hbox[4 * e];
-                if (!(d[2] > d[0] && d[3] > d[1])) continue;
-                // the coverage kernel reports whole 32 x 8 blocks (32 << xshift wide): compare on that grid
-                const int t_ = (int)(e / n_img), gx = 32 << xshift[t_];
-                const bool inside = hb[2] > hb[0] && hb[0] / gx * gx <= d[0] && hb[1] / 8 * 8 <= d[1] &&
-                                    std::min((hb[2] + gx - 1) / gx * gx, ht_[t_].wt) >= d[2] && std::min((hb[3] + 7) / 8 * 8, ht_[t_].ht) >= d[3];
-                APS_REQUIRE(inside, APS_E_INTERNAL,
-                            "analytic footprint [%d %d %d %d] does not contain the exact one [%d %d %d %d] (tile %zu, image %zu)",
-                            hb[0], hb[1], hb[2], hb[3], d[0], d[1], d[2], d[3], e / n_img, e % n_img);
-            }
-        } else {
-            hbox = dbox;
-        }
-    }
+    const bool analytic = !std::getenv("APS_RENDER_DEVICE_COVER") && host_footprints(himgs, n_img, A.cv, P.tiles, hbox);
+    if (analytic && !check_rects) return hbox;
+    std::vector<int> dbox = device_footprints(A, n_img, P, d_xshift);
+    if (!analytic) return dbox;
+    require_rects_contain(hbox, dbox, n_img, P);
+    return hbox;
+}
 
+// ---- stage: entries ----------------------------------------------------------------------------------------------------------
+// One entry per (tile, image) with a footprint, tile-major in ascending image order: its footprint at every level of the tile
+// (next_footprint, the step of pyramid_footprints) and where its compact G_l stores start.  Sets each tile's e0 / ne and g_total.
+std::vector<RwEntry> build_entries(TilePlan& P, const std::vector<int>& hbox, int n_img, int radius) {
+    std::vector<RwEntry> ents;
+    P.g_total = 0;
+    for (size_t t = 0; t < P.tiles.size(); ++t) {
+        RwTile& T = P.tiles[t];
+        T.e0 = (int)ents.size();
+        for (int i = 0; i < n_img; ++i) {
+            const int* b = &hbox[(t * n_img + i) * 4];
+            if (!(b[2] > b[0] && b[3] > b[1])) continue;
+            RwEntry E;
+            std::memset(&E, 0, sizeof E);
+            E.tile = (int)t;
+            E.img = i;
+            E.g[0] = clip_rect(Rect{b[0], b[1], b[2], b[3]}, T.wt, T.ht);
+            for (int l = 0; l + 1 < T.nl; ++l) E.g[l + 1] = next_footprint(E.g[l], radius, T.lh[l], T.lw[l], T.lh[l + 1], T.lw[l + 1]);
+            for (int l = 0; l < T.nl; ++l) {
+                E.off[l] = P.g_total;
+                P.g_total += (long long)(E.g[l].x1 - E.g[l].x0) * (E.g[l].y1 - E.g[l].y0);
+            }
+            ents.push_back(E);
+        }
+        T.ne = (int)ents.size() - T.e0;
+    }
+    return ents;
+}
+// the images these tiles meet: their pixels are needed from here on
+void report_used_images(const std::vector<RwEntry>& ents, int n_img, const NeedImages& need_images) {
+    std::vector<char> used(n_img, 0);
+    for (const RwEntry& E : ents) used[E.img] = 1;
+    need_images(used);
+}
+
+// ---- stage: the multiband block tables ---------------------------------------------------------------------------------------
+// Work items of every launch as prefix tables: the warp over the level-0 grid of every tile with layers; the shrink l -> l+1,
+// l = 0 .. max_nl-2, over the entries' G_(l+1) rectangles; the collapse of level l, l = 0 .. max_nl-1, over the tiles.  A tile
+// with fewer levels contributes no blocks to the levels it does not have.
+struct BlockTables {
+    std::vector<int> warp;    // [nt + 1]
+    std::vector<int> levels;  // [max_nl][ne + 1] (shrinks), then from `up_base` [max_nl][nt + 1] (collapse)
+    std::vector<int> down_blocks, up_blocks;
+    int warp_blocks = 0, ne = 0, nt = 0;
+    size_t up_base = 0;
+    size_t down_at(int l) const { return (size_t)l * (ne + 1); }
+    size_t up_at(int l) const { return up_base + (size_t)l * (nt + 1); }
+};
+BlockTables multiband_block_tables(const TilePlan& P, const std::vector<RwEntry>& ents) {
+    BlockTables B;
+    B.nt = (int)P.tiles.size();
+    B.ne = (int)ents.size();
+    B.up_base = (size_t)P.max_nl * (B.ne + 1);
+    B.warp.assign(B.nt + 1, 0);
+    B.levels.assign(B.up_base + (size_t)P.max_nl * (B.nt + 1), 0);
+    B.down_blocks.assign(P.max_nl, 0);
+    B.up_blocks.assign(P.max_nl, 0);
+    B.warp_blocks = block_prefix(B.warp.data(), B.nt, "canvas", [&](int t) {
+        const RwTile& T = P.tiles[t];
+        return T.ne > 0 ? (long long)cdiv(T.wt, kUW) * cdiv(T.ht, kUH) : 0ll;
+    });
+    for (int l = 0; l + 1 < P.max_nl; ++l)
+        B.down_blocks[l] = block_prefix(&B.levels[B.down_at(l)], B.ne, "pyramid", [&](int e) {
+            if (l + 1 >= P.tiles[ents[e].tile].nl) return 0ll;
+            const Rect& g = ents[e].g[l + 1];
+            return (long long)cdiv(std::max(g.x1 - g.x0, 0), kBW) * cdiv(std::max(g.y1 - g.y0, 0), kBH);
+        });
+    for (int l = 0; l < P.max_nl; ++l)
+        B.up_blocks[l] = block_prefix(&B.levels[B.up_at(l)], B.nt, "canvas", [&](int t) {
+            const RwTile& T = P.tiles[t];
+            // level 0 always paints; the upper levels exist only for tiles with layers
+            return l < T.nl && (l == 0 || T.ne > 0) ? (long long)cdiv(T.lw[l], kUW) * cdiv(T.lh[l], kUH * kUP) : 0ll;
+        });
+    return B;
+}
+
+// ---- stage: the multiband launches -------------------------------------------------------------------------------------------
+unsigned xcd_grid(int n_blocks) { return 8u * (unsigned)((n_blocks + 7) / 8); }  // (see xcd_contiguous_id)
+
+void launch_warp(const RwArgs& A, const int* d_blk0, int n_blocks, bool exact) {
+    if (n_blocks == 0) return;
+    Prof prof("render_warp");
+    if (exact)
+        rw_warp_kernel<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+    else
+        rw_warp_staged_kernel<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+    check_launch("rw_warp_kernel");
+}
+// the pyramids, fine to coarse
+void launch_shrinks(const RwArgs& A, const BlockTables& B, const int* d_levels, bool exact) {
+    Prof prof("render_pyr_down");
+    for (int l = 0; l + 1 < (int)B.down_blocks.size(); ++l) {
+        if (B.down_blocks[l] == 0) continue;
+        launch_down(A.tp.r, A, l, d_levels + B.down_at(l), B.down_blocks[l], exact);
+        check_launch("rw_down_kernel");
+    }
+}
+// Laplacian sums + collapse, coarse to fine; level 0 paints
+void launch_collapse(const RwArgs& A, const BlockTables& B, const int* d_levels) {
+    Prof prof("render_collapse");
+    for (int l = (int)B.up_blocks.size() - 1; l >= 0; --l) {
+        if (B.up_blocks[l] == 0) continue;
+        if (l == 0)
+            rw_up_kernel<true><<<xcd_grid(B.up_blocks[l]), 256, 0, stream()>>>(A, l, d_levels + B.up_at(l), B.up_blocks[l]);
+        else
+            rw_up_kernel<false><<<xcd_grid(B.up_blocks[l]), 256, 0, stream()>>>(A, l, d_levels + B.up_at(l), B.up_blocks[l]);
+        check_launch("rw_up_kernel");
+    }
 }
 
 }  // namespace
 
+// Multiband: screen, plan, tap tables, args and trig, footprints, entries, block tables, upload, warp, down, collapse, status.
 bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int n_img, const DevCanvas& cv, const aps_render_opts& o,
                               const std::vector<TileRect>& tiles, int out_layout, uint8_t* pano, uint8_t* covered,
                               const NeedImages& need_images) {
+    using Clock = std::chrono::steady_clock;
     const int nt = (int)tiles.size();
     if (nt == 0) return true;
     const bool trace = std::getenv("APS_TRACE") != nullptr;  // host phases of this call on stderr
-    auto t_now = [] { return std::chrono::steady_clock::now(); };
-    auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    const auto T0 = t_now();
+    auto t_ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto T0 = Clock::now();
     const Taps tp = make_taps(o.pyr_sigma);
     APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built",
                 (double)o.pyr_sigma, 2 * tp.r + 1);
     if (o.pyr_levels > kML) return false;
     for (const TileRect& tr : tiles)  // footprint stores are addressed with 32-bit byte offsets
         if ((long long)tr.ht * tr.wt * 16 >= (1ll << 31)) return false;
-    // ---- tiles, level sizes, tap tables --------------------------------------------------------------------
-    std::vector<RwTile> ht_(nt);
-    std::vector<TapJob> jobs;
-    std::map<std::pair<int, int>, int> down_off, up_off;
-    int n_down = 0, n_up = 0;
-    auto tap_table = [&](int in_len, int out_len, bool down) {
-        auto& m = down ? down_off : up_off;
-        int& total = down ? n_down : n_up;
-        auto it = m.find({in_len, out_len});
-        if (it != m.end()) return it->second;
-        const int off = total;
-        m[{in_len, out_len}] = off;
-        jobs.push_back(TapJob{in_len, out_len, down ? kTD : kTU, off});
-        total += out_len;
-        return off;
-    };
-    long long plane_px = 0, f_total = 0;
-    int max_ht = 0, max_wt = 0;
-    std::vector<int> xshift(nt);
-    for (int t = 0; t < nt; ++t) {
-        RwTile& T = ht_[t];
-        std::memset(&T, 0, sizeof T);
-        T.r0 = tiles[t].r0;
-        T.c0 = tiles[t].c0;
-        T.ht = tiles[t].ht;
-        T.wt = tiles[t].wt;
-        max_ht = std::max(max_ht, T.ht);
-        max_wt = std::max(max_wt, T.wt);
-        const int maxl = (int)std::floor(std::log2((double)std::min(T.ht, T.wt)));  // multiBandBlending.m:98-109
-        T.nl = std::max(1, std::min(o.pyr_levels, maxl));
-        T.lh[0] = T.ht;
-        T.lw[0] = T.wt;
-        for (int l = 1; l < T.nl; ++l) {
-            T.lh[l] = std::max(1, T.lh[l - 1] / 2);
-            T.lw[l] = std::max(1, T.lw[l - 1] / 2);
-        }
-        for (int l = 0; l + 1 < T.nl; ++l) {
-            T.tdr[l] = tap_table(T.lh[l], T.lh[l + 1], true);
-            T.tdc[l] = tap_table(T.lw[l], T.lw[l + 1], true);
-            T.tur[l] = tap_table(T.lh[l + 1], T.lh[l], false);
-            T.tuc[l] = tap_table(T.lw[l + 1], T.lw[l], false);
-            if (rows_first(T.lh[l], T.lw[l], T.lh[l + 1], T.lw[l + 1])) T.rf_down |= 1 << l;
-            if (rows_first(T.lh[l + 1], T.lw[l + 1], T.lh[l], T.lw[l])) T.rf_up |= 1 << l;
-        }
-        T.plane = plane_px;
-        plane_px += (long long)T.ht * T.wt;
-        for (int l = 1; l < T.nl; ++l) {
-            T.f[l] = f_total;
-            f_total += (long long)T.lh[l] * T.lw[l];
-        }
-        int xs = 0;
-        while ((cdiv(T.wt, 32) >> xs) > 64 || (((cdiv(T.wt, 32) - 1) >> xs) > 63)) ++xs;
-        xshift[t] = xs;
-    }
+    const bool exact = std::getenv("APS_WARP_EXACT") != nullptr;  // the warp and the shrink keep the per-tile path's arithmetic
+
+    TilePlan plan = plan_tiles(tiles, o.pyr_levels);
+    TapTables taps;
+    for (RwTile& T : plan.tiles) taps.add_tile(T);
     Ws<int> d_status(1), d_xshift(nt);
     APS_HIP(hipMemsetAsync(d_status, 0, sizeof(int), stream()));
-    APS_HIP(hipMemcpyAsync(d_xshift, xshift.data(), nt * sizeof(int), hipMemcpyHostToDevice, stream()));
-    Ws<int> td_idx((size_t)std::max(n_down, 1) * kTD), tu_idx((size_t)std::max(n_up, 1) * kTU);
-    Ws<float> td_w((size_t)std::max(n_down, 1) * kTD), tu_w((size_t)std::max(n_up, 1) * kTU);
-    Ws<TapJob> d_jobs(std::max<size_t>(jobs.size(), 1));
-    if (!jobs.empty()) {
-        APS_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(TapJob), hipMemcpyHostToDevice, stream()));
-        int longest = 1;
-        for (const TapJob& j : jobs) longest = std::max(longest, j.out_len);
-        rw_taps_kernel<<<dim3(cdiv(longest, 256), (unsigned)jobs.size()), 256, 0, stream()>>>(d_jobs, td_idx, td_w, tu_idx, tu_w,
-                                                                                              d_status);
-        check_launch("rw_taps_kernel");
-    }
-    // APS_WARP_EXACT=1: the warp and the shrink keep the per-tile path's arithmetic
-    const bool exact = std::getenv("APS_WARP_EXACT") != nullptr;
-    const int ncp = (kTD + 2 * tp.r + 3) & ~3;
-    Ws<int> cd_s0((size_t)std::max(n_down, 1));
-    Ws<float> cd_w((size_t)std::max(n_down, 1) * ncp);
-    if (!jobs.empty() && !exact) {
-        int longest = 1;
-        for (const TapJob& j : jobs) longest = std::max(longest, j.out_len);
-        rw_ctaps_kernel<<<dim3(cdiv(longest, 256), (unsigned)jobs.size()), 256, 0, stream()>>>(d_jobs, tp, ncp, cd_s0, cd_w, d_status);
-        check_launch("rw_ctaps_kernel");
-    }
+    upload(d_xshift, plan.xshift);
+    taps.build(tp, exact, d_status);
     Ws<RwTile> d_tiles(nt);
-    APS_HIP(hipMemcpyAsync(d_tiles, ht_.data(), nt * sizeof(RwTile), hipMemcpyHostToDevice, stream()));
-    Ws<uint8_t> d_cov((size_t)plane_px);
-    APS_HIP(hipMemsetAsync(d_cov, 0, (size_t)plane_px, stream()));  // tiles without layers stay uncovered
+    upload(d_tiles, plan.tiles);
+    Ws<uint8_t> d_cov((size_t)plan.plane_px);
+    APS_HIP(hipMemsetAsync(d_cov, 0, (size_t)plan.plane_px, stream()));  // tiles without layers stay uncovered
 
-    RwArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.tiles = d_tiles;
-    A.n_tiles = nt;
-    A.imgs = dimgs;
-    A.cv = cv;
-    A.angle_pow = o.angle_power;
+    RwArgs A = base_args(d_tiles, nt, dimgs, cv, o, out_layout, pano, covered);
     A.tp = tp;
-    A.td_idx = td_idx;
-    A.td_w = td_w;
-    A.tu_idx = tu_idx;
-    A.tu_w = tu_w;
-    A.cd_s0 = cd_s0;
-    A.cd_w = cd_w;
+    taps.set_args(A);
     A.cov = d_cov;
     A.status = d_status;
-    A.pano = pano;
-    A.covered = covered;
-    A.H = cv.H;
-    A.W = cv.W;
-    A.out_layout = out_layout;
-    A.white = o.canvas_white;
     Ws<ColTrig> d_ct((size_t)std::max(cv.W, 1));
     Ws<RowTrig> d_rt((size_t)std::max(cv.H, 1));
     rw_trig_kernel<<<cdiv(std::max(cv.W, cv.H), 256), 256, 0, stream()>>>(cv, d_ct, d_rt);
@@ -1899,240 +2088,73 @@ bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int 
     A.ct = d_ct;
     A.rt = d_rt;
 
-    // ---- pass 1: the footprint rectangle of every image in every tile ----------------------------------------------
-    const auto T1 = t_now();
-    std::vector<int> hbox;
-    tile_footprints(A, himgs, n_img, ht_, xshift, d_xshift, d_tiles, max_ht, max_wt, hbox);
-    const auto T2 = t_now();
+    const auto T1 = Clock::now();
+    const std::vector<int> hbox = tile_footprints(A, himgs, n_img, plan, d_xshift);
+    const auto T2 = Clock::now();
+    const std::vector<RwEntry> ents = build_entries(plan, hbox, n_img, tp.r);
+    report_used_images(ents, n_img, need_images);
+    const BlockTables B = multiband_block_tables(plan, ents);
+    const auto T3 = Clock::now();
 
-    // ---- entries, compact stores, block tables ----------------------------------------------------------------
-    std::vector<RwEntry> ents;
-    long long g_total = 0;
-    int max_nl = 1;
-    for (int t = 0; t < nt; ++t) {
-        RwTile& T = ht_[t];
-        T.e0 = (int)ents.size();
-        max_nl = std::max(max_nl, T.nl);
-        for (int i = 0; i < n_img; ++i) {
-            const int* b = &hbox[((size_t)t * n_img + i) * 4];
-            if (!(b[2] > b[0] && b[3] > b[1])) continue;
-            RwEntry E;
-            std::memset(&E, 0, sizeof E);
-            E.tile = t;
-            E.img = i;
-            E.g[0] = clip_rect(Rect{b[0], b[1], b[2], b[3]}, T.wt, T.ht);
-            for (int l = 0; l + 1 < T.nl; ++l) {
-                const Rect g = E.g[l];
-                const bool empty = g.x1 <= g.x0;
-                const Rect br = empty ? g : clip_rect(Rect{g.x0 - tp.r, g.y0 - tp.r, g.x1 + tp.r, g.y1 + tp.r}, T.lw[l], T.lh[l]);
-                E.g[l + 1] = empty ? g : map_rect(br, T.lh[l], T.lw[l], T.lh[l + 1], T.lw[l + 1]);
-            }
-            for (int l = 0; l < T.nl; ++l) {
-                E.off[l] = g_total;
-                g_total += (long long)(E.g[l].x1 - E.g[l].x0) * (E.g[l].y1 - E.g[l].y0);
-            }
-            ents.push_back(E);
-        }
-        T.ne = (int)ents.size() - T.e0;
-    }
-    const int ne = (int)ents.size();
-    {  // the images these tiles meet: their pixels are needed from here on
-        std::vector<char> used(n_img, 0);
-        for (const RwEntry& E : ents) used[E.img] = 1;
-        need_images(used);
-    }
-    // block tables: levels 0 .. max_nl-2 of the shrink over entries, levels 0 .. max_nl-1 of the collapse over tiles
-    std::vector<int> blk((size_t)(max_nl) * (ne + 1) + (size_t)max_nl * (nt + 1), 0);
-    std::vector<int> down_blocks(max_nl, 0), up_blocks(max_nl, 0);
-    // the warp: blocks over the level-0 grid of every tile with layers
-    std::vector<int> blk0(nt + 1, 0);
-    int warp_blocks = 0;
-    {
-        long long run = 0;
-        for (int t = 0; t < nt; ++t) {
-            blk0[t] = (int)run;
-            const RwTile& T = ht_[t];
-            if (T.ne > 0) run += (long long)cdiv(T.wt, kUW) * cdiv(T.ht, kUH);
-        }
-        APS_REQUIRE(run < (1ll << 30), APS_E_DIM, "too many canvas blocks in one render call (%lld)", run);
-        blk0[nt] = (int)run;
-        warp_blocks = (int)run;
-    }
-    for (int l = 0; l + 1 < max_nl; ++l) {
-        int* p = &blk[(size_t)l * (ne + 1)];
-        long long run = 0;
-        for (int e = 0; e < ne; ++e) {
-            p[e] = (int)run;
-            const RwEntry& E = ents[e];
-            if (l + 1 < ht_[E.tile].nl) {
-                const Rect& g = E.g[l + 1];
-                run += (long long)cdiv(std::max(g.x1 - g.x0, 0), kBW) * cdiv(std::max(g.y1 - g.y0, 0), kBH);
-            }
-        }
-        APS_REQUIRE(run < (1ll << 30), APS_E_DIM, "too many pyramid blocks in one render call (%lld)", run);
-        p[ne] = (int)run;
-        down_blocks[l] = (int)run;
-    }
-    const size_t up_base = (size_t)max_nl * (ne + 1);
-    for (int l = 0; l < max_nl; ++l) {
-        int* p = &blk[up_base + (size_t)l * (nt + 1)];
-        long long run = 0;
-        for (int t = 0; t < nt; ++t) {
-            p[t] = (int)run;
-            const RwTile& T = ht_[t];
-            // level 0 always paints; the upper levels exist only for tiles with layers
-            if (l < T.nl && (l == 0 || T.ne > 0)) run += (long long)cdiv(T.lw[l], kUW) * cdiv(T.lh[l], kUH * kUP);
-        }
-        APS_REQUIRE(run < (1ll << 30), APS_E_DIM, "too many canvas blocks in one render call (%lld)", run);
-        p[nt] = (int)run;
-        up_blocks[l] = (int)run;
-    }
-    const auto T3 = t_now();
-    Ws<RwEntry> d_ents(std::max(ne, 1));
-    Ws<int> d_blk(blk.size()), d_blk0(blk0.size());
-    APS_HIP(hipMemcpyAsync(d_blk0, blk0.data(), blk0.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
-    Ws<float4> d_G((size_t)std::max<long long>(g_total, 1)), d_F((size_t)std::max<long long>(f_total, 1));
-    if (ne) APS_HIP(hipMemcpyAsync(d_ents, ents.data(), ne * sizeof(RwEntry), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_tiles, ht_.data(), nt * sizeof(RwTile), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+    Ws<RwEntry> d_ents(std::max<size_t>(ents.size(), 1));
+    Ws<int> d_levels(B.levels.size()), d_blk0(B.warp.size());
+    Ws<float4> d_G((size_t)std::max<long long>(plan.g_total, 1)), d_F((size_t)std::max<long long>(plan.f_total, 1));
+    upload(d_blk0, B.warp);
+    upload(d_ents, ents);
+    upload(d_tiles, plan.tiles);  // (again: e0 / ne)
+    upload(d_levels, B.levels);
     A.entries = d_ents;
-    A.n_entries = ne;
+    A.n_entries = (int)ents.size();
     A.G = d_G;
     A.F = d_F;
-
-    // ---- pass 2: pyramids, fine to coarse ------------------------------------------------------------------------
-    if (warp_blocks) {
-        Prof prof("render_warp");
-        const unsigned wgrid = 8u * (unsigned)((warp_blocks + 7) / 8);
-        if (exact)
-            rw_warp_kernel<<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        else
-            rw_warp_staged_kernel<<<wgrid, 256, 0, stream()>>>(A, d_blk0, warp_blocks);
-        check_launch("rw_warp_kernel");
-    }
-    {
-        Prof prof("render_pyr_down");
-        for (int l = 0; l + 1 < max_nl; ++l) {
-            if (down_blocks[l] == 0) continue;
-            launch_down(tp.r, A, l, d_blk.get() + (size_t)l * (ne + 1), down_blocks[l], exact);
-            check_launch("rw_down_kernel");
-        }
-    }
-    {
-        // Laplacian sums + collapse, coarse to fine; level 0 paints
-        Prof prof("render_collapse");
-        for (int l = max_nl - 1; l >= 0; --l) {
-            if (up_blocks[l] == 0) continue;
-            const int* bp = d_blk.get() + up_base + (size_t)l * (nt + 1);
-            const unsigned grid = 8u * (unsigned)((up_blocks[l] + 7) / 8);
-            if (l == 0)
-                rw_up_kernel<true><<<grid, 256, 0, stream()>>>(A, l, bp, up_blocks[l]);
-            else
-                rw_up_kernel<false><<<grid, 256, 0, stream()>>>(A, l, bp, up_blocks[l]);
-            check_launch("rw_up_kernel");
-        }
-    }
-    const auto T4 = t_now();
+    launch_warp(A, d_blk0, B.warp_blocks, exact);
+    launch_shrinks(A, B, d_levels, exact);
+    launch_collapse(A, B, d_levels);
+    const auto T4 = Clock::now();
     int status = 0;
     APS_HIP(hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, stream()));
     APS_HIP(hipStreamSynchronize(stream()));  // also keeps the host tables alive until their uploads have run
     if (trace)
         std::fprintf(stderr, "[aps render] host: tiles + tap tables %.2f ms, footprints %.2f, entries + block tables %.2f, uploads + launches %.2f, wait for the kernels %.2f\n",
-                     t_ms(T0, T1), t_ms(T1, T2), t_ms(T2, T3), t_ms(T3, T4), t_ms(T4, t_now()));
+                     t_ms(T0, T1), t_ms(T1, T2), t_ms(T2, T3), t_ms(T3, T4), t_ms(T4, Clock::now()));
     APS_REQUIRE(status == 0, APS_E_INTERNAL, "batched render: tap table assumption violated (status %d)", status);
     return true;
 }
 
-// 'linear' / 'none': all tiles in one launch (rw_fuse_kernel).  Same tile list and footprints as the multiband form.
+// 'linear' / 'none': all tiles in one launch (rw_fuse_kernel).  Same tile plan, footprints and entries as the multiband form,
+// with one level.
 bool render_fuse_batched(const DevImage* dimgs, const DevImage* himgs, int n_img, const DevCanvas& cv, const aps_render_opts& o,
                          const std::vector<TileRect>& tiles, int out_layout, uint8_t* pano, uint8_t* covered,
                          const NeedImages& need_images) {
     const int nt = (int)tiles.size();
     if (nt == 0) return true;
     if (o.blending != APS_BLEND_LINEAR && o.blending != APS_BLEND_NONE) return false;
-    std::vector<RwTile> ht_(nt);
-    std::vector<int> xshift(nt);
-    int max_ht = 0, max_wt = 0;
-    for (int t = 0; t < nt; ++t) {
-        RwTile& T = ht_[t];
-        std::memset(&T, 0, sizeof T);
-        T.r0 = tiles[t].r0;
-        T.c0 = tiles[t].c0;
-        T.ht = tiles[t].ht;
-        T.wt = tiles[t].wt;
-        T.nl = 1;
-        T.lh[0] = T.ht;
-        T.lw[0] = T.wt;
-        max_ht = std::max(max_ht, T.ht);
-        max_wt = std::max(max_wt, T.wt);
-        int xs = 0;
-        while ((cdiv(T.wt, 32) >> xs) > 64 || (((cdiv(T.wt, 32) - 1) >> xs) > 63)) ++xs;
-        xshift[t] = xs;
-    }
+    TilePlan plan = plan_tiles(tiles, 1);
     Ws<int> d_xshift(nt);
     Ws<RwTile> d_tiles(nt);
-    APS_HIP(hipMemcpyAsync(d_xshift, xshift.data(), nt * sizeof(int), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_tiles, ht_.data(), nt * sizeof(RwTile), hipMemcpyHostToDevice, stream()));
-    RwArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.tiles = d_tiles;
-    A.n_tiles = nt;
-    A.imgs = dimgs;
-    A.cv = cv;
-    A.angle_pow = o.angle_power;
-    A.pano = pano;
-    A.covered = covered;
-    A.H = cv.H;
-    A.W = cv.W;
-    A.out_layout = out_layout;
-    A.white = o.canvas_white;
-    std::vector<int> hbox;
-    tile_footprints(A, himgs, n_img, ht_, xshift, d_xshift, d_tiles, max_ht, max_wt, hbox);
-    std::vector<RwEntry> ents;
-    for (int t = 0; t < nt; ++t) {
-        RwTile& T = ht_[t];
-        T.e0 = (int)ents.size();
-        for (int i = 0; i < n_img; ++i) {
-            const int* b = &hbox[((size_t)t * n_img + i) * 4];
-            if (!(b[2] > b[0] && b[3] > b[1])) continue;
-            RwEntry E;
-            std::memset(&E, 0, sizeof E);
-            E.tile = t;
-            E.img = i;
-            E.g[0] = clip_rect(Rect{b[0], b[1], b[2], b[3]}, T.wt, T.ht);
-            ents.push_back(E);
-        }
-        T.ne = (int)ents.size() - T.e0;
-    }
-    {
-        std::vector<char> used(n_img, 0);
-        for (const RwEntry& E : ents) used[E.img] = 1;
-        need_images(used);
-    }
+    upload(d_xshift, plan.xshift);
+    upload(d_tiles, plan.tiles);
+    RwArgs A = base_args(d_tiles, nt, dimgs, cv, o, out_layout, pano, covered);
+    const std::vector<int> hbox = tile_footprints(A, himgs, n_img, plan, d_xshift);
+    const std::vector<RwEntry> ents = build_entries(plan, hbox, n_img, 0);
+    report_used_images(ents, n_img, need_images);
     // every tile is painted (a tile without layers gets the canvas colour): blocks over the level-0 grid of all tiles
     std::vector<int> blk0(nt + 1, 0);
-    long long run = 0;
-    for (int t = 0; t < nt; ++t) {
-        blk0[t] = (int)run;
-        run += (long long)cdiv(ht_[t].wt, kUW) * cdiv(ht_[t].ht, kUH);
-    }
-    APS_REQUIRE(run < (1ll << 30), APS_E_DIM, "too many canvas blocks in one render call (%lld)", run);
-    blk0[nt] = (int)run;
-    const int ne = (int)ents.size();
-    Ws<RwEntry> d_ents(std::max(ne, 1));
+    const int n_blocks = block_prefix(blk0.data(), nt, "canvas",
+                                      [&](int t) { return (long long)cdiv(plan.tiles[t].wt, kUW) * cdiv(plan.tiles[t].ht, kUH); });
+    Ws<RwEntry> d_ents(std::max<size_t>(ents.size(), 1));
     Ws<int> d_blk0(blk0.size());
-    if (ne) APS_HIP(hipMemcpyAsync(d_ents, ents.data(), ne * sizeof(RwEntry), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_tiles, ht_.data(), nt * sizeof(RwTile), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_blk0, blk0.data(), blk0.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+    upload(d_ents, ents);
+    upload(d_tiles, plan.tiles);  // (again: e0 / ne)
+    upload(d_blk0, blk0);
     A.entries = d_ents;
-    A.n_entries = ne;
+    A.n_entries = (int)ents.size();
     {
         Prof prof("render_fuse");
-        const unsigned grid = 8u * (unsigned)((run + 7) / 8);
         if (o.blending == APS_BLEND_LINEAR)
-            rw_fuse_kernel<APS_BLEND_LINEAR><<<grid, 256, 0, stream()>>>(A, d_blk0, (int)run, o.none_policy);
+            rw_fuse_kernel<APS_BLEND_LINEAR><<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks, o.none_policy);
         else
-            rw_fuse_kernel<APS_BLEND_NONE><<<grid, 256, 0, stream()>>>(A, d_blk0, (int)run, o.none_policy);
+            rw_fuse_kernel<APS_BLEND_NONE><<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks, o.none_policy);
     }
     check_launch("rw_fuse_kernel");
     APS_HIP(hipStreamSynchronize(stream()));  // keeps the host tables alive until their uploads have run

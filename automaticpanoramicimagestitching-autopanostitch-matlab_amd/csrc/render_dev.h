@@ -1,7 +1,8 @@
 // render_dev.h — device-side structures and sampling functions shared by render.hip (per-tile reference path,
 // linear/none blending, diagnostics), render_batch.hip (the batched multiband path) and planar.hip (the planar compositors),
 // and the one statement of the multiband pyramid's arithmetic (resize_with, blur_tile, lap_accumulate) and shape
-// (pyramid_levels, pyramid_footprints).  See render.hip's header comment for the reference lines restated here.
+// (pyramid_levels, next_footprint, pyramid_footprints), and of the cover pass's column shift (cover_xshift).  See render.hip's
+// header comment for the reference lines restated here.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -364,8 +365,15 @@ inline void pyramid_levels(int h, int w, int levels, std::vector<int>& lh, std::
         lw[l] = std::max(1, lw[l - 1] / 2);
     }
 }
-// Footprints per level from the level-0 footprints g0 (clipped to the level): G_l, B_l = blurred G_l (grown by the filter
-// radius), G_(l+1) = B_l mapped through the resize.  An empty footprint stays empty at every level.
+// One level's step of a footprint, G_(l+1) = map(clip(grow(G_l))): B_l = the blurred G_l (grown by the filter radius, clipped
+// to the h x w level), G_(l+1) = B_l mapped through the resize to oh x ow.  An empty footprint stays empty.
+inline Rect blurred_footprint(const Rect& g, int radius, int h, int w) {
+    return g.x1 <= g.x0 ? g : clip_rect(Rect{g.x0 - radius, g.y0 - radius, g.x1 + radius, g.y1 + radius}, w, h);
+}
+inline Rect next_footprint(const Rect& g, int radius, int h, int w, int oh, int ow) {
+    return g.x1 <= g.x0 ? g : map_rect(blurred_footprint(g, radius, h, w), h, w, oh, ow);
+}
+// Footprints per level from the level-0 footprints g0 (clipped to the level): G_l and B_l of every level.
 inline void pyramid_footprints(const std::vector<Rect>& g0, int radius, const std::vector<int>& lh, const std::vector<int>& lw,
                                std::vector<std::vector<Rect>>& gr, std::vector<std::vector<Rect>>& br) {
     const int L = (int)lh.size();
@@ -373,11 +381,18 @@ inline void pyramid_footprints(const std::vector<Rect>& g0, int radius, const st
     br.assign(L, g0);
     for (int l = 0; l < L; ++l)
         for (size_t k = 0; k < g0.size(); ++k) {
-            const Rect g = gr[l][k];
-            const bool empty = g.x1 <= g.x0;
-            br[l][k] = empty ? g : clip_rect(Rect{g.x0 - radius, g.y0 - radius, g.x1 + radius, g.y1 + radius}, lw[l], lh[l]);
-            if (l + 1 < L) gr[l + 1][k] = empty ? g : map_rect(br[l][k], lh[l], lw[l], lh[l + 1], lw[l + 1]);
+            br[l][k] = blurred_footprint(gr[l][k], radius, lh[l], lw[l]);
+            if (l + 1 < L) gr[l + 1][k] = next_footprint(gr[l][k], radius, lh[l], lw[l], lh[l + 1], lw[l + 1]);
         }
+}
+// The cover pass (cover_kernel / footprint_kernel in render.hip, their rw_ twins in render_batch.hip) records the block columns
+// an image touches as bits of ONE 64-bit word per block row: bit (block column >> xshift).  A tile of more than 64 columns of
+// 32-pixel blocks shares a bit between 2^xshift neighbouring columns: the smallest shift at which the last column's bit is <= 63.
+inline int cover_xshift(int wt) {
+    const int nbx = cdiv(wt, 32);
+    int xs = 0;
+    while ((nbx >> xs) > 64 || ((nbx - 1) >> xs) > 63) ++xs;
+    return xs;
 }
 // Pixels of levels from..to-1.
 inline int64_t pyramid_px(const std::vector<int>& lh, const std::vector<int>& lw, int from, int to) {

@@ -130,9 +130,7 @@ def release_device_memory():
     import torch
 
     _capi.check(_capi.lib.aps_release_workspace())
-    from . import renderPanorama as _rp
-
-    for pool in (_SIFT_POOL, _SIFT_GROUP_POOL, getattr(_rp, "_RENDER_POOL", None)):
+    for pool in (_SIFT_POOL, _SIFT_GROUP_POOL):
         n = len(getattr(pool, "_threads", ())) if pool is not None else 0
         if not n:
             continue

@@ -728,15 +728,11 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
     else:
         pano = np.zeros((H, W, 3), np.uint8)
         cov = np.zeros((H, W), np.uint8)
-    # ONE call renders all tiles (render_batch.hip: multiband level-major, 'linear' / 'none' as one fused launch); the
-    # per-tile path (APS_RENDER_LEGACY=1) still gains from a few host threads driving interleaved tile subsets
-    import os as _os
-
-    batched = not _os.environ.get("APS_RENDER_LEGACY")  # (since round 4 'linear' and 'none' are one fused launch as well)
-    workers = _render_workers() if (device_out and not batched) else 1
-    if tile_subset is None and workers <= 1:
+    # ONE call renders all tiles on the calling thread (render_batch.hip: multiband level-major, 'linear' / 'none' as one fused
+    # launch; APS_RENDER_LEGACY=1: the per-tile path the tests compare it with, tile after tile inside the same call)
+    if tile_subset is None:
         check(lib.aps_render(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC, ptr(pano), ptr(cov)))
-    elif tile_subset is not None and tile_subset[0] == "range":
+    elif tile_subset[0] == "range":
         # ("range", begin, end): the contiguous tiles begin <= t < end - a rank's band of the canvas (parallel.tile_ranges)
         import torch
 
@@ -749,30 +745,15 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
         check(lib.aps_render_tile_range(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC,
                                         int(tile_subset[1]), int(tile_subset[2]), ptr(pano), ptr(cov)))
     else:  # (first, step): only tiles t with t % step == first — an interleaved shard of the tile loop
-        first, step = (0, 1) if tile_subset is None else (int(tile_subset[0]), int(tile_subset[1]))
-        if device_out and tile_subset is not None:
+        first, step = int(tile_subset[0]), int(tile_subset[1])
+        if device_out:
             import torch
 
             pano.zero_()
             cov.zero_()
             torch.cuda.current_stream().synchronize()  # torch's fills must land before the library's stream paints tiles
-        if workers <= 1:
-            check(lib.aps_render_tiles(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC,
-                                       first, step, ptr(pano), ptr(cov)))
-        else:
-            # The tile loop of renderPanorama.m:342-406 is a parfor candidate: tiles are independent and paint
-            # disjoint canvas rectangles.  A few host threads each drive their own stream over an interleaved
-            # share of this rank's tiles (t % (step*workers) == first + step*k), so the many small pyramid
-            # launches of one tile overlap with another tile's; every tile's arithmetic is unchanged.
-            here = lib.aps_get_device()
-
-            def work(k):
-                check(lib.aps_set_thread_device(here))  # not the process-wide default another thread may have changed
-                check(lib.aps_render_tiles(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC,
-                                           first + step * k, step * workers, ptr(pano), ptr(cov)))
-                check(lib.aps_synchronize())  # this thread's stream
-
-            list(_render_pool(workers).map(work, range(workers)))
+        check(lib.aps_render_tiles(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC,
+                                   first, step, ptr(pano), ptr(cov)))
     del keep
     if o["cropBorder"] and tile_subset is None:  # renderPanorama.m:430-432 (a tile shard is cropped after it is combined)
         if device_out:
@@ -781,24 +762,6 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
     if return_covered:
         return pano, None, cov, geo
     return pano, None
-
-
-_RENDER_POOL = None
-
-
-def _render_workers():
-    import os
-
-    return max(1, int(os.environ.get("APS_RENDER_WORKERS", "2")))
-
-
-def _render_pool(workers):
-    global _RENDER_POOL
-    from concurrent.futures import ThreadPoolExecutor
-
-    if _RENDER_POOL is None or _RENDER_POOL._max_workers < workers:
-        _RENDER_POOL = ThreadPoolExecutor(max_workers=workers)
-    return _RENDER_POOL
 
 
 def warp_tile(image, camera, geo, r0, c0, ht, wt, anglePower=2.0, gain=(1.0, 1.0, 1.0)):

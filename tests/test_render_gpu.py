@@ -283,9 +283,10 @@ def test_contiguous_tile_ranges_compose_to_the_full_render(gpu, rp, world, blend
 @pytest.mark.parametrize("workers", [1, 2, 3])
 @pytest.mark.parametrize("subset", [None, (1, 2)])
 def test_threaded_tile_loop_changes_no_byte(rp, monkeypatch, workers, subset):
-    """Resident renders drive the tile loop from a few host threads (own stream each, interleaved tile shares,
-    APS_RENDER_WORKERS): the canvas must equal the single-stream render in every byte, for the full tile set and
-    for a multi-GPU shard of it."""
+    """A resident render (torch tensors in, torch tensor out) must equal the host-buffer render in every byte, for the
+    full tile set and for a multi-GPU shard of it, on the first call and on a repeat that reuses the workspaces.  (The test's
+    name and its `workers` parameter date from a host thread pool that drove the per-tile path's tile loop; the batched
+    path never used it and it is gone: every render runs on the calling thread, and APS_RENDER_WORKERS is no longer read.)"""
     import torch
 
     rng = np.random.default_rng(32)
@@ -484,6 +485,53 @@ def test_batched_multiband_tile_subsets_compose(rp, monkeypatch):
     assert np.array_equal(np.maximum(parts[0][0], parts[1][0]), full)
     assert np.array_equal(np.maximum(parts[0][2], parts[1][2]), cov)
     assert not np.any((parts[0][2] == 1) & (parts[1][2] == 1))
+
+
+def test_more_levels_than_the_batched_path_builds_fall_back_to_the_per_tile_path(rp, monkeypatch):
+    """pyrLevels = 9 is more than render_multiband_batched is built for (8): it declines and the call takes the per-tile
+    path.  With tile = (64, 80) every tile clamps to at most floor(log2(64)) = 6 levels, so the result must equal the batched
+    render at pyrLevels = 6 with the per-tile arithmetic (APS_WARP_EXACT=1) in every byte of panorama and coverage."""
+    rng = np.random.default_rng(35)
+    imgs, cams = _scene(rng, n=5, W=200, H=130, f=280.0)
+    sizes = [(130, 200, 3)] * 5
+    opts = {"anglePower": 2, "blending": "multiband", "pyrLevels": 9, "pyrSigma": 1.0, "tile": (64, 80), "cropBorder": False}
+    for name in ("APS_RENDER_LEGACY", "APS_WARP_EXACT"):
+        monkeypatch.delenv(name, raising=False)
+    deep, _, dcov, _ = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, opts, return_covered=True)
+    monkeypatch.setenv("APS_WARP_EXACT", "1")
+    six, _, scov, _ = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, dict(opts, pyrLevels=6), return_covered=True)
+    assert scov.sum() > 10000 and (scov == 0).sum() > 100
+    assert np.array_equal(dcov, scov)
+    assert np.array_equal(deep, six)
+
+
+def test_tiles_with_one_level_beside_tiles_with_several(rp, monkeypatch):
+    """A last tile row two pixels tall: on the 147 x 597 canvas of this scene the tile (145, 80) gives tiles of 145 x 80 and
+    145 x 37 with four levels above tiles of 2 x 80 and 2 x 37 with one, so the block tables of the shrink and of the collapse
+    must leave those out level by level.  The batched path with the per-tile arithmetic (APS_WARP_EXACT=1) must equal the
+    per-tile path (APS_RENDER_LEGACY=1) in every byte; the default render must cover the same pixels, with every exact
+    footprint inside its analytic rectangle (APS_RENDER_CHECK_RECTS=1 raises otherwise)."""
+    rng = np.random.default_rng(36)
+    imgs, cams = _scene(rng, n=5, W=200, H=130, f=280.0)
+    sizes = [(130, 200, 3)] * 5
+    opts = {"anglePower": 2, "blending": "multiband", "pyrLevels": 4, "pyrSigma": 1.0, "tile": (64, 80), "cropBorder": False}
+    for name in ("APS_RENDER_LEGACY", "APS_WARP_EXACT", "APS_RENDER_CHECK_RECTS"):
+        monkeypatch.delenv(name, raising=False)
+    _, _, _, geo = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, opts, return_covered=True)
+    H, W = int(geo["H"]), int(geo["W"])
+    opts["tile"] = (H - 2, 80) if H - 2 >= 8 else (64, W - 2)
+    assert min(opts["tile"]) >= 16 and (H, W) == (147, 597)  # (four levels beside one, the sizes the docstring states)
+    monkeypatch.setenv("APS_RENDER_CHECK_RECTS", "1")
+    fast, _, fcov, _ = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, opts, return_covered=True)
+    monkeypatch.delenv("APS_RENDER_CHECK_RECTS")
+    monkeypatch.setenv("APS_WARP_EXACT", "1")
+    pano, _, cov, _ = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, opts, return_covered=True)
+    monkeypatch.delenv("APS_WARP_EXACT")
+    monkeypatch.setenv("APS_RENDER_LEGACY", "1")
+    ref, _, rcov, _ = rp.renderPanorama({}, imgs, sizes, cams, "spherical", 2, opts, return_covered=True)
+    assert cov.sum() > 10000 and (cov == 0).sum() > 100
+    assert np.array_equal(cov, rcov) and np.array_equal(pano, ref)
+    assert np.array_equal(fcov, cov)
 
 
 @pytest.mark.parametrize("mode", ["spherical", "cylindrical"])
