@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle
+from global_cases import oracle_chain
 from util import bits, sift_like
 
 pytestmark = pytest.mark.gpu
@@ -51,16 +52,7 @@ def test_global_matcher_equals_oracle_chain(fm):
     inp = {"k": 4, "Ratiothreshold": 0.6}
     cells = fm.featureMatchingGlobal(inp, descs, 4)
     # oracle chain: same pooling/normalisation, exact kNN, sequential filter
-    pool = np.concatenate(descs)
-    sq = np.zeros(len(pool), np.float32)
-    for kk in range(128):
-        sq = sq + pool[:, kk] * pool[:, kk]
-    pool = (pool / np.sqrt(sq + np.float32(np.finfo(np.float32).eps))[:, None]).astype(np.float32)
-    counts = [len(d) for d in descs]
-    img = np.repeat(np.arange(1, 5, dtype=np.uint32), counts)
-    loc = np.concatenate([np.arange(1, c + 1, dtype=np.uint32) for c in counts])
-    ni, nd = oracle.knn(pool, pool, 4)
-    rows = oracle.global_filter(ni, nd, img, loc, 0.6)
+    rows = oracle_chain(descs, 0.6, 4)
     total = 0
     for i in range(4):
         for j in range(i + 1, 4):
@@ -208,16 +200,7 @@ def test_screened_pooled_matcher_equals_plain_search_and_oracle(gpu, monkeypatch
     monkeypatch.delenv("APS_MATCH_NO_SCREEN")
     assert np.array_equal(pp, pp1) and np.array_equal(oi, oi1) and np.array_equal(oj, oj1)
     # the oracle chain
-    pool = np.concatenate(descs)
-    sq = np.zeros(len(pool), np.float32)
-    for kk in range(128):
-        sq = sq + pool[:, kk] * pool[:, kk]
-    pool = (pool / np.sqrt(sq + np.float32(np.finfo(np.float32).eps))[:, None]).astype(np.float32)
-    counts = [len(d) for d in descs]
-    img = np.repeat(np.arange(1, n_img + 1, dtype=np.uint32), counts)
-    loc = np.concatenate([np.arange(1, c + 1, dtype=np.uint32) for c in counts])
-    ni, nd = oracle.knn(pool, pool, 4)
-    want = oracle.global_filter(ni, nd, img, loc, 0.6)
+    want = oracle_chain(descs, 0.6, 4)
     for p, (i, j) in enumerate(fm.pair_order(n_img)):
         exp = want[(want[:, 0] == i + 1) & (want[:, 1] == j + 1)][:, 2:]
         got = np.stack([oi[pp[p]:pp[p + 1]], oj[pp[p]:pp[p + 1]]], axis=1)
