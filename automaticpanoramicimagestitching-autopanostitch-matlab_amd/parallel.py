@@ -979,6 +979,9 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     pipeline.stitch plus "owner" and the owner's wall "seconds") and times["bundle_adjustment"] replaces
     times["host_cameras"].  Planar sets (cameras with noRotation = 1, or input.forcePlanarScan) are rendered whole by one
     rank through the planar compositor, also when `cameras` are given.
+    input['showPanoramaImgsNums'] / input['showCropBoundingBox'] are ignored here: no annotated panorama is produced (a
+    rank renders a shard of the tiles; annotate the combined result with renderPanorama.annotate_panorama, or use
+    pipeline.stitch, whose info['annotated'] carries it).
     Returns (panorama of the component that holds the best-connected image, uint8 H x W x 3 CUDA tensor; info dict
     with info["panoramas"]: one entry per connected component of at least two images, in component order)."""
     from . import pipeline as pl

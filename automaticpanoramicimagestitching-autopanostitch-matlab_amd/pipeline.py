@@ -581,7 +581,9 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     they are estimated (focal estimation + bundle adjustment, recognize_panoramas); info then holds
     times['bundle_adjustment'] and 'ba': per component the estimated focal, the initial and final RMSE, the LM's
     normal-equation evaluations and noRotation.
-    Every connected component of at least two images is rendered (displayPanorama.m:88-116).
+    Every connected component of at least two images is rendered (displayPanorama.m:88-116).  With
+    input['showPanoramaImgsNums'] and input['showCropBoundingBox'] both true, info['annotated'] holds, per component, the
+    panorama with the images' outlines and numbers (renderPanorama's second output, drawn on the device).
     Returns (panoramas [one per component, in component order], info dict with per-stage wall times in seconds)."""
     times = StageTimes()
     n = len(images)
@@ -607,12 +609,17 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     t0 = time.perf_counter()
     opts = {"anglePower": 2, "blending": input["blending"], "pyrLevels": input["bands"], "pyrSigma": input["MBBsigma"],
             "canvasColor": input["canvasColor"], "tile": tile, "cropBorder": bool(input.get("cropBorder", True))}  # displayPanorama.m:101
+    annotate = bool(input.get("showPanoramaImgsNums")) and bool(input.get("showCropBoundingBox"))
+    if annotate:  # displayPanorama.m:109-110; the panoramas are the same bytes with and without
+        opts.update(showPanoramaImgsNums=True, showCropBoundingBox=True)
+    annotated = []
     for c in comps:
         members = c["members"]
-        pano, _ = rp.renderPanorama(input, [images[k] for k in members], [sizes[k] for k in members],
-                                    c["cameras"], input["panorama2DisplaynSave"], c["ref"], opts,
-                                    device_out=device_out)
+        pano, ann = rp.renderPanorama(input, [images[k] for k in members], [sizes[k] for k in members],
+                                      c["cameras"], input["panorama2DisplaynSave"], c["ref"], opts,
+                                      device_out=device_out)
         panos.append(pano)
+        annotated.append(ann)
     _sync()
     times.add("render", t0)
     cams = [None] * n
@@ -625,4 +632,6 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
             "images_processed": images}
     if ba_info is not None:
         info["ba"] = ba_info
+    if annotate:
+        info["annotated"] = annotated
     return panos, info

@@ -292,6 +292,131 @@ def cropNonzeroBbox(panorama, canvasColor="black"):
     return panorama[r1 - 1:r2, c1 - 1:c2], (r1, r2, c1, c2), True
 
 
+# ---- rgbAnnotation: outlines and numbers (renderPanorama.m:438-477, :653-679, :1148-1280) -----------------------------
+def vivid_palette(n):
+    """n x 3 uint8 outline colours.  The reference's brightColors draws from rand and cannot be reproduced; this is a stated
+    deterministic stand-in: hue_k = frac(k * (sqrt(5) - 1) / 2), k = 0 .. n-1 (golden-ratio steps), saturation = value = 1,
+    the usual six-sector HSV -> RGB in f64, each channel floor(255 v + 0.5).  Every row has a channel at 255."""
+    k = np.arange(int(n), dtype=np.float64)
+    h6 = 6.0 * np.mod(k * ((math.sqrt(5.0) - 1.0) / 2.0), 1.0)
+    sector = np.floor(h6).astype(np.int64) % 6
+    f = h6 - np.floor(h6)
+    one, zero = np.ones_like(f), np.zeros_like(f)
+    table = np.stack([np.stack([one, f, zero], 1), np.stack([1 - f, one, zero], 1), np.stack([zero, one, f], 1),
+                      np.stack([zero, 1 - f, one], 1), np.stack([f, zero, one], 1), np.stack([one, zero, 1 - f], 1)])
+    rgb = table[sector, np.arange(int(n))] if n else np.zeros((0, 3))
+    return np.floor(255.0 * rgb + 0.5).astype(np.uint8)
+
+
+def warped_boxes(cameras, imgSize, geo):
+    """allWarpedBoxes / warpedBBoxes (renderPanorama.m:1148-1280) for the canvas `geo` (canvas_geometry): the corners
+    (1,1), (1,W), (H,W), (H,1) [row, col] of every image as rays rayW = R' * (K \\ [x; y; 1]), through the forward map of
+    geo['mode'], in f64.  Returns (polys [n, 4, 2] as x, y; centers [n, 2] = the mean of the four corners), in 1-based
+    coordinates of the UNCROPPED canvas: x = (a - o0) * fPan + 1, the exact inverse of the pixel-to-direction map the
+    renderer uses (pixel column c looks along a = o0 + (c - 1) / fPan), so an image corner lands on the canvas pixel that
+    samples it.  (The reference writes x = (a - o0) * fPan, one pixel up and to the left; DESIGN.md, "Annotation contract".)"""
+    mode = geo["mode"]
+    f, o0, o1 = float(geo["fPan"]), float(geo["o0"]), float(geo["o1"])
+    Rref = np.asarray(geo["Rref"], np.float64)
+    n = len(cameras)
+    polys = np.zeros((n, 4, 2), np.float64)
+    with np.errstate(all="ignore"):
+        for i, cam in enumerate(cameras):
+            Hc, Wc = float(imgSize[i][0]), float(imgSize[i][1])
+            xy1 = np.array([[1.0, Wc, Wc, 1.0], [1.0, 1.0, Hc, Hc], [1.0, 1.0, 1.0, 1.0]])
+            rayC = _solve_K(np.asarray(cam["K"], np.float64)[None], xy1[None])[0]
+            rayW = np.asarray(cam["R"], np.float64).T @ rayC
+            if mode in ("planar", "perspective"):
+                rayR = Rref @ rayW
+                a, b = rayR[0] / rayR[2], rayR[1] / rayR[2]
+            elif mode == "cylindrical":
+                a = np.arctan2(rayW[0], rayW[2])
+                b = rayW[1] / np.hypot(rayW[0], rayW[2])
+            elif mode in ("spherical", "equirectangular"):
+                a = np.arctan2(rayW[0], rayW[2])
+                b = np.arctan2(rayW[1], np.hypot(rayW[0], rayW[2]))
+            elif mode == "stereographic":
+                rayR = Rref @ rayW
+                xr, yr, zr = rayR / np.sqrt((rayR ** 2).sum(0))
+                den = np.maximum(1 + zr, 1e-6)  # :1269
+                a, b = xr / den, yr / den
+            else:
+                raise ValueError("mode")
+            polys[i, :, 0] = (a - o0) * f + 1.0
+            polys[i, :, 1] = (b - o1) * f + 1.0
+    return polys, polys.mean(axis=1)
+
+
+def planar_boxes(shapes, tforms, view):
+    """The boxes of pureNonRotationalImagesToCanvas (renderPanorama.m:738-742): the corners (x, y) = (1,1), (W,1), (W,H), (1,H)
+    through transformPointsForwardScratch, minus the world limits of the canvas; the centre is the mean over the CLOSED
+    five-point polygon the reference builds (the first corner counts twice), as written."""
+    from .imageProcessing import transformPointsForwardScratch
+
+    n = len(shapes)
+    polys, centers = np.zeros((n, 4, 2), np.float64), np.zeros((n, 2), np.float64)
+    for k in range(n):
+        r, c = float(shapes[k][0]), float(shapes[k][1])
+        q = np.asarray(transformPointsForwardScratch(tforms[k], np.array([[1, 1], [c, 1], [c, r], [1, r], [1, 1]], np.float64)),
+                       np.float64)
+        q = q - np.array([float(view["XWorldLimits"][0]), float(view["YWorldLimits"][0])])
+        polys[k] = q[:4]
+        centers[k] = q.mean(axis=0)
+    return polys, centers
+
+
+def annotate_panorama(pano, polys, anchors, colors=None, lineWidth=2):
+    """rgbAnnotation = insertText(insertShape(pano, 'Polygon', ...), anchors, 1:numValid) on the device
+    (aps_annotate_panorama; the raster rule is DESIGN.md's "Annotation contract").  pano: uint8 H x W x 3 (H x W and
+    H x W x 1 are replicated), a numpy array or a torch tensor; the result is a new array of the same kind, resident when
+    pano is, and pano is not written.  polys [n, 4, 2] (x, y), anchors [n, 2], 1-based canvas coordinates; colors [n, 3]
+    uint8 (default vivid_palette(n)).  Returns (annotated, number of polygons drawn = the highest label)."""
+    polys = np.ascontiguousarray(np.asarray(polys, np.float64).reshape(-1, 4, 2))
+    n = int(polys.shape[0])
+    anchors = np.ascontiguousarray(np.asarray(anchors, np.float64).reshape(-1, 2))
+    colors = vivid_palette(n) if colors is None else np.ascontiguousarray(np.asarray(colors).reshape(-1, 3).astype(np.uint8))
+    if anchors.shape[0] != n or colors.shape[0] != n:
+        raise ValueError("polys, anchors and colors must have one row per polygon")
+    drawn = C.c_int(0)
+    is_t = _capi.is_torch(pano)
+    if not is_t:
+        pano = np.asarray(pano)
+    if pano.ndim == 2:
+        pano = pano[:, :, None]
+    if str(pano.dtype).split(".")[-1] != "uint8" or pano.ndim != 3 or int(pano.shape[2]) not in (1, 3):
+        raise ValueError(f"pano must be uint8 H x W, H x W x 1 or H x W x 3, got {pano.dtype} {tuple(pano.shape)}")
+    if is_t and pano.is_cuda:
+        check(lib.aps_synchronize())  # the panorama may still be in flight on the library's stream of this thread
+    # `own`: src is a copy made here (a replicated channel, a cropped view made contiguous), so it is drawn on in place:
+    # one copy of the canvas either way
+    if int(pano.shape[2]) == 1:
+        src, own = (pano.expand(-1, -1, 3).contiguous() if is_t else np.repeat(pano, 3, axis=2)), True
+    elif is_t:
+        src, own = (pano, False) if pano.is_contiguous() else (pano.contiguous(), True)
+    else:
+        src, own = (pano, False) if pano.flags.c_contiguous else (np.ascontiguousarray(pano), True)
+    H, W = int(src.shape[0]), int(src.shape[1])
+    if own:
+        dst = src
+    elif is_t:
+        import torch
+
+        dst = torch.empty_like(src)
+    else:
+        dst = np.empty_like(src)
+    if is_t and src.is_cuda:
+        import torch
+
+        torch.cuda.current_stream().synchronize()  # torch produced them; the library draws on its own stream
+    check(lib.aps_annotate_panorama(ptr(src), H, W, ptr(polys), ptr(anchors), ptr(colors), n, int(lineWidth), ptr(dst),
+                                    C.byref(drawn)))
+    return dst, int(drawn.value)
+
+
+def _wants_annotation(opts):
+    return bool(opts) and bool(opts.get("showPanoramaImgsNums")) and bool(opts.get("showCropBoundingBox"))
+
+
 def make_image_structs(images, cameras, gains=None):
     n = len(images)
     arr = (_capi.aps_image * n)()
@@ -622,7 +747,10 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
     (_planar_host: every image warped to the FULL canvas by imageWarp, numpy in between), whose bytes the device path
     reproduces.
     Gains: pass `gains` (N x 3), or set opts['gainCompensation'] to have gainCompensationH run on the warped images
-    (:584-591: overlap statistics on the device, solve on the host); otherwise ones."""
+    (:584-591: overlap statistics on the device, solve on the host); otherwise ones.
+    rgbAnnotation (:653-679): with opts['showPanoramaImgsNums'] and opts['showCropBoundingBox'] both true, the panorama with
+    every image's outline (planar_boxes) and number drawn on the device (annotate_panorama; opts['annotationColors'] N x 3
+    overrides vivid_palette), for all three compositors; otherwise None.  The panorama itself is the same bytes either way."""
     from .imageProcessing import imref2dScratch, outputLimitsScratch
 
     o = {"blending": "multiband", "pyrLevels": 3, "pyrSigma": 1.0, "canvasColor": "black",
@@ -647,7 +775,7 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
         one = gains is None and not o.get("gainCompensation") or gains is not None and all(np.size(g) == 1 for g in gains)
         if gray and one and str(o["blending"]).lower() == "none":
             pano = pano[:, :, :1]  # (the host path's 'none' keeps the single channel of its input; the blends return three)
-        return pano, None
+        return pano, _planar_annotation(pano, images, tforms, view, o)
     if any(_capi.is_torch(im) for im in images):
         images = [im.cpu().numpy() if _capi.is_torch(im) else im for im in images]
     pano = _planar_host(images, tforms, view, o, gains)
@@ -655,7 +783,16 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
         import torch
 
         pano = torch.from_numpy(pano).cuda()
-    return pano, None
+    return pano, _planar_annotation(pano, images, tforms, view, o)
+
+
+def _planar_annotation(pano, images, tforms, view, o):
+    """renderPanorama.m:653-679: the annotated planar-scan panorama (None unless both flags are set); resident when pano is."""
+    if not _wants_annotation(o):
+        return None
+    polys, centers = planar_boxes([im.shape for im in images], tforms, view)
+    ann, _ = annotate_panorama(pano, polys, centers, o.get("annotationColors"), int(o.get("annotationLineWidth", 2)))
+    return ann
 
 
 def _planar_host(images, tforms, view, o, gains=None):
@@ -700,7 +837,12 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
         canvas — the value the reference's auto-tiler reaches whenever memory is plentiful.
       * gains: pass `gains` (N x 3), or set opts['gainCompensation'] explicitly to have gainCompensationRKf run
         (statistics on the device, solve on the host); otherwise ones.
-      * annotations (insertShape/insertText) are not produced: rgbAnnotation is always None."""
+      * rgbAnnotation (:438-477) is produced when opts carries showPanoramaImgsNums and showCropBoundingBox, both true: the
+        (cropped) panorama with every image's warped outline (warped_boxes, shifted by the crop origin as :434-455) and its
+        number, drawn on the device by annotate_panorama under this project's own raster rule ("Annotation
+        contract"; insertShape / insertText are closed).  Colours: opts['annotationColors'] (N x 3) or vivid_palette(N) -
+        brightColors draws from rand.  Resident when device_out is set; None otherwise and for a tile shard.  The panorama
+        itself is the same bytes with and without the flags."""
     if cameras and (cameras[0].get("noRotation", 0) == 1 or input.get("forcePlanarScan", False)):
         # renderPanorama.m:78-90: planar scans bypass the tiled ray renderer
         pano, ann = pureNonRotationalPanoramas(images, cameras, len(images), opts or {}, gains, device_out)
@@ -755,13 +897,20 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
         check(lib.aps_render_tiles(arr, len(images), C.byref(cv), C.byref(ro), _capi.APS_IMG_U8_HWC,
                                    first, step, ptr(pano), ptr(cov)))
     del keep
+    rect = (1, H, 1, W)
     if o["cropBorder"] and tile_subset is None:  # renderPanorama.m:430-432 (a tile shard is cropped after it is combined)
         if device_out:
             check(lib.aps_synchronize())  # the panorama was painted on the library's stream of this thread
-        pano, _, _ = cropNonzeroBbox(pano, o["canvasColor"])
+        pano, rect, _ = cropNonzeroBbox(pano, o["canvasColor"])
+    ann = None
+    if _wants_annotation(o) and tile_subset is None:
+        polys, centers = warped_boxes(cameras, imgSize, geo)
+        shift = np.array([rect[2] - 1, rect[0] - 1], np.float64)  # dx = c1 - 1, dy = r1 - 1 (:434-455)
+        ann, _ = annotate_panorama(pano, polys - shift, centers - shift, o.get("annotationColors"),
+                                   int(o.get("annotationLineWidth", 2)))
     if return_covered:
-        return pano, None, cov, geo
-    return pano, None
+        return pano, ann, cov, geo
+    return pano, ann
 
 
 def warp_tile(image, camera, geo, r0, c0, ht, wt, anglePower=2.0, gain=(1.0, 1.0, 1.0)):
@@ -774,3 +923,63 @@ def warp_tile(image, camera, geo, r0, c0, ht, wt, anglePower=2.0, gain=(1.0, 1.0
     Wf = np.zeros((ht, wt), np.float32)
     check(lib.aps_warp_tile(arr, C.byref(cv), r0, c0, ht, wt, float(anglePower), ptr(S), ptr(M), ptr(Wa), ptr(Wf)))
     return S, M.astype(bool), Wa, Wf
+
+
+_DISPLAY_PROJECTIONS = ("planar", "cylindrical", "spherical", "equirectangular", "stereographic")
+
+
+def displayPanorama(input, finalPanoramaTforms, finalrefIdxs, imagesAll, imageSizesAll, panoIndices, device_out=False):
+    """panoStore = displayPanorama(input, finalPanoramaTforms, finalrefIdxs, imagesAll, imageSizesAll, panoIndices)
+    (displayPanorama.m:58-137): every component rendered in every projection of input['panorama2DisplaynSave'] (one
+    string or a list of them) with the opts of :100-111.  finalPanoramaTforms: per component its list of camera dicts (an
+    empty one is skipped, :90); finalrefIdxs and panoIndices are 1-based like the reference's (the messages name 1..N).
+    Returns the list of dicts cropNsavePanorama consumes: one per component, projection -> [panorama, annotated or None]
+    (the reference's 1 x C struct array of 1 x 2 cells); the arrays are resident torch tensors with device_out.  Same
+    length and index checks, same messages.  No figures are drawn (input.displayPanoramas is not read); input['tile'], when
+    present, is passed on as opts['tile'] (renderPanorama's explicit tile)."""
+    nC = len(finalPanoramaTforms)
+    if np.size(finalrefIdxs) != nC:
+        raise ValueError(f"displayPanorama:InvalidRefIdxsLength: finalrefIdxs must have one entry per component ({nC}).")
+    if len(panoIndices) != nC:
+        raise ValueError(f"displayPanorama:InvalidPanoIndicesLength: panoIndices must have one cell per component ({nC}).")
+    refs = np.asarray(finalrefIdxs).reshape(-1)
+    nImgs = len(imagesAll)
+    idx_lists = []
+    for ii in range(nC):
+        raw = panoIndices[ii]
+        try:
+            idxs = np.asarray(raw)
+            numeric = idxs.dtype.kind in "iuf" and idxs.ndim <= 2 and (idxs.ndim < 2 or 1 in idxs.shape or idxs.size == 0)
+        except Exception:  # noqa: BLE001 - a ragged or non-array cell is not a numeric vector
+            idxs, numeric = np.zeros(0), False
+        if not numeric:
+            if idxs.size == 0:
+                idx_lists.append(np.zeros(0, np.int64))
+                continue
+            raise ValueError(f"displayPanorama:InvalidPanoIndexType: panoIndices{{{ii + 1}}} must be a numeric vector of image indices.")
+        idxs = idxs.reshape(-1)
+        if idxs.size and (idxs.min() < 1 or idxs.max() > nImgs):
+            raise ValueError(f"displayPanorama:ImageIndexOutOfBounds: panoIndices{{{ii + 1}}} has indices outside 1..{nImgs}.")
+        idx_lists.append(idxs.astype(np.int64))
+    projections = input["panorama2DisplaynSave"]
+    projections = [projections] if isinstance(projections, str) else [str(p) for p in projections]
+    panoStore = [dict() for _ in range(nC)]
+    for ii in range(nC):
+        cameras = finalPanoramaTforms[ii]
+        if cameras is None or len(cameras) == 0:
+            continue
+        refIdx = int(refs[ii]) - 1
+        images = [imagesAll[k - 1] for k in idx_lists[ii]]
+        imageSizes = [tuple(int(v) for v in np.asarray(imageSizesAll[k - 1]).reshape(-1)) for k in idx_lists[ii]]
+        opts = {"fPan": float(np.asarray(cameras[refIdx]["K"])[0, 0]), "resScale": 1.0, "anglePower": 2, "cropBorder": True,
+                "canvasColor": input["canvasColor"], "gainCompensation": input["gainCompensation"], "sigmaN": input["sigmaN"],
+                "sigmag": input["sigmag"], "pyrLevels": input["bands"], "blending": input["blending"],
+                "pyrSigma": input["MBBsigma"], "showPanoramaImgsNums": input["showPanoramaImgsNums"],
+                "showCropBoundingBox": input["showCropBoundingBox"], "useMATLABImwarp": input.get("useMATLABImwarp", 0)}
+        if input.get("tile") is not None:
+            opts["tile"] = input["tile"]
+        for projection in projections:
+            panorama, annoRGB = renderPanorama(input, images, imageSizes, cameras, projection, refIdx, opts, device_out=device_out)
+            if projection in _DISPLAY_PROJECTIONS:  # :126-136
+                panoStore[ii][projection] = [panorama, annoRGB]
+    return panoStore

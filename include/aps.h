@@ -539,6 +539,28 @@ int aps_crop_rect(const uint8_t* img, int64_t h, int64_t w, int layout, int canv
 int aps_crop_nonzero_bbox(const uint8_t* img, int64_t h, int64_t w, int layout, int canvas_white, int64_t* rect,
                           int* did_crop);
 
+/* rgbAnnotation of renderPanorama (renderPanorama.m:438-477; planar scans :653-679): the panorama with every image's warped
+ * outline (insertShape 'Polygon', LineWidth 2) and its number in a red box at the centroid (insertText), drawn on the device.
+ * Both toolbox calls are closed; the raster rule is this library's own ("Annotation contract"; parity with MATLAB
+ * unpinned), integer arithmetic throughout, restated byte for byte by tests/annotate_mirror.py.
+ *   src, dst : uint8 h x w x 3, APS_IMG_U8_HWC, host or device memory each; dst == src draws in place, otherwise the two must
+ *              not overlap and src is never written.
+ *   polys    : f64 n x 4 x 2, the corners of polygon p as x then y in 1-based canvas coordinates (pixel (r, c) has its centre
+ *              at x = c, y = r); anchors: f64 n x 2 (x, y), where label p's box has its top-left corner; colors: uint8 n x 3.
+ *              Host or device memory (they are read on the host: the edges are binned to canvas tiles there).
+ *   A polygon is valid when its eight coordinates are finite and |v| <= 2^20; the others are skipped and NOT numbered: the
+ *   labels are 1 .. *n_drawn in order of the valid polygons (the reference numbers 1:numel(valid) the same way, :474).
+ *   line_width in 1..64: an edge paints every pixel whose centre lies within line_width / 2 of the closed segment between its
+ *   corners quantised to 1/16 px (round caps and joins); a later polygon paints over an earlier one; labels (5 x 7 digit font
+ *   scaled by 3, box (255, 0, 0) at 60 %, text white) come after all outlines in ascending order; everything is clipped.
+ *   *n_drawn (host memory): the number of valid polygons.
+ * Cost: one copy src -> dst (none in place), then one workgroup per 64 x 64 canvas tile that an edge or a label touches; one
+ * host synchronisation, at the end of the call (a resident result is complete on return).
+ * Errors, all before any device work: APS_E_ARG for a NULL pointer (the three tables may be NULL when n == 0), h or w < 1 (or
+ * above 2^31 - 1), n < 0, line_width outside 1..64, partially overlapping src / dst. */
+int aps_annotate_panorama(const uint8_t* src, int64_t h, int64_t w, const double* polys, const double* anchors,
+                          const uint8_t* colors, int n, int line_width, uint8_t* dst, int* n_drawn);
+
 /* SURVEY 8(f) rank 1 -- the overlap statistics of gainCompensationRKf (PP/gainCompensation/gainCompensationRKf.m:96-149,
  * 239-367): every `stride`-th canvas point (1-based coordinates, :106-107) that two images i < j both cover
  * (front, inside, tent weight > 0) adds 1 to n_ij(i,j) and the two bilinear RAW (0..255) colour samples to
