@@ -236,6 +236,10 @@ _SIGNATURES = {
                                  _vp, _i64, C.POINTER(_i64)],
     "aps_fast_extract_uniform": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_uniform_params), _vp, _i, _i64, _vp, _i64,
                                  _vp, _i64, C.POINTER(_i64)],
+    "aps_sift_extract_batch_strongest": [C.POINTER(aps_sift_view), _i, _i, _i, _i, _i, C.POINTER(aps_sift_strongest_params),
+                                         _i, _i64, _i64],
+    "aps_sift_extract_batch_uniform": [C.POINTER(aps_sift_view), _i, _i, _i, _i, _i, C.POINTER(aps_sift_uniform_params),
+                                       _i, _i64, _i64],
     "aps_uniform_quota": [_vp, _i, _i64, _vp],
     "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
 }

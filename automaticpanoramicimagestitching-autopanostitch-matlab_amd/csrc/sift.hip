@@ -19,11 +19,20 @@
 //   refine_kernel                  : Newton refinement + contrast/edge tests, one lane per candidate.
 //   orient_kernel / descr_kernel   : one 64-lane wave per keypoint, histograms in LDS (int64 atomics).
 //   sift_contr_key_kernel, select_by_key, select_compact_kernel (select_dev.h)
-//                                  : aps_sift_extract_strongest only - the N rows of largest contrast, picked from the list of
-//                                    oriented keypoints before descr_kernel runs (DESIGN.md "Strongest-N for SIFT and SURF").
+//                                  : aps_sift_extract_strongest and a group of one - the N rows of largest contrast, picked from
+//                                    the list of oriented keypoints before descr_kernel runs (DESIGN.md "Strongest-N for SIFT and
+//                                    SURF"): a 32-bit sort.
 //   sift_uniform_key_kernel, select_uniform, select_compact_kernel (select_dev.h)
-//                                  : aps_sift_extract_uniform only - N rows spread over the cells of a grid, the largest
-//                                    contrast first within a cell (DESIGN.md "Uniform-N selection").
+//                                  : aps_sift_extract_uniform, aps_sift_extract_batch_uniform - N rows per view spread over the
+//                                    cells of a grid, the largest contrast first within a cell (DESIGN.md "Uniform-N selection");
+//                                    and aps_sift_extract_batch_strongest on two views or more, as the 1 x 1 grid.
+//
+// The selection is a stage of the group chain (select_rows): the oriented rows of a group are view-contiguous, a row's view is the
+// one its keypoint record carries, segment = view * cells + cell, and the views' budgets min(rows, N) are on the host since the
+// read-back of orient_keypoints.  One key kernel, one sort, one bounds / quota / flag pass, one ballot and scan and one compaction
+// serve all the views, without a further read-back; the stage is skipped only when no view of the group is cut.  A group's
+// strongest-N takes the uniform form with one cell per view (a 32 + 14-bit sort, byte for byte the strongest result) rather than a
+// 64-bit sort of a key with the view in its top bits.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1039,8 +1048,12 @@ __global__ __launch_bounds__(256) void sift_contr_key_kernel(const KpRec* __rest
     vals[i] = i;
 }
 
-// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the row's segment = its cell in the rows x cols grid over the H x W
-// image, from the pixel clamp(floor(loc) - 1, 0, size - 1) of the row's 1-based f64 location.
+// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the row's segment = view * (rows * cols) + its cell in the
+// rows x cols grid over the H x W image, from the pixel clamp(floor(loc) - 1, 0, size - 1) of the row's 1-based f64 location.  The
+// view is the one the keypoint's record carries (key_view), so no table of the views' row ranges is looked up.  A group's
+// strongest-N is the 1 x 1 grid: segment = view.
+static_assert(kMaxViews <= kSelectGroups, "a view of the group is a group of the selection");
+static_assert(kMaxViews * kUniformMaxCells <= (1 << kSegmentBits), "view * cells + cell fits the segment field");
 __global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __restrict__ kps, const OrientedKp* __restrict__ oks,
                                                                unsigned int n, int H, int W, int rows, int cols,
                                                                unsigned long long* __restrict__ keys, unsigned int* __restrict__ vals) {
@@ -1050,7 +1063,8 @@ __global__ __launch_bounds__(256) void sift_uniform_key_kernel(const KpRec* __re
     const float step = octave_step(key_octave(kp.key));
     const double x = sift_loc(sift_pt((int)(kp.key & 0xffff), kp.xc), step), y = sift_loc(sift_pt((int)((kp.key >> 16) & 0xffff), kp.xr), step);
     const int px = min(max((int)floor(x) - 1, 0), W - 1), py = min(max((int)floor(y) - 1, 0), H - 1);
-    keys[i] = (unsigned long long)uniform_cell(py, px, H, W, rows, cols) << kSegmentShift | strength_key_f32(kp.contr);
+    const int seg = key_view(kp.key) * (rows * cols) + uniform_cell(py, px, H, W, rows, cols);
+    keys[i] = (unsigned long long)seg << kSegmentShift | strength_key_f32(kp.contr);
     vals[i] = i;
 }
 
@@ -1706,11 +1720,14 @@ static unsigned int orient_keypoints(const Pyramid& P, const Ws<KpRec>& kps, con
     return segment_counts(O.opos, O.ocount, segments_of(n_kp, P.nv), P.nv, n_rows);
 }
 
-// The n_out <= n_all rows to describe, in canonical order: all n_all oriented keypoints, or with n_out < n_all (one view) the ones
-// that come first by (contrast descending, canonical index ascending) - over the whole image, or with grid_rows > 0 within their cell
-// of the grid_rows x grid_cols grid over the H x W image, the cells' shares by water-filling n_out.  No read-back.
+// The rows to describe, in canonical order, the views' one after the other: all n_all oriented keypoints of the group, or when a
+// view is cut (n_out < n_all) the n_view_out[v] of every view v that come first by (contrast descending, canonical index ascending) -
+// over the whole image, or with grid_rows > 0 within their cell of the grid_rows x grid_cols grid over the H x W image, the cells'
+// shares by water-filling n_view_out[v].  One selection serves the group: a view is a group of the uniform form (a view that keeps
+// all its rows is filled to the brim), and the strongest rows of several views are its 1 x 1 grid, which is the strongest result
+// byte for byte.  The strongest rows of a single view keep their 32-bit sort (select_by_key).  No read-back.
 static Ws<OrientedKp> select_rows(const Ws<KpRec>& kps, unsigned int n_kp, const Orientations& O, unsigned int n_all, unsigned int n_out,
-                                  int H, int W, int grid_rows, int grid_cols) {
+                                  const unsigned int* n_view_out, int nv, int H, int W, int grid_rows, int grid_cols) {
     Ws<OrientedKp> oks_all(n_all);
     expand_oriented_kernel<<<cdiv(n_kp, 256), 256, 0, stream()>>>(O.ocount, O.opos, O.oangle, n_kp, oks_all);
     check_launch("expand_oriented_kernel");
@@ -1719,12 +1736,13 @@ static Ws<OrientedKp> select_rows(const Ws<KpRec>& kps, unsigned int n_kp, const
     Ws<unsigned long long> skeys(n_all), words;
     Ws<unsigned int> svals(n_all), sprefix;
     unsigned int n_words = 0;
-    if (grid_rows > 0) {
-        sift_uniform_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, H, W, grid_rows, grid_cols, skeys, svals);
+    if (grid_rows > 0 || nv > 1) {
+        const int rows = grid_rows > 0 ? grid_rows : 1, cols = grid_rows > 0 ? grid_cols : 1;
+        sift_uniform_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, H, W, rows, cols, skeys, svals);
         check_launch("sift_uniform_key_kernel");
         UniformBudget budget = {};
-        budget.q[0] = n_out;
-        select_uniform(skeys, nullptr, svals, n_all, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, sprefix, n_words);
+        for (int v = 0; v < nv; ++v) budget.q[v] = n_view_out[v];
+        select_uniform(skeys, nullptr, svals, n_all, (unsigned int)nv, (unsigned int)(rows * cols), budget, words, sprefix, n_words);
     } else {
         sift_contr_key_kernel<<<cdiv(n_all, 256), 256, 0, stream()>>>(kps, oks_all, n_all, skeys, svals);
         check_launch("sift_contr_key_kernel");
@@ -1792,10 +1810,11 @@ static void describe(const Pyramid& P, const Ws<KpRec>& kps, const Ws<OrientedKp
 using namespace aps;
 
 // The body of every SIFT entry, on a group of nv views of one shape: aps_sift_extract_batch's group, or the single entries' group of
-// one.  n_strongest = 0: every row (aps_sift_extract); n_strongest > 0 (one view): the n_strongest rows of largest contrast
-// (aps_sift_extract_strongest, DESIGN.md "Strongest-N for SIFT and SURF"), or with grid_rows > 0 spread over the cells of a
-// grid_rows x grid_cols grid instead (aps_sift_extract_uniform, DESIGN.md "Uniform-N selection").  views[v].count is the view's rows
-// whenever the counts are known, so on APS_E_CAP every view holds what it needs.
+// one.  n_strongest = 0: every row (aps_sift_extract, aps_sift_extract_batch); n_strongest > 0: of every view, its n_strongest rows
+// of largest contrast (aps_sift_extract_strongest, aps_sift_extract_batch_strongest, DESIGN.md "Strongest-N for SIFT and SURF"), or
+// with grid_rows > 0 spread over the cells of a grid_rows x grid_cols grid instead (aps_sift_extract_uniform,
+// aps_sift_extract_batch_uniform, DESIGN.md "Uniform-N selection").  views[v].count is the view's rows whenever the counts are
+// known, so on APS_E_CAP every view holds what it needs.
 static void sift_chain(aps_sift_view* views, int nv, int height, int width, int channels, int img_layout, const aps_sift_params* params,
                        long long n_strongest, int grid_rows, int grid_cols, int desc_layout, int64_t ldd, int64_t ldl) {
     check_sift_args(views, nv, height, width, channels, img_layout, params, desc_layout);
@@ -1831,7 +1850,7 @@ static void sift_chain(aps_sift_view* views, int nv, int height, int width, int 
     for (int v = 0; v < nv && !fits; ++v)
         if ((int64_t)n_out[v] > views[v].cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)views[v].cap, n_out[v]);
     if (n_out_sum == 0) return;
-    const Ws<OrientedKp> oks = select_rows(kps, n_kp_sum, ori, n_all_sum, n_out_sum, H, W, grid_rows, grid_cols);
+    const Ws<OrientedKp> oks = select_rows(kps, n_kp_sum, ori, n_all_sum, n_out_sum, n_out, nv, H, W, grid_rows, grid_cols);
     describe(pyr, kps, oks, n_out, n_out_sum, views, desc_layout, ldd, ldl);
 }
 
@@ -1861,6 +1880,25 @@ int aps_sift_extract(const uint8_t* img, int height, int width, int channels, in
 int aps_sift_extract_batch(aps_sift_view* views, int n_views, int height, int width, int channels, int img_layout,
                            const aps_sift_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
     return guarded([&] { sift_chain(views, n_views, height, width, channels, img_layout, params, 0, 0, 0, desc_layout, ldd, ldl); });
+}
+
+int aps_sift_extract_batch_strongest(aps_sift_view* views, int n_views, int height, int width, int channels, int img_layout,
+                                     const aps_sift_strongest_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+        sift_chain(views, n_views, height, width, channels, img_layout, &params->sift, params->n_strongest, 0, 0, desc_layout, ldd, ldl);
+    });
+}
+
+int aps_sift_extract_batch_uniform(aps_sift_view* views, int n_views, int height, int width, int channels, int img_layout,
+                                   const aps_sift_uniform_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
+        sift_chain(views, n_views, height, width, channels, img_layout, &params->strongest.sift, params->strongest.n_strongest,
+                   params->grid_rows, params->grid_cols, desc_layout, ldd, ldl);
+    });
 }
 
 int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int channels, int img_layout,

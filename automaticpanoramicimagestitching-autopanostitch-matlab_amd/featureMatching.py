@@ -742,10 +742,14 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
 def sift_extract_batch(input, images, device_out=False, want_aux=False, points_device=False, compact=False):
     """aps_sift_extract_batch with automatic capacity: sift_extract for 1.._capi.APS_SIFT_MAX_VIEWS images of one shape in one call,
     every stage once for the group.  Returns a list of sift_extract's results, one (features, validPts[, aux]) per image, bit for
-    bit those of sift_extract(input, image, ...) on each.  The arguments are sift_extract's; input.NumStrongest and input.NumUniform
-    are per-view selections and not taken here (ValueError)."""
-    if "NumStrongest" in input or "NumUniform" in input:
-        raise ValueError("sift_extract_batch extracts every row: NumStrongest / NumUniform go through sift_extract, view by view")
+    bit those of sift_extract(input, image, ...) on each.  The arguments are sift_extract's.
+
+    input.NumStrongest and input.NumUniform (with input.UniformGrid) select per view, as in sift_extract: every view keeps its own
+    min(N, rows) rows through aps_sift_extract_batch_strongest / aps_sift_extract_batch_uniform, whose selection is one more stage of
+    the group's chain (one sort and one compaction for all the views, no further read-back).  The capacity per view is then
+    min(default, max(N, 1)), so a resident result holds N rows per view.  Both keys together are a ValueError, raised before any
+    library call; the values themselves are the library's to refuse (APS_E_ARG)."""
+    uniform = _uniform_keys(input)
     g = len(images)
     imgs = [im.contiguous() if _capi.is_torch(im) else np.ascontiguousarray(im, np.uint8) for im in images]
     shape = tuple(imgs[0].shape) if g else ()
@@ -755,8 +759,15 @@ def sift_extract_batch(input, images, device_out=False, want_aux=False, points_d
     c = 1 if len(shape) == 2 else (int(shape[2]) if g else 3)
     if c not in (1, 3):
         raise ValueError("image must be gray or RGB")
-    prm = _sift_params(input)
-    caps = [max(4096, (h * w) // 64)] * g
+    prm, entry = _sift_params(input), lib.aps_sift_extract_batch
+    cap = max(4096, (h * w) // 64)
+    if "NumStrongest" in input:
+        prm, entry = _sift_strongest_params(input), lib.aps_sift_extract_batch_strongest
+        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
+    if uniform:
+        prm = _uniform_params(_capi.aps_sift_uniform_params, _sift_strongest_params(input, uniform[0]), uniform)
+        entry, cap = lib.aps_sift_extract_batch_uniform, min(cap, max(uniform[0], 1))
+    caps = [cap] * g
     dev_pts = device_out and points_device
     if device_out:
         import torch
@@ -773,7 +784,7 @@ def sift_extract_batch(input, images, device_out=False, want_aux=False, points_d
         if device_out:
             _fence_fresh_blocks()
         # (the views share one capacity, which is the leading dimension of their column-major locations)
-        rc = lib.aps_sift_extract_batch(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, caps[0] if g else 0)
+        rc = entry(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, caps[0] if g else 0)
         if rc == _capi.APS_E_CAP and any(views[k].count > caps[k] for k in range(g)):
             caps = [max(int(views[k].count) for k in range(g))] * g
             continue

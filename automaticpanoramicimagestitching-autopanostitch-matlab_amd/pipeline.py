@@ -57,8 +57,8 @@ def _sync():
 _SIFT_POOL = None
 
 
-# Host threads / HIP streams of the per-image feature extraction (host images, SURF, FAST, NumStrongest / NumUniform; resident SIFT
-# views go in groups, below).  Measured on the 64 x 4K scene on several boxes:
+# Host threads / HIP streams of the per-image feature extraction (host images, SURF, FAST; resident SIFT views go in groups, below,
+# with or without NumStrongest / NumUniform).  Measured on the 64 x 4K scene on several boxes:
 # 4, 5, 10, 11, 12, 14 threads give 88-93 ms, 10 the best or tied everywhere; 7-9 threads read 100 ms on some boxes and
 # 92 on others (reproducibly per box; the HIP runtime maps streams onto 8 hardware queues), 12 costs the end-to-end
 # step's uploads 14 ms.
@@ -153,8 +153,9 @@ def release_device_memory():
 def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_device=False):
     """The asynchronous form of sift_many: one future per image, submitted in input order to the worker pool, so that
     a caller can start matching the first images while the later ones are still being extracted (parallel._match_pass).
-    Resident SIFT images without a per-view selection are submitted as groups of up to SIFT_GROUP_VIEWS consecutive images of one
-    shape (fm.sift_extract_batch) to SIFT_GROUP_WORKERS threads; the futures of a group resolve together.
+    Resident SIFT images are submitted as groups of up to SIFT_GROUP_VIEWS consecutive images of one shape (fm.sift_extract_batch,
+    which selects per view under input.NumStrongest / input.NumUniform) to SIFT_GROUP_WORKERS threads; the futures of a group
+    resolve together.
     Each future resolves to (descriptors, keypoints) once that worker's stream has finished the image.
     points_device: resident images only - the keypoints stay on the device (fm.sift_extract)."""
     global _SIFT_POOL, _SIFT_GROUP_POOL
@@ -166,7 +167,7 @@ def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_
     dev = _capi.is_torch(images[0]) and images[0].is_cuda
     if dev and ready is None:
         torch.cuda.synchronize()  # the images were produced on torch's stream; worker streams must see them
-    if dev and input.get("detector", "SIFT") == "SIFT" and "NumStrongest" not in input and "NumUniform" not in input:
+    if dev and input.get("detector", "SIFT") == "SIFT":
         # resident SIFT views: groups of consecutive images of one shape, one pool task per group, one future per image
         if _SIFT_GROUP_POOL is None:
             _SIFT_GROUP_POOL = ThreadPoolExecutor(max_workers=SIFT_GROUP_WORKERS, initializer=_init_worker,

@@ -779,6 +779,19 @@ int aps_sift_extract_strongest(const uint8_t* img, int height, int width, int ch
                                const aps_sift_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
                                double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
+/* aps_sift_extract_strongest for a group of views of one shape: aps_sift_extract_batch's chain with the selection as one more stage
+ * of the group.  The rows of view k (descriptor, location, aux, order and count) are bit for bit those of aps_sift_extract_strongest
+ * on views[k].img with the same params, whatever the other views contain; views[k].count = rows kept, and
+ * views[k].cap >= min(candidates_k, n_strongest) always suffices.  When any view's kept rows exceed its cap nothing is written and the
+ * call returns APS_E_CAP with EVERY view's count set to the rows it needs.  A view without features gets count = 0 and does not touch
+ * the others; sift.max_features stays the candidate capacity of each view.  Before any device work: n_strongest < 1, n_views outside
+ * 1..APS_SIFT_MAX_VIEWS, a NULL views, params or views[k].img are APS_E_ARG.  Count-only mode, padding, layouts and host / device
+ * pointers behave view by view as aps_sift_extract_batch's.  One sort, one flag pass, one ballot and scan and one compaction select
+ * for all the views, with no read-back beyond aps_sift_extract_batch's; only kept rows are described. */
+int aps_sift_extract_batch_strongest(aps_sift_view* views, int n_views, int height, int width, int channels,
+                                     int img_layout, const aps_sift_strongest_params* params,
+                                     int desc_layout, int64_t ldd, int64_t ldl);
+
 /* ============================================================================================
  * (4b) SURF — PP/featureMatching/getFeaturePoints.m:54-55,71-74
  * ============================================================================================ */
@@ -966,6 +979,16 @@ int aps_surf_extract_uniform(const uint8_t* img, int height, int width, int chan
 int aps_fast_extract_uniform(const uint8_t* img, int height, int width, int channels, int img_layout,
                              const aps_fast_uniform_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
                              double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* aps_sift_extract_uniform for a group of views of one shape, as aps_sift_extract_batch_strongest is for aps_sift_extract_strongest:
+ * the rows of view k (descriptor, location, aux, order and count) are bit for bit those of aps_sift_extract_uniform on views[k].img
+ * with the same params, whatever the other views contain; the budget of view k is min(candidates_k, N), spread over the cells of its
+ * own grid.  Arguments, capacities, APS_E_CAP and the checks are aps_sift_extract_batch_strongest's, with a grid value outside 1..32
+ * refused (APS_E_ARG) before any device work.  The selection of the whole group is one sort and one pass of each of its kernels, with
+ * no read-back beyond aps_sift_extract_batch's. */
+int aps_sift_extract_batch_uniform(aps_sift_view* views, int n_views, int height, int width, int channels,
+                                   int img_layout, const aps_sift_uniform_params* params,
+                                   int desc_layout, int64_t ldd, int64_t ldl);
 
 /* The water-filling of that rule (host only, needs no device; the function the device kernel calls): keep[k] of n_cells cells (1..1024)
  * with counts[k] in 0..2^32-1 under min(budget, sum counts).  counts and keep: host int64[n_cells]. */
