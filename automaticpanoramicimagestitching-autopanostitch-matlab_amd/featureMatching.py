@@ -344,10 +344,9 @@ def matchFeaturesScratch(F1, F2, Method="Exhaustive", MatchThreshold=3.5, MaxRat
     return np.stack([i1[:k], i2[:k]], axis=1), met[:k].copy()
 
 
-def match_pairwise_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True, normalize=2,
-                       device_out=False):
-    """Batched all-pairs matcher: the CSR form of featureMatchingPairwise used by the resident pipeline.
-    Returns (pair_ptr int64[P+1], idx_i, idx_j, metric) with pairs in the reference's triu order."""
+def _desc_table(allDescriptors):
+    """The descriptor sets of a float CSR matcher as the library takes them: (ptrs, counts, lds, layout, rows per set, and the
+    prepared arrays, which the caller keeps alive for the length of the call).  Sets of mixed storage order are a ValueError."""
     n = len(allDescriptors)
     prepared = [_as_desc(_pad_rows(d)) for d in allDescriptors]
     layouts = {p[3] for p in prepared if p[1] > 0}
@@ -357,65 +356,14 @@ def match_pairwise_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True, no
     ptrs = (C.c_void_p * n)(*[ptr(p[0]) if p[1] > 0 else None for p in prepared])
     counts = (C.c_int64 * n)(*[p[1] for p in prepared])
     lds = (C.c_int64 * n)(*[max(p[2], DIM if layout == _capi.APS_ROWMAJOR else p[1]) for p in prepared])
-    npairs = n * (n - 1) // 2
-    pair_ptr = np.zeros(npairs + 1, np.int64)
-    o = _opts(MaxRatio, MatchThreshold, Unique, normalize)
+    return ptrs, counts, lds, layout, [p[1] for p in prepared], prepared
+
+
+def _match_lists_regrow(call, cap, device_out):
+    """The output lists of a float CSR matcher with automatic capacity: call(idx_a, idx_b, metric, cap, count) runs the library
+    entry on freshly allocated lists (resident with device_out, fenced against torch's stream) and returns its status; on
+    APS_E_CAP the count is the exact need and the call is repeated with it.  Returns the three lists cut to the count."""
     cnt = C.c_int64(0)
-    # resident outputs: room for every row of every pair (see match_pairs_csr); host outputs: a modest first capacity,
-    # APS_E_CAP reports the exact need
-    rows = sum(prepared[i][1] * (n - 1 - i) for i in range(n))  # pair (i, j), i < j, has image i's rows
-    cap = max(1, rows if device_out else sum(p[1] for p in prepared) // 4)
-    while True:
-        if device_out:
-            import torch
-
-            i_i = torch.empty(cap, dtype=torch.int32, device="cuda")
-            i_j = torch.empty(cap, dtype=torch.int32, device="cuda")
-            met = torch.empty(cap, dtype=torch.float32, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            i_i = np.zeros(cap, np.uint32)
-            i_j = np.zeros(cap, np.uint32)
-            met = np.zeros(cap, np.float32)
-        rc = lib.aps_match_pairwise(ptrs, counts, lds, n, DIM, layout, C.byref(o), ptr(pair_ptr),
-                                    ptr(i_i), ptr(i_j), ptr(met), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP:
-            cap = cnt.value
-            continue
-        check(rc)
-        break
-    k = cnt.value
-    return pair_ptr, i_i[:k], i_j[:k], met[:k]
-
-
-def match_pairs_csr(allDescriptors, pairs, MaxRatio, MatchThreshold, Unique=True, normalize=2, device_out=False):
-    """aps_match_pairs: the matcher on an explicit list of (a, b) image pairs (0-based) — the unit that is
-    sharded across GPUs.  Returns (pair_ptr int64[P+1], idx_a, idx_b, metric) as numpy arrays, or with
-    device_out=True the three match arrays as resident torch tensors (int32, int32, float32)."""
-    n = len(allDescriptors)
-    prepared = [_as_desc(_pad_rows(d)) for d in allDescriptors]
-    layouts = {p[3] for p in prepared if p[1] > 0}
-    if len(layouts) > 1:
-        raise ValueError("all descriptor matrices must share a storage order")
-    layout = layouts.pop() if layouts else _capi.APS_ROWMAJOR
-    ptrs = (C.c_void_p * n)(*[ptr(p[0]) if p[1] > 0 else None for p in prepared])
-    counts = (C.c_int64 * n)(*[p[1] for p in prepared])
-    lds = (C.c_int64 * n)(*[max(p[2], DIM if layout == _capi.APS_ROWMAJOR else p[1]) for p in prepared])
-    if isinstance(pairs, np.ndarray):  # [P, 2] (pair_order_array and slices of it)
-        pa = np.ascontiguousarray(pairs[:, 0], np.int32)
-        pb = np.ascontiguousarray(pairs[:, 1], np.int32)
-    else:
-        pa = np.ascontiguousarray([p[0] for p in pairs], np.int32)
-        pb = np.ascontiguousarray([p[1] for p in pairs], np.int32)
-    P = len(pairs)
-    pair_ptr = np.zeros(P + 1, np.int64)
-    o = _opts(MaxRatio, MatchThreshold, Unique, normalize)
-    cnt = C.c_int64(0)
-    rows = int(np.asarray([p[1] for p in prepared], np.int64)[pa].sum()) if P else 0
-    # resident outputs: room for every row (uninitialised device memory from torch's cache costs nothing, and a second
-    # pass over all pairs after APS_E_CAP costs the whole matcher again - well-overlapping small sets keep more than a
-    # sixteenth of their rows); host outputs: a sixteenth, grown on demand
-    cap = max(1, rows if device_out else rows // 16)
     while True:
         if device_out:
             import torch
@@ -428,15 +376,54 @@ def match_pairs_csr(allDescriptors, pairs, MaxRatio, MatchThreshold, Unique=True
             i_a = np.zeros(cap, np.uint32)
             i_b = np.zeros(cap, np.uint32)
             met = np.zeros(cap, np.float32)
-        rc = lib.aps_match_pairs(ptrs, counts, lds, n, DIM, layout, ptr(pa), ptr(pb), P, C.byref(o), ptr(pair_ptr),
-                                 ptr(i_a), ptr(i_b), ptr(met), cap, C.byref(cnt))
+        rc = call(ptr(i_a), ptr(i_b), ptr(met), cap, C.byref(cnt))
         if rc == _capi.APS_E_CAP:
             cap = cnt.value
             continue
         check(rc)
-        break
-    k = cnt.value
-    return pair_ptr, i_a[:k], i_b[:k], met[:k]
+        k = cnt.value
+        return i_a[:k], i_b[:k], met[:k]
+
+
+def match_pairwise_csr(allDescriptors, MaxRatio, MatchThreshold, Unique=True, normalize=2,
+                       device_out=False):
+    """Batched all-pairs matcher: the CSR form of featureMatchingPairwise used by the resident pipeline.
+    Returns (pair_ptr int64[P+1], idx_i, idx_j, metric) with pairs in the reference's triu order."""
+    n = len(allDescriptors)
+    ptrs, counts, lds, layout, ns, _keep = _desc_table(allDescriptors)
+    pair_ptr = np.zeros(n * (n - 1) // 2 + 1, np.int64)
+    o = _opts(MaxRatio, MatchThreshold, Unique, normalize)
+    # resident outputs: room for every row of every pair (see match_pairs_csr); host outputs: a modest first capacity,
+    # APS_E_CAP reports the exact need
+    rows = sum(ns[i] * (n - 1 - i) for i in range(n))  # pair (i, j), i < j, has image i's rows
+    cap = max(1, rows if device_out else sum(ns) // 4)
+    return (pair_ptr,) + _match_lists_regrow(
+        lambda *out: lib.aps_match_pairwise(ptrs, counts, lds, n, DIM, layout, C.byref(o), ptr(pair_ptr), *out), cap, device_out)
+
+
+def match_pairs_csr(allDescriptors, pairs, MaxRatio, MatchThreshold, Unique=True, normalize=2, device_out=False):
+    """aps_match_pairs: the matcher on an explicit list of (a, b) image pairs (0-based) — the unit that is
+    sharded across GPUs.  Returns (pair_ptr int64[P+1], idx_a, idx_b, metric) as numpy arrays, or with
+    device_out=True the three match arrays as resident torch tensors (int32, int32, float32)."""
+    n = len(allDescriptors)
+    ptrs, counts, lds, layout, ns, _keep = _desc_table(allDescriptors)
+    if isinstance(pairs, np.ndarray):  # [P, 2] (pair_order_array and slices of it)
+        pa = np.ascontiguousarray(pairs[:, 0], np.int32)
+        pb = np.ascontiguousarray(pairs[:, 1], np.int32)
+    else:
+        pa = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        pb = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+    P = len(pairs)
+    pair_ptr = np.zeros(P + 1, np.int64)
+    o = _opts(MaxRatio, MatchThreshold, Unique, normalize)
+    rows = int(np.asarray(ns, np.int64)[pa].sum()) if P else 0
+    # resident outputs: room for every row (uninitialised device memory from torch's cache costs nothing, and a second
+    # pass over all pairs after APS_E_CAP costs the whole matcher again - well-overlapping small sets keep more than a
+    # sixteenth of their rows); host outputs: a sixteenth, grown on demand
+    cap = max(1, rows if device_out else rows // 16)
+    return (pair_ptr,) + _match_lists_regrow(
+        lambda *out: lib.aps_match_pairs(ptrs, counts, lds, n, DIM, layout, ptr(pa), ptr(pb), P, C.byref(o), ptr(pair_ptr), *out),
+        cap, device_out)
 
 
 _PAIR_ORDER = {}
@@ -651,6 +638,111 @@ def _fence_fresh_blocks():
     torch.cuda.current_stream().synchronize()
 
 
+def _image_hwc(image):
+    """The image preamble of the extraction wrappers: (contiguous uint8 image, h, w, c) of an H x W [x C] numpy array or torch
+    tensor; channel counts other than 1 and 3 are a ValueError."""
+    if _capi.is_torch(image):
+        img = image.contiguous()
+        h, w = int(img.shape[0]), int(img.shape[1])
+        c = 1 if img.dim() == 2 else int(img.shape[2])
+    else:
+        img = np.ascontiguousarray(image, np.uint8)
+        h, w = img.shape[:2]
+        c = 1 if img.ndim == 2 else img.shape[2]
+    if c not in (1, 3):
+        raise ValueError("image must be gray or RGB")
+    return img, h, w, c
+
+
+def _pick_entry(input, uniform, cap, plain, strongest, uniform_struct, uniform_entry):
+    """(parameter struct, library entry, first capacity) of an extraction call, from the detector's own pieces.
+    plain: (params, entry) without a selection key; strongest: (builder of the strongest params taking N or None for
+    input.NumStrongest, entry); uniform: what _uniform_keys(input) returned (the caller asks first: its ValueError comes before
+    any library call), with the detector's uniform struct and entry; cap: the capacity without a selection key.
+    With a selection of N rows the capacity is min(cap, max(N, 1)): a resident result then holds N rows (a value below 1 is the
+    library's to refuse)."""
+    (prm, entry), n_keep = plain, None
+    if "NumStrongest" in input:
+        prm, entry = strongest[0](None), strongest[1]
+        n_keep = prm.n_strongest
+    if uniform:
+        prm, entry = _uniform_params(uniform_struct, strongest[0](uniform[0]), uniform), uniform_entry
+        n_keep = uniform[0]
+    return prm, entry, (cap if n_keep is None else min(cap, max(n_keep, 1)))
+
+
+def _extract_regrow(g, cap, call, retry, width, dtype, device_out, points_device, compact, want_aux):
+    """The driver of every extraction wrapper: allocate the outputs of g views -> fence -> call -> regrow on APS_E_CAP -> finish.
+    call(bufs, cap) runs the library entry on bufs = [(desc, loc, aux)] * g, each of capacity `cap` (desc: cap x width rows of
+    `dtype`, resident with device_out; loc: column-major cap x 2 float64, resident with device_out and points_device; aux: cap x 4
+    float32 on the host, or None) and returns (status, [count per view]).  On APS_E_CAP with retry(counts, cap) true, everything
+    is allocated again with the largest count as every view's capacity.
+    Returns [(rows, points, aux or None)] * g: rows is the first count rows of the capacity buffer (resident: a view, or a
+    right-sized clone with compact), points count x 2.
+    Streams: fresh resident buffers are fenced against torch's stream once per attempt (_fence_fresh_blocks); the library's stream
+    is drained before torch reads resident outputs (an entry whose outputs are all resident returns before its last kernel);
+    torch's stream is drained after the transposes and clones, whose consumers run on the library's again."""
+    dev_pts = device_out and points_device
+    if device_out:
+        import torch
+    while True:
+        bufs = []
+        for _ in range(g):
+            desc = (torch.empty((cap, width), dtype=getattr(torch, np.dtype(dtype).name), device="cuda") if device_out
+                    else np.zeros((cap, width), dtype))
+            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda") if dev_pts else np.zeros((2, cap), np.float64)
+            bufs.append((desc, loc, np.zeros((cap, 4), np.float32) if want_aux else None))
+        if device_out:
+            _fence_fresh_blocks()
+        rc, counts = call(bufs, cap)
+        if rc == _capi.APS_E_CAP and retry(counts, cap):
+            cap = max(counts)
+            continue
+        check(rc)
+        break
+    if device_out:
+        check(lib.aps_synchronize())  # (with every output resident the call returns without waiting for its last kernel)
+    out = []
+    for (desc, loc, aux), n in zip(bufs, counts):
+        pts = loc[:, :n].t().contiguous() if dev_pts else np.ascontiguousarray(loc[:, :n].T)
+        # Resident output: the first n rows of the capacity buffer, as a view.  (Until round 4 a right-sized clone was handed
+        # back so that the worst-case buffer - H*W/64 rows = 66 MB for a 4K view - could be freed: a 10 MB device copy per view
+        # on torch's stream plus a stream synchronisation, 23 us of a chip-filling copy kernel and the host wait, to save
+        # 64 x 56 MB = 3.6 GB of a 288 GB device for the length of one step.)
+        if device_out:
+            d = desc[:n].clone() if compact else desc[:n]
+        else:
+            d = np.ascontiguousarray(desc[:n])
+        out.append((d, pts, aux[:n].copy() if want_aux else None))
+    if device_out and (dev_pts or compact):
+        torch.cuda.current_stream().synchronize()  # the transposes / clones ran on torch's stream; consumers run on the library's
+    return out
+
+
+def _one_view_call(entry, prm, img, h, w, c, ld):
+    """call(bufs, cap) of _extract_regrow for the single-image entries (aps_sift_extract and its kin)."""
+    cnt = C.c_int64(0)
+
+    def call(bufs, cap):
+        desc, loc, aux = bufs[0]
+        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc), _capi.APS_ROWMAJOR, ld, ptr(loc), cap,
+                   ptr(aux), cap, C.byref(cnt))
+        return rc, [int(cnt.value)]
+
+    return call
+
+
+def _over_capacity(counts, cap):
+    """SIFT's retry predicate: some view found more than its buffers hold (maxFeatures is a candidate capacity there, not a row
+    limit)."""
+    return any(n > cap for n in counts)
+
+
+def _over_capacity_unless_limited(max_features):
+    """SURF's and FAST's retry predicate: the count exceeds the capacity and is not the count before a maxFeatures row limit."""
+    return lambda counts, cap: counts[0] > cap and not (0 < max_features < counts[0])
+
+
 def sift_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
     """aps_sift_extract with automatic capacity: returns (features, validPts[, aux]).
 
@@ -673,70 +765,13 @@ def sift_extract(input, image, device_out=False, want_aux=False, points_device=F
     cells of the input.UniformGrid = (rows, cols) grid (default (8, 8), each 1..32) on the image by water-filling, the largest
     contrast first within a cell (DESIGN.md "Uniform-N selection").  The kept rows are rows of the result without the key, bit for
     bit and in the same order; a resident result holds NumUniform rows.  Together with NumStrongest it is a ValueError."""
-    if _capi.is_torch(image):
-        img = image.contiguous()
-        h, w = int(img.shape[0]), int(img.shape[1])
-        c = 1 if img.dim() == 2 else int(img.shape[2])
-    else:
-        img = np.ascontiguousarray(image, np.uint8)
-        h, w = img.shape[:2]
-        c = 1 if img.ndim == 2 else img.shape[2]
-    if c not in (1, 3):
-        raise ValueError("image must be gray or RGB")
-    uniform = _uniform_keys(input)
-    prm, entry = _sift_params(input), lib.aps_sift_extract
-    cap = max(4096, (h * w) // 64)
-    if "NumStrongest" in input:
-        prm, entry = _sift_strongest_params(input), lib.aps_sift_extract_strongest
-        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
-    if uniform:
-        prm = _uniform_params(_capi.aps_sift_uniform_params, _sift_strongest_params(input, uniform[0]), uniform)
-        entry, cap = lib.aps_sift_extract_uniform, min(cap, max(uniform[0], 1))
-    cnt = C.c_int64(0)
-    while True:
-        if device_out:
-            import torch
-
-            desc = torch.empty((cap, DIM), dtype=torch.float32, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            desc = np.zeros((cap, DIM), np.float32)
-        if device_out and points_device:
-            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
-        aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                   _capi.APS_ROWMAJOR, DIM, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP and cnt.value > cap:
-            cap = int(cnt.value)
-            continue
-        check(rc)
-        break
-    n = cnt.value
-    dev_pts = device_out and points_device
-    if dev_pts:
-        check(lib.aps_synchronize())  # (with every output resident the call returns without waiting for its last kernel)
-        pts = loc[:, :n].t().contiguous()
-        torch.cuda.current_stream().synchronize()  # the (small) transpose ran on torch's stream; consumers run on the library's
-    else:
-        pts = np.ascontiguousarray(loc[:, :n].T)
-    # Resident output: the first n rows of the capacity buffer, as a view.  (Until round 4 a right-sized clone was handed
-    # back so that the worst-case buffer - H*W/64 rows = 66 MB for a 4K view - could be freed: a 10 MB device copy per view
-    # on torch's stream plus a stream synchronisation, 23 us of a chip-filling copy kernel and the host wait, to save
-    # 64 x 56 MB = 3.6 GB of a 288 GB device for the length of one step.)
-    if device_out and compact:
-        check(lib.aps_synchronize())                # the extraction ran on the library's stream,
-        d = desc[:n].clone()                        # the copy runs on torch's,
-        torch.cuda.current_stream().synchronize()   # and the consumers on the library's again
-    elif device_out:
-        d = desc[:n]
-    else:
-        d = np.ascontiguousarray(desc[:n])
-    if want_aux:
-        return d, pts, aux[:n].copy()
-    return d, pts
+    img, h, w, c = _image_hwc(image)
+    prm, entry, cap = _pick_entry(input, _uniform_keys(input), max(4096, (h * w) // 64), (_sift_params(input), lib.aps_sift_extract),
+                                  (lambda n: _sift_strongest_params(input, n), lib.aps_sift_extract_strongest),
+                                  _capi.aps_sift_uniform_params, lib.aps_sift_extract_uniform)
+    d, pts, aux = _extract_regrow(1, cap, _one_view_call(entry, prm, img, h, w, c, DIM), _over_capacity, DIM, np.float32,
+                                  device_out, points_device, compact, want_aux)[0]
+    return (d, pts, aux) if want_aux else (d, pts)
 
 
 def sift_extract_batch(input, images, device_out=False, want_aux=False, points_device=False, compact=False):
@@ -751,64 +786,26 @@ def sift_extract_batch(input, images, device_out=False, want_aux=False, points_d
     library call; the values themselves are the library's to refuse (APS_E_ARG)."""
     uniform = _uniform_keys(input)
     g = len(images)
-    imgs = [im.contiguous() if _capi.is_torch(im) else np.ascontiguousarray(im, np.uint8) for im in images]
-    shape = tuple(imgs[0].shape) if g else ()
-    if any(tuple(im.shape) != shape for im in imgs):
+    prepared = [_image_hwc(im) for im in images]
+    imgs = [p[0] for p in prepared]
+    if any(tuple(im.shape) != tuple(imgs[0].shape) for im in imgs):
         raise ValueError("the images of a batch must have one shape")
-    h, w = (int(shape[0]), int(shape[1])) if g else (1, 1)
-    c = 1 if len(shape) == 2 else (int(shape[2]) if g else 3)
-    if c not in (1, 3):
-        raise ValueError("image must be gray or RGB")
-    prm, entry = _sift_params(input), lib.aps_sift_extract_batch
-    cap = max(4096, (h * w) // 64)
-    if "NumStrongest" in input:
-        prm, entry = _sift_strongest_params(input), lib.aps_sift_extract_batch_strongest
-        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
-    if uniform:
-        prm = _uniform_params(_capi.aps_sift_uniform_params, _sift_strongest_params(input, uniform[0]), uniform)
-        entry, cap = lib.aps_sift_extract_batch_uniform, min(cap, max(uniform[0], 1))
-    caps = [cap] * g
-    dev_pts = device_out and points_device
-    if device_out:
-        import torch
+    h, w, c = prepared[0][1:] if g else (1, 1, 3)
+    prm, entry, cap = _pick_entry(input, uniform, max(4096, (h * w) // 64), (_sift_params(input), lib.aps_sift_extract_batch),
+                                  (lambda n: _sift_strongest_params(input, n), lib.aps_sift_extract_batch_strongest),
+                                  _capi.aps_sift_uniform_params, lib.aps_sift_extract_batch_uniform)
     views = (_capi.aps_sift_view * max(g, 1))()
-    while True:
-        descs, locs, auxs = [], [], []
-        for k in range(g):
-            cap = caps[k]
-            descs.append(torch.empty((cap, DIM), dtype=torch.float32, device="cuda") if device_out else np.zeros((cap, DIM), np.float32))
-            locs.append(torch.empty((2, cap), dtype=torch.float64, device="cuda") if dev_pts else np.zeros((2, cap), np.float64))
-            auxs.append(np.zeros((cap, 4), np.float32) if want_aux else None)
-            views[k].img, views[k].desc, views[k].loc, views[k].aux = ptr(imgs[k]), ptr(descs[k]), ptr(locs[k]), ptr(auxs[k])
+
+    def call(bufs, cap):
+        for k, (desc, loc, aux) in enumerate(bufs):
+            views[k].img, views[k].desc, views[k].loc, views[k].aux = ptr(imgs[k]), ptr(desc), ptr(loc), ptr(aux)
             views[k].cap, views[k].count = cap, 0
-        if device_out:
-            _fence_fresh_blocks()
         # (the views share one capacity, which is the leading dimension of their column-major locations)
-        rc = entry(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, caps[0] if g else 0)
-        if rc == _capi.APS_E_CAP and any(views[k].count > caps[k] for k in range(g)):
-            caps = [max(int(views[k].count) for k in range(g))] * g
-            continue
-        check(rc)
-        break
-    if device_out:
-        check(lib.aps_synchronize())  # (with every output resident the call returns without waiting for its last kernel)
-    out = []
-    for k in range(g):
-        n = int(views[k].count)
-        if dev_pts:
-            pts = locs[k][:, :n].t().contiguous()
-        else:
-            pts = np.ascontiguousarray(locs[k][:, :n].T)
-        if device_out and compact:
-            d = descs[k][:n].clone()
-        elif device_out:
-            d = descs[k][:n]
-        else:
-            d = np.ascontiguousarray(descs[k][:n])
-        out.append((d, pts, auxs[k][:n].copy()) if want_aux else (d, pts))
-    if device_out and (dev_pts or compact):
-        torch.cuda.current_stream().synchronize()  # the transposes / clones ran on torch's stream; consumers run on the library's
-    return out
+        rc = entry(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, cap if g else 0)
+        return rc, [int(views[k].count) for k in range(g)]
+
+    out = _extract_regrow(g, cap, call, _over_capacity, DIM, np.float32, device_out, points_device, compact, want_aux)
+    return [r if want_aux else r[:2] for r in out]
 
 
 SURF_DIM = 64
@@ -847,65 +844,17 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps min(N, rows) rows through
     aps_surf_extract_uniform, spread over the grid's cells by water-filling, the largest metric first within a cell; a row's cell is
     that of its detection sample, before refinement (DESIGN.md "Uniform-N selection")."""
-    if _capi.is_torch(image):
-        img = image.contiguous()
-        h, w = int(img.shape[0]), int(img.shape[1])
-        c = 1 if img.dim() == 2 else int(img.shape[2])
-    else:
-        img = np.ascontiguousarray(image, np.uint8)
-        h, w = img.shape[:2]
-        c = 1 if img.ndim == 2 else img.shape[2]
-    if c not in (1, 3):
-        raise ValueError("image must be gray or RGB")
-    uniform = _uniform_keys(input)
-    prm, entry, max_features = _surf_params(input), lib.aps_surf_extract, int(input.get("maxFeatures", 0))
-    cap = max(4096, (h * w) // 64)
-    if "NumStrongest" in input:
-        prm, entry = _surf_strongest_params(input), lib.aps_surf_extract_strongest
-        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
-    if uniform:
-        prm = _uniform_params(_capi.aps_surf_uniform_params, _surf_strongest_params(input, uniform[0]), uniform)
-        entry, cap = lib.aps_surf_extract_uniform, min(cap, max(uniform[0], 1))
-    cnt = C.c_int64(0)
-    ld = DIM if device_out else SURF_DIM
-    while True:
-        if device_out:
-            import torch
-
-            desc = torch.empty((cap, DIM), dtype=torch.float32, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            desc = np.zeros((cap, SURF_DIM), np.float32)
-        if device_out and points_device:
-            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
-        aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                   _capi.APS_ROWMAJOR, ld, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < max_features < cnt.value):
-            cap = int(cnt.value)
-            continue
-        check(rc)
-        break
-    n = cnt.value
-    if device_out and points_device:
-        pts = loc[:, :n].t().contiguous()
-        torch.cuda.current_stream().synchronize()  # the (small) transpose ran on torch's stream; consumers run on the library's
-    else:
-        pts = np.ascontiguousarray(loc[:, :n].T)
-    if device_out and compact:
-        d = desc[:n].clone()                        # (the call returned after its last kernel: it reads the count back)
-        torch.cuda.current_stream().synchronize()
-        d = d if padded else d[:, :SURF_DIM]
-    elif device_out:
-        d = desc[:n] if padded else desc[:n, :SURF_DIM]
-    else:
-        d = np.ascontiguousarray(desc[:n])
-    if want_aux:
-        return d, pts, aux[:n].copy()
-    return d, pts
+    img, h, w, c = _image_hwc(image)
+    prm, entry, cap = _pick_entry(input, _uniform_keys(input), max(4096, (h * w) // 64), (_surf_params(input), lib.aps_surf_extract),
+                                  (lambda n: _surf_strongest_params(input, n), lib.aps_surf_extract_strongest),
+                                  _capi.aps_surf_uniform_params, lib.aps_surf_extract_uniform)
+    width = DIM if device_out else SURF_DIM  # (resident rows are 128 wide, host rows 64; the leading dimension follows)
+    d, pts, aux = _extract_regrow(1, cap, _one_view_call(entry, prm, img, h, w, c, width),
+                                  _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), width, np.float32,
+                                  device_out, points_device, compact, want_aux)[0]
+    if device_out and not padded:
+        d = d[:, :SURF_DIM]
+    return (d, pts, aux) if want_aux else (d, pts)
 
 
 FREAK_BYTES = 64
@@ -953,73 +902,24 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps the same number of rows per level as
     NumStrongest = N does, through aps_fast_extract_uniform, but spreads each level's rows over the cells of the grid on the level's
     plane by water-filling, the largest Harris response first within a cell (DESIGN.md "Uniform-N selection"); aux as above."""
-    if _capi.is_torch(image):
-        img = image.contiguous()
-        h, w = int(img.shape[0]), int(img.shape[1])
-        c = 1 if img.dim() == 2 else int(img.shape[2])
-    else:
-        img = np.ascontiguousarray(image, np.uint8)
-        h, w = img.shape[:2]
-        c = 1 if img.ndim == 2 else img.shape[2]
-    if c not in (1, 3):
-        raise ValueError("image must be gray or RGB")
+    img, h, w, c = _image_hwc(image)
     n_levels = int(input.get("NumLevels", 1))
     uniform = _uniform_keys(input)
-    strongest = "NumStrongest" in input
-    if n_levels == 1 and not strongest and not uniform:
-        prm, entry, pixels = _fast_params(input), lib.aps_fast_extract, h * w
+    if n_levels == 1 and "NumStrongest" not in input and not uniform:
+        plain, pixels = (_fast_params(input), lib.aps_fast_extract), h * w
     else:
-        prm, entry = _fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid
+        plain = (_fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid)
         hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
-        check(lib.aps_fast_pyramid_plan(h, w, prm.n_levels, prm.scale_num, prm.scale_den, hs, ws, C.byref(used)))
+        check(lib.aps_fast_pyramid_plan(h, w, plain[0].n_levels, plain[0].scale_num, plain[0].scale_den, hs, ws, C.byref(used)))
         pixels = sum(hs[l] * ws[l] for l in range(used.value))
-    max_features = int(input.get("maxFeatures", 0))
-    cap = max(4096, pixels // 64)
-    if strongest:
-        prm, entry = _fast_strongest_params(input, n_levels), lib.aps_fast_extract_strongest
-        cap = min(cap, max(prm.n_strongest, 1))   # (a value below 1 is the library's to refuse)
-    if uniform:
-        prm = _uniform_params(_capi.aps_fast_uniform_params, _fast_strongest_params(input, n_levels, uniform[0]), uniform)
-        entry, cap = lib.aps_fast_extract_uniform, min(cap, max(uniform[0], 1))
-    cnt = C.c_int64(0)
-    while True:
-        if device_out:
-            import torch
-
-            desc = torch.empty((cap, FREAK_BYTES), dtype=torch.uint8, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            desc = np.zeros((cap, FREAK_BYTES), np.uint8)
-        if device_out and points_device:
-            loc = torch.empty((2, cap), dtype=torch.float64, device="cuda")
-            _fence_fresh_blocks()
-        else:
-            loc = np.zeros((2, cap), np.float64)  # column-major cap x 2
-        aux = np.zeros((cap, 4), np.float32) if want_aux else None
-        rc = entry(ptr(img), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), ptr(desc),
-                   _capi.APS_ROWMAJOR, FREAK_BYTES, ptr(loc), cap, ptr(aux), cap, C.byref(cnt))
-        if rc == _capi.APS_E_CAP and cnt.value > cap and not (0 < max_features < cnt.value):
-            cap = int(cnt.value)
-            continue
-        check(rc)
-        break
-    n = cnt.value
-    if device_out and points_device:
-        pts = loc[:, :n].t().contiguous()
-        torch.cuda.current_stream().synchronize()  # the (small) transpose ran on torch's stream; consumers run on the library's
-    else:
-        pts = np.ascontiguousarray(loc[:, :n].T)
-    if device_out and compact:
-        d = desc[:n].clone()                        # (the call returned after its last kernel: it reads the count back)
-        torch.cuda.current_stream().synchronize()
-    elif device_out:
-        d = desc[:n]
-    else:
-        d = np.ascontiguousarray(desc[:n])
+    prm, entry, cap = _pick_entry(input, uniform, max(4096, pixels // 64), plain,
+                                  (lambda n: _fast_strongest_params(input, n_levels, n), lib.aps_fast_extract_strongest),
+                                  _capi.aps_fast_uniform_params, lib.aps_fast_extract_uniform)
+    d, pts, aux = _extract_regrow(1, cap, _one_view_call(entry, prm, img, h, w, c, FREAK_BYTES),
+                                  _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), FREAK_BYTES, np.uint8,
+                                  device_out, points_device, compact, want_aux)[0]
     f = binaryFeatures(d)
-    if want_aux:
-        return f, pts, aux[:n].copy()
-    return f, pts
+    return (f, pts, aux) if want_aux else (f, pts)
 
 
 def extract_features(input, image, **kw):

@@ -241,23 +241,54 @@ def ransac_batch_drawn(pts_src, pts_dst, pair_ptr, counts, input, seed=0, keys=N
         n_samples = min(4 * n_samples, limit)
 
 
-def candidate_pairs(matchesAll, n, m):
-    """Top-m candidate selection of imageMatching.m:76-100 (Brown-Lowe m = 6): union over images of the m
-    partners with the most putative matches (stable descending sort), upper triangle, column-major order."""
-    put = np.zeros((n, n), np.int64)
-    for i in range(n):
-        for j in range(n):
-            c = matchesAll[i][j]
-            put[i, j] = 0 if c is None else len(c)
-    sym = put + put.T
-    np.fill_diagonal(sym, 0)
-    order = np.argsort(-sym, axis=1, kind="stable")  # MATLAB sort(...,'descend') is stable
-    top = order[:, : min(m, n - 1)]
+_PAIR_INDEX = {}
+
+
+def pair_index_arrays(n):
+    """(i, j) of every pair of fm.pair_order(n) as two index arrays (pair (i, j), i < j, sits at j (j - 1) / 2 + i)."""
+    if n not in _PAIR_INDEX:
+        jj = np.repeat(np.arange(1, n), np.arange(1, n))
+        ii = np.concatenate([np.arange(j) for j in range(1, n)]) if n > 1 else np.zeros(0, np.int64)
+        _PAIR_INDEX[n] = (ii.astype(np.int64), jj.astype(np.int64))
+    return _PAIR_INDEX[n]
+
+
+def candidate_positions(n_match, n, m):
+    """The top-m candidate rule of imageMatching.m:76-100 (Brown-Lowe m = 6), stated once for the package.
+    n_match: putative match count per pair in fm.pair_order(n) order (pair (i, j), i < j, at j (j - 1) / 2 + i).
+    Returns the positions, in that order, of ALL candidate pairs in the reference's column-major find order (int64 array);
+    the >= 4 filter of imageMatching.m:133 is the caller's.
+      :76-86  symCounts(i, j) = symCounts(j, i) = the pair's count, zero diagonal (the counts come per pair, i < j, so
+              the diagonal is zero by construction)
+      :88-90  [~, idx] = sort(symCounts, 2, 'descend'): MATLAB's sort is stable, ties keep ascending column order -
+              argsort of the negated counts, kind="stable"
+      :91-95  the first min(m, n - 1) columns of every row are that image's candidates (an image whose row is all zeros
+              takes the lowest indices, itself included)
+      :96-98  cand = cand | cand': a pair is a candidate when either image names the other
+      :99     triu(cand, 1): i < j only, which drops the diagonal
+      :100    find walks column-major: j outer, i inner - the order of pair_order itself, so the positions ascend"""
+    n, n_match = int(n), np.asarray(n_match, np.int64)
+    oi, oj = pair_index_arrays(n)
+    sym = np.zeros((n, n), np.int64)
+    sym[oi, oj] = n_match
+    sym[oj, oi] = n_match
+    top = np.argsort(-sym, axis=1, kind="stable")[:, : min(int(m), n - 1)]
     cand = np.zeros((n, n), bool)
     cand[np.repeat(np.arange(n), top.shape[1]), top.reshape(-1)] = True
     cand = np.triu(cand | cand.T, 1)
-    jj, ii = np.nonzero(cand.T)  # find() walks column-major
-    return list(zip(ii.tolist(), jj.tolist()))
+    cj, ci = np.nonzero(cand.T)  # find() walks column-major
+    return cj * (cj - 1) // 2 + ci
+
+
+def candidate_pairs(matchesAll, n, m):
+    """Top-m candidate selection of imageMatching.m:76-100 (Brown-Lowe m = 6): union over images of the m
+    partners with the most putative matches (stable descending sort), upper triangle, column-major order."""
+    oi, oj = pair_index_arrays(n)
+    cell = lambda i, j: 0 if matchesAll[i][j] is None else len(matchesAll[i][j])  # noqa: E731
+    # (symCounts sums both triangles of the cell array; the diagonal cells take no part)
+    n_match = [cell(i, j) + cell(j, i) for i, j in zip(oi.tolist(), oj.tolist())]
+    pos = candidate_positions(n_match, n, m)
+    return list(zip(oi[pos].tolist(), oj[pos].tolist()))
 
 
 def imageMatching(input, n, keypoints, matchesAll, imagesProcessed=None, seed=0):

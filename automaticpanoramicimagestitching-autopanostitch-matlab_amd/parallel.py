@@ -474,124 +474,194 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
     Returns dict(counts, kps_t, pairs, models, num_matches, n_match, order)."""
     from . import featureMatching as fm
     from . import imageMatching as im
-    from . import pipeline as pl
 
     ws, rank = world()
-    owner = lambda i: i % ws  # noqa: E731
-
     submit_features_rest(features)  # (a handle whose second part was never submitted)
     use_global = not int(input.get("matchFeaturesPairwise", 1))  # main.m:95-99
     host_lists = bool(os.environ.get("APS_PARALLEL_HOST_LISTS"))  # A/B switch: lists through the host (round-1 path)
     order = fm.pair_order(n)
-    mine_img = sorted(local_images)
-    ready = [image_events[i] for i in mine_img] if image_events is not None else None
-    # One rank, optional (APS_MATCH_OVERLAP_CHUNK=<images per chunk>, default off): feature extraction and matching overlap.
-    # The pair order is j-major (featureMatchingPairwise.m:48), so the pairs whose later image lies in a chunk of images form
-    # one contiguous run of it: as soon as a chunk is extracted, that run is matched on this thread's stream while the
-    # worker streams go on with the next images.  The match lists are the same, only earlier.  Measured on the 64 x 4K
-    # scene it buys nothing (236.5 ms against 236.8; chunks of 8: 263): the screening kernel has to keep its SIMDs to
-    # itself (see match_screen_i8_kernel), so the overlap is time slicing at CU granularity, paid for with repeated
-    # descriptor preparation.  Kept as a switch for scenes with fewer, larger images.
+    ready = [image_events[i] for i in sorted(local_images)] if image_events is not None else None
     chunk = int(os.environ.get("APS_MATCH_OVERLAP_CHUNK", "0"))
-    if not _multi(ws) and not use_global and not host_lists and chunk > 0 and n > chunk and len(mine_img) == n:
-        t0 = time.perf_counter()
-        futs = pl.sift_submit(input, [local_images[i] for i in range(n)], ready=ready)
-        descs, kps_t, pps, ias, ibs = [], [], [np.zeros(1, np.int64)], [], []
-        t_match = 0.0
-        for lo in range(0, n, chunk):
-            hi = min(n, lo + chunk)
-            for i in range(lo, hi):
-                d, p = futs[i].result()
-                descs.append(d)
-                kps_t.append(torch.from_numpy(p).to(dev))
-            if hi == n:
-                times.add("features", t0)  # wall time until the last image is extracted (part of the matching ran under it)
-                t0 = time.perf_counter()
-            p0, p1 = lo * (lo - 1) // 2 if lo else 0, hi * (hi - 1) // 2
-            if p1 > p0:
-                pp_k, ia_k, ib_k, _ = fm.match_pairs_csr(descs, order[p0:p1], input["Ratiothreshold"], input["Matchingthreshold"],
-                                                         True, device_out=True)
-                pps.append(pp_k[1:] + pps[-1][-1])
-                ias.append(ia_k)
-                ibs.append(ib_k)
-        counts = [int(d.shape[0]) for d in descs]
-        pp = np.concatenate(pps).astype(np.int64)
-        ia_d, ib_d = torch.cat(ias), torch.cat(ibs)
-        my = list(range(len(order)))
-        pown = np.zeros(len(order), np.int64)
-        times.add("exchange", time.perf_counter())
+    if not _multi(ws) and not use_global and not host_lists and chunk > 0 and n > chunk and len(local_images) == n:
+        kps_t, counts, n_match, ia_d, ib_d, gpos = _features_matched_in_chunks(input, local_images, n, chunk, ready, times, dev)
     else:
-        # 1) SIFT on the local shard; 2) the exchange of descriptors and keypoints.  With more than one rank the exchange
-        # runs in chunks BESIDE the extraction (FeatureExchange): a chunk is all-gathered while the worker streams
-        # extract the next one, so only the last chunk's collective is left on the critical path.
-        t0 = time.perf_counter()
-        if _multi(ws):
-            if features is not None:
-                assert features["images"] == mine_img, "submit_features() was called for other images"
-                futs = dict(zip(mine_img, features["futures"]))
-            else:
-                futs = dict(zip(mine_img, pl.sift_submit(input, [local_images[i] for i in mine_img], ready=ready))) if mine_img else {}
-            ex = FeatureExchange(futs, n, dev).run()
-            times.add("features", t0)  # (the last local image is extracted; all but the last chunk have been sent)
-            t0 = time.perf_counter()
-            descs, kps_t = ex.wait()
-            if before_match is not None:
-                before_match()  # e.g. the early image all-gather: no collective may run beside the matching kernels
-            if dev.type == "cuda":
-                torch.cuda.synchronize()  # gathered blocks are produced on RCCL's / torch's streams, consumed on the library's
-        else:
-            ldesc, lkps = {}, {}
-            if mine_img:
-                # resident images: the keypoints never leave the device (the host copy and the 64 small uploads after the last
-                # image were 2 ms of every step); host images: uploaded as soon as their image is done
-                resident = dev.type == "cuda" and all(_is_cuda_tensor(local_images[i]) for i in mine_img)
-                if features is not None:
-                    assert features["images"] == mine_img and features["resident"] == resident, "submit_features() was called for other images"
-                    futs = features["futures"]
-                else:
-                    futs = pl.sift_submit(input, [local_images[i] for i in mine_img], ready=ready, points_device=resident)
-                for i, f in zip(mine_img, futs):
-                    d, p = f.result()
-                    ldesc[i] = d
-                    lkps[i] = p if resident else torch.from_numpy(p).to(dev)
-            times.add("features", t0)
-            t0 = time.perf_counter()
-            descs = [ldesc[i] for i in range(n)]
-            kps_t = [lkps[i] for i in range(n)]
-        counts = [int(d.shape[0]) for d in descs]
-        times.add("exchange", t0)
+        # 1) SIFT on the local shard; 2) the exchange of descriptors and keypoints
+        descs, kps_t, counts = _features_exchanged(input, local_images, n, ready, features, before_match, times, dev)
         if after_features is not None:
             after_features()  # caller's hook: the worker streams are idle from here until the next extraction
-
         # 3) match: pair list partitioned by N_i * N_j; the index lists stay on the device
+        n_match, ia_d, ib_d, gpos = _match_lists(input, descs, counts, n, use_global, host_lists, times, dev)
+    if after_matching is not None:
+        after_matching()  # caller's hook: no int8 kernel runs from here on (e.g. submit_features() for the next set)
+
+    # 4) candidate selection (redundant, deterministic; im.candidate_positions) + RANSAC sharded round-robin
+    t0 = time.perf_counter()
+    pw = im.candidate_positions(n_match, n, int(input["mBrownLowe"]))
+    work = pw[n_match[pw] >= 4].tolist()  # imageMatching.m:133
+    rows = list(range(rank, len(work), ws))  # work item k is verified by rank k % ws
+    times.add("im_select", t0)
+    t0 = time.perf_counter()
+    # model (9), found, inliers per candidate pair: a device tensor only when it has to be all-reduced
+    rec = (torch.zeros((max(len(work), 1), 11), dtype=torch.float64, device=dev) if _multi(ws)
+           else np.zeros((max(len(work), 1), 11), np.float64))
+    my_inl = torch.zeros((0, 2), dtype=torch.int32, device=dev) if want_inliers else None
+    if rows:
+        batch = _ransac_own_pairs(input, kps_t, ia_d, ib_d, gpos, n_match, order, work, rows, n, seed, want_inliers, times, t0)
+        if after_ransac is not None:
+            after_ransac()
         t0 = time.perf_counter()
-        if _multi(ws):
-            w = [float(counts[i]) * float(counts[j]) for (i, j) in order]
-            pown = partition_pairs_blocked(order, w, n, ws)
-            my = [p for p in range(len(order)) if pown[p] == rank]
-            my_pairs = [order[p] for p in my]
-        else:  # (one rank: every pair, handed over as the cached array - no per-step walk over 2016 tuples)
-            pown = np.zeros(len(order), np.int64)
-            my = slice(None)
-            my_pairs = fm.pair_order_array(n)
-        if use_global:
-            # featureMatchingGlobal (the reference's default, inputs.m:46): pooled exact k-NN + per-query filter.  Every rank
-            # holds all descriptors after the exchange and computes the (deterministic) result itself: no further exchange.
-            pp, ia_d, ib_d = fm.match_global_csr(descs, input["Ratiothreshold"], int(input.get("k", 4)), device_out=True)
-            my = slice(None)
+        my_inl = _record_own_pairs(rec, my_inl, batch, work, rows, gpos, ia_d, ib_d, dev)
+    elif after_ransac is not None:
+        after_ransac()  # (a rank without candidate pairs of its own)
+    pairs, models, num_matches, verified, vninl = _merge_verdicts(rec, work, n_match, order, n)
+    out = {"counts": counts, "kps_t": kps_t, "pairs": pairs, "models": models, "num_matches": num_matches,
+           "n_match": n_match, "order": order}
+    if want_inliers:
+        # the owner (k % ws) and the length (ninl) of every verified pair are known from `rec`: the offsets into the per-rank
+        # blocks follow without a second exchange (inlier_slices)
+        parts = [p_.cpu().numpy() for p_ in allgather_ragged(my_inl)]
+        out["inliers"] = split_inliers(parts, verified, vninl, ws)
+        out["keypoints"] = [k.cpu().numpy() for k in kps_t]
+    times.add("im_merge", t0)
+    return out
+
+
+def _features_matched_in_chunks(input, local_images, n, chunk, ready, times, dev):
+    """The overlap-chunk arm of _match_pass: stages 1 and 3 interleaved.
+    One rank, optional (APS_MATCH_OVERLAP_CHUNK=<images per chunk>, default off): feature extraction and matching overlap.
+    The pair order is j-major (featureMatchingPairwise.m:48), so the pairs whose later image lies in a chunk of images form
+    one contiguous run of it: as soon as a chunk is extracted, that run is matched on this thread's stream while the
+    worker streams go on with the next images.  The match lists are the same, only earlier.  Measured on the 64 x 4K
+    scene it buys nothing (236.5 ms against 236.8; chunks of 8: 263): the screening kernel has to keep its SIMDs to
+    itself (see match_screen_i8_kernel), so the overlap is time slicing at CU granularity, paid for with repeated
+    descriptor preparation.  Kept as a switch for scenes with fewer, larger images.
+    Takes: all n images local, `ready` events per image.  Returns (kps_t, counts, n_match, ia_d, ib_d, gpos): what
+    _features_exchanged and _match_lists return together, without the descriptors.  Collectives: none.  Streams: the match lists
+    are written on the library's stream of this thread; kps_t are uploads on torch's.  Times: features, exchange, matching."""
+    from . import featureMatching as fm
+    from . import pipeline as pl
+
+    order = fm.pair_order(n)
+    t0 = time.perf_counter()
+    futs = pl.sift_submit(input, [local_images[i] for i in range(n)], ready=ready)
+    descs, kps_t, pps, ias, ibs = [], [], [np.zeros(1, np.int64)], [], []
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        for i in range(lo, hi):
+            d, p = futs[i].result()
+            descs.append(d)
+            kps_t.append(torch.from_numpy(p).to(dev))
+        if hi == n:
+            times.add("features", t0)  # wall time until the last image is extracted (part of the matching ran under it)
+            t0 = time.perf_counter()
+        p0, p1 = lo * (lo - 1) // 2 if lo else 0, hi * (hi - 1) // 2
+        if p1 > p0:
+            pp_k, ia_k, ib_k, _ = fm.match_pairs_csr(descs, order[p0:p1], input["Ratiothreshold"], input["Matchingthreshold"],
+                                                     True, device_out=True)
+            pps.append(pp_k[1:] + pps[-1][-1])
+            ias.append(ia_k)
+            ibs.append(ib_k)
+    pp = np.concatenate(pps).astype(np.int64)
+    ia_d, ib_d = torch.cat(ias), torch.cat(ibs)
+    times.add("exchange", time.perf_counter())
+    times.add("matching", t0)
+    return kps_t, [int(d.shape[0]) for d in descs], np.diff(pp), ia_d, ib_d, pp[:-1]
+
+
+def _features_exchanged(input, local_images, n, ready, features, before_match, times, dev):
+    """Stages 1 and 2 of _match_pass: SIFT on the local shard, then every rank holds every image's features.
+    Takes: this rank's images, the `ready` events in ascending image order (or None), the submit_features() handle (or None).
+    Returns (descs, kps_t, counts): per image the resident [k, 128] descriptors, the resident [k, 2] float64 keypoints and k.
+    Collectives (more than one rank): FeatureExchange's per round one count all-gather and two padded all-gathers; the
+    before_match hook fires here, after the last of them has been waited for.  One rank: none.
+    Streams: more than one rank - the device has been synchronised, every stream may read the outputs; one rank - the worker
+    streams have drained (the futures resolve after that), host keypoints are uploads on torch's stream.
+    Times: features (until the last local image is extracted), exchange (the rest)."""
+    from . import pipeline as pl
+
+    ws, _ = world()
+    mine_img = sorted(local_images)
+    t0 = time.perf_counter()
+    if _multi(ws):
+        # The exchange runs in chunks BESIDE the extraction (FeatureExchange): a chunk is all-gathered while the worker streams
+        # extract the next one, so only the last chunk's collective is left on the critical path.
+        if features is not None:
+            assert features["images"] == mine_img, "submit_features() was called for other images"
+            futs = dict(zip(mine_img, features["futures"]))
         else:
-            pp, ia_d, ib_d, _ = fm.match_pairs_csr(descs, my_pairs, input["Ratiothreshold"],
-                                                   input["Matchingthreshold"], True, device_out=not host_lists)
-    if host_lists and not use_global:
-        ia_d = torch.from_numpy(ia_d.astype(np.int32)).to(dev)
-        ib_d = torch.from_numpy(ib_d.astype(np.int32)).to(dev)
+            futs = dict(zip(mine_img, pl.sift_submit(input, [local_images[i] for i in mine_img], ready=ready))) if mine_img else {}
+        ex = FeatureExchange(futs, n, dev).run()
+        times.add("features", t0)  # (the last local image is extracted; all but the last chunk have been sent)
+        t0 = time.perf_counter()
+        descs, kps_t = ex.wait()
+        if before_match is not None:
+            before_match()  # e.g. the early image all-gather: no collective may run beside the matching kernels
+        if dev.type == "cuda":
+            torch.cuda.synchronize()  # gathered blocks are produced on RCCL's / torch's streams, consumed on the library's
+    else:
+        ldesc, lkps = {}, {}
+        if mine_img:
+            # resident images: the keypoints never leave the device (the host copy and the 64 small uploads after the last
+            # image were 2 ms of every step); host images: uploaded as soon as their image is done
+            resident = dev.type == "cuda" and all(_is_cuda_tensor(local_images[i]) for i in mine_img)
+            if features is not None:
+                assert features["images"] == mine_img and features["resident"] == resident, "submit_features() was called for other images"
+                futs = features["futures"]
+            else:
+                futs = pl.sift_submit(input, [local_images[i] for i in mine_img], ready=ready, points_device=resident)
+            for i, f in zip(mine_img, futs):
+                d, p = f.result()
+                ldesc[i] = d
+                lkps[i] = p if resident else torch.from_numpy(p).to(dev)
+        times.add("features", t0)
+        t0 = time.perf_counter()
+        descs = [ldesc[i] for i in range(n)]
+        kps_t = [lkps[i] for i in range(n)]
+    counts = [int(d.shape[0]) for d in descs]
+    times.add("exchange", t0)
+    return descs, kps_t, counts
+
+
+def _match_lists(input, descs, counts, n, use_global, host_lists, times, dev):
+    """Stage 3 of _match_pass: the putative matches of every image pair, as one pair of resident index lists on every rank.
+    Takes: all descriptors and counts (on every rank alike).  Returns (n_match, ia_d, ib_d, gpos): the match count of every pair
+    in fm.pair_order(n) order, the 1-based keypoint indices of all matches as two resident int32 lists, and where each pair's
+    run starts in them.
+    Collectives (more than one rank, pairwise matcher): one all-reduce of the counts, then allgather_ragged of the lists (a count
+    all-gather and one padded all-gather).  The global matcher and one rank: none.
+    Streams: the matcher writes on the library's stream; _sync_lib() drains it before the collective reads the lists on
+    torch's / RCCL's.  Times: matching."""
+    from . import featureMatching as fm
+
+    ws, rank = world()
+    order = fm.pair_order(n)
+    t0 = time.perf_counter()
+    if _multi(ws):
+        w = [float(counts[i]) * float(counts[j]) for (i, j) in order]
+        pown = partition_pairs_blocked(order, w, n, ws)
+        my = [p for p in range(len(order)) if pown[p] == rank]
+        my_pairs = [order[p] for p in my]
+    else:  # (one rank: every pair, handed over as the cached array - no per-step walk over 2016 tuples)
+        my = slice(None)
+        my_pairs = fm.pair_order_array(n)
+    if use_global:
+        # featureMatchingGlobal (the reference's default, inputs.m:46): pooled exact k-NN + per-query filter.  Every rank
+        # holds all descriptors after the exchange and computes the (deterministic) result itself: no further exchange.
+        pp, ia_d, ib_d = fm.match_global_csr(descs, input["Ratiothreshold"], int(input.get("k", 4)), device_out=True)
+        my = slice(None)
+    else:
+        pp, ia_d, ib_d, _ = fm.match_pairs_csr(descs, my_pairs, input["Ratiothreshold"],
+                                               input["Matchingthreshold"], True, device_out=not host_lists)
+        if host_lists:
+            ia_d = torch.from_numpy(ia_d.astype(np.int32)).to(dev)
+            ib_d = torch.from_numpy(ib_d.astype(np.int32)).to(dev)
     n_match = np.zeros(len(order), np.int64)
     n_match[my] = np.diff(pp)
     if _multi(ws) and not use_global:
         nm = torch.from_numpy(n_match).to(dev)
         _all_reduce(nm)
         n_match = nm.cpu().numpy()
-        _sync_lib()
+        _sync_lib()  # the lists were written on the library's stream; the collective below reads them on torch's / RCCL's
         parts = allgather_ragged(torch.stack([ia_d, ib_d], 1).contiguous())
         base = np.concatenate([[0], np.cumsum([int(p_.shape[0]) for p_ in parts])])
         allidx = torch.cat(parts)
@@ -605,112 +675,91 @@ def _match_pass(input, local_images, n, seed, times, dev, image_events=None, bef
     else:
         gpos = pp[:-1].astype(np.int64)
     times.add("matching", t0)
-    if after_matching is not None:
-        after_matching()  # caller's hook: no int8 kernel runs from here on (e.g. submit_features() for the next set)
+    return n_match, ia_d, ib_d, gpos
 
-    # 4) candidate selection (redundant, deterministic) + RANSAC sharded round-robin
+
+def _ransac_own_pairs(input, kps_t, ia_d, ib_d, gpos, n_match, order, work, rows, n, seed, want_inliers, times, t0):
+    """Stage 5 of _match_pass: this rank's RANSAC batch.
+    Takes: the resident keypoints and match lists, the candidate work list (positions in the pair order) and `rows`, the
+    entries of it this rank verifies (not empty); t0, the start of the im_gather window.
+    Returns (cnts, wptr, models, mask, found, ninl): the match count per own pair, their prefix sums, and ransac_batch_drawn's
+    host results.  Collectives: none.  Streams: everything runs on the library's stream and has been read back when the call
+    returns - the caller fires after_ransac directly after it.  Times: im_gather, im_ransac."""
+    from . import imageMatching as im
+
+    mine = [work[k] for k in rows]
+    cnts = [int(n_match[p]) for p in mine]
+    wptr = np.concatenate([[0], np.cumsum(cnts)]).astype(np.int64)
+    # imageMatching.m:121-135 (keypoints{i}(matches(:,1),:), keypoints{j}(matches(:,2),:)) as one library launch over
+    # the resident keypoint tables and match lists (a host fancy-index of ~1e6 rows costs tens of milliseconds)
+    dst, src = im.gather_match_points(kps_t, ia_d, ib_d, gpos[mine], wptr, [order[p][0] for p in mine],
+                                      [order[p][1] for p in mine])
+    times.add("im_gather", t0)
     t0 = time.perf_counter()
-    oi, oj = _pair_index_arrays(n)
-    put = np.zeros((n, n), np.int64)
-    put[oi, oj] = n_match
-    sym = put + put.T
-    srt = np.argsort(-sym, axis=1, kind="stable")[:, : min(int(input["mBrownLowe"]), n - 1)]
-    cand = np.zeros((n, n), bool)
-    cand[np.repeat(np.arange(n), srt.shape[1]), srt.reshape(-1)] = True
-    cand = np.triu(cand | cand.T, 1)
-    cj, ci = np.nonzero(cand.T)  # column-major walk of the candidate matrix, like the reference's find
-    pw = cj * (cj - 1) // 2 + ci  # position of pair (i, j), i < j, in the j-major pair order
-    work = pw[n_match[pw] >= 4].tolist()
-    mine = [p for k, p in enumerate(work) if k % ws == rank]
-    times.add("im_select", t0)
-    t0 = time.perf_counter()
-    # model (9), found, inliers per candidate pair: a device tensor only when it has to be all-reduced
-    rec = (torch.zeros((max(len(work), 1), 11), dtype=torch.float64, device=dev) if _multi(ws)
-           else np.zeros((max(len(work), 1), 11), np.float64))
-    my_inl = torch.zeros((0, 2), dtype=torch.int32, device=dev) if want_inliers else None
-    if mine:
-        cnts = [int(n_match[p]) for p in mine]
-        wptr = np.concatenate([[0], np.cumsum(cnts)]).astype(np.int64)
-        # imageMatching.m:121-135 (keypoints{i}(matches(:,1),:), keypoints{j}(matches(:,2),:)) as one library launch over
-        # the resident keypoint tables and match lists (a host fancy-index of ~1e6 rows costs tens of milliseconds)
-        dst, src = im.gather_match_points(kps_t, ia_d, ib_d, gpos[mine], wptr, [order[p][0] for p in mine],
-                                          [order[p][1] for p in mine])
-        times.add("im_gather", t0)
-        t0 = time.perf_counter()
-        # Draws are keyed so that they do not depend on the sharding: by the global pair index - or, when the cameras are to be
-        # estimated, by candidate_keys: the estimate starts from these models, and a set of images has to get the same
-        # cameras alone and beside other sets, and in a set of its own those of pipeline.stitch.
-        wk = {p: k for k, p in enumerate(work)}
-        keys = mine
-        if want_inliers:
-            ck = candidate_keys([order[p] for p in work], n)
-            keys = [ck[wk[p]] for p in mine]
-        models, mask, found, ninl = im.ransac_batch_drawn(src, dst, wptr, cnts, input, seed, keys=keys)
-        times.add("im_ransac", t0)
-        if after_ransac is not None:
-            after_ransac()
-            after_ransac = None
-        t0 = time.perf_counter()
-        vals = np.concatenate([models.reshape(len(mine), 9), found.reshape(-1, 1).astype(np.float64),
-                               ninl.reshape(-1, 1).astype(np.float64)], axis=1)
-        if _multi(ws):
-            rows = torch.tensor([wk[p] for p in mine], dtype=torch.int64, device=dev)
-            rec[rows] = torch.from_numpy(vals).to(dev)
-        else:
-            rec[[wk[p] for p in mine]] = vals
-        if want_inliers:
-            # rows of this rank's verified pairs in `mine` order: mask -> positions in the resident match lists, one device
-            # gather; the threshold is the one applied to the all-reduced verdicts below, so every rank agrees on who sends
-            pos = []
-            for q, p in enumerate(mine):
-                if found[q] and int(ninl[q]) > 8 + 0.3 * cnts[q]:
-                    sel = np.nonzero(mask[wptr[q]:wptr[q + 1]])[0]
-                    if sel.size != int(ninl[q]):
-                        raise RuntimeError("pair %d: %d mask entries for %d inliers" % (p, sel.size, int(ninl[q])))
-                    pos.append(int(gpos[p]) + sel)
-            if pos:
-                at = torch.from_numpy(np.concatenate(pos).astype(np.int64)).to(dev)
-                my_inl = torch.stack([ia_d[at], ib_d[at]], 1).to(torch.int32).contiguous()
-    if after_ransac is not None:
-        after_ransac()  # (a rank without candidate pairs of its own)
-    if _multi(ws):
+    # Draws are keyed so that they do not depend on the sharding: by the global pair index - or, when the cameras are to be
+    # estimated, by candidate_keys: the estimate starts from these models, and a set of images has to get the same
+    # cameras alone and beside other sets, and in a set of its own those of pipeline.stitch.
+    keys = mine
+    if want_inliers:
+        ck = candidate_keys([order[p] for p in work], n)
+        keys = [ck[k] for k in rows]
+    models, mask, found, ninl = im.ransac_batch_drawn(src, dst, wptr, cnts, input, seed, keys=keys)
+    times.add("im_ransac", t0)
+    return cnts, wptr, models, mask, found, ninl
+
+
+def _record_own_pairs(rec, my_inl, batch, work, rows, gpos, ia_d, ib_d, dev):
+    """Stage 6 of _match_pass: this rank's rows of the verdict table and, when my_inl is not None, its verified pairs' inliers.
+    Takes: `rec` (one row of model (9), found, inlier count per work item; a device tensor when it will be all-reduced),
+    `batch` as _ransac_own_pairs returns it.  Writes rec[rows]; returns my_inl: None, or the K x 2 int32 resident keypoint
+    indices of the inliers of this rank's verified pairs, in work order.  Collectives: none.  Streams: torch's (one upload and
+    one indexed write; one device gather of the match lists, which the RANSAC batch has long finished reading)."""
+    cnts, wptr, models, mask, found, ninl = batch
+    vals = np.concatenate([models.reshape(len(rows), 9), found.reshape(-1, 1).astype(np.float64),
+                           ninl.reshape(-1, 1).astype(np.float64)], axis=1)
+    if torch.is_tensor(rec):
+        rec[torch.tensor(rows, dtype=torch.int64, device=dev)] = torch.from_numpy(vals).to(dev)
+    else:
+        rec[rows] = vals
+    if my_inl is None:
+        return None
+    # rows of this rank's verified pairs in work order: mask -> positions in the resident match lists, one device
+    # gather; the threshold is the one applied to the all-reduced verdicts (_merge_verdicts), so every rank agrees on who sends
+    pos = []
+    for q, k in enumerate(rows):
+        if found[q] and int(ninl[q]) > 8 + 0.3 * cnts[q]:
+            sel = np.nonzero(mask[wptr[q]:wptr[q + 1]])[0]
+            if sel.size != int(ninl[q]):
+                raise RuntimeError("pair %d: %d mask entries for %d inliers" % (work[k], sel.size, int(ninl[q])))
+            pos.append(int(gpos[work[k]]) + sel)
+    if pos:
+        at = torch.from_numpy(np.concatenate(pos).astype(np.int64)).to(dev)
+        my_inl = torch.stack([ia_d[at], ib_d[at]], 1).to(torch.int32).contiguous()
+    return my_inl
+
+
+def _merge_verdicts(rec, work, n_match, order, n):
+    """Stage 7 of _match_pass: every rank's verdicts on every rank, and the verified pairs.
+    Takes: `rec` with this rank's rows written and zeros elsewhere.  Returns (pairs, models, num_matches, verified, vninl): the
+    pairs that pass imageMatching.m:150 in work order, their 3 x 3 models, the n x n inlier counts, and for split_inliers the
+    positions of those pairs in the work list with their inlier counts.
+    Collectives (more than one rank): one all-reduce of rec.  Streams: torch's; the result is on the host."""
+    if torch.is_tensor(rec):
         _all_reduce(rec)  # every row is written by exactly one rank, zero elsewhere
         rec = rec.cpu().numpy()
-    pairs, models_l, num_matches = [], [], np.zeros((n, n))
+    pairs, models, num_matches = [], [], np.zeros((n, n))
     verified, vninl = [], []
     if work:
-        wk_ = np.asarray(work, np.int64)
-        nf = n_match[wk_]
+        nf = n_match[np.asarray(work, np.int64)]
         ni = np.where(rec[: len(work), 9] != 0, rec[: len(work), 10].astype(np.int64), 0)
         for k in np.nonzero(ni > 8 + 0.3 * nf)[0].tolist():  # imageMatching.m:150
             i, j = order[work[k]]
             pairs.append((i, j))
-            models_l.append(rec[k, :9].reshape(3, 3).copy())
+            models.append(rec[k, :9].reshape(3, 3).copy())
             num_matches[i, j] = ni[k]
             verified.append(k)
             vninl.append(int(ni[k]))
-    out = {"counts": counts, "kps_t": kps_t, "pairs": pairs, "models": models_l, "num_matches": num_matches,
-           "n_match": n_match, "order": order}
-    if want_inliers:
-        # the owner (k % ws) and the length (ninl) of every verified pair are known from `rec`: the offsets into the per-rank
-        # blocks follow without a second exchange (inlier_slices)
-        parts = [p_.cpu().numpy() for p_ in allgather_ragged(my_inl)]
-        out["inliers"] = split_inliers(parts, verified, vninl, ws)
-        out["keypoints"] = [k.cpu().numpy() for k in kps_t]
-    times.add("im_merge", t0)
-    return out
-
-
-_PAIR_INDEX = {}
-
-
-def _pair_index_arrays(n):
-    """(i, j) of every pair of fm.pair_order(n) as two index arrays (pair (i, j), i < j, sits at j (j - 1) / 2 + i)."""
-    if n not in _PAIR_INDEX:
-        jj = np.repeat(np.arange(1, n), np.arange(1, n))
-        ii = np.concatenate([np.arange(j) for j in range(1, n)]) if n > 1 else np.zeros(0, np.int64)
-        _PAIR_INDEX[n] = (ii.astype(np.int64), jj.astype(np.int64))
-    return _PAIR_INDEX[n]
+    return pairs, models, num_matches, verified, vninl
 
 
 def _sync_lib():
@@ -985,7 +1034,6 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     Returns (panorama of the component that holds the best-connected image, uint8 H x W x 3 CUDA tensor; info dict
     with info["panoramas"]: one entry per connected component of at least two images, in component order)."""
     from . import pipeline as pl
-    from . import renderPanorama as rp
 
     if input.get("detector", "SIFT") == "FAST":
         # the descriptor all-gather and the sharded matchers are built for 128-wide float rows
@@ -1005,6 +1053,7 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     estimate = Ks is None and cameras is None  # no intrinsics: step 5 estimates the cameras and needs the RANSAC inliers
     cam_key = "bundle_adjustment" if estimate else "host_cameras"
 
+    # 1-4) features, exchange, matching, RANSAC
     res = _match_pass(input, local_images, n, seed, times, dev, image_events, before_match=img_gather.finish,
                       after_features=after_features, features=features, after_matching=after_matching, after_ransac=after_ransac,
                       want_inliers=estimate)
@@ -1019,33 +1068,11 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
         # component), features re-extracted, everything re-matched and re-verified; the component labels of the
         # FIRST pass are kept (the reference does not recompute them)
         t0 = time.perf_counter()
-        szs = torch.zeros((n, 2), dtype=torch.int64, device=dev)
-        for k, im_ in local_originals.items():
-            szs[k, 0], szs[k, 1] = int(im_.shape[0]), int(im_.shape[1])
-        if _multi(ws):
-            _all_reduce(szs)
-        first_hw = torch.zeros((n, 2), dtype=torch.int64, device=dev)
-        for k, im_ in local_images.items():
-            first_hw[k, 0], first_hw[k, 1] = int(im_.shape[0]), int(im_.shape[1])
-        local_images = pl.resize_per_component(input, local_originals, labels, szs.cpu().tolist())  # resident: no host hop
-        new_hw = torch.zeros((n, 2), dtype=torch.int64, device=dev)
-        for k, im_ in local_images.items():
-            new_hw[k, 0], new_hw[k, 1] = int(im_.shape[0]), int(im_.shape[1])
-        if _multi(ws):
-            both_hw = torch.cat([first_hw, new_hw], 1)
-            _all_reduce(both_hw)
-            first_hw, new_hw = both_hw[:, :2], both_hw[:, 2:]
-        if Ks is not None:  # the intrinsics follow the per-component resize (pipeline.rescale_K)
-            fh, nh = first_hw.cpu().tolist(), new_hw.cpu().tolist()
-            Ks = [pl.rescale_K(K, fh[k], nh[k]) for k, K in enumerate(Ks)]
-        img_gather.wait()
-        img_gather = ImageGather(local_images, n, dev)
+        local_images, Ks, img_gather = _second_pass_inputs(input, local_images, local_originals, labels, Ks, n, dev, img_gather)
         times.add("exchange", t0)
-        first_counts = res["counts"]
-        res = _match_pass(input, local_images, n, seed, times, dev, before_match=img_gather.finish, want_inliers=estimate)
-        res["second_pass"], res["counts_first_pass"] = True, first_counts
-    t0 = time.perf_counter()
-    ba_info = None
+        res = dict(_match_pass(input, local_images, n, seed, times, dev, before_match=img_gather.finish, want_inliers=estimate),
+                   second_pass=True, counts_first_pass=res["counts"])
+    t0, ba_info = time.perf_counter(), None
     if estimate:
         comps, ba_info = _estimate_components(input, n, res, labels, img_gather.sizes(), dev)
     else:
@@ -1061,9 +1088,73 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     t0 = time.perf_counter()
     opts = {"anglePower": 2, "blending": input["blending"], "pyrLevels": input["bands"], "pyrSigma": input["MBBsigma"],
             "canvasColor": input["canvasColor"], "tile": tile, "cropBorder": bool(input.get("cropBorder", True))}  # displayPanorama.m:101
+    geos, by_component, comp_owner = _render_plan(input, comps, images, opts)
+    panos = []
+    for ci, c in enumerate(comps):
+        sizes, geo = geos[ci]
+        views = [images[k] for k in c["members"]]
+        owner = int(comp_owner[ci]) if ci in comp_owner else None
+        if geo is None:
+            pano = _render_planar(input, c, views, sizes, opts, owner, pano_root, dev)
+        else:
+            gains = _component_gains(input, c, views, geo, times, dev) if input.get("gainCompensation") else None
+            if by_component:
+                pano = _render_ray_whole(input, c, views, sizes, opts, gains, geo, owner, pano_root, dev)
+            else:
+                pano = _render_ray_tiles(input, c, views, sizes, opts, gains, geo, pano_root)
+        panos.append(pano)
+    times.add("render", t0)
+    return _main_panorama(res, comps, panos, ncomp, labels, times, ba_info, n, dev)
+
+
+def _hw_table(images, n, dev):
+    """(n, 2) int64 device table of (rows, cols) of the images a rank holds (dict index -> image), zero rows for the others:
+    summed over the ranks it is the table of all n."""
+    t = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+    for k, im_ in images.items():
+        t[k, 0], t[k, 1] = int(im_.shape[0]), int(im_.shape[1])
+    return t
+
+
+def _second_pass_inputs(input, local_images, local_originals, labels, Ks, n, dev, img_gather):
+    """The inputs of the second match pass (imageMatchingPanoramaConComps.m:48-91): this rank's originals resized per component.
+    Takes: the first pass's local images and image all-gather, the local originals, the first pass's component labels.
+    Returns (local_images, Ks, img_gather): the resized local images (resident: no host hop), the intrinsics rescaled to them
+    (pipeline.rescale_K; None stays None) and the all-gather of the NEW images, started.
+    Collectives (more than one rank): one all-reduce of the originals' sizes, one of the first-pass and new sizes side by
+    side, then the first image all-gather is waited for and ImageGather's own (a shape all-reduce, the asynchronous all-gather).
+    Streams: torch's throughout."""
+    from . import pipeline as pl
+
+    ws, _ = world()
+    szs = _hw_table(local_originals, n, dev)
+    if _multi(ws):
+        _all_reduce(szs)
+    first_hw = _hw_table(local_images, n, dev)
+    local_images = pl.resize_per_component(input, local_originals, labels, szs.cpu().tolist())
+    new_hw = _hw_table(local_images, n, dev)
+    if _multi(ws):
+        both_hw = torch.cat([first_hw, new_hw], 1)
+        _all_reduce(both_hw)
+        first_hw, new_hw = both_hw[:, :2], both_hw[:, 2:]
+    if Ks is not None:  # the intrinsics follow the per-component resize (pipeline.rescale_K)
+        fh, nh = first_hw.cpu().tolist(), new_hw.cpu().tolist()
+        Ks = [pl.rescale_K(K, fh[k], nh[k]) for k, K in enumerate(Ks)]
+    img_gather.wait()
+    return local_images, Ks, ImageGather(local_images, n, dev)
+
+
+def _render_plan(input, comps, images, opts):
+    """Who renders what.  The geometry of every canvas (host, f64) decides the sharding: components to ranks when there are at
+    least as many ray-rendered ones as ranks, tiles of each canvas otherwise; a planar set has no ray-render geometry, goes
+    whole to one rank and takes no part in that decision.
+    Returns (geos, by_component, comp_owner): per component (sizes of its members, canvas geometry or None for a planar
+    set); whether ray-rendered components go whole to ranks; component index -> rank for every component rendered whole
+    (empty on one rank).  Collectives: none - every rank computes the same plan."""
+    from . import renderPanorama as rp
+
+    ws, _ = world()
     mode = input["panorama2DisplaynSave"]
-    # geometry of every canvas (host, f64) decides the sharding: components to ranks when there are enough of them
-    # (a planar set has no ray-render geometry: it goes whole to one rank below and takes no part in this decision)
     geos, ray = [], []
     for ci, c in enumerate(comps):
         sizes = [(int(images[k].shape[0]), int(images[k].shape[1]), 3) for k in c["members"]]
@@ -1082,64 +1173,91 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
         # the rank that estimated the set renders it; sets that came with `cameras` are dealt by the same rule
         dealt = component_owners([len(comps[ci]["members"]) for ci in flat], ws)
         comp_owner.update({ci: comps[ci].get("owner", int(dealt[q])) for q, ci in enumerate(flat)})
-    panos = []
-    for ci, c in enumerate(comps):
-        sizes, geo = geos[ci]
-        members = c["members"]
-        if geo is None:
-            # planar scan (renderPanorama.m:78-90): no canvas_geometry, no gainCompensationRKf; rp.renderPanorama routes to
-            # pureNonRotationalPanoramas, which runs gainCompensationH itself when the opts ask for it (:584-591)
-            popts = dict(opts, **{k: input[k] for k in ("gainCompensation", "sigmaN", "sigmag") if k in input})
-            pano = None
-            if not _multi(ws) or int(comp_owner[ci]) == rank:
-                pano, _ = rp.renderPanorama(input, [images[k] for k in members], sizes, c["cameras"], mode, c["ref"], popts,
-                                            device_out=True)
-                pl._sync()
-            if _multi(ws):
-                pano = _deliver_panorama(pano, int(comp_owner[ci]), pano_root, dev)
-            panos.append(pano)
-            continue
-        gains = None
-        if input.get("gainCompensation"):
-            # gainCompensationRKf between cameras and render (renderPanorama.m:303-330).  The device sums in an
-            # unspecified order, so rank 0's gains are broadcast: every tile must be rendered with the same numbers.
-            from . import gainCompensation as gc
+    return geos, by_component, comp_owner
 
-            tg = time.perf_counter()
-            gains = gc.gainCompensationRKf([images[k] for k in members], c["cameras"], mode, c["ref"], input, geo)
-            if _multi(ws):
-                gt_ = torch.from_numpy(np.ascontiguousarray(gains)).to(dev)
-                _broadcast(gt_, 0)
-                gains = gt_.cpu().numpy()
-            times.add("gain_compensation", tg)
-        if by_component:
-            pano = None
-            if int(comp_owner[ci]) == rank:
-                pano, _ = rp.renderPanorama(input, [images[k] for k in members], sizes, c["cameras"], mode, c["ref"], opts,
-                                            gains=gains, device_out=True, geo=geo)
-                pl._sync()
-            root = pano_root if pano_root is not None else None
-            pano = _deliver_panorama(pano, int(comp_owner[ci]), root, dev)
+
+def _component_gains(input, c, views, geo, times, dev):
+    """gainCompensationRKf between cameras and render (renderPanorama.m:303-330) for one ray-rendered component, on every rank.
+    The device sums in an unspecified order, so rank 0's gains are broadcast: every tile must be rendered with the same
+    numbers.  Returns the gains (host).  Collectives (more than one rank): one broadcast from rank 0.
+    Times: gain_compensation (inside render)."""
+    from . import gainCompensation as gc
+
+    tg = time.perf_counter()
+    gains = gc.gainCompensationRKf(views, c["cameras"], input["panorama2DisplaynSave"], c["ref"], input, geo)
+    if _multi(world()[0]):
+        gt_ = torch.from_numpy(np.ascontiguousarray(gains)).to(dev)
+        _broadcast(gt_, 0)
+        gains = gt_.cpu().numpy()
+    times.add("gain_compensation", tg)
+    return gains
+
+
+def _render_planar(input, c, views, sizes, opts, owner, pano_root, dev):
+    """A planar scan (renderPanorama.m:78-90), whole, on its owner (one rank: here): no canvas_geometry, no
+    gainCompensationRKf; rp.renderPanorama routes to pureNonRotationalPanoramas, which runs gainCompensationH itself when the
+    opts ask for it (:584-591).  Returns what _deliver_panorama returns (one rank: the panorama).
+    Collectives (more than one rank): _deliver_panorama's.  Streams: the library's stream is drained before the hand-over."""
+    from . import pipeline as pl
+    from . import renderPanorama as rp
+
+    ws, rank = world()
+    popts = dict(opts, **{k: input[k] for k in ("gainCompensation", "sigmaN", "sigmag") if k in input})
+    pano = None
+    if not _multi(ws) or owner == rank:
+        pano, _ = rp.renderPanorama(input, views, sizes, c["cameras"], input["panorama2DisplaynSave"], c["ref"], popts,
+                                    device_out=True)
+        pl._sync()
+    if _multi(ws):
+        pano = _deliver_panorama(pano, owner, pano_root, dev)
+    return pano
+
+
+def _render_ray_whole(input, c, views, sizes, opts, gains, geo, owner, pano_root, dev):
+    """Components first: a ray-rendered component, whole, on its owner (more than one rank only).  Returns what
+    _deliver_panorama returns.  Collectives: _deliver_panorama's.  Streams: the library's stream is drained before the hand-over."""
+    from . import pipeline as pl
+    from . import renderPanorama as rp
+
+    pano = None
+    if owner == world()[1]:
+        pano, _ = rp.renderPanorama(input, views, sizes, c["cameras"], input["panorama2DisplaynSave"], c["ref"], opts,
+                                    gains=gains, device_out=True, geo=geo)
+        pl._sync()
+    return _deliver_panorama(pano, owner, pano_root, dev)
+
+
+def _render_ray_tiles(input, c, views, sizes, opts, gains, geo, pano_root):
+    """Tiles second: every rank renders a contiguous, area-balanced run of one canvas's tile list (one rank: all of it).
+    Returns the panorama: complete on every rank (pano_root None), or on pano_root only.
+    Collectives (more than one rank): one MAX all-reduce of the canvas, or gather_tiles_to_root.
+    Streams: the library's stream is drained after the render; the device is synchronised before the collective reads the
+    canvas and after it, before the crop reads the combined one."""
+    from . import pipeline as pl
+    from . import renderPanorama as rp
+
+    ws, rank = world()
+    tranges = tile_ranges(int(geo["H"]), int(geo["W"]), rp.effective_tile(opts, geo), ws) if _multi(ws) else None
+    subset = ("range",) + tranges[rank] if tranges is not None else None
+    pano, _ = rp.renderPanorama(input, views, sizes, c["cameras"], input["panorama2DisplaynSave"], c["ref"], opts,
+                                gains=gains, device_out=True, tile_subset=subset, geo=geo,
+                                # (runs gathered to a root cover the canvas: nothing outside a rank's run is read)
+                                zero_rest=not (tranges is not None and pano_root is not None))
+    pl._sync()
+    if _multi(ws):
+        torch.cuda.synchronize()
+        if pano_root is None:
+            _all_reduce(pano, dist.ReduceOp.MAX)  # disjoint tiles, zero elsewhere
         else:
-            # tiles second: every rank a contiguous, area-balanced run of the tile list
-            tranges = tile_ranges(int(geo["H"]), int(geo["W"]), rp.effective_tile(opts, geo), ws) if _multi(ws) else None
-            subset = ("range",) + tranges[rank] if tranges is not None else None
-            pano, _ = rp.renderPanorama(input, [images[k] for k in members], sizes, c["cameras"], mode, c["ref"], opts,
-                                        gains=gains, device_out=True, tile_subset=subset, geo=geo,
-                                        # (runs gathered to a root cover the canvas: nothing outside a rank's run is read)
-                                        zero_rest=not (tranges is not None and pano_root is not None))
-            pl._sync()
-            if _multi(ws):
-                torch.cuda.synchronize()
-                if pano_root is None:
-                    _all_reduce(pano, dist.ReduceOp.MAX)  # disjoint tiles, zero elsewhere
-                else:
-                    pano = gather_tiles_to_root(pano, rp.effective_tile(opts, geo), pano_root, ranges=tranges)
-                torch.cuda.synchronize()
-                if opts["cropBorder"] and (pano_root is None or rank == pano_root):
-                    pano = rp.cropNonzeroBbox(pano, opts["canvasColor"])[0]  # the combined canvas (renderPanorama.m:430-432)
-        panos.append(pano)
-    times.add("render", t0)
+            pano = gather_tiles_to_root(pano, rp.effective_tile(opts, geo), pano_root, ranges=tranges)
+        torch.cuda.synchronize()
+        if opts["cropBorder"] and (pano_root is None or rank == pano_root):
+            pano = rp.cropNonzeroBbox(pano, opts["canvasColor"])[0]  # the combined canvas (renderPanorama.m:430-432)
+    return pano
+
+
+def _main_panorama(res, comps, panos, ncomp, labels, times, ba_info, n, dev):
+    """The panorama of the component that holds the best-connected image, and stitch_distributed's info dict."""
     main = 0
     if comps:
         deg = (res["num_matches"] + res["num_matches"].T).sum(1)

@@ -247,24 +247,12 @@ def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None):
     if times is not None:
         times.add("matching", t0)
     t0 = time.perf_counter()
-    # top-m candidate selection (imageMatching.m:76-100) straight from the CSR counts
+    # top-m candidate selection (imageMatching.m:76-100, im.candidate_positions) straight from the CSR counts
+    n_match = np.diff(pair_ptr).astype(np.int64)
     put = np.zeros((n, n), np.int64)
-    for p, (i, j) in enumerate(order):
-        put[i, j] = pair_ptr[p + 1] - pair_ptr[p]
-    sym = put + put.T
-    srt = np.argsort(-sym, axis=1, kind="stable")[:, : min(int(input["mBrownLowe"]), n - 1)]
-    cand = np.zeros((n, n), bool)
-    cand[np.repeat(np.arange(n), srt.shape[1]), srt.reshape(-1)] = True
-    cand = np.triu(cand | cand.T, 1)
-    pidx = {ij: p for p, ij in enumerate(order)}
-    work = []
-    cj, ci = np.nonzero(cand.T)
-    for (i, j) in zip(ci.tolist(), cj.tolist()):
-        p = pidx[(i, j)]
-        s, e = int(pair_ptr[p]), int(pair_ptr[p + 1])
-        if e - s < 4:
-            continue
-        work.append((i, j, s, e))
+    put[im.pair_index_arrays(n)] = n_match
+    pw = im.candidate_positions(n_match, n, int(input["mBrownLowe"]))
+    work = [order[p] + (int(pair_ptr[p]), int(pair_ptr[p + 1])) for p in pw[n_match[pw] >= 4].tolist()]  # imageMatching.m:133
     out = {"pairs": [], "models": [], "inliers": [], "numMatches": np.zeros((n, n)), "putative": put}
     if work:
         counts = [e - s for (_, _, s, e) in work]

@@ -76,16 +76,7 @@ lo, med, out_all = timed(lambda: fm.match_pairs_csr(descs, order, inp["Ratiothre
 print(f"matching of all {len(order)} pairs: min {lo:.2f} ms")
 pp, ia_d, ib_d, _ = out_all
 n_match = np.diff(pp)
-oi, oj = par._pair_index_arrays(n)
-put = np.zeros((n, n), np.int64)
-put[oi, oj] = n_match
-sym = put + put.T
-srt = np.argsort(-sym, axis=1, kind="stable")[:, : min(int(inp["mBrownLowe"]), n - 1)]
-cand = np.zeros((n, n), bool)
-cand[np.repeat(np.arange(n), srt.shape[1]), srt.reshape(-1)] = True
-cand = np.triu(cand | cand.T, 1)
-cj, ci = np.nonzero(cand.T)
-pw = cj * (cj - 1) // 2 + ci
+pw = im.candidate_positions(n_match, n, int(inp["mBrownLowe"]))
 work = pw[n_match[pw] >= 4].tolist()
 gpos = pp[:-1].astype(np.int64)
 

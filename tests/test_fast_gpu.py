@@ -190,3 +190,42 @@ def test_resident_output_equals_host_output(fm):
         assert np.array_equal(f.Features.cpu().numpy(), md) and np.array_equal(pts.cpu().numpy(), mloc)
     f, pts = fm.getFeaturePoints(inp, img)
     assert np.array_equal(f.Features, md) and np.array_equal(pts, mloc)
+
+
+_DENSE = []
+
+
+def dense_mirror():
+    """The mirror's result on sift_param_cases.dense_image() (300 x 400) at MinContrast 0.05, MinQuality 0: 4910 corners, more
+    than the wrapper's first capacity max(4096, h w / 64) = 4096.  Computed once, shared, read-only."""
+    if not _DENSE:
+        import sift_param_cases as sc
+
+        out = fmir.extract(sc.dense_image(), fc.tables(), MinContrast=0.05, MinQuality=0)
+        for a in out:
+            a.setflags(write=False)
+        _DENSE.append((sc.dense_image(),) + out)
+    return _DENSE[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["host", "device_out", "device_points_compact"])
+def test_wrapper_grows_its_capacity_and_retries(fm, mode):
+    """More corners than the first capacity: the first call reports APS_E_CAP with the count, the wrapper allocates that many
+    rows and calls again; rows, points and aux are the mirror's."""
+    img, md, mloc, maux = dense_mirror()
+    assert len(md) > 4096 == max(4096, img.shape[0] * img.shape[1] // 64)
+    inp = {"detector": "FAST", "MinContrast": 0.05, "MinQuality": 0}
+    if mode == "host":
+        f, pts, aux = fm.fast_extract(inp, img, want_aux=True)
+        d = f.Features
+    else:
+        more = dict(points_device=True, compact=True) if mode == "device_points_compact" else {}
+        f, pts, aux = fm.fast_extract(inp, img, device_out=True, want_aux=True, **more)
+        assert f.Features.is_cuda and (mode == "device_out" or pts.is_cuda)
+        if mode == "device_points_compact":
+            assert f.Features.numel() == f.Features.untyped_storage().nbytes(), "compact=True returns a right-sized buffer"
+            pts = pts.cpu().numpy()
+        d = f.Features.cpu().numpy()
+    assert isinstance(f, fm.binaryFeatures) and f.NumFeatures == len(md)
+    assert_equals_mirror(d, pts, aux, md, mloc, maux)

@@ -199,3 +199,25 @@ def test_argument_checks(gpu):
     assert capi.lib.aps_sift_extract_batch(None, 1, 35, 47, 3, capi.APS_IMG_U8_HWC, C.byref(p), capi.APS_ROWMAJOR, 128, 64) == capi.APS_E_ARG
     views = (capi.aps_sift_view * 1)()  # (a view without an image)
     assert capi.lib.aps_sift_extract_batch(views, 1, 35, 47, 3, capi.APS_IMG_U8_HWC, C.byref(p), capi.APS_ROWMAJOR, 128, 64) == capi.APS_E_ARG
+
+
+@pytest.mark.parametrize("resident", [False, True])
+def test_wrapper_grows_every_view_when_one_exceeds_its_capacity(fm, resident):
+    """Two 300 x 400 gray views, first capacity max(4096, h w / 64) = 4096 each: sift_param_cases.dense_image() has 6367 oracle
+    features, gray_image(300, 400) 2951.  One view over its capacity makes the wrapper allocate the largest count for every view
+    and call again; every view's result is sift_extract's of that view, bit for bit."""
+    import sift_param_cases as sc
+
+    imgs = [sc.dense_image(), sc.gray_image(300, 400)]
+    kw = dict(device_out=True, points_device=True, compact=True) if resident else {}
+    got = fm.sift_extract_batch(INPUT, imgs, want_aux=True, **kw)
+    want = [fm.sift_extract(INPUT, im, want_aux=True, **kw) for im in imgs]
+    if resident:
+        assert all(r[0].is_cuda and r[1].is_cuda for r in got)
+        assert all(r[0].numel() * 4 == r[0].untyped_storage().nbytes() for r in got), "compact=True returns right-sized buffers"
+        got = [(f.cpu().numpy(), p.cpu().numpy(), a) for f, p, a in got]
+        want = [(f.cpu().numpy(), p.cpu().numpy(), a) for f, p, a in want]
+    assert max(len(r[0]) for r in got) > 4096 == max(4096, 300 * 400 // 64), "no view exceeds the first capacity"
+    for k in range(2):
+        assert len(got[k][0]) >= 20
+        assert same(got[k], want[k]), f"view {k} differs from sift_extract"
