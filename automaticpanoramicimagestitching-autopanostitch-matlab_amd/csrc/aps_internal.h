@@ -202,19 +202,54 @@ inline void check_launch(const char* what) {
     if (e != hipSuccess) fail(APS_E_DEVICE, "launch of %s failed: %s", what, hipGetErrorString(e));
 }
 
+// elements a matrix of n rows x cols columns spans under a leading dimension (n > 0)
+inline size_t matrix_extent(int64_t n, int64_t ld, int64_t cols, int layout) {
+    return layout == APS_ROWMAJOR ? (size_t)(n - 1) * ld + cols : (size_t)(cols - 1) * ld + n;
+}
+
+// the largest j in [0, n) with off(j) <= key, for ascending off with off(0) <= key: the segment a row, a tile or a block lies in
+template <class Off, class Key>
+__device__ __forceinline__ int last_at_or_below_by(Off&& off, int n, Key key) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off(mid) <= key) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+template <class T, class Key>
+__device__ __forceinline__ int last_at_or_below(const T* __restrict__ off, int n, Key key) {
+    return last_at_or_below_by([off](int j) { return off[j]; }, n, key);
+}
+
+// The (row, column set) slot table of the global k-NN (match.hip): the rows of set i against set j own the slots
+// job_off[i n + j] + local row.  every_j: the pooled matcher's form - every j, the diagonal too, for the query sets
+// [a, b) (the other sets' entries are 0); otherwise the blocked form - different sets only, -1 on the diagonal.
+struct SlotTable {
+    std::vector<int64_t> job_off;
+    int64_t slots = 0;
+};
+SlotTable slot_table(const std::vector<int64_t>& off, int a, int b, bool every_j);
 // match.hip: the screening half of the blocked global k-NN (see the definition)
-int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& block_off,
-                            std::vector<int64_t>& job_off, uint32_t* t3_idx, float* t3_d, float* t3_b);
-// The pooled matcher's search with featureMatchingGlobal's filter in view (match.hip): rows the filter provably drops
-// at `ratio` are flagged in dismissed[] and not searched; for the others t3_* hold, per (row, image) slot, the certified
-// prefix of the three nearest rows of that image and the bound of its unlisted rows.
-int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& img_off, float ratio,
-                             std::vector<int64_t>& job_off, uint32_t* t3_idx, float* t3_d, float* t3_b, uint8_t* dismissed,
-                             int64_t* n_survivors, int img_a = 0, int img_b = -1,  // [img_a, img_b): the query images of this call
-                             struct GlobalPrep* keep = nullptr);  // the images' operand forms, built by the first pass and reused by the next
-// (a search in several passes over ranges of query images prepares the column sets once: global_prep_new / _free own them)
-struct GlobalPrep* global_prep_new();
-void global_prep_free(struct GlobalPrep* p);
+void screened_block_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& block_off, const SlotTable& table,
+                         uint32_t* t3_idx, float* t3_d, float* t3_b);
+// The images' prepared operand forms and their stats (match.hip): the first pass of a search builds them, the later ones
+// reuse them, the destructor releases them.
+struct GlobalSets {
+    struct Impl;
+    Impl* impl = nullptr;
+    GlobalSets() = default;
+    GlobalSets(const GlobalSets&) = delete;
+    GlobalSets& operator=(const GlobalSets&) = delete;
+    ~GlobalSets();
+};
+// The pooled matcher's search with featureMatchingGlobal's filter in view (match.hip), for the query images [img_a, img_b):
+// rows the filter provably drops at `ratio` are flagged in dismissed[] and not searched; for the others t3_* hold, per
+// (row, image) slot, the certified prefix of the three nearest rows of that image and the bound of its unlisted rows.
+// Returns the rows that survive phase 0's proof.
+int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& img_off, int img_a, int img_b,
+                             float ratio, const SlotTable& table, const int64_t* d_img_off, const int64_t* d_job_off, GlobalSets& sets,
+                             uint32_t* t3_idx, float* t3_d, float* t3_b, uint8_t* dismissed);
 
 // set bits of a 64-bit ballot word, as a rocprim transform (surf.hip, fast.hip, hamming_pairs.hip: the scans behind their ordered compactions)
 struct PopcOp {

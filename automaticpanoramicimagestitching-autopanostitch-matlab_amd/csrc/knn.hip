@@ -16,8 +16,7 @@
 #include <vector>
 
 #include "aps_internal.h"
-
-#include <rocprim/rocprim.hpp>
+#include "prims_dev.h"
 
 namespace aps {
 
@@ -180,6 +179,84 @@ __global__ __launch_bounds__(256, 2) void knn_f32_kernel(const float* __restrict
 // screened_block_top3).  The global top-4 is the (distance, index)-ascending head of their union, and it is CERTIFIED when
 // its fourth distance is strictly below every block's bound (no unlisted row can enter or tie).  Uncertified rows - a
 // query with three or more near-identical rows in ANOTHER block - are recomputed against the whole pool.
+
+// ascending (distance, global index) list of four; id < 0: an empty slot, behind every entry
+struct Top4 {
+    float v[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+    long long id[4] = {-1, -1, -1, -1};
+    __device__ __forceinline__ void insert(float d, long long g) {
+        bool lt[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lt[e] = id[e] < 0 || d < v[e] || (d == v[e] && g < id[e]);
+        // entries move up from the end while (d, g) goes ahead of them; it lands where that stops.  (Selects, no early
+        // return: with branches between the element accesses the arrays stay in memory)
+        bool go = lt[3];
+#pragma unroll
+        for (int e = 3; e >= 1; --e) {
+            const bool shift = go && lt[e - 1];
+            v[e] = shift ? v[e - 1] : (go ? d : v[e]);
+            id[e] = shift ? id[e - 1] : (go ? g : id[e]);
+            go = shift;
+        }
+        v[0] = go ? d : v[0];
+        id[0] = go ? g : id[0];
+    }
+    __device__ __forceinline__ float kth(int k) const {  // (selected, not indexed: a variable index sends the arrays to memory)
+        float d = INFINITY;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e == k - 1 && id[e] >= 0) d = v[e];
+        return d;
+    }
+};
+
+// element (row, e) of an output table under the caller's layout and leading dimension
+__device__ __forceinline__ int64_t out_at(int64_t row, int e, int64_t ldo, int layout) {
+    return layout == APS_ROWMAJOR ? row * ldo + e : (int64_t)e * ldo + row;
+}
+__device__ __forceinline__ void write_top(const Top4& top, int64_t row, int kk, uint32_t* __restrict__ idx, float* __restrict__ dist,
+                                          int64_t ldo, int layout) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e >= kk) break;
+        const int64_t o = out_at(row, e, ldo, layout);
+        idx[o] = top.id[e] >= 0 ? (uint32_t)(top.id[e] + 1) : 0u;
+        dist[o] = top.id[e] >= 0 ? top.v[e] : INFINITY;
+    }
+}
+
+// The merge both forms share.  `top` comes in holding what the caller knows exactly about row q of set bi (nothing, or the
+// own block's top-4); the three listed rows of every non-empty set j != exact_own join it, and the smallest of those sets'
+// bounds is what an unlisted row can have.  Certified: the k-th distance reported is strictly below that - the row is
+// written; otherwise it goes on the uncertified list.  (An own block given exactly contributes no bound: its fourth entry
+// may itself be the global fourth, and ties there are resolved by index, which the exact own-block list already did.)
+__device__ __forceinline__ void merge_listed_rows(int64_t q, int bi, int exact_own, Top4& top, const int64_t* __restrict__ block_off, int nb,
+                                                  const int64_t* __restrict__ job_off, const uint32_t* __restrict__ t3_idx,
+                                                  const float* __restrict__ t3_d, const float* __restrict__ t3_b, int k_out,
+                                                  uint32_t* __restrict__ idx, float* __restrict__ dist, int64_t ldo, int layout,
+                                                  uint32_t* __restrict__ unc_list, unsigned int* __restrict__ unc_count) {
+    const int64_t r = q - block_off[bi];
+    float bound = INFINITY;
+    for (int j = 0; j < nb; ++j) {
+        if (j == exact_own || block_off[j + 1] == block_off[j]) continue;
+        const int64_t slot = job_off[(size_t)bi * nb + j] + r;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const uint32_t li = t3_idx[slot * 3 + e];
+            if (li) top.insert(t3_d[slot * 3 + e], block_off[j] + (long long)li - 1);
+        }
+        bound = fminf(bound, t3_b[slot]);
+    }
+    const int kk = k_out < 4 ? k_out : 4;
+    const float dk = top.kth(kk);
+    const bool certified = dk < bound || !(bound < INFINITY);
+    if (certified)
+        write_top(top, q, kk, idx, dist, ldo, layout);
+    else
+        unc_list[atomicAdd(unc_count, 1u)] = (uint32_t)q;
+}
+
+// blocks of the pool: the own block's exact top-4 feeds the merge, the other blocks come as lists
 __global__ void knn_merge_kernel(const int64_t* __restrict__ block_off, int nb, const int64_t* __restrict__ job_off,
                                  const uint32_t* __restrict__ self_idx, const float* __restrict__ self_d,
                                  const uint32_t* __restrict__ t3_idx, const float* __restrict__ t3_d,
@@ -188,73 +265,20 @@ __global__ void knn_merge_kernel(const int64_t* __restrict__ block_off, int nb, 
                                  unsigned int* __restrict__ unc_count) {
     const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (q >= f) return;
-    int lo = 0, hi = nb - 1;  // block of q
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (block_off[mid] <= q) lo = mid; else hi = mid - 1;
-    }
-    const int bi = lo;
-    const int64_t r = q - block_off[bi];
-    float v[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-    long long id[4] = {-1, -1, -1, -1};
-    auto put = [&](float d, long long g) {
-        if (g < 0) return;
-        bool lt[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lt[e] = id[e] < 0 || d < v[e] || (d == v[e] && g < id[e]);
-        if (!lt[3]) return;
-#pragma unroll
-        for (int e = 3; e >= 1; --e) {
-            v[e] = lt[e - 1] ? v[e - 1] : d;
-            id[e] = lt[e - 1] ? id[e - 1] : g;
-            if (!lt[e - 1]) return;
-        }
-        v[0] = d;
-        id[0] = g;
-    };
+    const int bi = last_at_or_below(block_off, nb, q);
+    Top4 top;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const uint32_t li = self_idx[q * 4 + e];
-        if (li) put(self_d[q * 4 + e], block_off[bi] + (long long)li - 1);
+        if (li) top.insert(self_d[q * 4 + e], block_off[bi] + (long long)li - 1);
     }
-    float min_bound = INFINITY;
-    // the own block's list is exact and complete up to its fourth entry: anything unlisted there is at least that far
-    if (self_idx[q * 4 + 3]) min_bound = self_d[q * 4 + 3];
-    for (int j = 0; j < nb; ++j) {
-        if (j == bi) continue;
-        const int64_t slot = job_off[(size_t)bi * nb + j] + r;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            const uint32_t li = t3_idx[slot * 3 + e];
-            if (li) put(t3_d[slot * 3 + e], block_off[j] + (long long)li - 1);
-        }
-        min_bound = fminf(min_bound, t3_b[slot]);
-    }
-    // certified: the k-th distance reported is strictly below what any unlisted row can have.  (The own block's fourth
-    // entry may itself be the global fourth: then nothing unlisted of that block matters only if it is strictly farther -
-    // ties are resolved by index, which the exact own-block list already did, so that bound is taken non-strictly.)
-    const int kk = k_out < 4 ? k_out : 4;
-    const float dk = id[kk - 1] >= 0 ? v[kk - 1] : INFINITY;
-    float other_bound = INFINITY;
-    for (int j = 0; j < nb; ++j)
-        if (j != bi) other_bound = fminf(other_bound, t3_b[job_off[(size_t)bi * nb + j] + r]);
-    const bool certified = dk < other_bound || !(other_bound < INFINITY);
-    (void)min_bound;
-    if (certified) {
-        for (int e = 0; e < kk; ++e) {
-            const int64_t o = layout == APS_ROWMAJOR ? q * ldo + e : (int64_t)e * ldo + q;
-            idx[o] = id[e] >= 0 ? (uint32_t)(id[e] + 1) : 0u;
-            dist[o] = id[e] >= 0 ? v[e] : INFINITY;
-        }
-    } else {
-        unc_list[atomicAdd(unc_count, 1u)] = (uint32_t)q;
-    }
+    merge_listed_rows(q, bi, bi, top, block_off, nb, job_off, t3_idx, t3_d, t3_b, k_out, idx, dist, ldo, layout, unc_list, unc_count);
 }
 
-// The same merge for the pooled matcher's screened search (screened_global_top3): blocks = images, EVERY image
-// (the row's own too) comes as a certified prefix of three with a bound; rows the filter provably drops are written as
-// four copies of themselves (featureMatchingGlobal.m:129-141 removes the self matches, fewer than two candidates
-// remain, the query is skipped) and are never looked up.
+// The pooled matcher's screened search (screened_global_top3): blocks = images, EVERY image (the row's own too) comes as a
+// certified prefix of three with a bound; rows the filter provably drops are written as four copies of themselves
+// (featureMatchingGlobal.m:129-141 removes the self matches, fewer than two candidates remain, the query is skipped) and
+// are never looked up.
 __global__ void knn_merge3_kernel(const int64_t* __restrict__ block_off, int nb, const int64_t* __restrict__ job_off,
                                   const uint8_t* __restrict__ dismissed, const uint32_t* __restrict__ t3_idx,
                                   const float* __restrict__ t3_d, const float* __restrict__ t3_b, int64_t f, int k_out,
@@ -262,60 +286,17 @@ __global__ void knn_merge3_kernel(const int64_t* __restrict__ block_off, int nb,
                                   uint32_t* __restrict__ unc_list, unsigned int* __restrict__ unc_count, int64_t q_lo) {
     const int64_t q = q_lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;  // this call's rows: [q_lo, f)
     if (q >= f) return;
-    const int kk = k_out < 4 ? k_out : 4;
     if (dismissed[q]) {
-        for (int e = 0; e < kk; ++e) {
-            const int64_t o = layout == APS_ROWMAJOR ? q * ldo + e : (int64_t)e * ldo + q;
+        for (int e = 0; e < (k_out < 4 ? k_out : 4); ++e) {
+            const int64_t o = out_at(q, e, ldo, layout);
             idx[o] = (uint32_t)(q + 1);
             dist[o] = 0.f;
         }
         return;
     }
-    int lo = 0, hi = nb - 1;  // image of q
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (block_off[mid] <= q) lo = mid; else hi = mid - 1;
-    }
-    const int bi = lo;
-    const int64_t r = q - block_off[bi];
-    float v[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-    long long id[4] = {-1, -1, -1, -1};
-    auto put = [&](float d, long long g) {
-        bool lt[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lt[e] = id[e] < 0 || d < v[e] || (d == v[e] && g < id[e]);
-        if (!lt[3]) return;
-#pragma unroll
-        for (int e = 3; e >= 1; --e) {
-            v[e] = lt[e - 1] ? v[e - 1] : d;
-            id[e] = lt[e - 1] ? id[e - 1] : g;
-            if (!lt[e - 1]) return;
-        }
-        v[0] = d;
-        id[0] = g;
-    };
-    float bound = INFINITY;
-    for (int j = 0; j < nb; ++j) {
-        if (block_off[j + 1] == block_off[j]) continue;
-        const int64_t slot = job_off[(size_t)bi * nb + j] + r;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            const uint32_t li = t3_idx[slot * 3 + e];
-            if (li) put(t3_d[slot * 3 + e], block_off[j] + (long long)li - 1);
-        }
-        bound = fminf(bound, t3_b[slot]);
-    }
-    const float dk = id[kk - 1] >= 0 ? v[kk - 1] : INFINITY;
-    const bool certified = dk < bound || !(bound < INFINITY);
-    if (certified) {
-        for (int e = 0; e < kk; ++e) {
-            const int64_t o = layout == APS_ROWMAJOR ? q * ldo + e : (int64_t)e * ldo + q;
-            idx[o] = id[e] >= 0 ? (uint32_t)(id[e] + 1) : 0u;
-            dist[o] = id[e] >= 0 ? v[e] : INFINITY;
-        }
-    } else {
-        unc_list[atomicAdd(unc_count, 1u)] = (uint32_t)q;
-    }
+    Top4 top;
+    merge_listed_rows(q, last_at_or_below(block_off, nb, q), -1, top, block_off, nb, job_off, t3_idx, t3_d, t3_b, k_out, idx, dist, ldo,
+                      layout, unc_list, unc_count);
 }
 
 // Exact top-4 of one uncertified query row inside ONE block of the pool (one wave per (row, block); lane j takes the
@@ -373,24 +354,13 @@ __global__ __launch_bounds__(64) void knn_rows_block_top4_kernel(const float* __
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float bd[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-        int bi[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-        for (int e2 = 0; e2 < 64 * 4; ++e2) {
-            const float dq = s_d[e2];
-            const int iq = s_i[e2];
-            int pos = 4;
-            while (pos > 0 && (dq < bd[pos - 1] || (dq == bd[pos - 1] && iq < bi[pos - 1]))) --pos;
-            if (pos >= 4) continue;
-            for (int e = 3; e > pos; --e) {
-                bd[e] = bd[e - 1];
-                bi[e] = bi[e - 1];
-            }
-            bd[pos] = dq;
-            bi[pos] = iq;
-        }
+        Top4 top;  // (indices within the block; 0x7fffffff: a lane's empty slot)
+        for (int e2 = 0; e2 < 64 * 4; ++e2)
+            if (s_i[e2] < nt) top.insert(s_d[e2], s_i[e2]);
+#pragma unroll
         for (int e = 0; e < 4; ++e) {
-            out_i[((size_t)ri * nb + b) * 4 + e] = bi[e] < nt ? t0 + bi[e] : -1;
-            out_d[((size_t)ri * nb + b) * 4 + e] = bd[e];
+            out_i[((size_t)ri * nb + b) * 4 + e] = top.id[e] >= 0 ? t0 + top.id[e] : -1;
+            out_d[((size_t)ri * nb + b) * 4 + e] = top.v[e];
         }
     }
 }
@@ -401,28 +371,12 @@ __global__ void knn_rows_merge_kernel(const uint32_t* __restrict__ rows, int n_r
                                       float* __restrict__ dist, int64_t ldo, int layout) {
     const int ri = blockIdx.x * blockDim.x + threadIdx.x;
     if (ri >= n_rows) return;
-    float v[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-    long long id[4] = {-1, -1, -1, -1};
+    Top4 top;
     for (int e2 = 0; e2 < nb * 4; ++e2) {
         const long long g = li[(size_t)ri * nb * 4 + e2];
-        const float d = ld_[(size_t)ri * nb * 4 + e2];
-        if (g < 0) continue;
-        int pos = 4;
-        while (pos > 0 && (id[pos - 1] < 0 || d < v[pos - 1] || (d == v[pos - 1] && g < id[pos - 1]))) --pos;
-        if (pos >= 4) continue;
-        for (int e = 3; e > pos; --e) {
-            v[e] = v[e - 1];
-            id[e] = id[e - 1];
-        }
-        v[pos] = d;
-        id[pos] = g;
+        if (g >= 0) top.insert(ld_[(size_t)ri * nb * 4 + e2], g);
     }
-    const int64_t q = rows[ri];
-    for (int e = 0; e < k_out && e < 4; ++e) {
-        const int64_t o = layout == APS_ROWMAJOR ? q * ldo + e : (int64_t)e * ldo + q;
-        idx[o] = id[e] >= 0 ? (uint32_t)(id[e] + 1) : 0u;
-        dist[o] = id[e] >= 0 ? v[e] : INFINITY;
-    }
+    write_top(top, rows[ri], k_out < 4 ? k_out : 4, idx, dist, ldo, layout);
 }
 
 // allDesc ./ sqrt(sum(allDesc.^2, 2) + eps('single'))  (featureMatchingGlobal.m:83-85: eps INSIDE the root); the sum is
@@ -609,6 +563,182 @@ using namespace aps;
 
 static thread_local int64_t g_global_rows = 0, g_global_surv = 0;  // aps_knn_global_screen_stats
 
+// ---- the global k-NN's host chain: stages shared by aps_knn_global and aps_knn_global_screened --------------------------------
+static bool plain_mode_asked() {  // APS_KNN_MODE=f32: the all-f32 search on every row
+    const char* e = std::getenv("APS_KNN_MODE");
+    return e && !std::strcmp(e, "f32");
+}
+
+// Strided copy-back of a rows x k table: with ldo beyond the logical extent the elements in between stay the caller's.
+// Ends in a synchronisation.
+static void commit_table(Out<uint32_t>& oi, Out<float>& od, int64_t rows, int k, int64_t ldo, int layout) {
+    const size_t width = layout == APS_ROWMAJOR ? (size_t)k : (size_t)rows, runs = layout == APS_ROWMAJOR ? (size_t)rows : (size_t)k;
+    oi.commit_2d(width, runs, (size_t)ldo);
+    od.commit_2d(width, runs, (size_t)ldo);
+    APS_HIP(hipStreamSynchronize(stream()));
+}
+
+// The few rows a merge could not certify (four or more near-identical rows in one other block / image): their exact top-4
+// in EVERY block, one wave per (row, block), then the global head of those lists.  P, sq: the pool as knn_prep_kernel
+// leaves it; unc: the n_unc listed rows.  Writes those rows of (idx, dist); no synchronisation.
+static void repair_uncertified_rows(const float* P, const float* sq, const uint32_t* unc, unsigned int n_unc, const int64_t* d_boff, int nb,
+                                    int k, uint32_t* idx, float* dist, int64_t ldo, int layout) {
+    Ws<long long> li((size_t)n_unc * nb * 4);
+    Ws<float> ldv((size_t)n_unc * nb * 4);
+    knn_rows_block_top4_kernel<<<(unsigned)((size_t)n_unc * nb), 64, 0, stream()>>>(P, sq, unc, (int)n_unc, d_boff, nb, li, ldv);
+    knn_rows_merge_kernel<<<cdiv(n_unc, 64), 64, 0, stream()>>>(unc, (int)n_unc, nb, li, ldv, k, idx, dist, ldo, layout);
+    check_launch("knn exact rows");
+}
+
+// ft == 0: index 0 / distance inf in the logical fq x k elements only (what lies between them under a padded ldo is the
+// caller's).  Ends in a synchronisation: the host vectors go out of scope.
+static void fill_no_neighbours(uint32_t* oi, float* od, int64_t fq, int k, int64_t ldo, int layout) {
+    const size_t wd = layout == APS_ROWMAJOR ? (size_t)k : (size_t)fq, rows = layout == APS_ROWMAJOR ? (size_t)fq : (size_t)k;
+    std::vector<uint32_t> z(wd * rows, 0u);
+    std::vector<float> inf(wd * rows, INFINITY);
+    APS_HIP(hipMemcpy2DAsync(oi, ldo * sizeof(uint32_t), z.data(), wd * sizeof(uint32_t), wd * sizeof(uint32_t), rows, hipMemcpyHostToDevice,
+                             stream()));
+    APS_HIP(hipMemcpy2DAsync(od, ldo * sizeof(float), inf.data(), wd * sizeof(float), wd * sizeof(float), rows, hipMemcpyHostToDevice,
+                             stream()));
+    APS_HIP(hipStreamSynchronize(stream()));
+}
+
+// The plain search: every query row against the whole train set in the exact f32 kernel.  No synchronisation.
+static void knn_plain_f32(const float* pq, const float* sq, int64_t fq, const float* PT, const float* sT, int64_t ft, int k, uint32_t* oi,
+                          float* od, int64_t ldo, int layout) {
+    Prof prof("knn_f32");
+    if (k <= 4)
+        knn_f32_kernel<4><<<cdiv(fq, 128), 256, 0, stream()>>>(pq, sq, (int)fq, PT, sT, (int)ft, k, oi, od, ldo, layout, 0);
+    else
+        knn_f32_kernel<8><<<cdiv(fq, 128), 256, 0, stream()>>>(pq, sq, (int)fq, PT, sT, (int)ft, k, oi, od, ldo, layout, 0);
+}
+
+// The blocked, screened form (featureMatchingGlobal's call: the pool against itself, k <= 4).  Inside its own block a row's
+// top-4 (self included) comes from the exact f32 kernel; against every other block the f16 candidate kernel of the pairwise
+// matcher finds the three nearest with exact distances and a certified bound; the merge yields the global top-4,
+// bit-identical to the all-f32 path (APS_KNN_MODE=f32), in ~1/8 of its matrix time; the rows it cannot certify are repaired.
+// dT: the pool as given, PT / sT: its prepared copy.  Ends in a synchronisation (the uncertified count), the repair after it.
+static void knn_blocked(const float* dT, int64_t ldt, int layout, const float* PT, const float* sT, int64_t ft, int k, uint32_t* oi, float* od,
+                        int64_t ldo) {
+    // rows per block: 40 workgroups of the candidate kernel (APS_KNN_BLOCK: smaller blocks for tests)
+    const int64_t bs = std::getenv("APS_KNN_BLOCK") ? std::max<int64_t>(512, std::atoll(std::getenv("APS_KNN_BLOCK")) / 128 * 128) : 20480;
+    const int nb = (int)((ft + bs - 1) / bs);
+    std::vector<int64_t> boff(nb + 1);
+    for (int b = 0; b <= nb; ++b) boff[b] = std::min<int64_t>((int64_t)b * bs, ft);
+    Ws<uint32_t> self_i((size_t)ft * 4);
+    Ws<float> self_d((size_t)ft * 4);
+    {
+        Prof prof("knn_f32");  // every block against itself, one launch (the row tile tells the block)
+        knn_f32_kernel<4><<<cdiv(ft, 128), 256, 0, stream()>>>(PT, sT, (int)ft, PT, sT, (int)ft, 4, self_i, self_d, 4, APS_ROWMAJOR, (int)bs);
+    }
+    check_launch("knn_f32_kernel");
+    const SlotTable table = slot_table(boff, 0, nb, false);
+    Ws<uint32_t> t3i((size_t)std::max<int64_t>(table.slots, 1) * 3);
+    Ws<float> t3d((size_t)std::max<int64_t>(table.slots, 1) * 3), t3b((size_t)std::max<int64_t>(table.slots, 1));
+    if (table.slots) screened_block_top3(dT, ldt, layout, boff, table, t3i, t3d, t3b);
+    Ws<int64_t> d_boff(nb + 1), d_joff((size_t)nb * nb);
+    Ws<uint32_t> unc((size_t)ft);
+    Ws<unsigned int> unc_n(1);
+    APS_HIP(hipMemcpyAsync(d_boff, boff.data(), (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
+    APS_HIP(hipMemcpyAsync(d_joff, table.job_off.data(), (size_t)nb * nb * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
+    APS_HIP(hipMemsetAsync(unc_n, 0, sizeof(unsigned int), stream()));
+    {
+        Prof prof("knn_merge");
+        knn_merge_kernel<<<cdiv(ft, 256), 256, 0, stream()>>>(d_boff, nb, d_joff, self_i, self_d, t3i, t3d, t3b, ft, k, oi, od, ldo, layout, unc,
+                                                             unc_n);
+    }
+    check_launch("knn_merge_kernel");
+    const unsigned int n_unc = read_back(unc_n.get());
+    if (n_unc) {
+        Prof prof("knn_exact_rows");
+        repair_uncertified_rows(PT, sT, unc, n_unc, d_boff, nb, k, oi, od, ldo, layout);
+    }
+    if (std::getenv("APS_TRACE"))
+        std::fprintf(stderr, "[aps] blocked k-NN: %d blocks, %u of %lld rows recomputed against the whole pool\n", nb, n_unc, (long long)ft);
+}
+
+// aps_knn_global past its argument checks: stage the operands, prepare them, search in the form the sizes ask for, copy back.
+static void knn_global_search(const float* train, int64_t ft, int64_t ldt, const float* query, int64_t fq, int64_t ldq, int layout, int k,
+                              uint32_t* idx, float* dist, int64_t ldo) {
+    const size_t oe = matrix_extent(fq, ldo, k, layout);
+    const bool same = train == query && ft == fq && ldt == ldq;
+    In<float> dT(train, ft == 0 ? 0 : matrix_extent(ft, ldt, kDim, layout)), dQ;
+    if (!same) dQ.bind(query, matrix_extent(fq, ldq, kDim, layout));
+    Out<uint32_t> oi(idx, oe);
+    Out<float> od(dist, oe);
+    Ws<float> PT((size_t)std::max<int64_t>(ft, 1) * kDim), sT(std::max<int64_t>(ft, 1)), PQ, sQ;
+    if (ft > 0) knn_prep_kernel<<<cdiv(ft, 64), 64, 0, stream()>>>(dT, ft, ldt, layout, PT, sT);
+    const float *pq = PT, *sq = sT;
+    if (!same) {
+        PQ.alloc((size_t)fq * kDim);
+        sQ.alloc(fq);
+        knn_prep_kernel<<<cdiv(fq, 64), 64, 0, stream()>>>(dQ, fq, ldq, layout, PQ, sQ);
+        pq = PQ;
+        sq = sQ;
+    }
+    check_launch("knn_prep_kernel");
+    if (ft == 0)
+        fill_no_neighbours(oi, od, fq, k, ldo, layout);
+    else if (same && k <= 4 && ft >= 8192 && !plain_mode_asked())
+        knn_blocked(dT, ldt, layout, PT, sT, ft, k, oi, od, ldo);
+    else
+        knn_plain_f32(pq, sq, fq, PT, sT, ft, k, oi, od, ldo, layout);
+    check_launch("knn_f32_kernel");
+    commit_table(oi, od, fq, k, ldo, layout);
+}
+
+// The (row, image) tables are addressed with 32-bit slots: a pool with more than 2^31 of them (BASELINE configs[4]: 500 images,
+// 5.4 M rows = 2.7e9 slots) is searched in several passes over ranges of QUERY images - every pass sees all images as columns,
+// so every row still gets its exact neighbours in the whole pool.  cuts: the passes' image ranges [cuts[c], cuts[c + 1]), each
+// within slot_cap slots where a single image allows.  False: one image alone exceeds the 32-bit slot range, no pass can hold
+// its table.
+static bool plan_query_passes(const std::vector<int64_t>& ioff, int64_t slot_cap, std::vector<int>& cuts) {
+    const int n_img = (int)ioff.size() - 1;
+    cuts.assign(1, 0);
+    int64_t run = 0;
+    for (int i = 0; i < n_img; ++i) {
+        const int64_t need = (ioff[i + 1] - ioff[i]) * (int64_t)n_img;
+        if (need > ((int64_t)1 << 31) - 2) return false;
+        if (run > 0 && run + need > slot_cap) {
+            cuts.push_back(i);
+            run = 0;
+        }
+        run += need;
+    }
+    cuts.push_back(n_img);
+    return true;
+}
+
+// The pass loop of the screened search: per range of query images the slot table, the screened lists (screened_global_top3)
+// and their merge into (oi, od) or onto the uncertified list.  The images' operand forms are prepared by the first pass and
+// reused by the others.  Every pass ends in a synchronisation (its tables go out of scope).  Returns the rows searched.
+static int64_t screened_passes(const float* dT, int64_t ld, int layout, const std::vector<int64_t>& ioff, const std::vector<int>& cuts,
+                               float ratio, int k, const int64_t* d_boff, uint32_t* oi, float* od, int64_t ldo, uint32_t* unc,
+                               unsigned int* unc_n) {
+    const int n_img = (int)ioff.size() - 1;
+    Ws<uint8_t> dismissed((size_t)ioff[n_img]);
+    Ws<int64_t> d_joff((size_t)n_img * n_img);
+    GlobalSets sets;
+    int64_t n_surv = 0;
+    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+        const int ia = cuts[c], ib = cuts[c + 1];
+        const SlotTable table = slot_table(ioff, ia, ib, true);
+        if (table.slots == 0) continue;
+        Ws<uint32_t> t3i((size_t)table.slots * 3);
+        Ws<float> t3d((size_t)table.slots * 3), t3b((size_t)table.slots);
+        APS_HIP(hipMemcpyAsync(d_joff, table.job_off.data(), (size_t)n_img * n_img * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
+        n_surv += screened_global_top3(dT, ld, layout, ioff, ia, ib, ratio, table, d_boff, d_joff, sets, t3i, t3d, t3b, dismissed);
+        {
+            Prof prof("knn_merge");
+            knn_merge3_kernel<<<cdiv(ioff[ib] - ioff[ia], 256), 256, 0, stream()>>>(d_boff, n_img, d_joff, dismissed, t3i, t3d, t3b, ioff[ib], k, oi,
+                                                                                    od, ldo, layout, unc, unc_n, ioff[ia]);
+        }
+        check_launch("knn_merge3_kernel");
+        APS_HIP(hipStreamSynchronize(stream()));
+    }
+    return n_surv;
+}
+
 extern "C" {
 
 int aps_knn_global(const float* train, int64_t ft, int64_t ldt, const float* query, int64_t fq, int64_t ldq,
@@ -627,103 +757,7 @@ int aps_knn_global(const float* train, int64_t ft, int64_t ldt, const float* que
             APS_REQUIRE(ldt >= ft && ldq >= fq && ldo >= fq, APS_E_DIM, "leading dimension too small");
         ctx();
         if (fq == 0) return;
-        const size_t te = ft == 0 ? 0 : (layout == APS_ROWMAJOR ? (size_t)(ft - 1) * ldt + dim : (size_t)(dim - 1) * ldt + ft);
-        const size_t qe = layout == APS_ROWMAJOR ? (size_t)(fq - 1) * ldq + dim : (size_t)(dim - 1) * ldq + fq;
-        const size_t oe = layout == APS_ROWMAJOR ? (size_t)(fq - 1) * ldo + k : (size_t)(k - 1) * ldo + fq;
-        const bool same = train == query && ft == fq && ldt == ldq;
-        In<float> dT(train, te), dQ;
-        if (!same) dQ.bind(query, qe);
-        Out<uint32_t> oi(idx, oe);
-        Out<float> od(dist, oe);
-        Ws<float> PT((size_t)std::max<int64_t>(ft, 1) * kDim), sT(std::max<int64_t>(ft, 1)), PQ, sQ;
-        if (ft > 0) knn_prep_kernel<<<cdiv(ft, 64), 64, 0, stream()>>>(dT, ft, ldt, layout, PT, sT);
-        const float *pq = PT, *sq = sT;
-        if (!same) {
-            PQ.alloc((size_t)fq * kDim);
-            sQ.alloc(fq);
-            knn_prep_kernel<<<cdiv(fq, 64), 64, 0, stream()>>>(dQ, fq, ldq, layout, PQ, sQ);
-            pq = PQ;
-            sq = sQ;
-        }
-        check_launch("knn_prep_kernel");
-        if (ft == 0) {
-            // (the logical fq x k elements only: what lies between them under a padded ldo is the caller's)
-            const size_t wd = layout == APS_ROWMAJOR ? (size_t)k : (size_t)fq, rows = layout == APS_ROWMAJOR ? (size_t)fq : (size_t)k;
-            std::vector<uint32_t> z(wd * rows, 0u);
-            std::vector<float> inf(wd * rows, INFINITY);
-            APS_HIP(hipMemcpy2DAsync(oi.get(), ldo * sizeof(uint32_t), z.data(), wd * sizeof(uint32_t), wd * sizeof(uint32_t), rows,
-                                     hipMemcpyHostToDevice, stream()));
-            APS_HIP(hipMemcpy2DAsync(od.get(), ldo * sizeof(float), inf.data(), wd * sizeof(float), wd * sizeof(float), rows,
-                                     hipMemcpyHostToDevice, stream()));
-            APS_HIP(hipStreamSynchronize(stream()));
-        } else if (same && k <= 4 && ft >= 8192 && !(std::getenv("APS_KNN_MODE") && !std::strcmp(std::getenv("APS_KNN_MODE"), "f32"))) {
-            // Blocked, screened form (featureMatchingGlobal's call: the pool against itself, k = 4).  Inside its own block a
-            // row's top-4 (self included) comes from the exact f32 kernel; against every other block the f16 candidate
-            // kernel of the pairwise matcher finds the three nearest with exact distances and a certified bound; the merge
-            // yields the global top-4, bit-identical to the all-f32 path (APS_KNN_MODE=f32), in ~1/8 of its matrix time.
-            // rows per block: 40 workgroups of the candidate kernel (APS_KNN_BLOCK: smaller blocks for tests)
-            const int64_t bs = std::getenv("APS_KNN_BLOCK") ? std::max<int64_t>(512, std::atoll(std::getenv("APS_KNN_BLOCK")) / 128 * 128) : 20480;
-            const int nb = (int)((ft + bs - 1) / bs);
-            std::vector<int64_t> boff(nb + 1);
-            for (int b = 0; b <= nb; ++b) boff[b] = std::min<int64_t>((int64_t)b * bs, ft);
-            Ws<uint32_t> self_i((size_t)ft * 4);
-            Ws<float> self_d((size_t)ft * 4);
-            {
-                Prof prof("knn_f32");  // every block against itself, one launch (the row tile tells the block)
-                knn_f32_kernel<4><<<cdiv(ft, 128), 256, 0, stream()>>>(PT, sT, (int)ft, PT, sT, (int)ft, 4, self_i, self_d, 4, APS_ROWMAJOR,
-                                                                      (int)bs);
-            }
-            check_launch("knn_f32_kernel");
-            std::vector<int64_t> job_off;
-            const int64_t slots = screened_block_top3(dT, ldt, layout, boff, job_off, nullptr, nullptr, nullptr);
-            Ws<uint32_t> t3i((size_t)std::max<int64_t>(slots, 1) * 3);
-            Ws<float> t3d((size_t)std::max<int64_t>(slots, 1) * 3), t3b((size_t)std::max<int64_t>(slots, 1));
-            if (nb > 1) screened_block_top3(dT, ldt, layout, boff, job_off, t3i, t3d, t3b);
-            Ws<int64_t> d_boff(nb + 1), d_joff((size_t)nb * nb);
-            Ws<uint32_t> unc((size_t)ft);
-            Ws<unsigned int> unc_n(1);
-            APS_HIP(hipMemcpyAsync(d_boff, boff.data(), (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
-            APS_HIP(hipMemcpyAsync(d_joff, job_off.data(), (size_t)nb * nb * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
-            APS_HIP(hipMemsetAsync(unc_n, 0, sizeof(unsigned int), stream()));
-            {
-                Prof prof("knn_merge");
-                knn_merge_kernel<<<cdiv(ft, 256), 256, 0, stream()>>>(d_boff, nb, d_joff, self_i, self_d, t3i, t3d, t3b, ft, k, oi, od, ldo,
-                                                                     layout, unc, unc_n);
-            }
-            check_launch("knn_merge_kernel");
-            unsigned int n_unc = 0;
-            APS_HIP(hipMemcpyAsync(&n_unc, unc_n, sizeof n_unc, hipMemcpyDeviceToHost, stream()));
-            APS_HIP(hipStreamSynchronize(stream()));
-            if (n_unc) {
-                // the few rows the merge could not certify (four or more near-identical rows in another block): their
-                // exact top-4 in EVERY block, one wave per (row, block), then the global head of those lists
-                Prof prof("knn_exact_rows");
-                Ws<long long> li((size_t)n_unc * nb * 4);
-                Ws<float> ldv((size_t)n_unc * nb * 4);
-                knn_rows_block_top4_kernel<<<(unsigned)((size_t)n_unc * nb), 64, 0, stream()>>>(PT, sT, unc, (int)n_unc, d_boff, nb, li, ldv);
-                knn_rows_merge_kernel<<<cdiv(n_unc, 64), 64, 0, stream()>>>(unc, (int)n_unc, nb, li, ldv, k, oi, od, ldo, layout);
-                check_launch("knn exact rows");
-            }
-            if (std::getenv("APS_TRACE"))
-                std::fprintf(stderr, "[aps] blocked k-NN: %d blocks, %u of %lld rows recomputed against the whole pool\n", nb, n_unc,
-                             (long long)ft);
-        } else {
-            Prof prof("knn_f32");
-            if (k <= 4)
-                knn_f32_kernel<4><<<cdiv(fq, 128), 256, 0, stream()>>>(pq, sq, (int)fq, PT, sT, (int)ft, k, oi, od, ldo, layout, 0);
-            else
-                knn_f32_kernel<8><<<cdiv(fq, 128), 256, 0, stream()>>>(pq, sq, (int)fq, PT, sT, (int)ft, k, oi, od, ldo, layout, 0);
-        }
-        check_launch("knn_f32_kernel");
-        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
-        if (layout == APS_ROWMAJOR) {
-            oi.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
-            od.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
-        } else {
-            oi.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
-            od.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
-        }
-        APS_HIP(hipStreamSynchronize(stream()));
+        knn_global_search(train, ft, ldt, query, fq, ldq, layout, k, idx, dist, ldo);
     });
 }
 
@@ -741,91 +775,30 @@ int aps_knn_global_screened(const float* pool, int64_t f, int64_t ld, int dim, i
         ctx();
         if (f == 0) return;
         const std::vector<int64_t> ioff(img_off, img_off + n_img + 1);
-        std::vector<int64_t> job_off;
-        if (f < 8192 || (std::getenv("APS_KNN_MODE") && !std::strcmp(std::getenv("APS_KNN_MODE"), "f32"))) {
-            // a tiny pool, or the exact mode asked for: the plain search
-            const int rc = aps_knn_global(pool, f, ld, pool, f, ld, dim, layout, k, idx, dist, ldo);
-            if (rc != APS_OK) {
-                const std::string why = aps_last_error();
-                fail(rc, "%s", why.c_str());
-            }
-            return;
-        }
-        // The (row, image) tables are addressed with 32-bit slots: a pool with more than 2^31 of them (BASELINE configs[4]:
-        // 500 images, 5.4 M rows = 2.7e9 slots) is searched in several passes over ranges of QUERY images - every pass sees
-        // all images as columns, so every row still gets its exact neighbours in the whole pool.  APS_KNN_SLOT_CAP (test
-        // hook) lowers the budget so that small pools take the chunked path too.
+        // APS_KNN_SLOT_CAP (test hook) lowers the slot budget of a pass so that small pools take the chunked path too
         int64_t slot_cap = ((int64_t)1 << 31) - 2;
         if (const char* e = std::getenv("APS_KNN_SLOT_CAP")) slot_cap = std::max<int64_t>(1, std::atoll(e));
-        std::vector<int> cuts{0};  // query image ranges [cuts[c], cuts[c + 1])
-        {
-            int64_t run = 0;
-            for (int i = 0; i < n_img; ++i) {
-                const int64_t need = (ioff[i + 1] - ioff[i]) * (int64_t)n_img;
-                if (need > ((int64_t)1 << 31) - 2) {
-                    // one image alone exceeds the 32-bit slot range: no pass can hold its table - the plain exact search
-                    // answers the whole call (slower, same result), as it did before the search was cut into passes
-                    const int rc = aps_knn_global(pool, f, ld, pool, f, ld, dim, layout, k, idx, dist, ldo);
-                    if (rc != APS_OK) {
-                        const std::string why = aps_last_error();
-                        fail(rc, "%s", why.c_str());
-                    }
-                    return;
-                }
-                if (run > 0 && run + need > slot_cap) {
-                    cuts.push_back(i);
-                    run = 0;
-                }
-                run += need;
-            }
-            cuts.push_back(n_img);
-        }
-        const size_t te = layout == APS_ROWMAJOR ? (size_t)(f - 1) * ld + dim : (size_t)(dim - 1) * ld + f;
-        const size_t oe = layout == APS_ROWMAJOR ? (size_t)(f - 1) * ldo + k : (size_t)(k - 1) * ldo + f;
-        In<float> dT(pool, te);
+        std::vector<int> cuts;
+        // a tiny pool, the exact mode asked for, or an image no pass can hold: the unscreened search answers the whole call
+        // (slower, same result)
+        if (f < 8192 || plain_mode_asked() || !plan_query_passes(ioff, slot_cap, cuts))
+            return knn_global_search(pool, f, ld, pool, f, ld, layout, k, idx, dist, ldo);
+        const size_t oe = matrix_extent(f, ldo, k, layout);
+        In<float> dT(pool, matrix_extent(f, ld, kDim, layout));
         Out<uint32_t> oi(idx, oe);
         Out<float> od(dist, oe);
-        Ws<uint8_t> dismissed((size_t)f);
-        Ws<int64_t> d_boff(n_img + 1), d_joff((size_t)n_img * n_img);
+        Ws<int64_t> d_boff(n_img + 1);
         Ws<uint32_t> unc((size_t)f);
         Ws<unsigned int> unc_n(1);
         APS_HIP(hipMemcpyAsync(d_boff, ioff.data(), (n_img + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
         APS_HIP(hipMemsetAsync(unc_n, 0, sizeof(unsigned int), stream()));
-        int64_t n_surv = 0;
-        struct PrepKeep {  // the images' operand forms are prepared by the first pass and reused by the others
-            GlobalPrep* p = global_prep_new();
-            ~PrepKeep() { global_prep_free(p); }
-        } keep;
-        for (size_t c = 0; c + 1 < cuts.size(); ++c) {
-            const int ia = cuts[c], ib = cuts[c + 1];
-            const int64_t slots = screened_global_top3(nullptr, ld, layout, ioff, ratio, job_off, nullptr, nullptr, nullptr, nullptr, nullptr, ia, ib);
-            if (slots == 0) continue;
-            Ws<uint32_t> t3i((size_t)slots * 3);
-            Ws<float> t3d((size_t)slots * 3), t3b((size_t)slots);
-            int64_t n_surv_c = 0;
-            screened_global_top3(dT, ld, layout, ioff, ratio, job_off, t3i, t3d, t3b, dismissed, &n_surv_c, ia, ib, keep.p);
-            n_surv += n_surv_c;
-            APS_HIP(hipMemcpyAsync(d_joff, job_off.data(), (size_t)n_img * n_img * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
-            {
-                Prof prof("knn_merge");
-                knn_merge3_kernel<<<cdiv(ioff[ib] - ioff[ia], 256), 256, 0, stream()>>>(d_boff, n_img, d_joff, dismissed, t3i, t3d, t3b, ioff[ib], k, oi,
-                                                                                        od, ldo, layout, unc, unc_n, ioff[ia]);
-            }
-            check_launch("knn_merge3_kernel");
-            APS_HIP(hipStreamSynchronize(stream()));  // job_off is rebuilt by the next pass; the t3 tables go out of scope
-        }
-        unsigned int n_unc = 0;
-        APS_HIP(hipMemcpyAsync(&n_unc, unc_n, sizeof n_unc, hipMemcpyDeviceToHost, stream()));
-        APS_HIP(hipStreamSynchronize(stream()));
-        if (n_unc) {  // (as in aps_knn_global: the exact top-4 of those rows in every image, then the head of the lists)
+        const int64_t n_surv = screened_passes(dT, ld, layout, ioff, cuts, ratio, k, d_boff, oi, od, ldo, unc, unc_n);
+        const unsigned int n_unc = read_back(unc_n.get());
+        if (n_unc) {  // (as in knn_blocked, on a prepared copy made for these rows only)
             Prof prof("knn_exact_rows");
             Ws<float> PT((size_t)f * kDim), sT((size_t)f);
             knn_prep_kernel<<<cdiv(f, 64), 64, 0, stream()>>>(dT, f, ld, layout, PT, sT);
-            Ws<long long> li((size_t)n_unc * n_img * 4);
-            Ws<float> ldv((size_t)n_unc * n_img * 4);
-            knn_rows_block_top4_kernel<<<(unsigned)((size_t)n_unc * n_img), 64, 0, stream()>>>(PT, sT, unc, (int)n_unc, d_boff, n_img, li, ldv);
-            knn_rows_merge_kernel<<<cdiv(n_unc, 64), 64, 0, stream()>>>(unc, (int)n_unc, n_img, li, ldv, k, oi, od, ldo, layout);
-            check_launch("knn exact rows");
+            repair_uncertified_rows(PT, sT, unc, n_unc, d_boff, n_img, k, oi, od, ldo, layout);
             APS_HIP(hipStreamSynchronize(stream()));
         }
         if (std::getenv("APS_TRACE"))
@@ -833,17 +806,10 @@ int aps_knn_global_screened(const float* pool, int64_t f, int64_t ld, int dim, i
                          (long long)n_surv, (long long)f, n_unc);
         g_global_rows = f;
         g_global_surv = n_surv;
-        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
-        if (layout == APS_ROWMAJOR) {
-            oi.commit_2d((size_t)k, (size_t)f, (size_t)ldo);
-            od.commit_2d((size_t)k, (size_t)f, (size_t)ldo);
-        } else {
-            oi.commit_2d((size_t)f, (size_t)k, (size_t)ldo);
-            od.commit_2d((size_t)f, (size_t)k, (size_t)ldo);
-        }
-        APS_HIP(hipStreamSynchronize(stream()));
+        commit_table(oi, od, f, k, ldo, layout);
     });
 }
+
 
 int aps_knn_global_screen_stats(int64_t* rows, int64_t* survivors) {
     if (rows) *rows = g_global_rows;
@@ -859,8 +825,7 @@ int aps_global_normalize(const float* X, int64_t n, int64_t ld, int dim, int lay
         APS_REQUIRE(layout == APS_ROWMAJOR ? ld >= dim : ld >= n, APS_E_DIM, "leading dimension too small");
         ctx();
         if (n == 0) return;
-        const size_t ne = layout == APS_ROWMAJOR ? (size_t)(n - 1) * ld + dim : (size_t)(dim - 1) * ld + n;
-        In<float> dX(X, ne);
+        In<float> dX(X, matrix_extent(n, ld, dim, layout));
         Out<float> dO(out, (size_t)n * kDim);
         Prof prof("global_normalize");
         global_normalize_kernel<<<cdiv(n, 64), 64, 0, stream()>>>(dX, n, ld, layout, dO);
@@ -884,7 +849,7 @@ int aps_global_filter(const uint32_t* nn_idx, const float* nn_dist, int64_t f, i
         *count = 0;
         std::vector<int64_t> hp(std::max<int64_t>(n_pairs, 0) + 1, 0);
         if (f > 0 && n_pairs > 0) {
-            const size_t ne = layout == APS_ROWMAJOR ? (size_t)(f - 1) * ldn + k : (size_t)(k - 1) * ldn + f;
+            const size_t ne = matrix_extent(f, ldn, k, layout);
             In<uint32_t> di(nn_idx, ne), dimg(img_idx, f), dloc(local_idx, f);
             In<float> dd(nn_dist, ne);
             Ws<unsigned long long> keys(f), sorted(f), pc(n_pairs);
@@ -947,9 +912,7 @@ int aps_hamming_2nn(const uint8_t* A, int64_t n1, int64_t lda, const uint8_t* B,
             APS_HIP(hipMemcpyAsync(o2.get(), nan.data(), n1 * sizeof(float), hipMemcpyHostToDevice, stream()));
             APS_HIP(hipStreamSynchronize(stream()));
         } else {
-            const size_t ae = layout == APS_ROWMAJOR ? (size_t)(n1 - 1) * lda + nbytes : (size_t)(nbytes - 1) * lda + n1;
-            const size_t be = layout == APS_ROWMAJOR ? (size_t)(n2 - 1) * ldb + nbytes : (size_t)(nbytes - 1) * ldb + n2;
-            In<uint8_t> dA(A, ae), dB(B, be);
+            In<uint8_t> dA(A, matrix_extent(n1, lda, nbytes, layout)), dB(B, matrix_extent(n2, ldb, nbytes, layout));
             const int nw = nbytes <= 32 ? 8 : 16;
             Ws<uint32_t> pa((size_t)n1 * nw), pb((size_t)n2 * nw);
             pack_bytes_kernel<<<cdiv((size_t)n1 * nw, 256), 256, 0, stream()>>>(dA, n1, lda, nbytes, layout, nw, pa);
@@ -984,10 +947,8 @@ int aps_knn_hamming(const uint8_t* train, int64_t ft, int64_t ldt, const uint8_t
             APS_REQUIRE(ldt >= ft && ldq >= fq && ldo >= fq, APS_E_DIM, "leading dimension too small");
         ctx();
         if (fq == 0) return;
-        const size_t te = ft == 0 ? 0 : (layout == APS_ROWMAJOR ? (size_t)(ft - 1) * ldt + nbytes : (size_t)(nbytes - 1) * ldt + ft);
-        const size_t qe = layout == APS_ROWMAJOR ? (size_t)(fq - 1) * ldq + nbytes : (size_t)(nbytes - 1) * ldq + fq;
-        const size_t oe = layout == APS_ROWMAJOR ? (size_t)(fq - 1) * ldo + k : (size_t)(k - 1) * ldo + fq;
-        In<uint8_t> dT(train, te), dQ(query, qe);
+        const size_t oe = matrix_extent(fq, ldo, k, layout);
+        In<uint8_t> dT(train, ft == 0 ? 0 : matrix_extent(ft, ldt, nbytes, layout)), dQ(query, matrix_extent(fq, ldq, nbytes, layout));
         Out<uint32_t> oi(idx, oe);
         Out<float> od(dist, oe);
         const int nw = nbytes <= 32 ? 8 : 16;
@@ -1006,15 +967,7 @@ int aps_knn_hamming(const uint8_t* train, int64_t ft, int64_t ldt, const uint8_t
 #undef APS_HK
         }
         check_launch("hamming_knn_kernel");
-        // strided copy-back: with ldo beyond the logical extent the elements in between stay the caller's
-        if (layout == APS_ROWMAJOR) {
-            oi.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
-            od.commit_2d((size_t)k, (size_t)fq, (size_t)ldo);
-        } else {
-            oi.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
-            od.commit_2d((size_t)fq, (size_t)k, (size_t)ldo);
-        }
-        APS_HIP(hipStreamSynchronize(stream()));
+        commit_table(oi, od, fq, k, ldo, layout);
     });
 }
 

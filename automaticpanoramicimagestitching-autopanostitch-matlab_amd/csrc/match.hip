@@ -414,12 +414,7 @@ struct PrepJob {
     int* cin;
 };
 __device__ __forceinline__ int prep_find_job(const int* __restrict__ blk_ptr, int n_jobs, int b) {
-    int lo = 0, hi = n_jobs - 1;  // largest j with blk_ptr[j] <= b
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_ptr[mid] <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return last_at_or_below(blk_ptr, n_jobs, b);
 }
 __global__ __launch_bounds__(kPrepThreads) void prep_desc_batch_kernel(const PrepJob* __restrict__ jobs, const int* __restrict__ blk_ptr, int n_jobs) {
     __shared__ __attribute__((aligned(16))) PrepLds L;
@@ -2577,15 +2572,7 @@ struct FilterJob {
 
 // row -> job lookup by binary search over row_off
 __device__ __forceinline__ int find_job(const FilterJob* __restrict__ fj, int njobs, int64_t slot) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (fj[mid].row_off <= slot)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
+    return last_at_or_below_by([fj](int j) { return fj[j].row_off; }, njobs, slot);
 }
 
 __global__ void filter_mark_kernel(const FilterJob* __restrict__ fj, int njobs, int64_t total_rows,
@@ -3255,12 +3242,8 @@ static void launch_screen(const MatchJob* djobs, const WgJob* dbw, size_t n_bw, 
 __global__ void expand_tiles_kernel(const int* __restrict__ off, int n_jobs, int n_tiles, int rows_per_tile, WgJob* __restrict__ out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_tiles) return;
-    int lo = 0, hi = n_jobs - 1;  // the largest j with off[j] <= k (jobs without rows have empty ranges)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= k) lo = mid; else hi = mid - 1;
-    }
-    out[k] = WgJob{lo, (k - off[lo]) * rows_per_tile, 0, 0, 0, 0};
+    const int j = last_at_or_below(off, n_jobs, k);  // (jobs without rows have empty ranges)
+    out[k] = WgJob{j, (k - off[j]) * rows_per_tile, 0, 0, 0, 0};
 }
 // ---- run_match_jobs and its steps: the 2-NN search for a list of jobs whose operands are already prepared on the device ----
 
@@ -3523,24 +3506,29 @@ __global__ void fb_jobs_kernel(const long long* __restrict__ dst, const unsigned
     for (unsigned int e = threadIdx.x; e < cnt; e += blockDim.x) job_of[dst[j] + e] = j;
 }
 
+SlotTable slot_table(const std::vector<int64_t>& off, int a, int b, bool every_j) {
+    const int n = (int)off.size() - 1;
+    SlotTable t;
+    t.job_off.assign((size_t)n * n, every_j ? 0 : -1);
+    for (int i = a; i < b; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (i == j && !every_j) continue;
+            t.job_off[(size_t)i * n + j] = t.slots;
+            t.slots += off[i + 1] - off[i];
+        }
+    return t;
+}
+
 // The screening half of the blocked global k-NN (aps_knn_global on a pool against itself, knn.hip): the pool is cut into
 // blocks; for every ordered pair of DIFFERENT blocks (i, j) the candidate kernel finds, for each row of block i, its three
 // nearest rows of block j (exact canonical distances, ascending by (distance, index)) and a bound below which no other
 // row of block j lies.  Rows the f16 screen cannot certify are recomputed exactly (knn3_rows_kernel).
-// Outputs are indexed by slot = job_off[i * nb + j] + local row:  t3_idx[3 slot + e] (1-based within block j, 0 = none),
-// t3_d[3 slot + e], t3_b[slot].  Returns the slot count; call with t3_* == nullptr to get it first.
-int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& block_off,
-                            std::vector<int64_t>& job_off, uint32_t* t3_idx, float* t3_d, float* t3_b) {
+// Outputs are indexed by slot = table.job_off[i * nb + j] + local row:  t3_idx[3 slot + e] (1-based within block j, 0 = none),
+// t3_d[3 slot + e], t3_b[slot].  table: slot_table(block_off, 0, nb, false), with slots > 0.
+void screened_block_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& block_off, const SlotTable& table,
+                         uint32_t* t3_idx, float* t3_d, float* t3_b) {
     const int nb = (int)block_off.size() - 1;
-    job_off.assign((size_t)nb * nb, -1);
-    int64_t slots = 0;
-    for (int i = 0; i < nb; ++i)
-        for (int j = 0; j < nb; ++j) {
-            if (i == j) continue;
-            job_off[(size_t)i * nb + j] = slots;
-            slots += block_off[i + 1] - block_off[i];
-        }
-    if (!t3_idx || slots == 0) return slots;
+    const int64_t slots = table.slots;
     APS_REQUIRE(slots < ((int64_t)1 << 31), APS_E_DIM, "too many (row, block) pairs for one pass (%lld)", (long long)slots);
     std::vector<Prepared> prep(nb);
     for (int b = 0; b < nb; ++b) {
@@ -3554,7 +3542,7 @@ int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const st
             if (i == j) continue;
             const int nA = (int)(block_off[i + 1] - block_off[i]), nB = (int)(block_off[j + 1] - block_off[j]);
             for (int r = 0; r < nA; r += kTMB) bw.push_back({(int)jobs.size(), r, 0});
-            jobs.push_back(make_job(prep[i], prep[j], nA, nB, job_off[(size_t)i * nb + j]));
+            jobs.push_back(make_job(prep[i], prep[j], nA, nB, table.job_off[(size_t)i * nb + j]));
         }
     Ws<MatchJob> djobs(jobs.size());
     Ws<WgJob> dbw(bw.size());
@@ -3570,8 +3558,9 @@ int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const st
     }
     check_launch("match_cand_f16_kernel");
     std::vector<unsigned int> h_cnt(jobs.size());
-    APS_HIP(hipMemcpyAsync(h_cnt.data(), fb_count, jobs.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
+    read_back(fb_count.get(), h_cnt.data(), (int)jobs.size());
+    // The uncertified rows pooled in JOB order (fallback_pass pools them by B set, for the 128-row tiles of match2nn_kernel):
+    // knn3_rows_kernel takes one row per workgroup and finds its job through job_of, so there are no tiles to share.
     std::vector<long long> h_dst(jobs.size());
     size_t n_fb = 0;
     for (size_t j = 0; j < jobs.size(); ++j) {
@@ -3593,7 +3582,6 @@ int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const st
     if (std::getenv("APS_TRACE"))
         std::fprintf(stderr, "[aps] blocked k-NN screen: %d blocks, %zu jobs, %lld slots, %zu uncertified (%.3f %%)\n", nb, jobs.size(),
                      (long long)slots, n_fb, 100.0 * (double)n_fb / (double)slots);
-    return slots;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3606,6 +3594,34 @@ int64_t screened_block_top3(const float* X_dev, int64_t ld, int layout, const st
 // c2 <= min(second smallest H1(j), min_j H2(j)).  Whatever the k nearest are, the two cross-image rows the ratio test
 // compares are no nearer than c1 and c2 - so  min_j L1(j) > ratio * max(that upper bound, eps)  proves that q is dropped,
 // and only the other rows need their exact neighbours.
+
+// The proof: lmin = min_j L1(j), hsec >= the second smallest cross-image distance (at least eps('single'), as the reference
+// divides).  The factors 1 -+ 1e-5 and the 1e-30 cover the rounding of the two products, so that the f32 test errs on the
+// side of keeping the row; an infinite or missing bound (the unscreened mode writes NaN bounds, which fminf skips) proves
+// nothing.
+__device__ __forceinline__ bool proves_drop(float lmin, float hsec, float ratio) {
+    return hsec < INFINITY && lmin > -INFINITY && lmin < INFINITY && lmin * (1.0f - 1e-5f) - 1e-30f > ratio * hsec * (1.0f + 1e-5f);
+}
+// An image whose lower bound l1 lies beyond the cut holds none of the row's four nearest; the same margins on l1's side
+// (the cut carries its own).  NaN / -inf bounds are not beyond any cut: the image is kept.
+__device__ __forceinline__ bool beyond_cut(float l1, float cut) { return l1 * (1.0f - 1e-5f) - 1e-30f > cut; }
+
+// x into the ascending three v0 <= v1 <= v2 if it is below v2 (a tie stays behind the earlier entry); p travels with it.
+// (Selects on purpose: branches that end in "... = x" are merged into one store through a chosen address, and the
+// callers' variables then live in memory.)
+template <class P>
+__device__ __forceinline__ void top3_insert(float x, P p, float& v0, float& v1, float& v2, P& p0, P& p1, P& p2) {
+    const bool b0 = x < v0, b1 = x < v1, b2 = x < v2;
+    v2 = b1 ? v1 : (b2 ? x : v2), p2 = b1 ? p1 : (b2 ? p : p2);
+    v1 = b0 ? v0 : (b1 ? x : v1), p1 = b0 ? p0 : (b1 ? p : p1);
+    v0 = b0 ? x : v0, p0 = b0 ? p : p0;
+}
+struct NoPayload {};
+__device__ __forceinline__ void top3_insert(float x, float& v0, float& v1, float& v2) {
+    NoPayload n0, n1, n2;
+    top3_insert(x, NoPayload{}, v0, v1, v2, n0, n1, n2);
+}
+
 // A wave's rows lie in at most two images of >= 64 rows (rows are pooled image by image): the lanes of image `iw` append
 // to job (iw, j) with one atomic per wave.  `keep` must be false for lanes of another image.
 __device__ __forceinline__ void global_list_append(bool keep, int job, int64_t r, const int64_t* __restrict__ job_off,
@@ -3618,6 +3634,28 @@ __device__ __forceinline__ void global_list_append(bool keep, int job, int64_t r
     if (lane == leader) base = atomicAdd(&list_count[job], (unsigned int)__popcll(m));
     base = __shfl(base, leader);
     if (keep) row_list[job_off[job] + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)r;
+}
+// Row r of image i (act: the row is live and searched) joins the list of job (i, j) for every non-empty image j with
+// keep(j): one wave-wide pass for the image of the wave's first lane, one for that of its last, and plain atomics for the
+// lanes of an image of fewer than 64 rows strictly inside the wave (`edge`), which neither pass serves.  Called by all lanes.
+template <class Keep>
+__device__ __forceinline__ void global_lists_append(bool act, int i, int64_t r, const int64_t* __restrict__ img_off, int n_img,
+                                                    const int64_t* __restrict__ job_off, uint32_t* __restrict__ row_list,
+                                                    unsigned int* __restrict__ list_count, Keep keep) {
+    const int i_first = __shfl(i, 0), i_last = __shfl(i, 63);
+    const bool edge = i != i_first && i != i_last;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int iw = pass ? i_last : i_first;
+        if (pass && i_last == i_first) break;
+        for (int j = 0; j < n_img; ++j) {
+            if (img_off[j + 1] == img_off[j]) continue;
+            global_list_append(act && i == iw && keep(j), iw * n_img + j, r, job_off, row_list, list_count);
+        }
+    }
+    if (act && edge) {
+        for (int j = 0; j < n_img; ++j)
+            if (img_off[j + 1] != img_off[j] && keep(j)) row_list[job_off[i * n_img + j] + atomicAdd(&list_count[i * n_img + j], 1u)] = (uint32_t)r;
+    }
 }
 
 // Phase 0 of the pooled search: per row the verdict of the proof (dismissed), the bound-based cut (three distinct rows of
@@ -3632,57 +3670,24 @@ __global__ __launch_bounds__(256) void global_screen_reduce_kernel(const float* 
     const int64_t q = q_lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;  // this call's rows: [q_lo, f)
     const bool live = q < f;
     const int64_t qc = live ? q : f - 1;
-    int lo = 0, hi = n_img - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (img_off[mid] <= qc) lo = mid; else hi = mid - 1;
-    }
-    const int i = lo;
+    const int i = last_at_or_below(img_off, n_img, qc);
     const int64_t r = qc - img_off[i];
     float lmin = INFINITY, h2m = INFINITY;
     float u0 = INFINITY, u1 = INFINITY, u2 = INFINITY;  // three smallest of {H1(j), H2(j)}: distinct columns each
     float g0 = INFINITY, g1 = INFINITY, g2 = INFINITY;  // three smallest H1(j) ...
     int a0 = -1, a1 = -1, a2 = -1;                      // ... and their images
-    auto put3 = [&](float h) {
-        if (h < u2) {
-            if (h < u1) {
-                u2 = u1;
-                if (h < u0) {
-                    u1 = u0;
-                    u0 = h;
-                } else {
-                    u1 = h;
-                }
-            } else {
-                u2 = h;
-            }
-        }
-    };
     for (int j = 0; j < n_img; ++j) {
         if (j == i || img_off[j + 1] == img_off[j]) continue;
         const float* b = bounds + (size_t)(job_off[(size_t)i * n_img + j] + r) * 3;
         const float l1 = b[0], h1 = b[1], h2 = b[2];
         lmin = fminf(lmin, l1);
         h2m = fminf(h2m, h2);
-        put3(h1);
-        put3(h2);
-        if (h1 < g2) {
-            if (h1 < g1) {
-                g2 = g1, a2 = a1;
-                if (h1 < g0) {
-                    g1 = g0, a1 = a0;
-                    g0 = h1, a0 = j;
-                } else {
-                    g1 = h1, a1 = j;
-                }
-            } else {
-                g2 = h1, a2 = j;
-            }
-        }
+        top3_insert(h1, u0, u1, u2);
+        top3_insert(h2, u0, u1, u2);
+        top3_insert(h1, j, g0, g1, g2, a0, a1, a2);
     }
     const float hsec = fmaxf(fminf(g1, h2m), 1.1920929e-07f);  // (the reference divides by max(second, eps('single')))
-    const bool drop = live && hsec < INFINITY && lmin > -INFINITY && lmin < INFINITY &&
-                      lmin * (1.0f - 1e-5f) - 1e-30f > ratio * hsec * (1.0f + 1e-5f);
+    const bool drop = live && proves_drop(lmin, hsec, ratio);
     if (live) {
         dismissed[q] = drop ? 1 : 0;
         cut_out[q] = u2 < INFINITY ? u2 * (1.0f + 1e-5f) + 1e-30f : INFINITY;
@@ -3690,22 +3695,8 @@ __global__ __launch_bounds__(256) void global_screen_reduce_kernel(const float* 
         first_imgs[q * 3 + 1] = a1;
         first_imgs[q * 3 + 2] = a2;
     }
-    const int i_first = __shfl(i, 0), i_last = __shfl(i, 63);
-    const bool edge = i != i_first && i != i_last;  // (an image of fewer than 64 rows inside one wave: plain atomics)
-    for (int pass = 0; pass < 2; ++pass) {
-        const int iw = pass ? i_last : i_first;
-        if (pass && i_last == i_first) break;
-        for (int j = 0; j < n_img; ++j) {
-            if (img_off[j + 1] == img_off[j]) continue;
-            const bool keep = live && !drop && i == iw && (j == i || j == a0 || j == a1 || j == a2);
-            global_list_append(keep, iw * n_img + j, r, job_off, row_list, list_count);
-        }
-    }
-    if (live && !drop && edge) {
-        const int js[4] = {i, a0, a1, a2};
-        for (int e = 0; e < 4; ++e)
-            if (js[e] >= 0) row_list[job_off[i * n_img + js[e]] + atomicAdd(&list_count[i * n_img + js[e]], 1u)] = (uint32_t)r;
-    }
+    global_lists_append(live && !drop, i, r, img_off, n_img, job_off, row_list, list_count,
+                        [=](int j) { return j == i || j == a0 || j == a1 || j == a2; });
 }
 
 // Phase B: with the exact distances of phase A's candidates the third nearest non-self row found so far replaces the
@@ -3720,21 +3711,18 @@ __global__ __launch_bounds__(256) void global_phase_b_kernel(const float* __rest
     const int64_t q = q_lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;  // this call's rows: [q_lo, f)
     const bool live = q < f;
     const int64_t qc = live ? q : f - 1;
-    int lo = 0, hi = n_img - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (img_off[mid] <= qc) lo = mid; else hi = mid - 1;
-    }
-    const int i = lo;
+    const int i = last_at_or_below(img_off, n_img, qc);
     const int64_t r = qc - img_off[i];
     bool act = live && !dismissed[qc];
     const int a0 = first_imgs[qc * 3], a1 = first_imgs[qc * 3 + 1], a2 = first_imgs[qc * 3 + 2];
     float cut = cut_in[qc];
+    auto l1 = [=](int j) { return bounds[(size_t)(job_off[(size_t)i * n_img + j] + r) * 3]; };  // L1(j) of this row
     if (act) {
         // the three smallest exact distances to rows other than q itself among phase A's (certified) candidates, and the
         // two smallest among those of OTHER images
         float x0 = INFINITY, x1 = INFINITY, x2 = INFINITY, c0 = INFINITY, c1 = INFINITY;
         const int js[4] = {i, a0, a1, a2};
+#pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int j = js[e];
             if (j < 0) continue;
@@ -3751,19 +3739,7 @@ __global__ __launch_bounds__(256) void global_phase_b_kernel(const float* __rest
                         c1 = d;
                     }
                 }
-                if (d < x2) {
-                    if (d < x1) {
-                        x2 = x1;
-                        if (d < x0) {
-                            x1 = x0;
-                            x0 = d;
-                        } else {
-                            x1 = d;
-                        }
-                    } else {
-                        x2 = d;
-                    }
-                }
+                top3_insert(d, x0, x1, x2);
             }
         }
         if (x2 < INFINITY) cut = fminf(cut, x2 * (1.0f + 1e-6f) + 1e-30f);
@@ -3773,38 +3749,16 @@ __global__ __launch_bounds__(256) void global_phase_b_kernel(const float* __rest
             float lmin = INFINITY;
             for (int j = 0; j < n_img; ++j) {
                 if (j == i || img_off[j + 1] == img_off[j]) continue;
-                lmin = fminf(lmin, bounds[(size_t)(job_off[(size_t)i * n_img + j] + r) * 3]);
+                lmin = fminf(lmin, l1(j));
             }
-            const float hsec = fmaxf(c1, 1.1920929e-07f);
-            // (lmin == +inf: no bound at all - the unscreened mode writes NaN bounds, which fminf skips)
-            if (lmin > -INFINITY && lmin < INFINITY && lmin * (1.0f - 1e-5f) - 1e-30f > ratio * hsec * (1.0f + 1e-5f)) {
+            if (proves_drop(lmin, fmaxf(c1, 1.1920929e-07f), ratio)) {
                 dismissed[qc] = 1;
                 act = false;
             }
         }
     }
-    const int i_first = __shfl(i, 0), i_last = __shfl(i, 63);
-    const bool edge = i != i_first && i != i_last;
-    for (int pass = 0; pass < 2; ++pass) {
-        const int iw = pass ? i_last : i_first;
-        if (pass && i_last == i_first) break;
-        for (int j = 0; j < n_img; ++j) {
-            if (img_off[j + 1] == img_off[j]) continue;
-            bool keep = act && i == iw && j != i && j != a0 && j != a1 && j != a2;
-            if (keep) {
-                const float l1 = bounds[(size_t)(job_off[(size_t)i * n_img + j] + r) * 3];
-                keep = !(l1 * (1.0f - 1e-5f) - 1e-30f > cut);  // (NaN / -inf bounds keep the image)
-            }
-            global_list_append(keep, iw * n_img + j, r, job_off, row_list, list_count);
-        }
-    }
-    if (act && edge) {
-        for (int j = 0; j < n_img; ++j) {
-            if (img_off[j + 1] == img_off[j] || j == i || j == a0 || j == a1 || j == a2) continue;
-            const float l1 = bounds[(size_t)(job_off[(size_t)i * n_img + j] + r) * 3];
-            if (!(l1 * (1.0f - 1e-5f) - 1e-30f > cut)) row_list[job_off[i * n_img + j] + atomicAdd(&list_count[i * n_img + j], 1u)] = (uint32_t)r;
-        }
-    }
+    global_lists_append(act, i, r, img_off, n_img, job_off, row_list, list_count,
+                        [=](int j) { return j != i && j != a0 && j != a1 && j != a2 && !beyond_cut(l1(j), cut); });
 }
 
 // (row, image) slots that are not searched: no candidates, and nothing unlisted there can matter (bound = +inf)
@@ -3816,52 +3770,40 @@ __global__ void global_t3_init_kernel(uint32_t* __restrict__ t3_idx, float* __re
     t3_b[s] = INFINITY;
 }
 
-struct GlobalPrep {
+// ---- screened_global_top3 and its stages ---------------------------------------------------------------------------------
+struct GlobalSets::Impl {
     std::vector<Prepared> prep;
     Ws<float> stats;
-    bool ready = false;
 };
-GlobalPrep* global_prep_new() { return new GlobalPrep(); }
-void global_prep_free(GlobalPrep* p) { delete p; }
+GlobalSets::~GlobalSets() { delete impl; }
 
-// X_dev: the (normalised) pool; img_off: n + 1 row offsets of the images.  Slots: job (i, j), EVERY j (the diagonal too:
-// the rows of q's own image and q itself are candidates of the k nearest), slot = job_off[i n + j] + local row.
-// Outputs t3_* as screened_block_top3 for the rows with dismissed[q] == 0 (the other slots are not written).
-// Returns the slot count; call with t3_idx == nullptr to get it (and job_off) first.
-int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& img_off, float ratio,
-                             std::vector<int64_t>& job_off, uint32_t* t3_idx, float* t3_d, float* t3_b, uint8_t* dismissed,
-                             int64_t* n_survivors, int img_a, int img_b, GlobalPrep* keep) {
-    // [img_a, img_b): the QUERY images of this call (every image is a column set); a pool whose (row, image) table exceeds
-    // 2^31 slots - BASELINE configs[4]: 500 images, 5.4 M rows - is searched in several calls over ranges of query images
+// Stage 1 (first pass only): the images' operand forms, every set in one batch of launches (as in match_pairs_impl).
+// X_dev: the (normalised) pool, img_off: n + 1 row offsets.  No synchronisation of its own.
+static const std::vector<Prepared>& prepared_sets(GlobalSets& sets, const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& img_off) {
+    if (sets.impl) return sets.impl->prep;
     const int n = (int)img_off.size() - 1;
-    if (img_b < 0) img_b = n;
-    const int64_t q_lo = img_off[img_a], f = img_off[img_b];  // this call's rows (f: their end)
-    job_off.assign((size_t)n * n, 0);
-    int64_t slots = 0;
-    for (int i = img_a; i < img_b; ++i)
-        for (int j = 0; j < n; ++j) {
-            job_off[(size_t)i * n + j] = slots;
-            slots += img_off[i + 1] - img_off[i];
-        }
-    if (!t3_idx || slots == 0) return slots;
-    APS_REQUIRE(slots < ((int64_t)1 << 31), APS_E_DIM, "too many (row, image) pairs for one pass (%lld)", (long long)slots);
-    GlobalPrep local;
-    GlobalPrep& G = keep ? *keep : local;
-    std::vector<Prepared>& prep = G.prep;
-    Ws<float>& prep_stats = G.stats;
-    if (!G.ready) {  // the images' operand forms: every set in one batch of launches (as in match_pairs_impl)
-        prep.resize(n);
-        prep_stats.alloc((size_t)kStatWords * std::max(n, 1));
-        APS_HIP(hipMemsetAsync(prep_stats, 0, (size_t)kStatWords * std::max(n, 1) * sizeof(float), stream()));
-        std::vector<PrepRequest> req;
-        for (int b = 0; b < n; ++b) {
-            const float* xb = layout == APS_ROWMAJOR ? X_dev + (size_t)img_off[b] * ld : X_dev + img_off[b];
-            req.push_back({xb, img_off[b + 1] - img_off[b], ld, false, &prep[b], prep_stats.get() + kStatWords * b});
-        }
-        prepare_batch(req, layout);
-        G.ready = true;
+    sets.impl = new GlobalSets::Impl();
+    std::vector<Prepared>& prep = sets.impl->prep;
+    Ws<float>& stats = sets.impl->stats;
+    prep.resize(n);
+    stats.alloc((size_t)kStatWords * std::max(n, 1));
+    APS_HIP(hipMemsetAsync(stats, 0, (size_t)kStatWords * std::max(n, 1) * sizeof(float), stream()));
+    std::vector<PrepRequest> req;
+    for (int b = 0; b < n; ++b) {
+        const float* xb = layout == APS_ROWMAJOR ? X_dev + (size_t)img_off[b] * ld : X_dev + img_off[b];
+        req.push_back({xb, img_off[b + 1] - img_off[b], ld, false, &prep[b], stats.get() + kStatWords * b});
     }
-    // ---- the int8 screen over every ordered pair of different images: bounds per (row, image) ----
+    prepare_batch(req, layout);
+    return prep;
+}
+
+// Stage 2: bounds[3 slot ..] = (L1, H1, H2) of every (row of a query image, other image) from the int8 screen over every
+// ordered pair of different images, ending in a synchronisation (its tables go out of scope); without the screen
+// (APS_MATCH_NO_SCREEN, or no pair at all) NaN bounds - every comparison fails, every row survives and is searched in every
+// image - and no synchronisation.
+static void global_bounds(const std::vector<Prepared>& prep, const std::vector<int64_t>& img_off, int img_a, int img_b, const SlotTable& table,
+                          float* bounds) {
+    const int n = (int)img_off.size() - 1;
     std::vector<MatchJob> jobs;
     std::vector<WgJob> bw;
     for (int i = img_a; i < img_b; ++i)
@@ -3869,110 +3811,167 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
             const int nA = (int)(img_off[i + 1] - img_off[i]), nB = (int)(img_off[j + 1] - img_off[j]);
             if (i == j || nA == 0 || nB == 0) continue;
             for (int r = 0; r < nA; r += kTMB) bw.push_back({(int)jobs.size(), r, 0});
-            jobs.push_back(make_job(prep[i], prep[j], nA, nB, job_off[(size_t)i * n + j]));
+            jobs.push_back(make_job(prep[i], prep[j], nA, nB, table.job_off[(size_t)i * n + j]));
         }
-    Ws<float> bounds((size_t)slots * 3);
-    Ws<int64_t> d_ioff(n + 1), d_joff((size_t)n * n);
-    Ws<uint32_t> row_list((size_t)slots);
-    Ws<unsigned int> list_count((size_t)n * n);
-    APS_HIP(hipMemcpyAsync(d_ioff, img_off.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(d_joff, job_off.data(), (size_t)n * n * sizeof(int64_t), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemsetAsync(list_count, 0, (size_t)n * n * sizeof(unsigned int), stream()));
-    const bool screen = !std::getenv("APS_MATCH_NO_SCREEN") && !jobs.empty();
-    if (screen) {
-        Ws<MatchJob> djobs(jobs.size());
-        Ws<WgJob> dbw(bw.size());
-        APS_HIP(hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(MatchJob), hipMemcpyHostToDevice, stream()));
-        APS_HIP(hipMemcpyAsync(dbw, bw.data(), bw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
-        {
-            Prof prof("match_screen_i8_bounds");
-            launch_screen<true>(djobs, dbw, bw.size(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
-        }
-        check_launch("match_screen_i8_kernel (bounds)");
-        APS_HIP(hipStreamSynchronize(stream()));  // djobs / dbw go out of scope
-    } else {
-        // no screen: NaN bounds - every comparison fails, every row survives and is searched in every image
-        APS_HIP(hipMemsetAsync(bounds, 0xff, (size_t)slots * 3 * sizeof(float), stream()));
+    if (std::getenv("APS_MATCH_NO_SCREEN") || jobs.empty()) {
+        APS_HIP(hipMemsetAsync(bounds, 0xff, (size_t)table.slots * 3 * sizeof(float), stream()));
+        return;
     }
-    Ws<float> cut((size_t)f);
-    Ws<int> first_imgs((size_t)f * 3);
+    Ws<MatchJob> djobs(jobs.size());
+    Ws<WgJob> dbw(bw.size());
+    APS_HIP(hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(MatchJob), hipMemcpyHostToDevice, stream()));
+    APS_HIP(hipMemcpyAsync(dbw, bw.data(), bw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("match_screen_i8_bounds");
+        launch_screen<true>(djobs, dbw, bw.size(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
+    }
+    check_launch("match_screen_i8_kernel (bounds)");
+    APS_HIP(hipStreamSynchronize(stream()));
+}
+
+// What the row kernels of a pass share: the device tables of the query rows [q_lo, f) and their lists
+struct GlobalRows {
+    const float* bounds;
+    const int64_t *d_img_off, *d_job_off;
+    int n;
+    int64_t q_lo, f;
+    float ratio;
+    uint8_t* dismissed;
+    float* cut;
+    int* first_imgs;
+    uint32_t* row_list;
+    unsigned int* list_count;  // n x n, zero before phase 0
+};
+
+// Stage 3, phase 0: the proof's verdict, the cut and the first images of every row (global_screen_reduce_kernel), the t3
+// tables set to "not searched".  Returns the lists' lengths per job (i n + j); ends in the synchronisation of that read-back.
+static std::vector<unsigned int> global_phase_0(const GlobalRows& R, uint32_t* t3_idx, float* t3_d, float* t3_b, int64_t slots) {
     {
         Prof prof("global_screen_reduce");
-        global_screen_reduce_kernel<<<cdiv(f - q_lo, 256), 256, 0, stream()>>>(bounds, d_ioff, n, d_joff, f, ratio, dismissed, cut, first_imgs,
-                                                                               row_list, list_count, q_lo);
+        global_screen_reduce_kernel<<<cdiv(R.f - R.q_lo, 256), 256, 0, stream()>>>(R.bounds, R.d_img_off, R.n, R.d_job_off, R.f, R.ratio, R.dismissed,
+                                                                                   R.cut, R.first_imgs, R.row_list, R.list_count, R.q_lo);
         global_t3_init_kernel<<<cdiv(slots, 256), 256, 0, stream()>>>(t3_idx, t3_d, t3_b, slots);
     }
     check_launch("global_screen_reduce_kernel");
-    std::vector<unsigned int> h_a((size_t)n * n), h_b((size_t)n * n);
-    APS_HIP(hipMemcpyAsync(h_a.data(), list_count, (size_t)n * n * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    int64_t n_surv = 0;
-    for (int i = 0; i < n; ++i) n_surv += h_a[(size_t)i * n + i];  // (the diagonal job lists every surviving row of image i)
-    if (n_survivors) *n_survivors = n_surv;
-    if (n_surv == 0) return slots;
-    // ---- the exact three nearest rows (with a certified bound) of the listed (row, image) pairs, in two phases ----
-    std::vector<MatchJob> cj;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            cj.push_back(make_job(prep[i], prep[j], (int)(img_off[i + 1] - img_off[i]), (int)(img_off[j + 1] - img_off[j]),
-                                  job_off[(size_t)i * n + j]));  // (job index == i n + j)
-    Ws<MatchJob> dcj(cj.size());
-    Ws<uint32_t> fb_list(1);
-    Ws<unsigned int> fb_count(cj.size());
-    APS_HIP(hipMemcpyAsync(dcj, cj.data(), cj.size() * sizeof(MatchJob), hipMemcpyHostToDevice, stream()));
-    const bool pooled = !std::getenv("APS_MATCH_NO_POOL");
-    Ws<unsigned int> d_from((size_t)n * n);
-    auto search = [&](const std::vector<unsigned int>& from, const std::vector<unsigned int>& to) {  // list entries [from, to) of every job
-        std::vector<WgJob> lw;
-        Ws<uint32_t> pool;
-        Ws<int> pool_job;
-        if (pooled) {  // the lists of the jobs (i, j) that share the column image j in common tiles (list_count holds `to`)
-            APS_HIP(hipMemcpyAsync(d_from, from.data(), (size_t)n * n * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
-            lw = pool_lists(cj, job_off, row_list, from, to, d_from, list_count, pool, pool_job);
-        } else {
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < n; ++j) {
-                    if (img_off[i + 1] == img_off[i] || img_off[j + 1] == img_off[j]) continue;
-                    const size_t job = (size_t)i * n + j;
-                    for (unsigned int r = from[job]; r < to[job]; r += kTMB) lw.push_back({(int)job, (int)r, (int)std::min<unsigned int>(kTMB, to[job] - r)});
-                }
-        }
-        if (lw.empty()) return;
-        Ws<WgJob> dlw(lw.size());
-        APS_HIP(hipMemcpyAsync(dlw, lw.data(), lw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
-        {
-            Prof prof("match_cand_f16");
-            match_cand_f16_kernel<true><<<(unsigned)lw.size(), 512, 0, stream()>>>(dcj, dlw, (int)lw.size(), nullptr, nullptr, nullptr, fb_list,
-                                                                                    fb_count, 0.f, 0.f, t3_idx, t3_d, t3_b,
-                                                                                    pooled ? pool.get() : row_list.get(),
-                                                                                    pooled ? pool_job.get() : nullptr);
-        }
-        check_launch("match_cand_f16_kernel (pooled, list mode)");
-        APS_HIP(hipStreamSynchronize(stream()));  // lw / dlw go out of scope
-    };
-    const std::vector<unsigned int> zero((size_t)n * n, 0u);
-    search(zero, h_a);  // phase A: the own image and the three most promising ones
+    std::vector<unsigned int> h_a((size_t)R.n * R.n);
+    read_back(R.list_count, h_a.data(), R.n * R.n);
+    return h_a;
+}
+
+// Stage 5, phase B: the rows' further images by their exact distances so far (global_phase_b_kernel).  Returns the lists'
+// new lengths; ends in the synchronisation of that read-back.
+static std::vector<unsigned int> global_phase_b(const GlobalRows& R, const uint32_t* t3_idx, const float* t3_d) {
     {
         Prof prof("global_screen_reduce");
-        global_phase_b_kernel<<<cdiv(f - q_lo, 256), 256, 0, stream()>>>(bounds, d_ioff, n, d_joff, f, ratio, dismissed, cut, first_imgs, t3_idx,
-                                                                         t3_d, row_list, list_count, q_lo);
+        global_phase_b_kernel<<<cdiv(R.f - R.q_lo, 256), 256, 0, stream()>>>(R.bounds, R.d_img_off, R.n, R.d_job_off, R.f, R.ratio, R.dismissed, R.cut,
+                                                                             R.first_imgs, t3_idx, t3_d, R.row_list, R.list_count, R.q_lo);
     }
     check_launch("global_phase_b_kernel");
-    APS_HIP(hipMemcpyAsync(h_b.data(), list_count, (size_t)n * n * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
-    APS_HIP(hipStreamSynchronize(stream()));
-    bounds.reset();
-    int64_t n_a = 0, n_b = 0;
-    for (size_t job = 0; job < (size_t)n * n; ++job) {
-        n_a += h_a[job];
-        n_b += h_b[job] - h_a[job];
+    std::vector<unsigned int> h_b((size_t)R.n * R.n);
+    read_back(R.list_count, h_b.data(), R.n * R.n);
+    return h_b;
+}
+
+// The list search's fixed inputs: one job per (i, j), job index == i n + j, on the device as dcj
+struct ListJobs {
+    std::vector<MatchJob> cj;
+    Ws<MatchJob> dcj;
+    Ws<uint32_t> fb_list{1};
+    Ws<unsigned int> fb_count, d_from;
+    bool pooled = !std::getenv("APS_MATCH_NO_POOL");
+    ListJobs(const std::vector<Prepared>& prep, const std::vector<int64_t>& img_off, const SlotTable& table) {
+        const int n = (int)img_off.size() - 1;
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j)
+                cj.push_back(make_job(prep[i], prep[j], (int)(img_off[i + 1] - img_off[i]), (int)(img_off[j + 1] - img_off[j]),
+                                      table.job_off[(size_t)i * n + j]));
+        dcj.alloc(cj.size());
+        fb_count.alloc(cj.size());
+        d_from.alloc(cj.size());
+        APS_HIP(hipMemcpyAsync(dcj, cj.data(), cj.size() * sizeof(MatchJob), hipMemcpyHostToDevice, stream()));
     }
-    if (std::getenv("APS_TRACE"))
+};
+
+// Stages 4 and 6: the exact three nearest rows (with a certified bound) of the listed (row, image) pairs, entries
+// [from, to) of every job's list (list_count holds `to` on the device): the f16 candidate kernel in list mode, over the
+// lists of the jobs (i, j) that share the column image j pooled into common tiles, or (APS_MATCH_NO_POOL) over every job's
+// own tiles.  Writes t3_* at the listed slots; ends in a synchronisation (the tile table goes out of scope).
+static void global_list_search(const ListJobs& L, const std::vector<int64_t>& img_off, const SlotTable& table, const uint32_t* row_list,
+                               const unsigned int* list_count, const std::vector<unsigned int>& from, const std::vector<unsigned int>& to,
+                               uint32_t* t3_idx, float* t3_d, float* t3_b) {
+    const int n = (int)img_off.size() - 1;
+    std::vector<WgJob> lw;
+    Ws<uint32_t> pool;
+    Ws<int> pool_job;
+    if (L.pooled) {
+        APS_HIP(hipMemcpyAsync(L.d_from, from.data(), (size_t)n * n * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
+        lw = pool_lists(L.cj, table.job_off, row_list, from, to, L.d_from, list_count, pool, pool_job);
+    } else {
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) {
+                if (img_off[i + 1] == img_off[i] || img_off[j + 1] == img_off[j]) continue;
+                const size_t job = (size_t)i * n + j;
+                for (unsigned int r = from[job]; r < to[job]; r += kTMB) lw.push_back({(int)job, (int)r, (int)std::min<unsigned int>(kTMB, to[job] - r)});
+            }
+    }
+    if (lw.empty()) return;
+    Ws<WgJob> dlw(lw.size());
+    APS_HIP(hipMemcpyAsync(dlw, lw.data(), lw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("match_cand_f16");
+        match_cand_f16_kernel<true><<<(unsigned)lw.size(), 512, 0, stream()>>>(L.dcj, dlw, (int)lw.size(), nullptr, nullptr, nullptr, L.fb_list,
+                                                                                L.fb_count, 0.f, 0.f, t3_idx, t3_d, t3_b,
+                                                                                L.pooled ? pool.get() : row_list,
+                                                                                L.pooled ? pool_job.get() : nullptr);
+    }
+    check_launch("match_cand_f16_kernel (pooled, list mode)");
+    APS_HIP(hipStreamSynchronize(stream()));
+}
+
+// X_dev: the (normalised) pool; img_off: n + 1 row offsets of the images; [img_a, img_b): the QUERY images of this call
+// (every image is a column set; a pool whose (row, image) table exceeds 2^31 slots is searched in several calls).
+// table: slot_table(img_off, img_a, img_b, true) with slots > 0 - job (i, j), EVERY j (the diagonal too: the rows of q's own
+// image and q itself are candidates of the k nearest); d_img_off / d_job_off: img_off and table.job_off on the device.
+// Outputs t3_* as screened_block_top3 for the rows with dismissed[q] == 0 (the other slots are "not searched").
+int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const std::vector<int64_t>& img_off, int img_a, int img_b,
+                             float ratio, const SlotTable& table, const int64_t* d_img_off, const int64_t* d_job_off, GlobalSets& sets,
+                             uint32_t* t3_idx, float* t3_d, float* t3_b, uint8_t* dismissed) {
+    const int n = (int)img_off.size() - 1;
+    const int64_t q_lo = img_off[img_a], f = img_off[img_b], slots = table.slots;  // this call's rows (f: their end)
+    APS_REQUIRE(slots < ((int64_t)1 << 31), APS_E_DIM, "too many (row, image) pairs for one pass (%lld)", (long long)slots);
+    const std::vector<Prepared>& prep = prepared_sets(sets, X_dev, ld, layout, img_off);
+    Ws<float> bounds((size_t)slots * 3), cut((size_t)f);
+    Ws<uint32_t> row_list((size_t)slots);
+    Ws<unsigned int> list_count((size_t)n * n);
+    Ws<int> first_imgs((size_t)f * 3);
+    APS_HIP(hipMemsetAsync(list_count, 0, (size_t)n * n * sizeof(unsigned int), stream()));
+    global_bounds(prep, img_off, img_a, img_b, table, bounds);
+    const GlobalRows R{bounds, d_img_off, d_job_off, n, q_lo, f, ratio, dismissed, cut, first_imgs, row_list, list_count};
+    const std::vector<unsigned int> h_a = global_phase_0(R, t3_idx, t3_d, t3_b, slots);
+    int64_t n_surv = 0;
+    for (int i = 0; i < n; ++i) n_surv += h_a[(size_t)i * n + i];  // (the diagonal job lists every surviving row of image i)
+    if (n_surv == 0) return 0;
+    ListJobs L(prep, img_off, table);
+    const std::vector<unsigned int> zero((size_t)n * n, 0u);
+    // phase A: the own image and the three most promising ones
+    global_list_search(L, img_off, table, row_list, list_count, zero, h_a, t3_idx, t3_d, t3_b);
+    const std::vector<unsigned int> h_b = global_phase_b(R, t3_idx, t3_d);
+    bounds.reset();
+    if (std::getenv("APS_TRACE")) {
+        int64_t n_a = 0, n_b = 0;
+        for (size_t job = 0; job < (size_t)n * n; ++job) {
+            n_a += h_a[job];
+            n_b += h_b[job] - h_a[job];
+        }
         std::fprintf(stderr, "[aps] pooled matcher screen: %lld of %lld rows survive (%.2f %%); (row, image) searches: %lld first + %lld more of %lld (%.2f %%)\n",
                      (long long)n_surv, (long long)(f - q_lo), 100.0 * (double)n_surv / (double)std::max<int64_t>(f - q_lo, 1), (long long)n_a, (long long)n_b,
                      (long long)slots, 100.0 * (double)(n_a + n_b) / (double)slots);
-    search(h_a, h_b);  // phase B: every other image that can still hold one of the four nearest
-    return slots;
+    }
+    // phase B: every other image that can still hold one of the four nearest
+    global_list_search(L, img_off, table, row_list, list_count, h_a, h_b, t3_idx, t3_d, t3_b);
+    return n_surv;
 }
+
 
 // ratio/threshold/unique for a list of jobs; returns total kept.  Outputs are device pointers.
 static int64_t run_filter(const std::vector<FilterJob>& fjobs, int64_t total_rows, int64_t total_cols,

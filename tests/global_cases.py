@@ -84,6 +84,18 @@ PINNED = {
     "solo": (8200, {0.3: (0, 0), 0.6: (0, 0), 0.95: (0, 0)}),
     "crowded": (8279, {0.3: (866, 33), 0.6: (2356, 60), 0.95: (6830, 122)}),
 }
+# ---- pinned work of the device chain (measured on the library BEFORE its merge / proof / append steps were stated once; a
+# refactor that screens or certifies less leaves every table bit-exact and only these counts move) ---------------------------
+# pool -> {ratio: rows aps_knn_global_screen_stats reports as survivors of phase 0's proof, k = 4}
+SCREEN_SURVIVORS = {
+    "mosaic": {0.3: 1239, 0.6: 3239, 0.95: 8307},
+    "pair2": {0.3: 1492, 0.6: 2565, 0.95: 8298},
+    "solo": {0.3: 8200, 0.6: 8200, 0.95: 8200},
+    "crowded": {0.3: 7538, 0.6: 7750, 0.95: 8279},
+}
+# rows the merge kernels could not certify (APS_TRACE's counts): crowded through aps_knn_global_screened at ratio 0.6,
+# unit8193 through the blocked aps_knn_global at APS_KNN_BLOCK = BLOCK
+RECOMPUTED = {"crowded": 8, "unit8193": 2}
 MOSAIC_TINY_IMAGES_MATCHED = 13  # distinct images under 64 rows that take part in a match at ratio 0.6
 
 

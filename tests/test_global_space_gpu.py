@@ -138,6 +138,20 @@ def test_screened_search_rows_are_the_oracles_or_provably_dropped(capi, name):
         assert seen_dismissed > 0     # the screen does dismiss rows on this pool: both arms of the check above ran
 
 
+@pytest.mark.parametrize("name", list(gc.POOLS))
+def test_screen_statistics_are_pinned(capi, capfd, name):
+    """Bit-exact tables cannot see a screen that dismisses fewer rows than it did: the result is the same, only the work
+    grows.  aps_knn_global_screen_stats' (rows, survivors) at k = 4 are counts, not orders of atomics: pinned."""
+    pool = gc.pool_knn(name, 4)[0]
+    got = {}
+    for ratio in gc.RATIOS:
+        _screened(capi, pool, gc.POOL_SIZES[name], ratio, 4)
+        got[ratio] = _screen_stats(capi)
+        with capfd.disabled():
+            print(name, ratio, "(rows, survivors)", got[ratio])
+    assert got == {ratio: (len(pool), gc.SCREEN_SURVIVORS[name][ratio]) for ratio in gc.RATIOS}, name
+
+
 # ---- the same at list level, under every switch ----------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(gc.POOLS))
 def test_match_lists_equal_the_oracle_chain_under_every_switch(fm, capi, monkeypatch, name):
@@ -193,6 +207,7 @@ def test_exact_rows_repair_is_reached(fm, capi, monkeypatch, capfd):
     with capfd.disabled():
         print("crowded: recomputed exactly", m.group(4), "searched", m.group(2), "of", m.group(3))
     assert int(m.group(1)) == len(gc.CROWDED_SIZES) and int(m.group(3)) == len(pool) and int(m.group(4)) >= 1
+    assert int(m.group(4)) == gc.RECOMPUTED["crowded"] and int(m.group(2)) == gc.SCREEN_SURVIVORS["crowded"][0.6]
     _check_screened_table("crowded", 0.6, 4, idx, dist)
     x = gc.blocked_pool("unit8193").x
     monkeypatch.setenv("APS_KNN_BLOCK", str(gc.BLOCK))
@@ -204,6 +219,7 @@ def test_exact_rows_repair_is_reached(fm, capi, monkeypatch, capfd):
     with capfd.disabled():
         print("unit8193: recomputed", m.group(2), "of", m.group(3), "in", m.group(1), "blocks")
     assert int(m.group(1)) == 17 and int(m.group(3)) == 8193 and int(m.group(2)) >= 1
+    assert int(m.group(2)) == gc.RECOMPUTED["unit8193"]
     oi, od = gc.blocked_knn("unit8193")
     assert np.array_equal(bi, oi) and np.array_equal(bits(bd), bits(od))
 
