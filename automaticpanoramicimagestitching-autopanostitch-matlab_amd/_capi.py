@@ -91,6 +91,22 @@ class aps_surf_params(C.Structure):
                 ("upright", C.c_int), ("max_features", C.c_int)]
 
 
+APS_SURF_MAX_VIEWS = 16
+
+
+class aps_surf_view(C.Structure):
+    _fields_ = [("img", C.c_void_p), ("desc", C.c_void_p), ("loc", C.c_void_p), ("aux", C.c_void_p),
+                ("cap", C.c_int64), ("count", C.c_int64)]
+
+
+APS_FAST_MAX_VIEWS = 16
+
+
+class aps_fast_view(C.Structure):
+    _fields_ = [("img", C.c_void_p), ("desc", C.c_void_p), ("loc", C.c_void_p), ("aux", C.c_void_p),
+                ("cap", C.c_int64), ("count", C.c_int64)]
+
+
 class aps_sift_strongest_params(C.Structure):
     _fields_ = [("sift", aps_sift_params), ("n_strongest", C.c_int)]
 
@@ -240,6 +256,12 @@ _SIGNATURES = {
                                          _i, _i64, _i64],
     "aps_sift_extract_batch_uniform": [C.POINTER(aps_sift_view), _i, _i, _i, _i, _i, C.POINTER(aps_sift_uniform_params),
                                        _i, _i64, _i64],
+    "aps_surf_extract_batch": [C.POINTER(aps_surf_view), _i, _i, _i, _i, _i, C.POINTER(aps_surf_params), _i, _i64, _i64],
+    "aps_surf_extract_batch_strongest": [C.POINTER(aps_surf_view), _i, _i, _i, _i, _i, C.POINTER(aps_surf_strongest_params),
+                                         _i, _i64, _i64],
+    "aps_surf_extract_batch_uniform": [C.POINTER(aps_surf_view), _i, _i, _i, _i, _i, C.POINTER(aps_surf_uniform_params),
+                                       _i, _i64, _i64],
+    "aps_fast_extract_batch": [C.POINTER(aps_fast_view), _i, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _i, _i64, _i64],
     "aps_uniform_quota": [_vp, _i, _i64, _vp],
     "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
 }

@@ -6,9 +6,11 @@
 // a NumPy restatement (tests/fast_mirror.py) reproduces the outputs bit for bit: no device transcendental, no float summation.
 // The pattern's f64 layout is rounded to integer tables on the host, once (aps_freak_pattern hands them to the tests).
 //
-// Chain of one call (no host read-back until the final count; every grid is a capacity grid).  The call works on a plan of 1..16
-// levels (FastPlan; aps_fast_extract's plan is level 0 alone, aps_fast_extract_pyramid's is DESIGN.md "FAST/FREAK scale pyramid");
-// the planes, score planes, integral images and bitmap words of the levels lie packed one after the other:
+// Chain of one call (no host read-back until the final counts; every grid is a capacity grid).  The call works on a plan of 1..16
+// levels (FastPlan; aps_fast_extract's plan is level 0 alone, aps_fast_extract_pyramid's is DESIGN.md "FAST/FREAK scale pyramid")
+// and on a group of 1..16 views of one shape, which share the plan (aps_fast_extract_batch; the single-view entries are groups of
+// one).  Every stage is one launch for the group: the view is the last grid dimension or is decoded from the packed item's offset,
+// as the level is.  The planes, score planes, integral images and bitmap words lie packed [view][level]:
 //   integral_image        level 0: the u8 gray plane, stored once, and the exact 32-bit integral image (integral_dev.h, shared with
 //                         surf.hip); level l >= 1: the integral image of the resampled plane
 //   fast_resample_kernel  level l >= 1 from level l - 1: bilinear, half-pixel centres, 8-bit weights, integers only (one launch per
@@ -16,15 +18,16 @@
 //   fast_detect_kernel    64 x 8 tile of a level's plane (+4 halo: 3 for the ring, 1 for suppression) into LDS, the FAST-9 score of the
 //                         tile (+1 halo) into LDS, strict 3 x 3 maximum; writes the plane of kept scores (0 = no corner); one launch
 //                         over the tiles of all levels
-//   maximum of each level's score plane (rocprim, integers) = that level's s_max of the quality gate
+//   fast_smax_kernel      segmented maximum of the score planes (integers): s_max of the quality gate per (view, level)
 //   fast_gate_kernel      quality gate per pixel; one ballot = one 64-bit word of the candidate bitmap, whose bit order IS the
-//                         canonical feature order (level, row, col)
-//   exclusive scan of the words' popcounts (rocprim), fast_emit_kernel (ordered compaction, no atomics, no sort; the level is
-//                         decoded from the word's offset)
+//                         canonical feature order (level, row, col) within the view
+//   exclusive scan of all views' words' popcounts (rocprim), fast_emit_kernel (ordered compaction, no atomics, no sort; view and
+//                         level are decoded from the word's offset)
+//   group_rows_kernel     (group_dev.h) every view's count, first keypoint and rows to write: all views' or, if one does not fit, none
 //   freak_keypoint_kernel one wave per keypoint: 43 box sums on its level's integral image, 45-pair orientation moment, bin, 43 box
 //                         sums on the bin's table, 64 lanes x 8 tests = 512 bits; lane = output byte
-// aps_fast_extract_strongest (DESIGN.md "FAST/FREAK strongest-N") shares the chain up to the scan, reads the counts per level back,
-// and goes on with grids of the candidates' size:
+// aps_fast_extract_strongest (DESIGN.md "FAST/FREAK strongest-N"; one view: its selection group is a level) shares the chain up to the
+// scan, reads the counts per level back, and goes on with grids of the candidates' size:
 //   fast_emit_kernel      the candidate list
 //   fast_harris_kernel    one wave per candidate: integer Harris response of its level's plane, and the sort key (level, -R)
 //   select_by_key         (select_dev.h, shared with sift.hip and surf.hip) stable radix sort (rocprim) of (key, index),
@@ -40,10 +43,9 @@
 #include <cstring>
 
 #include "aps_internal.h"
+#include "group_dev.h"
 #include "integral_dev.h"
 #include "select_dev.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace aps {
 namespace {
@@ -63,10 +65,15 @@ struct FastLevel {
     long long plane0;        // first byte of the u8 plane (and of the plane of kept scores)
     long long integ0;        // first element of the (h + 1) x (w + 1) integral image
 };
+// A call works on nv views of one shape, which share the levels; what a view holds is packed [view][level]: view v's items of a
+// level start v * (the per-view total) after FastLevel's offsets.
 struct FastPlan {
-    int n;
+    int n, nv;
+    unsigned int view_tiles, view_words;  // detection tiles and bitmap words of one view
+    long long view_plane, view_integ;     // plane bytes and integral-image elements of one view
     FastLevel lv[kMaxLevels];
 };
+static_assert(kGroupViews == APS_FAST_MAX_VIEWS, "the group's tables hold kGroupViews views");
 // the level that holds item q of a packed sequence (tiles or words): `first` is the member of FastLevel that starts it
 __device__ __forceinline__ int level_of(const FastPlan& P, unsigned int FastLevel::*first, unsigned int q) {
     int l = 0;
@@ -198,10 +205,13 @@ constexpr int kRingDy[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, 
 
 // dst (hd x wd) from src (hs x ws), hd <= hs, wd <= ws: the contract's bilinear resampling.  The first 96 threads of a 64 x 32 tile
 // work out its 64 column and 32 row entries (first tap, 8-bit weight), one 64-bit division each; then a wave takes a row at a time.
+// blockIdx.z is the view: its planes lie view_plane bytes after the first view's.
 __global__ __launch_bounds__(256) void fast_resample_kernel(const uint8_t* __restrict__ src, int hs, int ws, uint8_t* __restrict__ dst,
-                                                            int hd, int wd) {
+                                                            int hd, int wd, long long view_plane) {
     __shared__ int2 s_x[kRW], s_y[kRH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    src += blockIdx.z * view_plane;
+    dst += blockIdx.z * view_plane;
     const int x0 = blockIdx.x * kRW, y0 = blockIdx.y * kRH;
     if (tid < kRW + kRH) {
         const bool col = tid < kRW;
@@ -239,12 +249,13 @@ __global__ __launch_bounds__(256) void fast_detect_kernel(const uint8_t* __restr
     __shared__ uint8_t G[kTH + 2 * kHalo][kTW + 2 * kHalo];
     __shared__ uint8_t S[kTH + 2][kTW + 2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const FastLevel& L = P.lv[level_of(P, &FastLevel::tile0, blockIdx.x)];
-    const unsigned int tile = blockIdx.x - L.tile0;
+    const unsigned int view = blockIdx.x / P.view_tiles, vtile = blockIdx.x - view * P.view_tiles;
+    const FastLevel& L = P.lv[level_of(P, &FastLevel::tile0, vtile)];
+    const unsigned int tile = vtile - L.tile0;
     const int h = L.h, w = L.w;
     const int x0 = (int)(tile % L.wpr) * kTW, y0 = (int)(tile / L.wpr) * kTH;
-    const uint8_t* __restrict__ gray = planes + L.plane0;
-    uint8_t* __restrict__ kept = kept_all + L.plane0;
+    const uint8_t* __restrict__ gray = planes + view * P.view_plane + L.plane0;
+    uint8_t* __restrict__ kept = kept_all + view * P.view_plane + L.plane0;
     constexpr int kGW = kTW + 2 * kHalo, kGN = (kTH + 2 * kHalo) * kGW;
     for (int e = tid; e < kGN; e += 256) {
         const int r = e / kGW, cc = e % kGW, y = y0 - kHalo + r, x = x0 - kHalo + cc;
@@ -290,32 +301,58 @@ __global__ __launch_bounds__(256) void fast_detect_kernel(const uint8_t* __restr
     }
 }
 
-struct U8ToU32 {
-    __host__ __device__ unsigned int operator()(uint8_t v) const { return v; }
-};
+// s_max of the quality gate for every (view, level), smax[view * P.n + level] (zeroed by the caller): the segmented maximum of the
+// packed planes of kept scores in one launch.  blockIdx.x is a chunk of kSmaxChunk bytes of the view blockIdx.y; of every level the
+// chunk meets, a wave takes the maximum of its bytes (words where they are aligned) and hands it over with one atomic maximum - of
+// integers, so the result does not depend on the order.
+constexpr long long kSmaxChunk = 1 << 16;
+__global__ __launch_bounds__(256) void fast_smax_kernel(const uint8_t* __restrict__ kept, const FastPlan P, unsigned int* __restrict__ smax) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long long c0 = (long long)blockIdx.x * kSmaxChunk, c1 = min(c0 + kSmaxChunk, P.view_plane);
+    const uint8_t* __restrict__ p = kept + blockIdx.y * P.view_plane;
+    for (int l = 0; l < P.n; ++l) {
+        const long long lo = max(c0, P.lv[l].plane0), hi = min(c1, l + 1 < P.n ? P.lv[l + 1].plane0 : P.view_plane);
+        if (lo >= hi) continue;  // (uniform in the workgroup)
+        // [lo, a) and [b, hi) byte by byte, [a, b) as aligned words
+        const long long mis = (long long)((4 - ((uintptr_t)(p + lo) & 3)) & 3), a = min(lo + mis, hi), b = a + ((hi - a) & ~3LL);
+        unsigned int m = 0;
+        for (long long i = a + 4LL * tid; i < b; i += 4 * 256) {
+            const unsigned int v = *reinterpret_cast<const unsigned int*>(p + i);
+            m = max(max(m, v & 255u), max(max((v >> 8) & 255u, (v >> 16) & 255u), v >> 24));
+        }
+        if (lo + tid < a) m = max(m, (unsigned int)p[lo + tid]);
+        if (b + tid < hi) m = max(m, (unsigned int)p[b + tid]);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) m = max(m, (unsigned int)__shfl_xor((int)m, off));
+        if (lane == 0 && m) atomicMax(&smax[blockIdx.y * P.n + l], m);
+    }
+}
 
-// keep iff s * q_den >= s_max * q_num, s_max being the level's; one wave per bitmap word = row segment of 64 pixels, its ballot is the word
+// keep iff s * q_den >= s_max * q_num, s_max being that of the view's level (d_smax[view * P.n + level]); one wave per bitmap word =
+// row segment of 64 pixels, its ballot is the word
 __global__ __launch_bounds__(256) void fast_gate_kernel(const uint8_t* __restrict__ kept, const FastPlan P, unsigned int n_words,
                                                         const unsigned int* __restrict__ d_smax, unsigned int q_num, unsigned int q_den,
                                                         unsigned long long* __restrict__ bitmap) {
     const int lane = threadIdx.x & 63;
     const unsigned int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (q >= n_words) return;  // (uniform in the wave)
-    const int l = level_of(P, &FastLevel::word0, q);
+    const unsigned int view = q / P.view_words, qv = q - view * P.view_words;
+    const int l = level_of(P, &FastLevel::word0, qv);
     const FastLevel& L = P.lv[l];
-    const unsigned int ql = q - L.word0;
+    const unsigned int ql = qv - L.word0;
     const int y = (int)(ql / L.wpr), x = (int)(ql % L.wpr) * 64 + lane;
-    const unsigned long long smax = d_smax[l];
-    const unsigned long long s = x < L.w ? kept[L.plane0 + (size_t)y * L.w + x] : 0;
+    const unsigned long long smax = d_smax[view * P.n + l];
+    const unsigned long long s = x < L.w ? kept[view * P.view_plane + L.plane0 + (size_t)y * L.w + x] : 0;
     const unsigned long long mask = __ballot(s > 0 && s * q_den >= smax * q_num);
     if (lane == 0) bitmap[q] = mask;
 }
 
 struct Keypoint {
-    int y, x, level;
+    int y, x, level, view;
 };
 
-// Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (level, row, col).
+// Ordered compaction: bit k of word q (of n_words, all views') becomes keypoint prefix[q] + (set bits below k) as (view, level, row,
+// col); the view and the level are decoded from the word's offset.
 __global__ __launch_bounds__(256) void fast_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
                                                         const FastPlan P, unsigned int n_words, Keypoint* __restrict__ kps, unsigned int kcap) {
     const unsigned int q = blockIdx.x * 256 + threadIdx.x;
@@ -323,13 +360,14 @@ __global__ __launch_bounds__(256) void fast_emit_kernel(const unsigned long long
     unsigned long long bits = bitmap[q];
     if (!bits) return;
     unsigned int pos = prefix[q];
-    const int l = level_of(P, &FastLevel::word0, q);
-    const unsigned int ql = q - P.lv[l].word0;
+    const unsigned int view = q / P.view_words, qv = q - view * P.view_words;
+    const int l = level_of(P, &FastLevel::word0, qv);
+    const unsigned int ql = qv - P.lv[l].word0;
     const int y = (int)(ql / P.lv[l].wpr), xw = (int)(ql % P.lv[l].wpr) * 64;
     while (bits) {
         const int k = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
-        if (pos < kcap) kps[pos] = Keypoint{y, xw + k, l};
+        if (pos < kcap) kps[pos] = Keypoint{y, xw + k, l, (int)view};
         ++pos;
     }
 }
@@ -349,19 +387,24 @@ __device__ __forceinline__ long long wave_max(long long v) {
     return v;
 }
 
-// One wave per keypoint.  Every wave of the capacity grid passes every barrier; the ones beyond the count do no work.
+// One wave per keypoint; blockIdx.y is the view, whose record (group_dev.h) says where its keypoints start and how many rows it
+// writes.  Every wave of the capacity grid passes every barrier; the ones beyond the view's rows do no work.
 __global__ __launch_bounds__(256) void freak_keypoint_kernel(const uint32_t* __restrict__ integ, const FastPlan P, const FreakDev* __restrict__ tb,
                                                              const uint8_t* __restrict__ kept, const Keypoint* __restrict__ kps,
-                                                             const unsigned int* __restrict__ d_total, unsigned int kcap,
-                                                             uint8_t* __restrict__ desc, int desc_layout, long long ldd,
-                                                             double* __restrict__ loc, long long ldl, float* __restrict__ aux) {
+                                                             const ViewRows<uint8_t>* __restrict__ views, int desc_layout, long long ldd,
+                                                             long long ldl) {
     __shared__ int s_S[4][kFields + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned int kidx = blockIdx.x * 4 + wave;
-    const unsigned int total = min(*d_total, kcap);
-    const bool active = kidx < total;
-    Keypoint kp{0, 0, 0};
-    if (active) kp = kps[kidx];
+    const ViewRows<uint8_t> V = views[blockIdx.y];
+    const unsigned int kidx = blockIdx.x * 4 + wave;  // the row of the view
+    const bool active = kidx < V.rows;
+    uint8_t* __restrict__ desc = V.desc;
+    double* __restrict__ loc = V.loc;
+    float* __restrict__ aux = V.aux;
+    integ += blockIdx.y * P.view_integ;
+    kept += blockIdx.y * P.view_plane;
+    Keypoint kp{0, 0, 0, 0};
+    if (active) kp = kps[V.kp0 + kidx];
     const FastLevel& L = P.lv[__builtin_amdgcn_readfirstlane(kp.level)];  // (one keypoint per wave)
     const uint32_t* __restrict__ I = integ + L.integ0;
     const size_t ws = (size_t)L.w + 1;
@@ -451,10 +494,10 @@ __global__ __launch_bounds__(256) void fast_harris_kernel(const uint8_t* __restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned int kidx = blockIdx.x * 4 + wave;
     const bool active = kidx < n;
-    Keypoint kp{0, 0, 0};
+    Keypoint kp{0, 0, 0, 0};
     if (active) kp = kps[kidx];
     const FastLevel& L = P.lv[__builtin_amdgcn_readfirstlane(kp.level)];  // (one candidate per wave)
-    const uint8_t* __restrict__ g = planes + L.plane0;
+    const uint8_t* __restrict__ g = planes + kp.view * P.view_plane + L.plane0;
     if (active) {
         for (int e = lane; e < kHarrisPatch * kHarrisPatch; e += 64) {
             const int r = e / kHarrisPatch, c = e % kHarrisPatch;
@@ -541,13 +584,13 @@ __global__ __launch_bounds__(256) void strongest_aux_kernel(const long long* __r
 // ---- host: the plan and the chain ----------------------------------------------------------------------------------------
 struct HostPlan {
     FastPlan dev;
-    size_t plane_bytes, integ_elems;  // of all levels
-    unsigned int n_tiles, n_words;
+    size_t plane_bytes, integ_elems;  // of all levels of one view
+    unsigned int n_tiles, n_words;    // of all levels of all views
 };
 
 // Level 0 is the image; level l is level l - 1 divided by num / den, each side rounded half up.  The plan ends before the first level
-// that has no pixel at least `margin` from every edge, or at n_levels.
-HostPlan make_plan(int h, int w, int n_levels, long long num, long long den) {
+// that has no pixel at least `margin` from every edge, or at n_levels.  nv views share it.
+HostPlan make_plan(int h, int w, int n_levels, long long num, long long den, int nv = 1) {
     HostPlan hp;
     std::memset(&hp, 0, sizeof hp);
     const int least = 2 * host_pattern().margin + 1;
@@ -571,12 +614,22 @@ HostPlan make_plan(int h, int w, int n_levels, long long num, long long den) {
         hp.integ_elems += (size_t)(h + 1) * (w + 1);
         hp.dev.n = l + 1;
     }
+    hp.dev.nv = nv;
+    hp.dev.view_tiles = hp.n_tiles;
+    hp.dev.view_words = hp.n_words;
+    hp.dev.view_plane = (long long)hp.plane_bytes;
+    hp.dev.view_integ = (long long)hp.integ_elems;
+    hp.n_tiles *= (unsigned int)nv;
+    hp.n_words *= (unsigned int)nv;
     return hp;
 }
 
-// the checks of aps_fast_extract, which come before any device work
-void check_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_params& prm, int desc_layout, int64_t cap) {
-    APS_REQUIRE(img, APS_E_ARG, "NULL argument");
+// the checks of the FAST entries on their group of views (the single-view entries: a group of one), which come before any device work
+void check_args(const aps_fast_view* views, int nv, int height, int width, int channels, int img_layout, const aps_fast_params& prm,
+                int desc_layout) {
+    APS_REQUIRE(views, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(nv >= 1 && nv <= kGroupViews, APS_E_ARG, "n_views must be in 1..%d", kGroupViews);
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].img, APS_E_ARG, "NULL argument");
     APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
     APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
     APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
@@ -584,7 +637,7 @@ void check_args(const uint8_t* img, int height, int width, int channels, int img
     APS_REQUIRE(prm.threshold >= 0 && prm.threshold <= 255, APS_E_ARG, "threshold (floor(MinContrast * 255)) must be in 0..255");
     APS_REQUIRE(prm.quality_den > 0 && prm.quality_den <= (1 << 24) && prm.quality_num >= 0 && prm.quality_num <= prm.quality_den, APS_E_ARG,
                 "MinQuality must be a rational in [0, 1] with a denominator of at most 2^24");
-    APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].cap >= 0 && views[v].cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
     // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
     APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
                 "FAST: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
@@ -596,29 +649,50 @@ void check_pyramid(int n_levels, int scale_num, int scale_den) {
                 "ScaleFactor = scale_num / scale_den must lie in (1, 2]");
 }
 
-// The planes and integral images of all levels, in the order of their dependences, on the calling thread's stream.
-// T: scratch of level 0's size; I: hp.integ_elems; planes: hp.plane_bytes.
-void build_levels(const uint8_t* dimg, int channels, int img_layout, const HostPlan& hp, uint8_t* planes, uint32_t* T, uint32_t* I) {
+// The planes and integral images of all levels of all views, in the order of their dependences, on the calling thread's stream: one
+// chain of launches whatever the number of views.  imgs: the views' images on the device; T: scratch of nv level-0 planes;
+// I: nv * hp.integ_elems; planes: nv * hp.plane_bytes.
+void build_levels(const ViewImgs& imgs, int channels, int img_layout, const HostPlan& hp, uint8_t* planes, uint32_t* T, uint32_t* I) {
+    const int nv = hp.dev.nv;
+    const size_t t_pitch = (size_t)hp.dev.lv[0].h * hp.dev.lv[0].w;
     for (int l = 0; l < hp.dev.n; ++l) {
         const FastLevel& L = hp.dev.lv[l];
         if (l) {
             const FastLevel& S = hp.dev.lv[l - 1];
             Prof prof("fast_resample");
-            fast_resample_kernel<<<dim3(cdiv(L.w, kRW), cdiv(L.h, kRH)), 256, 0, stream()>>>(planes + S.plane0, S.h, S.w, planes + L.plane0, L.h, L.w);
+            fast_resample_kernel<<<dim3(cdiv(L.w, kRW), cdiv(L.h, kRH), nv), 256, 0, stream()>>>(planes + S.plane0, S.h, S.w, planes + L.plane0, L.h,
+                                                                                              L.w, hp.dev.view_plane);
             check_launch("fast_resample_kernel");
         }
         Prof prof("fast_integral");
-        if (l == 0)
-            integral_image(dimg, L.h, L.w, channels, img_layout, T, I, planes);
-        else
-            integral_image(planes + L.plane0, L.h, L.w, 1, APS_IMG_U8_HWC, T, I + L.integ0, nullptr);
+        if (l == 0) {
+            integral_image(imgs, nv, L.h, L.w, channels, img_layout, T, t_pitch, I, hp.integ_elems, planes, hp.plane_bytes);
+        } else {
+            ViewImgs lv;
+            std::memset(&lv, 0, sizeof lv);
+            for (int v = 0; v < nv; ++v) lv.p[v] = planes + v * hp.plane_bytes + L.plane0;
+            integral_image(lv, nv, L.h, L.w, 1, APS_IMG_U8_HWC, T, t_pitch, I + L.integ0, hp.integ_elems, nullptr, 0);
+        }
     }
 }
 
-// What the chain holds once the candidates are known: the levels, the plane of kept scores, the candidate bitmap (bit order =
-// canonical order) and the exclusive scan of its popcounts; prefix[n_words] is the number of candidates.
+// the views' images on the device, staged where they live on the host
+struct StagedImgs {
+    std::vector<In<uint8_t>> dimg;
+    ViewImgs imgs;
+    StagedImgs(const aps_fast_view* views, int nv, size_t bytes) : dimg(nv) {
+        std::memset(&imgs, 0, sizeof imgs);
+        for (int v = 0; v < nv; ++v) {
+            dimg[v].bind(views[v].img, bytes);
+            imgs.p[v] = dimg[v];
+        }
+    }
+};
+
+// What the chain holds once the candidates are known: the levels, the plane of kept scores, the candidate bitmap (bit order = the
+// views one after the other, each in canonical order) and the exclusive scan of its popcounts; prefix[v * view_words] is the first
+// candidate of view v, prefix[n_words] the number of all.
 struct FastFront {
-    In<uint8_t> dimg;
     Ws<uint32_t> T, I;
     Ws<uint8_t> planes, kept;
     Ws<unsigned int> smax, prefix;
@@ -626,18 +700,18 @@ struct FastFront {
     const unsigned int* d_total() const { return prefix.get() + prefix.n - 1; }
 };
 
-// levels, detection, gate and scan on the calling thread's stream; no read-back
-void fast_front(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, FastFront& F) {
+// levels, detection, gate and scan of the group on the calling thread's stream; no read-back
+void fast_front(const aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, FastFront& F) {
     const FastPlan& P = hp.dev;
-    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
+    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin, nv = P.nv;
     const size_t n_words = hp.n_words;
-    F.dimg.bind(img, (size_t)H * W * channels);
-    F.T.alloc((size_t)H * W);
-    F.I.alloc(hp.integ_elems);
-    F.planes.alloc(hp.plane_bytes);
-    build_levels(F.dimg, channels, img_layout, hp, F.planes, F.T, F.I);
-    F.kept.alloc(hp.plane_bytes);
-    F.smax.alloc((size_t)P.n);
+    StagedImgs staged(views, nv, (size_t)H * W * channels);
+    F.T.alloc((size_t)nv * H * W);
+    F.I.alloc(nv * hp.integ_elems);
+    F.planes.alloc(nv * hp.plane_bytes);
+    build_levels(staged.imgs, channels, img_layout, hp, F.planes, F.T, F.I);
+    F.kept.alloc(nv * hp.plane_bytes);
+    F.smax.alloc((size_t)nv * P.n);
     F.bitmap.alloc(n_words + 1);  // (+1: a zero word, whose prefix is the total)
     F.prefix.alloc(n_words + 1);
     const Ws<uint8_t>&planes = F.planes, &kept = F.kept;
@@ -648,18 +722,9 @@ void fast_front(const uint8_t* img, int channels, int img_layout, const aps_fast
         Prof prof("fast_detect");
         fast_detect_kernel<<<hp.n_tiles, 256, 0, stream()>>>(planes, P, params->threshold, margin, kept);
         check_launch("fast_detect_kernel");
-        auto scores = rocprim::make_transform_iterator(kept.get(), U8ToU32());
-        // s_max of each level; the reductions run one after the other and share the temporary storage of the one that needs most
-        size_t lbytes[kMaxLevels], rbytes = 0;
-        for (int l = 0; l < P.n; ++l) {
-            APS_HIP(rocprim::reduce(nullptr, lbytes[l], scores + P.lv[l].plane0, smax.get() + l, 0u, (size_t)P.lv[l].h * P.lv[l].w,
-                                    rocprim::maximum<unsigned int>(), stream()));
-            rbytes = std::max(rbytes, lbytes[l]);
-        }
-        Ws<char> rtmp(rbytes);
-        for (int l = 0; l < P.n; ++l)
-            APS_HIP(rocprim::reduce(rtmp.get(), lbytes[l], scores + P.lv[l].plane0, smax.get() + l, 0u, (size_t)P.lv[l].h * P.lv[l].w,
-                                    rocprim::maximum<unsigned int>(), stream()));
+        APS_HIP(hipMemsetAsync(smax.get(), 0, (size_t)nv * P.n * sizeof(unsigned int), stream()));
+        fast_smax_kernel<<<dim3(cdiv(hp.plane_bytes, (size_t)kSmaxChunk), nv), 256, 0, stream()>>>(kept, P, smax);
+        check_launch("fast_smax_kernel");
         fast_gate_kernel<<<cdiv(n_words, 4), 256, 0, stream()>>>(kept, P, hp.n_words, smax, (unsigned int)params->quality_num,
                                                                  (unsigned int)params->quality_den, bitmap);
         check_launch("fast_gate_kernel");
@@ -670,64 +735,63 @@ void fast_front(const uint8_t* img, int channels, int img_layout, const aps_fast
     }
 }
 
-// aps_fast_extract and aps_fast_extract_pyramid behind their argument checks (check_args, check_pyramid).
-void fast_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, uint8_t* desc,
-                int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+// the rows of the views in `kps` (view v's at its record's kp0) -> every view's desc, loc and aux: one launch, the view in the grid
+void freak_describe(const HostPlan& hp, const FastFront& F, const Keypoint* kps, GroupOut<uint8_t, aps_fast_view>& out, unsigned int most) {
+    Ws<FreakDev> d_tb(1);
+    Prof prof("freak_keypoint");  // (with the upload of the pattern tables)
+    APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
+    freak_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.I, hp.dev, d_tb, F.kept, kps, out.d_rows, out.desc_layout,
+                                                                            (long long)out.ldd, (long long)out.ldl);
+    check_launch("freak_keypoint_kernel");
+}
+
+// aps_fast_extract, aps_fast_extract_pyramid and aps_fast_extract_batch behind their argument checks (check_args, check_pyramid), on
+// the plan's group of views.  One read-back: the views' counts.
+void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, int desc_layout,
+                int64_t ldd, int64_t ldl) {
     ctx();
-    *count = 0;
     const FastPlan& P = hp.dev;
-    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
+    const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin, nv = P.nv;
+    for (int v = 0; v < nv; ++v) views[v].count = 0;
+    unsigned int room[kGroupViews], n[kGroupViews];
+    check_views(views, nv, 64, desc_layout, ldd, ldl, room);
     if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
     FastFront F;
-    fast_front(img, channels, img_layout, params, hp, F);
-    const size_t n_words = hp.n_words;
-    const Ws<uint32_t>& I = F.I;
-    const Ws<uint8_t>& kept = F.kept;
-    const Ws<unsigned int>& prefix = F.prefix;
-    const Ws<unsigned long long>& bitmap = F.bitmap;
-    const unsigned int* d_total = F.d_total();
-    const bool write = cap > 0 && desc && loc;
-    const unsigned int kcap = write ? (unsigned int)cap : 0u;
-    Out<uint8_t> odesc;
-    Out<double> oloc;
-    Out<float> oaux;
-    if (write) {
-        if (desc_layout == APS_ROWMAJOR)
-            APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
-        else
-            APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
-        APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
-        odesc.bind(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
-        oloc.bind(loc, (size_t)ldl + cap);
-        oaux.bind(aux, (size_t)cap * 4);
-        Ws<Keypoint> kps((size_t)kcap);
-        Ws<FreakDev> d_tb(1);
+    fast_front(views, channels, img_layout, params, hp, F);
+    GroupOut<uint8_t, aps_fast_view> out(views, nv, room, 64, 64, desc_layout, ldd, ldl, nullptr, nullptr);
+    ViewLimits lim = {};
+    size_t kcap = 0;
+    for (int v = 0; v < nv; ++v) kcap += lim.cap[v] = room[v];
+    lim.max_features = params->max_features;
+    Ws<unsigned int> d_n(nv);
+    group_rows_kernel<uint8_t><<<1, 64, 0, stream()>>>(F.prefix, (long long)P.view_words, nv, lim, out.d_rows, d_n);
+    check_launch("group_rows_kernel");
+    if (kcap) {  // (views that fit have at most kcap keypoints between them; when one does not fit, no row is written)
+        Ws<Keypoint> kps(kcap);
         {
-            Prof prof("fast_emit");  // (with the upload of the pattern tables)
-            APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
-            fast_emit_kernel<<<cdiv(n_words, 256), 256, 0, stream()>>>(bitmap, prefix, P, hp.n_words, kps, kcap);
+            Prof prof("fast_emit");
+            fast_emit_kernel<<<cdiv(hp.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, P, hp.n_words, kps,
+                                                                          (unsigned int)std::min<size_t>(kcap, 0xffffffffu));
             check_launch("fast_emit_kernel");
         }
-        {
-            Prof prof("freak_keypoint");
-            freak_keypoint_kernel<<<cdiv(kcap, 4), 256, 0, stream()>>>(I, P, d_tb, kept, kps, d_total, kcap, odesc, desc_layout, (long long)ldd,
-                                                                      oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
-        }
-        check_launch("freak_keypoint_kernel");
+        freak_describe(hp, F, kps, out, *std::max_element(room, room + nv));
     }
-    const unsigned int n = read_back(d_total);  // the one read-back of the chain
-    *count = n;
-    if (params->max_features > 0 && n > (unsigned int)params->max_features)
-        fail(APS_E_CAP, "FAST found %u features, more than params.max_features = %d", n, params->max_features);
-    if ((int64_t)n > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n);
-    if (n == 0) return;
-    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-    if (desc_layout == APS_ROWMAJOR)
-        odesc.commit_2d(64, n, (size_t)ldd);
-    else
-        odesc.commit_2d(n, 64, (size_t)ldd);
-    oloc.commit_2d(n, 2, (size_t)ldl);
-    oaux.commit((size_t)n * 4);
+    read_back(d_n.get(), n, nv);  // the one read-back of the chain
+    settle_counts(views, nv, n, n, params->max_features, "FAST");
+    out.commit(n);
+}
+
+// the single-view entries: a group of one, *count from the view whether the chain returns or fails
+template <class Chain>
+void fast_single(const uint8_t* img, uint8_t* desc, double* loc, float* aux, int64_t cap, int64_t* count, Chain&& chain) {
+    aps_fast_view view = {img, desc, loc, aux, cap, *count};
+    try {
+        chain(&view);
+    } catch (...) {
+        *count = view.count;
+        throw;
+    }
+    *count = view.count;
 }
 
 // ---- strongest-N on the host -----------------------------------------------------------------------------------------------
@@ -780,8 +844,9 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     const FastPlan& P = hp.dev;
     const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin;
     if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
+    aps_fast_view view = {img, desc, loc, aux, cap, 0};  // (the chain's kernels take a group: this is a group of one)
     FastFront F;
-    fast_front(img, channels, img_layout, params, hp, F);
+    fast_front(&view, channels, img_layout, params, hp, F);
     Candidates Cd;
     harris_candidates(hp, F, Cd);
     const unsigned int M = Cd.M;
@@ -840,29 +905,16 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
         kresp = sel_resp;
         d_total = prefix.get() + n_words;
     }
-    Out<uint8_t> odesc(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + 64 : (size_t)63 * ldd + cap);
-    Out<double> oloc(loc, (size_t)ldl + cap);
-    Out<float> oaux(aux, (size_t)cap * 4);
-    Ws<FreakDev> d_tb(1);
-    {
-        Prof prof("freak_keypoint");  // (with the upload of the pattern tables)
-        APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
-        freak_keypoint_kernel<<<cdiv(K, 4), 256, 0, stream()>>>(F.I, P, d_tb, F.kept, kps, d_total, K, odesc, desc_layout, (long long)ldd, oloc,
-                                                                (long long)ldl, oaux.present() ? oaux.get() : nullptr);
-        check_launch("freak_keypoint_kernel");
-        if (oaux.present()) {
-            strongest_aux_kernel<<<cdiv(K, 256), 256, 0, stream()>>>(kresp, K, oaux);
-            check_launch("strongest_aux_kernel");
-        }
+    const unsigned int first = 0;
+    GroupOut<uint8_t, aps_fast_view> out(&view, 1, &K, 64, 64, desc_layout, ldd, ldl, &first, &K);
+    freak_describe(hp, F, kps, out, K);
+    if (out.aux[0].present()) {
+        strongest_aux_kernel<<<cdiv(K, 256), 256, 0, stream()>>>(kresp, K, out.aux[0]);
+        check_launch("strongest_aux_kernel");
     }
     const unsigned int n = read_back(d_total);  // the second read-back: the count the device kept is the count the host worked out
     APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
-    if (desc_layout == APS_ROWMAJOR)
-        odesc.commit_2d(64, K, (size_t)ldd);
-    else
-        odesc.commit_2d(K, 64, (size_t)ldd);
-    oloc.commit_2d(K, 2, (size_t)ldl);
-    oaux.commit((size_t)K * 4);
+    out.commit(&K);
 }
 
 }  // namespace
@@ -889,8 +941,10 @@ int aps_fast_extract(const uint8_t* img, int height, int width, int channels, in
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
-        check_args(img, height, width, channels, img_layout, *params, desc_layout, cap);
-        fast_chain(img, channels, img_layout, params, make_plan(height, width, 1, 1, 1), desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+        fast_single(img, desc, loc, aux, cap, count, [&](aps_fast_view* view) {
+            check_args(view, 1, height, width, channels, img_layout, *params, desc_layout);
+            fast_chain(view, channels, img_layout, params, make_plan(height, width, 1, 1, 1), desc_layout, ldd, ldl);
+        });
     });
 }
 
@@ -899,10 +953,23 @@ int aps_fast_extract_pyramid(const uint8_t* img, int height, int width, int chan
                              double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
-        check_args(img, height, width, channels, img_layout, params->fast, desc_layout, cap);
+        fast_single(img, desc, loc, aux, cap, count, [&](aps_fast_view* view) {
+            check_args(view, 1, height, width, channels, img_layout, params->fast, desc_layout);
+            check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+            fast_chain(view, channels, img_layout, &params->fast,
+                       make_plan(height, width, params->n_levels, params->scale_num, params->scale_den), desc_layout, ldd, ldl);
+        });
+    });
+}
+
+int aps_fast_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels, int img_layout,
+                           const aps_fast_pyramid_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        check_args(views, n_views, height, width, channels, img_layout, params->fast, desc_layout);
         check_pyramid(params->n_levels, params->scale_num, params->scale_den);
-        fast_chain(img, channels, img_layout, &params->fast, make_plan(height, width, params->n_levels, params->scale_num, params->scale_den),
-                   desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+        fast_chain(views, channels, img_layout, &params->fast,
+                   make_plan(height, width, params->n_levels, params->scale_num, params->scale_den, n_views), desc_layout, ldd, ldl);
     });
 }
 
@@ -927,7 +994,8 @@ int aps_fast_extract_strongest(const uint8_t* img, int height, int width, int ch
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
         const aps_fast_pyramid_params& pyr = params->pyramid;
         APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
-        check_args(img, height, width, channels, img_layout, pyr.fast, desc_layout, cap);
+        const aps_fast_view view = {img, desc, loc, aux, cap, 0};
+        check_args(&view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
         check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
         strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
                         params->n_strongest, 0, 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
@@ -941,7 +1009,8 @@ int aps_fast_extract_uniform(const uint8_t* img, int height, int width, int chan
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
         const aps_fast_pyramid_params& pyr = params->strongest.pyramid;
         check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
-        check_args(img, height, width, channels, img_layout, pyr.fast, desc_layout, cap);
+        const aps_fast_view view = {img, desc, loc, aux, cap, 0};
+        check_args(&view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
         check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
         strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
                         params->strongest.n_strongest, params->grid_rows, params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
@@ -966,14 +1035,15 @@ int aps_fast_harris(const uint8_t* img, int height, int width, int channels, int
                     int64_t* response, int64_t cap, int64_t* count) {
     return guarded([&] {
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
-        check_args(img, height, width, channels, img_layout, params->fast, APS_ROWMAJOR, cap);
+        const aps_fast_view view = {img, nullptr, nullptr, nullptr, cap, 0};
+        check_args(&view, 1, height, width, channels, img_layout, params->fast, APS_ROWMAJOR);
         check_pyramid(params->n_levels, params->scale_num, params->scale_den);
         const HostPlan hp = make_plan(height, width, params->n_levels, params->scale_num, params->scale_den);
         ctx();
         *count = 0;
         if (std::min(height, width) < 2 * host_pattern().margin + 1) return;
         FastFront F;
-        fast_front(img, channels, img_layout, &params->fast, hp, F);
+        fast_front(&view, channels, img_layout, &params->fast, hp, F);
         Candidates Cd;
         harris_candidates(hp, F, Cd);
         *count = Cd.M;
@@ -993,17 +1063,18 @@ int aps_fast_pyramid_planes(const uint8_t* img, int height, int width, int chann
                             const aps_fast_pyramid_params* params, uint8_t* out, int64_t cap_bytes, int64_t* bytes) {
     return guarded([&] {
         APS_REQUIRE(params && bytes, APS_E_ARG, "NULL argument");
-        check_args(img, height, width, channels, img_layout, params->fast, APS_ROWMAJOR, 0);
+        const aps_fast_view view = {img, nullptr, nullptr, nullptr, 0, 0};
+        check_args(&view, 1, height, width, channels, img_layout, params->fast, APS_ROWMAJOR);
         check_pyramid(params->n_levels, params->scale_num, params->scale_den);
         const HostPlan hp = make_plan(height, width, params->n_levels, params->scale_num, params->scale_den);
         *bytes = (int64_t)hp.plane_bytes;
         if (!out) return;  // (the size alone: no device work)
         APS_REQUIRE(cap_bytes >= *bytes, APS_E_CAP, "plane capacity %lld < %lld bytes", (long long)cap_bytes, (long long)*bytes);
         ctx();
-        In<uint8_t> dimg(img, (size_t)height * width * channels);
+        StagedImgs staged(&view, 1, (size_t)height * width * channels);
         Ws<uint32_t> T((size_t)height * width), I(hp.integ_elems);
         Out<uint8_t> planes(out, hp.plane_bytes);
-        build_levels(dimg, channels, img_layout, hp, planes, T, I);
+        build_levels(staged.imgs, channels, img_layout, hp, planes, T, I);
         planes.commit();
         APS_HIP(hipStreamSynchronize(stream()));
     });

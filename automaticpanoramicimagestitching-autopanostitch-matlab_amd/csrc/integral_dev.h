@@ -4,6 +4,8 @@
 //                             (workgroup per row, carried across 1024-px chunks)
 //   integral_colscan_kernel   column prefix sums inside chunks of 64 rows, in place
 //   integral_colcarry_kernel  adds the totals of the chunks above and writes the (h+1) x (w+1) integral image
+// Every launch works on a group of 1 .. kGroupViews images of one shape: the view is the last grid dimension, and the view's
+// image comes from a table of pointers, its scratch, integral image and gray plane from a pitch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,12 @@ namespace aps {
 namespace {
 
 constexpr int kColChunk = 64;  // rows per chunk of the column scan
+constexpr int kGroupViews = 16;  // views of one call (APS_SURF_MAX_VIEWS, APS_FAST_MAX_VIEWS)
+
+// the images of a group, one device pointer per view (a kernel argument, by value)
+struct ViewImgs {
+    const uint8_t* p[kGroupViews];
+};
 
 // the caller's check: the whole image at full brightness has to fit the 32-bit sums
 inline bool integral_fits(int height, int width) { return (uint64_t)height * (uint64_t)width * 255u < ((uint64_t)1 << 32); }
@@ -29,10 +37,14 @@ __device__ __forceinline__ uint32_t gray_at(const uint8_t* __restrict__ img, int
 
 // T[y][x] = sum of gray[y][0..x]: one workgroup per row, 4 pixels per thread and pass, the running total carried from pass to pass.
 // gray, if not NULL, receives the h x w row-major gray plane itself.
-__global__ __launch_bounds__(256) void integral_rowscan_kernel(const uint8_t* __restrict__ img, int h, int w, int c, int layout,
-                                                               uint32_t* __restrict__ T, uint8_t* __restrict__ gray) {
+__global__ __launch_bounds__(256) void integral_rowscan_kernel(const ViewImgs imgs, int h, int w, int c, int layout,
+                                                               uint32_t* __restrict__ T, size_t t_pitch, uint8_t* __restrict__ gray,
+                                                               size_t gray_pitch) {
     __shared__ uint32_t s_tot[2][4];
     const int y = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint8_t* __restrict__ img = imgs.p[blockIdx.y];
+    T += blockIdx.y * t_pitch;
+    if (gray) gray += blockIdx.y * gray_pitch;
     uint32_t carry = 0;
     int it = 0;
     for (int x0 = 0; x0 < w; x0 += 1024, ++it) {
@@ -71,9 +83,10 @@ __global__ __launch_bounds__(256) void integral_rowscan_kernel(const uint8_t* __
 }
 
 // Column prefix sums inside each chunk of kColChunk rows, in place.
-__global__ __launch_bounds__(256) void integral_colscan_kernel(uint32_t* __restrict__ T, int h, int w) {
+__global__ __launch_bounds__(256) void integral_colscan_kernel(uint32_t* __restrict__ T, size_t t_pitch, int h, int w) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= w) return;
+    T += blockIdx.z * t_pitch;
     const int y0 = blockIdx.y * kColChunk, y1 = min(h, y0 + kColChunk);
     uint32_t acc = 0;
     for (int y = y0; y < y1; ++y) {
@@ -82,10 +95,17 @@ __global__ __launch_bounds__(256) void integral_colscan_kernel(uint32_t* __restr
     }
 }
 
-// I[y+1][x+1] = T[y][x] + the last rows of the chunks above; column 0 of I is written here, row 0 by the caller's memset.
-__global__ __launch_bounds__(256) void integral_colcarry_kernel(const uint32_t* __restrict__ T, int h, int w, uint32_t* __restrict__ I) {
+// I[y+1][x+1] = T[y][x] + the last rows of the chunks above; column 0 of I and, by the first chunk, row 0 are written here.
+__global__ __launch_bounds__(256) void integral_colcarry_kernel(const uint32_t* __restrict__ T, size_t t_pitch, int h, int w,
+                                                                uint32_t* __restrict__ I, size_t i_pitch) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= w) return;
+    T += blockIdx.z * t_pitch;
+    I += blockIdx.z * i_pitch;
+    if (blockIdx.y == 0) {
+        I[x + 1] = 0u;
+        if (x == 0) I[0] = 0u;
+    }
     const int y0 = blockIdx.y * kColChunk, y1 = min(h, y0 + kColChunk);
     uint32_t carry = 0;
     for (int k = 0; k < (int)blockIdx.y; ++k) carry += T[(size_t)(k * kColChunk + kColChunk - 1) * w + x];
@@ -96,16 +116,16 @@ __global__ __launch_bounds__(256) void integral_colcarry_kernel(const uint32_t* 
     }
 }
 
-// The three launches on the calling thread's stream: T is H x W scratch, I receives the (H+1) x (W+1) integral image,
-// gray (H x W, or NULL) the gray plane.
-inline void integral_image(const uint8_t* dimg, int H, int W, int channels, int img_layout, uint32_t* T, uint32_t* I, uint8_t* gray) {
-    integral_rowscan_kernel<<<H, 256, 0, stream()>>>(dimg, H, W, channels, img_layout, T, gray);
+// The three launches on the calling thread's stream, for nv views: view v reads imgs.p[v], uses T + v * t_pitch (H x W scratch) and
+// receives the (H+1) x (W+1) integral image at I + v * i_pitch and, with gray not NULL, the H x W gray plane at gray + v * gray_pitch.
+inline void integral_image(const ViewImgs& imgs, int nv, int H, int W, int channels, int img_layout, uint32_t* T, size_t t_pitch,
+                           uint32_t* I, size_t i_pitch, uint8_t* gray, size_t gray_pitch) {
+    integral_rowscan_kernel<<<dim3(H, nv), 256, 0, stream()>>>(imgs, H, W, channels, img_layout, T, t_pitch, gray, gray_pitch);
     check_launch("integral_rowscan_kernel");
-    const dim3 cg(cdiv(W, 256), cdiv(H, kColChunk));
-    integral_colscan_kernel<<<cg, 256, 0, stream()>>>(T, H, W);
+    const dim3 cg(cdiv(W, 256), cdiv(H, kColChunk), nv);
+    integral_colscan_kernel<<<cg, 256, 0, stream()>>>(T, t_pitch, H, W);
     check_launch("integral_colscan_kernel");
-    APS_HIP(hipMemsetAsync(I, 0, ((size_t)W + 1) * sizeof(uint32_t), stream()));
-    integral_colcarry_kernel<<<cg, 256, 0, stream()>>>(T, H, W, I);
+    integral_colcarry_kernel<<<cg, 256, 0, stream()>>>(T, t_pitch, H, W, I, i_pitch);
     check_launch("integral_colcarry_kernel");
 }
 

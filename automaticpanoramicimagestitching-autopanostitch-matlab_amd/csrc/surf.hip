@@ -7,21 +7,25 @@
 // elsewhere, Gaussian weights and window directions from host tables (f64 -> f32), and no device transcendental in any
 // stored value or discrete decision (atan2f only feeds aux's angle_deg).
 //
-// Chain of one call (no host read-back until the final count; every grid is a capacity grid):
+// A call works on a group of 1 .. 16 views of one shape (aps_surf_extract_batch; the single-view entries are groups of one): every
+// stage below is one launch for the group, with the view as the last grid dimension or decoded from the packed word's offset.
+// The integral images lie one after the other, the candidate bitmap is packed [view][octave][level][row][word].
+// Chain of one call (no host read-back until the final counts; every grid is a capacity grid):
 //   integral_image        gray plane and the exact 32-bit integral image (integral_dev.h: row scan, column scan, column carry)
 //   surf_detect_kernel   per octave: all levels of a 64 x 8 tile (+1 halo) into LDS, threshold, strict 3x3x3 maximum and the
 //                         refinement's verdict; one ballot = one 64-bit word of the candidate bitmap, whose bit order IS the
-//                         canonical feature order (octave, level, row, col)
-//   exclusive scan of the words' popcounts (rocprim), surf_emit_kernel (ordered compaction, no atomics)
+//                         canonical feature order (octave, level, row, col) within the view
+//   exclusive scan of all views' words' popcounts (rocprim), surf_emit_kernel (ordered compaction, no atomics)
+//   group_rows_kernel     (group_dev.h) every view's count, first keypoint and rows to write: all views' or, if one does not fit, none
 //   surf_keypoint_kernel  one wave per keypoint: the 27 responses again, refinement, orientation, descriptor, outputs
-// aps_surf_extract_strongest (DESIGN.md "Strongest-N for SIFT and SURF") shares the chain up to the scan, reads the candidate count
-// back, and goes on with grids of the candidates' size:
-//   surf_emit_kernel      the candidate list
-//   surf_metric_kernel    the centre response of every candidate = its metric, as the sort key
+// aps_surf_extract_strongest and aps_surf_extract_batch_strongest (DESIGN.md "Strongest-N for SIFT and SURF") share the chain up to
+// the scan, read the views' candidate counts back, and go on with grids of the candidates' size:
+//   surf_emit_kernel      the candidate list, the views' one after the other
+//   surf_metric_kernel    the centre response of every candidate = its metric, as the sort key under the view = the selection's group
 //   select_by_key         (select_dev.h) stable radix sort, flags, ballot words, scan; select_compact_kernel (canonical order again)
 //   surf_keypoint_kernel  on the kept keypoints only
-// aps_surf_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with surf_uniform_key_kernel and select_uniform in the place
-// of surf_metric_kernel and select_by_key.
+// aps_surf_extract_uniform and aps_surf_extract_batch_uniform (DESIGN.md "Uniform-N selection") are that chain with
+// surf_uniform_key_kernel and select_uniform in the place of surf_metric_kernel and select_by_key.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +33,7 @@
 #include <cstring>
 
 #include "aps_internal.h"
+#include "group_dev.h"
 #include "integral_dev.h"
 #include "select_dev.h"
 
@@ -50,8 +55,15 @@ struct SurfOct {
 };
 struct SurfPlan {
     int n_oct, nlv, h, w;
+    long long n_words;      // bitmap words of one view
+    size_t integ_pitch;     // elements of one view's (h + 1) x (w + 1) integral image
     SurfOct oct[kMaxOct];
 };
+static_assert(kGroupViews == APS_SURF_MAX_VIEWS && kGroupViews <= kSelectGroups, "a view is a group of the selection (select_dev.h)");
+
+// a keypoint of the group as the lists hold it: (octave | view << 16, level, row, col) of its detection sample
+__device__ __forceinline__ int kp_octave(const int4 kp) { return kp.x & 0xffff; }
+__device__ __forceinline__ int kp_view(const int4 kp) { return kp.x >> 16; }
 
 // host tables (f64 -> f32), uploaded with every call
 struct SurfTables {
@@ -130,10 +142,12 @@ __device__ __forceinline__ bool surf_refine(const A& a, float& ox, float& oy, fl
     return fabsf(ox) <= 1.0f && fabsf(oy) <= 1.0f && fabsf(os) <= 1.0f;
 }
 
-__global__ __launch_bounds__(256) void surf_detect_kernel(const uint32_t* __restrict__ I, int h, int w, SurfOct oc, int nlv, float thr,
-                                                          unsigned long long* __restrict__ bitmap) {
+__global__ __launch_bounds__(256) void surf_detect_kernel(const uint32_t* __restrict__ I, size_t integ_pitch, int h, int w, SurfOct oc, int nlv,
+                                                          float thr, unsigned long long* __restrict__ bitmap, long long n_words) {
     __shared__ float R[kMaxLev][kTH + 2][kTW + 2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    I += blockIdx.z * integ_pitch;  // (the view)
+    bitmap += blockIdx.z * n_words;
     const int j0 = blockIdx.x * kTW - 1, i0 = blockIdx.y * kTH - 1;
     constexpr int kTile = (kTH + 2) * (kTW + 2);
     for (int e = tid; e < nlv * kTile; e += 256) {
@@ -175,7 +189,8 @@ __global__ __launch_bounds__(256) void surf_detect_kernel(const uint32_t* __rest
     }
 }
 
-// Ordered compaction: bit k of word q becomes keypoint prefix[q] + (set bits below k) as (octave, level, row, col).
+// Ordered compaction: bit k of word q (of n_words, all views') becomes keypoint prefix[q] + (set bits below k) as
+// (octave | view << 16, level, row, col); the view and the octave are decoded from the word's offset.
 __global__ __launch_bounds__(256) void surf_emit_kernel(const unsigned long long* __restrict__ bitmap, const unsigned int* __restrict__ prefix,
                                                         long long n_words, SurfPlan plan, int4* __restrict__ kps, unsigned int kcap) {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -183,15 +198,17 @@ __global__ __launch_bounds__(256) void surf_emit_kernel(const unsigned long long
     unsigned long long bits = bitmap[q];
     if (!bits) return;
     unsigned int pos = prefix[q];
+    const int view = (int)(q / plan.n_words);
+    const long long qv = q - view * plan.n_words;
     int o = 0;
-    while (o + 1 < plan.n_oct && q >= plan.oct[o + 1].word0) ++o;
+    while (o + 1 < plan.n_oct && qv >= plan.oct[o + 1].word0) ++o;
     const SurfOct& oc = plan.oct[o];
-    const long long rel = q - oc.word0;
+    const long long rel = qv - oc.word0;
     const int jw = (int)(rel % oc.wpr), row = (int)(rel / oc.wpr), i = row % oc.gh, m = 1 + row / oc.gh;
     while (bits) {
         const int k = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
-        if (pos < kcap) kps[pos] = make_int4(o, m, i, jw * 64 + k);
+        if (pos < kcap) kps[pos] = make_int4(o | view << 16, m, i, jw * 64 + k);
         ++pos;
     }
 }
@@ -209,21 +226,25 @@ __device__ __forceinline__ bool haar(const uint32_t* __restrict__ I, int h, int 
     return true;
 }
 
-// One wave per keypoint.  Every wave of the capacity grid passes every barrier; the ones beyond the count do no work.
+// One wave per keypoint; blockIdx.y is the view, whose record says where its keypoints start and how many rows it writes.  Every
+// wave of the capacity grid passes every barrier; the ones beyond the view's rows do no work.
 __global__ __launch_bounds__(256) void surf_keypoint_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const SurfTables* __restrict__ tb,
-                                                            const int4* __restrict__ kps, const unsigned int* __restrict__ d_total,
-                                                            unsigned int kcap, int upright, float* __restrict__ desc, int desc_layout,
-                                                            long long ldd, double* __restrict__ loc, long long ldl, float* __restrict__ aux) {
+                                                            const int4* __restrict__ kps, const ViewRows<float>* __restrict__ views,
+                                                            int upright, int desc_layout, long long ldd, long long ldl) {
     __shared__ float s_a[4][32];
     __shared__ float s_x[4][400], s_y[4][400];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned int kidx = blockIdx.x * 4 + wave;
-    const unsigned int total = min(*d_total, kcap);
-    const bool active = kidx < total;
+    const ViewRows<float> V = views[blockIdx.y];
+    const unsigned int kidx = blockIdx.x * 4 + wave;  // the row of the view
+    const bool active = kidx < V.rows;
+    float* __restrict__ desc = V.desc;
+    double* __restrict__ loc = V.loc;
+    float* __restrict__ aux = V.aux;
+    I += blockIdx.y * plan.integ_pitch;
     const int h = plan.h, w = plan.w;
     int4 kp = make_int4(0, 1, 0, 0);
-    if (active) kp = kps[kidx];
-    const SurfOct& oc = plan.oct[kp.x];
+    if (active) kp = kps[V.kp0 + kidx];
+    const SurfOct& oc = plan.oct[kp_octave(kp)];
     const int m = kp.y;
     float ctr_trace = 0.0f;
     if (active && lane < 27) {
@@ -336,40 +357,44 @@ __global__ __launch_bounds__(256) void surf_keypoint_kernel(const uint32_t* __re
 
 // ---- strongest-N (DESIGN.md "Strongest-N for SIFT and SURF") ----------------------------------------------------------------
 // The metric of every candidate: the centre response, s_a[wave][13] of surf_keypoint_kernel - the same device function on the same
-// operands, so the same bits - as the selection's key (select_dev.h: one group), and the candidate's index as the sort's value.
+// operands, so the same bits - as the selection's key (select_dev.h: the view is the group), and the candidate's index as the sort's value.
 __device__ __forceinline__ float surf_metric(const uint32_t* __restrict__ I, const SurfPlan& plan, const int4 kp) {
-    const SurfOct& oc = plan.oct[kp.x];
+    const SurfOct& oc = plan.oct[kp_octave(kp)];
     const int m = kp.y;
     float tr;
-    return surf_response(I, plan.h, plan.w, kp.z * oc.step, kp.w * oc.step, oc.size[m], oc.inv[m], oc.inv_xy[m], &tr);
+    return surf_response(I + kp_view(kp) * plan.integ_pitch, plan.h, plan.w, kp.z * oc.step, kp.w * oc.step, oc.size[m], oc.inv[m], oc.inv_xy[m], &tr);
 }
 __global__ __launch_bounds__(256) void surf_metric_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const int4* __restrict__ cand,
                                                           unsigned int n, unsigned long long* __restrict__ keys,
                                                           unsigned int* __restrict__ vals) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    keys[i] = strength_key_f32(surf_metric(I, plan, cand[i]));
+    const int4 kp = cand[i];
+    keys[i] = (unsigned long long)kp_view(kp) << 60 | strength_key_f32(surf_metric(I, plan, kp));
     vals[i] = i;
 }
 
-// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the candidate's segment = the cell of its detection sample
-// (i * step, j * step), the unrefined one that surf_emit_kernel lists, in the rows x cols grid over the image.
+// Uniform-N (DESIGN.md "Uniform-N selection"): the same key under the candidate's segment = view * cells + the cell of its detection
+// sample (i * step, j * step), the unrefined one that surf_emit_kernel lists, in the rows x cols grid over the image.
 __global__ __launch_bounds__(256) void surf_uniform_key_kernel(const uint32_t* __restrict__ I, SurfPlan plan, const int4* __restrict__ cand,
                                                                unsigned int n, int rows, int cols, unsigned long long* __restrict__ keys,
                                                                unsigned int* __restrict__ vals) {
     const unsigned int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int4 kp = cand[i];
-    const int step = plan.oct[kp.x].step;
-    keys[i] = (unsigned long long)uniform_cell(kp.z * step, kp.w * step, plan.h, plan.w, rows, cols) << kSegmentShift |
+    const int step = plan.oct[kp_octave(kp)].step;
+    const unsigned int cell = (unsigned int)uniform_cell(kp.z * step, kp.w * step, plan.h, plan.w, rows, cols);
+    keys[i] = (unsigned long long)(kp_view(kp) * rows * cols + cell) << kSegmentShift |
               strength_key_f32(surf_metric(I, plan, kp));
     vals[i] = i;
 }
 
-// the checks of aps_surf_extract, which come before any device work
-void check_args(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_surf_params* params, int desc_layout,
-                int64_t cap, const int64_t* count) {
-    APS_REQUIRE(img && params && count, APS_E_ARG, "NULL argument");
+// the checks of the SURF entries, which come before any device work
+void check_args(const aps_surf_view* views, int nv, int height, int width, int channels, int img_layout, const aps_surf_params* params,
+                int desc_layout) {
+    APS_REQUIRE(views && params, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(nv >= 1 && nv <= kGroupViews, APS_E_ARG, "n_views must be in 1..%d", kGroupViews);
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].img, APS_E_ARG, "NULL argument");
     APS_REQUIRE(height > 0 && width > 0, APS_E_DIM, "empty image");
     APS_REQUIRE(channels == 1 || channels == 3, APS_E_DIM, "channels must be 1 or 3");
     APS_REQUIRE(img_layout == APS_IMG_U8_HWC || img_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown image layout");
@@ -377,26 +402,27 @@ void check_args(const uint8_t* img, int height, int width, int channels, int img
     APS_REQUIRE(params->n_octaves >= 1 && params->n_octaves <= kMaxOct, APS_E_ARG, "NumOctaves must be in 1..%d", kMaxOct);
     APS_REQUIRE(params->n_scale_levels >= 3 && params->n_scale_levels <= kMaxLev, APS_E_ARG, "NumScaleLevels must be in 3..%d", kMaxLev);
     APS_REQUIRE(params->metric_threshold >= 0, APS_E_ARG, "MetricThreshold must be >= 0");
-    APS_REQUIRE(cap >= 0 && cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(views[v].cap >= 0 && views[v].cap < (int64_t)1 << 31, APS_E_ARG, "capacity out of range");
     // the integral image holds exact 32-bit sums: the whole image at full brightness has to fit
     APS_REQUIRE(integral_fits(height, width), APS_E_ARG,
                 "SURF: %d x %d pixels exceed the 32-bit integral image (height * width * 255 must stay below 2^32)", height, width);
 }
 
-// What both entries hold once the candidates are known: the integral image, the candidate bitmap (bit order = canonical order) and
-// the exclusive scan of its popcounts; prefix[n_words] is the number of candidates.
+// What every entry holds once the candidates are known: the views' integral images, the candidate bitmap (bit order = the views one
+// after the other, each in canonical order) and the exclusive scan of its popcounts; prefix[v * plan.n_words] is the first candidate
+// of view v, prefix[n_words] the number of all.
 struct SurfFront {
     SurfPlan plan;
-    long long n_words = 0;
-    In<uint8_t> dimg;
+    long long n_words = 0;  // of all views
+    std::vector<In<uint8_t>> dimg;
     Ws<uint32_t> T, I;
     Ws<unsigned long long> bitmap;
     Ws<unsigned int> prefix;
-    const unsigned int* d_total() const { return prefix.get() + n_words; }
 };
 
-// plan, integral image, detection and scan on the calling thread's stream; no read-back.  false: smaller than the first octave's support.
-bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, const aps_surf_params* params, SurfFront& F) {
+// plan, integral images, detection and scan of the group on the calling thread's stream; no read-back.  false: smaller than the first
+// octave's support.
+bool surf_front(const aps_surf_view* views, int nv, int H, int W, int channels, int img_layout, const aps_surf_params* params, SurfFront& F) {
     const int nlv = params->n_scale_levels;
     // plan: octaves whose largest filter fits
     SurfPlan& plan = F.plan;
@@ -404,6 +430,7 @@ bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, 
     plan.nlv = nlv;
     plan.h = H;
     plan.w = W;
+    plan.integ_pitch = (size_t)(H + 1) * (W + 1);
     long long n_words = 0;
     for (int o = 1; o <= params->n_octaves; ++o) {
         const long long top = 3ll * ((1ll << o) * nlv + 1);
@@ -422,103 +449,188 @@ bool surf_front(const uint8_t* img, int H, int W, int channels, int img_layout, 
         oc.word0 = n_words;
         n_words += (long long)(nlv - 2) * oc.gh * oc.wpr;
     }
-    F.n_words = n_words;
+    plan.n_words = n_words;
+    F.n_words = n_words * nv;
     if (plan.n_oct == 0) return false;
-    F.dimg.bind(img, (size_t)H * W * channels);
-    F.T.alloc((size_t)H * W);
-    F.I.alloc((size_t)(H + 1) * (W + 1));
+    ViewImgs imgs;
+    std::memset(&imgs, 0, sizeof imgs);
+    F.dimg = std::vector<In<uint8_t>>(nv);
+    for (int v = 0; v < nv; ++v) {
+        F.dimg[v].bind(views[v].img, (size_t)H * W * channels);
+        imgs.p[v] = F.dimg[v];
+    }
+    const size_t t_pitch = (size_t)H * W;
+    F.T.alloc(nv * t_pitch);
+    F.I.alloc(nv * plan.integ_pitch);
     {
         Prof prof("surf_integral");
-        integral_image(F.dimg, H, W, channels, img_layout, F.T, F.I, nullptr);
+        integral_image(imgs, nv, H, W, channels, img_layout, F.T, t_pitch, F.I, plan.integ_pitch, nullptr, 0);
     }
-    F.bitmap.alloc((size_t)n_words + 1);  // (+1: a zero word, whose prefix is the total)
-    F.prefix.alloc((size_t)n_words + 1);
-    APS_HIP(hipMemsetAsync(F.bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
+    F.bitmap.alloc((size_t)F.n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    F.prefix.alloc((size_t)F.n_words + 1);
+    APS_HIP(hipMemsetAsync(F.bitmap.get() + F.n_words, 0, sizeof(unsigned long long), stream()));
     {
         Prof prof("surf_detect");
         for (int o = 0; o < plan.n_oct; ++o) {
             const SurfOct& oc = plan.oct[o];
-            surf_detect_kernel<<<dim3(oc.wpr, cdiv(oc.gh, kTH)), 256, 0, stream()>>>(F.I, H, W, oc, nlv, (float)params->metric_threshold, F.bitmap);
+            surf_detect_kernel<<<dim3(oc.wpr, cdiv(oc.gh, kTH), nv), 256, 0, stream()>>>(F.I, plan.integ_pitch, H, W, oc, nlv,
+                                                                                       (float)params->metric_threshold, F.bitmap, n_words);
         }
         check_launch("surf_detect_kernel");
     }
-    exclusive_scan(popcounts(F.bitmap.get()), F.prefix.get(), 0u, (size_t)n_words + 1);
+    exclusive_scan(popcounts(F.bitmap.get()), F.prefix.get(), 0u, (size_t)F.n_words + 1);
     return true;
 }
 
-// aps_surf_extract_strongest and, with grid_rows > 0, aps_surf_extract_uniform behind their argument checks.  Two read-backs: the
-// candidate count, which sizes the grids and the sort below, then the final count.
-void surf_strongest_chain(const uint8_t* img, int H, int W, int channels, int img_layout, const aps_surf_params* params, long long N,
-                          int grid_rows, int grid_cols, float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
-    ctx();
-    *count = 0;
-    SurfFront F;
-    if (!surf_front(img, H, W, channels, img_layout, params, F)) return;
-    const unsigned int M = read_back(F.d_total());  // the first read-back: the candidates
-    const unsigned int K = (unsigned int)std::min<long long>(M, N);
-    *count = K;
-    if (params->max_features > 0 && M > (unsigned int)params->max_features) {
-        *count = M;
-        fail(APS_E_CAP, "SURF found %u features, more than params.max_features = %d", M, params->max_features);
-    }
-    if ((int64_t)K > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, K);
-    if (K == 0) return;
-    APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-    if (desc_layout == APS_ROWMAJOR)
-        APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
-    else
-        APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
-    APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
-    Ws<int4> cand(M), sel;
-    surf_emit_kernel<<<cdiv((size_t)F.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, F.n_words, F.plan, cand, M);
-    check_launch("surf_emit_kernel");
-    // the kept keypoints, in canonical order
-    Ws<unsigned long long> keys, words;
-    Ws<unsigned int> vals, prefix;
-    const int4* kps = cand;
-    const unsigned int* d_total = F.d_total();
-    if (K < M) {
-        Prof prof("surf_select");
-        keys.alloc(M);
-        vals.alloc(M);
-        unsigned int n_words = 0;
-        if (grid_rows > 0) {  // uniform-N: the candidates that come first in their cell, the cells' shares by water-filling K
-            surf_uniform_key_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, grid_rows, grid_cols, keys, vals);
-            check_launch("surf_uniform_key_kernel");
-            UniformBudget budget = {};
-            budget.q[0] = K;
-            select_uniform(keys, nullptr, vals, M, 1u, (unsigned int)(grid_rows * grid_cols), budget, words, prefix, n_words);
-        } else {
-            surf_metric_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.I, F.plan, cand, M, keys, vals);
-            check_launch("surf_metric_kernel");
-            select_by_key(keys, vals, M, single_group_cut(M, K), words, prefix, n_words, 32u);
-        }
-        sel.alloc(K);
-        select_compact_kernel<int4><<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, M, sel, K);
-        check_launch("select_compact_kernel");
-        kps = sel;
-        d_total = prefix.get() + n_words;
-    }
-    const size_t dwidth = desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64;
-    Out<float> odesc(desc, desc_layout == APS_ROWMAJOR ? (size_t)(K - 1) * ldd + dwidth : (size_t)63 * ldd + K);
-    Out<double> oloc(loc, (size_t)ldl + K);
-    Out<float> oaux(aux, (size_t)K * 4);
+// the rows of the views in `kps` (view v's at its record's kp0) -> every view's desc, loc and aux: one launch, the view in the grid
+void surf_describe(const SurfFront& F, const int4* kps, GroupOut<float, aps_surf_view>& out, unsigned int most, int upright) {
     Ws<SurfTables> d_tb(1);
     APS_HIP(hipMemcpyAsync(d_tb, &host_tables(), sizeof(SurfTables), hipMemcpyHostToDevice, stream()));
     {
         Prof prof("surf_keypoint");
-        surf_keypoint_kernel<<<cdiv(K, 4), 256, 0, stream()>>>(F.I, F.plan, d_tb, kps, d_total, K, params->upright ? 1 : 0, odesc, desc_layout,
-                                                              (long long)ldd, oloc, (long long)ldl, oaux.present() ? oaux.get() : nullptr);
+        surf_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.I, F.plan, d_tb, kps, out.d_rows, upright, out.desc_layout,
+                                                                               (long long)out.ldd, (long long)out.ldl);
     }
     check_launch("surf_keypoint_kernel");
-    const unsigned int n = read_back(d_total);  // the second read-back: the count the device kept is the count the host worked out
-    APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
-    if (desc_layout == APS_ROWMAJOR)
-        odesc.commit_2d(dwidth, K, (size_t)ldd);
-    else
-        odesc.commit_2d(K, 64, (size_t)ldd);
-    oloc.commit_2d(K, 2, (size_t)ldl);
-    oaux.commit((size_t)K * 4);
+}
+
+inline size_t surf_row_width(int desc_layout, int64_t ldd) { return desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64; }
+
+// aps_surf_extract and aps_surf_extract_batch behind their argument checks, on a group of nv views.  One read-back: the views' counts.
+void surf_chain(aps_surf_view* views, int nv, int H, int W, int channels, int img_layout, const aps_surf_params* params, int desc_layout,
+                int64_t ldd, int64_t ldl) {
+    ctx();
+    for (int v = 0; v < nv; ++v) views[v].count = 0;
+    unsigned int room[kGroupViews], n[kGroupViews];
+    check_views(views, nv, 64, desc_layout, ldd, ldl, room);
+    SurfFront F;
+    if (!surf_front(views, nv, H, W, channels, img_layout, params, F)) return;  // smaller than the first octave's support: no features, no error
+    GroupOut<float, aps_surf_view> out(views, nv, room, 64, surf_row_width(desc_layout, ldd), desc_layout, ldd, ldl, nullptr, nullptr);
+    ViewLimits lim = {};
+    size_t kcap = 0;
+    for (int v = 0; v < nv; ++v) kcap += lim.cap[v] = room[v];
+    lim.max_features = params->max_features;
+    Ws<unsigned int> d_n(nv);
+    group_rows_kernel<float><<<1, 64, 0, stream()>>>(F.prefix, F.plan.n_words, nv, lim, out.d_rows, d_n);
+    check_launch("group_rows_kernel");
+    if (kcap) {  // (views that fit have at most kcap keypoints between them; when one does not fit, no row is written)
+        Ws<int4> kps(kcap);
+        surf_emit_kernel<<<cdiv((size_t)F.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, F.n_words, F.plan, kps,
+                                                                             (unsigned int)std::min<size_t>(kcap, 0xffffffffu));
+        check_launch("surf_emit_kernel");
+        surf_describe(F, kps, out, *std::max_element(room, room + nv), params->upright ? 1 : 0);
+    }
+    read_back(d_n.get(), n, nv);  // the one read-back of the chain
+    settle_counts(views, nv, n, n, params->max_features, "SURF");
+    out.commit(n);
+}
+
+// The selection entries behind their argument checks, on a group of nv views: of every view its N strongest candidates, or with
+// grid_rows > 0 N spread over the cells of its grid.  Two read-backs: the views' candidate counts, which size the grids and the sort
+// below, then the counts the device kept.
+void surf_select_chain(aps_surf_view* views, int nv, int H, int W, int channels, int img_layout, const aps_surf_params* params, long long N,
+                       int grid_rows, int grid_cols, int desc_layout, int64_t ldd, int64_t ldl) {
+    ctx();
+    for (int v = 0; v < nv; ++v) views[v].count = 0;
+    unsigned int room[kGroupViews], M[kGroupViews], K[kGroupViews], row0[kGroupViews], kept[kGroupViews];
+    check_views(views, nv, 64, desc_layout, ldd, ldl, room);
+    SurfFront F;
+    if (!surf_front(views, nv, H, W, channels, img_layout, params, F)) return;
+    Ws<unsigned int> d_n(nv);
+    view_counts_kernel<<<1, 64, 0, stream()>>>(F.prefix, F.plan.n_words, nv, d_n);
+    check_launch("view_counts_kernel");
+    read_back(d_n.get(), M, nv);  // the first read-back: the candidates
+    ViewOffsets off = {};
+    unsigned int Kt = 0, most = 0;
+    bool cut = false;
+    for (int v = 0; v < kGroupViews; ++v) {
+        if (v < nv) {
+            K[v] = (unsigned int)std::min<long long>(M[v], N);
+            row0[v] = Kt;
+            Kt += K[v];
+            most = std::max(most, K[v]);
+            cut = cut || K[v] < M[v];
+        }
+        off.off[v + 1] = off.off[v] + (v < nv ? M[v] : 0u);
+    }
+    settle_counts(views, nv, K, M, params->max_features, "SURF");
+    if (Kt == 0) return;
+    const unsigned int Mt = off.off[nv];
+    Ws<int4> cand(Mt), sel;
+    surf_emit_kernel<<<cdiv((size_t)F.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, F.n_words, F.plan, cand, Mt);
+    check_launch("surf_emit_kernel");
+    // the kept keypoints, the views one after the other, each in canonical order
+    const int4* kps = cand;
+    if (cut) {  // (a view that keeps all its candidates goes through the selection with them as its budget)
+        Prof prof("surf_select");
+        Ws<unsigned long long> keys(Mt), words;
+        Ws<unsigned int> vals(Mt), prefix;
+        unsigned int n_words = 0;
+        if (grid_rows > 0) {  // uniform-N: the candidates that come first in their cell, the cells' shares by water-filling K
+            surf_uniform_key_kernel<<<cdiv(Mt, 256), 256, 0, stream()>>>(F.I, F.plan, cand, Mt, grid_rows, grid_cols, keys, vals);
+            check_launch("surf_uniform_key_kernel");
+            UniformBudget budget = {};
+            for (int v = 0; v < nv; ++v) budget.q[v] = K[v];
+            select_uniform(keys, nullptr, vals, Mt, (unsigned int)nv, (unsigned int)(grid_rows * grid_cols), budget, words, prefix, n_words);
+        } else {
+            surf_metric_kernel<<<cdiv(Mt, 256), 256, 0, stream()>>>(F.I, F.plan, cand, Mt, keys, vals);
+            check_launch("surf_metric_kernel");
+            StrongestCut c;
+            for (int g = 0; g < kSelectGroups; ++g) {
+                c.start[g] = g < nv ? off.off[g] : Mt;
+                c.keep[g] = g < nv ? K[g] : 0u;
+            }
+            select_by_key(keys, vals, Mt, c, words, prefix, n_words, nv > 1 ? 64u : 32u);
+        }
+        sel.alloc(Kt);
+        select_compact_kernel<int4><<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, Mt, sel, Kt);
+        check_launch("select_compact_kernel");
+        view_kept_kernel<<<1, 64, 0, stream()>>>(words, prefix, off, nv, d_n);
+        check_launch("view_kept_kernel");
+        kps = sel;
+    }
+    GroupOut<float, aps_surf_view> out(views, nv, K, 64, surf_row_width(desc_layout, ldd), desc_layout, ldd, ldl, row0, K);
+    surf_describe(F, kps, out, most, params->upright ? 1 : 0);
+    read_back(d_n.get(), kept, nv);  // the second read-back: the counts the device kept are the counts the host worked out
+    for (int v = 0; v < nv; ++v) APS_REQUIRE(kept[v] == K[v], APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", kept[v], K[v]);
+    out.commit(K);
+}
+
+// the single-view entries: a group of one, *count from the view whether the chain returns or fails
+template <class Chain>
+void surf_single(const uint8_t* img, float* desc, double* loc, float* aux, int64_t cap, int64_t* count, Chain&& chain) {
+    APS_REQUIRE(count, APS_E_ARG, "NULL argument");
+    aps_surf_view view = {img, desc, loc, aux, cap, *count};
+    try {
+        chain(&view);
+    } catch (...) {
+        *count = view.count;
+        throw;
+    }
+    *count = view.count;
+}
+
+void surf_plain(aps_surf_view* views, int nv, int height, int width, int channels, int img_layout, const aps_surf_params* params,
+                int desc_layout, int64_t ldd, int64_t ldl) {
+    check_args(views, nv, height, width, channels, img_layout, params, desc_layout);
+    surf_chain(views, nv, height, width, channels, img_layout, params, desc_layout, ldd, ldl);
+}
+
+void surf_strongest(aps_surf_view* views, int nv, int height, int width, int channels, int img_layout, const aps_surf_strongest_params* params,
+                    int desc_layout, int64_t ldd, int64_t ldl) {
+    APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
+    check_args(views, nv, height, width, channels, img_layout, &params->surf, desc_layout);
+    surf_select_chain(views, nv, height, width, channels, img_layout, &params->surf, params->n_strongest, 0, 0, desc_layout, ldd, ldl);
+}
+
+void surf_uniform(aps_surf_view* views, int nv, int height, int width, int channels, int img_layout, const aps_surf_uniform_params* params,
+                  int desc_layout, int64_t ldd, int64_t ldl) {
+    APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+    check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
+    check_args(views, nv, height, width, channels, img_layout, &params->strongest.surf, desc_layout);
+    surf_select_chain(views, nv, height, width, channels, img_layout, &params->strongest.surf, params->strongest.n_strongest, params->grid_rows,
+                      params->grid_cols, desc_layout, ldd, ldl);
 }
 
 }  // namespace
@@ -532,58 +644,8 @@ int aps_surf_extract(const uint8_t* img, int height, int width, int channels, in
                      const aps_surf_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        check_args(img, height, width, channels, img_layout, params, desc_layout, cap, count);
-        ctx();
-        *count = 0;
-        const int H = height, W = width;
-        SurfFront F;
-        if (!surf_front(img, H, W, channels, img_layout, params, F)) return;  // smaller than the first octave's support: no features, no error
-        const SurfPlan& plan = F.plan;
-        const long long n_words = F.n_words;
-        const Ws<uint32_t>& I = F.I;
-        const Ws<unsigned long long>& bitmap = F.bitmap;
-        const Ws<unsigned int>& prefix = F.prefix;
-        const unsigned int* d_total = prefix.get() + n_words;
-        const bool write = cap > 0 && desc && loc;
-        const unsigned int kcap = write ? (unsigned int)cap : 0u;
-        Out<float> odesc, oaux;
-        Out<double> oloc;
-        const size_t dwidth = desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64;
-        if (write) {
-            if (desc_layout == APS_ROWMAJOR)
-                APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
-            else
-                APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
-            APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
-            odesc.bind(desc, desc_layout == APS_ROWMAJOR ? (size_t)(cap - 1) * ldd + dwidth : (size_t)63 * ldd + cap);
-            oloc.bind(loc, (size_t)ldl + cap);
-            oaux.bind(aux, (size_t)cap * 4);
-            Ws<int4> kps((size_t)kcap);
-            Ws<SurfTables> d_tb(1);
-            APS_HIP(hipMemcpyAsync(d_tb, &host_tables(), sizeof(SurfTables), hipMemcpyHostToDevice, stream()));
-            surf_emit_kernel<<<cdiv((size_t)n_words, 256), 256, 0, stream()>>>(bitmap, prefix, n_words, plan, kps, kcap);
-            check_launch("surf_emit_kernel");
-            {
-                Prof prof("surf_keypoint");
-                surf_keypoint_kernel<<<cdiv(kcap, 4), 256, 0, stream()>>>(I, plan, d_tb, kps, d_total, kcap, params->upright ? 1 : 0, odesc,
-                                                                         desc_layout, (long long)ldd, oloc, (long long)ldl,
-                                                                         oaux.present() ? oaux.get() : nullptr);
-            }
-            check_launch("surf_keypoint_kernel");
-        }
-        const unsigned int n = read_back(d_total);  // the one read-back of the chain
-        *count = n;
-        if (params->max_features > 0 && n > (unsigned int)params->max_features)
-            fail(APS_E_CAP, "SURF found %u features, more than params.max_features = %d", n, params->max_features);
-        if ((int64_t)n > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, n);
-        if (n == 0) return;
-        APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
-        if (desc_layout == APS_ROWMAJOR)
-            odesc.commit_2d(dwidth, n, (size_t)ldd);
-        else
-            odesc.commit_2d(n, 64, (size_t)ldd);
-        oloc.commit_2d(n, 2, (size_t)ldl);
-        oaux.commit((size_t)n * 4);
+        surf_single(img, desc, loc, aux, cap, count,
+                    [&](aps_surf_view* view) { surf_plain(view, 1, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
     });
 }
 
@@ -591,11 +653,8 @@ int aps_surf_extract_strongest(const uint8_t* img, int height, int width, int ch
                                const aps_surf_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
                                double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
-        APS_REQUIRE(params->n_strongest >= 1, APS_E_ARG, "n_strongest (NumStrongest) must be at least 1");
-        check_args(img, height, width, channels, img_layout, &params->surf, desc_layout, cap, count);
-        surf_strongest_chain(img, height, width, channels, img_layout, &params->surf, params->n_strongest, 0, 0, desc, desc_layout, ldd, loc,
-                             ldl, aux, cap, count);
+        surf_single(img, desc, loc, aux, cap, count,
+                    [&](aps_surf_view* view) { surf_strongest(view, 1, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
     });
 }
 
@@ -603,12 +662,25 @@ int aps_surf_extract_uniform(const uint8_t* img, int height, int width, int chan
                              const aps_surf_uniform_params* params, float* desc, int desc_layout, int64_t ldd,
                              double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
-        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
-        check_uniform(params->strongest.n_strongest, params->grid_rows, params->grid_cols);
-        check_args(img, height, width, channels, img_layout, &params->strongest.surf, desc_layout, cap, count);
-        surf_strongest_chain(img, height, width, channels, img_layout, &params->strongest.surf, params->strongest.n_strongest,
-                             params->grid_rows, params->grid_cols, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+        surf_single(img, desc, loc, aux, cap, count,
+                    [&](aps_surf_view* view) { surf_uniform(view, 1, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
     });
 }
 
+int aps_surf_extract_batch(aps_surf_view* views, int n_views, int height, int width, int channels, int img_layout,
+                           const aps_surf_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] { surf_plain(views, n_views, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
+}
+
+int aps_surf_extract_batch_strongest(aps_surf_view* views, int n_views, int height, int width, int channels, int img_layout,
+                                     const aps_surf_strongest_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] { surf_strongest(views, n_views, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
+}
+
+int aps_surf_extract_batch_uniform(aps_surf_view* views, int n_views, int height, int width, int channels, int img_layout,
+                                   const aps_surf_uniform_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] { surf_uniform(views, n_views, height, width, channels, img_layout, params, desc_layout, ldd, ldl); });
+}
+
 }  // extern "C"
+

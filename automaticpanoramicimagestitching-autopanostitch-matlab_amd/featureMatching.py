@@ -739,8 +739,35 @@ def _over_capacity(counts, cap):
 
 
 def _over_capacity_unless_limited(max_features):
-    """SURF's and FAST's retry predicate: the count exceeds the capacity and is not the count before a maxFeatures row limit."""
-    return lambda counts, cap: counts[0] > cap and not (0 < max_features < counts[0])
+    """SURF's and FAST's retry predicate: some view's count exceeds the capacity and none is the count before a maxFeatures row
+    limit."""
+    return lambda counts, cap: any(n > cap for n in counts) and not any(0 < max_features < n for n in counts)
+
+
+def _group_images(images):
+    """The image preamble of the group wrappers: ([contiguous uint8 images], h, w, c) of images of one shape (ValueError
+    otherwise); an empty list gives a 1 x 1 x 3 shape, which no call uses."""
+    prepared = [_image_hwc(im) for im in images]
+    imgs = [p[0] for p in prepared]
+    if any(tuple(im.shape) != tuple(imgs[0].shape) for im in imgs):
+        raise ValueError("the images of a batch must have one shape")
+    return (imgs,) + (tuple(prepared[0][1:]) if imgs else (1, 1, 3))
+
+
+def _group_call(view_struct, entry, prm, imgs, h, w, c, ld):
+    """call(bufs, cap) of _extract_regrow for the group entries (aps_sift_extract_batch and its kin): one view record per image,
+    all of one capacity, which is also the leading dimension of their column-major locations."""
+    g = len(imgs)
+    views = (view_struct * max(g, 1))()
+
+    def call(bufs, cap):
+        for k, (desc, loc, aux) in enumerate(bufs):
+            views[k].img, views[k].desc, views[k].loc, views[k].aux = ptr(imgs[k]), ptr(desc), ptr(loc), ptr(aux)
+            views[k].cap, views[k].count = cap, 0
+        rc = entry(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, ld, cap if g else 0)
+        return rc, [int(views[k].count) for k in range(g)]
+
+    return call
 
 
 def sift_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
@@ -785,26 +812,12 @@ def sift_extract_batch(input, images, device_out=False, want_aux=False, points_d
     min(default, max(N, 1)), so a resident result holds N rows per view.  Both keys together are a ValueError, raised before any
     library call; the values themselves are the library's to refuse (APS_E_ARG)."""
     uniform = _uniform_keys(input)
-    g = len(images)
-    prepared = [_image_hwc(im) for im in images]
-    imgs = [p[0] for p in prepared]
-    if any(tuple(im.shape) != tuple(imgs[0].shape) for im in imgs):
-        raise ValueError("the images of a batch must have one shape")
-    h, w, c = prepared[0][1:] if g else (1, 1, 3)
+    imgs, h, w, c = _group_images(images)
     prm, entry, cap = _pick_entry(input, uniform, max(4096, (h * w) // 64), (_sift_params(input), lib.aps_sift_extract_batch),
                                   (lambda n: _sift_strongest_params(input, n), lib.aps_sift_extract_batch_strongest),
                                   _capi.aps_sift_uniform_params, lib.aps_sift_extract_batch_uniform)
-    views = (_capi.aps_sift_view * max(g, 1))()
-
-    def call(bufs, cap):
-        for k, (desc, loc, aux) in enumerate(bufs):
-            views[k].img, views[k].desc, views[k].loc, views[k].aux = ptr(imgs[k]), ptr(desc), ptr(loc), ptr(aux)
-            views[k].cap, views[k].count = cap, 0
-        # (the views share one capacity, which is the leading dimension of their column-major locations)
-        rc = entry(views, g, h, w, c, _capi.APS_IMG_U8_HWC, C.byref(prm), _capi.APS_ROWMAJOR, DIM, cap if g else 0)
-        return rc, [int(views[k].count) for k in range(g)]
-
-    out = _extract_regrow(g, cap, call, _over_capacity, DIM, np.float32, device_out, points_device, compact, want_aux)
+    out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_sift_view, entry, prm, imgs, h, w, c, DIM), _over_capacity, DIM,
+                          np.float32, device_out, points_device, compact, want_aux)
     return [r if want_aux else r[:2] for r in out]
 
 
@@ -855,6 +868,29 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
     if device_out and not padded:
         d = d[:, :SURF_DIM]
     return (d, pts, aux) if want_aux else (d, pts)
+
+
+def surf_extract_batch(input, images, device_out=False, want_aux=False, points_device=False, compact=False, padded=False):
+    """aps_surf_extract_batch with automatic capacity: surf_extract for 1.._capi.APS_SURF_MAX_VIEWS images of one shape in one call,
+    every stage once for the group.  Returns a list of surf_extract's results, one (features, validPts[, aux]) per image, bit for
+    bit those of surf_extract(input, image, ...) on each.  The arguments are surf_extract's.
+
+    input.NumStrongest and input.NumUniform (with input.UniformGrid) select per view, as in surf_extract: every view keeps its own
+    min(N, rows) rows through aps_surf_extract_batch_strongest / aps_surf_extract_batch_uniform, whose selection is one more stage of
+    the group's chain.  The capacity per view is then min(default, max(N, 1)).  Both keys together are a ValueError, raised before
+    any library call; the values themselves are the library's to refuse (APS_E_ARG)."""
+    uniform = _uniform_keys(input)
+    imgs, h, w, c = _group_images(images)
+    prm, entry, cap = _pick_entry(input, uniform, max(4096, (h * w) // 64), (_surf_params(input), lib.aps_surf_extract_batch),
+                                  (lambda n: _surf_strongest_params(input, n), lib.aps_surf_extract_batch_strongest),
+                                  _capi.aps_surf_uniform_params, lib.aps_surf_extract_batch_uniform)
+    width = DIM if device_out else SURF_DIM  # (resident rows are 128 wide, host rows 64; the leading dimension follows)
+    out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_surf_view, entry, prm, imgs, h, w, c, width),
+                          _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), width, np.float32, device_out,
+                          points_device, compact, want_aux)
+    if device_out and not padded:
+        out = [(d[:, :SURF_DIM], pts, aux) for d, pts, aux in out]
+    return [r if want_aux else r[:2] for r in out]
 
 
 FREAK_BYTES = 64
@@ -920,6 +956,27 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
                                   device_out, points_device, compact, want_aux)[0]
     f = binaryFeatures(d)
     return (f, pts, aux) if want_aux else (f, pts)
+
+
+def fast_extract_batch(input, images, device_out=False, want_aux=False, points_device=False, compact=False):
+    """aps_fast_extract_batch with automatic capacity: fast_extract for 1.._capi.APS_FAST_MAX_VIEWS images of one shape in one call,
+    every stage once for the group, for any input.NumLevels.  Returns a list of fast_extract's results, one (binaryFeatures,
+    validPts[, aux]) per image, byte for byte those of fast_extract(input, image, ...) on each (aux is [score, bin, level, 0], also
+    with NumLevels = 1, where the level is 0).  The arguments are fast_extract's.
+
+    input.NumStrongest and input.NumUniform have no group form - a FAST selection group is a level, and a group of views would need
+    views x levels of them: with either key this is a ValueError; call fast_extract per view."""
+    if "NumStrongest" in input or "NumUniform" in input:
+        raise ValueError("fast_extract_batch takes no input.NumStrongest / input.NumUniform: call fast_extract per view")
+    imgs, h, w, c = _group_images(images)
+    prm = _fast_pyramid_params(input, int(input.get("NumLevels", 1)))
+    hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
+    check(lib.aps_fast_pyramid_plan(h, w, prm.n_levels, prm.scale_num, prm.scale_den, hs, ws, C.byref(used)))
+    cap = max(4096, sum(hs[l] * ws[l] for l in range(used.value)) // 64)  # (no selection key: nothing for _pick_entry to pick)
+    out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_fast_view, lib.aps_fast_extract_batch, prm, imgs, h, w, c, FREAK_BYTES),
+                          _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), FREAK_BYTES, np.uint8, device_out,
+                          points_device, compact, want_aux)
+    return [(binaryFeatures(d), pts, aux) if want_aux else (binaryFeatures(d), pts) for d, pts, aux in out]
 
 
 def extract_features(input, image, **kw):

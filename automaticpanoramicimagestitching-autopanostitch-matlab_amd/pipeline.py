@@ -57,8 +57,9 @@ def _sync():
 _SIFT_POOL = None
 
 
-# Host threads / HIP streams of the per-image feature extraction (host images, SURF, FAST; resident SIFT views go in groups, below,
-# with or without NumStrongest / NumUniform).  Measured on the 64 x 4K scene on several boxes:
+# Host threads / HIP streams of the per-image feature extraction (host images, and resident SURF and FAST views, which the
+# measurements below keep view by view; resident SIFT views go in groups, below, with or without NumStrongest / NumUniform).
+# Measured on the 64 x 4K scene on several boxes:
 # 4, 5, 10, 11, 12, 14 threads give 88-93 ms, 10 the best or tied everywhere; 7-9 threads read 100 ms on some boxes and
 # 92 on others (reproducibly per box; the HIP runtime maps streams onto 8 hardware queues), 12 costs the end-to-end
 # step's uploads 14 ms.
@@ -73,7 +74,43 @@ SIFT_WORKERS_DEFAULT = 10
 # 16 x 3 157.0-160.2, 2 x 8 166.0-166.7.
 SIFT_GROUP_VIEWS = 8
 SIFT_GROUP_WORKERS = 3
-_SIFT_GROUP_POOL = None
+
+# Resident SURF views, with or without NumStrongest / NumUniform, can go in groups too (fm.surf_extract_batch); a group size of 0
+# keeps them view by view on the SIFT_WORKERS_DEFAULT streams, and that is the default, because no group setting was faster.
+# Measured with scripts/probe/feature_groups_time.py on 64 resident 4K views of the dense synthetic texture (2047 rows per view),
+# ms per extraction pass, median (range) of three alternating series of five passes; per-view = the commit before the group entries,
+# in the same process: per-view 38.97 (38.29-39.14); 4 views x 2 workers 40.78 (40.52-40.88), 4 x 3 39.73 (39.68-39.76), 4 x 4 39.95
+# (39.84-40.31), 8 x 2 41.78 (41.52-43.35), 8 x 3 40.59 (40.31-41.10), 8 x 4 40.95 (40.84-42.70), 16 x 2 42.37 (41.75-43.86), 16 x 3
+# 42.25 (41.96-42.73), 16 x 4 43.03 (42.34-43.18).  With NumStrongest = 5000 (above every view's count): per-view 37.79 (37.70-38.35);
+# 4 x 2 39.32, 4 x 3 38.22 (38.19-38.40), 4 x 4 39.10, 8 x 2 41.49, 8 x 3 39.89, 8 x 4 39.91, 16 x 2 40.80, 16 x 3 40.64, 16 x 4 40.75.
+# Ten streams already keep the device busy: a pass takes 0.6 ms per view, less than the 0.77 ms of kernels a view runs (DESIGN.md
+# section 7), so there is no launch gap left to close.  The workers are those of the best setting.
+SURF_GROUP_VIEWS = 0
+SURF_GROUP_WORKERS = 3
+
+# Resident FAST views without NumStrongest / NumUniform likewise (fm.fast_extract_batch; with either key a FAST selection group is a
+# level, there is no group form, and the views go one by one whatever this says).  Default 0, view by view: same probe, NumLevels = 3,
+# MinContrast = 0.08 (58 103 rows per view): per-view 39.02 (30.93-44.29); 4 x 2 42.06 (42.01-42.70), 4 x 3 41.61 (41.17-42.19), 4 x 4
+# 42.06 (40.05-42.71), 8 x 2 55.38 (52.89-55.71), 8 x 3 55.15 (41.94-55.92), 8 x 4 39.88 (39.10-40.77), 16 x 2 61.27 (55.18-64.99),
+# 16 x 3 45.19 (44.79-45.20), 16 x 4 51.66 (42.19-52.85): the best setting is inside the per-view spread.
+FAST_GROUP_VIEWS = 0
+FAST_GROUP_WORKERS = 4
+_GROUP_POOLS = {}  # detector -> the pool of its group workers
+
+
+def _group_route(input):
+    """(detector, batch extractor, views per group, workers) for resident views of this input, or None where they go view by
+    view: a detector without a group form, FAST with a selection key, or a group size of 0."""
+    det = input.get("detector", "SIFT")
+    if det == "SIFT":
+        route = (det, fm.sift_extract_batch, SIFT_GROUP_VIEWS, SIFT_GROUP_WORKERS)
+    elif det == "SURF":  # (padded: the 128-wide rows the matchers take, as extract_features asks of surf_extract)
+        route = (det, lambda *a, **kw: fm.surf_extract_batch(*a, padded=True, **kw), SURF_GROUP_VIEWS, SURF_GROUP_WORKERS)
+    elif det == "FAST" and "NumStrongest" not in input and "NumUniform" not in input:
+        route = (det, fm.fast_extract_batch, FAST_GROUP_VIEWS, FAST_GROUP_WORKERS)
+    else:
+        return None
+    return route if route[2] > 0 else None
 
 
 def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
@@ -130,7 +167,7 @@ def release_device_memory():
     import torch
 
     _capi.check(_capi.lib.aps_release_workspace())
-    for pool in (_SIFT_POOL, _SIFT_GROUP_POOL):
+    for pool in (_SIFT_POOL, *_GROUP_POOLS.values()):
         n = len(getattr(pool, "_threads", ())) if pool is not None else 0
         if not n:
             continue
@@ -153,12 +190,14 @@ def release_device_memory():
 def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_device=False):
     """The asynchronous form of sift_many: one future per image, submitted in input order to the worker pool, so that
     a caller can start matching the first images while the later ones are still being extracted (parallel._match_pass).
-    Resident SIFT images are submitted as groups of up to SIFT_GROUP_VIEWS consecutive images of one shape (fm.sift_extract_batch,
-    which selects per view under input.NumStrongest / input.NumUniform) to SIFT_GROUP_WORKERS threads; the futures of a group
-    resolve together.
+    Resident SIFT images are submitted as groups of up to SIFT_GROUP_VIEWS consecutive images of one shape and device
+    (fm.sift_extract_batch, which selects per view under input.NumStrongest / input.NumUniform) to SIFT_GROUP_WORKERS threads; the
+    futures of a group resolve together.  Resident SURF views, and FAST views without a selection key, take the same route through
+    fm.surf_extract_batch / fm.fast_extract_batch when SURF_GROUP_VIEWS / FAST_GROUP_VIEWS is above 0 (_group_route); by default,
+    and for host images and FAST with a selection key, every image is a task of its own.
     Each future resolves to (descriptors, keypoints) once that worker's stream has finished the image.
     points_device: resident images only - the keypoints stay on the device (fm.sift_extract)."""
-    global _SIFT_POOL, _SIFT_GROUP_POOL
+    global _SIFT_POOL
     import os
     import torch
     from concurrent.futures import Future, ThreadPoolExecutor
@@ -167,14 +206,17 @@ def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_
     dev = _capi.is_torch(images[0]) and images[0].is_cuda
     if dev and ready is None:
         torch.cuda.synchronize()  # the images were produced on torch's stream; worker streams must see them
-    if dev and input.get("detector", "SIFT") == "SIFT":
-        # resident SIFT views: groups of consecutive images of one shape, one pool task per group, one future per image
-        if _SIFT_GROUP_POOL is None:
-            _SIFT_GROUP_POOL = ThreadPoolExecutor(max_workers=SIFT_GROUP_WORKERS, initializer=_init_worker,
-                                                  initargs=(_capi.lib.aps_get_device(),))
+    route = _group_route(input) if dev else None
+    if route:
+        # resident views: groups of consecutive images of one shape, one pool task per group, one future per image
+        det, extract_batch, group_views, group_workers = route
+        if det not in _GROUP_POOLS:
+            _GROUP_POOLS[det] = ThreadPoolExecutor(max_workers=group_workers, initializer=_init_worker,
+                                                   initargs=(_capi.lib.aps_get_device(),))
+        group_pool = _GROUP_POOLS[det]
         groups = []
         for k, img in enumerate(images):
-            if groups and len(groups[-1]) < SIFT_GROUP_VIEWS and tuple(images[groups[-1][0]].shape) == tuple(img.shape) \
+            if groups and len(groups[-1]) < group_views and tuple(images[groups[-1][0]].shape) == tuple(img.shape) \
                     and images[groups[-1][0]].device == img.device:
                 groups[-1].append(k)
             else:
@@ -189,8 +231,8 @@ def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_
                 if ready is not None:
                     for k in ks:
                         ready[k].synchronize()
-                res = fm.sift_extract_batch(input, [images[k] for k in ks], device_out=True, points_device=bool(points_device),
-                                            compact=len(images) > 96)
+                res = extract_batch(input, [images[k] for k in ks], device_out=True, points_device=bool(points_device),
+                                    compact=len(images) > 96)
                 _sync()  # this thread's stream
             except BaseException as e:
                 for k in ks:
@@ -200,7 +242,7 @@ def sift_submit(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None, points_
                 futs[k].set_result(r)
 
         for ks in groups:
-            _SIFT_GROUP_POOL.submit(work_group, ks)
+            group_pool.submit(work_group, ks)
         return futs
     if _SIFT_POOL is None:
         _SIFT_POOL = ThreadPoolExecutor(max_workers=workers, initializer=_init_worker, initargs=(_capi.lib.aps_get_device(),))

@@ -837,6 +837,41 @@ int aps_surf_extract_strongest(const uint8_t* img, int height, int width, int ch
                                const aps_surf_strongest_params* params, float* desc, int desc_layout, int64_t ldd,
                                double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
+/* aps_surf_extract for a group of views of one shape (height x width x channels, img_layout): every stage runs once for the group -
+ * the three integral-image launches, one detection launch per octave, one scan, one compaction, one per-keypoint launch - where
+ * n_views single calls run it n_views times.  The rows of view k (descriptor, location, aux, order and count) are bit for bit those
+ * of aps_surf_extract on views[k].img with the same params, whatever the other views hold. */
+#define APS_SURF_MAX_VIEWS 16
+typedef struct aps_surf_view {
+    const uint8_t* img;   /* H x W x channels, host or device, as aps_surf_extract */
+    float* desc; double* loc; float* aux;   /* per-view outputs, host or device; aux may be NULL */
+    int64_t cap;          /* rows of room in this view's outputs */
+    int64_t count;        /* out: rows found (on APS_E_CAP: rows needed) */
+} aps_surf_view;
+/* n_views in 1..APS_SURF_MAX_VIEWS (else APS_E_ARG, as for a NULL views, params or views[k].img, an image the 32-bit integral image
+ * cannot hold and every parameter range aps_surf_extract checks - all before any device work).  desc_layout, ldd and ldl hold for
+ * every view; host / device pointers, row-major / column-major layout, padding, the rows count..cap that are never written and the
+ * zeroing of columns 64..127 with ldd >= 128 behave as aps_surf_extract's, view by view.  When any view's rows exceed its cap (a
+ * view with desc = NULL or cap = 0 only counts) nothing is written and the call returns APS_E_CAP with EVERY view's count set to the
+ * rows it needs, so one retry is enough.  A view without features gets count = 0 and does not touch the others.
+ * params->max_features keeps its meaning per view.  The call reads back once, for all counts; it runs on the calling thread's
+ * stream with that thread's workspace, which holds the views' integral images side by side: 8 bytes per pixel and view. */
+int aps_surf_extract_batch(aps_surf_view* views, int n_views, int height, int width, int channels,
+                           int img_layout, const aps_surf_params* params,
+                           int desc_layout, int64_t ldd, int64_t ldl);
+
+/* aps_surf_extract_strongest for a group of views of one shape: aps_surf_extract_batch's chain with the selection as one more stage
+ * of the group, the view being the selection's group.  The rows of view k are bit for bit those of aps_surf_extract_strongest on
+ * views[k].img with the same params, whatever the other views hold; views[k].count = rows kept, and
+ * views[k].cap >= min(candidates_k, n_strongest) always suffices.  Arguments, capacities, APS_E_CAP with nothing written and every
+ * count set, and the checks are aps_surf_extract_batch's, with n_strongest < 1 refused (APS_E_ARG) before any device work;
+ * surf.max_features is tested against each view's candidates.  One sort, one flag pass, one ballot and scan and one compaction
+ * select for all the views.  The call reads back twice, as aps_surf_extract_strongest does: the views' candidate counts, then the
+ * counts kept. */
+int aps_surf_extract_batch_strongest(aps_surf_view* views, int n_views, int height, int width, int channels,
+                                     int img_layout, const aps_surf_strongest_params* params,
+                                     int desc_layout, int64_t ldd, int64_t ldl);
+
 /* ============================================================================================
  * (4c) FAST + FREAK — PP/featureMatching/getFeaturePoints.m:51-52,71-74
  * ============================================================================================ */
@@ -888,6 +923,32 @@ typedef struct aps_fast_pyramid_params {
 int aps_fast_extract_pyramid(const uint8_t* img, int height, int width, int channels, int img_layout,
                              const aps_fast_pyramid_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
                              double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* aps_fast_extract_pyramid for a group of views of one shape (n_levels = 1: aps_fast_extract's plan): every stage runs once for the
+ * group - the integral-image launches and one resampling launch per level, one detection launch, one segmented maximum for the
+ * quality gate's s_max per (view, level), one gate, one scan, one compaction, one FREAK launch - where n_views single calls run it
+ * n_views times.  The views share one plan; planes, score planes, integral images and bitmap words are packed [view][level].  The
+ * rows of view k (descriptor, location, aux = [score, bin, level, 0], order and count) are byte for byte those of
+ * aps_fast_extract_pyramid on views[k].img with the same params, whatever the other views hold. */
+#define APS_FAST_MAX_VIEWS 16
+typedef struct aps_fast_view {
+    const uint8_t* img;   /* H x W x channels, host or device, as aps_fast_extract */
+    uint8_t* desc; double* loc; float* aux;   /* per-view outputs, host or device; aux may be NULL */
+    int64_t cap;          /* rows of room in this view's outputs */
+    int64_t count;        /* out: rows found (on APS_E_CAP: rows needed) */
+} aps_fast_view;
+/* n_views in 1..APS_FAST_MAX_VIEWS (else APS_E_ARG, as for a NULL views, params or views[k].img, an image the 32-bit integral image
+ * cannot hold and every parameter range aps_fast_extract_pyramid checks - all before any device work).  desc_layout, ldd and ldl
+ * hold for every view; host / device pointers, row-major / column-major layout, padding and the rows count..cap that are never
+ * written behave as aps_fast_extract's, view by view.  When any view's rows exceed its cap (a view with desc = NULL or cap = 0 only
+ * counts) nothing is written and the call returns APS_E_CAP with EVERY view's count set to the rows it needs, so one retry is
+ * enough.  A view without features gets count = 0 and does not touch the others.  fast.max_features keeps its meaning per view.
+ * The call reads back once, for all counts; it runs on the calling thread's stream with that thread's workspace.
+ * aps_fast_extract_strongest and aps_fast_extract_uniform have no group form: their selection group is a level, and a group of
+ * views would need views x levels of them. */
+int aps_fast_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels,
+                           int img_layout, const aps_fast_pyramid_params* params,
+                           int desc_layout, int64_t ldd, int64_t ldl);
 
 /* The plan of that call (host only, needs no device): h_0 = height, h_l = floor((2 h_{l-1} scale_den + scale_num) / (2 scale_num)),
  * widths alike; the plan ends before the first level with min(h_l, w_l) < 2 * margin + 1 (aps_freak_pattern's margin) or at
@@ -988,6 +1049,15 @@ int aps_fast_extract_uniform(const uint8_t* img, int height, int width, int chan
  * no read-back beyond aps_sift_extract_batch's. */
 int aps_sift_extract_batch_uniform(aps_sift_view* views, int n_views, int height, int width, int channels,
                                    int img_layout, const aps_sift_uniform_params* params,
+                                   int desc_layout, int64_t ldd, int64_t ldl);
+
+/* aps_surf_extract_uniform for a group of views of one shape, as aps_surf_extract_batch_strongest is for aps_surf_extract_strongest:
+ * the rows of view k are bit for bit those of aps_surf_extract_uniform on views[k].img with the same params, whatever the other
+ * views hold; the budget of view k is min(candidates_k, N), spread over the cells of its own grid.  Arguments, capacities,
+ * APS_E_CAP, the checks and the two read-backs are aps_surf_extract_batch_strongest's, with a grid value outside 1..32 refused
+ * (APS_E_ARG) before any device work.  The selection of the whole group is one sort and one pass of each of its kernels. */
+int aps_surf_extract_batch_uniform(aps_surf_view* views, int n_views, int height, int width, int channels,
+                                   int img_layout, const aps_surf_uniform_params* params,
                                    int desc_layout, int64_t ldd, int64_t ldl);
 
 /* The water-filling of that rule (host only, needs no device; the function the device kernel calls): keep[k] of n_cells cells (1..1024)
