@@ -139,6 +139,19 @@ class aps_fast_uniform_params(C.Structure):
     _fields_ = [("strongest", aps_fast_strongest_params), ("grid_rows", C.c_int), ("grid_cols", C.c_int)]
 
 
+APS_MARK_SEGMENT, APS_MARK_RING = 0, 1
+
+
+class aps_mark(C.Structure):
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double), ("kind", C.c_int32),
+                ("line_width", C.c_int32), ("rgb", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+# the same 48 bytes as a NumPy record: an array of this dtype is an aps_mark table
+MARK_DTYPE = np.dtype([("x0", "<f8"), ("y0", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("kind", "<i4"), ("line_width", "<i4"),
+                       ("rgb", "u1", (3,)), ("reserved", "u1")], align=True)
+assert MARK_DTYPE.itemsize == C.sizeof(aps_mark) == 48
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/aps.h one to one
@@ -198,6 +211,8 @@ _SIGNATURES = {
     "aps_crop_rect": [_vp, _i64, _i64, _i, _i, _d, _vp, _vp],
     "aps_crop_nonzero_bbox": [_vp, _i64, _i64, _i, _i, _vp, _vp],
     "aps_annotate_panorama": [_vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "aps_draw_marks": [_vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(_i64)],
+    "aps_montage_pair": [_vp, _i64, _i64, _vp, _i64, _i64, _vp],
     "aps_ransac_draws_exhausted": [],
     "aps_gather_match_points": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i64],
     "aps_match_screen_stats": [_vp, _vp],

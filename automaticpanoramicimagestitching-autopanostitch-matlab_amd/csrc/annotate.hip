@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "aps_internal.h"
+#include "raster_dev.h"  // ann_mulhi / ann_disc / ann_seg_hit: the exact edge test, shared with marks.hip
 
 namespace aps {
 
@@ -56,37 +57,6 @@ struct AnnItem {
     uint32_t e;
     uint32_t kind;
 };
-
-__host__ __device__ __forceinline__ uint64_t ann_mulhi(uint64_t x, uint64_t y) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __umul64hi(x, y);
-#else
-    return (uint64_t)(((unsigned __int128)x * y) >> 64);
-#endif
-}
-
-// |ax|^2 + |ay|^2 <= R^2 (squares taken only of values already known to be <= R)
-__host__ __device__ __forceinline__ bool ann_disc(int64_t ax, int64_t ay, int64_t R) {
-    if (ax < 0) ax = -ax;
-    if (ay < 0) ay = -ay;
-    if (ax > R || ay > R) return false;
-    return ax * ax + ay * ay <= R * R;
-}
-
-// Exact: squared distance from (cx, cy) to the closed segment (x0, y0)-(x1, y1) <= R^2.  See the header for the ranges.
-__host__ __device__ __forceinline__ bool ann_seg_hit(int64_t cx, int64_t cy, int64_t x0, int64_t y0, int64_t x1, int64_t y1,
-                                                     int64_t R) {
-    const int64_t Dx = x1 - x0, Dy = y1 - y0, Ax = cx - x0, Ay = cy - y0;
-    const int64_t DD = Dx * Dx + Dy * Dy;
-    const int64_t t = Ax * Dx + Ay * Dy;
-    if (t <= 0) return ann_disc(Ax, Ay, R);  // before the start point, or a zero-length edge (a dot)
-    if (t >= DD) return ann_disc(cx - x1, cy - y1, R);
-    int64_t cr = Ax * Dy - Ay * Dx;
-    if (cr < 0) cr = -cr;
-    const uint64_t u = (uint64_t)cr, r2 = (uint64_t)(R * R), dd = (uint64_t)DD;
-    const uint64_t lhi = ann_mulhi(u, u), llo = u * u, rhi = ann_mulhi(r2, dd), rlo = r2 * dd;
-    return lhi < rhi || (lhi == rhi && llo <= rlo);
-}
 
 // One workgroup per touched tile; lane t owns column (t & 63) and the 16 rows (t >> 6) + 4 i of the tile.
 __global__ __launch_bounds__(256) void annotate_tiles_kernel(uint8_t* __restrict__ img, int64_t H, int64_t W,

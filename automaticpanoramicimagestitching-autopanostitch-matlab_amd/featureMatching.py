@@ -1171,3 +1171,34 @@ def featureMatchingGlobal(input, allDescriptors, numImg):
         if e > s:
             matches[i][j] = np.stack([oi[s:e], oj[s:e]], axis=1).astype(np.float64)
     return matches
+
+
+def keypoint_marks(points, scales=None, angles_deg=None, color=(0, 255, 0), markerRadius=3, lineWidth=1):
+    """The marks of a keypoint plot ("Mark contract"): one ring per keypoint, of radius scales[k] when given and
+    markerRadius otherwise; with angles_deg, after all rings, one segment per keypoint from its centre to
+    centre + radius * (cos a, -sin a), a = deg2rad(angles_deg[k]) (counter-clockwise on the screen, y pointing down), computed
+    here in f64.  points: n x 2 (x, y), 1-based; the columns of a detector's aux array differ, so the caller picks them."""
+    from . import imageProcessing as ip
+
+    pts = np.asarray(points.detach().cpu() if _capi.is_torch(points) else points, np.float64).reshape(-1, 2)
+    host = lambda v: np.asarray(v.detach().cpu() if _capi.is_torch(v) else v, np.float64).reshape(-1)  # noqa: E731
+    radii = np.full(len(pts), float(markerRadius)) if scales is None else host(scales)
+    if len(radii) != len(pts):
+        raise ValueError("scales must have one entry per keypoint")
+    marks = [ip.mark_rings(pts, radii, color, lineWidth)]
+    if angles_deg is not None:
+        a = np.deg2rad(host(angles_deg))
+        if len(a) != len(pts):
+            raise ValueError("angles_deg must have one entry per keypoint")
+        tips = pts + radii[:, None] * np.stack([np.cos(a), -np.sin(a)], axis=1)
+        marks.append(ip.mark_segments(pts, tips, color, lineWidth))
+    return np.concatenate(marks)
+
+
+def showKeypoints(image, points, scales=None, angles_deg=None, color=(0, 255, 0), markerRadius=3, lineWidth=1):
+    """The keypoints drawn on a copy of image (ip.draw_marks of keypoint_marks): a ring per keypoint and, with angles_deg, its
+    orientation as a radius.  Rings above 4096 px, and keypoints with a non-finite coordinate, scale or angle, are skipped by
+    the mark contract.  Returns the drawn image, of the kind of `image` (resident when it is)."""
+    from . import imageProcessing as ip
+
+    return ip.draw_marks(image, keypoint_marks(points, scales, angles_deg, color, markerRadius, lineWidth))[0]

@@ -339,3 +339,91 @@ def imageMatching(input, n, keypoints, matchesAll, imagesProcessed=None, seed=0)
             tforms[i][j] = models[p]
             tforms[j][i] = np.linalg.inv(models[p])
     return allMatches, numMatches, tforms
+
+
+# ---- input.showKeypointsPlot: the pictures of refineMatch (imageMatching.m:257-269), drawn on the device -------------------
+MATCH_PLOT_COLORS = ((255, 0, 0), (0, 255, 0), (255, 255, 0))  # MATLAB's default {'ro', 'g+', 'y-'}: points 1, points 2, lines
+
+
+def _host_points(p):
+    if _capi.is_torch(p):
+        p = p.detach().cpu().numpy()
+    p = np.asarray(p, np.float64)
+    return p.reshape(len(p), -1)[:, :2] if p.size else np.zeros((0, 2))
+
+
+def match_plot_marks(matchedPoints1, matchedPoints2, w1, markerRadius=3, lineWidth=1, colors=None):
+    """The marks of one match plot ("Mark contract") on the montage whose left image is w1 pixels wide: the n
+    connecting lines, then n rings at the points of image 1, then a plus (two segments) per point of image 2, shifted by w1.
+    Rows with a non-finite coordinate are dropped.  colors: (points 1, points 2, lines) as RGB triples."""
+    from . import imageProcessing as ip
+
+    p1, p2 = _host_points(matchedPoints1), _host_points(matchedPoints2)
+    if p1.shape != p2.shape or p1.shape[1] != 2:
+        raise ValueError("matchedPoints1 and matchedPoints2 must both be n x 2")
+    c1, c2, cl = MATCH_PLOT_COLORS if colors is None else colors
+    keep = np.isfinite(p1).all(1) & np.isfinite(p2).all(1)
+    p1, p2 = p1[keep], p2[keep] + [float(w1), 0.0]
+    m = float(markerRadius)
+    plus = np.stack([p2 - [m, 0], p2 + [m, 0], p2 - [0, m], p2 + [0, m]], axis=1).reshape(-1, 2, 2)  # per point: across, then down
+    return np.concatenate([ip.mark_segments(p1, p2, cl, lineWidth), ip.mark_rings(p1, m, c1, lineWidth),
+                           ip.mark_segments(plus[:, 0], plus[:, 1], c2, lineWidth)])
+
+
+def showMatchedFeatures(I1, I2, matchedPoints1, matchedPoints2, method="montage", markerRadius=3, lineWidth=1, colors=None):
+    """showMatchedFeatures(I1, I2, matchedPoints1, matchedPoints2, 'montage') as a picture: the two images side by side
+    (ip.montage_pair), a line per match, a ring on every point of image 1 and a plus on every point of image 2
+    (match_plot_marks, drawn in place by ip.draw_marks).  Points are n x 2 (x, y), 1-based.  Resident when either image is a
+    CUDA tensor.  The raster rule is this project's own ("Mark contract"); 'falsecolor' and 'blend' are not served."""
+    from . import imageProcessing as ip
+
+    if str(method).lower() != "montage":
+        raise ValueError(f"showMatchedFeatures: only method='montage' is supported, got {method!r}")
+    w1 = int(I1.shape[1])
+    marks = match_plot_marks(matchedPoints1, matchedPoints2, w1, markerRadius, lineWidth, colors)
+    canvas = ip.montage_pair(I1, I2)
+    return _draw(canvas, marks, canvas)
+
+
+def _draw(src, marks, dst):
+    """aps_draw_marks between contiguous H x W x 3 canvases made by this module (dst is src: in place, no copy)."""
+    check(lib.aps_draw_marks(ptr(src), int(src.shape[0]), int(src.shape[1]), ptr(marks), len(marks), ptr(dst), None))
+    return dst
+
+
+def match_plot_bytes(sizes, pairs):
+    """Bytes of the three pictures (original, putative, inliers) of every pair: sum of 3 * max(h_i, h_j) * (w_i + w_j) * 3.
+    sizes: (h, w, ...) per image; pairs: (i, j), 0-based.  Host only."""
+    return sum(3 * max(int(sizes[i][0]), int(sizes[j][0])) * (int(sizes[i][1]) + int(sizes[j][1])) * 3 for i, j in pairs)
+
+
+def matchPlots(images, keypoints, putative, inliers, pairs, **style):
+    """The three subplots of refineMatch (imageMatching.m:257-269) for every pair (i, j) of `pairs` (0-based, image 1 is image
+    i): {(i, j): {'original': the montage, 'putative': the putative matches over it, 'inliers': the RANSAC inliers over it}}.
+    putative / inliers: per pair (a dict keyed by (i, j), or a sequence in the order of `pairs`) a K x 2 array of 1-based
+    keypoint indices, column 0 into keypoints[i], column 1 into keypoints[j]; K = 0 gives the bare montage.
+    style: markerRadius, lineWidth, colors, as for showMatchedFeatures.  One montage per pair is made; each drawing is one
+    copy of it with the marks on top."""
+    from . import imageProcessing as ip
+
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    at = lambda lists, k: lists[pairs[k]] if isinstance(lists, dict) else lists[k]  # noqa: E731
+    out = {}
+    for k, (i, j) in enumerate(pairs):
+        original = ip.montage_pair(images[i], images[j])
+        p_i, p_j = _host_points(keypoints[i]), _host_points(keypoints[j])
+        plot = {"original": original}
+        for name, lists in (("putative", putative), ("inliers", inliers)):
+            mt = np.asarray(at(lists, k), np.int64).reshape(-1, 2)
+            if len(mt) and (mt[:, 0].min() < 1 or mt[:, 1].min() < 1 or mt[:, 0].max() > len(p_i) or mt[:, 1].max() > len(p_j)):
+                raise ValueError("Match indices exceed keypoint array sizes.")  # refineMatch :222-226
+            marks = match_plot_marks(p_i[mt[:, 0] - 1], p_j[mt[:, 1] - 1], int(images[i].shape[1]), **style)
+            if _capi.is_torch(original):
+                import torch
+
+                canvas = torch.empty_like(original)
+            else:
+                canvas = np.empty_like(original)
+            plot[name] = _draw(original, marks, canvas)
+        out[(i, j)] = plot
+    return out

@@ -1,6 +1,8 @@
 """Host-side mirror of PP/imageProcessing/imageWarp.m and its imref2d helpers."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import _capi
@@ -319,3 +321,109 @@ def imreadAutoRotate(filename, device=None):
 
         arr = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
     return applyOrientation(arr, orientation)
+
+
+# ---- drawing on images: marks (segments and rings) and the montage of a pair ("Mark contract") ---------------
+def drawing_buffers(image, what="image"):
+    """(src, dst, H, W) for an entry that draws src into dst: image is uint8 H x W x 3 (H x W and H x W x 1 are replicated), a
+    numpy array or a torch tensor; dst is of the same kind, resident when image is, and image itself is never written.  When
+    src is a copy made here (a replicated channel, a non-contiguous view made contiguous) it is drawn on in place (dst is
+    src): one copy of the canvas either way."""
+    is_t = _capi.is_torch(image)
+    if not is_t:
+        image = np.asarray(image)
+    if image.ndim == 2:
+        image = image[:, :, None]
+    if str(image.dtype).split(".")[-1] != "uint8" or image.ndim != 3 or int(image.shape[2]) not in (1, 3):
+        raise ValueError(f"{what} must be uint8 H x W, H x W x 1 or H x W x 3, got {image.dtype} {tuple(image.shape)}")
+    if is_t and image.is_cuda:
+        check(lib.aps_synchronize())  # the image may still be in flight on the library's stream of this thread
+    if int(image.shape[2]) == 1:
+        src, own = (image.expand(-1, -1, 3).contiguous() if is_t else np.repeat(image, 3, axis=2)), True
+    elif is_t:
+        src, own = (image, False) if image.is_contiguous() else (image.contiguous(), True)
+    else:
+        src, own = (image, False) if image.flags.c_contiguous else (np.ascontiguousarray(image), True)
+    if own:
+        dst = src
+    elif is_t:
+        import torch
+
+        dst = torch.empty_like(src)
+    else:
+        dst = np.empty_like(src)
+    if is_t and src.is_cuda:
+        import torch
+
+        torch.cuda.current_stream().synchronize()  # torch produced them; the library draws on its own stream
+    return src, dst, int(src.shape[0]), int(src.shape[1])
+
+
+def _marks(kind, a, b, rgb, lineWidth):
+    a = np.asarray(a, np.float64).reshape(-1, 2)
+    m = np.zeros(len(a), _capi.MARK_DTYPE)
+    m["x0"], m["y0"] = a[:, 0], a[:, 1]
+    m["x1"], m["y1"] = b
+    m["kind"] = kind
+    m["line_width"] = np.asarray(lineWidth, np.int64)  # a scalar, or one per mark
+    m["rgb"] = np.asarray(rgb, np.uint8).reshape(-1, 3)  # one colour, or one per mark
+    return m
+
+
+def mark_segments(p0, p1, rgb, lineWidth=1):
+    """The marks (an array of _capi.MARK_DTYPE = aps_mark) of the segments p0[k] -> p1[k]: [n, 2] (x, y), 1-based.  rgb: one
+    uint8 triple or [n, 3]; lineWidth: one value or [n], each in 1..64.  Concatenating mark arrays gives the drawing order."""
+    p1 = np.asarray(p1, np.float64).reshape(-1, 2)
+    if len(p1) != len(np.asarray(p0, np.float64).reshape(-1, 2)):
+        raise ValueError("p0 and p1 must have one row per segment")
+    return _marks(_capi.APS_MARK_SEGMENT, p0, (p1[:, 0], p1[:, 1]), rgb, lineWidth)
+
+
+def mark_rings(centres, radii, rgb, lineWidth=1):
+    """The marks of rings around centres[k] ([n, 2] (x, y), 1-based) of radius radii[k] pixels (one value or [n]; radius 0 is a
+    disc of diameter lineWidth; rings above 4096 px are skipped when drawn).  rgb and lineWidth as for mark_segments."""
+    return _marks(_capi.APS_MARK_RING, centres, (np.asarray(radii, np.float64), 0.0), rgb, lineWidth)
+
+
+def draw_marks(image, marks):
+    """(drawn_image, marks_drawn): the marks drawn on a copy of image on the device (aps_draw_marks; the raster rule is
+    DESIGN.md's "Mark contract"), in ascending index, the highest index on top.  image as drawing_buffers takes it; the result
+    is a new H x W x 3 array of the same kind, resident when image is.  marks: an array of _capi.MARK_DTYPE (mark_segments,
+    mark_rings, np.concatenate of them).  marks_drawn counts the valid marks (finite, |coordinate| <= 2^20, radius in 0..4096)."""
+    marks = np.ascontiguousarray(marks)
+    if marks.dtype != _capi.MARK_DTYPE or marks.ndim != 1:
+        raise ValueError("marks must be a one-dimensional array of _capi.MARK_DTYPE (mark_segments / mark_rings)")
+    src, dst, H, W = drawing_buffers(image)
+    drawn = C.c_int64(0)
+    check(lib.aps_draw_marks(ptr(src), H, W, ptr(marks), len(marks), ptr(dst), C.byref(drawn)))
+    return dst, int(drawn.value)
+
+
+def montage_pair(I1, I2):
+    """The 'montage' of showMatchedFeatures: I1 and I2 side by side on a max(h1, h2) x (w1 + w2) x 3 canvas, 0 elsewhere
+    (aps_montage_pair).  I1, I2: uint8 H x W, H x W x 1 or H x W x 3, numpy arrays or torch tensors; the result is a CUDA tensor
+    when either is one, a host tensor when either is a torch tensor, a numpy array otherwise."""
+    imgs = []
+    for k, im in enumerate((I1, I2)):
+        is_t = _capi.is_torch(im)
+        if not is_t:
+            im = np.asarray(im)
+        if str(im.dtype).split(".")[-1] != "uint8" or im.ndim not in (2, 3) or (im.ndim == 3 and int(im.shape[2]) not in (1, 3)):
+            raise ValueError(f"I{k + 1} must be uint8 H x W, H x W x 1 or H x W x 3, got {im.dtype} {tuple(im.shape)}")
+        im = convertToRGB(im)
+        imgs.append(im.contiguous() if is_t else np.ascontiguousarray(im))
+    (h1, w1), (h2, w2) = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+    shape = (max(h1, h2), w1 + w2, 3)
+    tens = [im for im in imgs if _capi.is_torch(im)]
+    if tens:
+        import torch
+
+        cuda = [t for t in tens if t.is_cuda]
+        if cuda:
+            check(lib.aps_synchronize())
+            torch.cuda.current_stream().synchronize()  # torch produced them; the library copies on its own stream
+        dst = torch.empty(shape, dtype=torch.uint8, device=cuda[0].device if cuda else "cpu")
+    else:
+        dst = np.empty(shape, np.uint8)
+    check(lib.aps_montage_pair(ptr(imgs[0]), h1, w1, ptr(imgs[1]), h2, w2, ptr(dst)))
+    return dst

@@ -1030,7 +1030,8 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     rank through the planar compositor, also when `cameras` are given.
     input['showPanoramaImgsNums'] / input['showCropBoundingBox'] are ignored here: no annotated panorama is produced (a
     rank renders a shard of the tiles; annotate the combined result with renderPanorama.annotate_panorama, or use
-    pipeline.stitch, whose info['annotated'] carries it).
+    pipeline.stitch, whose info['annotated'] carries it).  input['showKeypointsPlot'] is ignored here too, as the annotation
+    flags are: no match plots are produced (pipeline.stitch fills info['match_plots'], or call imageMatching.matchPlots).
     Returns (panorama of the component that holds the best-connected image, uint8 H x W x 3 CUDA tensor; info dict
     with info["panoramas"]: one entry per connected component of at least two images, in component order)."""
     from . import pipeline as pl

@@ -275,10 +275,14 @@ def extract_features(input, images, times=None):
     return descs, kps
 
 
-def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None):
+def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None, plots=None):
     """featureMatchingPairwise + imageMatching (main.m:95-107) in CSR form.
 
-    Returns dict(pairs=[(i,j)], models=[3x3 j->i], inliers=[K x 2 index arrays], numMatches n x n)."""
+    Returns dict(pairs=[(i,j)], models=[3x3 j->i], inliers=[K x 2 index arrays], numMatches n x n).
+    plots: an optional dict that receives, for every pair handed to RANSAC (refineMatch's pairs: candidates with at least 4
+    matches), {(i, j): {'putative': K x 2, 'inliers': K' x 2}} - the 1-based index lists refineMatch plots under
+    input.showKeypointsPlot (imageMatching.m:257-269), before and whatever the acceptance test of :150 says; a pair whose
+    model was not found has no inliers."""
     n = len(descs)
     t0 = time.perf_counter()
     if any(isinstance(d, fm.binaryFeatures) for d in descs):  # detector = 'FAST': the batched Hamming matcher, same CSR
@@ -305,6 +309,10 @@ def match_and_verify(input, descs, kps, seed=0, times=None, pair_subset=None):
         for w, (i, j, s, e) in enumerate(work):
             nf = e - s
             ni = int(ninl[w]) if found[w] else 0
+            if plots is not None:
+                sel = np.nonzero(mask[wptr[w]:wptr[w + 1]])[0] if found[w] else np.zeros(0, np.int64)
+                both = np.stack([ii[s:e], jj[s:e]], axis=1).astype(np.int64)
+                plots[(i, j)] = {"putative": both, "inliers": both[sel]}
             if ni > 8 + 0.3 * nf:  # imageMatching.m:150
                 sel = np.nonzero(mask[wptr[w]:wptr[w + 1]])[0]
                 out["pairs"].append((i, j))
@@ -586,13 +594,14 @@ def rescale_K(K, old_hw, new_hw):
     return np.diag([sx, sy, 1.0]) @ np.asarray(K, np.float64)
 
 
-def imageMatchingPanoramaConComps(input, images_original, images_processed, descs, kps, seed=0, times=None):
+def imageMatchingPanoramaConComps(input, images_original, images_processed, descs, kps, seed=0, times=None, plots=None):
     """[allMatchesRefined, numMatches, initialTforms, imagesProcessed, ..., concomps] =
     imageMatchingPanoramaConComps(...) (imageMatchingPanoramaConComps.m:39-91) in CSR form: first-pass matching and
     verification, connected components, and - with input.resizeImage and input.resizeImagePanoramaCluster set and
     more than one component - the second pass on images resized per component.
+    plots: match_and_verify's; it holds the lists of the final pass.
     Returns (result dict of match_and_verify, images_processed, descs, kps, ncomp, labels, second_pass: bool)."""
-    res = match_and_verify(input, descs, kps, seed, times)
+    res = match_and_verify(input, descs, kps, seed, times, plots=plots)
     ncomp, labels = connected_components(res["numMatches"])
     second = int(input.get("resizeImage", 0)) == 1 and int(input.get("resizeImagePanoramaCluster", 0)) == 1 and ncomp > 1
     if second:
@@ -600,7 +609,9 @@ def imageMatchingPanoramaConComps(input, images_original, images_processed, desc
         resized = resize_per_component(input, dict(enumerate(images_original)), labels, sizes)
         images_processed = [resized[k] for k in range(len(images_original))]
         descs, kps = extract_features(input, images_processed, times)
-        res = match_and_verify(input, descs, kps, seed, times)
+        if plots is not None:
+            plots.clear()
+        res = match_and_verify(input, descs, kps, seed, times, plots=plots)
     return res, images_processed, descs, kps, ncomp, labels, second
 
 
@@ -615,15 +626,24 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     Every connected component of at least two images is rendered (displayPanorama.m:88-116).  With
     input['showPanoramaImgsNums'] and input['showCropBoundingBox'] both true, info['annotated'] holds, per component, the
     panorama with the images' outlines and numbers (renderPanorama's second output, drawn on the device).
+    With input['showKeypointsPlot'] true, info['match_plots'] holds {(i, j): {'original', 'putative', 'inliers'}}, the three
+    pictures refineMatch shows for a pair handed to RANSAC (im.matchPlots on the final pass's images; resident with device_out),
+    info['match_plot_lists'] the index lists they were drawn from and info['keypoints'] the points those index; over
+    input['keypointsPlotPairs'] when given (a pair RANSAC never saw is a ValueError), over all those pairs otherwise.  When
+    the pictures would exceed input['keypointsPlotLimitBytes'] (default 2^31) the call raises ValueError before drawing any.
+    The panoramas and every other entry of info are the same with and without the flag.
     Returns (panoramas [one per component, in component order], info dict with per-stage wall times in seconds)."""
     times = StageTimes()
+    plots = {} if input.get("showKeypointsPlot") else None
     n = len(images)
     descs, kps = extract_features(input, images, times)
     first_hw = [(int(im_.shape[0]), int(im_.shape[1])) for im_ in images]
     first_counts = [len(k) for k in kps]
     res, images, descs, kps, ncomp, labels, second = imageMatchingPanoramaConComps(
-        input, images if images_original is None else images_original, images, descs, kps, seed, times)
+        input, images if images_original is None else images_original, images, descs, kps, seed, times, plots=plots)
     sizes = [(int(im_.shape[0]), int(im_.shape[1]), 3) for im_ in images]
+    if plots is not None:  # refused before the cameras and the render, which cost more than the check
+        plot_pairs = _match_plot_pairs(input, plots, sizes)
     if second and Ks is not None:  # the intrinsics follow the per-component resize
         Ks = [rescale_K(K, first_hw[k], sizes[k][:2]) for k, K in enumerate(Ks)]
     t0 = time.perf_counter()
@@ -665,4 +685,36 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
         info["ba"] = ba_info
     if annotate:
         info["annotated"] = annotated
+    if plots is not None:
+        info["match_plot_lists"] = {p: plots[p] for p in plot_pairs}
+        info["keypoints"] = kps  # (what the lists index: the final pass's keypoints, one n x 2 (x, y) array per image)
+        info["match_plots"] = _match_plots(images, kps, plots, plot_pairs, device_out)
     return panos, info
+
+
+def _match_plot_pairs(input, plots, sizes):
+    """The pairs input.showKeypointsPlot is served for: input.keypointsPlotPairs, or every pair RANSAC saw; checked against
+    those pairs and against input.keypointsPlotLimitBytes."""
+    asked = input.get("keypointsPlotPairs")
+    pairs = list(plots) if asked is None else [(int(i), int(j)) for i, j in asked]
+    unseen = [p for p in pairs if p not in plots]
+    if unseen:
+        raise ValueError(f"keypointsPlotPairs: no RANSAC ran on {unseen} (0-based (i, j), i < j, candidate pairs with at least 4 matches)")
+    need, limit = im.match_plot_bytes(sizes, pairs), int(input.get("keypointsPlotLimitBytes", 2 ** 31))
+    if need > limit:
+        raise ValueError(f"showKeypointsPlot: the pictures of {len(pairs)} pairs take {need} bytes, above keypointsPlotLimitBytes = "
+                         f"{limit}; name the pairs to plot in keypointsPlotPairs")
+    return pairs
+
+
+def _match_plots(images, kps, plots, pairs, device_out):
+    """im.matchPlots for stitch: resident pictures with device_out, numpy arrays otherwise, whatever kind the images are."""
+    import torch
+
+    used = sorted({k for p in pairs for k in p})  # (only the images of the plotted pairs move)
+    if device_out:
+        views = {k: images[k] if _capi.is_torch(images[k]) and images[k].is_cuda else torch.as_tensor(np.asarray(images[k])).cuda()
+                 for k in used}
+    else:
+        views = {k: images[k].cpu().numpy() if _capi.is_torch(images[k]) else np.asarray(images[k]) for k in used}
+    return im.matchPlots(views, kps, {p: plots[p]["putative"] for p in pairs}, {p: plots[p]["inliers"] for p in pairs}, pairs)

@@ -377,37 +377,10 @@ def annotate_panorama(pano, polys, anchors, colors=None, lineWidth=2):
     colors = vivid_palette(n) if colors is None else np.ascontiguousarray(np.asarray(colors).reshape(-1, 3).astype(np.uint8))
     if anchors.shape[0] != n or colors.shape[0] != n:
         raise ValueError("polys, anchors and colors must have one row per polygon")
+    from .imageProcessing import drawing_buffers
+
     drawn = C.c_int(0)
-    is_t = _capi.is_torch(pano)
-    if not is_t:
-        pano = np.asarray(pano)
-    if pano.ndim == 2:
-        pano = pano[:, :, None]
-    if str(pano.dtype).split(".")[-1] != "uint8" or pano.ndim != 3 or int(pano.shape[2]) not in (1, 3):
-        raise ValueError(f"pano must be uint8 H x W, H x W x 1 or H x W x 3, got {pano.dtype} {tuple(pano.shape)}")
-    if is_t and pano.is_cuda:
-        check(lib.aps_synchronize())  # the panorama may still be in flight on the library's stream of this thread
-    # `own`: src is a copy made here (a replicated channel, a cropped view made contiguous), so it is drawn on in place:
-    # one copy of the canvas either way
-    if int(pano.shape[2]) == 1:
-        src, own = (pano.expand(-1, -1, 3).contiguous() if is_t else np.repeat(pano, 3, axis=2)), True
-    elif is_t:
-        src, own = (pano, False) if pano.is_contiguous() else (pano.contiguous(), True)
-    else:
-        src, own = (pano, False) if pano.flags.c_contiguous else (np.ascontiguousarray(pano), True)
-    H, W = int(src.shape[0]), int(src.shape[1])
-    if own:
-        dst = src
-    elif is_t:
-        import torch
-
-        dst = torch.empty_like(src)
-    else:
-        dst = np.empty_like(src)
-    if is_t and src.is_cuda:
-        import torch
-
-        torch.cuda.current_stream().synchronize()  # torch produced them; the library draws on its own stream
+    src, dst, H, W = drawing_buffers(pano, "pano")
     check(lib.aps_annotate_panorama(ptr(src), H, W, ptr(polys), ptr(anchors), ptr(colors), n, int(lineWidth), ptr(dst),
                                     C.byref(drawn)))
     return dst, int(drawn.value)

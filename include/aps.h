@@ -561,6 +561,42 @@ int aps_crop_nonzero_bbox(const uint8_t* img, int64_t h, int64_t w, int layout, 
 int aps_annotate_panorama(const uint8_t* src, int64_t h, int64_t w, const double* polys, const double* anchors,
                           const uint8_t* colors, int n, int line_width, uint8_t* dst, int* n_drawn);
 
+/* Marks on an image: the drawing under showMatchedFeatures(I1, I2, p1, p2, 'montage') as refineMatch calls it with
+ * input.showKeypointsPlot (imageMatching.m:257-269), and under keypoint plots.  The toolbox call is closed; the raster rule is
+ * this library's own ("Mark contract"; parity with MATLAB unpinned), integer arithmetic throughout, restated byte
+ * for byte by tests/marks_mirror.py.  A mark is a segment or a ring with its own line width and opaque colour. */
+#define APS_MARK_SEGMENT 0
+#define APS_MARK_RING    1
+typedef struct aps_mark {
+    double x0, y0, x1, y1;   /* ring: x1 = radius, y1 unused */
+    int32_t kind, line_width;
+    uint8_t rgb[3], reserved;
+} aps_mark;
+
+/*   src, dst : uint8 h x w x 3, APS_IMG_U8_HWC, host or device memory each; dst == src draws in place, otherwise the two must
+ *              not overlap and src is never written.
+ *   marks    : n marks, HOST memory.  Coordinates are 1-based f64, x = column (pixel (r, c) has its centre at x = c, y = r),
+ *              quantised to 1/16 px.  A segment paints every pixel whose centre lies within line_width / 2 of the closed segment
+ *              (round caps; equal end points give a dot).  A ring paints every pixel whose centre lies between radius -
+ *              line_width / 2 (not below 0) and radius + line_width / 2 of the centre (x0, y0), both closed; radius 0 is a disc.
+ *   A mark is valid when its coordinates are finite with |v| <= 2^20 and, for a ring, the radius is finite with
+ *   0 <= radius <= 4096 (y1 is not looked at); the others are skipped and not counted.  Marks are drawn in ascending index: where
+ *   they overlap the highest index wins.  Everything is clipped; a valid mark wholly outside the canvas counts.
+ *   *n_drawn (host memory, may be NULL): the number of valid marks.  n = 0 is a plain copy.
+ * Cost: one copy src -> dst (none in place), then one workgroup per 64 x 64 tile that a mark can touch; one host
+ * synchronisation, at the end of the call (a resident result is complete on return).  Runs on the calling thread's stream.
+ * Errors, all before any device work and with nothing written: APS_E_ARG for a NULL pointer (marks may be NULL when n == 0),
+ * h or w < 1 (or above 2^31 - 1), n < 0, any mark with a kind other than 0 / 1 or a line_width outside 1..64, partially
+ * overlapping src / dst, or tile lists of 2^31 - 1 entries or more. */
+int aps_draw_marks(const uint8_t* src, int64_t h, int64_t w, const aps_mark* marks, int64_t n, uint8_t* dst,
+                   int64_t* n_drawn);
+
+/* The 'montage' of showMatchedFeatures: dst = uint8 max(h1, h2) x (w1 + w2) x 3 with img1 (h1 x w1 x 3) in rows 1..h1, columns
+ * 1..w1, img2 in rows 1..h2, columns w1 + 1..w1 + w2, and 0 everywhere else.  Each pointer is host or device memory; dst must
+ * not overlap either source.  Two strided copies and a fill on the calling thread's stream; complete on return.
+ * Errors: APS_E_ARG for a NULL pointer, a size below 1 (or a destination side above 2^31 - 1), or an overlapping destination. */
+int aps_montage_pair(const uint8_t* img1, int64_t h1, int64_t w1, const uint8_t* img2, int64_t h2, int64_t w2, uint8_t* dst);
+
 /* SURVEY 8(f) rank 1 -- the overlap statistics of gainCompensationRKf (PP/gainCompensation/gainCompensationRKf.m:96-149,
  * 239-367): every `stride`-th canvas point (1-based coordinates, :106-107) that two images i < j both cover
  * (front, inside, tent weight > 0) adds 1 to n_ij(i,j) and the two bilinear RAW (0..255) colour samples to
