@@ -139,6 +139,11 @@ class aps_fast_uniform_params(C.Structure):
     _fields_ = [("strongest", aps_fast_strongest_params), ("grid_rows", C.c_int), ("grid_cols", C.c_int)]
 
 
+class aps_fast_orb_params(C.Structure):
+    _fields_ = [("pyramid", aps_fast_pyramid_params), ("select", C.c_int), ("n_select", C.c_int), ("grid_rows", C.c_int),
+                ("grid_cols", C.c_int)]
+
+
 APS_MARK_SEGMENT, APS_MARK_RING = 0, 1
 
 
@@ -277,6 +282,10 @@ _SIGNATURES = {
     "aps_surf_extract_batch_uniform": [C.POINTER(aps_surf_view), _i, _i, _i, _i, _i, C.POINTER(aps_surf_uniform_params),
                                        _i, _i64, _i64],
     "aps_fast_extract_batch": [C.POINTER(aps_fast_view), _i, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _i, _i64, _i64],
+    "aps_fast_orb_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_orb_params), _vp, _i, _i64, _vp, _i64,
+                             _vp, _i64, C.POINTER(_i64)],
+    "aps_fast_orb_extract_batch": [C.POINTER(aps_fast_view), _i, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _i, _i64, _i64],
+    "aps_orb_pattern": [_vp, _vp, _vp, C.POINTER(_i)],
     "aps_uniform_quota": [_vp, _i, _i64, _vp],
     "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
 }

@@ -1,4 +1,4 @@
-// fast.hip — FAST-9 corners + FREAK 512-bit descriptors on the gfx950.
+// fast.hip — FAST-9 corners + FREAK 512-bit (or, on request, ORB 256-bit) descriptors on the gfx950.
 // Stands behind PP/featureMatching/getFeaturePoints.m:51-52,71-74 (rgb2gray -> detectFASTFeatures(gray) -> extractFeatures, which
 // describes corner points with FREAK).  The toolbox functions are closed code; the algorithms are FAST-9 of Rosten & Drummond and
 // FREAK of Alahi, Ortiz & Vandergheynst, restated in DESIGN.md "FAST/FREAK contract".  Every stored value and every discrete
@@ -34,6 +34,9 @@
 //                         strongest_flag_kernel (rank within the level < k_l, written back by index), strongest_word_kernel (ballot),
 //                         scan of the popcounts; then strongest_compact_kernel (canonical order again)
 //   freak_keypoint_kernel on the kept keypoints only; strongest_aux_kernel writes f32(R) into aux[3]
+// aps_fast_orb_extract and aps_fast_orb_extract_batch (DESIGN.md "FAST/ORB contract") are these chains with another describer (Describer):
+//   orb_keypoint_kernel   one wave per keypoint: the 31 x 31 patch of its level's plane into LDS, the intensity-centroid moments on the
+//                         way, bin, a 27 x 27 plane of 5 x 5 box sums in LDS, 64 lanes x 4 steered tests = 256 bits in 32 bytes
 // aps_fast_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with fast_segment_kernel and select_uniform in the place of
 // select_by_key: the k_l rows of a level are spread over the cells of a grid on the level's plane.
 #include <hip/hip_runtime.h>
@@ -581,6 +584,191 @@ __global__ __launch_bounds__(256) void strongest_aux_kernel(const long long* __r
     if (i < n) aux[(size_t)i * 4 + 3] = (float)kresp[i];
 }
 
+// ---- ORB: intensity-centroid orientation and steered BRIEF, 256 bits (DESIGN.md "FAST/ORB contract") -------------------------
+constexpr int kOrbTests = 256, kOrbBytes = 32;
+constexpr int kOrbDiscR = 15, kOrbDisc = 709;        // the moments' disc u^2 + v^2 <= 225 and its pixels
+constexpr int kOrbRadius = 13, kOrbBoxR = 2;         // test points lie in x^2 + y^2 <= 169, steered or not; S is a 5 x 5 box sum
+constexpr int kOrbReach = kOrbRadius + kOrbBoxR + 1;
+constexpr int kOrbPatch = 2 * kOrbDiscR + 1, kOrbPatchLd = 32;  // the 31 x 31 patch in LDS, rows of 32 bytes
+constexpr int kOrbSums = 2 * kOrbRadius + 1;                    // the 27 x 27 plane of box sums
+constexpr int kFreakMargin = 23;  // host_pattern().margin: the candidates are those of the FREAK entries (orb_describe checks it)
+static_assert(kOrbReach == 16 && kOrbReach <= kFreakMargin, "the descriptor's reach stays within the margin of the candidates");
+static_assert(kOrbDiscR <= kFreakMargin, "the staged patch stays inside the level's plane");
+static_assert(kOrbRadius + kOrbBoxR <= kOrbDiscR, "every box sum lies within the staged patch");
+static_assert(kOrbPatch <= kOrbPatchLd && 2 * kOrbSums <= 64 && kOrbTests == 4 * 64, "orb_keypoint_kernel's lane maps");
+
+// what the keypoint kernel reads: the steered tests of bins 0..63 (the quarter turns are applied in the kernel) and FREAK's cos_sin
+struct OrbDev {
+    char4 test[64][kOrbTests];  // dxa, dya, dxb, dyb
+    short2 cos_sin[kBins];
+};
+struct OrbTables {
+    int32_t tests[kOrbTests][4];  // xa, ya, xb, yb
+    OrbDev dev;
+    int reach;
+    OrbTables() {
+        std::memset(this, 0, sizeof *this);
+        // the contract's generator: a stated deviation from the trained table, as FREAK's pairs are
+        unsigned long long s = 1;
+        const auto draw = [&] {
+            s = (1103515245ULL * s + 12345ULL) & 0x7fffffffULL;
+            return (int)((s >> 16) % 27) - 13;
+        };
+        for (int n = 0; n < kOrbTests;) {
+            const int xa = draw(), ya = draw(), xb = draw(), yb = draw();
+            bool ok = xa * xa + ya * ya <= kOrbRadius * kOrbRadius && xb * xb + yb * yb <= kOrbRadius * kOrbRadius &&
+                      (xa - xb) * (xa - xb) + (ya - yb) * (ya - yb) >= 16;
+            for (int i = 0; ok && i < n; ++i) {
+                const int32_t* t = tests[i];
+                ok = !((t[0] == xa && t[1] == ya && t[2] == xb && t[3] == yb) || (t[0] == xb && t[1] == yb && t[2] == xa && t[3] == ya));
+            }
+            if (!ok) continue;
+            tests[n][0] = xa, tests[n][1] = ya, tests[n][2] = xb, tests[n][3] = yb;
+            ++n;
+        }
+        const FreakHost& h = host_pattern();
+        int far = 0;
+        for (int k = 0; k < kBins; ++k) dev.cos_sin[k] = make_short2((short)h.cos_sin[k][0], (short)h.cos_sin[k][1]);
+        for (int k = 0; k < 64; ++k)
+            for (int i = 0; i < kOrbTests; ++i) {
+                int d[4];
+                for (int j = 0; j < 4; j += 2) {
+                    const int x = tests[i][j], y = tests[i][j + 1], c = h.cos_sin[k][0], sn = h.cos_sin[k][1];
+                    d[j] = (x * c - y * sn + (1 << 13)) >> 14;  // (arithmetic shift)
+                    d[j + 1] = (x * sn + y * c + (1 << 13)) >> 14;
+                    far = std::max(far, std::max(std::abs(d[j]), std::abs(d[j + 1])));
+                }
+                dev.test[k][i] = make_char4((signed char)d[0], (signed char)d[1], (signed char)d[2], (signed char)d[3]);
+            }
+        reach = far + kOrbBoxR + 1;
+    }
+};
+const OrbTables& orb_tables() {
+    static const OrbTables t;
+    return t;
+}
+
+// One wave per keypoint, the view in blockIdx.y and the row in blockIdx.x * 4 + wave, as freak_keypoint_kernel.  Every wave of the
+// capacity grid passes every barrier; the ones beyond the view's rows do no work.  A wave's stages, each on its own slice of LDS:
+//   the 31 x 31 patch of the level's plane, byte loads (lane = column, two rows at a time), with the two moments taken from the
+//     loaded values on the way - every byte lies in rows y - 15 .. y + 15 and columns x - 15 .. x + 15 of the level's plane, which
+//     the margin (23 >= 15) keeps inside it, so no load leaves the view's planes whatever the plane's byte offset
+//   the bin, as FREAK's: 4 bins per lane, wave maximum, ballot
+//   the 27 x 27 plane of 5 x 5 box sums (u16, <= 6375): 54 lanes, a column and half of the rows each, sliding down the patch
+//   4 tests per lane on the bin's table (bins 64..255: the quarter turn of bin & 63's), a nibble each; even lanes write the byte
+__global__ __launch_bounds__(256) void orb_keypoint_kernel(const uint8_t* __restrict__ planes, const FastPlan P, const OrbDev* __restrict__ tb,
+                                                           const uint8_t* __restrict__ kept, const Keypoint* __restrict__ kps,
+                                                           const ViewRows<uint8_t>* __restrict__ views, int desc_layout, long long ldd,
+                                                           long long ldl) {
+    __shared__ uint8_t s_g[4][kOrbPatch * kOrbPatchLd];
+    __shared__ unsigned short s_S[4][kOrbSums * kOrbSums + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const ViewRows<uint8_t> V = views[blockIdx.y];
+    const unsigned int kidx = blockIdx.x * 4 + wave;  // the row of the view
+    const bool active = kidx < V.rows;
+    uint8_t* __restrict__ desc = V.desc;
+    double* __restrict__ loc = V.loc;
+    float* __restrict__ aux = V.aux;
+    planes += blockIdx.y * P.view_plane;
+    kept += blockIdx.y * P.view_plane;
+    Keypoint kp{0, 0, 0, 0};
+    if (active) kp = kps[V.kp0 + kidx];
+    const FastLevel& L = P.lv[__builtin_amdgcn_readfirstlane(kp.level)];  // (one keypoint per wave)
+    // ---- the patch and the moments: m10 = sum u g, m01 = sum v g over the disc (|m| <= 255 * 4528 < 2^21) -----------------
+    int m10 = 0, m01 = 0;
+    {
+        const int c = lane & 31, r0 = lane >> 5;
+        if (active && c < kOrbPatch) {
+            const uint8_t* __restrict__ src = planes + L.plane0 + (size_t)(kp.y - kOrbDiscR + r0) * L.w + (kp.x - kOrbDiscR + c);
+#pragma unroll
+            for (int i = 0; i < (kOrbPatch + 1) / 2; ++i) {
+                const int r = r0 + 2 * i;
+                if (r < kOrbPatch) {
+                    const int v = src[(size_t)(2 * i) * L.w];
+                    s_g[wave][r * kOrbPatchLd + c] = (uint8_t)v;
+                    const int du = c - kOrbDiscR, dv = r - kOrbDiscR;
+                    if (du * du + dv * dv <= kOrbDiscR * kOrbDiscR) {
+                        m10 += du * v;
+                        m01 += dv * v;
+                    }
+                }
+            }
+        }
+    }
+    const long long mx = wave_sum_i32(m10), my = wave_sum_i32(m01);
+    // lane holds bins 4 * lane .. 4 * lane + 3: the lowest lane among equals holds the lowest bin among equals
+    long long best = 0;
+    int best_k = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const short2 cs = tb->cos_sin[4 * lane + j];
+        const long long v = mx * cs.x + my * cs.y;
+        if (j == 0 || v > best) {
+            best = v;
+            best_k = 4 * lane + j;
+        }
+    }
+    const long long top = wave_max(best);
+    const unsigned long long tie = __ballot(best == top);
+    const int bin = __shfl(best_k, __ffsll((long long)tie) - 1);
+    __syncthreads();  // (the patch is written)
+    // ---- S[r][c] = the box sum centred on patch pixel (r + 2, c + 2), offset (c - 13, r - 13) from the keypoint ------------
+    if (active && lane < 2 * kOrbSums) {
+        const int c = lane < kOrbSums ? lane : lane - kOrbSums, ra = lane < kOrbSums ? 0 : (kOrbSums + 1) / 2;
+        const uint8_t* p = &s_g[wave][c];
+        const auto hsum = [&](int r) {
+            const uint8_t* q = p + r * kOrbPatchLd;
+            return (int)q[0] + q[1] + q[2] + q[3] + q[4];
+        };
+        int h0 = hsum(ra), h1 = hsum(ra + 1), h2 = hsum(ra + 2), h3 = hsum(ra + 3);
+#pragma unroll
+        for (int i = 0; i < (kOrbSums + 1) / 2; ++i) {
+            const int r = ra + i;
+            if (r < kOrbSums) {
+                const int h4 = hsum(r + 4);
+                s_S[wave][r * kOrbSums + c] = (unsigned short)(h0 + h1 + h2 + h3 + h4);
+                h0 = h1, h1 = h2, h2 = h3, h3 = h4;
+            }
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+    // ---- descriptor: bit i = S(a_i) < S(b_i); lane holds tests 4 * lane .. 4 * lane + 3, bits (4 * lane) % 8 .. of byte lane / 2 ------
+    const int q = bin >> 6, cq = q == 0 ? 1 : q == 2 ? -1 : 0, sq = q == 1 ? 1 : q == 3 ? -1 : 0;  // the quarter turn (dx, dy) -> (-dy, dx), q times
+    const uint4 raw = *reinterpret_cast<const uint4*>(&tb->test[bin & 63][4 * lane]);
+    const unsigned int words[4] = {raw.x, raw.y, raw.z, raw.w};
+    const auto sum_at = [&](int dx, int dy) {
+        const int x = dx * cq - dy * sq, y = dx * sq + dy * cq;
+        return (int)s_S[wave][(y + kOrbRadius) * kOrbSums + x + kOrbRadius];
+    };
+    unsigned int nib = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const unsigned int w = words[t];
+        const int a = sum_at((signed char)(w & 255u), (signed char)((w >> 8) & 255u));
+        const int b = sum_at((signed char)((w >> 16) & 255u), (signed char)(w >> 24));
+        nib |= (a < b ? 1u : 0u) << t;
+    }
+    const unsigned int byte = nib | (unsigned int)__shfl_xor((int)nib, 1) << 4;
+    if (!(lane & 1)) {
+        if (desc_layout == APS_ROWMAJOR)
+            desc[(size_t)kidx * ldd + (lane >> 1)] = (uint8_t)byte;
+        else
+            desc[(size_t)(lane >> 1) * ldd + kidx] = (uint8_t)byte;
+    }
+    if (lane == 0) {
+        // the pixel's centre in level-0 coordinates, as freak_keypoint_kernel's
+        loc[kidx] = (double)((2LL * kp.x + 1) * P.lv[0].w) / (double)(2LL * L.w) + 0.5;
+        loc[(size_t)ldl + kidx] = (double)((2LL * kp.y + 1) * P.lv[0].h) / (double)(2LL * L.h) + 0.5;
+        if (aux) {
+            aux[(size_t)kidx * 4 + 0] = (float)kept[L.plane0 + (size_t)kp.y * L.w + kp.x];
+            aux[(size_t)kidx * 4 + 1] = (float)bin;
+            aux[(size_t)kidx * 4 + 2] = (float)kp.level;
+            aux[(size_t)kidx * 4 + 3] = 0.0f;
+        }
+    }
+}
+
 // ---- host: the plan and the chain ----------------------------------------------------------------------------------------
 struct HostPlan {
     FastPlan dev;
@@ -745,20 +933,39 @@ void freak_describe(const HostPlan& hp, const FastFront& F, const Keypoint* kps,
     check_launch("freak_keypoint_kernel");
 }
 
-// aps_fast_extract, aps_fast_extract_pyramid and aps_fast_extract_batch behind their argument checks (check_args, check_pyramid), on
-// the plan's group of views.  One read-back: the views' counts.
+// the same for ORB: the level planes in the integral images' place
+void orb_describe(const HostPlan& hp, const FastFront& F, const Keypoint* kps, GroupOut<uint8_t, aps_fast_view>& out, unsigned int most) {
+    APS_REQUIRE(host_pattern().margin >= kFreakMargin && orb_tables().reach == kOrbReach, APS_E_INTERNAL, "ORB tables reach %d pixels, margin %d",
+                orb_tables().reach, host_pattern().margin);
+    Ws<OrbDev> d_tb(1);
+    Prof prof("orb_keypoint");  // (with the upload of the pattern tables)
+    APS_HIP(hipMemcpyAsync(d_tb, &orb_tables().dev, sizeof(OrbDev), hipMemcpyHostToDevice, stream()));
+    orb_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.planes, hp.dev, d_tb, F.kept, kps, out.d_rows, out.desc_layout,
+                                                                          (long long)out.ldd, (long long)out.ldl);
+    check_launch("orb_keypoint_kernel");
+}
+
+// what a chain knows about its descriptor: the bytes of a row and the launch that writes the rows
+struct Describer {
+    size_t width;
+    void (*describe)(const HostPlan&, const FastFront&, const Keypoint*, GroupOut<uint8_t, aps_fast_view>&, unsigned int);
+};
+constexpr Describer kFreak = {64, freak_describe}, kOrb = {kOrbBytes, orb_describe};
+
+// aps_fast_extract, aps_fast_extract_pyramid, aps_fast_extract_batch and the ORB entries without a selection behind their argument
+// checks (check_args, check_pyramid), on the plan's group of views.  One read-back: the views' counts.
 void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, int desc_layout,
-                int64_t ldd, int64_t ldl) {
+                int64_t ldd, int64_t ldl, const Describer& D = kFreak) {
     ctx();
     const FastPlan& P = hp.dev;
     const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin, nv = P.nv;
     for (int v = 0; v < nv; ++v) views[v].count = 0;
     unsigned int room[kGroupViews], n[kGroupViews];
-    check_views(views, nv, 64, desc_layout, ldd, ldl, room);
+    check_views(views, nv, D.width, desc_layout, ldd, ldl, room);
     if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
     FastFront F;
     fast_front(views, channels, img_layout, params, hp, F);
-    GroupOut<uint8_t, aps_fast_view> out(views, nv, room, 64, 64, desc_layout, ldd, ldl, nullptr, nullptr);
+    GroupOut<uint8_t, aps_fast_view> out(views, nv, room, D.width, D.width, desc_layout, ldd, ldl, nullptr, nullptr);
     ViewLimits lim = {};
     size_t kcap = 0;
     for (int v = 0; v < nv; ++v) kcap += lim.cap[v] = room[v];
@@ -774,7 +981,7 @@ void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fa
                                                                           (unsigned int)std::min<size_t>(kcap, 0xffffffffu));
             check_launch("fast_emit_kernel");
         }
-        freak_describe(hp, F, kps, out, *std::max_element(room, room + nv));
+        D.describe(hp, F, kps, out, *std::max_element(room, room + nv));
     }
     read_back(d_n.get(), n, nv);  // the one read-back of the chain
     settle_counts(views, nv, n, n, params->max_features, "FAST");
@@ -838,7 +1045,8 @@ void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
 // aps_fast_extract_strongest and, with grid_rows > 0, aps_fast_extract_uniform (each level's k_l spread over the cells of its plane)
 // behind their argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.
 void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, long long N,
-                     int grid_rows, int grid_cols, uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+                     int grid_rows, int grid_cols, uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count,
+                     const Describer& D = kFreak) {
     ctx();
     *count = 0;
     const FastPlan& P = hp.dev;
@@ -872,7 +1080,7 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     if (K == 0) return;
     APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
     if (desc_layout == APS_ROWMAJOR)
-        APS_REQUIRE(ldd >= 64, APS_E_DIM, "ldd < 64");
+        APS_REQUIRE(ldd >= (int64_t)D.width, APS_E_DIM, "ldd < %d", (int)D.width);
     else
         APS_REQUIRE(ldd >= cap, APS_E_DIM, "ldd < cap");
     APS_REQUIRE(ldl >= cap, APS_E_DIM, "ldl < cap");
@@ -906,8 +1114,8 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
         d_total = prefix.get() + n_words;
     }
     const unsigned int first = 0;
-    GroupOut<uint8_t, aps_fast_view> out(&view, 1, &K, 64, 64, desc_layout, ldd, ldl, &first, &K);
-    freak_describe(hp, F, kps, out, K);
+    GroupOut<uint8_t, aps_fast_view> out(&view, 1, &K, D.width, D.width, desc_layout, ldd, ldl, &first, &K);
+    D.describe(hp, F, kps, out, K);
     if (out.aux[0].present()) {
         strongest_aux_kernel<<<cdiv(K, 256), 256, 0, stream()>>>(kresp, K, out.aux[0]);
         check_launch("strongest_aux_kernel");
@@ -970,6 +1178,72 @@ int aps_fast_extract_batch(aps_fast_view* views, int n_views, int height, int wi
         check_pyramid(params->n_levels, params->scale_num, params->scale_den);
         fast_chain(views, channels, img_layout, &params->fast,
                    make_plan(height, width, params->n_levels, params->scale_num, params->scale_den, n_views), desc_layout, ldd, ldl);
+    });
+}
+
+int aps_fast_orb_extract(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_orb_params* params,
+                         uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        const aps_fast_pyramid_params& pyr = params->pyramid;
+        APS_REQUIRE(params->select >= 0 && params->select <= 2, APS_E_ARG, "select must be 0 (none), 1 (strongest-N) or 2 (uniform-N)");
+        if (params->select == 1) APS_REQUIRE(params->n_select >= 1, APS_E_ARG, "n_select (NumStrongest) must be at least 1");
+        if (params->select == 2) check_uniform(params->n_select, params->grid_rows, params->grid_cols);
+        if (params->select == 0) {
+            fast_single(img, desc, loc, aux, cap, count, [&](aps_fast_view* view) {
+                check_args(view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
+                check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+                fast_chain(view, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
+                           desc_layout, ldd, ldl, kOrb);
+            });
+            return;
+        }
+        const aps_fast_view view = {img, desc, loc, aux, cap, 0};
+        check_args(&view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
+        check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+        const bool grid = params->select == 2;
+        strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den), params->n_select,
+                        grid ? params->grid_rows : 0, grid ? params->grid_cols : 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count, kOrb);
+    });
+}
+
+int aps_fast_orb_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels, int img_layout,
+                               const aps_fast_pyramid_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] {
+        APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+        check_args(views, n_views, height, width, channels, img_layout, params->fast, desc_layout);
+        check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+        fast_chain(views, channels, img_layout, &params->fast,
+                   make_plan(height, width, params->n_levels, params->scale_num, params->scale_den, n_views), desc_layout, ldd, ldl, kOrb);
+    });
+}
+
+int aps_orb_pattern(int32_t* tests, int32_t* table, int32_t* disc, int* reach) {
+    return guarded([&] {
+        const OrbTables& t = orb_tables();
+        if (tests) std::memcpy(tests, t.tests, sizeof t.tests);
+        for (int k = 0; table && k < kBins; ++k)
+            for (int i = 0; i < kOrbTests; ++i) {
+                const char4 e = t.dev.test[k & 63][i];
+                int d[4] = {e.x, e.y, e.z, e.w};
+                for (int q = 0; q < k >> 6; ++q)  // exact quarter turns (dx, dy) -> (-dy, dx)
+                    for (int j = 0; j < 4; j += 2) {
+                        const int dx = d[j];
+                        d[j] = -d[j + 1];
+                        d[j + 1] = dx;
+                    }
+                for (int j = 0; j < 4; ++j) table[((size_t)k * kOrbTests + i) * 4 + j] = d[j];
+            }
+        int n = 0;
+        for (int v = -kOrbDiscR; disc && v <= kOrbDiscR; ++v)  // ascending (v, u)
+            for (int u = -kOrbDiscR; u <= kOrbDiscR; ++u)
+                if (u * u + v * v <= kOrbDiscR * kOrbDiscR) {
+                    disc[2 * n] = u;
+                    disc[2 * n + 1] = v;
+                    ++n;
+                }
+        APS_REQUIRE(!disc || n == kOrbDisc, APS_E_INTERNAL, "the disc holds %d pixels", n);
+        if (reach) *reach = t.reach;
     });
 }
 

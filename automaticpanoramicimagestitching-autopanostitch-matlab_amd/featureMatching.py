@@ -894,6 +894,16 @@ def surf_extract_batch(input, images, device_out=False, want_aux=False, points_d
 
 
 FREAK_BYTES = 64
+ORB_BYTES = 32
+
+
+def _descriptor_method(input):
+    """input.DescriptorMethod (extractFeatures' Method) of detector = 'FAST': 'FREAK' (the default when the key is absent) or 'ORB';
+    anything else is a ValueError, raised before any library call."""
+    method = input.get("DescriptorMethod", "FREAK")
+    if method not in ("FREAK", "ORB"):
+        raise ValueError(f"input.DescriptorMethod must be 'FREAK' or 'ORB', not {method!r}")
+    return method
 
 
 def _fast_params(input):
@@ -919,6 +929,24 @@ def _fast_strongest_params(input, n_levels, n=None):
     return p
 
 
+def _fast_plan_pixels(h, w, pyramid):
+    """The pixels of all levels of aps_fast_pyramid_plan's plan for an h x w image: what the first capacity is sized by."""
+    hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
+    check(lib.aps_fast_pyramid_plan(h, w, pyramid.n_levels, pyramid.scale_num, pyramid.scale_den, hs, ws, C.byref(used)))
+    return sum(hs[l] * ws[l] for l in range(used.value))
+
+
+def _fast_orb_params(input, n_levels, uniform):
+    """aps_fast_orb_params of fast_extract's keys: the pyramid, and the selection that NumStrongest or NumUniform asks for."""
+    p = _capi.aps_fast_orb_params()
+    p.pyramid = _fast_pyramid_params(input, n_levels)
+    if uniform:
+        p.select, p.n_select, p.grid_rows, p.grid_cols = 2, *uniform
+    elif "NumStrongest" in input:
+        p.select, p.n_select = 1, int(input["NumStrongest"])
+    return p
+
+
 def fast_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False):
     """aps_fast_extract with automatic capacity: returns (binaryFeatures, validPts[, aux]); the arguments are sift_extract's.
     Features are n x 64 uint8 (FREAK, 512 bits), on the host or, with device_out, resident; validPts n x 2 [x y] 1-based,
@@ -937,17 +965,31 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
 
     input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps the same number of rows per level as
     NumStrongest = N does, through aps_fast_extract_uniform, but spreads each level's rows over the cells of the grid on the level's
-    plane by water-filling, the largest Harris response first within a cell (DESIGN.md "Uniform-N selection"); aux as above."""
+    plane by water-filling, the largest Harris response first within a cell (DESIGN.md "Uniform-N selection"); aux as above.
+
+    input.DescriptorMethod = 'ORB' (extractFeatures' Method; absent or 'FREAK': the above) describes the same rows - count, validPts,
+    score, level and f32(R) are bit for bit those of the FREAK call with the same keys - with ORB's intensity-centroid orientation
+    and steered BRIEF descriptor through aps_fast_orb_extract (DESIGN.md "FAST/ORB contract"): Features are n x 32 uint8 (256 bits)
+    and aux[:, 1] is the ORB bin.  Any other value is a ValueError."""
+    method = _descriptor_method(input)
     img, h, w, c = _image_hwc(image)
     n_levels = int(input.get("NumLevels", 1))
     uniform = _uniform_keys(input)
+    if method == "ORB":
+        prm = _fast_orb_params(input, n_levels, uniform)
+        cap = max(4096, _fast_plan_pixels(h, w, prm.pyramid) // 64)
+        if prm.select:  # (as _pick_entry: a resident result holds N rows)
+            cap = min(cap, max(prm.n_select, 1))
+        d, pts, aux = _extract_regrow(1, cap, _one_view_call(lib.aps_fast_orb_extract, prm, img, h, w, c, ORB_BYTES),
+                                      _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), ORB_BYTES, np.uint8,
+                                      device_out, points_device, compact, want_aux)[0]
+        f = binaryFeatures(d)
+        return (f, pts, aux) if want_aux else (f, pts)
     if n_levels == 1 and "NumStrongest" not in input and not uniform:
         plain, pixels = (_fast_params(input), lib.aps_fast_extract), h * w
     else:
         plain = (_fast_pyramid_params(input, n_levels), lib.aps_fast_extract_pyramid)
-        hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
-        check(lib.aps_fast_pyramid_plan(h, w, plain[0].n_levels, plain[0].scale_num, plain[0].scale_den, hs, ws, C.byref(used)))
-        pixels = sum(hs[l] * ws[l] for l in range(used.value))
+        pixels = _fast_plan_pixels(h, w, plain[0])
     prm, entry, cap = _pick_entry(input, uniform, max(4096, pixels // 64), plain,
                                   (lambda n: _fast_strongest_params(input, n_levels, n), lib.aps_fast_extract_strongest),
                                   _capi.aps_fast_uniform_params, lib.aps_fast_extract_uniform)
@@ -965,16 +1007,18 @@ def fast_extract_batch(input, images, device_out=False, want_aux=False, points_d
     with NumLevels = 1, where the level is 0).  The arguments are fast_extract's.
 
     input.NumStrongest and input.NumUniform have no group form - a FAST selection group is a level, and a group of views would need
-    views x levels of them: with either key this is a ValueError; call fast_extract per view."""
+    views x levels of them: with either key this is a ValueError; call fast_extract per view.
+
+    input.DescriptorMethod = 'ORB' goes through aps_fast_orb_extract_batch: rows of 32 bytes, as fast_extract's."""
     if "NumStrongest" in input or "NumUniform" in input:
         raise ValueError("fast_extract_batch takes no input.NumStrongest / input.NumUniform: call fast_extract per view")
+    entry, nbytes = ((lib.aps_fast_orb_extract_batch, ORB_BYTES) if _descriptor_method(input) == "ORB"
+                     else (lib.aps_fast_extract_batch, FREAK_BYTES))
     imgs, h, w, c = _group_images(images)
     prm = _fast_pyramid_params(input, int(input.get("NumLevels", 1)))
-    hs, ws, used = (C.c_int * 16)(), (C.c_int * 16)(), C.c_int(0)
-    check(lib.aps_fast_pyramid_plan(h, w, prm.n_levels, prm.scale_num, prm.scale_den, hs, ws, C.byref(used)))
-    cap = max(4096, sum(hs[l] * ws[l] for l in range(used.value)) // 64)  # (no selection key: nothing for _pick_entry to pick)
-    out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_fast_view, lib.aps_fast_extract_batch, prm, imgs, h, w, c, FREAK_BYTES),
-                          _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), FREAK_BYTES, np.uint8, device_out,
+    cap = max(4096, _fast_plan_pixels(h, w, prm) // 64)  # (no selection key: nothing for _pick_entry to pick)
+    out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_fast_view, entry, prm, imgs, h, w, c, nbytes),
+                          _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), nbytes, np.uint8, device_out,
                           points_device, compact, want_aux)
     return [(binaryFeatures(d), pts, aux) if want_aux else (binaryFeatures(d), pts) for d, pts, aux in out]
 
@@ -994,7 +1038,8 @@ def extract_features(input, image, **kw):
 def getFeaturePoints(input, ImageOriginal):
     """[features, validPts] = getFeaturePoints(input, ImageOriginal) (getFeaturePoints.m:1-76) for
     input.detector == 'SIFT' (features Kf x 128 single, unit norm), 'SURF' (Kf x 64 single, unit norm; :54-55) and 'FAST'
-    (binaryFeatures, Kf x 64 uint8 FREAK; :51-52); validPts Kf x 2 double [x y] 1-based.
+    (binaryFeatures, Kf x 64 uint8 FREAK, or Kf x 32 uint8 ORB with input.DescriptorMethod = 'ORB'; :51-52); validPts Kf x 2 double
+    [x y] 1-based.
     The other detectors of the switch (:33-68) are toolbox calls with no device counterpart here."""
     det = input.get("detector", "SIFT")
     if det == "SURF":

@@ -1037,6 +1037,41 @@ int aps_fast_harris(const uint8_t* img, int height, int width, int channels, int
  *   margin                  largest max(|dx|, |dy|) + r + 1 of `fields`: pixels closer than this to the edge are never corners */
 int aps_freak_pattern(int32_t* fields, int32_t* pairs, int32_t* ori_pairs, int32_t* ori_dir, int32_t* cos_sin, int* margin);
 
+/* FAST corners with ORB descriptors (DESIGN.md "FAST/ORB contract"; extractFeatures' Method = 'ORB'): the candidates, their order
+ * and the selections are exactly those of the FAST/FREAK entries for the same image and parameters - count, loc, aux[0], aux[2] and
+ * aux[3] are bit for bit theirs - and each kept row is described with the intensity-centroid orientation and a steered BRIEF
+ * descriptor of 256 bits on its level's plane, integer arithmetic throughout:
+ *   desc : u8 count x 32, leading dimension ldd >= 32 (row-major) / >= cap (column-major); bit i = S(a_i) < S(b_i), LSB first in
+ *          byte i / 8, S the 5 x 5 box sum on the steered point
+ *   aux  : [FAST score, ORB bin 0..255, level, f32(R) with a selection else 0]
+ * select = 0 is aps_fast_extract_pyramid's chain, 1 aps_fast_extract_strongest's with N = n_select, 2 aps_fast_extract_uniform's with
+ * N = n_select on the grid_rows x grid_cols grid.  Capacity, count-only mode, padding, host and device pointers, both layouts,
+ * max_features and APS_E_CAP with nothing written behave as in those entries.  APS_E_ARG before any device work: select outside 0..2,
+ * n_select < 1 with a selection, a grid value outside 1..32 with select = 2, NULL params, and whatever those entries refuse. */
+typedef struct aps_fast_orb_params {
+    aps_fast_pyramid_params pyramid;   /* n_levels = 1: aps_fast_extract's plan */
+    int select;                        /* 0 none | 1 strongest-N | 2 uniform-N */
+    int n_select;                      /* N >= 1 when select != 0 */
+    int grid_rows, grid_cols;          /* 1..32 each when select == 2 */
+} aps_fast_orb_params;
+int aps_fast_orb_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                         const aps_fast_orb_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                         double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* aps_fast_extract_batch with ORB descriptors: the group's protocol (all-or-nothing capacity, counts, one read-back) is that entry's;
+ * the rows of view k are byte for byte those of aps_fast_orb_extract with select = 0 on views[k].img, whatever the other views hold. */
+int aps_fast_orb_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels,
+                               int img_layout, const aps_fast_pyramid_params* params,
+                               int desc_layout, int64_t ldd, int64_t ldl);
+
+/* The integer ORB tables the extractor uses (tests restate the contract on them; host only, needs no device).  Every pointer may be
+ * NULL.  All arrays are host int32, row-major:
+ *   tests  [256][4]        the generated test pattern (xa, ya, xb, yb), unsteered
+ *   table  [256][256][4]   per orientation bin the steered tests (dxa, dya, dxb, dyb)
+ *   disc   [709][2]        the offsets (u, v), u^2 + v^2 <= 225, of the orientation's moments, in ascending (v, u) order
+ *   reach                  largest |d| of `table` + 2 (the box) + 1 = 16, at most aps_freak_pattern's margin */
+int aps_orb_pattern(int32_t* tests, int32_t* table, int32_t* disc, int* reach);
+
 /* ============================================================================================
  * (4d) Uniform-N selection for SIFT, SURF and FAST — selectUniform next to selectStrongest
  * ============================================================================================ */
