@@ -16,7 +16,8 @@
 //              tail; what it cannot certify goes to the fallback list.
 //   streaming  xcd_order / lds_dma_16B / claim_whole_register_file: shared by the candidate kernel and the int8 kernels;
 //              Q8TileDma + Q8Stream: the int8 B-tile stream (LDS image, DMA cadence, hand-over, read-ahead, MFMAs),
-//              stated once - a kernel hands it a consumer for the finished blocks.
+//              stated once for 64 and 128 A rows per wave (512- and 1024-row workgroups: APS_SCREEN_ROWS, cut_rows) - a
+//              kernel hands it a consumer for the finished blocks.
 //   screen     match_screen_i8x16_kernel (16x16x64, default; on Q8Stream) / match_screen_i8_kernel (32x32x32, superseded:
 //              its own loop on the shared pieces): the int8 pass that dismisses rows which provably fail the caller's
 //              filter; <true> writes bounds for the pooled matcher instead.  match_list_i8_kernel (on Q8Stream) +
@@ -1898,38 +1899,53 @@ struct Q8TileDma {
 };
 
 // What a consumer is told, at compile time, about the slice it is handed: the finished block's accumulator parity, the row
-// group g, the block's index within its tile, whether columns >= nB can lie in it (ragged last tile only), and whether it
-// is the last block of the tile BEFORE the one being streamed (it is searched during block 0 of the next).
-template <int PAR, int G, int BLK, bool MASKED, bool PREV>
+// group g, the block's index within its tile (of NBLK), whether columns >= nB can lie in it (ragged last tile only), and
+// whether it is the last block of the tile BEFORE the one being streamed (it is searched during block 0 of the next).
+template <int PAR, int G, int BLK, int NBLK, bool MASKED, bool PREV>
 struct Q8Slice {
     static constexpr int par = PAR, g = G, blk = BLK;
-    static constexpr bool masked = MASKED, prev = PREV, first = BLK == 0, last = BLK == kQBlk - 1;
+    static constexpr bool masked = MASKED, prev = PREV, first = BLK == 0, last = BLK == NBLK - 1;
 };
 
-// The stream of match_screen_i8x16_kernel and match_list_i8_kernel: a 512-thread workgroup, every wave holding 64 A rows
-// (aq: four groups of 16, two 64-byte k-steps), sweeps a B set in tiles of 256 columns on v_mfma_i32_16x16x64_i8.
+// The stream of match_screen_i8x16_kernel and match_list_i8_kernel: a 512-thread workgroup, every wave holding RPW = 64 or
+// 128 A rows (aq: kG = RPW / 16 groups of 16, two 64-byte k-steps), sweeps a B set in tiles of 256 columns on
+// v_mfma_i32_16x16x64_i8.  The bytes of a tile - 32 DMA pieces, one hand-over barrier, its start values - are the same for
+// both row counts; with 128 rows per wave they are paid once per 1024 rows of the workgroup instead of once per 512.
 // LDS: [buf][256][128 B], tile t in buf t % 3; then [buf][256] accumulator start values (cinB, 1 KiB per tile).
-// Software pipeline (the scheme of match_cand_f16_kernel): the consumer's search of block g-1 is cut into four slices that
-// sit between the MFMA groups of block g (two accumulator sets); operand reads run three slots ahead, across block and tile
-// boundaries, so the hand-over sits one block early - tile t+1 must have landed at the barrier after block kLast - 1 of tile
-// t - and tile t is still being read during its last block, hence three buffers.
+// A block is what two accumulator sets of 32 registers hold: kU = 8 / kG sub-blocks of 16 columns x kG row groups - 32
+// columns x 64 rows, or 16 columns x 128 rows.  Its 16 MFMAs run in the order (sub-block, k-step, row group), one operand
+// read (a sub-block's 16 columns x one k-step) feeding kG of them, and are cut into four slices of four MFMAs.
+// Software pipeline (the scheme of match_cand_f16_kernel): the consumer's search of block b-1 is cut into four slices that
+// sit between the MFMA slices of block b (two accumulator sets); operand reads run three reads ahead, across block and tile
+// boundaries, so the hand-over sits early - tile t+1 must have landed at the barrier after column 224 of tile t, the reads
+// reach it from column 224 on - and tile t is still being read during its last block, hence three buffers.
 // A kernel declares `lds`, gathers its rows into aq and calls start(), tile() per tile, finish().
+template <int RPW>
 struct Q8Stream {
+    static_assert(RPW == 64 || RPW == 128, "rows per wave: 64 or 128");
     static constexpr int kLdsBytes = 3 * kQTileBytes + 3 * 1024;
-    static constexpr int kAhead = 3;  // an LDS round trip under load is longer than one slot (four MFMAs + a slice)
+    static constexpr int kAhead = 3;  // an LDS round trip under load is longer than one slice (four MFMAs + a search)
+    static constexpr int kG = RPW / 16;           // row groups per wave
+    static constexpr int kU = 8 / kG;             // 16-column sub-blocks per block
+    static constexpr int kBlkCols = 16 * kU;      // columns per block
+    static constexpr int kBlk = kQTN / kBlkCols;  // blocks per tile
+    static constexpr int kReads = 2 * kU;         // operand reads per block
+    static constexpr int kGps = kG / 4;           // row groups searched per slice
+    static constexpr int kRows = 8 * RPW;         // A rows per workgroup
+    static constexpr int kHandCol = kQTN - 32;    // the hand-over: after the block that ends at this column of the tile
     unsigned char* const lds;
     const Q8TileDma dma;
     const int* const cinB;  // the accumulators' start values, one per column (with_cin; otherwise the kernel zero-fills the area)
     const bool with_cin;
     const int ncin, ntiles;
     const int lane, wave, c, kq;
-    // per-lane read offsets: slot s of a block = sub-block s >> 1, k-step s & 1: row 16 (s >> 1) + c, chunk (4 (s & 1) + kq)
+    // per-lane read offsets: read q of a block = sub-block q >> 1, k-step q & 1: row 16 (q >> 1) + c, chunk (4 (q & 1) + kq)
     // ^ ((c >> 1) & 7)  (the sub-block's 16 rows leave (row >> 1) & 7 alone)
     const int hx;
     const unsigned char* const cin_lds;
-    i32x4 acc[2][2][4];  // [block parity][sub-block][row group]: D[column 4 kq + r of the sub-block][row c of the group]
-    i32x4 bq[4];
-    i32x4 cin[2];  // cin[u]: the start values of the lane's four columns 16 u + 4 kq + r of the NEXT block to start (read one block ahead)
+    i32x4 acc[2][kU][kG];  // [block parity][sub-block][row group]: D[column 4 kq + r of the sub-block][row c of the group]
+    i32x4 bq[4];           // operand read r of the stream (counted over blocks and tiles) lives in bq[r & 3]
+    i32x4 cin[kU];  // cin[u]: the start values of the lane's four columns 16 u + 4 kq + r of the NEXT block to start (read one block ahead)
     int b_cur = 0;  // t % 3
 
     __device__ __forceinline__ Q8Stream(unsigned char* lds_, const signed char* B_, const int* cinB_, int ncin_, bool with_cin_, int nB_)
@@ -1939,12 +1955,13 @@ struct Q8Stream {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
+            for (int u = 0; u < kU; ++u)
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
+                for (int g = 0; g < kG; ++g)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[p][u][g][e] = kScreenNone;
-        cin[0] = cin[1] = i32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < kU; ++u) cin[u] = i32x4{0, 0, 0, 0};
     }
     __device__ __forceinline__ void issue_piece(int t, int buf, int u) const { dma.issue_piece(t, buf, u); }
     // The start values of tile t travel with piece 0 of the tile, issued by wave 0; entries past the set's padded length are
@@ -1952,10 +1969,14 @@ struct Q8Stream {
     __device__ __forceinline__ void issue_cin(int t, int buf) const {
         if (with_cin && wave == 0) lds_dma_16B(cinB + min(t * kQTN + 4 * lane, ncin - 4), dma.lds_base + 3 * kQTileBytes + buf * 1024);
     }
-    __device__ __forceinline__ int slot_off(int s) const { return (s >> 1) * 16 * kDim + ((64 * (s & 1)) ^ hx); }
+    // read r of a tile (r = kReads x block + read of the block), from the lane's row c of the tile's first sub-block
+    __device__ __forceinline__ int read_off(int r) const {
+        const int q = r % kReads;
+        return (r / kReads) * kBlkCols * kDim + (q >> 1) * 16 * kDim + ((64 * (q & 1)) ^ hx);
+    }
 
     // tile 0 in full, piece 0 of tile 1, the first reads
-    __device__ __forceinline__ void start(const i32x4 (&aq)[4][2]) {
+    __device__ __forceinline__ void start(const i32x4 (&aq)[kG][2]) {
         if (ntiles > 0) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) issue_piece(0, 0, u);
@@ -1964,7 +1985,7 @@ struct Q8Stream {
         // touch the resident operand here: otherwise the compiler's pending-load state for these registers reaches the loop
         // header and it drains vmcnt (DMA included) at their first use in EVERY iteration
 #pragma unroll
-        for (int g = 0; g < 4; ++g) asm volatile("" ::"v"(aq[g][0]), "v"(aq[g][1]));
+        for (int g = 0; g < kG; ++g) asm volatile("" ::"v"(aq[g][0]), "v"(aq[g][1]));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (ntiles > 0) {
@@ -1973,18 +1994,18 @@ struct Q8Stream {
                 issue_cin(1, 1);
             }
 #pragma unroll
-            for (int s = 0; s < kAhead; ++s) bq[s] = *reinterpret_cast<const i32x4*>(lds + c * kDim + slot_off(s));
-            cin[0] = *reinterpret_cast<const i32x4*>(cin_lds);
-            cin[1] = *reinterpret_cast<const i32x4*>(cin_lds + 64);
+            for (int r = 0; r < kAhead; ++r) bq[r] = *reinterpret_cast<const i32x4*>(lds + c * kDim + read_off(r));
+#pragma unroll
+            for (int u = 0; u < kU; ++u) cin[u] = *reinterpret_cast<const i32x4*>(cin_lds + 64 * u);
         }
     }
 
     // Tile t.  MASK: its columns may reach past nB (the consumer is told per slice).  tile_start(t) runs before block 0,
-    // consume(Q8Slice, col0) once per slot and row group on the block finished before (col0 = that block's first column; at
-    // t == 0, block 0, there is none: the accumulators still hold kScreenNone and col0 < 0), after_block0(t) when block 0
-    // is through, i.e. when the last block of tile t - 1 has been consumed.
+    // consume(Q8Slice, col0) once per row group - kGps of them after every slice - on the block finished before (col0 = that
+    // block's first column; at t == 0, block 0, there is none: the accumulators still hold kScreenNone and col0 < 0),
+    // after_block0(t) when block 0 is through, i.e. when the last block of tile t - 1 has been consumed.
     template <bool MASK, class TileStart, class Consume, class AfterBlock0>
-    __device__ __forceinline__ void tile(int t, const i32x4 (&aq)[4][2], TileStart&& tile_start, Consume&& consume,
+    __device__ __forceinline__ void tile(int t, const i32x4 (&aq)[kG][2], TileStart&& tile_start, Consume&& consume,
                                          AfterBlock0&& after_block0) {
         const bool more = t + 1 < ntiles;
         const bool more2 = t + 2 < ntiles;
@@ -1995,51 +2016,58 @@ struct Q8Stream {
         const unsigned char* cin_n = cin_lds + b_nxt * 1024;
         b_cur = b_nxt;
         tile_start(t);
-        static_for<0, kQBlk>([&](auto CB) {
+        static_for<0, kBlk>([&](auto CB) {
             constexpr int cb = decltype(CB)::value;
-            constexpr int kLast = kQBlk - 1;
+            constexpr int kLast = kBlk - 1;
             constexpr int par = cb & 1;
-            // DMA: pieces 1..3 of tile t+1 in blocks 0, 2, 4; piece 0 of tile t+2 (and its start values) in the last block
-            // (after the hand-over, into the buffer tile t-1 has just left for good)
-            if (cb == 0 || cb == 2 || cb == 4) {
-                if (more) issue_piece(t + 1, b_nxt, cb / 2 + 1);
-            } else if (cb == kLast) {
+            constexpr int col = cb * kBlkCols;  // the block's first column within the tile
+            // DMA: pieces 1..3 of tile t+1 in the blocks that start at columns 0, 64, 128; piece 0 of tile t+2 (and its start
+            // values) in the block that starts at column 224 (after the hand-over, into the buffer tile t-1 has just left for good)
+            if (col == 0 || col == 64 || col == 128) {
+                if (more) issue_piece(t + 1, b_nxt, col / 64 + 1);
+            } else if (col == kHandCol) {
                 if (more2) {
                     issue_piece(t + 2, b_nxt2, 0);
                     issue_cin(t + 2, b_nxt2);
                 }
             }
-            const unsigned char* blk = tile + cb * 32 * kDim;
-            // first operands of the next block: same tile, or block 0 of the tile handed over one block ago
-            const unsigned char* nblk = cb < kLast ? blk + 32 * kDim : tile_n;
-            const bool fetch = cb < kLast || more;
             // the block being searched is the previous one: (t, cb - 1), or the last block of tile t - 1 (never ragged)
-            const int col0 = t * kQTN + (cb - 1) * 32;
+            const int col0 = t * kQTN + col - kBlkCols;
             static_for<0, 4>([&](auto S) {
                 constexpr int s = decltype(S)::value;
-                constexpr int u = s >> 1, ks = s & 1;
-                const i32x4 xq = bq[s & 3];
-                if (s + kAhead < 4) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(blk + slot_off(s + kAhead));
-                } else if (fetch) {
-                    bq[(s + kAhead) & 3] = *reinterpret_cast<const i32x4*>(nblk + slot_off(s + kAhead - 4));
+                // the slice's four MFMAs: read q of the block (sub-block u, k-step ks) on row groups g0 .. g0 + 3
+                constexpr int q = 4 * s / kG, g0 = 4 * s % kG;
+                constexpr int u = q >> 1, ks = q & 1;
+                constexpr int r = cb * kReads + q;  // the read's number within the tile
+                const i32x4 xq = bq[r & 3];
+                if (g0 == 0) {
+                    // a new operand comes into use: fetch the one kAhead reads on - this tile's, or one of the first of the tile
+                    // handed over at column 224
+                    constexpr int rn = r + kAhead, kTileReads = kBlk * kReads;
+                    if (rn < kTileReads) {
+                        bq[rn & 3] = *reinterpret_cast<const i32x4*>(tile + read_off(rn));
+                    } else if (more) {
+                        bq[rn & 3] = *reinterpret_cast<const i32x4*>(tile_n + read_off(rn - kTileReads));
+                    }
                 }
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
+                for (int g = g0; g < g0 + 4; ++g)
                     acc[par][u][g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xq, aq[g][ks], ks == 0 ? cin[u] : acc[par][u][g], 0, 0, 0);
                 // sub-block u's start values are consumed: fetch the next block's (the same tile's, or the next tile's first)
-                if (ks == 1) {
+                if (ks == 1 && g0 == 0) {
                     if (cb < kLast)
-                        cin[u] = *reinterpret_cast<const i32x4*>(cin_t + (32 * (cb + 1) + 16 * u) * 4);
+                        cin[u] = *reinterpret_cast<const i32x4*>(cin_t + (kBlkCols * (cb + 1) + 16 * u) * 4);
                     else if (more)
                         cin[u] = *reinterpret_cast<const i32x4*>(cin_n + (16 * u) * 4);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                consume(Q8Slice<par ^ 1, s, (cb + kLast) % kQBlk, MASK && cb != 0, cb == 0>{}, col0);
+                static_for<0, kGps>([&](auto J) {
+                    consume(Q8Slice<par ^ 1, s * kGps + decltype(J)::value, (cb + kLast) % kBlk, kBlk, MASK && cb != 0, cb == 0>{}, col0);
+                });
                 __builtin_amdgcn_sched_barrier(0);
             });
             if (cb == 0) after_block0(t);
-            if (cb == kLast - 1) {
+            if (col + kBlkCols == kHandCol) {
                 // hand-over: this wave's DMA pieces of tile t+1 have landed; after the barrier that holds for every
                 // wave, and every wave has left tile t-1
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2051,8 +2079,8 @@ struct Q8Stream {
     // the last block of the last tile (call it only where ntiles > 0)
     template <bool MASK, class Consume>
     __device__ __forceinline__ void finish(Consume&& consume) {
-        const int col0 = (ntiles - 1) * kQTN + (kQBlk - 1) * 32;
-        static_for<0, 4>([&](auto S) { consume(Q8Slice<(kQBlk - 1) & 1, decltype(S)::value, kQBlk - 1, MASK, false>{}, col0); });
+        const int col0 = (ntiles - 1) * kQTN + (kBlk - 1) * kBlkCols;
+        static_for<0, kG>([&](auto GI) { consume(Q8Slice<(kBlk - 1) & 1, decltype(GI)::value, kBlk - 1, kBlk, MASK, false>{}, col0); });
     }
 };
 
@@ -2247,14 +2275,39 @@ __global__ __launch_bounds__(512) void match_screen_i8_kernel(const MatchJob* __
 // and stay conflict-free for this read pattern: row c, chunk (4 ks + kq) ^ ((c >> 1) & 7)), each feeding four MFMAs of 16
 // cycles - the cadence of the 32x32x32 loop.  The stream itself is Q8Stream; this kernel's own: the choice of operands, the
 // selection (fold_group, seg_fold) and the merge of the four lane quarters of a row at the end.
-template <bool BOUNDS>
+// RPW = 128 (the default, APS_SCREEN_ROWS=1024): a wave owns 128 rows as eight groups, the workgroup 1024; a block is one
+// 16-column sub-block x two k-steps = two ds_read_b128 per lane, each feeding eight MFMAs.  A lane still holds columns
+// 4 kq + r of every 16-column sub-block, 64 of a tile, so every group maximum - and with it d0 / d1, s_best / s_second and
+// the survivor set - is what the 64-row form finds; per tile the workgroup pays the same 32 DMA pieces, start values and
+// barrier for twice the rows.  A job's remainder of up to 512 rows runs on the 64-row form (launch_screen).
+// fold_max: the running maximum m of a lane's NV = 4 or 8 finished products, (NV + 1) / 2 v_max3 (FIRST: m starts here).
+// (volatile asm: left to itself the compiler sinks the whole search of a tile's blocks behind the tile's last MFMA - nothing
+// needs the result earlier - and then has all the blocks' accumulators alive at once)
+template <bool FIRST, int NV>
+__device__ __forceinline__ void fold_max(int& m, const int (&v)[NV]) {
+    static_assert(NV == 4 || NV == 8, "a lane holds four products per sub-block");
+    if constexpr (FIRST && NV == 8)
+        asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
+                     : "=&v"(m)
+                     : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+    else if constexpr (NV == 8)
+        asm volatile("v_max3_i32 %0, %0, %1, %2\n\tv_max3_i32 %0, %0, %3, %4\n\tv_max3_i32 %0, %0, %5, %6\n\tv_max3_i32 %0, %0, %7, %8"
+                     : "+v"(m)
+                     : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+    else if constexpr (FIRST)
+        asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max_i32 %0, %0, %4" : "=&v"(m) : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+    else
+        asm volatile("v_max3_i32 %0, %0, %1, %2\n\tv_max3_i32 %0, %0, %3, %4" : "+v"(m) : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+}
+
+template <bool BOUNDS, int RPW>
 __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob* __restrict__ jobs,
                                                                     const WgJob* __restrict__ wgs, int n_wg,
                                                                     uint32_t* __restrict__ out_idx, float* __restrict__ out_d1,
                                                                     float* __restrict__ out_d2, uint32_t* __restrict__ surv_list,
                                                                     unsigned int* __restrict__ surv_count, float prune_r2,
                                                                     float prune_thr, float* __restrict__ bounds_out, unsigned int* __restrict__ exact_flag) {
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[Q8Stream::kLdsBytes];
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[Q8Stream<RPW>::kLdsBytes];
     const int wg = xcd_order(blockIdx.x, n_wg);
     claim_whole_register_file();
     const WgJob w = wgs[wg];
@@ -2268,31 +2321,33 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     if (!BOUNDS && exact && tid == 0) exact_flag[w.job] = 1u;  // (diagnostics: aps_match_screen_exact_jobs)
     const signed char* const opA = exact ? jb.AX : jb.AQ;
     // (exact: the columns in ascending order of their divisor)
-    Q8Stream st(lds, exact ? jb.BXs : jb.BQ, jb.cinBs, jb.ncinB, exact, nB);
+    using Stream = Q8Stream<RPW>;
+    constexpr int kG = Stream::kG, kNV = 4 * Stream::kU;  // row groups of the wave; the lane's products per block and row group
+    Stream st(lds, exact ? jb.BXs : jb.BQ, jb.cinBs, jb.ncinB, exact, nB);
     const int lane = st.lane, c = st.c, kq = st.kq, ntiles = st.ntiles;
-    const int rowb = w.row0 + st.wave * 64;  // this wave's rows: rowb + 16 g + c, every lane quarter kq sees them
+    const int rowb = w.row0 + st.wave * RPW;  // this wave's rows: rowb + 16 g + c, every lane quarter kq sees them
 
-    i32x4 aq[4][2];
+    i32x4 aq[kG][2];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
+    for (int g = 0; g < kG; ++g) {
         const int arow = min(rowb + 16 * g + c, nA - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
             aq[g][ks] = *reinterpret_cast<const i32x4*>(opA + (size_t)arow * kDim + 64 * ks + 16 * kq);
     }
     constexpr int kNone = kScreenNone;
-    int d0[4] = {kNone, kNone, kNone, kNone}, d1[4] = {kNone, kNone, kNone, kNone};
+    int d0[kG], d1[kG];
     // general codes: the three 1-KiB areas of start values are zero-filled once
     if (!exact && tid < 192) *reinterpret_cast<i32x4*>(lds + 3 * kQTileBytes + 16 * tid) = i32x4{0, 0, 0, 0};
 
-    // The search of a finished block for row group g: the lane's 8 columns, 16 u + 4 kq + r of the block, are folded into the
-    // running maximum of the lane's columns of the TILE (4 v_max3); the tile's last block then updates the two best:
+    // The search of a finished block for row group g: the lane's kNV columns, 16 u + 4 kq + r of the block, are folded into the
+    // running maximum of the lane's columns of the TILE (fold_max: 4 v_max3 per 32 columns); the tile's last block then updates the two best:
     // D1 = med3(D0, D1, m), D0 = max(D0, m).  A group is thus the 64 columns a lane holds of a 256-column tile: D1 is the
     // second largest GROUP maximum, which can only be lower than the second largest dot (when a row's two best columns fall
     // into one group of one lane: 64 of ~20 000 columns) - still a bound, and 17 instead of 24 VALU per block, which matters
     // here: a 16x16x64 MFMA holds the SIMD's vector issue for half of its 16 cycles, twice the share of the 32x32x32 form.
     // limit (ragged last tile only) = number of valid columns counted from the block's first.
-    int m_run[4] = {kNone, kNone, kNone, kNone};
+    int m_run[kG];
     // Exact codes: the columns come sorted by their divisor, and every kSeg tiles the integer best two (d0, d1) of the SEGMENT
     // are turned into bounds on I / t_j with the segment's divisor range [tlo of its first tile, thi of its last] and join the
     // row's best two in f32: s0 = max I / tlo, (f0, f1) = the two largest I / thi; then the integers start again.  (Per TILE
@@ -2300,17 +2355,18 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     // tiles still spans only a tenth of the set's divisor range: 2.0x % of the rows survive either way.)
     constexpr int kSeg = 8;
     int seg_first = 0;  // first tile of the segment being collected (wave-uniform)
-    float s0[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, f0[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY},
-          f1[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int rc[4] = {0, 0, 0, 0};  // 128 sum p_i + 128^3 of the lane's four rows
-    if (exact) {
+    float s0[kG], f0[kG], f1[kG];
+    int rc[kG];  // 128 sum p_i + 128^3 of the lane's rows
 #pragma unroll
-        for (int g = 0; g < 4; ++g) rc[g] = jb.cinA[min(rowb + 16 * g + c, nA - 1)] + 2097152;
+    for (int g = 0; g < kG; ++g) {
+        d0[g] = d1[g] = m_run[g] = kNone;
+        s0[g] = f0[g] = f1[g] = -INFINITY;
+        rc[g] = exact ? jb.cinA[min(rowb + 16 * g + c, nA - 1)] + 2097152 : 0;
     }
     auto seg_fold = [&](int t_first, int t_last) __attribute__((always_inline)) {  // tiles t_first .. t_last are folded
         const float rlo = jb.tscB[t_first].x, rhi = jb.tscB[t_last].y;  // (wave-uniform)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < kG; ++g) {
             const int a0 = d0[g], a1 = d1[g];
             const float i0 = (float)(a0 + rc[g]), i1 = (float)(a1 + rc[g]);  // (I < 2^24: exact)
             const float hi = a0 != kNone ? i0 * rlo : -INFINITY;
@@ -2325,23 +2381,14 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     auto fold_group = [&](auto SL, int col0) __attribute__((always_inline)) {
         using sl = decltype(SL);
         constexpr int g = sl::g;
-        int v[8];
+        int v[kNV];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < kNV; ++e) {
             v[e] = st.acc[sl::par][e >> 2][g][e & 3];
             if (sl::masked) v[e] = (16 * (e >> 2) + 4 * kq + (e & 3)) < nB - col0 ? v[e] : kNone;
         }
-        // (volatile asm: left to itself the compiler sinks the whole search of a tile's eight blocks behind the tile's last
-        // MFMA - nothing needs the result earlier - and then has eight blocks' accumulators alive at once)
         int m = m_run[g];
-        if (sl::first)
-            asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
-                         : "=&v"(m)
-                         : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
-        else
-            asm volatile("v_max3_i32 %0, %0, %1, %2\n\tv_max3_i32 %0, %0, %3, %4\n\tv_max3_i32 %0, %0, %5, %6\n\tv_max3_i32 %0, %0, %7, %8"
-                         : "+v"(m)
-                         : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+        fold_max<sl::first>(m, v);
         m_run[g] = m;
         if (sl::last) {
             // the runner-up of {d0, d1, m} given d0 >= d1, then the new best
@@ -2365,19 +2412,24 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
     st.start(aq);
     // full tiles run unmasked; a ragged last tile (columns >= nB: the DMA re-reads the last row for them) runs the masked copy
     const int nfull = nB / kQTN;
-    for (int t = 0; t < nfull; ++t) st.tile<false>(t, aq, no_hook, fold_group, seg_close);
+    for (int t = 0; t < nfull; ++t) st.template tile<false>(t, aq, no_hook, fold_group, seg_close);
     if (nfull < ntiles) {
-        st.tile<true>(nfull, aq, no_hook, fold_group, seg_close);
-        st.finish<true>(fold_group);
+        st.template tile<true>(nfull, aq, no_hook, fold_group, seg_close);
+        st.template finish<true>(fold_group);
     } else if (ntiles > 0) {
-        st.finish<false>(fold_group);
+        st.template finish<false>(fold_group);
     }
     if (exact && ntiles > 0) seg_fold(seg_first, ntiles - 1);  // the last segment
-    // the four lane quarters of a wave saw disjoint columns of the same rows; quarter kq then decides row group kq
-    int e0 = kNone, e1 = kNone;
-    float s_best = -INFINITY, s_second = -INFINITY;
+    // the four lane quarters of a wave saw disjoint columns of the same rows; quarter kq then decides row groups kq, kq + 4, ..
+    int e0[kG / 4], e1[kG / 4];
+    float s_best[kG / 4], s_second[kG / 4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
+    for (int h = 0; h < kG / 4; ++h) {
+        e0[h] = e1[h] = kNone;
+        s_best[h] = s_second[h] = -INFINITY;
+    }
+#pragma unroll
+    for (int g = 0; g < kG; ++g) {
         int a0 = d0[g], a1 = d1[g];
         float b0 = s0[g], c0 = f0[g], c1 = f1[g];
 #pragma unroll
@@ -2392,16 +2444,19 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
             c1 = fmaxf(fminf(c0, q0), fmaxf(c1, q1));
             c0 = m0;
         }
-        if (g == kq) {
-            e0 = a0;
-            e1 = a1;
-            s_best = b0;
-            s_second = c1;
+        if ((g & 3) == kq) {
+            e0[g >> 2] = a0;
+            e1[g >> 2] = a1;
+            s_best[g >> 2] = b0;
+            s_second[g >> 2] = c1;
         }
     }
-    const int row = rowb + lane;  // = rowb + 16 kq + c
-    screen_tail<BOUNDS>(jb, w.job, row, e0, e1, lane, out_idx, out_d1, out_d2, surv_list, surv_count, prune_r2, prune_thr, bounds_out, exact,
-                        s_best, s_second);
+#pragma unroll
+    for (int h = 0; h < kG / 4; ++h) {
+        const int row = rowb + 64 * h + lane;  // = rowb + 16 (4 h + kq) + c
+        screen_tail<BOUNDS>(jb, w.job, row, e0[h], e1[h], lane, out_idx, out_d1, out_d2, surv_list, surv_count, prune_r2, prune_thr, bounds_out,
+                            exact, s_best[h], s_second[h]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2411,40 +2466,45 @@ __global__ __launch_bounds__(512) void match_screen_i8x16_kernel(const MatchJob*
 // column) with a certified error bound (match_cand_f16_kernel<LIST>).  With exact integer codes the same sweep runs on the
 // int8 pipe at twice the rate and needs no error analysis: the products are exact, and the screen has left every survivor a
 // threshold (screen_tail) that only the columns which can be its best or second best by the canonical f32 distance reach - a
-// handful per row.  This kernel streams a pooled 512-row survivor tile against its B set through the screening kernel's
-// Q8Stream and compares instead of folding - per (32-column block, row group) the maximum of the lane's eight products
-// against the row's threshold, and only on a hit (rare) the eight values one by one - and appends (column; its position in
+// handful per row.  This kernel streams a pooled survivor tile of 8 RPW rows (1024, or a remainder of up to 512: cut_rows)
+// against its B set through the screening kernel's Q8Stream and compares instead of folding - per (block, row group) the
+// maximum of the lane's eight (four: RPW = 128) products against the row's threshold, and only on a hit (rare) the values
+// one by one - and appends (column; its position in
 // the B set's divisor-sorted order) to the row's candidate list: cand[p * kCandCap ..], count in cand_cnt[p], p = the row's
 // position in the pooled survivor list (counts beyond the capacity are kept: such a row goes to the exact-f32 fallback).
 // match_rescore_kernel then evaluates the canonical f32 distance of every candidate and writes the row's (idx, d1, d2).
 constexpr int kCandCap = 32;
 
+template <int RPW>
 __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __restrict__ jobs, const WgJob* __restrict__ wgs, int n_wg,
                                                             const uint32_t* __restrict__ row_list, const int* __restrict__ list_job,
                                                             const float* __restrict__ thr_slot, uint32_t* __restrict__ cand,
                                                             unsigned int* __restrict__ cand_cnt) {
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[Q8Stream::kLdsBytes];
-    __shared__ unsigned int s_cnt[512];  // candidates found so far per row of the tile (the four lane quarters of a wave share a row)
-    s_cnt[threadIdx.x] = 0u;
+    using Stream = Q8Stream<RPW>;
+    constexpr int kG = Stream::kG, kNV = 4 * Stream::kU, kRows = Stream::kRows;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[Stream::kLdsBytes];
+    __shared__ unsigned int s_cnt[kRows];  // candidates found so far per row of the tile (the four lane quarters of a wave share a row)
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int e = tid; e < kRows; e += 512) s_cnt[e] = 0u;
     const int wg = xcd_order(blockIdx.x, n_wg);
     claim_whole_register_file();
     const WgJob w = wgs[wg];
     const MatchJob jb = jobs[w.job];  // (any job of the tile's group: the B set is common)
-    const int tid = threadIdx.x;
     const int nB = jb.nB;
-    Q8Stream st(lds, jb.BXs, jb.cinBs, jb.ncinB, true, nB);
+    Stream st(lds, jb.BXs, jb.cinBs, jb.ncinB, true, nB);
     const int wave = st.wave, c = st.c, kq = st.kq;
-    // this lane's four rows: list entries w.row0 + wave * 64 + 16 g + c (entries past the tile's end: no row, nothing can hit)
-    i32x4 aq[4][2];
+    // this lane's kG rows: list entries w.row0 + wave * RPW + 16 g + c (entries past the tile's end: no row, nothing can hit)
+    i32x4 aq[kG][2];
     // thr[g]: the row's threshold in accumulator units for the tile being streamed, thr_prev[g]: for the tile before (the last
     // block of a tile is tested in the first block of the next); s2[g] = the row's lower bound of its second largest I / t_j
     // (screen_tail), rcr[g] = 128 sum p_i + 128^3.  A column of a tile with smallest divisor tlo can reach s2 only with
     // I >= s2 tlo; margin 2e-4 (see screen_tail), -2 for the f32 product's rounding.  A tile of all-zero columns (tlo = 0: I = 0,
     // similarity 0) qualifies only for a row whose bound is not positive.
-    int thr[4], thr_prev[4];
-    float s2[4];
-    int rcr[4];
-    int pos_of[4];
+    int thr[kG], thr_prev[kG];
+    float s2[kG];
+    int rcr[kG];
+    int pos_of[kG];
     auto tile_thr = [&](int g, float tlo) __attribute__((always_inline)) {
         if (!(s2[g] > -1e9f)) return -2147483647 - 1;          // no bound (or a dead lane's +inf, below): everything / nothing
         if (!(tlo > 0.f)) return s2[g] > 0.f ? 2147483647 : -2147483647 - 1;
@@ -2452,8 +2512,8 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
         return v < 2.0e9f ? (int)v - rcr[g] : 2147483647;
     };
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int e = wave * 64 + 16 * g + c;
+    for (int g = 0; g < kG; ++g) {
+        const int e = wave * RPW + 16 * g + c;
         const bool live = e < w.list_cnt;
         pos_of[g] = w.row0 + (live ? e : 0);
         const int arow = (int)row_list[pos_of[g]];  // (the pooled list names rows within their job: list_pool_kernel)
@@ -2469,7 +2529,7 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
     auto next_thr = [&](int t) __attribute__((always_inline)) {
         const float tlo = jb.tscB[t].z;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < kG; ++g) {
             thr_prev[g] = thr[g];
             thr[g] = tile_thr(g, tlo);
         }
@@ -2479,20 +2539,18 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
         using sl = decltype(SL);
         constexpr int g = sl::g;
         if (sl::prev && col0 < 0) return;  // (block 0 of tile 0: nothing is finished yet)
-        const int (&th)[4] = sl::prev ? thr_prev : thr;
-        int v[8];
+        const int (&th)[kG] = sl::prev ? thr_prev : thr;
+        int v[kNV];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = st.acc[sl::par][e >> 2][g][e & 3];
+        for (int e = 0; e < kNV; ++e) v[e] = st.acc[sl::par][e >> 2][g][e & 3];
         int m;
-        asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
-                     : "=&v"(m)
-                     : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+        fold_max<true>(m, v);
         if (__builtin_expect(__any(m >= th[g]), 0)) {
             // (one emission site behind a bit mask of the lane's hits: with the eight tests unrolled around eight atomics the
             // kernel's loop body outgrew the instruction cache - 32 call sites per tile - and ran at half the screen's rate)
             unsigned hits = 0u;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) hits |= (v[e] >= th[g] ? 1u : 0u) << e;
+            for (int e = 0; e < kNV; ++e) hits |= (v[e] >= th[g] ? 1u : 0u) << e;
 #pragma unroll 1
             while (hits) {
                 const int e = __builtin_ctz(hits);
@@ -2501,17 +2559,20 @@ __global__ __launch_bounds__(512) void match_list_i8_kernel(const MatchJob* __re
                 if (col < nB) {
                     // (the row's counter lives in LDS: a returning GLOBAL atomic is waited for on vmcnt, behind the tile's
                     // LDS-DMA pieces in flight - every hit then stalled its wave until the next tile had landed)
-                    const unsigned int pos = atomicAdd(&s_cnt[wave * 64 + 16 * g + c], 1u);
+                    const unsigned int pos = atomicAdd(&s_cnt[wave * RPW + 16 * g + c], 1u);
                     if (pos < (unsigned)kCandCap) cand[(size_t)pos_of[g] * kCandCap + pos] = (uint32_t)col;
                 }
             }
         }
     };
     st.start(aq);
-    for (int t = 0; t < st.ntiles; ++t) st.tile<false>(t, aq, next_thr, test_group, [](int) {});
-    if (st.ntiles > 0) st.finish<false>(test_group);
+    for (int t = 0; t < st.ntiles; ++t) st.template tile<false>(t, aq, next_thr, test_group, [](int) {});
+    if (st.ntiles > 0) st.template finish<false>(test_group);
     __syncthreads();
-    if (tid < w.list_cnt) cand_cnt[w.row0 + tid] = s_cnt[tid];  // (row e of the tile = wave e / 64, group (e % 64) / 16, c = e % 16: s_cnt's order)
+    // (row e of the tile = wave e / RPW, group (e % RPW) / 16, c = e % 16: s_cnt's order)
+#pragma unroll
+    for (int e = tid; e < kRows; e += 512)
+        if (e < w.list_cnt) cand_cnt[w.row0 + e] = s_cnt[e];
 }
 
 // The candidates of a row (match_list_i8_kernel) -> its exact (idx, d1, d2): eight lanes per row, lane e evaluates the
@@ -3138,14 +3199,54 @@ __global__ void list_pool_kernel(const int64_t* __restrict__ seg_off, const uint
     }
 }
 
+// A/B switch: APS_SCREEN_ROWS=512 keeps every workgroup of the int8 screen (and of the pooled matcher's bounds pass) at 512
+// rows, 64 per wave (rounds 4-6); the default, 1024, gives a wave 128 rows, so that a B tile's DMA pieces, start values and
+// hand-over barrier are paid once per 1024 rows.  The 32x32x32 screen (APS_SCREEN_SHAPE=32) has the 512-row form only.
+static bool stream_rows_1024() {
+    const char* e = std::getenv("APS_SCREEN_ROWS");
+    return !(e && std::atoi(e) == 512);
+}
+// ... and APS_LIST_ROWS=1024 gives the exact list pass the same cut.  Its default stays 512: on the 64 x 4K scene the
+// 1024-row list kernel ran 2.5 ms against 2.0 (its 128 test sites per tile against 32: 8.2 k instructions against 3.5 k),
+// where the screen went from 63.8 to 58.3 ms (profiles/r10_screen_rows1024.txt).
+static bool list_rows_1024() {
+    const char* e = std::getenv("APS_LIST_ROWS");
+    return e && std::atoi(e) == 1024;
+}
+
+// How n rows (of a job, or of a pooled list) are cut into workgroups of the int8 stream: `wide` 1024-row workgroups, and
+// `narrow` 512-row ones from row narrow0 on.  With the 1024-row form a remainder of up to 512 rows takes one 512-row
+// workgroup instead of a half-empty wide one (19.8 k rows: 19 + 1); a larger one takes a ragged wide workgroup.
+struct RowCut {
+    int wide, narrow, narrow0;
+};
+static RowCut cut_rows(size_t n, bool rows_1024) {
+    if (!rows_1024) return {0, (int)((n + 511) / 512), 0};
+    const int full = (int)(n / 1024), rem = (int)(n % 1024);
+    if (rem > 512) return {full + 1, 0, 0};
+    return {full, rem > 0 ? 1 : 0, full * 1024};
+}
+// ... as tiles {job, row0 + first row, rows of the tile (list mode)}
+static void push_row_tiles(int job, size_t row0, size_t n, bool rows_1024, std::vector<WgJob>& wide, std::vector<WgJob>& narrow) {
+    const RowCut cut = cut_rows(n, rows_1024);
+    for (int k = 0; k < cut.wide; ++k)
+        wide.push_back({job, (int)(row0 + (size_t)k * 1024), (int)std::min<size_t>(1024, n - (size_t)k * 1024), 0, 0, 0});
+    for (int k = 0; k < cut.narrow; ++k) {
+        const size_t r = (size_t)cut.narrow0 + (size_t)k * 512;
+        narrow.push_back({job, (int)(row0 + r), (int)std::min<size_t>(512, n - r), 0, 0, 0});
+    }
+}
+
 // The walk over the jobs that share a B set - same operand pointer (`key`: the operand the pass streams) and same column
 // count - with the groups in pointer order and the jobs of a group in job order: job j's cnt[j] list entries get the place
 // dst[j] ... of one packed list, and every group's stretch of that list is cut into tiles of tile_rows rows, appended to
-// `tiles` as WgJob{the group's first job, start in the packed list, rows}.  Returns the packed list's length.
+// `tiles` as WgJob{the group's first job, start in the packed list, rows} - or, with wide_tiles, into the int8 stream's
+// 1024-row tiles (wide_tiles) and 512-row remainders (tiles): cut_rows.  Returns the packed list's length.
 // skip_empty_sets: groups whose B set has no columns get places but no tiles.
 template <class Ptr>
 static size_t tile_by_b_set(const std::vector<MatchJob>& jobs, Ptr MatchJob::*key, const std::vector<unsigned int>& cnt,
-                            int tile_rows, bool skip_empty_sets, std::vector<long long>& dst, std::vector<WgJob>& tiles) {
+                            int tile_rows, bool skip_empty_sets, std::vector<long long>& dst, std::vector<WgJob>& tiles,
+                            std::vector<WgJob>* wide_tiles = nullptr) {
     const size_t nj = jobs.size();
     std::vector<int> order(nj);
     for (size_t j = 0; j < nj; ++j) order[j] = (int)j;
@@ -3162,9 +3263,13 @@ static size_t tile_by_b_set(const std::vector<MatchJob>& jobs, Ptr MatchJob::*ke
             total += cnt[order[b]];
             ++b;
         }
-        if (!skip_empty_sets || jobs[order[a]].nB > 0)
-            for (size_t r = g0; r < total; r += tile_rows)
-                tiles.push_back({order[a], (int)r, (int)std::min<size_t>(tile_rows, total - r), 0, 0, 0});
+        if (!skip_empty_sets || jobs[order[a]].nB > 0) {
+            if (wide_tiles)
+                push_row_tiles(order[a], g0, total - g0, true, *wide_tiles, tiles);
+            else
+                for (size_t r = g0; r < total; r += tile_rows)
+                    tiles.push_back({order[a], (int)r, (int)std::min<size_t>(tile_rows, total - r), 0, 0, 0});
+        }
         a = b;
     }
     return total;
@@ -3172,16 +3277,17 @@ static size_t tile_by_b_set(const std::vector<MatchJob>& jobs, Ptr MatchJob::*ke
 
 // Pools the list segments of jobs that share a B set into common tiles of kTMB rows: returns the tiles; pool / pool_job
 // are filled on the stream.  from / to: host copies of the per-job entry ranges (from may be empty = zeros); d_from /
-// d_to: device copies.
+// d_to: device copies.  wide_tiles: cut for the int8 stream instead (tile_by_b_set) - its 1024-row tiles go there.
 static std::vector<WgJob> pool_lists(const std::vector<MatchJob>& jobs, const std::vector<int64_t>& seg_off,
                                      const uint32_t* d_list, const std::vector<unsigned int>& from, const std::vector<unsigned int>& to,
-                                     const unsigned int* d_from, const unsigned int* d_to, Ws<uint32_t>& pool, Ws<int>& pool_job) {
+                                     const unsigned int* d_from, const unsigned int* d_to, Ws<uint32_t>& pool, Ws<int>& pool_job,
+                                     std::vector<WgJob>* wide_tiles = nullptr) {
     const size_t nj = jobs.size();
     std::vector<unsigned int> cnt(to);
     for (size_t j = 0; j < from.size(); ++j) cnt[j] -= from[j];
     std::vector<long long> h_dst;
     std::vector<WgJob> tiles;
-    const size_t total = tile_by_b_set(jobs, &MatchJob::BF, cnt, kTMB, true, h_dst, tiles);
+    const size_t total = tile_by_b_set(jobs, &MatchJob::BF, cnt, kTMB, true, h_dst, tiles, wide_tiles);
     if (total == 0) return tiles;
     APS_REQUIRE(total < ((size_t)1 << 31), APS_E_DIM, "pooled row list too long (%zu)", total);
     pool.alloc(total);
@@ -3210,9 +3316,11 @@ static bool screen_shape_32() {
 // SIMD, 256 registers each (claim_whole_register_file).  That holds only while the compiler really allocates 256: checked
 // against the loaded code object before a kernel's first launch in a process, and by tests/test_abi.py against the code
 // object's metadata on the CPU.
-static const void* screen_kernel(bool shape32, bool bounds) {
-    return shape32 ? (bounds ? reinterpret_cast<const void*>(&match_screen_i8_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8_kernel<false>))
-                   : (bounds ? reinterpret_cast<const void*>(&match_screen_i8x16_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8x16_kernel<false>));
+static const void* screen_kernel(bool shape32, bool bounds, bool rows_1024 = false) {
+    if (shape32) return bounds ? reinterpret_cast<const void*>(&match_screen_i8_kernel<true>) : reinterpret_cast<const void*>(&match_screen_i8_kernel<false>);
+    if (rows_1024)
+        return bounds ? reinterpret_cast<const void*>(&match_screen_i8x16_kernel<true, 128>) : reinterpret_cast<const void*>(&match_screen_i8x16_kernel<false, 128>);
+    return bounds ? reinterpret_cast<const void*>(&match_screen_i8x16_kernel<true, 64>) : reinterpret_cast<const void*>(&match_screen_i8x16_kernel<false, 64>);
 }
 static void require_whole_simd(const void* kernel, const char* what) {
     static std::mutex mu;  // (one code object for every device of the process: the answer is the same on all of them)
@@ -3225,25 +3333,48 @@ static void require_whole_simd(const void* kernel, const char* what) {
                 "the int8 %s kernel holds %d registers per lane, not 256: other kernels' waves could share its SIMDs (DESIGN.md section 5)", what, fa.numRegs);
     ok[kernel] = true;
 }
-// The screening pass over the dense tiles dbw in the selected MFMA shape (APS_SCREEN_SHAPE); BOUNDS: the pooled matcher's form.
+// The dense tiles of a screening pass on the device: the workgroups of 1024 rows (none under APS_SCREEN_ROWS=512 or
+// APS_SCREEN_SHAPE=32) and those of 512 (cut_rows).
+struct ScreenTiles {
+    Ws<WgJob> wide, narrow;
+    size_t n_wide = 0, n_narrow = 0;
+};
+static bool screen_rows_1024() { return stream_rows_1024() && !screen_shape_32(); }
+static void trace_screen_tiles(const ScreenTiles& T) {
+    if (std::getenv("APS_TRACE"))
+        std::fprintf(stderr, "[aps] int8 screen workgroups: %zu of 1024 rows, %zu of 512 rows\n", T.n_wide, T.n_narrow);
+}
+
+// The screening pass over the dense tiles T in the selected MFMA shape (APS_SCREEN_SHAPE); BOUNDS: the pooled matcher's form.
+// The few 512-row workgroups go first: what idles while a launch drains is then their short tail.
 template <bool BOUNDS>
-static void launch_screen(const MatchJob* djobs, const WgJob* dbw, size_t n_bw, uint32_t* idx, float* d1, float* d2, uint32_t* surv_list,
+static void launch_screen(const MatchJob* djobs, const ScreenTiles& T, uint32_t* idx, float* d1, float* d2, uint32_t* surv_list,
                           unsigned int* surv_count, float prune_r2, float prune_thr, float* bounds, unsigned int* exact_flag) {
     const bool shape32 = screen_shape_32();
-    require_whole_simd(screen_kernel(shape32, BOUNDS), "screening");
-    if (shape32)
-        match_screen_i8_kernel<BOUNDS><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list, surv_count, prune_r2,
-                                                                              prune_thr, bounds);
-    else
-        match_screen_i8x16_kernel<BOUNDS><<<(unsigned)n_bw, 512, 0, stream()>>>(djobs, dbw, (int)n_bw, idx, d1, d2, surv_list, surv_count, prune_r2,
-                                                                                 prune_thr, bounds, exact_flag);
+    if (T.n_narrow > 0) {
+        require_whole_simd(screen_kernel(shape32, BOUNDS), "screening");
+        if (shape32)
+            match_screen_i8_kernel<BOUNDS><<<(unsigned)T.n_narrow, 512, 0, stream()>>>(djobs, T.narrow, (int)T.n_narrow, idx, d1, d2, surv_list,
+                                                                                        surv_count, prune_r2, prune_thr, bounds);
+        else
+            match_screen_i8x16_kernel<BOUNDS, 64><<<(unsigned)T.n_narrow, 512, 0, stream()>>>(djobs, T.narrow, (int)T.n_narrow, idx, d1, d2, surv_list,
+                                                                                               surv_count, prune_r2, prune_thr, bounds, exact_flag);
+    }
+    if (T.n_wide > 0) {
+        APS_REQUIRE(!shape32, APS_E_INTERNAL, "the 32x32x32 screen has no 1024-row form");
+        require_whole_simd(screen_kernel(false, BOUNDS, true), "screening (1024 rows)");
+        match_screen_i8x16_kernel<BOUNDS, 128><<<(unsigned)T.n_wide, 512, 0, stream()>>>(djobs, T.wide, (int)T.n_wide, idx, d1, d2, surv_list,
+                                                                                          surv_count, prune_r2, prune_thr, bounds, exact_flag);
+    }
 }
-// tile k of a dense pass = rows [r, r + rows_per_tile) of job j, where off[j] <= k < off[j + 1] and r = (k - off[j]) * rows_per_tile
-__global__ void expand_tiles_kernel(const int* __restrict__ off, int n_jobs, int n_tiles, int rows_per_tile, WgJob* __restrict__ out) {
+// tile k of a dense pass = rows [r, r + rows_per_tile) of job j, where off[j] <= k < off[j + 1] and
+// r = (first ? first[j] : 0) + (k - off[j]) * rows_per_tile
+__global__ void expand_tiles_kernel(const int* __restrict__ off, const int* __restrict__ first, int n_jobs, int n_tiles, int rows_per_tile,
+                                    WgJob* __restrict__ out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_tiles) return;
     const int j = last_at_or_below(off, n_jobs, k);  // (jobs without rows have empty ranges)
-    out[k] = WgJob{j, (k - off[j]) * rows_per_tile, 0, 0, 0, 0};
+    out[k] = WgJob{j, (first ? first[j] : 0) + (k - off[j]) * rows_per_tile, 0, 0, 0, 0};
 }
 // ---- run_match_jobs and its steps: the 2-NN search for a list of jobs whose operands are already prepared on the device ----
 
@@ -3277,16 +3408,29 @@ static std::vector<WgJob> exact_list_pass(const std::vector<MatchJob>& jobs, con
     APS_HIP(hipMemcpyAsync(d_cnt_g, cnt_g.data(), jobs.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream()));
     Ws<uint32_t> pool_x;
     Ws<int> pool_job_x;
-    const std::vector<WgJob> lx = pool_lists(jobs, seg, surv_list, {}, cnt_x, nullptr, d_cnt_x, pool_x, pool_job_x);
-    Ws<WgJob> dlx(lx.size());
+    // (APS_LIST_ROWS=1024: the pooled survivor tiles are cut as the screen's, 1024-row tiles in lx_wide, remainders of up to
+    // 512 rows in lx)
+    std::vector<WgJob> lx_wide;
+    const std::vector<WgJob> lx = pool_lists(jobs, seg, surv_list, {}, cnt_x, nullptr, d_cnt_x, pool_x, pool_job_x,
+                                             list_rows_1024() ? &lx_wide : nullptr);
+    Ws<WgJob> dlx(std::max<size_t>(lx.size(), 1)), dlx_wide(std::max<size_t>(lx_wide.size(), 1));
     Ws<uint32_t> cand(n_x * kCandCap);
     Ws<unsigned int> cand_cnt(n_x);
-    APS_HIP(hipMemcpyAsync(dlx, lx.data(), lx.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    if (!lx.empty()) APS_HIP(hipMemcpyAsync(dlx, lx.data(), lx.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    if (!lx_wide.empty())
+        APS_HIP(hipMemcpyAsync(dlx_wide, lx_wide.data(), lx_wide.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
     APS_HIP(hipMemsetAsync(cand_cnt, 0, n_x * sizeof(unsigned int), stream()));
     {
         Prof prof("match_list_i8");
-        require_whole_simd(reinterpret_cast<const void*>(&match_list_i8_kernel), "list");
-        match_list_i8_kernel<<<(unsigned)lx.size(), 512, 0, stream()>>>(djobs, dlx, (int)lx.size(), pool_x, pool_job_x, d1, cand, cand_cnt);
+        if (!lx.empty()) {
+            require_whole_simd(reinterpret_cast<const void*>(&match_list_i8_kernel<64>), "list");
+            match_list_i8_kernel<64><<<(unsigned)lx.size(), 512, 0, stream()>>>(djobs, dlx, (int)lx.size(), pool_x, pool_job_x, d1, cand, cand_cnt);
+        }
+        if (!lx_wide.empty()) {
+            require_whole_simd(reinterpret_cast<const void*>(&match_list_i8_kernel<128>), "list (1024 rows)");
+            match_list_i8_kernel<128><<<(unsigned)lx_wide.size(), 512, 0, stream()>>>(djobs, dlx_wide, (int)lx_wide.size(), pool_x, pool_job_x, d1,
+                                                                                       cand, cand_cnt);
+        }
     }
     {
         Prof prof("match_rescore");
@@ -3301,7 +3445,7 @@ static std::vector<WgJob> exact_list_pass(const std::vector<MatchJob>& jobs, con
 
 // Filtered callers: the int8 screen over the dense tiles dbw dismisses the rows that provably fail the filter, the
 // survivor passes (exact_list_pass, match_cand_f16_kernel<true>) then run on the survivors only (row lists, 512 to a workgroup).
-static void screen_and_survivor_passes(const std::vector<MatchJob>& jobs, const MatchJob* djobs, const WgJob* dbw, size_t n_bw,
+static void screen_and_survivor_passes(const std::vector<MatchJob>& jobs, const MatchJob* djobs, const ScreenTiles& tiles,
                                        int64_t total_rows, uint32_t* idx, float* d1, float* d2, float prune_r2, float prune_thr,
                                        uint32_t* fb_list, unsigned int* fb_count) {
     Ws<uint32_t> surv_list((size_t)total_rows);
@@ -3309,9 +3453,10 @@ static void screen_and_survivor_passes(const std::vector<MatchJob>& jobs, const 
     APS_HIP(hipMemsetAsync(surv_count, 0, 2 * jobs.size() * sizeof(unsigned int), stream()));
     {
         Prof prof("match_screen_i8");
-        launch_screen<false>(djobs, dbw, n_bw, idx, d1, d2, surv_list, surv_count, prune_r2, prune_thr, nullptr, surv_count.get() + jobs.size());
+        launch_screen<false>(djobs, tiles, idx, d1, d2, surv_list, surv_count, prune_r2, prune_thr, nullptr, surv_count.get() + jobs.size());
     }
     check_launch("match_screen_i8_kernel");
+    trace_screen_tiles(tiles);
     const auto S0 = std::chrono::steady_clock::now();
     std::vector<unsigned int> h_surv(2 * jobs.size());
     APS_HIP(hipMemcpyAsync(h_surv.data(), surv_count, 2 * jobs.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, stream()));
@@ -3478,21 +3623,37 @@ static void run_match_jobs(const std::vector<MatchJob>& jobs, uint32_t* idx, flo
     APS_HIP(hipMemsetAsync(fb_count, 0, jobs.size() * sizeof(unsigned int), stream()));
     // the dense tile table {job, first row} of the screening / candidate kernels, expanded on the device from the jobs' tile
     // offsets (round 6: 78 k entries for the 64 x 4K scene were built on the host and uploaded from pageable memory, ~0.2 ms)
-    std::vector<int> wg_off(jobs.size() + 1, 0);
-    for (size_t j = 0; j < jobs.size(); ++j) wg_off[j + 1] = wg_off[j] + (jobs[j].nA + kTMB - 1) / kTMB;
-    const size_t n_bw = (size_t)wg_off.back();
-    Ws<WgJob> dbw(std::max<size_t>(n_bw, 1));
-    Ws<int> d_wg_off(wg_off.size());
-    APS_HIP(hipMemcpyAsync(d_wg_off, wg_off.data(), wg_off.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
-    if (n_bw > 0) {
-        expand_tiles_kernel<<<(unsigned)cdiv(n_bw, 256), 256, 0, stream()>>>(d_wg_off, (int)jobs.size(), (int)n_bw, kTMB, dbw);
-        check_launch("expand_tiles_kernel");
-    }
     // APS_MATCH_NO_SCREEN=1: every row takes the f16 path
-    if (prune_r2 > 0.f && !std::getenv("APS_MATCH_NO_SCREEN"))
-        screen_and_survivor_passes(jobs, djobs, dbw, n_bw, total_rows, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
+    const bool screen = prune_r2 > 0.f && !std::getenv("APS_MATCH_NO_SCREEN");
+    // (the screen's jobs are cut into 1024-row workgroups and 512-row remainders, cut_rows; the candidate kernel's into kTMB =
+    // 512 rows throughout.  One table of 3 nj + 2 words: the wide tiles' offsets, the narrow tiles' offsets, their first rows)
+    const size_t nj = jobs.size();
+    const bool rows_1024 = screen && screen_rows_1024();
+    std::vector<int> wg_tab(3 * nj + 2, 0);
+    int *off_w = wg_tab.data(), *off_n = off_w + nj + 1, *first_n = off_n + nj + 1;
+    for (size_t j = 0; j < nj; ++j) {
+        const RowCut cut = cut_rows((size_t)jobs[j].nA, rows_1024);
+        off_w[j + 1] = off_w[j] + cut.wide;
+        off_n[j + 1] = off_n[j] + cut.narrow;
+        first_n[j] = cut.narrow0;
+    }
+    ScreenTiles tiles;
+    tiles.n_wide = (size_t)off_w[nj];
+    tiles.n_narrow = (size_t)off_n[nj];
+    tiles.wide.alloc(std::max<size_t>(tiles.n_wide, 1));
+    tiles.narrow.alloc(std::max<size_t>(tiles.n_narrow, 1));
+    Ws<int> d_wg_tab(wg_tab.size());
+    APS_HIP(hipMemcpyAsync(d_wg_tab, wg_tab.data(), wg_tab.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+    if (tiles.n_wide > 0)
+        expand_tiles_kernel<<<(unsigned)cdiv(tiles.n_wide, 256), 256, 0, stream()>>>(d_wg_tab, nullptr, (int)nj, (int)tiles.n_wide, 1024, tiles.wide);
+    if (tiles.n_narrow > 0)
+        expand_tiles_kernel<<<(unsigned)cdiv(tiles.n_narrow, 256), 256, 0, stream()>>>(d_wg_tab.get() + nj + 1, d_wg_tab.get() + 2 * nj + 2, (int)nj,
+                                                                                       (int)tiles.n_narrow, kTMB, tiles.narrow);
+    check_launch("expand_tiles_kernel");
+    if (screen)
+        screen_and_survivor_passes(jobs, djobs, tiles, total_rows, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
     else
-        dense_cand_pass(djobs, dbw, n_bw, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
+        dense_cand_pass(djobs, tiles.narrow, tiles.n_narrow, idx, d1, d2, prune_r2, prune_thr, fb_list, fb_count);
     check_launch("match_cand_f16_kernel");
     fallback_pass(jobs, djobs, fb_list, fb_count, idx, d1, d2);
 }
@@ -3805,12 +3966,13 @@ static void global_bounds(const std::vector<Prepared>& prep, const std::vector<i
                           float* bounds) {
     const int n = (int)img_off.size() - 1;
     std::vector<MatchJob> jobs;
-    std::vector<WgJob> bw;
+    std::vector<WgJob> bw_wide, bw;
+    const bool rows_1024 = screen_rows_1024();
     for (int i = img_a; i < img_b; ++i)
         for (int j = 0; j < n; ++j) {
             const int nA = (int)(img_off[i + 1] - img_off[i]), nB = (int)(img_off[j + 1] - img_off[j]);
             if (i == j || nA == 0 || nB == 0) continue;
-            for (int r = 0; r < nA; r += kTMB) bw.push_back({(int)jobs.size(), r, 0});
+            push_row_tiles((int)jobs.size(), 0, (size_t)nA, rows_1024, bw_wide, bw);
             jobs.push_back(make_job(prep[i], prep[j], nA, nB, table.job_off[(size_t)i * n + j]));
         }
     if (std::getenv("APS_MATCH_NO_SCREEN") || jobs.empty()) {
@@ -3818,14 +3980,21 @@ static void global_bounds(const std::vector<Prepared>& prep, const std::vector<i
         return;
     }
     Ws<MatchJob> djobs(jobs.size());
-    Ws<WgJob> dbw(bw.size());
+    ScreenTiles tiles;
+    tiles.n_wide = bw_wide.size();
+    tiles.n_narrow = bw.size();
+    tiles.wide.alloc(std::max<size_t>(tiles.n_wide, 1));
+    tiles.narrow.alloc(std::max<size_t>(tiles.n_narrow, 1));
     APS_HIP(hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(MatchJob), hipMemcpyHostToDevice, stream()));
-    APS_HIP(hipMemcpyAsync(dbw, bw.data(), bw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    if (tiles.n_wide > 0)
+        APS_HIP(hipMemcpyAsync(tiles.wide, bw_wide.data(), bw_wide.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
+    if (tiles.n_narrow > 0) APS_HIP(hipMemcpyAsync(tiles.narrow, bw.data(), bw.size() * sizeof(WgJob), hipMemcpyHostToDevice, stream()));
     {
         Prof prof("match_screen_i8_bounds");
-        launch_screen<true>(djobs, dbw, bw.size(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
+        launch_screen<true>(djobs, tiles, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, bounds, nullptr);
     }
     check_launch("match_screen_i8_kernel (bounds)");
+    trace_screen_tiles(tiles);
     APS_HIP(hipStreamSynchronize(stream()));
 }
 
