@@ -144,6 +144,10 @@ class aps_fast_orb_params(C.Structure):
                 ("grid_cols", C.c_int)]
 
 
+class aps_lens(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")]
+
+
 APS_MARK_SEGMENT, APS_MARK_RING = 0, 1
 
 
@@ -288,6 +292,9 @@ _SIGNATURES = {
     "aps_orb_pattern": [_vp, _vp, _vp, C.POINTER(_i)],
     "aps_uniform_quota": [_vp, _i, _i64, _vp],
     "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
+    "aps_undistort_image_u8": [_vp, _i, _i, _i, _i, C.POINTER(aps_lens), _i, _i, _i, _i, _i, _vp],
+    "aps_undistort_points": [_vp, _i64, _i64, C.POINTER(aps_lens), _vp],
+    "aps_undistort_valid_view": [_i, _i, C.POINTER(aps_lens), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
 }
 _RESTYPES = {"aps_last_error": C.c_char_p, "aps_planar_composite_bytes": C.c_int64,
              "aps_planar_composite_compact_bytes": C.c_int64}

@@ -427,3 +427,112 @@ def montage_pair(I1, I2):
         dst = np.empty(shape, np.uint8)
     check(lib.aps_montage_pair(ptr(imgs[0]), h1, w1, ptr(imgs[1]), h2, w2, ptr(dst)))
     return dst
+
+
+# ---- lens distortion: cameraIntrinsics, undistortImage, undistortPoints ("Lens distortion contract") -------------------
+class cameraIntrinsics:
+    """intrinsics = cameraIntrinsics(K | (fx, fy, cx, cy), RadialDistortion=(k1, k2[, k3]), TangentialDistortion=(p1, p2)): a lens
+    without skew in the project's 1-based pixel frame (the frame of keypoints and of Ks).  K is 3 x 3 with K[0, 1] == 0."""
+
+    def __init__(self, K, RadialDistortion=(0.0, 0.0), TangentialDistortion=(0.0, 0.0)):
+        K = np.asarray(K, np.float64)
+        if K.shape == (3, 3):
+            if K[0, 1] != 0:
+                raise ValueError("cameraIntrinsics: skew (K[0, 1] != 0) is not modelled")
+            fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        elif K.shape == (4,):
+            fx, fy, cx, cy = K
+        else:
+            raise ValueError("cameraIntrinsics: give a 3 x 3 K or (fx, fy, cx, cy)")
+        k = tuple(float(v) for v in np.asarray(RadialDistortion, np.float64).ravel())
+        p = tuple(float(v) for v in np.asarray(TangentialDistortion, np.float64).ravel())
+        if len(k) not in (2, 3):
+            raise ValueError("cameraIntrinsics: RadialDistortion has 2 or 3 coefficients")
+        if len(p) != 2:
+            raise ValueError("cameraIntrinsics: TangentialDistortion has 2 coefficients")
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.RadialDistortion, self.TangentialDistortion = k, p
+
+    @property
+    def K(self):
+        return np.array([[self.fx, 0.0, self.cx], [0.0, self.fy, self.cy], [0.0, 0.0, 1.0]])
+
+    def lens(self):
+        """The aps_lens of the C ABI (a two-term radial model has k3 = 0)."""
+        k = self.RadialDistortion + (0.0,) * (3 - len(self.RadialDistortion))
+        return _capi.aps_lens(self.fx, self.fy, self.cx, self.cy, *k, *self.TangentialDistortion)
+
+    def __repr__(self):
+        return (f"cameraIntrinsics(fx={self.fx}, fy={self.fy}, cx={self.cx}, cy={self.cy}, RadialDistortion={self.RadialDistortion}, "
+                f"TangentialDistortion={self.TangentialDistortion})")
+
+
+def undistort_valid_view(shape, intrinsics):
+    """(x0, y0, out_h, out_w): the 'valid' view of an image of shape (h, w[, c]) - the largest rectangle of whole pixels inside
+    the undistorted images of its four border rows and columns (aps_undistort_valid_view; an empty one raises ApsError)."""
+    v = [C.c_int(0) for _ in range(4)]
+    lens = intrinsics.lens()
+    check(lib.aps_undistort_valid_view(int(shape[0]), int(shape[1]), C.byref(lens), *(C.byref(x) for x in v)))
+    return tuple(x.value for x in v)
+
+
+def undistortImage(I, intrinsics, OutputView="same", FillValues=0):
+    """(J, newOrigin) = undistortImage(I, intrinsics, OutputView, FillValues) on the device (aps_undistort_image_u8): bilinear,
+    uint8 H x W or H x W x {1, 3}.  OutputView 'same' keeps the input's size and origin (1, 1); 'valid' is undistort_valid_view's
+    rectangle.  newOrigin = (x0, y0): pixel (row i, column j), 0-based, of J has the ideal coordinates (x0 + j, y0 + i).  Pixels
+    that sample outside I get FillValues (a scalar in 0..255).  A torch CUDA tensor stays resident: the result is a CUDA tensor and
+    nothing visits the host."""
+    view = str(OutputView).lower()
+    if view not in ("same", "valid"):
+        raise ValueError(f"unknown OutputView '{OutputView}' ('same' or 'valid')")
+    if not (np.isscalar(FillValues) and 0 <= FillValues <= 255 and int(FillValues) == FillValues):
+        raise ValueError("FillValues must be an integer scalar in 0..255")
+    dev = _capi.is_torch(I) and I.is_cuda
+    a = I.contiguous() if _capi.is_torch(I) else np.ascontiguousarray(I)
+    if str(a.dtype).split(".")[-1] != "uint8":
+        raise TypeError("uint8 images only")
+    sq = a.ndim == 2
+    if sq:
+        a = a[..., None]
+    if a.ndim != 3 or int(a.shape[2]) not in (1, 3):
+        raise ValueError(f"I must be H x W, H x W x 1 or H x W x 3, got {tuple(I.shape)}")
+    h, w, c = (int(v) for v in a.shape)
+    x0, y0, oh, ow = (1, 1, h, w) if view == "same" else undistort_valid_view((h, w), intrinsics)
+    if dev:
+        import torch
+
+        out = torch.empty((oh, ow, c), dtype=torch.uint8, device=a.device)
+        torch.cuda.current_stream().synchronize()  # the input came from torch's stream; the library runs on its own
+    elif _capi.is_torch(a):
+        import torch
+
+        out = torch.empty((oh, ow, c), dtype=torch.uint8)
+    else:
+        out = np.empty((oh, ow, c), np.uint8)
+    lens = intrinsics.lens()
+    check(lib.aps_undistort_image_u8(ptr(a), h, w, c, _capi.APS_IMG_U8_HWC, C.byref(lens), oh, ow, x0, y0, int(FillValues), ptr(out)))
+    return (out[..., 0] if sq else out), (x0, y0)
+
+
+def undistortPoints(points, intrinsics):
+    """undistortedPoints = undistortPoints(points, intrinsics): n x 2 [x y] float64, 1-based, through the inverse of the lens map
+    (aps_undistort_points: 20 fixed-point steps).  A numpy array gives a numpy array, a torch CUDA tensor a resident one."""
+    is_t = _capi.is_torch(points)
+    p = points if is_t else np.asarray(points, np.float64)
+    if p.ndim != 2 or int(p.shape[1]) != 2 or str(p.dtype).split(".")[-1] != "float64":
+        raise ValueError(f"points must be n x 2 float64, got {p.dtype} {tuple(p.shape)}")
+    n = int(p.shape[0])
+    lens = intrinsics.lens()
+    if is_t:
+        import torch
+
+        src = p.t().contiguous()  # x at [k], y at [n + k]
+        dst = torch.empty_like(src)
+        if p.is_cuda:
+            torch.cuda.current_stream().synchronize()  # torch produced the transpose; the library runs on its own stream
+        check(lib.aps_undistort_points(ptr(src), n, n, C.byref(lens), ptr(dst)))
+        return dst.t().contiguous()
+    src = np.ascontiguousarray(p.T)
+    dst = np.empty_like(src)
+    check(lib.aps_undistort_points(ptr(src), n, n, C.byref(lens), ptr(dst)))
+    return np.ascontiguousarray(dst.T)

@@ -1039,6 +1039,10 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     if input.get("detector", "SIFT") == "FAST":
         # the descriptor all-gather and the sharded matchers are built for 128-wide float rows
         raise NotImplementedError("stitch_distributed does not take binary descriptors (detector = 'FAST'); use pipeline.stitch")
+    if "cameraIntrinsics" in input:
+        # the ranks exchange image sizes and intrinsics of the frame the images came in
+        raise NotImplementedError("stitch_distributed does not undistort (input.cameraIntrinsics); use pipeline.stitch, or "
+                                  "imageProcessing.undistortImage on the images first")
     ws, rank = world()
     dev = next(iter(local_images.values())).device if local_images else torch.device("cuda", torch.cuda.current_device())
     times = pl.StageTimes()

@@ -615,6 +615,44 @@ def imageMatchingPanoramaConComps(input, images_original, images_processed, desc
     return res, images_processed, descs, kps, ncomp, labels, second
 
 
+def shift_K(K, origin):
+    """Intrinsics in the frame of a view with origin (x0, y0): its pixel (1, 1) is the old pixel (x0, y0), so
+    cx' = cx - (x0 - 1), cy' = cy - (y0 - 1)."""
+    K = np.array(K, np.float64)
+    K[0, 2] -= origin[0] - 1
+    K[1, 2] -= origin[1] - 1
+    return K
+
+
+def undistort_prologue(input, images, images_original, Ks, times=None):
+    """stitch's first step under input['cameraIntrinsics']: ip.undistortImage on every image (resident images stay resident)
+    and on every image of images_original when given, into input['undistortOutputView'] ('valid' by default).
+    Returns (images, images_original, Ks carried into the new frames or None, the per-image records of info['undistort'])."""
+    from . import imageProcessing as ip
+
+    t0 = time.perf_counter()
+    lenses = input["cameraIntrinsics"]
+    if isinstance(lenses, ip.cameraIntrinsics):
+        lenses = [lenses] * len(images)
+    if len(lenses) != len(images) or not all(isinstance(L, ip.cameraIntrinsics) for L in lenses):
+        raise ValueError("input.cameraIntrinsics: one cameraIntrinsics, or a list with one per image")
+    view = input.get("undistortOutputView", "valid")
+    out, records = [], []
+    for img, L in zip(images, lenses):
+        J, origin = ip.undistortImage(img, L, view)
+        out.append(J)
+        records.append({"origin": origin, "size": (int(J.shape[0]), int(J.shape[1])), "K": shift_K(L.K, origin)})
+    if images_original is not None:
+        if len(images_original) != len(images):
+            raise ValueError("images_original must have one image per image")
+        images_original = [ip.undistortImage(img, L, view)[0] for img, L in zip(images_original, lenses)]
+    if Ks is not None:
+        Ks = [shift_K(K, r["origin"]) for K, r in zip(Ks, records)]
+    if times is not None:
+        times.add("undistort", t0)
+    return out, images_original, Ks, records
+
+
 def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, device_out=True, profile=False,
            images_original=None):
     """main.m for one dataset.  images: list of uint8 H x W x 3 (torch CUDA tensors stay resident).
@@ -632,10 +670,20 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     input['keypointsPlotPairs'] when given (a pair RANSAC never saw is a ValueError), over all those pairs otherwise.  When
     the pictures would exceed input['keypointsPlotLimitBytes'] (default 2^31) the call raises ValueError before drawing any.
     The panoramas and every other entry of info are the same with and without the flag.
+    With input['cameraIntrinsics'] (one imageProcessing.cameraIntrinsics for all images, or a list with one per image; the key
+    is not in DEFAULT_INPUT) every image, and every image of images_original, is undistorted first (undistort_prologue) into
+    the view input['undistortOutputView'] ('valid' by default, so that no fill pixel reaches the blend; or 'same'), and
+    everything after runs on the undistorted images: Ks, when given, are carried into the new frame, and
+    info['images_processed'], info['keypoints'], the match plots and the cameras are in the undistorted frame.
+    info['undistort'] lists per image {'origin': (x0, y0), 'size': (h, w), 'K': the lens' K in the new frame}, and
+    times['undistort'] is added.  Without the key nothing of this runs and the results are what they were.
     Returns (panoramas [one per component, in component order], info dict with per-stage wall times in seconds)."""
     times = StageTimes()
     plots = {} if input.get("showKeypointsPlot") else None
     n = len(images)
+    undistorted = None
+    if "cameraIntrinsics" in input:
+        images, images_original, Ks, undistorted = undistort_prologue(input, images, images_original, Ks, times)
     descs, kps = extract_features(input, images, times)
     first_hw = [(int(im_.shape[0]), int(im_.shape[1])) for im_ in images]
     first_counts = [len(k) for k in kps]
@@ -683,6 +731,8 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
             "images_processed": images}
     if ba_info is not None:
         info["ba"] = ba_info
+    if undistorted is not None:
+        info["undistort"] = undistorted
     if annotate:
         info["annotated"] = annotated
     if plots is not None:

@@ -1141,6 +1141,53 @@ int aps_uniform_quota(const int64_t* counts, int n_cells, int64_t budget, int64_
 int aps_uniform_cell(int py, int px, int plane_h, int plane_w, int grid_rows, int grid_cols, int* cell);
 
 /* ============================================================================================
+ * Lens distortion: undistortImage / undistortPoints of the Computer Vision Toolbox ("Lens distortion contract")
+ * ============================================================================================ */
+/* A lens without skew.  Coordinates are the library's 1-based pixel coordinates (the frame of keypoints, of K and of
+ * aps_image_warp_u8): the 0-based pixel (row i, column j) sits at (u, v) = (j + 1, i + 1).  A two-term radial model has k3 = 0.
+ * The forward (distorting) map of a point (u, v) of the ideal image, in f64, evaluated exactly as parenthesised, no contraction:
+ *     x = (u - cx) / fx;  y = (v - cy) / fy;  r2 = x*x + y*y
+ *     rad = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *     dx = ((2*p1)*x)*y + p2*(r2 + (2*x)*x)
+ *     dy = p1*(r2 + (2*y)*y) + ((2*p2)*x)*y
+ *     ud = fx*(x*rad + dx) + cx;  vd = fy*(y*rad + dy) + cy
+ * tests/undistort_mirror.py restates the three entries below in NumPy, bit for bit.  Domain: moderate lenses, normalised
+ * radius below about 1; no fisheye. */
+typedef struct aps_lens {
+    double fx, fy, cx, cy, k1, k2, k3, p1, p2;
+} aps_lens;
+
+/* undistortImage: output pixel (i, j), 0-based, of the out_h x out_w view has the ideal coordinates (u, v) = (x0 + j, y0 + i)
+ * and samples the distorted image img (h x w x c uint8, c = 1 or 3, img_layout APS_IMG_U8_HWC or APS_IMG_U8_MATLAB; out has
+ * the same layout) at (ud, vd).  The sample is valid iff 1 <= ud <= w and 1 <= vd <= h (a NaN fails); then x1 = floor(ud),
+ * x2 = min(x1 + 1, w), wx = ud - x1, likewise in y, and the value is that of aps_image_warp_u8's bilinear branch:
+ * ((w11*p11 + w12*p12) + w21*p21) + w22*p22 with w11 = (1-wx)*(1-wy), w12 = (1-wx)*wy, w21 = wx*(1-wy), w22 = wx*wy and
+ * p11 = (y1, x1), p12 = (y2, x1), p21 = (y1, x2), p22 = (y2, x2), rounded half away from zero and clamped to 0..255.  An
+ * invalid sample gives `fill`.  A lens whose five coefficients are all zero copies the input into the view (ud = u, vd = v,
+ * decided on the host).  img and out: host or device memory each, not overlapping.  One launch on the calling thread's stream, one lane per output
+ * pixel; complete on return.
+ * Errors, all before any device work: APS_E_ARG for a NULL pointer, fx or fy not finite or not above 0, any other field not
+ * finite, fill outside 0..255, an origin of 2^24 or more in magnitude; APS_E_DIM for a non-positive size, c other than 1 or 3,
+ * an image of 2^31 / 3 pixels or more; APS_E_TYPE for an unknown layout. */
+int aps_undistort_image_u8(const uint8_t* img, int h, int w, int c, int img_layout, const aps_lens* lens, int out_h, int out_w,
+                           int x0, int y0, int fill, uint8_t* out);
+
+/* undistortPoints: the inverse map of n distorted points by exactly 20 fixed-point steps from x = xd = (ud - cx) / fx,
+ * y = yd = (vd - cy) / fy: each step is x <- (xd - dx(x, y)) / rad(x, y), y <- (yd - dy(x, y)) / rad(x, y), both from the
+ * previous (x, y); then u = fx*x + cx, v = fy*y + cy.  There is no convergence test.  pts and out: f64, x at [k] and y at
+ * [ld + k] (the layout of the extractors' loc), host or device memory each; the entries n..ld-1 of out are not written.
+ * n = 0 is a no-op.  Errors, before any device work: the lens errors above, APS_E_DIM for n < 0 or ld < n, APS_E_ARG for a
+ * NULL pointer when n > 0. */
+int aps_undistort_points(const double* pts, int64_t n, int64_t ld, const aps_lens* lens, double* out);
+
+/* The 'valid' output view of an h x w image: with (ux, uy) the aps_undistort_points images (the same kernel, on the device) of
+ * the pixel centres of the four border rows and columns, *x0 = ceil(max ux over the left column), x1 = floor(min ux over the
+ * right column), *y0 = ceil(max uy over the top row), y1 = floor(min uy over the bottom row), *out_h = y1 - *y0 + 1,
+ * *out_w = x1 - *x0 + 1 (host memory; the host takes the extrema).  Errors: the lens errors above, APS_E_DIM for a
+ * non-positive size, APS_E_ARG for a NULL pointer, a border that does not map to finite points, or an empty rectangle. */
+int aps_undistort_valid_view(int h, int w, const aps_lens* lens, int* x0, int* y0, int* out_h, int* out_w);
+
+/* ============================================================================================
  * Bench / test support — NOT part of the reference boundary
  * ============================================================================================ */
 /* One uint8 H x W x 3 (row-major interleaved) view of the seeded procedural world used by bench.py and the
