@@ -477,7 +477,8 @@ __global__ void image_warp_h_kernel(const T* __restrict__ in, int in_h, int in_w
                     rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr);
                     o = (T)rr;
                 } else {
-                    v = v < 0 ? 0 : (v > 1.0 ? 1.0 : v);  // max(0, min(maxVal, .)) with maxVal = 1 for float images (:216,:254)
+                    // max(0, min(maxVal, .)) with maxVal = 1 for float images (:216,:254); MATLAB's min skips a NaN: it gives maxVal
+                    v = v != v ? 1.0 : (v < 0 ? 0 : (v > 1.0 ? 1.0 : v));
                     o = (T)v;
                 }
             }

@@ -118,10 +118,18 @@ def _center_crop(J, Ht, Wt):
 def resizeImagesToLimits(imageFiles, heightLimit, widthLimit, mode="fit"):
     """imageFilesResized = resizeImagesToLimits(imageFiles, heightLimit, widthLimit, mode)
     (resizeImagesToLimits.m:1-160): 'fit' (isotropic shrink to the box, then all images to the common largest size),
-    'pad' (fit, then replicate-pad to the box) or 'fillcrop' (cover, then centre crop).  Resizing runs on the device."""
+    'pad' (fit, then replicate-pad to the box) or 'fillcrop' (cover, then centre crop).  Resizing runs on the device.
+    When no image exceeds the limits and all have one size, the input comes back untouched in every mode (:29-42)."""
     mode = str(mode).lower()
     if mode not in ("fit", "pad", "fillcrop"):
         raise ValueError(f"unknown mode '{mode}'")
+    if not isinstance(imageFiles, (list, tuple)) or len(imageFiles) == 0:
+        raise ValueError("imageFiles must be a nonempty cell array of images.")  # :21-23
+    if not (np.isscalar(heightLimit) and np.isscalar(widthLimit) and heightLimit > 0 and widthLimit > 0):
+        raise ValueError("heightLimit and widthLimit must be positive scalars.")  # :25-27
+    initial = [tuple(a.shape[:2]) if a.size else (0, 0) for a in map(np.asarray, imageFiles)]  # size([]) is [0 0]
+    if not any(h > heightLimit or w > widthLimit for (h, w) in initial) and len(set(initial)) == 1:
+        return list(imageFiles)  # all the same size, nothing to do
     stage1 = []
     for I in imageFiles:
         I = np.asarray(I)

@@ -645,7 +645,7 @@ int aps_image_warp_h_f32(const float* in, int in_h, int in_w, int c, const doubl
                          float* out);
 /* The same with options.method: 'nearest' (imageWarp.m:109-123: round(src), valid inside [1,w] x [1,h]), 'bilinear'
  * (:125-168) or 'bicubic' (:170-264: Keys kernel bicubicKernel :275-301 on the 4 x 4 taps around floor(src), valid for
- * 2 <= floor(src) <= size - 2, x direction first, result clamped to [0, 255] and rounded for uint8, to [0, 1] for f32). */
+ * 2 <= floor(src) <= size - 2, x direction first, result clamped to [0, 255] and rounded for uint8, to [0, 1] for f32, where a NaN gives 1: MATLAB's min and max skip it). */
 enum { APS_WARP_NEAREST = 0, APS_WARP_BILINEAR = 1, APS_WARP_BICUBIC = 2 };
 int aps_image_warp_u8(const uint8_t* in, int in_h, int in_w, int c, const double* H, int out_h, int out_w, double x0,
                       double y0, double sx, double sy, uint8_t fill, int method, uint8_t* out);

@@ -637,7 +637,8 @@ ORC_API void orc_image_warp_h_m(const float* in, int in_h, int in_w, int C, cons
                         rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr);
                         o = (float)rr;
                     } else {
-                        v = v < 0 ? 0 : (v > 1.0 ? 1.0 : v); /* maxVal = 1 for float images (:216,:254) */
+                        /* max(0, min(maxVal, v)), maxVal = 1 for float images (:216,:254); min skips a NaN: maxVal */
+                        v = v != v ? 1.0 : (v < 0 ? 0 : (v > 1.0 ? 1.0 : v));
                         o = (float)v;
                     }
                 }
