@@ -992,7 +992,7 @@ static void prepare_images(const aps_image* images, int n, PreparedImages& P, bo
 }
 
 static DevCanvas make_canvas(const aps_canvas& c) {
-    APS_REQUIRE(c.mode >= APS_PROJ_CYLINDRICAL && c.mode <= APS_PROJ_STEREOGRAPHIC, APS_E_ARG, "unknown projection mode %d", c.mode);
+    APS_REQUIRE(c.mode >= APS_PROJ_CYLINDRICAL && c.mode <= APS_PROJ_PANINI, APS_E_ARG, "unknown projection mode %d", c.mode);
     APS_REQUIRE(c.height > 0 && c.width > 0, APS_E_DIM, "empty canvas");
     APS_REQUIRE(c.f_pan > 0, APS_E_ARG, "fPan must be positive");
     DevCanvas d;
@@ -1302,18 +1302,29 @@ __device__ __forceinline__ void gain_ray(const DevCanvas& cv, float xp, float yp
         d[0] = cp * sinf(th);
         d[1] = sp;
         d[2] = cp * cosf(th);
+    } else if (cv.mode == APS_PROJ_MILLER) {
+        const float th = cv.o0 + xp / cv.f, ph = miller_elevation(cv.o1 + yp / cv.f);
+        const float cp = cosf(ph), sp = sinf(ph);
+        d[0] = cp * sinf(th);
+        d[1] = sp;
+        d[2] = cp * cosf(th);
     } else {
         float rx, ry, rz;
         if (cv.mode == APS_PROJ_PLANAR) {
             rx = cv.o0 + xp / cv.f;
             ry = cv.o1 + yp / cv.f;
             rz = 1.0f;
-        } else {
+        } else if (cv.mode == APS_PROJ_STEREOGRAPHIC) {
             const float a = cv.o0 + xp / cv.f, b = cv.o1 + yp / cv.f;
             const float r2 = a * a + b * b, den = 1.0f + r2;
             rx = 2.0f * a / den;
             ry = 2.0f * b / den;
             rz = (1.0f - r2) / den;
+        } else {  // fisheye / Panini; a fisheye point beyond pi: the zero ray, dropped by gain_sample (cam z = 0 is not in front)
+            const Ray3 r = wide_ray(cv.mode, cv.o0 + xp / cv.f, cv.o1 + yp / cv.f);
+            rx = r.v[0];
+            ry = r.v[1];
+            rz = r.v[2];
         }
         d[0] = (cv.Rref[0] * rx + cv.Rref[1] * ry) + cv.Rref[2] * rz;
         d[1] = (cv.Rref[3] * rx + cv.Rref[4] * ry) + cv.Rref[5] * rz;

@@ -66,7 +66,7 @@ struct ColTrig {
     float s, c;  // sin/cos of theta (cylindrical, spherical)
 };
 struct RowTrig {
-    float s, c;  // spherical: sin/cos of phi; cylindrical: s = height
+    float s, c;  // spherical, Miller: sin/cos of the elevation; cylindrical: s = height
 };
 
 struct RwArgs {
@@ -90,8 +90,8 @@ struct RwArgs {
     int H, W, out_layout, white;
     const int* cd_s0;     // fused shrink (rw_down_fused_kernel): first source index per output sample ...
     const float* cd_w;    // ... and the weights of the consecutive source samples from there, [sample][NCP]
-    const ColTrig* ct;  // per canvas column: sin/cos of theta (cylindrical, spherical), rw_trig_kernel
-    const RowTrig* rt;  // per canvas row: sin/cos of phi (spherical) or the height (cylindrical)
+    const ColTrig* ct;  // per canvas column: sin/cos of theta (cylindrical, spherical, Miller), rw_trig_kernel
+    const RowTrig* rt;  // per canvas row: sin/cos of the elevation (spherical, Miller) or the height (cylindrical)
 };
 
 // largest s with ptr[s] <= bid (ptr nondecreasing, ptr[0] = 0, n segments); every wave evaluates it for itself
@@ -241,12 +241,17 @@ __device__ __forceinline__ ColTrig col_trig(const DevCanvas& cv, float xp) {
     t.c = cosf(th);
     return t;
 }
+template <bool NEW = true>
 __device__ __forceinline__ RowTrig row_trig(const DevCanvas& cv, float yp) {
     RowTrig t;
     const float ph = cv.o1 + yp / cv.f;
     if (cv.mode == APS_PROJ_SPHERICAL) {
         t.c = cosf(ph);
         t.s = sinf(ph);
+    } else if (NEW && cv.mode == APS_PROJ_MILLER) {  // (ph is the canvas height here: the elevation behind it, then as spherical)
+        const float el = miller_elevation(ph);
+        t.c = cosf(el);
+        t.s = sinf(el);
     } else {
         t.s = ph;
         t.c = 1.0f;
@@ -263,11 +268,12 @@ __global__ void rw_trig_kernel(DevCanvas cv, ColTrig* __restrict__ ct, RowTrig* 
     if (i < cv.H) rt[i] = row_trig(cv, (float)i);
 }
 
-// canvas_ray with the transcendental parts taken from the tables (cylindrical / spherical) or evaluated in
-// place (planar / stereographic have none)
+// canvas_ray with the transcendental parts taken from the tables (cylindrical / spherical / Miller) or evaluated in
+// place (the R_ref family: planar / stereographic / Panini have none, the fisheye's depend on both coordinates)
+template <bool NEW = true>
 __device__ __forceinline__ void ray_from_tables(const DevCanvas& cv, const ColTrig& ct, const RowTrig& rt, float xp,
                                                 float yp, float d[3]) {
-    if (cv.mode == APS_PROJ_CYLINDRICAL || cv.mode == APS_PROJ_SPHERICAL) {
+    if (cv.mode == APS_PROJ_CYLINDRICAL || cv.mode == APS_PROJ_SPHERICAL || (NEW && cv.mode == APS_PROJ_MILLER)) {
         float x, y, z;
         if (cv.mode == APS_PROJ_CYLINDRICAL) {
             x = ct.s;
@@ -284,7 +290,7 @@ __device__ __forceinline__ void ray_from_tables(const DevCanvas& cv, const ColTr
         d[1] = y / n;
         d[2] = z / n;
     } else {
-        canvas_ray(cv, xp, yp, d);
+        canvas_ray<NEW>(cv, xp, yp, d);
     }
 }
 
@@ -479,9 +485,10 @@ __device__ __forceinline__ float4 sample_fast(const DevImage& im, const FastImag
 
 // the ray of ray_from_tables with the normalisation through v_rsq_f32 (the spherical / cylindrical rays are unit
 // vectors up to rounding already)
+template <bool NEW = true>
 __device__ __forceinline__ void ray_fast(const DevCanvas& cv, const ColTrig& ct, const RowTrig& rt, float xp, float yp,
                                          float d[3]) {
-    if (cv.mode == APS_PROJ_CYLINDRICAL || cv.mode == APS_PROJ_SPHERICAL) {
+    if (cv.mode == APS_PROJ_CYLINDRICAL || cv.mode == APS_PROJ_SPHERICAL || (NEW && cv.mode == APS_PROJ_MILLER)) {
         float x, y, z;
         if (cv.mode == APS_PROJ_CYLINDRICAL) {
             x = ct.s;
@@ -498,7 +505,7 @@ __device__ __forceinline__ void ray_fast(const DevCanvas& cv, const ColTrig& ct,
         d[1] = y * r;
         d[2] = z * r;
     } else {
-        canvas_ray(cv, xp, yp, d);
+        canvas_ray<NEW>(cv, xp, yp, d);
     }
 }
 
@@ -658,7 +665,7 @@ constexpr int kWL = 6;  // layers of a block whose samples are parked in LDS; fu
 // pyramids, collapse) byte for byte against render.hip's per-tile kernels.
 // The walking form of a block: ray once per pixel, then the tile's layers that meet the block one after the other
 // (sample -> first sum, second sum, store).  ct / rt: the pixel's column / row trig entries.
-template <bool FAST>
+template <bool FAST, bool NEW>
 __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T, int x0, int y0, float* s_u8, float4 (*s_g)[256],
                                                 const ColTrig& ct, const RowTrig& rt) {
     const int tid = threadIdx.x;
@@ -668,14 +675,14 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
     float d[3] = {0.f, 0.f, 1.f};
     if (in_tile) {
         if (FAST)
-            ray_fast(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
+            ray_fast<NEW>(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
         else
-            ray_from_tables(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
+            ray_from_tables<NEW>(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
     }
     // (always_inline: left to its cost model the compiler turned `sample` into a real function - every by-reference
     // capture, the kernel arguments included, then lives in scratch memory: 400 bytes per lane and a 5x slower kernel)
     auto exact_ray = [&](float de[3]) __attribute__((always_inline)) {
-        ray_from_tables(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), de);
+        ray_from_tables<NEW>(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), de);
     };
     auto sample = [&](const DevImage& im) __attribute__((always_inline)) {
         if (FAST && im.w > 3 && im.h > 3)
@@ -743,6 +750,8 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
 }
 
 // The exact form (APS_WARP_EXACT=1): the walking form on the canvas-wide trig tables (A.ct, A.rt).
+// NEW: the mode family (canvas_ray in render_dev.h); NEW = false serves the reference's four modes with the code they always had.
+template <bool NEW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_kernel(RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
     __shared__ float s_u8[256];
     __shared__ float4 s_g[kWL][256];
@@ -758,7 +767,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     __syncthreads();
     const ColTrig ct = A.ct[T.c0 + min(x0 + (tid & (kUW - 1)), w - 1)];
     const RowTrig rt = A.rt[T.r0 + min(y0 + tid / kUW, h - 1)];
-    warp_block_walk<false>(A, T, x0, y0, s_u8, s_g, ct, rt);
+    warp_block_walk<false, NEW>(A, T, x0, y0, s_u8, s_g, ct, rt);
 }
 
 // ---- the warp in its staged form (default) ----------------------------------------------------------------------------
@@ -808,6 +817,7 @@ __device__ __forceinline__ bool project_lc(const float R[9], float fx, float fy,
     return inside && front && cam[2] > 0.0f;
 }
 
+template <bool NEW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_staged_kernel(
     RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
     __shared__ LayerConst s_lc[kWF];
@@ -824,7 +834,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     const int x0 = (local % nbx) * kUW, y0 = (local / nbx) * kUH;
     const int bx1 = min(x0 + kUW, w), by1 = min(y0 + kUH, h);
     if (tid < kUW) s_ct[tid] = col_trig(A.cv, (float)(T.c0 + min(x0 + tid, w - 1)));
-    if (tid >= 64 && tid < 64 + kUH) s_rt[tid - 64] = row_trig(A.cv, (float)(T.r0 + min(y0 + tid - 64, h - 1)));
+    if (tid >= 64 && tid < 64 + kUH) s_rt[tid - 64] = row_trig<NEW>(A.cv, (float)(T.r0 + min(y0 + tid - 64, h - 1)));
     const LayerSet ls = block_layers(A, T, 0, x0, y0, bx1, by1);
     const int n0 = __popcll(ls.m[0]);
     const int nvis = n0 + __popcll(ls.m[1]);
@@ -859,13 +869,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (staged)
         for (int j = 0; j < nvis; ++j) small_image |= f2i(s_lc[j].q[4].w) == 0;
     if (!staged || small_image) {
-        warp_block_walk<true>(A, T, x0, y0, nullptr, s_g, ct, rt);
+        warp_block_walk<true, NEW>(A, T, x0, y0, nullptr, s_g, ct, rt);
         return;
     }
     const int x = x0 + (tid & (kUW - 1)), y = y0 + tid / kUW;
     const bool in_tile = x < w && y < h;
     float d[3] = {0.f, 0.f, 1.f};
-    if (in_tile) ray_fast(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
+    if (in_tile) ray_fast<NEW>(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), d);
     // pass A: (u, v, w) per staged layer, no global memory; parked in LDS (the parking area of the walking form, which
     // this block does not use).  Rolled loops: unrolled over kWF the kernel was 17 000 instructions, twice the
     // instruction cache.
@@ -899,7 +909,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             }
             if (exact) {
                 float de[3];
-                ray_from_tables(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), de);
+                ray_from_tables<NEW>(A.cv, ct, rt, (float)(T.c0 + x), (float)(T.r0 + y), de);
                 ok = project_lc(R, fx, fy, cx, cy, iw, ih, de, u, v, cam2);
             }
             if (ok) {
@@ -1722,13 +1732,13 @@ RwArgs base_args(const RwTile* d_tiles, int nt, const DevImage* dimgs, const Dev
 }
 
 // ---- stage: footprints -------------------------------------------------------------------------------------------------------
-// Footprints on the host (cylindrical / spherical canvases): the image rectangle [1,w] x [1,h] maps to a region of the
+// Footprints on the host (cylindrical / spherical / Miller canvases): the image rectangle [1,w] x [1,h] maps to a region of the
 // canvas whose outline is the forward image of the rectangle's border (pixel -> K^-1 -> R' -> angles -> canvas pixels,
 // f64 on the f32 camera / canvas values the kernels use).  The outline, sampled in short chords and grown by half a pixel,
 // is clipped against each tile (Sutherland-Hodgman) and the clipped polygon's bounding box, padded by 3 pixels (chord sag
 // < 0.1, f32 vs f64 rounding < 0.01), is a SUPERSET of the tile pixels that sample the image - which is all a footprint must
 // be (kernels evaluate the exact predicate per pixel inside it).  This replaces the coverage kernel and its read-back.
-// Not applicable (host_footprints returns false, the caller runs rw_cover_kernel): planar / stereographic canvases, an outline
+// Not applicable (host_footprints returns false, the caller runs rw_cover_kernel): the R_ref family's canvases, an outline
 // that crosses the theta = +-pi seam, an image that contains a pole.
 struct Polygon {
     std::vector<double> x, y;
@@ -1756,9 +1766,9 @@ struct Bounds {
 // image pixel (u, v) -> canvas pixel (x, y) and the azimuth th it lies at
 struct ToCanvas {
     double R[9], fx, fy, cx, cy, f, o0, o1;
-    bool spherical;
+    int mode;
     ToCanvas(const DevImage& im, const DevCanvas& cv)
-        : fx(im.fx), fy(im.fy), cx(im.cx), cy(im.cy), f(cv.f), o0(cv.o0), o1(cv.o1), spherical(cv.mode == APS_PROJ_SPHERICAL) {
+        : fx(im.fx), fy(im.fy), cx(im.cx), cy(im.cy), f(cv.f), o0(cv.o0), o1(cv.o1), mode(cv.mode) {
         for (int k = 0; k < 9; ++k) R[k] = im.R[k];
     }
     void operator()(double u, double v, double& x, double& y, double& th) const {
@@ -1769,7 +1779,9 @@ struct ToCanvas {
         const double d2 = R[6] * c[0] + R[7] * c[1] + R[8] * c[2];
         th = std::atan2(d0, d2);
         const double hz = std::hypot(d0, d2);
-        const double b = spherical ? std::atan2(d1, hz) : d1 / hz;
+        const double b = mode == APS_PROJ_SPHERICAL ? std::atan2(d1, hz)
+                         : mode == APS_PROJ_MILLER  ? 1.25 * std::asinh(std::tan(0.8 * std::atan2(d1, hz)))
+                                                    : d1 / hz;
         x = (th - o0) * f;
         y = (b - o1) * f;
     }
@@ -1869,7 +1881,7 @@ bool host_footprints_range(const DevImage* himgs, int n_img, int i_begin, int i_
 // (round 6: 0.65 ms of every render call on one thread, in front of the call's first kernel launch - most of a rank's fixed
 // render cost at 8 ranks).  APS_RENDER_HOST_THREADS=1: one thread.
 bool host_footprints(const DevImage* himgs, int n_img, const DevCanvas& cv, const std::vector<RwTile>& tiles, std::vector<int>& hbox) {
-    if (cv.mode != APS_PROJ_SPHERICAL && cv.mode != APS_PROJ_CYLINDRICAL) return false;
+    if (cv.mode != APS_PROJ_SPHERICAL && cv.mode != APS_PROJ_CYLINDRICAL && cv.mode != APS_PROJ_MILLER) return false;
     std::fill(hbox.begin(), hbox.end(), 0);
     const char* e = std::getenv("APS_RENDER_HOST_THREADS");
     int nthr = e ? std::atoi(e) : 6;
@@ -2016,10 +2028,11 @@ unsigned xcd_grid(int n_blocks) { return 8u * (unsigned)((n_blocks + 7) / 8); } 
 void launch_warp(const RwArgs& A, const int* d_blk0, int n_blocks, bool exact) {
     if (n_blocks == 0) return;
     Prof prof("render_warp");
+    const bool nw = A.cv.mode >= APS_PROJ_MILLER;  // (the kernels' mode family)
     if (exact)
-        rw_warp_kernel<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+        (nw ? rw_warp_kernel<true> : rw_warp_kernel<false>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
     else
-        rw_warp_staged_kernel<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+        (nw ? rw_warp_staged_kernel<true> : rw_warp_staged_kernel<false>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
     check_launch("rw_warp_kernel");
 }
 // the pyramids, fine to coarse

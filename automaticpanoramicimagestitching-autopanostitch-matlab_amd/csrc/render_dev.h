@@ -35,6 +35,38 @@ struct DevCanvas {
     float Rref[9];
 };
 
+// The ray generators of the projections that are not in the reference ("Projection contract"); canvas_ray, gain_ray
+// (render.hip) and row_trig (render_batch.hip) all come here, so each operation order is stated once.
+// Miller: the elevation at canvas height b.
+__device__ __forceinline__ float miller_elevation(float b) { return 1.25f * atanf(sinhf(0.8f * b)); }
+// Fisheye / Panini: the ray at (a, b) in the reference frame, not normalised.  A fisheye pixel further than pi from the axis
+// looks at nothing: the zero vector, which stays zero through R_ref and the normalisation and which project() refuses.
+// A real function, result in registers: inlined, its sinf / cosf raised the register count of rw_warp_staged_kernel for
+// every mode (73 -> 78 VGPRs); called, the kernels of the other modes keep their registers (DESIGN.md has the table).
+struct Ray3 {
+    float v[3];
+};
+inline __device__ __noinline__ Ray3 wide_ray(int mode, float a, float b) {
+    Ray3 ray;
+    float* r = ray.v;
+    if (mode == APS_PROJ_FISHEYE) {
+        const float rad = sqrtf(a * a + b * b);
+        const float s = rad > 1e-6f ? sinf(rad) / rad : 1.0f;
+        const bool seen = !(rad > 3.14159265f);
+        r[0] = seen ? s * a : 0.0f;
+        r[1] = seen ? s * b : 0.0f;
+        r[2] = seen ? cosf(rad) : 0.0f;
+    } else {  // APS_PROJ_PANINI
+        r[0] = a;
+        r[1] = b;
+        r[2] = 1.0f - 0.25f * a * a;
+    }
+    return ray;
+}
+
+// NEW = false: the four modes of the reference only, the code the kernels had before the other projections came (the hot
+// warp kernels of render_batch.hip are instantiated per mode family, so that those modes run the instructions they ran).
+template <bool NEW = true>
 __device__ __forceinline__ void canvas_ray(const DevCanvas& cv, float xp, float yp, float d[3]) {
     float x, y, z;
     if (cv.mode == APS_PROJ_CYLINDRICAL) {
@@ -48,18 +80,29 @@ __device__ __forceinline__ void canvas_ray(const DevCanvas& cv, float xp, float 
         x = cp * sinf(th);
         y = sp;
         z = cp * cosf(th);
+    } else if (NEW && cv.mode == APS_PROJ_MILLER) {
+        const float th = cv.o0 + xp / cv.f, ph = miller_elevation(cv.o1 + yp / cv.f);
+        const float cp = cosf(ph), sp = sinf(ph);
+        x = cp * sinf(th);
+        y = sp;
+        z = cp * cosf(th);
     } else {
         float rx, ry, rz;
         if (cv.mode == APS_PROJ_PLANAR) {
             rx = cv.o0 + xp / cv.f;
             ry = cv.o1 + yp / cv.f;
             rz = 1.0f;
-        } else {
+        } else if (!NEW || cv.mode == APS_PROJ_STEREOGRAPHIC) {
             const float a = cv.o0 + xp / cv.f, b = cv.o1 + yp / cv.f;
             const float r2 = a * a + b * b, den = 1.0f + r2;
             rx = 2.0f * a / den;
             ry = 2.0f * b / den;
             rz = (1.0f - r2) / den;
+        } else {
+            const Ray3 r = wide_ray(cv.mode, cv.o0 + xp / cv.f, cv.o1 + yp / cv.f);
+            rx = r.v[0];
+            ry = r.v[1];
+            rz = r.v[2];
         }
         x = (cv.Rref[0] * rx + cv.Rref[1] * ry) + cv.Rref[2] * rz;
         y = (cv.Rref[3] * rx + cv.Rref[4] * ry) + cv.Rref[5] * rz;

@@ -76,7 +76,7 @@ def gainCompensationRKf(images, cameras, mode, refIdx, opts, geo):
     o = dict(opts or {})
     stride = max(1, int(o.get("overlapStride", 5)))
     g = dict(geo)
-    g["mode"] = mode
+    g["mode"] = str(mode).lower()  # (canvas_geometry's spelling: the canvas struct is keyed by it)
     Nij, sCi, sCj = gain_overlap_stats(images, cameras, g, stride)
     return solve_gains(Nij, sCi, sCj, o, refIdx)
 

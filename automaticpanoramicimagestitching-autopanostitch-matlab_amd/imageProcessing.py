@@ -211,7 +211,7 @@ def panoramaCropper(input, stitchedImage):
     return stitchedImage[oy - 1:oy + ch, ox - 1:ox + cw]
 
 
-PANO_PROJECTIONS = ("planar", "cylindrical", "spherical", "equirectangular", "stereographic")
+PANO_PROJECTIONS = ("planar", "cylindrical", "spherical", "equirectangular", "stereographic", "miller", "fisheye", "panini")
 
 
 def panorama_file_names(input, panoStore, myImg, datasetName):

@@ -17,7 +17,11 @@ from ._capi import check, lib, ptr
 
 _MODES = {"cylindrical": _capi.APS_PROJ_CYLINDRICAL, "spherical": _capi.APS_PROJ_SPHERICAL,
           "equirectangular": _capi.APS_PROJ_SPHERICAL, "planar": _capi.APS_PROJ_PLANAR,
-          "perspective": _capi.APS_PROJ_PLANAR, "stereographic": _capi.APS_PROJ_STEREOGRAPHIC}
+          "perspective": _capi.APS_PROJ_PLANAR, "stereographic": _capi.APS_PROJ_STEREOGRAPHIC,
+          # not in the reference (its README's "inclusion of other projections"); DESIGN.md, "Projection contract"
+          "miller": _capi.APS_PROJ_MILLER, "fisheye": _capi.APS_PROJ_FISHEYE, "panini": _capi.APS_PROJ_PANINI}
+_PLANE_MODES = ("planar", "perspective", "panini")  # asymmetric bounds about Rref, planarBounds' structure
+_DISC_MODES = ("stereographic", "fisheye")          # a centred square about Rref, stereographicBounds' structure
 _BLEND = {"none": _capi.APS_BLEND_NONE, "linear": _capi.APS_BLEND_LINEAR, "multiband": _capi.APS_BLEND_MULTIBAND}
 _POLICY = {"last": _capi.APS_NONE_LAST, "first": _capi.APS_NONE_FIRST, "maxangle": _capi.APS_NONE_MAXANGLE}
 
@@ -205,25 +209,94 @@ def stereographicBounds(cams, imgSize, Rref, robustPct, absCap):
     return amin, amax, bmin, bmax
 
 
+def millerHeight(ph):
+    """The Miller cylindrical projection's canvas height of the elevation ph (f64): 1.25 asinh(tan(0.8 ph)); the poles
+    lie at +-2.3034.  Its inverse, 1.25 atan(sinh(0.8 y)), is what the device evaluates per canvas row."""
+    return 1.25 * np.arcsinh(np.tan(0.8 * np.asarray(ph, np.float64)))
+
+
+MILLER_POLE = 1.25 * math.asinh(math.tan(0.4 * math.pi))  # 2.3034...: the canvas height of a pole
+
+
+def millerBounds(cams, imgSize):
+    """sphericalBounds with both elevation limits mapped through millerHeight (monotonic, so the extrema map to the extrema)."""
+    tmin, tmax, pmin, pmax = sphericalBounds(cams, imgSize)
+    return tmin, tmax, float(millerHeight(pmin)), float(millerHeight(pmax))
+
+
+def fisheyeBounds(cams, imgSize, Rref, robustPct):
+    """stereographicBounds' structure (512-sample border grid, percentiles per image, +-1 fallbacks) for the equidistant
+    azimuthal map about Rref: theta = acos(z) of the unit ray, (a, b) = theta * (x, y) / hypot(x, y), (0, 0) on the axis.
+    |(a, b)| <= pi, so there is nothing to cap."""
+    amin = bmin = math.inf
+    amax = bmax = -math.inf
+    for rays in _all_grid_rays(cams, imgSize, border=512):
+        rayR = np.asarray(Rref, np.float64) @ rays
+        nr = np.sqrt((rayR ** 2).sum(0))
+        xr, yr, zr = rayR / nr
+        theta = np.arccos(np.clip(zr, -1.0, 1.0))
+        rho = np.hypot(xr, yr)
+        with np.errstate(all="ignore"):
+            k = np.where(rho > 0, theta / np.where(rho > 0, rho, 1.0), 0.0)
+        a, b = k * xr, k * yr
+        amin, amax = min(amin, _prctile(a, robustPct[0])), max(amax, _prctile(a, robustPct[1]))
+        bmin, bmax = min(bmin, _prctile(b, robustPct[0])), max(bmax, _prctile(b, robustPct[1]))
+    if not (np.isfinite(amin) and np.isfinite(amax)) or amin >= amax:
+        amin, amax = -1.0, 1.0
+    if not (np.isfinite(bmin) and np.isfinite(bmax)) or bmin >= bmax:
+        bmin, bmax = -1.0, 1.0
+    return amin, amax, bmin, bmax
+
+
+def paniniBounds(cams, imgSize, Rref, robustPct, uvAbsCap):
+    """planarBounds' structure for the Pannini map (d = 1) about Rref: on unit rays, hz = hypot(x, z), valid where
+    hz + z > 1e-4 (everything but the half plane straight behind the axis), a = 2 x / (hz + z), b = 2 y / (hz + z)."""
+    umin = vmin = math.inf
+    umax = vmax = -math.inf
+    for rays in _all_grid_rays(cams, imgSize, border=512):
+        rayR = np.asarray(Rref, np.float64) @ rays
+        xr, yr, zr = rayR / np.sqrt((rayR ** 2).sum(0))
+        den = np.hypot(xr, zr) + zr
+        m = den > 1e-4
+        if not m.any():
+            continue
+        ur, vr = 2.0 * xr[m] / den[m], 2.0 * yr[m] / den[m]
+        if np.isfinite(uvAbsCap) and uvAbsCap > 0:
+            ur = np.clip(ur, -uvAbsCap, uvAbsCap)
+            vr = np.clip(vr, -uvAbsCap, uvAbsCap)
+        umin, umax = min(umin, _prctile(ur, robustPct[0])), max(umax, _prctile(ur, robustPct[1]))
+        vmin, vmax = min(vmin, _prctile(vr, robustPct[0])), max(vmax, _prctile(vr, robustPct[1]))
+    if not (np.isfinite(umin) and np.isfinite(umax)) or umin >= umax:
+        umin, umax = -1.0, 1.0
+    if not (np.isfinite(vmin) and np.isfinite(vmax)) or vmin >= vmax:
+        vmin, vmax = -1.0, 1.0
+    return umin, umax, vmin, vmax
+
+
 def canvas_geometry(cameras, imgSize, mode, refIdx, opts):
-    """Bounds + canvas size (renderPanorama.m:84-232).  Returns dict(mode, H, W, fPan, o0, o1, Rref, refIdx)."""
+    """Bounds + canvas size (renderPanorama.m:84-232).  Returns dict(mode, H, W, fPan, o0, o1, Rref, refIdx).  'fisheye' is
+    sized like 'stereographic' (a centred square, autoRef by its area) and 'panini' like 'planar'; 'miller' like 'spherical'."""
     mode = str(mode).lower()
     if mode not in _MODES:
         raise ValueError("mode must be cylindrical, spherical, or planar/perspective")
     o = opts
     f = float(o["fPan"])
     n = len(cameras)
-    if mode in ("planar", "perspective", "stereographic") and o["autoRef"]:  # :84-122
+    if mode in _PLANE_MODES + _DISC_MODES and o["autoRef"]:  # :84-122
         best, best_idx = math.inf, refIdx
         for ii in range(n):
             Rr = cameras[ii]["R"]
-            if mode == "stereographic":
-                a0, a1, b0, b1 = stereographicBounds(cameras, imgSize, Rr, o["robustPct"], o["uvAbsCap"])
+            if mode in _DISC_MODES:
+                if mode == "stereographic":
+                    a0, a1, b0, b1 = stereographicBounds(cameras, imgSize, Rr, o["robustPct"], o["uvAbsCap"])
+                else:
+                    a0, a1, b0, b1 = fisheyeBounds(cameras, imgSize, Rr, o["robustPct"])
                 ext = max(abs(a0), abs(a1), abs(b0), abs(b1)) * (1 + 2 * o["margin"]) + o["pixelPad"] / f
                 Wi = max(1, math.ceil(2 * f * ext * o["resScale"]))
                 area = float(Wi) * Wi
             else:
-                u0, u1, v0, v1 = planarBounds(cameras, imgSize, Rr, o["robustPct"], o["uvAbsCap"])
+                plane = paniniBounds if mode == "panini" else planarBounds
+                u0, u1, v0, v1 = plane(cameras, imgSize, Rr, o["robustPct"], o["uvAbsCap"])
                 du, dv = u1 - u0, v1 - v0
                 u0, u1 = u0 - o["margin"] * du - o["pixelPad"] / f, u1 + o["margin"] * du + o["pixelPad"] / f
                 v0, v1 = v0 - o["margin"] * dv - o["pixelPad"] / f, v1 + o["margin"] * dv + o["pixelPad"] / f
@@ -237,21 +310,30 @@ def canvas_geometry(cameras, imgSize, mode, refIdx, opts):
         a0, a1, b0, b1 = cylindricalBounds(cameras, imgSize)
     elif mode in ("spherical", "equirectangular"):
         a0, a1, b0, b1 = sphericalBounds(cameras, imgSize)
+    elif mode == "miller":
+        a0, a1, b0, b1 = millerBounds(cameras, imgSize)
     elif mode in ("planar", "perspective"):
         a0, a1, b0, b1 = planarBounds(cameras, imgSize, Rref, o["robustPct"], o["uvAbsCap"])
+    elif mode == "panini":
+        a0, a1, b0, b1 = paniniBounds(cameras, imgSize, Rref, o["robustPct"], o["uvAbsCap"])
     else:
-        a0, a1, b0, b1 = stereographicBounds(cameras, imgSize, Rref, o["robustPct"], o["uvAbsCap"])
+        if mode == "stereographic":
+            a0, a1, b0, b1 = stereographicBounds(cameras, imgSize, Rref, o["robustPct"], o["uvAbsCap"])
+        else:
+            a0, a1, b0, b1 = fisheyeBounds(cameras, imgSize, Rref, o["robustPct"])
         ext = max(abs(a0), abs(a1), abs(b0), abs(b1))
         a0, a1, b0, b1 = -ext, ext, -ext, ext
     da, db = a1 - a0, b1 - b0
     a0, a1 = a0 - o["margin"] * da, a1 + o["margin"] * da
     b0, b1 = b0 - o["margin"] * db, b1 + o["margin"] * db
-    if mode in ("planar", "perspective", "stereographic"):
+    if mode == "miller":  # the margin must not push rows past a pole: there the elevation runs beyond 90 degrees and the ray
+        b0, b1 = max(b0, -MILLER_POLE), min(b1, MILLER_POLE)  # wraps to the opposite azimuth ("Projection contract")
+    if mode in _PLANE_MODES + _DISC_MODES:
         a0, a1 = a0 - o["pixelPad"] / f, a1 + o["pixelPad"] / f
         b0, b1 = b0 - o["pixelPad"] / f, b1 + o["pixelPad"] / f
     W = max(1, math.ceil(f * (a1 - a0) * rs))
     H = max(1, math.ceil(f * (b1 - b0) * rs))
-    if mode in ("planar", "perspective", "stereographic"):  # global pixel cap (:170-177)
+    if mode in _PLANE_MODES + _DISC_MODES:  # global pixel cap (:170-177)
         maxPixel = round(o["maxMegapixel"] * 1e6)
         if float(H) * float(W) > maxPixel:
             s = math.sqrt(maxPixel / (float(H) * float(W)))
@@ -340,6 +422,20 @@ def warped_boxes(cameras, imgSize, geo):
                 xr, yr, zr = rayR / np.sqrt((rayR ** 2).sum(0))
                 den = np.maximum(1 + zr, 1e-6)  # :1269
                 a, b = xr / den, yr / den
+            elif mode == "miller":
+                a = np.arctan2(rayW[0], rayW[2])
+                b = millerHeight(np.arctan2(rayW[1], np.hypot(rayW[0], rayW[2])))
+            elif mode == "fisheye":
+                rayR = Rref @ rayW
+                xr, yr, zr = rayR / np.sqrt((rayR ** 2).sum(0))
+                rho = np.hypot(xr, yr)
+                k = np.where(rho > 0, np.arccos(np.clip(zr, -1.0, 1.0)) / np.where(rho > 0, rho, 1.0), 0.0)
+                a, b = k * xr, k * yr
+            elif mode == "panini":
+                rayR = Rref @ rayW
+                xr, yr, zr = rayR / np.sqrt((rayR ** 2).sum(0))
+                den = np.maximum(np.hypot(xr, zr) + zr, 1e-6)  # (clamped like the stereographic denominator)
+                a, b = 2.0 * xr / den, 2.0 * yr / den
             else:
                 raise ValueError("mode")
             polys[i, :, 0] = (a - o0) * f + 1.0
@@ -898,7 +994,7 @@ def warp_tile(image, camera, geo, r0, c0, ht, wt, anglePower=2.0, gain=(1.0, 1.0
     return S, M.astype(bool), Wa, Wf
 
 
-_DISPLAY_PROJECTIONS = ("planar", "cylindrical", "spherical", "equirectangular", "stereographic")
+_DISPLAY_PROJECTIONS = ("planar", "cylindrical", "spherical", "equirectangular", "stereographic", "miller", "fisheye", "panini")
 
 
 def displayPanorama(input, finalPanoramaTforms, finalrefIdxs, imagesAll, imageSizesAll, panoIndices, device_out=False):

@@ -396,11 +396,16 @@ int aps_ransac_homography_batch(const double* pts1, const double* pts2, int64_t 
  * (3) Rendering — PP/renderPanorama/renderPanorama.m, PP/blending/ (both .m files), PP/imageProcessing/imageWarp.m
  * ============================================================================================ */
 
+/* Canvas pixel (xp, yp), 0-based -> a = origin0 + xp / f_pan, b = origin1 + yp / f_pan -> ray ("Projection
+ * contract").  Modes 0, 1 and 4 are separable in (azimuth, height); modes 2, 3, 5 and 6 are drawn about R_ref. */
 enum {
-    APS_PROJ_CYLINDRICAL = 0,
-    APS_PROJ_SPHERICAL = 1, /* 'equirectangular' is an alias (renderPanorama.m:180-189,357) */
-    APS_PROJ_PLANAR = 2,
-    APS_PROJ_STEREOGRAPHIC = 3
+    APS_PROJ_CYLINDRICAL = 0,   /* azimuth a, height b = y / hypot(x, z)                                          */
+    APS_PROJ_SPHERICAL = 1,     /* azimuth a, elevation b; 'equirectangular' is an alias (renderPanorama.m:180-189,357) */
+    APS_PROJ_PLANAR = 2,        /* pinhole about R_ref: ray (a, b, 1)                                             */
+    APS_PROJ_STEREOGRAPHIC = 3, /* about R_ref: (a, b) = (x, y) / (1 + z) of the unit ray                         */
+    APS_PROJ_MILLER = 4,        /* Miller cylindrical: azimuth a, elevation 1.25 atan(sinh(0.8 b)); poles at b = +-2.3034 */
+    APS_PROJ_FISHEYE = 5,       /* equidistant azimuthal about R_ref: hypot(a, b) = angle from the axis; void beyond pi */
+    APS_PROJ_PANINI = 6         /* Pannini, d = 1, about R_ref: ray (a, b, 1 - a^2 / 4); verticals stay straight  */
 };
 enum { APS_BLEND_NONE = 0, APS_BLEND_LINEAR = 1, APS_BLEND_MULTIBAND = 2 };
 enum { APS_NONE_LAST = 0, APS_NONE_FIRST = 1, APS_NONE_MAXANGLE = 2 };
@@ -424,9 +429,9 @@ typedef struct aps_canvas {
     int mode;            /* APS_PROJ_*                                                          */
     int height, width;   /* H, W (:137-146,180-189)                                             */
     double f_pan;        /* opts.fPan * opts.resScale enters only through these three:          */
-    double origin0;      /* th0 (cyl/sph) or u0 (planar/stereo)                                 */
-    double origin1;      /* h0 (cyl), ph0 (sph) or v0 (planar/stereo)                           */
-    double R_ref[9];     /* cameras(refIdx).R, column-major (planar/stereographic only)         */
+    double origin0;      /* th0 (cyl/sph/miller) or u0 (planar/stereo/fisheye/panini)           */
+    double origin1;      /* h0 (cyl), ph0 (sph), y0 (miller) or v0 (planar/stereo/fisheye/panini) */
+    double R_ref[9];     /* cameras(refIdx).R, column-major (planar/stereo/fisheye/panini only) */
 } aps_canvas;
 
 typedef struct aps_render_opts {
