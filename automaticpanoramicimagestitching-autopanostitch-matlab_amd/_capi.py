@@ -145,6 +145,14 @@ class aps_fast_orb_params(C.Structure):
                 ("grid_cols", C.c_int)]
 
 
+APS_CORNER_FAST, APS_CORNER_HARRIS = 0, 1
+APS_DESC_FREAK, APS_DESC_ORB = 0, 1
+
+
+class aps_corner_params(C.Structure):
+    _fields_ = [("chain", aps_fast_orb_params), ("corner", C.c_int), ("descriptor", C.c_int)]
+
+
 class aps_lens(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")]
 
@@ -291,6 +299,10 @@ _SIGNATURES = {
                              _vp, _i64, C.POINTER(_i64)],
     "aps_fast_orb_extract_batch": [C.POINTER(aps_fast_view), _i, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _i, _i64, _i64],
     "aps_orb_pattern": [_vp, _vp, _vp, C.POINTER(_i)],
+    "aps_corner_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_corner_params), _vp, _i, _i64, _vp, _i64,
+                           _vp, _i64, C.POINTER(_i64)],
+    "aps_corner_extract_batch": [C.POINTER(aps_fast_view), _i, _i, _i, _i, _i, C.POINTER(aps_corner_params), _i, _i64, _i64],
+    "aps_harris_planes": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i64, C.POINTER(_i64)],
     "aps_uniform_quota": [_vp, _i, _i64, _vp],
     "aps_uniform_cell": [_i, _i, _i, _i, _i, _i, C.POINTER(_i)],
     "aps_undistort_image_u8": [_vp, _i, _i, _i, _i, C.POINTER(aps_lens), _i, _i, _i, _i, _i, _vp],

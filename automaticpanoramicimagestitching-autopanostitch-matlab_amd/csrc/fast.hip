@@ -37,7 +37,14 @@
 // aps_fast_orb_extract and aps_fast_orb_extract_batch (DESIGN.md "FAST/ORB contract") are these chains with another describer (Describer):
 //   orb_keypoint_kernel   one wave per keypoint: the 31 x 31 patch of its level's plane into LDS, the intensity-centroid moments on the
 //                         way, bin, a 27 x 27 plane of 5 x 5 box sums in LDS, 64 lanes x 4 steered tests = 256 bits in 32 bytes
-// aps_fast_extract_uniform (DESIGN.md "Uniform-N selection") is that chain with fast_segment_kernel and select_uniform in the place of
+// aps_corner_extract and aps_corner_extract_batch (DESIGN.md "Harris corner contract") are these chains with another detector in
+// fast_front, whichever the describer and the selection:
+//   harris_detect_kernel  64 x 8 tile (+5 halo) into LDS, the Sobel products once per pixel, 7 x 7 sums row pass then column pass, the
+//                         64-bit response, strict 3 x 3 maximum; writes the int64 plane of candidate responses and, per wave, one
+//                         atomic maximum into the (view, level)'s Rmax
+//   harris_gate_kernel    R q_den >= Rmax q_num in 128 bits; the ballot is the bitmap word, as fast_gate_kernel's
+//   harris_aux_kernel     aux[0] = f32(R) of the described rows
+// aps_fast_extract_uniform (DESIGN.md "Uniform-N selection") is the strongest-N chain with fast_segment_kernel and select_uniform in the place of
 // select_by_key: the k_l rows of a level are spread over the cells of a grid on the level's plane.
 #include <hip/hip_runtime.h>
 
@@ -584,6 +591,166 @@ __global__ __launch_bounds__(256) void strongest_aux_kernel(const long long* __r
     if (i < n) aux[(size_t)i * 4 + 3] = (float)kresp[i];
 }
 
+// ---- Harris corners: the dense detector (DESIGN.md "Harris corner contract") ----------------------------------------------------
+constexpr int kHarrisR = kHarrisWin / 2;    // the window's reach: 3
+constexpr int kHarrisHalo = kHarrisR + 2;   // Sobel 1 + window 3 + suppression 1
+constexpr int kHarrisReach = kHarrisR + 1;  // of the response alone: the pixels whose 9 x 9 patch lies inside the plane have one
+
+// 64 x 8 tile of a level's plane, tiles and grid as fast_detect_kernel's.  Stages, each over its own region of LDS:
+//   G   (8 + 10) x (64 + 10)  the gray tile, 0 outside the plane
+//   Pa, Pb, Pc  (8 + 8) x (64 + 8)   ix^2, iy^2, ix iy of the Sobel taps, once per pixel
+//   Ha, Hb, Hc  (8 + 8) x (64 + 2)   their sums over 7 columns
+//   R   (8 + 2) x (64 + 2)    the sums over 7 rows -> A, B, C (int32: 49 * 1020^2 < 2^26) -> R = 25 (A B - C^2) - (A + B)^2, int64;
+//                             item e of the pass reads H[e + dy * 66]: consecutive lanes, consecutive banks, rows included
+//   suppression               a band pixel stays iff R > 0 and R > the eight neighbours' R
+// kDense = false: `out` is the plane of candidates (R at candidates, else 0) and every wave hands its largest candidate R to
+// rmax[view * P.n + level] (zeroed by the caller) with one atomic maximum - of integers, so the result does not depend on the order.
+// kDense = true (aps_harris_planes): `out` is R wherever the 9 x 9 patch lies inside the plane, else 0; rmax is not touched.
+// Integers only.  A band pixel's neighbours all have their patch inside the plane (margin >= kHarrisHalo), so the zeros outside
+// the plane reach no value that a band pixel is compared with.
+template <bool kDense>
+__global__ __launch_bounds__(256) void harris_detect_kernel(const uint8_t* __restrict__ planes, const FastPlan P, int margin,
+                                                            long long* __restrict__ out_all, unsigned long long* __restrict__ rmax) {
+    constexpr int kGH = kTH + 2 * kHarrisHalo, kGW = kTW + 2 * kHarrisHalo;  // 18 x 74
+    constexpr int kPH = kTH + 2 * kHarrisReach, kPW = kTW + 2 * kHarrisReach;  // 16 x 72
+    constexpr int kRH2 = kTH + 2, kRW2 = kTW + 2;                              // 10 x 66
+    __shared__ uint8_t G[kGH][kGW];
+    __shared__ int Pa[kPH * kPW], Pb[kPH * kPW], Pc[kPH * kPW];
+    __shared__ int Ha[kPH * kRW2], Hb[kPH * kRW2], Hc[kPH * kRW2];
+    __shared__ long long R[kRH2][kRW2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned int view = blockIdx.x / P.view_tiles, vtile = blockIdx.x - view * P.view_tiles;
+    const int l = level_of(P, &FastLevel::tile0, vtile);
+    const FastLevel& L = P.lv[l];
+    const unsigned int tile = vtile - L.tile0;
+    const int h = L.h, w = L.w;
+    const int x0 = (int)(tile % L.wpr) * kTW, y0 = (int)(tile / L.wpr) * kTH;
+    const uint8_t* __restrict__ gray = planes + view * P.view_plane + L.plane0;
+    long long* __restrict__ out = out_all + view * P.view_plane + L.plane0;
+    // the pixels that can hold a value: the band, or for the dense plane the pixels with a patch (both uniform in the workgroup)
+    const int edge = kDense ? kHarrisReach : margin;
+    if (y0 + kTH - 1 < edge || y0 > h - 1 - edge || x0 + kTW - 1 < edge || x0 > w - 1 - edge) {
+        for (int rr = wave; rr < kTH; rr += 4) {
+            const int y = y0 + rr, x = x0 + lane;
+            if (y >= h) break;  // (uniform in the wave)
+            if (x < w) out[(size_t)y * w + x] = 0;
+        }
+        return;
+    }
+    for (int e = tid; e < kGH * kGW; e += 256) {
+        const int r = e / kGW, cc = e % kGW, y = y0 - kHarrisHalo + r, x = x0 - kHarrisHalo + cc;
+        G[r][cc] = y >= 0 && y < h && x >= 0 && x < w ? gray[(size_t)y * w + x] : (uint8_t)0;
+    }
+    __syncthreads();
+    for (int e = tid; e < kPH * kPW; e += 256) {
+        const int r = e / kPW, cc = e % kPW;  // product (r, cc) is pixel (y0 - 4 + r, x0 - 4 + cc): G[r + 1][cc + 1]
+        const int g00 = G[r][cc], g01 = G[r][cc + 1], g02 = G[r][cc + 2];
+        const int g10 = G[r + 1][cc], g12 = G[r + 1][cc + 2];
+        const int g20 = G[r + 2][cc], g21 = G[r + 2][cc + 1], g22 = G[r + 2][cc + 2];
+        const int ix = (g02 + 2 * g12 + g22) - (g00 + 2 * g10 + g20);
+        const int iy = (g20 + 2 * g21 + g22) - (g00 + 2 * g01 + g02);
+        Pa[e] = ix * ix;
+        Pb[e] = iy * iy;
+        Pc[e] = ix * iy;
+    }
+    __syncthreads();
+    for (int e = tid; e < kPH * kRW2; e += 256) {
+        const int r = e / kRW2, cc = e % kRW2, p = r * kPW + cc;  // columns cc .. cc + 6 of the products: centred on x0 - 1 + cc
+        int a = 0, b = 0, c = 0;
+#pragma unroll
+        for (int d = 0; d < kHarrisWin; ++d) {
+            a += Pa[p + d];
+            b += Pb[p + d];
+            c += Pc[p + d];
+        }
+        Ha[e] = a;
+        Hb[e] = b;
+        Hc[e] = c;
+    }
+    __syncthreads();
+    for (int e = tid; e < kRH2 * kRW2; e += 256) {
+        int a = 0, b = 0, c = 0;  // rows r .. r + 6 of the column sums: centred on y0 - 1 + r
+#pragma unroll
+        for (int d = 0; d < kHarrisWin; ++d) {
+            a += Ha[e + d * kRW2];
+            b += Hb[e + d * kRW2];
+            c += Hc[e + d * kRW2];
+        }
+        const long long A = a, B = b, Cxy = c;
+        R[e / kRW2][e % kRW2] = 25 * (A * B - Cxy * Cxy) - (A + B) * (A + B);
+    }
+    __syncthreads();
+    long long best = 0;
+    for (int rr = wave; rr < kTH; rr += 4) {
+        const int y = y0 + rr, x = x0 + lane;
+        if (y >= h) break;  // (uniform in the wave)
+        const long long v = R[rr + 1][lane + 1];
+        bool keep = y >= edge && y <= h - 1 - edge && x >= edge && x <= w - 1 - edge;
+        if (!kDense) {
+            keep = keep && v > 0;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx)
+                    if (!(dy == 1 && dx == 1)) keep = keep && v > R[rr + dy][lane + dx];
+            if (keep && v > best) best = v;
+        }
+        if (x < w) out[(size_t)y * w + x] = keep ? v : 0;
+    }
+    if (!kDense) {
+        // every wave of every tile would queue on the one address: the atomic is issued only where the maximum as it stands is
+        // smaller (a stale reading costs a needless atomic, never a wrong result)
+        best = wave_max(best);
+        unsigned long long* top = &rmax[view * P.n + l];
+        if (lane == 0 && best > 0 && (unsigned long long)best > __hip_atomic_load(top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(top, (unsigned long long)best);
+    }
+}
+
+// a >= b for the 128-bit products a = a0 * a1, b = b0 * b1
+__device__ __forceinline__ bool product_ge(unsigned long long a0, unsigned long long a1, unsigned long long b0, unsigned long long b1) {
+    const unsigned long long ah = __umul64hi(a0, a1), al = a0 * a1, bh = __umul64hi(b0, b1), bl = b0 * b1;
+    return ah > bh || (ah == bh && al >= bl);
+}
+
+// keep iff R * q_den >= Rmax * q_num, exactly (the products pass 2^64), Rmax being that of the view's level; one wave per bitmap
+// word = row segment of 64 pixels, its ballot is the word - as fast_gate_kernel
+__global__ __launch_bounds__(256) void harris_gate_kernel(const long long* __restrict__ cand, const FastPlan P, unsigned int n_words,
+                                                          const unsigned long long* __restrict__ d_rmax, unsigned int q_num, unsigned int q_den,
+                                                          unsigned long long* __restrict__ bitmap) {
+    const int lane = threadIdx.x & 63;
+    const unsigned int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (q >= n_words) return;  // (uniform in the wave)
+    const unsigned int view = q / P.view_words, qv = q - view * P.view_words;
+    const int l = level_of(P, &FastLevel::word0, qv);
+    const FastLevel& L = P.lv[l];
+    const unsigned int ql = qv - L.word0;
+    const int y = (int)(ql / L.wpr), x = (int)(ql % L.wpr) * 64 + lane;
+    const unsigned long long top = d_rmax[view * P.n + l];
+    const long long r = x < L.w ? cand[view * P.view_plane + L.plane0 + (size_t)y * L.w + x] : 0;
+    const unsigned long long mask = __ballot(r > 0 && product_ge((unsigned long long)r, q_den, top, q_num));
+    if (lane == 0) bitmap[q] = mask;
+}
+
+// aux[0] of the described rows of a Harris chain: f32(R), round to nearest, from the candidate plane (a kept row is a candidate).
+// The view in blockIdx.y and its record, as the keypoint kernels.
+__global__ __launch_bounds__(256) void harris_aux_kernel(const long long* __restrict__ cand, const FastPlan P, const Keypoint* __restrict__ kps,
+                                                         const ViewRows<uint8_t>* __restrict__ views) {
+    const ViewRows<uint8_t> V = views[blockIdx.y];
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= V.rows || !V.aux) return;
+    const Keypoint kp = kps[V.kp0 + i];
+    int w = 1;
+    long long plane0 = 0;
+#pragma unroll
+    for (int l = 0; l < kMaxLevels; ++l)  // (constant indices: the plan stays in scalar registers)
+        if (kp.level == l) {
+            w = P.lv[l].w;
+            plane0 = P.lv[l].plane0;
+        }
+    V.aux[(size_t)i * 4] = (float)cand[blockIdx.y * P.view_plane + plane0 + (size_t)kp.y * w + kp.x];
+}
+
 // ---- ORB: intensity-centroid orientation and steered BRIEF, 256 bits (DESIGN.md "FAST/ORB contract") -------------------------
 constexpr int kOrbTests = 256, kOrbBytes = 32;
 constexpr int kOrbDiscR = 15, kOrbDisc = 709;        // the moments' disc u^2 + v^2 <= 225 and its pixels
@@ -885,11 +1052,18 @@ struct FastFront {
     Ws<uint8_t> planes, kept;
     Ws<unsigned int> smax, prefix;
     Ws<unsigned long long> bitmap;
+    // a Harris front holds the int64 plane of candidate responses and the levels' maxima in the place of kept and smax
+    Ws<long long> cand;
+    Ws<unsigned long long> rmax;
     const unsigned int* d_total() const { return prefix.get() + prefix.n - 1; }
+    // the u8 plane the describers read aux[0] from: a Harris front has no score plane, its rows' aux[0] is written after the
+    // description (harris_aux), so there the describers read a byte of the level planes, which are of the same size
+    const uint8_t* scores() const { return cand.get() ? planes.get() : kept.get(); }
 };
 
 // levels, detection, gate and scan of the group on the calling thread's stream; no read-back
-void fast_front(const aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, FastFront& F) {
+void fast_front(const aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, FastFront& F,
+                int corner = APS_CORNER_FAST) {
     const FastPlan& P = hp.dev;
     const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin, nv = P.nv;
     const size_t n_words = hp.n_words;
@@ -898,14 +1072,32 @@ void fast_front(const aps_fast_view* views, int channels, int img_layout, const 
     F.I.alloc(nv * hp.integ_elems);
     F.planes.alloc(nv * hp.plane_bytes);
     build_levels(staged.imgs, channels, img_layout, hp, F.planes, F.T, F.I);
-    F.kept.alloc(nv * hp.plane_bytes);
-    F.smax.alloc((size_t)nv * P.n);
     F.bitmap.alloc(n_words + 1);  // (+1: a zero word, whose prefix is the total)
     F.prefix.alloc(n_words + 1);
+    APS_HIP(hipMemsetAsync(F.bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
+    if (corner == APS_CORNER_HARRIS) {
+        static_assert(kFreakMargin >= kHarrisHalo, "the neighbours of a band pixel have their whole patch inside the plane");
+        APS_REQUIRE(margin >= kHarrisHalo, APS_E_INTERNAL, "margin %d", margin);
+        F.cand.alloc(nv * hp.plane_bytes);
+        F.rmax.alloc((size_t)nv * P.n);
+        {
+            Prof prof("harris_detect");
+            APS_HIP(hipMemsetAsync(F.rmax.get(), 0, (size_t)nv * P.n * sizeof(unsigned long long), stream()));
+            harris_detect_kernel<false><<<hp.n_tiles, 256, 0, stream()>>>(F.planes, P, margin, F.cand, F.rmax);
+            check_launch("harris_detect_kernel");
+            harris_gate_kernel<<<cdiv(n_words, 4), 256, 0, stream()>>>(F.cand, P, hp.n_words, F.rmax, (unsigned int)params->quality_num,
+                                                                       (unsigned int)params->quality_den, F.bitmap);
+            check_launch("harris_gate_kernel");
+        }
+        Prof prof("fast_scan");
+        exclusive_scan(popcounts(F.bitmap.get()), F.prefix.get(), 0u, n_words + 1);
+        return;
+    }
+    F.kept.alloc(nv * hp.plane_bytes);
+    F.smax.alloc((size_t)nv * P.n);
     const Ws<uint8_t>&planes = F.planes, &kept = F.kept;
     const Ws<unsigned int>&smax = F.smax, &prefix = F.prefix;
     const Ws<unsigned long long>& bitmap = F.bitmap;
-    APS_HIP(hipMemsetAsync(bitmap.get() + n_words, 0, sizeof(unsigned long long), stream()));
     {
         Prof prof("fast_detect");
         fast_detect_kernel<<<hp.n_tiles, 256, 0, stream()>>>(planes, P, params->threshold, margin, kept);
@@ -928,7 +1120,7 @@ void freak_describe(const HostPlan& hp, const FastFront& F, const Keypoint* kps,
     Ws<FreakDev> d_tb(1);
     Prof prof("freak_keypoint");  // (with the upload of the pattern tables)
     APS_HIP(hipMemcpyAsync(d_tb, &dev_pattern(), sizeof(FreakDev), hipMemcpyHostToDevice, stream()));
-    freak_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.I, hp.dev, d_tb, F.kept, kps, out.d_rows, out.desc_layout,
+    freak_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.I, hp.dev, d_tb, F.scores(), kps, out.d_rows, out.desc_layout,
                                                                             (long long)out.ldd, (long long)out.ldl);
     check_launch("freak_keypoint_kernel");
 }
@@ -940,7 +1132,7 @@ void orb_describe(const HostPlan& hp, const FastFront& F, const Keypoint* kps, G
     Ws<OrbDev> d_tb(1);
     Prof prof("orb_keypoint");  // (with the upload of the pattern tables)
     APS_HIP(hipMemcpyAsync(d_tb, &orb_tables().dev, sizeof(OrbDev), hipMemcpyHostToDevice, stream()));
-    orb_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.planes, hp.dev, d_tb, F.kept, kps, out.d_rows, out.desc_layout,
+    orb_keypoint_kernel<<<dim3(cdiv(most, 4), out.nv), 256, 0, stream()>>>(F.planes, hp.dev, d_tb, F.scores(), kps, out.d_rows, out.desc_layout,
                                                                           (long long)out.ldd, (long long)out.ldl);
     check_launch("orb_keypoint_kernel");
 }
@@ -952,10 +1144,16 @@ struct Describer {
 };
 constexpr Describer kFreak = {64, freak_describe}, kOrb = {kOrbBytes, orb_describe};
 
+// aux[0] of the rows a Harris chain has described (the describers leave a byte of the level planes there): f32(R)
+void harris_aux(const HostPlan& hp, const FastFront& F, const Keypoint* kps, GroupOut<uint8_t, aps_fast_view>& out, unsigned int most) {
+    harris_aux_kernel<<<dim3(cdiv(most, 256), out.nv), 256, 0, stream()>>>(F.cand, hp.dev, kps, out.d_rows);
+    check_launch("harris_aux_kernel");
+}
+
 // aps_fast_extract, aps_fast_extract_pyramid, aps_fast_extract_batch and the ORB entries without a selection behind their argument
 // checks (check_args, check_pyramid), on the plan's group of views.  One read-back: the views' counts.
 void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, int desc_layout,
-                int64_t ldd, int64_t ldl, const Describer& D = kFreak) {
+                int64_t ldd, int64_t ldl, const Describer& D = kFreak, int corner = APS_CORNER_FAST) {
     ctx();
     const FastPlan& P = hp.dev;
     const int H = P.lv[0].h, W = P.lv[0].w, margin = host_pattern().margin, nv = P.nv;
@@ -964,7 +1162,7 @@ void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fa
     check_views(views, nv, D.width, desc_layout, ldd, ldl, room);
     if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
     FastFront F;
-    fast_front(views, channels, img_layout, params, hp, F);
+    fast_front(views, channels, img_layout, params, hp, F, corner);
     GroupOut<uint8_t, aps_fast_view> out(views, nv, room, D.width, D.width, desc_layout, ldd, ldl, nullptr, nullptr);
     ViewLimits lim = {};
     size_t kcap = 0;
@@ -982,9 +1180,10 @@ void fast_chain(aps_fast_view* views, int channels, int img_layout, const aps_fa
             check_launch("fast_emit_kernel");
         }
         D.describe(hp, F, kps, out, *std::max_element(room, room + nv));
+        if (corner == APS_CORNER_HARRIS) harris_aux(hp, F, kps, out, *std::max_element(room, room + nv));
     }
     read_back(d_n.get(), n, nv);  // the one read-back of the chain
-    settle_counts(views, nv, n, n, params->max_features, "FAST");
+    settle_counts(views, nv, n, n, params->max_features, corner == APS_CORNER_HARRIS ? "Harris" : "FAST");
     out.commit(n);
 }
 
@@ -1046,7 +1245,7 @@ void harris_candidates(const HostPlan& hp, const FastFront& F, Candidates& Cd) {
 // behind their argument checks.  Two read-backs: the counts per level (harris_candidates), then the final count.
 void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps_fast_params* params, const HostPlan& hp, long long N,
                      int grid_rows, int grid_cols, uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count,
-                     const Describer& D = kFreak) {
+                     const Describer& D = kFreak, int corner = APS_CORNER_FAST) {
     ctx();
     *count = 0;
     const FastPlan& P = hp.dev;
@@ -1054,7 +1253,7 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     if (H < 2 * margin + 1 || W < 2 * margin + 1) return;  // no pixel is far enough from the edge: no features, no error
     aps_fast_view view = {img, desc, loc, aux, cap, 0};  // (the chain's kernels take a group: this is a group of one)
     FastFront F;
-    fast_front(&view, channels, img_layout, params, hp, F);
+    fast_front(&view, channels, img_layout, params, hp, F, corner);
     Candidates Cd;
     harris_candidates(hp, F, Cd);
     const unsigned int M = Cd.M;
@@ -1075,7 +1274,8 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     }
     *count = K;
     if (params->max_features > 0 && K > (unsigned int)params->max_features)
-        fail(APS_E_CAP, "FAST kept %u features, more than params.max_features = %d", K, params->max_features);
+        fail(APS_E_CAP, "%s kept %u features, more than params.max_features = %d", corner == APS_CORNER_HARRIS ? "Harris" : "FAST", K,
+             params->max_features);
     if ((int64_t)K > cap) fail(APS_E_CAP, "feature capacity %lld < %u features", (long long)cap, K);
     if (K == 0) return;
     APS_REQUIRE(desc && loc, APS_E_ARG, "NULL output with features present");
@@ -1116,6 +1316,7 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     const unsigned int first = 0;
     GroupOut<uint8_t, aps_fast_view> out(&view, 1, &K, D.width, D.width, desc_layout, ldd, ldl, &first, &K);
     D.describe(hp, F, kps, out, K);
+    if (corner == APS_CORNER_HARRIS) harris_aux(hp, F, kps, out, K);
     if (out.aux[0].present()) {
         strongest_aux_kernel<<<cdiv(K, 256), 256, 0, stream()>>>(kresp, K, out.aux[0]);
         check_launch("strongest_aux_kernel");
@@ -1123,6 +1324,40 @@ void strongest_chain(const uint8_t* img, int channels, int img_layout, const aps
     const unsigned int n = read_back(d_total);  // the second read-back: the count the device kept is the count the host worked out
     APS_REQUIRE(n == K, APS_E_INTERNAL, "strongest-N kept %u rows on the device, %u on the host", n, K);
     out.commit(&K);
+}
+
+// aps_fast_orb_extract and aps_corner_extract behind their NULL checks: the checks of the selection and of the FAST entries, then
+// the chain of `select` with the describer and the corner detector
+void select_entry(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_orb_params* params,
+                         const Describer& D, int corner, uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux,
+                         int64_t cap, int64_t* count) {
+    const aps_fast_pyramid_params& pyr = params->pyramid;
+    APS_REQUIRE(params->select >= 0 && params->select <= 2, APS_E_ARG, "select must be 0 (none), 1 (strongest-N) or 2 (uniform-N)");
+    if (params->select == 1) APS_REQUIRE(params->n_select >= 1, APS_E_ARG, "n_select (NumStrongest) must be at least 1");
+    if (params->select == 2) check_uniform(params->n_select, params->grid_rows, params->grid_cols);
+    if (params->select == 0) {
+        fast_single(img, desc, loc, aux, cap, count, [&](aps_fast_view* view) {
+            check_args(view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
+            check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+            fast_chain(view, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den), desc_layout,
+                       ldd, ldl, D, corner);
+        });
+        return;
+    }
+    const aps_fast_view view = {img, desc, loc, aux, cap, 0};
+    check_args(&view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
+    check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
+    const bool grid = params->select == 2;
+    strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den), params->n_select,
+                    grid ? params->grid_rows : 0, grid ? params->grid_cols : 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count, D, corner);
+}
+
+// the describer of an APS_DESC_* value (the corner entries check the range first)
+const Describer& describer_of(int descriptor) { return descriptor == APS_DESC_ORB ? kOrb : kFreak; }
+void check_corner(const aps_corner_params* params) {
+    APS_REQUIRE(params, APS_E_ARG, "NULL argument");
+    APS_REQUIRE(params->corner == APS_CORNER_FAST || params->corner == APS_CORNER_HARRIS, APS_E_ARG, "corner must be APS_CORNER_FAST or APS_CORNER_HARRIS");
+    APS_REQUIRE(params->descriptor == APS_DESC_FREAK || params->descriptor == APS_DESC_ORB, APS_E_ARG, "descriptor must be APS_DESC_FREAK or APS_DESC_ORB");
 }
 
 }  // namespace
@@ -1185,25 +1420,55 @@ int aps_fast_orb_extract(const uint8_t* img, int height, int width, int channels
                          uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
     return guarded([&] {
         APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
-        const aps_fast_pyramid_params& pyr = params->pyramid;
-        APS_REQUIRE(params->select >= 0 && params->select <= 2, APS_E_ARG, "select must be 0 (none), 1 (strongest-N) or 2 (uniform-N)");
-        if (params->select == 1) APS_REQUIRE(params->n_select >= 1, APS_E_ARG, "n_select (NumStrongest) must be at least 1");
-        if (params->select == 2) check_uniform(params->n_select, params->grid_rows, params->grid_cols);
-        if (params->select == 0) {
-            fast_single(img, desc, loc, aux, cap, count, [&](aps_fast_view* view) {
-                check_args(view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
-                check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
-                fast_chain(view, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den),
-                           desc_layout, ldd, ldl, kOrb);
-            });
-            return;
-        }
-        const aps_fast_view view = {img, desc, loc, aux, cap, 0};
-        check_args(&view, 1, height, width, channels, img_layout, pyr.fast, desc_layout);
+        select_entry(img, height, width, channels, img_layout, params, kOrb, APS_CORNER_FAST, desc, desc_layout, ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_corner_extract(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_corner_params* params,
+                       uint8_t* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(count, APS_E_ARG, "NULL argument");
+        check_corner(params);
+        select_entry(img, height, width, channels, img_layout, &params->chain, describer_of(params->descriptor), params->corner, desc, desc_layout,
+                     ldd, loc, ldl, aux, cap, count);
+    });
+}
+
+int aps_corner_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels, int img_layout,
+                             const aps_corner_params* params, int desc_layout, int64_t ldd, int64_t ldl) {
+    return guarded([&] {
+        check_corner(params);
+        APS_REQUIRE(params->chain.select == 0, APS_E_ARG, "the group form has no selection: select must be 0");
+        const aps_fast_pyramid_params& pyr = params->chain.pyramid;
+        check_args(views, n_views, height, width, channels, img_layout, pyr.fast, desc_layout);
         check_pyramid(pyr.n_levels, pyr.scale_num, pyr.scale_den);
-        const bool grid = params->select == 2;
-        strongest_chain(img, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den), params->n_select,
-                        grid ? params->grid_rows : 0, grid ? params->grid_cols : 0, desc, desc_layout, ldd, loc, ldl, aux, cap, count, kOrb);
+        fast_chain(views, channels, img_layout, &pyr.fast, make_plan(height, width, pyr.n_levels, pyr.scale_num, pyr.scale_den, n_views), desc_layout,
+                   ldd, ldl, describer_of(params->descriptor), params->corner);
+    });
+}
+
+int aps_harris_planes(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_fast_pyramid_params* params,
+                      int64_t* out, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(params && count, APS_E_ARG, "NULL argument");
+        const aps_fast_view view = {img, nullptr, nullptr, nullptr, 0, 0};
+        check_args(&view, 1, height, width, channels, img_layout, params->fast, APS_ROWMAJOR);
+        check_pyramid(params->n_levels, params->scale_num, params->scale_den);
+        const HostPlan hp = make_plan(height, width, params->n_levels, params->scale_num, params->scale_den);
+        *count = (int64_t)hp.plane_bytes;  // one response per pixel of every level
+        if (!out) return;                  // (the size alone: no device work)
+        APS_REQUIRE(cap >= *count, APS_E_CAP, "response capacity %lld < %lld pixels", (long long)cap, (long long)*count);
+        ctx();
+        StagedImgs staged(&view, 1, (size_t)height * width * channels);
+        Ws<uint32_t> T((size_t)height * width), I(hp.integ_elems);
+        Ws<uint8_t> planes(hp.plane_bytes);
+        static_assert(sizeof(long long) == sizeof(int64_t), "responses are stored as 64-bit integers");
+        Out<long long> resp(reinterpret_cast<long long*>(out), hp.plane_bytes);
+        build_levels(staged.imgs, channels, img_layout, hp, planes, T, I);
+        harris_detect_kernel<true><<<hp.n_tiles, 256, 0, stream()>>>(planes, hp.dev, 0, resp, nullptr);
+        check_launch("harris_detect_kernel");
+        resp.commit();
+        APS_HIP(hipStreamSynchronize(stream()));
     });
 }
 

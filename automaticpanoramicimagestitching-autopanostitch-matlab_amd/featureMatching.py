@@ -906,6 +906,26 @@ def _descriptor_method(input):
     return method
 
 
+def _corner_method(input):
+    """input.CornerMethod of detector = 'FAST': 'FAST' (the default when the key is absent; detectFASTFeatures) or 'Harris'
+    (detectHarrisFeatures: the dense integer Harris detector, DESIGN.md "Harris corner contract"); anything else is a ValueError,
+    raised before any library call."""
+    method = input.get("CornerMethod", "FAST")
+    if method not in ("FAST", "Harris"):
+        raise ValueError(f"input.CornerMethod must be 'FAST' or 'Harris', not {method!r}")
+    return method
+
+
+def _corner_params(input, n_levels, uniform, method):
+    """aps_corner_params of CornerMethod = 'Harris': fast_extract's keys, with detectHarrisFeatures' MinQuality default of 0.01.
+    MinContrast is not read by the detector; the threshold field carries 0."""
+    p = _capi.aps_corner_params()
+    p.chain = _fast_orb_params({**input, "MinContrast": 0.0, "MinQuality": input.get("MinQuality", 0.01)}, n_levels, uniform)
+    p.corner = _capi.APS_CORNER_HARRIS
+    p.descriptor = _capi.APS_DESC_ORB if method == "ORB" else _capi.APS_DESC_FREAK
+    return p
+
+
 def _fast_params(input):
     p = _capi.aps_fast_params()
     p.threshold = int(np.floor(float(input.get("MinContrast", 0.2)) * 255))  # detectFASTFeatures: MinContrast 0.2
@@ -970,18 +990,28 @@ def fast_extract(input, image, device_out=False, want_aux=False, points_device=F
     input.DescriptorMethod = 'ORB' (extractFeatures' Method; absent or 'FREAK': the above) describes the same rows - count, validPts,
     score, level and f32(R) are bit for bit those of the FREAK call with the same keys - with ORB's intensity-centroid orientation
     and steered BRIEF descriptor through aps_fast_orb_extract (DESIGN.md "FAST/ORB contract"): Features are n x 32 uint8 (256 bits)
-    and aux[:, 1] is the ORB bin.  Any other value is a ValueError."""
+    and aux[:, 1] is the ORB bin.  Any other value is a ValueError.
+
+    input.CornerMethod = 'Harris' (absent or 'FAST': the above, through the same entries) replaces the detector alone, through
+    aps_corner_extract (DESIGN.md "Harris corner contract"): on every level the integer Harris response at every pixel, strict 3 x 3
+    suppression, and the gate R >= MinQuality * Rmax of the level, MinQuality defaulting to detectHarrisFeatures' 0.01; MinContrast
+    is ignored.  Every other key keeps its meaning; aux is [f32(R), bin, level, f32(R) with a selection else 0].  Any other value
+    is a ValueError."""
     method = _descriptor_method(input)
+    harris = _corner_method(input) == "Harris"
     img, h, w, c = _image_hwc(image)
     n_levels = int(input.get("NumLevels", 1))
     uniform = _uniform_keys(input)
-    if method == "ORB":
-        prm = _fast_orb_params(input, n_levels, uniform)
-        cap = max(4096, _fast_plan_pixels(h, w, prm.pyramid) // 64)
-        if prm.select:  # (as _pick_entry: a resident result holds N rows)
-            cap = min(cap, max(prm.n_select, 1))
-        d, pts, aux = _extract_regrow(1, cap, _one_view_call(lib.aps_fast_orb_extract, prm, img, h, w, c, ORB_BYTES),
-                                      _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), ORB_BYTES, np.uint8,
+    if method == "ORB" or harris:
+        nbytes = ORB_BYTES if method == "ORB" else FREAK_BYTES
+        prm = _corner_params(input, n_levels, uniform, method) if harris else _fast_orb_params(input, n_levels, uniform)
+        chain = prm.chain if harris else prm
+        cap = max(4096, _fast_plan_pixels(h, w, chain.pyramid) // 64)
+        if chain.select:  # (as _pick_entry: a resident result holds N rows)
+            cap = min(cap, max(chain.n_select, 1))
+        entry = lib.aps_corner_extract if harris else lib.aps_fast_orb_extract
+        d, pts, aux = _extract_regrow(1, cap, _one_view_call(entry, prm, img, h, w, c, nbytes),
+                                      _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), nbytes, np.uint8,
                                       device_out, points_device, compact, want_aux)[0]
         f = binaryFeatures(d)
         return (f, pts, aux) if want_aux else (f, pts)
@@ -1009,14 +1039,18 @@ def fast_extract_batch(input, images, device_out=False, want_aux=False, points_d
     input.NumStrongest and input.NumUniform have no group form - a FAST selection group is a level, and a group of views would need
     views x levels of them: with either key this is a ValueError; call fast_extract per view.
 
-    input.DescriptorMethod = 'ORB' goes through aps_fast_orb_extract_batch: rows of 32 bytes, as fast_extract's."""
+    input.DescriptorMethod = 'ORB' goes through aps_fast_orb_extract_batch: rows of 32 bytes, as fast_extract's.
+    input.CornerMethod = 'Harris' goes through aps_corner_extract_batch, with either descriptor."""
     if "NumStrongest" in input or "NumUniform" in input:
         raise ValueError("fast_extract_batch takes no input.NumStrongest / input.NumUniform: call fast_extract per view")
-    entry, nbytes = ((lib.aps_fast_orb_extract_batch, ORB_BYTES) if _descriptor_method(input) == "ORB"
-                     else (lib.aps_fast_extract_batch, FREAK_BYTES))
+    method = _descriptor_method(input)
+    harris = _corner_method(input) == "Harris"
+    entry, nbytes = ((lib.aps_fast_orb_extract_batch, ORB_BYTES) if method == "ORB" else (lib.aps_fast_extract_batch, FREAK_BYTES))
     imgs, h, w, c = _group_images(images)
     prm = _fast_pyramid_params(input, int(input.get("NumLevels", 1)))
     cap = max(4096, _fast_plan_pixels(h, w, prm) // 64)  # (no selection key: nothing for _pick_entry to pick)
+    if harris:
+        entry, prm = lib.aps_corner_extract_batch, _corner_params(input, prm.n_levels, None, method)
     out = _extract_regrow(len(imgs), cap, _group_call(_capi.aps_fast_view, entry, prm, imgs, h, w, c, nbytes),
                           _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), nbytes, np.uint8, device_out,
                           points_device, compact, want_aux)

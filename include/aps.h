@@ -1077,6 +1077,39 @@ int aps_fast_orb_extract_batch(aps_fast_view* views, int n_views, int height, in
  *   reach                  largest |d| of `table` + 2 (the box) + 1 = 16, at most aps_freak_pattern's margin */
 int aps_orb_pattern(int32_t* tests, int32_t* table, int32_t* disc, int* reach);
 
+/* Corner detector x descriptor (DESIGN.md "Harris corner contract"): one entry states the whole family of the FAST chains.
+ * corner = APS_CORNER_FAST gives, byte for byte, the existing entry for the same descriptor and selection (aps_fast_extract_pyramid,
+ * aps_fast_extract_strongest, aps_fast_extract_uniform, aps_fast_orb_extract; the group form aps_fast_extract_batch,
+ * aps_fast_orb_extract_batch).  corner = APS_CORNER_HARRIS replaces the detector alone: on every level plane of the same plan the
+ * integer Harris response R = 25 (A B - C^2) - (A + B)^2 of aps_fast_harris (Sobel 3 x 3, 7 x 7 window, k = 0.04) at every pixel;
+ * a pixel at least aps_freak_pattern's margin from every edge is a candidate iff R > 0 and R exceeds the R of its eight neighbours;
+ * a candidate stays iff R * quality_den >= Rmax * quality_num, exactly, Rmax the largest candidate R of the (view, level).
+ * chain.pyramid.fast.threshold is checked as ever and not read.  Order, locations, description, selections (strength R), capacity
+ * protocol, count-only mode, layouts, padding, host and device pointers, max_features and APS_E_CAP with nothing written are those
+ * of the FAST entries.
+ *   aux : [f32(R), orientation bin, level, f32(R) with a selection else 0]
+ * APS_E_ARG before any device work: corner or descriptor out of range, the group form with chain.select != 0, and whatever the
+ * existing entries refuse. */
+enum { APS_CORNER_FAST = 0, APS_CORNER_HARRIS = 1 };
+enum { APS_DESC_FREAK = 0, APS_DESC_ORB = 1 };
+typedef struct aps_corner_params {
+    aps_fast_orb_params chain;   /* pyramid, select, n_select, grid */
+    int corner;                  /* APS_CORNER_* */
+    int descriptor;              /* APS_DESC_* */
+} aps_corner_params;
+int aps_corner_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                       const aps_corner_params* params, uint8_t* desc, int desc_layout, int64_t ldd,
+                       double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+int aps_corner_extract_batch(aps_fast_view* views, int n_views, int height, int width, int channels,
+                             int img_layout, const aps_corner_params* params,
+                             int desc_layout, int64_t ldd, int64_t ldl);
+
+/* Test hook: the dense response R of every level plane of aps_fast_extract_pyramid's plan, before suppression and gate, packed like
+ * aps_fast_pyramid_planes (one int64 per pixel, host or device); 0 at pixels closer than 4 to an edge, where the 9 x 9 patch leaves
+ * the plane.  out = NULL: *count = the pixels of all levels, no device work; cap < *count is APS_E_CAP. */
+int aps_harris_planes(const uint8_t* img, int height, int width, int channels, int img_layout,
+                      const aps_fast_pyramid_params* params, int64_t* out, int64_t cap, int64_t* count);
+
 /* ============================================================================================
  * (4d) Uniform-N selection for SIFT, SURF and FAST — selectUniform next to selectStrongest
  * ============================================================================================ */

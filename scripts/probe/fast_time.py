@@ -5,8 +5,11 @@ noise of the figure.  The groups of the rows alternate, so drift of the device s
 With --orb every row is timed a second time with DescriptorMethod = 'ORB' (orb_keypoint_kernel beside freak_keypoint_kernel), and
 with --match the batched pairwise Hamming matcher is timed on the rows of two such views at 64 bytes (FREAK) and at 32 (ORB): the
 same keypoints, host clock around calls that end in a synchronise, alternating groups again.
+With --corner harris every row is timed once more with CornerMethod = 'Harris' (launch site harris_detect: harris_detect_kernel and
+harris_gate_kernel, beside fast_detect: fast_detect_kernel, fast_smax_kernel and fast_gate_kernel).
 
     python scripts/probe/fast_time.py [--levels 1 8] [--scale 1.2] [--reps 5] [--repeats 5] [--strongest 5000] [--orb] [--match]
+                                      [--corner harris]
 """
 import argparse
 import statistics
@@ -25,6 +28,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--strongest", type=int, default=None, help="also time every NumLevels with NumStrongest = N")
 ap.add_argument("--orb", action="store_true", help="also time every row with DescriptorMethod = 'ORB'")
 ap.add_argument("--match", action="store_true", help="time batched pairwise matching of two views' rows at 64 and 32 bytes")
+ap.add_argument("--corner", choices=["harris"], default=None, help="also time every row with CornerMethod = 'Harris'")
 args = ap.parse_args()
 
 fm = import_module(apsamd.__name__ + ".featureMatching")
@@ -38,13 +42,16 @@ import torch  # noqa: E402
 torch.cuda.synchronize()
 rows = [(nl, None) for nl in args.levels] + ([(nl, args.strongest) for nl in args.levels] if args.strongest is not None else [])
 rows = [row + (m,) for row in rows for m in (("FREAK", "ORB") if args.orb else ("FREAK",))]
+rows = [row + (c,) for row in rows for c in (("FAST", "Harris") if args.corner else ("FAST",))]
 
 
-def inputs(nl, strongest, method="FREAK"):
+def inputs(nl, strongest, method="FREAK", corner="FAST"):
     # (the synthetic world is smooth: the default MinContrast 0.2 finds next to nothing)
     inp = {"detector": "FAST", "MinContrast": 0.08, "NumLevels": nl, "ScaleFactor": args.scale}
     if method != "FREAK":
         inp["DescriptorMethod"] = method
+    if corner != "FAST":
+        inp["CornerMethod"] = corner
     return inp if strongest is None else {**inp, "NumStrongest": strongest}
 
 
@@ -64,11 +71,11 @@ for _ in range(args.repeats):
         groups[row].append(sum(v[0] for v in last[row].values()) / args.reps)
 totals = {}
 for row in rows:
-    nl, strongest, method = row
+    nl, strongest, method, corner = row
     g = groups[row]
     totals[row] = statistics.median(g)
     name = f"NumLevels={nl}" + ("" if strongest is None else f" NumStrongest={strongest}")
-    print(f"FAST/{method} {name}: {found[row]} features, {totals[row]:.3f} ms in profiled kernels per view, range {min(g):.3f} .. {max(g):.3f} "
+    print(f"{corner}/{method} {name}: {found[row]} features, {totals[row]:.3f} ms in profiled kernels per view, range {min(g):.3f} .. {max(g):.3f} "
           f"(groups of {args.reps}: {' '.join('%.3f' % v for v in g)})")
     for k, (ms, n) in sorted(last[row].items()):  # (the last group)
         print(f"  {k:20s} {ms / args.reps:8.3f} ms  ({n // args.reps} launches)")
