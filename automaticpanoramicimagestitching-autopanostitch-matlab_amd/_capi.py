@@ -24,7 +24,7 @@ APS_WARP_NEAREST, APS_WARP_BILINEAR, APS_WARP_BICUBIC = 0, 1, 2
 APS_TFORM_PROJECTIVE, APS_TFORM_AFFINE, APS_TFORM_SIMILARITY, APS_TFORM_RIGID, APS_TFORM_TRANSLATION = 0, 1, 2, 3, 4
 APS_PROJ_CYLINDRICAL, APS_PROJ_SPHERICAL, APS_PROJ_PLANAR, APS_PROJ_STEREOGRAPHIC = 0, 1, 2, 3
 APS_PROJ_MILLER, APS_PROJ_FISHEYE, APS_PROJ_PANINI = 4, 5, 6
-APS_BLEND_NONE, APS_BLEND_LINEAR, APS_BLEND_MULTIBAND = 0, 1, 2
+APS_BLEND_NONE, APS_BLEND_LINEAR, APS_BLEND_MULTIBAND, APS_BLEND_MULTIBAND_MAXWEIGHT = 0, 1, 2, 3
 APS_NONE_LAST, APS_NONE_FIRST, APS_NONE_MAXANGLE = 0, 1, 2
 APS_IMG_U8_HWC, APS_IMG_U8_MATLAB = 0, 1
 
@@ -245,6 +245,7 @@ _SIGNATURES = {
     "aps_ba_normal_eqns": [_vp, _vp, _vp, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp],
     "aps_ba_h_normal_eqns": [_vp, _vp, _i, _i, _d, _i, _vp, _vp, _vp],
     "aps_multiband_blend": [_vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "aps_maxweight_weights": [_vp, _i, _i, _i, _vp],
     "aps_linear_blend": [_vp, _vp, _i, _i, _i, _vp],
     "aps_image_warp_h_u8": [_vp, _i, _i, _i, _vp, _i, _i, _d, _d, _d, _d, C.c_uint8, _vp],
     "aps_image_warp_h_f32": [_vp, _i, _i, _i, _vp, _i, _i, _d, _d, _d, _d, _f, _vp],

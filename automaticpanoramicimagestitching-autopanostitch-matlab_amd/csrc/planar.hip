@@ -312,6 +312,31 @@ __global__ __launch_bounds__(256) void planar_norm_kernel(Set set, uint8_t* __re
     cov[(size_t)y * set.W + x] = any ? 1 : 0;
 }
 
+// APS_BLEND_MULTIBAND_MAXWEIGHT: the max-weight partition in planar_norm_kernel's place ("Max-weight multiband
+// contract"): weight 1 for the first layer of maximal raw weight (> 0; `w > best` as planar_fuse_kernel<APS_BLEND_NONE>, so a
+// NaN never owns), 0 for the others; coverage as planar_norm_kernel.
+template <class Set>
+__global__ __launch_bounds__(256) void planar_maxweight_kernel(Set set, uint8_t* __restrict__ cov) {
+    int x, y;
+    if (!set.thread_pixel(x, y)) return;
+    const auto at = set.at(x, y);
+    float best = 0.f;
+    int owner = -1;
+    for (int i = 0; i < at.n; ++i) {
+        if (!in_rect(at.rect(i), x, y)) continue;
+        const float wv = at.pixel(i)->w;
+        if (wv > best) {
+            best = wv;
+            owner = i;
+        }
+    }
+    for (int i = 0; i < at.n; ++i) {
+        if (!in_rect(at.rect(i), x, y)) continue;
+        at.pixel(i)->w = i == owner ? 1.0f : 0.0f;
+    }
+    cov[(size_t)y * set.W + x] = owner >= 0 ? 1 : 0;
+}
+
 // uint8(round(255 * f)) as the host tail forms it: the product in f64, MATLAB round (half away from zero), clamp.
 // (paint_kernel of the tiled renderer rounds 255.0f * v in f32, which can land on the other side of a half.)
 __device__ __forceinline__ uint8_t planar_u8(float f) {
@@ -467,18 +492,22 @@ static void planar_check_shapes(const PlanarArgs& a, int max_images, bool need_i
     }
 }
 
-// need_sigma = false: the byte formulas, which know no sigma
-static void planar_check_blending(int blending, int levels, float sigma, bool need_sigma) {
-    APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND, APS_E_ARG,
-                "unknown blending mode %d", blending);
+// need_sigma = false: the byte formulas, which know no sigma.  Returns the mode the plans and byte formulas see:
+// APS_BLEND_MULTIBAND_MAXWEIGHT differs from APS_BLEND_MULTIBAND in one kernel of planar_composite_impl only.
+static int planar_check_blending(int blending, int levels, float sigma, bool need_sigma) {
+    APS_REQUIRE(blending == APS_BLEND_NONE || blending == APS_BLEND_LINEAR || blending == APS_BLEND_MULTIBAND ||
+                    blending == APS_BLEND_MULTIBAND_MAXWEIGHT,
+                APS_E_ARG, "unknown blending mode %d", blending);
+    if (blending == APS_BLEND_MULTIBAND_MAXWEIGHT) blending = APS_BLEND_MULTIBAND;
     if (blending == APS_BLEND_MULTIBAND) {
         APS_REQUIRE(levels >= 1, APS_E_ARG, "levels must be a positive integer");
-        if (!need_sigma) return;
+        if (!need_sigma) return blending;
         APS_REQUIRE(sigma > 0, APS_E_ARG, "sigma must be positive");
         const Taps tp = make_taps(sigma);
         APS_REQUIRE(tp.r >= 1 && tp.r <= 4, APS_E_ARG, "pyrSigma %g needs a %d-tap filter; 3..9 taps are built", (double)sigma,
                     2 * tp.r + 1);
     }
+    return blending;
 }
 
 // Refuses before the first launch when the request cannot fit (renderPanorama.m:245-266: "skip this panorama").
@@ -839,7 +868,8 @@ static void planar_composite_impl(const PlanarArgs& a, int blending, int levels,
                                   uint8_t* pano, uint8_t* covered) {
     planar_check_shapes(a, Compositor::kMaxImages);
     APS_REQUIRE(pano, APS_E_ARG, "NULL argument");
-    planar_check_blending(blending, levels, sigma, true);
+    const bool maxweight = blending == APS_BLEND_MULTIBAND_MAXWEIGHT;
+    blending = planar_check_blending(blending, levels, sigma, true);
     ctx();
     Compositor c{a};
     c.plan(blending, levels, sigma, 0);
@@ -853,7 +883,10 @@ static void planar_composite_impl(const PlanarArgs& a, int blending, int levels,
     if (blending == APS_BLEND_MULTIBAND) {
         Ws<uint8_t> cov(P);
         Ws<float4> F(P);
-        planar_norm_kernel<<<grid, 256, 0, stream()>>>(set, cov.get());
+        if (maxweight)
+            planar_maxweight_kernel<<<grid, 256, 0, stream()>>>(set, cov.get());
+        else
+            planar_norm_kernel<<<grid, 256, 0, stream()>>>(set, cov.get());
         check_launch(Compositor::kNorm);
         c.multiband(levels, sigma, F);
         planar_finish_kernel<<<cdiv(P, 256), 256, 0, stream()>>>(F, cov, P, white, oP.get(), cov_out);
@@ -909,7 +942,7 @@ int64_t aps_planar_composite_bytes(int n_img, const int* img_h, const int* img_w
     const int st = guarded([&] {
         const PlanarArgs a{nullptr, img_h, img_w, img_c, n_img, nullptr, out_h, out_w, 0, 0, 1, 1};
         planar_check_shapes(a, kPlanarMaxImages, false, false);
-        planar_check_blending(blending, levels, 0.f, false);
+        blending = planar_check_blending(blending, levels, 0.f, false);
         bytes = planar_bytes(a, blending, levels);
     });
     return st == APS_OK ? bytes : (int64_t)st;
@@ -963,7 +996,7 @@ int64_t aps_planar_composite_compact_bytes(int n_img, const int* img_h, const in
     const int st = guarded([&] {
         const PlanarArgs a{nullptr, img_h, img_w, img_c, n_img, H, out_h, out_w, x0, y0, sx, sy};
         planar_check_shapes(a, kCompactMaxImages, false);
-        planar_check_blending(blending, levels, 0.f, false);
+        blending = planar_check_blending(blending, levels, 0.f, false);
         CompactPlan pl;
         compact_plan(a, blending == APS_BLEND_MULTIBAND ? levels : 1, kCompactRadius, false, pl);
         bytes = compact_bytes(pl, a, blending);

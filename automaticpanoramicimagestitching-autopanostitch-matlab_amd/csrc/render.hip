@@ -239,6 +239,47 @@ __global__ void norm_weights_kernel(Tab layers_tab, RectTab rects, int use_rects
     if (cov) cov[p] = any ? 1 : 0;
 }
 
+// The max-weight partition in place of both normalisations ("Max-weight multiband contract"): the first layer of
+// maximal raw weight (> 0; `w > best`, so a NaN never owns) gets weight 1, every other layer 0; coverage = some weight > 0.
+// Layers are walked in order and tested against their footprint one at a time, so K is not capped.
+template <class Tab>
+__global__ void maxweight_weights_kernel(Tab layers_tab, RectTab rects, int use_rects, int K, int w, size_t n,
+                                         uint8_t* __restrict__ cov) {
+    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
+    float best = 0.f;
+    int owner = -1;
+    for (int k = 0; k < K; ++k) {
+        if (use_rects && !in_rect(rects.r[k], x, y)) continue;
+        const float wv = tab_get<Tab>(layers_tab, k)[p].w;
+        if (wv > best) {
+            best = wv;
+            owner = k;
+        }
+    }
+    for (int k = 0; k < K; ++k)
+        if (!use_rects || in_rect(rects.r[k], x, y)) tab_get<Tab>(layers_tab, k)[p].w = k == owner ? 1.0f : 0.0f;
+    if (cov) cov[p] = owner >= 0 ? 1 : 0;
+}
+
+// aps_maxweight_weights: the same partition on K plain weight planes, one lane per pixel, layers in order.  A lane reads all K
+// weights of its pixel before it writes any, so `out` may be Wt itself.
+__global__ void maxweight_planes_kernel(const float* Wt, int K, size_t hw, float* out) {
+    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (p >= hw) return;
+    float best = 0.f;
+    int owner = -1;
+    for (int k = 0; k < K; ++k) {
+        const float wv = Wt[(size_t)k * hw + p];
+        if (wv > best) {
+            best = wv;
+            owner = k;
+        }
+    }
+    for (int k = 0; k < K; ++k) out[(size_t)k * hw + p] = k == owner ? 1.0f : 0.0f;
+}
+
 // dim 0 (rows): in h x w -> out oh x w
 __global__ void resize_rows_kernel(const float4* __restrict__ in, int h, int w, int oh,
                                    float4* __restrict__ out) {
@@ -712,6 +753,23 @@ static void normalize_weights(const std::vector<float4*>& layers, const Rect* re
     }
 }
 
+// The max-weight partition over K layers (maxweight_weights_kernel), coverage optional; rects as normalize_weights takes them.
+static void maxweight_weights(const std::vector<float4*>& layers, const Rect* rects, int h, int w, uint8_t* cov) {
+    const int K = (int)layers.size();
+    const size_t n = (size_t)h * w;
+    if (K <= kMaxK) {
+        maxweight_weights_kernel<PtrTab><<<cdiv(n, 256), 256, 0, stream()>>>(
+            make_tab(layers.data(), K), make_rtab(rects, rects ? K : 0), rects ? 1 : 0, K, w, n, cov);
+        check_launch("maxweight_weights_kernel");
+    } else {
+        Ws<float4*> dl(K);
+        APS_HIP(hipMemcpyAsync(dl, layers.data(), K * sizeof(float4*), hipMemcpyHostToDevice, stream()));
+        maxweight_weights_kernel<float4* const*><<<cdiv(n, 256), 256, 0, stream()>>>(dl.get(), RectTab{}, 0, K, w, n, cov);
+        check_launch("maxweight_weights_kernel");
+        APS_HIP(hipStreamSynchronize(stream()));
+    }
+}
+
 // multiBandBlending on K float4 layers whose weights are ALREADY normalised (normalize_weights(..., mbb=1));
 // result float4 in F (unclamped).  Level-major: per level one launch blurs up to 16 layers, one launch
 // downsamples them, one pass forms their Laplacians and accumulates them in layer order.  No host sync.
@@ -1113,8 +1171,11 @@ static void render_tiles_per_tile(const DevCanvas& cv, const DevImage* dimgs, in
                         APS_HIP(hipStreamSynchronize(stream()));
                     }
                 } else {
-                    // fuseTile's normalisation (:991-1006) and multiBandBlending's own (:72-85), one pass
-                    normalize_weights(layers, culled ? rects.data() : nullptr, ht, wt, 1, 1, cov);
+                    // fuseTile's normalisation (:991-1006) and multiBandBlending's own (:72-85), one pass; or the partition
+                    if (o.blending == APS_BLEND_MULTIBAND_MAXWEIGHT)
+                        maxweight_weights(layers, culled ? rects.data() : nullptr, ht, wt, cov);
+                    else
+                        normalize_weights(layers, culled ? rects.data() : nullptr, ht, wt, 1, 1, cov);
                     multiband_device(layers, culled ? rects.data() : nullptr, ht, wt, o.pyr_levels, o.pyr_sigma, F);
                 }
             }
@@ -1183,6 +1244,21 @@ int aps_multiband_blend(const float* C, const float* Wt, int k, int h, int w, in
     });
 }
 
+int aps_maxweight_weights(const float* Wt, int k, int h, int w, float* out) {
+    return guarded([&] {
+        APS_REQUIRE(Wt && out, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(k >= 1 && h >= 1 && w >= 1, APS_E_ARG, "need k >= 1 non-empty weight planes");
+        ctx();
+        const size_t hw = (size_t)h * w;
+        In<float> dW(Wt, hw * k);
+        Out<float> oW(out, hw * k);
+        maxweight_planes_kernel<<<cdiv(hw, 256), 256, 0, stream()>>>(dW.get(), k, hw, oW.get());
+        check_launch("maxweight_planes_kernel");
+        oW.commit();
+        APS_HIP(hipStreamSynchronize(stream()));
+    });
+}
+
 int aps_linear_blend(const float* C, const float* Wt, int k, int h, int w, float* F) {
     return guarded([&] {
         APS_REQUIRE(C && Wt && F, APS_E_ARG, "NULL argument");
@@ -1223,9 +1299,10 @@ static int render_tiles_impl(const aps_image* images, int n_img, const aps_canva
         APS_REQUIRE(n_img >= 1, APS_E_ARG, "need at least one image");
         APS_REQUIRE(opts->tile_h > 0 && opts->tile_w > 0, APS_E_ARG,
                     "opts.tile must be given explicitly (never derived from free memory)");
-        APS_REQUIRE(opts->blending >= APS_BLEND_NONE && opts->blending <= APS_BLEND_MULTIBAND, APS_E_ARG, "unknown blending");
+        APS_REQUIRE(opts->blending >= APS_BLEND_NONE && opts->blending <= APS_BLEND_MULTIBAND_MAXWEIGHT, APS_E_ARG, "unknown blending");
+        const bool multiband = opts->blending == APS_BLEND_MULTIBAND || opts->blending == APS_BLEND_MULTIBAND_MAXWEIGHT;
         APS_REQUIRE(out_layout == APS_IMG_U8_HWC || out_layout == APS_IMG_U8_MATLAB, APS_E_TYPE, "unknown output layout");
-        if (opts->blending == APS_BLEND_MULTIBAND) {
+        if (multiband) {
             APS_REQUIRE(opts->pyr_levels >= 1, APS_E_ARG, "pyrLevels must be >= 1");
             APS_REQUIRE(opts->pyr_sigma > 0, APS_E_ARG, "pyrSigma must be positive");
         }
@@ -1257,7 +1334,7 @@ static int render_tiles_impl(const aps_image* images, int n_img, const aps_canva
         // launch.  APS_RENDER_LEGACY=1, or a configuration the batched kernels are not built for, takes the per-tile path, whose
         // bytes they reproduce.
         uint8_t* const d_cov = oC.present() ? oC.get() : nullptr;
-        const auto batched = opts->blending == APS_BLEND_MULTIBAND ? render_multiband_batched : render_fuse_batched;
+        const auto batched = multiband ? render_multiband_batched : render_fuse_batched;
         if (std::getenv("APS_RENDER_LEGACY") || !batched(P.dev, P.host.data(), n_img, cv, *opts, tiles, out_layout, oP, d_cov, convert)) {
             convert_images(P, nullptr);  // the per-tile path samples whatever its cover pass finds
             render_tiles_per_tile(cv, P.dev, n_img, *opts, tiles, out_layout, oP, d_cov);

@@ -665,7 +665,9 @@ constexpr int kWL = 6;  // layers of a block whose samples are parked in LDS; fu
 // pyramids, collapse) byte for byte against render.hip's per-tile kernels.
 // The walking form of a block: ray once per pixel, then the tile's layers that meet the block one after the other
 // (sample -> first sum, second sum, store).  ct / rt: the pixel's column / row trig entries.
-template <bool FAST, bool NEW>
+// MW (APS_BLEND_MULTIBAND_MAXWEIGHT; DESIGN.md, "Max-weight multiband contract"): pass A tracks the first layer of maximal raw
+// weight (> 0) in place of the first sum, pass B is not run, pass C stores 1 for that layer and 0 for the others.
+template <bool FAST, bool NEW, bool MW = false>
 __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T, int x0, int y0, float* s_u8, float4 (*s_g)[256],
                                                 const ColTrig& ct, const RowTrig& rt) {
     const int tid = threadIdx.x;
@@ -701,32 +703,44 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
     float ssum = 0.f;
     bool any = false;
     int kc = 0;  // layers met so far (block-uniform)
+    float best = 0.f;  // (MW) the largest raw weight so far and the layer that brought it
+    int owner = -1;
     for_block_layers(ls, A, T, 0, x0, y0, bx1, by1, [&](int k) {
         const RwEntry& E = A.entries[T.e0 + k];
         const Rect g = E.g[0];
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (in_tile && in_rect(g, x, y)) v = sample(A.imgs[E.img]);
-        ssum = ssum + v.w;
-        any |= v.w > 0.f;
+        if (MW) {
+            if (v.w > best) {
+                best = v.w;
+                owner = kc;
+            }
+        } else {
+            ssum = ssum + v.w;
+            any |= v.w > 0.f;
+        }
         if (kc < kWL) s_g[kc][tid] = v;
         ++kc;
     });
+    if (MW) any = owner >= 0;
     const float inv = ssum > 1e-8f ? (FAST ? fast_rcp(ssum) : 1.0f / ssum) : 0.f;
     // pass B: the second sum over the rescaled weights
     float s2 = 0.f;
     kc = 0;
-    for_block_layers(ls, A, T, 0, x0, y0, bx1, by1, [&](int k) {
-        float wv;
-        if (kc < kWL) {
-            wv = s_g[kc][tid].w;
-        } else {
-            const RwEntry& E = A.entries[T.e0 + k];
-            wv = (in_tile && in_rect(E.g[0], x, y)) ? sample(A.imgs[E.img]).w : 0.f;
-        }
-        const float w1 = wv * inv;
-        s2 = s2 + (w1 > 0.f ? w1 : 0.f);
-        ++kc;
-    });
+    if (!MW) {
+        for_block_layers(ls, A, T, 0, x0, y0, bx1, by1, [&](int k) {
+            float wv;
+            if (kc < kWL) {
+                wv = s_g[kc][tid].w;
+            } else {
+                const RwEntry& E = A.entries[T.e0 + k];
+                wv = (in_tile && in_rect(E.g[0], x, y)) ? sample(A.imgs[E.img]).w : 0.f;
+            }
+            const float w1 = wv * inv;
+            s2 = s2 + (w1 > 0.f ? w1 : 0.f);
+            ++kc;
+        });
+    }
     const float2 nrm = make_float2(inv, s2);
     const float inv2 = s2 > 1e-8f ? fast_rcp(s2) : 0.f;  // (FAST only)
     // pass C: store with the final weight
@@ -736,7 +750,9 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
         const Rect g = E.g[0];
         if (in_tile && in_rect(g, x, y)) {
             float4 v = kc < kWL ? s_g[kc][tid] : sample(A.imgs[E.img]);
-            if (FAST) {
+            if (MW) {
+                v.w = kc == owner ? 1.0f : 0.0f;
+            } else if (FAST) {
                 const float w1 = v.w * inv;
                 v.w = (w1 > 0.f ? w1 : 0.f) * inv2;
             } else {
@@ -751,7 +767,7 @@ __device__ __forceinline__ void warp_block_walk(const RwArgs& A, const RwTile& T
 
 // The exact form (APS_WARP_EXACT=1): the walking form on the canvas-wide trig tables (A.ct, A.rt).
 // NEW: the mode family (canvas_ray in render_dev.h); NEW = false serves the reference's four modes with the code they always had.
-template <bool NEW>
+template <bool NEW, bool MW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_kernel(RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
     __shared__ float s_u8[256];
     __shared__ float4 s_g[kWL][256];
@@ -767,7 +783,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     __syncthreads();
     const ColTrig ct = A.ct[T.c0 + min(x0 + (tid & (kUW - 1)), w - 1)];
     const RowTrig rt = A.rt[T.r0 + min(y0 + tid / kUW, h - 1)];
-    warp_block_walk<false, NEW>(A, T, x0, y0, s_u8, s_g, ct, rt);
+    warp_block_walk<false, NEW, MW>(A, T, x0, y0, s_u8, s_g, ct, rt);
 }
 
 // ---- the warp in its staged form (default) ----------------------------------------------------------------------------
@@ -817,7 +833,8 @@ __device__ __forceinline__ bool project_lc(const float R[9], float fx, float fy,
     return inside && front && cam[2] > 0.0f;
 }
 
-template <bool NEW>
+// MW: as in warp_block_walk - (best, owner) in pass A, no pass B, 1 or 0 in pass C; the weights are not parked.
+template <bool NEW, bool MW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void rw_warp_staged_kernel(
     RwArgs A, const int* __restrict__ blk_ptr, int n_blocks) {
     __shared__ LayerConst s_lc[kWF];
@@ -869,7 +886,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (staged)
         for (int j = 0; j < nvis; ++j) small_image |= f2i(s_lc[j].q[4].w) == 0;
     if (!staged || small_image) {
-        warp_block_walk<true, NEW>(A, T, x0, y0, nullptr, s_g, ct, rt);
+        warp_block_walk<true, NEW, MW>(A, T, x0, y0, nullptr, s_g, ct, rt);
         return;
     }
     const int x = x0 + (tid & (kUW - 1)), y = y0 + tid / kUW;
@@ -884,6 +901,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     float* s_w = s_v + kWF * 256;
     static_assert(3 * kWF * 256 * sizeof(float) <= sizeof(float4) * kWL * 256, "parking area");
     float ssum = 0.f;
+    float best = 0.f;  // (MW) the largest raw weight so far and the staged layer that brought it
+    int owner = -1;
     unsigned okm = 0u;  // bit j: layer j covers the pixel (its colour is stored even where its weight is zero)
     for (int j = 0; j < nvis; ++j) {
         const float4 q5 = s_lc[j].q[5];
@@ -925,13 +944,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         }
         s_u[j * 256 + tid] = uo;
         s_v[j * 256 + tid] = vo;
-        s_w[j * 256 + tid] = wo;
-        ssum = ssum + wo;
+        if (MW) {
+            if (wo > best) {
+                best = wo;
+                owner = j;
+            }
+        } else {
+            s_w[j * 256 + tid] = wo;
+            ssum = ssum + wo;
+        }
     }
     const float inv = ssum > 1e-8f ? fast_rcp(ssum) : 0.f;
     float s2 = 0.f;
-    bool any = false;
-    for (int j = 0; j < nvis; ++j) {
+    bool any = MW && owner >= 0;
+    for (int j = 0; !MW && j < nvis; ++j) {
         const float wv = s_w[j * 256 + tid];
         const float w1 = wv * inv;
         s2 = s2 + (w1 > 0.f ? w1 : 0.f);
@@ -963,8 +989,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
                     const float b01 = (float)((p01 >> (8 * c)) & 255u), b11 = (float)((p11 >> (8 * c)) & 255u);
                     c3[c] = lerp1(lerp1(b00, b10, s), lerp1(b01, b11, s), tt) * g3[c];
                 }
-                const float w1 = s_w[j * 256 + tid] * inv;
-                o = make_float4(c3[0], c3[1], c3[2], (w1 > 0.f ? w1 : 0.f) * inv2);
+                if (MW) {
+                    o = make_float4(c3[0], c3[1], c3[2], j == owner ? 1.0f : 0.0f);
+                } else {
+                    const float w1 = s_w[j * 256 + tid] * inv;
+                    o = make_float4(c3[0], c3[1], c3[2], (w1 > 0.f ? w1 : 0.f) * inv2);
+                }
             }
             const long long off = (long long)(((unsigned long long)(unsigned)f2i(q7.w) << 32) | (unsigned)f2i(q7.z));
             A.G[off + ((y - gy0) * (gx1 - gx0) + (x - gx0))] = o;  // (a footprint store is < 2^31 bytes: host check)
@@ -2025,11 +2055,15 @@ BlockTables multiband_block_tables(const TilePlan& P, const std::vector<RwEntry>
 // ---- stage: the multiband launches -------------------------------------------------------------------------------------------
 unsigned xcd_grid(int n_blocks) { return 8u * (unsigned)((n_blocks + 7) / 8); }  // (see xcd_contiguous_id)
 
-void launch_warp(const RwArgs& A, const int* d_blk0, int n_blocks, bool exact) {
+void launch_warp(const RwArgs& A, const int* d_blk0, int n_blocks, bool exact, bool maxweight) {
     if (n_blocks == 0) return;
     Prof prof("render_warp");
     const bool nw = A.cv.mode >= APS_PROJ_MILLER;  // (the kernels' mode family)
-    if (exact)
+    if (maxweight && exact)
+        (nw ? rw_warp_kernel<true, true> : rw_warp_kernel<false, true>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+    else if (maxweight)
+        (nw ? rw_warp_staged_kernel<true, true> : rw_warp_staged_kernel<false, true>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
+    else if (exact)
         (nw ? rw_warp_kernel<true> : rw_warp_kernel<false>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
     else
         (nw ? rw_warp_staged_kernel<true> : rw_warp_staged_kernel<false>)<<<xcd_grid(n_blocks), 256, 0, stream()>>>(A, d_blk0, n_blocks);
@@ -2120,7 +2154,7 @@ bool render_multiband_batched(const DevImage* dimgs, const DevImage* himgs, int 
     A.n_entries = (int)ents.size();
     A.G = d_G;
     A.F = d_F;
-    launch_warp(A, d_blk0, B.warp_blocks, exact);
+    launch_warp(A, d_blk0, B.warp_blocks, exact, o.blending == APS_BLEND_MULTIBAND_MAXWEIGHT);
     launch_shrinks(A, B, d_levels, exact);
     launch_collapse(A, B, d_levels);
     const auto T4 = Clock::now();

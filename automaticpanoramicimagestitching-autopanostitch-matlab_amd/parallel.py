@@ -1093,6 +1093,8 @@ def stitch_distributed(input, local_images, n, Ks=None, tile=(2048, 2048), seed=
     t0 = time.perf_counter()
     opts = {"anglePower": 2, "blending": input["blending"], "pyrLevels": input["bands"], "pyrSigma": input["MBBsigma"],
             "canvasColor": input["canvasColor"], "tile": tile, "cropBorder": bool(input.get("cropBorder", True))}  # displayPanorama.m:101
+    if input.get("multibandWeights") is not None:  # 'tent' / 'maxweight' (renderPanorama.multiband_weights)
+        opts["multibandWeights"] = input["multibandWeights"]
     geos, by_component, comp_owner = _render_plan(input, comps, images, opts)
     panos = []
     for ci, c in enumerate(comps):

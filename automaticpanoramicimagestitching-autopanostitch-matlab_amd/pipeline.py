@@ -710,6 +710,8 @@ def stitch(input, images, Ks=None, cameras=None, tile=(2048, 2048), seed=0, devi
     t0 = time.perf_counter()
     opts = {"anglePower": 2, "blending": input["blending"], "pyrLevels": input["bands"], "pyrSigma": input["MBBsigma"],
             "canvasColor": input["canvasColor"], "tile": tile, "cropBorder": bool(input.get("cropBorder", True))}  # displayPanorama.m:101
+    if input.get("multibandWeights") is not None:  # 'tent' / 'maxweight' (renderPanorama.multiband_weights)
+        opts["multibandWeights"] = input["multibandWeights"]
     annotate = bool(input.get("showPanoramaImgsNums")) and bool(input.get("showCropBoundingBox"))
     if annotate:  # displayPanorama.m:109-110; the panoramas are the same bytes with and without
         opts.update(showPanoramaImgsNums=True, showCropBoundingBox=True)

@@ -24,6 +24,27 @@ _PLANE_MODES = ("planar", "perspective", "panini")  # asymmetric bounds about Rr
 _DISC_MODES = ("stereographic", "fisheye")          # a centred square about Rref, stereographicBounds' structure
 _BLEND = {"none": _capi.APS_BLEND_NONE, "linear": _capi.APS_BLEND_LINEAR, "multiband": _capi.APS_BLEND_MULTIBAND}
 _POLICY = {"last": _capi.APS_NONE_LAST, "first": _capi.APS_NONE_FIRST, "maxangle": _capi.APS_NONE_MAXANGLE}
+_MULTIBAND_WEIGHTS = ("tent", "maxweight")
+
+
+def multiband_weights(opts):
+    """opts['multibandWeights'] for a multiband blend: 'tent' (default: the reference's normalised tent weights in every
+    band) or 'maxweight' (Brown & Lowe Eq. 15-19: each band blended over the partition by largest weight; DESIGN.md,
+    "Max-weight multiband contract").  The key is read only with blending = 'multiband'; any other value is a ValueError."""
+    if str(opts.get("blending", "multiband")).lower() != "multiband":
+        return "tent"
+    v = opts.get("multibandWeights", "tent")
+    if not isinstance(v, str) or v.lower() not in _MULTIBAND_WEIGHTS:
+        raise ValueError(f"multibandWeights must be 'tent' or 'maxweight', not {v!r}")
+    return v.lower()
+
+
+def blend_mode(opts):
+    """The APS_BLEND_* value of opts['blending'] and opts['multibandWeights'] (None for an unknown blending)."""
+    mode = _BLEND.get(str(opts["blending"]).lower())
+    if mode == _capi.APS_BLEND_MULTIBAND and multiband_weights(opts) == "maxweight":
+        mode = _capi.APS_BLEND_MULTIBAND_MAXWEIGHT
+    return mode
 
 
 def default_opts(opts, cameras, refIdx):
@@ -530,7 +551,9 @@ def make_render_opts(opts):
     tile = opts["tile"]
     ro.tile_h, ro.tile_w = int(tile[0]), int(tile[1])
     ro.angle_power = float(opts["anglePower"])
-    ro.blending = _BLEND[str(opts["blending"]).lower()]
+    ro.blending = blend_mode(opts)
+    if ro.blending is None:
+        raise KeyError(str(opts["blending"]).lower())
     ro.pyr_levels = int(opts["pyrLevels"])
     ro.pyr_sigma = float(opts["pyrSigma"])
     ro.none_policy = _POLICY[str(opts["composeNonePolicy"]).lower()]
@@ -721,11 +744,11 @@ def planar_composite(images, tforms, view, opts=None, gains=None, device_out=Fal
     o.update(opts or {})
     n, keep, pim, ih, iw, ic, Hs = _planar_args(images, tforms)
     Hc, Wc, x0, y0, sx, sy = _planar_view(view)
-    mode = _BLEND.get(str(o["blending"]).lower())
+    mode = blend_mode(o)
     if mode is None:
         raise ValueError("Wrong blening mode.")
     levels, sigma = int(o["pyrLevels"]), float(o["pyrSigma"])
-    if mode == _capi.APS_BLEND_MULTIBAND:
+    if mode in (_capi.APS_BLEND_MULTIBAND, _capi.APS_BLEND_MULTIBAND_MAXWEIGHT):
         if int(o["pyrLevels"]) != o["pyrLevels"] or levels < 1:
             raise ValueError("levels must be a positive integer")
         if sigma <= 0:
@@ -825,6 +848,7 @@ def pureNonRotationalPanoramas(images, cameras, numImages, opts, gains=None, dev
     o = {"blending": "multiband", "pyrLevels": 3, "pyrSigma": 1.0, "canvasColor": "black",
          "sigmaN": 10.0, "sigmag": 0.1}  # (renderPanorama.m:56-58: the defaults opts carries into gainCompensationH)
     o.update(opts or {})
+    multiband_weights(o)  # (an unknown value is refused before any work)
     images = [im if _capi.is_torch(im) else np.asarray(im) for im in images[:numImages]]
     tforms = [np.asarray(cam["H2refined"], np.float64) for cam in cameras[:numImages]]
     lims = [outputLimitsScratch(T, (1, int(im.shape[1])), (1, int(im.shape[0])))
@@ -886,7 +910,7 @@ def _planar_host(images, tforms, view, o, gains=None):
     elif mode == "linear":
         pano = linearBlending(Iw, Ww)
     elif mode == "multiband":
-        pano = multiBandBlending(Iw, Ww, int(o["pyrLevels"]), True, float(o["pyrSigma"]))
+        pano = multiBandBlending(Iw, Ww, int(o["pyrLevels"]), True, float(o["pyrSigma"]), Weights=multiband_weights(o))
     else:
         raise ValueError("Wrong blening mode.")
     pano = np.array(pano, np.float32, copy=True)
@@ -917,6 +941,7 @@ def renderPanorama(input, images, imgSize, cameras, mode, refIdx, opts=None, gai
         pano, ann = pureNonRotationalPanoramas(images, cameras, len(images), opts or {}, gains, device_out)
         return (pano, ann, None, None) if return_covered else (pano, ann)
     o = default_opts(opts, cameras, refIdx)
+    multiband_weights(o)  # (an unknown value is refused before any library call)
     imgSize = [tuple(int(v) for v in s) for s in imgSize]
     if geo is None:  # (a caller that has sized the canvas already - the sharded driver - passes it in)
         geo = canvas_geometry(cameras, imgSize, mode, refIdx, o)
@@ -1047,6 +1072,8 @@ def displayPanorama(input, finalPanoramaTforms, finalrefIdxs, imagesAll, imageSi
                 "showCropBoundingBox": input["showCropBoundingBox"], "useMATLABImwarp": input.get("useMATLABImwarp", 0)}
         if input.get("tile") is not None:
             opts["tile"] = input["tile"]
+        if input.get("multibandWeights") is not None:
+            opts["multibandWeights"] = input["multibandWeights"]
         for projection in projections:
             panorama, annoRGB = renderPanorama(input, images, imageSizes, cameras, projection, refIdx, opts, device_out=device_out)
             if projection in _DISPLAY_PROJECTIONS:  # :126-136

@@ -407,7 +407,10 @@ enum {
     APS_PROJ_FISHEYE = 5,       /* equidistant azimuthal about R_ref: hypot(a, b) = angle from the axis; void beyond pi */
     APS_PROJ_PANINI = 6         /* Pannini, d = 1, about R_ref: ray (a, b, 1 - a^2 / 4); verticals stay straight  */
 };
-enum { APS_BLEND_NONE = 0, APS_BLEND_LINEAR = 1, APS_BLEND_MULTIBAND = 2 };
+/* APS_BLEND_MULTIBAND_MAXWEIGHT: multiband over the max-weight partition (Brown & Lowe Eq. 15-19; DESIGN.md, "Max-weight
+ * multiband contract"): every pixel's level-0 weight is 1 for the first layer of maximal raw weight (> 0) and 0 for the others;
+ * pyramids, collapse, clamp, void paint and coverage are APS_BLEND_MULTIBAND's.  Accepted wherever APS_BLEND_MULTIBAND is. */
+enum { APS_BLEND_NONE = 0, APS_BLEND_LINEAR = 1, APS_BLEND_MULTIBAND = 2, APS_BLEND_MULTIBAND_MAXWEIGHT = 3 };
 enum { APS_NONE_LAST = 0, APS_NONE_FIRST = 1, APS_NONE_MAXANGLE = 2 };
 enum {
     APS_IMG_U8_HWC = 0,   /* row-major interleaved H x W x C (numpy / torch)            */
@@ -634,6 +637,13 @@ int aps_warp_tile(const aps_image* image, const aps_canvas* canvas, int r0, int 
 int aps_multiband_blend(const float* C, const float* Wt, int k, int h, int w, int levels,
                         float sigma, float* F);
 
+/* The max-weight partition, the stand-alone partner of aps_multiband_blend ("Max-weight multiband contract"):
+ * out[k] = 1.0f at the pixels where layer k is the FIRST layer of maximal weight and that maximum is > 0 (written `w > best`,
+ * so a NaN never owns), 0.0f elsewhere; a pixel without a positive weight has no owner.
+ *   Wt, out: f32 k x h x w as aps_multiband_blend takes Wt, host or device memory; out may alias Wt.  No cap on k.
+ * Errors: APS_E_ARG for a NULL pointer, k < 1, h < 1 or w < 1, before any device work. */
+int aps_maxweight_weights(const float* Wt, int k, int h, int w, float* out);
+
 /* a22: linearBlending (linearBlending.m:46-115) on f32 layers: sum(I.*W)/max(sum(W),eps('single')). */
 int aps_linear_blend(const float* C, const float* Wt, int k, int h, int w, float* F);
 
@@ -664,7 +674,8 @@ int aps_image_warp_f32(const float* in, int in_h, int in_w, int c, const double*
  *   buffer of this library; sizes may differ per image.  H: n_img 3x3 f64 matrices, column-major each, as aps_image_warp_* takes
  *   them.  out_h, out_w, x0, y0, sx, sy: the canvas (imref2dScratch: ImageSize, XWorldLimits(1), YWorldLimits(1),
  *   PixelExtentInWorldX/Y); its size is the caller's computation (outputLimitsScratch, :547-575) and is not re-derived here.
- *   blending: APS_BLEND_*; levels, sigma: multiBandBlending's (used by APS_BLEND_MULTIBAND only).  white_canvas: void pixels
+ *   blending: APS_BLEND_*; levels, sigma: multiBandBlending's (used by APS_BLEND_MULTIBAND and APS_BLEND_MULTIBAND_MAXWEIGHT
+ *   only; the byte formulas return for the latter what they return for the former).  white_canvas: void pixels
  *   (no image has weight > 0 there) become 255 instead of 0.  gains: f32 n_img x 3 row-major, or NULL for ones (:584-591: one
  *   f32 multiply per channel after the warp).  pano: uint8 out_h x out_w x 3 row-major interleaved (a single-channel image is
  *   replicated); covered (optional, may be NULL): uint8 out_h x out_w, 1 where some image has weight > 0.
