@@ -100,6 +100,14 @@ class aps_surf_view(C.Structure):
                 ("cap", C.c_int64), ("count", C.c_int64)]
 
 
+APS_KAZE_DIFFUSION_REGION, APS_KAZE_DIFFUSION_SHARPEDGE, APS_KAZE_DIFFUSION_EDGE = 0, 1, 2
+
+
+class aps_kaze_params(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("num_octaves", C.c_int), ("num_scale_levels", C.c_int),
+                ("diffusion", C.c_int), ("max_features", C.c_int)]
+
+
 APS_FAST_MAX_VIEWS = 16
 
 
@@ -266,6 +274,8 @@ _SIGNATURES = {
     "aps_surf_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_surf_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
     "aps_fast_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_params), _vp, _i, _i64, _vp, _i64,
+                         _vp, _i64, C.POINTER(_i64)],
+    "aps_kaze_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_kaze_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
     "aps_freak_pattern": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
     "aps_fast_extract_pyramid": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i, _i64, _vp, _i64,

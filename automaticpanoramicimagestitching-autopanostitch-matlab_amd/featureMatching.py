@@ -893,6 +893,46 @@ def surf_extract_batch(input, images, device_out=False, want_aux=False, points_d
     return [r if want_aux else r[:2] for r in out]
 
 
+KAZE_DIM = 64
+_KAZE_DIFFUSION = {"region": _capi.APS_KAZE_DIFFUSION_REGION, "sharpedge": _capi.APS_KAZE_DIFFUSION_SHARPEDGE,
+                   "edge": _capi.APS_KAZE_DIFFUSION_EDGE}
+
+
+def _kaze_params(input):
+    """detectKAZEFeatures' defaults; a Diffusion the library does not build is a ValueError here, before any library call."""
+    diffusion = str(input.get("Diffusion", "region"))
+    if diffusion not in _KAZE_DIFFUSION:
+        raise ValueError(f"Diffusion must be 'region', 'sharpedge' or 'edge', not {diffusion!r}")
+    if diffusion != "region":
+        raise ValueError(f"Diffusion = {diffusion!r} is not built (it needs exp on the device); only 'region' is")
+    p = _capi.aps_kaze_params()
+    p.threshold = float(input.get("Threshold", 0.0001))
+    p.num_octaves = int(input.get("NumOctaves", 3))
+    p.num_scale_levels = int(input.get("NumScaleLevels", 4))
+    p.diffusion = _KAZE_DIFFUSION[diffusion]
+    p.max_features = int(input.get("maxFeatures", 0))
+    return p
+
+
+def kaze_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False, padded=False):
+    """aps_kaze_extract with automatic capacity: returns (features, validPts[, aux]); the arguments are surf_extract's.
+
+    Keys of `input`, all optional: Threshold (0.0001), NumOctaves (3, 1..4), NumScaleLevels (4, 3..10), Diffusion ('region'; the
+    other two are a ValueError), maxFeatures.  Host results are n x 64 unit-norm oriented M-SURF rows.  Resident results
+    (device_out=True) are the [:, :64] view of an n x 128 buffer whose columns 64..127 the library zeroed, or with padded=True that
+    buffer itself, as surf_extract's.  validPts: n x 2 float64 [x y] 1-based.  aux: n x 4 [scale, angle_deg, metric, level].
+    There is no NumStrongest / NumUniform selection and no group form (DESIGN.md "KAZE contract")."""
+    img, h, w, c = _image_hwc(image)
+    prm = _kaze_params(input)
+    width = DIM if device_out else KAZE_DIM  # (resident rows are 128 wide, host rows 64; the leading dimension follows)
+    d, pts, aux = _extract_regrow(1, max(4096, (h * w) // 64), _one_view_call(lib.aps_kaze_extract, prm, img, h, w, c, width),
+                                  _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), width, np.float32,
+                                  device_out, points_device, compact, want_aux)[0]
+    if device_out and not padded:
+        d = d[:, :KAZE_DIM]
+    return (d, pts, aux) if want_aux else (d, pts)
+
+
 FREAK_BYTES = 64
 ORB_BYTES = 32
 
@@ -1058,12 +1098,15 @@ def fast_extract_batch(input, images, device_out=False, want_aux=False, points_d
 
 
 def extract_features(input, image, **kw):
-    """sift_extract, surf_extract or fast_extract, as input.detector says (the dispatch of the pipeline's extraction stages)."""
+    """sift_extract, surf_extract, kaze_extract or fast_extract, as input.detector says (the dispatch of the pipeline's extraction
+    stages).  'KAZE' enters here and not through getFeaturePoints, which keeps refusing it."""
     det = input.get("detector", "SIFT")
     if det == "FAST":
         return fast_extract(input, image, **kw)
     if det == "SURF":
         return surf_extract(input, image, padded=bool(kw.get("device_out")), **kw)
+    if det == "KAZE":
+        return kaze_extract(input, image, padded=bool(kw.get("device_out")), **kw)
     if det == "SIFT":
         return sift_extract(input, image, **kw)
     return getFeaturePoints(input, image)  # raises for the rest of the switch

@@ -115,7 +115,7 @@ def _group_route(input):
 
 def sift_many(input, images, workers=SIFT_WORKERS_DEFAULT, ready=None):
     """getFeaturePoints for many images — the reference runs this loop as a parfor (loadImages.m:82-99).
-    input.detector selects SIFT, SURF or FAST (fm.extract_features); the name is kept, it is public.  With FAST, the optional
+    input.detector selects SIFT, SURF, KAZE or FAST (fm.extract_features); the name is kept, it is public.  With FAST, the optional
     input.DescriptorMethod ('FREAK' | 'ORB') and input.CornerMethod ('FAST' | 'Harris') travel with `input` to fm.fast_extract and
     fm.fast_extract_batch on every route below.
     Here a few host threads each drive their own HIP stream (the C ABI is thread-safe with per-thread streams

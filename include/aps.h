@@ -1190,6 +1190,45 @@ int aps_uniform_quota(const int64_t* counts, int n_cells, int64_t budget, int64_
 int aps_uniform_cell(int py, int px, int plane_h, int plane_w, int grid_rows, int grid_cols, int* cell);
 
 /* ============================================================================================
+ * (4e) KAZE — PP/featureMatching/getFeaturePoints.m:63-64,71-74
+ * ============================================================================================ */
+
+#define APS_KAZE_DIFFUSION_REGION 0      /* Perona-Malik g2, 1 / (1 + |grad|^2 / k^2): detectKAZEFeatures' default, the one built */
+#define APS_KAZE_DIFFUSION_SHARPEDGE 1   /* g1 = exp(-|grad|^2 / k^2): not built (APS_E_ARG) */
+#define APS_KAZE_DIFFUSION_EDGE 2        /* Weickert's: not built (APS_E_ARG) */
+
+typedef struct aps_kaze_params {
+    double threshold;          /* detectKAZEFeatures Threshold (0.0001), >= 0 */
+    int num_octaves;           /* NumOctaves (3), 1..4 */
+    int num_scale_levels;      /* NumScaleLevels (4), 3..10 */
+    int diffusion;             /* APS_KAZE_DIFFUSION_*: only _REGION is built */
+    int max_features;          /* capacity guard; 0 = library default (none beyond cap) */
+} aps_kaze_params;
+
+/* [features, validPts] for detector 'KAZE' (getFeaturePoints.m:63-64,71-74): rgb2gray, detectKAZEFeatures(gray), extractFeatures.
+ * Both toolbox calls are closed code; the algorithm restated is KAZE of Alcantarilla, Bartoli and Davison (ECCV 2012) with the
+ * parameters that call implies — see DESIGN.md "KAZE contract", which fixes every operation and its order (parity with MATLAB is
+ * unpinned); tests/kaze_mirror.py restates it in NumPy, bit for bit.  num_octaves * num_scale_levels evolution levels, all at full
+ * resolution; keypoints are strict 3x3x3 maxima of the scale-normalised Hessian determinant above `threshold` on the levels between
+ * the first and the last, refined as SURF's are.
+ *   desc : f32 count x 64 oriented M-SURF rows, `desc_layout` with leading dimension ldd >= 64 (row-major) / >= cap (column-major),
+ *          unit L2 norm; row-major with ldd >= 128: columns 64..127 are zeroed as well, so resident rows feed the 128-wide matchers
+ *   loc  : f64 count x 2 [x y], 1-based sub-pixel, column-major with leading dimension ldl >= cap
+ *   aux  : f32 count x 4 row-major [scale (sigma, pixels), angle_deg, metric (the response), level] or NULL
+ * cap = rows available in desc/loc/aux; *count = features found (APS_E_CAP if cap is too small, with the true count and nothing
+ * written; desc = NULL or cap = 0 counts).  Rows beyond the count are never written.  Every argument is checked before any device
+ * work: NULL img / params / count, num_octaves outside 1..4, num_scale_levels outside 3..10, threshold < 0, a diffusion other than
+ * APS_KAZE_DIFFUSION_REGION and height * width >= 2^31 are APS_E_ARG.  An image too small for level 1's margin gives
+ * count 0, not an error.  Host and device pointers are accepted; the call runs on the calling thread's library stream with that
+ * thread's workspace (4 bytes x (5 + 3 levels) planes: 1.36 GB for a 3840 x 2160 view at the defaults) and reads back once, the count.
+ * Feature order is canonical: ascending (level, row, col).
+ * Not built: the 'sharpedge' and 'edge' diffusivities, 128-D rows, Upright, group (batch) entries, NumStrongest / NumUniform
+ * selections and a MATLAB gateway command. */
+int aps_kaze_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
+                     const aps_kaze_params* params, float* desc, int desc_layout, int64_t ldd,
+                     double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+/* ============================================================================================
  * Lens distortion: undistortImage / undistortPoints of the Computer Vision Toolbox ("Lens distortion contract")
  * ============================================================================================ */
 /* A lens without skew.  Coordinates are the library's 1-based pixel coordinates (the frame of keypoints, of K and of
