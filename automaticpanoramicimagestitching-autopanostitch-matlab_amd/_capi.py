@@ -108,6 +108,11 @@ class aps_kaze_params(C.Structure):
                 ("diffusion", C.c_int), ("max_features", C.c_int)]
 
 
+class aps_kaze_select_params(C.Structure):
+    _fields_ = [("kaze", aps_kaze_params), ("select", C.c_int), ("n_select", C.c_int), ("grid_rows", C.c_int),
+                ("grid_cols", C.c_int), ("upright", C.c_int)]
+
+
 APS_FAST_MAX_VIEWS = 16
 
 
@@ -277,6 +282,8 @@ _SIGNATURES = {
                          _vp, _i64, C.POINTER(_i64)],
     "aps_kaze_extract": [_vp, _i, _i, _i, _i, C.POINTER(aps_kaze_params), _vp, _i, _i64, _vp, _i64,
                          _vp, _i64, C.POINTER(_i64)],
+    "aps_kaze_extract_select": [_vp, _i, _i, _i, _i, C.POINTER(aps_kaze_select_params), _vp, _i, _i64, _vp, _i64,
+                                _vp, _i64, C.POINTER(_i64)],
     "aps_freak_pattern": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
     "aps_fast_extract_pyramid": [_vp, _i, _i, _i, _i, C.POINTER(aps_fast_pyramid_params), _vp, _i, _i64, _vp, _i64,
                                  _vp, _i64, C.POINTER(_i64)],

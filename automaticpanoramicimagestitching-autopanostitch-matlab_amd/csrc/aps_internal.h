@@ -251,6 +251,15 @@ int64_t screened_global_top3(const float* X_dev, int64_t ld, int layout, const s
                              float ratio, const SlotTable& table, const int64_t* d_img_off, const int64_t* d_job_off, GlobalSets& sets,
                              uint32_t* t3_idx, float* t3_d, float* t3_b, uint8_t* dismissed);
 
+// surf.hip: select_dev.h's selection and ordered compaction for a translation unit that builds the keys of its own int4 candidates
+// (kaze.hip).  The selection's kernels are instantiated in every translation unit that launches them; a detector whose candidates
+// are SURF's records runs surf.hip's copies instead of carrying a fourth set.  One group of n candidates (keys below 2^60), of which
+// `keep` <= n stay: cells == 0 by (key ascending, index ascending), keys of 32 bits (select_by_key); cells > 0 spread over the
+// segments key >> 32 < cells by water-filling (select_uniform's composite-key form).  sel[0 .. keep - 1] = the kept candidates in
+// the order they had; *d_kept = the number the device kept.  On the calling thread's stream; no read-back.
+void select_int4_group(const unsigned long long* keys, const unsigned int* vals, const int4* cand, unsigned int n, unsigned int keep,
+                       unsigned int cells, int4* sel, unsigned int* d_kept);
+
 // set bits of a 64-bit ballot word, as a rocprim transform (surf.hip, fast.hip, hamming_pairs.hip: the scans behind their ordered compactions)
 struct PopcOp {
     __host__ __device__ unsigned int operator()(unsigned long long v) const {

@@ -23,6 +23,15 @@
 //                           canonical feature order (level, row, col)
 //   exclusive scan of the words' popcounts (rocprim), group_rows_kernel (group_dev.h: a group of one view), kaze_emit_kernel
 //   kaze_keypoint_kernel    one wave per keypoint: the 27 responses again, refinement, orientation, descriptor, outputs
+//
+// aps_kaze_extract_select (DESIGN.md "KAZE selection and Upright") shares the chain up to the scan (kaze_front).  With a selection
+// it reads the candidate count back, lists all candidates and continues with
+//   kaze_key_kernel         the metric of every candidate as the selection's key, under its grid cell for uniform-N
+//   select_int4_group       (surf.hip's copies of select_dev.h's kernels) stable radix sort, flags, ballot words, scan, water-filling
+//                           for uniform-N, select_compact_kernel (canonical order again)
+//   kaze_keypoint_kernel    on the kept candidates only
+// and a second read-back, the count the device kept.  Upright is the keypoint kernel's second instantiation, without the
+// orientation stage.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +41,7 @@
 
 #include "aps_internal.h"
 #include "group_dev.h"
+#include "select_key.h"  // (the key's layout and the uniform entries' checks; the selection itself is surf.hip's select_int4_group)
 
 namespace aps {
 namespace {
@@ -450,7 +460,9 @@ __device__ __forceinline__ float bilinear(const float* __restrict__ P, int h, in
 }
 
 // One wave per keypoint (blockIdx.y: the view of group_dev.h's records, always 0 here).  Every wave of the capacity grid passes every
-// barrier; the ones beyond the rows do no work.
+// barrier; the ones beyond the rows do no work.  UPRIGHT: no orientation stage; the descriptor stage is the same code at
+// (c, sn) = (1.0f, 0.0f), which the compiler may fold only as IEEE arithmetic allows, and angle_deg is +0.0.
+template <bool UPRIGHT>
 __global__ __launch_bounds__(256) void kaze_keypoint_kernel(const float* __restrict__ Rp, const float* __restrict__ Dx, const float* __restrict__ Dy,
                                                             KazePlan plan, const KazeTables* __restrict__ tb, const int4* __restrict__ kps,
                                                             const ViewRows<float>* __restrict__ views, int desc_layout, long long ldd,
@@ -484,7 +496,7 @@ __global__ __launch_bounds__(256) void kaze_keypoint_kernel(const float* __restr
     __syncthreads();
     // ---- orientation --------------------------------------------------------------------------------------------------
     float c = 1.0f, sn = 0.0f, angle = 0.0f;
-    if (active) {
+    if (!UPRIGHT && active) {
         for (int k = lane; k < kOriN; k += 64) {
             const float X = px + (float)tb->ori_dj[k] * s, Y = py + (float)tb->ori_di[k] * s;
             const size_t at = (size_t)clampi(round_half_up(Y), h - 1) * w + clampi(round_half_up(X), w - 1);
@@ -493,8 +505,8 @@ __global__ __launch_bounds__(256) void kaze_keypoint_kernel(const float* __restr
             s_y[wave][k] = g * Ly[at];
         }
     }
-    __syncthreads();
-    if (active) {
+    if (!UPRIGHT) __syncthreads();
+    if (!UPRIGHT && active) {
         // lane = window; members are summed in sample order 0..108
         const float cw = tb->win_c[lane], sw = tb->win_s[lane];
         float sx = 0.0f, sy = 0.0f;
@@ -520,7 +532,7 @@ __global__ __launch_bounds__(256) void kaze_keypoint_kernel(const float* __restr
             if (angle < 0.0f) angle += 360.0f;
         }
     }
-    __syncthreads();
+    if (!UPRIGHT) __syncthreads();
     // ---- descriptor ---------------------------------------------------------------------------------------------------
     if (active) {
         for (int q = lane; q < kGrid * kGrid; q += 64) {
@@ -601,16 +613,40 @@ void check_args(const uint8_t* img, int height, int width, int channels, int img
     APS_REQUIRE((int64_t)height * width < (int64_t)1 << 31, APS_E_ARG, "KAZE: %d x %d pixels exceed the 2^31 elements of a plane", height, width);
 }
 
-// aps_kaze_extract behind its argument checks.  One read-back: the count.
-void kaze_chain(KazeView* view, int H, int W, int channels, int img_layout, const aps_kaze_params* params, int desc_layout, int64_t ldd,
-                int64_t ldl) {
-    ctx();
-    view->count = 0;
-    unsigned int room[1], n[1];
-    check_views(view, 1, 64, desc_layout, ldd, ldl, room);
+// ---- selection (DESIGN.md "KAZE selection and Upright") ---------------------------------------------------------------------
+// The key of every candidate and its index as the sort's value.  The strength is the candidate's metric: the plane element that
+// kaze_keypoint_kernel puts in s_a[wave][13], so the same bits.  rows == 0: strongest-N, the key of group 0.  rows > 0: uniform-N, the
+// same key under the segment = the cell of the detection pixel (kp.y, kp.z), the unrefined one that kaze_emit_kernel lists, in the
+// rows x cols grid over the image (surf_uniform_key_kernel's composite).
+__global__ __launch_bounds__(256) void kaze_key_kernel(const float* __restrict__ Rp, KazePlan plan, const int4* __restrict__ cand, unsigned int n,
+                                                       int rows, int cols, unsigned long long* __restrict__ keys,
+                                                       unsigned int* __restrict__ vals) {
+    const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int4 kp = cand[i];
+    const float metric = Rp[(size_t)kp.x * plan.pitch + (size_t)kp.y * plan.w + kp.z];
+    const unsigned int cell = rows > 0 ? (unsigned int)uniform_cell(kp.y, kp.z, plan.h, plan.w, rows, cols) : 0u;
+    keys[i] = (unsigned long long)cell << kSegmentShift | strength_key_f32(metric);
+    vals[i] = i;
+}
+
+// What both entries hold once the candidates are known: the planes the keypoint kernel reads, the candidate bitmap, whose bit order
+// is the canonical order, and the exclusive scan of its popcounts; prefix[plan.n_words] is the number of candidates.  The scratch
+// planes of the scale space stay allocated with the rest until the chain returns.
+struct KazeFront {
+    KazePlan plan;
+    In<uint8_t> dimg;
+    Ws<float> P0, La, Lb, Cc, Ls, Dx, Dy, Rr, stats;
+    Ws<unsigned int> hist, prefix;
+    Ws<unsigned long long> bitmap;
+};
+
+// plan, scale space, detection and scan on the calling thread's stream; no read-back.  false: no pixel of level 1 lies inside its
+// margin.
+bool kaze_front(const KazeView* view, int H, int W, int channels, int img_layout, const aps_kaze_params* params, KazeFront& F) {
     const int S = params->num_scale_levels, nl = params->num_octaves * S;
     static_assert(4 * 10 <= kMaxLevels, "the levels of the largest call");
-    KazePlan plan;
+    KazePlan& plan = F.plan;
     std::memset(&plan, 0, sizeof plan);
     plan.n_levels = nl;
     plan.h = H;
@@ -627,12 +663,17 @@ void kaze_chain(KazeView* view, int H, int W, int channels, int img_layout, cons
         plan.inv[i] = (float)(1.0 / (32.0 * (double)plan.step[i]));
         plan.norm4[i] = (float)(sig[i] * sig[i] * sig[i] * sig[i]);
     }
-    if (std::min(H, W) < 2 * plan.margin[1] + 1) return;  // no pixel of level 1 lies inside its margin: no features, no error
+    if (std::min(H, W) < 2 * plan.margin[1] + 1) return false;
     const size_t N = plan.pitch;
     const GaussW g0 = gauss_weights(1.6, kR0), g1 = gauss_weights(1.0, kR1);
-    In<uint8_t> dimg(view->img, N * channels);
-    Ws<float> P0(N), La(N), Lb(N), Cc(N), Ls(N), Dx((size_t)nl * N), Dy((size_t)nl * N), Rr((size_t)nl * N), stats(2);
-    Ws<unsigned int> hist(1 + kBins);  // [0]: the bits of the largest gradient magnitude
+    F.dimg.bind(view->img, N * channels);
+    const In<uint8_t>& dimg = F.dimg;
+    Ws<float>&P0 = F.P0, &La = F.La, &Lb = F.Lb, &Cc = F.Cc, &Ls = F.Ls, &Dx = F.Dx, &Dy = F.Dy, &Rr = F.Rr, &stats = F.stats;
+    for (Ws<float>* plane : {&P0, &La, &Lb, &Cc, &Ls}) plane->alloc(N);
+    for (Ws<float>* planes : {&Dx, &Dy, &Rr}) planes->alloc((size_t)nl * N);
+    stats.alloc(2);
+    Ws<unsigned int>& hist = F.hist;  // [0]: the bits of the largest gradient magnitude
+    hist.alloc(1 + kBins);
     const dim3 tiles(cdiv(W, kTW), cdiv(H, kTH));
     {
         Prof prof("kaze_contrast");
@@ -681,8 +722,10 @@ void kaze_chain(KazeView* view, int H, int W, int channels, int img_layout, cons
             check_launch("kaze_fed_kernel");
         }
     }
-    Ws<unsigned long long> bitmap((size_t)plan.n_words + 1);  // (+1: a zero word, whose prefix is the total)
-    Ws<unsigned int> prefix((size_t)plan.n_words + 1);
+    Ws<unsigned long long>& bitmap = F.bitmap;
+    Ws<unsigned int>& prefix = F.prefix;
+    bitmap.alloc((size_t)plan.n_words + 1);  // (+1: a zero word, whose prefix is the total)
+    prefix.alloc((size_t)plan.n_words + 1);
     APS_HIP(hipMemsetAsync(bitmap.get() + plan.n_words, 0, sizeof(unsigned long long), stream()));
     {
         Prof prof("kaze_detect");
@@ -690,29 +733,96 @@ void kaze_chain(KazeView* view, int H, int W, int channels, int img_layout, cons
         check_launch("kaze_detect_kernel");
     }
     exclusive_scan(popcounts(bitmap.get()), prefix.get(), 0u, (size_t)plan.n_words + 1);
-    GroupOut<float, KazeView> out(view, 1, room, 64, desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64, desc_layout, ldd, ldl, nullptr, nullptr);
+    return true;
+}
+
+// the first `kcap` set bits of the candidate bitmap -> kps, in canonical order
+void kaze_emit(const KazeFront& F, int4* kps, unsigned int kcap) {
+    kaze_emit_kernel<<<cdiv((size_t)F.plan.n_words, 256), 256, 0, stream()>>>(F.bitmap, F.prefix, F.plan, kps, kcap);
+    check_launch("kaze_emit_kernel");
+}
+
+// the rows of the view's record in `kps` -> desc, loc and aux: one launch of `most` waves
+void kaze_describe(const KazeFront& F, const int4* kps, GroupOut<float, KazeView>& out, unsigned int most, bool upright) {
+    Ws<KazeTables> d_tb(1);
+    APS_HIP(hipMemcpyAsync(d_tb, &host_tables(), sizeof(KazeTables), hipMemcpyHostToDevice, stream()));
+    {
+        Prof prof("kaze_keypoint");
+        const dim3 grid(cdiv(most, 4), 1);
+        if (upright)
+            kaze_keypoint_kernel<true><<<grid, 256, 0, stream()>>>(F.Rr, F.Dx, F.Dy, F.plan, d_tb, kps, out.d_rows, out.desc_layout,
+                                                                   (long long)out.ldd, (long long)out.ldl);
+        else
+            kaze_keypoint_kernel<false><<<grid, 256, 0, stream()>>>(F.Rr, F.Dx, F.Dy, F.plan, d_tb, kps, out.d_rows, out.desc_layout,
+                                                                    (long long)out.ldd, (long long)out.ldl);
+        check_launch("kaze_keypoint_kernel");
+    }
+}
+
+inline size_t kaze_row_width(int desc_layout, int64_t ldd) { return desc_layout == APS_ROWMAJOR && ldd >= 128 ? 128 : 64; }
+
+// aps_kaze_extract, and aps_kaze_extract_select without a selection, behind their argument checks.  One read-back: the count.
+void kaze_chain(KazeView* view, int H, int W, int channels, int img_layout, const aps_kaze_params* params, bool upright, int desc_layout,
+                int64_t ldd, int64_t ldl) {
+    ctx();
+    view->count = 0;
+    unsigned int room[1], n[1];
+    check_views(view, 1, 64, desc_layout, ldd, ldl, room);
+    KazeFront F;
+    if (!kaze_front(view, H, W, channels, img_layout, params, F)) return;  // no features, no error
+    GroupOut<float, KazeView> out(view, 1, room, 64, kaze_row_width(desc_layout, ldd), desc_layout, ldd, ldl, nullptr, nullptr);
     ViewLimits lim = {};
     lim.cap[0] = room[0];
     lim.max_features = params->max_features;
     Ws<unsigned int> d_n(1);
-    group_rows_kernel<float><<<1, 64, 0, stream()>>>(prefix, plan.n_words, 1, lim, out.d_rows, d_n);
+    group_rows_kernel<float><<<1, 64, 0, stream()>>>(F.prefix, F.plan.n_words, 1, lim, out.d_rows, d_n);
     check_launch("group_rows_kernel");
     if (room[0]) {
         Ws<int4> kps(room[0]);
-        Ws<KazeTables> d_tb(1);
-        APS_HIP(hipMemcpyAsync(d_tb, &host_tables(), sizeof(KazeTables), hipMemcpyHostToDevice, stream()));
-        kaze_emit_kernel<<<cdiv((size_t)plan.n_words, 256), 256, 0, stream()>>>(bitmap, prefix, plan, kps, room[0]);
-        check_launch("kaze_emit_kernel");
-        {
-            Prof prof("kaze_keypoint");
-            kaze_keypoint_kernel<<<dim3(cdiv(room[0], 4), 1), 256, 0, stream()>>>(Rr, Dx, Dy, plan, d_tb, kps, out.d_rows, desc_layout,
-                                                                                 (long long)ldd, (long long)ldl);
-            check_launch("kaze_keypoint_kernel");
-        }
+        kaze_emit(F, kps, room[0]);
+        kaze_describe(F, kps, out, room[0], upright);
     }
     read_back(d_n.get(), n, 1);  // the one read-back of the chain
     settle_counts(view, 1, n, n, params->max_features, "KAZE");
     out.commit(n);
+}
+
+// aps_kaze_extract_select with a selection, behind its argument checks: the N strongest candidates, or with grid_rows > 0 N spread
+// over the cells of the grid.  Two read-backs: the candidate count, which sizes the sort and the grid below, then the count the
+// device kept.  Only the kept candidates reach the keypoint kernel.
+void kaze_select_chain(KazeView* view, int H, int W, int channels, int img_layout, const aps_kaze_params* params, long long N, int grid_rows,
+                       int grid_cols, bool upright, int desc_layout, int64_t ldd, int64_t ldl) {
+    ctx();
+    view->count = 0;
+    unsigned int room[1];
+    check_views(view, 1, 64, desc_layout, ldd, ldl, room);
+    KazeFront F;
+    if (!kaze_front(view, H, W, channels, img_layout, params, F)) return;
+    const unsigned int M = read_back(F.prefix.get() + F.plan.n_words);  // the first read-back: the candidates
+    const unsigned int K = (unsigned int)std::min<long long>(M, N), row0 = 0;
+    settle_counts(view, 1, &K, &M, params->max_features, "KAZE");
+    if (K == 0) return;
+    Ws<int4> cand(M), sel;
+    kaze_emit(F, cand, M);
+    const int4* kps = cand;  // the kept keypoints, in canonical order
+    Ws<unsigned int> d_kept(1);
+    if (K < M) {
+        Prof prof("kaze_select");
+        Ws<unsigned long long> keys(M);
+        Ws<unsigned int> vals(M);
+        kaze_key_kernel<<<cdiv(M, 256), 256, 0, stream()>>>(F.Rr, F.plan, cand, M, grid_rows, grid_cols, keys, vals);
+        check_launch("kaze_key_kernel");
+        sel.alloc(K);
+        select_int4_group(keys, vals, cand, M, K, (unsigned int)(grid_rows * grid_cols), sel, d_kept);
+        kps = sel;
+    }
+    GroupOut<float, KazeView> out(view, 1, &K, 64, kaze_row_width(desc_layout, ldd), desc_layout, ldd, ldl, &row0, &K);
+    kaze_describe(F, kps, out, K, upright);
+    if (K < M) {  // the second read-back: the count the device kept is the count the host worked out
+        const unsigned int kept = read_back(d_kept.get());
+        APS_REQUIRE(kept == K, APS_E_INTERNAL, "the selection kept %u rows on the device, %u on the host", kept, K);
+    }
+    out.commit(&K);
 }
 
 }  // namespace
@@ -729,7 +839,32 @@ int aps_kaze_extract(const uint8_t* img, int height, int width, int channels, in
         check_args(img, height, width, channels, img_layout, params, desc_layout, cap);
         KazeView view = {img, desc, loc, aux, cap, 0};
         try {
-            kaze_chain(&view, height, width, channels, img_layout, params, desc_layout, ldd, ldl);
+            kaze_chain(&view, height, width, channels, img_layout, params, false, desc_layout, ldd, ldl);
+        } catch (...) {
+            *count = view.count;
+            throw;
+        }
+        *count = view.count;
+    });
+}
+
+int aps_kaze_extract_select(const uint8_t* img, int height, int width, int channels, int img_layout, const aps_kaze_select_params* params,
+                            float* desc, int desc_layout, int64_t ldd, double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count) {
+    return guarded([&] {
+        APS_REQUIRE(count && params, APS_E_ARG, "NULL argument");
+        APS_REQUIRE(params->select >= 0 && params->select <= 2, APS_E_ARG, "select must be 0 (none), 1 (strongest-N) or 2 (uniform-N)");
+        if (params->select == 1) APS_REQUIRE(params->n_select >= 1, APS_E_ARG, "n_select (NumStrongest) must be at least 1");
+        if (params->select == 2) check_uniform(params->n_select, params->grid_rows, params->grid_cols);
+        APS_REQUIRE(params->upright == 0 || params->upright == 1, APS_E_ARG, "upright must be 0 or 1");
+        check_args(img, height, width, channels, img_layout, &params->kaze, desc_layout, cap);
+        const bool uniform = params->select == 2;
+        KazeView view = {img, desc, loc, aux, cap, 0};
+        try {
+            if (params->select == 0)
+                kaze_chain(&view, height, width, channels, img_layout, &params->kaze, params->upright != 0, desc_layout, ldd, ldl);
+            else
+                kaze_select_chain(&view, height, width, channels, img_layout, &params->kaze, params->n_select, uniform ? params->grid_rows : 0,
+                                  uniform ? params->grid_cols : 0, params->upright != 0, desc_layout, ldd, ldl);
         } catch (...) {
             *count = view.count;
             throw;

@@ -23,6 +23,7 @@
 
 #include "aps_internal.h"
 #include "prims_dev.h"
+#include "select_key.h"
 #include "uniform_rule.h"
 
 namespace aps {
@@ -45,9 +46,7 @@ inline StrongestCut single_group_cut(unsigned int n, unsigned int k) {
     return cut;
 }
 
-// The key of a non-negative f32 strength in group 0: for such floats the order of the values is the order of their u32 bit
-// patterns, so the complement of the bits ascends as the strength descends.  32 significant bits (select_by_key's key_bits).
-__device__ __forceinline__ unsigned long long strength_key_f32(float strength) { return (unsigned long long)(~__float_as_uint(strength)); }
+// (strength_key_f32, the key of a non-negative f32 strength in group 0: select_key.h)
 
 // position p of the sorted sequence -> flag of the item it came from
 __global__ __launch_bounds__(256) void strongest_flag_kernel(const unsigned long long* __restrict__ sorted_keys,
@@ -124,15 +123,7 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const unsigned long
 }
 
 // ---- uniform-N (DESIGN.md "Uniform-N selection") ------------------------------------------------------------------------------
-constexpr unsigned int kSegmentBits = 14;                              // segment = group * cells + cell < 16 * 1024
-constexpr unsigned int kSegmentShift = 32;                             // a composite key: segment << 32 | strength_key_f32
-
-// the argument checks of the three uniform entries, before any device work
-inline void check_uniform(int n_uniform, int grid_rows, int grid_cols) {
-    APS_REQUIRE(n_uniform >= 1, APS_E_ARG, "n_strongest (NumUniform) must be at least 1");
-    APS_REQUIRE(grid_rows >= 1 && grid_rows <= kUniformMaxGrid && grid_cols >= 1 && grid_cols <= kUniformMaxGrid, APS_E_ARG,
-                "grid_rows and grid_cols (UniformGrid) must be in 1..%d", kUniformMaxGrid);
-}
+// (kSegmentBits, kSegmentShift and check_uniform, the argument checks of the uniform entries: select_key.h)
 
 // the budgets Q_g of the groups, known on the host
 struct UniformBudget {

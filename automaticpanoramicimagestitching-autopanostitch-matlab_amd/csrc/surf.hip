@@ -634,6 +634,28 @@ void surf_uniform(aps_surf_view* views, int nv, int height, int width, int chann
 }
 
 }  // namespace
+
+// aps_internal.h: the selection over one group of int4 candidates, with this translation unit's copies of select_dev.h's kernels
+void select_int4_group(const unsigned long long* keys, const unsigned int* vals, const int4* cand, unsigned int n, unsigned int keep,
+                       unsigned int cells, int4* sel, unsigned int* d_kept) {
+    Ws<unsigned long long> words;
+    Ws<unsigned int> prefix;
+    unsigned int n_words = 0;
+    if (cells > 0) {
+        UniformBudget budget = {};
+        budget.q[0] = keep;
+        select_uniform(keys, nullptr, vals, n, 1u, cells, budget, words, prefix, n_words);
+    } else {
+        select_by_key(keys, vals, n, single_group_cut(n, keep), words, prefix, n_words, 32u);
+    }
+    select_compact_kernel<int4><<<cdiv(n_words, 256), 256, 0, stream()>>>(words, prefix, n_words, cand, n, sel, keep);
+    check_launch("select_compact_kernel");
+    ViewOffsets off = {};
+    for (int v = 1; v <= kGroupViews; ++v) off.off[v] = n;
+    view_kept_kernel<<<1, 64, 0, stream()>>>(words, prefix, off, 1, d_kept);
+    check_launch("view_kept_kernel");
+}
+
 }  // namespace aps
 
 using namespace aps;

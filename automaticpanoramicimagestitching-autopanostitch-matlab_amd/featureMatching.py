@@ -829,7 +829,7 @@ def _surf_params(input):
     p.metric_threshold = float(input.get("MetricThreshold", 1000.0))
     p.n_octaves = int(input.get("NumOctaves", 8))  # getFeaturePoints.m:55
     p.n_scale_levels = int(input.get("NumScaleLevels", 4))
-    p.upright = 0
+    p.upright = int(bool(input.get("Upright", False)))  # extractFeatures' Upright; the strongest and uniform structs nest it
     p.max_features = int(input.get("maxFeatures", 0))
     return p
 
@@ -856,7 +856,10 @@ def surf_extract(input, image, device_out=False, want_aux=False, points_device=F
 
     input.NumUniform with input.UniformGrid (sift_extract's keys; selectUniform) keeps min(N, rows) rows through
     aps_surf_extract_uniform, spread over the grid's cells by water-filling, the largest metric first within a cell; a row's cell is
-    that of its detection sample, before refinement (DESIGN.md "Uniform-N selection")."""
+    that of its detection sample, before refinement (DESIGN.md "Uniform-N selection").
+
+    input.Upright (absent or false by default; extractFeatures' Upright) skips the orientation stage on every entry above: the rows
+    are described along the image axes, angle_deg is 0, and count, validPts, scale and metric are those of the oriented call."""
     img, h, w, c = _image_hwc(image)
     prm, entry, cap = _pick_entry(input, _uniform_keys(input), max(4096, (h * w) // 64), (_surf_params(input), lib.aps_surf_extract),
                                   (lambda n: _surf_strongest_params(input, n), lib.aps_surf_extract_strongest),
@@ -914,6 +917,19 @@ def _kaze_params(input):
     return p
 
 
+def _kaze_select_params(input, kaze, uniform):
+    """aps_kaze_select_params around kaze_extract's params: the selection that NumStrongest or NumUniform (uniform: what
+    _uniform_keys(input) returned) asks for, and Upright."""
+    p = _capi.aps_kaze_select_params()
+    p.kaze = kaze
+    if uniform:
+        p.select, p.n_select, p.grid_rows, p.grid_cols = 2, *uniform
+    elif "NumStrongest" in input:
+        p.select, p.n_select = 1, int(input["NumStrongest"])
+    p.upright = int(bool(input.get("Upright", False)))
+    return p
+
+
 def kaze_extract(input, image, device_out=False, want_aux=False, points_device=False, compact=False, padded=False):
     """aps_kaze_extract with automatic capacity: returns (features, validPts[, aux]); the arguments are surf_extract's.
 
@@ -921,11 +937,27 @@ def kaze_extract(input, image, device_out=False, want_aux=False, points_device=F
     other two are a ValueError), maxFeatures.  Host results are n x 64 unit-norm oriented M-SURF rows.  Resident results
     (device_out=True) are the [:, :64] view of an n x 128 buffer whose columns 64..127 the library zeroed, or with padded=True that
     buffer itself, as surf_extract's.  validPts: n x 2 float64 [x y] 1-based.  aux: n x 4 [scale, angle_deg, metric, level].
-    There is no NumStrongest / NumUniform selection and no group form (DESIGN.md "KAZE contract")."""
+    There is no group form (DESIGN.md "KAZE contract").
+
+    Four more keys, all absent by default, go through aps_kaze_extract_select (DESIGN.md "KAZE selection and Upright"); without
+    any of them the call is aps_kaze_extract.
+    input.NumStrongest (selectStrongest) keeps at most that many rows: those that come first by (metric descending, row index
+    ascending), in one group with no quota per level.  input.NumUniform with input.UniformGrid = (rows, cols) (default (8, 8), each
+    1..32; selectUniform) keeps min(N, rows) rows spread over the grid's cells by water-filling, the largest metric first within a
+    cell; a row's cell is that of its detection pixel, before refinement.  Either way the kept rows are rows of the result without
+    the key, bit for bit and in the same order, and the capacity buffer of a resident result holds N rows.  Both keys together are
+    a ValueError, raised before any library call; a value below 1 or a grid value outside 1..32 is an ApsError (APS_E_ARG).
+    input.Upright (extractFeatures' Upright) skips the orientation: the rows are described along the image axes, angle_deg is 0,
+    and count, validPts, scale, metric and level are those of the oriented call.  It combines with either selection."""
+    uniform = _uniform_keys(input)
     img, h, w, c = _image_hwc(image)
-    prm = _kaze_params(input)
+    prm, entry, cap = _kaze_params(input), lib.aps_kaze_extract, max(4096, (h * w) // 64)
+    if any(k in input for k in ("NumStrongest", "NumUniform", "UniformGrid", "Upright")):
+        prm, entry = _kaze_select_params(input, prm, uniform), lib.aps_kaze_extract_select
+        if prm.select:  # (as _pick_entry: a resident result holds N rows)
+            cap = min(cap, max(prm.n_select, 1))
     width = DIM if device_out else KAZE_DIM  # (resident rows are 128 wide, host rows 64; the leading dimension follows)
-    d, pts, aux = _extract_regrow(1, max(4096, (h * w) // 64), _one_view_call(lib.aps_kaze_extract, prm, img, h, w, c, width),
+    d, pts, aux = _extract_regrow(1, cap, _one_view_call(entry, prm, img, h, w, c, width),
                                   _over_capacity_unless_limited(int(input.get("maxFeatures", 0))), width, np.float32,
                                   device_out, points_device, compact, want_aux)[0]
     if device_out and not padded:

@@ -1222,11 +1222,42 @@ typedef struct aps_kaze_params {
  * count 0, not an error.  Host and device pointers are accepted; the call runs on the calling thread's library stream with that
  * thread's workspace (4 bytes x (5 + 3 levels) planes: 1.36 GB for a 3840 x 2160 view at the defaults) and reads back once, the count.
  * Feature order is canonical: ascending (level, row, col).
- * Not built: the 'sharpedge' and 'edge' diffusivities, 128-D rows, Upright, group (batch) entries, NumStrongest / NumUniform
- * selections and a MATLAB gateway command. */
+ * Not built: the 'sharpedge' and 'edge' diffusivities, 128-D rows, group (batch) entries and a MATLAB gateway command.  Upright and
+ * the NumStrongest / NumUniform selections are aps_kaze_extract_select's, below. */
 int aps_kaze_extract(const uint8_t* img, int height, int width, int channels, int img_layout,
                      const aps_kaze_params* params, float* desc, int desc_layout, int64_t ldd,
                      double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
+
+typedef struct aps_kaze_select_params {
+    aps_kaze_params kaze;      /* what aps_kaze_extract takes: the candidates are its rows */
+    int select;                /* 0 none, 1 strongest-N, 2 uniform-N (aps_fast_orb_params' convention) */
+    int n_select;              /* N (NumStrongest / NumUniform), >= 1 with a selection; not read with select == 0 */
+    int grid_rows;             /* UniformGrid rows, 1..32; read with select == 2 */
+    int grid_cols;             /* UniformGrid columns, 1..32; read with select == 2 */
+    int upright;               /* 0 | 1: extractFeatures' Upright */
+} aps_kaze_select_params;
+
+/* aps_kaze_extract with a selection of its rows and / or upright descriptors (DESIGN.md "KAZE selection and Upright").  The
+ * candidates are the rows aps_kaze_extract returns for the same image and `kaze`, in canonical order; their strength is `metric`
+ * (aux[:, 2]), in one group with no quota per level.
+ *   select == 1  keeps the first min(n_select, candidates) by (metric descending, canonical index ascending): the rule of
+ *                aps_surf_extract_strongest
+ *   select == 2  keeps Q = min(n_select, candidates) rows spread over the grid_rows x grid_cols cells of the image by water-filling
+ *                (aps_uniform_quota), the largest metric first within a cell; a row's cell is aps_uniform_cell of its detection
+ *                pixel, before refinement: the rule of aps_surf_extract_uniform.  A 1 x 1 grid is select == 1's result
+ *   upright == 1 skips the orientation: the descriptor is the oriented one's arithmetic at (cos, sin) = (1.0f, 0.0f) and angle_deg
+ *                is +0.0; count, loc, scale, metric and level are the oriented call's bits
+ * Kept rows come out in canonical order, and every byte of a kept row (with upright == 0) is that row's of the unselected call;
+ * n_select at or above the candidates gives the unselected result.  With select == 0 and upright == 0 the call is aps_kaze_extract.
+ * Outputs, layouts, host / device pointers and the capacity protocol are aps_kaze_extract's, with *count = rows kept: cap >=
+ * min(candidates, n_select) suffices.  kaze.max_features > 0 limits the candidates found, before the selection (APS_E_CAP with the
+ * candidate count), as in aps_surf_extract_strongest.  With a selection the call reads back twice: the candidates, then the rows
+ * the device kept.  No atomics in the selection; the result is the same from run to run.
+ * Errors, all before any device work: every refusal of aps_kaze_extract, and APS_E_ARG for NULL params, select outside 0..2,
+ * n_select < 1 with a selection, a grid value outside 1..32 with select == 2, upright outside 0..1. */
+int aps_kaze_extract_select(const uint8_t* img, int height, int width, int channels, int img_layout,
+                            const aps_kaze_select_params* params, float* desc, int desc_layout, int64_t ldd,
+                            double* loc, int64_t ldl, float* aux, int64_t cap, int64_t* count);
 
 /* ============================================================================================
  * Lens distortion: undistortImage / undistortPoints of the Computer Vision Toolbox ("Lens distortion contract")

@@ -46,3 +46,40 @@ for det, fn in (("KAZE", fm.kaze_extract), ("SURF", fm.surf_extract), ("SIFT", f
         print(line)
     if det == "KAZE":
         print(f"  ({fed_steps} diffusion steps in {NL - 1} cycles; workspace {(5 + 3 * NL) * W * H * 4 / 1e9:.2f} GB of planes)")
+
+# The selection keys and Upright (DESIGN.md "KAZE selection and Upright") against the call without keys, alternated in one process:
+# SERIES rounds, each variant once per round.  Per variant the wall time of a resident call (library stream drained) and the
+# profiled time of the sites that differ, as median (min-max) over the rounds.  The call without keys runs the parent's launches:
+# the only comparison that matters is against that row.
+import statistics  # noqa: E402
+import time  # noqa: E402
+
+VARIANTS = (("no keys", {}), ("NumStrongest=2000", {"NumStrongest": 2000}), ("NumUniform=2000", {"NumUniform": 2000}),
+            ("Upright", {"Upright": True}), ("NumUniform=2000 + Upright", {"NumUniform": 2000, "Upright": True}))
+SITES = ("kaze_keypoint", "kaze_select", "kaze_detect")
+SERIES = 7
+for _, keys in VARIANTS:
+    fm.kaze_extract(dict(keys, detector="KAZE"), img, device_out=True)  # warm-up
+wall = {name: [] for name, _ in VARIANTS}
+site = {name: {s: [] for s in SITES} for name, _ in VARIANTS}
+rows = {}
+for _ in range(SERIES):
+    for name, keys in VARIANTS:
+        inp = dict(keys, detector="KAZE")
+        capi.check(capi.lib.aps_synchronize())
+        t0 = time.perf_counter()
+        d, _ = fm.kaze_extract(inp, img, device_out=True)   # (drains the library's stream before it returns)
+        wall[name].append((time.perf_counter() - t0) * 1e3)
+        rows[name] = int(d.shape[0])
+        capi.profile_enable(True)
+        capi.profile_reset()
+        fm.kaze_extract(inp, img, device_out=True)
+        capi.check(capi.lib.aps_synchronize())
+        prof = capi.profile_all()
+        capi.profile_enable(False)
+        for s in SITES:
+            site[name][s].append(prof.get(s, (0.0, 0))[0])
+fmt = lambda v: f"{statistics.median(v):7.3f} ({min(v):.3f}-{max(v):.3f})"  # noqa: E731
+print(f"KAZE keys, {SERIES} alternating rounds, ms as median (min-max):")
+for name, _ in VARIANTS:
+    print(f"  {name:26s} {rows[name]:6d} rows  wall {fmt(wall[name])}  " + "  ".join(f"{s} {fmt(site[name][s])}" for s in SITES))
